@@ -3,7 +3,8 @@
 synthetic Gaussians, one view per GPU (weak scaling by independent views; the only collective is the
 4-float loss all-reduce, RCCL over xGMI).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C4|C3|C2] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C4|C3|C2] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--headline-only]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -17,7 +18,12 @@ MAX over ranks:  (A) forward-only render under no_grad  -> `value` (Mpixels/s, w
                  (B) train step = render + L1 + backward + densification stats (+ loss all-reduce)
                      -> `ms_per_step`.
 Rank r renders view r of the eight C5 orbit views in them (one view per GPU: weak scaling; N = 8 is SURVEY §8e's partition).
-Further regions of the same protocol, reported as extra fields of the same line (never as `value`):
+A plain run does only that: set-up, the W warm-ups, the untimed pre-warm steps, the two headline regions, and the line.
+--dump-outputs DIR then writes what the last step of each headline region returned (rank 0's view) as DIR/<name>.npy:
+the two images in full, the loss, and radii / parameter gradients / densification statistics at a fixed seeded sample
+of the Gaussians (under 64 MB in all).  The inputs depend on the arguments only, so two builds can be compared file by file.
+--full adds everything else, as further regions of the same protocol reported as extra fields of the same line (never as
+`value`), plus the stage-timer pass and roofline objects, the one-rank RCCL probe and the CPU baseline:
   cold_*                 the first K steps after the W warm-ups, before the untimed pre-warm steps (GPU clocks still ramping);
   *_readback_every_frame the same steps with the count read-back in every frame (GSR_SYNC_FREE=0, upstream's behaviour);
   train_step_ms_l1_dssim the train step with the reference's real loss, 0.8 L1 + 0.2 (1 - SSIM) (train.py:99-101);
@@ -356,6 +362,39 @@ def rccl_single_rank_probe(timeout=120):
             "returncode": r.returncode}
 
 
+DUMP_SAMPLE = 32768          # Gaussians whose per-Gaussian outputs --dump-outputs writes
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, fwd_image, train_pkg, loss, model):
+    """--dump-outputs: what the headline regions handed their caller in their last step, as float32 DIR/<name>.npy.
+    The two images in full; the per-Gaussian arrays (radii, visibility, every parameter gradient, d loss / d means2D and
+    the densification accumulators) at DUMP_SAMPLE indices: randperm(P) of a generator seeded with 0, sorted (at 6 M
+    Gaussians the full arrays would be 1.6 GB).  Returns the bytes written."""
+    import numpy as np
+    P = int(model._xyz.shape[0])
+    idx = torch.randperm(P, generator=torch.Generator().manual_seed(0))[:min(DUMP_SAMPLE, P)].sort().values
+    idx = idx.to(model._xyz.device)
+    per_gaussian = {
+        "radii": train_pkg["radii"], "visibility_filter": train_pkg["visibility_filter"],
+        "grad_xyz": model._xyz.grad, "grad_features_dc": model._features_dc.grad,
+        "grad_features_rest": model._features_rest.grad, "grad_opacity": model._opacity.grad,
+        "grad_scaling": model._scaling.grad, "grad_rotation": model._rotation.grad,
+        "grad_means2D": train_pkg["viewspace_points"].grad,
+        "xyz_gradient_accum": model.xyz_gradient_accum, "denom": model.denom, "max_radii2D": model.max_radii2D,
+    }
+    arrays = {"render_fwd": fwd_image, "render": train_pkg["render"], "loss": loss.reshape(1)}
+    arrays.update({k: v[idx] for k, v in per_gaussian.items()})
+    host = {k: np.ascontiguousarray(v.detach().to(torch.float32).cpu().numpy()) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -363,7 +402,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="C4", choices=["C2", "C3", "C4"])
     ap.add_argument("--gaussians", type=int, default=None, help="override P (debug only; marks the line invalid)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the extra regions, stage timers + roofline objects, RCCL probe, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last headline steps' outputs (rank 0) as DIR/<name>.npy, float32, under 64 MB")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--unfused", action="store_true",
                     help="feed the operator through the reference getters (cat/exp/normalize/sigmoid in torch)")
     ap.add_argument("--fuse-stats", action="store_true",
@@ -371,16 +414,17 @@ def main():
     ap.add_argument("--no-prewarm", action="store_true",
                     help="skip the extra untimed steps in front of each headline region (GPU clock ramp)")
     ap.add_argument("--headline-only", action="store_true",
-                    help="only the two headline regions + the stage-timer pass (what the rocprofv3 passes run: every launch "
-                         "of a kernel then belongs to the headline view)")
+                    help="with --full: only the two headline regions + the stage-timer pass (what the rocprofv3 passes run: "
+                         "every launch of a kernel then belongs to the headline view)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--no-rccl-probe", action="store_true", help="skip the one-rank RCCL communicator probe (N = 1 only)")
     args = ap.parse_args()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # the plain command form: this process becomes the launcher of N rank processes (it has not touched the GPU)
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))
+    full = args.full
     rccl_probe = None
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.headline_only and not args.no_rccl_probe:
+    if full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.headline_only and not args.no_rccl_probe:
         # a child process, started BEFORE this process creates its HIP context (a process that holds the GPU starts nothing)
         rccl_probe = rccl_single_rank_probe()
     # stdout carries exactly one line, the JSON result: native libraries (the RCCL / gloo banners) write to fd 1 too,
@@ -488,27 +532,35 @@ def main():
             all_reduce(loss_vec, dist.ReduceOp.SUM)
         return pkg, loss
 
-    # the eight C5 orbit views partitioned {r, r + N, ...}
-    from mvs_gaussian_splatting_amd.synthetic import orbit_camera
-    my_views = c5_views_of_rank(rank, world)
-    c5_cams = [orbit_camera(v, 8, W, H, cfg.fx, cfg.fy, device=dev) for v in my_views]
-    c5_targets = [torch.rand(3, H, W, generator=torch.Generator().manual_seed(1 + v)).to(dev) for v in my_views]
+    # the regions beyond the headline (--full; --headline-only keeps only the stage-timer pass and the roofline objects)
+    extras = full and not args.headline_only
+    if extras:
+        # the eight C5 orbit views partitioned {r, r + N, ...}
+        from mvs_gaussian_splatting_amd.synthetic import orbit_camera
+        my_views = c5_views_of_rank(rank, world)
+        c5_cams = [orbit_camera(v, 8, W, H, cfg.fx, cfg.fy, device=dev) for v in my_views]
+        c5_targets = [torch.rand(3, H, W, generator=torch.Generator().manual_seed(1 + v)).to(dev) for v in my_views]
 
+    visible = None          # visible Gaussians of this view: from the last warm-up (--warmup 0: the --full count step)
     for _ in range(args.warmup):
         fwd_step()
         pkg, loss = train_step()
-    radii = pkg["radii"]
-    visible = int((radii > 0).sum())
+    if args.warmup > 0:
+        visible = int((pkg["radii"] > 0).sum())
 
-    def timed(fn, k):
+    def timed(fn, k, keep=None):
         """-> (wall seconds of the K steps, MAX over ranks; per-step device ms of this rank from events recorded on
-        the stream the kernels run on -- the operator launches on torch's current stream)."""
+        the stream the kernels run on -- the operator launches on torch's current stream).  `keep` (a list) receives
+        what the last step returned; every other step's result is dropped at once, as without it."""
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(k + 1)]
         barrier()
         t0 = time.perf_counter()
         evs[0].record()
         for i in range(k):
-            fn()
+            if keep is not None and i == k - 1:
+                keep.append(fn())
+            else:
+                fn()
             evs[i + 1].record()
         barrier()
         dt = time.perf_counter() - t0
@@ -555,21 +607,40 @@ def main():
     # a frame in 0.13 ms and is never what the GPU waits for).  A sustained run is what the metric describes, so each
     # headline region is preceded by a fixed number of further UNTIMED steps of its own kind; they are reported in the
     # line, and the first K of them are timed as the COLD region and reported beside the headline.
+    # (the cold region is timed with --full only: a plain run takes the same pre-warm steps untimed)
     prewarm = {"fwd": 0 if args.no_prewarm else 60, "train": 0 if args.no_prewarm else 25}
     cold = {}
-    if not args.no_prewarm:
+    dump = args.dump_outputs is not None and rank == 0
+    kept_fwd, kept_train = ([], []) if dump else (None, None)
+    if full and not args.no_prewarm:
         t_c, _ = timed(fwd_step, K)
         cold["cold_fwd_ms"] = round(t_c / K * 1e3, 3)
         for _ in range(max(0, prewarm["fwd"] - K)):
             fwd_step()
+    else:
+        for _ in range(prewarm["fwd"]):
+            fwd_step()
     # Headline regions: EXACTLY K steps each, nothing but the steps between the barriers.
-    t_fwd, (fwd_steps, fwd_order) = timed(fwd_step, K)
-    if not args.no_prewarm:
+    t_fwd, (fwd_steps, fwd_order) = timed(fwd_step, K, keep=kept_fwd)
+    if dump:      # the image to the host, the rest of the frame freed before the train region
+        fwd_image = kept_fwd.pop()["render"].cpu()
+    if full and not args.no_prewarm:
         t_c, _ = timed(train_step, K)
         cold["cold_train_ms"] = round(t_c / K * 1e3, 3)
         for _ in range(max(0, prewarm["train"] - K)):
             train_step()
-    t_train, (train_steps, train_order) = timed(train_step, K)
+    else:
+        for _ in range(prewarm["train"]):
+            train_step()
+    t_train, (train_steps, train_order) = timed(train_step, K, keep=kept_train)
+    if dump:
+        # before anything else runs: the --full regions below take further steps on the same model
+        t_d = time.perf_counter()
+        pkg_last, loss_last = kept_train.pop()
+        n_bytes = dump_outputs(args.dump_outputs, fwd_image, pkg_last, loss_last, model)
+        del pkg_last, loss_last, fwd_image
+        print(f"[bench] --dump-outputs: {n_bytes / 1e6:.1f} MB to {args.dump_outputs} in {time.perf_counter() - t_d:.1f} s",
+              file=sys.stderr, flush=True)
     # every rank's own device time of the two headline regions (sum of its per-step event intervals), gathered
     per_rank = torch.zeros(2 * world, dtype=torch.float64, device=dev)
     per_rank[2 * rank] = sum(fwd_order) / K
@@ -580,15 +651,15 @@ def main():
     # Per-kernel times for the roofline objects: the same K + K steps once more with the library's stage timers on (a HIP
     # event pair around every stage, on the stream the kernels run on).  Kept out of the headline regions because the
     # 14-16 event records per frame cost the frame 5-10 % (they serialise the stream: `profiled_*_ms` below shows it).
-    prof = _lib.StageProfile()
-    with prof:
-        t_fwd_prof, _ = timed(fwd_step, K)
-        stages_fwd = prof.collect()
-        t_train_prof, _ = timed(train_step, K)
-        stages_train = prof.collect()
-    prof.close()
+    if full:
+        prof = _lib.StageProfile()
+        with prof:
+            t_fwd_prof, _ = timed(fwd_step, K)
+            stages_fwd = prof.collect()
+            t_train_prof, _ = timed(train_step, K)
+            stages_train = prof.collect()
+        prof.close()
     # the reference's real training loss (train.py:99-101): same step, fused L1 + D-SSIM kernel pair instead of L1
-    extras = not args.headline_only
     t_dssim = float("nan")
     if extras:
         for _ in range(3):
@@ -644,17 +715,22 @@ def main():
         pipe.fuse_activations = True
         pipe.fuse_densify_stats = fuse_stats_was
 
-    # instances of this rank's view: read back from the stage the operator itself ran
+    # instances of this rank's view: read back from the stage the operator itself ran (--full: one more train step)
     from mvs_gaussian_splatting_amd.rasterizer import frame_counts
-    pkg, _ = train_step()
-    R = int(frame_counts(pkg["render"])[0]) if pkg["render"].grad_fn is not None else 0
+    R, per_rank_R = None, None
+    if full:
+        pkg, _ = train_step()
+        R = int(frame_counts(pkg["render"])[0]) if pkg["render"].grad_fn is not None else 0
+        if visible is None:
+            visible = int((pkg["radii"] > 0).sum())
 
-    # every rank's instance count: the views differ (8.2 M .. 8.6 M instances at C4), and the job is as slow as its slowest rank
-    per_rank_R = torch.zeros(world, dtype=torch.float64, device=dev)
-    per_rank_R[rank] = float(R)
-    if world > 1:
-        all_reduce(per_rank_R, dist.ReduceOp.SUM)
-    per_rank_R = [int(v) for v in per_rank_R.cpu().tolist()]
+        # every rank's instance count: the views differ (8.2 M .. 8.6 M instances at C4), and the job is as slow as its
+        # slowest rank
+        per_rank_R = torch.zeros(world, dtype=torch.float64, device=dev)
+        per_rank_R[rank] = float(R)
+        if world > 1:
+            all_reduce(per_rank_R, dist.ReduceOp.SUM)
+        per_rank_R = [int(v) for v in per_rank_R.cpu().tolist()]
     # A cloud shaped like a TRAINED scene (synthetic.make_heavy_tail_model: footprints with a heavy tail, dense blobs, depths
     # over seven binades -- R / P = 4.6 against the headline cloud's 1.4, per-tile lists up to 31 k long, every frame needs
     # the depth sort's fourth pass): the same P, camera, image size and protocol, reported as heavy_tail_* and never as
@@ -704,7 +780,8 @@ def main():
         t_lt, _ = timed(train_step, K)
         layout = {"morton_layout_fwd_ms": round(t_lf / K * 1e3, 3), "morton_layout_train_ms": round(t_lt / K * 1e3, 3),
                   "morton_layout_mpixels_per_s": round(world * W * H / (t_lf / K) / 1e6, 1)}
-    if rank == 0:
+    full_fields = {}
+    if rank == 0 and full:
         tiles = ((W + 15) // 16) * ((H + 15) // 16)
         tb = max(1, (tiles - 1).bit_length())
         passes = (32 + tb + 7) // 8
@@ -829,29 +906,39 @@ def main():
 
         copy_GBs = round(copy_ceiling(), 1)
         roof = roofline_of(dominant)
+        full_fields = {
+            "train_step_ms_l1_dssim": round(t_dssim / K * 1e3, 3) if extras else None,
+            "per_rank_instances": per_rank_R,
+            "c5_eight_views": c5,
+            "profiled_fwd_ms": round(t_fwd_prof / K * 1e3, 3), "profiled_train_ms": round(t_train_prof / K * 1e3, 3),
+            "hbm_copy_measured_GBs": copy_GBs,
+            "hbm_elementwise_kernel_GBs": round(getattr(copy_ceiling, "kernel_rate", 0.0), 1),
+            "roofline": roof,
+            "roofline_step": roofline_of(dominant_step),
+            # the two compositing kernels north_star singles out (VALU-issue-bound: DESIGN.md section 5)
+            "roofline_render_fwd": roofline_of("render_fwd") if "render_fwd" in table else None,
+            "roofline_render_bwd": roofline_of("render_bwd") if "render_bwd" in table else None,
+            "roofline_by_kernel": table,
+            "fwd_algorithmic_GB": round(sum(alg[n] for n in fwd_names) / 1e9, 3),
+        }
+    if rank == 0:
         fwd_ms = t_fwd / K * 1e3
         train_ms = t_train / K * 1e3
         line = {
             "metric": "Mpixels/s fwd + train-step ms @1080p, 6M Gaussians, 1->8 MI355X",
             "value": round(world * W * H / (t_fwd / K) / 1e6, 2), "unit": "Mpixels/s",
-            "n_gpus": world, "steps": K, "warmup": args.warmup,
+            "n_gpus": world, "steps": K, "warmup": args.warmup, "full": full,
             "extra_untimed_warmup_steps": dict(prewarm, why="GPU clock ramp after idle: see profiles/r03/clock_ramp.txt; "
-                                                            "the first K of them are the cold_* region; --no-prewarm makes "
-                                                            "the cold region the headline"),
+                                                            "with --full the first K of them are the cold_* region; "
+                                                            "--no-prewarm makes the cold region the headline"),
             "ms_per_step": round(train_ms, 3), "fwd_ms_per_step": round(fwd_ms, 3),
             "train_mpixels_per_s": round(world * W * H / (t_train / K) / 1e6, 2),
             "fwd_fps": round(1e3 / fwd_ms, 2),
-            "train_step_ms_l1_dssim": round(t_dssim / K * 1e3, 3) if extras else None,
             "per_rank_fwd_ms": [round(per_rank[2 * r], 4) for r in range(world)],
             "per_rank_train_ms": [round(per_rank[2 * r + 1], 4) for r in range(world)],
-            "per_rank_instances": per_rank_R,
-            "c5_eight_views": c5,
-            "profiled_fwd_ms": round(t_fwd_prof / K * 1e3, 3), "profiled_train_ms": round(t_train_prof / K * 1e3, 3),
             "fwd_step_ms_in_order": [round(v, 3) for v in fwd_order], "train_step_ms_in_order": [round(v, 3) for v in train_order],
             "fwd_step_ms_p10_p50_p90": [pct(fwd_steps, 0.1), pct(fwd_steps, 0.5), pct(fwd_steps, 0.9)],
             "train_step_ms_p10_p50_p90": [pct(train_steps, 0.1), pct(train_steps, 0.5), pct(train_steps, 0.9)],
-            "hbm_copy_measured_GBs": copy_GBs,
-            "hbm_elementwise_kernel_GBs": round(getattr(copy_ceiling, "kernel_rate", 0.0), 1),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": f"{args.config}: {P} Gaussians, SH degree {cfg.sh_degree}, {W}x{H}, one view per GPU "
                                    f"(rank r renders orbit view r of 8); value = forward-only steps, ms_per_step = "
@@ -872,14 +959,8 @@ def main():
                        # up (the gloo numbers are diagnostics, not the north-star collective)
                        # ... and a rehearsal with several ranks on ONE card (GSR_BENCH_SHARE_GPU=1) is never a multi-GPU result
                        "valid": args.gaussians is None and not rccl_failed and not (share and world > 1)},
-            "roofline": roof,
-            "roofline_step": roofline_of(dominant_step),
-            # the two compositing kernels north_star singles out (VALU-issue-bound: DESIGN.md section 5)
-            "roofline_render_fwd": roofline_of("render_fwd") if "render_fwd" in table else None,
-            "roofline_render_bwd": roofline_of("render_bwd") if "render_bwd" in table else None,
-            "roofline_by_kernel": table,
-            "fwd_algorithmic_GB": round(sum(alg[n] for n in fwd_names) / 1e9, 3),
         }
+        line.update(full_fields)
         line.update(cold)
         line.update(readback)
         if unfused:
@@ -890,7 +971,7 @@ def main():
             line.update(heavy)
         if rccl_probe is not None:
             line["rccl_single_rank_probe"] = rccl_probe
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(cfg, args.seed)
             except Exception as ex:  # noqa: BLE001

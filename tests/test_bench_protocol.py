@@ -228,3 +228,77 @@ def test_bench_refuses_a_world_size_that_contradicts_gpus(monkeypatch):
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--no-rccl-probe"], env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
     assert r.returncode != 0 and b"WORLD_SIZE=2 but --gpus 1" in r.stderr
+
+
+# ---- --dump-outputs / --full ----------------------------------------------------------------------------------------------
+def _dump_inputs(P, H, W):
+    """A stand-in for the last train step of a headline region: a model whose gradients and accumulators encode the
+    Gaussian's index, so the rows a dump holds say which Gaussians were sampled."""
+    import types
+    import torch
+    ix = torch.arange(P, dtype=torch.float32)
+    model = types.SimpleNamespace()
+    for name, shape in (("_xyz", (P, 3)), ("_features_dc", (P, 1, 3)), ("_features_rest", (P, 15, 3)),
+                        ("_opacity", (P, 1)), ("_scaling", (P, 3)), ("_rotation", (P, 4))):
+        t = torch.zeros(shape)
+        t.grad = ix.reshape((P,) + (1,) * (len(shape) - 1)).expand(shape).clone()
+        setattr(model, name, t)
+    model.xyz_gradient_accum, model.denom, model.max_radii2D = ix[:, None].clone(), ix[:, None].clone(), ix.clone()
+    means2d = torch.zeros(P, 3)
+    means2d.grad = ix[:, None].expand(P, 3).clone()
+    radii = (torch.arange(P) % 7).to(torch.int32)
+    pkg = {"render": torch.rand(3, H, W, generator=torch.Generator().manual_seed(1)), "viewspace_points": means2d,
+           "visibility_filter": radii > 0, "radii": radii}
+    return torch.rand(3, H, W, generator=torch.Generator().manual_seed(2)), pkg, torch.tensor(0.25, dtype=torch.float64), model
+
+
+def test_dump_outputs_writes_float32_arrays_at_a_fixed_sample(tmp_path):
+    """--dump-outputs: every array float32, the images whole, the per-Gaussian arrays at the same DUMP_SAMPLE sorted indices
+    in every run, under the 64 MB limit at the benchmark's own 1080p image size."""
+    import numpy as np
+    bench = _bench_module()
+    P, H, W = 3 * bench.DUMP_SAMPLE + 5, 1080, 1920
+    fwd_image, pkg, loss, model = _dump_inputs(P, H, W)
+    n1 = bench.dump_outputs(str(tmp_path / "a"), fwd_image, pkg, loss, model)
+    n2 = bench.dump_outputs(str(tmp_path / "b"), fwd_image, pkg, loss, model)
+    assert n1 == n2 <= 64 * 2 ** 20
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(k + ".npy" for k in ("render_fwd", "render", "loss", "radii", "visibility_filter", "grad_xyz",
+                                                "grad_features_dc", "grad_features_rest", "grad_opacity", "grad_scaling",
+                                                "grad_rotation", "grad_means2D", "xyz_gradient_accum", "denom",
+                                                "max_radii2D"))
+    arrays = {n: np.load(tmp_path / "a" / n) for n in names}
+    assert sum(a.nbytes for a in arrays.values()) == n1
+    for n, a in arrays.items():
+        assert a.dtype == np.float32, n
+        assert np.array_equal(a, np.load(tmp_path / "b" / n)), n
+    assert np.array_equal(arrays["render_fwd.npy"], fwd_image.numpy()) and np.array_equal(arrays["render.npy"], pkg["render"].numpy())
+    assert arrays["loss.npy"].tolist() == [0.25]
+    idx = arrays["max_radii2D.npy"].astype(np.int64)
+    assert idx.shape == (bench.DUMP_SAMPLE,) and np.all(np.diff(idx) > 0) and idx[-1] < P
+    assert idx.max() > 2 * bench.DUMP_SAMPLE                      # a sample of the whole cloud, not its first rows
+    for n in ("grad_xyz.npy", "grad_features_rest.npy", "grad_means2D.npy", "denom.npy"):
+        assert np.array_equal(arrays[n].reshape(len(idx), -1)[:, 0], idx), n
+    assert np.array_equal(arrays["radii.npy"], (idx % 7).astype(np.float32))
+    assert np.array_equal(arrays["visibility_filter.npy"], (idx % 7 > 0).astype(np.float32))
+
+
+def test_dump_outputs_keeps_every_gaussian_of_a_small_cloud(tmp_path):
+    import numpy as np
+    bench = _bench_module()
+    fwd_image, pkg, loss, model = _dump_inputs(100, 16, 24)
+    bench.dump_outputs(str(tmp_path), fwd_image, pkg, loss, model)
+    assert np.array_equal(np.load(tmp_path / "max_radii2D.npy"), np.arange(100, dtype=np.float32))
+
+
+def test_bench_offers_full_and_dump_outputs():
+    """The command line the benchmark is driven with: --full (the regions beyond the headline) and --dump-outputs DIR."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, timeout=120)
+    assert r.returncode == 0
+    out = r.stdout.decode()
+    assert "--full" in out and "--dump-outputs" in out

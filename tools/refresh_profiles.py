@@ -5,9 +5,9 @@ profiles/traffic.json (stamped with the kernel sources the passes were taken on)
 
 The capture is produced on the GPU box by tools/capture_profiles.sh (cd /tmp; export TMPDIR=/tmp first; --pmc passes are
 separate runs, never combined with tracing):
-  python bench.py                                                                  > <cap>/bench_c4_n1.json
-  rocprofv3 --kernel-trace --stats --output-format csv -d <cap>/stats -- python bench.py --no-cpu-baseline
-  rocprofv3 --pmc FETCH_SIZE ... -d <cap>/fetch -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline
+  python bench.py --full                                                           > <cap>/bench_c4_n1.json
+  rocprofv3 --kernel-trace --stats --output-format csv -d <cap>/stats -- python bench.py --full --no-cpu-baseline
+  rocprofv3 --pmc FETCH_SIZE ... -d <cap>/fetch -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
   rocprofv3 --pmc WRITE_SIZE ... -d <cap>/write -- ...
   rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU \\
             SQ_WAIT_INST_ANY ... -d <cap>/sq -- ...
@@ -41,7 +41,7 @@ for d, name in (("fetch", "FETCH_SIZE"), ("write", "WRITE_SIZE"), ("sq", "SQ"), 
         print("no capture for", d)
 rows = list(csv.DictReader(open(ks)))
 with open(os.path.join(dst, "kernel_stats_summary.txt"), "w") as f:
-    f.write(f"# rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --no-cpu-baseline   (C4: 6M Gaussians, "
+    f.write(f"# rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --full --no-cpu-baseline   (C4: 6M Gaussians, "
             f"1080p, 1x MI355X; {label})\n# kernel | calls | avg us | % of GPU time\n")
     for r in rows[:30]:
         f.write(f"{r['Name'][:100]} | {r['Calls']} | {float(r['AverageNs']) / 1e3:.1f} | {float(r['Percentage']):.2f}\n")
@@ -53,7 +53,7 @@ for name in ("SQ", "SQ2"):
             agg[r["Kernel_Name"].split("(")[0].replace("void ", "")][r["Counter_Name"]].append(float(r["Counter_Value"]))
 stats = {r["Name"].split("(")[0].replace("void ", ""): float(r["AverageNs"]) for r in rows}
 with open(os.path.join(dst, "pmc_SQ_render_summary.txt"), "w") as f:
-    f.write("# rocprofv3 --pmc <SQ counters, two passes> -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline; per-launch means\n"
+    f.write("# rocprofv3 --pmc <SQ counters, two passes> -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline; per-launch means\n"
             "# issue utilisations at the rates measured by tools/ubench/valu_rate.hip (profiles/r02/valu_rate.txt):\n"
             "#   valu  = SQ_INSTS_VALU x 2 cycles / (1024 SIMDs x 2.4 GHz x t)   (full-rate floor; v_cmp/v_cndmask/v_min/v_max 4.7, v_exp/v_rcp 8.3)\n"
             "#   salu  = SQ_INSTS_SALU x 4 cycles / (1024 SIMDs x 2.4 GHz x t)\n"
@@ -107,7 +107,7 @@ if os.path.exists(pg):
             clk[names[base]].append(float(r["Counter_Value"]) / 8.0 / dt)      # cycles per ns = GHz
 with open(os.path.join(dst, "pmc_valu_mix_summary.txt"), "w") as f:
     f.write("# rocprofv3 --pmc SQ_INSTS_VALU + its ADD/MUL/FMA/TRANS/INT32/INT64/CVT sub-counters (one pass) and --pmc "
-            "GRBM_GUI_ACTIVE (its own pass) -- python bench.py --headline-only; per-launch means of the wave-level counts; "
+            "GRBM_GUI_ACTIVE (its own pass) -- python bench.py --full --headline-only; per-launch means of the wave-level counts; "
             "clock = GRBM_GUI_ACTIVE / 8 XCDs / dispatch duration (median over the launches; reads high on dispatches "
             "shorter than ~0.3 ms per the guide)\n")
     for stage in names.values():
