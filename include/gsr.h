@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 13
+#define GSR_ABI_VERSION 14
 
 enum {
   GSR_OK = 0,
@@ -320,6 +320,65 @@ int gsr_densify_gather_rows(int32_t P, int32_t row_floats, const float* src, con
 int gsr_densify_split_children(int32_t P, const float* xyz, const float* scaling_raw, const float* rotation_raw,
                                const float* noise, const void* workspace, const uint32_t counts[4], float* dst_xyz,
                                float* dst_scaling, void* stream);
+
+/* The fork's grow / learned-split branch of render() (gaussian_renderer/__init__.py:91-253), ABI v14.  Every frame the
+ * branch runs, G "virtual" Gaussians are appended after the P of the model (row P + j has source row src[j], in row
+ * order), the extended raw-parameter arrays feed the rasterizer unchanged, and the gradients of the virtual rows are
+ * folded back onto their sources.  mode: GSR_GROW_DIR or GSR_GROW_CONTINUOUS (grow mode, :94-119, optionally with
+ * GSR_GROW_DISTANCE), else GSR_SPLIT_DISTANCE and / or GSR_SPLIT_SCALE (learned split, :186-253).
+ *   gsr_grow_plan: g = xyz_gradient_accum / denom (NaN -> 0); grow mode selects |g| >= grad_threshold, split mode
+ *     |g| >= grad_threshold & max(exp(scaling_raw)) > percent_dense_extent.  Writes vidx[P] (virtual row or -1),
+ *     src[P] (first G entries used) and selected[P] (0 / 1), synchronises the stream and returns counts_host =
+ *     {G, selected rows whose max scale exceeds percent_dense_extent}.
+ *   gsr_grow_expand: out arrays have P + G rows: bit copies, then the grown / split positions and split scales
+ *     (raw - log(k)).  noise [G,3]: the standard-normal draws of torch.normal(0, stds) when GSR_SPLIT_DISTANCE is off.
+ *   gsr_grow_fold: GsrGrowGrads.in[k] are the [P+G]-row gradients of (xyz, means2D, f_dc, f_rest, opacity, scaling,
+ *     rotation), out[k] the [P]-row gradients of the same inputs; d_* the dense [P, ...] gradients of the learned
+ *     tensors of the mode (NULL otherwise), zeroed by the caller: only the selected rows are written. */
+enum {
+  GSR_GROW_DIR = 1,
+  GSR_GROW_CONTINUOUS = 2,
+  GSR_GROW_DISTANCE = 4,
+  GSR_SPLIT_DISTANCE = 8,
+  GSR_SPLIT_SCALE = 16
+};
+
+typedef struct GsrGrow {
+  int32_t P, G, mode, num_dirs, n_rest;        /* n_rest: floats per row of f_rest (45 or 0) */
+  const float* xyz;                            /* device [P,3] raw model tensors */
+  const float* f_dc;                           /* [P,1,3] */
+  const float* f_rest;                         /* [P,15,3] or NULL */
+  const float* opacity;                        /* [P,1] raw */
+  const float* scaling;                        /* [P,3] raw */
+  const float* rotation;                       /* [P,4] raw */
+  const float* dirs_prob;                      /* [P,num_dirs] logits (GSR_GROW_DIR) */
+  const float* dirs;                           /* [num_dirs,3] (GSR_GROW_DIR) */
+  const float* conti_dirs;                     /* [P,3] (GSR_GROW_CONTINUOUS) */
+  const float* grow_dist;                      /* [P,1] raw (GSR_GROW_DISTANCE) */
+  const float* split_distance;                 /* [P,3] raw (GSR_SPLIT_DISTANCE) */
+  const float* split_scale;                    /* [P,1] raw (GSR_SPLIT_SCALE) */
+  const float* noise;                          /* [G,3] (split without GSR_SPLIT_DISTANCE) */
+  const int32_t* vidx;                         /* [P] from gsr_grow_plan */
+  const int32_t* src;                          /* [G] from gsr_grow_plan */
+} GsrGrow;
+
+typedef struct GsrGrowGrads {
+  const float* in[7];
+  float* out[7];
+  float* d_dirs_prob;
+  float* d_conti_dirs;
+  float* d_grow_dist;
+  float* d_split_distance;
+  float* d_split_scale;
+} GsrGrowGrads;
+
+size_t gsr_grow_workspace_bytes(int32_t P);
+int gsr_grow_plan(int32_t P, const float* xyz_gradient_accum, const float* denom, const float* scaling_raw,
+                  float grad_threshold, float percent_dense_extent, int32_t mode, void* workspace, size_t workspace_bytes,
+                  int32_t* vidx, int32_t* src, uint8_t* selected, uint32_t counts_host[2], void* stream);
+int gsr_grow_expand(const GsrGrow* g, float* xyz_out, float* f_dc_out, float* f_rest_out, float* opacity_out,
+                    float* scaling_out, float* rotation_out, void* stream);
+int gsr_grow_fold(const GsrGrow* g, const GsrGrowGrads* grads, void* stream);
 
 #ifdef __cplusplus
 }

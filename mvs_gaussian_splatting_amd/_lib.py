@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # instead of copying it over the in-tree library
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 
 class GsrParams(C.Structure):
@@ -41,6 +41,19 @@ class GsrGrads(C.Structure):
         ("stats_xyz_gradient_accum", C.c_void_p), ("stats_denom", C.c_void_p), ("stats_max_radii2D", C.c_void_p),
     ]
 
+
+class GsrGrow(C.Structure):
+    _fields_ = [("P", C.c_int32), ("G", C.c_int32), ("mode", C.c_int32), ("num_dirs", C.c_int32), ("n_rest", C.c_int32)] + [
+        (n, C.c_void_p) for n in ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation", "dirs_prob", "dirs",
+                                  "conti_dirs", "grow_dist", "split_distance", "split_scale", "noise", "vidx", "src")]
+
+
+class GsrGrowGrads(C.Structure):
+    _fields_ = [("in_", C.c_void_p * 7), ("out", C.c_void_p * 7)] + [
+        (n, C.c_void_p) for n in ("d_dirs_prob", "d_conti_dirs", "d_grow_dist", "d_split_distance", "d_split_scale")]
+
+
+GROW_DIR, GROW_CONTINUOUS, GROW_DISTANCE, SPLIT_DISTANCE, SPLIT_SCALE = 1, 2, 4, 8, 16
 ACT_SCALE_EXP, ACT_ROT_NORMALIZE, ACT_OPACITY_SIGMOID = 1, 2, 4
 BINNING_TWO_LEVEL, BINNING_KEYS64, BINNING_TWO_LEVEL_CULLED = 0, 1, 2
 DSSIM_ONE_MINUS_MEAN, DSSIM_CLAMPED_HALF = 0, 1
@@ -100,6 +113,11 @@ SYMBOLS = {
                                           C.c_void_p, C.c_void_p]),
     "gsr_densify_split_children": (C.c_int, [C.c_int32] + [C.c_void_p] * 5 + [C.POINTER(C.c_uint32), C.c_void_p,
                                              C.c_void_p, C.c_void_p]),
+    "gsr_grow_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "gsr_grow_plan": (C.c_int, [C.c_int32] + [C.c_void_p] * 3 + [C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_size_t]
+                      + [C.c_void_p] * 3 + [C.POINTER(C.c_uint32), C.c_void_p]),
+    "gsr_grow_expand": (C.c_int, [C.POINTER(GsrGrow)] + [C.c_void_p] * 7),
+    "gsr_grow_fold": (C.c_int, [C.POINTER(GsrGrow), C.POINTER(GsrGrowGrads), C.c_void_p]),
     "gsr_profile_create": (C.c_int, [C.POINTER(C.c_void_p)]),
     "gsr_profile_destroy": (C.c_int, [C.c_void_p]),
     "gsr_profile_collect": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),

@@ -113,6 +113,16 @@ void launch_splat2d_bwd(int N, int K, int H, int W, const float* sx, const float
                         float* d_colours, hipStream_t s);
 
 // densify.hip.  counts = {kept originals, kept clones, kept children per copy, split-selected}
+struct GrowLayout {
+  size_t flags, block_counts, block_offs, totals, bytes;
+  int nblocks;
+  explicit GrowLayout(int P);
+};
+void launch_grow_plan(int P, const float* accum, const float* denom, const float* scaling, float thr, float pde,
+                      int split_mode, void* ws, int32_t* vidx, int32_t* src, uint8_t* selected, hipStream_t s);
+void launch_grow_expand(const GsrGrow& g, float* const out[6], hipStream_t s);
+void launch_grow_fold(const GsrGrow& g, const GsrGrowGrads& d, hipStream_t s);
+
 struct DensifyLayout {
   size_t flags, block_counts, block_offs, totals, pos, bytes;
   int nblocks;

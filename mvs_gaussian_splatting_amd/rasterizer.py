@@ -359,18 +359,25 @@ def synchronize_counts() -> None:
     _drain_pending(block=True)
 
 
-def last_counts(dev, P: int, W: int, H: int) -> tuple:
-    """(num_rendered, num_visible) of the most recent checked frame of that shape on ``dev`` ((0, 0) if none)."""
-    key = (torch.device(dev).index or 0, int(P), int(W), int(H), _binning_mode_value)
+def _grown_key(P: int) -> tuple:
+    """Capacity-state key of the frames that render a P-Gaussian model with virtual rows appended (grow.py): P + G changes
+    from frame to frame, and all of them share one state instead of one (evicting) state per row count."""
+    return ("grown", int(P))
+
+
+def last_counts(dev, P: int, W: int, H: int, grown: bool = False) -> tuple:
+    """(num_rendered, num_visible) of the most recent checked frame of that shape on ``dev`` ((0, 0) if none).
+    ``grown``: of the frames of a P-Gaussian model with grown / split rows appended."""
+    key = (torch.device(dev).index or 0, _grown_key(P) if grown else int(P), int(W), int(H), _binning_mode_value)
     with _defer_lock:
         st = _states.get(key)
         return st.last_counts if st is not None else (0, 0)
 
 
-def reissued_frames(dev, P: int, W: int, H: int) -> int:
+def reissued_frames(dev, P: int, W: int, H: int, grown: bool = False) -> int:
     """Frames of that shape that were issued a second time (verified mode): they did not fit their capacity, or spanned
-    2^24 depth-key steps after being issued without the depth sort's fourth pass."""
-    key = (torch.device(dev).index or 0, int(P), int(W), int(H), _binning_mode_value)
+    2^24 depth-key steps after being issued without the depth sort's fourth pass.  ``grown``: as in last_counts."""
+    key = (torch.device(dev).index or 0, _grown_key(P) if grown else int(P), int(W), int(H), _binning_mode_value)
     with _defer_lock:
         st = _states.get(key)
         return st.reissued if st is not None else 0
@@ -425,19 +432,21 @@ def _depth_span(words, V: int) -> int:
     return mx - mn if V > 0 and mx >= mn else 0
 
 
-def _run_forward(lib, dev, params, P: int, W: int, H: int):
-    """Native forward on torch's current stream.  Returns (color, _Frame)."""
+def _run_forward(lib, dev, params, P: int, W: int, H: int, state_key=None):
+    """Native forward on torch's current stream.  Returns (color, _Frame).  ``state_key``: the capacity state's key in
+    place of P (grown frames, ``_grown_key``); such frames do not keep forward-only workspaces (their size varies)."""
     stream = _stream(dev)
     dev_index = dev.index or 0
     radii = torch.empty(P, dtype=torch.int32, device=dev)      # written for every Gaussian by the kernel
     color = torch.empty(3, H, W, dtype=torch.float32, device=dev)
     mode = params.binning_mode
-    st = _state_for((dev_index, P, W, H, mode))
+    st = _state_for((dev_index, P if state_key is None else state_key, W, H, mode))
     if _pending:
         _drain_pending()
     sync_mode = _sync_free_value
     sync_free = sync_mode != SYNC_OFF and st.capacity > 0 and mode != _lib.BINNING_KEYS64 and P > 0
-    cached = st.fo_ws.get(stream) if (sync_free and params.forward_only) else None
+    keep_fo = params.forward_only and state_key is None
+    cached = st.fo_ws.get(stream) if (sync_free and keep_fo) else None
     if cached is not None and cached[0] == st.capacity:
         # forward-only frames of one stream run one after the other and nothing outlives them: same workspaces every frame
         _, geom, img, binning = cached
@@ -450,7 +459,7 @@ def _run_forward(lib, dev, params, P: int, W: int, H: int):
         nbytes = lib.gsr_binning_bytes(cap, P, W, H, mode)
         if binning is None:
             binning = torch.empty(_round_ws(nbytes), dtype=torch.uint8, device=dev)
-            if params.forward_only:
+            if keep_fo:
                 _keep_forward_only_ws(st, stream, (cap, geom, img, binning))
         if sync_mode == SYNC_DEFERRED:
             slot, event = _pinned_slot(), _new_event(dev_index)
@@ -644,8 +653,10 @@ class _RasterizeGaussiansFused(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations,
-                raster_settings: GaussianRasterizationSettings, forward_only: bool = False, stats=None, visible=None):
-        """``visible``: None, or a bool [P] tensor the forward fills with ``radii > 0`` (render()'s visibility_filter)."""
+                raster_settings: GaussianRasterizationSettings, forward_only: bool = False, stats=None, visible=None,
+                state_key=None):
+        """``visible``: None, or a bool [P] tensor the forward fills with ``radii > 0`` (render()'s visibility_filter).
+        ``state_key``: see ``_run_forward``."""
         lib = _lib.load()
         dev = _require_gpu(means3D)
         P = int(means3D.shape[0])
@@ -678,7 +689,7 @@ class _RasterizeGaussiansFused(torch.autograd.Function):
                     raise TypeError("visible must be a contiguous bool [P] tensor on the Gaussians' device")
                 params.visible_out = visible.data_ptr()
             try:
-                color, frame = _run_forward(lib, dev, params, P, W, H)
+                color, frame = _run_forward(lib, dev, params, P, W, H, state_key)
             except _lib.GsrError:
                 if raster_settings.debug:      # same snapshot convention as the getter-fed operator above
                     torch.save((means3D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations, tuple(raster_settings)),
@@ -703,7 +714,7 @@ class _RasterizeGaussiansFused(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii):
         if grad_out_color is None:
-            return (None,) * 11
+            return (None,) * 12
         lib = _lib.load()
         means3D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations, radii, geom, binning, img = ctx.saved_tensors
         settings = ctx.raster_settings
@@ -733,7 +744,7 @@ class _RasterizeGaussiansFused(torch.autograd.Function):
                     print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
                 raise
         del keep
-        return g_means3D, g_means2D, g_dc, g_rest, g_opac, g_scales, g_rot, None, None, None, None
+        return g_means3D, g_means2D, g_dc, g_rest, g_opac, g_scales, g_rot, None, None, None, None, None
 
 
 def _forward_only(*tensors) -> bool:
@@ -756,16 +767,17 @@ class _NoGraph:
 
 
 def rasterize_gaussians_fused(means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations, raster_settings,
-                              densify_stats=None, visible=None):
+                              densify_stats=None, visible=None, _state_key=None):
     """``densify_stats``: None, or (xyz_gradient_accum, denom, max_radii2D) -- the backward then also accumulates the
     densification statistics of ``scene/gaussian_model.py:775-777`` / ``train.py:130``.
-    ``visible``: None, or a bool [P] tensor that receives ``radii > 0`` from the preprocess kernel."""
+    ``visible``: None, or a bool [P] tensor that receives ``radii > 0`` from the preprocess kernel.
+    ``_state_key`` (internal): the capacity state of grown frames (``_grown_key``) instead of the one of P rows."""
     if _forward_only(means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations):
         with torch.no_grad():
             return _RasterizeGaussiansFused.forward(_NoGraph(), means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales,
-                                                    raw_rotations, raster_settings, True, None, visible)
+                                                    raw_rotations, raster_settings, True, None, visible, _state_key)
     return _RasterizeGaussiansFused.apply(means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations,
-                                          raster_settings, False, densify_stats, visible)
+                                          raster_settings, False, densify_stats, visible, _state_key)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,

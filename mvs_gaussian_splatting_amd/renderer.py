@@ -1,7 +1,13 @@
-"""Render host: the plain path of the reference's ``gaussian_renderer.render``
-(``gaussian_renderer/__init__.py:19-90,256-313``) on duck-typed camera / model objects.
+"""Render host: the reference's ``gaussian_renderer.render`` (``gaussian_renderer/__init__.py:19-313``) on duck-typed
+camera / model objects, with the fork's grow / learned-split branch (``:91-253``, ``grow.py``).
 
-The fork's default-off grow / learned-split branch (``:91-253``) is out of scope.
+The branch opens when ``iteration`` and ``opt`` are given (``train.py:91`` passes both, ``training_report`` only ``opt``):
+grow mode (``grow_dir`` / ``continous_dir`` inside the densification window, after the first opacity reset) or the
+learned split (``modelcg.learn_split_distance`` / ``learn_split_scale``, every training frame).  An open frame renders
+P + G Gaussians and returns ``radii`` / ``visibility_filter`` of the P originals and ``selected_pts_mask``; the gradient
+of every virtual row lands on its source's parameters, the learned tensors (``_dirs_prob``, ``_conti_dirs``,
+``_grow_dist``, ``_split_distance``, ``_split_scale``) and ``viewspace_points``.  A closed frame is the plain frame,
+kernel for kernel.
 """
 from __future__ import annotations
 
@@ -9,7 +15,8 @@ import math
 
 import torch
 
-from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians_fused
+from . import grow
+from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, _grown_key, rasterize_gaussians_fused
 from .sh import eval_sh
 
 
@@ -59,27 +66,8 @@ def _fused_stats(pc, pipe, xyz):
     return trio
 
 
-def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier: float = 1.0,
-           override_color=None, **_fork_kwargs):
-    """Render the scene; ``bg_color`` must be on the GPU.  Returns the reference's result dict
-    (``gaussian_renderer/__init__.py:309-313``).
-
-    ``pipe.fuse_densify_stats = True`` (this build's extension) makes the backward of this frame also run
-    ``add_densification_stats`` (``scene/gaussian_model.py:775-777``) and the ``max_radii2D`` update of ``train.py:130``
-    on the model's accumulators; the ``add_densification_stats`` of this package then recognises the frame and does
-    nothing, so the reference's call sequence (render, backward, add_densification_stats) stays as it is."""
-    xyz = pc.get_xyz
-    # zero tensor whose .grad receives dL/d(mean2D) for the densification statistics.  The reference builds it as
-    # `zeros_like(...) + 0` + retain_grad() (gaussian_renderer/__init__.py:32-36); a leaf with requires_grad gets
-    # its .grad populated all the same and saves a 72 MB copy kernel per frame at 6 M Gaussians.
-    # The operator never reads (or writes) its values, so every frame's leaf aliases one cached block of zeros: a
-    # fresh 72 MB memset per frame is 20 us of the 6 M-Gaussian forward.
-    screenspace_points = _zero_leaf(xyz)
-    stats = _fused_stats(pc, pipe, xyz)
-    if stats is not None:
-        screenspace_points._gsr_stats_fused = True      # read by losses.add_densification_stats
-
-    raster_settings = GaussianRasterizationSettings(
+def _settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier):
+    return GaussianRasterizationSettings(
         image_height=int(viewpoint_camera.image_height),
         image_width=int(viewpoint_camera.image_width),
         tanfovx=math.tan(viewpoint_camera.FoVx * 0.5),
@@ -93,6 +81,35 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier:
         prefiltered=False,
         debug=bool(getattr(pipe, "debug", False)),
     )
+
+
+def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier: float = 1.0,
+           override_color=None, grow_dir=False, densify_grad_threshold=0, iteration=None, opt=None,
+           continous_dir=False, grow_distance=False, modelcg=None, cameras_extent=None):
+    """Render the scene; ``bg_color`` must be on the GPU.  Returns the reference's result dict
+    (``gaussian_renderer/__init__.py:309-313``).  The keyword arguments after ``override_color`` are the reference's
+    (``:19``) and drive the grow / learned-split branch (module docstring); the frame of a closed branch is unchanged.
+
+    ``pipe.fuse_densify_stats = True`` (this build's extension) makes the backward of this frame also run
+    ``add_densification_stats`` (``scene/gaussian_model.py:775-777``) and the ``max_radii2D`` update of ``train.py:130``
+    on the model's accumulators; the ``add_densification_stats`` of this package then recognises the frame and does
+    nothing, so the reference's call sequence (render, backward, add_densification_stats) stays as it is."""
+    which = grow.branch(iteration, opt, grow_dir, continous_dir, modelcg)
+    if which is not None:
+        return _render_grown(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, which, grow_dir,
+                             densify_grad_threshold, continous_dir, grow_distance, modelcg, cameras_extent)
+    xyz = pc.get_xyz
+    # zero tensor whose .grad receives dL/d(mean2D) for the densification statistics.  The reference builds it as
+    # `zeros_like(...) + 0` + retain_grad() (gaussian_renderer/__init__.py:32-36); a leaf with requires_grad gets
+    # its .grad populated all the same and saves a 72 MB copy kernel per frame at 6 M Gaussians.
+    # The operator never reads (or writes) its values, so every frame's leaf aliases one cached block of zeros: a
+    # fresh 72 MB memset per frame is 20 us of the 6 M-Gaussian forward.
+    screenspace_points = _zero_leaf(xyz)
+    stats = _fused_stats(pc, pipe, xyz)
+    if stats is not None:
+        screenspace_points._gsr_stats_fused = True      # read by losses.add_densification_stats
+
+    raster_settings = _settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier)
     if _can_fuse(pc, pipe, override_color):
         # same result as the getter path below, without materialising cat(f_dc, f_rest), exp, normalize, sigmoid (and
         # without building an nn.Module per frame: the operator is called as a function)
@@ -136,3 +153,41 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier:
             "visibility_filter": radii > 0,
             "radii": radii,
             "selected_pts_mask": None}
+
+
+def _render_grown(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, which, grow_dir,
+                  densify_grad_threshold, continous_dir, grow_distance, modelcg, cameras_extent):
+    """A frame of the open grow / learned-split branch (``gaussian_renderer/__init__.py:91-253``) on the fused
+    raw-parameter path: plan (one count read-back), expansion to P + G rows, the fused operator, radii of the P originals.
+    The in-backward densification statistics are not taken (their accumulators have P rows): the caller's
+    ``add_densification_stats`` reads the folded ``viewspace_points.grad``."""
+    if override_color is not None or getattr(pipe, "convert_SHs_python", False) or \
+            getattr(pipe, "compute_cov3D_python", False):
+        raise ValueError("the grow / learned-split branch exists for SH + scale / rotation inputs only: with "
+                         "override_color, convert_SHs_python or compute_cov3D_python the reference's own branch fails "
+                         "on torch.cat(None, ...) (gaussian_renderer/__init__.py:114-115, :246)")
+    if not _can_fuse(pc, pipe, None):
+        raise ValueError("the grow / learned-split branch runs on the fused raw-parameter path only: the model must be "
+                         "the reference's parameterisation on the GPU with pipe.fuse_activations left on")
+    mode = grow.mode_bits(which, grow_dir, continous_dir, grow_distance, modelcg)
+    pde = grow.percent_dense_extent(pc, which, modelcg, cameras_extent)
+    pl = grow.plan(pc, mode, densify_grad_threshold, pde)
+    if which == grow.GROW and pde != math.inf and pl.n_big > 0:
+        raise ValueError(grow._QUIRK.format(n=pl.n_big))
+    xyz = pc.get_xyz
+    P = int(xyz.shape[0])
+    screenspace_points = _zero_leaf(xyz)
+    raster_settings = _settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier)
+    if which == grow.SPLIT and pl.G == 0:
+        # :196 nothing to split: the plain frame (the learned split tensors take no part in it)
+        visible = torch.empty(P, dtype=torch.bool, device=xyz.device)
+        rendered_image, radii = rasterize_gaussians_fused(xyz, screenspace_points, pc._features_dc, pc._features_rest,
+                                                          pc._opacity, pc._scaling, pc._rotation, raster_settings,
+                                                          visible=visible)
+        return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": visible,
+                "radii": radii, "selected_pts_mask": pl.selected}
+    _, ext = grow.expand(pc, screenspace_points, mode, densify_grad_threshold, pde, pl=pl)
+    visible = torch.empty(P + pl.G, dtype=torch.bool, device=xyz.device)
+    rendered_image, radii = rasterize_gaussians_fused(*ext, raster_settings, visible=visible, _state_key=_grown_key(P))
+    return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": visible[:P],
+            "radii": radii[:P], "selected_pts_mask": pl.selected}
