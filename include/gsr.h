@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 14
+#define GSR_ABI_VERSION 15
 
 enum {
   GSR_OK = 0,
@@ -379,6 +379,59 @@ int gsr_grow_plan(int32_t P, const float* xyz_gradient_accum, const float* denom
 int gsr_grow_expand(const GsrGrow* g, float* xyz_out, float* f_dc_out, float* f_rest_out, float* opacity_out,
                     float* scaling_out, float* rotation_out, void* stream);
 int gsr_grow_fold(const GsrGrow* g, const GsrGrowGrads* grads, void* stream);
+
+/* The fork's densify_and_prune (scene/gaussian_model.py:751-773), ABI v15: the clone + split branch with the learned
+ * tensors (:509-610) and the grow branch (densify_and_grow :612-677, densify_and_growsplit :679-749), then the prune,
+ * as one plan and one read-once / write-once pass per tensor.  mode: the GSR_GROW_* / GSR_SPLIT_* bits of the model's
+ * flags, GSR_DENSIFY_GROW when the grow branch runs (:755), GSR_DENSIFY_SYMMETRIC for modelcg.symmetric_split.
+ *   gsr_densify_fork_plan: as gsr_densify_plan, with split_scale_raw [P,1] (NULL without learn_split_scale) giving
+ *     each row's child divisor 2 (0.6 sigmoid + 0.5) instead of 1.6 (:560-563, also in the children's prune test).
+ *     Synchronises the stream and returns counts_host = {kept originals, kept clones / grown copies, kept children
+ *     PER COPY, split-selected, selected}.  The output has counts[0] + counts[1] + c * counts[2] rows, c = 4 in the
+ *     grow branch (children of the originals and of their grown copies), else 2:
+ *       [kept originals | clones or grown | first children (of originals, then of grown) | second children (same)]
+ *   gsr_densify_fork_gather_rows: dst[rows_out, row_floats] <- src[P, row_floats] with a value policy per role
+ *     (GSR_ROW_POLICY(selected originals, clones / grown, children)): GSR_ROW_COPY, GSR_ROW_CONST (`value`: 0 for the
+ *     new rows' Adam moments :458-459 and the re-inits of :560-574 / :653-655, 1 / num_dirs for :646-648) or
+ *     GSR_ROW_SKIP (written by gsr_densify_fork_rows).  Originals that are not selected always copy.
+ *   gsr_densify_fork_rows: the computed rows -- grown xyz + dir * max(exp(scaling)) * d (:617-635, dir the largest
+ *     logit of _dirs_prob, lowest index on ties, or normalize(_conti_dirs)), the children's xyz R s + centre and
+ *     scaling log(exp(scaling) / k), and (conti_out != NULL) normalize(dir_noise) into every row of a selected Gaussian
+ *     (:650-651).  noise: the standard-normal draws of torch.normal(0, stds) over the split rows of the reference's
+ *     order, [2n,3], or [n,3] with GSR_DENSIFY_SYMMETRIC (second child = -first), unused with GSR_SPLIT_DISTANCE;
+ *     n = counts[3] (clone + split) or 2 counts[3] (grow).  dir_noise [counts[4],3]: torch.randn of :650. */
+enum {
+  GSR_DENSIFY_GROW = 32,
+  GSR_DENSIFY_SYMMETRIC = 64
+};
+enum { GSR_ROW_COPY = 0, GSR_ROW_CONST = 1, GSR_ROW_SKIP = 2 };
+#define GSR_ROW_POLICY(orig_sel, extra, child) ((orig_sel) | ((extra) << 2) | ((child) << 4))
+
+typedef struct GsrDensifyFork {
+  int32_t P, mode, num_dirs;
+  const float* xyz;                            /* device [P,3] raw model tensors */
+  const float* scaling;                        /* [P,3] raw */
+  const float* rotation;                       /* [P,4] raw */
+  const float* dirs_prob;                      /* [P,num_dirs] (grow branch with GSR_GROW_DIR) */
+  const float* dirs;                           /* [num_dirs,3] (grow branch with GSR_GROW_DIR) */
+  const float* conti_dirs;                     /* [P,3] (grow branch with GSR_GROW_CONTINUOUS) */
+  const float* grow_dist;                      /* [P,1] raw (grow branch with GSR_GROW_DISTANCE) */
+  const float* split_distance;                 /* [P,3] raw (GSR_SPLIT_DISTANCE) */
+  const float* split_scale;                    /* [P,1] raw (GSR_SPLIT_SCALE) */
+  const float* noise;                          /* split draws, see above */
+  const float* dir_noise;                      /* [counts[4],3] (conti_out != NULL) */
+} GsrDensifyFork;
+
+size_t gsr_densify_fork_workspace_bytes(int32_t P);
+int gsr_densify_fork_plan(int32_t P, const float* xyz_gradient_accum, const float* denom, const float* scaling_raw,
+                          const float* opacity_raw, const float* split_scale_raw, float grad_threshold,
+                          float percent_dense_extent, float min_opacity, float max_world_scale, void* workspace,
+                          size_t workspace_bytes, uint32_t counts_host[5], void* stream);
+int gsr_densify_fork_gather_rows(int32_t P, int32_t row_floats, const float* src, const void* workspace,
+                                 const uint32_t counts[5], int32_t grow_branch, int32_t policy, float value, float* dst,
+                                 void* stream);
+int gsr_densify_fork_rows(const GsrDensifyFork* f, const void* workspace, const uint32_t counts[5], float* xyz_out,
+                          float* scaling_out, float* conti_dirs_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # instead of copying it over the in-tree library
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 
 class GsrParams(C.Structure):
@@ -54,6 +54,22 @@ class GsrGrowGrads(C.Structure):
 
 
 GROW_DIR, GROW_CONTINUOUS, GROW_DISTANCE, SPLIT_DISTANCE, SPLIT_SCALE = 1, 2, 4, 8, 16
+
+
+class GsrDensifyFork(C.Structure):
+    _fields_ = [("P", C.c_int32), ("mode", C.c_int32), ("num_dirs", C.c_int32)] + [
+        (n, C.c_void_p) for n in ("xyz", "scaling", "rotation", "dirs_prob", "dirs", "conti_dirs", "grow_dist",
+                                  "split_distance", "split_scale", "noise", "dir_noise")]
+
+
+# the fork's densify_and_prune (gsr_densify_fork_*): branch / split bits next to the GROW_* / SPLIT_* flags, and the
+# value policy of one tensor's roles, ROW_POLICY(selected originals, clones / grown copies, children)
+DENSIFY_GROW, DENSIFY_SYMMETRIC = 32, 64
+ROW_COPY, ROW_CONST, ROW_SKIP = 0, 1, 2
+
+
+def ROW_POLICY(orig_sel: int, extra: int, child: int) -> int:
+    return orig_sel | (extra << 2) | (child << 4)
 ACT_SCALE_EXP, ACT_ROT_NORMALIZE, ACT_OPACITY_SIGMOID = 1, 2, 4
 BINNING_TWO_LEVEL, BINNING_KEYS64, BINNING_TWO_LEVEL_CULLED = 0, 1, 2
 DSSIM_ONE_MINUS_MEAN, DSSIM_CLAMPED_HALF = 0, 1
@@ -113,6 +129,14 @@ SYMBOLS = {
                                           C.c_void_p, C.c_void_p]),
     "gsr_densify_split_children": (C.c_int, [C.c_int32] + [C.c_void_p] * 5 + [C.POINTER(C.c_uint32), C.c_void_p,
                                              C.c_void_p, C.c_void_p]),
+    # scene/gaussian_model.py:751-773, the fork's branches (clone + split :509-610, grow :612-749): include/gsr.h
+    "gsr_densify_fork_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "gsr_densify_fork_plan": (C.c_int, [C.c_int32] + [C.c_void_p] * 5 + [C.c_float] * 4 + [C.c_void_p, C.c_size_t,
+                                        C.POINTER(C.c_uint32), C.c_void_p]),
+    "gsr_densify_fork_gather_rows": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32),
+                                               C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
+    "gsr_densify_fork_rows": (C.c_int, [C.POINTER(GsrDensifyFork), C.c_void_p, C.POINTER(C.c_uint32)] +
+                              [C.c_void_p] * 4),
     "gsr_grow_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "gsr_grow_plan": (C.c_int, [C.c_int32] + [C.c_void_p] * 3 + [C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_size_t]
                       + [C.c_void_p] * 3 + [C.POINTER(C.c_uint32), C.c_void_p]),

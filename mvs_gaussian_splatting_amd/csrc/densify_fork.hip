@@ -1,0 +1,334 @@
+// The fork's densification (scene/gaussian_model.py:751-773): the clone + split branch with the learned tensors
+// (:509-610) and the grow branch (densify_and_grow :612-677, densify_and_growsplit :679-749), then the prune, as one plan
+// and one read-once / write-once pass per tensor -- densify.hip's shape, with more roles per source row.
+//
+// A grown row shares scaling, opacity and _split_scale with its source, so every decision of either branch is a decision
+// about the P source rows.  Each source row i yields up to four output roles, all subject to the final prune:
+//
+//   orig   : row i itself                 kept unless it is split or pruned
+//   extra  : its clone / its grown copy   exists when sel & !big, kept unless pruned
+//   child  : the split children of row i (and, in the grow branch, of its grown copy), when sel & big and not pruned
+//
+//   out = [ orig | extra | children #1 of orig | (grow) #1 of grown | children #2 of orig | (grow) #2 of grown ]
+//
+// which is the reference's order: clone + split gives [kept | clones | first | second]; grow gives A = [P | G grown],
+// then B = [A without split rows | first children in A order | second children in A order], then the prune.
+//
+//   plan      : g = accum / denom (NaN -> 0); sel = g >= thr; big = max(exp(scaling)) > pd*extent; the prune test of
+//               the children reads exp(log(exp(scaling) / (2k))) with the row's own k (0.8, or 0.6 sigmoid(split_scale)
+//               + 0.5 with learn_split_scale)
+//   positions : exclusive scans of the five classes {orig, extra, child, split-selected, selected}; sel_src lists the
+//               selected rows in row order
+//   gather    : dst row <- src row with a per-role value policy (copy, a constant, or left to the computed-row pass);
+//               16-byte accesses for rows of 4k floats (_dirs_prob is 512 B per row at 128 directions)
+//   rows      : the computed rows of the selected Gaussians -- grown xyz, children xyz and scaling, the normalised
+//               conti_dirs re-init -- one wave per row when the direction needs the argmax over _dirs_prob
+//
+// The per-Gaussian arithmetic keeps the reference's float32 operation order (built with -ffp-contract=off).
+#include "gsr_common.h"
+#include "gsr_launch.h"
+#include "grow_common.h"
+
+namespace gsr {
+
+constexpr int DF_BLOCK = PRE_BLOCK;
+constexpr int DF_NC = 5;
+enum : uint8_t { DF_ORIG = 1, DF_EXTRA = 2, DF_CHILD = 4, DF_SPLIT_SEL = 8, DF_SEL = 16 };
+
+// 2 (0.6 sigmoid(_split_scale) + 0.5) or 0.8 * 2 (:560-563 / :714-718): `splitscale * N` in float32
+__device__ inline float fork_split_div(const float* __restrict__ split_scale, int i) {
+  return split_scale ? (0.6f * sigmoidf_(split_scale[i]) + 0.5f) * 2.0f : 1.6f;
+}
+
+__global__ __launch_bounds__(DF_BLOCK) void densify_fork_plan_kernel(int P, const float* __restrict__ accum,
+                                                                      const float* __restrict__ denom,
+                                                                      const float* __restrict__ scaling,
+                                                                      const float* __restrict__ opacity,
+                                                                      const float* __restrict__ split_scale, float thr,
+                                                                      float pde, float min_opacity, float ws_limit,
+                                                                      int use_ws, uint8_t* __restrict__ flags,
+                                                                      uint32_t* __restrict__ block_counts, int nblocks) {
+  __shared__ uint32_t cnt[DF_NC];
+  if (threadIdx.x < DF_NC) cnt[threadIdx.x] = 0;
+  __syncthreads();
+  const int i = blockIdx.x * DF_BLOCK + threadIdx.x;
+  uint8_t f = 0;
+  if (i < P) {
+    float g = accum[i] / denom[i];
+    if (g != g) g = 0.0f;
+    const float s0 = expf(scaling[3 * i]), s1 = expf(scaling[3 * i + 1]), s2 = expf(scaling[3 * i + 2]);
+    const float mx = fmaxf(fmaxf(s0, s1), s2);
+    const bool sel = g >= thr, big = mx > pde;
+    const float op = 1.0f / (1.0f + expf(-opacity[i]));
+    const bool low = op < min_opacity;
+    const bool prune_o = low || (use_ws && mx > ws_limit);
+    const float k = fork_split_div(split_scale, i);
+    const float c0 = expf(logf(s0 / k)), c1 = expf(logf(s1 / k)), c2 = expf(logf(s2 / k));
+    const bool prune_c = low || (use_ws && fmaxf(fmaxf(c0, c1), c2) > ws_limit);
+    if (!(sel && big) && !prune_o) f |= DF_ORIG;
+    if (sel && !big && !prune_o) f |= DF_EXTRA;
+    if (sel && big && !prune_c) f |= DF_CHILD;
+    if (sel && big) f |= DF_SPLIT_SEL;
+    if (sel) f |= DF_SEL;
+    flags[i] = f;
+  }
+#pragma unroll
+  for (int b = 0; b < DF_NC; ++b) {
+    const uint64_t m = __builtin_amdgcn_ballot_w64((f >> b) & 1);
+    if ((threadIdx.x & (WAVE - 1)) == 0 && m) atomicAdd(&cnt[b], (uint32_t)__builtin_popcountll(m));
+  }
+  __syncthreads();
+  if (threadIdx.x < DF_NC) block_counts[threadIdx.x * (nblocks + 1) + blockIdx.x] = cnt[threadIdx.x];
+}
+
+// pos[c * P + i] = rank of row i in class c, or -1; sel_src[rank among the selected] = i
+__global__ __launch_bounds__(DF_BLOCK) void densify_fork_positions_kernel(int P, const uint8_t* __restrict__ flags,
+                                                                           const uint32_t* __restrict__ block_offs,
+                                                                           int nblocks, int32_t* __restrict__ pos,
+                                                                           int32_t* __restrict__ sel_src) {
+  __shared__ uint32_t wave_tot[DF_NC][DF_BLOCK / WAVE];
+  const int i = blockIdx.x * DF_BLOCK + threadIdx.x;
+  const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
+  const uint8_t f = i < P ? flags[i] : 0;
+  uint32_t rank[DF_NC];
+#pragma unroll
+  for (int b = 0; b < DF_NC; ++b) {
+    const uint64_t m = __builtin_amdgcn_ballot_w64((f >> b) & 1);
+    rank[b] = (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_tot[b][wid] = (uint32_t)__builtin_popcountll(m);
+  }
+  __syncthreads();
+  if (i >= P) return;
+#pragma unroll
+  for (int b = 0; b < DF_NC; ++b) {
+    uint32_t base = block_offs[b * (nblocks + 1) + blockIdx.x];
+    for (int w = 0; w < wid; ++w) base += wave_tot[b][w];
+    const int32_t r = ((f >> b) & 1) ? (int32_t)(base + rank[b]) : -1;
+    pos[(size_t)b * P + i] = r;
+    if (b == DF_NC - 1 && r >= 0) sel_src[r] = i;      // r < #selected <= P
+  }
+}
+
+__device__ inline float splat_const(float, float c) { return c; }
+__device__ inline float4 splat_const(float4, float c) { return make_float4(c, c, c, c); }
+
+// One chunk (a float or a float4) of one source row per thread; every output role of the row gets its policy's value.
+// Non-selected originals always copy.  ncopies: children per split row (2 clone + split, 4 grow).
+template <typename V>
+__global__ __launch_bounds__(256) void densify_fork_gather_kernel(size_t total, int wv, int P,
+                                                                   const V* __restrict__ src,
+                                                                   const uint8_t* __restrict__ flags,
+                                                                   const int32_t* __restrict__ pos, uint32_t n_orig,
+                                                                   uint32_t n_extra, uint32_t n_child, int ncopies,
+                                                                   int pol_orig, int pol_extra, int pol_child,
+                                                                   float value, V* __restrict__ dst) {
+  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= total) return;
+  const uint32_t i = (uint32_t)(e / (size_t)wv), c = (uint32_t)(e - (size_t)i * wv);
+  const int32_t po = pos[i], pe = pos[(size_t)P + i], pc = pos[2 * (size_t)P + i];
+  const int o_pol = (flags[i] & DF_SEL) ? pol_orig : GSR_ROW_COPY;
+  const bool w_o = po >= 0 && o_pol != GSR_ROW_SKIP, w_e = pe >= 0 && pol_extra != GSR_ROW_SKIP,
+             w_c = pc >= 0 && pol_child != GSR_ROW_SKIP;
+  if (!w_o && !w_e && !w_c) return;
+  const bool need = (w_o && o_pol == GSR_ROW_COPY) || (w_e && pol_extra == GSR_ROW_COPY) ||
+                    (w_c && pol_child == GSR_ROW_COPY);
+  const V k = splat_const(V{}, value);
+  const V v = need ? src[e] : k;
+  if (w_o) dst[(size_t)po * wv + c] = o_pol == GSR_ROW_COPY ? v : k;
+  if (w_e) dst[((size_t)n_orig + pe) * wv + c] = pol_extra == GSR_ROW_COPY ? v : k;
+  if (w_c) {
+    const V vc = pol_child == GSR_ROW_COPY ? v : k;
+    for (int j = 0; j < ncopies; ++j) dst[((size_t)n_orig + n_extra + (size_t)j * n_child + pc) * wv + c] = vc;
+  }
+}
+
+struct ForkRowsArgs {
+  GsrDensifyFork f;
+  const int32_t* pos;
+  const int32_t* sel_src;
+  uint32_t n_orig, n_extra, n_child, n_split, n_sel;
+  float* xyz_out;
+  float* scaling_out;
+  float* conti_out;
+};
+
+// The computed rows of selected row i; dir: the grow direction (grow branch only).
+__device__ inline void fork_rows(const ForkRowsArgs& a, int i, const float* dir) {
+  const GsrDensifyFork& f = a.f;
+  const size_t P = (size_t)f.P;
+  const int32_t po = a.pos[i], pe = a.pos[P + i], pc = a.pos[2 * P + i];
+  const bool grow = (f.mode & GSR_DENSIFY_GROW) != 0;
+  const int ncopies = grow ? 4 : 2;
+  const size_t child0 = (size_t)a.n_orig + a.n_extra;
+  float stds[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) stds[c] = expf(f.scaling[3 * i + c]);
+  const float* p = f.xyz + 3 * (size_t)i;
+  float gx[3] = {p[0], p[1], p[2]};
+  if (grow) {       // :632-635, read before the re-init of :645-655
+    const float s = fmaxf(fmaxf(stds[0], stds[1]), stds[2]);
+    const float d = (f.mode & GSR_GROW_DISTANCE) ? 2.0f * sigmoidf_(f.grow_dist[i]) : 1.0f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) gx[c] = p[c] + (dir[c] * s) * d;
+    if (pe >= 0)
+      for (int c = 0; c < 3; ++c) a.xyz_out[3 * ((size_t)a.n_orig + pe) + c] = gx[c];
+  }
+  if (a.conti_out) {  // :650-651: every row that comes from row i carries normalize(randn)
+    const float* z = f.dir_noise + 3 * (size_t)a.pos[4 * P + i];
+    const float n = fmaxf(sqrtf(z[0] * z[0] + z[1] * z[1] + z[2] * z[2]), 1e-12f);
+    const float u[3] = {z[0] / n, z[1] / n, z[2] / n};
+    for (int c = 0; c < 3; ++c) {
+      if (po >= 0) a.conti_out[3 * (size_t)po + c] = u[c];
+      if (pe >= 0) a.conti_out[3 * ((size_t)a.n_orig + pe) + c] = u[c];
+      if (pc >= 0)
+        for (int j = 0; j < ncopies; ++j) a.conti_out[3 * (child0 + (size_t)j * a.n_child + pc) + c] = u[c];
+    }
+  }
+  if (pc < 0) return;
+  // children (:523-548 / :694-718): samples, rotation, scaling
+  Rot r;
+  build_rotation(f.rotation + 4 * (size_t)i, r);
+  const float k = fork_split_div(f.split_scale, i);
+  float ls[3], sd[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    ls[c] = logf(stds[c] / k);
+    sd[c] = (f.mode & GSR_SPLIT_DISTANCE) ? stds[c] * (2.2f * sigmoidf_(f.split_distance[3 * i + c])) : 0.0f;
+  }
+  // the split rows of A (the reference's order of samples): originals, then (grow) grown copies
+  const uint32_t r_split = (uint32_t)a.pos[3 * P + i], nA = grow ? 2 * a.n_split : a.n_split;
+  const int nsrc = grow ? 2 : 1;
+  for (int h = 0; h < 2; ++h) {             // first / second child
+    for (int q = 0; q < nsrc; ++q) {        // of the original / of the grown copy
+      const uint32_t ra = (uint32_t)q * a.n_split + r_split;      // row of A among its split rows
+      float s[3];
+      if (f.mode & GSR_SPLIT_DISTANCE) {
+        for (int c = 0; c < 3; ++c) s[c] = h ? -sd[c] : sd[c];
+      } else if (f.mode & GSR_DENSIFY_SYMMETRIC) {
+        const float* z = f.noise + 3 * (size_t)ra;
+        for (int c = 0; c < 3; ++c) { const float v = 0.0f + stds[c] * z[c]; s[c] = h ? -v : v; }
+      } else {
+        const float* z = f.noise + 3 * ((size_t)h * nA + ra);
+        for (int c = 0; c < 3; ++c) s[c] = 0.0f + stds[c] * z[c];
+      }
+      const float* ctr = q ? gx : p;
+      const size_t o = 3 * (child0 + (size_t)(h * nsrc + q) * a.n_child + pc);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float* R = r.R + 3 * c;
+        a.xyz_out[o + c] = ((R[0] * s[0] + R[1] * s[1]) + R[2] * s[2]) + ctr[c];
+        a.scaling_out[o + c] = ls[c];
+      }
+    }
+  }
+}
+
+// one thread per selected row (no argmax needed)
+__global__ __launch_bounds__(256) void densify_fork_rows_kernel(ForkRowsArgs a) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= a.n_sel) return;
+  const int i = a.sel_src[j];
+  float dir[3] = {0.f, 0.f, 0.f};
+  if ((a.f.mode & GSR_DENSIFY_GROW) && (a.f.mode & GSR_GROW_CONTINUOUS)) {
+    const float* v = a.f.conti_dirs + 3 * (size_t)i;
+    const float n = fmaxf(sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]), 1e-12f);   // F.normalize (:623)
+    dir[0] = v[0] / n; dir[1] = v[1] / n; dir[2] = v[2] / n;
+  }
+  fork_rows(a, i, dir);
+}
+
+// one wave per selected row: the straight-through one-hot of softmax(_dirs_prob) times dirs (:617-621, :360-366)
+__global__ __launch_bounds__(256) void densify_fork_rows_dir_kernel(ForkRowsArgs a) {
+  const uint32_t j = blockIdx.x * (256 / WAVE) + threadIdx.x / WAVE;
+  const int lane = threadIdx.x & (WAVE - 1);
+  if (j >= a.n_sel) return;
+  const int i = a.sel_src[j];
+  const int nd = a.f.num_dirs;
+  const float* __restrict__ row = a.f.dirs_prob + (size_t)i * nd;
+  float best;
+  int bi;
+  wave_argmax(row, nd, lane, best, bi);
+  float sum = 0.0f;
+  for (int n = lane; n < nd; n += WAVE) sum += expf(row[n] - best);
+  sum = wave_reduce_add_f32(sum);
+  if (lane != 0) return;
+  const float y = 1.0f / sum;           // softmax at the argmax
+  const float h = (1.0f - y) + y;       // y_hard - y_soft.detach() + y_soft
+  const float dir[3] = {h * a.f.dirs[3 * bi], h * a.f.dirs[3 * bi + 1], h * a.f.dirs[3 * bi + 2]};
+  fork_rows(a, i, dir);
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------
+DensifyForkLayout::DensifyForkLayout(int P) {
+  nblocks = (P + DF_BLOCK - 1) / DF_BLOCK;
+  if (nblocks < 1) nblocks = 1;
+  const size_t Pn = (size_t)(P > 0 ? P : 1);
+  size_t o = 0;
+  flags = o;        o = align_up(o + Pn, 256);
+  block_counts = o; o = align_up(o + 4 * DF_NC * (size_t)(nblocks + 1), 256);
+  block_offs = o;   o = align_up(o + 4 * DF_NC * (size_t)(nblocks + 1), 256);
+  totals = o;       o = align_up(o + 64, 256);
+  pos = o;          o = align_up(o + 4 * DF_NC * Pn, 256);
+  sel_src = o;      o = align_up(o + 4 * Pn, 256);
+  bytes = o;
+}
+
+void launch_densify_fork_plan(int P, const float* accum, const float* denom, const float* scaling,
+                              const float* opacity, const float* split_scale, float thr, float pde, float min_opacity,
+                              float ws_limit, int use_ws, void* ws, hipStream_t s) {
+  const DensifyForkLayout L(P);
+  char* base = static_cast<char*>(ws);
+  uint8_t* flags = reinterpret_cast<uint8_t*>(base + L.flags);
+  uint32_t* counts = reinterpret_cast<uint32_t*>(base + L.block_counts);
+  uint32_t* offs = reinterpret_cast<uint32_t*>(base + L.block_offs);
+  uint32_t* totals = reinterpret_cast<uint32_t*>(base + L.totals);
+  int32_t* pos = reinterpret_cast<int32_t*>(base + L.pos);
+  int32_t* sel_src = reinterpret_cast<int32_t*>(base + L.sel_src);
+  const int nb = L.nblocks, st = nb + 1;
+  hipLaunchKernelGGL(densify_fork_plan_kernel, dim3(nb), dim3(DF_BLOCK), 0, s, P, accum, denom, scaling, opacity,
+                     split_scale, thr, pde, min_opacity, ws_limit, use_ws, flags, counts, nb);
+  launch_scan_block_sums(counts, offs, totals, counts + st, offs + st, totals + 1, nb, s);
+  launch_scan_block_sums(counts + 2 * st, offs + 2 * st, totals + 2, counts + 3 * st, offs + 3 * st, totals + 3, nb, s);
+  launch_scan_block_sums(counts + 4 * st, offs + 4 * st, totals + 4, nullptr, nullptr, nullptr, nb, s);
+  hipLaunchKernelGGL(densify_fork_positions_kernel, dim3(nb), dim3(DF_BLOCK), 0, s, P, flags, offs, nb, pos, sel_src);
+}
+
+void launch_densify_fork_gather_rows(int P, int w, const float* src, const void* ws, const uint32_t counts[5],
+                                     int ncopies, int policy, float value, float* dst, hipStream_t s) {
+  const DensifyForkLayout L(P);
+  const char* base = static_cast<const char*>(ws);
+  const uint8_t* flags = reinterpret_cast<const uint8_t*>(base + L.flags);
+  const int32_t* pos = reinterpret_cast<const int32_t*>(base + L.pos);
+  const int po = policy & 3, pe = (policy >> 2) & 3, pc = (policy >> 4) & 3;
+  const bool vec = (w & 3) == 0 && (((uintptr_t)src | (uintptr_t)dst) & 15u) == 0;
+  const int wv = vec ? w / 4 : w;
+  const size_t total = (size_t)P * wv;
+  if (total == 0) return;
+  const dim3 grid((unsigned)((total + 255) / 256));
+  if (vec)
+    hipLaunchKernelGGL(densify_fork_gather_kernel<float4>, grid, dim3(256), 0, s, total, wv, P,
+                       reinterpret_cast<const float4*>(src), flags, pos, counts[0], counts[1], counts[2], ncopies, po,
+                       pe, pc, value, reinterpret_cast<float4*>(dst));
+  else
+    hipLaunchKernelGGL(densify_fork_gather_kernel<float>, grid, dim3(256), 0, s, total, wv, P, src, flags, pos,
+                       counts[0], counts[1], counts[2], ncopies, po, pe, pc, value, dst);
+}
+
+void launch_densify_fork_rows(const GsrDensifyFork& f, const void* ws, const uint32_t counts[5], float* xyz_out,
+                              float* scaling_out, float* conti_out, hipStream_t s) {
+  const DensifyForkLayout L(f.P);
+  const char* base = static_cast<const char*>(ws);
+  ForkRowsArgs a;
+  a.f = f;
+  a.pos = reinterpret_cast<const int32_t*>(base + L.pos);
+  a.sel_src = reinterpret_cast<const int32_t*>(base + L.sel_src);
+  a.n_orig = counts[0]; a.n_extra = counts[1]; a.n_child = counts[2]; a.n_split = counts[3]; a.n_sel = counts[4];
+  a.xyz_out = xyz_out; a.scaling_out = scaling_out; a.conti_out = conti_out;
+  if (a.n_sel == 0) return;
+  if ((f.mode & GSR_DENSIFY_GROW) && (f.mode & GSR_GROW_DIR))
+    hipLaunchKernelGGL(densify_fork_rows_dir_kernel, dim3((a.n_sel + 3) / 4), dim3(256), 0, s, a);
+  else
+    hipLaunchKernelGGL(densify_fork_rows_kernel, dim3((a.n_sel + 255) / 256), dim3(256), 0, s, a);
+}
+
+}  // namespace gsr

@@ -14,13 +14,12 @@
 // The per-Gaussian arithmetic keeps the reference's float32 operation order (built with -ffp-contract=off).
 #include "gsr_common.h"
 #include "gsr_launch.h"
+#include "grow_common.h"
 
 namespace gsr {
 
 constexpr int GR_BLOCK = PRE_BLOCK;
 constexpr int GR_WAVES = GR_BLOCK / WAVE;
-
-__device__ inline float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // index of the largest of three scales; ties go to the lowest index (torch.max's CPU tie-break, :108 / :190)
 __device__ inline int argmax3(float a, float b, float c) {
@@ -29,22 +28,6 @@ __device__ inline int argmax3(float a, float b, float c) {
   if (b > m) { m = b; k = 1; }
   if (c > m) k = 2;
   return k;
-}
-
-struct Rot {
-  float w, x, y, z, norm;   // normalised quaternion and the norm it was divided by
-  float R[9];
-};
-
-// utils/general_utils.py:78-99 build_rotation
-__device__ inline void build_rotation(const float* __restrict__ q, Rot& r) {
-  const float qr = q[0], qx = q[1], qy = q[2], qz = q[3];
-  r.norm = sqrtf(qr * qr + qx * qx + qy * qy + qz * qz);
-  const float w = qr / r.norm, x = qx / r.norm, y = qy / r.norm, z = qz / r.norm;
-  r.w = w; r.x = x; r.y = y; r.z = z;
-  r.R[0] = 1.f - 2.f * (y * y + z * z); r.R[1] = 2.f * (x * y - w * z); r.R[2] = 2.f * (x * z + w * y);
-  r.R[3] = 2.f * (x * y + w * z); r.R[4] = 1.f - 2.f * (x * x + z * z); r.R[5] = 2.f * (y * z - w * x);
-  r.R[6] = 2.f * (x * z - w * y); r.R[7] = 2.f * (y * z + w * x); r.R[8] = 1.f - 2.f * (x * x + y * y);
 }
 
 // dL/d(raw quaternion) from dL/dR (row-major 3x3), through build_rotation's normalisation
@@ -147,24 +130,6 @@ __global__ __launch_bounds__(256) void grow_expand_rows_kernel(RowArrays a, int 
       out[e] = in[(size_t)src[j] * w + c];
     }
   }
-}
-
-// argmax of softmax(logits) over one row, in every lane: the largest logit, the lowest index on ties (:361-363).  A row
-// without any ordered value yields index 0 and max -inf.
-__device__ inline void wave_argmax(const float* __restrict__ row, int nd, int lane, float& best, int& bi) {
-  best = -INFINITY;
-  bi = nd;
-  for (int n = lane; n < nd; n += WAVE) {
-    const float v = row[n];
-    if (v > best || (bi == nd && v == best)) { best = v; bi = n; }
-  }
-#pragma unroll
-  for (int k = WAVE / 2; k > 0; k >>= 1) {
-    const float ob = __shfl_xor(best, k, WAVE);
-    const int oi = __shfl_xor(bi, k, WAVE);
-    if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-  }
-  if (bi >= nd) bi = 0;
 }
 
 // One wave per virtual row: the argmax over num_dirs logits needs the whole row (any num_dirs)

@@ -815,6 +815,69 @@ int gsr_densify_split_children(int32_t P, const float* xyz, const float* scaling
   return check(nullptr, s, "densify_split_children");
 }
 
+size_t gsr_densify_fork_workspace_bytes(int32_t P) { return P < 0 ? 0 : DensifyForkLayout(P).bytes; }
+int gsr_densify_fork_plan(int32_t P, const float* xyz_gradient_accum, const float* denom, const float* scaling_raw,
+                          const float* opacity_raw, const float* split_scale_raw, float grad_threshold,
+                          float percent_dense_extent, float min_opacity, float max_world_scale, void* workspace,
+                          size_t workspace_bytes, uint32_t counts_host[5], void* stream) {
+  if (P < 0) return fail(GSR_E_BADARG, "P < 0");
+  if (!counts_host) return fail(GSR_E_BADARG, "NULL counts_host");
+  for (int k = 0; k < 5; ++k) counts_host[k] = 0;
+  if (P == 0) return 0;
+  if (!xyz_gradient_accum || !denom || !scaling_raw || !opacity_raw || !workspace) return fail(GSR_E_BADARG, "NULL input");
+  if (((uintptr_t)workspace & 255u) != 0) return fail(GSR_E_ALIGN, "workspace must be 256-byte aligned");
+  const DensifyForkLayout L(P);
+  if (workspace_bytes < L.bytes) return fail(GSR_E_CAPACITY, "densify_fork workspace too small");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_densify_fork_plan(P, xyz_gradient_accum, denom, scaling_raw, opacity_raw, split_scale_raw, grad_threshold,
+                           percent_dense_extent, min_opacity, max_world_scale, max_world_scale >= 0.0f ? 1 : 0,
+                           workspace, s);
+  if (int rc = check(nullptr, s, "densify_fork_plan")) return rc;
+  GSR_HIP(hipMemcpyAsync(counts_host, static_cast<char*>(workspace) + L.totals, 20, hipMemcpyDeviceToHost, s));
+  GSR_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+int gsr_densify_fork_gather_rows(int32_t P, int32_t row_floats, const float* src, const void* workspace,
+                                 const uint32_t counts[5], int32_t grow_branch, int32_t policy, float value, float* dst,
+                                 void* stream) {
+  if (P < 0 || row_floats <= 0) return fail(GSR_E_BADARG, "bad P / row_floats");
+  if (policy < 0 || policy >= 64 || (policy & 3) == 3 || ((policy >> 2) & 3) == 3 || ((policy >> 4) & 3) == 3)
+    return fail(GSR_E_BADARG, "bad row policy");
+  if (P == 0) return 0;
+  if (!src || !workspace || !counts) return fail(GSR_E_BADARG, "NULL argument");
+  if (!dst && counts[0] + counts[1] + counts[2] > 0) return fail(GSR_E_BADARG, "NULL dst");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_densify_fork_gather_rows(P, row_floats, src, workspace, counts, grow_branch ? 4 : 2, policy, value, dst, s);
+  return check(nullptr, s, "densify_fork_gather_rows");
+}
+int gsr_densify_fork_rows(const GsrDensifyFork* f, const void* workspace, const uint32_t counts[5], float* xyz_out,
+                          float* scaling_out, float* conti_dirs_out, void* stream) {
+  if (!f || !counts) return fail(GSR_E_BADARG, "NULL argument");
+  if (f->P < 0) return fail(GSR_E_BADARG, "P < 0");
+  if (f->P == 0 || counts[4] == 0 || counts[0] + counts[1] + counts[2] == 0) return 0;     // nothing to write
+  if (counts[4] > (uint32_t)f->P || counts[3] > counts[4] || counts[2] > counts[3])
+    return fail(GSR_E_BADARG, "counts do not come from gsr_densify_fork_plan of this P");
+  GsrDensifyFork g = *f;
+  const int grow = (g.mode & GSR_DENSIFY_GROW) != 0;
+  if (grow && ((g.mode & GSR_GROW_DIR) != 0) == ((g.mode & GSR_GROW_CONTINUOUS) != 0))
+    return fail(GSR_E_BADARG, "the grow branch needs exactly one of GSR_GROW_DIR and GSR_GROW_CONTINUOUS");
+  if (!g.xyz || !g.scaling || !g.rotation || !workspace || !xyz_out || !scaling_out)
+    return fail(GSR_E_BADARG, "NULL model tensor or output");
+  if (grow && (g.mode & GSR_GROW_DIR) && (!g.dirs_prob || !g.dirs || g.num_dirs <= 0))
+    return fail(GSR_E_BADARG, "GSR_GROW_DIR needs dirs_prob, dirs and num_dirs > 0");
+  if (grow && (g.mode & GSR_GROW_CONTINUOUS) && !g.conti_dirs) return fail(GSR_E_BADARG, "NULL conti_dirs");
+  if (grow && (g.mode & GSR_GROW_DISTANCE) && !g.grow_dist) return fail(GSR_E_BADARG, "NULL grow_dist");
+  if ((g.mode & GSR_SPLIT_DISTANCE) && !g.split_distance) return fail(GSR_E_BADARG, "NULL split_distance");
+  if ((g.mode & GSR_SPLIT_SCALE) && !g.split_scale) return fail(GSR_E_BADARG, "NULL split_scale");
+  if (!(g.mode & GSR_SPLIT_DISTANCE) && counts[3] > 0 && !g.noise) return fail(GSR_E_BADARG, "NULL noise");
+  if (conti_dirs_out && (!grow || !(g.mode & GSR_GROW_CONTINUOUS) || !g.dir_noise))
+    return fail(GSR_E_BADARG, "conti_dirs_out needs the continuous grow branch and dir_noise");
+  if (!(g.mode & GSR_SPLIT_SCALE)) g.split_scale = nullptr;     // the kernels read k = 1.6 from a NULL split_scale
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_densify_fork_rows(g, workspace, counts, xyz_out, scaling_out, conti_dirs_out, s);
+  return check(nullptr, s, "densify_fork_rows");
+}
+
 size_t gsr_grow_workspace_bytes(int32_t P) { return P < 0 ? 0 : GrowLayout(P).bytes; }
 int gsr_grow_plan(int32_t P, const float* xyz_gradient_accum, const float* denom, const float* scaling_raw,
                   float grad_threshold, float percent_dense_extent, int32_t mode, void* workspace, size_t workspace_bytes,

@@ -136,6 +136,20 @@ void launch_densify_split_children(int P, const float* xyz, const float* scaling
                                    const float* noise, const void* ws, const uint32_t counts[4], float* dst_xyz,
                                    float* dst_scaling, hipStream_t s);
 
+// densify_fork.hip.  counts = {kept originals, kept clones / grown, kept children per copy, split-selected, selected}
+struct DensifyForkLayout {
+  size_t flags, block_counts, block_offs, totals, pos, sel_src, bytes;
+  int nblocks;
+  explicit DensifyForkLayout(int P);
+};
+void launch_densify_fork_plan(int P, const float* accum, const float* denom, const float* scaling,
+                              const float* opacity, const float* split_scale, float thr, float pde, float min_opacity,
+                              float ws_limit, int use_ws, void* ws, hipStream_t s);
+void launch_densify_fork_gather_rows(int P, int w, const float* src, const void* ws, const uint32_t counts[5],
+                                     int ncopies, int policy, float value, float* dst, hipStream_t s);
+void launch_densify_fork_rows(const GsrDensifyFork& f, const void* ws, const uint32_t counts[5], float* xyz_out,
+                              float* scaling_out, float* conti_out, hipStream_t s);
+
 // knn.hip
 size_t knn_workspace_bytes(int N);
 void launch_knn3(const float* pts, int N, float* mean_dist2, void* ws, hipStream_t s);

@@ -24,7 +24,7 @@ from typing import Optional
 import torch
 from torch import nn
 
-from .densify import GROUP_ATTR
+from .densify import FORK_ATTR, GROUP_ATTR
 
 STATS_ATTR = ("xyz_gradient_accum", "denom", "max_radii2D")
 
@@ -58,7 +58,8 @@ def morton_permutation(xyz: torch.Tensor) -> torch.Tensor:
 def reorder_gaussians_(model, perm: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Permute every per-Gaussian tensor of a model in place: row i of the result is row ``perm[i]`` of the input
     (default: ``morton_permutation(model._xyz)``).  The model is duck-typed as in ``densify.py``: the six parameter
-    tensors, the densification statistics if present, and ``model.optimizer`` (one parameter per named group) if present,
+    tensors, the fork's learned tensors (``FORK_ATTR``) that have one row per Gaussian, the densification statistics if
+    present, and ``model.optimizer`` (one parameter per named group) if present,
     whose ``exp_avg`` / ``exp_avg_sq`` rows move with their Gaussians.  Returns the permutation."""
     xyz = model._xyz
     P = int(xyz.shape[0])
@@ -67,7 +68,12 @@ def reorder_gaussians_(model, perm: Optional[torch.Tensor] = None) -> torch.Tens
     perm = perm.to(device=xyz.device, dtype=torch.int64)
     if perm.shape != (P,) or (P and not torch.equal(torch.sort(perm).values, torch.arange(P, device=perm.device))):
         raise ValueError(f"perm must be a permutation of range({P})")
-    new = {k: getattr(model, a).detach()[perm].contiguous() for k, a in GROUP_ATTR.items()}
+    attrs = dict(GROUP_ATTR)
+    for k, a in FORK_ATTR.items():
+        t = getattr(model, a, None)
+        if isinstance(t, torch.Tensor) and t.dim() >= 1 and t.shape[0] == P and P > 0:
+            attrs[k] = a
+    new = {k: getattr(model, a).detach()[perm].contiguous() for k, a in attrs.items()}
     optimizer = getattr(model, "optimizer", None)
     owned = set()
     if optimizer is not None:
@@ -86,7 +92,7 @@ def reorder_gaussians_(model, perm: Optional[torch.Tensor] = None) -> torch.Tens
                 optimizer.state[group["params"][0]] = stored
             new[name] = group["params"][0]
             owned.add(name)
-    for k, a in GROUP_ATTR.items():
+    for k, a in attrs.items():
         t, old = new[k], getattr(model, a)
         if k not in owned:
             t = nn.Parameter(t, requires_grad=old.requires_grad) if isinstance(old, nn.Parameter) \
