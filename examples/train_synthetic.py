@@ -15,11 +15,13 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from mvs_gaussian_splatting_amd import render, l1_dssim_loss, add_densification_stats  # noqa: E402
 from mvs_gaussian_splatting_amd.densify import densify_and_prune, GROUP_ATTR  # noqa: E402
+from mvs_gaussian_splatting_amd.optim import Adam  # noqa: E402
 from mvs_gaussian_splatting_amd.synthetic import SyntheticGaussianModel, PipelineParams, orbit_camera  # noqa: E402
 
 
-def make_problem(dev, P=4000, W=256, H=160, n_views=8, seed=0):
-    """(ground-truth images per view, cameras, trainable model)."""
+def make_problem(dev, P=4000, W=256, H=160, n_views=8, seed=0, optimizer="torch"):
+    """(ground-truth images per view, cameras, trainable model).  optimizer: "torch" (torch.optim.Adam, as the reference)
+    or "hip" (mvs_gaussian_splatting_amd.optim.Adam: the same step in one HIP launch, bit-identical)."""
     gt = SyntheticGaussianModel(P, 3, seed=seed, log_scale_mean=math.log(0.06), extent=(1.6, 1.0, 0.8), centre=(0, 0, 4.0))
     gt._opacity += 1.0
     gt.to(dev)
@@ -43,18 +45,22 @@ def make_problem(dev, P=4000, W=256, H=160, n_views=8, seed=0):
     # arguments/__init__.py:85-92 (position_lr_init * spatial_lr_scale, feature_lr, feature_lr / 20, opacity_lr,
     # scaling_lr, rotation_lr); the colours get a larger step because this toy starts from forgotten colours
     lrs = {"xyz": 1.6e-4, "f_dc": 2e-2, "f_rest": 1e-3, "opacity": 0.05, "scaling": 5e-3, "rotation": 1e-3}
-    model.optimizer = torch.optim.Adam([{"params": [getattr(model, a)], "lr": lrs[k], "name": k}
-                                        for k, a in GROUP_ATTR.items()], lr=0.0, eps=1e-15)
+    if optimizer not in ("torch", "hip"):
+        raise ValueError(f"optimizer must be 'torch' or 'hip', got {optimizer!r}")
+    adam = torch.optim.Adam if optimizer == "torch" else Adam
+    model.optimizer = adam([{"params": [getattr(model, a)], "lr": lrs[k], "name": k}
+                            for k, a in GROUP_ATTR.items()], lr=0.0, eps=1e-15)
     pipe.fuse_densify_stats = True      # the backward takes the densification statistics; add_densification_stats below
                                         # stays where the reference has it and recognises such a frame
     return targets, cams, bg, pipe, model
 
 
 def train(dev, iterations=60, densification_interval=20, densify_from_iter=10, extent=2.0, grad_threshold=0.0006, log=None,
-          spatial_order=False):
+          spatial_order=False, optimizer="torch"):
     """spatial_order: after every densification the cloud (and the Adam moments) is stored along a Morton curve
-    (mvs_gaussian_splatting_amd/layout.py) instead of the reference's [kept | clones | children] order."""
-    targets, cams, bg, pipe, model = make_problem(dev)
+    (mvs_gaussian_splatting_amd/layout.py) instead of the reference's [kept | clones | children] order.
+    optimizer: see make_problem."""
+    targets, cams, bg, pipe, model = make_problem(dev, optimizer=optimizer)
     history, sizes = [], []
     for it in range(1, iterations + 1):
         v = (it * 3) % len(cams)

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 15
+#define GSR_ABI_VERSION 16
 
 enum {
   GSR_OK = 0,
@@ -432,6 +432,40 @@ int gsr_densify_fork_gather_rows(int32_t P, int32_t row_floats, const float* src
                                  void* stream);
 int gsr_densify_fork_rows(const GsrDensifyFork* f, const void* workspace, const uint32_t counts[5], float* xyz_out,
                           float* scaling_out, float* conti_dirs_out, void* stream);
+
+/* One Adam step over up to GSR_ADAM_MAX_TENSORS tensors in one launch, ABI v16: the update of torch.optim.Adam's
+ * default (`foreach`) path, `_multi_tensor_adam` with weight_decay = 0, amsgrad = maximize = capturable = False, as the
+ * reference's `gaussians.optimizer.step()` runs it (train.py:136-139; optimizer built at scene/gaussian_model.py:264).
+ * Per element, each line one torch op with its own float32 rounding:
+ *     exp_avg    = lerp(exp_avg, grad, lerp_weight)            (ATen/native/Lerp.h, small-weight branch for |w| < 0.5)
+ *     exp_avg_sq = exp_avg_sq * beta2
+ *     exp_avg_sq = exp_avg_sq + sq_weight * (grad * grad)       (addcmul)
+ *     d = sqrt(exp_avg_sq);  d = d / bc2_sqrt;  d = d + eps
+ *     param      = param + step_size * (exp_avg / d)            (addcdiv)
+ * The scalars are torch's, computed by the caller in double and converted to float: lerp_weight = 1 - beta1,
+ * sq_weight = 1 - beta2, bc2_sqrt = (1 - beta2**step) ** 0.5, step_size = -(lr / (1 - beta1**step)), step the
+ * tensor's own count after its increment.  All four arrays are contiguous fp32 with `numel` elements and must not
+ * overlap; any alignment (16-byte aligned tensors take 16-byte accesses).  Entries with numel = 0 are skipped.
+ * Returns GSR_E_BADARG for a NULL batch, count outside 0..GSR_ADAM_MAX_TENSORS, a negative numel or a NULL array of a
+ * non-empty entry.  No host synchronisation. */
+#define GSR_ADAM_MAX_TENSORS 16
+
+typedef struct GsrAdamTensor {
+  float* param;                                /* device [numel], updated in place */
+  const float* grad;                           /* device [numel] */
+  float* exp_avg;                              /* device [numel], updated in place */
+  float* exp_avg_sq;                           /* device [numel], updated in place */
+  int64_t numel;
+  float lerp_weight, beta2, sq_weight, bc2_sqrt, eps, step_size;
+} GsrAdamTensor;
+
+typedef struct GsrAdamBatch {
+  int32_t count;                               /* entries of t[] in use */
+  int32_t reserved;                            /* 0 */
+  GsrAdamTensor t[GSR_ADAM_MAX_TENSORS];
+} GsrAdamBatch;
+
+int gsr_adam_step(const GsrAdamBatch* batch, void* stream);
 
 #ifdef __cplusplus
 }

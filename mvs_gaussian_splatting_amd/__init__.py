@@ -7,6 +7,7 @@ from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, rast
                          rasterize_gaussians_fused)
 from .renderer import render  # noqa: F401
 from .losses import l1_loss, l1_dssim_loss, add_densification_stats  # noqa: F401
+from .optim import Adam  # noqa: F401
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "render", "l1_loss", "l1_dssim_loss",
-           "add_densification_stats"]
+           "add_densification_stats", "Adam"]

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # instead of copying it over the in-tree library
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 
 class GsrParams(C.Structure):
@@ -74,6 +74,19 @@ ACT_SCALE_EXP, ACT_ROT_NORMALIZE, ACT_OPACITY_SIGMOID = 1, 2, 4
 BINNING_TWO_LEVEL, BINNING_KEYS64, BINNING_TWO_LEVEL_CULLED = 0, 1, 2
 DSSIM_ONE_MINUS_MEAN, DSSIM_CLAMPED_HALF = 0, 1
 DEBUG_NO_MINIBLOCK_CULL = 1
+
+
+ADAM_MAX_TENSORS = 16
+
+
+class GsrAdamTensor(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("numel", C.c_int64)] + [
+        (n, C.c_float) for n in ("lerp_weight", "beta2", "sq_weight", "bc2_sqrt", "eps", "step_size")]
+
+
+class GsrAdamBatch(C.Structure):
+    _fields_ = [("count", C.c_int32), ("reserved", C.c_int32), ("t", GsrAdamTensor * ADAM_MAX_TENSORS)]
 
 
 # name -> (restype, argtypes); every symbol include/gsr.h declares
@@ -148,6 +161,8 @@ SYMBOLS = {
     "gsr_stage_name": (C.c_char_p, [C.c_int32]),
     "gsr_densify_stats": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
+    # torch.optim.Adam's foreach step over up to ADAM_MAX_TENSORS tensors in one launch (optim.py)
+    "gsr_adam_step": (C.c_int, [C.POINTER(GsrAdamBatch), C.c_void_p]),
 }
 
 _lib = None

@@ -955,4 +955,19 @@ int gsr_grow_fold(const GsrGrow* g, const GsrGrowGrads* grads, void* stream) {
   return check(nullptr, s, "grow_fold");
 }
 
+int gsr_adam_step(const GsrAdamBatch* batch, void* stream) {
+  if (!batch) return fail(GSR_E_BADARG, "NULL batch");
+  if (batch->count < 0 || batch->count > GSR_ADAM_MAX_TENSORS)
+    return fail(GSR_E_BADARG, "count must be 0..GSR_ADAM_MAX_TENSORS");
+  for (int k = 0; k < batch->count; ++k) {
+    const GsrAdamTensor& t = batch->t[k];
+    if (t.numel < 0) return fail(GSR_E_BADARG, "negative numel");
+    if (t.numel > 0 && (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq))
+      return fail(GSR_E_BADARG, "NULL param / grad / exp_avg / exp_avg_sq");
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (launch_adam_step(*batch, s)) return fail(GSR_E_BADARG, "batch too large for one launch (more than 2^32 work-items)");
+  return check(nullptr, s, "adam_step");
+}
+
 }  // extern "C"

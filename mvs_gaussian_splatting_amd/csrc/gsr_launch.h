@@ -150,6 +150,10 @@ void launch_densify_fork_gather_rows(int P, int w, const float* src, const void*
 void launch_densify_fork_rows(const GsrDensifyFork& f, const void* ws, const uint32_t counts[5], float* xyz_out,
                               float* scaling_out, float* conti_out, hipStream_t s);
 
+// adam.hip: one launch over the batch's tensors; returns nonzero (nothing enqueued) if the grid would exceed 2^32
+// work-items
+int launch_adam_step(const GsrAdamBatch& batch, hipStream_t s);
+
 // knn.hip
 size_t knn_workspace_bytes(int N);
 void launch_knn3(const float* pts, int N, float* mean_dist2, void* ws, hipStream_t s);

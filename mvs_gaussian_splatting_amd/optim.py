@@ -1,0 +1,203 @@
+"""The reference's optimizer on the HIP path: ``torch.optim.Adam(l, lr=0.0, eps=1e-15)`` of ``training_setup``
+(``scene/gaussian_model.py:240-268``), stepped at ``train.py:136-139``, and its learning-rate schedule
+(``utils/general_utils.py:29-62``, ``scene/gaussian_model.py:271-277``).
+
+``Adam`` is a drop-in for ``torch.optim.Adam`` whose ``step()`` is one launch of ``csrc/adam.hip`` per 16 tensors
+(``gsr_adam_step``) instead of torch's ~8 ``_foreach_*`` passes.  It gives the bits of torch's default (``foreach``)
+path for float32 and keeps torch's state layout -- ``{"step": float32 CPU tensor, "exp_avg", "exp_avg_sq"}`` per
+parameter -- so the code that edits ``optimizer.state`` (``densify.densify_and_prune``, ``layout.reorder_gaussians_``,
+the reference's ``replace_tensor_to_optimizer`` / ``_prune_optimizer``) and ``state_dict()`` work unchanged, in both
+directions.  It covers what the reference uses: no weight decay, amsgrad, maximize, capturable, differentiable or fused
+variants (``ValueError``), and float32 contiguous parameters on a ROCm GPU (no CPU path).
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, List, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from .densify import FORK_ATTR, FORK_FLAG, GROUP_ATTR
+
+_UNSUPPORTED = ("weight_decay", "amsgrad", "maximize", "capturable", "differentiable", "fused", "decoupled_weight_decay")
+
+
+def _scalar_dtype():
+    # torch.optim.optimizer._get_scalar_dtype(): the dtype of torch's CPU "step" tensors
+    return torch.float64 if torch.get_default_dtype() == torch.float64 else torch.float32
+
+
+def _check_group(group) -> None:
+    for key in _UNSUPPORTED:
+        if group.get(key):
+            raise ValueError(f"mvs_gaussian_splatting_amd.optim.Adam does not support {key}={group[key]!r} "
+                             "(the reference's Adam uses none of them)")
+
+
+def adam_scalars(lr: float, betas: Tuple[float, float], eps: float, step: float) -> Dict[str, float]:
+    """The per-tensor scalars of one step as ``_multi_tensor_adam`` computes them (in double, ``step`` the count after
+    its increment); ``gsr_adam_step`` receives each converted to float, where torch's foreach kernels convert them."""
+    beta1, beta2 = betas
+    bias_correction1 = 1 - beta1 ** step
+    bias_correction2 = 1 - beta2 ** step
+    return {"lerp_weight": 1 - beta1, "beta2": beta2, "sq_weight": 1 - beta2, "bc2_sqrt": bias_correction2 ** 0.5,
+            "eps": eps, "step_size": (lr / bias_correction1) * -1}
+
+
+class Adam(torch.optim.Optimizer):
+    """``torch.optim.Adam`` with the update of ``csrc/adam.hip``: same signature, state and results (bit for bit
+    against torch's default ``foreach`` step on float32).  ``foreach`` is accepted and ignored."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, foreach=None,
+                 maximize=False, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False):
+        if isinstance(lr, torch.Tensor):
+            if lr.numel() != 1:
+                raise ValueError("Tensor lr must be 1-element")
+            lr = lr.item()
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        betas = tuple(float(b) for b in betas)
+        defaults = {"lr": lr, "betas": betas, "eps": eps, "weight_decay": weight_decay, "amsgrad": amsgrad,
+                    "maximize": maximize, "foreach": foreach, "capturable": capturable,
+                    "differentiable": differentiable, "fused": fused, "decoupled_weight_decay": decoupled_weight_decay}
+        _check_group(defaults)
+        super().__init__(params, defaults)
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        for group in self.param_groups:
+            for key, default in (("weight_decay", 0), ("amsgrad", False), ("maximize", False), ("foreach", None),
+                                 ("capturable", False), ("differentiable", False), ("fused", None),
+                                 ("decoupled_weight_decay", False)):
+                group.setdefault(key, default)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        """One Adam step of every parameter whose ``.grad`` is not None (the others keep their step count and
+        moments), enqueued on the current stream of the parameters' device; no host synchronisation."""
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        todo = []                                                    # every check before any state changes
+        for group in self.param_groups:
+            _check_group(group)
+            lr = group["lr"]
+            lr = lr.item() if isinstance(lr, torch.Tensor) else float(lr)
+            betas = tuple(b.item() if isinstance(b, torch.Tensor) else float(b) for b in group["betas"])
+            eps = float(group["eps"])
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if not p.is_cuda:
+                    raise _lib.GsrError("Adam.step needs ROCm GPU parameters (no CPU path)")
+                if p.dtype != torch.float32 or p.grad.dtype != torch.float32:
+                    raise TypeError(f"Adam.step supports float32 parameters and gradients, got {p.dtype} / "
+                                    f"{p.grad.dtype}")
+                if p.is_sparse or p.grad.is_sparse:
+                    raise RuntimeError("Adam does not support sparse gradients")
+                if not p.is_contiguous():
+                    raise ValueError("Adam.step needs contiguous parameters")
+                for name in ("exp_avg", "exp_avg_sq"):
+                    t = self.state[p].get(name) if p in self.state else None
+                    if t is not None and (t.device != p.device or t.dtype != torch.float32 or t.numel() != p.numel()
+                                          or not t.is_contiguous()):
+                        raise ValueError(f"state[{name!r}] must be a contiguous float32 tensor like its parameter")
+                todo.append((p, lr, betas, eps))
+        per_device: Dict[torch.device, List[Tuple]] = {}
+        for p, lr, betas, eps in todo:
+            grad = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+            state = self.state[p]
+            if len(state) == 0:                                      # torch's _init_group, capturable = fused = False
+                state["step"] = torch.tensor(0.0, dtype=_scalar_dtype())
+                state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            state["step"] += 1
+            per_device.setdefault(p.device, []).append(
+                (p, grad, state["exp_avg"], state["exp_avg_sq"], adam_scalars(lr, betas, eps, state["step"].item())))
+        lib = _lib.load() if per_device else None
+        for dev, items in per_device.items():
+            with torch.cuda.device(dev):
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                for first in range(0, len(items), _lib.ADAM_MAX_TENSORS):
+                    chunk = items[first:first + _lib.ADAM_MAX_TENSORS]
+                    batch = _lib.GsrAdamBatch()
+                    batch.count = len(chunk)
+                    for e, (p, g, m, v, sc) in zip(batch.t, chunk):
+                        e.param, e.grad, e.exp_avg, e.exp_avg_sq = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()
+                        e.numel = p.numel()
+                        for k, val in sc.items():
+                            setattr(e, k, val)
+                    _lib.check(lib.gsr_adam_step(C.byref(batch), stream), "gsr_adam_step")
+        return loss
+
+
+def expon_lr_func(lr_init, lr_final, lr_delay_steps=0, lr_delay_mult=1.0, max_steps=1000000):
+    """``get_expon_lr_func`` (``utils/general_utils.py:29-62``): log-linear decay from ``lr_init`` at step 0 to
+    ``lr_final`` at ``max_steps``, eased in over ``lr_delay_steps`` from ``lr_init * lr_delay_mult``."""
+    def helper(step):
+        if step < 0 or (lr_init == 0.0 and lr_final == 0.0):
+            return 0.0
+        if lr_delay_steps > 0:
+            delay_rate = lr_delay_mult + (1 - lr_delay_mult) * np.sin(0.5 * np.pi * np.clip(step / lr_delay_steps, 0, 1))
+        else:
+            delay_rate = 1.0
+        t = np.clip(step / max_steps, 0, 1)
+        log_lerp = np.exp(np.log(lr_init) * (1 - t) + np.log(lr_final) * t)
+        return delay_rate * log_lerp
+    return helper
+
+
+def param_groups(model, opt) -> List[dict]:
+    """The group list ``l`` of ``training_setup`` (``:244-262``): the six plain groups, then the fork's groups whose
+    model flags are set (``densify.FORK_FLAG``), in the reference's order."""
+    lrs = {"xyz": opt.position_lr_init * model.spatial_lr_scale, "f_dc": opt.feature_lr,
+           "f_rest": opt.feature_lr / 20.0, "opacity": opt.opacity_lr, "scaling": opt.scaling_lr,
+           "rotation": opt.rotation_lr}
+    fork_lr = {"dirs_prob": "growdirs_lr", "conti_dirs": "growdirs_lr", "grow_dist": "growdistance_lr",
+               "split_distance": "splitdistance_lr", "split_scale": "splitscale_lr"}
+    groups = [{"params": [getattr(model, a)], "lr": lrs[k], "name": k} for k, a in GROUP_ATTR.items()]
+    for k, a in FORK_ATTR.items():
+        if getattr(model, FORK_FLAG[k], False):
+            groups.append({"params": [getattr(model, a)], "lr": getattr(opt, fork_lr[k]), "name": k})
+    return groups
+
+
+def training_setup(model, opt, optimizer_cls=Adam):
+    """``GaussianModel.training_setup(training_args)`` (``scene/gaussian_model.py:240-268``) with this module's
+    ``Adam``: sets ``percent_dense``, zeroed ``xyz_gradient_accum`` / ``denom`` ``[P, 1]`` on the model's device,
+    ``optimizer`` (``lr=0.0, eps=1e-15``) and ``xyz_scheduler_args``.  Returns the optimizer."""
+    model.percent_dense = opt.percent_dense
+    P, dev = model._xyz.shape[0], model._xyz.device
+    model.xyz_gradient_accum = torch.zeros((P, 1), device=dev)
+    model.denom = torch.zeros((P, 1), device=dev)
+    model.optimizer = optimizer_cls(param_groups(model, opt), lr=0.0, eps=1e-15)
+    model.xyz_scheduler_args = expon_lr_func(lr_init=opt.position_lr_init * model.spatial_lr_scale,
+                                             lr_final=opt.position_lr_final * model.spatial_lr_scale,
+                                             lr_delay_mult=opt.position_lr_delay_mult,
+                                             max_steps=opt.position_lr_max_steps)
+    return model.optimizer
+
+
+def update_learning_rate(model, iteration):
+    """``GaussianModel.update_learning_rate`` (``:271-277``): the ``xyz`` group's lr from ``xyz_scheduler_args``;
+    returns it (None without an ``xyz`` group)."""
+    for group in model.optimizer.param_groups:
+        if group["name"] == "xyz":
+            lr = model.xyz_scheduler_args(iteration)
+            group["lr"] = lr
+            return lr
+    return None
+
+
+__all__ = ["Adam", "adam_scalars", "expon_lr_func", "param_groups", "training_setup", "update_learning_rate"]
