@@ -16,6 +16,7 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from mvs_gaussian_splatting_amd.graphed import GraphedRenderer  # noqa: E402
 from mvs_gaussian_splatting_amd.layout import reorder_gaussians_  # noqa: E402
+from mvs_gaussian_splatting_amd.metrics import to_uint8_hwc  # noqa: E402
 from mvs_gaussian_splatting_amd.ply_io import load_ply  # noqa: E402
 from mvs_gaussian_splatting_amd.synthetic import PipelineParams, orbit_camera  # noqa: E402
 
@@ -39,7 +40,7 @@ class PlyModel:
 
 def write_ppm(path, image):
     """image: [3, H, W] in [0, 1] -> binary PPM (P6)."""
-    img = (image.clamp(0.0, 1.0) * 255.0 + 0.5).to(torch.uint8).permute(1, 2, 0).contiguous().cpu().numpy()
+    img = to_uint8_hwc(image, "nearest").cpu().numpy()      # (clamp(x, 0, 1) * 255 + 0.5) truncated, HWC, in one kernel
     with open(path, "wb") as f:
         f.write(f"P6\n{img.shape[1]} {img.shape[0]}\n255\n".encode())
         f.write(img.tobytes())

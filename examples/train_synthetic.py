@@ -13,7 +13,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from mvs_gaussian_splatting_amd import render, l1_dssim_loss, add_densification_stats  # noqa: E402
+from mvs_gaussian_splatting_amd import render, l1_dssim_loss, add_densification_stats, evaluate_views  # noqa: E402
 from mvs_gaussian_splatting_amd.densify import densify_and_prune, GROUP_ATTR  # noqa: E402
 from mvs_gaussian_splatting_amd.optim import Adam  # noqa: E402
 from mvs_gaussian_splatting_amd.synthetic import SyntheticGaussianModel, PipelineParams, orbit_camera  # noqa: E402
@@ -55,12 +55,28 @@ def make_problem(dev, P=4000, W=256, H=160, n_views=8, seed=0, optimizer="torch"
     return targets, cams, bg, pipe, model
 
 
+def make_held_out(dev, P=4000, W=256, H=160, n_views=4, seed=0):
+    """Cameras half-way between the training views with the ground-truth cloud's images in ``original_image`` (where the
+    reference's cameras keep theirs): the test set of the optional report."""
+    gt = SyntheticGaussianModel(P, 3, seed=seed, log_scale_mean=math.log(0.06), extent=(1.6, 1.0, 0.8), centre=(0, 0, 4.0))
+    gt._opacity += 1.0
+    gt.to(dev)
+    cams = [orbit_camera(2 * v + 1, 2 * n_views, W, H, 220.0, 220.0, centre=(0.0, 0.0, 4.0), device=dev) for v in range(n_views)]
+    with torch.no_grad():
+        for c in cams:
+            c.original_image = render(c, gt, PipelineParams(), torch.zeros(3, device=dev))["render"].clone()
+    return cams
+
+
 def train(dev, iterations=60, densification_interval=20, densify_from_iter=10, extent=2.0, grad_threshold=0.0006, log=None,
-          spatial_order=False, optimizer="torch"):
+          spatial_order=False, optimizer="torch", report_every=0):
     """spatial_order: after every densification the cloud (and the Adam moments) is stored along a Morton curve
     (mvs_gaussian_splatting_amd/layout.py) instead of the reference's [kept | clones | children] order.
-    optimizer: see make_problem."""
+    optimizer: see make_problem.
+    report_every: every so many iterations (0: never) the held-out views are evaluated as train.py:217-232 does, in
+    fused passes accumulated on the device (evaluate_views), and L1 / PSNR are logged."""
     targets, cams, bg, pipe, model = make_problem(dev, optimizer=optimizer)
+    test_cams = make_held_out(dev) if report_every else []
     history, sizes = [], []
     for it in range(1, iterations + 1):
         v = (it * 3) % len(cams)
@@ -76,6 +92,10 @@ def train(dev, iterations=60, densification_interval=20, densify_from_iter=10, e
                 sizes.append(info["points"])
                 if log:
                     log(f"  iteration {it}: densify_and_prune -> {info}")
+        if report_every and it % report_every == 0:
+            rep = evaluate_views(test_cams, model, PipelineParams(), bg)
+            if log:
+                log(f"\n[ITER {it}] Evaluating test: L1 {rep['l1']} PSNR {rep['psnr']}")
         history.append(float(loss.detach()))
         if log and it % 10 == 0:
             log(f"iteration {it}: loss {history[-1]:.5f}  points {model._xyz.shape[0]}")

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 16
+#define GSR_ABI_VERSION 17
 
 enum {
   GSR_OK = 0,
@@ -268,6 +268,38 @@ int gsr_l1_loss_fwd_bwd(const float* x, const float* gt, size_t n, float scale, 
 size_t gsr_l1_dssim_workspace_bytes(int32_t C, int32_t H, int32_t W);
 int gsr_l1_dssim_loss_fwd_bwd(const float* x, const float* gt, int32_t C, int32_t H, int32_t W, float lambda_dssim,
                               int32_t dssim_mode, float* sums, float* dL_dx, void* workspace, void* stream);
+
+/* ---- per-view evaluation (train.py:210-235 training_report, metrics.py:71-78, render.py / train.py:63) ------------
+ * gsr_eval_image: one streaming read of x, gt (device, [3,H,W] float32, contiguous) gives the view's L1, PSNR and, with
+ * GSR_EVAL_SSIM, its SSIM (the training loss' 11x11 window, forward only: no derivative maps), and optionally the 8-bit
+ * [H,W,3] image of x.  flags:
+ *   GSR_EVAL_CLAMP_X / GSR_EVAL_CLAMP_GT  clamp that image to [0, 1] on load (training_report clamps both);
+ *   GSR_EVAL_SSIM                         also run the SSIM tile kernel (same clamps);
+ *   GSR_EVAL_PSNR_WHOLE                   PSNR of the whole image (psnr() of a [1,3,H,W] batch, metrics.py) instead of
+ *                                         the mean of the three per-channel values (psnr() of a [3,H,W] image,
+ *                                         training_report): the rows of utils/image_utils.py:18 view(shape[0], -1);
+ *   GSR_EVAL_U8_TRUNCATE                  u8_out = (clamp(x,0,1) * 255) truncated (train.py:63); default
+ *                                         (clamp(x,0,1) * 255 + 0.5) truncated (torchvision save_image).  The bytes
+ *                                         always come from clamp(x, 0, 1), whatever GSR_EVAL_CLAMP_X says.
+ * view_out (device float[GSR_EVAL_VIEW_FLOATS], or NULL): l1, psnr, ssim (0 without GSR_EVAL_SSIM), sum|d| of the three
+ *   channels, sum d^2 of the three channels, PSNR of the three channels.  psnr = 20 log10(1 / sqrt(mse)): +inf for
+ *   mse == 0, as the reference.
+ * acc (device double[4], or NULL): {sum l1, sum psnr, sum ssim, views} += this view, in double before the rounding to
+ *   float32 -- the reference's .double() running sums; the caller zero-fills it once and reads it back once per report.
+ * u8_out (device uint8 [H,W,3], or NULL).  workspace: gsr_eval_workspace_bytes(C, H, W, flags) bytes of device scratch
+ * for the per-block partial sums, which are added in a fixed order in double (no atomics: bitwise reproducible).
+ * C must be 3.  Asynchronous on `stream`; nothing is allocated; arguments are checked before any HIP call.
+ * gsr_image_to_u8: the conversion alone (flags: 0 or GSR_EVAL_U8_TRUNCATE); same bytes as the fused output. */
+#define GSR_EVAL_CLAMP_X 1
+#define GSR_EVAL_CLAMP_GT 2
+#define GSR_EVAL_SSIM 4
+#define GSR_EVAL_PSNR_WHOLE 8
+#define GSR_EVAL_U8_TRUNCATE 16
+#define GSR_EVAL_VIEW_FLOATS 12
+size_t gsr_eval_workspace_bytes(int32_t C, int32_t H, int32_t W, int32_t flags);
+int gsr_eval_image(const float* x, const float* gt, int32_t C, int32_t H, int32_t W, int32_t flags, float* view_out,
+                   double* acc, uint8_t* u8_out, void* workspace, void* stream);
+int gsr_image_to_u8(const float* x, int32_t C, int32_t H, int32_t W, int32_t flags, uint8_t* u8_out, void* stream);
 
 /* BASELINE config 1: `generate_2D_gaussian_splatting(kernel_size, sigma_x, sigma_y, rho, coords, colours, image_size)`
  * (2D-Gaussian-Splatting-main/2d_gaussian_splatting.py:44-123) without the N x 3 x H x W intermediate.

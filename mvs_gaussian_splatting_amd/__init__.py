@@ -8,6 +8,8 @@ from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, rast
 from .renderer import render  # noqa: F401
 from .losses import l1_loss, l1_dssim_loss, add_densification_stats  # noqa: F401
 from .optim import Adam  # noqa: F401
+from .metrics import psnr, ssim, image_metrics, to_uint8_hwc, EvalAccumulator, evaluate_views  # noqa: F401
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "render", "l1_loss", "l1_dssim_loss",
-           "add_densification_stats", "Adam"]
+           "add_densification_stats", "Adam", "psnr", "ssim", "image_metrics", "to_uint8_hwc", "EvalAccumulator",
+           "evaluate_views"]

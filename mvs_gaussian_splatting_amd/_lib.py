@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # instead of copying it over the in-tree library
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 
 class GsrParams(C.Structure):
@@ -74,6 +74,9 @@ ACT_SCALE_EXP, ACT_ROT_NORMALIZE, ACT_OPACITY_SIGMOID = 1, 2, 4
 BINNING_TWO_LEVEL, BINNING_KEYS64, BINNING_TWO_LEVEL_CULLED = 0, 1, 2
 DSSIM_ONE_MINUS_MEAN, DSSIM_CLAMPED_HALF = 0, 1
 DEBUG_NO_MINIBLOCK_CULL = 1
+# gsr_eval_image flags and the floats of its per-view record (l1, psnr, ssim, 3 x sum|d|, 3 x sum d^2, 3 x psnr_c)
+EVAL_CLAMP_X, EVAL_CLAMP_GT, EVAL_SSIM, EVAL_PSNR_WHOLE, EVAL_U8_TRUNCATE = 1, 2, 4, 8, 16
+EVAL_VIEW_FLOATS = 12
 
 
 ADAM_MAX_TENSORS = 16
@@ -129,6 +132,10 @@ SYMBOLS = {
     "gsr_l1_dssim_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "gsr_l1_dssim_loss_fwd_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                             C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # per-view evaluation (metrics.py): L1 / PSNR / SSIM + 8-bit image in one pass, accumulated on the device
+    "gsr_eval_workspace_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "gsr_eval_image": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p] * 5),
+    "gsr_image_to_u8": (C.c_int, [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p]),
     "gsr_splat2d_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "gsr_splat2d_forward": (C.c_int, [C.c_int32] * 4 + [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p,
                                       C.POINTER(C.c_int32), C.c_void_p]),

@@ -705,6 +705,37 @@ int gsr_l1_dssim_loss_fwd_bwd(const float* x, const float* gt, int32_t C, int32_
   return check(nullptr, s, "l1_dssim");
 }
 
+static const int32_t kEvalFlags = GSR_EVAL_CLAMP_X | GSR_EVAL_CLAMP_GT | GSR_EVAL_SSIM | GSR_EVAL_PSNR_WHOLE |
+                                  GSR_EVAL_U8_TRUNCATE;
+size_t gsr_eval_workspace_bytes(int32_t C, int32_t H, int32_t W, int32_t flags) {
+  if (C != 3 || H <= 0 || W <= 0 || (flags & ~kEvalFlags)) return 0;
+  return sizeof(float) * (6 * (size_t)EVAL_MAX_BLOCKS + ((flags & GSR_EVAL_SSIM) ? eval_ssim_blocks(H, W) : 0));
+}
+int gsr_eval_image(const float* x, const float* gt, int32_t C, int32_t H, int32_t W, int32_t flags, float* view_out,
+                   double* acc, uint8_t* u8_out, void* workspace, void* stream) {
+  if (!x || !gt) return fail(GSR_E_BADARG, "NULL image");
+  if (!workspace) return fail(GSR_E_BADARG, "NULL workspace");
+  if (!view_out && !acc && !u8_out) return fail(GSR_E_BADARG, "no output: view_out, acc and u8_out are all NULL");
+  if (H <= 0 || W <= 0) return fail(GSR_E_BADARG, "bad image shape");
+  if (C != 3) return fail(GSR_E_BADARG, "evaluation needs a 3-channel image");
+  if (flags & ~kEvalFlags) return fail(GSR_E_BADARG, "unknown evaluation flag bits");
+  if ((((uintptr_t)x | (uintptr_t)gt | (uintptr_t)view_out | (uintptr_t)workspace) & 3u) != 0 || ((uintptr_t)acc & 7u) != 0)
+    return fail(GSR_E_ALIGN, "images, view_out and workspace must be 4-byte aligned, acc 8-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_eval_image(x, gt, H, W, flags, view_out, acc, u8_out, static_cast<float*>(workspace), s);
+  return check(nullptr, s, "eval_image");
+}
+int gsr_image_to_u8(const float* x, int32_t C, int32_t H, int32_t W, int32_t flags, uint8_t* u8_out, void* stream) {
+  if (!x || !u8_out) return fail(GSR_E_BADARG, "NULL image");
+  if (H <= 0 || W <= 0) return fail(GSR_E_BADARG, "bad image shape");
+  if (C != 3) return fail(GSR_E_BADARG, "the 8-bit output needs a 3-channel image");
+  if (flags & ~GSR_EVAL_U8_TRUNCATE) return fail(GSR_E_BADARG, "unknown conversion flag bits");
+  if (((uintptr_t)x & 3u) != 0) return fail(GSR_E_ALIGN, "image must be 4-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_eval_image(x, nullptr, H, W, flags, nullptr, nullptr, u8_out, nullptr, s);
+  return check(nullptr, s, "image_to_u8");
+}
+
 size_t gsr_splat2d_workspace_bytes(int32_t N, int32_t H, int32_t W) {
   return (N < 0 || H <= 0 || W <= 0) ? 0 : Splat2dLayout(N, H, W).bytes;
 }

@@ -98,6 +98,16 @@ void launch_render_bwd(int W, int H, const uint2* ranges, const uint32_t* point_
 void launch_l1_dssim(const float* x, const float* gt, int C, int H, int W, float lambda, int dssim_mode, float* sums,
                      float* dL_dx, float* maps, hipStream_t s);
 
+// forward-only SSIM of the evaluation path: one partial per 16x16 tile and channel, no derivative maps
+void launch_ssim_metric(const float* x, const float* gt, int C, int H, int W, int clamp_flags, float* partials,
+                        hipStream_t s);
+
+// metrics.hip: gt == nullptr converts only.  workspace: 6 floats per streaming block, then eval_ssim_blocks floats
+constexpr int EVAL_MAX_BLOCKS = 2048;
+size_t eval_ssim_blocks(int H, int W);
+void launch_eval_image(const float* x, const float* gt, int H, int W, int flags, float* view, double* acc, uint8_t* u8,
+                       float* workspace, hipStream_t s);
+
 // splat2d.hip (BASELINE config 1)
 struct Splat2dLayout {
   size_t rec, flag, pre, gmask, partial, bytes;

@@ -22,10 +22,15 @@ __device__ inline float halo_load(const float* __restrict__ img, int W, int H, i
   return (x >= 0 && x < W && y >= 0 && y < H) ? img[(size_t)y * W + x] : 0.0f;
 }
 
+// METRIC = false: the training loss (value partials + the three derivative maps).  METRIC = true: SSIM as a metric
+// (metrics.py:75, csrc/metrics.hip): no derivative maps and no workspace for them, one SSIM partial per block, and the
+// optional clamp of either image to [0, 1] on load (clamp_flags: GSR_EVAL_CLAMP_X | GSR_EVAL_CLAMP_GT; the zero padding
+// is unchanged by it).
+template <bool METRIC>
 __global__ __launch_bounds__(SS_T * SS_T) void ssim_fwd_kernel(const float* __restrict__ X, const float* __restrict__ Y,
                                                                 int W, int H, Win11 win, float lambda, float inv_n,
                                                                 int dssim_mode, float* __restrict__ partials,
-                                                                float* __restrict__ maps) {
+                                                                float* __restrict__ maps, int clamp_flags) {
   __shared__ float sx[SS_H][SS_H + 1];
   __shared__ float sy[SS_H][SS_H + 1];
   __shared__ float hz[5][SS_H][SS_T + 1];   // horizontally filtered x, y, xx, yy, xy
@@ -37,8 +42,14 @@ __global__ __launch_bounds__(SS_T * SS_T) void ssim_fwd_kernel(const float* __re
   const float* __restrict__ yc = Y + plane * blockIdx.z;
   for (int i = threadIdx.x; i < SS_H * SS_H; i += SS_T * SS_T) {
     const int hy = i / SS_H, hx = i - hy * SS_H;
-    sx[hy][hx] = halo_load(xc, W, H, x0 + hx - SS_R, y0 + hy - SS_R);
-    sy[hy][hx] = halo_load(yc, W, H, x0 + hx - SS_R, y0 + hy - SS_R);
+    float xv = halo_load(xc, W, H, x0 + hx - SS_R, y0 + hy - SS_R);
+    float yv = halo_load(yc, W, H, x0 + hx - SS_R, y0 + hy - SS_R);
+    if constexpr (METRIC) {
+      if (clamp_flags & GSR_EVAL_CLAMP_X) xv = fminf(fmaxf(xv, 0.0f), 1.0f);
+      if (clamp_flags & GSR_EVAL_CLAMP_GT) yv = fminf(fmaxf(yv, 0.0f), 1.0f);
+    }
+    sx[hy][hx] = xv;
+    sy[hy][hx] = yv;
   }
   __syncthreads();
   for (int i = threadIdx.x; i < SS_H * SS_T; i += SS_T * SS_T) {
@@ -69,24 +80,28 @@ __global__ __launch_bounds__(SS_T * SS_T) void ssim_fwd_kernel(const float* __re
     const float N1 = 2.0f * mu12 + C1, N2 = 2.0f * s12 + C2, D1 = mu1_sq + mu2_sq + C1, D2 = s1 + s2 + C2;
     const float inv = 1.0f / (D1 * D2);
     s = N1 * N2 * inv;
-    float dLds = -lambda * inv_n;                                     // d/ds of lambda * (1 - mean s)
-    if (dssim_mode == GSR_DSSIM_CLAMPED_HALF) {                       // lambda * mean(clamp((1 - s)/2, 0, 1))
-      const float d = (1.0f - s) * 0.5f;
-      dLds = (d >= 0.0f && d <= 1.0f) ? 0.5f * dLds : 0.0f;
-      s_acc = fminf(fmaxf(d, 0.0f), 1.0f);
-    } else {
+    if constexpr (METRIC) {
       s_acc = s;
+    } else {
+      float dLds = -lambda * inv_n;                                     // d/ds of lambda * (1 - mean s)
+      if (dssim_mode == GSR_DSSIM_CLAMPED_HALF) {                       // lambda * mean(clamp((1 - s)/2, 0, 1))
+        const float d = (1.0f - s) * 0.5f;
+        dLds = (d >= 0.0f && d <= 1.0f) ? 0.5f * dLds : 0.0f;
+        s_acc = fminf(fmaxf(d, 0.0f), 1.0f);
+      } else {
+        s_acc = s;
+      }
+      const float ds_dm1 = 2.0f * m2 * (N2 - N1) * inv - s * 2.0f * m1 * (D2 - D1) * inv;
+      const size_t o = plane * blockIdx.z + (size_t)py * W + px;
+      const size_t total = plane * gridDim.z;
+      maps[o] = dLds * ds_dm1;
+      maps[total + o] = dLds * (-s / D2);
+      maps[2 * total + o] = dLds * (2.0f * N1 * inv);
+      l1 = fabsf(sx[ty + SS_R][tx + SS_R] - sy[ty + SS_R][tx + SS_R]);
     }
-    const float ds_dm1 = 2.0f * m2 * (N2 - N1) * inv - s * 2.0f * m1 * (D2 - D1) * inv;
-    const size_t o = plane * blockIdx.z + (size_t)py * W + px;
-    const size_t total = plane * gridDim.z;
-    maps[o] = dLds * ds_dm1;
-    maps[total + o] = dLds * (-s / D2);
-    maps[2 * total + o] = dLds * (2.0f * N1 * inv);
-    l1 = fabsf(sx[ty + SS_R][tx + SS_R] - sy[ty + SS_R][tx + SS_R]);
   }
   s = wave_reduce_add_f32(s_acc);
-  l1 = wave_reduce_add_f32(l1);
+  if constexpr (!METRIC) l1 = wave_reduce_add_f32(l1);
   const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
   if (lane == 0) { red[0][wid] = l1; red[1][wid] = s; }
   __syncthreads();
@@ -97,8 +112,12 @@ __global__ __launch_bounds__(SS_T * SS_T) void ssim_fwd_kernel(const float* __re
     // one partial pair per block, summed in block order by ssim_sum_kernel: tens of thousands of atomics on two
     // addresses serialise (0.6 ms at 1080p) and would make the loss value depend on the arrival order
     const size_t blk = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    partials[2 * blk] = a;
-    partials[2 * blk + 1] = b;
+    if constexpr (METRIC) {
+      partials[blk] = b;
+    } else {
+      partials[2 * blk] = a;
+      partials[2 * blk + 1] = b;
+    }
   }
 }
 
@@ -163,8 +182,7 @@ __global__ __launch_bounds__(SS_T * SS_T) void ssim_bwd_kernel(const float* __re
   }
 }
 
-void launch_l1_dssim(const float* x, const float* gt, int C, int H, int W, float lambda, int dssim_mode, float* sums,
-                     float* dL_dx, float* maps, hipStream_t s) {
+static Win11 make_window() {
   Win11 win;
   double g[11], tot = 0.0;
   for (int i = 0; i < 11; ++i) { g[i] = exp(-(double)((i - 5) * (i - 5)) / (2.0 * 1.5 * 1.5)); tot += g[i]; }
@@ -173,14 +191,29 @@ void launch_l1_dssim(const float* x, const float* gt, int C, int H, int W, float
   for (int i = 0; i < 11; ++i) { gf[i] = (float)g[i]; totf += gf[i]; }
   for (int i = 0; i < 11; ++i) win.w[i] = gf[i] / totf;
   (void)tot;
+  return win;
+}
+
+void launch_l1_dssim(const float* x, const float* gt, int C, int H, int W, float lambda, int dssim_mode, float* sums,
+                     float* dL_dx, float* maps, hipStream_t s) {
+  const Win11 win = make_window();
   const dim3 grid((W + SS_T - 1) / SS_T, (H + SS_T - 1) / SS_T, C);
   const float inv_n = 1.0f / ((float)C * (float)H * (float)W);
   float* partials = maps + 3 * (size_t)C * H * W;      // behind the three derivative maps
   const size_t nblocks = (size_t)grid.x * grid.y * grid.z;
-  hipLaunchKernelGGL(ssim_fwd_kernel, grid, dim3(SS_T * SS_T), 0, s, x, gt, W, H, win, lambda, inv_n, dssim_mode,
-                     partials, maps);
+  hipLaunchKernelGGL(ssim_fwd_kernel<false>, grid, dim3(SS_T * SS_T), 0, s, x, gt, W, H, win, lambda, inv_n, dssim_mode,
+                     partials, maps, 0);
   hipLaunchKernelGGL(ssim_sum_kernel, dim3(1), dim3(1024), 0, s, nblocks, partials, sums);
   hipLaunchKernelGGL(ssim_bwd_kernel, grid, dim3(SS_T * SS_T), 0, s, x, gt, W, H, win, (1.0f - lambda) * inv_n, maps, dL_dx);
+}
+
+// partials[block] = sum of the block's per-pixel SSIM, blocks in (channel, tile row, tile column) order; summed by
+// metrics.hip's eval_finish_kernel
+void launch_ssim_metric(const float* x, const float* gt, int C, int H, int W, int clamp_flags, float* partials,
+                        hipStream_t s) {
+  const dim3 grid((W + SS_T - 1) / SS_T, (H + SS_T - 1) / SS_T, C);
+  hipLaunchKernelGGL(ssim_fwd_kernel<true>, grid, dim3(SS_T * SS_T), 0, s, x, gt, W, H, make_window(), 0.0f, 0.0f,
+                     GSR_DSSIM_ONE_MINUS_MEAN, partials, nullptr, clamp_flags);
 }
 
 }  // namespace gsr
