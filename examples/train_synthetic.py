@@ -69,16 +69,26 @@ def make_held_out(dev, P=4000, W=256, H=160, n_views=4, seed=0):
 
 
 def train(dev, iterations=60, densification_interval=20, densify_from_iter=10, extent=2.0, grad_threshold=0.0006, log=None,
-          spatial_order=False, optimizer="torch", report_every=0):
+          spatial_order=False, optimizer="torch", report_every=0, sh_increase_every=0, on_sh_increase=None):
     """spatial_order: after every densification the cloud (and the Adam moments) is stored along a Morton curve
     (mvs_gaussian_splatting_amd/layout.py) instead of the reference's [kept | clones | children] order.
     optimizer: see make_problem.
     report_every: every so many iterations (0: never) the held-out views are evaluated as train.py:217-232 does, in
-    fused passes accumulated on the device (evaluate_views), and L1 / PSNR are logged."""
+    fused passes accumulated on the device (evaluate_views), and L1 / PSNR are logged.
+    sh_increase_every: 0 trains at the full SH degree from the start; n > 0 starts at ``active_sh_degree = 0`` (as the
+    reference's model does, scene/gaussian_model.py:47) and raises it by one, up to the stored degree, at the start of
+    every iteration with ``it % n == 0`` (train.py:75-76, ``oneupSHdegree``).  on_sh_increase(it, model), if given, is
+    called immediately before each such step."""
     targets, cams, bg, pipe, model = make_problem(dev, optimizer=optimizer)
+    if sh_increase_every:
+        model.active_sh_degree = 0
     test_cams = make_held_out(dev) if report_every else []
     history, sizes = [], []
     for it in range(1, iterations + 1):
+        if sh_increase_every and it % sh_increase_every == 0 and model.active_sh_degree < model.max_sh_degree:
+            if on_sh_increase:
+                on_sh_increase(it, model)
+            model.active_sh_degree += 1
         v = (it * 3) % len(cams)
         pkg = render(cams[v], model, pipe, bg)
         loss = l1_dssim_loss(pkg["render"], targets[v], 0.2)

@@ -201,11 +201,19 @@ def _kwargs(v, extent=2.0):
 
 @pytest.mark.parametrize("variant", list(VARIANTS))
 def test_grown_frame_end_to_end(gpu_device, variant):
+    _grown_frame_end_to_end(gpu_device, variant)
+
+
+def _grown_frame_end_to_end(gpu_device, variant, active_sh_degree=None):
+    """active_sh_degree: None renders at the stored degree; a value below it is set on the model first (the reference
+    restatement then runs at that degree too: both read it from the model).  Returns (folded gradients, P)."""
     from mvs_gaussian_splatting_amd import render
     from mvs_gaussian_splatting_amd.rasterizer import GaussianRasterizer
     from mvs_gaussian_splatting_amd.renderer import _settings
     from mvs_gaussian_splatting_amd.synthetic import PipelineParams
     model, cam, bg, target = _scene(gpu_device)
+    if active_sh_degree is not None:
+        model.active_sh_degree = active_sh_degree
     P = model._xyz.shape[0]
     v = VARIANTS[variant]
     kw = _kwargs(v)
@@ -251,6 +259,8 @@ def test_grown_frame_end_to_end(gpu_device, variant):
         scale = float(r.abs().max())
         err = float((g - r).abs().max()) / scale if scale > 0 else float(g.abs().max())
         assert err <= 1e-4, f"{variant}: gradient of {k} off by {err:.2e}"
+    assert st.sh_degree == model.active_sh_degree
+    return got, P
 
 
 @pytest.fixture()

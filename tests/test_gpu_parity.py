@@ -36,9 +36,16 @@ def _oracle_forward(model, cam, bg, deg, dtype=torch.float32, **kw):
 @pytest.mark.parametrize("mode", [0, 1], ids=["two_level", "keys64"])
 @pytest.mark.parametrize("deg,P,w,h", [(3, 3000, 320, 176), (0, 2000, 200, 200), (1, 1500, 97, 131), (2, 800, 64, 48)])
 def test_forward_stages_match_oracle(gpu_device, deg, P, w, h, mode):
+    _forward_stages_match_oracle(gpu_device, deg, deg, P, w, h, mode)
+
+
+def _forward_stages_match_oracle(gpu_device, stored, active, P, w, h, mode):
+    """Every forward stage of a model with degree-`stored` SH storage rendered at SH degree `active` <= `stored`."""
     from gpu_util import forward_with_state, product_settings
-    model, cam, bg, _ = small_scene(P=P, sh_degree=deg, width=w, height=h)
+    model, cam, bg, _ = small_scene(P=P, sh_degree=stored, width=w, height=h)
     bg = torch.tensor([0.1, 0.2, 0.3])
+    deg = active
+    assert model.get_features.shape[1] == (stored + 1) ** 2 and 0 <= active <= stored
     col, radii, aux = _oracle_forward(model, cam, bg, deg)
     st = product_settings(cam, bg, deg, gpu_device)
     out = forward_with_state(gpu_device, st, model.get_xyz, model.get_opacity, shs=model.get_features,
@@ -130,10 +137,15 @@ def test_empty_and_degenerate_inputs(gpu_device):
     assert int((radii > 0).sum()) > 0 and torch.allclose(col.cpu(), expect)
 
 
-def _masked_grad_parity(dev, model, cam, bg, target, deg, label, use_cov=False, use_colors=None, smod=1.0, unmasked=True):
+def _masked_grad_parity(dev, model, cam, bg, target, deg, label, use_cov=False, use_colors=None, smod=1.0, unmasked=True,
+                        must_be_zero=(), check=None):
     """float64 oracle defines the loss weights; float32 oracle bounds the conditioning; HIP must meet the bar.
     unmasked: also run a discontinuity-free loss over EVERY pixel (the threshold-fragile ones included): at the same bar
-    when the scene has no fragile pixel, at the per-scene fragile-share bar when it has (tests/grad_util.py)."""
+    when the scene has no fragile pixel, at the per-scene fragile-share bar when it has (tests/grad_util.py).
+    must_be_zero: the tensors that cannot carry a signal in this configuration (f_rest at SH degree 0): instead of a
+    signal, reference and HIP result must both be exactly zero there.  Every tensor not named must carry one.
+    check: called as check(got, ref, aux) after every backward of this helper (masked run and all-pixel runs), for
+    assertions on top of the comparison."""
     from gpu_util import grads_product, product_settings
     from grad_util import grads_oracle, compare_grads, compare_grads_unmasked
     st_o = make_settings(cam, bg, deg, scale_modifier=smod)
@@ -142,6 +154,14 @@ def _masked_grad_parity(dev, model, cam, bg, target, deg, label, use_cov=False, 
                                   weight=weight)
     got, col = grads_product(dev, model, product_settings(cam, bg, deg, dev, scale_modifier=smod), target, weight,
                              use_cov, use_colors)
+
+    def also(got_, ref_):
+        for k in must_be_zero:
+            assert int(torch.count_nonzero(ref_[k])) == 0, f"{label}: the reference gradient of {k} is not all zero"
+            assert int(torch.count_nonzero(got_[k])) == 0, f"{label}: the gradient of {k} must be exactly zero"
+        if check is not None:
+            check(got_, ref_, aux)
+
     n_fragile = int((aux["margin"] <= 1e-4).sum())
     n_masked = int((weight == 0).sum())
     assert n_masked <= 0.3 * weight.numel(), "the mask must leave most of the image in the loss"
@@ -149,8 +169,9 @@ def _masked_grad_parity(dev, model, cam, bg, target, deg, label, use_cov=False, 
     # the z component of the screen-space gradient is never written to
     assert float(got["means2D"][:, 2].abs().max()) == 0.0
     for k, r in ref.items():          # every compared tensor carries a real signal
-        if k != "means2D" and r.numel():
+        if k != "means2D" and r.numel() and k not in must_be_zero:
             assert float(r.abs().max()) > 0.0, k
+    also(got, ref)
     assert float(ref["means2D"][:, :2].abs().max()) > 0.0
     if unmasked:
         # EVERY pixel in the loss, through a loss that has no discontinuity of its own (grad_util.weighted_sum)
@@ -160,6 +181,7 @@ def _masked_grad_parity(dev, model, cam, bg, target, deg, label, use_cov=False, 
         ref_u, _, _, _ = grads_oracle(model, st_o, target, weight=wts, **kw_o)
         got_u, _ = grads_product(dev, model, product_settings(cam, bg, deg, dev, scale_modifier=smod), target, wts,
                                  use_cov, use_colors, loss_kind="linear")
+        also(got_u, ref_u)
         if n_fragile == 0:
             # no pixel on which float32 and float64 may decide differently: the bar of the masked run, on every pixel
             ref_u32, _, _, _ = grads_oracle(model, st_o, target, dtype=torch.float32, weight=wts, **kw_o)
@@ -179,6 +201,7 @@ def _masked_grad_parity(dev, model, cam, bg, target, deg, label, use_cov=False, 
             # scaling).  The cap (2e-4) is unchanged.
             got_r, _ = grads_product(dev, model, product_settings(cam, bg, deg, dev, scale_modifier=smod), target, robust_w,
                                      use_cov, use_colors, loss_kind="linear")
+            also(got_r, ref_r)
             compare_grads(got_r, ref_r, ref_r32, f"{label}, every pixel but the {n_fragile} threshold-fragile ones in the loss",
                           e32_factor=3.0)
     return got, ref, weight, aux
@@ -197,12 +220,19 @@ def test_backward_matches_fp64_oracle(gpu_device, deg, use_cov, colors):
 def test_fused_raw_parameter_path_matches_unfused_and_oracle(gpu_device, deg):
     """SURVEY §8 f2: render() fed with raw parameters (split SH for degree-3 storage, f_dc alone for degree-0 storage;
     activations inside the kernels) must give the pixels and raw-parameter gradients of the getter path / the fp64 oracle."""
+    _fused_raw_parameter_path(gpu_device, deg, deg)
+
+
+def _fused_raw_parameter_path(gpu_device, stored, active):
+    """render() of a degree-`stored` model at active_sh_degree `active`, fused and through the getters.
+    Returns ({fused: (image, radii, grads)}, reference grads, the model)."""
     from mvs_gaussian_splatting_amd import render
     from mvs_gaussian_splatting_amd.synthetic import PipelineParams
     from grad_util import grads_oracle, compare_grads, masked_l1
     dev = gpu_device
     from mvs_gaussian_splatting_amd.renderer import _can_fuse
-    model, cam, _, target = small_scene(P=2500, sh_degree=deg, width=208, height=120, scale=0.06)
+    model, cam, _, target = small_scene(P=2500, sh_degree=stored, width=208, height=120, scale=0.06)
+    model.active_sh_degree = deg = active
     bg = torch.tensor([0.3, 0.1, 0.2])
     st_o = make_settings(cam, bg, deg)
     ref, weight, aux, _ = grads_oracle(model, st_o, target)
@@ -229,7 +259,9 @@ def test_fused_raw_parameter_path_matches_unfused_and_oracle(gpu_device, deg):
     assert float((out[True][0] - out[False][0]).abs().max()) <= 2.0 / 255.0
     n_fragile = int((aux["margin"] <= 1e-4).sum())
     for fused in (True, False):
-        compare_grads(out[fused][2], ref, ref32, f"render() fused={fused} (fragile pixels {n_fragile})")
+        compare_grads(out[fused][2], ref, ref32, f"render() stored degree {stored}, active {active}, fused={fused} "
+                                                 f"(fragile pixels {n_fragile})")
+    return out, ref, model
 
 
 @pytest.mark.parametrize("n,end_bit", [(1, 45), (63, 45), (4097, 45), (1_000_003, 45), (300_000, 64), (50_000, 17)])

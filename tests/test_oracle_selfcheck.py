@@ -69,11 +69,16 @@ def test_autograd_matches_finite_differences(use_cov):
     """Gradient truth check: fp64 autograd of the restatement vs central differences of a smooth loss.
     exact_grad (upstream_grad=False) is used because finite differences see the exact derivative; the two
     documented upstream deviations are checked separately below."""
+    _autograd_vs_finite_differences(1, 1, use_cov)
+
+
+def _autograd_vs_finite_differences(stored, active, use_cov):
+    """SH storage of degree `stored` evaluated at degree `active`; returns the autograd gradient of f_rest."""
     from oracle import rasterize_ref
     torch.manual_seed(0)
-    model, cam, bg, target = small_scene(P=40, sh_degree=1, width=48, height=32, scale=0.25, focal=40.0)
+    model, cam, bg, target = small_scene(P=40, sh_degree=stored, width=48, height=32, scale=0.25, focal=40.0)
     bg = torch.tensor([0.1, 0.3, 0.2], dtype=torch.float64)
-    st = make_settings(cam, bg, 1)
+    st = make_settings(cam, bg, active)
     d = torch.float64
     xyz = model._xyz.to(d).requires_grad_(True)
     op = model._opacity.to(d).requires_grad_(True)
@@ -110,6 +115,45 @@ def test_autograd_matches_finite_differences(use_cov):
             fd = (lp - lm) / (2 * eps)
             an = g.reshape(-1)[idx].item()
             assert abs(fd - an) <= 2e-4 * max(1.0, abs(an)) + 2e-6, (p.shape, idx, fd, an)
+    return grads[3]
+
+
+@pytest.mark.parametrize("stored,active", [(3, 1), (2, 0)])
+def test_autograd_matches_finite_differences_below_the_stored_sh_degree(stored, active):
+    """The oracle is the truth for the GPU tests that render a model at an active SH degree below the one its storage was
+    sized for (every training run's first 3000 iterations): same scene size, step and bar as above, and the gradient of
+    the coefficients above the active degree is not small but exactly zero."""
+    g_rest = _autograd_vs_finite_differences(stored, active, False)
+    used = (active + 1) ** 2 - 1
+    assert g_rest.shape[1] == (stored + 1) ** 2 - 1 > used
+    assert int(torch.count_nonzero(g_rest[:, used:])) == 0
+    if used:
+        assert int(torch.count_nonzero(g_rest[:, :used])) > 0
+
+
+@pytest.mark.parametrize("stored,active", [(3, 0), (3, 1), (3, 2), (2, 1), (1, 0)])
+def test_image_below_the_stored_sh_degree_is_the_image_of_the_truncated_model(stored, active):
+    """Degree `active` of a degree-`stored` model reads the first (active + 1)^2 coefficients and nothing else: the image
+    and the radii equal those of the model cut down to degree-`active` storage, bit for bit in float64 -- also when the
+    coefficients above are not finite."""
+    from oracle import rasterize_ref
+    model, cam, _, _ = small_scene(P=1200, sh_degree=stored, width=112, height=80, focal=60.0, scale=0.07)
+    bg = torch.tensor([0.2, 0.3, 0.1])
+    used = (active + 1) ** 2
+    d = torch.float64
+    kw = dict(scales=model.get_scaling.to(d), rotations=model.get_rotation.to(d))
+    shs = model.get_features.to(d)
+    st = make_settings(cam, bg, active)
+    full = rasterize_ref(model.get_xyz.to(d), None, model.get_opacity.to(d), st, shs=shs, **kw)
+    cut = rasterize_ref(model.get_xyz.to(d), None, model.get_opacity.to(d), st, shs=shs[:, :used].contiguous(), **kw)
+    poisoned = shs.clone()
+    poisoned[:, used:] = float("nan")
+    nan = rasterize_ref(model.get_xyz.to(d), None, model.get_opacity.to(d), st, shs=poisoned, **kw)
+    assert int((full[1] > 0).sum()) > 100
+    for other in (cut, nan):
+        assert torch.equal(full[0], other[0]) and torch.equal(full[1], other[1])
+    higher = rasterize_ref(model.get_xyz.to(d), None, model.get_opacity.to(d), make_settings(cam, bg, stored), shs=shs, **kw)
+    assert not torch.equal(full[0], higher[0])          # ... and the degree really changes the image
 
 
 def test_upstream_gradient_deviations_are_small_and_documented():
