@@ -1,0 +1,130 @@
+"""The reference's training loop (``train.py:34-160``) on a synthetic scene, from this package's ``GaussianModel`` and
+``trainer.training_iteration``: initialise from a point cloud, train with the reference's schedule (learning-rate decay,
+SH degree steps, densification, opacity resets, the optional opacity sparsity term), checkpoint, resume, write a PLY.
+
+    python examples/train.py [--iterations N] [--checkpoint_iterations N ...] [--start_checkpoint FILE] [--out DIR]
+
+The scene: a ground-truth cloud rendered from orbit views gives the images; the model starts, as the reference's does
+from a COLMAP cloud, from a jittered subsample of the ground truth's centres with their base colours.
+"""
+import argparse
+import math
+import os
+import sys
+import types
+
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from mvs_gaussian_splatting_amd import GaussianModel, render  # noqa: E402
+from mvs_gaussian_splatting_amd.sh import SH2RGB  # noqa: E402
+from mvs_gaussian_splatting_amd.synthetic import PipelineParams, SyntheticGaussianModel, orbit_camera  # noqa: E402
+from mvs_gaussian_splatting_amd.trainer import (OptimizationParams, load_checkpoint, save_checkpoint,  # noqa: E402
+                                                training_iteration)
+
+CAMERAS_EXTENT = 2.0
+
+
+def make_problem(dev, P=4000, W=256, H=160, n_views=8, seed=0, keep_every=2):
+    """(cameras with ``original_image``, background, point cloud ``(points, colors)`` on the device)."""
+    gt = SyntheticGaussianModel(P, 3, seed=seed, log_scale_mean=math.log(0.06), extent=(1.6, 1.0, 0.8), centre=(0, 0, 4.0))
+    gt._opacity += 1.0
+    gt.to(dev)
+    cams = [orbit_camera(v, n_views, W, H, 220.0, 220.0, centre=(0.0, 0.0, 4.0), device=dev) for v in range(n_views)]
+    bg = torch.zeros(3, device=dev)
+    with torch.no_grad():
+        for c in cams:
+            c.original_image = render(c, gt, PipelineParams(), bg)["render"].clone()
+    g = torch.Generator().manual_seed(seed + 7)
+    points = gt._xyz[::keep_every] + 0.02 * torch.randn(gt._xyz[::keep_every].shape, generator=g).to(dev)
+    colors = SH2RGB(gt._features_dc[::keep_every, 0, :]).clamp(0.0, 1.0)
+    return cams, bg, (points.contiguous(), colors.contiguous())
+
+
+def small_opt(iterations=60, **over):
+    """The reference's defaults with the schedule shrunk to a run of tens of iterations."""
+    kw = dict(iterations=iterations, position_lr_max_steps=iterations, densify_from_iter=10, densification_interval=10,
+              opacity_reset_interval=30, densify_until_iter=50, densify_grad_threshold=0.0006)
+    kw.update(over)
+    return OptimizationParams(**kw)
+
+
+def example_opt(iterations=200, **over):
+    """This example's schedule: the reference's proportions at ``iterations`` -- densification every tenth of the run
+    from the first tenth to three quarters, one opacity reset half-way."""
+    n = iterations
+    kw = dict(densify_from_iter=max(n // 10, 1), densification_interval=max(n // 10, 1),
+              opacity_reset_interval=max(n // 2, 1), densify_until_iter=max(3 * n // 4, 2))
+    kw.update(over)
+    return small_opt(n, **kw)
+
+
+def make_model(problem, opt, dataset=None, sh_degree=3, optimizer_cls=None, seed=0):
+    _, _, (points, colors) = problem
+    flag = lambda n: bool(getattr(dataset, n, False))   # noqa: E731
+    model = GaussianModel(sh_degree, grow_dir=flag("grow_dir"), num_dirs=getattr(dataset, "num_dirs", 128),
+                          continous_dir=flag("continous_dir"), grow_distance=flag("grow_distance"), modelcg=dataset)
+    torch.manual_seed(seed)
+    model.create_from_pcd(points, colors, CAMERAS_EXTENT)
+    if optimizer_cls is None:
+        model.training_setup(opt)
+    else:
+        model.training_setup(opt, optimizer_cls)
+    return model
+
+
+def train(model, problem, opt, first_iter=0, last_iter=None, dataset=None, pipe=None, seed=0, log=None, on_iteration=None):
+    """Iterations ``first_iter + 1 .. last_iter`` (default ``opt.iterations``), as ``train.py:54`` counts them.  The
+    device generator is seeded from the iteration number before each one, so that the draws of a densification are the
+    same in a resumed run as in an uninterrupted one.  Returns the losses as device tensors."""
+    cams, bg, _ = problem
+    pipe = pipe or PipelineParams()
+    losses = []
+    for iteration in range(first_iter + 1, (last_iter or opt.iterations) + 1):
+        torch.manual_seed(seed * 1_000_003 + iteration)
+        cam = cams[(iteration * 3) % len(cams)]
+        losses.append(training_iteration(model, cam, opt, pipe, bg, iteration, dataset=dataset,
+                                         cameras_extent=CAMERAS_EXTENT))
+        if on_iteration:
+            on_iteration(iteration, model)
+        if log and iteration % 10 == 0:
+            log(f"iteration {iteration}: loss {float(losses[-1]):.5f}  points {model._xyz.shape[0]}  "
+                f"sh degree {model.active_sh_degree}")
+    return losses
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--iterations", type=int, default=200)
+    ap.add_argument("--checkpoint_iterations", type=int, nargs="*", default=[])
+    ap.add_argument("--start_checkpoint", default=None)
+    ap.add_argument("--opacitysparse", type=float, default=0.0)
+    ap.add_argument("--out", default=os.path.dirname(os.path.abspath(__file__)))
+    args = ap.parse_args(argv)
+    dev = torch.device("cuda:0")
+    n = args.iterations
+    opt = example_opt(n, opacitysparse=args.opacitysparse)
+    dataset = types.SimpleNamespace(white_background=False)
+    problem = make_problem(dev)
+    model = make_model(problem, opt, dataset)
+    first_iter = 0
+    if args.start_checkpoint:
+        first_iter = load_checkpoint(model, args.start_checkpoint, opt)
+        print(f"resumed from {args.start_checkpoint} at iteration {first_iter}")
+    os.makedirs(args.out, exist_ok=True)
+
+    def on_iteration(iteration, m):
+        if iteration in args.checkpoint_iterations:
+            path = os.path.join(args.out, f"chkpnt{iteration}.pth")
+            save_checkpoint(m, iteration, path)
+            print(f"[ITER {iteration}] saved checkpoint {path}")
+
+    losses = train(model, problem, opt, first_iter, dataset=dataset, log=print, on_iteration=on_iteration)
+    ply = os.path.join(args.out, "point_cloud.ply")
+    model.save_ply(ply)
+    if losses:
+        print(f"loss {float(losses[0]):.5f} -> {float(losses[-1]):.5f}; {model._xyz.shape[0]} Gaussians; wrote {ply}")
+
+
+if __name__ == "__main__":
+    main()

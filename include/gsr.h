@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 17
+#define GSR_ABI_VERSION 18
 
 enum {
   GSR_OK = 0,
@@ -498,6 +498,30 @@ typedef struct GsrAdamBatch {
 } GsrAdamBatch;
 
 int gsr_adam_step(const GsrAdamBatch* batch, void* stream);
+
+/* The model's per-opacity lifecycle steps, ABI v18 (csrc/model.hip).  opacity_raw is the model's `_opacity`, device
+ * [P,1] fp32, pre-activation.  Nothing here allocates, synchronises or reads back: every call can sit in a captured
+ * graph.
+ *   gsr_opacity_sparsity_fwd: the fork's sparsity term of train.py:102-106.  With o = sigmoid(raw) in float,
+ *     S = {i : o_i < threshold} (train.py:102 uses 0.005) and n = |S|, writes the 16-byte aligned device record
+ *       record[0] = float  weight / n * sum_S |o_i - 1|     (0 when n == 0: the reference skips the term, :104)
+ *       record[1] = uint32 n
+ *       record[2] = float  weight / n                        (0 when n == 0)
+ *       record[3] = 0
+ *     One streaming pass leaves a (sum, count) pair per block in `workspace`
+ *     (gsr_opacity_sparsity_workspace_bytes(), 4-byte aligned), one block adds them in a fixed order in double: the
+ *     result is the same from run to run.
+ *   gsr_opacity_sparsity_bwd: grad_raw[i] = grad_out[0] * record[2] * sign(o_i - 1) * o_i * (1 - o_i) on S, 0
+ *     elsewhere (dense [P,1]).  grad_out is the DEVICE address of the upstream 0-dim gradient.
+ *   gsr_reset_opacity: reset_opacity (scene/gaussian_model.py:312-315) in place: raw <- log(c / (1 - c)) with
+ *     c = min(sigmoid(raw), cap), each op rounded to float as torch does (rows below the cap make the round trip too),
+ *     and exp_avg / exp_avg_sq (each NULL or [P]) zero-filled as replace_tensor_to_optimizer does (:391-392). */
+size_t gsr_opacity_sparsity_workspace_bytes(void);
+int gsr_opacity_sparsity_fwd(const float* opacity_raw, int64_t P, float weight, float threshold, float* record,
+                             void* workspace, void* stream);
+int gsr_opacity_sparsity_bwd(const float* opacity_raw, int64_t P, float threshold, const float* record,
+                             const float* grad_out, float* grad_raw, void* stream);
+int gsr_reset_opacity(float* opacity_raw, int64_t P, float cap, float* exp_avg, float* exp_avg_sq, void* stream);
 
 #ifdef __cplusplus
 }

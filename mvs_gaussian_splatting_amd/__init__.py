@@ -6,10 +6,11 @@
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians,  # noqa: F401
                          rasterize_gaussians_fused)
 from .renderer import render  # noqa: F401
-from .losses import l1_loss, l1_dssim_loss, add_densification_stats  # noqa: F401
+from .losses import l1_loss, l1_dssim_loss, opacity_sparsity_loss, add_densification_stats  # noqa: F401
 from .optim import Adam  # noqa: F401
+from .model import GaussianModel  # noqa: F401
 from .metrics import psnr, ssim, image_metrics, to_uint8_hwc, EvalAccumulator, evaluate_views  # noqa: F401
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "render", "l1_loss", "l1_dssim_loss",
-           "add_densification_stats", "Adam", "psnr", "ssim", "image_metrics", "to_uint8_hwc", "EvalAccumulator",
+           "opacity_sparsity_loss", "add_densification_stats", "Adam", "GaussianModel", "psnr", "ssim", "image_metrics", "to_uint8_hwc", "EvalAccumulator",
            "evaluate_views"]

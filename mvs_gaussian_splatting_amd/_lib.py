@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # instead of copying it over the in-tree library
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 
 class GsrParams(C.Structure):
@@ -170,6 +170,13 @@ SYMBOLS = {
                                     C.c_void_p]),
     # torch.optim.Adam's foreach step over up to ADAM_MAX_TENSORS tensors in one launch (optim.py)
     "gsr_adam_step": (C.c_int, [C.POINTER(GsrAdamBatch), C.c_void_p]),
+    # the opacity sparsity term of train.py:102-106 and the in-place reset_opacity (csrc/model.hip; losses.py, model.py)
+    "gsr_opacity_sparsity_workspace_bytes": (C.c_size_t, []),
+    "gsr_opacity_sparsity_fwd": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
+    "gsr_opacity_sparsity_bwd": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
+    "gsr_reset_opacity": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

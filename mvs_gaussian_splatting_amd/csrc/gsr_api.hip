@@ -1001,4 +1001,38 @@ int gsr_adam_step(const GsrAdamBatch* batch, void* stream) {
   return check(nullptr, s, "adam_step");
 }
 
+size_t gsr_opacity_sparsity_workspace_bytes(void) { return (size_t)OPACITY_MAX_BLOCKS * (sizeof(float) + sizeof(uint32_t)); }
+int gsr_opacity_sparsity_fwd(const float* opacity_raw, int64_t P, float weight, float threshold, float* record,
+                             void* workspace, void* stream) {
+  if (P < 0) return fail(GSR_E_BADARG, "negative P");
+  if (!record || !workspace || (P > 0 && !opacity_raw)) return fail(GSR_E_BADARG, "NULL argument");
+  if ((((uintptr_t)opacity_raw | (uintptr_t)workspace) & 3u) != 0 || ((uintptr_t)record & 15u) != 0)
+    return fail(GSR_E_ALIGN, "opacity and workspace must be 4-byte aligned, the record 16-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_opacity_sparsity_fwd(opacity_raw, (size_t)P, weight, threshold, record, workspace, s);
+  return check(nullptr, s, "opacity_sparsity_fwd");
+}
+int gsr_opacity_sparsity_bwd(const float* opacity_raw, int64_t P, float threshold, const float* record,
+                             const float* grad_out, float* grad_raw, void* stream) {
+  if (P < 0) return fail(GSR_E_BADARG, "negative P");
+  if (!record || !grad_out || (P > 0 && (!opacity_raw || !grad_raw))) return fail(GSR_E_BADARG, "NULL argument");
+  if ((((uintptr_t)opacity_raw | (uintptr_t)grad_raw | (uintptr_t)record | (uintptr_t)grad_out) & 3u) != 0)
+    return fail(GSR_E_ALIGN, "arrays must be 4-byte aligned");
+  if (P == 0) return 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_opacity_sparsity_bwd(opacity_raw, (size_t)P, threshold, record, grad_out, grad_raw, s);
+  return check(nullptr, s, "opacity_sparsity_bwd");
+}
+int gsr_reset_opacity(float* opacity_raw, int64_t P, float cap, float* exp_avg, float* exp_avg_sq, void* stream) {
+  if (P < 0) return fail(GSR_E_BADARG, "negative P");
+  if (P > 0 && !opacity_raw) return fail(GSR_E_BADARG, "NULL opacity");
+  if (!(cap > 0.0f && cap < 1.0f)) return fail(GSR_E_BADARG, "cap must lie in (0, 1)");
+  if ((((uintptr_t)opacity_raw | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 3u) != 0)
+    return fail(GSR_E_ALIGN, "arrays must be 4-byte aligned");
+  if (P == 0) return 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_reset_opacity(opacity_raw, (size_t)P, cap, exp_avg, exp_avg_sq, s);
+  return check(nullptr, s, "reset_opacity");
+}
+
 }  // extern "C"

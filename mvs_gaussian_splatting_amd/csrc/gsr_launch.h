@@ -164,6 +164,15 @@ void launch_densify_fork_rows(const GsrDensifyFork& f, const void* ws, const uin
 // work-items
 int launch_adam_step(const GsrAdamBatch& batch, hipStream_t s);
 
+// model.hip: the opacity sparsity term (workspace: OPACITY_MAX_BLOCKS float sums, then as many uint32 counts; record:
+// {float loss, uint32 n, float weight / n, 0}) and the in-place opacity reset (moments may be nullptr)
+constexpr int OPACITY_MAX_BLOCKS = 2048;
+void launch_opacity_sparsity_fwd(const float* raw, size_t P, float weight, float thr, float* record, void* workspace,
+                                 hipStream_t s);
+void launch_opacity_sparsity_bwd(const float* raw, size_t P, float thr, const float* record, const float* grad_out,
+                                 float* grad_raw, hipStream_t s);
+void launch_reset_opacity(float* raw, size_t P, float cap, float* exp_avg, float* exp_avg_sq, hipStream_t s);
+
 // knn.hip
 size_t knn_workspace_bytes(int N);
 void launch_knn3(const float* pts, int N, float* mean_dist2, void* ws, hipStream_t s);

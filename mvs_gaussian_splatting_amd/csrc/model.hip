@@ -1,0 +1,217 @@
+// Two steps of the model's lifecycle that touch every opacity (include/gsr.h, ABI v18):
+//
+//   * the fork's opacity sparsity term of train.py:102-106, `w * mean(|o - 1|)` over the rows with o = sigmoid(raw)
+//     below 0.005: opacity_sparsity_kernel streams the [P,1] tensor once and leaves one (sum, count) pair per block,
+//     opacity_sparsity_finish_kernel adds the pairs in a fixed order in double and writes the record the backward reads
+//     from device memory (loss, n, w / n), opacity_sparsity_bwd_kernel writes the dense gradient.  No atomics: the
+//     value does not depend on arrival order.  The host never sees n, so a train step keeps its queue full.
+//   * reset_opacity (scene/gaussian_model.py:312-315 with replace_tensor_to_optimizer :386-399) in place:
+//     raw <- log(c / (1 - c)) with c = min(sigmoid(raw), cap), and the two Adam moments zero-filled, in one launch.
+//
+// Built with -ffp-contract=off: sigmoid, min, sub, div, log are torch's ops, each rounded to float32 on its own.
+#include "gsr_common.h"
+#include "gsr_launch.h"
+
+namespace gsr {
+
+namespace {
+
+constexpr int OS_THREADS = 256;
+constexpr int OS_WAVES = OS_THREADS / WAVE;
+constexpr int OS_FIN_THREADS = 256;
+
+// torch's sigmoid kernel: 1 / (1 + exp(-x)) in float
+__device__ __forceinline__ float sigmoid_f32(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+struct SparsityAcc {
+  float sum;
+  uint32_t n;
+  __device__ __forceinline__ void add(float raw, float thr) {
+    const float o = sigmoid_f32(raw);
+    if (o < thr) {
+      sum += fabsf(o - 1.0f);
+      n += 1u;
+    }
+  }
+};
+
+// VEC: a lane owns 4 consecutive rows (one 16-byte load); the P % 4 tail rows go to the first lanes of block 0.
+template <bool VEC>
+__global__ __launch_bounds__(OS_THREADS) void opacity_sparsity_kernel(const float* __restrict__ raw, size_t P, float thr,
+                                                                      float* __restrict__ part_sum,
+                                                                      uint32_t* __restrict__ part_n) {
+  __shared__ float red_s[OS_WAVES];
+  __shared__ uint32_t red_n[OS_WAVES];
+  SparsityAcc a = {0.0f, 0u};
+  const size_t stride = (size_t)gridDim.x * OS_THREADS;
+  const size_t first = (size_t)blockIdx.x * OS_THREADS + threadIdx.x;
+  if constexpr (VEC) {
+    const size_t items = P / 4;
+    for (size_t i = first; i < items; i += stride) {
+      const float4 v = reinterpret_cast<const float4*>(raw)[i];
+      a.add(v.x, thr); a.add(v.y, thr); a.add(v.z, thr); a.add(v.w, thr);
+    }
+    const size_t tail = 4 * items + first;                       // first < 4 only in block 0
+    if (first < 4 && tail < P) a.add(raw[tail], thr);
+  } else {
+    for (size_t i = first; i < P; i += stride) a.add(raw[i], thr);
+  }
+  const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
+  const float s = wave_reduce_add_f32(a.sum);
+  const uint32_t n = wave_reduce_add_u32(a.n);
+  if (lane == 0) { red_s[wid] = s; red_n[wid] = n; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float ts = 0.0f;
+    uint32_t tn = 0u;
+#pragma unroll
+    for (int w = 0; w < OS_WAVES; ++w) { ts += red_s[w]; tn += red_n[w]; }
+    part_sum[blockIdx.x] = ts;                                   // one pair per block: no atomics, see metrics.hip
+    part_n[blockIdx.x] = tn;
+  }
+}
+
+__device__ __forceinline__ double wave_reduce_add_f64(double v) {
+#pragma unroll
+  for (int d = WAVE / 2; d > 0; d >>= 1) v += __shfl_xor(v, d, WAVE);
+  return v;
+}
+
+// One block.  Lane t adds pairs t, t + 256, ... in order, then a fixed butterfly and a fixed walk over the waves.
+// record = {float loss, uint32 n, float weight / n, 0}; n == 0 gives loss = factor = 0 (train.py:104 skips the term).
+__global__ __launch_bounds__(OS_FIN_THREADS) void opacity_sparsity_finish_kernel(const float* __restrict__ part_sum,
+                                                                                 const uint32_t* __restrict__ part_n,
+                                                                                 int nblocks, float weight,
+                                                                                 float* __restrict__ record) {
+  __shared__ double red_s[OS_FIN_THREADS / WAVE];
+  __shared__ uint32_t red_n[OS_FIN_THREADS / WAVE];
+  double s = 0.0;
+  uint32_t n = 0u;
+  for (int i = threadIdx.x; i < nblocks; i += OS_FIN_THREADS) {
+    s += (double)part_sum[i];
+    n += part_n[i];
+  }
+  const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
+  s = wave_reduce_add_f64(s);
+  n = wave_reduce_add_u32(n);
+  if (lane == 0) { red_s[wid] = s; red_n[wid] = n; }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double ts = 0.0;
+  uint32_t tn = 0u;
+  for (int w = 0; w < OS_FIN_THREADS / WAVE; ++w) { ts += red_s[w]; tn += red_n[w]; }
+  const double factor = tn ? (double)weight / (double)tn : 0.0;
+  record[0] = (float)(factor * ts);
+  reinterpret_cast<uint32_t*>(record)[1] = tn;
+  record[2] = (float)factor;
+  record[3] = 0.0f;
+}
+
+// d/d raw of w/n * |o - 1| on the selected rows: g * (w/n) * sign(o - 1) * o * (1 - o); 0 elsewhere
+__device__ __forceinline__ float sparsity_grad(float raw, float thr, float scale) {
+  const float o = sigmoid_f32(raw);
+  if (!(o < thr)) return 0.0f;
+  const float d = o - 1.0f;
+  const float sgn = (float)((d > 0.0f) - (d < 0.0f));
+  return (scale * sgn) * ((1.0f - o) * o);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(OS_THREADS) void opacity_sparsity_bwd_kernel(const float* __restrict__ raw, size_t P,
+                                                                          float thr, const float* __restrict__ record,
+                                                                          const float* __restrict__ grad_out,
+                                                                          float* __restrict__ grad_raw) {
+  const float scale = grad_out[0] * record[2];                   // both live in device memory: no host read-back
+  const size_t stride = (size_t)gridDim.x * OS_THREADS;
+  const size_t first = (size_t)blockIdx.x * OS_THREADS + threadIdx.x;
+  if constexpr (VEC) {
+    const size_t items = P / 4;
+    for (size_t i = first; i < items; i += stride) {
+      const float4 v = reinterpret_cast<const float4*>(raw)[i];
+      reinterpret_cast<float4*>(grad_raw)[i] = make_float4(sparsity_grad(v.x, thr, scale), sparsity_grad(v.y, thr, scale),
+                                                           sparsity_grad(v.z, thr, scale), sparsity_grad(v.w, thr, scale));
+    }
+    const size_t tail = 4 * items + first;
+    if (first < 4 && tail < P) grad_raw[tail] = sparsity_grad(raw[tail], thr, scale);
+  } else {
+    for (size_t i = first; i < P; i += stride) grad_raw[i] = sparsity_grad(raw[i], thr, scale);
+  }
+}
+
+// inverse_sigmoid(torch.min(sigmoid(raw), cap)) as the reference evaluates it: the uncapped rows make the round trip
+// too.  `o > cap ? cap : o` keeps a NaN, as torch.min does.
+__device__ __forceinline__ float reset_value(float raw, float cap) {
+  const float o = sigmoid_f32(raw);
+  const float c = o > cap ? cap : o;
+  return logf(c / (1.0f - c));
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(OS_THREADS) void reset_opacity_kernel(float* __restrict__ raw, size_t P, float cap,
+                                                                   float* __restrict__ exp_avg,
+                                                                   float* __restrict__ exp_avg_sq) {
+  const size_t stride = (size_t)gridDim.x * OS_THREADS;
+  const size_t first = (size_t)blockIdx.x * OS_THREADS + threadIdx.x;
+  if constexpr (VEC) {
+    const size_t items = P / 4;
+    const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    for (size_t i = first; i < items; i += stride) {
+      const float4 v = reinterpret_cast<const float4*>(raw)[i];
+      reinterpret_cast<float4*>(raw)[i] = make_float4(reset_value(v.x, cap), reset_value(v.y, cap),
+                                                      reset_value(v.z, cap), reset_value(v.w, cap));
+      if (exp_avg) reinterpret_cast<float4*>(exp_avg)[i] = zero;
+      if (exp_avg_sq) reinterpret_cast<float4*>(exp_avg_sq)[i] = zero;
+    }
+    const size_t tail = 4 * items + first;
+    if (first < 4 && tail < P) {
+      raw[tail] = reset_value(raw[tail], cap);
+      if (exp_avg) exp_avg[tail] = 0.0f;
+      if (exp_avg_sq) exp_avg_sq[tail] = 0.0f;
+    }
+  } else {
+    for (size_t i = first; i < P; i += stride) {
+      raw[i] = reset_value(raw[i], cap);
+      if (exp_avg) exp_avg[i] = 0.0f;
+      if (exp_avg_sq) exp_avg_sq[i] = 0.0f;
+    }
+  }
+}
+
+int stream_blocks(size_t P, bool vec) {
+  const size_t items = vec ? P / 4 : P;
+  const size_t b = (items + OS_THREADS - 1) / OS_THREADS;
+  return (int)(b < (size_t)OPACITY_MAX_BLOCKS ? (b ? b : 1) : (size_t)OPACITY_MAX_BLOCKS);
+}
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+}  // namespace
+
+void launch_opacity_sparsity_fwd(const float* raw, size_t P, float weight, float thr, float* record, void* workspace,
+                                 hipStream_t s) {
+  float* part_sum = static_cast<float*>(workspace);              // [OPACITY_MAX_BLOCKS] sums, then as many counts
+  uint32_t* part_n = reinterpret_cast<uint32_t*>(part_sum + OPACITY_MAX_BLOCKS);
+  const bool vec = aligned16(raw);
+  const int blocks = stream_blocks(P, vec);
+  if (vec) hipLaunchKernelGGL((opacity_sparsity_kernel<true>), dim3(blocks), dim3(OS_THREADS), 0, s, raw, P, thr, part_sum, part_n);
+  else hipLaunchKernelGGL((opacity_sparsity_kernel<false>), dim3(blocks), dim3(OS_THREADS), 0, s, raw, P, thr, part_sum, part_n);
+  hipLaunchKernelGGL(opacity_sparsity_finish_kernel, dim3(1), dim3(OS_FIN_THREADS), 0, s, part_sum, part_n, blocks, weight,
+                     record);
+}
+
+void launch_opacity_sparsity_bwd(const float* raw, size_t P, float thr, const float* record, const float* grad_out,
+                                 float* grad_raw, hipStream_t s) {
+  const bool vec = aligned16(raw) && aligned16(grad_raw);
+  const int blocks = stream_blocks(P, vec);
+  if (vec) hipLaunchKernelGGL((opacity_sparsity_bwd_kernel<true>), dim3(blocks), dim3(OS_THREADS), 0, s, raw, P, thr, record, grad_out, grad_raw);
+  else hipLaunchKernelGGL((opacity_sparsity_bwd_kernel<false>), dim3(blocks), dim3(OS_THREADS), 0, s, raw, P, thr, record, grad_out, grad_raw);
+}
+
+void launch_reset_opacity(float* raw, size_t P, float cap, float* exp_avg, float* exp_avg_sq, hipStream_t s) {
+  const bool vec = aligned16(raw) && aligned16(exp_avg) && aligned16(exp_avg_sq);      // NULL counts as aligned
+  const int blocks = stream_blocks(P, vec);
+  if (vec) hipLaunchKernelGGL((reset_opacity_kernel<true>), dim3(blocks), dim3(OS_THREADS), 0, s, raw, P, cap, exp_avg, exp_avg_sq);
+  else hipLaunchKernelGGL((reset_opacity_kernel<false>), dim3(blocks), dim3(OS_THREADS), 0, s, raw, P, cap, exp_avg, exp_avg_sq);
+}
+
+}  // namespace gsr

@@ -1,6 +1,6 @@
 """Caller-side loss / statistics steps that sit next to the rasterizer in the train loop, fused into
-single HIP kernels behind the C ABI: L1 (``utils/loss_utils.py:17-18``, ``train.py:99``) and the
-densification statistics (``scene/gaussian_model.py:775-777``, ``train.py:130``)."""
+single HIP kernels behind the C ABI: L1 (``utils/loss_utils.py:17-18``, ``train.py:99``), the fork's opacity sparsity
+term (``train.py:102-106``) and the densification statistics (``scene/gaussian_model.py:775-777``, ``train.py:130``)."""
 from __future__ import annotations
 
 import torch
@@ -72,6 +72,61 @@ def l1_dssim_loss(network_output: torch.Tensor, gt: torch.Tensor, lambda_dssim: 
     ``utils/loss_utils.py:17-63``, ``arguments/__init__.py:96`` lambda_dssim = 0.2) as two fused kernels that
     produce the value and the gradient together."""
     return _L1DssimLoss.apply(network_output, gt, lambda_dssim)
+
+
+class _OpacitySparsity(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, raw: torch.Tensor, weight: float, threshold: float, holder: list):
+        lib = _lib.load()
+        rc = raw.contiguous()
+        P = rc.numel()
+        record = torch.empty(4, dtype=torch.float32, device=raw.device)          # loss, n (uint32 bits), weight / n, 0
+        ws = torch.empty(lib.gsr_opacity_sparsity_workspace_bytes(), dtype=torch.uint8, device=raw.device)
+        with torch.cuda.device(raw.device):
+            stream = torch.cuda.current_stream(raw.device).cuda_stream
+            _lib.check(lib.gsr_opacity_sparsity_fwd(rc.data_ptr(), P, weight, threshold, record.data_ptr(),
+                                                    ws.data_ptr(), stream), "gsr_opacity_sparsity_fwd")
+        ctx.save_for_backward(rc, record)
+        ctx.threshold = threshold
+        ctx.shape = raw.shape
+        holder.append(record)
+        return record[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        rc, record = ctx.saved_tensors
+        g = g.to(torch.float32).contiguous()                                     # a 0-dim device tensor: never .item()
+        grad = torch.empty_like(rc)
+        with torch.cuda.device(rc.device):
+            stream = torch.cuda.current_stream(rc.device).cuda_stream
+            _lib.check(_lib.load().gsr_opacity_sparsity_bwd(rc.data_ptr(), rc.numel(), ctx.threshold, record.data_ptr(),
+                                                            g.data_ptr(), grad.data_ptr(), stream),
+                       "gsr_opacity_sparsity_bwd")
+        return grad.view(ctx.shape), None, None, None
+
+
+def opacity_sparsity_loss(raw_opacity: torch.Tensor, weight: float, threshold: float = 0.005,
+                          return_record: bool = False) -> torch.Tensor:
+    """The fork's ``opt.opacitysparse`` term (``train.py:102-106``) as a 0-dim device tensor: with
+    ``o = sigmoid(raw_opacity)`` and ``S = {o < threshold}``, ``weight * mean_S |o - 1|``, and exactly 0 with an
+    all-zero gradient when ``S`` is empty (the reference then skips the term).  ``threshold`` is the literal 0.005 of
+    ``train.py:102``, not ``opt.min_opacity``.  The count of ``S`` stays on the device (``csrc/model.hip``): neither
+    the forward nor the backward synchronises with the host, where the torch form drains the queue twice (the ``if`` on
+    the device sum and the boolean-mask gather).  ``weight <= 0`` returns a constant zero without a launch (the
+    reference's ``opt.opacitysparse > 0`` test).
+    return_record: also return the kernel's record as a float32 ``[4]`` device tensor, ``(loss, n as uint32 bits,
+    weight / n, 0)`` (``record.view(torch.int32)[1]`` is ``n``)."""
+    if not isinstance(raw_opacity, torch.Tensor) or not raw_opacity.is_cuda:
+        raise _lib.GsrError("opacity_sparsity_loss needs a ROCm GPU tensor (no CPU path)")
+    if raw_opacity.dtype != torch.float32:
+        raise TypeError(f"opacity_sparsity_loss expects a float32 tensor, got {raw_opacity.dtype}")
+    weight = float(weight)
+    if not weight > 0.0:
+        zero = torch.zeros((), dtype=torch.float32, device=raw_opacity.device)
+        return (zero, torch.zeros(4, dtype=torch.float32, device=raw_opacity.device)) if return_record else zero
+    holder = []
+    loss = _OpacitySparsity.apply(raw_opacity, weight, float(threshold), holder)
+    return (loss, holder[0]) if return_record else loss
 
 
 @torch.no_grad()

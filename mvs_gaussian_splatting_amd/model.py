@@ -1,0 +1,327 @@
+"""The reference's ``GaussianModel`` (``scene/gaussian_model.py``) for the HIP path: the object that ``render``,
+``add_densification_stats``, ``densify.densify_and_prune``, ``optim.training_setup``, ``layout.reorder_gaussians_``,
+``ply_io.save_ply`` and ``evaluate_views`` are handed, with the lifecycle around them -- initialisation from a point
+cloud (``create_from_pcd`` ``:200-238``), ``oneupSHdegree`` (``:196-198``), ``reset_opacity`` (``:312-315``),
+checkpoints (``capture`` / ``restore`` ``:84-149``) and PLY files (``:293-358``).
+
+    gaussians = GaussianModel(sh_degree, grow_dir=..., num_dirs=..., continous_dir=..., grow_distance=..., modelcg=dataset)
+    gaussians.create_from_pcd(pcd.points, pcd.colors, cameras_extent)
+    gaussians.training_setup(opt)
+
+Same constructor, attribute names and getters as the reference, so code written against its class runs unchanged;
+densification stays the function ``densify.densify_and_prune(gaussians, ...)`` and the statistics
+``add_densification_stats(gaussians, ...)`` (``trainer.training_iteration`` calls both in the reference's order).
+There is no CPU path: the methods that compute raise ``GsrError`` on CPU tensors; constructing a model, ``capture`` and
+``oneupSHdegree`` are host code and run anywhere.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+from torch import nn
+
+from . import _lib, knn, optim, ply_io
+from .densify import FORK_ATTR, FORK_FLAG, GROUP_ATTR
+from .sh import RGB2SH
+
+RESET_OPACITY_CAP = 0.01            # scene/gaussian_model.py:313
+INITIAL_OPACITY = 0.1               # :215
+MIN_DIST2 = 0.0000001               # :210
+
+
+def sphere_points(n: int = 128) -> np.ndarray:
+    """``utils/general_utils.py:135-148``: ``n`` directions on a golden-angle spiral over the unit sphere, float64
+    ``[n, 3]``, from ``z = 1 - 1/n`` down to ``1/n - 1``."""
+    golden_angle = np.pi * (3.0 - np.sqrt(5.0))
+    theta = golden_angle * np.arange(n)
+    z = np.linspace(1 - 1.0 / n, 1.0 / n - 1, n)
+    radius = np.sqrt(1 - z * z)
+    return np.stack((radius * np.cos(theta), radius * np.sin(theta), z), axis=1)
+
+
+def inverse_sigmoid(x: torch.Tensor) -> torch.Tensor:
+    """``utils/general_utils.py:18-19``."""
+    return torch.log(x / (1 - x))
+
+
+def covariance_from_scaling_rotation(scaling, scaling_modifier, rotation):
+    """``scene/gaussian_model.py:28-32``: the six unique entries of ``(R S)(R S)^T``, ``[P, 6]``, from activated scales
+    and raw quaternions."""
+    s = scaling_modifier * scaling
+    q = torch.nn.functional.normalize(rotation)
+    r, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    R = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y),
+                     2 * (x * y + r * z), 1 - 2 * (x * x + z * z), 2 * (y * z - r * x),
+                     2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)], dim=1).reshape(-1, 3, 3)
+    L = R * s[:, None, :]
+    cov = L @ L.transpose(1, 2)
+    return torch.stack([cov[:, 0, 0], cov[:, 0, 1], cov[:, 0, 2], cov[:, 1, 1], cov[:, 1, 2], cov[:, 2, 2]], dim=1)
+
+
+def _need_gpu(name: str, t: torch.Tensor) -> None:
+    if not t.is_cuda:
+        raise _lib.GsrError(f"{name} needs ROCm GPU tensors (no CPU path)")
+
+
+class GaussianModel:
+    """See the module docstring.  ``modelcg`` is the reference's dataset namespace (``learn_split_distance``,
+    ``learn_split_scale``, ``symmetric_split``, ``split_notreinit``, ``prob_notreinit``); None means no learned split."""
+
+    def __init__(self, sh_degree: int, grow_dir=False, num_dirs=128, continous_dir=False, grow_distance=False,
+                 modelcg=None):
+        self.active_sh_degree = 0
+        self.max_sh_degree = sh_degree
+        self._xyz = torch.empty(0)
+        self._features_dc = torch.empty(0)
+        self._features_rest = torch.empty(0)
+        self._scaling = torch.empty(0)
+        self._rotation = torch.empty(0)
+        self._opacity = torch.empty(0)
+        self.max_radii2D = torch.empty(0)
+        self.xyz_gradient_accum = torch.empty(0)
+        self.denom = torch.empty(0)
+        self.optimizer = None
+        self.percent_dense = 0
+        self.spatial_lr_scale = 0
+        self.grow_dir = grow_dir
+        self.continous_dir = continous_dir
+        self.grow_distance = grow_distance
+        self.num_dirs = num_dirs
+        self.modelcg = modelcg
+        self.learn_split_distance = bool(getattr(modelcg, "learn_split_distance", False))
+        self.learn_split_scale = bool(getattr(modelcg, "learn_split_scale", False))
+        if self.grow_dir:                                       # :68-73 (an `elif` there: grow_dir wins)
+            self._dirs_prob = torch.empty(0)
+            self.dirs = torch.tensor(sphere_points(self.num_dirs)).to(torch.float32)      # moved with the parameters
+        elif self.continous_dir:
+            self._conti_dirs = torch.empty(0)
+        if self.grow_distance:
+            self._grow_dist = torch.empty(0)
+        if self.learn_split_distance:
+            self._split_distance = torch.empty(0)
+        if self.learn_split_scale:
+            self._split_scale = torch.empty(0)
+        self._optimizer_cls = optim.Adam
+        # :34-42; render's raw-parameter path recognises the model by these three
+        self.scaling_activation = torch.exp
+        self.scaling_inverse_activation = torch.log
+        self.covariance_activation = covariance_from_scaling_rotation
+        self.opacity_activation = torch.sigmoid
+        self.inverse_opacity_activation = inverse_sigmoid
+        self.rotation_activation = torch.nn.functional.normalize
+
+    # ---- getters :151-194 -------------------------------------------------------------------------------------------
+    @property
+    def get_scaling(self):
+        return self.scaling_activation(self._scaling)
+
+    @property
+    def get_grow_dist(self):
+        return 2 * torch.sigmoid(self._grow_dist)
+
+    @property
+    def get_split_distance(self):
+        return 2.2 * torch.sigmoid(self._split_distance)
+
+    @property
+    def get_split_scale(self):
+        return 0.6 * torch.sigmoid(self._split_scale) + 0.5
+
+    @property
+    def get_rotation(self):
+        return self.rotation_activation(self._rotation)
+
+    @property
+    def get_xyz(self):
+        return self._xyz
+
+    @property
+    def get_features(self):
+        return torch.cat((self._features_dc, self._features_rest), dim=1)
+
+    @property
+    def get_opacity(self):
+        return self.opacity_activation(self._opacity)
+
+    @property
+    def get_dirs_prob(self):
+        return self._dirs_prob
+
+    @property
+    def get_conti_dirs(self):
+        return self._conti_dirs
+
+    def get_covariance(self, scaling_modifier=1):
+        return self.covariance_activation(self.get_scaling, scaling_modifier, self._rotation)
+
+    def oneupSHdegree(self):
+        if self.active_sh_degree < self.max_sh_degree:
+            self.active_sh_degree += 1
+
+    # ---- the tensors a model of these flags owns ------------------------------------------------------------------
+    def _fork_attrs(self):
+        """group name -> attribute of the fork tensors this model carries (``densify.FORK_FLAG``; ``:68-80``)."""
+        return {k: a for k, a in FORK_ATTR.items() if getattr(self, FORK_FLAG[k], False) and hasattr(self, a)}
+
+    def parameters(self):
+        return [getattr(self, a) for a in list(GROUP_ATTR.values()) + list(self._fork_attrs().values())]
+
+    # ---- initialisation :200-238 ------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def create_from_pcd(self, points, colors=None, spatial_lr_scale: float = 1.0, *, dir_noise=None, dist2=None,
+                        device=None):
+        """``create_from_pcd(pcd, spatial_lr_scale)``.  points / colors: ``[N, 3]`` arrays or tensors (colours in
+        [0, 1]), or one object with ``.points`` / ``.colors`` in place of both.  A tensor must already live on the GPU;
+        arrays are moved to ``device`` (default: the current ROCm device).
+        dir_noise: the ``[N, 3]`` standard-normal draws of ``:227`` (``continous_dir``; default ``torch.randn``).
+        dist2: the ``[N]`` result of ``distCUDA2`` if the caller already has it (default: ``knn.distCUDA2``)."""
+        if hasattr(points, "points") and hasattr(points, "colors"):      # create_from_pcd(pcd, spatial_lr_scale)
+            if colors is not None:
+                spatial_lr_scale = colors
+            points, colors = points.points, points.colors
+        if colors is None:
+            raise TypeError("create_from_pcd needs points and colors")
+
+        def on_device(a, name):
+            if isinstance(a, torch.Tensor):
+                _need_gpu("create_from_pcd", a)
+                return a.detach().float()
+            dev = torch.device(device if device is not None else "cuda")
+            if dev.type != "cuda" or not torch.cuda.is_available():
+                raise _lib.GsrError("create_from_pcd needs a ROCm GPU (no CPU path)")
+            return torch.tensor(np.asarray(a)).float().to(dev)
+
+        xyz = on_device(points, "points").contiguous()
+        rgb = on_device(colors, "colors").to(xyz.device)
+        if xyz.dim() != 2 or xyz.shape[1] != 3 or rgb.shape != xyz.shape:
+            raise ValueError(f"points and colors must both be [N, 3], got {tuple(xyz.shape)} and {tuple(rgb.shape)}")
+        dev, N = xyz.device, int(xyz.shape[0])
+        M = (self.max_sh_degree + 1) ** 2
+        self.spatial_lr_scale = spatial_lr_scale
+        f_dc = RGB2SH(rgb).reshape(N, 1, 3).contiguous()                              # :203-206, :218
+        f_rest = torch.zeros((N, M - 1, 3), dtype=torch.float32, device=dev)          # :219
+        if dist2 is None:
+            dist2 = knn.distCUDA2(xyz)
+        else:
+            dist2 = torch.as_tensor(dist2, dtype=torch.float32).to(dev)
+            if tuple(dist2.shape) != (N,):
+                raise ValueError(f"dist2 must be [{N}], got {tuple(dist2.shape)}")
+        dist2 = torch.clamp_min(dist2, MIN_DIST2)                                     # :210
+        scales = torch.log(torch.sqrt(dist2))[..., None].repeat(1, 3)                 # :211
+        rots = torch.zeros((N, 4), dtype=torch.float32, device=dev)                   # :212-213
+        rots[:, 0] = 1
+        opacities = inverse_sigmoid(INITIAL_OPACITY * torch.ones((N, 1), dtype=torch.float32, device=dev))   # :215
+
+        def param(t):
+            return nn.Parameter(t.contiguous().requires_grad_(True))
+
+        self._xyz = param(xyz.clone())
+        self._features_dc = param(f_dc)
+        self._features_rest = param(f_rest)
+        self._scaling = param(scales)
+        self._rotation = param(rots)
+        self._opacity = param(opacities)
+        if self.grow_dir:                                                             # :223-225
+            self._dirs_prob = param(torch.ones((N, self.num_dirs), dtype=torch.float32, device=dev) / self.num_dirs)
+            self.dirs = self.dirs.to(dev)
+        if self.continous_dir:                                                        # :226-228
+            if dir_noise is None:
+                dir_noise = torch.randn((N, 3), dtype=torch.float32, device=dev)
+            dir_noise = torch.as_tensor(dir_noise, dtype=torch.float32).to(dev)
+            if tuple(dir_noise.shape) != (N, 3):
+                raise ValueError(f"dir_noise must be [{N}, 3], got {tuple(dir_noise.shape)}")
+            self._conti_dirs = param(torch.nn.functional.normalize(dir_noise, p=2.0, dim=-1))
+        if self.grow_distance:                                                        # :229-231
+            self._grow_dist = param(torch.zeros((N, 1), dtype=torch.float32, device=dev))
+        if self.learn_split_distance:                                                 # :232-234
+            self._split_distance = param(torch.zeros((N, 3), dtype=torch.float32, device=dev))
+        if self.learn_split_scale:                                                    # :235-237
+            self._split_scale = param(torch.zeros((N, 1), dtype=torch.float32, device=dev))
+        self.max_radii2D = torch.zeros((N,), dtype=torch.float32, device=dev)         # :238
+        return self
+
+    # ---- optimizer :240-277 (optim.py) ------------------------------------------------------------------------------
+    def training_setup(self, training_args, optimizer_cls=optim.Adam):
+        self._optimizer_cls = optimizer_cls
+        return optim.training_setup(self, training_args, optimizer_cls)
+
+    def update_learning_rate(self, iteration):
+        return optim.update_learning_rate(self, iteration)
+
+    # ---- reset_opacity :312-315 with replace_tensor_to_optimizer :386-399 -------------------------------------------
+    @torch.no_grad()
+    def reset_opacity(self):
+        """Cap the opacities at 0.01 and zero the opacity group's Adam moments, in place, in one launch
+        (``gsr_reset_opacity``): ``_opacity`` stays the same ``Parameter``.  What the reference's version does besides the
+        values is kept: the state's ``step`` count stays, and ``_opacity.grad`` becomes None -- the reference builds a new
+        ``Parameter`` and resets before ``optimizer.step()`` (``train.py:136-141``), so that iteration's step skips the
+        opacity group."""
+        p = self._opacity
+        _need_gpu("reset_opacity", p)
+        if p.dtype != torch.float32 or not p.is_contiguous():
+            raise TypeError("reset_opacity needs a contiguous float32 _opacity")
+        state = self.optimizer.state.get(p, None) if self.optimizer is not None else None
+        moments = [state.get(k) if state else None for k in ("exp_avg", "exp_avg_sq")]
+        for m in moments:
+            if m is not None and not (m.is_cuda and m.device == p.device and m.dtype == torch.float32
+                                      and m.is_contiguous() and m.numel() == p.numel()):
+                raise TypeError("the opacity group's Adam moments must be contiguous float32 tensors like _opacity")
+        with torch.cuda.device(p.device):
+            stream = torch.cuda.current_stream(p.device).cuda_stream
+            _lib.check(_lib.load().gsr_reset_opacity(p.data_ptr(), p.numel(), RESET_OPACITY_CAP,
+                                                     *(m.data_ptr() if m is not None else None for m in moments),
+                                                     stream), "gsr_reset_opacity")
+        p.grad = None
+
+    # ---- checkpoints :84-149 ----------------------------------------------------------------------------------------
+    def capture(self):
+        """The reference's 12-tuple of a plain model (``:118-131``).  A model with a fork flag appends a 13th element,
+        the dict of its learned tensors by attribute name (this build's extension: the reference's own tuples for those
+        models leave the optimizer state out and cannot be restored)."""
+        out = (self.active_sh_degree, self._xyz, self._features_dc, self._features_rest, self._scaling, self._rotation,
+               self._opacity, self.max_radii2D, self.xyz_gradient_accum, self.denom, self.optimizer.state_dict(),
+               self.spatial_lr_scale)
+        fork = {a: getattr(self, a) for a in self._fork_attrs().values()}
+        return out + (fork,) if fork else out
+
+    def restore(self, model_args, training_args, optimizer_cls=None):
+        """``:133-149``; accepts the 12-tuple or the 13-tuple of ``capture``.  ``training_setup`` runs first, with
+        ``optimizer_cls`` (default: the class ``training_setup`` was last given, else ``optim.Adam``), then the saved
+        state is loaded into it: state dicts move freely between ``torch.optim.Adam`` and ``optim.Adam``."""
+        model_args = tuple(model_args)
+        if len(model_args) not in (12, 13):
+            raise ValueError(f"restore expects the 12- or 13-element tuple of capture(), got {len(model_args)} elements")
+        fork = model_args[12] if len(model_args) == 13 else {}
+        want = set(self._fork_attrs().values())
+        if not isinstance(fork, dict) or set(fork) != want:
+            raise ValueError(f"the checkpoint holds the learned tensors {sorted(fork) if isinstance(fork, dict) else fork!r}, "
+                             f"this model's flags need {sorted(want)}")
+        (self.active_sh_degree, self._xyz, self._features_dc, self._features_rest, self._scaling, self._rotation,
+         self._opacity, self.max_radii2D, xyz_gradient_accum, denom, opt_dict, self.spatial_lr_scale) = model_args[:12]
+        for a, t in fork.items():
+            setattr(self, a, t)
+        if self.grow_dir:
+            self.dirs = self.dirs.to(self._xyz.device)
+        self.training_setup(training_args, optimizer_cls or self._optimizer_cls)
+        self.xyz_gradient_accum = xyz_gradient_accum
+        self.denom = denom
+        self.optimizer.load_state_dict(opt_dict)
+
+    # ---- PLY :293-358 (ply_io.py) -----------------------------------------------------------------------------------
+    def save_ply(self, path):
+        ply_io.save_ply(self, path)
+
+    def load_ply(self, path, device=None):
+        """``load_ply``: the six parameters from the file, on ``device`` (default: where the model lives, else the
+        current ROCm device); ``active_sh_degree`` becomes ``max_sh_degree`` (``:358``)."""
+        if device is None:
+            device = self._xyz.device if self._xyz.is_cuda else "cuda"
+        if torch.device(device).type != "cuda" or not torch.cuda.is_available():
+            raise _lib.GsrError("load_ply needs a ROCm GPU (no CPU path)")
+        tensors = ply_io.load_ply(path, self.max_sh_degree, device)
+        for a in GROUP_ATTR.values():
+            setattr(self, a, nn.Parameter(tensors[a].requires_grad_(True)))
+        self.active_sh_degree = self.max_sh_degree
+
+
+__all__ = ["GaussianModel", "sphere_points", "inverse_sigmoid"]

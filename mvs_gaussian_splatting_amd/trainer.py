@@ -1,0 +1,124 @@
+"""One iteration of the reference's training loop (``train.py:72-142``) from this package's drop-ins, its
+``OptimizationParams`` defaults (``arguments/__init__.py:82-108``) and the checkpoint file of ``train.py:41,159``.
+
+    opt, pipe = OptimizationParams(), PipelineParams()
+    gaussians.training_setup(opt)
+    for iteration in range(first_iter + 1, opt.iterations + 1):
+        loss = training_iteration(gaussians, camera, opt, pipe, background, iteration, dataset=dataset,
+                                  cameras_extent=scene.cameras_extent)
+
+``training_iteration`` reads nothing back from the device: the loss it returns is a device tensor and the caller
+decides when to log it.  (Densification itself reads its row counts, as the reference's does.)
+"""
+from __future__ import annotations
+
+import torch
+
+from .densify import densify_and_prune
+from .losses import add_densification_stats, l1_dssim_loss, opacity_sparsity_loss
+from .renderer import render
+from .synthetic import PipelineParams  # noqa: F401  (the two parameter classes live side by side)
+
+
+class OptimizationParams:
+    """``arguments/__init__.py:82-108`` defaults."""
+    iterations = 30_000
+    position_lr_init = 0.00016
+    position_lr_final = 0.0000016
+    position_lr_delay_mult = 0.01
+    position_lr_max_steps = 30_000
+    feature_lr = 0.0025
+    opacity_lr = 0.05
+    scaling_lr = 0.005
+    rotation_lr = 0.001
+    percent_dense = 0.01
+    growdirs_lr = 0.005
+    growdistance_lr = 0.001
+    lambda_dssim = 0.2
+    densification_interval = 100
+    opacity_reset_interval = 3000
+    densify_from_iter = 500
+    densify_until_iter = 15_000
+    densify_grad_threshold = 0.0002
+    min_opacity = 0.005
+    random_background = False
+    opacitysparse = 0.0
+    splitdistance_lr = 0.005
+    splitscale_lr = 0.005
+
+    def __init__(self, **overrides):
+        for k, v in overrides.items():
+            if not hasattr(type(self), k):
+                raise TypeError(f"OptimizationParams has no field {k!r}")
+            setattr(self, k, v)
+
+
+def schedule(opt, iteration: int, white_background: bool = False) -> dict:
+    """Which steps of ``train.py:72-142`` fire at ``iteration`` -- host arithmetic only:
+    ``sh_up`` (:75), ``stats`` (:127), ``densify`` and its ``size_threshold`` (:132-133), ``reset`` (:136), ``step`` (:140)."""
+    stats = iteration < opt.densify_until_iter
+    densify = stats and iteration > opt.densify_from_iter and iteration % opt.densification_interval == 0
+    reset = stats and (iteration % opt.opacity_reset_interval == 0 or
+                       (white_background and iteration == opt.densify_from_iter))
+    return {"sh_up": iteration % 1000 == 0, "stats": stats, "densify": densify,
+            "size_threshold": 20 if iteration > opt.opacity_reset_interval else None,
+            "reset": reset, "step": iteration < opt.iterations}
+
+
+def training_iteration(model, camera, opt, pipe, background, iteration, *, dataset=None, cameras_extent,
+                       first_reset=None, gt_image=None, densify_kwargs=None):
+    """``train.py:72-142`` for one camera, in the reference's order: learning rate, SH degree, background, ``render``
+    with the fork's keyword arguments, L1 + D-SSIM against ``camera.original_image``, the opacity sparsity term
+    (``opt.opacitysparse``), ``backward``; then, without gradients, the densification statistics, ``densify_and_prune``,
+    ``reset_opacity``, and the optimizer step.  Returns the loss, a 0-dim device tensor.
+
+    dataset: the reference's model namespace (``grow_dir``, ``continous_dir``, ``grow_distance``, the learned-split
+    switches, ``white_background``); None is a plain model on a black background.
+    first_reset: whether the extra opacity reset at ``densify_from_iter`` runs (``train.py:136``); default
+    ``dataset.white_background``.
+    gt_image: the target instead of ``camera.original_image``.  densify_kwargs: passed on to ``densify_and_prune``
+    (``noise``, ``dir_noise``, ``spatial_order``)."""
+    flag = lambda name: bool(getattr(dataset, name, False))      # noqa: E731
+    if first_reset is None:
+        first_reset = flag("white_background")
+    todo = schedule(opt, iteration, first_reset)
+    model.update_learning_rate(iteration)                                                       # :72
+    if todo["sh_up"]:                                                                           # :75-76
+        model.oneupSHdegree()
+    bg = torch.rand((3), device=background.device) if opt.random_background else background    # :89
+    pkg = render(camera, model, pipe, bg, grow_dir=flag("grow_dir"), densify_grad_threshold=opt.densify_grad_threshold,
+                 iteration=iteration, opt=opt, continous_dir=flag("continous_dir"), grow_distance=flag("grow_distance"),
+                 modelcg=dataset, cameras_extent=cameras_extent)                                # :91
+    gt = camera.original_image if gt_image is None else gt_image
+    loss = l1_dssim_loss(pkg["render"], gt.to(pkg["render"].device), opt.lambda_dssim)          # :99-101
+    if opt.opacitysparse > 0:                                                                   # :102-106
+        loss = loss + opacity_sparsity_loss(model._opacity, opt.opacitysparse)
+    loss.backward()                                                                             # :107
+    with torch.no_grad():
+        if todo["stats"]:                                                                       # :127-137
+            add_densification_stats(model, pkg["viewspace_points"], pkg["radii"])
+            if todo["densify"]:
+                densify_and_prune(model, opt.densify_grad_threshold, opt.min_opacity, cameras_extent,
+                                  todo["size_threshold"], opt=opt, iteration=iteration, **(densify_kwargs or {}))
+            if todo["reset"]:
+                model.reset_opacity()
+        if todo["step"]:                                                                        # :140-142
+            model.optimizer.step()
+            model.optimizer.zero_grad(set_to_none=True)
+    return loss.detach()
+
+
+def save_checkpoint(model, iteration: int, path: str) -> None:
+    """``torch.save((gaussians.capture(), iteration), path)`` (``train.py:159``)."""
+    torch.save((model.capture(), iteration), path)
+
+
+def load_checkpoint(model, path: str, opt, optimizer_cls=None) -> int:
+    """``train.py:41-42``: restores ``model`` from the file and returns the iteration it was written at.  The file is
+    a pickle of tensors, numbers and the optimizer's state dict: load only files you wrote."""
+    model_params, first_iter = torch.load(path, weights_only=False)
+    model.restore(model_params, opt, optimizer_cls)
+    return int(first_iter)
+
+
+__all__ = ["OptimizationParams", "PipelineParams", "schedule", "training_iteration", "save_checkpoint", "load_checkpoint"]
