@@ -1,0 +1,84 @@
+"""The reference's ``render.py:24-49`` on this package: load the Gaussians a training run saved under ``model_path`` and
+write every view of the scene as PNG.
+
+    python examples/render.py -m <model directory> [--iteration N] [--skip_train] [--skip_test]
+                              [-s <COLMAP or Blender directory>] [-r ...] [--eval] [--white_background]
+
+The dataset's location and options come from the ``cfg_args.json`` that ``examples/train.py -s ... -m ...`` left in the
+model directory; ``-s`` and the other switches override it.
+
+writes ``<model>/<train|test>/ours_<N>/renders/%05d.png`` and ``.../gt/%05d.png``.  The 8-bit images come from
+``metrics.to_uint8_hwc`` (torchvision's ``save_image`` rounding) on the device; Pillow only encodes the files.
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from mvs_gaussian_splatting_amd import GaussianModel, ModelParams, Scene, render, to_uint8_hwc  # noqa: E402
+from mvs_gaussian_splatting_amd.synthetic import PipelineParams  # noqa: E402
+
+
+def save_png(image, path):
+    from PIL import Image
+    Image.fromarray(to_uint8_hwc(image).cpu().numpy()).save(path)
+
+
+def render_set(model_path, name, iteration, views, gaussians, pipeline, background):
+    render_path = os.path.join(model_path, name, "ours_{}".format(iteration), "renders")
+    gts_path = os.path.join(model_path, name, "ours_{}".format(iteration), "gt")
+    os.makedirs(render_path, exist_ok=True)
+    os.makedirs(gts_path, exist_ok=True)
+    for idx, view in enumerate(views):
+        rendering = render(view, gaussians, pipeline, background)["render"]
+        save_png(rendering, os.path.join(render_path, "{0:05d}".format(idx) + ".png"))
+        save_png(view.original_image[0:3, :, :].to(rendering.device), os.path.join(gts_path, "{0:05d}".format(idx) + ".png"))
+
+
+def render_sets(dataset, iteration, pipeline, skip_train=False, skip_test=False):
+    with torch.no_grad():
+        gaussians = GaussianModel(dataset.sh_degree)
+        scene = Scene(dataset, gaussians, load_iteration=iteration, shuffle=False)
+        bg_color = [1, 1, 1] if dataset.white_background else [0, 0, 0]
+        background = torch.tensor(bg_color, dtype=torch.float32, device="cuda")
+        if not skip_train:
+            render_set(dataset.model_path, "train", scene.loaded_iter, scene.getTrainCameras(), gaussians, pipeline,
+                       background)
+        if not skip_test:
+            render_set(dataset.model_path, "test", scene.loaded_iter, scene.getTestCameras(), gaussians, pipeline,
+                       background)
+    return scene
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("-s", "--source_path", default=None)
+    ap.add_argument("-m", "--model_path", required=True)
+    ap.add_argument("--images", default=None)
+    ap.add_argument("-r", "--resolution", type=int, default=None)
+    ap.add_argument("--eval", action="store_true", default=None)
+    ap.add_argument("--white_background", action="store_true", default=None)
+    ap.add_argument("--iteration", type=int, default=-1)
+    ap.add_argument("--skip_train", action="store_true")
+    ap.add_argument("--skip_test", action="store_true")
+    args = ap.parse_args(argv)
+    fields = {}
+    cfg = os.path.join(args.model_path, "cfg_args.json")
+    if os.path.exists(cfg):
+        with open(cfg) as f:
+            fields = json.load(f)
+    for k in ("source_path", "images", "resolution", "eval", "white_background"):
+        if getattr(args, k) is not None:
+            fields[k] = getattr(args, k)
+    if not fields.get("source_path"):
+        ap.error("no cfg_args.json in the model directory: give the dataset with -s")
+    dataset = ModelParams(model_path=args.model_path, **fields)
+    print("Rendering " + args.model_path)
+    render_sets(dataset, args.iteration, PipelineParams(), args.skip_train, args.skip_test)
+
+
+if __name__ == "__main__":
+    main()

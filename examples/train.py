@@ -3,13 +3,20 @@
 SH degree steps, densification, opacity resets, the optional opacity sparsity term), checkpoint, resume, write a PLY.
 
     python examples/train.py [--iterations N] [--checkpoint_iterations N ...] [--start_checkpoint FILE] [--out DIR]
+    python examples/train.py -s <COLMAP or Blender directory> -m <output directory> [-r 1|2|4|8|width] [--eval]
+                             [--white_background] [--images DIR] [--data_device cuda|cpu] [--save_iterations N ...]
+
+With ``-s`` the example trains on a dataset through ``Scene`` (``scene.py``) and saves
+``<output>/point_cloud/iteration_N/point_cloud.ply``, which ``examples/render.py -m <output>`` renders.  Without it:
 
 The scene: a ground-truth cloud rendered from orbit views gives the images; the model starts, as the reference's does
 from a COLMAP cloud, from a jittered subsample of the ground truth's centres with their base colours.
 """
 import argparse
+import json
 import math
 import os
+import random
 import sys
 import types
 
@@ -93,8 +100,50 @@ def train(model, problem, opt, first_iter=0, last_iter=None, dataset=None, pipe=
     return losses
 
 
+def train_scene(args, dev):
+    """``train.py:34-160`` on a dataset: ``Scene`` loads it, a random camera is popped from a copy of the training list
+    that is refilled when it empties (:81-83), the model is saved at ``--save_iterations`` and at the end."""
+    from mvs_gaussian_splatting_amd import ModelParams, Scene
+    dataset = ModelParams(source_path=args.source_path, model_path=args.model_path, images=args.images,
+                          resolution=args.resolution, white_background=args.white_background,
+                          data_device=args.data_device, eval=args.eval)
+    n = args.iterations
+    opt = example_opt(n, opacitysparse=args.opacitysparse) if n < 3000 else \
+        OptimizationParams(iterations=n, opacitysparse=args.opacitysparse)
+    model = GaussianModel(dataset.sh_degree)
+    scene = Scene(dataset, model)
+    with open(os.path.join(args.model_path, "cfg_args.json"), "w") as f:         # what examples/render.py -m needs
+        json.dump({k: getattr(dataset, k) for k in ("source_path", "images", "resolution", "white_background", "eval",
+                                                    "sh_degree")}, f)
+    model.training_setup(opt)
+    first_iter = load_checkpoint(model, args.start_checkpoint, opt) if args.start_checkpoint else 0
+    bg = torch.tensor([1.0, 1.0, 1.0] if dataset.white_background else [0.0, 0.0, 0.0], device=dev)
+    pipe, stack, loss = PipelineParams(), None, None
+    for iteration in range(first_iter + 1, n + 1):
+        if not stack:
+            stack = scene.getTrainCameras().copy()
+        cam = stack.pop(random.randint(0, len(stack) - 1))
+        loss = training_iteration(model, cam, opt, pipe, bg, iteration, dataset=dataset,
+                                  cameras_extent=scene.cameras_extent)
+        if iteration % 10 == 0:
+            print(f"iteration {iteration}: loss {float(loss):.5f}  points {model._xyz.shape[0]}")
+        if iteration in args.save_iterations or iteration == n:
+            scene.save(iteration)
+            print(f"[ITER {iteration}] saved the Gaussians under {args.model_path}")
+        if iteration in args.checkpoint_iterations:
+            save_checkpoint(model, iteration, os.path.join(args.model_path, f"chkpnt{iteration}.pth"))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("-s", "--source_path", default=None)
+    ap.add_argument("-m", "--model_path", default=None)
+    ap.add_argument("--images", default="images")
+    ap.add_argument("-r", "--resolution", type=int, default=-1)
+    ap.add_argument("--eval", action="store_true")
+    ap.add_argument("--white_background", action="store_true")
+    ap.add_argument("--data_device", default="cuda")
+    ap.add_argument("--save_iterations", type=int, nargs="*", default=[])
     ap.add_argument("--iterations", type=int, default=200)
     ap.add_argument("--checkpoint_iterations", type=int, nargs="*", default=[])
     ap.add_argument("--start_checkpoint", default=None)
@@ -102,6 +151,10 @@ def main(argv=None):
     ap.add_argument("--out", default=os.path.dirname(os.path.abspath(__file__)))
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
+    if args.source_path:
+        if not args.model_path:
+            ap.error("-s needs -m, the directory the model is saved under")
+        return train_scene(args, dev)
     n = args.iterations
     opt = example_opt(n, opacitysparse=args.opacitysparse)
     dataset = types.SimpleNamespace(white_background=False)

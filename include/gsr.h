@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 18
+#define GSR_ABI_VERSION 19
 
 enum {
   GSR_OK = 0,
@@ -522,6 +522,29 @@ int gsr_opacity_sparsity_fwd(const float* opacity_raw, int64_t P, float weight, 
 int gsr_opacity_sparsity_bwd(const float* opacity_raw, int64_t P, float threshold, const float* record,
                              const float* grad_out, float* grad_raw, void* stream);
 int gsr_reset_opacity(float* opacity_raw, int64_t P, float cap, float* exp_avg, float* exp_avg_sq, void* stream);
+
+/* Load-time image ingest, ABI v19 (csrc/image.hip): the per-image work of the reference's scene loading between the
+ * file decode and the training target, on the caller's stream.  Images are device uint8, HWC, densely packed.
+ *   gsr_image_composite_u8: the Blender reader's alpha composite (scene/dataset_readers.py:204-210).  rgba [H,W,4]
+ *     (4-byte aligned) -> rgb [H,W,3]; per channel, in float64 with every operation rounded on its own,
+ *       n = v / 255.0;  arr = n_rgb * n_a + bg * (1 - n_a);  byte = low 8 bits of trunc(arr * 255.0)
+ *     (the reference casts to int8 and hands those bytes to an 8-bit RGB image).  bg: three values in [0, 1].
+ *   gsr_image_resize_u8: Pillow's Image.resize((out_w, out_h)) with its default bicubic filter for C = 1 or 3, bit
+ *     for bit: a horizontal pass, then a vertical one; a pass whose size does not change is skipped (with neither, a
+ *     copy).  Per output index o a pass reads bounds[2o] = first input index, bounds[2o+1] = tap count (<= ksize) and
+ *     int32 taps[o*ksize .. ], the host's restatement of Pillow's precompute_coeffs / normalize_coeffs_8bpc
+ *     (image_ingest.resize_tables); out = clamp((2^21 + sum pixel * tap) >> 22, 0, 255), stored as uint8 between the
+ *     passes.  h_* may be NULL when out_w == in_w, v_* when out_h == in_h; tmp ([in_h, out_w, C] bytes) only when both
+ *     passes run.  src, tmp and dst must not overlap.
+ *   gsr_image_to_float_chw: src [H,W,C], C = 3 or 4 (4: 4-byte aligned) -> dst float [3,H,W]:
+ *     clamp(float(v) / 255.0f, 0, 1), times float(a) / 255.0f when C == 4 (utils/general_utils.py:21-27,
+ *     utils/camera_utils.py:43-47, scene/cameras.py:39-46); bit-equal to torch's `uint8 / 255.0` and `*=`. */
+int gsr_image_composite_u8(const uint8_t* rgba, int32_t H, int32_t W, double bg_r, double bg_g, double bg_b,
+                           uint8_t* rgb, void* stream);
+int gsr_image_resize_u8(const uint8_t* src, int32_t C, int32_t in_h, int32_t in_w, int32_t out_h, int32_t out_w,
+                        const int32_t* h_bounds, const int32_t* h_taps, int32_t h_ksize, const int32_t* v_bounds,
+                        const int32_t* v_taps, int32_t v_ksize, uint8_t* tmp, uint8_t* dst, void* stream);
+int gsr_image_to_float_chw(const uint8_t* src, int32_t C, int32_t H, int32_t W, float* dst, void* stream);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # instead of copying it over the in-tree library
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 
 class GsrParams(C.Structure):
@@ -177,6 +177,12 @@ SYMBOLS = {
     "gsr_opacity_sparsity_bwd": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p]),
     "gsr_reset_opacity": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # load-time image ingest on uint8 HWC images (csrc/image.hip; image_ingest.py)
+    "gsr_image_composite_u8": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,
+                                         C.c_void_p, C.c_void_p]),
+    "gsr_image_resize_u8": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p, C.c_int32] * 2 +
+                            [C.c_void_p] * 3),
+    "gsr_image_to_float_chw": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -1035,4 +1035,55 @@ int gsr_reset_opacity(float* opacity_raw, int64_t P, float cap, float* exp_avg, 
   return check(nullptr, s, "reset_opacity");
 }
 
+static int image_shape_ok(int32_t H, int32_t W) { return H > 0 && W > 0 && (int64_t)H * (int64_t)W <= (int64_t)1 << 28; }
+int gsr_image_composite_u8(const uint8_t* rgba, int32_t H, int32_t W, double bg_r, double bg_g, double bg_b,
+                           uint8_t* rgb, void* stream) {
+  if (!rgba || !rgb) return fail(GSR_E_BADARG, "NULL image");
+  if (!image_shape_ok(H, W)) return fail(GSR_E_BADARG, "bad image shape");
+  const double bg[3] = {bg_r, bg_g, bg_b};
+  for (double b : bg)
+    if (!(b >= 0.0 && b <= 1.0)) return fail(GSR_E_BADARG, "background must lie in [0, 1]");
+  if (((uintptr_t)rgba & 3u) != 0) return fail(GSR_E_ALIGN, "the RGBA image must be 4-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_image_composite_u8(rgba, (size_t)H * (size_t)W, bg, rgb, s);
+  return check(nullptr, s, "image_composite_u8");
+}
+int gsr_image_resize_u8(const uint8_t* src, int32_t C, int32_t in_h, int32_t in_w, int32_t out_h, int32_t out_w,
+                        const int32_t* h_bounds, const int32_t* h_taps, int32_t h_ksize, const int32_t* v_bounds,
+                        const int32_t* v_taps, int32_t v_ksize, uint8_t* tmp, uint8_t* dst, void* stream) {
+  if (!src || !dst) return fail(GSR_E_BADARG, "NULL image");
+  if (C != 1 && C != 3) return fail(GSR_E_BADARG, "resize takes 1 or 3 channels");
+  if (!image_shape_ok(in_h, in_w) || !image_shape_ok(out_h, out_w) || !image_shape_ok(in_h, out_w))
+    return fail(GSR_E_BADARG, "bad image shape");
+  const bool horiz = out_w != in_w, vert = out_h != in_h;
+  if (horiz && (!h_bounds || !h_taps || h_ksize <= 0)) return fail(GSR_E_BADARG, "horizontal pass needs its tap table");
+  if (vert && (!v_bounds || !v_taps || v_ksize <= 0)) return fail(GSR_E_BADARG, "vertical pass needs its tap table");
+  if (horiz && vert && !tmp) return fail(GSR_E_BADARG, "two passes need the intermediate image");
+  if ((((uintptr_t)h_bounds | (uintptr_t)h_taps | (uintptr_t)v_bounds | (uintptr_t)v_taps) & 3u) != 0)
+    return fail(GSR_E_ALIGN, "tap tables must be 4-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (!horiz && !vert) {
+    GSR_HIP(hipMemcpyAsync(dst, src, (size_t)in_h * (size_t)in_w * (size_t)C, hipMemcpyDeviceToDevice, s));
+    return 0;
+  }
+  const uint8_t* mid = src;
+  if (horiz) {
+    uint8_t* out = vert ? tmp : dst;
+    launch_image_resize_pass(false, C, src, in_w, out_w, in_h, h_bounds, h_taps, h_ksize, out, s);
+    mid = out;
+  }
+  if (vert) launch_image_resize_pass(true, C, mid, in_h, out_h, out_w, v_bounds, v_taps, v_ksize, dst, s);
+  return check(nullptr, s, "image_resize_u8");
+}
+int gsr_image_to_float_chw(const uint8_t* src, int32_t C, int32_t H, int32_t W, float* dst, void* stream) {
+  if (!src || !dst) return fail(GSR_E_BADARG, "NULL image");
+  if (C != 3 && C != 4) return fail(GSR_E_BADARG, "the float target needs a 3- or 4-channel image");
+  if (!image_shape_ok(H, W)) return fail(GSR_E_BADARG, "bad image shape");
+  if (((uintptr_t)dst & 3u) != 0 || (C == 4 && ((uintptr_t)src & 3u) != 0))
+    return fail(GSR_E_ALIGN, "the float image and a 4-channel source must be 4-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_image_to_float_chw(src, C, (size_t)H * (size_t)W, dst, s);
+  return check(nullptr, s, "image_to_float_chw");
+}
+
 }  // extern "C"

@@ -173,6 +173,12 @@ void launch_opacity_sparsity_bwd(const float* raw, size_t P, float thr, const fl
                                  float* grad_raw, hipStream_t s);
 void launch_reset_opacity(float* raw, size_t P, float cap, float* exp_avg, float* exp_avg_sq, hipStream_t s);
 
+// image.hip: load-time ingest of uint8 HWC images (one resize pass per call; bounds / taps: include/gsr.h)
+void launch_image_composite_u8(const uint8_t* rgba, size_t pixels, const double bg[3], uint8_t* rgb, hipStream_t s);
+void launch_image_resize_pass(bool vertical, int C, const uint8_t* in, int in_len, int out_len, int other,
+                              const int32_t* bounds, const int32_t* taps, int ksize, uint8_t* out, hipStream_t s);
+void launch_image_to_float_chw(const uint8_t* in, int C, size_t pixels, float* out, hipStream_t s);
+
 // knn.hip
 size_t knn_workspace_bytes(int N);
 void launch_knn3(const float* pts, int N, float* mean_dist2, void* ws, hipStream_t s);

@@ -59,6 +59,22 @@ def save_ply(model, path: str) -> None:
         f.write(np.ascontiguousarray(cols).tobytes())
 
 
+_PLY_NAMES = {"i1": "char", "u1": "uchar", "i2": "short", "u2": "ushort", "i4": "int", "u4": "uint", "f4": "float",
+              "f8": "double"}
+
+
+def write_ply_vertices(path: str, elements: np.ndarray) -> None:
+    """``PlyData([PlyElement.describe(elements, 'vertex')]).write(path)``: the header ``plyfile`` writes for a structured
+    array (binary little-endian, one ``property <type> <name>`` per field) and the array's bytes."""
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {elements.shape[0]}"]
+    header += [f"property {_PLY_NAMES[elements.dtype[n].str[1:]]} {n}" for n in elements.dtype.names]
+    header.append("end_header")
+    packed = np.dtype([(n, "<" + elements.dtype[n].str[1:]) for n in elements.dtype.names])
+    with open(path, "wb") as f:
+        f.write(("\n".join(header) + "\n").encode("ascii"))
+        f.write(np.ascontiguousarray(elements.astype(packed)).tobytes())
+
+
 def read_ply_vertices(path: str) -> Tuple[np.ndarray, List[str]]:
     """Structured array of the ``vertex`` element of a binary-little-endian or ascii PLY, and its property names."""
     with open(path, "rb") as f:

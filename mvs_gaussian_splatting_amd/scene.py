@@ -1,0 +1,244 @@
+"""``Scene``, ``Camera`` and ``loadCam`` of the reference's ingest layer (``scene/__init__.py``, ``scene/cameras.py``,
+``utils/camera_utils.py``): point the package at a COLMAP or Blender directory.
+
+    dataset = ModelParams(source_path=..., model_path=..., resolution=-1)
+    gaussians = GaussianModel(dataset.sh_degree)
+    scene = Scene(dataset, gaussians)
+    for camera in scene.getTrainCameras(): ...          # camera.original_image is the [3, H, W] float32 target
+
+The readers are ``dataset_readers``; every image goes from its decoded bytes to the training target on the GPU
+(``image_ingest.load_image``).  One thing differs from the reference on purpose: ``loadCam`` tests ``shape[1] == 4`` (the
+image *height*) to find an alpha channel, so there an RGBA image's mask is applied only to images four pixels tall;
+here the alpha channel of an RGBA image always multiplies the target, which is what ``Camera.__init__`` does with the
+mask it is given.
+"""
+from __future__ import annotations
+
+import json
+import os
+import random
+
+import numpy as np
+import torch
+
+from . import image_ingest
+from .dataset_readers import decode_image, fov2focal, sceneLoadTypeCallbacks
+from .synthetic import get_projection_matrix, get_world2view2
+
+
+class ModelParams:
+    """``arguments/__init__.py:47-66`` defaults."""
+    sh_degree = 3
+    source_path = ""
+    model_path = ""
+    images = "images"
+    resolution = -1
+    white_background = False
+    data_device = "cuda"
+    eval = False
+    grow_dir = False
+    continous_dir = False
+    grow_distance = False
+    num_dirs = 128
+    prob_notreinit = False
+    symmetric_split = False
+    split_notreinit = False
+    learn_split_distance = False
+    learn_split_scale = False
+
+    def __init__(self, **overrides):
+        for k, v in overrides.items():
+            if not hasattr(type(self), k):
+                raise TypeError(f"ModelParams has no field {k!r}")
+            setattr(self, k, v)
+        if self.source_path:
+            self.source_path = os.path.abspath(self.source_path)
+
+
+class Camera:
+    """``scene/cameras.py:17-57``.  image: the finished ``[3, H, W]`` float32 target (``image_ingest.load_image`` has
+    clamped and masked it already); gt_alpha_mask: a further ``[1, H, W]`` mask to multiply in, as the reference's
+    constructor does.  The matrices live on ``device``, the target on ``data_device``."""
+
+    def __init__(self, colmap_id, R, T, FoVx, FoVy, image, gt_alpha_mask, image_name, uid,
+                 trans=np.array([0.0, 0.0, 0.0]), scale=1.0, data_device="cuda", device="cuda"):
+        self.uid = uid
+        self.colmap_id = colmap_id
+        self.R = R
+        self.T = T
+        self.FoVx = FoVx
+        self.FoVy = FoVy
+        self.image_name = image_name
+        try:
+            self.data_device = torch.device(data_device)
+        except Exception as e:
+            print(e)
+            print(f"[Warning] Custom device {data_device} failed, fallback to default cuda device")
+            self.data_device = torch.device("cuda")
+        self.original_image = image.clamp(0.0, 1.0).to(self.data_device)
+        self.image_width = self.original_image.shape[2]
+        self.image_height = self.original_image.shape[1]
+        if gt_alpha_mask is not None:
+            self.original_image *= gt_alpha_mask.to(self.data_device)
+        self.zfar = 100.0
+        self.znear = 0.01
+        self.trans = trans
+        self.scale = scale
+        self.world_view_transform = torch.tensor(get_world2view2(R, T, trans, scale)).transpose(0, 1).to(device)
+        self.projection_matrix = get_projection_matrix(znear=self.znear, zfar=self.zfar, fovX=self.FoVx,
+                                                       fovY=self.FoVy).transpose(0, 1).to(device)
+        self.full_proj_transform = (self.world_view_transform.unsqueeze(0)
+                                    .bmm(self.projection_matrix.unsqueeze(0))).squeeze(0)
+        self.camera_center = self.world_view_transform.inverse()[3, :3]
+
+
+class MiniCam:
+    """``scene/cameras.py:59-70``."""
+
+    def __init__(self, width, height, fovy, fovx, znear, zfar, world_view_transform, full_proj_transform):
+        self.image_width = width
+        self.image_height = height
+        self.FoVy = fovy
+        self.FoVx = fovx
+        self.znear = znear
+        self.zfar = zfar
+        self.world_view_transform = world_view_transform
+        self.full_proj_transform = full_proj_transform
+        self.camera_center = torch.inverse(self.world_view_transform)[3][:3]
+
+
+_WARNED = False
+
+
+def load_resolution(orig_w: int, orig_h: int, resolution, resolution_scale: float = 1.0):
+    """``loadCam``'s (width, height) (``utils/camera_utils.py:20-39``): ``-r`` 1/2/4/8 divides and rounds with Python's
+    ``round``; -1 scales images wider than 1600 pixels down to 1600; any other value is the target width; those two
+    truncate with ``int``."""
+    global _WARNED
+    if resolution in [1, 2, 4, 8]:
+        return round(orig_w / (resolution_scale * resolution)), round(orig_h / (resolution_scale * resolution))
+    if resolution == -1:
+        if orig_w > 1600:
+            if not _WARNED:
+                print("[ INFO ] Encountered quite large input images (>1.6K pixels width), rescaling to 1.6K.\n "
+                      "If this is not desired, please explicitly specify '--resolution/-r' as 1")
+                _WARNED = True
+            global_down = orig_w / 1600
+        else:
+            global_down = 1
+    else:
+        global_down = orig_w / resolution
+    scale = float(global_down) * float(resolution_scale)
+    return int(orig_w / scale), int(orig_h / scale)
+
+
+def load_cam(args, id, cam_info, resolution_scale, device="cuda") -> Camera:
+    """``loadCam``: decode on the host, then composite / resize / convert on ``device``."""
+    orig_w, orig_h = cam_info.image.size
+    resolution = load_resolution(orig_w, orig_h, args.resolution, resolution_scale)
+    target = image_ingest.load_image(decode_image(cam_info), resolution, device, composite_bg=cam_info.composite_bg)
+    return Camera(colmap_id=cam_info.uid, R=cam_info.R, T=cam_info.T, FoVx=cam_info.FovX, FoVy=cam_info.FovY,
+                  image=target, gt_alpha_mask=None, image_name=cam_info.image_name, uid=id,
+                  data_device=args.data_device, device=device)
+
+
+loadCam = load_cam
+
+
+def cameraList_from_camInfos(cam_infos, resolution_scale, args, device="cuda"):
+    return [load_cam(args, id, c, resolution_scale, device) for id, c in enumerate(cam_infos)]
+
+
+def camera_to_JSON(id, camera) -> dict:
+    """``utils/camera_utils.py:62-82`` for a ``CameraInfo``."""
+    Rt = np.zeros((4, 4))
+    Rt[:3, :3] = camera.R.transpose()
+    Rt[:3, 3] = camera.T
+    Rt[3, 3] = 1.0
+    W2C = np.linalg.inv(Rt)
+    pos = W2C[:3, 3]
+    rot = W2C[:3, :3]
+    return {"id": id, "img_name": camera.image_name, "width": camera.width, "height": camera.height,
+            "position": pos.tolist(), "rotation": [x.tolist() for x in rot],
+            "fy": fov2focal(camera.FovY, camera.height), "fx": fov2focal(camera.FovX, camera.width)}
+
+
+def searchForMaxIteration(folder: str) -> int:
+    return max(int(fname.split("_")[-1]) for fname in os.listdir(folder))
+
+
+class Scene:
+    """``scene/__init__.py:21-93``.  defer_cameras: stop after the host work (readers, ``input.ply``, ``cameras.json``,
+    shuffle, ``cameras_extent``, the model's initialisation) and leave the images to a later ``load_cameras()``."""
+
+    def __init__(self, args, gaussians, load_iteration=None, shuffle=True, resolution_scales=[1.0], *,
+                 defer_cameras=False, device="cuda"):
+        self.model_path = args.model_path
+        self.loaded_iter = None
+        self.gaussians = gaussians
+        self.args = args
+        self.device = device
+        self.resolution_scales = list(resolution_scales)
+        if load_iteration:
+            if load_iteration == -1:
+                self.loaded_iter = searchForMaxIteration(os.path.join(self.model_path, "point_cloud"))
+            else:
+                self.loaded_iter = load_iteration
+            print("Loading trained model at iteration {}".format(self.loaded_iter))
+        self.train_cameras = {}
+        self.test_cameras = {}
+
+        if os.path.exists(os.path.join(args.source_path, "sparse")):
+            scene_info = sceneLoadTypeCallbacks["Colmap"](args.source_path, args.images, args.eval)
+        elif os.path.exists(os.path.join(args.source_path, "transforms_train.json")):
+            print("Found transforms_train.json file, assuming Blender data set!")
+            scene_info = sceneLoadTypeCallbacks["Blender"](args.source_path, args.white_background, args.eval)
+        else:
+            raise ValueError(f"Could not recognize scene type of {args.source_path!r}: neither sparse/ nor "
+                             f"transforms_train.json is there")
+        self.scene_info = scene_info
+
+        if not self.loaded_iter:
+            os.makedirs(self.model_path, exist_ok=True)
+            with open(scene_info.ply_path, "rb") as src_file, \
+                    open(os.path.join(self.model_path, "input.ply"), "wb") as dest_file:
+                dest_file.write(src_file.read())
+            camlist = list(scene_info.test_cameras or []) + list(scene_info.train_cameras or [])
+            json_cams = [camera_to_JSON(id, cam) for id, cam in enumerate(camlist)]
+            with open(os.path.join(self.model_path, "cameras.json"), "w") as file:
+                json.dump(json_cams, file)
+
+        if shuffle:
+            random.shuffle(scene_info.train_cameras)  # Multi-res consistent random shuffling
+            random.shuffle(scene_info.test_cameras)
+
+        self.cameras_extent = scene_info.nerf_normalization["radius"]
+        if not defer_cameras:
+            self.load_cameras()
+
+        if self.loaded_iter:
+            self.gaussians.load_ply(os.path.join(self.model_path, "point_cloud", "iteration_" + str(self.loaded_iter),
+                                                 "point_cloud.ply"))
+        else:
+            self.gaussians.create_from_pcd(scene_info.point_cloud, self.cameras_extent)
+
+    def load_cameras(self):
+        for resolution_scale in self.resolution_scales:
+            self.train_cameras[resolution_scale] = cameraList_from_camInfos(self.scene_info.train_cameras,
+                                                                            resolution_scale, self.args, self.device)
+            self.test_cameras[resolution_scale] = cameraList_from_camInfos(self.scene_info.test_cameras,
+                                                                           resolution_scale, self.args, self.device)
+
+    def save(self, iteration):
+        point_cloud_path = os.path.join(self.model_path, "point_cloud/iteration_{}".format(iteration))
+        self.gaussians.save_ply(os.path.join(point_cloud_path, "point_cloud.ply"))
+
+    def getTrainCameras(self, scale=1.0):
+        return self.train_cameras[scale]
+
+    def getTestCameras(self, scale=1.0):
+        return self.test_cameras[scale]
+
+
+__all__ = ["ModelParams", "Camera", "MiniCam", "Scene", "load_cam", "loadCam", "load_resolution",
+           "cameraList_from_camInfos", "camera_to_JSON", "searchForMaxIteration"]
