@@ -5,9 +5,13 @@ SH degree steps, densification, opacity resets, the optional opacity sparsity te
     python examples/train.py [--iterations N] [--checkpoint_iterations N ...] [--start_checkpoint FILE] [--out DIR]
     python examples/train.py -s <COLMAP or Blender directory> -m <output directory> [-r 1|2|4|8|width] [--eval]
                              [--white_background] [--images DIR] [--data_device cuda|cpu] [--save_iterations N ...]
+                             [--refine_poses [--pose_lr LR]]
 
 With ``-s`` the example trains on a dataset through ``Scene`` (``scene.py``) and saves
-``<output>/point_cloud/iteration_N/point_cloud.ply``, which ``examples/render.py -m <output>`` renders.  Without it:
+``<output>/point_cloud/iteration_N/point_cloud.ply``, which ``examples/render.py -m <output>`` renders.
+``--refine_poses`` (off by default) wraps every training camera in a ``PoseCamera`` and refines the poses with the model
+(Adam at ``--pose_lr`` on the six pose parameters of each camera); the refined poses are written to
+``<output>/refined_poses.json`` at the end.  Without ``-s``:
 
 The scene: a ground-truth cloud rendered from orbit views gives the images; the model starts, as the reference's does
 from a COLMAP cloud, from a jittered subsample of the ground truth's centres with their base colours.
@@ -119,12 +123,17 @@ def train_scene(args, dev):
     first_iter = load_checkpoint(model, args.start_checkpoint, opt) if args.start_checkpoint else 0
     bg = torch.tensor([1.0, 1.0, 1.0] if dataset.white_background else [0.0, 0.0, 0.0], device=dev)
     pipe, stack, loss = PipelineParams(), None, None
+    train_cameras, pose_optimizer = scene.getTrainCameras(), None
+    if args.refine_poses:
+        from mvs_gaussian_splatting_amd import PoseCamera
+        train_cameras = [PoseCamera(c) for c in train_cameras]
+        pose_optimizer = torch.optim.Adam([p for c in train_cameras for p in c.parameters()], lr=args.pose_lr)
     for iteration in range(first_iter + 1, n + 1):
         if not stack:
-            stack = scene.getTrainCameras().copy()
+            stack = train_cameras.copy()
         cam = stack.pop(random.randint(0, len(stack) - 1))
         loss = training_iteration(model, cam, opt, pipe, bg, iteration, dataset=dataset,
-                                  cameras_extent=scene.cameras_extent)
+                                  cameras_extent=scene.cameras_extent, pose_optimizer=pose_optimizer)
         if iteration % 10 == 0:
             print(f"iteration {iteration}: loss {float(loss):.5f}  points {model._xyz.shape[0]}")
         if iteration in args.save_iterations or iteration == n:
@@ -132,6 +141,10 @@ def train_scene(args, dev):
             print(f"[ITER {iteration}] saved the Gaussians under {args.model_path}")
         if iteration in args.checkpoint_iterations:
             save_checkpoint(model, iteration, os.path.join(args.model_path, f"chkpnt{iteration}.pth"))
+    if args.refine_poses:
+        poses = {c.image_name: dict(zip(("R", "T"), (a.tolist() for a in c.pose()))) for c in train_cameras}
+        with open(os.path.join(args.model_path, "refined_poses.json"), "w") as f:
+            json.dump(poses, f)
 
 
 def main(argv=None):
@@ -148,6 +161,8 @@ def main(argv=None):
     ap.add_argument("--checkpoint_iterations", type=int, nargs="*", default=[])
     ap.add_argument("--start_checkpoint", default=None)
     ap.add_argument("--opacitysparse", type=float, default=0.0)
+    ap.add_argument("--refine_poses", action="store_true", help="with -s: refine the training cameras' poses too")
+    ap.add_argument("--pose_lr", type=float, default=1e-4)
     ap.add_argument("--out", default=os.path.dirname(os.path.abspath(__file__)))
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 19
+#define GSR_ABI_VERSION 20
 
 enum {
   GSR_OK = 0,
@@ -138,6 +138,16 @@ typedef struct GsrGrads {
   float* stats_xyz_gradient_accum; /* device [P] (the reference keeps [P,1]) */
   float* stats_denom;              /* device [P] */
   float* stats_max_radii2D;        /* device [P] */
+  /* Camera gradients (ABI v20): all three NULL, or all three set -- then camera_ws is required, the per-Gaussian
+   * backward runs its camera instantiation and a one-block kernel behind it stores the three gradients (float32,
+   * written in full, reproducible bit for bit: block partials in double, added in a fixed order, no atomics).
+   * Layout as the inputs: m[4*row + col] of the row-vector-convention matrices.  dL_dviewmatrix column 3 and
+   * dL_dprojmatrix column 2 are exact zeros (the rasterizer does not read those entries); dL_dcampos is exactly zero
+   * with colors_precomp or at active SH degree 0.  Every other output is bit-identical with and without them. */
+  float* dL_dviewmatrix;           /* device [16] */
+  float* dL_dprojmatrix;           /* device [16] */
+  float* dL_dcampos;               /* device [3] */
+  void* camera_ws;                 /* device scratch of gsr_camera_grad_bytes(P) bytes, 256-byte aligned */
 } GsrGrads;
 
 /* ---- introspection ------------------------------------------------------------------ */
@@ -151,6 +161,7 @@ size_t gsr_image_bytes(int32_t width, int32_t height);   /* per-pixel + per-tile
 size_t gsr_binning_bytes(uint32_t num_rendered, uint32_t num_visible, int32_t width, int32_t height,
                          int32_t binning_mode);          /* keys/values/sort scratch ("binningBuffer") */
 size_t gsr_backward_bytes(int32_t P, uint32_t num_rendered); /* per-instance gradient rows + flags */
+size_t gsr_camera_grad_bytes(int32_t P);                 /* GsrGrads.camera_ws: 27 double sums per block of 256 Gaussians */
 
 /* ---- forward -------------------------------------------------------------------------- */
 /* Stage 1: preprocess (cull, project, cov3D->cov2D->conic, radius, tile rect, SH->RGB) and the

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # instead of copying it over the in-tree library
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")
 
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 
 class GsrParams(C.Structure):
@@ -39,6 +39,9 @@ class GsrGrads(C.Structure):
         ("dL_dcolors", C.c_void_p), ("dL_dopacities", C.c_void_p), ("dL_dscales", C.c_void_p),
         ("dL_drotations", C.c_void_p), ("dL_dcov3D", C.c_void_p), ("dL_dshs_rest", C.c_void_p),
         ("stats_xyz_gradient_accum", C.c_void_p), ("stats_denom", C.c_void_p), ("stats_max_radii2D", C.c_void_p),
+        # camera gradients: all three NULL or all three set, then camera_ws (gsr_camera_grad_bytes(P)) is required
+        ("dL_dviewmatrix", C.c_void_p), ("dL_dprojmatrix", C.c_void_p), ("dL_dcampos", C.c_void_p),
+        ("camera_ws", C.c_void_p),
     ]
 
 
@@ -101,6 +104,7 @@ SYMBOLS = {
     "gsr_image_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "gsr_binning_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32]),
     "gsr_backward_bytes": (C.c_size_t, [C.c_int32, C.c_uint32]),
+    "gsr_camera_grad_bytes": (C.c_size_t, [C.c_int32]),
     "gsr_forward_preprocess": (C.c_int, [C.POINTER(GsrParams), C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "gsr_forward_render": (C.c_int, [C.POINTER(GsrParams), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,

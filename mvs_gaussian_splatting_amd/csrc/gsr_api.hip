@@ -200,6 +200,7 @@ size_t gsr_binning_bytes(uint32_t num_rendered, uint32_t num_visible, int32_t, i
   return BinLayout(num_rendered, num_visible, mode).bytes;
 }
 size_t gsr_backward_bytes(int32_t P, uint32_t num_rendered) { return BwdLayout(P, num_rendered).bytes; }
+size_t gsr_camera_grad_bytes(int32_t P) { return camera_grad_bytes(P); }
 size_t gsr_sort_scratch_bytes(uint32_t n) { return SortLayout(n).bytes; }
 
 }  // extern "C"
@@ -500,7 +501,18 @@ int gsr_backward(const GsrParams* p, const int32_t* radii, const void* geom_ws, 
   if (p && p->forward_only) return fail(GSR_E_BADARG, "the forward ran with forward_only = 1: no state for a backward");
   if (int rc = validate(p)) return rc;
   if (!grads) return fail(GSR_E_BADARG, "grads is NULL");
-  if (p->P == 0) return 0;
+  const int n_cam = (grads->dL_dviewmatrix != nullptr) + (grads->dL_dprojmatrix != nullptr) + (grads->dL_dcampos != nullptr);
+  if (n_cam != 0 && n_cam != 3)
+    return fail(GSR_E_BADARG, "dL_dviewmatrix / dL_dprojmatrix / dL_dcampos must be given together");
+  if (n_cam && !grads->camera_ws) return fail(GSR_E_BADARG, "camera gradients need camera_ws (gsr_camera_grad_bytes(P) bytes)");
+  if (n_cam && ((uintptr_t)grads->camera_ws & 255u) != 0) return fail(GSR_E_ALIGN, "camera_ws must be 256-byte aligned");
+  if (p->P == 0) {
+    if (n_cam) {        // no Gaussian: the three camera gradients are zeros
+      launch_camera_grad_finish(*grads, 0, static_cast<hipStream_t>(stream));
+      return check(p, static_cast<hipStream_t>(stream), "camera_grad_finish");
+    }
+    return 0;
+  }
   if (!radii || !geom_ws || !img_ws || !dL_dout_color || !bwd_ws) return fail(GSR_E_BADARG, "NULL workspace / input");
   if (!grads->dL_dmeans3D || !grads->dL_dmeans2D || !grads->dL_dopacities)
     return fail(GSR_E_BADARG, "dL_dmeans3D / dL_dmeans2D / dL_dopacities must be non-NULL");

@@ -24,6 +24,11 @@ void launch_scan_block_sums(const uint32_t* sums_a, uint32_t* offs_a, uint32_t* 
 void launch_preprocess_bwd(const GsrParams& p, const int32_t* radii, const GeomRec* rec, const uint32_t* slot_base,
                            const GradRow* rows,
                            const uint8_t* row_flags, const GsrGrads& g, hipStream_t s);
+// camera gradients (GsrGrads.dL_dviewmatrix ...): launch_preprocess_bwd then runs the camera instantiation, whose blocks
+// leave 27 double sums each in g.camera_ws (camera_grad_bytes(P) bytes), and the one-block finish that adds the first
+// nslots of them in a fixed order (nslots = 0: writes zeros)
+size_t camera_grad_bytes(int P);
+void launch_camera_grad_finish(const GsrGrads& g, int nslots, hipStream_t s);
 
 // binning.hip
 void launch_duplicate_with_keys(int P, int grid_x, const BinInfo* bin, const uint32_t* block_offs, uint32_t* slot_base,

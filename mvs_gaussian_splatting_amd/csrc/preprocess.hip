@@ -567,6 +567,15 @@ __global__ __launch_bounds__(1024) void scan_block_sums_kernel(const uint32_t* _
 // (written by the compositing backward) in slot order, then chains conic -> cov2D -> cov3D /
 // mean, mean2D -> mean3D, colour -> SH (+ direction), cov3D -> scale / rotation.
 // ------------------------------------------------------------------------------------------
+//
+// CAM = true (GsrGrads.dL_dviewmatrix / dL_dprojmatrix / dL_dcampos set) is the camera instantiation: the same body, and
+// every active lane also forms the CAM_TERMS = 27 per-Gaussian terms of dL/dviewmatrix (rows 0-3 x columns 0-2),
+// dL/dprojmatrix (rows 0-3 x columns 0, 1, 3) and dL/dcampos from the quantities it holds anyway.  The terms are added
+// across the wave and then across the block's four waves in double, in a fixed order, and the block stores its 27 sums in
+// its own slot of GsrGrads.camera_ws; camera_grad_finish_kernel adds the slots.  No atomics: the result is reproducible
+// bit for bit.  CAM = false compiles to the float operations this kernel had before the camera variant existed.
+constexpr int CAM_TERMS = 27;     // [0,12): dV[i][c] at 3 i + c;  [12,24): dM[i][0 | 1 | 3] at 12 + 3 i + k;  [24,27): dcampos
+template <bool CAM>
 __global__ __launch_bounds__(PRE_BLOCK) void preprocess_bwd_kernel(GsrParams p, const int32_t* __restrict__ radii,
                                                                    const GeomRec* __restrict__ rec,
                                                                    const uint32_t* __restrict__ slot_base,
@@ -590,6 +599,11 @@ __global__ __launch_bounds__(PRE_BLOCK) void preprocess_bwd_kernel(GsrParams p, 
   float dcov[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   float dscale[3] = {0.f, 0.f, 0.f};
   float drot[4] = {0.f, 0.f, 0.f, 0.f};
+  float cam[CAM ? CAM_TERMS : 1];
+  if constexpr (CAM) {
+#pragma unroll
+    for (int k = 0; k < CAM_TERMS; ++k) cam[k] = 0.f;
+  }
   const bool vis = valid && radii[idx] > 0;
   const int wave_first = blockIdx.x * PRE_BLOCK + wid * WAVE;
   const int rows_valid = min(WAVE, p.P - wave_first);
@@ -809,6 +823,20 @@ __global__ __launch_bounds__(PRE_BLOCK) void preprocess_bwd_kernel(GsrParams p, 
     // view = [p,1] @ V  ->  dL/dp_i = sum_c V[i][c] dv_c   (assigned, A.6 (ii))
 #pragma unroll
     for (int i = 0; i < 3; ++i) dmean[i] = V.m[4 * i + 0] * dvx + V.m[4 * i + 1] * dvy + V.m[4 * i + 2] * dvz;
+    if constexpr (CAM) {
+      // the same two paths towards V: view = [p,1] @ V, and A = J W with W the upper 3x3 of V
+      const float pq[4] = {px, py, pz, 1.0f}, dv[3] = {dvx, dvy, dvz};
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) cam[3 * i + c] = pq[i] * dv[c];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        cam[3 * j + 0] += pr.j00 * dA0[j];
+        cam[3 * j + 1] += pr.j11 * dA1[j];
+        cam[3 * j + 2] += pr.j02 * dA0[j] + pr.j12 * dA1[j];
+      }
+    }
 
     // ---- (iii) mean2D (NDC units) -> mean3D through p_hom / (w + 1e-7) ----------------------
     {
@@ -821,6 +849,17 @@ __global__ __launch_bounds__(PRE_BLOCK) void preprocess_bwd_kernel(GsrParams p, 
       for (int i = 0; i < 3; ++i) {
         dmean[i] += (Mx.m[4 * i + 0] * m_w - Mx.m[4 * i + 3] * mul1) * dm2x +
                     (Mx.m[4 * i + 1] * m_w - Mx.m[4 * i + 3] * mul2) * dm2y;
+      }
+      if constexpr (CAM) {
+        // ndc = (hx, hy) / (hw + 1e-7) with h = [p,1] @ M: columns 0, 1 and 3 of M
+        const float pq[4] = {px, py, pz, 1.0f};
+        const float dhw = mul1 * dm2x + mul2 * dm2y;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          cam[12 + 3 * i + 0] = pq[i] * m_w * dm2x;
+          cam[12 + 3 * i + 1] = pq[i] * m_w * dm2y;
+          cam[12 + 3 * i + 2] = -(pq[i] * dhw);
+        }
       }
     }
 
@@ -911,9 +950,15 @@ __global__ __launch_bounds__(PRE_BLOCK) void preprocess_bwd_kernel(GsrParams p, 
       // through dir = d / |d|
       const float sum2 = dxr * dxr + dyr * dyr + dzr * dzr;
       const float inv3 = 1.0f / (ln * sum2);
-      dmean[0] += ((sum2 - dxr * dxr) * ddx - dyr * dxr * ddy - dzr * dxr * ddz) * inv3;
-      dmean[1] += (-dxr * dyr * ddx + (sum2 - dyr * dyr) * ddy - dzr * dyr * ddz) * inv3;
-      dmean[2] += (-dxr * dzr * ddx - dyr * dzr * ddy + (sum2 - dzr * dzr) * ddz) * inv3;
+      const float dd0 = ((sum2 - dxr * dxr) * ddx - dyr * dxr * ddy - dzr * dxr * ddz) * inv3;
+      const float dd1 = (-dxr * dyr * ddx + (sum2 - dyr * dyr) * ddy - dzr * dyr * ddz) * inv3;
+      const float dd2 = (-dxr * dzr * ddx - dyr * dzr * ddy + (sum2 - dzr * dzr) * ddz) * inv3;
+      dmean[0] += dd0;
+      dmean[1] += dd1;
+      dmean[2] += dd2;
+      if constexpr (CAM) {        // dir = (mean - campos) / |mean - campos|: the camera takes what the mean takes, negated
+        cam[24] = -dd0; cam[25] = -dd1; cam[26] = -dd2;
+      }
     }
 
     // ---- (v) cov3D -> scale, rotation -------------------------------------------------------
@@ -991,6 +1036,25 @@ __global__ __launch_bounds__(PRE_BLOCK) void preprocess_bwd_kernel(GsrParams p, 
         const float* q = st + row * SH_ROW + c;
         *reinterpret_cast<float4*>(out + flat) = make_float4(q[0], q[1], q[2], q[3]);
       }
+    }
+  }
+  if constexpr (CAM) {
+    // every lane of the block arrives here (inactive lanes carry zeros).  Wave: xor butterfly in double (the partners
+    // of a lane are fixed, so the sum depends on the Gaussians' indices only); block: the four wave sums in wave order.
+    __shared__ double cam_wave[PRE_BLOCK / WAVE][CAM_TERMS];
+#pragma unroll
+    for (int k = 0; k < CAM_TERMS; ++k) {
+      double d = (double)cam[k];
+#pragma unroll
+      for (int off = WAVE / 2; off > 0; off >>= 1) d += __shfl_xor(d, off, WAVE);
+      if (lane == 0) cam_wave[wid][k] = d;
+    }
+    __syncthreads();
+    if (threadIdx.x < CAM_TERMS) {
+      double d = cam_wave[0][threadIdx.x];
+#pragma unroll
+      for (int w = 1; w < PRE_BLOCK / WAVE; ++w) d += cam_wave[w][threadIdx.x];
+      static_cast<double*>(g.camera_ws)[(size_t)blockIdx.x * CAM_TERMS + threadIdx.x] = d;
     }
   }
   if (!valid) return;
@@ -1123,10 +1187,55 @@ void launch_sum_big_rows(const uint32_t* big_count, const uint32_t* big_offs, in
     hipLaunchKernelGGL(sum_big_rows_kernel, dim3(SUM_BIG_BLOCKS), dim3(256), 0, s, big_count, big_offs, nb, big_list, rec, slot_base, rows,
                        row_flags);
 }
+// One block adds the per-block camera sums (slot b = 27 doubles of block b of preprocess_bwd_kernel<true>) in a fixed order:
+// thread (stripe, term) walks the slots stripe, stripe + 32, ... of its term, then the 32 stripe sums are added in stripe
+// order.  Stores float32 dL/dviewmatrix [4,4] (column 3 = 0), dL/dprojmatrix [4,4] (column 2 = 0) and dL/dcampos [3].
+constexpr int CAM_FINISH_THREADS = 1024, CAM_STRIPES = CAM_FINISH_THREADS / 32;
+__global__ __launch_bounds__(CAM_FINISH_THREADS) void camera_grad_finish_kernel(const double* __restrict__ slots, int nslots,
+                                                                                float* __restrict__ dV,
+                                                                                float* __restrict__ dM,
+                                                                                float* __restrict__ dC) {
+  __shared__ double part[CAM_STRIPES][CAM_TERMS];
+  __shared__ double tot[CAM_TERMS];
+  const int term = threadIdx.x & 31, stripe = threadIdx.x >> 5;
+  if (term < CAM_TERMS) {
+    double acc = 0.0;
+#pragma unroll 4
+    for (int b = stripe; b < nslots; b += CAM_STRIPES) acc += slots[(size_t)b * CAM_TERMS + term];
+    part[stripe][term] = acc;
+  }
+  __syncthreads();
+  if (threadIdx.x < CAM_TERMS) {
+    double acc = part[0][threadIdx.x];
+    for (int k = 1; k < CAM_STRIPES; ++k) acc += part[k][threadIdx.x];
+    tot[threadIdx.x] = acc;
+  }
+  __syncthreads();
+  if (threadIdx.x < 16) {
+    const int i = threadIdx.x >> 2, c = threadIdx.x & 3;
+    dV[threadIdx.x] = c < 3 ? (float)tot[3 * i + c] : 0.0f;
+    dM[threadIdx.x] = c == 2 ? 0.0f : (float)tot[12 + 3 * i + (c == 3 ? 2 : c)];
+  }
+  if (threadIdx.x < 3) dC[threadIdx.x] = (float)tot[24 + threadIdx.x];
+}
+
+size_t camera_grad_bytes(int P) {
+  const size_t nb = P > 0 ? ((size_t)P + PRE_BLOCK - 1) / PRE_BLOCK : 0;
+  return align_up((nb ? nb : 1) * CAM_TERMS * sizeof(double), 256);
+}
 void launch_preprocess_bwd(const GsrParams& p, const int32_t* radii, const GeomRec* rec, const uint32_t* slot_base,
                            const GradRow* rows, const uint8_t* row_flags, const GsrGrads& g, hipStream_t s) {
   const int nb = (p.P + PRE_BLOCK - 1) / PRE_BLOCK;
-  if (nb > 0) hipLaunchKernelGGL(preprocess_bwd_kernel, dim3(nb), dim3(PRE_BLOCK), 0, s, p, radii, rec, slot_base, rows, row_flags, g);
+  if (!g.dL_dviewmatrix) {
+    if (nb > 0) hipLaunchKernelGGL(preprocess_bwd_kernel<false>, dim3(nb), dim3(PRE_BLOCK), 0, s, p, radii, rec, slot_base, rows, row_flags, g);
+    return;
+  }
+  if (nb > 0) hipLaunchKernelGGL(preprocess_bwd_kernel<true>, dim3(nb), dim3(PRE_BLOCK), 0, s, p, radii, rec, slot_base, rows, row_flags, g);
+  launch_camera_grad_finish(g, nb, s);
+}
+void launch_camera_grad_finish(const GsrGrads& g, int nslots, hipStream_t s) {
+  hipLaunchKernelGGL(camera_grad_finish_kernel, dim3(1), dim3(CAM_FINISH_THREADS), 0, s,
+                     static_cast<const double*>(g.camera_ws), nslots, g.dL_dviewmatrix, g.dL_dprojmatrix, g.dL_dcampos);
 }
 
 }  // namespace gsr

@@ -20,6 +20,12 @@ iteration, ``render.py:32-35`` saves every image at once) -- it is bit-identical
 ``0`` / ``False`` every frame on the two-call path;  ``deferred`` the count is compared with the capacity at the
 latest when the frame's backward starts, when the next frame is issued or in ``synchronize_counts()`` -- an overflowed
 frame raises ``GsrError`` THERE (its image and gradients are incomplete).  Only for callers that can redo a frame.
+
+Camera gradients.  ``GaussianRasterizationSettings`` stays the 12-field tuple.  When its ``viewmatrix``, ``projmatrix`` or
+``campos`` requires grad (and grad mode is on) the three tensors also enter the autograd functions as inputs of their own
+and receive gradients of their own shapes ([4,4], [4,4], [3]; entries the rasterizer does not read -- ``viewmatrix``
+column 3, ``projmatrix`` column 2 -- are zero): ``scene.PoseCamera`` builds such tensors from a learnable pose.  A frame
+whose camera does not require grad takes the path, the kernels and the allocations it always took.
 """
 from __future__ import annotations
 
@@ -554,10 +560,34 @@ def _stats_ptrs(stats, P: int, dev):
     return tuple(out)
 
 
+def _camera_inputs(settings: GaussianRasterizationSettings):
+    """(viewmatrix, projmatrix, campos) when one of them requires grad and grad mode is on -- the autograd functions then
+    take the three as inputs of their own -- else the empty tuple (the frame is issued exactly as without this feature)."""
+    cam = (settings.viewmatrix, settings.projmatrix, settings.campos)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in cam):
+        return cam
+    return ()
+
+
+def _camera_grads(lib, grads: "_lib.GsrGrads", cam_shapes, P: int, dev):
+    """Attach the camera outputs and their workspace to ``grads``; returns (tensors to keep alive, the three gradients
+    in the shapes of the inputs)."""
+    g_view = torch.empty(16, dtype=torch.float32, device=dev)
+    g_proj = torch.empty(16, dtype=torch.float32, device=dev)
+    g_pos = torch.empty(3, dtype=torch.float32, device=dev)
+    ws = torch.empty(lib.gsr_camera_grad_bytes(P), dtype=torch.uint8, device=dev)
+    grads.dL_dviewmatrix, grads.dL_dprojmatrix, grads.dL_dcampos = g_view.data_ptr(), g_proj.data_ptr(), g_pos.data_ptr()
+    grads.camera_ws = ws.data_ptr()
+    return ws, tuple(g.view(shape) for g, shape in zip((g_view, g_proj, g_pos), cam_shapes))
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings: GaussianRasterizationSettings, forward_only: bool = False, stats=None):
+                raster_settings: GaussianRasterizationSettings, forward_only: bool = False, stats=None,
+                cam_view=None, cam_proj=None, cam_pos=None):
+        """``cam_view`` / ``cam_proj`` / ``cam_pos``: the settings' three camera tensors again, given when they are to
+        receive gradients (``_camera_inputs``); the values are read from ``raster_settings`` either way."""
         lib = _lib.load()
         dev = _require_gpu(means3D)
         P = int(means3D.shape[0])
@@ -599,6 +629,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.counts = frame.counts
         ctx.binning_mode = params.binning_mode
         ctx.stats = stats
+        ctx.cam_shapes = None if cam_view is None else (cam_view.shape, cam_proj.shape, cam_pos.shape)
+        ctx.has_means2D = means2D is not None       # a caller that wants no dL/dmeans2D may pass None: it gets None back
         ctx.keep = keep
         ctx.save_for_backward(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, frame.radii,
                               frame.geom, frame.binning, frame.img)
@@ -609,7 +641,7 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii):
         if grad_out_color is None:
-            return (None,) * 11
+            return (None,) * (11 if ctx.cam_shapes is None else 14)
         lib = _lib.load()
         (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, radii, geom, binning,
          img) = ctx.saved_tensors
@@ -632,6 +664,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             g_cov = new(P, 6) if cov3Ds_precomp.numel() else None
             grads = _lib.GsrGrads(_ptr(g_means3D), _ptr(g_means2D), _ptr(g_sh), _ptr(g_col), _ptr(g_opac),
                                   _ptr(g_scales), _ptr(g_rot), _ptr(g_cov), None, *_stats_ptrs(ctx.stats, P, dev))
+            cam_ws, g_cam = (None, ()) if ctx.cam_shapes is None else _camera_grads(lib, grads, ctx.cam_shapes, P, dev)
             frame = _Frame(geom, binning, img, radii, ctx.layout[0], ctx.layout[1], ctx.frame_pending, ctx.counts)
             try:
                 _run_backward(lib, dev, params, frame, grad_out_color, grads)
@@ -641,8 +674,8 @@ class _RasterizeGaussians(torch.autograd.Function):
                                 grad_out_color, tuple(settings)), "snapshot_bw.dump")
                     print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
                 raise
-        del keep
-        return g_means3D, g_means2D, g_sh, g_col, g_opac, g_scales, g_rot, g_cov, None, None, None
+        del keep, cam_ws
+        return (g_means3D, g_means2D if ctx.has_means2D else None, g_sh, g_col, g_opac, g_scales, g_rot, g_cov, None, None, None) + g_cam
 
 
 class _RasterizeGaussiansFused(torch.autograd.Function):
@@ -654,9 +687,9 @@ class _RasterizeGaussiansFused(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations,
                 raster_settings: GaussianRasterizationSettings, forward_only: bool = False, stats=None, visible=None,
-                state_key=None):
+                state_key=None, cam_view=None, cam_proj=None, cam_pos=None):
         """``visible``: None, or a bool [P] tensor the forward fills with ``radii > 0`` (render()'s visibility_filter).
-        ``state_key``: see ``_run_forward``."""
+        ``state_key``: see ``_run_forward``.  ``cam_*``: as in ``_RasterizeGaussians.forward``."""
         lib = _lib.load()
         dev = _require_gpu(means3D)
         P = int(means3D.shape[0])
@@ -704,6 +737,8 @@ class _RasterizeGaussiansFused(torch.autograd.Function):
         ctx.binning_mode = params.binning_mode
         ctx.act_flags = flags
         ctx.stats = stats
+        ctx.cam_shapes = None if cam_view is None else (cam_view.shape, cam_proj.shape, cam_pos.shape)
+        ctx.has_means2D = means2D is not None       # a caller that wants no dL/dmeans2D may pass None: it gets None back
         ctx.keep = keep
         ctx.save_for_backward(means3D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations, frame.radii, frame.geom,
                               frame.binning, frame.img)
@@ -714,7 +749,7 @@ class _RasterizeGaussiansFused(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii):
         if grad_out_color is None:
-            return (None,) * 12
+            return (None,) * (12 if ctx.cam_shapes is None else 15)
         lib = _lib.load()
         means3D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations, radii, geom, binning, img = ctx.saved_tensors
         settings = ctx.raster_settings
@@ -734,6 +769,7 @@ class _RasterizeGaussiansFused(torch.autograd.Function):
             g_opac, g_scales, g_rot = new(*raw_opacity.shape), new(P, 3), new(P, 4)
             grads = _lib.GsrGrads(_ptr(g_means3D), _ptr(g_means2D), _ptr(g_dc), None, _ptr(g_opac), _ptr(g_scales),
                                   _ptr(g_rot), None, _ptr(g_rest) if has_rest else None, *_stats_ptrs(ctx.stats, P, dev))
+            cam_ws, g_cam = (None, ()) if ctx.cam_shapes is None else _camera_grads(lib, grads, ctx.cam_shapes, P, dev)
             frame = _Frame(geom, binning, img, radii, ctx.layout[0], ctx.layout[1], ctx.frame_pending, ctx.counts)
             try:
                 _run_backward(lib, dev, params, frame, grad_out_color, grads)
@@ -743,8 +779,8 @@ class _RasterizeGaussiansFused(torch.autograd.Function):
                                 tuple(settings)), "snapshot_bw.dump")
                     print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
                 raise
-        del keep
-        return g_means3D, g_means2D, g_dc, g_rest, g_opac, g_scales, g_rot, None, None, None, None, None
+        del keep, cam_ws
+        return (g_means3D, g_means2D if ctx.has_means2D else None, g_dc, g_rest, g_opac, g_scales, g_rot, None, None, None, None, None) + g_cam
 
 
 def _forward_only(*tensors) -> bool:
@@ -772,22 +808,24 @@ def rasterize_gaussians_fused(means3D, means2D, f_dc, f_rest, raw_opacity, raw_s
     densification statistics of ``scene/gaussian_model.py:775-777`` / ``train.py:130``.
     ``visible``: None, or a bool [P] tensor that receives ``radii > 0`` from the preprocess kernel.
     ``_state_key`` (internal): the capacity state of grown frames (``_grown_key``) instead of the one of P rows."""
-    if _forward_only(means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations):
+    cam = _camera_inputs(raster_settings)
+    if _forward_only(means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations, *cam):
         with torch.no_grad():
             return _RasterizeGaussiansFused.forward(_NoGraph(), means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales,
                                                     raw_rotations, raster_settings, True, None, visible, _state_key)
     return _RasterizeGaussiansFused.apply(means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations,
-                                          raster_settings, False, densify_stats, visible, _state_key)
+                                          raster_settings, False, densify_stats, visible, _state_key, *cam)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings, densify_stats=None):
-    if _forward_only(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp):
+    cam = _camera_inputs(raster_settings)
+    if _forward_only(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, *cam):
         with torch.no_grad():
             return _RasterizeGaussians.forward(_NoGraph(), means3D, means2D, sh, colors_precomp, opacities, scales,
                                                rotations, cov3Ds_precomp, raster_settings, True, None)
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, False, densify_stats)
+                                     cov3Ds_precomp, raster_settings, False, densify_stats, *cam)
 
 
 class GaussianRasterizer(nn.Module):

@@ -107,6 +107,133 @@ class MiniCam:
         self.camera_center = torch.inverse(self.world_view_transform)[3][:3]
 
 
+def so3_exp(rot: torch.Tensor) -> torch.Tensor:
+    """Rodrigues: the rotation matrix of the axis-angle vector ``rot[3]``, ``I + a K + b K^2`` with ``K = [rot]_x``,
+    ``a = sin(t)/t`` and ``b = (1 - cos t)/t^2 = (sin(t/2)/(t/2))^2 / 2``.  Below ``t^2 = 1e-6`` the two factors are their
+    series in ``t^2``, so the map and its derivative are exact at zero (where the result is the identity bit for bit)."""
+    t2 = (rot * rot).sum()
+    small = t2 < 1e-6
+    t = torch.sqrt(torch.where(small, torch.ones_like(t2), t2))      # the unused branch stays away from sqrt(0)
+    half = 0.5 * t
+    a = torch.where(small, 1.0 - t2 / 6.0 + t2 * t2 / 120.0, torch.sin(t) / t)
+    b = torch.where(small, 0.5 - t2 / 24.0 + t2 * t2 / 720.0, 0.5 * (torch.sin(half) / half) ** 2)
+    x, y, z = rot[0], rot[1], rot[2]
+    o = torch.zeros_like(x)
+    K = torch.stack([torch.stack([o, -z, y]), torch.stack([z, o, -x]), torch.stack([-y, x, o])])
+    return torch.eye(3, dtype=rot.dtype, device=rot.device) + a * K + b * (K @ K)
+
+
+def pose_transforms(world_view, projection, full_proj, rot_delta, trans_delta):
+    """(world_view_transform, full_proj_transform, camera_center) of a camera whose world-to-camera transform is
+    ``D @ W2C``, ``D = [[so3_exp(rot_delta), trans_delta], [0, 1]]``.  The tensors are the row-vector-convention ones of
+    ``Camera`` (``world_view = W2C^T``), so the increment multiplies from the right: ``world_view @ D^T``; the other two
+    follow with ``Camera``'s own ops (``bmm`` with the projection matrix, ``inverse()[3, :3]``).  A camera without a
+    projection matrix (``MiniCam``; pass ``projection=None``) gets ``full_proj + world_view (D^T - I) inv(world_view)
+    full_proj``: the same matrix, and again the base's bits at zero delta."""
+    dR = so3_exp(rot_delta)
+    zero = torch.zeros(3, 1, dtype=dR.dtype, device=dR.device)
+    one = torch.ones(1, dtype=dR.dtype, device=dR.device)
+    Dt = torch.cat([torch.cat([dR.transpose(0, 1), zero], dim=1), torch.cat([trans_delta, one]).unsqueeze(0)], dim=0)
+    if not world_view.is_contiguous() and world_view.transpose(0, 1).is_contiguous():
+        # Camera keeps its matrix as a transposed view; the product takes the same strides, so that inverse() and bmm
+        # below walk the memory they walk for the base camera and give the same bits at zero delta
+        view = (Dt.transpose(0, 1) @ world_view.transpose(0, 1)).transpose(0, 1)
+    else:
+        view = world_view @ Dt
+    if projection is not None:
+        full = (view.unsqueeze(0).bmm(projection.unsqueeze(0))).squeeze(0)
+    else:
+        eye = torch.eye(4, dtype=Dt.dtype, device=Dt.device)
+        full = full_proj + world_view @ (Dt - eye) @ (world_view.inverse() @ full_proj)
+    return view, full, view.inverse()[3, :3]
+
+
+class PoseCamera(torch.nn.Module):
+    """A camera with a learnable pose: wraps a ``Camera``, ``MiniCam`` or ``SyntheticCamera`` and applies the SE(3)
+    increment (``rot_delta[3]`` axis-angle, ``trans_delta[3]``) on the left of its world-to-camera transform.
+
+    ``world_view_transform``, ``full_proj_transform`` and ``camera_center`` are computed by torch on the base camera's
+    device every time they are read and carry the graph back to the two parameters; ``render()`` hands them to the
+    rasterizer, whose backward returns their gradients.  Every other attribute ``render()`` or the training loop reads
+    (``image_width``, ``FoVx``, ``original_image``, ...) is the base camera's.  At zero delta the three tensors are
+    ``torch.equal`` to the base's: the frame is the base camera's frame bit for bit.
+
+        cam = PoseCamera(scene.getTrainCameras()[0])
+        pose_opt = torch.optim.Adam(cam.parameters(), lr=1e-3)
+        training_iteration(model, cam, opt, pipe, background, it, cameras_extent=extent, pose_optimizer=pose_opt)
+    """
+
+    def __init__(self, base_camera):
+        super().__init__()
+        if isinstance(base_camera, PoseCamera):
+            raise TypeError("PoseCamera wraps a plain camera: bake() the inner one first")
+        self.__dict__["_base"] = base_camera
+        wv = base_camera.world_view_transform
+        self.rot_delta = torch.nn.Parameter(torch.zeros(3, dtype=wv.dtype, device=wv.device))
+        self.trans_delta = torch.nn.Parameter(torch.zeros(3, dtype=wv.dtype, device=wv.device))
+
+    def __getattr__(self, name):
+        try:
+            return super().__getattr__(name)
+        except AttributeError:
+            base = self.__dict__.get("_base")
+            # a failure inside one of the three properties must surface, not fall back to the base camera's fixed tensor
+            if base is None or name.startswith("__") or name in ("world_view_transform", "full_proj_transform",
+                                                                  "camera_center"):
+                raise
+            return getattr(base, name)
+
+    @property
+    def base_camera(self):
+        return self.__dict__["_base"]
+
+    def transforms(self):
+        """The three tensors at the current pose, from one evaluation of the increment."""
+        b = self.base_camera
+        return pose_transforms(b.world_view_transform, getattr(b, "projection_matrix", None), b.full_proj_transform,
+                               self.rot_delta, self.trans_delta)
+
+    @property
+    def world_view_transform(self):
+        return self.transforms()[0]
+
+    @property
+    def full_proj_transform(self):
+        return self.transforms()[1]
+
+    @property
+    def camera_center(self):
+        return self.transforms()[2]
+
+    def pose(self):
+        """The current (R, T) in ``Camera``'s convention (R camera-to-world, T the world-to-camera translation), float64
+        numpy, evaluated in float64 from the base camera's matrix and the two parameters."""
+        with torch.no_grad():
+            wv = self.base_camera.world_view_transform.detach().double().cpu()
+            view, _, _ = pose_transforms(wv, None, wv, self.rot_delta.detach().double().cpu(),
+                                         self.trans_delta.detach().double().cpu())
+        return view[:3, :3].numpy().copy(), view[3, :3].numpy().copy()
+
+    def bake(self):
+        """A plain camera of the base's class at the current pose (for ``MiniCam``: the current matrices, detached)."""
+        b = self.base_camera
+        R, T = self.pose()
+        if isinstance(b, Camera):
+            dev = b.world_view_transform.device
+            return Camera(b.colmap_id, R, T, b.FoVx, b.FoVy, b.original_image, None, b.image_name, b.uid,
+                          data_device=b.data_device, device=dev)
+        if isinstance(b, MiniCam):
+            with torch.no_grad():
+                view, full, _ = self.transforms()
+            return MiniCam(b.image_width, b.image_height, b.FoVy, b.FoVx, b.znear, b.zfar, view.detach(), full.detach())
+        from .synthetic import SyntheticCamera
+        if isinstance(b, SyntheticCamera):
+            return SyntheticCamera(b.image_width, b.image_height, fov2focal(b.FoVx, b.image_width),
+                                   fov2focal(b.FoVy, b.image_height), R=R, T=T, znear=b.znear, zfar=b.zfar,
+                                   device=b.world_view_transform.device)
+        raise TypeError(f"cannot bake a {type(b).__name__}: PoseCamera knows Camera, MiniCam and SyntheticCamera")
+
+
 _WARNED = False
 
 
@@ -240,5 +367,5 @@ class Scene:
         return self.test_cameras[scale]
 
 
-__all__ = ["ModelParams", "Camera", "MiniCam", "Scene", "load_cam", "loadCam", "load_resolution",
+__all__ = ["ModelParams", "Camera", "MiniCam", "PoseCamera", "so3_exp", "pose_transforms", "Scene", "load_cam", "loadCam", "load_resolution",
            "cameraList_from_camInfos", "camera_to_JSON", "searchForMaxIteration"]

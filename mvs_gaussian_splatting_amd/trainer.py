@@ -66,7 +66,7 @@ def schedule(opt, iteration: int, white_background: bool = False) -> dict:
 
 
 def training_iteration(model, camera, opt, pipe, background, iteration, *, dataset=None, cameras_extent,
-                       first_reset=None, gt_image=None, densify_kwargs=None):
+                       first_reset=None, gt_image=None, densify_kwargs=None, pose_optimizer=None):
     """``train.py:72-142`` for one camera, in the reference's order: learning rate, SH degree, background, ``render``
     with the fork's keyword arguments, L1 + D-SSIM against ``camera.original_image``, the opacity sparsity term
     (``opt.opacitysparse``), ``backward``; then, without gradients, the densification statistics, ``densify_and_prune``,
@@ -77,7 +77,9 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
     first_reset: whether the extra opacity reset at ``densify_from_iter`` runs (``train.py:136``); default
     ``dataset.white_background``.
     gt_image: the target instead of ``camera.original_image``.  densify_kwargs: passed on to ``densify_and_prune``
-    (``noise``, ``dir_noise``, ``spatial_order``)."""
+    (``noise``, ``dir_noise``, ``spatial_order``).
+    pose_optimizer: an optimizer over the parameters of ``camera`` when that is a ``scene.PoseCamera`` (the backward
+    leaves dL/dpose in them); it is stepped and zeroed where the model's optimizer is.  None: the camera is not refined."""
     flag = lambda name: bool(getattr(dataset, name, False))      # noqa: E731
     if first_reset is None:
         first_reset = flag("white_background")
@@ -105,6 +107,9 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
         if todo["step"]:                                                                        # :140-142
             model.optimizer.step()
             model.optimizer.zero_grad(set_to_none=True)
+            if pose_optimizer is not None:
+                pose_optimizer.step()
+                pose_optimizer.zero_grad(set_to_none=True)
     return loss.detach()
 
 
