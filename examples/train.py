@@ -7,6 +7,8 @@ SH degree steps, densification, opacity resets, the optional opacity sparsity te
                              [--white_background] [--images DIR] [--data_device cuda|cpu] [--save_iterations N ...]
                              [--refine_poses [--pose_lr LR]]
 
+``--optimizer_type sparse_adam`` (both forms) steps only the Gaussians each frame saw (``optim.SparseGaussianAdam``).
+
 With ``-s`` the example trains on a dataset through ``Scene`` (``scene.py``) and saves
 ``<output>/point_cloud/iteration_N/point_cloud.ply``, which ``examples/render.py -m <output>`` renders.
 ``--refine_poses`` (off by default) wraps every training camera in a ``PoseCamera`` and refines the poses with the model
@@ -112,8 +114,8 @@ def train_scene(args, dev):
                           resolution=args.resolution, white_background=args.white_background,
                           data_device=args.data_device, eval=args.eval)
     n = args.iterations
-    opt = example_opt(n, opacitysparse=args.opacitysparse) if n < 3000 else \
-        OptimizationParams(iterations=n, opacitysparse=args.opacitysparse)
+    over = dict(opacitysparse=args.opacitysparse, optimizer_type=args.optimizer_type)
+    opt = example_opt(n, **over) if n < 3000 else OptimizationParams(iterations=n, **over)
     model = GaussianModel(dataset.sh_degree)
     scene = Scene(dataset, model)
     with open(os.path.join(args.model_path, "cfg_args.json"), "w") as f:         # what examples/render.py -m needs
@@ -161,6 +163,8 @@ def main(argv=None):
     ap.add_argument("--checkpoint_iterations", type=int, nargs="*", default=[])
     ap.add_argument("--start_checkpoint", default=None)
     ap.add_argument("--opacitysparse", type=float, default=0.0)
+    ap.add_argument("--optimizer_type", choices=("default", "sparse_adam"), default="default",
+                    help="sparse_adam: step only the Gaussians each frame saw (optim.SparseGaussianAdam)")
     ap.add_argument("--refine_poses", action="store_true", help="with -s: refine the training cameras' poses too")
     ap.add_argument("--pose_lr", type=float, default=1e-4)
     ap.add_argument("--out", default=os.path.dirname(os.path.abspath(__file__)))
@@ -171,7 +175,7 @@ def main(argv=None):
             ap.error("-s needs -m, the directory the model is saved under")
         return train_scene(args, dev)
     n = args.iterations
-    opt = example_opt(n, opacitysparse=args.opacitysparse)
+    opt = example_opt(n, opacitysparse=args.opacitysparse, optimizer_type=args.optimizer_type)
     dataset = types.SimpleNamespace(white_background=False)
     problem = make_problem(dev)
     model = make_model(problem, opt, dataset)

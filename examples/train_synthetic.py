@@ -2,10 +2,13 @@
 this repo's drop-ins: ``render`` -> fused L1 + D-SSIM loss -> backward -> ``add_densification_stats`` -> Adam step ->
 ``densify_and_prune`` every ``densification_interval`` iterations -> ``save_ply``.
 
-    python examples/train_synthetic.py [iterations]
+    python examples/train_synthetic.py [iterations] [--optimizer_type {default,sparse_adam}]
+
+``--optimizer_type sparse_adam`` steps only the Gaussians each frame saw (``optim.SparseGaussianAdam``, one HIP launch).
 
 It fits a perturbed copy of a small Gaussian cloud to images rendered from the unperturbed cloud (8 orbit views).
 """
+import argparse
 import math
 import os
 import sys
@@ -15,13 +18,14 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from mvs_gaussian_splatting_amd import render, l1_dssim_loss, add_densification_stats, evaluate_views  # noqa: E402
 from mvs_gaussian_splatting_amd.densify import densify_and_prune, GROUP_ATTR  # noqa: E402
-from mvs_gaussian_splatting_amd.optim import Adam  # noqa: E402
+from mvs_gaussian_splatting_amd.optim import Adam, SparseGaussianAdam  # noqa: E402
 from mvs_gaussian_splatting_amd.synthetic import SyntheticGaussianModel, PipelineParams, orbit_camera  # noqa: E402
 
 
-def make_problem(dev, P=4000, W=256, H=160, n_views=8, seed=0, optimizer="torch"):
+def make_problem(dev, P=4000, W=256, H=160, n_views=8, seed=0, optimizer="torch", optimizer_type="default"):
     """(ground-truth images per view, cameras, trainable model).  optimizer: "torch" (torch.optim.Adam, as the reference)
-    or "hip" (mvs_gaussian_splatting_amd.optim.Adam: the same step in one HIP launch, bit-identical)."""
+    or "hip" (mvs_gaussian_splatting_amd.optim.Adam: the same step in one HIP launch, bit-identical).
+    optimizer_type: "default", or "sparse_adam" for optim.SparseGaussianAdam (a HIP step: with optimizer="hip")."""
     gt = SyntheticGaussianModel(P, 3, seed=seed, log_scale_mean=math.log(0.06), extent=(1.6, 1.0, 0.8), centre=(0, 0, 4.0))
     gt._opacity += 1.0
     gt.to(dev)
@@ -47,7 +51,11 @@ def make_problem(dev, P=4000, W=256, H=160, n_views=8, seed=0, optimizer="torch"
     lrs = {"xyz": 1.6e-4, "f_dc": 2e-2, "f_rest": 1e-3, "opacity": 0.05, "scaling": 5e-3, "rotation": 1e-3}
     if optimizer not in ("torch", "hip"):
         raise ValueError(f"optimizer must be 'torch' or 'hip', got {optimizer!r}")
-    adam = torch.optim.Adam if optimizer == "torch" else Adam
+    if optimizer_type not in ("default", "sparse_adam"):
+        raise ValueError(f"optimizer_type must be 'default' or 'sparse_adam', got {optimizer_type!r}")
+    if optimizer_type == "sparse_adam" and optimizer != "hip":
+        raise ValueError("optimizer_type='sparse_adam' is a HIP step: pass optimizer='hip'")
+    adam = torch.optim.Adam if optimizer == "torch" else SparseGaussianAdam if optimizer_type == "sparse_adam" else Adam
     model.optimizer = adam([{"params": [getattr(model, a)], "lr": lrs[k], "name": k}
                             for k, a in GROUP_ATTR.items()], lr=0.0, eps=1e-15)
     pipe.fuse_densify_stats = True      # the backward takes the densification statistics; add_densification_stats below
@@ -69,17 +77,19 @@ def make_held_out(dev, P=4000, W=256, H=160, n_views=4, seed=0):
 
 
 def train(dev, iterations=60, densification_interval=20, densify_from_iter=10, extent=2.0, grad_threshold=0.0006, log=None,
-          spatial_order=False, optimizer="torch", report_every=0, sh_increase_every=0, on_sh_increase=None):
+          spatial_order=False, optimizer="torch", report_every=0, sh_increase_every=0, on_sh_increase=None,
+          optimizer_type="default"):
     """spatial_order: after every densification the cloud (and the Adam moments) is stored along a Morton curve
     (mvs_gaussian_splatting_amd/layout.py) instead of the reference's [kept | clones | children] order.
-    optimizer: see make_problem.
+    optimizer, optimizer_type: see make_problem; with "sparse_adam" each step updates the rows in the frame's
+    ``visibility_filter`` only.
     report_every: every so many iterations (0: never) the held-out views are evaluated as train.py:217-232 does, in
     fused passes accumulated on the device (evaluate_views), and L1 / PSNR are logged.
     sh_increase_every: 0 trains at the full SH degree from the start; n > 0 starts at ``active_sh_degree = 0`` (as the
     reference's model does, scene/gaussian_model.py:47) and raises it by one, up to the stored degree, at the start of
     every iteration with ``it % n == 0`` (train.py:75-76, ``oneupSHdegree``).  on_sh_increase(it, model), if given, is
     called immediately before each such step."""
-    targets, cams, bg, pipe, model = make_problem(dev, optimizer=optimizer)
+    targets, cams, bg, pipe, model = make_problem(dev, optimizer=optimizer, optimizer_type=optimizer_type)
     if sh_increase_every:
         model.active_sh_degree = 0
     test_cams = make_held_out(dev) if report_every else []
@@ -95,7 +105,10 @@ def train(dev, iterations=60, densification_interval=20, densify_from_iter=10, e
         loss.backward()
         with torch.no_grad():
             add_densification_stats(model, pkg["viewspace_points"], pkg["radii"])
-            model.optimizer.step()
+            if optimizer_type == "sparse_adam":
+                model.optimizer.step(pkg["visibility_filter"])
+            else:
+                model.optimizer.step()
             model.optimizer.zero_grad(set_to_none=True)
             if it > densify_from_iter and it % densification_interval == 0:
                 info = densify_and_prune(model, grad_threshold, 0.005, extent, 20, spatial_order=spatial_order)
@@ -113,8 +126,13 @@ def train(dev, iterations=60, densification_interval=20, densify_from_iter=10, e
 
 
 if __name__ == "__main__":
-    n = int(sys.argv[1]) if len(sys.argv) > 1 else 100
-    model, history, _ = train(torch.device("cuda:0"), iterations=n, log=print)
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("iterations", type=int, nargs="?", default=100)
+    ap.add_argument("--optimizer_type", choices=("default", "sparse_adam"), default="default")
+    args = ap.parse_args()
+    model, history, _ = train(torch.device("cuda:0"), iterations=args.iterations, log=print,
+                              optimizer="hip" if args.optimizer_type == "sparse_adam" else "torch",
+                              optimizer_type=args.optimizer_type)
     from mvs_gaussian_splatting_amd.ply_io import save_ply
     out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "point_cloud.ply")
     save_ply(model, out)

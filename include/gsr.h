@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 20
+#define GSR_ABI_VERSION 21
 
 enum {
   GSR_OK = 0,
@@ -509,6 +509,33 @@ typedef struct GsrAdamBatch {
 } GsrAdamBatch;
 
 int gsr_adam_step(const GsrAdamBatch* batch, void* stream);
+
+/* The same step for the rows one frame saw, ABI v21 ("sparse Adam").  Every tensor of the batch is [rows, numel / rows]
+ * and `visibility` has one entry per row: GSR_ADAM_VIS_U8, one byte, visible iff non-zero (a torch bool / uint8
+ * tensor), or GSR_ADAM_VIS_I32, an int32, visible iff > 0 (the rasterizer's `radii`, as it stands).
+ *   visible rows:   every element gets exactly the update of gsr_adam_step, bit for bit;
+ *   invisible rows: param, exp_avg and exp_avg_sq keep their bits (NaN payloads included) and the gradient is never
+ *                   used: a NaN or Inf there reaches nothing.
+ * Memory that holds invisible rows only is neither read nor written (in 16-byte pieces on the aligned path, per element
+ * otherwise); a 16-byte piece that two rows of different visibility share is read and written back whole.  The scalars
+ * of t[] are those of gsr_adam_step: the caller counts a step for every tensor it passes, seen or not, so a visible row
+ * gets what the dense step would have given it from the same state.  (This is not the sparse kernel of upstream 3DGS,
+ * which drops the bias correction.)
+ * Returns GSR_E_BADARG for the cases of gsr_adam_step and for an unknown visibility_kind, negative rows, a NULL
+ * visibility with a non-empty tensor and a numel that is not a multiple of rows; GSR_E_ALIGN for an int32 visibility
+ * that is not 4-byte aligned.  No host synchronisation, no allocation. */
+#define GSR_ADAM_VIS_U8 0
+#define GSR_ADAM_VIS_I32 1
+
+typedef struct GsrAdamRowsBatch {
+  const void* visibility;                      /* device [rows], see visibility_kind */
+  int64_t rows;
+  int32_t visibility_kind;                     /* GSR_ADAM_VIS_* */
+  int32_t count;                               /* entries of t[] in use */
+  GsrAdamTensor t[GSR_ADAM_MAX_TENSORS];       /* row_floats of t[k] = t[k].numel / rows */
+} GsrAdamRowsBatch;
+
+int gsr_adam_step_rows(const GsrAdamRowsBatch* batch, void* stream);
 
 /* The model's per-opacity lifecycle steps, ABI v18 (csrc/model.hip).  opacity_raw is the model's `_opacity`, device
  * [P,1] fp32, pre-activation.  Nothing here allocates, synchronises or reads back: every call can sit in a captured

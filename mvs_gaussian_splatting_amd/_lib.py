@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # instead of copying it over the in-tree library
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")
 
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 
 class GsrParams(C.Structure):
@@ -93,6 +93,14 @@ class GsrAdamTensor(C.Structure):
 
 class GsrAdamBatch(C.Structure):
     _fields_ = [("count", C.c_int32), ("reserved", C.c_int32), ("t", GsrAdamTensor * ADAM_MAX_TENSORS)]
+
+
+ADAM_VIS_U8, ADAM_VIS_I32 = 0, 1
+
+
+class GsrAdamRowsBatch(C.Structure):
+    _fields_ = [("visibility", C.c_void_p), ("rows", C.c_int64), ("visibility_kind", C.c_int32), ("count", C.c_int32),
+                ("t", GsrAdamTensor * ADAM_MAX_TENSORS)]
 
 
 # name -> (restype, argtypes); every symbol include/gsr.h declares
@@ -174,6 +182,8 @@ SYMBOLS = {
                                     C.c_void_p]),
     # torch.optim.Adam's foreach step over up to ADAM_MAX_TENSORS tensors in one launch (optim.py)
     "gsr_adam_step": (C.c_int, [C.POINTER(GsrAdamBatch), C.c_void_p]),
+    # the same step for the rows a visibility array marks (optim.SparseGaussianAdam)
+    "gsr_adam_step_rows": (C.c_int, [C.POINTER(GsrAdamRowsBatch), C.c_void_p]),
     # the opacity sparsity term of train.py:102-106 and the in-place reset_opacity (csrc/model.hip; losses.py, model.py)
     "gsr_opacity_sparsity_workspace_bytes": (C.c_size_t, []),
     "gsr_opacity_sparsity_fwd": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_void_p, C.c_void_p,

@@ -1013,6 +1013,30 @@ int gsr_adam_step(const GsrAdamBatch* batch, void* stream) {
   return check(nullptr, s, "adam_step");
 }
 
+int gsr_adam_step_rows(const GsrAdamRowsBatch* batch, void* stream) {
+  if (!batch) return fail(GSR_E_BADARG, "NULL batch");
+  if (batch->count < 0 || batch->count > GSR_ADAM_MAX_TENSORS)
+    return fail(GSR_E_BADARG, "count must be 0..GSR_ADAM_MAX_TENSORS");
+  if (batch->visibility_kind != GSR_ADAM_VIS_U8 && batch->visibility_kind != GSR_ADAM_VIS_I32)
+    return fail(GSR_E_BADARG, "unknown visibility_kind");
+  if (batch->rows < 0) return fail(GSR_E_BADARG, "negative rows");
+  for (int k = 0; k < batch->count; ++k) {
+    const GsrAdamTensor& t = batch->t[k];
+    if (t.numel < 0) return fail(GSR_E_BADARG, "negative numel");
+    if (t.numel == 0) continue;
+    if (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq)
+      return fail(GSR_E_BADARG, "NULL param / grad / exp_avg / exp_avg_sq");
+    if (!batch->visibility) return fail(GSR_E_BADARG, "NULL visibility with a non-empty tensor");
+    if (batch->rows == 0 || t.numel % batch->rows != 0) return fail(GSR_E_BADARG, "numel is not a multiple of rows");
+  }
+  if (batch->visibility_kind == GSR_ADAM_VIS_I32 && ((uintptr_t)batch->visibility & 3u) != 0)
+    return fail(GSR_E_ALIGN, "an int32 visibility must be 4-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (launch_adam_step_rows(*batch, s))
+    return fail(GSR_E_BADARG, "batch too large for one launch (more than 2^32 work-items)");
+  return check(nullptr, s, "adam_step_rows");
+}
+
 size_t gsr_opacity_sparsity_workspace_bytes(void) { return (size_t)OPACITY_MAX_BLOCKS * (sizeof(float) + sizeof(uint32_t)); }
 int gsr_opacity_sparsity_fwd(const float* opacity_raw, int64_t P, float weight, float threshold, float* record,
                              void* workspace, void* stream) {

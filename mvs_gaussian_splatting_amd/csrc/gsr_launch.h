@@ -168,6 +168,8 @@ void launch_densify_fork_rows(const GsrDensifyFork& f, const void* ws, const uin
 // adam.hip: one launch over the batch's tensors; returns nonzero (nothing enqueued) if the grid would exceed 2^32
 // work-items
 int launch_adam_step(const GsrAdamBatch& batch, hipStream_t s);
+// the row-masked step; the caller has checked that rows > 0 divides the numel of every non-empty entry
+int launch_adam_step_rows(const GsrAdamRowsBatch& batch, hipStream_t s);
 
 // model.hip: the opacity sparsity term (workspace: OPACITY_MAX_BLOCKS float sums, then as many uint32 counts; record:
 // {float loss, uint32 n, float weight / n, 0}) and the in-place opacity reset (moments may be nullptr)

@@ -101,7 +101,7 @@ class GaussianModel:
             self._split_distance = torch.empty(0)
         if self.learn_split_scale:
             self._split_scale = torch.empty(0)
-        self._optimizer_cls = optim.Adam
+        self._optimizer_cls = None                                   # None: the class opt.optimizer_type names
         # :34-42; render's raw-parameter path recognises the model by these three
         self.scaling_activation = torch.exp
         self.scaling_inverse_activation = torch.log
@@ -241,7 +241,8 @@ class GaussianModel:
         return self
 
     # ---- optimizer :240-277 (optim.py) ------------------------------------------------------------------------------
-    def training_setup(self, training_args, optimizer_cls=optim.Adam):
+    def training_setup(self, training_args, optimizer_cls=None):
+        """optimizer_cls: None takes the class ``training_args.optimizer_type`` names (``optim.Adam`` by default)."""
         self._optimizer_cls = optimizer_cls
         return optim.training_setup(self, training_args, optimizer_cls)
 
@@ -286,7 +287,8 @@ class GaussianModel:
 
     def restore(self, model_args, training_args, optimizer_cls=None):
         """``:133-149``; accepts the 12-tuple or the 13-tuple of ``capture``.  ``training_setup`` runs first, with
-        ``optimizer_cls`` (default: the class ``training_setup`` was last given, else ``optim.Adam``), then the saved
+        ``optimizer_cls`` (default: the class ``training_setup`` was last given, else the one
+        ``training_args.optimizer_type`` names: ``optim.Adam`` unless it says ``"sparse_adam"``), then the saved
         state is loaded into it: state dicts move freely between ``torch.optim.Adam`` and ``optim.Adam``."""
         model_args = tuple(model_args)
         if len(model_args) not in (12, 13):

@@ -9,6 +9,9 @@ parameter -- so the code that edits ``optimizer.state`` (``densify.densify_and_p
 the reference's ``replace_tensor_to_optimizer`` / ``_prune_optimizer``) and ``state_dict()`` work unchanged, in both
 directions.  It covers what the reference uses: no weight decay, amsgrad, maximize, capturable, differentiable or fused
 variants (``ValueError``), and float32 contiguous parameters on a ROCm GPU (no CPU path).
+
+``SparseGaussianAdam`` is ``Adam`` with a row mask: ``step(visibility)`` updates the Gaussians a frame saw and leaves the
+rest of the model's memory alone (``gsr_adam_step_rows``); ``OptimizationParams.optimizer_type = "sparse_adam"``.
 """
 from __future__ import annotations
 
@@ -81,15 +84,10 @@ class Adam(torch.optim.Optimizer):
                                  ("decoupled_weight_decay", False)):
                 group.setdefault(key, default)
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        """One Adam step of every parameter whose ``.grad`` is not None (the others keep their step count and
-        moments), enqueued on the current stream of the parameters' device; no host synchronisation."""
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        todo = []                                                    # every check before any state changes
+    def _checked(self) -> List[Tuple]:
+        """``(param, lr, betas, eps, group name)`` of every parameter that has a gradient; every check of ``step``, and
+        no change to any state."""
+        todo = []
         for group in self.param_groups:
             _check_group(group)
             lr = group["lr"]
@@ -113,9 +111,14 @@ class Adam(torch.optim.Optimizer):
                     if t is not None and (t.device != p.device or t.dtype != torch.float32 or t.numel() != p.numel()
                                           or not t.is_contiguous()):
                         raise ValueError(f"state[{name!r}] must be a contiguous float32 tensor like its parameter")
-                todo.append((p, lr, betas, eps))
-        per_device: Dict[torch.device, List[Tuple]] = {}
-        for p, lr, betas, eps in todo:
+                todo.append((p, lr, betas, eps, group.get("name")))
+        return todo
+
+    def _advance(self, todo) -> List[Tuple]:
+        """Creates the missing states, counts the step of every entry of ``todo`` and returns, per entry,
+        ``(param, grad, exp_avg, exp_avg_sq, scalars of that count)``."""
+        items = []
+        for p, lr, betas, eps, _ in todo:
             grad = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
             state = self.state[p]
             if len(state) == 0:                                      # torch's _init_group, capturable = fused = False
@@ -123,22 +126,97 @@ class Adam(torch.optim.Optimizer):
                 state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
             state["step"] += 1
-            per_device.setdefault(p.device, []).append(
-                (p, grad, state["exp_avg"], state["exp_avg_sq"], adam_scalars(lr, betas, eps, state["step"].item())))
+            items.append((p, grad, state["exp_avg"], state["exp_avg_sq"],
+                          adam_scalars(lr, betas, eps, state["step"].item())))
+        return items
+
+    @staticmethod
+    def _launch(items, visibility=None) -> None:
+        """``gsr_adam_step`` over ``items`` (``gsr_adam_step_rows`` with a ``visibility``), 16 tensors a launch, on the
+        current stream of each parameter's device."""
+        per_device: Dict[torch.device, List[Tuple]] = {}
+        for item in items:
+            per_device.setdefault(item[0].device, []).append(item)
         lib = _lib.load() if per_device else None
-        for dev, items in per_device.items():
+        for dev, group in per_device.items():
             with torch.cuda.device(dev):
                 stream = torch.cuda.current_stream(dev).cuda_stream
-                for first in range(0, len(items), _lib.ADAM_MAX_TENSORS):
-                    chunk = items[first:first + _lib.ADAM_MAX_TENSORS]
-                    batch = _lib.GsrAdamBatch()
+                for first in range(0, len(group), _lib.ADAM_MAX_TENSORS):
+                    chunk = group[first:first + _lib.ADAM_MAX_TENSORS]
+                    batch = _lib.GsrAdamBatch() if visibility is None else _lib.GsrAdamRowsBatch()
                     batch.count = len(chunk)
                     for e, (p, g, m, v, sc) in zip(batch.t, chunk):
                         e.param, e.grad, e.exp_avg, e.exp_avg_sq = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()
                         e.numel = p.numel()
                         for k, val in sc.items():
                             setattr(e, k, val)
-                    _lib.check(lib.gsr_adam_step(C.byref(batch), stream), "gsr_adam_step")
+                    if visibility is None:
+                        _lib.check(lib.gsr_adam_step(C.byref(batch), stream), "gsr_adam_step")
+                    else:
+                        batch.visibility, batch.rows = visibility.data_ptr(), visibility.numel()
+                        batch.visibility_kind = _lib.ADAM_VIS_I32 if visibility.dtype == torch.int32 else _lib.ADAM_VIS_U8
+                        _lib.check(lib.gsr_adam_step_rows(C.byref(batch), stream), "gsr_adam_step_rows")
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        """One Adam step of every parameter whose ``.grad`` is not None (the others keep their step count and
+        moments), enqueued on the current stream of the parameters' device; no host synchronisation."""
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        todo = self._checked()                                       # every check before any state changes
+        self._launch(self._advance(todo))
+        return loss
+
+
+class SparseGaussianAdam(Adam):
+    """``Adam`` that can step only the rows -- the Gaussians -- one frame saw (``gsr_adam_step_rows``): the rows of
+    every other Gaussian are neither read nor written, which is where the time of a step goes.  Same constructor, same
+    state (``step`` float32 CPU tensor, ``exp_avg``, ``exp_avg_sq``), so ``state_dict()`` moves freely between this
+    class, ``Adam`` and ``torch.optim.Adam``, and the code that edits ``optimizer.state`` works unchanged.
+
+    After ``step(visibility)`` the visible rows hold what the dense step would have produced from the same state, bit
+    for bit, and every other row is untouched: its moments do not decay and its gradient is never read.  ``step``
+    counts once per call for every stepped parameter, seen rows or not, and the scalars are ``adam_scalars`` of that
+    count.  This is deliberately not the sparse Adam kernel of upstream Inria 3DGS, which drops the bias correction:
+    keeping torch's scalars keeps checkpoints interchangeable and the result checkable against ``torch.optim.Adam``."""
+
+    @torch.no_grad()
+    def step(self, visibility=None, dense=(), closure=None):
+        """visibility: None -- exactly ``Adam.step()`` -- or a contiguous device tensor ``[P]``, bool / uint8 (visible
+        iff non-zero) or int32 (visible iff > 0: ``radii`` as the rasterizer returns it).  Every parameter that has a
+        gradient must have ``shape[0] == P`` (``ValueError`` before any state changes); parameters without one are
+        skipped unchecked, as on the iteration after a densification.
+        dense: names of parameter groups that take the dense update in the same step."""
+        if visibility is None:
+            return super().step(closure)
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        if not isinstance(visibility, torch.Tensor) or visibility.dtype not in (torch.bool, torch.uint8, torch.int32):
+            raise TypeError("visibility must be a bool, uint8 or int32 tensor, got "
+                            f"{visibility.dtype if isinstance(visibility, torch.Tensor) else type(visibility).__name__}")
+        if visibility.dim() != 1 or not visibility.is_contiguous():
+            raise ValueError(f"visibility must be a contiguous [P] tensor, got shape {tuple(visibility.shape)}")
+        dense = (dense,) if isinstance(dense, str) else tuple(dense)
+        P = visibility.shape[0]
+        for group in self.param_groups:
+            if group.get("name") in dense:
+                continue
+            for p in group["params"]:
+                if p.grad is not None and (p.dim() == 0 or p.shape[0] != P):
+                    raise ValueError(f"visibility has {P} rows, a parameter of group {group.get('name')!r} has shape "
+                                     f"{tuple(p.shape)}")
+        todo = self._checked()
+        for p, *_ in todo:
+            if visibility.device != p.device:
+                raise ValueError(f"visibility is on {visibility.device}, a parameter on {p.device}")
+        items = self._advance(todo)
+        is_dense = [name in dense for *_, name in todo]
+        self._launch([it for it, d in zip(items, is_dense) if d])
+        self._launch([it for it, d in zip(items, is_dense) if not d], visibility)
         return loss
 
 
@@ -173,10 +251,25 @@ def param_groups(model, opt) -> List[dict]:
     return groups
 
 
-def training_setup(model, opt, optimizer_cls=Adam):
+OPTIMIZER_TYPES = {"default": Adam, "sparse_adam": SparseGaussianAdam}
+
+
+def optimizer_class(opt):
+    """The class ``opt.optimizer_type`` names (``"default"`` where ``opt`` has no such field): ``Adam`` or
+    ``SparseGaussianAdam``; ``ValueError`` for anything else."""
+    kind = getattr(opt, "optimizer_type", "default")
+    if kind not in OPTIMIZER_TYPES:
+        raise ValueError(f"optimizer_type must be one of {sorted(OPTIMIZER_TYPES)}, got {kind!r}")
+    return OPTIMIZER_TYPES[kind]
+
+
+def training_setup(model, opt, optimizer_cls=None):
     """``GaussianModel.training_setup(training_args)`` (``scene/gaussian_model.py:240-268``) with this module's
     ``Adam``: sets ``percent_dense``, zeroed ``xyz_gradient_accum`` / ``denom`` ``[P, 1]`` on the model's device,
-    ``optimizer`` (``lr=0.0, eps=1e-15``) and ``xyz_scheduler_args``.  Returns the optimizer."""
+    ``optimizer`` (``lr=0.0, eps=1e-15``) and ``xyz_scheduler_args``.  optimizer_cls: None takes the class
+    ``opt.optimizer_type`` names (``optimizer_class``).  Returns the optimizer."""
+    if optimizer_cls is None:
+        optimizer_cls = optimizer_class(opt)
     model.percent_dense = opt.percent_dense
     P, dev = model._xyz.shape[0], model._xyz.device
     model.xyz_gradient_accum = torch.zeros((P, 1), device=dev)
@@ -200,4 +293,5 @@ def update_learning_rate(model, iteration):
     return None
 
 
-__all__ = ["Adam", "adam_scalars", "expon_lr_func", "param_groups", "training_setup", "update_learning_rate"]
+__all__ = ["Adam", "SparseGaussianAdam", "adam_scalars", "expon_lr_func", "optimizer_class", "param_groups",
+           "training_setup", "update_learning_rate"]

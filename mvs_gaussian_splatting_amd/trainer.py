@@ -45,6 +45,9 @@ class OptimizationParams:
     opacitysparse = 0.0
     splitdistance_lr = 0.005
     splitscale_lr = 0.005
+    # this build's: "default" (optim.Adam, every row every step) or "sparse_adam" (optim.SparseGaussianAdam: the rows the
+    # frame saw, as upstream 3DGS names its option)
+    optimizer_type = "default"
 
     def __init__(self, **overrides):
         for k, v in overrides.items():
@@ -70,7 +73,8 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
     """``train.py:72-142`` for one camera, in the reference's order: learning rate, SH degree, background, ``render``
     with the fork's keyword arguments, L1 + D-SSIM against ``camera.original_image``, the opacity sparsity term
     (``opt.opacitysparse``), ``backward``; then, without gradients, the densification statistics, ``densify_and_prune``,
-    ``reset_opacity``, and the optimizer step.  Returns the loss, a 0-dim device tensor.
+    ``reset_opacity``, and the optimizer step (with ``opt.optimizer_type == "sparse_adam"``: of the rows the frame saw,
+    ``SparseGaussianAdam.step(visibility)``).  Returns the loss, a 0-dim device tensor.
 
     dataset: the reference's model namespace (``grow_dir``, ``continous_dir``, ``grow_distance``, the learned-split
     switches, ``white_background``); None is a plain model on a black background.
@@ -105,7 +109,16 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
             if todo["reset"]:
                 model.reset_opacity()
         if todo["step"]:                                                                        # :140-142
-            model.optimizer.step()
+            if getattr(opt, "optimizer_type", "default") == "sparse_adam":
+                # the rows this frame produced a gradient for: the ones it saw, and on a grown / learned-split frame the
+                # selected sources too (a source receives the folded gradient of its virtual copy even when it is off
+                # screen itself).  The sparsity term's gradient lands on low-opacity rows seen or not: opacity goes dense.
+                visibility = pkg["visibility_filter"]
+                if pkg["selected_pts_mask"] is not None:
+                    visibility = visibility | pkg["selected_pts_mask"]
+                model.optimizer.step(visibility, dense=("opacity",) if opt.opacitysparse > 0 else ())
+            else:
+                model.optimizer.step()
             model.optimizer.zero_grad(set_to_none=True)
             if pose_optimizer is not None:
                 pose_optimizer.step()
