@@ -2,13 +2,16 @@
 write every view of the scene as PNG.
 
     python examples/render.py -m <model directory> [--iteration N] [--skip_train] [--skip_test]
-                              [-s <COLMAP or Blender directory>] [-r ...] [--eval] [--white_background]
+                              [-s <COLMAP or Blender directory>] [-r ...] [--eval] [--white_background] [--depth]
 
 The dataset's location and options come from the ``cfg_args.json`` that ``examples/train.py -s ... -m ...`` left in the
 model directory; ``-s`` and the other switches override it.
 
 writes ``<model>/<train|test>/ours_<N>/renders/%05d.png`` and ``.../gt/%05d.png``.  The 8-bit images come from
 ``metrics.to_uint8_hwc`` (torchvision's ``save_image`` rounding) on the device; Pillow only encodes the files.
+``--depth`` also writes ``.../depth/%05d.png``: the expected depth ``depth / alpha`` of every pixel as a 16-bit
+greyscale PNG, scaled so that 65535 is the view's largest value (0 where nothing was composited); the scale of each
+view is listed in ``.../depth/scales.json`` (metres per step).
 """
 import argparse
 import json
@@ -27,18 +30,40 @@ def save_png(image, path):
     Image.fromarray(to_uint8_hwc(image).cpu().numpy()).save(path)
 
 
-def render_set(model_path, name, iteration, views, gaussians, pipeline, background):
+def save_depth_png(depth, alpha, path):
+    """``depth / alpha`` as 16-bit greyscale; returns the depth one step stands for."""
+    import numpy as np
+    from PIL import Image
+    expected = torch.where(alpha > 0, depth / alpha.clamp_min(1e-12), torch.zeros_like(depth))[0]
+    top = float(expected.max())
+    step = top / 65535.0 if top > 0 else 1.0
+    steps = torch.round(expected / step).clamp(0, 65535).cpu().numpy().astype(np.uint16)
+    Image.fromarray(steps).save(path)
+    return step
+
+
+def render_set(model_path, name, iteration, views, gaussians, pipeline, background, depth=False):
     render_path = os.path.join(model_path, name, "ours_{}".format(iteration), "renders")
     gts_path = os.path.join(model_path, name, "ours_{}".format(iteration), "gt")
+    depth_path = os.path.join(model_path, name, "ours_{}".format(iteration), "depth")
     os.makedirs(render_path, exist_ok=True)
     os.makedirs(gts_path, exist_ok=True)
+    scales = []
+    if depth:
+        os.makedirs(depth_path, exist_ok=True)
     for idx, view in enumerate(views):
-        rendering = render(view, gaussians, pipeline, background)["render"]
+        pkg = render(view, gaussians, pipeline, background, **({"return_depth": True} if depth else {}))
+        rendering = pkg["render"]
         save_png(rendering, os.path.join(render_path, "{0:05d}".format(idx) + ".png"))
         save_png(view.original_image[0:3, :, :].to(rendering.device), os.path.join(gts_path, "{0:05d}".format(idx) + ".png"))
+        if depth:
+            scales.append(save_depth_png(pkg["depth"], pkg["alpha"], os.path.join(depth_path, "{0:05d}".format(idx) + ".png")))
+    if depth:
+        with open(os.path.join(depth_path, "scales.json"), "w") as f:
+            json.dump(scales, f)
 
 
-def render_sets(dataset, iteration, pipeline, skip_train=False, skip_test=False):
+def render_sets(dataset, iteration, pipeline, skip_train=False, skip_test=False, depth=False):
     with torch.no_grad():
         gaussians = GaussianModel(dataset.sh_degree)
         scene = Scene(dataset, gaussians, load_iteration=iteration, shuffle=False)
@@ -46,10 +71,10 @@ def render_sets(dataset, iteration, pipeline, skip_train=False, skip_test=False)
         background = torch.tensor(bg_color, dtype=torch.float32, device="cuda")
         if not skip_train:
             render_set(dataset.model_path, "train", scene.loaded_iter, scene.getTrainCameras(), gaussians, pipeline,
-                       background)
+                       background, depth)
         if not skip_test:
             render_set(dataset.model_path, "test", scene.loaded_iter, scene.getTestCameras(), gaussians, pipeline,
-                       background)
+                       background, depth)
     return scene
 
 
@@ -64,6 +89,7 @@ def main(argv=None):
     ap.add_argument("--iteration", type=int, default=-1)
     ap.add_argument("--skip_train", action="store_true")
     ap.add_argument("--skip_test", action="store_true")
+    ap.add_argument("--depth", action="store_true", help="also write depth / alpha of every view as a 16-bit PNG")
     args = ap.parse_args(argv)
     fields = {}
     cfg = os.path.join(args.model_path, "cfg_args.json")
@@ -77,7 +103,7 @@ def main(argv=None):
         ap.error("no cfg_args.json in the model directory: give the dataset with -s")
     dataset = ModelParams(model_path=args.model_path, **fields)
     print("Rendering " + args.model_path)
-    render_sets(dataset, args.iteration, PipelineParams(), args.skip_train, args.skip_test)
+    render_sets(dataset, args.iteration, PipelineParams(), args.skip_train, args.skip_test, args.depth)
 
 
 if __name__ == "__main__":

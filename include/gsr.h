@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 21
+#define GSR_ABI_VERSION 22
 
 enum {
   GSR_OK = 0,
@@ -205,6 +205,50 @@ int gsr_backward(const GsrParams* p, const int32_t* radii, const void* geom_ws, 
                  const void* img_ws, uint32_t num_rendered, uint32_t num_visible,
                  const float* dL_dout_color /* [3,H,W] */,
                  void* bwd_ws, size_t bwd_ws_bytes, const GsrGrads* grads, void* stream);
+
+/* ---- depth, inverse-depth and accumulated-opacity maps of a rendered frame, ABI v22 (csrc/depth.hip) -----------------
+ * For a pixel, let i run over the list entries the colour pass composited there (the first n_contrib entries of the
+ * tile's list that pass the alpha >= 1/255 test: the colour pass's own decisions, taken with its own arithmetic),
+ * w_i = alpha_i T_i and z_i the view-space depth of entry i's Gaussian:
+ *     maps[0] = depth = sum_i w_i z_i,   maps[1] = invdepth = sum_i w_i / z_i,   maps[2] = alpha = sum_i w_i
+ * alpha equals 1 - (final transmittance of the colour pass) bit for bit.  No background term; a pixel outside every
+ * list is 0 in all three.  Kernels of their own: a frame that does not call these entry points runs exactly the launches
+ * it ran before they existed, and GsrParams / GsrGrads keep their layouts.
+ * GsrAuxFrame names the state a forward with p->forward_only = 0 left behind (the arguments of gsr_backward): both calls
+ * only read it, so they may run before or after the frame's gsr_backward, any number of times. */
+typedef struct GsrAuxFrame {
+  int32_t P, width, height;
+  int32_t binning_mode;          /* of the frame's forward */
+  uint32_t num_rendered;         /* what the workspaces were laid out for: the real counts after the two-call forward, */
+  uint32_t num_visible;          /*   (capacity, P) after gsr_forward */
+  const void* geom_ws;           /* device; may be NULL when P == 0 */
+  const void* bin_ws;            /* device; may be NULL when num_rendered == 0 */
+  const void* img_ws;            /* device */
+  const int32_t* radii;          /* device [P] (backward only) */
+} GsrAuxFrame;
+
+/* Gradient outputs of gsr_aux_maps_backward, each written in full: the maps' own contribution to the gradients of the
+ * frame's inputs, in the conventions of GsrGrads (dL_dmeans2D included); the caller adds them to the colour path's.
+ * dL_dscales / dL_drotations (with scales + rotations) or dL_dcov3D (with cov3D_precomp) may be NULL when not wanted.
+ * With GsrParams.act_flags the gradients are those of the raw parameters, as in gsr_backward. */
+typedef struct GsrAuxGrads {
+  float* dL_dmeans3D;   /* device [P,3] */
+  float* dL_dmeans2D;   /* device [P,3] */
+  float* dL_dopacities; /* device [P] */
+  float* dL_dscales;    /* device [P,3] */
+  float* dL_drotations; /* device [P,4] */
+  float* dL_dcov3D;     /* device [P,6] */
+} GsrAuxGrads;
+
+/* maps: device [3,H,W], written in full. */
+int gsr_aux_maps_forward(const GsrAuxFrame* frame, float* maps, void* stream);
+/* p: the inputs of the frame's forward (SH / colour members are not read).  dL_dmaps: device [3,H,W].
+ * acc_ws: device scratch of gsr_aux_maps_backward_bytes(P) bytes, 256-byte aligned: the [P,8] float accumulator the
+ * compositing backward adds into with float atomics (d mean2D x / y in pixels, d conic xx / xy / yy, d opacity, d z, one
+ * spare word); the call zero-fills it.  Atomics reorder: the gradients are reproducible to rounding, not bit for bit. */
+size_t gsr_aux_maps_backward_bytes(int32_t P);
+int gsr_aux_maps_backward(const GsrParams* p, const GsrAuxFrame* frame, const float* dL_dmaps, void* acc_ws,
+                          size_t acc_ws_bytes, const GsrAuxGrads* grads, void* stream);
 
 /* `_C.mark_visible(means3D, viewmatrix, projmatrix)` of the upstream module (unused by the reference): visible[i] = 1
  * when Gaussian i passes the near-plane test of the preprocess stage (view z > 0.2). */

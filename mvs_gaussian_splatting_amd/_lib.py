@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # instead of copying it over the in-tree library
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")
 
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 
 class GsrParams(C.Structure):
@@ -43,6 +43,18 @@ class GsrGrads(C.Structure):
         ("dL_dviewmatrix", C.c_void_p), ("dL_dprojmatrix", C.c_void_p), ("dL_dcampos", C.c_void_p),
         ("camera_ws", C.c_void_p),
     ]
+
+
+class GsrAuxFrame(C.Structure):
+    """The saved state of a rendered frame, as the depth / alpha map entry points take it (include/gsr.h)."""
+    _fields_ = [("P", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("binning_mode", C.c_int32),
+                ("num_rendered", C.c_uint32), ("num_visible", C.c_uint32),
+                ("geom_ws", C.c_void_p), ("bin_ws", C.c_void_p), ("img_ws", C.c_void_p), ("radii", C.c_void_p)]
+
+
+class GsrAuxGrads(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("dL_dmeans3D", "dL_dmeans2D", "dL_dopacities", "dL_dscales", "dL_drotations",
+                                          "dL_dcov3D")]
 
 
 class GsrGrow(C.Structure):
@@ -126,6 +138,11 @@ SYMBOLS = {
     "gsr_enable_markers": (C.c_int, [C.c_int32]),
     "gsr_backward": (C.c_int, [C.POINTER(GsrParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(GsrGrads), C.c_void_p]),
+    # depth / inverse-depth / alpha maps of a rendered frame and their gradients (csrc/depth.hip; rasterizer.py)
+    "gsr_aux_maps_forward": (C.c_int, [C.POINTER(GsrAuxFrame), C.c_void_p, C.c_void_p]),
+    "gsr_aux_maps_backward_bytes": (C.c_size_t, [C.c_int32]),
+    "gsr_aux_maps_backward": (C.c_int, [C.POINTER(GsrParams), C.POINTER(GsrAuxFrame), C.c_void_p, C.c_void_p, C.c_size_t,
+                                        C.POINTER(GsrAuxGrads), C.c_void_p]),
     "gsr_mark_visible": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gsr_sort_scratch_bytes": (C.c_size_t, [C.c_uint32]),
     "gsr_sort_pairs_u64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32,

@@ -560,6 +560,84 @@ int gsr_backward(const GsrParams* p, const int32_t* radii, const void* geom_ws, 
   return check(p, s, "preprocess_bwd");
 }
 
+// ---- depth / inverse-depth / alpha maps (csrc/depth.hip) -----------------------------------------------------------
+static int validate_aux_frame(const GsrAuxFrame* f) {
+  if (!f) return fail(GSR_E_BADARG, "frame is NULL");
+  if (f->P < 0 || f->width <= 0 || f->height <= 0) return fail(GSR_E_BADARG, "bad P / image size");
+  if (f->width > 8191 * TILE || f->height > 8191 * TILE) return fail(GSR_E_BADARG, "image too large (13-bit tile coordinates)");
+  if (!f->img_ws) return fail(GSR_E_BADARG, "img_ws is NULL");
+  if (f->binning_mode != GSR_BINNING_TWO_LEVEL && f->binning_mode != GSR_BINNING_KEYS64 &&
+      f->binning_mode != GSR_BINNING_TWO_LEVEL_CULLED)
+    return fail(GSR_E_BADARG, "unknown binning_mode");
+  if (f->P > 0 && f->num_rendered > 0 && (!f->geom_ws || !f->bin_ws)) return fail(GSR_E_BADARG, "geom_ws / bin_ws is NULL");
+  return 0;
+}
+
+// the members of GsrParams the maps' backward reads (validate() also insists on a colour input, which it does not need)
+static int validate_aux_inputs(const GsrParams* p) {
+  if (p->P <= 0) return 0;
+  if (!p->means3D || !p->opacities || !p->viewmatrix || !p->projmatrix)
+    return fail(GSR_E_BADARG, "means3D / opacities / viewmatrix / projmatrix must be non-NULL");
+  const bool sr = p->scales != nullptr || p->rotations != nullptr;
+  if (sr && (p->scales == nullptr || p->rotations == nullptr))
+    return fail(GSR_E_BADARG, "scales and rotations must be given together");
+  if (sr == (p->cov3D_precomp != nullptr))
+    return fail(GSR_E_BADARG, "provide exactly one of (scales, rotations) / cov3D_precomp");
+  if ((p->act_flags & (GSR_ACT_SCALE_EXP | GSR_ACT_ROT_NORMALIZE)) && !p->scales)
+    return fail(GSR_E_BADARG, "scale / rotation activations need the scales + rotations inputs");
+  if (p->rotations && ((uintptr_t)p->rotations & 15u) != 0) return fail(GSR_E_ALIGN, "rotations must be 16-byte aligned");
+  return 0;
+}
+
+size_t gsr_aux_maps_backward_bytes(int32_t P) { return align_up(32 * (size_t)(P > 0 ? P : 1), 256); }
+
+int gsr_aux_maps_forward(const GsrAuxFrame* f, float* maps, void* stream) {
+  if (int rc = validate_aux_frame(f)) return rc;
+  if (!maps) return fail(GSR_E_BADARG, "maps is NULL");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const ImageLayout I(f->width, f->height);
+  if (f->P == 0 || f->num_rendered == 0) {      // nothing was binned: every list is empty
+    GSR_HIP(hipMemsetAsync(maps, 0, 12 * (size_t)f->width * f->height, s));
+    return 0;
+  }
+  const GeomLayout L(f->P);
+  const SortedViews sv = sorted_views(f->bin_ws, f->num_rendered, f->num_visible, f->width, f->height, f->binning_mode);
+  launch_aux_maps_fwd(f->width, f->height, at<uint2>(f->img_ws, I.ranges), sv.point_list, at<GeomRec>(f->geom_ws, L.rec),
+                      at<BinInfo>(f->geom_ws, L.bin), at<uint32_t>(f->img_ws, I.n_contrib),
+                      at<uint32_t>(f->img_ws, I.tile_order), maps, s);
+  return check(nullptr, s, "aux_maps_fwd");
+}
+
+int gsr_aux_maps_backward(const GsrParams* p, const GsrAuxFrame* f, const float* dL_dmaps, void* acc_ws,
+                          size_t acc_ws_bytes, const GsrAuxGrads* g, void* stream) {
+  if (!p) return fail(GSR_E_BADARG, "params is NULL");
+  if (p->forward_only) return fail(GSR_E_BADARG, "the forward ran with forward_only = 1: no state for a backward");
+  if (int rc = validate_aux_frame(f)) return rc;
+  if (int rc = validate_aux_inputs(p)) return rc;
+  if (f->P != p->P || f->width != p->width || f->height != p->height) return fail(GSR_E_BADARG, "frame and params disagree");
+  if (!g) return fail(GSR_E_BADARG, "grads is NULL");
+  if (p->P == 0) return 0;
+  if (!dL_dmaps || !acc_ws || !f->radii) return fail(GSR_E_BADARG, "NULL workspace / input");
+  if (!g->dL_dmeans3D || !g->dL_dmeans2D || !g->dL_dopacities)
+    return fail(GSR_E_BADARG, "dL_dmeans3D / dL_dmeans2D / dL_dopacities must be non-NULL");
+  if (acc_ws_bytes < gsr_aux_maps_backward_bytes(p->P)) return fail(GSR_E_CAPACITY, "accumulator workspace too small");
+  if (((uintptr_t)acc_ws & 255u) != 0) return fail(GSR_E_ALIGN, "acc_ws must be 256-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const ImageLayout I(f->width, f->height);
+  const GeomLayout L(f->P);
+  float* acc = static_cast<float*>(acc_ws);
+  GSR_HIP(hipMemsetAsync(acc, 0, 32 * (size_t)p->P, s));
+  if (f->num_rendered > 0) {
+    const SortedViews sv = sorted_views(f->bin_ws, f->num_rendered, f->num_visible, f->width, f->height, f->binning_mode);
+    launch_aux_maps_bwd(f->width, f->height, at<uint2>(f->img_ws, I.ranges), sv.point_list, at<GeomRec>(f->geom_ws, L.rec),
+                        at<BinInfo>(f->geom_ws, L.bin), at<uint32_t>(f->img_ws, I.n_contrib), at<float>(f->img_ws, I.final_T),
+                        at<uint32_t>(f->img_ws, I.tile_order), dL_dmaps, acc, s);
+    if (int rc = check(p, s, "aux_maps_bwd")) return rc;
+  }
+  launch_aux_geom_bwd(*p, f->radii, acc, *g, s);
+  return check(p, s, "aux_geom_bwd");
+}
+
 int gsr_profile_create(void** handle) {
   if (!handle) return fail(GSR_E_BADARG, "handle is NULL");
   *handle = new Profile();

@@ -99,6 +99,15 @@ void launch_render_bwd(int W, int H, const uint2* ranges, const uint32_t* point_
                        const float* dL_dpix, GradRow* rows, uint8_t* row_flags, const uint32_t* tile_order,
                        hipStream_t s, const uint16_t* inst_mask);
 
+// depth.hip: depth / inverse-depth / alpha maps of a rendered frame and their gradients (acc: zeroed [P,8] floats)
+void launch_aux_maps_fwd(int W, int H, const uint2* ranges, const uint32_t* point_list, const GeomRec* rec,
+                         const BinInfo* bin, const uint32_t* n_contrib, const uint32_t* tile_order, float* out,
+                         hipStream_t s);
+void launch_aux_maps_bwd(int W, int H, const uint2* ranges, const uint32_t* point_list, const GeomRec* rec,
+                         const BinInfo* bin, const uint32_t* n_contrib, const float* final_T, const uint32_t* tile_order,
+                         const float* dL_dmaps, float* acc, hipStream_t s);
+void launch_aux_geom_bwd(const GsrParams& p, const int32_t* radii, const float* acc, const GsrAuxGrads& g, hipStream_t s);
+
 // loss.hip
 void launch_l1_dssim(const float* x, const float* gt, int C, int H, int W, float lambda, int dssim_mode, float* sums,
                      float* dL_dx, float* maps, hipStream_t s);

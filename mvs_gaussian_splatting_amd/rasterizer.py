@@ -26,6 +26,11 @@ Camera gradients.  ``GaussianRasterizationSettings`` stays the 12-field tuple.  
 and receive gradients of their own shapes ([4,4], [4,4], [3]; entries the rasterizer does not read -- ``viewmatrix``
 column 3, ``projmatrix`` column 2 -- are zero): ``scene.PoseCamera`` builds such tensors from a learnable pose.  A frame
 whose camera does not require grad takes the path, the kernels and the allocations it always took.
+
+Depth / alpha maps.  ``GaussianRasterizer(settings, aux_maps=True)`` returns ``(color, radii, aux)``: ``aux [3,H,W]`` holds
+the depth (``sum w z``), inverse-depth (``sum w / z``) and accumulated-opacity (``sum w``) maps of the frame, from
+kernels of their own (``csrc/depth.hip``) behind a second autograd node (``_AuxMaps``) that reads the colour node's frame.
+Without ``aux_maps`` nothing of it runs.
 """
 from __future__ import annotations
 
@@ -802,13 +807,145 @@ class _NoGraph:
         pass
 
 
+class _KeepFrame(_NoGraph):
+    """A stand-in context that keeps what the colour forward saves: the frame of a forward that runs outside autograd
+    but whose depth / alpha maps are wanted."""
+
+    def save_for_backward(self, *tensors):
+        self.saved_tensors = tensors
+
+
+def _frame_of(node):
+    """(_Frame, binning mode) of a colour node: its autograd context, or a ``_KeepFrame``.  The workspaces are the
+    tensors the node saved, by reference."""
+    radii, geom, binning, img = node.saved_tensors[-4:]
+    return _Frame(geom, binning, img, radii, node.layout[0], node.layout[1], node.frame_pending, node.counts), node.binning_mode
+
+
+def _aux_frame(frame: _Frame, P: int, W: int, H: int, binning_mode: int) -> "_lib.GsrAuxFrame":
+    f = _lib.GsrAuxFrame()
+    f.P, f.width, f.height, f.binning_mode = P, W, H, int(binning_mode)
+    f.num_rendered, f.num_visible = int(frame.layout_R), int(frame.layout_V)
+    f.geom_ws, f.bin_ws, f.img_ws, f.radii = _ptr(frame.geom), _ptr(frame.binning), _ptr(frame.img), _ptr(frame.radii)
+    return f
+
+
+class _AuxMaps(torch.autograd.Function):
+    """Depth, inverse-depth and accumulated-opacity maps ``[3,H,W]`` of a frame the colour operator has rendered
+    (``include/gsr.h``: gsr_aux_maps_*; ``csrc/depth.hip``).  A node of its own next to the colour node: it reads the
+    colour node's frame (the same ``geom`` / ``binning`` / ``img`` tensors, by reference) and returns the maps' own
+    gradients for means3D, means2D, opacities and scales / rotations or cov3D_precomp; autograd adds them to the colour
+    node's.  ``act_flags``: the geometry inputs are the raw parameters of the fused path."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, opacities, scales, rotations, cov3Ds_precomp,
+                raster_settings: GaussianRasterizationSettings, frame: _Frame, binning_mode: int, act_flags: int = 0):
+        lib = _lib.load()
+        dev = _require_gpu(means3D)
+        P = int(means3D.shape[0])
+        means3D = _f32c(means3D, "means3D", dev)
+        opacities = _f32c(opacities, "opacities", dev)
+        scales = _f32c(scales, "scales", dev)
+        rotations = _f32c(rotations, "rotations", dev, align16=True)
+        cov3Ds_precomp = _f32c(cov3Ds_precomp, "cov3D_precomp", dev)
+        H, W = int(raster_settings.image_height), int(raster_settings.image_width)
+        maps = torch.empty(3, H, W, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.gsr_aux_maps_forward(C.byref(_aux_frame(frame, P, W, H, binning_mode)), maps.data_ptr(),
+                                                _stream(dev)), "gsr_aux_maps_forward")
+        ctx.raster_settings = raster_settings
+        ctx.layout = (frame.layout_R, frame.layout_V)
+        ctx.frame_pending = frame.pending
+        ctx.counts = frame.counts
+        ctx.binning_mode = binning_mode
+        ctx.act_flags = int(act_flags)
+        ctx.has_means2D = means2D is not None
+        ctx.save_for_backward(means3D, opacities, scales, rotations, cov3Ds_precomp, frame.radii, frame.geom,
+                              frame.binning, frame.img)
+        return maps
+
+    @staticmethod
+    def backward(ctx, grad_maps):
+        if grad_maps is None:
+            return (None,) * 10
+        lib = _lib.load()
+        means3D, opacities, scales, rotations, cov3Ds_precomp, radii, geom, binning, img = ctx.saved_tensors
+        settings = ctx.raster_settings
+        dev = means3D.device
+        P = int(means3D.shape[0])
+        H, W = int(settings.image_height), int(settings.image_width)
+        if ctx.frame_pending is not None:
+            _verify(ctx.frame_pending, block=True)      # deferred mode: as the colour backward
+        grad_maps = _f32c(grad_maps, "grad_maps", dev)
+        empty = torch.empty(0, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            params, keep = _make_params(dev, settings, means3D, empty, empty, opacities, scales, rotations,
+                                        cov3Ds_precomp, act_flags=ctx.act_flags)
+            params.profile = None
+            params.binning_mode = ctx.binning_mode
+            new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
+            g_means3D, g_means2D, g_opac = new(P, 3), new(P, 3), new(*opacities.shape)
+            g_scales = new(P, 3) if scales.numel() else None
+            g_rot = new(P, 4) if rotations.numel() else None
+            g_cov = new(P, 6) if cov3Ds_precomp.numel() else None
+            grads = _lib.GsrAuxGrads(_ptr(g_means3D), _ptr(g_means2D), _ptr(g_opac), _ptr(g_scales), _ptr(g_rot),
+                                     _ptr(g_cov))
+            nbytes = lib.gsr_aux_maps_backward_bytes(P)
+            acc = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            frame = _Frame(geom, binning, img, radii, ctx.layout[0], ctx.layout[1], ctx.frame_pending, ctx.counts)
+            _lib.check(lib.gsr_aux_maps_backward(C.byref(params), C.byref(_aux_frame(frame, P, W, H, ctx.binning_mode)),
+                                                 grad_maps.data_ptr(), acc.data_ptr(), nbytes, C.byref(grads),
+                                                 _stream(dev)), "gsr_aux_maps_backward")
+        del keep
+        return (g_means3D, g_means2D if ctx.has_means2D else None, g_opac, g_scales, g_rot, g_cov, None, None, None, None)
+
+
+def _aux_maps_of(node, grad: bool, means3D, means2D, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
+                 act_flags: int = 0):
+    frame, mode = _frame_of(node)
+    if grad:
+        return _AuxMaps.apply(means3D, means2D, opacities, scales, rotations, cov3Ds_precomp, raster_settings, frame,
+                              mode, act_flags)
+    return _AuxMaps.forward(_NoGraph(), means3D, means2D, opacities, scales, rotations, cov3Ds_precomp,
+                            raster_settings, frame, mode, act_flags)
+
+
+def _check_aux_request(cam, state_key=None, densify_stats=None) -> None:
+    if densify_stats is not None:
+        raise ValueError("aux_maps=True cannot be combined with densify_stats: the in-backward statistics would see the "
+                         "colour node's dL/dmeans2D alone, without the maps' share (take them from the summed "
+                         "means2D.grad after the backward)")
+    if cam:
+        raise ValueError("aux_maps=True cannot be combined with camera tensors that require grad: the depth / alpha maps "
+                         "have no camera gradients (detach viewmatrix / projmatrix / campos, or render the maps in a "
+                         "frame of their own)")
+    if state_key is not None:
+        raise ValueError("aux_maps=True is not available on a frame with grown / split rows appended")
+
+
 def rasterize_gaussians_fused(means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations, raster_settings,
-                              densify_stats=None, visible=None, _state_key=None):
+                              densify_stats=None, visible=None, _state_key=None, aux_maps=False):
     """``densify_stats``: None, or (xyz_gradient_accum, denom, max_radii2D) -- the backward then also accumulates the
     densification statistics of ``scene/gaussian_model.py:775-777`` / ``train.py:130``.
     ``visible``: None, or a bool [P] tensor that receives ``radii > 0`` from the preprocess kernel.
-    ``_state_key`` (internal): the capacity state of grown frames (``_grown_key``) instead of the one of P rows."""
+    ``_state_key`` (internal): the capacity state of grown frames (``_grown_key``) instead of the one of P rows.
+    ``aux_maps``: also return the depth / inverse-depth / alpha maps ``[3,H,W]`` (``_AuxMaps``) as a third result."""
     cam = _camera_inputs(raster_settings)
+    if aux_maps:
+        _check_aux_request(cam, _state_key, densify_stats)
+        empty = torch.empty(0, dtype=torch.float32, device=means3D.device)
+        flags = _lib.ACT_SCALE_EXP | _lib.ACT_ROT_NORMALIZE | _lib.ACT_OPACITY_SIGMOID
+        geometry = (means3D, means2D, raw_opacity, raw_scales, raw_rotations, empty, raster_settings, flags)
+        if _forward_only(means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations):
+            with torch.no_grad():       # the maps read the state only a forward that tracks its contributors leaves
+                node = _KeepFrame()
+                color, radii = _RasterizeGaussiansFused.forward(node, means3D, means2D, f_dc, f_rest, raw_opacity,
+                                                                raw_scales, raw_rotations, raster_settings, False, None,
+                                                                visible)
+                return color, radii, _aux_maps_of(node, False, *geometry)
+        color, radii = _RasterizeGaussiansFused.apply(means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales,
+                                                      raw_rotations, raster_settings, False, densify_stats, visible)
+        return color, radii, _aux_maps_of(color.grad_fn, True, *geometry)
     if _forward_only(means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations, *cam):
         with torch.no_grad():
             return _RasterizeGaussiansFused.forward(_NoGraph(), means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales,
@@ -818,8 +955,20 @@ def rasterize_gaussians_fused(means3D, means2D, f_dc, f_rest, raw_opacity, raw_s
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, densify_stats=None):
+                        raster_settings, densify_stats=None, aux_maps=False):
     cam = _camera_inputs(raster_settings)
+    if aux_maps:
+        _check_aux_request(cam, densify_stats=densify_stats)
+        geometry = (means3D, means2D, opacities, scales, rotations, cov3Ds_precomp, raster_settings)
+        if _forward_only(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp):
+            with torch.no_grad():       # the maps read the state only a forward that tracks its contributors leaves
+                node = _KeepFrame()
+                color, radii = _RasterizeGaussians.forward(node, means3D, means2D, sh, colors_precomp, opacities, scales,
+                                                           rotations, cov3Ds_precomp, raster_settings, False, None)
+                return color, radii, _aux_maps_of(node, False, *geometry)
+        color, radii = _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                                 cov3Ds_precomp, raster_settings, False, densify_stats)
+        return color, radii, _aux_maps_of(color.grad_fn, True, *geometry)
     if _forward_only(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, *cam):
         with torch.no_grad():
             return _RasterizeGaussians.forward(_NoGraph(), means3D, means2D, sh, colors_precomp, opacities, scales,
@@ -832,9 +981,13 @@ class GaussianRasterizer(nn.Module):
     """Same call contract as the module the reference constructs per frame
     (``gaussian_renderer/__init__.py:57``) and calls at ``:257-265``."""
 
-    def __init__(self, raster_settings: GaussianRasterizationSettings):
+    def __init__(self, raster_settings: GaussianRasterizationSettings, aux_maps: bool = False):
+        """``aux_maps=True``: the call returns ``(color, radii, aux)`` with ``aux [3,H,W]`` = the depth
+        (``sum w z``), inverse-depth (``sum w / z``) and accumulated-opacity (``sum w``) maps of the frame,
+        differentiable in means3D, means2D, opacities and scales / rotations or cov3D_precomp."""
         super().__init__()
         self.raster_settings = raster_settings
+        self.aux_maps = bool(aux_maps)
 
     def markVisible(self, positions: torch.Tensor) -> torch.Tensor:
         """Frustum (near-plane) visibility of the upstream module's ``markVisible``; bool ``[P]``."""
@@ -863,9 +1016,9 @@ class GaussianRasterizer(nn.Module):
         rotations = empty if rotations is None else rotations
         cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                   cov3D_precomp, raster_settings, densify_stats)
+                                   cov3D_precomp, raster_settings, densify_stats, aux_maps=self.aux_maps)
 
     def forward_fused(self, means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations, densify_stats=None):
         """Raw-parameter entry: see :class:`_RasterizeGaussiansFused`."""
         return rasterize_gaussians_fused(means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations,
-                                         self.raster_settings, densify_stats)
+                                         self.raster_settings, densify_stats, aux_maps=self.aux_maps)

@@ -66,6 +66,11 @@ def _fused_stats(pc, pipe, xyz):
     return trio
 
 
+def _aux_entries(aux: torch.Tensor) -> dict:
+    """The operator's ``[3,H,W]`` maps as the three ``[1,H,W]`` entries of the result dict."""
+    return {"depth": aux[0:1], "invdepth": aux[1:2], "alpha": aux[2:3]}
+
+
 def _settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier):
     return GaussianRasterizationSettings(
         image_height=int(viewpoint_camera.image_height),
@@ -85,7 +90,7 @@ def _settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier):
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier: float = 1.0,
            override_color=None, grow_dir=False, densify_grad_threshold=0, iteration=None, opt=None,
-           continous_dir=False, grow_distance=False, modelcg=None, cameras_extent=None):
+           continous_dir=False, grow_distance=False, modelcg=None, cameras_extent=None, return_depth=False):
     """Render the scene; ``bg_color`` must be on the GPU.  Returns the reference's result dict
     (``gaussian_renderer/__init__.py:309-313``).  The keyword arguments after ``override_color`` are the reference's
     (``:19``) and drive the grow / learned-split branch (module docstring); the frame of a closed branch is unchanged.
@@ -93,8 +98,18 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier:
     ``pipe.fuse_densify_stats = True`` (this build's extension) makes the backward of this frame also run
     ``add_densification_stats`` (``scene/gaussian_model.py:775-777``) and the ``max_radii2D`` update of ``train.py:130``
     on the model's accumulators; the ``add_densification_stats`` of this package then recognises the frame and does
-    nothing, so the reference's call sequence (render, backward, add_densification_stats) stays as it is."""
+    nothing, so the reference's call sequence (render, backward, add_densification_stats) stays as it is.
+
+    ``return_depth=True`` (this build's extension): the dict gains ``"depth"`` (``sum w z``), ``"invdepth"``
+    (``sum w / z``, upstream's inverse-depth map) and ``"alpha"`` (``sum w = 1 - T``), each ``[1,H,W]`` and
+    differentiable; ``z`` is the view-space depth, there is no background term.  On such a frame the in-backward
+    densification statistics are not taken (``viewspace_points.grad`` is the sum of the colour node's and the maps'
+    node's gradients, which only exists after the backward): ``add_densification_stats`` reads it, as on grown frames.
+    Not available on a frame of the open grow / learned-split branch."""
     which = grow.branch(iteration, opt, grow_dir, continous_dir, modelcg)
+    if which is not None and return_depth:
+        raise ValueError("return_depth=True is not available on a frame of the open grow / learned-split branch "
+                         "(virtual rows appended): render the maps in a frame of their own")
     if which is not None:
         return _render_grown(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, which, grow_dir,
                              densify_grad_threshold, continous_dir, grow_distance, modelcg, cameras_extent)
@@ -105,7 +120,7 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier:
     # The operator never reads (or writes) its values, so every frame's leaf aliases one cached block of zeros: a
     # fresh 72 MB memset per frame is 20 us of the 6 M-Gaussian forward.
     screenspace_points = _zero_leaf(xyz)
-    stats = _fused_stats(pc, pipe, xyz)
+    stats = None if return_depth else _fused_stats(pc, pipe, xyz)
     if stats is not None:
         screenspace_points._gsr_stats_fused = True      # read by losses.add_densification_stats
 
@@ -116,13 +131,20 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier:
         # visibility_filter (= radii > 0, gaussian_renderer/__init__.py:311) is stored by the preprocess kernel itself:
         # a torch compare over 6 M radii is a 9-us kernel per frame
         visible = torch.empty(xyz.shape[0], dtype=torch.bool, device=xyz.device)
+        if return_depth:
+            rendered_image, radii, aux = rasterize_gaussians_fused(xyz, screenspace_points, pc._features_dc,
+                                                                   pc._features_rest, pc._opacity, pc._scaling,
+                                                                   pc._rotation, raster_settings, visible=visible,
+                                                                   aux_maps=True)
+            return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": visible,
+                    "radii": radii, "selected_pts_mask": None, **_aux_entries(aux)}
         rendered_image, radii = rasterize_gaussians_fused(xyz, screenspace_points, pc._features_dc, pc._features_rest,
                                                           pc._opacity, pc._scaling, pc._rotation, raster_settings,
                                                           densify_stats=stats, visible=visible)
         return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": visible,
                 "radii": radii, "selected_pts_mask": None}
 
-    rasterizer = GaussianRasterizer(raster_settings=raster_settings)
+    rasterizer = GaussianRasterizer(raster_settings=raster_settings, **({"aux_maps": True} if return_depth else {}))
     scales = rotations = cov3D_precomp = None
     if getattr(pipe, "compute_cov3D_python", False):
         cov3D_precomp = pc.get_covariance(scaling_modifier)
@@ -145,14 +167,16 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier:
     # exactly the reference's eight keyword arguments (gaussian_renderer/__init__.py:257-265); the statistics request of
     # this build travels as a ninth only when the caller asked for it
     extra = {} if stats is None else {"densify_stats": stats}
-    rendered_image, radii = rasterizer(means3D=xyz, means2D=screenspace_points, shs=shs,
-                                       colors_precomp=colors_precomp, opacities=pc.get_opacity, scales=scales,
-                                       rotations=rotations, cov3D_precomp=cov3D_precomp, **extra)
+    out = rasterizer(means3D=xyz, means2D=screenspace_points, shs=shs,
+                     colors_precomp=colors_precomp, opacities=pc.get_opacity, scales=scales,
+                     rotations=rotations, cov3D_precomp=cov3D_precomp, **extra)
+    rendered_image, radii = out[0], out[1]
     return {"render": rendered_image,
             "viewspace_points": screenspace_points,
             "visibility_filter": radii > 0,
             "radii": radii,
-            "selected_pts_mask": None}
+            "selected_pts_mask": None,
+            **(_aux_entries(out[2]) if return_depth else {})}
 
 
 def _render_grown(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, which, grow_dir,

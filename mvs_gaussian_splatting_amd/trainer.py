@@ -69,7 +69,7 @@ def schedule(opt, iteration: int, white_background: bool = False) -> dict:
 
 
 def training_iteration(model, camera, opt, pipe, background, iteration, *, dataset=None, cameras_extent,
-                       first_reset=None, gt_image=None, densify_kwargs=None, pose_optimizer=None):
+                       first_reset=None, gt_image=None, densify_kwargs=None, pose_optimizer=None, depth_loss=None):
     """``train.py:72-142`` for one camera, in the reference's order: learning rate, SH degree, background, ``render``
     with the fork's keyword arguments, L1 + D-SSIM against ``camera.original_image``, the opacity sparsity term
     (``opt.opacitysparse``), ``backward``; then, without gradients, the densification statistics, ``densify_and_prune``,
@@ -83,7 +83,11 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
     gt_image: the target instead of ``camera.original_image``.  densify_kwargs: passed on to ``densify_and_prune``
     (``noise``, ``dir_noise``, ``spatial_order``).
     pose_optimizer: an optimizer over the parameters of ``camera`` when that is a ``scene.PoseCamera`` (the backward
-    leaves dL/dpose in them); it is stepped and zeroed where the model's optimizer is.  None: the camera is not refined."""
+    leaves dL/dpose in them); it is stepped and zeroed where the model's optimizer is.  None: the camera is not refined.
+    depth_loss: None, or ``(target, weight)`` with ``target [1,H,W]`` an inverse-depth map (from multi-view stereo, say):
+    the frame is rendered with ``return_depth=True`` and ``weight * mean|invdepth - target|`` joins the loss (plain torch
+    ops on the map; the map and its gradients are the HIP path's).  Not on a frame of the open grow / learned-split
+    branch."""
     flag = lambda name: bool(getattr(dataset, name, False))      # noqa: E731
     if first_reset is None:
         first_reset = flag("white_background")
@@ -94,11 +98,15 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
     bg = torch.rand((3), device=background.device) if opt.random_background else background    # :89
     pkg = render(camera, model, pipe, bg, grow_dir=flag("grow_dir"), densify_grad_threshold=opt.densify_grad_threshold,
                  iteration=iteration, opt=opt, continous_dir=flag("continous_dir"), grow_distance=flag("grow_distance"),
-                 modelcg=dataset, cameras_extent=cameras_extent)                                # :91
+                 modelcg=dataset, cameras_extent=cameras_extent,                                # :91
+                 **({} if depth_loss is None else {"return_depth": True}))
     gt = camera.original_image if gt_image is None else gt_image
     loss = l1_dssim_loss(pkg["render"], gt.to(pkg["render"].device), opt.lambda_dssim)          # :99-101
     if opt.opacitysparse > 0:                                                                   # :102-106
         loss = loss + opacity_sparsity_loss(model._opacity, opt.opacitysparse)
+    if depth_loss is not None:
+        depth_target, depth_weight = depth_loss
+        loss = loss + float(depth_weight) * (pkg["invdepth"] - depth_target.to(pkg["invdepth"].device)).abs().mean()
     loss.backward()                                                                             # :107
     with torch.no_grad():
         if todo["stats"]:                                                                       # :127-137

@@ -1,0 +1,86 @@
+"""Restatement of the depth / inverse-depth / alpha maps over the oracle's public results (float64 or float32).
+
+For a pixel, i runs over the entries of its tile's list that the oracle's colour pass composited: the first
+``n_contrib[pixel]`` entries that pass the oracle's two skip tests (``power > 0``, ``alpha < 1/255``).  With
+``w_i = alpha_i T_i`` and ``z_i`` the view-space depth:
+
+    depth = sum w z,   invdepth = sum w / z,   alpha = sum w          (no background term)
+
+Everything differentiable comes from ``pre["v_depth"]``, ``v_xy``, ``v_conic`` and ``v_opacity`` of
+``oracle.rasterize_ref(..., want_aux=True)``, so autograd reaches the operator's inputs through the oracle's own
+preprocess (its upstream-convention backward pieces included).  The 0.99 clamp passes the gradient on, as the oracle's
+colour pass does.  Shared by tests/test_depth_host.py and tests/test_gpu_depth.py.
+"""
+import numpy as np
+import torch
+
+from oracle import rasterize_ref
+
+TILE = 16
+ALPHA_MIN = 1.0 / 255.0
+ALPHA_MAX = 0.99
+
+
+def maps_from_lists(pre, point_list, ranges, n_contrib, settings):
+    """-> maps [3,H,W] (depth, invdepth, alpha) in the dtype of ``pre``; ``point_list`` / ``ranges`` / ``n_contrib`` are
+    the oracle's (held fixed: they are decisions, not differentiable quantities)."""
+    dt = pre["v_xy"].dtype
+    H, W = int(settings.image_height), int(settings.image_width)
+    grid_x, grid_y = pre["grid"]
+    slot_of = torch.full((int(pre["radii"].shape[0]),), -1, dtype=torch.int64)
+    slot_of[pre["idx"]] = torch.arange(pre["idx"].shape[0])
+    plist = torch.from_numpy(np.asarray(point_list).astype(np.int64))
+    xy, conic, opac, depth = pre["v_xy"], pre["v_conic"], pre["v_opacity"], pre["v_depth"]
+    lx = torch.arange(TILE).repeat(TILE)
+    ly = torch.arange(TILE).repeat_interleave(TILE)
+    a_min = torch.tensor(ALPHA_MIN, dtype=dt)
+    nc = torch.zeros(grid_y * TILE, grid_x * TILE, dtype=torch.int64)
+    nc[:H, :W] = n_contrib.to(torch.int64)
+    zero_tile = torch.zeros(3, TILE, TILE, dtype=dt)
+    rows = []
+    for ty in range(grid_y):
+        row = []
+        for tx in range(grid_x):
+            t = ty * grid_x + tx
+            last = nc[ty * TILE:(ty + 1) * TILE, tx * TILE:(tx + 1) * TILE].reshape(-1)
+            n = int(last.max())
+            if n == 0:
+                row.append(zero_tile)
+                continue
+            s = int(ranges[t, 0])
+            assert s + n <= int(ranges[t, 1])
+            sl = slot_of[plist[s:s + n]]
+            pxf = (tx * TILE + lx).to(dt)
+            pyf = (ty * TILE + ly).to(dt)
+            g_xy, g_con, g_o, g_z = xy[sl], conic[sl], opac[sl], depth[sl]
+            dx = g_xy[:, 0:1] - pxf[None, :]
+            dy = g_xy[:, 1:2] - pyf[None, :]
+            power = -0.5 * (g_con[:, 0:1] * dx * dx + g_con[:, 2:3] * dy * dy) - g_con[:, 1:2] * dx * dy
+            raw = g_o[:, None] * torch.exp(power)
+            alpha = raw + (torch.clamp_max(raw, ALPHA_MAX) - raw).detach()
+            pos = torch.arange(n)[:, None]
+            use = (power <= 0) & (alpha >= a_min) & (pos < last[None, :])
+            one_minus = torch.where(use, 1.0 - alpha, torch.ones_like(alpha))
+            cp = torch.cumprod(one_minus, dim=0)
+            T_excl = torch.cat([torch.ones(1, TILE * TILE, dtype=dt), cp[:-1]], dim=0)
+            w = torch.where(use, alpha * T_excl, torch.zeros_like(alpha))
+            m = torch.stack([(w * g_z[:, None]).sum(0), (w / g_z[:, None]).sum(0), w.sum(0)], dim=0)
+            row.append(m.reshape(3, TILE, TILE))
+        rows.append(torch.cat(row, dim=2))
+    return torch.cat(rows, dim=1)[:, :H, :W]
+
+
+def maps_ref(means3D, means2D, opacities, settings, **kw):
+    """The oracle's frame and its maps: -> (maps [3,H,W], color, radii, aux) with ``aux["margin"]`` etc."""
+    color, radii, aux = rasterize_ref(means3D, means2D, opacities, settings, want_aux=True, want_margin=True, **kw)
+    maps = maps_from_lists(aux["pre"], aux["point_list"], aux["ranges"], aux["n_contrib"], settings)
+    return maps, color, radii, aux
+
+
+def map_weights(H, W, seed=4711):
+    """Fixed weights in (-1, 1) for the smooth loss ``sum(w * maps) / (3 H W)`` that mixes the three maps."""
+    return torch.rand((3, H, W), generator=torch.Generator().manual_seed(seed), dtype=torch.float64) * 2.0 - 1.0
+
+
+def maps_loss(maps, weights):
+    return (maps * weights.to(maps.dtype).to(maps.device)).sum() / weights.numel()
