@@ -3,6 +3,7 @@ write every view of the scene as PNG.
 
     python examples/render.py -m <model directory> [--iteration N] [--skip_train] [--skip_test]
                               [-s <COLMAP or Blender directory>] [-r ...] [--eval] [--white_background] [--depth]
+                              [--use_trained_exp]
 
 The dataset's location and options come from the ``cfg_args.json`` that ``examples/train.py -s ... -m ...`` left in the
 model directory; ``-s`` and the other switches override it.
@@ -12,6 +13,8 @@ writes ``<model>/<train|test>/ours_<N>/renders/%05d.png`` and ``.../gt/%05d.png`
 ``--depth`` also writes ``.../depth/%05d.png``: the expected depth ``depth / alpha`` of every pixel as a 16-bit
 greyscale PNG, scaled so that 65535 is the view's largest value (0 where nothing was composited); the scale of each
 view is listed in ``.../depth/scales.json`` (metres per step).
+``--use_trained_exp`` renders every view that has one with the exposure saved in the iteration's ``exposure.json``
+(``examples/train.py --train_exposure``); test views have none and are rendered as they are.
 """
 import argparse
 import json
@@ -42,7 +45,8 @@ def save_depth_png(depth, alpha, path):
     return step
 
 
-def render_set(model_path, name, iteration, views, gaussians, pipeline, background, depth=False):
+def render_set(model_path, name, iteration, views, gaussians, pipeline, background, depth=False,
+               use_trained_exp=False):
     render_path = os.path.join(model_path, name, "ours_{}".format(iteration), "renders")
     gts_path = os.path.join(model_path, name, "ours_{}".format(iteration), "gt")
     depth_path = os.path.join(model_path, name, "ours_{}".format(iteration), "depth")
@@ -52,7 +56,9 @@ def render_set(model_path, name, iteration, views, gaussians, pipeline, backgrou
     if depth:
         os.makedirs(depth_path, exist_ok=True)
     for idx, view in enumerate(views):
-        pkg = render(view, gaussians, pipeline, background, **({"return_depth": True} if depth else {}))
+        with_exp = use_trained_exp and view.image_name in (gaussians.pretrained_exposures or {})
+        pkg = render(view, gaussians, pipeline, background, **({"return_depth": True} if depth else {}),
+                     **({"use_trained_exp": True} if with_exp else {}))
         rendering = pkg["render"]
         save_png(rendering, os.path.join(render_path, "{0:05d}".format(idx) + ".png"))
         save_png(view.original_image[0:3, :, :].to(rendering.device), os.path.join(gts_path, "{0:05d}".format(idx) + ".png"))
@@ -63,18 +69,20 @@ def render_set(model_path, name, iteration, views, gaussians, pipeline, backgrou
             json.dump(scales, f)
 
 
-def render_sets(dataset, iteration, pipeline, skip_train=False, skip_test=False, depth=False):
+def render_sets(dataset, iteration, pipeline, skip_train=False, skip_test=False, depth=False, use_trained_exp=False):
     with torch.no_grad():
         gaussians = GaussianModel(dataset.sh_degree)
         scene = Scene(dataset, gaussians, load_iteration=iteration, shuffle=False)
         bg_color = [1, 1, 1] if dataset.white_background else [0, 0, 0]
         background = torch.tensor(bg_color, dtype=torch.float32, device="cuda")
+        if use_trained_exp and gaussians.pretrained_exposures is None:
+            raise FileNotFoundError("--use_trained_exp: the iteration's point-cloud directory has no exposure.json")
         if not skip_train:
             render_set(dataset.model_path, "train", scene.loaded_iter, scene.getTrainCameras(), gaussians, pipeline,
-                       background, depth)
+                       background, depth, use_trained_exp)
         if not skip_test:
             render_set(dataset.model_path, "test", scene.loaded_iter, scene.getTestCameras(), gaussians, pipeline,
-                       background, depth)
+                       background, depth, use_trained_exp)
     return scene
 
 
@@ -90,6 +98,7 @@ def main(argv=None):
     ap.add_argument("--skip_train", action="store_true")
     ap.add_argument("--skip_test", action="store_true")
     ap.add_argument("--depth", action="store_true", help="also write depth / alpha of every view as a 16-bit PNG")
+    ap.add_argument("--use_trained_exp", action="store_true", help="apply the saved per-image exposures")
     args = ap.parse_args(argv)
     fields = {}
     cfg = os.path.join(args.model_path, "cfg_args.json")
@@ -103,7 +112,8 @@ def main(argv=None):
         ap.error("no cfg_args.json in the model directory: give the dataset with -s")
     dataset = ModelParams(model_path=args.model_path, **fields)
     print("Rendering " + args.model_path)
-    render_sets(dataset, args.iteration, PipelineParams(), args.skip_train, args.skip_test, args.depth)
+    render_sets(dataset, args.iteration, PipelineParams(), args.skip_train, args.skip_test, args.depth,
+                args.use_trained_exp)
 
 
 if __name__ == "__main__":

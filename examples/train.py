@@ -6,6 +6,8 @@ SH degree steps, densification, opacity resets, the optional opacity sparsity te
     python examples/train.py -s <COLMAP or Blender directory> -m <output directory> [-r 1|2|4|8|width] [--eval]
                              [--white_background] [--images DIR] [--data_device cuda|cpu] [--save_iterations N ...]
                              [--refine_poses [--pose_lr LR]]
+                             [--train_exposure [--exposure_lr_init LR] [--exposure_lr_final LR]
+                              [--exposure_lr_delay_steps N] [--exposure_lr_delay_mult M]]
 
 ``--optimizer_type sparse_adam`` (both forms) steps only the Gaussians each frame saw (``optim.SparseGaussianAdam``).
 
@@ -13,7 +15,9 @@ With ``-s`` the example trains on a dataset through ``Scene`` (``scene.py``) and
 ``<output>/point_cloud/iteration_N/point_cloud.ply``, which ``examples/render.py -m <output>`` renders.
 ``--refine_poses`` (off by default) wraps every training camera in a ``PoseCamera`` and refines the poses with the model
 (Adam at ``--pose_lr`` on the six pose parameters of each camera); the refined poses are written to
-``<output>/refined_poses.json`` at the end.  Without ``-s``:
+``<output>/refined_poses.json`` at the end.  ``--train_exposure`` (off by default; upstream 3DGS's option) gives every
+training image a learnable 3x4 colour affine, trains it with the model and saves ``exposure.json`` next to each point
+cloud; ``examples/render.py --use_trained_exp`` renders with it.  Without ``-s``:
 
 The scene: a ground-truth cloud rendered from orbit views gives the images; the model starts, as the reference's does
 from a COLMAP cloud, from a jittered subsample of the ground truth's centres with their base colours.
@@ -114,13 +118,17 @@ def train_scene(args, dev):
                           resolution=args.resolution, white_background=args.white_background,
                           data_device=args.data_device, eval=args.eval)
     n = args.iterations
-    over = dict(opacitysparse=args.opacitysparse, optimizer_type=args.optimizer_type)
+    over = dict(opacitysparse=args.opacitysparse, optimizer_type=args.optimizer_type,
+                exposure_lr_init=args.exposure_lr_init, exposure_lr_final=args.exposure_lr_final,
+                exposure_lr_delay_steps=args.exposure_lr_delay_steps, exposure_lr_delay_mult=args.exposure_lr_delay_mult)
     opt = example_opt(n, **over) if n < 3000 else OptimizationParams(iterations=n, **over)
     model = GaussianModel(dataset.sh_degree)
     scene = Scene(dataset, model)
     with open(os.path.join(args.model_path, "cfg_args.json"), "w") as f:         # what examples/render.py -m needs
         json.dump({k: getattr(dataset, k) for k in ("source_path", "images", "resolution", "white_background", "eval",
                                                     "sh_degree")}, f)
+    if args.train_exposure:
+        model.setup_exposures([c.image_name for c in scene.getTrainCameras()])
     model.training_setup(opt)
     first_iter = load_checkpoint(model, args.start_checkpoint, opt) if args.start_checkpoint else 0
     bg = torch.tensor([1.0, 1.0, 1.0] if dataset.white_background else [0.0, 0.0, 0.0], device=dev)
@@ -135,7 +143,8 @@ def train_scene(args, dev):
             stack = train_cameras.copy()
         cam = stack.pop(random.randint(0, len(stack) - 1))
         loss = training_iteration(model, cam, opt, pipe, bg, iteration, dataset=dataset,
-                                  cameras_extent=scene.cameras_extent, pose_optimizer=pose_optimizer)
+                                  cameras_extent=scene.cameras_extent, pose_optimizer=pose_optimizer,
+                                  train_exposure=args.train_exposure)
         if iteration % 10 == 0:
             print(f"iteration {iteration}: loss {float(loss):.5f}  points {model._xyz.shape[0]}")
         if iteration in args.save_iterations or iteration == n:
@@ -167,6 +176,12 @@ def main(argv=None):
                     help="sparse_adam: step only the Gaussians each frame saw (optim.SparseGaussianAdam)")
     ap.add_argument("--refine_poses", action="store_true", help="with -s: refine the training cameras' poses too")
     ap.add_argument("--pose_lr", type=float, default=1e-4)
+    ap.add_argument("--train_exposure", action="store_true",
+                    help="with -s: learn a 3x4 colour affine per training image (saved as exposure.json)")
+    ap.add_argument("--exposure_lr_init", type=float, default=OptimizationParams.exposure_lr_init)
+    ap.add_argument("--exposure_lr_final", type=float, default=OptimizationParams.exposure_lr_final)
+    ap.add_argument("--exposure_lr_delay_steps", type=int, default=OptimizationParams.exposure_lr_delay_steps)
+    ap.add_argument("--exposure_lr_delay_mult", type=float, default=OptimizationParams.exposure_lr_delay_mult)
     ap.add_argument("--out", default=os.path.dirname(os.path.abspath(__file__)))
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")

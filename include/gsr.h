@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 22
+#define GSR_ABI_VERSION 23
 
 enum {
   GSR_OK = 0,
@@ -627,6 +627,24 @@ int gsr_image_resize_u8(const uint8_t* src, int32_t C, int32_t in_h, int32_t in_
                         const int32_t* h_bounds, const int32_t* h_taps, int32_t h_ksize, const int32_t* v_bounds,
                         const int32_t* v_taps, int32_t v_ksize, uint8_t* tmp, uint8_t* dst, void* stream);
 int gsr_image_to_float_chw(const uint8_t* src, int32_t C, int32_t H, int32_t W, float* dst, void* stream);
+
+/* Per-image exposure compensation, ABI v23 (csrc/exposure.hip): upstream 3DGS's learnable 3x4 colour affine on the
+ * rendered image.  x, y, g, dx: device fp32 [3,H,W] in planes; A, dA: device fp32 [3,4] row-major, read from device
+ * memory.  With k the input channel, c the output channel and p the pixel,
+ *     y[c,p]  = x[0,p]*A[0,c] + x[1,p]*A[1,c] + x[2,p]*A[2,c] + A[c,3]
+ *     dx[k,p] = A[k,0]*g[0,p] + A[k,1]*g[1,p] + A[k,2]*g[2,p]                    (g = dL/dy)
+ *     dA[k,c] = sum_p x[k,p]*g[c,p]  (k, c in 0..2)        dA[c,3] = sum_p g[c,p]
+ * (upstream's matmul(img.permute(1,2,0), A[:3,:3]).permute(2,0,1) + A[:3,3,None,None]); no clamp.  y and dx are summed
+ * left to right as written, every operation rounded to float32 on its own: with A = eye(3,4) and finite inputs y == x
+ * and dx == g bit for bit (a -0 comes out as +0).  dA: products and sums in double, one 12-double slot per block in
+ * `workspace` (gsr_exposure_workspace_bytes(H, W) bytes, 8-byte aligned), the slots added by one block in a fixed order,
+ * one rounding to float32; no atomics, the same bits from run to run.
+ * dx may be NULL (the image needs no gradient; A may then be NULL) and dA may be NULL (the exposure needs none; x and
+ * workspace may then be NULL).  Nothing here allocates, synchronises or reads back. */
+size_t gsr_exposure_workspace_bytes(int32_t H, int32_t W);
+int gsr_exposure_apply_fwd(const float* x, const float* A, int32_t H, int32_t W, float* y, void* stream);
+int gsr_exposure_apply_bwd(const float* x, const float* A, const float* g, int32_t H, int32_t W, float* dx, float* dA,
+                           void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

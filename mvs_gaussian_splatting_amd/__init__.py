@@ -8,12 +8,13 @@ from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, rast
 from .renderer import render  # noqa: F401
 from .losses import l1_loss, l1_dssim_loss, opacity_sparsity_loss, add_densification_stats  # noqa: F401
 from .optim import Adam  # noqa: F401
+from .exposure import apply_exposure, save_exposures, load_exposures  # noqa: F401
 from .model import GaussianModel  # noqa: F401
 from .metrics import psnr, ssim, image_metrics, to_uint8_hwc, EvalAccumulator, evaluate_views  # noqa: F401
 from .image_ingest import load_image, load_image_host  # noqa: F401
 from .scene import Scene, Camera, MiniCam, PoseCamera, ModelParams  # noqa: F401
 
 __all__ = ["Scene", "Camera", "MiniCam", "PoseCamera", "ModelParams", "load_image", "load_image_host",
-           "GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "render", "l1_loss", "l1_dssim_loss",
+           "GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "render", "l1_loss", "apply_exposure", "save_exposures", "load_exposures", "l1_dssim_loss",
            "opacity_sparsity_loss", "add_densification_stats", "Adam", "GaussianModel", "psnr", "ssim", "image_metrics", "to_uint8_hwc", "EvalAccumulator",
            "evaluate_views"]

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # instead of copying it over the in-tree library
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")
 
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 
 class GsrParams(C.Structure):
@@ -214,6 +214,10 @@ SYMBOLS = {
     "gsr_image_resize_u8": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p, C.c_int32] * 2 +
                             [C.c_void_p] * 3),
     "gsr_image_to_float_chw": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    # per-image exposure compensation: the 3x4 colour affine on the rendered image (csrc/exposure.hip; exposure.py)
+    "gsr_exposure_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "gsr_exposure_apply_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "gsr_exposure_apply_bwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 2 + [C.c_void_p] * 4),
 }
 
 _lib = None

@@ -1200,4 +1200,28 @@ int gsr_image_to_float_chw(const uint8_t* src, int32_t C, int32_t H, int32_t W, 
   return check(nullptr, s, "image_to_float_chw");
 }
 
+size_t gsr_exposure_workspace_bytes(int32_t H, int32_t W) {
+  return image_shape_ok(H, W) ? exposure_workspace_bytes((size_t)H * (size_t)W) : 0;
+}
+int gsr_exposure_apply_fwd(const float* x, const float* A, int32_t H, int32_t W, float* y, void* stream) {
+  if (!x || !A || !y) return fail(GSR_E_BADARG, "NULL argument");
+  if (!image_shape_ok(H, W)) return fail(GSR_E_BADARG, "bad image shape");
+  if ((((uintptr_t)x | (uintptr_t)A | (uintptr_t)y) & 3u) != 0) return fail(GSR_E_ALIGN, "arrays must be 4-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_exposure_apply_fwd(x, A, (size_t)H * (size_t)W, y, s);
+  return check(nullptr, s, "exposure_apply_fwd");
+}
+int gsr_exposure_apply_bwd(const float* x, const float* A, const float* g, int32_t H, int32_t W, float* dx, float* dA,
+                           void* workspace, void* stream) {
+  if (!g || (dx && !A) || (dA && (!x || !workspace))) return fail(GSR_E_BADARG, "NULL argument");
+  if (!image_shape_ok(H, W)) return fail(GSR_E_BADARG, "bad image shape");
+  if ((((uintptr_t)x | (uintptr_t)A | (uintptr_t)g | (uintptr_t)dx | (uintptr_t)dA) & 3u) != 0)
+    return fail(GSR_E_ALIGN, "arrays must be 4-byte aligned");
+  if (dA && ((uintptr_t)workspace & 7u) != 0) return fail(GSR_E_ALIGN, "the workspace must be 8-byte aligned");
+  if (!dx && !dA) return 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_exposure_apply_bwd(x, A, g, (size_t)H * (size_t)W, dx, dA, workspace, s);
+  return check(nullptr, s, "exposure_apply_bwd");
+}
+
 }  // extern "C"

@@ -189,6 +189,15 @@ void launch_opacity_sparsity_bwd(const float* raw, size_t P, float thr, const fl
                                  float* grad_raw, hipStream_t s);
 void launch_reset_opacity(float* raw, size_t P, float cap, float* exp_avg, float* exp_avg_sq, hipStream_t s);
 
+// exposure.hip: the per-image 3x4 colour affine on a [3,pixels] image and its gradients.  dx / dA may be nullptr; with
+// dA the backward leaves 12 double sums per block in `workspace` (exposure_workspace_bytes(pixels): at most
+// EXPOSURE_MAX_BLOCKS slots) and a one-block kernel behind it adds them in a fixed order
+constexpr int EXPOSURE_MAX_BLOCKS = 480;      // just under two 256-lane blocks per CU; 30 slots per finish stripe
+size_t exposure_workspace_bytes(size_t pixels);
+void launch_exposure_apply_fwd(const float* x, const float* A, size_t pixels, float* y, hipStream_t s);
+void launch_exposure_apply_bwd(const float* x, const float* A, const float* g, size_t pixels, float* dx, float* dA,
+                               void* workspace, hipStream_t s);
+
 // image.hip: load-time ingest of uint8 HWC images (one resize pass per call; bounds / taps: include/gsr.h)
 void launch_image_composite_u8(const uint8_t* rgba, size_t pixels, const double bg[3], uint8_t* rgb, hipStream_t s);
 void launch_image_resize_pass(bool vertical, int C, const uint8_t* in, int in_len, int out_len, int other,

@@ -102,6 +102,11 @@ class GaussianModel:
         if self.learn_split_scale:
             self._split_scale = torch.empty(0)
         self._optimizer_cls = None                                   # None: the class opt.optimizer_type names
+        # per-image exposure compensation (upstream 3DGS; setup_exposures): absent until asked for
+        self._exposure = None
+        self.exposure_mapping = {}
+        self.pretrained_exposures = None
+        self.exposure_optimizer = None
         # :34-42; render's raw-parameter path recognises the model by these three
         self.scaling_activation = torch.exp
         self.scaling_inverse_activation = torch.log
@@ -240,6 +245,41 @@ class GaussianModel:
         self.max_radii2D = torch.zeros((N,), dtype=torch.float32, device=dev)         # :238
         return self
 
+    # ---- per-image exposures (upstream 3DGS's gaussian_model.py; exposure.py) -----------------------------------------
+    def setup_exposures(self, image_names, device=None):
+        """One learnable 3x4 colour affine per training image, at the identity: ``_exposure`` ``[N,3,4]``,
+        ``exposure_mapping`` name -> row, ``pretrained_exposures = None``.  Call it before ``training_setup``, which
+        then builds ``exposure_optimizer``.  device: default where the model lives, else the current ROCm device (a
+        CPU device is accepted: the tensor is host data until ``apply_exposure`` reads it)."""
+        names = list(image_names)
+        if not names:
+            raise ValueError("setup_exposures needs at least one image name")
+        if len(set(names)) != len(names):
+            raise ValueError("setup_exposures needs distinct image names")
+        if device is None:
+            device = self._xyz.device if self._xyz.is_cuda else "cuda"
+        eye = torch.eye(3, 4, dtype=torch.float32, device=device)
+        self._exposure = nn.Parameter(eye[None].repeat(len(names), 1, 1).contiguous().requires_grad_(True))
+        self.exposure_mapping = {name: i for i, name in enumerate(names)}
+        self.pretrained_exposures = None
+        self.exposure_optimizer = None
+        return self
+
+    @property
+    def has_exposures(self) -> bool:
+        return self._exposure is not None
+
+    def get_exposure_from_name(self, image_name):
+        """The ``[3,4]`` exposure of one image: a view of its row of ``_exposure`` (the gradient lands there), or the
+        loaded tensor when ``pretrained_exposures`` is set.  ``KeyError`` for a name that has none."""
+        table = self.exposure_mapping if self.pretrained_exposures is None else self.pretrained_exposures
+        if image_name not in table:
+            raise KeyError(f"no exposure for image {image_name!r}" +
+                           ("" if table else " (setup_exposures has not been called and none were loaded)"))
+        if self.pretrained_exposures is not None:
+            return self.pretrained_exposures[image_name]
+        return self._exposure[self.exposure_mapping[image_name]]
+
     # ---- optimizer :240-277 (optim.py) ------------------------------------------------------------------------------
     def training_setup(self, training_args, optimizer_cls=None):
         """optimizer_cls: None takes the class ``training_args.optimizer_type`` names (``optim.Adam`` by default)."""
@@ -283,16 +323,30 @@ class GaussianModel:
                self._opacity, self.max_radii2D, self.xyz_gradient_accum, self.denom, self.optimizer.state_dict(),
                self.spatial_lr_scale)
         fork = {a: getattr(self, a) for a in self._fork_attrs().values()}
-        return out + (fork,) if fork else out
+        out = out + (fork,) if fork else out
+        if self.has_exposures:                        # last, and told from the fork's dict by its "exposure_mapping" key
+            out = out + ({"exposure": self._exposure, "exposure_mapping": dict(self.exposure_mapping),
+                          "exposure_optimizer": self.exposure_optimizer.state_dict()},)
+        return out
 
     def restore(self, model_args, training_args, optimizer_cls=None):
-        """``:133-149``; accepts the 12-tuple or the 13-tuple of ``capture``.  ``training_setup`` runs first, with
+        """``:133-149``; accepts every form ``capture`` returns: the 12-tuple, with the fork's dict, and either with the
+        exposures' dict (``ValueError`` when the checkpoint has exposures and this model none, or the reverse: call
+        ``setup_exposures`` first, or not at all).  ``training_setup`` runs first, with
         ``optimizer_cls`` (default: the class ``training_setup`` was last given, else the one
         ``training_args.optimizer_type`` names: ``optim.Adam`` unless it says ``"sparse_adam"``), then the saved
         state is loaded into it: state dicts move freely between ``torch.optim.Adam`` and ``optim.Adam``."""
         model_args = tuple(model_args)
+        exposures = None
+        if len(model_args) in (13, 14) and isinstance(model_args[-1], dict) and "exposure_mapping" in model_args[-1]:
+            exposures, model_args = model_args[-1], model_args[:-1]
         if len(model_args) not in (12, 13):
-            raise ValueError(f"restore expects the 12- or 13-element tuple of capture(), got {len(model_args)} elements")
+            raise ValueError(f"restore expects the 12- or 13-element tuple of capture(), with the exposures' dict behind "
+                             f"it for a model that has them, got {len(model_args) + (exposures is not None)} elements")
+        if (exposures is not None) != self.has_exposures:
+            raise ValueError("the checkpoint holds exposures and this model has none (call setup_exposures before restore)"
+                             if exposures is not None else
+                             "this model has exposures and the checkpoint holds none")
         fork = model_args[12] if len(model_args) == 13 else {}
         want = set(self._fork_attrs().values())
         if not isinstance(fork, dict) or set(fork) != want:
@@ -304,10 +358,15 @@ class GaussianModel:
             setattr(self, a, t)
         if self.grow_dir:
             self.dirs = self.dirs.to(self._xyz.device)
+        if exposures is not None:
+            self._exposure = exposures["exposure"]
+            self.exposure_mapping = dict(exposures["exposure_mapping"])
         self.training_setup(training_args, optimizer_cls or self._optimizer_cls)
         self.xyz_gradient_accum = xyz_gradient_accum
         self.denom = denom
         self.optimizer.load_state_dict(opt_dict)
+        if exposures is not None:
+            self.exposure_optimizer.load_state_dict(exposures["exposure_optimizer"])
 
     # ---- PLY :293-358 (ply_io.py) -----------------------------------------------------------------------------------
     def save_ply(self, path):

@@ -263,10 +263,15 @@ def optimizer_class(opt):
     return OPTIMIZER_TYPES[kind]
 
 
+EXPOSURE_LR_INIT, EXPOSURE_LR_FINAL = 0.01, 0.001      # upstream's defaults, for an `opt` without the fields
+
+
 def training_setup(model, opt, optimizer_cls=None):
     """``GaussianModel.training_setup(training_args)`` (``scene/gaussian_model.py:240-268``) with this module's
     ``Adam``: sets ``percent_dense``, zeroed ``xyz_gradient_accum`` / ``denom`` ``[P, 1]`` on the model's device,
-    ``optimizer`` (``lr=0.0, eps=1e-15``) and ``xyz_scheduler_args``.  optimizer_cls: None takes the class
+    ``optimizer`` (``lr=0.0, eps=1e-15``) and ``xyz_scheduler_args``; for a model with exposures
+    (``GaussianModel.setup_exposures``) also ``exposure_optimizer`` (``Adam([_exposure], lr=0.0, eps=1e-8)``, always
+    dense) and ``exposure_scheduler_args`` over ``opt.iterations`` steps, else ``exposure_optimizer = None``.  optimizer_cls: None takes the class
     ``opt.optimizer_type`` names (``optimizer_class``).  Returns the optimizer."""
     if optimizer_cls is None:
         optimizer_cls = optimizer_class(opt)
@@ -279,12 +284,24 @@ def training_setup(model, opt, optimizer_cls=None):
                                              lr_final=opt.position_lr_final * model.spatial_lr_scale,
                                              lr_delay_mult=opt.position_lr_delay_mult,
                                              max_steps=opt.position_lr_max_steps)
+    # per-image exposures (upstream 3DGS): an optimizer of their own, only for a model that had setup_exposures()
+    model.exposure_optimizer = None
+    if getattr(model, "_exposure", None) is not None:
+        model.exposure_optimizer = Adam([model._exposure], lr=0.0, eps=1e-8)
+        model.exposure_scheduler_args = expon_lr_func(getattr(opt, "exposure_lr_init", EXPOSURE_LR_INIT),
+                                                      getattr(opt, "exposure_lr_final", EXPOSURE_LR_FINAL),
+                                                      lr_delay_steps=getattr(opt, "exposure_lr_delay_steps", 0),
+                                                      lr_delay_mult=getattr(opt, "exposure_lr_delay_mult", 0.0),
+                                                      max_steps=opt.iterations)
     return model.optimizer
 
 
 def update_learning_rate(model, iteration):
     """``GaussianModel.update_learning_rate`` (``:271-277``): the ``xyz`` group's lr from ``xyz_scheduler_args``;
-    returns it (None without an ``xyz`` group)."""
+    returns it (None without an ``xyz`` group).  The exposure optimizer's lr follows ``exposure_scheduler_args``."""
+    if getattr(model, "exposure_optimizer", None) is not None:
+        for group in model.exposure_optimizer.param_groups:
+            group["lr"] = model.exposure_scheduler_args(iteration)
     for group in model.optimizer.param_groups:
         if group["name"] == "xyz":
             lr = model.xyz_scheduler_args(iteration)

@@ -16,6 +16,7 @@ import math
 import torch
 
 from . import grow
+from .exposure import apply_exposure
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, _grown_key, rasterize_gaussians_fused
 from .sh import eval_sh
 
@@ -90,7 +91,8 @@ def _settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier):
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier: float = 1.0,
            override_color=None, grow_dir=False, densify_grad_threshold=0, iteration=None, opt=None,
-           continous_dir=False, grow_distance=False, modelcg=None, cameras_extent=None, return_depth=False):
+           continous_dir=False, grow_distance=False, modelcg=None, cameras_extent=None, return_depth=False,
+           use_trained_exp=False):
     """Render the scene; ``bg_color`` must be on the GPU.  Returns the reference's result dict
     (``gaussian_renderer/__init__.py:309-313``).  The keyword arguments after ``override_color`` are the reference's
     (``:19``) and drive the grow / learned-split branch (module docstring); the frame of a closed branch is unchanged.
@@ -105,7 +107,22 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier:
     differentiable; ``z`` is the view-space depth, there is no background term.  On such a frame the in-backward
     densification statistics are not taken (``viewspace_points.grad`` is the sum of the colour node's and the maps'
     node's gradients, which only exists after the backward): ``add_densification_stats`` reads it, as on grown frames.
-    Not available on a frame of the open grow / learned-split branch."""
+    Not available on a frame of the open grow / learned-split branch.
+
+    ``use_trained_exp=True`` (upstream 3DGS's name): ``"render"`` is the rasterizer's image after the camera's 3x4
+    exposure, ``apply_exposure(image, pc.get_exposure_from_name(viewpoint_camera.image_name))`` (``exposure.py``), on
+    every path; the maps of ``return_depth`` are untouched.  False leaves the frame exactly as it was."""
+    pkg = _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, grow_dir,
+                  densify_grad_threshold, iteration, opt, continous_dir, grow_distance, modelcg, cameras_extent,
+                  return_depth)
+    if use_trained_exp:
+        pkg["render"] = apply_exposure(pkg["render"], pc.get_exposure_from_name(viewpoint_camera.image_name))
+    return pkg
+
+
+def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, grow_dir, densify_grad_threshold,
+            iteration, opt, continous_dir, grow_distance, modelcg, cameras_extent, return_depth):
+    """The frame of ``render`` as the rasterizer leaves it."""
     which = grow.branch(iteration, opt, grow_dir, continous_dir, modelcg)
     if which is not None and return_depth:
         raise ValueError("return_depth=True is not available on a frame of the open grow / learned-split branch "

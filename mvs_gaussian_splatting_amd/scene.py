@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import image_ingest
+from .exposure import load_exposures, save_exposures
 from .dataset_readers import decode_image, fov2focal, sceneLoadTypeCallbacks
 from .synthetic import get_projection_matrix, get_world2view2
 
@@ -346,6 +347,11 @@ class Scene:
         if self.loaded_iter:
             self.gaussians.load_ply(os.path.join(self.model_path, "point_cloud", "iteration_" + str(self.loaded_iter),
                                                  "point_cloud.ply"))
+            # upstream 3DGS: the exposures trained with the model, if it was trained with any
+            exposure_file = os.path.join(self.model_path, "point_cloud", "iteration_" + str(self.loaded_iter),
+                                         "exposure.json")
+            if os.path.exists(exposure_file):
+                self.gaussians.pretrained_exposures = load_exposures(exposure_file, device=self.gaussians._xyz.device)
         else:
             self.gaussians.create_from_pcd(scene_info.point_cloud, self.cameras_extent)
 
@@ -359,6 +365,9 @@ class Scene:
     def save(self, iteration):
         point_cloud_path = os.path.join(self.model_path, "point_cloud/iteration_{}".format(iteration))
         self.gaussians.save_ply(os.path.join(point_cloud_path, "point_cloud.ply"))
+        if getattr(self.gaussians, "_exposure", None) is not None:
+            save_exposures(os.path.join(point_cloud_path, "exposure.json"), self.gaussians.exposure_mapping,
+                           self.gaussians._exposure)
 
     def getTrainCameras(self, scale=1.0):
         return self.train_cameras[scale]

@@ -48,6 +48,11 @@ class OptimizationParams:
     # this build's: "default" (optim.Adam, every row every step) or "sparse_adam" (optim.SparseGaussianAdam: the rows the
     # frame saw, as upstream 3DGS names its option)
     optimizer_type = "default"
+    # upstream 3DGS's per-image exposure compensation (training_iteration(train_exposure=True)): its Adam's schedule
+    exposure_lr_init = 0.01
+    exposure_lr_final = 0.001
+    exposure_lr_delay_steps = 0
+    exposure_lr_delay_mult = 0.0
 
     def __init__(self, **overrides):
         for k, v in overrides.items():
@@ -69,7 +74,8 @@ def schedule(opt, iteration: int, white_background: bool = False) -> dict:
 
 
 def training_iteration(model, camera, opt, pipe, background, iteration, *, dataset=None, cameras_extent,
-                       first_reset=None, gt_image=None, densify_kwargs=None, pose_optimizer=None, depth_loss=None):
+                       first_reset=None, gt_image=None, densify_kwargs=None, pose_optimizer=None, depth_loss=None,
+                       train_exposure=False):
     """``train.py:72-142`` for one camera, in the reference's order: learning rate, SH degree, background, ``render``
     with the fork's keyword arguments, L1 + D-SSIM against ``camera.original_image``, the opacity sparsity term
     (``opt.opacitysparse``), ``backward``; then, without gradients, the densification statistics, ``densify_and_prune``,
@@ -87,7 +93,12 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
     depth_loss: None, or ``(target, weight)`` with ``target [1,H,W]`` an inverse-depth map (from multi-view stereo, say):
     the frame is rendered with ``return_depth=True`` and ``weight * mean|invdepth - target|`` joins the loss (plain torch
     ops on the map; the map and its gradients are the HIP path's).  Not on a frame of the open grow / learned-split
-    branch."""
+    branch.
+    train_exposure: the frame is rendered with ``use_trained_exp=True`` -- the loss sees the image after the camera's
+    3x4 exposure (``model.setup_exposures`` before ``training_setup``) -- and ``model.exposure_optimizer`` is stepped and
+    zeroed where the model's optimizer is."""
+    if train_exposure and getattr(model, "exposure_optimizer", None) is None:
+        raise ValueError("train_exposure=True needs model.setup_exposures(image names) before training_setup")
     flag = lambda name: bool(getattr(dataset, name, False))      # noqa: E731
     if first_reset is None:
         first_reset = flag("white_background")
@@ -99,7 +110,8 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
     pkg = render(camera, model, pipe, bg, grow_dir=flag("grow_dir"), densify_grad_threshold=opt.densify_grad_threshold,
                  iteration=iteration, opt=opt, continous_dir=flag("continous_dir"), grow_distance=flag("grow_distance"),
                  modelcg=dataset, cameras_extent=cameras_extent,                                # :91
-                 **({} if depth_loss is None else {"return_depth": True}))
+                 **({} if depth_loss is None else {"return_depth": True}),
+                 **({"use_trained_exp": True} if train_exposure else {}))
     gt = camera.original_image if gt_image is None else gt_image
     loss = l1_dssim_loss(pkg["render"], gt.to(pkg["render"].device), opt.lambda_dssim)          # :99-101
     if opt.opacitysparse > 0:                                                                   # :102-106
@@ -128,6 +140,9 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
             else:
                 model.optimizer.step()
             model.optimizer.zero_grad(set_to_none=True)
+            if train_exposure:
+                model.exposure_optimizer.step()
+                model.exposure_optimizer.zero_grad(set_to_none=True)
             if pose_optimizer is not None:
                 pose_optimizer.step()
                 pose_optimizer.zero_grad(set_to_none=True)
