@@ -8,6 +8,7 @@ SH degree steps, densification, opacity resets, the optional opacity sparsity te
                              [--refine_poses [--pose_lr LR]]
                              [--train_exposure [--exposure_lr_init LR] [--exposure_lr_final LR]
                               [--exposure_lr_delay_steps N] [--exposure_lr_delay_mult M]]
+                             [--prune_iterations N [N ...] --prune_keep_ratio R [--prune_kind sum|max|count|mean]]
 
 ``--optimizer_type sparse_adam`` (both forms) steps only the Gaussians each frame saw (``optim.SparseGaussianAdam``).
 
@@ -17,7 +18,10 @@ With ``-s`` the example trains on a dataset through ``Scene`` (``scene.py``) and
 (Adam at ``--pose_lr`` on the six pose parameters of each camera); the refined poses are written to
 ``<output>/refined_poses.json`` at the end.  ``--train_exposure`` (off by default; upstream 3DGS's option) gives every
 training image a learnable 3x4 colour affine, trains it with the model and saves ``exposure.json`` next to each point
-cloud; ``examples/render.py --use_trained_exp`` renders with it.  Without ``-s``:
+cloud; ``examples/render.py --use_trained_exp`` renders with it.  ``--prune_iterations`` (both forms; off by default):
+after each of those iterations the blending-weight statistics of every training camera are measured (``contribution.py``)
+and the ``--prune_keep_ratio`` share of the Gaussians with the highest ``--prune_kind`` score is kept
+(``examples/prune.py`` does the same to a saved scene).  Without ``-s``:
 
 The scene: a ground-truth cloud rendered from orbit views gives the images; the model starts, as the reference's does
 from a COLMAP cloud, from a jittered subsample of the ground truth's centres with their base colours.
@@ -33,7 +37,7 @@ import types
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from mvs_gaussian_splatting_amd import GaussianModel, render  # noqa: E402
+from mvs_gaussian_splatting_amd import GaussianModel, measure, prune_by_contribution, render  # noqa: E402
 from mvs_gaussian_splatting_amd.sh import SH2RGB  # noqa: E402
 from mvs_gaussian_splatting_amd.synthetic import PipelineParams, SyntheticGaussianModel, orbit_camera  # noqa: E402
 from mvs_gaussian_splatting_amd.trainer import (OptimizationParams, load_checkpoint, save_checkpoint,  # noqa: E402
@@ -90,10 +94,33 @@ def make_model(problem, opt, dataset=None, sh_degree=3, optimizer_cls=None, seed
     return model
 
 
-def train(model, problem, opt, first_iter=0, last_iter=None, dataset=None, pipe=None, seed=0, log=None, on_iteration=None):
+def prune_options(args):
+    """``{"iterations", "keep_ratio", "kind"}`` of the ``--prune_*`` arguments, or None when pruning is off."""
+    if not args.prune_iterations:
+        return None
+    if args.prune_keep_ratio is None:
+        raise SystemExit("--prune_iterations needs --prune_keep_ratio")
+    return {"iterations": set(args.prune_iterations), "keep_ratio": args.prune_keep_ratio, "kind": args.prune_kind}
+
+
+def prune_step(model, cameras, pipe, bg, iteration, prune, log=print):
+    """At the iterations of ``prune``: measure the contribution of every Gaussian over ``cameras`` and keep the best."""
+    if not prune or iteration not in prune["iterations"]:
+        return None
+    out = prune_by_contribution(model, measure(model, cameras, pipe, bg), kind=prune["kind"],
+                                keep_ratio=prune["keep_ratio"])
+    if log:
+        log(f"[ITER {iteration}] pruned by contribution ({prune['kind']}): {out['points'] + out['pruned']} -> "
+            f"{out['points']} points")
+    return out
+
+
+def train(model, problem, opt, first_iter=0, last_iter=None, dataset=None, pipe=None, seed=0, log=None, on_iteration=None,
+          prune=None):
     """Iterations ``first_iter + 1 .. last_iter`` (default ``opt.iterations``), as ``train.py:54`` counts them.  The
     device generator is seeded from the iteration number before each one, so that the draws of a densification are the
-    same in a resumed run as in an uninterrupted one.  Returns the losses as device tensors."""
+    same in a resumed run as in an uninterrupted one.  ``prune``: ``prune_options``.  Returns the losses as device
+    tensors."""
     cams, bg, _ = problem
     pipe = pipe or PipelineParams()
     losses = []
@@ -102,6 +129,7 @@ def train(model, problem, opt, first_iter=0, last_iter=None, dataset=None, pipe=
         cam = cams[(iteration * 3) % len(cams)]
         losses.append(training_iteration(model, cam, opt, pipe, bg, iteration, dataset=dataset,
                                          cameras_extent=CAMERAS_EXTENT))
+        prune_step(model, cams, pipe, bg, iteration, prune, log)
         if on_iteration:
             on_iteration(iteration, model)
         if log and iteration % 10 == 0:
@@ -133,6 +161,7 @@ def train_scene(args, dev):
     first_iter = load_checkpoint(model, args.start_checkpoint, opt) if args.start_checkpoint else 0
     bg = torch.tensor([1.0, 1.0, 1.0] if dataset.white_background else [0.0, 0.0, 0.0], device=dev)
     pipe, stack, loss = PipelineParams(), None, None
+    prune = prune_options(args)
     train_cameras, pose_optimizer = scene.getTrainCameras(), None
     if args.refine_poses:
         from mvs_gaussian_splatting_amd import PoseCamera
@@ -145,6 +174,7 @@ def train_scene(args, dev):
         loss = training_iteration(model, cam, opt, pipe, bg, iteration, dataset=dataset,
                                   cameras_extent=scene.cameras_extent, pose_optimizer=pose_optimizer,
                                   train_exposure=args.train_exposure)
+        prune_step(model, train_cameras, pipe, bg, iteration, prune)
         if iteration % 10 == 0:
             print(f"iteration {iteration}: loss {float(loss):.5f}  points {model._xyz.shape[0]}")
         if iteration in args.save_iterations or iteration == n:
@@ -182,6 +212,10 @@ def main(argv=None):
     ap.add_argument("--exposure_lr_final", type=float, default=OptimizationParams.exposure_lr_final)
     ap.add_argument("--exposure_lr_delay_steps", type=int, default=OptimizationParams.exposure_lr_delay_steps)
     ap.add_argument("--exposure_lr_delay_mult", type=float, default=OptimizationParams.exposure_lr_delay_mult)
+    ap.add_argument("--prune_iterations", type=int, nargs="*", default=[],
+                    help="after these iterations: measure every training view and prune by contribution")
+    ap.add_argument("--prune_keep_ratio", type=float, default=None, help="share of the Gaussians a pruning keeps")
+    ap.add_argument("--prune_kind", choices=("sum", "max", "count", "mean"), default="sum")
     ap.add_argument("--out", default=os.path.dirname(os.path.abspath(__file__)))
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
@@ -206,7 +240,8 @@ def main(argv=None):
             save_checkpoint(m, iteration, path)
             print(f"[ITER {iteration}] saved checkpoint {path}")
 
-    losses = train(model, problem, opt, first_iter, dataset=dataset, log=print, on_iteration=on_iteration)
+    losses = train(model, problem, opt, first_iter, dataset=dataset, log=print, on_iteration=on_iteration,
+                   prune=prune_options(args))
     ply = os.path.join(args.out, "point_cloud.ply")
     model.save_ply(ply)
     if losses:

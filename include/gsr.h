@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 23
+#define GSR_ABI_VERSION 24
 
 enum {
   GSR_OK = 0,
@@ -249,6 +249,21 @@ int gsr_aux_maps_forward(const GsrAuxFrame* frame, float* maps, void* stream);
 size_t gsr_aux_maps_backward_bytes(int32_t P);
 int gsr_aux_maps_backward(const GsrParams* p, const GsrAuxFrame* frame, const float* dL_dmaps, void* acc_ws,
                           size_t acc_ws_bytes, const GsrAuxGrads* grads, void* stream);
+
+/* ---- per-Gaussian contribution statistics of a rendered frame, ABI v24 (csrc/contribution.hip) ----------------------
+ * For Gaussian g let p run over the pixels where the colour pass composited g (the rule above: the first n_contrib
+ * entries of the tile's list that pass alpha >= 1/255) and w = alpha T, the weight the maps above sum.  Three int64 per
+ * Gaussian, ADDED INTO the caller's buffer:
+ *     stats[g][0] += sum_p round-to-nearest(w * 2^30)     (w <= 0.99, so a term fits 30 bits)
+ *     stats[g][1] += number of such pixels
+ *     stats[g][2]  = max(stats[g][2], float32 bit pattern of max_p w)   (w > 0: integer order is float order; 0 = never)
+ * Integer adds and an integer max only: the result is the same bits from run to run and whatever the order of the
+ * views, so many views accumulate in one buffer on the device.  Range of column 0: 2^63 / 2^30 weight units, about 4000
+ * fully covered 1920x1080 frames for a single Gaussian.
+ * pixel_mask: NULL, or device uint8 [H,W]: pixels whose byte is 0 are left out of all three numbers.
+ * frame: the state of a forward with p->forward_only = 0 (the kernel reads the contributor counts); radii is not read.
+ * A frame with P == 0 or num_rendered == 0 returns success and launches nothing.  stats: device [P,3], 8-byte aligned. */
+int gsr_contribution_accumulate(const GsrAuxFrame* frame, const uint8_t* pixel_mask, int64_t* stats, void* stream);
 
 /* `_C.mark_visible(means3D, viewmatrix, projmatrix)` of the upstream module (unused by the reference): visible[i] = 1
  * when Gaussian i passes the near-plane test of the preprocess stage (view z > 0.2). */

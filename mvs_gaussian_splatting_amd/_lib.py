@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # instead of copying it over the in-tree library
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")
 
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 
 class GsrParams(C.Structure):
@@ -143,6 +143,8 @@ SYMBOLS = {
     "gsr_aux_maps_backward_bytes": (C.c_size_t, [C.c_int32]),
     "gsr_aux_maps_backward": (C.c_int, [C.POINTER(GsrParams), C.POINTER(GsrAuxFrame), C.c_void_p, C.c_void_p, C.c_size_t,
                                         C.POINTER(GsrAuxGrads), C.c_void_p]),
+    # per-Gaussian contribution statistics of a rendered frame, added into int64 [P,3] (csrc/contribution.hip)
+    "gsr_contribution_accumulate": (C.c_int, [C.POINTER(GsrAuxFrame), C.c_void_p, C.c_void_p, C.c_void_p]),
     "gsr_mark_visible": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gsr_sort_scratch_bytes": (C.c_size_t, [C.c_uint32]),
     "gsr_sort_pairs_u64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32,

@@ -638,6 +638,21 @@ int gsr_aux_maps_backward(const GsrParams* p, const GsrAuxFrame* f, const float*
   return check(p, s, "aux_geom_bwd");
 }
 
+// ---- per-Gaussian contribution statistics (csrc/contribution.hip) --------------------------------------------------
+int gsr_contribution_accumulate(const GsrAuxFrame* f, const uint8_t* pixel_mask, int64_t* stats, void* stream) {
+  if (int rc = validate_aux_frame(f)) return rc;
+  if (f->P == 0 || f->num_rendered == 0) return 0;      // nothing was binned: every list is empty
+  if (!stats) return fail(GSR_E_BADARG, "stats is NULL");
+  if (((uintptr_t)stats & 7u) != 0) return fail(GSR_E_ALIGN, "stats must be 8-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const ImageLayout I(f->width, f->height);
+  const GeomLayout L(f->P);
+  const SortedViews sv = sorted_views(f->bin_ws, f->num_rendered, f->num_visible, f->width, f->height, f->binning_mode);
+  launch_contribution(f->width, f->height, at<uint2>(f->img_ws, I.ranges), sv.point_list, at<GeomRec>(f->geom_ws, L.rec),
+                      at<uint32_t>(f->img_ws, I.n_contrib), at<uint32_t>(f->img_ws, I.tile_order), pixel_mask, stats, s);
+  return check(nullptr, s, "contribution");
+}
+
 int gsr_profile_create(void** handle) {
   if (!handle) return fail(GSR_E_BADARG, "handle is NULL");
   *handle = new Profile();

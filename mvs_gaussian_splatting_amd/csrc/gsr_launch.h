@@ -108,6 +108,12 @@ void launch_aux_maps_bwd(int W, int H, const uint2* ranges, const uint32_t* poin
                          const float* dL_dmaps, float* acc, hipStream_t s);
 void launch_aux_geom_bwd(const GsrParams& p, const int32_t* radii, const float* acc, const GsrAuxGrads& g, hipStream_t s);
 
+// contribution.hip: per-Gaussian blending-weight statistics of a rendered frame, added into stats [P,3] (int64: sum of
+// round(w 2^30), pixel count, float bits of the largest w) with integer atomics; pixel_mask: nullptr or [H,W] bytes
+void launch_contribution(int W, int H, const uint2* ranges, const uint32_t* point_list, const GeomRec* rec,
+                         const uint32_t* n_contrib, const uint32_t* tile_order, const uint8_t* pixel_mask, int64_t* stats,
+                         hipStream_t s);
+
 // loss.hip
 void launch_l1_dssim(const float* x, const float* gt, int C, int H, int W, float lambda, int dssim_mode, float* sums,
                      float* dL_dx, float* maps, hipStream_t s);

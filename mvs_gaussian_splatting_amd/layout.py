@@ -54,6 +54,47 @@ def morton_permutation(xyz: torch.Tensor) -> torch.Tensor:
     return torch.sort(code, stable=True).indices
 
 
+def _take_rows_(model, index: torch.Tensor, P: int) -> None:
+    """Row ``index`` (an int64 index or a bool mask over the P rows) of every per-Gaussian tensor of the model, in place:
+    the parameter tensors, the fork's learned tensors with one row per Gaussian, the Adam moments of ``model.optimizer``
+    (the surgery of the reference's ``_prune_optimizer``: same groups, same state keys) and the densification
+    statistics."""
+    attrs = dict(GROUP_ATTR)
+    for k, a in FORK_ATTR.items():
+        t = getattr(model, a, None)
+        if isinstance(t, torch.Tensor) and t.dim() >= 1 and t.shape[0] == P and P > 0:
+            attrs[k] = a
+    new = {k: getattr(model, a).detach()[index].contiguous() for k, a in attrs.items()}
+    optimizer = getattr(model, "optimizer", None)
+    owned = set()
+    if optimizer is not None:
+        for group in optimizer.param_groups:
+            name = group.get("name")
+            if name not in new:
+                continue
+            old = group["params"][0]
+            stored = optimizer.state.get(old, None)
+            group["params"][0] = nn.Parameter(new[name].requires_grad_(True))
+            if stored is not None:
+                for key in ("exp_avg", "exp_avg_sq"):
+                    if key in stored:
+                        stored[key] = stored[key][index].contiguous()
+                del optimizer.state[old]
+                optimizer.state[group["params"][0]] = stored
+            new[name] = group["params"][0]
+            owned.add(name)
+    for k, a in attrs.items():
+        t, old = new[k], getattr(model, a)
+        if k not in owned:
+            t = nn.Parameter(t, requires_grad=old.requires_grad) if isinstance(old, nn.Parameter) \
+                else t.requires_grad_(old.requires_grad)
+        setattr(model, a, t)
+    for a in STATS_ATTR:
+        t = getattr(model, a, None)
+        if isinstance(t, torch.Tensor) and t.dim() >= 1 and t.shape[0] == P:
+            setattr(model, a, t[index].contiguous())
+
+
 @torch.no_grad()
 def reorder_gaussians_(model, perm: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Permute every per-Gaussian tensor of a model in place: row i of the result is row ``perm[i]`` of the input
@@ -68,38 +109,20 @@ def reorder_gaussians_(model, perm: Optional[torch.Tensor] = None) -> torch.Tens
     perm = perm.to(device=xyz.device, dtype=torch.int64)
     if perm.shape != (P,) or (P and not torch.equal(torch.sort(perm).values, torch.arange(P, device=perm.device))):
         raise ValueError(f"perm must be a permutation of range({P})")
-    attrs = dict(GROUP_ATTR)
-    for k, a in FORK_ATTR.items():
-        t = getattr(model, a, None)
-        if isinstance(t, torch.Tensor) and t.dim() >= 1 and t.shape[0] == P and P > 0:
-            attrs[k] = a
-    new = {k: getattr(model, a).detach()[perm].contiguous() for k, a in attrs.items()}
-    optimizer = getattr(model, "optimizer", None)
-    owned = set()
-    if optimizer is not None:
-        for group in optimizer.param_groups:
-            name = group.get("name")
-            if name not in new:
-                continue
-            old = group["params"][0]
-            stored = optimizer.state.get(old, None)
-            group["params"][0] = nn.Parameter(new[name].requires_grad_(True))
-            if stored is not None:
-                for key in ("exp_avg", "exp_avg_sq"):
-                    if key in stored:
-                        stored[key] = stored[key][perm].contiguous()
-                del optimizer.state[old]
-                optimizer.state[group["params"][0]] = stored
-            new[name] = group["params"][0]
-            owned.add(name)
-    for k, a in attrs.items():
-        t, old = new[k], getattr(model, a)
-        if k not in owned:
-            t = nn.Parameter(t, requires_grad=old.requires_grad) if isinstance(old, nn.Parameter) \
-                else t.requires_grad_(old.requires_grad)
-        setattr(model, a, t)
-    for a in STATS_ATTR:
-        t = getattr(model, a, None)
-        if isinstance(t, torch.Tensor) and t.dim() >= 1 and t.shape[0] == P:
-            setattr(model, a, t[perm].contiguous())
+    _take_rows_(model, perm, P)
     return perm
+
+
+@torch.no_grad()
+def prune_points_(model, keep: torch.Tensor) -> int:
+    """Keep the Gaussians a bool ``[P]`` mask marks and drop the rest, in place and in order: the rows of everything
+    ``reorder_gaussians_`` moves (parameters, the fork's learned tensors, the Adam moments, the densification
+    statistics); the kept rows keep their bits.  Per-image exposures have no row per Gaussian and are untouched.  Plain
+    torch indexing -- a cold path -- so it also serves a model on the CPU.  Returns the number of points left."""
+    xyz = model._xyz
+    P = int(xyz.shape[0])
+    if not isinstance(keep, torch.Tensor) or keep.dtype != torch.bool or tuple(keep.shape) != (P,):
+        raise ValueError(f"keep must be a bool [P={P}] mask, got "
+                         f"{getattr(keep, 'dtype', type(keep).__name__)} {list(getattr(keep, 'shape', ()))}")
+    _take_rows_(model, keep.to(xyz.device), P)
+    return int(model._xyz.shape[0])

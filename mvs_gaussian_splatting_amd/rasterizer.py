@@ -31,6 +31,12 @@ Depth / alpha maps.  ``GaussianRasterizer(settings, aux_maps=True)`` returns ``(
 the depth (``sum w z``), inverse-depth (``sum w / z``) and accumulated-opacity (``sum w``) maps of the frame, from
 kernels of their own (``csrc/depth.hip``) behind a second autograd node (``_AuxMaps``) that reads the colour node's frame.
 Without ``aux_maps`` nothing of it runs.
+
+Contribution statistics.  ``GaussianRasterizer(settings, contribution=stats)`` (``contribution.ContributionStats``; any
+object with ``raw`` -- int64 ``[P,3]`` on the device -- and ``views``) adds the frame's per-Gaussian blending-weight
+statistics into ``stats.raw`` after the colour forward (``csrc/contribution.hip``) and counts the view;
+``contribution_mask`` (uint8 ``[H,W]``) leaves pixels out.  Nothing enters the autograd graph, and the call's results are
+what they are without it.  Without ``contribution`` nothing of it runs.
 """
 from __future__ import annotations
 
@@ -923,29 +929,82 @@ def _check_aux_request(cam, state_key=None, densify_stats=None) -> None:
         raise ValueError("aux_maps=True is not available on a frame with grown / split rows appended")
 
 
+def _check_contribution_request(stats, mask, means3D, settings, state_key=None) -> None:
+    """The refusals of a ``contribution=stats`` request, before anything is enqueued."""
+    if state_key is not None:
+        raise ValueError("contribution statistics are not available on a frame with grown / split rows appended")
+    raw = getattr(stats, "raw", None)
+    P = int(means3D.shape[0])
+    if not isinstance(raw, torch.Tensor) or raw.dtype != torch.int64 or raw.dim() != 2 or raw.shape[1] != 3 or \
+            not raw.is_contiguous():
+        raise ValueError("contribution must carry `raw`, a contiguous int64 [P,3] tensor (contribution.ContributionStats)")
+    if raw.shape[0] != P:
+        raise ValueError(f"contribution statistics have {int(raw.shape[0])} rows, the frame has P={P} Gaussians")
+    H, W = int(settings.image_height), int(settings.image_width)
+    if mask is not None and (not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or
+                             tuple(mask.shape) != (H, W)):
+        raise ValueError(f"contribution_mask must be a uint8 [H={H}, W={W}] tensor, got "
+                         f"{getattr(mask, 'dtype', type(mask).__name__)} {list(getattr(mask, 'shape', ()))}")
+    dev = _require_gpu(means3D)
+    for name, t in (("contribution.raw", raw), ("contribution_mask", mask)):
+        if t is not None and not t.is_cuda:
+            raise _lib.GsrError(f"{name} is on {t.device}: the statistics accumulate on the ROCm GPU (no CPU path)")
+        if t is not None and t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, expected {dev}")
+
+
+def _accumulate_contribution(node, stats, mask, means3D, settings) -> None:
+    """Add the statistics of the colour node's frame into ``stats.raw`` (``gsr_contribution_accumulate``) and count the
+    view.  Reads the frame's saved state only; no host synchronisation, nothing for autograd."""
+    frame, mode = _frame_of(node)
+    dev = means3D.device
+    mask = None if mask is None else mask.contiguous()
+    with torch.cuda.device(dev):
+        f = _aux_frame(frame, int(means3D.shape[0]), int(settings.image_width), int(settings.image_height), mode)
+        _lib.check(_lib.load().gsr_contribution_accumulate(C.byref(f), _ptr(mask), _ptr(stats.raw), _stream(dev)),
+                   "gsr_contribution_accumulate")
+    stats.views += 1
+
+
+def _with_frame_outputs(color, radii, node, grad: bool, geometry, aux_maps, contribution, contribution_mask):
+    """The results of a frame that kept its state: the statistics are accumulated, the maps appended when asked for."""
+    if contribution is not None:
+        _accumulate_contribution(node, contribution, contribution_mask, geometry[0], geometry[6])
+    if aux_maps:
+        return color, radii, _aux_maps_of(node, grad, *geometry)
+    return color, radii
+
+
 def rasterize_gaussians_fused(means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations, raster_settings,
-                              densify_stats=None, visible=None, _state_key=None, aux_maps=False):
+                              densify_stats=None, visible=None, _state_key=None, aux_maps=False, contribution=None,
+                              contribution_mask=None):
     """``densify_stats``: None, or (xyz_gradient_accum, denom, max_radii2D) -- the backward then also accumulates the
     densification statistics of ``scene/gaussian_model.py:775-777`` / ``train.py:130``.
     ``visible``: None, or a bool [P] tensor that receives ``radii > 0`` from the preprocess kernel.
     ``_state_key`` (internal): the capacity state of grown frames (``_grown_key``) instead of the one of P rows.
-    ``aux_maps``: also return the depth / inverse-depth / alpha maps ``[3,H,W]`` (``_AuxMaps``) as a third result."""
+    ``aux_maps``: also return the depth / inverse-depth / alpha maps ``[3,H,W]`` (``_AuxMaps``) as a third result.
+    ``contribution`` / ``contribution_mask``: accumulate the frame's contribution statistics (module docstring)."""
     cam = _camera_inputs(raster_settings)
-    if aux_maps:
-        _check_aux_request(cam, _state_key, densify_stats)
+    if aux_maps or contribution is not None:
+        # both read the state only a forward that tracks its contributors leaves: the frame runs with forward_only = 0
+        if aux_maps:
+            _check_aux_request(cam, _state_key, densify_stats)
+        if contribution is not None:
+            _check_contribution_request(contribution, contribution_mask, means3D, raster_settings, _state_key)
         empty = torch.empty(0, dtype=torch.float32, device=means3D.device)
         flags = _lib.ACT_SCALE_EXP | _lib.ACT_ROT_NORMALIZE | _lib.ACT_OPACITY_SIGMOID
         geometry = (means3D, means2D, raw_opacity, raw_scales, raw_rotations, empty, raster_settings, flags)
-        if _forward_only(means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations):
-            with torch.no_grad():       # the maps read the state only a forward that tracks its contributors leaves
+        if _forward_only(means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations, *cam):
+            with torch.no_grad():
                 node = _KeepFrame()
                 color, radii = _RasterizeGaussiansFused.forward(node, means3D, means2D, f_dc, f_rest, raw_opacity,
                                                                 raw_scales, raw_rotations, raster_settings, False, None,
                                                                 visible)
-                return color, radii, _aux_maps_of(node, False, *geometry)
+                return _with_frame_outputs(color, radii, node, False, geometry, aux_maps, contribution, contribution_mask)
         color, radii = _RasterizeGaussiansFused.apply(means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales,
-                                                      raw_rotations, raster_settings, False, densify_stats, visible)
-        return color, radii, _aux_maps_of(color.grad_fn, True, *geometry)
+                                                      raw_rotations, raster_settings, False, densify_stats, visible,
+                                                      _state_key, *cam)
+        return _with_frame_outputs(color, radii, color.grad_fn, True, geometry, aux_maps, contribution, contribution_mask)
     if _forward_only(means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations, *cam):
         with torch.no_grad():
             return _RasterizeGaussiansFused.forward(_NoGraph(), means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales,
@@ -955,20 +1014,24 @@ def rasterize_gaussians_fused(means3D, means2D, f_dc, f_rest, raw_opacity, raw_s
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, densify_stats=None, aux_maps=False):
+                        raster_settings, densify_stats=None, aux_maps=False, contribution=None, contribution_mask=None):
     cam = _camera_inputs(raster_settings)
-    if aux_maps:
-        _check_aux_request(cam, densify_stats=densify_stats)
+    if aux_maps or contribution is not None:
+        # both read the state only a forward that tracks its contributors leaves: the frame runs with forward_only = 0
+        if aux_maps:
+            _check_aux_request(cam, densify_stats=densify_stats)
+        if contribution is not None:
+            _check_contribution_request(contribution, contribution_mask, means3D, raster_settings)
         geometry = (means3D, means2D, opacities, scales, rotations, cov3Ds_precomp, raster_settings)
-        if _forward_only(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp):
-            with torch.no_grad():       # the maps read the state only a forward that tracks its contributors leaves
+        if _forward_only(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, *cam):
+            with torch.no_grad():
                 node = _KeepFrame()
                 color, radii = _RasterizeGaussians.forward(node, means3D, means2D, sh, colors_precomp, opacities, scales,
                                                            rotations, cov3Ds_precomp, raster_settings, False, None)
-                return color, radii, _aux_maps_of(node, False, *geometry)
+                return _with_frame_outputs(color, radii, node, False, geometry, aux_maps, contribution, contribution_mask)
         color, radii = _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                                 cov3Ds_precomp, raster_settings, False, densify_stats)
-        return color, radii, _aux_maps_of(color.grad_fn, True, *geometry)
+                                                 cov3Ds_precomp, raster_settings, False, densify_stats, *cam)
+        return _with_frame_outputs(color, radii, color.grad_fn, True, geometry, aux_maps, contribution, contribution_mask)
     if _forward_only(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, *cam):
         with torch.no_grad():
             return _RasterizeGaussians.forward(_NoGraph(), means3D, means2D, sh, colors_precomp, opacities, scales,
@@ -981,13 +1044,18 @@ class GaussianRasterizer(nn.Module):
     """Same call contract as the module the reference constructs per frame
     (``gaussian_renderer/__init__.py:57``) and calls at ``:257-265``."""
 
-    def __init__(self, raster_settings: GaussianRasterizationSettings, aux_maps: bool = False):
+    def __init__(self, raster_settings: GaussianRasterizationSettings, aux_maps: bool = False, contribution=None,
+                 contribution_mask: Optional[torch.Tensor] = None):
         """``aux_maps=True``: the call returns ``(color, radii, aux)`` with ``aux [3,H,W]`` = the depth
         (``sum w z``), inverse-depth (``sum w / z``) and accumulated-opacity (``sum w``) maps of the frame,
-        differentiable in means3D, means2D, opacities and scales / rotations or cov3D_precomp."""
+        differentiable in means3D, means2D, opacities and scales / rotations or cov3D_precomp.
+        ``contribution``: a ``contribution.ContributionStats`` that every call adds its frame's per-Gaussian statistics
+        into; ``contribution_mask``: uint8 ``[H,W]``, pixels with 0 are left out.  Not differentiable."""
         super().__init__()
         self.raster_settings = raster_settings
         self.aux_maps = bool(aux_maps)
+        self.contribution = contribution
+        self.contribution_mask = contribution_mask
 
     def markVisible(self, positions: torch.Tensor) -> torch.Tensor:
         """Frustum (near-plane) visibility of the upstream module's ``markVisible``; bool ``[P]``."""
@@ -1016,9 +1084,11 @@ class GaussianRasterizer(nn.Module):
         rotations = empty if rotations is None else rotations
         cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                   cov3D_precomp, raster_settings, densify_stats, aux_maps=self.aux_maps)
+                                   cov3D_precomp, raster_settings, densify_stats, aux_maps=self.aux_maps,
+                                   contribution=self.contribution, contribution_mask=self.contribution_mask)
 
     def forward_fused(self, means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations, densify_stats=None):
         """Raw-parameter entry: see :class:`_RasterizeGaussiansFused`."""
         return rasterize_gaussians_fused(means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations,
-                                         self.raster_settings, densify_stats, aux_maps=self.aux_maps)
+                                         self.raster_settings, densify_stats, aux_maps=self.aux_maps,
+                                         contribution=self.contribution, contribution_mask=self.contribution_mask)

@@ -92,7 +92,7 @@ def _settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier):
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier: float = 1.0,
            override_color=None, grow_dir=False, densify_grad_threshold=0, iteration=None, opt=None,
            continous_dir=False, grow_distance=False, modelcg=None, cameras_extent=None, return_depth=False,
-           use_trained_exp=False):
+           use_trained_exp=False, contribution=None, contribution_mask=None):
     """Render the scene; ``bg_color`` must be on the GPU.  Returns the reference's result dict
     (``gaussian_renderer/__init__.py:309-313``).  The keyword arguments after ``override_color`` are the reference's
     (``:19``) and drive the grow / learned-split branch (module docstring); the frame of a closed branch is unchanged.
@@ -111,19 +111,30 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier:
 
     ``use_trained_exp=True`` (upstream 3DGS's name): ``"render"`` is the rasterizer's image after the camera's 3x4
     exposure, ``apply_exposure(image, pc.get_exposure_from_name(viewpoint_camera.image_name))`` (``exposure.py``), on
-    every path; the maps of ``return_depth`` are untouched.  False leaves the frame exactly as it was."""
+    every path; the maps of ``return_depth`` are untouched.  False leaves the frame exactly as it was.
+
+    ``contribution=stats`` (a ``contribution.ContributionStats`` with one row per Gaussian): the frame's per-Gaussian
+    blending-weight statistics are added into ``stats`` after the colour forward and ``stats.views`` counts the frame;
+    ``contribution_mask`` (uint8 ``[H,W]``) leaves the pixels with value 0 out.  Not differentiable; the result dict is
+    what it is without it.  Not available on a frame of the open grow / learned-split branch."""
     pkg = _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, grow_dir,
                   densify_grad_threshold, iteration, opt, continous_dir, grow_distance, modelcg, cameras_extent,
-                  return_depth)
+                  return_depth, contribution, contribution_mask)
     if use_trained_exp:
         pkg["render"] = apply_exposure(pkg["render"], pc.get_exposure_from_name(viewpoint_camera.image_name))
     return pkg
 
 
 def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, grow_dir, densify_grad_threshold,
-            iteration, opt, continous_dir, grow_distance, modelcg, cameras_extent, return_depth):
+            iteration, opt, continous_dir, grow_distance, modelcg, cameras_extent, return_depth, contribution=None,
+            contribution_mask=None):
     """The frame of ``render`` as the rasterizer leaves it."""
     which = grow.branch(iteration, opt, grow_dir, continous_dir, modelcg)
+    if which is not None and contribution is not None:
+        raise ValueError("contribution statistics are not available on a frame of the open grow / learned-split branch "
+                         "(virtual rows appended): measure in a frame of its own")
+    # the statistics request travels only when the caller made one: a frame without it is issued exactly as before
+    extra_stats = {} if contribution is None else {"contribution": contribution, "contribution_mask": contribution_mask}
     if which is not None and return_depth:
         raise ValueError("return_depth=True is not available on a frame of the open grow / learned-split branch "
                          "(virtual rows appended): render the maps in a frame of their own")
@@ -152,16 +163,17 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
             rendered_image, radii, aux = rasterize_gaussians_fused(xyz, screenspace_points, pc._features_dc,
                                                                    pc._features_rest, pc._opacity, pc._scaling,
                                                                    pc._rotation, raster_settings, visible=visible,
-                                                                   aux_maps=True)
+                                                                   aux_maps=True, **extra_stats)
             return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": visible,
                     "radii": radii, "selected_pts_mask": None, **_aux_entries(aux)}
         rendered_image, radii = rasterize_gaussians_fused(xyz, screenspace_points, pc._features_dc, pc._features_rest,
                                                           pc._opacity, pc._scaling, pc._rotation, raster_settings,
-                                                          densify_stats=stats, visible=visible)
+                                                          densify_stats=stats, visible=visible, **extra_stats)
         return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": visible,
                 "radii": radii, "selected_pts_mask": None}
 
-    rasterizer = GaussianRasterizer(raster_settings=raster_settings, **({"aux_maps": True} if return_depth else {}))
+    rasterizer = GaussianRasterizer(raster_settings=raster_settings, **({"aux_maps": True} if return_depth else {}),
+                                    **extra_stats)
     scales = rotations = cov3D_precomp = None
     if getattr(pipe, "compute_cov3D_python", False):
         cov3D_precomp = pc.get_covariance(scaling_modifier)
