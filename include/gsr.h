@@ -275,6 +275,29 @@ size_t gsr_sort_scratch_bytes(uint32_t n);
 int gsr_sort_pairs_u64(uint64_t* keys, uint32_t* vals, uint64_t* keys_tmp, uint32_t* vals_tmp,
                        uint32_t n, int32_t end_bit, void* scratch, void* stream,
                        int32_t* result_in_tmp /* host out: 1 if the sorted data ended in *_tmp */);
+/* The 32-bit-key sorts of the two-level binning (the default mode), same conventions as gsr_sort_pairs_u64.
+ * val_words = 1: uint32 values (the tile sort); 2: 8-byte values, 8-byte aligned (the depth sort's payload).
+ * n_dev = NULL: `capacity` is the element count.  Otherwise the count is read from device memory (*n_dev <= capacity),
+ * the grids are sized for `capacity`, and nothing at index *n_dev or beyond is read or written.  Buffers hold `capacity`
+ * elements; scratch: gsr_sort_scratch_bytes(capacity).  end_bit in [0, 32]. */
+int gsr_sort_pairs_u32(uint32_t* keys, void* vals, uint32_t* keys_tmp, void* vals_tmp, uint32_t capacity,
+                       const uint32_t* n_dev, int32_t end_bit, int32_t val_words, void* scratch, void* stream,
+                       int32_t* result_in_tmp);
+/* One more stable pass on bits [shift, shift + nbits) of 32-bit keys with 8-byte values, nbits in [1, 8]: the depth
+ * sort's top-digit pass.  Reads *_in, writes *_out; *n_dev = 0 writes nothing. */
+int gsr_sort_extra_pass_u32(const uint32_t* keys_in, const void* vals_in, uint32_t* keys_out, void* vals_out,
+                            uint32_t capacity, const uint32_t* n_dev, int32_t shift, int32_t nbits, void* scratch,
+                            void* stream);
+/* The tile sort of the two-level binning with what it derives from its own histograms: a gsr_sort_pairs_u32 (uint32
+ * values) of keys in [0, n_keys), then -- when the sort took at most two passes (*runs_valid = 1) -- ranges[k] =
+ * [first, last + 1) of key k in the sorted array, (0, 0) for a key without items, and `order`: per chunk of 8192 keys a
+ * permutation of the chunk's keys, longest run first by length bucket.  With *runs_valid = 0 ranges and order are not
+ * written.  ranges: device uint32 [n_keys, 2], 16-byte aligned (also the sort's scratch for relative runs); order:
+ * device uint32 [n_keys].  end_bit: what the forward passes for an image of n_keys tiles, max(1, ceil(log2 n_keys))
+ * (tile_sort_bits at the tile sort of enqueue_stage2, csrc/gsr_api.hip); n_keys <= 2^end_bit is required. */
+int gsr_sort_tile_runs_u32(uint32_t* keys, uint32_t* vals, uint32_t* keys_tmp, uint32_t* vals_tmp, uint32_t capacity,
+                           const uint32_t* n_dev, int32_t end_bit, uint32_t n_keys, void* ranges, uint32_t* order,
+                           void* scratch, void* stream, int32_t* result_in_tmp, int32_t* runs_valid);
 /* copies internal state out for inspection (any pointer may be NULL) */
 int gsr_debug_read_geom(const void* geom_ws, int32_t P, float* xy /*[P,2]*/, float* conic_opacity /*[P,4]*/,
                         float* rgb /*[P,3]*/, float* depth /*[P]*/, uint32_t* tiles_touched /*[P]*/,

@@ -149,6 +149,13 @@ SYMBOLS = {
     "gsr_sort_scratch_bytes": (C.c_size_t, [C.c_uint32]),
     "gsr_sort_pairs_u64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32,
                                      C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
+    # the 32-bit-key sorts of the two-level binning, callable on their own (tests/test_gpu_sort.py)
+    "gsr_sort_pairs_u32": (C.c_int, [C.c_void_p] * 4 + [C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                     C.c_void_p, C.POINTER(C.c_int32)]),
+    "gsr_sort_extra_pass_u32": (C.c_int, [C.c_void_p] * 4 + [C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                          C.c_void_p]),
+    "gsr_sort_tile_runs_u32": (C.c_int, [C.c_void_p] * 4 + [C.c_uint32, C.c_void_p, C.c_int32, C.c_uint32] +
+                               [C.c_void_p] * 4 + [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "gsr_debug_read_geom": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 9),
     "gsr_debug_read_binning": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32,
                                          C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),

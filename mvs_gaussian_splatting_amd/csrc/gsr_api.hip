@@ -734,6 +734,67 @@ int gsr_sort_pairs_u64(uint64_t* keys, uint32_t* vals, uint64_t* keys_tmp, uint3
   return check(nullptr, s, "sort_pairs");
 }
 
+int gsr_sort_pairs_u32(uint32_t* keys, void* vals, uint32_t* keys_tmp, void* vals_tmp, uint32_t capacity,
+                       const uint32_t* n_dev, int32_t end_bit, int32_t val_words, void* scratch, void* stream,
+                       int32_t* result_in_tmp) {
+  if (!result_in_tmp) return fail(GSR_E_BADARG, "result_in_tmp is NULL");
+  *result_in_tmp = 0;
+  if (val_words != 1 && val_words != 2) return fail(GSR_E_BADARG, "val_words must be 1 or 2");
+  if (end_bit < 0 || end_bit > 32) return fail(GSR_E_BADARG, "end_bit out of range");
+  if (capacity == 0) return 0;
+  if (!keys || !vals || !keys_tmp || !vals_tmp || !scratch) return fail(GSR_E_BADARG, "NULL buffer");
+  if (val_words == 2 && ((((uintptr_t)vals) | ((uintptr_t)vals_tmp)) & 7u) != 0)
+    return fail(GSR_E_ALIGN, "two-word values must be 8-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool in_tmp =
+      val_words == 1
+          ? launch_sort_pairs_u32(keys, static_cast<uint32_t*>(vals), keys_tmp, static_cast<uint32_t*>(vals_tmp), capacity,
+                                  end_bit, scratch, s, n_dev)
+          : launch_sort_pairs_u32_v64(keys, static_cast<uint2*>(vals), keys_tmp, static_cast<uint2*>(vals_tmp), capacity,
+                                      end_bit, scratch, s, n_dev);
+  *result_in_tmp = in_tmp ? 1 : 0;
+  return check(nullptr, s, "sort_pairs_u32");
+}
+
+int gsr_sort_extra_pass_u32(const uint32_t* keys_in, const void* vals_in, uint32_t* keys_out, void* vals_out,
+                            uint32_t capacity, const uint32_t* n_dev, int32_t shift, int32_t nbits, void* scratch,
+                            void* stream) {
+  if (nbits < 1 || nbits > 8 || shift < 0 || shift + nbits > 32) return fail(GSR_E_BADARG, "shift / nbits out of range");
+  if (capacity == 0) return 0;
+  if (!keys_in || !vals_in || !keys_out || !vals_out || !scratch) return fail(GSR_E_BADARG, "NULL buffer");
+  if (((((uintptr_t)vals_in) | ((uintptr_t)vals_out)) & 7u) != 0)
+    return fail(GSR_E_ALIGN, "two-word values must be 8-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_sort_extra_pass_u32(keys_in, static_cast<const uint2*>(vals_in), keys_out, static_cast<uint2*>(vals_out), capacity,
+                             n_dev, shift, nbits, scratch, s);
+  return check(nullptr, s, "sort_extra_pass_u32");
+}
+
+int gsr_sort_tile_runs_u32(uint32_t* keys, uint32_t* vals, uint32_t* keys_tmp, uint32_t* vals_tmp, uint32_t capacity,
+                           const uint32_t* n_dev, int32_t end_bit, uint32_t n_keys, void* ranges, uint32_t* order,
+                           void* scratch, void* stream, int32_t* result_in_tmp, int32_t* runs_valid) {
+  if (!result_in_tmp || !runs_valid) return fail(GSR_E_BADARG, "result_in_tmp / runs_valid is NULL");
+  *result_in_tmp = 0;
+  *runs_valid = 0;
+  if (end_bit < 1 || end_bit > 32) return fail(GSR_E_BADARG, "end_bit out of range");
+  // every key value needs a digit row in the last pass and a slot in ranges / order
+  if (n_keys == 0 || n_keys > 0x7fffffffu || (end_bit < 32 && n_keys > (1u << end_bit)))
+    return fail(GSR_E_BADARG, "n_keys does not fit end_bit");
+  if (capacity == 0) return 0;
+  if (!keys || !vals || !keys_tmp || !vals_tmp || !scratch || !ranges || !order) return fail(GSR_E_BADARG, "NULL buffer");
+  if (((uintptr_t)ranges & 15u) != 0) return fail(GSR_E_ALIGN, "ranges must be 16-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  SortedRuns runs;
+  runs.valid = false;
+  runs.runs_rel = static_cast<uint2*>(ranges);
+  runs.n_keys = n_keys;
+  *result_in_tmp = launch_sort_pairs_u32(keys, vals, keys_tmp, vals_tmp, capacity, end_bit, scratch, s, n_dev, &runs) ? 1 : 0;
+  if (int rc = check(nullptr, s, "tile_sort")) return rc;
+  *runs_valid = runs.valid ? 1 : 0;
+  if (runs.valid) launch_ranges_and_order_from_sort((int)n_keys, runs, static_cast<uint2*>(ranges), order, s);
+  return check(nullptr, s, "ranges_and_order_from_sort");
+}
+
 int gsr_debug_read_geom(const void* geom_ws, int32_t P, float* xy, float* conic_opacity, float* rgb, float* depth,
                         uint32_t* tiles_touched, uint32_t* point_offsets, uint32_t* rect, uint32_t* clamped,
                         void* stream) {

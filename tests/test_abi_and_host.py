@@ -94,6 +94,34 @@ def test_bad_arguments_are_rejected_before_any_launch():
     assert lib.gsr_event_destroy(None) == 0
 
 
+def test_sort_entry_points_reject_bad_arguments_before_any_launch():
+    from mvs_gaussian_splatting_amd import _lib
+    lib = _lib.load()
+    for n in ("gsr_sort_pairs_u32", "gsr_sort_extra_pass_u32", "gsr_sort_tile_runs_u32"):
+        assert n in _declared_functions() and n in _lib.SYMBOLS
+    flag, valid = C.c_int32(7), C.c_int32(7)
+    p = 4096          # never dereferenced: every call below is refused on its arguments
+    assert lib.gsr_sort_pairs_u32(p, p, p, p, 10, None, 13, 1, p, None, None) == -1
+    assert lib.gsr_sort_pairs_u32(p, p, p, p, 10, None, 13, 3, p, None, C.byref(flag)) == -1 and flag.value == 0
+    assert lib.gsr_sort_pairs_u32(p, p, p, p, 10, None, 33, 1, p, None, C.byref(flag)) == -1
+    assert lib.gsr_sort_pairs_u32(p, None, p, p, 10, None, 13, 1, p, None, C.byref(flag)) == -1
+    assert lib.gsr_sort_pairs_u32(p, p + 4, p, p, 10, None, 13, 2, p, None, C.byref(flag)) == -3
+    assert lib.gsr_sort_pairs_u32(None, None, None, None, 0, None, 13, 1, None, None, C.byref(flag)) == 0   # nothing to sort
+    assert lib.gsr_sort_extra_pass_u32(p, p, p, p, 10, None, 24, 9, p, None) == -1
+    assert lib.gsr_sort_extra_pass_u32(p, p, p, p, 10, None, 28, 8, p, None) == -1
+    assert lib.gsr_sort_extra_pass_u32(p, p, p, p + 4, 10, None, 24, 8, p, None) == -3
+    assert lib.gsr_sort_extra_pass_u32(p, p, None, p, 10, None, 24, 8, p, None) == -1
+    args = lambda end_bit, n_keys, ranges: (p, p, p, p, 10, None, end_bit, n_keys, ranges, p, p, None,  # noqa: E731
+                                            C.byref(flag), C.byref(valid))
+    assert lib.gsr_sort_tile_runs_u32(*args(13, 8193, p)) == -1 and b"n_keys" in lib.gsr_last_error()
+    assert lib.gsr_sort_tile_runs_u32(*args(0, 1, p)) == -1
+    assert lib.gsr_sort_tile_runs_u32(*args(13, 0, p)) == -1
+    assert lib.gsr_sort_tile_runs_u32(*args(13, 8160, None)) == -1
+    assert lib.gsr_sort_tile_runs_u32(*args(13, 8160, p + 8)) == -3
+    assert flag.value == 0 and valid.value == 0
+    assert lib.gsr_sort_tile_runs_u32(p, p, p, p, 10, None, 13, 8160, p, p, p, None, C.byref(flag), None) == -1
+
+
 def _cpu_call(**over):
     from mvs_gaussian_splatting_amd import GaussianRasterizer, GaussianRasterizationSettings
     from conftest import small_scene, make_settings
