@@ -9,7 +9,10 @@ SH degree steps, densification, opacity resets, the optional opacity sparsity te
                              [--train_exposure [--exposure_lr_init LR] [--exposure_lr_final LR]
                               [--exposure_lr_delay_steps N] [--exposure_lr_delay_mult M]]
                              [--prune_iterations N [N ...] --prune_keep_ratio R [--prune_kind sum|max|count|mean]]
+                             [--strategy mcmc --cap_max N [--noise_lr LR] [--opacity_reg W] [--scale_reg W]]
 
+``--strategy mcmc --cap_max N`` (both forms) densifies the MCMC way (``mcmc.py``): a budget of N Gaussians, dead ones
+relocated onto live ones, 5 % growth a round, position noise and L1 priors on opacity and scale.
 ``--optimizer_type sparse_adam`` (both forms) steps only the Gaussians each frame saw (``optim.SparseGaussianAdam``).
 
 With ``-s`` the example trains on a dataset through ``Scene`` (``scene.py``) and saves
@@ -138,6 +141,14 @@ def train(model, problem, opt, first_iter=0, last_iter=None, dataset=None, pipe=
     return losses
 
 
+def strategy_options(args):
+    """The ``OptimizationParams`` overrides of the ``--strategy`` arguments."""
+    if args.strategy == "mcmc" and args.cap_max <= 0:
+        raise SystemExit("--strategy mcmc needs --cap_max N, the budget of Gaussians")
+    return dict(strategy=args.strategy, cap_max=args.cap_max, noise_lr=args.noise_lr, opacity_reg=args.opacity_reg,
+                scale_reg=args.scale_reg)
+
+
 def train_scene(args, dev):
     """``train.py:34-160`` on a dataset: ``Scene`` loads it, a random camera is popped from a copy of the training list
     that is refilled when it empties (:81-83), the model is saved at ``--save_iterations`` and at the end."""
@@ -148,7 +159,8 @@ def train_scene(args, dev):
     n = args.iterations
     over = dict(opacitysparse=args.opacitysparse, optimizer_type=args.optimizer_type,
                 exposure_lr_init=args.exposure_lr_init, exposure_lr_final=args.exposure_lr_final,
-                exposure_lr_delay_steps=args.exposure_lr_delay_steps, exposure_lr_delay_mult=args.exposure_lr_delay_mult)
+                exposure_lr_delay_steps=args.exposure_lr_delay_steps, exposure_lr_delay_mult=args.exposure_lr_delay_mult,
+                **strategy_options(args))
     opt = example_opt(n, **over) if n < 3000 else OptimizationParams(iterations=n, **over)
     model = GaussianModel(dataset.sh_degree)
     scene = Scene(dataset, model)
@@ -216,6 +228,12 @@ def main(argv=None):
                     help="after these iterations: measure every training view and prune by contribution")
     ap.add_argument("--prune_keep_ratio", type=float, default=None, help="share of the Gaussians a pruning keeps")
     ap.add_argument("--prune_kind", choices=("sum", "max", "count", "mean"), default="sum")
+    ap.add_argument("--strategy", choices=("default", "mcmc"), default="default",
+                    help="mcmc: relocation, 5 %% growth up to --cap_max, position noise, opacity / scale priors (mcmc.py)")
+    ap.add_argument("--cap_max", type=int, default=OptimizationParams.cap_max, help="with --strategy mcmc: the budget")
+    ap.add_argument("--noise_lr", type=float, default=OptimizationParams.noise_lr)
+    ap.add_argument("--opacity_reg", type=float, default=OptimizationParams.opacity_reg)
+    ap.add_argument("--scale_reg", type=float, default=OptimizationParams.scale_reg)
     ap.add_argument("--out", default=os.path.dirname(os.path.abspath(__file__)))
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
@@ -224,7 +242,7 @@ def main(argv=None):
             ap.error("-s needs -m, the directory the model is saved under")
         return train_scene(args, dev)
     n = args.iterations
-    opt = example_opt(n, opacitysparse=args.opacitysparse, optimizer_type=args.optimizer_type)
+    opt = example_opt(n, opacitysparse=args.opacitysparse, optimizer_type=args.optimizer_type, **strategy_options(args))
     dataset = types.SimpleNamespace(white_background=False)
     problem = make_problem(dev)
     model = make_model(problem, opt, dataset)

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 24
+#define GSR_ABI_VERSION 25
 
 enum {
   GSR_OK = 0,
@@ -683,6 +683,57 @@ size_t gsr_exposure_workspace_bytes(int32_t H, int32_t W);
 int gsr_exposure_apply_fwd(const float* x, const float* A, int32_t H, int32_t W, float* y, void* stream);
 int gsr_exposure_apply_bwd(const float* x, const float* A, const float* g, int32_t H, int32_t W, float* dx, float* dA,
                            void* workspace, void* stream);
+
+/* MCMC densification ("3DGS as Markov-chain Monte Carlo"), ABI v25 (csrc/mcmc.hip; mcmc.py).
+ * Every input is a RAW model tensor, device fp32: opacity_raw [P,1], scaling_raw [P,3], rotation_raw [P,4] (16-byte
+ * aligned).  The activations are formed in float32 exactly as GSR_ACT_* forms them in preprocess:
+ *     o = 1 / (1 + expf(-raw))      s = expf(raw)      q = raw / fmaxf(sqrtf(((x x + y y) + z z) + w w), 1e-12f)
+ * Every call is asynchronous on `stream`, allocates nothing, reads nothing back and can sit in a captured graph; it
+ * returns GSR_E_BADARG (NULL pointer, a count outside 0..2^31-1, a workspace that is too small) or GSR_E_ALIGN before
+ * any HIP call, and 0 without a launch for an empty problem.  No kernel waits on another workgroup.
+ *
+ *   gsr_mcmc_noise: xyz [P,3] += Sigma v in place, Sigma = R(q) diag(s^2) R(q)^T never formed, noise [P,3] the caller's
+ *     standard-normal draws.  One streaming pass (56 B read, 12 B written per row), float32, no contraction, in this
+ *     order:
+ *         gate = 1 / (1 + expf(-100 * ((1 - o) - 0.995f)))           v_k = (noise_k * gate) * step_scale
+ *         R = the rotation of q as preprocess forms it for cov3D (r, x, y, z = q[0..3])
+ *         u_j = (R_0j v_0 + R_1j v_1) + R_2j v_2     w_j = (s_j s_j) u_j     d_i = (R_i0 w_0 + R_i1 w_1) + R_i2 w_2
+ *         xyz_i = xyz_i + d_i
+ *     A row with o >= 0.9 has gate == 0 exactly (expf overflows to +inf) and keeps its bits, as does a row whose noise
+ *     is 0 (a -0 coordinate comes out as +0).
+ *   gsr_mcmc_reg_fwd: record (16-byte aligned, 4 floats) =
+ *         { opacity_reg * mean_i o_i + scale_reg * mean_ij s_ij,  opacity_reg / P,  scale_reg / (3 P),  0 }
+ *     The float32 activations are added in double, one pair of sums per block in `workspace`
+ *     (gsr_mcmc_reg_workspace_bytes(), 8-byte aligned), the pairs by one block in a fixed order; each record entry is
+ *     rounded once from double.  The same bits from run to run.
+ *   gsr_mcmc_reg_bwd: grad_opacity [P,1] = (g * record[1]) * (o * (1 - o)), grad_scaling [P,3] = (g * record[2]) * s,
+ *     dense; g = grad_out[0], the DEVICE address of the upstream 0-dim gradient.
+ *   gsr_mcmc_sample: n samples with replacement, exact in integers.  w_i = round-to-nearest(o_i 2^30) as int64 where
+ *     o_i > alive_threshold, else 0 (alive_threshold < 0: every row); C_i the inclusive prefix sum, T = C_{P-1}.  For
+ *     draw r = draws[j] (int64, uniform in [0, 2^63)): t = floor(r T / 2^63) by the 128-bit product, idx_out[j] (int32) =
+ *     the smallest i with C_i > t: a row of weight 0 is never returned.  count_out [P] (int32) is zero-filled, then
+ *     counts the samples per row (integer atomics).  T == 0: every idx_out is -1, the counts are 0.  T stays on the
+ *     device.  workspace: gsr_mcmc_sample_workspace_bytes(P) bytes, 8-byte aligned.  Every output is the same bits
+ *     whatever the launch shape.
+ *   gsr_mcmc_relocation: per sample j, with i = idx[j] and N = min(count[i] + 1, 51), in double from the float32
+ *     activations o, s to one final rounding:
+ *         o' = 1 - (1 - o)^(1/N)
+ *         D  = sum_{m=1..N} sum_{k=0..m-1} C(m-1,k) (-1)^k / sqrt(k+1) * o'^(k+1)       (m outer, k inner, ascending)
+ *         new_scaling_raw[j]  = log((o / D) * s)
+ *         new_opacity_raw[j]  = log(o'' / (1 - o'')),  o'' = clamp(o', 0.005, 1 - 2^-23)
+ *     A pure function of the sample: the outputs are arrays of their own ([n], [n,3]).  idx[j] < 0 writes zeros. */
+int gsr_mcmc_noise(int64_t P, float* xyz, const float* scaling_raw, const float* rotation_raw, const float* opacity_raw,
+                   const float* noise, float step_scale, void* stream);
+size_t gsr_mcmc_reg_workspace_bytes(void);
+int gsr_mcmc_reg_fwd(const float* opacity_raw, const float* scaling_raw, int64_t P, float opacity_reg, float scale_reg,
+                     float* record, void* workspace, size_t workspace_bytes, void* stream);
+int gsr_mcmc_reg_bwd(const float* opacity_raw, const float* scaling_raw, int64_t P, const float* record,
+                     const float* grad_out, float* grad_opacity, float* grad_scaling, void* stream);
+size_t gsr_mcmc_sample_workspace_bytes(int64_t P);
+int gsr_mcmc_sample(int64_t P, const float* opacity_raw, float alive_threshold, const int64_t* draws, int64_t n,
+                    int32_t* idx_out, int32_t* count_out, void* workspace, size_t workspace_bytes, void* stream);
+int gsr_mcmc_relocation(int64_t n, const int32_t* idx, const int32_t* count, const float* opacity_raw,
+                        const float* scaling_raw, float* new_opacity_raw, float* new_scaling_raw, void* stream);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # instead of copying it over the in-tree library
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")
 
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 
 class GsrParams(C.Structure):
@@ -227,6 +227,16 @@ SYMBOLS = {
     "gsr_exposure_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "gsr_exposure_apply_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "gsr_exposure_apply_bwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 2 + [C.c_void_p] * 4),
+    # MCMC densification on the raw model tensors: noise, priors, weighted sampler, relocation (csrc/mcmc.hip; mcmc.py)
+    "gsr_mcmc_noise": (C.c_int, [C.c_int64] + [C.c_void_p] * 5 + [C.c_float, C.c_void_p]),
+    "gsr_mcmc_reg_workspace_bytes": (C.c_size_t, []),
+    "gsr_mcmc_reg_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                   C.c_size_t, C.c_void_p]),
+    "gsr_mcmc_reg_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 5),
+    "gsr_mcmc_sample_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gsr_mcmc_sample": (C.c_int, [C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gsr_mcmc_relocation": (C.c_int, [C.c_int64] + [C.c_void_p] * 7),
 }
 
 _lib = None

@@ -1300,4 +1300,76 @@ int gsr_exposure_apply_bwd(const float* x, const float* A, const float* g, int32
   return check(nullptr, s, "exposure_apply_bwd");
 }
 
+// ---- MCMC densification (csrc/mcmc.hip) -----------------------------------------------------------------------------
+static int mcmc_rows_ok(int64_t P) { return P >= 0 && P <= (int64_t)INT32_MAX; }
+int gsr_mcmc_noise(int64_t P, float* xyz, const float* scaling_raw, const float* rotation_raw, const float* opacity_raw,
+                   const float* noise, float step_scale, void* stream) {
+  if (!mcmc_rows_ok(P)) return fail(GSR_E_BADARG, "P must lie in 0..2^31-1");
+  if (P > 0 && (!xyz || !scaling_raw || !rotation_raw || !opacity_raw || !noise)) return fail(GSR_E_BADARG, "NULL argument");
+  if ((((uintptr_t)xyz | (uintptr_t)scaling_raw | (uintptr_t)opacity_raw | (uintptr_t)noise) & 3u) != 0 ||
+      ((uintptr_t)rotation_raw & 15u) != 0)
+    return fail(GSR_E_ALIGN, "arrays must be 4-byte aligned, rotations 16-byte aligned");
+  if (P == 0) return 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_mcmc_noise((size_t)P, xyz, scaling_raw, rotation_raw, opacity_raw, noise, step_scale, s);
+  return check(nullptr, s, "mcmc_noise");
+}
+size_t gsr_mcmc_reg_workspace_bytes(void) { return mcmc_reg_workspace_bytes(); }
+int gsr_mcmc_reg_fwd(const float* opacity_raw, const float* scaling_raw, int64_t P, float opacity_reg, float scale_reg,
+                     float* record, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!mcmc_rows_ok(P)) return fail(GSR_E_BADARG, "P must lie in 0..2^31-1");
+  if (!record || !workspace || (P > 0 && (!opacity_raw || !scaling_raw))) return fail(GSR_E_BADARG, "NULL argument");
+  if (workspace_bytes < mcmc_reg_workspace_bytes()) return fail(GSR_E_BADARG, "workspace smaller than gsr_mcmc_reg_workspace_bytes()");
+  if ((((uintptr_t)opacity_raw | (uintptr_t)scaling_raw) & 3u) != 0 || ((uintptr_t)workspace & 7u) != 0 ||
+      ((uintptr_t)record & 15u) != 0)
+    return fail(GSR_E_ALIGN, "arrays must be 4-byte, the workspace 8-byte and the record 16-byte aligned");
+  if (P == 0) return 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_mcmc_reg_fwd((size_t)P, opacity_raw, scaling_raw, opacity_reg, scale_reg, record, workspace, s);
+  return check(nullptr, s, "mcmc_reg_fwd");
+}
+int gsr_mcmc_reg_bwd(const float* opacity_raw, const float* scaling_raw, int64_t P, const float* record,
+                     const float* grad_out, float* grad_opacity, float* grad_scaling, void* stream) {
+  if (!mcmc_rows_ok(P)) return fail(GSR_E_BADARG, "P must lie in 0..2^31-1");
+  if (!record || !grad_out || (P > 0 && (!opacity_raw || !scaling_raw || !grad_opacity || !grad_scaling)))
+    return fail(GSR_E_BADARG, "NULL argument");
+  if ((((uintptr_t)opacity_raw | (uintptr_t)scaling_raw | (uintptr_t)record | (uintptr_t)grad_out |
+        (uintptr_t)grad_opacity | (uintptr_t)grad_scaling) & 3u) != 0)
+    return fail(GSR_E_ALIGN, "arrays must be 4-byte aligned");
+  if (P == 0) return 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_mcmc_reg_bwd((size_t)P, opacity_raw, scaling_raw, record, grad_out, grad_opacity, grad_scaling, s);
+  return check(nullptr, s, "mcmc_reg_bwd");
+}
+size_t gsr_mcmc_sample_workspace_bytes(int64_t P) { return mcmc_rows_ok(P) ? mcmc_sample_workspace_bytes((size_t)P) : 0; }
+int gsr_mcmc_sample(int64_t P, const float* opacity_raw, float alive_threshold, const int64_t* draws, int64_t n,
+                    int32_t* idx_out, int32_t* count_out, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!mcmc_rows_ok(P) || !mcmc_rows_ok(n)) return fail(GSR_E_BADARG, "P and n must lie in 0..2^31-1");
+  if ((P > 0 && (!opacity_raw || !count_out || !workspace)) || (n > 0 && (!draws || !idx_out)))
+    return fail(GSR_E_BADARG, "NULL argument");
+  if (n > 0 && P == 0) return fail(GSR_E_BADARG, "samples asked of an empty model");
+  if (P > 0 && workspace_bytes < mcmc_sample_workspace_bytes((size_t)P))
+    return fail(GSR_E_BADARG, "workspace smaller than gsr_mcmc_sample_workspace_bytes(P)");
+  if ((((uintptr_t)opacity_raw | (uintptr_t)idx_out | (uintptr_t)count_out) & 3u) != 0 ||
+      (((uintptr_t)draws | (uintptr_t)workspace) & 7u) != 0)
+    return fail(GSR_E_ALIGN, "float / int32 arrays must be 4-byte, draws and workspace 8-byte aligned");
+  if (P == 0) return 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_mcmc_sample((size_t)P, opacity_raw, alive_threshold, draws, (size_t)n, idx_out, count_out, workspace, s);
+  return check(nullptr, s, "mcmc_sample");
+}
+int gsr_mcmc_relocation(int64_t n, const int32_t* idx, const int32_t* count, const float* opacity_raw,
+                        const float* scaling_raw, float* new_opacity_raw, float* new_scaling_raw, void* stream) {
+  if (!mcmc_rows_ok(n)) return fail(GSR_E_BADARG, "n must lie in 0..2^31-1");
+  if (n > 0 && (!idx || !count || !opacity_raw || !scaling_raw || !new_opacity_raw || !new_scaling_raw))
+    return fail(GSR_E_BADARG, "NULL argument");
+  if ((((uintptr_t)idx | (uintptr_t)count | (uintptr_t)opacity_raw | (uintptr_t)scaling_raw | (uintptr_t)new_opacity_raw |
+        (uintptr_t)new_scaling_raw) & 3u) != 0)
+    return fail(GSR_E_ALIGN, "arrays must be 4-byte aligned");
+  if (n == 0) return 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_mcmc_relocation((size_t)n, idx, count, opacity_raw, scaling_raw, new_opacity_raw, new_scaling_raw, s);
+  return check(nullptr, s, "mcmc_relocation");
+}
+
 }  // extern "C"

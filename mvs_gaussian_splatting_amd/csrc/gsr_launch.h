@@ -204,6 +204,23 @@ void launch_exposure_apply_fwd(const float* x, const float* A, size_t pixels, fl
 void launch_exposure_apply_bwd(const float* x, const float* A, const float* g, size_t pixels, float* dx, float* dA,
                                void* workspace, hipStream_t s);
 
+// mcmc.hip: the MCMC strategy's per-Gaussian steps on the RAW tensors (include/gsr.h).  Streaming kernels cap their
+// grid at MCMC_MAX_BLOCKS 256-lane blocks and stride; the priors leave one (sum o, sum s) pair of doubles per block in
+// their workspace; the sampler's workspace holds the int64 prefix sums [P], the scan-block offsets and the total
+constexpr int MCMC_MAX_BLOCKS = 2048;
+size_t mcmc_reg_workspace_bytes();
+size_t mcmc_sample_workspace_bytes(size_t P);
+void launch_mcmc_noise(size_t P, float* xyz, const float* scaling, const float* rotation, const float* opacity,
+                       const float* noise, float step_scale, hipStream_t s);
+void launch_mcmc_reg_fwd(size_t P, const float* opacity, const float* scaling, float opacity_reg, float scale_reg,
+                         float* record, void* workspace, hipStream_t s);
+void launch_mcmc_reg_bwd(size_t P, const float* opacity, const float* scaling, const float* record,
+                         const float* grad_out, float* grad_opacity, float* grad_scaling, hipStream_t s);
+void launch_mcmc_sample(size_t P, const float* opacity, float alive_threshold, const int64_t* draws, size_t n,
+                        int32_t* idx_out, int32_t* count_out, void* workspace, hipStream_t s);
+void launch_mcmc_relocation(size_t n, const int32_t* idx, const int32_t* count, const float* opacity,
+                            const float* scaling, float* new_opacity, float* new_scaling, hipStream_t s);
+
 // image.hip: load-time ingest of uint8 HWC images (one resize pass per call; bounds / taps: include/gsr.h)
 void launch_image_composite_u8(const uint8_t* rgba, size_t pixels, const double bg[3], uint8_t* rgb, hipStream_t s);
 void launch_image_resize_pass(bool vertical, int C, const uint8_t* in, int in_len, int out_len, int other,

@@ -14,8 +14,9 @@ from __future__ import annotations
 
 import torch
 
-from .densify import densify_and_prune
+from .densify import densify_and_prune, is_fork
 from .losses import add_densification_stats, l1_dssim_loss, opacity_sparsity_loss
+from .mcmc import add_new_gs, inject_noise, mcmc_regularizer, relocate_gs
 from .renderer import render
 from .synthetic import PipelineParams  # noqa: F401  (the two parameter classes live side by side)
 
@@ -53,6 +54,14 @@ class OptimizationParams:
     exposure_lr_final = 0.001
     exposure_lr_delay_steps = 0
     exposure_lr_delay_mult = 0.0
+    # densification strategy: "default" (the reference's / the fork's densify_and_prune) or "mcmc" (mcmc.py: a budget of
+    # cap_max Gaussians, relocation, 5 % growth, position noise at noise_lr * lr_xyz, L1 priors on opacity and scale;
+    # opacity_reg / scale_reg are read only under "mcmc")
+    strategy = "default"
+    cap_max = -1
+    noise_lr = 5e5
+    opacity_reg = 0.01
+    scale_reg = 0.01
 
     def __init__(self, **overrides):
         for k, v in overrides.items():
@@ -75,7 +84,7 @@ def schedule(opt, iteration: int, white_background: bool = False) -> dict:
 
 def training_iteration(model, camera, opt, pipe, background, iteration, *, dataset=None, cameras_extent,
                        first_reset=None, gt_image=None, densify_kwargs=None, pose_optimizer=None, depth_loss=None,
-                       train_exposure=False):
+                       train_exposure=False, mcmc_kwargs=None):
     """``train.py:72-142`` for one camera, in the reference's order: learning rate, SH degree, background, ``render``
     with the fork's keyword arguments, L1 + D-SSIM against ``camera.original_image``, the opacity sparsity term
     (``opt.opacitysparse``), ``backward``; then, without gradients, the densification statistics, ``densify_and_prune``,
@@ -96,7 +105,29 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
     branch.
     train_exposure: the frame is rendered with ``use_trained_exp=True`` -- the loss sees the image after the camera's
     3x4 exposure (``model.setup_exposures`` before ``training_setup``) -- and ``model.exposure_optimizer`` is stepped and
-    zeroed where the model's optimizer is."""
+    zeroed where the model's optimizer is.
+    mcmc_kwargs: under ``opt.strategy == "mcmc"`` (``mcmc.py``): ``generator``, ``draws`` (int64, for ``relocate_gs`` and
+    ``add_new_gs``: each uses its first n, so the two steps of one iteration see the same numbers -- meant for tests; leave
+    it out to have each step draw its own from ``generator``) and ``noise`` (``[>= P, 3]``, for ``inject_noise``), for reproducible runs.
+    Under that strategy the L1 priors join the loss, ``relocate_gs`` then ``add_new_gs`` replace ``densify_and_prune`` on
+    the schedule's densify iterations, there is no opacity reset and no densification statistics, ``inject_noise``
+    follows the optimizer step, and a ``sparse_adam`` step takes ``opacity`` and ``scaling`` dense (the priors'
+    gradients are).  ``ValueError`` for ``cap_max <= 0`` or a fork model."""
+    strategy = getattr(opt, "strategy", "default")
+    if strategy not in ("default", "mcmc"):
+        raise ValueError(f"strategy must be 'default' or 'mcmc', got {strategy!r}")
+    mcmc = strategy == "mcmc"
+    if mcmc:
+        if not int(getattr(opt, "cap_max", -1)) > 0:
+            raise ValueError("strategy='mcmc' needs opt.cap_max > 0, the budget of Gaussians")
+        if is_fork(model):
+            raise ValueError("strategy='mcmc' does not support the fork's grow / learned-split models")
+        mk = dict(mcmc_kwargs or {})
+        unknown = set(mk) - {"generator", "draws", "noise"}
+        if unknown:
+            raise ValueError(f"mcmc_kwargs: unknown keys {sorted(unknown)}")
+    elif mcmc_kwargs is not None:
+        raise ValueError("mcmc_kwargs needs opt.strategy == 'mcmc'")
     if train_exposure and getattr(model, "exposure_optimizer", None) is None:
         raise ValueError("train_exposure=True needs model.setup_exposures(image names) before training_setup")
     flag = lambda name: bool(getattr(dataset, name, False))      # noqa: E731
@@ -116,12 +147,18 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
     loss = l1_dssim_loss(pkg["render"], gt.to(pkg["render"].device), opt.lambda_dssim)          # :99-101
     if opt.opacitysparse > 0:                                                                   # :102-106
         loss = loss + opacity_sparsity_loss(model._opacity, opt.opacitysparse)
+    if mcmc:
+        loss = loss + mcmc_regularizer(model._opacity, model._scaling, opt.opacity_reg, opt.scale_reg)
     if depth_loss is not None:
         depth_target, depth_weight = depth_loss
         loss = loss + float(depth_weight) * (pkg["invdepth"] - depth_target.to(pkg["invdepth"].device)).abs().mean()
     loss.backward()                                                                             # :107
     with torch.no_grad():
-        if todo["stats"]:                                                                       # :127-137
+        if mcmc:
+            if todo["densify"]:
+                relocate_gs(model, generator=mk.get("generator"), draws=mk.get("draws"))
+                add_new_gs(model, opt.cap_max, generator=mk.get("generator"), draws=mk.get("draws"))
+        elif todo["stats"]:                                                                     # :127-137
             add_densification_stats(model, pkg["viewspace_points"], pkg["radii"])
             if todo["densify"]:
                 densify_and_prune(model, opt.densify_grad_threshold, opt.min_opacity, cameras_extent,
@@ -136,10 +173,13 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
                 visibility = pkg["visibility_filter"]
                 if pkg["selected_pts_mask"] is not None:
                     visibility = visibility | pkg["selected_pts_mask"]
-                model.optimizer.step(visibility, dense=("opacity",) if opt.opacitysparse > 0 else ())
+                dense = ("opacity", "scaling") if mcmc else (("opacity",) if opt.opacitysparse > 0 else ())
+                model.optimizer.step(visibility, dense=dense)
             else:
                 model.optimizer.step()
             model.optimizer.zero_grad(set_to_none=True)
+            if mcmc:
+                inject_noise(model, opt.noise_lr, generator=mk.get("generator"), noise=mk.get("noise"))
             if train_exposure:
                 model.exposure_optimizer.step()
                 model.exposure_optimizer.zero_grad(set_to_none=True)
