@@ -34,7 +34,8 @@ from typing import Dict, Optional
 import torch
 
 from . import _lib
-from .rasterizer import GaussianRasterizationSettings, _make_params, _round_ws
+from ._frames import _round_ws, capacity_for
+from .rasterizer import GaussianRasterizationSettings, _make_params
 from .renderer import _can_fuse
 
 
@@ -120,7 +121,7 @@ class GraphedRenderer:
     def _capture(self, f: _Format, need: int) -> None:
         lib, dev = self.lib, self.dev
         H, W = f.settings.image_height, f.settings.image_width
-        f.capacity = (int(need * 1.5) + (1 << 20)) >> 20 << 20
+        f.capacity = capacity_for(need)
         nbytes = lib.gsr_binning_bytes(f.capacity, self.P, W, H, f.params.binning_mode)
         f.binning = torch.empty(_round_ws(nbytes), dtype=torch.uint8, device=dev)
         f.nbytes = nbytes
