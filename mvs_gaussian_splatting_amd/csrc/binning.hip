@@ -492,22 +492,38 @@ __global__ __launch_bounds__(256) void radix_rowscan_kernel(uint32_t* __restrict
   }
 }
 
-template <typename KeyT, typename ValT, int BITS, int ITEMS>
-__global__ __launch_bounds__(SORT_THREADS) void radix_scatter_kernel(
+// What the rider workgroup of the tile sort's last scatter needs besides the pass's own digit totals
+// (ranges_and_order_from_sort_body); the other scatters take the empty NoRider.
+struct RangesRider {
+  int tiles, lo_bits, hi_bits;
+  bool relative;
+  uint2* ranges;
+  uint32_t* order;
+};
+template <int THREADS>
+__device__ __forceinline__ void ranges_and_order_from_sort_body(int tiles, const uint32_t* __restrict__ totals_last,
+                                                                int lo_bits, int hi_bits, bool relative,
+                                                                uint2* __restrict__ ranges, uint32_t* __restrict__ order,
+                                                                uint32_t* cnt, uint32_t* base, uint8_t* s_code,
+                                                                uint32_t* digit_base);
+
+// RIDER (the last pass of the tile sort only; a compile-time flag, so that every other scatter compiles to the code it
+// had without it): the launch has one workgroup more, at block index 0 so that it is dispatched first, which scatters
+// nothing and derives the tile ranges and the tile order from what the row scan of this pass left behind (the digit totals
+// and the relative runs) -- work that reads nothing the scatter writes and used to wait for it in a launch of its own, one
+// workgroup on an otherwise idle device.  It shares nothing with the scattering blocks and does not look at the
+// device-side count: a frame without instances still gets its (0, 0) ranges and a full tile order.  Its LDS overlays the
+// exchange buffer.  Left to itself the compiler spends 104 VGPRs on the rider branch (the scatter needs 68: three
+// workgroups per CU); the second launch bound keeps the variant at the scatter's own count.
+struct NoRider {};
+template <typename KeyT, typename ValT, int BITS, int ITEMS, bool RIDER = false>
+__global__ __launch_bounds__(SORT_THREADS, RIDER ? 6 : 1) void radix_scatter_kernel(
     const KeyT* __restrict__ keys_in, const ValT* __restrict__ vals_in, KeyT* __restrict__ keys_out,
     ValT* __restrict__ vals_out, uint32_t n, const uint32_t* __restrict__ n_dev, int shift, uint32_t mask,
     uint32_t nblocks, const uint32_t* __restrict__ hist, const uint32_t* __restrict__ totals,
-    const uint32_t* __restrict__ seg_totals = nullptr, int seg_count = 0) {
+    const uint32_t* __restrict__ seg_totals, int seg_count, typename std::conditional<RIDER, RangesRider, NoRider>::type rider) {
   constexpr int RADIX = 1 << BITS;
   constexpr int NW = SORT_THREADS / WAVE;
-  if (n_dev) n = *n_dev;
-  uint32_t base = blockIdx.x * (SORT_THREADS * ITEMS);
-  if (seg_totals) {                                        // segmented pass: see seg_block
-    const SegBlock sb = seg_block(seg_totals, seg_count, blockIdx.x);
-    if (!sb.valid) return;
-    base = sb.base;
-    n = sb.base + sb.count;                                // the block's items end where its segment (or its 4096) ends
-  } else if (base >= n) return;   // block beyond the device-side count (uniform: no barrier crossed)
   using WideT = typename std::conditional<(sizeof(ValT) > sizeof(KeyT)), ValT, KeyT>::type;
   __shared__ WideT xbuf_w[(SORT_THREADS * ITEMS)];         // exchange buffer: keys first, then reused for the values
   KeyT* xbuf = reinterpret_cast<KeyT*>(xbuf_w);
@@ -515,6 +531,28 @@ __global__ __launch_bounds__(SORT_THREADS) void radix_scatter_kernel(
   __shared__ uint32_t digit_start[RADIX];     // first local slot of every digit
   __shared__ uint32_t global_base[RADIX];     // global position of the block's first item of the digit
   __shared__ uint32_t scan_tmp[NW];
+  uint32_t bid = blockIdx.x;
+  if constexpr (RIDER) {
+    if (bid == 0) {
+      // cnt[256] | base[256] | digit_base[gsr::RADIX + 1, padded to 4 words] | s_code[8 * SORT_THREADS bytes]
+      constexpr int DB_WORDS = (gsr::RADIX + 1 + 3) & ~3;
+      static_assert(sizeof(xbuf_w) >= 4 * (512 + DB_WORDS) + 8 * SORT_THREADS, "the rider's LDS must fit the exchange buffer");
+      uint32_t* w = reinterpret_cast<uint32_t*>(xbuf_w);
+      ranges_and_order_from_sort_body<SORT_THREADS>(rider.tiles, totals, rider.lo_bits, rider.hi_bits, rider.relative,
+                                                    rider.ranges, rider.order, w, w + 256,
+                                                    reinterpret_cast<uint8_t*>(w + 512 + DB_WORDS), w + 512);
+      return;
+    }
+    bid -= 1;
+  }
+  if (n_dev) n = *n_dev;
+  uint32_t base = bid * (SORT_THREADS * ITEMS);
+  if (seg_totals) {                                        // segmented pass: see seg_block
+    const SegBlock sb = seg_block(seg_totals, seg_count, bid);
+    if (!sb.valid) return;
+    base = sb.base;
+    n = sb.base + sb.count;                                // the block's items end where its segment (or its 4096) ends
+  } else if (base >= n) return;   // block beyond the device-side count (uniform: no barrier crossed)
 
   const int tid = threadIdx.x, lane = tid & (WAVE - 1), wid = tid / WAVE;
   const uint32_t wbase = base + wid * (WAVE * ITEMS);
@@ -611,7 +649,7 @@ __global__ __launch_bounds__(SORT_THREADS) void radix_scatter_kernel(
       for (int e = 0; e < BPT; ++e) {
         const int d = tid * BPT + e;
         digit_start[d] = excl;
-        global_base[d] = texcl + hist[(size_t)d * nblocks + blockIdx.x];
+        global_base[d] = texcl + hist[(size_t)d * nblocks + bid];
         excl += dsum[e];
         texcl += tot[e];
       }
@@ -771,15 +809,18 @@ __global__ __launch_bounds__(1024) void build_tile_order_kernel(int tiles, const
 //   two-pass sort with a segmented last pass (seg_block): the row scan of that pass left in ranges[t] the run of tile
 //     t = hi << lo_bits | lo RELATIVE to the first item with top digit hi; adding digit_base[hi] completes it.
 // An empty tile gets (0, 0), as in the zero-filled array upstream's identifyTileRanges writes into.
-__global__ __launch_bounds__(1024) void ranges_and_order_from_sort_kernel(int tiles, const uint32_t* __restrict__ totals_last,
-                                                                          int lo_bits, int hi_bits, bool relative,
-                                                                          uint2* __restrict__ ranges,
-                                                                          uint32_t* __restrict__ order) {
-  constexpr int CHUNK = 8 * 1024;
-  __shared__ uint32_t cnt[256];
-  __shared__ uint32_t base[256];
-  __shared__ uint8_t s_code[CHUNK];
-  __shared__ uint32_t digit_base[RADIX + 1];   // exclusive scan of the last pass's digit totals
+// One workgroup of THREADS lanes, eight consecutive tiles per lane and 8 * THREADS tiles per chunk: the stand-alone kernel
+// below (1024 lanes) and the rider workgroup of the tile sort's last scatter (radix_scatter_kernel with RIDER, SORT_THREADS lanes) run
+// this one body.  The caller owns the LDS: cnt[256], base[256], s_code[8 * THREADS], digit_base[RADIX + 1] (the exclusive
+// scan of the last pass's digit totals).  The ranges do not depend on THREADS; the order does, chunk by chunk.
+template <int THREADS>
+__device__ __forceinline__ void ranges_and_order_from_sort_body(int tiles, const uint32_t* __restrict__ totals_last,
+                                                                int lo_bits, int hi_bits, bool relative,
+                                                                uint2* __restrict__ ranges, uint32_t* __restrict__ order,
+                                                                uint32_t* cnt, uint32_t* base, uint8_t* s_code,
+                                                                uint32_t* digit_base) {
+  static_assert(THREADS >= 256 && THREADS % WAVE == 0, "cnt[] is cleared by the first 256 lanes");
+  constexpr int CHUNK = 8 * THREADS;
   const int tid = threadIdx.x, lane = tid & (WAVE - 1);
   const unsigned long long lt = (1ull << lane) - 1ull;
   const int nhi = 1 << hi_bits;
@@ -847,7 +888,7 @@ __global__ __launch_bounds__(1024) void ranges_and_order_from_sort_kernel(int ti
     }
     __syncthreads();
     const int n = min(CHUNK, tiles - c0);
-    for (int t0 = 0; t0 < n; t0 += 1024) {
+    for (int t0 = 0; t0 < n; t0 += THREADS) {
       const int t = t0 + tid;
       const bool ok = t < n;
       const uint32_t code = s_code[t0 + tid];
@@ -864,7 +905,7 @@ __global__ __launch_bounds__(1024) void ranges_and_order_from_sort_kernel(int ti
       for (int k = 0; k < 4; ++k) { base[4 * tid + k] = rr; rr += b[k]; }
     }
     __syncthreads();
-    for (int t0 = 0; t0 < n; t0 += 1024) {
+    for (int t0 = 0; t0 < n; t0 += THREADS) {
       const int t = t0 + tid;
       const bool ok = t < n;
       const uint32_t code = s_code[t0 + tid];
@@ -876,6 +917,18 @@ __global__ __launch_bounds__(1024) void ranges_and_order_from_sort_kernel(int ti
       if (ok) order[c0 + first + (uint32_t)__popcll(peers & lt)] = (uint32_t)(c0 + t);
     }
   }
+}
+__global__ __launch_bounds__(1024) void ranges_and_order_from_sort_kernel(int tiles, const uint32_t* __restrict__ totals_last,
+                                                                          int lo_bits, int hi_bits, bool relative,
+                                                                          uint2* __restrict__ ranges,
+                                                                          uint32_t* __restrict__ order) {
+  constexpr int CHUNK = 8 * 1024;
+  __shared__ uint32_t cnt[256];
+  __shared__ uint32_t base[256];
+  __shared__ uint8_t s_code[CHUNK];
+  __shared__ uint32_t digit_base[RADIX + 1];
+  ranges_and_order_from_sort_body<CHUNK / 8>(tiles, totals_last, lo_bits, hi_bits, relative, ranges, order, cnt, base, s_code,
+                                             digit_base);
 }
 
 void launch_duplicate_with_keys(int P, int grid_x, const BinInfo* bin, const uint32_t* block_offs, uint32_t* slot_base,
@@ -890,7 +943,7 @@ template <typename KeyT, typename ValT, int BITS>
 static void sort_pass(const KeyT* kin, const ValT* vin, KeyT* kout, ValT* vout, uint32_t n, const uint32_t* n_dev,
                       int shift, int nbits, const SortLayout& L, uint32_t* hist, uint32_t* totals, hipStream_t s,
                       const uint32_t* seg_totals = nullptr, int seg_count = 0, uint2* runs_rel = nullptr,
-                      int lo_bits = 0, uint32_t n_keys = 0) {
+                      int lo_bits = 0, uint32_t n_keys = 0, const RangesRider* rider = nullptr) {
   const uint32_t mask = (1u << nbits) - 1u;      // nbits <= BITS: digits above the mask do not occur
   // (8192-item tiles for 32-bit keys were measured: no gain once the digits are <= 8 bits wide)
   constexpr int ITEMS = SORT_ITEMS;
@@ -901,8 +954,15 @@ static void sort_pass(const KeyT* kin, const ValT* vin, KeyT* kout, ValT* vout, 
                      mask, nblocks, hist, seg_totals, seg_count);
   hipLaunchKernelGGL(radix_rowscan_kernel, dim3(1 << BITS), dim3(256), 0, s, hist, nblocks, totals, n_dev, seg_totals,
                      seg_count, runs_rel, lo_bits, n_keys);
+  if constexpr (std::is_same<KeyT, uint32_t>::value && std::is_same<ValT, uint32_t>::value) {
+    if (rider) {   // the tile sort's last pass: the ranges and the tile order are built by one workgroup more in this launch
+      hipLaunchKernelGGL((radix_scatter_kernel<KeyT, ValT, BITS, ITEMS, true>), dim3(nblocks + 1), dim3(SORT_THREADS), 0, s,
+                         kin, vin, kout, vout, n, n_dev, shift, mask, nblocks, hist, totals, seg_totals, seg_count, *rider);
+      return;
+    }
+  }
   hipLaunchKernelGGL((radix_scatter_kernel<KeyT, ValT, BITS, ITEMS>), dim3(nblocks), dim3(SORT_THREADS), 0, s, kin, vin, kout,
-                     vout, n, n_dev, shift, mask, nblocks, hist, totals, seg_totals, seg_count);
+                     vout, n, n_dev, shift, mask, nblocks, hist, totals, seg_totals, seg_count, NoRider{});
 }
 
 // Digit widths of the passes.  A block scatters 4096 items: with 2^w digits a digit's run leaves the block as
@@ -924,7 +984,7 @@ int sort_pass_plan(int end_bit, int widths[8]) {
 template <typename KeyT, typename ValT>
 static bool sort_pairs_impl(KeyT* keys_a, ValT* vals_a, KeyT* keys_b, ValT* vals_b, uint32_t n, int end_bit,
                             void* scratch, hipStream_t s, const uint32_t* n_dev = nullptr, SortedRuns* runs = nullptr) {
-  if (runs) runs->valid = false;
+  if (runs) { runs->valid = false; runs->fused = false; }
   if (n == 0 || end_bit <= 0) return false;
   // the rows of a segmented pass write one relative run per key value: every row must exist in the launch, i.e. the last
   // digit's kernels are instantiated for exactly its width -- true for the 6..9-bit kernels; narrower last digits run the
@@ -946,10 +1006,26 @@ static bool sort_pairs_impl(KeyT* keys_a, ValT* vals_a, KeyT* keys_b, ValT* vals
     uint2* rr = seg ? runs->runs_rel : nullptr;
     const int lb = widths[0];
     const uint32_t nk = seg ? runs->n_keys : 0u;
-    if (w <= 6)      sort_pass<KeyT, ValT, 6>(kin, vin, kout, vout, n, n_dev, shift, w, L, hist, totals, s, st, sc, rr, lb, nk);
-    else if (w == 7) sort_pass<KeyT, ValT, 7>(kin, vin, kout, vout, n, n_dev, shift, w, L, hist, totals, s, st, sc, rr, lb, nk);
-    else if (w == 8) sort_pass<KeyT, ValT, 8>(kin, vin, kout, vout, n, n_dev, shift, w, L, hist, totals, s, st, sc, rr, lb, nk);
-    else             sort_pass<KeyT, ValT, 9>(kin, vin, kout, vout, n, n_dev, shift, w, L, hist, totals, s, st, sc, rr, lb, nk);
+    // the last scatter of a sort that delivers runs carries the ranges-and-order rider when the caller gave an order
+    // array (SortedRuns::order); the values mirror what *runs is filled with below
+    RangesRider rd{};
+    const RangesRider* rp = nullptr;
+    if constexpr (std::is_same<KeyT, uint32_t>::value && std::is_same<ValT, uint32_t>::value) {     // the tile sort
+      if (runs && runs->order && passes <= 2 && pass == passes - 1) {
+        rd.tiles = (int)runs->n_keys;
+        rd.lo_bits = passes == 2 ? widths[0] : 0;
+        rd.hi_bits = w;
+        rd.relative = passes == 2;
+        rd.ranges = runs->runs_rel;
+        rd.order = runs->order;
+        rp = &rd;
+        runs->fused = true;
+      }
+    }
+    if (w <= 6)      sort_pass<KeyT, ValT, 6>(kin, vin, kout, vout, n, n_dev, shift, w, L, hist, totals, s, st, sc, rr, lb, nk, rp);
+    else if (w == 7) sort_pass<KeyT, ValT, 7>(kin, vin, kout, vout, n, n_dev, shift, w, L, hist, totals, s, st, sc, rr, lb, nk, rp);
+    else if (w == 8) sort_pass<KeyT, ValT, 8>(kin, vin, kout, vout, n, n_dev, shift, w, L, hist, totals, s, st, sc, rr, lb, nk, rp);
+    else             sort_pass<KeyT, ValT, 9>(kin, vin, kout, vout, n, n_dev, shift, w, L, hist, totals, s, st, sc, rr, lb, nk, rp);
     shift += w;
     KeyT* tk = kin; kin = kout; kout = tk;
     ValT* tv = vin; vin = vout; vout = tv;

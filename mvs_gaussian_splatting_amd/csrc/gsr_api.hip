@@ -269,12 +269,15 @@ static int enqueue_stage2(const GsrParams* p, void* geom_ws, void* bin_ws, size_
                           uint32_t r_cap, uint32_t v_cap, bool device_counts, float* out_color, hipStream_t s) {
   const ImageLayout I(p->width, p->height);
   uint2* ranges = at<uint2>(img_ws, I.ranges);
-  // two-level modes: the ranges come out of the tile sort's own histogram (launch_ranges_and_order_from_sort: no memset,
-  // no pass over the sorted keys); 64-bit key mode, or nothing to bin: upstream's identifyTileRanges into a zero-filled array
+  // two-level modes: the ranges come out of the tile sort's own histogram (no memset, no pass over the sorted keys), and
+  // they and the tile order are built by a workgroup that rides in the sort's last scatter launch (SortedRuns::order);
+  // 64-bit key mode, or nothing to bin: upstream's identifyTileRanges into a zero-filled array
   SortedRuns runs;
   runs.valid = false;
+  runs.fused = false;
   runs.runs_rel = ranges;
   runs.n_keys = (uint32_t)I.tiles;
+  runs.order = at<uint32_t>(img_ws, I.tile_order);
   const uint32_t* point_list = nullptr;
   uint16_t* inst_mask = nullptr;     // the sort's spare payload buffer (see SortedViews)
   const GeomRec* rec = nullptr;
@@ -358,7 +361,7 @@ static int enqueue_stage2(const GsrParams* p, void* geom_ws, void* bin_ws, size_
   } else {
     GSR_HIP(hipMemsetAsync(ranges, 0, 8 * (size_t)I.tiles, s));      // nothing to bin: every tile is empty
   }
-  {
+  if (!runs.fused) {     // fused: the ranges stage has no interval of its own (its stage count stays 0)
     StageTimer t(p, GSR_STAGE_RANGES, s);
     if (runs.valid) launch_ranges_and_order_from_sort(I.tiles, runs, ranges, at<uint32_t>(img_ws, I.tile_order), s);
     else launch_build_tile_order(I.tiles, ranges, at<uint32_t>(img_ws, I.tile_order), s);
@@ -786,8 +789,10 @@ int gsr_sort_tile_runs_u32(uint32_t* keys, uint32_t* vals, uint32_t* keys_tmp, u
   hipStream_t s = static_cast<hipStream_t>(stream);
   SortedRuns runs;
   runs.valid = false;
+  runs.fused = false;
   runs.runs_rel = static_cast<uint2*>(ranges);
   runs.n_keys = n_keys;
+  runs.order = nullptr;      // the raw entry keeps the stand-alone ranges-and-order kernel behind the sort
   *result_in_tmp = launch_sort_pairs_u32(keys, vals, keys_tmp, vals_tmp, capacity, end_bit, scratch, s, n_dev, &runs) ? 1 : 0;
   if (int rc = check(nullptr, s, "tile_sort")) return rc;
   *runs_valid = runs.valid ? 1 : 0;

@@ -38,11 +38,15 @@ bool launch_sort_pairs(uint64_t* keys_a, uint32_t* vals_a, uint64_t* keys_b, uin
                        int end_bit, void* scratch, hipStream_t s);
 // n_dev != NULL: the element count is read from device memory and n is the capacity the grid is sized for
 // In / out of a sort that also delivers where every key value's run lies in the sorted array, without a pass over it
-// (binning.hip: seg_block, radix_rowscan_kernel, ranges_and_order_from_sort_kernel).
+// (binning.hip: seg_block, radix_rowscan_kernel, ranges_and_order_from_sort_body).
 struct SortedRuns {
   uint2* runs_rel;               // in: [n_keys] array the last pass's row scan writes RELATIVE runs into (two-pass sorts)
   uint32_t n_keys;               // in: number of key values (tiles)
+  uint32_t* order;               // in: nullptr, or the [n_keys] tile order: the last scatter then carries a workgroup that
+                                 //     completes runs_rel into the tile ranges and fills order (ranges_and_order_from_sort_body)
   bool valid;                    // out: false = more than two passes (use identify_tile_ranges)
+  bool fused;                    // out: the ranges and the order are already enqueued (valid, and order was given): the
+                                 //      caller skips launch_ranges_and_order_from_sort
   bool relative;                 // out: runs_rel was written (two passes); false: one pass, the runs are the digit totals' scan
   const uint32_t* totals_last;   // out: digit totals of the last pass
   int lo_bits, hi_bits;          // out: digit widths of the first / last pass (lo_bits = 0: one pass)
