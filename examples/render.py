@@ -3,7 +3,7 @@ write every view of the scene as PNG.
 
     python examples/render.py -m <model directory> [--iteration N] [--skip_train] [--skip_test]
                               [-s <COLMAP or Blender directory>] [-r ...] [--eval] [--white_background] [--depth]
-                              [--use_trained_exp]
+                              [--use_trained_exp] [--normals]
 
 The dataset's location and options come from the ``cfg_args.json`` that ``examples/train.py -s ... -m ...`` left in the
 model directory; ``-s`` and the other switches override it.
@@ -13,6 +13,8 @@ writes ``<model>/<train|test>/ours_<N>/renders/%05d.png`` and ``.../gt/%05d.png`
 ``--depth`` also writes ``.../depth/%05d.png``: the expected depth ``depth / alpha`` of every pixel as a 16-bit
 greyscale PNG, scaled so that 65535 is the view's largest value (0 where nothing was composited); the scale of each
 view is listed in ``.../depth/scales.json`` (metres per step).
+``--normals`` also writes ``.../normal/%05d.png``: the view-space normal map ``sum w n`` of ``render(return_normals=True)``
+as ``normal * 0.5 + 0.5`` in 8 bits.
 ``--use_trained_exp`` renders every view that has one with the exposure saved in the iteration's ``exposure.json``
 (``examples/train.py --train_exposure``); test views have none and are rendered as they are.
 """
@@ -46,7 +48,7 @@ def save_depth_png(depth, alpha, path):
 
 
 def render_set(model_path, name, iteration, views, gaussians, pipeline, background, depth=False,
-               use_trained_exp=False):
+               use_trained_exp=False, normals=False):
     render_path = os.path.join(model_path, name, "ours_{}".format(iteration), "renders")
     gts_path = os.path.join(model_path, name, "ours_{}".format(iteration), "gt")
     depth_path = os.path.join(model_path, name, "ours_{}".format(iteration), "depth")
@@ -55,21 +57,27 @@ def render_set(model_path, name, iteration, views, gaussians, pipeline, backgrou
     scales = []
     if depth:
         os.makedirs(depth_path, exist_ok=True)
+    normal_path = os.path.join(model_path, name, "ours_{}".format(iteration), "normal")
+    if normals:
+        os.makedirs(normal_path, exist_ok=True)
     for idx, view in enumerate(views):
         with_exp = use_trained_exp and view.image_name in (gaussians.pretrained_exposures or {})
         pkg = render(view, gaussians, pipeline, background, **({"return_depth": True} if depth else {}),
-                     **({"use_trained_exp": True} if with_exp else {}))
+                     **({"use_trained_exp": True} if with_exp else {}), **({"return_normals": True} if normals else {}))
         rendering = pkg["render"]
         save_png(rendering, os.path.join(render_path, "{0:05d}".format(idx) + ".png"))
         save_png(view.original_image[0:3, :, :].to(rendering.device), os.path.join(gts_path, "{0:05d}".format(idx) + ".png"))
         if depth:
             scales.append(save_depth_png(pkg["depth"], pkg["alpha"], os.path.join(depth_path, "{0:05d}".format(idx) + ".png")))
+        if normals:
+            save_png(pkg["normal"] * 0.5 + 0.5, os.path.join(normal_path, "{0:05d}".format(idx) + ".png"))
     if depth:
         with open(os.path.join(depth_path, "scales.json"), "w") as f:
             json.dump(scales, f)
 
 
-def render_sets(dataset, iteration, pipeline, skip_train=False, skip_test=False, depth=False, use_trained_exp=False):
+def render_sets(dataset, iteration, pipeline, skip_train=False, skip_test=False, depth=False, use_trained_exp=False,
+                normals=False):
     with torch.no_grad():
         gaussians = GaussianModel(dataset.sh_degree)
         scene = Scene(dataset, gaussians, load_iteration=iteration, shuffle=False)
@@ -79,10 +87,10 @@ def render_sets(dataset, iteration, pipeline, skip_train=False, skip_test=False,
             raise FileNotFoundError("--use_trained_exp: the iteration's point-cloud directory has no exposure.json")
         if not skip_train:
             render_set(dataset.model_path, "train", scene.loaded_iter, scene.getTrainCameras(), gaussians, pipeline,
-                       background, depth, use_trained_exp)
+                       background, depth, use_trained_exp, normals)
         if not skip_test:
             render_set(dataset.model_path, "test", scene.loaded_iter, scene.getTestCameras(), gaussians, pipeline,
-                       background, depth, use_trained_exp)
+                       background, depth, use_trained_exp, normals)
     return scene
 
 
@@ -98,6 +106,7 @@ def main(argv=None):
     ap.add_argument("--skip_train", action="store_true")
     ap.add_argument("--skip_test", action="store_true")
     ap.add_argument("--depth", action="store_true", help="also write depth / alpha of every view as a 16-bit PNG")
+    ap.add_argument("--normals", action="store_true", help="also write the view-space normal map of every view as PNG")
     ap.add_argument("--use_trained_exp", action="store_true", help="apply the saved per-image exposures")
     args = ap.parse_args(argv)
     fields = {}
@@ -113,7 +122,7 @@ def main(argv=None):
     dataset = ModelParams(model_path=args.model_path, **fields)
     print("Rendering " + args.model_path)
     render_sets(dataset, args.iteration, PipelineParams(), args.skip_train, args.skip_test, args.depth,
-                args.use_trained_exp)
+                args.use_trained_exp, args.normals)
 
 
 if __name__ == "__main__":

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 25
+#define GSR_ABI_VERSION 26
 
 enum {
   GSR_OK = 0,
@@ -249,6 +249,24 @@ int gsr_aux_maps_forward(const GsrAuxFrame* frame, float* maps, void* stream);
 size_t gsr_aux_maps_backward_bytes(int32_t P);
 int gsr_aux_maps_backward(const GsrParams* p, const GsrAuxFrame* frame, const float* dL_dmaps, void* acc_ws,
                           size_t acc_ws_bytes, const GsrAuxGrads* grads, void* stream);
+
+/* ---- per-Gaussian feature vectors composited to C-channel maps of a rendered frame, ABI v26 (csrc/features.hip) -------
+ * With i, w_i as above (the entries and weights of the depth / alpha maps) and features a device [P,C] float array,
+ * contiguous and row-major, C >= 1:
+ *     maps[c] = sum_i w_i features[id_i][c],   c = 0 .. C-1          (no background term, no clamp)
+ * Kernels of their own; the frame is only read.  maps: device [C,H,W], written in full, the same bits
+ * from run to run. */
+int gsr_feature_maps_forward(const GsrAuxFrame* frame, const float* features, int32_t C, float* maps, void* stream);
+/* p: the inputs of the frame's forward, as for gsr_aux_maps_backward.  dL_dmaps: device [C,H,W].
+ * dL_dfeatures: device [P,C], written in full (zero-filled, then added into with float atomics); NULL: not wanted.
+ * grads: the geometry gradients of the maps, as gsr_aux_maps_backward writes them; NULL: the feature gradient only -- the
+ * per-Gaussian geometry kernel is not launched and acc_ws may be NULL.
+ * acc_ws: device scratch of gsr_feature_maps_backward_bytes(P) bytes, 256-byte aligned (the [P,8] accumulator of
+ * gsr_aux_maps_backward; its d z word stays 0).  Gradients are reproducible to rounding, not bit for bit. */
+size_t gsr_feature_maps_backward_bytes(int32_t P);
+int gsr_feature_maps_backward(const GsrParams* p, const GsrAuxFrame* frame, const float* features, int32_t C,
+                              const float* dL_dmaps, float* dL_dfeatures, void* acc_ws, size_t acc_ws_bytes,
+                              const GsrAuxGrads* grads, void* stream);
 
 /* ---- per-Gaussian contribution statistics of a rendered frame, ABI v24 (csrc/contribution.hip) ----------------------
  * For Gaussian g let p run over the pixels where the colour pass composited g (the rule above: the first n_contrib

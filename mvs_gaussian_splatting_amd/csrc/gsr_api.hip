@@ -641,6 +641,72 @@ int gsr_aux_maps_backward(const GsrParams* p, const GsrAuxFrame* f, const float*
   return check(p, s, "aux_geom_bwd");
 }
 
+// ---- per-Gaussian feature vectors composited to C-channel maps (csrc/features.hip) ---------------------------------
+static int validate_features(const float* features, int32_t C) {
+  if (C < 1) return fail(GSR_E_BADARG, "C must be >= 1");
+  if (C > 8 * 65535) return fail(GSR_E_BADARG, "C too large (65535 channel groups)");
+  if (!features) return fail(GSR_E_BADARG, "features is NULL");
+  return 0;
+}
+
+size_t gsr_feature_maps_backward_bytes(int32_t P) { return gsr_aux_maps_backward_bytes(P); }
+
+int gsr_feature_maps_forward(const GsrAuxFrame* f, const float* features, int32_t C, float* maps, void* stream) {
+  if (int rc = validate_aux_frame(f)) return rc;
+  if (int rc = validate_features(features, C)) return rc;
+  if (!maps) return fail(GSR_E_BADARG, "maps is NULL");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const ImageLayout I(f->width, f->height);
+  if (f->P == 0 || f->num_rendered == 0) {      // nothing was binned: every list is empty
+    GSR_HIP(hipMemsetAsync(maps, 0, 4 * (size_t)C * f->width * f->height, s));
+    return 0;
+  }
+  const GeomLayout L(f->P);
+  const SortedViews sv = sorted_views(f->bin_ws, f->num_rendered, f->num_visible, f->width, f->height, f->binning_mode);
+  launch_feature_maps_fwd(f->width, f->height, at<uint2>(f->img_ws, I.ranges), sv.point_list,
+                          at<GeomRec>(f->geom_ws, L.rec), at<uint32_t>(f->img_ws, I.n_contrib),
+                          at<uint32_t>(f->img_ws, I.tile_order), features, C, maps, s);
+  return check(nullptr, s, "feature_maps_fwd");
+}
+
+int gsr_feature_maps_backward(const GsrParams* p, const GsrAuxFrame* f, const float* features, int32_t C,
+                              const float* dL_dmaps, float* dL_dfeatures, void* acc_ws, size_t acc_ws_bytes,
+                              const GsrAuxGrads* g, void* stream) {
+  if (!p) return fail(GSR_E_BADARG, "params is NULL");
+  if (p->forward_only) return fail(GSR_E_BADARG, "the forward ran with forward_only = 1: no state for a backward");
+  if (int rc = validate_aux_frame(f)) return rc;
+  if (int rc = validate_features(features, C)) return rc;
+  if (f->P != p->P || f->width != p->width || f->height != p->height) return fail(GSR_E_BADARG, "frame and params disagree");
+  if (p->P == 0 || (!g && !dL_dfeatures)) return 0;
+  if (!dL_dmaps) return fail(GSR_E_BADARG, "dL_dmaps is NULL");
+  float* acc = nullptr;
+  if (g) {
+    if (int rc = validate_aux_inputs(p)) return rc;
+    if (!acc_ws || !f->radii) return fail(GSR_E_BADARG, "NULL workspace / input");
+    if (!g->dL_dmeans3D || !g->dL_dmeans2D || !g->dL_dopacities)
+      return fail(GSR_E_BADARG, "dL_dmeans3D / dL_dmeans2D / dL_dopacities must be non-NULL");
+    if (acc_ws_bytes < gsr_feature_maps_backward_bytes(p->P)) return fail(GSR_E_CAPACITY, "accumulator workspace too small");
+    if (((uintptr_t)acc_ws & 255u) != 0) return fail(GSR_E_ALIGN, "acc_ws must be 256-byte aligned");
+    acc = static_cast<float*>(acc_ws);
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const ImageLayout I(f->width, f->height);
+  const GeomLayout L(f->P);
+  if (acc) GSR_HIP(hipMemsetAsync(acc, 0, 32 * (size_t)p->P, s));
+  if (dL_dfeatures) GSR_HIP(hipMemsetAsync(dL_dfeatures, 0, 4 * (size_t)p->P * (size_t)C, s));
+  if (f->num_rendered > 0) {
+    const SortedViews sv = sorted_views(f->bin_ws, f->num_rendered, f->num_visible, f->width, f->height, f->binning_mode);
+    launch_feature_maps_bwd(f->width, f->height, at<uint2>(f->img_ws, I.ranges), sv.point_list,
+                            at<GeomRec>(f->geom_ws, L.rec), at<uint32_t>(f->img_ws, I.n_contrib),
+                            at<float>(f->img_ws, I.final_T), at<uint32_t>(f->img_ws, I.tile_order), features, C, dL_dmaps,
+                            acc, dL_dfeatures, s);
+    if (int rc = check(p, s, "feature_maps_bwd")) return rc;
+  }
+  if (!g) return 0;
+  launch_aux_geom_bwd(*p, f->radii, acc, *g, s);
+  return check(p, s, "aux_geom_bwd");
+}
+
 // ---- per-Gaussian contribution statistics (csrc/contribution.hip) --------------------------------------------------
 int gsr_contribution_accumulate(const GsrAuxFrame* f, const uint8_t* pixel_mask, int64_t* stats, void* stream) {
   if (int rc = validate_aux_frame(f)) return rc;

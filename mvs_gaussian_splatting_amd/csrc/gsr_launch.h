@@ -112,6 +112,17 @@ void launch_aux_maps_bwd(int W, int H, const uint2* ranges, const uint32_t* poin
                          const float* dL_dmaps, float* acc, hipStream_t s);
 void launch_aux_geom_bwd(const GsrParams& p, const int32_t* radii, const float* acc, const GsrAuxGrads& g, hipStream_t s);
 
+// features.hip: per-Gaussian feature rows features[P,C] composited to C-channel maps of a rendered frame (the entries and
+// weights of depth.hip), and the backward: geometry sums into acc [P,8] (the layout launch_aux_geom_bwd reads; nullptr:
+// not wanted), dL/dfeatures added into dL_dfeatures [P,C] (zeroed by the caller; nullptr: not wanted)
+void launch_feature_maps_fwd(int W, int H, const uint2* ranges, const uint32_t* point_list, const GeomRec* rec,
+                             const uint32_t* n_contrib, const uint32_t* tile_order, const float* features, int C,
+                             float* out, hipStream_t s);
+void launch_feature_maps_bwd(int W, int H, const uint2* ranges, const uint32_t* point_list, const GeomRec* rec,
+                             const uint32_t* n_contrib, const float* final_T, const uint32_t* tile_order,
+                             const float* features, int C, const float* dL_dmaps, float* acc, float* dL_dfeatures,
+                             hipStream_t s);
+
 // contribution.hip: per-Gaussian blending-weight statistics of a rendered frame, added into stats [P,3] (int64: sum of
 // round(w 2^30), pixel count, float bits of the largest w) with integer atomics; pixel_mask: nullptr or [H,W] bytes
 void launch_contribution(int W, int H, const uint2* ranges, const uint32_t* point_list, const GeomRec* rec,

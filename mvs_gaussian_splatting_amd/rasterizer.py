@@ -30,6 +30,12 @@ object with ``raw`` -- int64 ``[P,3]`` on the device -- and ``views``) adds the 
 statistics into ``stats.raw`` after the colour forward (``csrc/contribution.hip``) and counts the view;
 ``contribution_mask`` (uint8 ``[H,W]``) leaves pixels out.  Nothing enters the autograd graph, and the call's results are
 what they are without it.  Without ``contribution`` nothing of it runs.
+
+Feature maps.  ``forward(..., features=F)`` with ``F`` float32 ``[P,C]`` (any C >= 1) appends ``feat [C,H,W]`` =
+``sum w F[id]`` to the call's results (after ``aux`` when ``aux_maps=True``): the per-Gaussian rows composited with the
+colour pass's blending weights, no background term, no clamp (``csrc/features.hip``), behind a third
+autograd node (``_FeatureMaps``) that reads the colour node's frame and returns gradients for ``F`` and the geometry.
+Without ``features`` nothing of it runs.
 """
 from __future__ import annotations
 
@@ -553,6 +559,125 @@ def _aux_maps_of(node, grad: bool, means3D, means2D, opacities, scales, rotation
                             raster_settings, frame, mode, act_flags)
 
 
+class _FeatureMaps(torch.autograd.Function):
+    """``feat [C,H,W] = sum w features[id]`` of a frame the colour operator has rendered (``include/gsr.h``:
+    gsr_feature_maps_*; ``csrc/features.hip``).  A node of its own next to the colour node, built like ``_AuxMaps``: it
+    reads the colour node's frame and returns the maps' own gradients for ``features`` and for means3D, means2D,
+    opacities and scales / rotations or cov3D_precomp.  Only the side ``ctx.needs_input_grad`` asks for is computed."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, opacities, scales, rotations, cov3Ds_precomp, features,
+                raster_settings: GaussianRasterizationSettings, frame: _Frame, binning_mode: int, act_flags: int = 0):
+        lib = _lib.load()
+        dev = _require_gpu(means3D)
+        P = int(means3D.shape[0])
+        means3D = _f32c(means3D, "means3D", dev)
+        opacities = _f32c(opacities, "opacities", dev)
+        scales = _f32c(scales, "scales", dev)
+        rotations = _f32c(rotations, "rotations", dev, align16=True)
+        cov3Ds_precomp = _f32c(cov3Ds_precomp, "cov3D_precomp", dev)
+        features = _f32c(features, "features", dev)
+        n_ch = int(features.shape[1])
+        H, W = int(raster_settings.image_height), int(raster_settings.image_width)
+        maps = torch.empty(n_ch, H, W, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            if P == 0:
+                maps.zero_()        # no row to point at: nothing was binned
+            else:
+                _lib.check(lib.gsr_feature_maps_forward(C.byref(_aux_frame(frame, P, W, H, binning_mode)),
+                                                        features.data_ptr(), n_ch, maps.data_ptr(), _stream(dev)),
+                           "gsr_feature_maps_forward")
+        ctx.raster_settings = raster_settings
+        ctx.layout = (frame.layout_R, frame.layout_V)
+        ctx.frame_pending = frame.pending
+        ctx.counts = frame.counts
+        ctx.binning_mode = binning_mode
+        ctx.act_flags = int(act_flags)
+        ctx.has_means2D = means2D is not None
+        ctx.save_for_backward(means3D, opacities, scales, rotations, cov3Ds_precomp, features, frame.radii, frame.geom,
+                              frame.binning, frame.img)
+        return maps
+
+    @staticmethod
+    def backward(ctx, grad_maps):
+        if grad_maps is None:
+            return (None,) * 11
+        need = ctx.needs_input_grad
+        want_geom, want_feat = any(need[:6]), bool(need[6])
+        if not (want_geom or want_feat):
+            return (None,) * 11
+        lib = _lib.load()
+        saved = ctx.saved_tensors
+        means3D, opacities, scales, rotations, cov3Ds_precomp, features = saved[:6]
+        frame, binning_mode = _frame_of(ctx, saved)
+        settings = ctx.raster_settings
+        dev = means3D.device
+        P, n_ch = int(means3D.shape[0]), int(features.shape[1])
+        H, W = int(settings.image_height), int(settings.image_width)
+        if frame.pending is not None:
+            _verify(frame.pending, block=True)      # deferred mode: as the colour backward
+        grad_maps = _f32c(grad_maps, "grad_maps", dev)
+        empty = torch.empty(0, dtype=torch.float32, device=dev)
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
+        g_means3D = g_means2D = g_opac = g_scales = g_rot = g_cov = g_feat = acc = grads = None
+        nbytes = 0
+        with torch.cuda.device(dev):
+            params, keep = _make_params(dev, settings, means3D, empty, empty, opacities, scales, rotations,
+                                        cov3Ds_precomp, act_flags=ctx.act_flags)
+            params.profile = None
+            params.binning_mode = binning_mode
+            if want_geom:
+                g_means3D, g_means2D, g_opac = new(P, 3), new(P, 3), new(*opacities.shape)
+                g_scales, g_rot, g_cov = (new(P, n) if t.numel() else None
+                                          for t, n in ((scales, 3), (rotations, 4), (cov3Ds_precomp, 6)))
+                grads = _lib.GsrAuxGrads(_ptr(g_means3D), _ptr(g_means2D), _ptr(g_opac), _ptr(g_scales), _ptr(g_rot),
+                                         _ptr(g_cov))
+                nbytes = lib.gsr_feature_maps_backward_bytes(P)
+                acc = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            if want_feat:
+                g_feat = new(P, n_ch)
+            if P > 0:
+                _lib.check(lib.gsr_feature_maps_backward(
+                    C.byref(params), C.byref(_aux_frame(frame, P, W, H, binning_mode)), features.data_ptr(), n_ch,
+                    grad_maps.data_ptr(), _ptr(g_feat), _ptr(acc), nbytes, None if grads is None else C.byref(grads),
+                    _stream(dev)), "gsr_feature_maps_backward")
+        del keep
+        return (g_means3D, g_means2D if ctx.has_means2D else None, g_opac, g_scales, g_rot, g_cov, g_feat, None, None,
+                None, None)
+
+
+def _feature_maps_of(node, grad: bool, features, means3D, means2D, opacities, scales, rotations, cov3Ds_precomp,
+                     raster_settings, act_flags: int = 0):
+    frame, mode = _frame_of(node)
+    if grad:
+        return _FeatureMaps.apply(means3D, means2D, opacities, scales, rotations, cov3Ds_precomp, features,
+                                  raster_settings, frame, mode, act_flags)
+    with torch.no_grad():
+        return _FeatureMaps.forward(_NoGraph(), means3D, means2D, opacities, scales, rotations, cov3Ds_precomp,
+                                    features, raster_settings, frame, mode, act_flags)
+
+
+def _check_feature_request(features, means3D, cam, state_key=None, densify_stats=None) -> None:
+    """The refusals of a ``features=F`` request, before anything is enqueued (and before a GPU is asked for)."""
+    if densify_stats is not None:
+        raise ValueError("features cannot be combined with densify_stats: the in-backward statistics would see the "
+                         "colour node's dL/dmeans2D alone, without the feature maps' share (take them from the summed "
+                         "means2D.grad after the backward)")
+    if cam:
+        raise ValueError("features cannot be combined with camera tensors that require grad: the feature maps have no "
+                         "camera gradients (detach viewmatrix / projmatrix / campos, or render the maps in a frame of "
+                         "their own)")
+    if state_key is not None:
+        raise ValueError("features are not available on a frame with grown / split rows appended")
+    P = int(means3D.shape[0])
+    if not isinstance(features, torch.Tensor) or features.dtype != torch.float32 or features.dim() != 2 or \
+            int(features.shape[0]) != P or int(features.shape[1]) < 1:
+        raise ValueError(f"features must be a float32 [P={P}, C>=1] tensor, got "
+                         f"{getattr(features, 'dtype', type(features).__name__)} {list(getattr(features, 'shape', ()))}")
+    if features.device != means3D.device:
+        raise ValueError(f"features is on {features.device}, expected {means3D.device}")
+
+
 def _check_aux_request(cam, state_key=None, densify_stats=None) -> None:
     if densify_stats is not None:
         raise ValueError("aux_maps=True cannot be combined with densify_stats: the in-backward statistics would see the "
@@ -603,65 +728,83 @@ def _accumulate_contribution(node, stats, mask, means3D, settings) -> None:
     stats.views += 1
 
 
-def _with_frame_outputs(color, radii, node, grad: bool, geometry, aux_maps, contribution, contribution_mask):
-    """The results of a frame that kept its state: the statistics are accumulated, the maps appended when asked for."""
+def _with_frame_outputs(color, radii, node, grad: bool, geometry, aux_maps, contribution, contribution_mask,
+                        features=None, grad_features: bool = False):
+    """The results of a frame that kept its state: the statistics are accumulated, the maps appended when asked for
+    (``aux``, then ``feat``).  ``grad``: the colour node is an autograd node; ``grad_features``: the feature maps get a
+    node although the colour forward ran outside autograd (only ``features`` requires grad)."""
     if contribution is not None:
         _accumulate_contribution(node, contribution, contribution_mask, geometry[0], geometry[6])
+    out = (color, radii)
     if aux_maps:
-        return color, radii, _aux_maps_of(node, grad, *geometry)
-    return color, radii
+        out += (_aux_maps_of(node, grad, *geometry),)
+    if features is not None:
+        out += (_feature_maps_of(node, grad or grad_features, features, *geometry),)
+    return out
 
 
 def _rasterize(fn, tensors, raster_settings, tail, geometry, densify_stats, aux_maps, contribution, contribution_mask,
-               state_key=None):
+               state_key=None, features=None):
     """One frame through the colour operator ``fn``.  ``tensors``: its forward's arguments in front of ``raster_settings``;
     ``tail``: those between ``stats`` and the camera's; ``geometry``: the arguments of ``_aux_maps_of`` after ``grad``
-    when ``aux_maps`` or ``contribution`` ask for the frame's state, else None."""
+    when ``aux_maps``, ``contribution`` or ``features`` ask for the frame's state, else None."""
     cam = _camera_inputs(raster_settings)
     if aux_maps:
         _check_aux_request(cam, state_key, densify_stats)
+    if features is not None:
+        _check_feature_request(features, tensors[0], cam, state_key, densify_stats)
     if contribution is not None:
         _check_contribution_request(contribution, contribution_mask, tensors[0], raster_settings, state_key)
     if _forward_only(*tensors, *cam):
+        grad_features = features is not None and not _forward_only(features)
         with torch.no_grad():
             if geometry is None:
                 return fn.forward(_NoGraph(), *tensors, raster_settings, True, None, *tail)
-            # the frame runs with forward_only = 0, here and below: both requests read the state only a forward that
+            # the frame runs with forward_only = 0, here and below: the requests read the state only a forward that
             node = _KeepFrame()     # tracks its contributors leaves
             color, radii = fn.forward(node, *tensors, raster_settings, False, None, *tail)
-            return _with_frame_outputs(color, radii, node, False, geometry, aux_maps, contribution, contribution_mask)
+            if not grad_features:
+                return _with_frame_outputs(color, radii, node, False, geometry, aux_maps, contribution,
+                                           contribution_mask, features)
+            head = _with_frame_outputs(color, radii, node, False, geometry, aux_maps, contribution, contribution_mask)
+        # only ``features`` requires grad: its node is built with grad mode as the caller has it
+        return head + (_feature_maps_of(node, True, features, *geometry),)
     out = fn.apply(*tensors, raster_settings, False, densify_stats, *tail, *cam)
     if geometry is None:
         return out
-    return _with_frame_outputs(*out, out[0].grad_fn, True, geometry, aux_maps, contribution, contribution_mask)
+    return _with_frame_outputs(*out, out[0].grad_fn, True, geometry, aux_maps, contribution, contribution_mask, features)
 
 
 def rasterize_gaussians_fused(means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations, raster_settings,
                               densify_stats=None, visible=None, _state_key=None, aux_maps=False, contribution=None,
-                              contribution_mask=None):
+                              contribution_mask=None, features=None):
     """``densify_stats``: None, or (xyz_gradient_accum, denom, max_radii2D) -- the backward then also accumulates the
     densification statistics of ``scene/gaussian_model.py:775-777`` / ``train.py:130``.
     ``visible``: None, or a bool [P] tensor that receives ``radii > 0`` from the preprocess kernel.
     ``_state_key`` (internal): the capacity state of grown frames (``_grown_key``) instead of the one of P rows.
     ``aux_maps``: also return the depth / inverse-depth / alpha maps ``[3,H,W]`` (``_AuxMaps``) as a third result.
-    ``contribution`` / ``contribution_mask``: accumulate the frame's contribution statistics (module docstring)."""
+    ``contribution`` / ``contribution_mask``: accumulate the frame's contribution statistics (module docstring).
+    ``features``: float32 ``[P,C]``; also return ``feat [C,H,W] = sum w features[id]`` (``_FeatureMaps``) as the last result."""
     geometry = None
-    if aux_maps or contribution is not None:
+    if aux_maps or contribution is not None or features is not None:
         empty = torch.empty(0, dtype=torch.float32, device=means3D.device)
         flags = _lib.ACT_SCALE_EXP | _lib.ACT_ROT_NORMALIZE | _lib.ACT_OPACITY_SIGMOID
         geometry = (means3D, means2D, raw_opacity, raw_scales, raw_rotations, empty, raster_settings, flags)
     return _rasterize(_RasterizeGaussiansFused,
                       (means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations), raster_settings,
-                      (visible, _state_key), geometry, densify_stats, aux_maps, contribution, contribution_mask, _state_key)
+                      (visible, _state_key), geometry, densify_stats, aux_maps, contribution, contribution_mask, _state_key,
+                      features)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, densify_stats=None, aux_maps=False, contribution=None, contribution_mask=None):
+                        raster_settings, densify_stats=None, aux_maps=False, contribution=None, contribution_mask=None,
+                        features=None):
     geometry = (means3D, means2D, opacities, scales, rotations, cov3Ds_precomp, raster_settings) \
-        if aux_maps or contribution is not None else None
+        if aux_maps or contribution is not None or features is not None else None
     return _rasterize(_RasterizeGaussians,
                       (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp),
-                      raster_settings, (), geometry, densify_stats, aux_maps, contribution, contribution_mask)
+                      raster_settings, (), geometry, densify_stats, aux_maps, contribution, contribution_mask,
+                      features=features)
 
 
 class GaussianRasterizer(nn.Module):
@@ -694,7 +837,9 @@ class GaussianRasterizer(nn.Module):
         return vis.bool()
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, densify_stats=None):
+                cov3D_precomp=None, densify_stats=None, features=None):
+        """``features``: float32 ``[P,C]``, C >= 1: the call's results gain a trailing ``feat [C,H,W] = sum w features[id]``
+        (after ``aux`` when ``aux_maps=True``), differentiable in ``features`` and the geometry inputs."""
         raster_settings = self.raster_settings
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")
@@ -709,10 +854,13 @@ class GaussianRasterizer(nn.Module):
         cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                    cov3D_precomp, raster_settings, densify_stats, aux_maps=self.aux_maps,
-                                   contribution=self.contribution, contribution_mask=self.contribution_mask)
+                                   contribution=self.contribution, contribution_mask=self.contribution_mask,
+                                   features=features)
 
-    def forward_fused(self, means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations, densify_stats=None):
+    def forward_fused(self, means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations, densify_stats=None,
+                      features=None):
         """Raw-parameter entry: see :class:`_RasterizeGaussiansFused`."""
         return rasterize_gaussians_fused(means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations,
                                          self.raster_settings, densify_stats, aux_maps=self.aux_maps,
-                                         contribution=self.contribution, contribution_mask=self.contribution_mask)
+                                         contribution=self.contribution, contribution_mask=self.contribution_mask,
+                                         features=features)

@@ -17,6 +17,7 @@ import torch
 
 from . import grow
 from .exposure import apply_exposure
+from .features import gaussian_normals
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, _grown_key, rasterize_gaussians_fused
 from .sh import eval_sh
 
@@ -92,7 +93,7 @@ def _settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier):
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier: float = 1.0,
            override_color=None, grow_dir=False, densify_grad_threshold=0, iteration=None, opt=None,
            continous_dir=False, grow_distance=False, modelcg=None, cameras_extent=None, return_depth=False,
-           use_trained_exp=False, contribution=None, contribution_mask=None):
+           use_trained_exp=False, contribution=None, contribution_mask=None, features=None, return_normals=False):
     """Render the scene; ``bg_color`` must be on the GPU.  Returns the reference's result dict
     (``gaussian_renderer/__init__.py:309-313``).  The keyword arguments after ``override_color`` are the reference's
     (``:19``) and drive the grow / learned-split branch (module docstring); the frame of a closed branch is unchanged.
@@ -116,10 +117,17 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier:
     ``contribution=stats`` (a ``contribution.ContributionStats`` with one row per Gaussian): the frame's per-Gaussian
     blending-weight statistics are added into ``stats`` after the colour forward and ``stats.views`` counts the frame;
     ``contribution_mask`` (uint8 ``[H,W]``) leaves the pixels with value 0 out.  Not differentiable; the result dict is
-    what it is without it.  Not available on a frame of the open grow / learned-split branch."""
+    what it is without it.  Not available on a frame of the open grow / learned-split branch.
+
+    ``features=F`` (float32 ``[P,C]``, C >= 1): the dict gains ``"features"`` ``[C,H,W]`` = ``sum w F[id]``, the rows of
+    ``F`` composited with the colour pass's blending weights (no background term, no clamp), differentiable in ``F`` and
+    the geometry.  ``return_normals=True``: the dict gains ``"normal"`` ``[3,H,W]`` = ``sum w n``, un-normalised, with
+    ``n = features.gaussian_normals(pc.get_scaling, pc.get_rotation, ...)`` the view-space normals; with both, one
+    concatenated call is split afterwards.  As with ``return_depth`` the in-backward densification statistics are not
+    taken on such a frame, and it is refused on the open grow / learned-split branch."""
     pkg = _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, grow_dir,
                   densify_grad_threshold, iteration, opt, continous_dir, grow_distance, modelcg, cameras_extent,
-                  return_depth, contribution, contribution_mask)
+                  return_depth, contribution, contribution_mask, features, return_normals)
     if use_trained_exp:
         pkg["render"] = apply_exposure(pkg["render"], pc.get_exposure_from_name(viewpoint_camera.image_name))
     return pkg
@@ -127,7 +135,7 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier:
 
 def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, grow_dir, densify_grad_threshold,
             iteration, opt, continous_dir, grow_distance, modelcg, cameras_extent, return_depth, contribution=None,
-            contribution_mask=None):
+            contribution_mask=None, features=None, return_normals=False):
     """The frame of ``render`` as the rasterizer leaves it."""
     which = grow.branch(iteration, opt, grow_dir, continous_dir, modelcg)
     if which is not None and contribution is not None:
@@ -137,6 +145,10 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
     extra_stats = {} if contribution is None else {"contribution": contribution, "contribution_mask": contribution_mask}
     if which is not None and return_depth:
         raise ValueError("return_depth=True is not available on a frame of the open grow / learned-split branch "
+                         "(virtual rows appended): render the maps in a frame of their own")
+    want_feat = features is not None or return_normals
+    if which is not None and want_feat:
+        raise ValueError("features / return_normals are not available on a frame of the open grow / learned-split branch "
                          "(virtual rows appended): render the maps in a frame of their own")
     if which is not None:
         return _render_grown(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, which, grow_dir,
@@ -148,30 +160,48 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
     # The operator never reads (or writes) its values, so every frame's leaf aliases one cached block of zeros: a
     # fresh 72 MB memset per frame is 20 us of the 6 M-Gaussian forward.
     screenspace_points = _zero_leaf(xyz)
-    stats = None if return_depth else _fused_stats(pc, pipe, xyz)
+    stats = None if return_depth or want_feat else _fused_stats(pc, pipe, xyz)
     if stats is not None:
         screenspace_points._gsr_stats_fused = True      # read by losses.add_densification_stats
 
     raster_settings = _settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier)
+    if want_feat:
+        rows = [] if features is None else [features]
+        if return_normals:
+            rows.append(gaussian_normals(pc.get_scaling, pc.get_rotation, xyz, raster_settings.viewmatrix,
+                                         raster_settings.campos))
+        extra_stats = dict(extra_stats, features=rows[0] if len(rows) == 1 else torch.cat(rows, dim=1))
+
+    def feature_entries(feat):
+        """The operator's trailing ``feat`` as the dict's ``"features"`` / ``"normal"`` entries."""
+        if not want_feat:
+            return {}
+        n_user = 0 if features is None else int(features.shape[1])
+        out = {} if features is None else {"features": feat[:n_user]}
+        if return_normals:
+            out["normal"] = feat[n_user:]
+        return out
+
     if _can_fuse(pc, pipe, override_color):
         # same result as the getter path below, without materialising cat(f_dc, f_rest), exp, normalize, sigmoid (and
         # without building an nn.Module per frame: the operator is called as a function)
         # visibility_filter (= radii > 0, gaussian_renderer/__init__.py:311) is stored by the preprocess kernel itself:
         # a torch compare over 6 M radii is a 9-us kernel per frame
         visible = torch.empty(xyz.shape[0], dtype=torch.bool, device=xyz.device)
-        if return_depth:
-            rendered_image, radii, aux = rasterize_gaussians_fused(xyz, screenspace_points, pc._features_dc,
-                                                                   pc._features_rest, pc._opacity, pc._scaling,
-                                                                   pc._rotation, raster_settings, visible=visible,
-                                                                   aux_maps=True, **extra_stats)
-            return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": visible,
-                    "radii": radii, "selected_pts_mask": None, **_aux_entries(aux)}
+        if return_depth or want_feat:
+            out = rasterize_gaussians_fused(xyz, screenspace_points, pc._features_dc, pc._features_rest, pc._opacity,
+                                            pc._scaling, pc._rotation, raster_settings, visible=visible,
+                                            **({"aux_maps": True} if return_depth else {}), **extra_stats)
+            return {"render": out[0], "viewspace_points": screenspace_points, "visibility_filter": visible,
+                    "radii": out[1], "selected_pts_mask": None, **(_aux_entries(out[2]) if return_depth else {}),
+                    **feature_entries(out[-1])}
         rendered_image, radii = rasterize_gaussians_fused(xyz, screenspace_points, pc._features_dc, pc._features_rest,
                                                           pc._opacity, pc._scaling, pc._rotation, raster_settings,
                                                           densify_stats=stats, visible=visible, **extra_stats)
         return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": visible,
                 "radii": radii, "selected_pts_mask": None}
 
+    feat_kw = {"features": extra_stats.pop("features")} if want_feat else {}
     rasterizer = GaussianRasterizer(raster_settings=raster_settings, **({"aux_maps": True} if return_depth else {}),
                                     **extra_stats)
     scales = rotations = cov3D_precomp = None
@@ -195,7 +225,7 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
 
     # exactly the reference's eight keyword arguments (gaussian_renderer/__init__.py:257-265); the statistics request of
     # this build travels as a ninth only when the caller asked for it
-    extra = {} if stats is None else {"densify_stats": stats}
+    extra = dict(feat_kw) if stats is None else {"densify_stats": stats}
     out = rasterizer(means3D=xyz, means2D=screenspace_points, shs=shs,
                      colors_precomp=colors_precomp, opacities=pc.get_opacity, scales=scales,
                      rotations=rotations, cov3D_precomp=cov3D_precomp, **extra)
@@ -205,7 +235,8 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
             "visibility_filter": radii > 0,
             "radii": radii,
             "selected_pts_mask": None,
-            **(_aux_entries(out[2]) if return_depth else {})}
+            **(_aux_entries(out[2]) if return_depth else {}),
+            **feature_entries(out[-1])}
 
 
 def _render_grown(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, which, grow_dir,
