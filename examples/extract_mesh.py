@@ -1,0 +1,80 @@
+"""From a trained model to a triangle mesh: render depth from the training views, fuse it into a TSDF volume and extract
+the surface by marching tetrahedra, all on the HIP path (``mvs_gaussian_splatting_amd/tsdf.py``).
+
+    python examples/extract_mesh.py -m <model directory> [--iteration N] [--voxel_size S | --resolution R]
+                                    [--sdf_trunc T] [--alpha_min A] [--max_depth D] [-s <dataset>] [-r ...]
+
+The scene is loaded as ``examples/render.py`` loads it (``cfg_args.json`` of the model directory; ``-s`` and the other
+switches override it).  The volume bounds the bulk of the model's positions (``tsdf.volume_for_points``); ``--resolution``
+is the number of samples along its longest side (default 256), ``--sdf_trunc`` defaults to 4 voxels.  Every training
+view contributes its expected depth ``depth / alpha`` where ``alpha >= --alpha_min``.
+
+writes ``<model>/mesh/iteration_<N>/tsdf_mesh.ply`` (binary PLY, vertex colours from the renders).
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from mvs_gaussian_splatting_amd import GaussianModel, ModelParams, Scene, fuse_views, volume_for_points  # noqa: E402
+from mvs_gaussian_splatting_amd.ply_io import write_ply_mesh  # noqa: E402
+from mvs_gaussian_splatting_amd.synthetic import PipelineParams  # noqa: E402
+
+
+def extract(dataset, iteration, voxel_size=None, resolution=None, sdf_trunc=None, alpha_min=0.5, max_depth=None):
+    with torch.no_grad():
+        gaussians = GaussianModel(dataset.sh_degree)
+        scene = Scene(dataset, gaussians, load_iteration=iteration, shuffle=False)
+        bg_color = [1, 1, 1] if dataset.white_background else [0, 0, 0]
+        background = torch.tensor(bg_color, dtype=torch.float32, device="cuda")
+        volume = volume_for_points(gaussians.get_xyz, voxel_size=voxel_size, resolution=resolution, sdf_trunc=sdf_trunc)
+        print(f"volume {volume.dims[0]} x {volume.dims[1]} x {volume.dims[2]}, voxel {volume.voxel_size:.5g}, "
+              f"truncation {volume.sdf_trunc:.5g}")
+        fuse_views(scene.getTrainCameras(), gaussians, PipelineParams(), background, volume, alpha_min=alpha_min,
+                   max_depth=max_depth)
+        vertices, faces, colors = volume.extract_mesh()
+    path = os.path.join(dataset.model_path, "mesh", "iteration_{}".format(scene.loaded_iter), "tsdf_mesh.ply")
+    write_ply_mesh(path, vertices, faces, colors)
+    print(f"{vertices.shape[0]} vertices, {faces.shape[0]} faces -> {path}")
+    return path
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("-s", "--source_path", default=None)
+    ap.add_argument("-m", "--model_path", required=True)
+    ap.add_argument("--images", default=None)
+    ap.add_argument("-r", "--resolution_scale", dest="image_resolution", type=int, default=None,
+                    help="the dataset's image down-scaling (examples/render.py -r)")
+    ap.add_argument("--eval", action="store_true", default=None)
+    ap.add_argument("--white_background", action="store_true", default=None)
+    ap.add_argument("--iteration", type=int, default=-1)
+    size = ap.add_mutually_exclusive_group()
+    size.add_argument("--voxel_size", type=float, default=None)
+    size.add_argument("--resolution", type=int, default=None, help="samples along the volume's longest side (256)")
+    ap.add_argument("--sdf_trunc", type=float, default=None, help="truncation distance (4 voxels)")
+    ap.add_argument("--alpha_min", type=float, default=0.5)
+    ap.add_argument("--max_depth", type=float, default=None)
+    args = ap.parse_args(argv)
+    fields = {}
+    cfg = os.path.join(args.model_path, "cfg_args.json")
+    if os.path.exists(cfg):
+        with open(cfg) as f:
+            fields = json.load(f)
+    for k in ("source_path", "images", "eval", "white_background"):
+        if getattr(args, k) is not None:
+            fields[k] = getattr(args, k)
+    if args.image_resolution is not None:
+        fields["resolution"] = args.image_resolution
+    if not fields.get("source_path"):
+        ap.error("no cfg_args.json in the model directory: give the dataset with -s")
+    dataset = ModelParams(model_path=args.model_path, **fields)
+    print("Extracting a mesh from " + args.model_path)
+    extract(dataset, args.iteration, args.voxel_size, args.resolution, args.sdf_trunc, args.alpha_min, args.max_depth)
+
+
+if __name__ == "__main__":
+    main()

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 26
+#define GSR_ABI_VERSION 27
 
 enum {
   GSR_OK = 0,
@@ -752,6 +752,53 @@ int gsr_mcmc_sample(int64_t P, const float* opacity_raw, float alive_threshold, 
                     int32_t* idx_out, int32_t* count_out, void* workspace, size_t workspace_bytes, void* stream);
 int gsr_mcmc_relocation(int64_t n, const int32_t* idx, const int32_t* count, const float* opacity_raw,
                         const float* scaling_raw, float* new_opacity_raw, float* new_scaling_raw, void* stream);
+
+/* ---- TSDF fusion of depth maps and marching-tetrahedra mesh extraction, ABI v27 (csrc/tsdf.hip; tsdf.py)
+ * A dense volume of nx x ny x nz grid points; point (i, j, k) is the sample at origin + voxel_size * (i, j, k), linear
+ * index (k * ny + j) * nx + i.  Device fields, float32, contiguous: tsdf [nz,ny,nx] (1 = untouched), weight [nz,ny,nx],
+ * color [nz,ny,nx,3] or NULL.  Indices are 32-bit: 7 * nx * ny * nz < 2^31 is required (seven edge slots per point).
+ * Every call checks its arguments before any HIP call (GSR_E_BADARG: NULL pointer, non-positive dims / voxel_size /
+ * sdf_trunc / image size / weight, an index space or launch that would overflow; GSR_E_ALIGN), is asynchronous on
+ * `stream`, allocates nothing and reads nothing back. */
+typedef struct GsrTsdfVolume {
+  int32_t nx, ny, nz;
+  float origin[3];
+  float voxel_size, sdf_trunc;
+  float* tsdf;
+  float* weight;
+  float* color;
+} GsrTsdfVolume;
+
+typedef struct GsrTsdfView {
+  int32_t width, height;
+  float fx, fy;                 /* W / (2 tan_fovx), H / (2 tan_fovy): the rasterizer's pixel-centre convention with */
+                                /* cx = (W - 1) / 2, cy = (H - 1) / 2 */
+  float weight;                 /* > 0 */
+  float max_depth, max_weight;  /* +inf: none */
+  const float* viewmatrix;      /* device [16], row-vector convention */
+  const float* depth;           /* device [H,W]; 0 marks an invalid pixel */
+  const float* color;           /* device [3,H,W]; given exactly when the volume has a colour field */
+} GsrTsdfView;
+
+/* One launch, one lane per grid point, float32 with every operation rounded on its own; the order is the header comment
+ * of csrc/tsdf.hip: project, nearest pixel, sdf = d - z, skip if z <= 0.2 / outside the image / d <= 0 / d > max_depth /
+ * sdf < -sdf_trunc, else running averages of min(1, sdf / sdf_trunc) and the pixel's colour with the view's weight.
+ * Skipped points are not written. */
+int gsr_tsdf_integrate(const GsrTsdfVolume* vol, const GsrTsdfView* view, void* stream);
+/* Marching tetrahedra on the Kuhn decomposition, first half.  Per grid point (uint8 [nz,ny,nx] each, written in full):
+ * tri_count = triangles of the cube based there (0 unless all eight corner weights >= min_weight), edge_mask = the owned
+ * edges (directions (1,0,0) (0,1,0) (0,0,1) (1,1,0) (0,1,1) (1,0,1) (1,1,1) = bits 0..6) that carry a referenced vertex,
+ * vert_count = its population count.  The caller scans vert_count and tri_count (exclusive, int64) and reads the totals. */
+int gsr_tsdf_mesh_count(const GsrTsdfVolume* vol, float min_weight, uint8_t* tri_count, uint8_t* edge_mask,
+                        uint8_t* vert_count, void* stream);
+/* Second half: vertices [V,3] float32 ordered by (owning point, direction), vcolors [V,3] or NULL (needs vol->color),
+ * faces [F,3] int32 ordered by (cube, tetrahedron, triangle), wound so that normals point from tsdf < 0 to tsdf >= 0.
+ * vert_offs / tri_offs: the exclusive scans, device int64 [nz,ny,nx], 8-byte aligned.  V and F must be positive (an
+ * empty mesh needs no call); nothing at or beyond row V / F is written whatever the offsets hold.  Plain stores at
+ * slots the scans fix: the same bits from run to run. */
+int gsr_tsdf_mesh_emit(const GsrTsdfVolume* vol, const uint8_t* tri_count, const uint8_t* edge_mask,
+                       const int64_t* vert_offs, const int64_t* tri_offs, int64_t V, int64_t F, float* vertices,
+                       float* vcolors, int32_t* faces, void* stream);
 
 #ifdef __cplusplus
 }

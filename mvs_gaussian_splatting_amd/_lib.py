@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # instead of copying it over the in-tree library
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")
 
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 
 class GsrParams(C.Structure):
@@ -55,6 +55,19 @@ class GsrAuxFrame(C.Structure):
 class GsrAuxGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("dL_dmeans3D", "dL_dmeans2D", "dL_dopacities", "dL_dscales", "dL_drotations",
                                           "dL_dcov3D")]
+
+
+class GsrTsdfVolume(C.Structure):
+    """A dense TSDF volume as the fusion / extraction entry points take it (include/gsr.h; tsdf.py)."""
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("origin", C.c_float * 3),
+                ("voxel_size", C.c_float), ("sdf_trunc", C.c_float),
+                ("tsdf", C.c_void_p), ("weight", C.c_void_p), ("color", C.c_void_p)]
+
+
+class GsrTsdfView(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_float), ("fy", C.c_float),
+                ("weight", C.c_float), ("max_depth", C.c_float), ("max_weight", C.c_float),
+                ("viewmatrix", C.c_void_p), ("depth", C.c_void_p), ("color", C.c_void_p)]
 
 
 class GsrGrow(C.Structure):
@@ -242,6 +255,11 @@ SYMBOLS = {
     "gsr_mcmc_sample": (C.c_int, [C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_size_t, C.c_void_p]),
     "gsr_mcmc_relocation": (C.c_int, [C.c_int64] + [C.c_void_p] * 7),
+    # depth-map fusion into a dense TSDF volume and marching-tetrahedra extraction (csrc/tsdf.hip; tsdf.py)
+    "gsr_tsdf_integrate": (C.c_int, [C.POINTER(GsrTsdfVolume), C.POINTER(GsrTsdfView), C.c_void_p]),
+    "gsr_tsdf_mesh_count": (C.c_int, [C.POINTER(GsrTsdfVolume), C.c_float] + [C.c_void_p] * 4),
+    "gsr_tsdf_mesh_emit": (C.c_int, [C.POINTER(GsrTsdfVolume)] + [C.c_void_p] * 4 + [C.c_int64, C.c_int64] +
+                           [C.c_void_p] * 4),
 }
 
 _lib = None

@@ -242,6 +242,16 @@ void launch_image_resize_pass(bool vertical, int C, const uint8_t* in, int in_le
                               const int32_t* bounds, const int32_t* taps, int ksize, uint8_t* out, hipStream_t s);
 void launch_image_to_float_chw(const uint8_t* in, int C, size_t pixels, float* out, hipStream_t s);
 
+// tsdf.hip: depth-map fusion into a dense TSDF volume and marching-tetrahedra extraction (include/gsr.h).  All kernels
+// share one launch shape; tsdf_grid_blocks is false when it would exceed 2^32 work-items (then nothing is launched)
+bool tsdf_grid_blocks(int nx, int ny, int nz, unsigned* xchunks, unsigned* blocks);
+void launch_tsdf_integrate(const GsrTsdfVolume& vol, const GsrTsdfView& view, hipStream_t s);
+void launch_tsdf_mesh_count(const GsrTsdfVolume& vol, float min_weight, uint8_t* tri_count, uint8_t* edge_mask,
+                            uint8_t* vert_count, hipStream_t s);
+void launch_tsdf_mesh_emit(const GsrTsdfVolume& vol, const uint8_t* tri_count, const uint8_t* edge_mask,
+                           const int64_t* vert_offs, const int64_t* tri_offs, int64_t V, int64_t F, float* vertices,
+                           float* vcolors, int32_t* faces, hipStream_t s);
+
 // knn.hip
 size_t knn_workspace_bytes(int N);
 void launch_knn3(const float* pts, int N, float* mean_dist2, void* ws, hipStream_t s);

@@ -75,6 +75,42 @@ def write_ply_vertices(path: str, elements: np.ndarray) -> None:
         f.write(np.ascontiguousarray(elements.astype(packed)).tobytes())
 
 
+def write_ply_mesh(path: str, vertices, faces, colors=None) -> None:
+    """A triangle mesh as binary little-endian PLY: a ``vertex`` element (float x, y, z and, with ``colors``, uchar red,
+    green, blue) and a ``face`` element ``property list uchar int vertex_indices``.  ``vertices [V,3]`` float, ``faces
+    [F,3]`` integer, ``colors [V,3]`` float in [0, 1] (clamped, times 255, rounded to nearest) or None; tensors or
+    arrays, V and F may be 0.  Host code."""
+    host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)      # noqa: E731
+    v = host(vertices).astype("<f4").reshape(-1, 3)
+    f = host(faces).reshape(-1, 3)
+    if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
+        raise ValueError(f"a face refers to a vertex outside 0..{v.shape[0] - 1}")
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if colors is not None:
+        c = host(colors).astype(np.float64).reshape(-1, 3)
+        if c.shape[0] != v.shape[0]:
+            raise ValueError(f"{c.shape[0]} colours for {v.shape[0]} vertices")
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    vert = np.zeros(v.shape[0], dtype=fields)
+    vert["x"], vert["y"], vert["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if colors is not None:
+        c8 = np.floor(np.clip(c, 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)
+        vert["red"], vert["green"], vert["blue"] = c8[:, 0], c8[:, 1], c8[:, 2]
+    face = np.zeros(f.shape[0], dtype=[("n", "u1"), ("idx", "<i4", (3,))])
+    face["n"] = 3
+    face["idx"] = f
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {v.shape[0]}"]
+    header += [f"property {_PLY_NAMES[t.lstrip('<')]} {n}" for n, t in fields]
+    header += [f"element face {f.shape[0]}", "property list uchar int vertex_indices", "end_header"]
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(path, "wb") as out:
+        out.write(("\n".join(header) + "\n").encode("ascii"))
+        out.write(vert.tobytes())
+        out.write(face.tobytes())
+
+
 def read_ply_vertices(path: str) -> Tuple[np.ndarray, List[str]]:
     """Structured array of the ``vertex`` element of a binary-little-endian or ascii PLY, and its property names."""
     with open(path, "rb") as f:

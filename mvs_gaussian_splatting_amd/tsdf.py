@@ -1,0 +1,236 @@
+"""From a trained model to a surface: fuse rendered depth maps into a dense truncated-signed-distance volume and extract
+a triangle mesh, both on the HIP path (``csrc/tsdf.hip`` behind ``gsr_tsdf_integrate`` / ``gsr_tsdf_mesh_count`` /
+``gsr_tsdf_mesh_emit``).
+
+    volume = volume_for_points(gaussians.get_xyz, resolution=256)
+    fuse_views(scene.getTrainCameras(), gaussians, pipe, background, volume)
+    vertices, faces, colors = volume.extract_mesh()
+    ply_io.write_ply_mesh("mesh.ply", vertices, faces, colors)
+
+Grid point ``(i, j, k)`` is the sample at ``origin + voxel_size * (i, j, k)``; the fields are stored ``[nz, ny, nx]``
+(x fastest) and are public: a field may be loaded into ``volume.tsdf`` / ``volume.weight`` / ``volume.color`` directly.
+The extraction is marching tetrahedra on the Kuhn decomposition of every cube; its definitions and output order are in
+``TSDFVolume.extract_mesh``.  There is no CPU path: a volume may be built on the CPU to be filled or inspected, but
+``integrate`` and ``extract_mesh`` need it on a ROCm GPU.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Optional, Sequence, Tuple
+
+import torch
+
+from . import _lib
+
+_INF = float("inf")
+_BLOCK_X, _BLOCK_ROWS = 64, 4          # the launch shape of csrc/tsdf.hip (tsdf_grid_blocks)
+
+
+def _limit(value: Optional[float], name: str) -> float:
+    """A missing ``max_depth`` / ``max_weight`` is no limit: ``+inf`` on the device."""
+    if value is None:
+        return _INF
+    value = float(value)
+    if not value > 0.0:
+        raise ValueError(f"{name} must be positive, got {value}")
+    return value
+
+
+class TSDFVolume:
+    """A dense TSDF volume: ``tsdf`` float32 ``[nz,ny,nx]`` (1 = untouched), ``weight`` float32 ``[nz,ny,nx]`` (0) and,
+    with ``with_color``, ``color`` float32 ``[nz,ny,nx,3]`` (0), on ``device``."""
+
+    def __init__(self, origin: Sequence[float], voxel_size: float, dims: Sequence[int], sdf_trunc: float,
+                 with_color: bool = True, device="cuda"):
+        origin = tuple(float(v) for v in origin)
+        dims = tuple(int(v) for v in dims)
+        if len(origin) != 3 or len(dims) != 3:
+            raise ValueError(f"origin and dims have three entries each, got {origin} and {dims}")
+        if any(n <= 0 for n in dims):
+            raise ValueError(f"dims must be positive, got {dims}")
+        nx, ny, nz = dims
+        if 7 * nx * ny * nz >= 2 ** 31:
+            raise ValueError(f"a volume of {nx} x {ny} x {nz} points overflows the 32-bit index space of its "
+                             f"7 edge slots per point (7 * nx * ny * nz must stay below 2^31)")
+        if -(-nx // _BLOCK_X) * -(-(ny * nz) // _BLOCK_ROWS) * _BLOCK_X * _BLOCK_ROWS >= 2 ** 32:
+            raise ValueError(f"a volume of {nx} x {ny} x {nz} points needs a launch of 2^32 work-items or more: make x "
+                             f"the long axis")
+        voxel_size, sdf_trunc = float(voxel_size), float(sdf_trunc)
+        if not voxel_size > 0.0 or not math.isfinite(voxel_size):
+            raise ValueError(f"voxel_size must be positive, got {voxel_size}")
+        if not sdf_trunc > 0.0 or not math.isfinite(sdf_trunc):
+            raise ValueError(f"sdf_trunc must be positive, got {sdf_trunc}")
+        self.origin, self.voxel_size, self.dims, self.sdf_trunc = origin, voxel_size, dims, sdf_trunc
+        self.with_color = bool(with_color)
+        self.device = torch.device(device)
+        self.tsdf = torch.ones((nz, ny, nx), dtype=torch.float32, device=self.device)
+        self.weight = torch.zeros((nz, ny, nx), dtype=torch.float32, device=self.device)
+        self.color = torch.zeros((nz, ny, nx, 3), dtype=torch.float32, device=self.device) if self.with_color else None
+
+    # ---- the native view of the volume -------------------------------------------------------------------------------
+    def _fields(self):
+        nx, ny, nz = self.dims
+        want = {"tsdf": (nz, ny, nx), "weight": (nz, ny, nx)}
+        if self.with_color:
+            want["color"] = (nz, ny, nx, 3)
+        for name, shape in want.items():
+            t = getattr(self, name)
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != shape \
+                    or not t.is_contiguous() or t.device != self.tsdf.device:
+                raise ValueError(f"volume.{name} must be a contiguous float32 {list(shape)} tensor on the volume's device")
+        return self.tsdf, self.weight, (self.color if self.with_color else None)
+
+    def _native(self) -> "_lib.GsrTsdfVolume":
+        tsdf, weight, color = self._fields()
+        v = _lib.GsrTsdfVolume()
+        v.nx, v.ny, v.nz = self.dims
+        v.origin[0], v.origin[1], v.origin[2] = self.origin
+        v.voxel_size, v.sdf_trunc = self.voxel_size, self.sdf_trunc
+        v.tsdf, v.weight, v.color = tsdf.data_ptr(), weight.data_ptr(), None if color is None else color.data_ptr()
+        return v
+
+    def _need_gpu(self, what: str) -> None:
+        if not self.tsdf.is_cuda:
+            raise _lib.GsrError(f"{what} needs the volume on a ROCm GPU (no CPU path)")
+
+    # ---- fusion --------------------------------------------------------------------------------------------------------
+    def integrate(self, depth: torch.Tensor, camera, color: Optional[torch.Tensor] = None, weight: float = 1.0,
+                  max_depth: Optional[float] = None, max_weight: Optional[float] = None) -> None:
+        """Fuse one view, in one launch.  ``depth`` float32 ``[H,W]`` or ``[1,H,W]``: the view-space depth of every
+        pixel, 0 where there is none.  ``camera``: anything with ``world_view_transform``, ``FoVx``, ``FoVy``,
+        ``image_width``, ``image_height``.  ``color`` float32 ``[3,H,W]``, given exactly when the volume has a colour
+        field.  Per grid point (float32; the order of operations is the header comment of ``csrc/tsdf.hip``): project
+        with the view matrix, skip if ``z <= 0.2``; nearest pixel ``floor(u + 0.5)`` with ``u = fx x / z + (W - 1) / 2``,
+        skip outside the image; ``d = depth[py, px]``, skip unless ``0 < d <= max_depth``; ``sdf = d - z``, skip if
+        ``sdf < -sdf_trunc``; then ``tsdf`` and the colour become the running averages with ``t = min(1, sdf /
+        sdf_trunc)`` and the pixel's colour, and ``weight`` grows by ``weight``, clamped to ``max_weight``.  Skipped
+        points are not written.  Asynchronous: nothing is read back."""
+        H, W = int(camera.image_height), int(camera.image_width)
+        dev = self.tsdf.device
+        if not isinstance(depth, torch.Tensor) or depth.dtype != torch.float32 or depth.device != dev \
+                or tuple(depth.shape) not in ((H, W), (1, H, W)):
+            raise ValueError(f"depth must be a float32 [{H},{W}] or [1,{H},{W}] tensor on {dev}, got "
+                             f"{getattr(depth, 'dtype', type(depth))} {tuple(getattr(depth, 'shape', ()))} on "
+                             f"{getattr(depth, 'device', None)}")
+        if self.with_color != (color is not None):
+            raise ValueError("color is given exactly when the volume has a colour field (with_color)")
+        if color is not None and (not isinstance(color, torch.Tensor) or color.dtype != torch.float32
+                                  or color.device != dev or tuple(color.shape) != (3, H, W)):
+            raise ValueError(f"color must be a float32 [3,{H},{W}] tensor on {dev}, got "
+                             f"{getattr(color, 'dtype', type(color))} {tuple(getattr(color, 'shape', ()))} on "
+                             f"{getattr(color, 'device', None)}")
+        if H <= 0 or W <= 0:
+            raise ValueError("the camera has an empty image")
+        weight = float(weight)
+        if not weight > 0.0 or not math.isfinite(weight):
+            raise ValueError(f"weight must be positive, got {weight}")
+        view = _lib.GsrTsdfView()
+        view.width, view.height = W, H
+        view.fx = W / (2.0 * math.tan(float(camera.FoVx) * 0.5))
+        view.fy = H / (2.0 * math.tan(float(camera.FoVy) * 0.5))
+        view.weight, view.max_depth, view.max_weight = weight, _limit(max_depth, "max_depth"), _limit(max_weight, "max_weight")
+        vol = self._native()
+        self._need_gpu("TSDFVolume.integrate")
+        viewmatrix = camera.world_view_transform.detach().to(device=dev, dtype=torch.float32).contiguous()
+        depth_c = depth.detach().contiguous()
+        color_c = None if color is None else color.detach().contiguous()
+        view.viewmatrix, view.depth = viewmatrix.data_ptr(), depth_c.data_ptr()
+        view.color = None if color_c is None else color_c.data_ptr()
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(_lib.load().gsr_tsdf_integrate(C.byref(vol), C.byref(view), stream), "gsr_tsdf_integrate")
+
+    # ---- extraction ----------------------------------------------------------------------------------------------------
+    def extract_mesh(self, min_weight: float = 1e-6) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+        """Marching tetrahedra -> ``(vertices float32 [V,3], faces int32 [F,3], colors float32 [V,3] or None)`` on the
+        device.  Every cube whose eight corners have ``weight >= min_weight`` is split into the six tetrahedra around
+        its diagonal from corner ``(0,0,0)`` to ``(1,1,1)``; a sample is inside when ``tsdf < 0``.  Each grid point owns
+        the edges that leave it along ``(1,0,0) (0,1,0) (0,0,1) (1,1,0) (0,1,1) (1,0,1) (1,1,1)``; a crossed edge
+        carries one vertex at ``p_a + (p_b - p_a) * t_a / (t_a - t_b)``, ``a`` the owner, colours likewise.  Vertices
+        are ordered by (owner's linear index, direction), faces by (cube, tetrahedron, triangle); only referenced
+        vertices are emitted; normals point from inside to outside; the same bits from run to run.  One host
+        synchronisation (the two sizes).  No crossing: ``[0,3]`` tensors."""
+        min_weight = float(min_weight)
+        if math.isnan(min_weight):
+            raise ValueError("min_weight is NaN")
+        vol = self._native()
+        self._need_gpu("TSDFVolume.extract_mesh")
+        lib, dev = _lib.load(), self.tsdf.device
+        nx, ny, nz = self.dims
+        n = nx * ny * nz
+        counts = torch.empty((3, n), dtype=torch.uint8, device=dev)          # triangles, edge mask, vertices per point
+        tri, mask, vert = counts[0], counts[1], counts[2]
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.gsr_tsdf_mesh_count(C.byref(vol), min_weight, tri.data_ptr(), mask.data_ptr(), vert.data_ptr(),
+                                               stream), "gsr_tsdf_mesh_count")
+            vert_end = torch.cumsum(vert, dim=0, dtype=torch.int64)
+            tri_end = torch.cumsum(tri, dim=0, dtype=torch.int64)
+            V, F = (int(v) for v in torch.stack((vert_end[-1], tri_end[-1])).tolist())     # the one read-back
+            vertices = torch.empty((V, 3), dtype=torch.float32, device=dev)
+            faces = torch.empty((F, 3), dtype=torch.int32, device=dev)
+            colors = torch.empty((V, 3), dtype=torch.float32, device=dev) if self.with_color else None
+            if V == 0 or F == 0:
+                return vertices[:0], faces[:0], None if colors is None else colors[:0]
+            vert_offs, tri_offs = vert_end - vert, tri_end - tri                            # exclusive scans
+            _lib.check(lib.gsr_tsdf_mesh_emit(C.byref(vol), tri.data_ptr(), mask.data_ptr(), vert_offs.data_ptr(),
+                                              tri_offs.data_ptr(), V, F, vertices.data_ptr(),
+                                              None if colors is None else colors.data_ptr(), faces.data_ptr(), stream),
+                       "gsr_tsdf_mesh_emit")
+        return vertices, faces, colors
+
+
+def fuse_views(cameras, model, pipe, bg, volume: TSDFVolume, *, alpha_min: float = 0.5,
+               max_depth: Optional[float] = None, renderer=None) -> TSDFVolume:
+    """Render every camera with ``renderer(camera, model, pipe, bg, return_depth=True)`` (default: ``render``) under
+    ``no_grad`` and integrate its expected depth ``depth / alpha`` where ``alpha >= alpha_min`` (0, invalid, elsewhere)
+    with the rendered colour.  No host synchronisation per view."""
+    if renderer is None:
+        from .renderer import render as renderer
+    with torch.no_grad():
+        for camera in cameras:
+            pkg = renderer(camera, model, pipe, bg, return_depth=True)
+            depth, alpha = pkg["depth"], pkg["alpha"]
+            expected = torch.where(alpha >= alpha_min, depth / alpha, torch.zeros_like(depth))
+            volume.integrate(expected, camera, color=pkg["render"] if volume.with_color else None, max_depth=max_depth)
+    return volume
+
+
+def volume_for_points(xyz: torch.Tensor, *, voxel_size: Optional[float] = None, resolution: Optional[int] = None,
+                      margin: float = 0.05, quantile: float = 0.01, sdf_trunc: Optional[float] = None,
+                      with_color: bool = True, device=None) -> TSDFVolume:
+    """A volume around the model's positions ``xyz [P,3]``: per axis the ``quantile`` .. ``1 - quantile`` range of the
+    coordinates (outliers of a trained model would blow the box up), widened on both sides by ``margin`` times the
+    longest side.  Give the ``voxel_size``, or the ``resolution``: the number of samples along the longest side
+    (default 256).  ``sdf_trunc`` defaults to 4 voxels.  Plain torch; one read-back of the six bounds."""
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] == 0:
+        raise ValueError(f"xyz must be [P,3] with P > 0, got {tuple(xyz.shape)}")
+    if voxel_size is not None and resolution is not None:
+        raise ValueError("give voxel_size or resolution, not both")
+    if not 0.0 <= quantile < 0.5 or margin < 0.0:
+        raise ValueError("quantile must lie in [0, 0.5) and margin must not be negative")
+    pts = xyz.detach().to(torch.float32)
+    P = int(pts.shape[0])
+    ordered = torch.sort(pts, dim=0).values
+    lo_i = min(P - 1, int(math.floor(quantile * (P - 1))))
+    lo, hi = ordered[lo_i].tolist(), ordered[P - 1 - lo_i].tolist()
+    longest = max(h - l for l, h in zip(lo, hi))
+    if not longest > 0.0:
+        raise ValueError("the points span no volume")
+    pad = margin * longest
+    lo, hi = [v - pad for v in lo], [v + pad for v in hi]
+    if voxel_size is None:
+        resolution = 256 if resolution is None else int(resolution)
+        if resolution < 2:
+            raise ValueError("resolution must be at least 2")
+        voxel_size = (longest + 2.0 * pad) / (resolution - 1)
+    voxel_size = float(voxel_size)
+    if not voxel_size > 0.0:
+        raise ValueError(f"voxel_size must be positive, got {voxel_size}")
+    dims = tuple(max(2, int(math.ceil((h - l) / voxel_size - 1e-9)) + 1) for l, h in zip(lo, hi))
+    return TSDFVolume(lo, voxel_size, dims, 4.0 * voxel_size if sdf_trunc is None else sdf_trunc, with_color=with_color,
+                      device=xyz.device if device is None else device)
+
+
+__all__ = ["TSDFVolume", "fuse_views", "volume_for_points"]
