@@ -3,7 +3,7 @@ write every view of the scene as PNG.
 
     python examples/render.py -m <model directory> [--iteration N] [--skip_train] [--skip_test]
                               [-s <COLMAP or Blender directory>] [-r ...] [--eval] [--white_background] [--depth]
-                              [--use_trained_exp] [--normals]
+                              [--use_trained_exp] [--normals] [--depth_normals]
 
 The dataset's location and options come from the ``cfg_args.json`` that ``examples/train.py -s ... -m ...`` left in the
 model directory; ``-s`` and the other switches override it.
@@ -15,18 +15,23 @@ greyscale PNG, scaled so that 65535 is the view's largest value (0 where nothing
 view is listed in ``.../depth/scales.json`` (metres per step).
 ``--normals`` also writes ``.../normal/%05d.png``: the view-space normal map ``sum w n`` of ``render(return_normals=True)``
 as ``normal * 0.5 + 0.5`` in 8 bits.
+``--depth_normals`` also writes ``.../depth_normal/%05d.png``: the normals of the rendered depth surface,
+``depth_to_normals(depth, alpha, ...)`` (``normal_consistency.py``), as ``depth_normal * 0.5 + 0.5`` in 8 bits -- the map
+the consistency loss pulls ``--normals`` towards; pixels without a valid normal come out mid-grey.
 ``--use_trained_exp`` renders every view that has one with the exposure saved in the iteration's ``exposure.json``
 (``examples/train.py --train_exposure``); test views have none and are rendered as they are.
 """
 import argparse
 import json
+import math
 import os
 import sys
 
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from mvs_gaussian_splatting_amd import GaussianModel, ModelParams, Scene, render, to_uint8_hwc  # noqa: E402
+from mvs_gaussian_splatting_amd import (GaussianModel, ModelParams, Scene, depth_to_normals, render,  # noqa: E402
+                                        to_uint8_hwc)
 from mvs_gaussian_splatting_amd.synthetic import PipelineParams  # noqa: E402
 
 
@@ -48,7 +53,7 @@ def save_depth_png(depth, alpha, path):
 
 
 def render_set(model_path, name, iteration, views, gaussians, pipeline, background, depth=False,
-               use_trained_exp=False, normals=False):
+               use_trained_exp=False, normals=False, depth_normals=False):
     render_path = os.path.join(model_path, name, "ours_{}".format(iteration), "renders")
     gts_path = os.path.join(model_path, name, "ours_{}".format(iteration), "gt")
     depth_path = os.path.join(model_path, name, "ours_{}".format(iteration), "depth")
@@ -60,9 +65,12 @@ def render_set(model_path, name, iteration, views, gaussians, pipeline, backgrou
     normal_path = os.path.join(model_path, name, "ours_{}".format(iteration), "normal")
     if normals:
         os.makedirs(normal_path, exist_ok=True)
+    depth_normal_path = os.path.join(model_path, name, "ours_{}".format(iteration), "depth_normal")
+    if depth_normals:
+        os.makedirs(depth_normal_path, exist_ok=True)
     for idx, view in enumerate(views):
         with_exp = use_trained_exp and view.image_name in (gaussians.pretrained_exposures or {})
-        pkg = render(view, gaussians, pipeline, background, **({"return_depth": True} if depth else {}),
+        pkg = render(view, gaussians, pipeline, background, **({"return_depth": True} if depth or depth_normals else {}),
                      **({"use_trained_exp": True} if with_exp else {}), **({"return_normals": True} if normals else {}))
         rendering = pkg["render"]
         save_png(rendering, os.path.join(render_path, "{0:05d}".format(idx) + ".png"))
@@ -71,13 +79,16 @@ def render_set(model_path, name, iteration, views, gaussians, pipeline, backgrou
             scales.append(save_depth_png(pkg["depth"], pkg["alpha"], os.path.join(depth_path, "{0:05d}".format(idx) + ".png")))
         if normals:
             save_png(pkg["normal"] * 0.5 + 0.5, os.path.join(normal_path, "{0:05d}".format(idx) + ".png"))
+        if depth_normals:
+            dn = depth_to_normals(pkg["depth"], pkg["alpha"], math.tan(view.FoVx * 0.5), math.tan(view.FoVy * 0.5))
+            save_png(dn * 0.5 + 0.5, os.path.join(depth_normal_path, "{0:05d}".format(idx) + ".png"))
     if depth:
         with open(os.path.join(depth_path, "scales.json"), "w") as f:
             json.dump(scales, f)
 
 
 def render_sets(dataset, iteration, pipeline, skip_train=False, skip_test=False, depth=False, use_trained_exp=False,
-                normals=False):
+                normals=False, depth_normals=False):
     with torch.no_grad():
         gaussians = GaussianModel(dataset.sh_degree)
         scene = Scene(dataset, gaussians, load_iteration=iteration, shuffle=False)
@@ -87,10 +98,10 @@ def render_sets(dataset, iteration, pipeline, skip_train=False, skip_test=False,
             raise FileNotFoundError("--use_trained_exp: the iteration's point-cloud directory has no exposure.json")
         if not skip_train:
             render_set(dataset.model_path, "train", scene.loaded_iter, scene.getTrainCameras(), gaussians, pipeline,
-                       background, depth, use_trained_exp, normals)
+                       background, depth, use_trained_exp, normals, depth_normals)
         if not skip_test:
             render_set(dataset.model_path, "test", scene.loaded_iter, scene.getTestCameras(), gaussians, pipeline,
-                       background, depth, use_trained_exp, normals)
+                       background, depth, use_trained_exp, normals, depth_normals)
     return scene
 
 
@@ -107,6 +118,8 @@ def main(argv=None):
     ap.add_argument("--skip_test", action="store_true")
     ap.add_argument("--depth", action="store_true", help="also write depth / alpha of every view as a 16-bit PNG")
     ap.add_argument("--normals", action="store_true", help="also write the view-space normal map of every view as PNG")
+    ap.add_argument("--depth_normals", action="store_true",
+                    help="also write the normals of the rendered depth surface of every view as PNG")
     ap.add_argument("--use_trained_exp", action="store_true", help="apply the saved per-image exposures")
     args = ap.parse_args(argv)
     fields = {}
@@ -122,7 +135,7 @@ def main(argv=None):
     dataset = ModelParams(model_path=args.model_path, **fields)
     print("Rendering " + args.model_path)
     render_sets(dataset, args.iteration, PipelineParams(), args.skip_train, args.skip_test, args.depth,
-                args.use_trained_exp, args.normals)
+                args.use_trained_exp, args.normals, args.depth_normals)
 
 
 if __name__ == "__main__":

@@ -10,9 +10,13 @@ SH degree steps, densification, opacity resets, the optional opacity sparsity te
                               [--exposure_lr_delay_steps N] [--exposure_lr_delay_mult M]]
                              [--prune_iterations N [N ...] --prune_keep_ratio R [--prune_kind sum|max|count|mean]]
                              [--strategy mcmc --cap_max N [--noise_lr LR] [--opacity_reg W] [--scale_reg W]]
+                             [--lambda_normal L [--normal_from_iter N]]
 
 ``--strategy mcmc --cap_max N`` (both forms) densifies the MCMC way (``mcmc.py``): a budget of N Gaussians, dead ones
 relocated onto live ones, 5 % growth a round, position noise and L1 priors on opacity and scale.
+``--lambda_normal L`` (both forms; off by default) adds the depth-normal consistency term of 2DGS from iteration
+``--normal_from_iter`` on (``normal_consistency.py``): the normals composited from the Gaussians are pulled towards the
+normals of the rendered depth surface.  2DGS uses 0.05 from iteration 7000.
 ``--optimizer_type sparse_adam`` (both forms) steps only the Gaussians each frame saw (``optim.SparseGaussianAdam``).
 
 With ``-s`` the example trains on a dataset through ``Scene`` (``scene.py``) and saves
@@ -146,7 +150,7 @@ def strategy_options(args):
     if args.strategy == "mcmc" and args.cap_max <= 0:
         raise SystemExit("--strategy mcmc needs --cap_max N, the budget of Gaussians")
     return dict(strategy=args.strategy, cap_max=args.cap_max, noise_lr=args.noise_lr, opacity_reg=args.opacity_reg,
-                scale_reg=args.scale_reg)
+                scale_reg=args.scale_reg, lambda_normal=args.lambda_normal, normal_from_iter=args.normal_from_iter)
 
 
 def train_scene(args, dev):
@@ -234,6 +238,10 @@ def main(argv=None):
     ap.add_argument("--noise_lr", type=float, default=OptimizationParams.noise_lr)
     ap.add_argument("--opacity_reg", type=float, default=OptimizationParams.opacity_reg)
     ap.add_argument("--scale_reg", type=float, default=OptimizationParams.scale_reg)
+    ap.add_argument("--lambda_normal", type=float, default=OptimizationParams.lambda_normal,
+                    help="weight of the depth-normal consistency term (normal_consistency.py); 2DGS uses 0.05; 0: off")
+    ap.add_argument("--normal_from_iter", type=int, default=OptimizationParams.normal_from_iter,
+                    help="first iteration the term joins the loss at (2DGS: 7000)")
     ap.add_argument("--out", default=os.path.dirname(os.path.abspath(__file__)))
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")

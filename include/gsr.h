@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 27
+#define GSR_ABI_VERSION 28
 
 enum {
   GSR_OK = 0,
@@ -799,6 +799,33 @@ int gsr_tsdf_mesh_count(const GsrTsdfVolume* vol, float min_weight, uint8_t* tri
 int gsr_tsdf_mesh_emit(const GsrTsdfVolume* vol, const uint8_t* tri_count, const uint8_t* edge_mask,
                        const int64_t* vert_offs, const int64_t* tri_offs, int64_t V, int64_t F, float* vertices,
                        float* vcolors, int32_t* faces, void* stream);
+
+/* ---- Depth-normal consistency loss, ABI v28 (csrc/normal_consistency.hip; normal_consistency.py)
+ * The normal-consistency term of 2DGS on the maps of a rendered frame: depth [H,W] = sum w z, alpha [H,W] = sum w,
+ * normal [3,H,W] = sum w n (un-normalised), device float32, contiguous.  Pixel convention of GsrTsdfView:
+ * fx = W / (2 tanfovx), fy = H / (2 tanfovy), each rounded once on the host, cx = (W - 1) / 2, cy = (H - 1) / 2; view
+ * space +z forward, x right, y down.
+ *     covered(q) = alpha(q) >= alpha_min       d(q) = depth(q) / alpha(q)       P(q) = (d (x - cx) / fx, d (y - cy) / fy, d)
+ *     tx = P(x+1,y) - P(x-1,y)     ty = P(x,y+1) - P(x,y-1)     c = ty x tx     s = |c|^2
+ *     valid(q): 1 <= x <= W-2, 1 <= y <= H-2, q and its four axis neighbours covered, s finite and s > 1e-20
+ *     n_d(q) = c / sqrt(s)  (faces the camera: a fronto-parallel plane gives (0,0,-1))
+ *     e(q) = alpha(q) - normal(q) . n_d(q)     loss = sum_valid e(q) / (H W)
+ * record (16-byte aligned, 4 floats) = { loss, n_valid as uint32 bits, 0, 0 }: written, not accumulated.
+ * dL_ddepth [H,W], dL_dalpha [H,W], dL_dnormal [3,H,W]: all three or none (NULL); the exact derivatives of `loss` for a
+ * unit upstream gradient, validity a decision without gradient; written in full (zeros where nothing arrives).
+ * depth_normal [3,H,W] or NULL: n_d on valid pixels, 0 elsewhere.  The loss and depth_normal are the same bits with and
+ * without the gradients, and every output is the same bits from run to run (a gather, no atomics; the loss is summed
+ * per workgroup and then over workgroups in a fixed order).  workspace: gsr_normal_consistency_workspace_bytes(H, W)
+ * bytes, 8-byte aligned (0: a shape the call refuses).
+ * Every argument is checked before any HIP call: GSR_E_BADARG for H, W < 1 (or H W > 2^28), a tan that is not positive,
+ * alpha_min outside (0, 1], a NULL input / record / workspace, a partial set of gradient pointers; GSR_E_ALIGN.
+ * Asynchronous on `stream`, allocates nothing, reads nothing back.  An image without interior (H < 3 or W < 3) or
+ * without a valid pixel gives loss = 0, n_valid = 0 and all-zero outputs. */
+size_t gsr_normal_consistency_workspace_bytes(int32_t H, int32_t W);
+int gsr_normal_consistency_fwd_bwd(const float* depth, const float* alpha, const float* normal, int32_t H, int32_t W,
+                                   float tanfovx, float tanfovy, float alpha_min, float* record, float* dL_ddepth,
+                                   float* dL_dalpha, float* dL_dnormal, float* depth_normal, void* workspace,
+                                   void* stream);
 
 #ifdef __cplusplus
 }

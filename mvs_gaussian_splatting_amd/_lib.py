@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # instead of copying it over the in-tree library
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")
 
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 
 class GsrParams(C.Structure):
@@ -260,6 +260,9 @@ SYMBOLS = {
     "gsr_tsdf_mesh_count": (C.c_int, [C.POINTER(GsrTsdfVolume), C.c_float] + [C.c_void_p] * 4),
     "gsr_tsdf_mesh_emit": (C.c_int, [C.POINTER(GsrTsdfVolume)] + [C.c_void_p] * 4 + [C.c_int64, C.c_int64] +
                            [C.c_void_p] * 4),
+    # depth-normal consistency loss of a rendered frame, value and unit gradients (csrc/normal_consistency.hip)
+    "gsr_normal_consistency_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "gsr_normal_consistency_fwd_bwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 2 + [C.c_float] * 3 + [C.c_void_p] * 7),
 }
 
 _lib = None

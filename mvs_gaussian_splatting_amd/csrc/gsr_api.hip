@@ -1429,6 +1429,35 @@ int gsr_tsdf_mesh_emit(const GsrTsdfVolume* vol, const uint8_t* tri_count, const
   return check(nullptr, s, "tsdf_mesh_emit");
 }
 
+// ---- depth-normal consistency loss (csrc/normal_consistency.hip) ------------------------------------------------------
+size_t gsr_normal_consistency_workspace_bytes(int32_t H, int32_t W) {
+  return image_shape_ok(H, W) ? normal_consistency_workspace_bytes(H, W) : 0;
+}
+int gsr_normal_consistency_fwd_bwd(const float* depth, const float* alpha, const float* normal, int32_t H, int32_t W,
+                                   float tanfovx, float tanfovy, float alpha_min, float* record, float* dL_ddepth,
+                                   float* dL_dalpha, float* dL_dnormal, float* depth_normal, void* workspace,
+                                   void* stream) {
+  unsigned xtiles, blocks;
+  if (!image_shape_ok(H, W) || !normal_consistency_blocks(H, W, &xtiles, &blocks))
+    return fail(GSR_E_BADARG, "bad image shape");
+  if (!(tanfovx > 0.0f) || !(tanfovy > 0.0f) || tanfovx > 3.0e38f || tanfovy > 3.0e38f)
+    return fail(GSR_E_BADARG, "tanfovx and tanfovy must be positive and finite");
+  if (!(alpha_min > 0.0f) || !(alpha_min <= 1.0f)) return fail(GSR_E_BADARG, "alpha_min must lie in (0, 1]");
+  if (!depth || !alpha || !normal || !record || !workspace) return fail(GSR_E_BADARG, "NULL argument");
+  const int ngrad = (dL_ddepth != nullptr) + (dL_dalpha != nullptr) + (dL_dnormal != nullptr);
+  if (ngrad != 0 && ngrad != 3) return fail(GSR_E_BADARG, "give all three gradient pointers or none");
+  if ((((uintptr_t)depth | (uintptr_t)alpha | (uintptr_t)normal | (uintptr_t)dL_ddepth | (uintptr_t)dL_dalpha |
+        (uintptr_t)dL_dnormal | (uintptr_t)depth_normal) & 3u) != 0)
+    return fail(GSR_E_ALIGN, "maps must be 4-byte aligned");
+  if (((uintptr_t)record & 15u) != 0) return fail(GSR_E_ALIGN, "the record must be 16-byte aligned");
+  if (((uintptr_t)workspace & 7u) != 0) return fail(GSR_E_ALIGN, "the workspace must be 8-byte aligned");
+  const float fx = (float)((double)W / (2.0 * (double)tanfovx)), fy = (float)((double)H / (2.0 * (double)tanfovy));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_normal_consistency(depth, alpha, normal, H, W, fx, fy, alpha_min, record, dL_ddepth, dL_dalpha, dL_dnormal,
+                            depth_normal, workspace, s);
+  return check(nullptr, s, "normal_consistency_fwd_bwd");
+}
+
 // ---- MCMC densification (csrc/mcmc.hip) -----------------------------------------------------------------------------
 static int mcmc_rows_ok(int64_t P) { return P >= 0 && P <= (int64_t)INT32_MAX; }
 int gsr_mcmc_noise(int64_t P, float* xyz, const float* scaling_raw, const float* rotation_raw, const float* opacity_raw,

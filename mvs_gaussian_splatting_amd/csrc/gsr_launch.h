@@ -252,6 +252,15 @@ void launch_tsdf_mesh_emit(const GsrTsdfVolume& vol, const uint8_t* tri_count, c
                            const int64_t* vert_offs, const int64_t* tri_offs, int64_t V, int64_t F, float* vertices,
                            float* vcolors, int32_t* faces, hipStream_t s);
 
+// normal_consistency.hip: the depth-normal consistency loss of a rendered frame, value and unit gradients in one launch
+// plus a one-block finish (include/gsr.h).  The three gradient pointers are all set or all nullptr (forward only);
+// depth_normal may be nullptr.  normal_consistency_blocks is false when the launch would exceed 2^32 work-items
+bool normal_consistency_blocks(int H, int W, unsigned* xtiles, unsigned* blocks);
+size_t normal_consistency_workspace_bytes(int H, int W);
+void launch_normal_consistency(const float* depth, const float* alpha, const float* normal, int H, int W, float fx,
+                               float fy, float alpha_min, float* record, float* dL_ddepth, float* dL_dalpha,
+                               float* dL_dnormal, float* depth_normal, void* workspace, hipStream_t s);
+
 // knn.hip
 size_t knn_workspace_bytes(int N);
 void launch_knn3(const float* pts, int N, float* mean_dist2, void* ws, hipStream_t s);

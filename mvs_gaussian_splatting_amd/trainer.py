@@ -12,11 +12,14 @@ decides when to log it.  (Densification itself reads its row counts, as the refe
 """
 from __future__ import annotations
 
+import math
+
 import torch
 
 from .densify import densify_and_prune, is_fork
 from .losses import add_densification_stats, l1_dssim_loss, opacity_sparsity_loss
 from .mcmc import add_new_gs, inject_noise, mcmc_regularizer, relocate_gs
+from .normal_consistency import normal_consistency_loss
 from .renderer import render
 from .synthetic import PipelineParams  # noqa: F401  (the two parameter classes live side by side)
 
@@ -62,6 +65,9 @@ class OptimizationParams:
     noise_lr = 5e5
     opacity_reg = 0.01
     scale_reg = 0.01
+    # depth-normal consistency (normal_consistency.py; 2DGS uses 0.05 from iteration 7000): 0 leaves the iteration as it is
+    lambda_normal = 0.0
+    normal_from_iter = 7000
 
     def __init__(self, **overrides):
         for k, v in overrides.items():
@@ -112,7 +118,13 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
     Under that strategy the L1 priors join the loss, ``relocate_gs`` then ``add_new_gs`` replace ``densify_and_prune`` on
     the schedule's densify iterations, there is no opacity reset and no densification statistics, ``inject_noise``
     follows the optimizer step, and a ``sparse_adam`` step takes ``opacity`` and ``scaling`` dense (the priors'
-    gradients are).  ``ValueError`` for ``cap_max <= 0`` or a fork model."""
+    gradients are).  ``ValueError`` for ``cap_max <= 0`` or a fork model.
+    ``opt.lambda_normal > 0`` from ``opt.normal_from_iter`` on: the frame is rendered with ``return_depth=True,
+    return_normals=True`` and ``lambda_normal * normal_consistency_loss(depth, alpha, normal, tan(FoVx / 2),
+    tan(FoVy / 2))`` joins the loss; the densification statistics are read from ``viewspace_points.grad``, as on
+    ``depth_loss`` frames.  Combines with ``depth_loss``, ``train_exposure``, ``sparse_adam`` and ``strategy="mcmc"``.
+    ``ValueError`` with ``pose_optimizer`` (the maps carry no camera gradient) and on a fork grow / learned-split model
+    (the maps are not rendered on its frames).  ``lambda_normal = 0``: exactly the calls made without it."""
     strategy = getattr(opt, "strategy", "default")
     if strategy not in ("default", "mcmc"):
         raise ValueError(f"strategy must be 'default' or 'mcmc', got {strategy!r}")
@@ -131,6 +143,15 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
     if train_exposure and getattr(model, "exposure_optimizer", None) is None:
         raise ValueError("train_exposure=True needs model.setup_exposures(image names) before training_setup")
     flag = lambda name: bool(getattr(dataset, name, False))      # noqa: E731
+    normal_on = float(getattr(opt, "lambda_normal", 0.0)) > 0.0 and iteration >= int(getattr(opt, "normal_from_iter", 0))
+    if normal_on:
+        if pose_optimizer is not None:
+            raise ValueError("lambda_normal > 0 does not combine with pose_optimizer: the depth, alpha and normal maps "
+                             "carry no camera gradient, so the pose would be refined against the colour loss alone")
+        if is_fork(model) or any(flag(n) for n in ("grow_dir", "continous_dir", "learn_split_distance",
+                                                   "learn_split_scale")):
+            raise ValueError("lambda_normal > 0 does not support the fork's grow / learned-split models: render refuses "
+                             "return_depth / return_normals on their frames (virtual rows appended)")
     if first_reset is None:
         first_reset = flag("white_background")
     todo = schedule(opt, iteration, first_reset)
@@ -141,7 +162,8 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
     pkg = render(camera, model, pipe, bg, grow_dir=flag("grow_dir"), densify_grad_threshold=opt.densify_grad_threshold,
                  iteration=iteration, opt=opt, continous_dir=flag("continous_dir"), grow_distance=flag("grow_distance"),
                  modelcg=dataset, cameras_extent=cameras_extent,                                # :91
-                 **({} if depth_loss is None else {"return_depth": True}),
+                 **({"return_depth": True} if depth_loss is not None or normal_on else {}),
+                 **({"return_normals": True} if normal_on else {}),
                  **({"use_trained_exp": True} if train_exposure else {}))
     gt = camera.original_image if gt_image is None else gt_image
     loss = l1_dssim_loss(pkg["render"], gt.to(pkg["render"].device), opt.lambda_dssim)          # :99-101
@@ -152,6 +174,9 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
     if depth_loss is not None:
         depth_target, depth_weight = depth_loss
         loss = loss + float(depth_weight) * (pkg["invdepth"] - depth_target.to(pkg["invdepth"].device)).abs().mean()
+    if normal_on:
+        loss = loss + float(opt.lambda_normal) * normal_consistency_loss(
+            pkg["depth"], pkg["alpha"], pkg["normal"], math.tan(camera.FoVx * 0.5), math.tan(camera.FoVy * 0.5))
     loss.backward()                                                                             # :107
     with torch.no_grad():
         if mcmc:
