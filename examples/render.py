@@ -3,7 +3,7 @@ write every view of the scene as PNG.
 
     python examples/render.py -m <model directory> [--iteration N] [--skip_train] [--skip_test]
                               [-s <COLMAP or Blender directory>] [-r ...] [--eval] [--white_background] [--depth]
-                              [--use_trained_exp] [--normals] [--depth_normals]
+                              [--use_trained_exp] [--normals] [--depth_normals] [--distortion]
 
 The dataset's location and options come from the ``cfg_args.json`` that ``examples/train.py -s ... -m ...`` left in the
 model directory; ``-s`` and the other switches override it.
@@ -40,6 +40,16 @@ def save_png(image, path):
     Image.fromarray(to_uint8_hwc(image).cpu().numpy()).save(path)
 
 
+def save_distortion_png(dist, path):
+    """The distortion map as 16-bit greyscale scaled by its maximum; returns the value one step stands for."""
+    import numpy as np
+    from PIL import Image
+    top = float(dist.max())
+    step = top / 65535.0 if top > 0 else 1.0
+    Image.fromarray(torch.round(dist[0] / step).clamp(0, 65535).cpu().numpy().astype(np.uint16)).save(path)
+    return step
+
+
 def save_depth_png(depth, alpha, path):
     """``depth / alpha`` as 16-bit greyscale; returns the depth one step stands for."""
     import numpy as np
@@ -53,7 +63,7 @@ def save_depth_png(depth, alpha, path):
 
 
 def render_set(model_path, name, iteration, views, gaussians, pipeline, background, depth=False,
-               use_trained_exp=False, normals=False, depth_normals=False):
+               use_trained_exp=False, normals=False, depth_normals=False, distortion=False):
     render_path = os.path.join(model_path, name, "ours_{}".format(iteration), "renders")
     gts_path = os.path.join(model_path, name, "ours_{}".format(iteration), "gt")
     depth_path = os.path.join(model_path, name, "ours_{}".format(iteration), "depth")
@@ -68,10 +78,15 @@ def render_set(model_path, name, iteration, views, gaussians, pipeline, backgrou
     depth_normal_path = os.path.join(model_path, name, "ours_{}".format(iteration), "depth_normal")
     if depth_normals:
         os.makedirs(depth_normal_path, exist_ok=True)
+    distortion_path = os.path.join(model_path, name, "ours_{}".format(iteration), "distortion")
+    dist_scales = []
+    if distortion:
+        os.makedirs(distortion_path, exist_ok=True)
     for idx, view in enumerate(views):
         with_exp = use_trained_exp and view.image_name in (gaussians.pretrained_exposures or {})
         pkg = render(view, gaussians, pipeline, background, **({"return_depth": True} if depth or depth_normals else {}),
-                     **({"use_trained_exp": True} if with_exp else {}), **({"return_normals": True} if normals else {}))
+                     **({"use_trained_exp": True} if with_exp else {}), **({"return_normals": True} if normals else {}),
+                     **({"return_distortion": True} if distortion else {}))
         rendering = pkg["render"]
         save_png(rendering, os.path.join(render_path, "{0:05d}".format(idx) + ".png"))
         save_png(view.original_image[0:3, :, :].to(rendering.device), os.path.join(gts_path, "{0:05d}".format(idx) + ".png"))
@@ -82,13 +97,19 @@ def render_set(model_path, name, iteration, views, gaussians, pipeline, backgrou
         if depth_normals:
             dn = depth_to_normals(pkg["depth"], pkg["alpha"], math.tan(view.FoVx * 0.5), math.tan(view.FoVy * 0.5))
             save_png(dn * 0.5 + 0.5, os.path.join(depth_normal_path, "{0:05d}".format(idx) + ".png"))
+        if distortion:
+            dist_scales.append(save_distortion_png(pkg["distortion"],
+                                                   os.path.join(distortion_path, "{0:05d}".format(idx) + ".png")))
     if depth:
         with open(os.path.join(depth_path, "scales.json"), "w") as f:
             json.dump(scales, f)
+    if distortion:
+        with open(os.path.join(distortion_path, "scales.json"), "w") as f:
+            json.dump(dist_scales, f)
 
 
 def render_sets(dataset, iteration, pipeline, skip_train=False, skip_test=False, depth=False, use_trained_exp=False,
-                normals=False, depth_normals=False):
+                normals=False, depth_normals=False, distortion=False):
     with torch.no_grad():
         gaussians = GaussianModel(dataset.sh_degree)
         scene = Scene(dataset, gaussians, load_iteration=iteration, shuffle=False)
@@ -98,10 +119,10 @@ def render_sets(dataset, iteration, pipeline, skip_train=False, skip_test=False,
             raise FileNotFoundError("--use_trained_exp: the iteration's point-cloud directory has no exposure.json")
         if not skip_train:
             render_set(dataset.model_path, "train", scene.loaded_iter, scene.getTrainCameras(), gaussians, pipeline,
-                       background, depth, use_trained_exp, normals, depth_normals)
+                       background, depth, use_trained_exp, normals, depth_normals, distortion)
         if not skip_test:
             render_set(dataset.model_path, "test", scene.loaded_iter, scene.getTestCameras(), gaussians, pipeline,
-                       background, depth, use_trained_exp, normals, depth_normals)
+                       background, depth, use_trained_exp, normals, depth_normals, distortion)
     return scene
 
 
@@ -120,6 +141,8 @@ def main(argv=None):
     ap.add_argument("--normals", action="store_true", help="also write the view-space normal map of every view as PNG")
     ap.add_argument("--depth_normals", action="store_true",
                     help="also write the normals of the rendered depth surface of every view as PNG")
+    ap.add_argument("--distortion", action="store_true",
+                    help="also write the depth-distortion map of every view as a 16-bit PNG scaled by its maximum")
     ap.add_argument("--use_trained_exp", action="store_true", help="apply the saved per-image exposures")
     args = ap.parse_args(argv)
     fields = {}
@@ -135,7 +158,7 @@ def main(argv=None):
     dataset = ModelParams(model_path=args.model_path, **fields)
     print("Rendering " + args.model_path)
     render_sets(dataset, args.iteration, PipelineParams(), args.skip_train, args.skip_test, args.depth,
-                args.use_trained_exp, args.normals, args.depth_normals)
+                args.use_trained_exp, args.normals, args.depth_normals, args.distortion)
 
 
 if __name__ == "__main__":

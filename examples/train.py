@@ -11,12 +11,16 @@ SH degree steps, densification, opacity resets, the optional opacity sparsity te
                              [--prune_iterations N [N ...] --prune_keep_ratio R [--prune_kind sum|max|count|mean]]
                              [--strategy mcmc --cap_max N [--noise_lr LR] [--opacity_reg W] [--scale_reg W]]
                              [--lambda_normal L [--normal_from_iter N]]
+                             [--lambda_dist L [--dist_from_iter N]]
 
 ``--strategy mcmc --cap_max N`` (both forms) densifies the MCMC way (``mcmc.py``): a budget of N Gaussians, dead ones
 relocated onto live ones, 5 % growth a round, position noise and L1 priors on opacity and scale.
 ``--lambda_normal L`` (both forms; off by default) adds the depth-normal consistency term of 2DGS from iteration
 ``--normal_from_iter`` on (``normal_consistency.py``): the normals composited from the Gaussians are pulled towards the
 normals of the rendered depth surface.  2DGS uses 0.05 from iteration 7000.
+``--lambda_dist L`` (both forms; off by default) adds the depth-distortion term of 2DGS from iteration
+``--dist_from_iter`` on: ``L`` times the mean of the rasterizer's distortion map, which pulls every ray's blending weights
+together in depth.  2DGS uses 100 to 1000 from iteration 3000.
 ``--optimizer_type sparse_adam`` (both forms) steps only the Gaussians each frame saw (``optim.SparseGaussianAdam``).
 
 With ``-s`` the example trains on a dataset through ``Scene`` (``scene.py``) and saves
@@ -150,7 +154,8 @@ def strategy_options(args):
     if args.strategy == "mcmc" and args.cap_max <= 0:
         raise SystemExit("--strategy mcmc needs --cap_max N, the budget of Gaussians")
     return dict(strategy=args.strategy, cap_max=args.cap_max, noise_lr=args.noise_lr, opacity_reg=args.opacity_reg,
-                scale_reg=args.scale_reg, lambda_normal=args.lambda_normal, normal_from_iter=args.normal_from_iter)
+                scale_reg=args.scale_reg, lambda_normal=args.lambda_normal, normal_from_iter=args.normal_from_iter,
+                lambda_dist=args.lambda_dist, dist_from_iter=args.dist_from_iter)
 
 
 def train_scene(args, dev):
@@ -242,6 +247,10 @@ def main(argv=None):
                     help="weight of the depth-normal consistency term (normal_consistency.py); 2DGS uses 0.05; 0: off")
     ap.add_argument("--normal_from_iter", type=int, default=OptimizationParams.normal_from_iter,
                     help="first iteration the term joins the loss at (2DGS: 7000)")
+    ap.add_argument("--lambda_dist", type=float, default=OptimizationParams.lambda_dist,
+                    help="weight of the depth-distortion term (the rasterizer's distortion map); 2DGS uses 100 to 1000; 0: off")
+    ap.add_argument("--dist_from_iter", type=int, default=OptimizationParams.dist_from_iter,
+                    help="first iteration the term joins the loss at (2DGS: 3000)")
     ap.add_argument("--out", default=os.path.dirname(os.path.abspath(__file__)))
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")

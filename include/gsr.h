@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 28
+#define GSR_ABI_VERSION 29
 
 enum {
   GSR_OK = 0,
@@ -267,6 +267,28 @@ size_t gsr_feature_maps_backward_bytes(int32_t P);
 int gsr_feature_maps_backward(const GsrParams* p, const GsrAuxFrame* frame, const float* features, int32_t C,
                               const float* dL_dmaps, float* dL_dfeatures, void* acc_ws, size_t acc_ws_bytes,
                               const GsrAuxGrads* grads, void* stream);
+
+/* ---- depth-distortion map of a rendered frame, ABI v29 (csrc/distortion.hip) -------------------------
+ * With i, w_i, z_i as above (the entries and weights of the depth / alpha maps), the regulariser of 2DGS:
+ *     dist = sum_i sum_{j<i} w_i w_j (m_i - m_j)^2,   m_i = m(z_i)        (no background term)
+ *     mapping 0 ("linear"): m(z) = z;   mapping 1 ("ndc"): m(z) = far / (far - near) * (1 - near / z)
+ * evaluated with recurrences over differences of m, not as A M2 - M1^2: a pixel whose contributors lie in a thin slab
+ * keeps its relative accuracy.  A pixel with zero or one contributor is exactly 0.  near / far are read with mapping 1 only.
+ * dist: device [1,H,W], state: device [2,H,W], both written in full, the same bits from run to run.  state is what the
+ * backward needs per pixel (m_last - mean m, dist / alpha); its content is opaque and belongs to the frame and mapping it
+ * was written for.  Every argument is checked before any HIP call: GSR_E_BADARG for a mapping outside {0, 1}, mapping 1
+ * without finite 0 < near < far, a NULL pointer, a workspace that is too small; GSR_E_ALIGN for acc_ws.  Nothing
+ * allocates, synchronises or reads back. */
+int gsr_distortion_forward(const GsrAuxFrame* frame, int32_t mapping, float near, float far, float* dist, float* state,
+                           void* stream);
+/* p: the inputs of the frame's forward, as for gsr_aux_maps_backward.  state: what the forward wrote; dL_ddist: device
+ * [1,H,W].  acc_ws: device scratch of gsr_distortion_backward_bytes(P) bytes, 256-byte aligned (the [P,8] accumulator of
+ * gsr_aux_maps_backward; the call zero-fills it).  grads: written in full, as by gsr_aux_maps_backward.  Gradients are
+ * reproducible to rounding, not bit for bit (float atomics). */
+size_t gsr_distortion_backward_bytes(int32_t P);
+int gsr_distortion_backward(const GsrParams* p, const GsrAuxFrame* frame, int32_t mapping, float near, float far,
+                            const float* state, const float* dL_ddist, void* acc_ws, size_t acc_ws_bytes,
+                            const GsrAuxGrads* grads, void* stream);
 
 /* ---- per-Gaussian contribution statistics of a rendered frame, ABI v24 (csrc/contribution.hip) ----------------------
  * For Gaussian g let p run over the pixels where the colour pass composited g (the rule above: the first n_contrib

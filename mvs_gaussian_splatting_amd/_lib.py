@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # instead of copying it over the in-tree library
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")
 
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 
 class GsrParams(C.Structure):
@@ -161,6 +161,13 @@ SYMBOLS = {
     "gsr_feature_maps_backward_bytes": (C.c_size_t, [C.c_int32]),
     "gsr_feature_maps_backward": (C.c_int, [C.POINTER(GsrParams), C.POINTER(GsrAuxFrame), C.c_void_p, C.c_int32, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(GsrAuxGrads), C.c_void_p]),
+    # depth-distortion map [1,H,W] of a rendered frame, its per-pixel state [2,H,W] and its gradients (csrc/distortion.hip)
+    "gsr_distortion_forward": (C.c_int, [C.POINTER(GsrAuxFrame), C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
+    "gsr_distortion_backward_bytes": (C.c_size_t, [C.c_int32]),
+    "gsr_distortion_backward": (C.c_int, [C.POINTER(GsrParams), C.POINTER(GsrAuxFrame), C.c_int32, C.c_float, C.c_float,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(GsrAuxGrads),
+                                          C.c_void_p]),
     # per-Gaussian contribution statistics of a rendered frame, added into int64 [P,3] (csrc/contribution.hip)
     "gsr_contribution_accumulate": (C.c_int, [C.POINTER(GsrAuxFrame), C.c_void_p, C.c_void_p, C.c_void_p]),
     "gsr_mark_visible": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

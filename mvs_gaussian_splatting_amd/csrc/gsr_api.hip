@@ -4,6 +4,7 @@
 #include <dlfcn.h>
 #include <stdio.h>
 #include <string.h>
+#include <cmath>
 #include <atomic>
 #include <mutex>
 #include <string>
@@ -703,6 +704,69 @@ int gsr_feature_maps_backward(const GsrParams* p, const GsrAuxFrame* f, const fl
     if (int rc = check(p, s, "feature_maps_bwd")) return rc;
   }
   if (!g) return 0;
+  launch_aux_geom_bwd(*p, f->radii, acc, *g, s);
+  return check(p, s, "aux_geom_bwd");
+}
+
+// ---- depth-distortion map (csrc/distortion.hip) --------------------------------------------------------------------
+static int validate_distortion_mapping(int32_t mapping, float near, float far) {
+  if (mapping != 0 && mapping != 1) return fail(GSR_E_BADARG, "mapping must be 0 (linear) or 1 (ndc)");
+  if (mapping == 1 && !(std::isfinite(near) && std::isfinite(far) && near > 0.0f && near < far))
+    return fail(GSR_E_BADARG, "mapping 1 needs finite 0 < near < far");
+  return 0;
+}
+
+size_t gsr_distortion_backward_bytes(int32_t P) { return gsr_aux_maps_backward_bytes(P); }
+
+int gsr_distortion_forward(const GsrAuxFrame* f, int32_t mapping, float near, float far, float* dist, float* state,
+                           void* stream) {
+  if (int rc = validate_aux_frame(f)) return rc;
+  if (int rc = validate_distortion_mapping(mapping, near, far)) return rc;
+  if (!dist || !state) return fail(GSR_E_BADARG, "dist / state is NULL");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const ImageLayout I(f->width, f->height);
+  if (f->P == 0 || f->num_rendered == 0) {      // nothing was binned: every list is empty
+    GSR_HIP(hipMemsetAsync(dist, 0, 4 * (size_t)f->width * f->height, s));
+    GSR_HIP(hipMemsetAsync(state, 0, 8 * (size_t)f->width * f->height, s));
+    return 0;
+  }
+  const GeomLayout L(f->P);
+  const SortedViews sv = sorted_views(f->bin_ws, f->num_rendered, f->num_visible, f->width, f->height, f->binning_mode);
+  launch_distortion_fwd(f->width, f->height, at<uint2>(f->img_ws, I.ranges), sv.point_list, at<GeomRec>(f->geom_ws, L.rec),
+                        at<BinInfo>(f->geom_ws, L.bin), at<uint32_t>(f->img_ws, I.n_contrib),
+                        at<uint32_t>(f->img_ws, I.tile_order), mapping, near, far, dist, state, s);
+  return check(nullptr, s, "distortion_fwd");
+}
+
+int gsr_distortion_backward(const GsrParams* p, const GsrAuxFrame* f, int32_t mapping, float near, float far,
+                            const float* state, const float* dL_ddist, void* acc_ws, size_t acc_ws_bytes,
+                            const GsrAuxGrads* g, void* stream) {
+  if (!p) return fail(GSR_E_BADARG, "params is NULL");
+  if (p->forward_only) return fail(GSR_E_BADARG, "the forward ran with forward_only = 1: no state for a backward");
+  if (int rc = validate_aux_frame(f)) return rc;
+  if (int rc = validate_distortion_mapping(mapping, near, far)) return rc;
+  if (int rc = validate_aux_inputs(p)) return rc;
+  if (f->P != p->P || f->width != p->width || f->height != p->height) return fail(GSR_E_BADARG, "frame and params disagree");
+  if (!g) return fail(GSR_E_BADARG, "grads is NULL");
+  if (p->P == 0) return 0;
+  if (!state || !dL_ddist || !acc_ws || !f->radii) return fail(GSR_E_BADARG, "NULL workspace / input");
+  if (!g->dL_dmeans3D || !g->dL_dmeans2D || !g->dL_dopacities)
+    return fail(GSR_E_BADARG, "dL_dmeans3D / dL_dmeans2D / dL_dopacities must be non-NULL");
+  if (acc_ws_bytes < gsr_distortion_backward_bytes(p->P)) return fail(GSR_E_BADARG, "accumulator workspace too small");
+  if (((uintptr_t)acc_ws & 255u) != 0) return fail(GSR_E_ALIGN, "acc_ws must be 256-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const ImageLayout I(f->width, f->height);
+  const GeomLayout L(f->P);
+  float* acc = static_cast<float*>(acc_ws);
+  GSR_HIP(hipMemsetAsync(acc, 0, 32 * (size_t)p->P, s));
+  if (f->num_rendered > 0) {
+    const SortedViews sv = sorted_views(f->bin_ws, f->num_rendered, f->num_visible, f->width, f->height, f->binning_mode);
+    launch_distortion_bwd(f->width, f->height, at<uint2>(f->img_ws, I.ranges), sv.point_list, at<GeomRec>(f->geom_ws, L.rec),
+                          at<BinInfo>(f->geom_ws, L.bin), at<uint32_t>(f->img_ws, I.n_contrib),
+                          at<float>(f->img_ws, I.final_T), at<uint32_t>(f->img_ws, I.tile_order), mapping, near, far, state,
+                          dL_ddist, acc, s);
+    if (int rc = check(p, s, "distortion_bwd")) return rc;
+  }
   launch_aux_geom_bwd(*p, f->radii, acc, *g, s);
   return check(p, s, "aux_geom_bwd");
 }

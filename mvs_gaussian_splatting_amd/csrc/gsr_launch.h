@@ -123,6 +123,17 @@ void launch_feature_maps_bwd(int W, int H, const uint2* ranges, const uint32_t* 
                              const float* features, int C, const float* dL_dmaps, float* acc, float* dL_dfeatures,
                              hipStream_t s);
 
+// distortion.hip: the depth-distortion map dist [1,H,W] of a rendered frame (the entries and weights of depth.hip; mapping
+// 0: m = z, 1: m = far / (far - near) (1 - near / z)), the per-pixel state [2,H,W] its backward reads, and the backward:
+// sums into acc [P,8] (zeroed by the caller; the layout launch_aux_geom_bwd reads, d z word included)
+void launch_distortion_fwd(int W, int H, const uint2* ranges, const uint32_t* point_list, const GeomRec* rec,
+                           const BinInfo* bin, const uint32_t* n_contrib, const uint32_t* tile_order, int mapping,
+                           float near, float far, float* dist, float* state, hipStream_t s);
+void launch_distortion_bwd(int W, int H, const uint2* ranges, const uint32_t* point_list, const GeomRec* rec,
+                           const BinInfo* bin, const uint32_t* n_contrib, const float* final_T, const uint32_t* tile_order,
+                           int mapping, float near, float far, const float* state, const float* dL_ddist, float* acc,
+                           hipStream_t s);
+
 // contribution.hip: per-Gaussian blending-weight statistics of a rendered frame, added into stats [P,3] (int64: sum of
 // round(w 2^30), pixel count, float bits of the largest w) with integer atomics; pixel_mask: nullptr or [H,W] bytes
 void launch_contribution(int W, int H, const uint2* ranges, const uint32_t* point_list, const GeomRec* rec,

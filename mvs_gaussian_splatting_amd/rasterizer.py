@@ -36,6 +36,13 @@ Feature maps.  ``forward(..., features=F)`` with ``F`` float32 ``[P,C]`` (any C 
 colour pass's blending weights, no background term, no clamp (``csrc/features.hip``), behind a third
 autograd node (``_FeatureMaps``) that reads the colour node's frame and returns gradients for ``F`` and the geometry.
 Without ``features`` nothing of it runs.
+
+Distortion map.  ``GaussianRasterizer(settings, distortion=True)`` (or ``distortion=dict(mapping="linear" | "ndc", near=,
+far=)``; ``True`` is ``"ndc"`` with near 0.2, far 100, what 2DGS trains with) appends ``dist [1,H,W]`` =
+``sum_i sum_{j<i} w_i w_j (m_i - m_j)^2`` to the call's results (after ``aux`` and ``feat``): the depth-distortion term of
+2DGS over the colour pass's contributors, evaluated without the cancelling ``A M2 - M1^2`` form (``csrc/distortion.hip``;
+DESIGN.md §7.16), behind a node of its own (``_DistortionMap``) that reads the colour node's frame.  Without ``distortion``
+nothing of it runs.
 """
 from __future__ import annotations
 
@@ -657,6 +664,131 @@ def _feature_maps_of(node, grad: bool, features, means3D, means2D, opacities, sc
                                     features, raster_settings, frame, mode, act_flags)
 
 
+_DIST_MAPPINGS = {"linear": 0, "ndc": 1}
+
+
+def _distortion_spec(distortion):
+    """``distortion`` of the operator as (mapping, near, far), or None when the map is not asked for.  Raises ValueError
+    for anything else, before anything is enqueued (the library's own refusals, restated where the caller can read them)."""
+    if distortion is None or distortion is False:
+        return None
+    if distortion is True:
+        distortion = {}
+    if not isinstance(distortion, dict):
+        raise ValueError(f"distortion must be True or a dict(mapping=, near=, far=), got {type(distortion).__name__}")
+    unknown = set(distortion) - {"mapping", "near", "far"}
+    if unknown:
+        raise ValueError(f"distortion: unknown keys {sorted(unknown)}")
+    name = distortion.get("mapping", "ndc")
+    if name not in _DIST_MAPPINGS:
+        raise ValueError(f"distortion mapping must be one of {sorted(_DIST_MAPPINGS)}, got {name!r}")
+    near, far = float(distortion.get("near", 0.2)), float(distortion.get("far", 100.0))
+    if name == "ndc" and not (0.0 < near < far < float("inf")):
+        raise ValueError(f"distortion mapping 'ndc' needs finite 0 < near < far, got near={near}, far={far}")
+    return _DIST_MAPPINGS[name], near, far
+
+
+class _DistortionMap(torch.autograd.Function):
+    """``dist [1,H,W]``, the depth-distortion map of a frame the colour operator has rendered (``include/gsr.h``:
+    gsr_distortion_*; ``csrc/distortion.hip``).  A node of its own next to the colour node, built like ``_AuxMaps``: it
+    reads the colour node's frame and returns the map's own gradients for means3D, means2D, opacities and scales /
+    rotations or cov3D_precomp.  The forward also leaves the per-pixel ``state [2,H,W]`` the backward reads."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, opacities, scales, rotations, cov3Ds_precomp,
+                raster_settings: GaussianRasterizationSettings, frame: _Frame, binning_mode: int, act_flags: int = 0,
+                spec=(1, 0.2, 100.0)):
+        lib = _lib.load()
+        dev = _require_gpu(means3D)
+        P = int(means3D.shape[0])
+        means3D = _f32c(means3D, "means3D", dev)
+        opacities = _f32c(opacities, "opacities", dev)
+        scales = _f32c(scales, "scales", dev)
+        rotations = _f32c(rotations, "rotations", dev, align16=True)
+        cov3Ds_precomp = _f32c(cov3Ds_precomp, "cov3D_precomp", dev)
+        H, W = int(raster_settings.image_height), int(raster_settings.image_width)
+        mapping, near, far = spec
+        dist = torch.empty(1, H, W, dtype=torch.float32, device=dev)
+        state = torch.empty(2, H, W, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.gsr_distortion_forward(C.byref(_aux_frame(frame, P, W, H, binning_mode)), mapping, near, far,
+                                                  dist.data_ptr(), state.data_ptr(), _stream(dev)),
+                       "gsr_distortion_forward")
+        ctx.raster_settings = raster_settings
+        ctx.layout = (frame.layout_R, frame.layout_V)
+        ctx.frame_pending = frame.pending
+        ctx.counts = frame.counts
+        ctx.binning_mode = binning_mode
+        ctx.act_flags = int(act_flags)
+        ctx.spec = (int(mapping), float(near), float(far))
+        ctx.has_means2D = means2D is not None
+        ctx.save_for_backward(means3D, opacities, scales, rotations, cov3Ds_precomp, state, frame.radii, frame.geom,
+                              frame.binning, frame.img)
+        return dist
+
+    @staticmethod
+    def backward(ctx, grad_dist):
+        if grad_dist is None:
+            return (None,) * 11
+        lib = _lib.load()
+        saved = ctx.saved_tensors
+        means3D, opacities, scales, rotations, cov3Ds_precomp, state = saved[:6]
+        frame, binning_mode = _frame_of(ctx, saved)
+        settings = ctx.raster_settings
+        dev = means3D.device
+        P = int(means3D.shape[0])
+        H, W = int(settings.image_height), int(settings.image_width)
+        if frame.pending is not None:
+            _verify(frame.pending, block=True)      # deferred mode: as the colour backward
+        grad_dist = _f32c(grad_dist, "grad_dist", dev)
+        empty = torch.empty(0, dtype=torch.float32, device=dev)
+        mapping, near, far = ctx.spec
+        with torch.cuda.device(dev):
+            params, keep = _make_params(dev, settings, means3D, empty, empty, opacities, scales, rotations,
+                                        cov3Ds_precomp, act_flags=ctx.act_flags)
+            params.profile = None
+            params.binning_mode = binning_mode
+            new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
+            g_means3D, g_means2D, g_opac = new(P, 3), new(P, 3), new(*opacities.shape)
+            g_scales, g_rot, g_cov = (new(P, n) if t.numel() else None
+                                      for t, n in ((scales, 3), (rotations, 4), (cov3Ds_precomp, 6)))
+            grads = _lib.GsrAuxGrads(_ptr(g_means3D), _ptr(g_means2D), _ptr(g_opac), _ptr(g_scales), _ptr(g_rot),
+                                     _ptr(g_cov))
+            nbytes = lib.gsr_distortion_backward_bytes(P)
+            acc = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            _lib.check(lib.gsr_distortion_backward(C.byref(params), C.byref(_aux_frame(frame, P, W, H, binning_mode)),
+                                                   mapping, near, far, state.data_ptr(), grad_dist.data_ptr(),
+                                                   acc.data_ptr(), nbytes, C.byref(grads), _stream(dev)),
+                       "gsr_distortion_backward")
+        del keep
+        return (g_means3D, g_means2D if ctx.has_means2D else None, g_opac, g_scales, g_rot, g_cov, None, None, None, None,
+                None)
+
+
+def _distortion_of(node, grad: bool, spec, means3D, means2D, opacities, scales, rotations, cov3Ds_precomp,
+                   raster_settings, act_flags: int = 0):
+    frame, mode = _frame_of(node)
+    if grad:
+        return _DistortionMap.apply(means3D, means2D, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
+                                    frame, mode, act_flags, spec)
+    return _DistortionMap.forward(_NoGraph(), means3D, means2D, opacities, scales, rotations, cov3Ds_precomp,
+                                  raster_settings, frame, mode, act_flags, spec)
+
+
+def _check_distortion_request(cam, state_key=None, densify_stats=None) -> None:
+    """The refusals of a ``distortion=`` request (those of ``aux_maps=True``), before anything is enqueued."""
+    if densify_stats is not None:
+        raise ValueError("distortion cannot be combined with densify_stats: the in-backward statistics would see the "
+                         "colour node's dL/dmeans2D alone, without the map's share (take them from the summed "
+                         "means2D.grad after the backward)")
+    if cam:
+        raise ValueError("distortion cannot be combined with camera tensors that require grad: the distortion map has no "
+                         "camera gradients (detach viewmatrix / projmatrix / campos, or render the map in a frame of "
+                         "its own)")
+    if state_key is not None:
+        raise ValueError("distortion is not available on a frame with grown / split rows appended")
+
+
 def _check_feature_request(features, means3D, cam, state_key=None, densify_stats=None) -> None:
     """The refusals of a ``features=F`` request, before anything is enqueued (and before a GPU is asked for)."""
     if densify_stats is not None:
@@ -729,10 +861,11 @@ def _accumulate_contribution(node, stats, mask, means3D, settings) -> None:
 
 
 def _with_frame_outputs(color, radii, node, grad: bool, geometry, aux_maps, contribution, contribution_mask,
-                        features=None, grad_features: bool = False):
+                        features=None, grad_features: bool = False, distortion=None):
     """The results of a frame that kept its state: the statistics are accumulated, the maps appended when asked for
-    (``aux``, then ``feat``).  ``grad``: the colour node is an autograd node; ``grad_features``: the feature maps get a
-    node although the colour forward ran outside autograd (only ``features`` requires grad)."""
+    (``aux``, then ``feat``, then ``dist``).  ``grad``: the colour node is an autograd node; ``grad_features``: the feature
+    maps get a node although the colour forward ran outside autograd (only ``features`` requires grad).
+    ``distortion``: the (mapping, near, far) of ``_distortion_spec``."""
     if contribution is not None:
         _accumulate_contribution(node, contribution, contribution_mask, geometry[0], geometry[6])
     out = (color, radii)
@@ -740,17 +873,22 @@ def _with_frame_outputs(color, radii, node, grad: bool, geometry, aux_maps, cont
         out += (_aux_maps_of(node, grad, *geometry),)
     if features is not None:
         out += (_feature_maps_of(node, grad or grad_features, features, *geometry),)
+    if distortion is not None:
+        out += (_distortion_of(node, grad, distortion, *geometry),)
     return out
 
 
 def _rasterize(fn, tensors, raster_settings, tail, geometry, densify_stats, aux_maps, contribution, contribution_mask,
-               state_key=None, features=None):
+               state_key=None, features=None, distortion=None):
     """One frame through the colour operator ``fn``.  ``tensors``: its forward's arguments in front of ``raster_settings``;
     ``tail``: those between ``stats`` and the camera's; ``geometry``: the arguments of ``_aux_maps_of`` after ``grad``
-    when ``aux_maps``, ``contribution`` or ``features`` ask for the frame's state, else None."""
+    when ``aux_maps``, ``contribution``, ``features`` or ``distortion`` ask for the frame's state, else None.
+    ``distortion``: None, or the (mapping, near, far) of ``_distortion_spec``."""
     cam = _camera_inputs(raster_settings)
     if aux_maps:
         _check_aux_request(cam, state_key, densify_stats)
+    if distortion is not None:
+        _check_distortion_request(cam, state_key, densify_stats)
     if features is not None:
         _check_feature_request(features, tensors[0], cam, state_key, densify_stats)
     if contribution is not None:
@@ -765,46 +903,52 @@ def _rasterize(fn, tensors, raster_settings, tail, geometry, densify_stats, aux_
             color, radii = fn.forward(node, *tensors, raster_settings, False, None, *tail)
             if not grad_features:
                 return _with_frame_outputs(color, radii, node, False, geometry, aux_maps, contribution,
-                                           contribution_mask, features)
+                                           contribution_mask, features, distortion=distortion)
             head = _with_frame_outputs(color, radii, node, False, geometry, aux_maps, contribution, contribution_mask)
+            dist = () if distortion is None else (_distortion_of(node, False, distortion, *geometry),)
         # only ``features`` requires grad: its node is built with grad mode as the caller has it
-        return head + (_feature_maps_of(node, True, features, *geometry),)
+        return head + (_feature_maps_of(node, True, features, *geometry),) + dist
     out = fn.apply(*tensors, raster_settings, False, densify_stats, *tail, *cam)
     if geometry is None:
         return out
-    return _with_frame_outputs(*out, out[0].grad_fn, True, geometry, aux_maps, contribution, contribution_mask, features)
+    return _with_frame_outputs(*out, out[0].grad_fn, True, geometry, aux_maps, contribution, contribution_mask, features,
+                               distortion=distortion)
 
 
 def rasterize_gaussians_fused(means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations, raster_settings,
                               densify_stats=None, visible=None, _state_key=None, aux_maps=False, contribution=None,
-                              contribution_mask=None, features=None):
+                              contribution_mask=None, features=None, distortion=None):
     """``densify_stats``: None, or (xyz_gradient_accum, denom, max_radii2D) -- the backward then also accumulates the
     densification statistics of ``scene/gaussian_model.py:775-777`` / ``train.py:130``.
     ``visible``: None, or a bool [P] tensor that receives ``radii > 0`` from the preprocess kernel.
     ``_state_key`` (internal): the capacity state of grown frames (``_grown_key``) instead of the one of P rows.
     ``aux_maps``: also return the depth / inverse-depth / alpha maps ``[3,H,W]`` (``_AuxMaps``) as a third result.
     ``contribution`` / ``contribution_mask``: accumulate the frame's contribution statistics (module docstring).
-    ``features``: float32 ``[P,C]``; also return ``feat [C,H,W] = sum w features[id]`` (``_FeatureMaps``) as the last result."""
+    ``features``: float32 ``[P,C]``; also return ``feat [C,H,W] = sum w features[id]`` (``_FeatureMaps``) after ``aux``.
+    ``distortion``: True or ``dict(mapping=, near=, far=)``; also return ``dist [1,H,W]`` (``_DistortionMap``) as the last
+    result."""
     geometry = None
-    if aux_maps or contribution is not None or features is not None:
+    distortion = _distortion_spec(distortion)
+    if aux_maps or contribution is not None or features is not None or distortion is not None:
         empty = torch.empty(0, dtype=torch.float32, device=means3D.device)
         flags = _lib.ACT_SCALE_EXP | _lib.ACT_ROT_NORMALIZE | _lib.ACT_OPACITY_SIGMOID
         geometry = (means3D, means2D, raw_opacity, raw_scales, raw_rotations, empty, raster_settings, flags)
     return _rasterize(_RasterizeGaussiansFused,
                       (means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations), raster_settings,
                       (visible, _state_key), geometry, densify_stats, aux_maps, contribution, contribution_mask, _state_key,
-                      features)
+                      features, distortion)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings, densify_stats=None, aux_maps=False, contribution=None, contribution_mask=None,
-                        features=None):
+                        features=None, distortion=None):
+    distortion = _distortion_spec(distortion)
     geometry = (means3D, means2D, opacities, scales, rotations, cov3Ds_precomp, raster_settings) \
-        if aux_maps or contribution is not None or features is not None else None
+        if aux_maps or contribution is not None or features is not None or distortion is not None else None
     return _rasterize(_RasterizeGaussians,
                       (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp),
                       raster_settings, (), geometry, densify_stats, aux_maps, contribution, contribution_mask,
-                      features=features)
+                      features=features, distortion=distortion)
 
 
 class GaussianRasterizer(nn.Module):
@@ -812,17 +956,21 @@ class GaussianRasterizer(nn.Module):
     (``gaussian_renderer/__init__.py:57``) and calls at ``:257-265``."""
 
     def __init__(self, raster_settings: GaussianRasterizationSettings, aux_maps: bool = False, contribution=None,
-                 contribution_mask: Optional[torch.Tensor] = None):
+                 contribution_mask: Optional[torch.Tensor] = None, distortion=None):
         """``aux_maps=True``: the call returns ``(color, radii, aux)`` with ``aux [3,H,W]`` = the depth
         (``sum w z``), inverse-depth (``sum w / z``) and accumulated-opacity (``sum w``) maps of the frame,
         differentiable in means3D, means2D, opacities and scales / rotations or cov3D_precomp.
         ``contribution``: a ``contribution.ContributionStats`` that every call adds its frame's per-Gaussian statistics
-        into; ``contribution_mask``: uint8 ``[H,W]``, pixels with 0 are left out.  Not differentiable."""
+        into; ``contribution_mask``: uint8 ``[H,W]``, pixels with 0 are left out.  Not differentiable.
+        ``distortion``: True, or ``dict(mapping="linear" | "ndc", near=0.2, far=100.0)``: the call's results gain a
+        trailing ``dist [1,H,W]``, the depth-distortion map (module docstring), differentiable in the geometry inputs."""
         super().__init__()
+        _distortion_spec(distortion)        # a malformed request is refused here, not at the first frame
         self.raster_settings = raster_settings
         self.aux_maps = bool(aux_maps)
         self.contribution = contribution
         self.contribution_mask = contribution_mask
+        self.distortion = distortion
 
     def markVisible(self, positions: torch.Tensor) -> torch.Tensor:
         """Frustum (near-plane) visibility of the upstream module's ``markVisible``; bool ``[P]``."""
@@ -855,7 +1003,7 @@ class GaussianRasterizer(nn.Module):
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                    cov3D_precomp, raster_settings, densify_stats, aux_maps=self.aux_maps,
                                    contribution=self.contribution, contribution_mask=self.contribution_mask,
-                                   features=features)
+                                   features=features, **({} if self.distortion is None else {"distortion": self.distortion}))
 
     def forward_fused(self, means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations, densify_stats=None,
                       features=None):
@@ -863,4 +1011,5 @@ class GaussianRasterizer(nn.Module):
         return rasterize_gaussians_fused(means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations,
                                          self.raster_settings, densify_stats, aux_maps=self.aux_maps,
                                          contribution=self.contribution, contribution_mask=self.contribution_mask,
-                                         features=features)
+                                         features=features,
+                                         **({} if self.distortion is None else {"distortion": self.distortion}))

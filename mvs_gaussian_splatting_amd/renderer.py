@@ -93,7 +93,8 @@ def _settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier):
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier: float = 1.0,
            override_color=None, grow_dir=False, densify_grad_threshold=0, iteration=None, opt=None,
            continous_dir=False, grow_distance=False, modelcg=None, cameras_extent=None, return_depth=False,
-           use_trained_exp=False, contribution=None, contribution_mask=None, features=None, return_normals=False):
+           use_trained_exp=False, contribution=None, contribution_mask=None, features=None, return_normals=False,
+           return_distortion=False, distortion_kwargs=None):
     """Render the scene; ``bg_color`` must be on the GPU.  Returns the reference's result dict
     (``gaussian_renderer/__init__.py:309-313``).  The keyword arguments after ``override_color`` are the reference's
     (``:19``) and drive the grow / learned-split branch (module docstring); the frame of a closed branch is unchanged.
@@ -124,10 +125,18 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier:
     the geometry.  ``return_normals=True``: the dict gains ``"normal"`` ``[3,H,W]`` = ``sum w n``, un-normalised, with
     ``n = features.gaussian_normals(pc.get_scaling, pc.get_rotation, ...)`` the view-space normals; with both, one
     concatenated call is split afterwards.  As with ``return_depth`` the in-backward densification statistics are not
-    taken on such a frame, and it is refused on the open grow / learned-split branch."""
+    taken on such a frame, and it is refused on the open grow / learned-split branch.
+
+    ``return_distortion=True``: the dict gains ``"distortion"`` ``[1,H,W]`` = ``sum_i sum_{j<i} w_i w_j (m_i - m_j)^2``, the
+    depth-distortion map of 2DGS (``rasterizer`` module docstring; DESIGN.md §7.16), differentiable in the geometry;
+    ``distortion_kwargs``: ``dict(mapping="linear" | "ndc", near=, far=)``, default ``"ndc"`` with near 0.2 and far 100.
+    The same two conditions as for ``return_depth`` apply."""
+    if distortion_kwargs is not None and not return_distortion:
+        raise ValueError("distortion_kwargs needs return_distortion=True")
     pkg = _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, grow_dir,
                   densify_grad_threshold, iteration, opt, continous_dir, grow_distance, modelcg, cameras_extent,
-                  return_depth, contribution, contribution_mask, features, return_normals)
+                  return_depth, contribution, contribution_mask, features, return_normals,
+                  (True if distortion_kwargs is None else dict(distortion_kwargs)) if return_distortion else None)
     if use_trained_exp:
         pkg["render"] = apply_exposure(pkg["render"], pc.get_exposure_from_name(viewpoint_camera.image_name))
     return pkg
@@ -135,8 +144,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier:
 
 def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, grow_dir, densify_grad_threshold,
             iteration, opt, continous_dir, grow_distance, modelcg, cameras_extent, return_depth, contribution=None,
-            contribution_mask=None, features=None, return_normals=False):
-    """The frame of ``render`` as the rasterizer leaves it."""
+            contribution_mask=None, features=None, return_normals=False, distortion=None):
+    """The frame of ``render`` as the rasterizer leaves it.  ``distortion``: None, or the operator's ``distortion=``."""
     which = grow.branch(iteration, opt, grow_dir, continous_dir, modelcg)
     if which is not None and contribution is not None:
         raise ValueError("contribution statistics are not available on a frame of the open grow / learned-split branch "
@@ -150,6 +159,9 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
     if which is not None and want_feat:
         raise ValueError("features / return_normals are not available on a frame of the open grow / learned-split branch "
                          "(virtual rows appended): render the maps in a frame of their own")
+    if which is not None and distortion is not None:
+        raise ValueError("return_distortion=True is not available on a frame of the open grow / learned-split branch "
+                         "(virtual rows appended): render the map in a frame of its own")
     if which is not None:
         return _render_grown(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, which, grow_dir,
                              densify_grad_threshold, continous_dir, grow_distance, modelcg, cameras_extent)
@@ -160,7 +172,7 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
     # The operator never reads (or writes) its values, so every frame's leaf aliases one cached block of zeros: a
     # fresh 72 MB memset per frame is 20 us of the 6 M-Gaussian forward.
     screenspace_points = _zero_leaf(xyz)
-    stats = None if return_depth or want_feat else _fused_stats(pc, pipe, xyz)
+    stats = None if return_depth or want_feat or distortion is not None else _fused_stats(pc, pipe, xyz)
     if stats is not None:
         screenspace_points._gsr_stats_fused = True      # read by losses.add_densification_stats
 
@@ -172,8 +184,14 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
                                          raster_settings.campos))
         extra_stats = dict(extra_stats, features=rows[0] if len(rows) == 1 else torch.cat(rows, dim=1))
 
-    def feature_entries(feat):
-        """The operator's trailing ``feat`` as the dict's ``"features"`` / ``"normal"`` entries."""
+    def feature_entries(out):
+        """The operator's trailing ``feat`` / ``dist`` as the dict's ``"features"`` / ``"normal"`` / ``"distortion"``
+        entries."""
+        if distortion is not None:
+            return {**_feature_entries(out[-2]), "distortion": out[-1]}
+        return _feature_entries(out[-1])
+
+    def _feature_entries(feat):
         if not want_feat:
             return {}
         n_user = 0 if features is None else int(features.shape[1])
@@ -188,13 +206,14 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
         # visibility_filter (= radii > 0, gaussian_renderer/__init__.py:311) is stored by the preprocess kernel itself:
         # a torch compare over 6 M radii is a 9-us kernel per frame
         visible = torch.empty(xyz.shape[0], dtype=torch.bool, device=xyz.device)
-        if return_depth or want_feat:
+        if return_depth or want_feat or distortion is not None:
             out = rasterize_gaussians_fused(xyz, screenspace_points, pc._features_dc, pc._features_rest, pc._opacity,
                                             pc._scaling, pc._rotation, raster_settings, visible=visible,
-                                            **({"aux_maps": True} if return_depth else {}), **extra_stats)
+                                            **({"aux_maps": True} if return_depth else {}), **extra_stats,
+                                            **({} if distortion is None else {"distortion": distortion}))
             return {"render": out[0], "viewspace_points": screenspace_points, "visibility_filter": visible,
                     "radii": out[1], "selected_pts_mask": None, **(_aux_entries(out[2]) if return_depth else {}),
-                    **feature_entries(out[-1])}
+                    **feature_entries(out)}
         rendered_image, radii = rasterize_gaussians_fused(xyz, screenspace_points, pc._features_dc, pc._features_rest,
                                                           pc._opacity, pc._scaling, pc._rotation, raster_settings,
                                                           densify_stats=stats, visible=visible, **extra_stats)
@@ -203,7 +222,7 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
 
     feat_kw = {"features": extra_stats.pop("features")} if want_feat else {}
     rasterizer = GaussianRasterizer(raster_settings=raster_settings, **({"aux_maps": True} if return_depth else {}),
-                                    **extra_stats)
+                                    **extra_stats, **({} if distortion is None else {"distortion": distortion}))
     scales = rotations = cov3D_precomp = None
     if getattr(pipe, "compute_cov3D_python", False):
         cov3D_precomp = pc.get_covariance(scaling_modifier)
@@ -236,7 +255,7 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
             "radii": radii,
             "selected_pts_mask": None,
             **(_aux_entries(out[2]) if return_depth else {}),
-            **feature_entries(out[-1])}
+            **feature_entries(out)}
 
 
 def _render_grown(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, which, grow_dir,

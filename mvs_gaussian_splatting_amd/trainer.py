@@ -68,6 +68,10 @@ class OptimizationParams:
     # depth-normal consistency (normal_consistency.py; 2DGS uses 0.05 from iteration 7000): 0 leaves the iteration as it is
     lambda_normal = 0.0
     normal_from_iter = 7000
+    # depth distortion (the rasterizer's distortion map; 2DGS uses 100 to 1000 from iteration 3000): 0 leaves the iteration
+    # as it is
+    lambda_dist = 0.0
+    dist_from_iter = 3000
 
     def __init__(self, **overrides):
         for k, v in overrides.items():
@@ -124,7 +128,10 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
     tan(FoVy / 2))`` joins the loss; the densification statistics are read from ``viewspace_points.grad``, as on
     ``depth_loss`` frames.  Combines with ``depth_loss``, ``train_exposure``, ``sparse_adam`` and ``strategy="mcmc"``.
     ``ValueError`` with ``pose_optimizer`` (the maps carry no camera gradient) and on a fork grow / learned-split model
-    (the maps are not rendered on its frames).  ``lambda_normal = 0``: exactly the calls made without it."""
+    (the maps are not rendered on its frames).  ``lambda_normal = 0``: exactly the calls made without it.
+    ``opt.lambda_dist > 0`` from ``opt.dist_from_iter`` on: the frame is rendered with ``return_distortion=True`` and
+    ``lambda_dist * distortion.mean()`` joins the loss; statistics, combinations and refusals as for ``lambda_normal``.
+    ``lambda_dist = 0``: exactly the calls made without it."""
     strategy = getattr(opt, "strategy", "default")
     if strategy not in ("default", "mcmc"):
         raise ValueError(f"strategy must be 'default' or 'mcmc', got {strategy!r}")
@@ -152,6 +159,15 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
                                                    "learn_split_scale")):
             raise ValueError("lambda_normal > 0 does not support the fork's grow / learned-split models: render refuses "
                              "return_depth / return_normals on their frames (virtual rows appended)")
+    dist_on = float(getattr(opt, "lambda_dist", 0.0)) > 0.0 and iteration >= int(getattr(opt, "dist_from_iter", 0))
+    if dist_on:
+        if pose_optimizer is not None:
+            raise ValueError("lambda_dist > 0 does not combine with pose_optimizer: the distortion map carries no camera "
+                             "gradient, so the pose would be refined against the colour loss alone")
+        if is_fork(model) or any(flag(n) for n in ("grow_dir", "continous_dir", "learn_split_distance",
+                                                   "learn_split_scale")):
+            raise ValueError("lambda_dist > 0 does not support the fork's grow / learned-split models: render refuses "
+                             "return_distortion on their frames (virtual rows appended)")
     if first_reset is None:
         first_reset = flag("white_background")
     todo = schedule(opt, iteration, first_reset)
@@ -164,6 +180,7 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
                  modelcg=dataset, cameras_extent=cameras_extent,                                # :91
                  **({"return_depth": True} if depth_loss is not None or normal_on else {}),
                  **({"return_normals": True} if normal_on else {}),
+                 **({"return_distortion": True} if dist_on else {}),
                  **({"use_trained_exp": True} if train_exposure else {}))
     gt = camera.original_image if gt_image is None else gt_image
     loss = l1_dssim_loss(pkg["render"], gt.to(pkg["render"].device), opt.lambda_dssim)          # :99-101
@@ -177,6 +194,8 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
     if normal_on:
         loss = loss + float(opt.lambda_normal) * normal_consistency_loss(
             pkg["depth"], pkg["alpha"], pkg["normal"], math.tan(camera.FoVx * 0.5), math.tan(camera.FoVy * 0.5))
+    if dist_on:
+        loss = loss + float(opt.lambda_dist) * pkg["distortion"].mean()
     loss.backward()                                                                             # :107
     with torch.no_grad():
         if mcmc:
