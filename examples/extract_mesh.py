@@ -2,12 +2,15 @@
 the surface by marching tetrahedra, all on the HIP path (``mvs_gaussian_splatting_amd/tsdf.py``).
 
     python examples/extract_mesh.py -m <model directory> [--iteration N] [--voxel_size S | --resolution R]
-                                    [--sdf_trunc T] [--alpha_min A] [--max_depth D] [-s <dataset>] [-r ...]
+                                    [--sdf_trunc T] [--alpha_min A] [--max_depth D] [--depth_ratio R]
+                                    [-s <dataset>] [-r ...]
 
 The scene is loaded as ``examples/render.py`` loads it (``cfg_args.json`` of the model directory; ``-s`` and the other
 switches override it).  The volume bounds the bulk of the model's positions (``tsdf.volume_for_points``); ``--resolution``
 is the number of samples along its longest side (default 256), ``--sdf_trunc`` defaults to 4 voxels.  Every training
-view contributes its expected depth ``depth / alpha`` where ``alpha >= --alpha_min``.
+view contributes its expected depth ``depth / alpha`` where ``alpha >= --alpha_min``; with ``--depth_ratio R`` (in [0, 1])
+the blend ``(1 - R) expected + R median`` depth (``surface_depth``): 2DGS meshes bounded scenes at 1, where a pixel that sees
+a thin edge in front of a far wall lands on one of the two instead of between them.
 
 writes ``<model>/mesh/iteration_<N>/tsdf_mesh.ply`` (binary PLY, vertex colours from the renders).
 """
@@ -24,7 +27,8 @@ from mvs_gaussian_splatting_amd.ply_io import write_ply_mesh  # noqa: E402
 from mvs_gaussian_splatting_amd.synthetic import PipelineParams  # noqa: E402
 
 
-def extract(dataset, iteration, voxel_size=None, resolution=None, sdf_trunc=None, alpha_min=0.5, max_depth=None):
+def extract(dataset, iteration, voxel_size=None, resolution=None, sdf_trunc=None, alpha_min=0.5, max_depth=None,
+            depth_ratio=0.0):
     with torch.no_grad():
         gaussians = GaussianModel(dataset.sh_degree)
         scene = Scene(dataset, gaussians, load_iteration=iteration, shuffle=False)
@@ -34,7 +38,7 @@ def extract(dataset, iteration, voxel_size=None, resolution=None, sdf_trunc=None
         print(f"volume {volume.dims[0]} x {volume.dims[1]} x {volume.dims[2]}, voxel {volume.voxel_size:.5g}, "
               f"truncation {volume.sdf_trunc:.5g}")
         fuse_views(scene.getTrainCameras(), gaussians, PipelineParams(), background, volume, alpha_min=alpha_min,
-                   max_depth=max_depth)
+                   max_depth=max_depth, **({"depth_ratio": depth_ratio} if depth_ratio else {}))
         vertices, faces, colors = volume.extract_mesh()
     path = os.path.join(dataset.model_path, "mesh", "iteration_{}".format(scene.loaded_iter), "tsdf_mesh.ply")
     write_ply_mesh(path, vertices, faces, colors)
@@ -58,6 +62,8 @@ def main(argv=None):
     ap.add_argument("--sdf_trunc", type=float, default=None, help="truncation distance (4 voxels)")
     ap.add_argument("--alpha_min", type=float, default=0.5)
     ap.add_argument("--max_depth", type=float, default=None)
+    ap.add_argument("--depth_ratio", type=float, default=0.0,
+                    help="share of the median depth in the fused surface (2DGS: 0 unbounded, 1 bounded)")
     args = ap.parse_args(argv)
     fields = {}
     cfg = os.path.join(args.model_path, "cfg_args.json")
@@ -73,7 +79,8 @@ def main(argv=None):
         ap.error("no cfg_args.json in the model directory: give the dataset with -s")
     dataset = ModelParams(model_path=args.model_path, **fields)
     print("Extracting a mesh from " + args.model_path)
-    extract(dataset, args.iteration, args.voxel_size, args.resolution, args.sdf_trunc, args.alpha_min, args.max_depth)
+    extract(dataset, args.iteration, args.voxel_size, args.resolution, args.sdf_trunc, args.alpha_min, args.max_depth,
+            args.depth_ratio)
 
 
 if __name__ == "__main__":

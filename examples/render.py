@@ -3,7 +3,7 @@ write every view of the scene as PNG.
 
     python examples/render.py -m <model directory> [--iteration N] [--skip_train] [--skip_test]
                               [-s <COLMAP or Blender directory>] [-r ...] [--eval] [--white_background] [--depth]
-                              [--use_trained_exp] [--normals] [--depth_normals] [--distortion]
+                              [--use_trained_exp] [--normals] [--depth_normals] [--distortion] [--median_depth]
 
 The dataset's location and options come from the ``cfg_args.json`` that ``examples/train.py -s ... -m ...`` left in the
 model directory; ``-s`` and the other switches override it.
@@ -18,6 +18,9 @@ as ``normal * 0.5 + 0.5`` in 8 bits.
 ``--depth_normals`` also writes ``.../depth_normal/%05d.png``: the normals of the rendered depth surface,
 ``depth_to_normals(depth, alpha, ...)`` (``normal_consistency.py``), as ``depth_normal * 0.5 + 0.5`` in 8 bits -- the map
 the consistency loss pulls ``--normals`` towards; pixels without a valid normal come out mid-grey.
+``--median_depth`` also writes ``.../median_depth/%05d.png``: 2DGS's median depth (``render(return_median_depth=True)``)
+as a 16-bit greyscale PNG scaled like ``--depth`` (``.../median_depth/scales.json``), and ``.../median_depth/%05d_id.npy``:
+the int32 ``[H,W]`` map of the Gaussian that owns each pixel (-1: none).
 ``--use_trained_exp`` renders every view that has one with the exposure saved in the iteration's ``exposure.json``
 (``examples/train.py --train_exposure``); test views have none and are rendered as they are.
 """
@@ -50,6 +53,17 @@ def save_distortion_png(dist, path):
     return step
 
 
+def save_median_png(median, median_id, path, id_path):
+    """The median depth as 16-bit greyscale and the id map as ``.npy``; returns the depth one step stands for."""
+    import numpy as np
+    from PIL import Image
+    top = float(median.max())
+    step = top / 65535.0 if top > 0 else 1.0
+    Image.fromarray(torch.round(median[0] / step).clamp(0, 65535).cpu().numpy().astype(np.uint16)).save(path)
+    np.save(id_path, median_id.cpu().numpy())
+    return step
+
+
 def save_depth_png(depth, alpha, path):
     """``depth / alpha`` as 16-bit greyscale; returns the depth one step stands for."""
     import numpy as np
@@ -63,7 +77,7 @@ def save_depth_png(depth, alpha, path):
 
 
 def render_set(model_path, name, iteration, views, gaussians, pipeline, background, depth=False,
-               use_trained_exp=False, normals=False, depth_normals=False, distortion=False):
+               use_trained_exp=False, normals=False, depth_normals=False, distortion=False, median_depth=False):
     render_path = os.path.join(model_path, name, "ours_{}".format(iteration), "renders")
     gts_path = os.path.join(model_path, name, "ours_{}".format(iteration), "gt")
     depth_path = os.path.join(model_path, name, "ours_{}".format(iteration), "depth")
@@ -82,11 +96,16 @@ def render_set(model_path, name, iteration, views, gaussians, pipeline, backgrou
     dist_scales = []
     if distortion:
         os.makedirs(distortion_path, exist_ok=True)
+    median_path = os.path.join(model_path, name, "ours_{}".format(iteration), "median_depth")
+    median_scales = []
+    if median_depth:
+        os.makedirs(median_path, exist_ok=True)
     for idx, view in enumerate(views):
         with_exp = use_trained_exp and view.image_name in (gaussians.pretrained_exposures or {})
         pkg = render(view, gaussians, pipeline, background, **({"return_depth": True} if depth or depth_normals else {}),
                      **({"use_trained_exp": True} if with_exp else {}), **({"return_normals": True} if normals else {}),
-                     **({"return_distortion": True} if distortion else {}))
+                     **({"return_distortion": True} if distortion else {}),
+                     **({"return_median_depth": True} if median_depth else {}))
         rendering = pkg["render"]
         save_png(rendering, os.path.join(render_path, "{0:05d}".format(idx) + ".png"))
         save_png(view.original_image[0:3, :, :].to(rendering.device), os.path.join(gts_path, "{0:05d}".format(idx) + ".png"))
@@ -100,6 +119,12 @@ def render_set(model_path, name, iteration, views, gaussians, pipeline, backgrou
         if distortion:
             dist_scales.append(save_distortion_png(pkg["distortion"],
                                                    os.path.join(distortion_path, "{0:05d}".format(idx) + ".png")))
+        if median_depth:
+            stem = os.path.join(median_path, "{0:05d}".format(idx))
+            median_scales.append(save_median_png(pkg["median_depth"], pkg["median_id"], stem + ".png", stem + "_id.npy"))
+    if median_depth:
+        with open(os.path.join(median_path, "scales.json"), "w") as f:
+            json.dump(median_scales, f)
     if depth:
         with open(os.path.join(depth_path, "scales.json"), "w") as f:
             json.dump(scales, f)
@@ -109,7 +134,7 @@ def render_set(model_path, name, iteration, views, gaussians, pipeline, backgrou
 
 
 def render_sets(dataset, iteration, pipeline, skip_train=False, skip_test=False, depth=False, use_trained_exp=False,
-                normals=False, depth_normals=False, distortion=False):
+                normals=False, depth_normals=False, distortion=False, median_depth=False):
     with torch.no_grad():
         gaussians = GaussianModel(dataset.sh_degree)
         scene = Scene(dataset, gaussians, load_iteration=iteration, shuffle=False)
@@ -119,10 +144,10 @@ def render_sets(dataset, iteration, pipeline, skip_train=False, skip_test=False,
             raise FileNotFoundError("--use_trained_exp: the iteration's point-cloud directory has no exposure.json")
         if not skip_train:
             render_set(dataset.model_path, "train", scene.loaded_iter, scene.getTrainCameras(), gaussians, pipeline,
-                       background, depth, use_trained_exp, normals, depth_normals, distortion)
+                       background, depth, use_trained_exp, normals, depth_normals, distortion, median_depth)
         if not skip_test:
             render_set(dataset.model_path, "test", scene.loaded_iter, scene.getTestCameras(), gaussians, pipeline,
-                       background, depth, use_trained_exp, normals, depth_normals, distortion)
+                       background, depth, use_trained_exp, normals, depth_normals, distortion, median_depth)
     return scene
 
 
@@ -143,6 +168,8 @@ def main(argv=None):
                     help="also write the normals of the rendered depth surface of every view as PNG")
     ap.add_argument("--distortion", action="store_true",
                     help="also write the depth-distortion map of every view as a 16-bit PNG scaled by its maximum")
+    ap.add_argument("--median_depth", action="store_true",
+                    help="also write the median depth of every view as a 16-bit PNG and the Gaussian id map as .npy")
     ap.add_argument("--use_trained_exp", action="store_true", help="apply the saved per-image exposures")
     args = ap.parse_args(argv)
     fields = {}
@@ -158,7 +185,7 @@ def main(argv=None):
     dataset = ModelParams(model_path=args.model_path, **fields)
     print("Rendering " + args.model_path)
     render_sets(dataset, args.iteration, PipelineParams(), args.skip_train, args.skip_test, args.depth,
-                args.use_trained_exp, args.normals, args.depth_normals, args.distortion)
+                args.use_trained_exp, args.normals, args.depth_normals, args.distortion, args.median_depth)
 
 
 if __name__ == "__main__":

@@ -10,14 +10,15 @@ SH degree steps, densification, opacity resets, the optional opacity sparsity te
                               [--exposure_lr_delay_steps N] [--exposure_lr_delay_mult M]]
                              [--prune_iterations N [N ...] --prune_keep_ratio R [--prune_kind sum|max|count|mean]]
                              [--strategy mcmc --cap_max N [--noise_lr LR] [--opacity_reg W] [--scale_reg W]]
-                             [--lambda_normal L [--normal_from_iter N]]
+                             [--lambda_normal L [--normal_from_iter N] [--depth_ratio R]]
                              [--lambda_dist L [--dist_from_iter N]]
 
 ``--strategy mcmc --cap_max N`` (both forms) densifies the MCMC way (``mcmc.py``): a budget of N Gaussians, dead ones
 relocated onto live ones, 5 % growth a round, position noise and L1 priors on opacity and scale.
 ``--lambda_normal L`` (both forms; off by default) adds the depth-normal consistency term of 2DGS from iteration
 ``--normal_from_iter`` on (``normal_consistency.py``): the normals composited from the Gaussians are pulled towards the
-normals of the rendered depth surface.  2DGS uses 0.05 from iteration 7000.
+normals of the rendered depth surface.  2DGS uses 0.05 from iteration 7000.  ``--depth_ratio R`` (in [0, 1]) takes that
+surface to be ``(1 - R) expected + R median`` depth: 2DGS uses 0 for unbounded scenes and 1 for bounded ones.
 ``--lambda_dist L`` (both forms; off by default) adds the depth-distortion term of 2DGS from iteration
 ``--dist_from_iter`` on: ``L`` times the mean of the rasterizer's distortion map, which pulls every ray's blending weights
 together in depth.  2DGS uses 100 to 1000 from iteration 3000.
@@ -155,7 +156,7 @@ def strategy_options(args):
         raise SystemExit("--strategy mcmc needs --cap_max N, the budget of Gaussians")
     return dict(strategy=args.strategy, cap_max=args.cap_max, noise_lr=args.noise_lr, opacity_reg=args.opacity_reg,
                 scale_reg=args.scale_reg, lambda_normal=args.lambda_normal, normal_from_iter=args.normal_from_iter,
-                lambda_dist=args.lambda_dist, dist_from_iter=args.dist_from_iter)
+                lambda_dist=args.lambda_dist, dist_from_iter=args.dist_from_iter, depth_ratio=args.depth_ratio)
 
 
 def train_scene(args, dev):
@@ -247,6 +248,9 @@ def main(argv=None):
                     help="weight of the depth-normal consistency term (normal_consistency.py); 2DGS uses 0.05; 0: off")
     ap.add_argument("--normal_from_iter", type=int, default=OptimizationParams.normal_from_iter,
                     help="first iteration the term joins the loss at (2DGS: 7000)")
+    ap.add_argument("--depth_ratio", type=float, default=OptimizationParams.depth_ratio,
+                    help="with --lambda_normal: the share of the median depth in the surface the term differentiates "
+                         "(2DGS: 0 unbounded, 1 bounded)")
     ap.add_argument("--lambda_dist", type=float, default=OptimizationParams.lambda_dist,
                     help="weight of the depth-distortion term (the rasterizer's distortion map); 2DGS uses 100 to 1000; 0: off")
     ap.add_argument("--dist_from_iter", type=int, default=OptimizationParams.dist_from_iter,

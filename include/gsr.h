@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 29
+#define GSR_ABI_VERSION 30
 
 enum {
   GSR_OK = 0,
@@ -289,6 +289,30 @@ size_t gsr_distortion_backward_bytes(int32_t P);
 int gsr_distortion_backward(const GsrParams* p, const GsrAuxFrame* frame, int32_t mapping, float near, float far,
                             const float* state, const float* dL_ddist, void* acc_ws, size_t acc_ws_bytes,
                             const GsrAuxGrads* grads, void* stream);
+
+/* ---- median-depth map and Gaussian id map of a rendered frame, ABI v30 (csrc/median.hip) ------------
+ * With i, z_i as above (the entries of the depth / alpha maps, in list order) and T_i the colour pass's transmittance
+ * BEFORE entry i (float32, its single-fma update), k* = the last composited entry with T_i > 0.5 -- the rule of 2DGS,
+ * `if (T > 0.5) { median_depth = depth; median_contributor = i; }`:
+ *     median = z_{k*},   median_id = id_{k*} (the Gaussian's row in the caller's tensors)
+ * The first composited entry always qualifies (T = 1); a ray that never gets below one half keeps its last composited
+ * entry; a pixel without a composited entry gets 0 / -1.  The walk of a pixel ends where its T reaches one half.
+ * median: device [1,H,W] float32, median_id: device [H,W] int32, state: device [H,W] uint32, all three written in full,
+ * the same bits from run to run.  state is what the backward needs per pixel (the list position of k*); its content is
+ * opaque and belongs to the frame it was written for.  Every argument is checked before any HIP call.  Nothing allocates,
+ * synchronises or reads back. */
+int gsr_median_depth_forward(const GsrAuxFrame* frame, float* median, int32_t* median_id, uint32_t* state, void* stream);
+/* The selection is piecewise constant: dL/dz_{k*} = dL_dmedian[pixel] and nothing else, so only means3D receives a
+ * gradient: dL_dmeans3D[id] = (sum over the pixels that chose id of dL_dmedian) * viewmatrix[0:3, 2].
+ * p: the inputs of the frame's forward; only P, width, height, forward_only, debug and viewmatrix are read.
+ * state: what the forward wrote; dL_dmedian: device [1,H,W].  acc_ws: device scratch of
+ * gsr_median_depth_backward_bytes(P) bytes, 256-byte aligned: a [P] float accumulator (the call zero-fills it) that
+ * receives at most one float atomic per tile and list entry.  dL_dmeans3D: device [P,3], written in full (rows no pixel
+ * chose are zero).  GSR_E_CAPACITY for a short workspace, GSR_E_ALIGN for acc_ws.  Gradients are reproducible to
+ * rounding, not bit for bit (float atomics). */
+size_t gsr_median_depth_backward_bytes(int32_t P);
+int gsr_median_depth_backward(const GsrParams* p, const GsrAuxFrame* frame, const uint32_t* state, const float* dL_dmedian,
+                              void* acc_ws, size_t acc_ws_bytes, float* dL_dmeans3D, void* stream);
 
 /* ---- per-Gaussian contribution statistics of a rendered frame, ABI v24 (csrc/contribution.hip) ----------------------
  * For Gaussian g let p run over the pixels where the colour pass composited g (the rule above: the first n_contrib

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # instead of copying it over the in-tree library
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")
 
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 
 class GsrParams(C.Structure):
@@ -168,6 +168,12 @@ SYMBOLS = {
     "gsr_distortion_backward": (C.c_int, [C.POINTER(GsrParams), C.POINTER(GsrAuxFrame), C.c_int32, C.c_float, C.c_float,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(GsrAuxGrads),
                                           C.c_void_p]),
+    # median-depth map [1,H,W], Gaussian id map [H,W] (int32) and per-pixel state [H,W] (uint32) of a rendered frame, and
+    # the map's gradient for means3D (csrc/median.hip)
+    "gsr_median_depth_forward": (C.c_int, [C.POINTER(GsrAuxFrame), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsr_median_depth_backward_bytes": (C.c_size_t, [C.c_int32]),
+    "gsr_median_depth_backward": (C.c_int, [C.POINTER(GsrParams), C.POINTER(GsrAuxFrame), C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     # per-Gaussian contribution statistics of a rendered frame, added into int64 [P,3] (csrc/contribution.hip)
     "gsr_contribution_accumulate": (C.c_int, [C.POINTER(GsrAuxFrame), C.c_void_p, C.c_void_p, C.c_void_p]),
     "gsr_mark_visible": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

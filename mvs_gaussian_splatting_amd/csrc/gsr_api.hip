@@ -771,6 +771,54 @@ int gsr_distortion_backward(const GsrParams* p, const GsrAuxFrame* f, int32_t ma
   return check(p, s, "aux_geom_bwd");
 }
 
+// ---- median-depth map and Gaussian id map (csrc/median.hip) ----------------------------------------------------------
+size_t gsr_median_depth_backward_bytes(int32_t P) { return align_up(4 * (size_t)(P > 0 ? P : 1), 256); }
+
+int gsr_median_depth_forward(const GsrAuxFrame* f, float* median, int32_t* median_id, uint32_t* state, void* stream) {
+  if (int rc = validate_aux_frame(f)) return rc;
+  if (!median || !median_id || !state) return fail(GSR_E_BADARG, "median / median_id / state is NULL");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const ImageLayout I(f->width, f->height);
+  if (f->P == 0 || f->num_rendered == 0) {      // nothing was binned: every list is empty
+    const size_t hw = (size_t)f->width * f->height;
+    GSR_HIP(hipMemsetAsync(median, 0, 4 * hw, s));
+    GSR_HIP(hipMemsetAsync(median_id, 0xff, 4 * hw, s));      // -1
+    GSR_HIP(hipMemsetAsync(state, 0xff, 4 * hw, s));          // no entry
+    return 0;
+  }
+  const GeomLayout L(f->P);
+  const SortedViews sv = sorted_views(f->bin_ws, f->num_rendered, f->num_visible, f->width, f->height, f->binning_mode);
+  launch_median_depth_fwd(f->width, f->height, at<uint2>(f->img_ws, I.ranges), sv.point_list, at<GeomRec>(f->geom_ws, L.rec),
+                          at<BinInfo>(f->geom_ws, L.bin), at<uint32_t>(f->img_ws, I.n_contrib),
+                          at<uint32_t>(f->img_ws, I.tile_order), median, median_id, state, s);
+  return check(nullptr, s, "median_depth_fwd");
+}
+
+int gsr_median_depth_backward(const GsrParams* p, const GsrAuxFrame* f, const uint32_t* state, const float* dL_dmedian,
+                              void* acc_ws, size_t acc_ws_bytes, float* dL_dmeans3D, void* stream) {
+  if (!p) return fail(GSR_E_BADARG, "params is NULL");
+  if (p->forward_only) return fail(GSR_E_BADARG, "the forward ran with forward_only = 1: no state for a backward");
+  if (int rc = validate_aux_frame(f)) return rc;
+  if (f->P != p->P || f->width != p->width || f->height != p->height) return fail(GSR_E_BADARG, "frame and params disagree");
+  if (p->P == 0) return 0;
+  if (!p->viewmatrix) return fail(GSR_E_BADARG, "viewmatrix must be non-NULL");
+  if (!state || !dL_dmedian || !acc_ws || !dL_dmeans3D) return fail(GSR_E_BADARG, "NULL workspace / input / output");
+  if (acc_ws_bytes < gsr_median_depth_backward_bytes(p->P)) return fail(GSR_E_CAPACITY, "accumulator workspace too small");
+  if (((uintptr_t)acc_ws & 255u) != 0) return fail(GSR_E_ALIGN, "acc_ws must be 256-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const ImageLayout I(f->width, f->height);
+  float* acc = static_cast<float*>(acc_ws);
+  GSR_HIP(hipMemsetAsync(acc, 0, 4 * (size_t)p->P, s));
+  if (f->num_rendered > 0) {
+    const SortedViews sv = sorted_views(f->bin_ws, f->num_rendered, f->num_visible, f->width, f->height, f->binning_mode);
+    launch_median_depth_bwd(f->width, f->height, at<uint2>(f->img_ws, I.ranges), sv.point_list,
+                            at<uint32_t>(f->img_ws, I.tile_order), state, dL_dmedian, acc, s);
+    if (int rc = check(p, s, "median_depth_bwd")) return rc;
+  }
+  launch_median_depth_finish(p->P, p->viewmatrix, acc, dL_dmeans3D, s);
+  return check(p, s, "median_depth_finish");
+}
+
 // ---- per-Gaussian contribution statistics (csrc/contribution.hip) --------------------------------------------------
 int gsr_contribution_accumulate(const GsrAuxFrame* f, const uint8_t* pixel_mask, int64_t* stats, void* stream) {
   if (int rc = validate_aux_frame(f)) return rc;

@@ -134,6 +134,17 @@ void launch_distortion_bwd(int W, int H, const uint2* ranges, const uint32_t* po
                            int mapping, float near, float far, const float* state, const float* dL_ddist, float* acc,
                            hipStream_t s);
 
+// median.hip: the median-depth map median [1,H,W] of a rendered frame (z of the last composited entry whose transmittance
+// in front of it exceeds one half; the entries of depth.hip), the id of that entry's Gaussian median_id [H,W] (-1: none) and
+// its list position state [H,W] (0xffffffff: none); the backward adds dL_dmedian into acc [P] (zeroed by the caller, one
+// global atomic per tile and entry) and the finish kernel writes d_means3D [P,3] = acc * viewmatrix[0:3, 2] in full
+void launch_median_depth_fwd(int W, int H, const uint2* ranges, const uint32_t* point_list, const GeomRec* rec,
+                             const BinInfo* bin, const uint32_t* n_contrib, const uint32_t* tile_order, float* median,
+                             int32_t* median_id, uint32_t* state, hipStream_t s);
+void launch_median_depth_bwd(int W, int H, const uint2* ranges, const uint32_t* point_list, const uint32_t* tile_order,
+                             const uint32_t* state, const float* dL_dmedian, float* acc, hipStream_t s);
+void launch_median_depth_finish(int P, const float* viewmatrix, const float* acc, float* d_means3D, hipStream_t s);
+
 // contribution.hip: per-Gaussian blending-weight statistics of a rendered frame, added into stats [P,3] (int64: sum of
 // round(w 2^30), pixel count, float bits of the largest w) with integer atomics; pixel_mask: nullptr or [H,W] bytes
 void launch_contribution(int W, int H, const uint2* ranges, const uint32_t* point_list, const GeomRec* rec,

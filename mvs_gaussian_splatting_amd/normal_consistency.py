@@ -14,6 +14,11 @@ finite and above 1e-20.  The loss is ``sum_valid (alpha - normal . n_d) / (H W)`
 contributors of a pixel share one normal.  The gradients reach ``depth`` (through ``n_d`` of the four neighbours),
 ``alpha`` and ``normal``; which pixels are valid is a decision and carries none.  Value, gradients and the depth normals
 come from one launch and are the same bits from run to run.
+
+``median=`` / ``depth_ratio=`` (2DGS's ``depth_ratio``): the surface is the blend ``(1 - r) depth / alpha
++ r median`` of the expected and the median depth (``render(return_median_depth=True)``).  The kernel is fed ``depth' =
+(1 - r) depth + r median alpha`` -- built with torch ops, so the gradients reach all three maps -- whose quotient by
+``alpha`` is that blend.  With ``median=None`` or ``r = 0`` the tensors passed are the ones passed without the arguments.
 """
 from __future__ import annotations
 
@@ -22,6 +27,7 @@ import math
 import torch
 
 from . import _lib
+from .surface import blend_weighted_depth
 
 
 def _check_maps(what: str, depth, alpha, normal, tanfovx, tanfovy, alpha_min):
@@ -93,16 +99,23 @@ class _NormalConsistency(torch.autograd.Function):
 
 
 def normal_consistency_loss(depth: torch.Tensor, alpha: torch.Tensor, normal: torch.Tensor, tanfovx: float,
-                            tanfovy: float, alpha_min: float = 0.5, return_record: bool = False):
+                            tanfovy: float, alpha_min: float = 0.5, return_record: bool = False, median=None,
+                            depth_ratio: float = 0.0):
     """The loss of the module docstring as a 0-dim device tensor, from ``depth [1,H,W]``, ``alpha [1,H,W]`` and
     ``normal [3,H,W]`` -- the ``"depth"``, ``"alpha"`` and ``"normal"`` entries of ``render`` -- float32 on one GPU (made
     contiguous if they are not).  One kernel call computes the value and, when an input requires a gradient, the three
     unit gradients; the backward multiplies them by the upstream gradient on the device.  Nothing is read back.
     ``alpha_min`` is the coverage threshold, the default that of ``tsdf.fuse_views``.
     return_record: also return the kernel's record, float32 ``[4]`` on the device: ``(loss, n_valid as uint32 bits, 0,
-    0)`` (``record.view(torch.int32)[1]`` is the number of valid pixels)."""
+    0)`` (``record.view(torch.int32)[1]`` is the number of valid pixels).
+    median, depth_ratio: the ``"median_depth"`` entry of ``render`` and 2DGS's ``depth_ratio`` in [0, 1] (module
+    docstring); ``depth_ratio > 0`` needs ``median``."""
     if not isinstance(normal, torch.Tensor):
         raise TypeError(f"normal_consistency_loss: normal must be a torch.Tensor, got {type(normal).__name__}")
+    if median is not None or depth_ratio != 0.0:
+        if not isinstance(depth, torch.Tensor) or not isinstance(alpha, torch.Tensor):
+            raise TypeError("normal_consistency_loss: depth and alpha must be torch.Tensors")
+        depth = blend_weighted_depth(depth, alpha, median, depth_ratio, "normal_consistency_loss")
     H, W = _check_maps("normal_consistency_loss", depth, alpha, normal, tanfovx, tanfovy, alpha_min)
     holder = []
     loss = _NormalConsistency.apply(depth, alpha, normal, H, W, tanfovx, tanfovy, alpha_min, holder)
@@ -111,10 +124,14 @@ def normal_consistency_loss(depth: torch.Tensor, alpha: torch.Tensor, normal: to
 
 @torch.no_grad()
 def depth_to_normals(depth: torch.Tensor, alpha: torch.Tensor, tanfovx: float, tanfovy: float,
-                     alpha_min: float = 0.5) -> torch.Tensor:
+                     alpha_min: float = 0.5, median=None, depth_ratio: float = 0.0) -> torch.Tensor:
     """``[3,H,W]`` view-space unit normals of the depth surface ``depth / alpha`` (+z forward, x right, y down; facing
     the camera), zeros on the pixels that are not valid (module docstring).  The loss kernel run forward only: the same
-    bits as the normals it uses.  No gradient."""
+    bits as the normals it uses.  No gradient.  ``median`` / ``depth_ratio``: as in ``normal_consistency_loss``."""
+    if median is not None or depth_ratio != 0.0:
+        if not isinstance(depth, torch.Tensor) or not isinstance(alpha, torch.Tensor):
+            raise TypeError("depth_to_normals: depth and alpha must be torch.Tensors")
+        depth = blend_weighted_depth(depth, alpha, median, depth_ratio, "depth_to_normals")
     H, W = _check_maps("depth_to_normals", depth, alpha, None, tanfovx, tanfovy, alpha_min)
     zeros = torch.zeros((3, H, W), dtype=torch.float32, device=depth.device)
     return _call(depth, alpha, zeros, H, W, tanfovx, tanfovy, alpha_min, False, True)[2]

@@ -43,6 +43,13 @@ far=)``; ``True`` is ``"ndc"`` with near 0.2, far 100, what 2DGS trains with) ap
 2DGS over the colour pass's contributors, evaluated without the cancelling ``A M2 - M1^2`` form (``csrc/distortion.hip``;
 DESIGN.md §7.16), behind a node of its own (``_DistortionMap``) that reads the colour node's frame.  Without ``distortion``
 nothing of it runs.
+
+Median depth.  ``GaussianRasterizer(settings, median_depth=True)`` appends two tensors to the call's results, after ``aux``,
+``feat`` and ``dist``: ``median [1,H,W]``, the view depth of the last composited entry in front of which the colour pass's
+transmittance still exceeds one half (2DGS's median depth; 0 where nothing was composited), and ``median_id [H,W]`` (int32),
+the row of that entry's Gaussian (-1 where nothing was composited) (``csrc/median.hip``), behind a node of
+its own (``_MedianDepth``) that reads the colour node's frame.  Only means3D receives a gradient.  Without ``median_depth``
+nothing of it runs.
 """
 from __future__ import annotations
 
@@ -789,6 +796,92 @@ def _check_distortion_request(cam, state_key=None, densify_stats=None) -> None:
         raise ValueError("distortion is not available on a frame with grown / split rows appended")
 
 
+class _MedianDepth(torch.autograd.Function):
+    """``median [1,H,W]`` and ``median_id [H,W]`` (int32) of a frame the colour operator has rendered (``include/gsr.h``:
+    gsr_median_depth_*; ``csrc/median.hip``).  A node of its own next to the colour node, in the style of
+    ``_DistortionMap``: it reads the colour node's frame by reference.  The selection of the median entry is piecewise
+    constant, so means3D is the node's only differentiable input (``dL/dmeans3D[id] = sum of the gradient over the
+    pixels that chose id, times viewmatrix[0:3, 2]``); means2D, opacities, scales, rotations and cov3D_precomp are not
+    inputs of the node and receive nothing from it (``None``, not zeros).  ``median_id`` is marked non-differentiable.  The
+    forward also leaves the per-pixel ``state [H,W]`` (uint32) the backward reads."""
+
+    @staticmethod
+    def forward(ctx, means3D, raster_settings: GaussianRasterizationSettings, frame: _Frame, binning_mode: int):
+        lib = _lib.load()
+        dev = _require_gpu(means3D)
+        P = int(means3D.shape[0])
+        means3D = _f32c(means3D, "means3D", dev)
+        H, W = int(raster_settings.image_height), int(raster_settings.image_width)
+        median = torch.empty(1, H, W, dtype=torch.float32, device=dev)
+        median_id = torch.empty(H, W, dtype=torch.int32, device=dev)
+        state = torch.empty(H, W, dtype=torch.int32, device=dev)      # uint32 on the device; opaque here
+        with torch.cuda.device(dev):
+            _lib.check(lib.gsr_median_depth_forward(C.byref(_aux_frame(frame, P, W, H, binning_mode)), median.data_ptr(),
+                                                    median_id.data_ptr(), state.data_ptr(), _stream(dev)),
+                       "gsr_median_depth_forward")
+        ctx.raster_settings = raster_settings
+        ctx.layout = (frame.layout_R, frame.layout_V)
+        ctx.frame_pending = frame.pending
+        ctx.counts = frame.counts
+        ctx.binning_mode = binning_mode
+        ctx.save_for_backward(means3D, state, frame.radii, frame.geom, frame.binning, frame.img)
+        ctx.mark_non_differentiable(median_id)
+        ctx.set_materialize_grads(False)
+        return median, median_id
+
+    @staticmethod
+    def backward(ctx, grad_median, _grad_id):
+        if grad_median is None:
+            return (None,) * 4
+        lib = _lib.load()
+        saved = ctx.saved_tensors
+        means3D, state = saved[:2]
+        frame, binning_mode = _frame_of(ctx, saved)
+        settings = ctx.raster_settings
+        dev = means3D.device
+        P = int(means3D.shape[0])
+        H, W = int(settings.image_height), int(settings.image_width)
+        if frame.pending is not None:
+            _verify(frame.pending, block=True)      # deferred mode: as the colour backward
+        grad_median = _f32c(grad_median, "grad_median", dev)
+        empty = torch.empty(0, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            params, keep = _make_params(dev, settings, means3D, empty, empty, empty, empty, empty, empty)
+            params.profile = None
+            params.binning_mode = binning_mode
+            g_means3D = torch.empty(P, 3, dtype=torch.float32, device=dev)
+            nbytes = lib.gsr_median_depth_backward_bytes(P)
+            acc = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            _lib.check(lib.gsr_median_depth_backward(C.byref(params), C.byref(_aux_frame(frame, P, W, H, binning_mode)),
+                                                     state.data_ptr(), grad_median.data_ptr(), acc.data_ptr(), nbytes,
+                                                     _ptr(g_means3D), _stream(dev)), "gsr_median_depth_backward")
+        del keep
+        return (g_means3D, None, None, None)
+
+
+def _median_of(node, grad: bool, means3D, means2D, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
+               act_flags: int = 0):
+    """(median, median_id) of the colour node's frame; of ``geometry`` only means3D and the settings are read."""
+    frame, mode = _frame_of(node)
+    if grad:
+        return _MedianDepth.apply(means3D, raster_settings, frame, mode)
+    return _MedianDepth.forward(_NoGraph(), means3D, raster_settings, frame, mode)
+
+
+def _check_median_request(cam, state_key=None, densify_stats=None) -> None:
+    """The refusals of a ``median_depth=True`` request (those of ``aux_maps=True``), before anything is enqueued."""
+    if densify_stats is not None:
+        raise ValueError("median_depth=True cannot be combined with densify_stats: a frame that keeps its state for the "
+                         "maps takes the densification statistics from the summed means2D.grad after the backward, as "
+                         "with aux_maps=True")
+    if cam:
+        raise ValueError("median_depth=True cannot be combined with camera tensors that require grad: the median-depth map "
+                         "has no camera gradients (detach viewmatrix / projmatrix / campos, or render the map in a frame "
+                         "of its own)")
+    if state_key is not None:
+        raise ValueError("median_depth=True is not available on a frame with grown / split rows appended")
+
+
 def _check_feature_request(features, means3D, cam, state_key=None, densify_stats=None) -> None:
     """The refusals of a ``features=F`` request, before anything is enqueued (and before a GPU is asked for)."""
     if densify_stats is not None:
@@ -861,9 +954,9 @@ def _accumulate_contribution(node, stats, mask, means3D, settings) -> None:
 
 
 def _with_frame_outputs(color, radii, node, grad: bool, geometry, aux_maps, contribution, contribution_mask,
-                        features=None, grad_features: bool = False, distortion=None):
+                        features=None, grad_features: bool = False, distortion=None, median_depth: bool = False):
     """The results of a frame that kept its state: the statistics are accumulated, the maps appended when asked for
-    (``aux``, then ``feat``, then ``dist``).  ``grad``: the colour node is an autograd node; ``grad_features``: the feature
+    (``aux``, then ``feat``, then ``dist``, then ``median`` and ``median_id``).  ``grad``: the colour node is an autograd node; ``grad_features``: the feature
     maps get a node although the colour forward ran outside autograd (only ``features`` requires grad).
     ``distortion``: the (mapping, near, far) of ``_distortion_spec``."""
     if contribution is not None:
@@ -875,20 +968,25 @@ def _with_frame_outputs(color, radii, node, grad: bool, geometry, aux_maps, cont
         out += (_feature_maps_of(node, grad or grad_features, features, *geometry),)
     if distortion is not None:
         out += (_distortion_of(node, grad, distortion, *geometry),)
+    if median_depth:
+        out += tuple(_median_of(node, grad, *geometry))
     return out
 
 
 def _rasterize(fn, tensors, raster_settings, tail, geometry, densify_stats, aux_maps, contribution, contribution_mask,
-               state_key=None, features=None, distortion=None):
+               state_key=None, features=None, distortion=None, median_depth=False):
     """One frame through the colour operator ``fn``.  ``tensors``: its forward's arguments in front of ``raster_settings``;
     ``tail``: those between ``stats`` and the camera's; ``geometry``: the arguments of ``_aux_maps_of`` after ``grad``
-    when ``aux_maps``, ``contribution``, ``features`` or ``distortion`` ask for the frame's state, else None.
+    when ``aux_maps``, ``contribution``, ``features``, ``distortion`` or ``median_depth`` ask for the frame's state, else
+    None.
     ``distortion``: None, or the (mapping, near, far) of ``_distortion_spec``."""
     cam = _camera_inputs(raster_settings)
     if aux_maps:
         _check_aux_request(cam, state_key, densify_stats)
     if distortion is not None:
         _check_distortion_request(cam, state_key, densify_stats)
+    if median_depth:
+        _check_median_request(cam, state_key, densify_stats)
     if features is not None:
         _check_feature_request(features, tensors[0], cam, state_key, densify_stats)
     if contribution is not None:
@@ -903,21 +1001,24 @@ def _rasterize(fn, tensors, raster_settings, tail, geometry, densify_stats, aux_
             color, radii = fn.forward(node, *tensors, raster_settings, False, None, *tail)
             if not grad_features:
                 return _with_frame_outputs(color, radii, node, False, geometry, aux_maps, contribution,
-                                           contribution_mask, features, distortion=distortion)
+                                           contribution_mask, features, distortion=distortion,
+                                           median_depth=median_depth)
             head = _with_frame_outputs(color, radii, node, False, geometry, aux_maps, contribution, contribution_mask)
             dist = () if distortion is None else (_distortion_of(node, False, distortion, *geometry),)
+            if median_depth:
+                dist += tuple(_median_of(node, False, *geometry))
         # only ``features`` requires grad: its node is built with grad mode as the caller has it
         return head + (_feature_maps_of(node, True, features, *geometry),) + dist
     out = fn.apply(*tensors, raster_settings, False, densify_stats, *tail, *cam)
     if geometry is None:
         return out
     return _with_frame_outputs(*out, out[0].grad_fn, True, geometry, aux_maps, contribution, contribution_mask, features,
-                               distortion=distortion)
+                               distortion=distortion, median_depth=median_depth)
 
 
 def rasterize_gaussians_fused(means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations, raster_settings,
                               densify_stats=None, visible=None, _state_key=None, aux_maps=False, contribution=None,
-                              contribution_mask=None, features=None, distortion=None):
+                              contribution_mask=None, features=None, distortion=None, median_depth=False):
     """``densify_stats``: None, or (xyz_gradient_accum, denom, max_radii2D) -- the backward then also accumulates the
     densification statistics of ``scene/gaussian_model.py:775-777`` / ``train.py:130``.
     ``visible``: None, or a bool [P] tensor that receives ``radii > 0`` from the preprocess kernel.
@@ -925,30 +1026,32 @@ def rasterize_gaussians_fused(means3D, means2D, f_dc, f_rest, raw_opacity, raw_s
     ``aux_maps``: also return the depth / inverse-depth / alpha maps ``[3,H,W]`` (``_AuxMaps``) as a third result.
     ``contribution`` / ``contribution_mask``: accumulate the frame's contribution statistics (module docstring).
     ``features``: float32 ``[P,C]``; also return ``feat [C,H,W] = sum w features[id]`` (``_FeatureMaps``) after ``aux``.
-    ``distortion``: True or ``dict(mapping=, near=, far=)``; also return ``dist [1,H,W]`` (``_DistortionMap``) as the last
-    result."""
+    ``distortion``: True or ``dict(mapping=, near=, far=)``; also return ``dist [1,H,W]`` (``_DistortionMap``) after ``feat``.
+    ``median_depth``: also return ``median [1,H,W]`` and ``median_id [H,W]`` (``_MedianDepth``) as the last two results."""
     geometry = None
     distortion = _distortion_spec(distortion)
-    if aux_maps or contribution is not None or features is not None or distortion is not None:
+    median_depth = bool(median_depth)
+    if aux_maps or contribution is not None or features is not None or distortion is not None or median_depth:
         empty = torch.empty(0, dtype=torch.float32, device=means3D.device)
         flags = _lib.ACT_SCALE_EXP | _lib.ACT_ROT_NORMALIZE | _lib.ACT_OPACITY_SIGMOID
         geometry = (means3D, means2D, raw_opacity, raw_scales, raw_rotations, empty, raster_settings, flags)
     return _rasterize(_RasterizeGaussiansFused,
                       (means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations), raster_settings,
                       (visible, _state_key), geometry, densify_stats, aux_maps, contribution, contribution_mask, _state_key,
-                      features, distortion)
+                      features, distortion, median_depth)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings, densify_stats=None, aux_maps=False, contribution=None, contribution_mask=None,
-                        features=None, distortion=None):
+                        features=None, distortion=None, median_depth=False):
     distortion = _distortion_spec(distortion)
+    median_depth = bool(median_depth)
     geometry = (means3D, means2D, opacities, scales, rotations, cov3Ds_precomp, raster_settings) \
-        if aux_maps or contribution is not None or features is not None or distortion is not None else None
+        if aux_maps or contribution is not None or features is not None or distortion is not None or median_depth else None
     return _rasterize(_RasterizeGaussians,
                       (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp),
                       raster_settings, (), geometry, densify_stats, aux_maps, contribution, contribution_mask,
-                      features=features, distortion=distortion)
+                      features=features, distortion=distortion, median_depth=median_depth)
 
 
 class GaussianRasterizer(nn.Module):
@@ -956,14 +1059,16 @@ class GaussianRasterizer(nn.Module):
     (``gaussian_renderer/__init__.py:57``) and calls at ``:257-265``."""
 
     def __init__(self, raster_settings: GaussianRasterizationSettings, aux_maps: bool = False, contribution=None,
-                 contribution_mask: Optional[torch.Tensor] = None, distortion=None):
+                 contribution_mask: Optional[torch.Tensor] = None, distortion=None, median_depth: bool = False):
         """``aux_maps=True``: the call returns ``(color, radii, aux)`` with ``aux [3,H,W]`` = the depth
         (``sum w z``), inverse-depth (``sum w / z``) and accumulated-opacity (``sum w``) maps of the frame,
         differentiable in means3D, means2D, opacities and scales / rotations or cov3D_precomp.
         ``contribution``: a ``contribution.ContributionStats`` that every call adds its frame's per-Gaussian statistics
         into; ``contribution_mask``: uint8 ``[H,W]``, pixels with 0 are left out.  Not differentiable.
         ``distortion``: True, or ``dict(mapping="linear" | "ndc", near=0.2, far=100.0)``: the call's results gain a
-        trailing ``dist [1,H,W]``, the depth-distortion map (module docstring), differentiable in the geometry inputs."""
+        trailing ``dist [1,H,W]``, the depth-distortion map (module docstring), differentiable in the geometry inputs.
+        ``median_depth=True``: the call's results gain, after everything else, ``median [1,H,W]`` (2DGS's median depth,
+        differentiable in means3D alone) and ``median_id [H,W]`` (int32: the Gaussian that owns the pixel, -1 for none)."""
         super().__init__()
         _distortion_spec(distortion)        # a malformed request is refused here, not at the first frame
         self.raster_settings = raster_settings
@@ -971,6 +1076,7 @@ class GaussianRasterizer(nn.Module):
         self.contribution = contribution
         self.contribution_mask = contribution_mask
         self.distortion = distortion
+        self.median_depth = bool(median_depth)
 
     def markVisible(self, positions: torch.Tensor) -> torch.Tensor:
         """Frustum (near-plane) visibility of the upstream module's ``markVisible``; bool ``[P]``."""
@@ -1003,7 +1109,8 @@ class GaussianRasterizer(nn.Module):
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                    cov3D_precomp, raster_settings, densify_stats, aux_maps=self.aux_maps,
                                    contribution=self.contribution, contribution_mask=self.contribution_mask,
-                                   features=features, **({} if self.distortion is None else {"distortion": self.distortion}))
+                                   features=features, **({} if self.distortion is None else {"distortion": self.distortion}),
+                                   **({"median_depth": True} if self.median_depth else {}))
 
     def forward_fused(self, means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations, densify_stats=None,
                       features=None):
@@ -1012,4 +1119,5 @@ class GaussianRasterizer(nn.Module):
                                          self.raster_settings, densify_stats, aux_maps=self.aux_maps,
                                          contribution=self.contribution, contribution_mask=self.contribution_mask,
                                          features=features,
-                                         **({} if self.distortion is None else {"distortion": self.distortion}))
+                                         **({} if self.distortion is None else {"distortion": self.distortion}),
+                                         **({"median_depth": True} if self.median_depth else {}))

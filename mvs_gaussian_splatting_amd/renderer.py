@@ -94,7 +94,7 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier:
            override_color=None, grow_dir=False, densify_grad_threshold=0, iteration=None, opt=None,
            continous_dir=False, grow_distance=False, modelcg=None, cameras_extent=None, return_depth=False,
            use_trained_exp=False, contribution=None, contribution_mask=None, features=None, return_normals=False,
-           return_distortion=False, distortion_kwargs=None):
+           return_distortion=False, distortion_kwargs=None, return_median_depth=False):
     """Render the scene; ``bg_color`` must be on the GPU.  Returns the reference's result dict
     (``gaussian_renderer/__init__.py:309-313``).  The keyword arguments after ``override_color`` are the reference's
     (``:19``) and drive the grow / learned-split branch (module docstring); the frame of a closed branch is unchanged.
@@ -130,13 +130,20 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier:
     ``return_distortion=True``: the dict gains ``"distortion"`` ``[1,H,W]`` = ``sum_i sum_{j<i} w_i w_j (m_i - m_j)^2``, the
     depth-distortion map of 2DGS (``rasterizer`` module docstring; DESIGN.md §7.16), differentiable in the geometry;
     ``distortion_kwargs``: ``dict(mapping="linear" | "ndc", near=, far=)``, default ``"ndc"`` with near 0.2 and far 100.
-    The same two conditions as for ``return_depth`` apply."""
+    The same two conditions as for ``return_depth`` apply.
+
+    ``return_median_depth=True``: the dict gains ``"median_depth"`` ``[1,H,W]``, the view depth of the last composited
+    Gaussian in front of which the transmittance still exceeds one half (2DGS's median depth, what it meshes bounded scenes
+    from; 0 where nothing was composited), differentiable in the positions alone, and ``"median_id"`` ``[H,W]`` (int32),
+    the row of that Gaussian (-1 where nothing was composited) (``rasterizer`` module docstring).  The
+    same two conditions as for ``return_depth`` apply."""
     if distortion_kwargs is not None and not return_distortion:
         raise ValueError("distortion_kwargs needs return_distortion=True")
     pkg = _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, grow_dir,
                   densify_grad_threshold, iteration, opt, continous_dir, grow_distance, modelcg, cameras_extent,
                   return_depth, contribution, contribution_mask, features, return_normals,
-                  (True if distortion_kwargs is None else dict(distortion_kwargs)) if return_distortion else None)
+                  (True if distortion_kwargs is None else dict(distortion_kwargs)) if return_distortion else None,
+                  **({"median_depth": True} if return_median_depth else {}))
     if use_trained_exp:
         pkg["render"] = apply_exposure(pkg["render"], pc.get_exposure_from_name(viewpoint_camera.image_name))
     return pkg
@@ -144,8 +151,9 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier:
 
 def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, grow_dir, densify_grad_threshold,
             iteration, opt, continous_dir, grow_distance, modelcg, cameras_extent, return_depth, contribution=None,
-            contribution_mask=None, features=None, return_normals=False, distortion=None):
-    """The frame of ``render`` as the rasterizer leaves it.  ``distortion``: None, or the operator's ``distortion=``."""
+            contribution_mask=None, features=None, return_normals=False, distortion=None, median_depth=False):
+    """The frame of ``render`` as the rasterizer leaves it.  ``distortion``: None, or the operator's ``distortion=``;
+    ``median_depth``: the operator's ``median_depth=``."""
     which = grow.branch(iteration, opt, grow_dir, continous_dir, modelcg)
     if which is not None and contribution is not None:
         raise ValueError("contribution statistics are not available on a frame of the open grow / learned-split branch "
@@ -162,6 +170,9 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
     if which is not None and distortion is not None:
         raise ValueError("return_distortion=True is not available on a frame of the open grow / learned-split branch "
                          "(virtual rows appended): render the map in a frame of its own")
+    if which is not None and median_depth:
+        raise ValueError("return_median_depth=True is not available on a frame of the open grow / learned-split branch "
+                         "(virtual rows appended): render the map in a frame of its own")
     if which is not None:
         return _render_grown(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, which, grow_dir,
                              densify_grad_threshold, continous_dir, grow_distance, modelcg, cameras_extent)
@@ -172,7 +183,7 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
     # The operator never reads (or writes) its values, so every frame's leaf aliases one cached block of zeros: a
     # fresh 72 MB memset per frame is 20 us of the 6 M-Gaussian forward.
     screenspace_points = _zero_leaf(xyz)
-    stats = None if return_depth or want_feat or distortion is not None else _fused_stats(pc, pipe, xyz)
+    stats = None if return_depth or want_feat or distortion is not None or median_depth else _fused_stats(pc, pipe, xyz)
     if stats is not None:
         screenspace_points._gsr_stats_fused = True      # read by losses.add_densification_stats
 
@@ -184,9 +195,16 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
                                          raster_settings.campos))
         extra_stats = dict(extra_stats, features=rows[0] if len(rows) == 1 else torch.cat(rows, dim=1))
 
+    median_kw = {"median_depth": True} if median_depth else {}
+
     def feature_entries(out):
-        """The operator's trailing ``feat`` / ``dist`` as the dict's ``"features"`` / ``"normal"`` / ``"distortion"``
-        entries."""
+        """The operator's trailing ``feat`` / ``dist`` / ``median``, ``median_id`` as the dict's ``"features"`` /
+        ``"normal"`` / ``"distortion"`` / ``"median_depth"``, ``"median_id"`` entries."""
+        if median_depth:
+            return {**_tail_entries(out[:-2]), "median_depth": out[-2], "median_id": out[-1]}
+        return _tail_entries(out)
+
+    def _tail_entries(out):
         if distortion is not None:
             return {**_feature_entries(out[-2]), "distortion": out[-1]}
         return _feature_entries(out[-1])
@@ -206,11 +224,11 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
         # visibility_filter (= radii > 0, gaussian_renderer/__init__.py:311) is stored by the preprocess kernel itself:
         # a torch compare over 6 M radii is a 9-us kernel per frame
         visible = torch.empty(xyz.shape[0], dtype=torch.bool, device=xyz.device)
-        if return_depth or want_feat or distortion is not None:
+        if return_depth or want_feat or distortion is not None or median_depth:
             out = rasterize_gaussians_fused(xyz, screenspace_points, pc._features_dc, pc._features_rest, pc._opacity,
                                             pc._scaling, pc._rotation, raster_settings, visible=visible,
                                             **({"aux_maps": True} if return_depth else {}), **extra_stats,
-                                            **({} if distortion is None else {"distortion": distortion}))
+                                            **({} if distortion is None else {"distortion": distortion}), **median_kw)
             return {"render": out[0], "viewspace_points": screenspace_points, "visibility_filter": visible,
                     "radii": out[1], "selected_pts_mask": None, **(_aux_entries(out[2]) if return_depth else {}),
                     **feature_entries(out)}
@@ -222,7 +240,7 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
 
     feat_kw = {"features": extra_stats.pop("features")} if want_feat else {}
     rasterizer = GaussianRasterizer(raster_settings=raster_settings, **({"aux_maps": True} if return_depth else {}),
-                                    **extra_stats, **({} if distortion is None else {"distortion": distortion}))
+                                    **extra_stats, **({} if distortion is None else {"distortion": distortion}), **median_kw)
     scales = rotations = cov3D_precomp = None
     if getattr(pipe, "compute_cov3D_python", False):
         cov3D_precomp = pc.get_covariance(scaling_modifier)

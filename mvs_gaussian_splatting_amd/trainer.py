@@ -68,6 +68,9 @@ class OptimizationParams:
     # depth-normal consistency (normal_consistency.py; 2DGS uses 0.05 from iteration 7000): 0 leaves the iteration as it is
     lambda_normal = 0.0
     normal_from_iter = 7000
+    # which depth the normal term differentiates: (1 - depth_ratio) expected + depth_ratio median (2DGS: 0 for unbounded
+    # scenes, 1 for bounded ones); read only while the normal term is on; 0 leaves the iteration as it is
+    depth_ratio = 0.0
     # depth distortion (the rasterizer's distortion map; 2DGS uses 100 to 1000 from iteration 3000): 0 leaves the iteration
     # as it is
     lambda_dist = 0.0
@@ -129,6 +132,10 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
     ``depth_loss`` frames.  Combines with ``depth_loss``, ``train_exposure``, ``sparse_adam`` and ``strategy="mcmc"``.
     ``ValueError`` with ``pose_optimizer`` (the maps carry no camera gradient) and on a fork grow / learned-split model
     (the maps are not rendered on its frames).  ``lambda_normal = 0``: exactly the calls made without it.
+    ``opt.depth_ratio > 0`` while the normal term is on: the frame is also rendered with ``return_median_depth=True`` and
+    the term is evaluated on the blend ``(1 - depth_ratio) depth / alpha + depth_ratio median`` (``median=``,
+    ``depth_ratio=`` of ``normal_consistency_loss``); the refusals are the normal term's, and ``ValueError`` outside
+    [0, 1].  ``depth_ratio = 0``, or the normal term off: exactly the calls made without it.
     ``opt.lambda_dist > 0`` from ``opt.dist_from_iter`` on: the frame is rendered with ``return_distortion=True`` and
     ``lambda_dist * distortion.mean()`` joins the loss; statistics, combinations and refusals as for ``lambda_normal``.
     ``lambda_dist = 0``: exactly the calls made without it."""
@@ -159,6 +166,10 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
                                                    "learn_split_scale")):
             raise ValueError("lambda_normal > 0 does not support the fork's grow / learned-split models: render refuses "
                              "return_depth / return_normals on their frames (virtual rows appended)")
+    depth_ratio = float(getattr(opt, "depth_ratio", 0.0)) if normal_on else 0.0
+    if not 0.0 <= depth_ratio <= 1.0:
+        raise ValueError(f"opt.depth_ratio must lie in [0, 1], got {depth_ratio}")
+    median_on = depth_ratio > 0.0
     dist_on = float(getattr(opt, "lambda_dist", 0.0)) > 0.0 and iteration >= int(getattr(opt, "dist_from_iter", 0))
     if dist_on:
         if pose_optimizer is not None:
@@ -181,6 +192,7 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
                  **({"return_depth": True} if depth_loss is not None or normal_on else {}),
                  **({"return_normals": True} if normal_on else {}),
                  **({"return_distortion": True} if dist_on else {}),
+                 **({"return_median_depth": True} if median_on else {}),
                  **({"use_trained_exp": True} if train_exposure else {}))
     gt = camera.original_image if gt_image is None else gt_image
     loss = l1_dssim_loss(pkg["render"], gt.to(pkg["render"].device), opt.lambda_dssim)          # :99-101
@@ -193,7 +205,8 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
         loss = loss + float(depth_weight) * (pkg["invdepth"] - depth_target.to(pkg["invdepth"].device)).abs().mean()
     if normal_on:
         loss = loss + float(opt.lambda_normal) * normal_consistency_loss(
-            pkg["depth"], pkg["alpha"], pkg["normal"], math.tan(camera.FoVx * 0.5), math.tan(camera.FoVy * 0.5))
+            pkg["depth"], pkg["alpha"], pkg["normal"], math.tan(camera.FoVx * 0.5), math.tan(camera.FoVy * 0.5),
+            **({"median": pkg["median_depth"], "depth_ratio": depth_ratio} if median_on else {}))
     if dist_on:
         loss = loss + float(opt.lambda_dist) * pkg["distortion"].mean()
     loss.backward()                                                                             # :107

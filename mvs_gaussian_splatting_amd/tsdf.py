@@ -22,6 +22,7 @@ from typing import Optional, Sequence, Tuple
 import torch
 
 from . import _lib
+from .surface import surface_depth
 
 _INF = float("inf")
 _BLOCK_X, _BLOCK_ROWS = 64, 4          # the launch shape of csrc/tsdf.hip (tsdf_grid_blocks)
@@ -182,17 +183,27 @@ class TSDFVolume:
 
 
 def fuse_views(cameras, model, pipe, bg, volume: TSDFVolume, *, alpha_min: float = 0.5,
-               max_depth: Optional[float] = None, renderer=None) -> TSDFVolume:
+               max_depth: Optional[float] = None, renderer=None, depth_ratio: float = 0.0) -> TSDFVolume:
     """Render every camera with ``renderer(camera, model, pipe, bg, return_depth=True)`` (default: ``render``) under
     ``no_grad`` and integrate its expected depth ``depth / alpha`` where ``alpha >= alpha_min`` (0, invalid, elsewhere)
-    with the rendered colour.  No host synchronisation per view."""
+    with the rendered colour.  No host synchronisation per view.
+    depth_ratio (2DGS's, in [0, 1]; it meshes bounded scenes at 1): above 0 the frames are rendered with
+    ``return_median_depth=True`` as well and ``surface.surface_depth(depth, alpha, median, depth_ratio, alpha_min)`` is
+    integrated -- at 1 the median depth, which lies on a surface at a depth edge where the expected depth floats between
+    two.  At 0 the renderer is called with exactly the keyword arguments above."""
+    if not (isinstance(depth_ratio, (int, float)) and 0.0 <= depth_ratio <= 1.0):
+        raise ValueError(f"depth_ratio must lie in [0, 1], got {depth_ratio!r}")
     if renderer is None:
         from .renderer import render as renderer
     with torch.no_grad():
         for camera in cameras:
-            pkg = renderer(camera, model, pipe, bg, return_depth=True)
-            depth, alpha = pkg["depth"], pkg["alpha"]
-            expected = torch.where(alpha >= alpha_min, depth / alpha, torch.zeros_like(depth))
+            if depth_ratio > 0.0:
+                pkg = renderer(camera, model, pipe, bg, return_depth=True, return_median_depth=True)
+                expected = surface_depth(pkg["depth"], pkg["alpha"], pkg["median_depth"], depth_ratio, alpha_min)
+            else:
+                pkg = renderer(camera, model, pipe, bg, return_depth=True)
+                depth, alpha = pkg["depth"], pkg["alpha"]
+                expected = torch.where(alpha >= alpha_min, depth / alpha, torch.zeros_like(depth))
             volume.integrate(expected, camera, color=pkg["render"] if volume.with_color else None, max_depth=max_depth)
     return volume
 
