@@ -245,3 +245,145 @@ def test_write_ply_mesh_round_trips_with_colours_without_and_empty(tmp_path, sph
         assert xyz.shape == (0, 3) and idx.shape == (0, 3) and (rgb is None) == (col is None)
     with pytest.raises(ValueError):
         write_ply_mesh(p, v32[:10], faces)
+
+
+# ---- census of the inputs past one x-chunk (tests/test_gpu_tsdf.py runs them on the GPU) ---------------------------------
+# Conditions of the inputs, from the float64 restatement alone: they keep the inputs from decaying into ones that leave the
+# kernels' branches unexercised.
+@pytest.mark.parametrize("n", range(len(R.WIDE_DIMS)))
+def test_wide_integration_inputs_reach_every_test_of_the_kernel(n):
+    case = R.wide_case(n)
+    nx, ny, nz = case["dims"]
+    assert nx > 64 and [(65, 1), (130, 2), (128, 0)][n] == (nx, nx % 64) and ((ny * nz) % 4 != 0 or n != 1)
+    assert [v["weight"] for v in case["views"]] == [0.5, 2.25, 1.0]
+    assert all(v["W"] % 2 == 1 and v["H"] % 2 == 1 and v["W"] % 16 and v["H"] % 16 for v in case["views"])
+    for v in case["views"]:                                  # every rotation mixes all three axes
+        assert np.abs(v["viewmatrix"][:3, :3]).max() < 0.999
+    vol, touched, fragile, per_view = R.run_wide(case, with_color=True)
+    robust = ~fragile
+    best = {}
+    for v, view in enumerate(case["views"]):
+        classes = R.view_classes(R.wide_volume(case, True, False), view)
+        assert np.array_equal(classes["updated"][robust], per_view[v][robust]), "the census disagrees with integrate()"
+        for name, mask in classes.items():
+            best[name] = max(best.get(name, 0), int((mask & robust).sum()))
+        if v == 1:
+            assert view["max_depth"] is None and int((classes["inf_update"] & robust).sum()) >= 1
+            assert int((classes["behind"] & robust).sum()) >= 100, "the inside camera has much of the grid behind it"
+        if v == 2:                                           # the small image: all four sides, negative u + 0.5 and v + 0.5 too
+            assert all(int((classes[k] & robust).sum()) >= 20 for k in ("off_left", "off_right", "off_top", "off_bottom"))
+    print(f"wide case {n} {case['dims']}: " + ", ".join(f"{k} {best[k]}" for k in best))
+    for name in R.CLASSES:
+        assert best[name] >= 20, f"{name}: only {best[name]} robust points in the best view"
+    # a side's test is only visible where the other coordinate is inside the image
+    for name in ("only_left", "only_right", "only_top", "only_bottom"):
+        assert best[name] >= 20, f"{name}: only {best[name]} robust points in the best view"
+    # and only where a test that is off by one pixel would turn the point into an update: the pixel it would read is a
+    # valid depth inside the band.  A handful suffices: each is a written point that must keep its bits.
+    for name in ("relaxed_left", "relaxed_right", "relaxed_top", "relaxed_bottom"):
+        assert best[name] >= 5, f"{name}: only {best[name]} robust points would be updated"
+    assert "guard" in case["views"][0] and "guard" not in case["views"][2]
+    if n == 1:                                               # sdf_trunc > 0.2: a 0 depth is stopped by d > 0 alone
+        assert case["sdf_trunc"] > 0.2 and best["zero_visible"] >= 5, f"zero_visible {best['zero_visible']}"
+    share = float(fragile.sum()) / fragile.size
+    assert share < 0.01, f"fragile share {share:.3f}"
+    assert touched.sum() > 200 and (~touched).sum() > 200
+    assert len(np.unique(vol["weight"])) >= 6, "the views must overlap in different combinations"
+    clamped, _, _, _ = R.run_wide(case, True, max_weight=R.WIDE_MAX_WEIGHT)
+    assert int(((clamped["weight"] == R.WIDE_MAX_WEIGHT) & robust).sum()) > 20
+    assert clamped["weight"].max() == R.WIDE_MAX_WEIGHT < vol["weight"].max()
+    # the pre-loaded state: w_old differs from point to point, and some pre-loaded weights exceed the clamp
+    pre = case["preload"]
+    assert set(np.unique(pre["weight"]).tolist()) == {0.0, 0.5, 4.0} and pre["tsdf"].min() < -0.9 and pre["tsdf"].max() > 0.9
+    loaded, up, _, _ = R.run_wide(case, True, max_weight=R.WIDE_MAX_WEIGHT, preload=True)
+    assert np.array_equal(up, touched), "which points a view updates does not depend on the state"
+    assert all(np.array_equal(loaded[k][~up], pre[k][~up].astype(np.float64)) for k in ("tsdf", "weight", "color"))
+    # the float32 restatement takes every decision as float64 does on the robust points: the margin is wide enough
+    _, _, _, per_view32 = R.run_wide(case, True, dtype=np.float32)
+    assert all(np.array_equal(a[robust], b[robust]) for a, b in zip(per_view, per_view32))
+
+
+def test_existing_integration_inputs_never_leave_the_frustum():
+    """Why the wide inputs exist: in ``integration_case`` no point is behind a camera or outside an image."""
+    _, views = R.integration_case()
+    vol = R.empty_volume(R.CASE_DIMS, R.CASE_ORIGIN, R.CASE_VOXEL, R.CASE_TRUNC, True)
+    for view in views:
+        classes = R.view_classes(vol, view)
+        assert not any(classes[k].any() for k in ("near", "behind", "off_left", "off_right", "off_top", "off_bottom"))
+
+
+@pytest.fixture(scope="module")
+def random_censuses():
+    return [R.mesh_census(R.random_field(n)) for n in range(len(R.RANDOM_DIMS))]
+
+
+def _end_values(field, census):
+    e = census["ends"]
+    return field["tsdf"][e[:, :, 2], e[:, :, 1], e[:, :, 0]]
+
+
+def test_random_fields_reach_the_cube_patterns_cases_polarities_and_hole_borders(random_censuses):
+    union = lambda key: set().union(*(c[key] for c in random_censuses))                     # noqa: E731
+    patterns, tet_cases, polarities = union("patterns"), union("tet_cases"), union("polarities")
+    orphans, shared = sum(c["orphans"] for c in random_censuses), sum(c["shared"] for c in random_censuses)
+    print(f"{len(patterns)} of 254 mixed cube patterns, {len(tet_cases)} of 84 (tetrahedron, case) pairs, "
+          f"{len(polarities)} of 14 (direction, polarity) pairs, {orphans} crossed edges without a processed cube, "
+          f"{shared} held by a processed and an unprocessed cube")
+    assert len(patterns) >= 250 and 0 not in patterns and 255 not in patterns
+    assert tet_cases == {(t, m) for t in range(6) for m in range(1, 15)}
+    assert polarities == {(d, s) for d in range(7) for s in (False, True)}
+    assert orphans >= 10 and shared >= 10
+    plus = minus = 0
+    for n, census in enumerate(random_censuses):
+        field = R.random_field(n)
+        nx, ny, nz = R.RANDOM_DIMS[n]
+        assert nx > 64 and tuple(field["tsdf"].shape) == (nz, ny, nx)
+        share = float((field["weight"] == 0).mean())
+        assert 0.01 < share < 0.06 and set(np.unique(field["weight"]).tolist()) == {0.0, 1.0, 2.0, 3.0}
+        vals = _end_values(field, census)
+        plus += int(((vals == 0) & ~np.signbit(vals)).sum())
+        minus += int(((vals == 0) & np.signbit(vals)).sum())
+        # the census, found edge by edge, names the vertices extract() finds triangle by triangle
+        vertices, faces, _ = R.extract(field)
+        assert len(census["keys"]) == len(vertices) and len(faces) > 4000
+        e = census["ends"]
+        # the smallest cross-section has 15 points, each with four edges that advance in x, about half of them crossed
+        assert int(((e[:, 0, 0] == 63) & (e[:, 1, 0] == 64)).sum()) >= 10, "vertices on edges across the chunk seam"
+    assert plus >= 1 and minus >= 1, "an emitted edge ends at 0.0, another at -0.0"
+
+
+def test_min_weight_variants_change_which_cubes_are_processed():
+    field = R.random_field(1)
+    sizes = {mw: len(R.extract(field, min_weight=mw)[1]) for mw in (0.0, 1e-6, 2.0, float("inf"))}
+    print(f"faces by min_weight: {sizes}")
+    assert sizes[0.0] > sizes[1e-6] > sizes[2.0] > 100 and sizes[float("inf")] == 0
+    empty = R.extract(field, min_weight=float("inf"))
+    assert empty[0].shape == (0, 3) and empty[1].shape == (0, 3)
+
+
+def test_seam_sphere_is_closed_and_crosses_the_chunk_seam():
+    field = R.seam_sphere_field()
+    vertices, faces, _ = R.extract(field)
+    R.assert_closed_oriented_sphere(vertices, faces)
+    assert abs(R.signed_volume(vertices, faces) / (4.0 / 3.0 * math.pi * R.SEAM_R ** 3) - 1.0) < 0.02
+    census = R.mesh_census(field)
+    e = census["ends"]
+    across = int(((e[:, 0, 0] == 63) & (e[:, 1, 0] == 64)).sum())
+    print(f"seam sphere: V {len(vertices)} F {len(faces)}, {across} vertices on edges from i = 63 to i = 64")
+    assert len(census["keys"]) == len(vertices) and across >= 50
+    assert vertices[:, 0].min() < 63 < 64 < vertices[:, 0].max()
+
+
+def test_fused_sphere_lies_within_a_voxel_of_the_analytic_one_where_two_views_agree():
+    _, views = R.fusion_case()
+    vol, fragile = R.run_fusion(views)
+    assert fragile.mean() < 0.01 and R.FUSE_DIMS[0] > 64
+    vertices, faces, _ = R.extract(vol, min_weight=1.0)
+    census = R.mesh_census(vol, 1.0)
+    e = census["ends"]
+    solid = (vol["weight"][e[:, :, 2], e[:, :, 1], e[:, :, 0]] >= 2).all(axis=1)
+    off = np.abs(np.linalg.norm(vertices - np.array(R.FUSE_C), axis=1) - R.FUSE_R) / R.FUSE_VOXEL
+    across = int(((e[:, 0, 0] == 63) & (e[:, 1, 0] == 64)).sum())
+    print(f"fused sphere: V {len(vertices)} F {len(faces)}, {int(solid.sum())} vertices between samples of weight >= 2, "
+          f"at most {off[solid].max():.3f} voxels off the sphere; {across} vertices across the seam")
+    assert solid.sum() > 1000 and off[solid].max() < 1.0 and across >= 50
