@@ -18,51 +18,19 @@
 // colour pass is written with explicit fma.
 #include "gsr_common.h"
 #include "gsr_launch.h"
+#include "map_walk.h"
 #include "preprocess_geom.h"
-#include "render_pair.h"
 
 namespace gsr {
 
-constexpr int AUX_CHUNK = 256;      // list entries staged per round: one per lane of the workgroup
-constexpr int AUX_SUMS = 7;         // per-entry sums of the backward (see aux_maps_bwd_kernel)
-
-struct AuxEntry {
-  LdsRec lr;
-  float z, cxx, cxy, cyy, opacity;
-  uint32_t id;
-};
-
-// the words of a list entry's Gaussian that the maps need, and the colour pass's LDS image of them
-__device__ inline void aux_load_entry(const GeomRec* __restrict__ rec, const BinInfo* __restrict__ bin, uint32_t id,
-                                      AuxEntry& e) {
-  const GeomRec* r = rec + id;
-  Staged st;
-  st.q0 = make_float4(r->x, r->y, r->cxx, 0.0f);
-  st.q1 = make_float4(0.0f, r->opacity, 0.0f, 0.0f);
-  st.q2 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  st.kk = r->kk;
-  st.isyy = r->isyy;
-  make_lds(st, e.lr);
-  e.cxx = r->cxx; e.cxy = r->cxy; e.cyy = r->cyy; e.opacity = r->opacity;
-  e.z = bin[id].depth;
-  e.id = id;
-}
-
-// largest value of v over the workgroup's 256 lanes (every lane calls it)
-__device__ inline uint32_t block_max_u32(uint32_t v, uint32_t* s4) {
-#pragma unroll
-  for (int d = WAVE / 2; d > 0; d >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, d, WAVE));
-  if ((threadIdx.x & (WAVE - 1)) == 0) s4[threadIdx.x / WAVE] = v;
-  __syncthreads();
-  return max(max(s4[0], s4[1]), max(s4[2], s4[3]));
-}
+constexpr int AUX_SUMS = MAP_GEOM + 1;      // per-entry sums of the backward: the geometry sums and d z
 
 // ------------------------------------------------------------------------------------------------------------------
 // Forward: one 256-lane workgroup per tile (the colour pass's tile order: longest list first), one lane per pixel.
 // A round stages up to 256 entries in LDS; every lane then walks the round's entries in list order up to ITS
 // n_contrib.  No early-out of its own: how far a pixel walks was decided by the colour pass.
 // ------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(AUX_CHUNK) void aux_maps_fwd_kernel(int W, int H, int grid_x,
+__global__ __launch_bounds__(MAP_CHUNK) void aux_maps_fwd_kernel(int W, int H, int grid_x,
                                                                  const uint32_t* __restrict__ tile_order,
                                                                  const uint2* __restrict__ ranges,
                                                                  const uint32_t* __restrict__ point_list,
@@ -70,37 +38,32 @@ __global__ __launch_bounds__(AUX_CHUNK) void aux_maps_fwd_kernel(int W, int H, i
                                                                  const BinInfo* __restrict__ bin,
                                                                  const uint32_t* __restrict__ n_contrib,
                                                                  float* __restrict__ out) {
-  __shared__ float4 sA[AUX_CHUNK];
-  __shared__ float4 sB[AUX_CHUNK];
-  __shared__ float2 sZ[AUX_CHUNK];      // z, 1 / z
+  __shared__ float4 sA[MAP_CHUNK];
+  __shared__ float4 sB[MAP_CHUNK];
+  __shared__ float2 sZ[MAP_CHUNK];      // z, 1 / z
   __shared__ uint32_t sMax[4];
   const int tid = threadIdx.x;
-  const int tile = __builtin_amdgcn_readfirstlane((int)tile_order[blockIdx.x]);
-  const int tile_x = tile % grid_x, tile_y = tile / grid_x;
-  const int px = tile_x * TILE + (tid & (TILE - 1)), py = tile_y * TILE + tid / TILE;
-  const bool inside = px < W && py < H;
-  const size_t pix = (size_t)py * W + px, HW = (size_t)W * H;
-  const float pxf = (float)px, pyf = (float)py;
-  const uint2 range = ranges[tile];
-  const uint32_t start = range.x, len = range.y - range.x;
-  const uint32_t last = inside ? min(n_contrib[pix], len) : 0u;
+  const MapPixel m = map_pixel(W, H, grid_x, tile_order, ranges);
+  const size_t pix = m.pix, HW = (size_t)W * H;
+  const float pxf = (float)m.px, pyf = (float)m.py;
+  const uint32_t last = map_last(m, n_contrib, m.inside);
   const uint32_t tmax = block_max_u32(last, sMax);
 
   float T = 1.0f, D = 0.0f, I = 0.0f;
-  for (uint32_t base = 0; base < tmax; base += AUX_CHUNK) {
-    const uint32_t n = min((uint32_t)AUX_CHUNK, tmax - base);
+  for (uint32_t base = 0; base < tmax; base += MAP_CHUNK) {
+    const uint32_t n = min((uint32_t)MAP_CHUNK, tmax - base);
     if ((uint32_t)tid < n) {
-      AuxEntry e;
-      aux_load_entry(rec, bin, point_list[start + base + tid], e);
+      const MapEntry e = load_entry(rec, point_list[m.start + base + tid]);
+      const float z = bin[e.id].depth;
       sA[tid] = e.lr.A;
       sB[tid] = e.lr.B;
-      sZ[tid] = make_float2(e.z, 1.0f / e.z);
+      sZ[tid] = make_float2(z, 1.0f / z);
     }
     __syncthreads();
     const uint32_t mine = last > base ? min(n, last - base) : 0u;
     for (uint32_t k = 0; k < mine; ++k) {
       const float4 a = sA[k], b = sB[k];
-      const float alpha = clamp_alpha(__builtin_amdgcn_exp2f(pair_p2(a.x - pxf, a.y - pyf, a.z, a.w, b.x, b.y)), b.x);
+      const float alpha = map_alpha(a, b, pxf, pyf);
       if (alpha >= ALPHA_MIN) {
         const float2 z = sZ[k];
         const float w = alpha * T;
@@ -111,7 +74,7 @@ __global__ __launch_bounds__(AUX_CHUNK) void aux_maps_fwd_kernel(int W, int H, i
     }
     __syncthreads();
   }
-  if (inside) {
+  if (m.inside) {
     out[pix] = D;
     out[HW + pix] = I;
     out[2 * HW + pix] = 1.0f - T;
@@ -129,7 +92,7 @@ __global__ __launch_bounds__(AUX_CHUNK) void aux_maps_fwd_kernel(int W, int H, i
 // d mean2D (pixels), d conic, d opacity and d z and issues one float atomic add per quantity into acc[P][8].  A wave none
 // of whose pixels the entry reaches skips the entry.
 // ------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(AUX_CHUNK) void aux_maps_bwd_kernel(int W, int H, int grid_x,
+__global__ __launch_bounds__(MAP_CHUNK) void aux_maps_bwd_kernel(int W, int H, int grid_x,
                                                                  const uint32_t* __restrict__ tile_order,
                                                                  const uint2* __restrict__ ranges,
                                                                  const uint32_t* __restrict__ point_list,
@@ -139,22 +102,18 @@ __global__ __launch_bounds__(AUX_CHUNK) void aux_maps_bwd_kernel(int W, int H, i
                                                                  const float* __restrict__ final_T,
                                                                  const float* __restrict__ dL_dmaps,
                                                                  float* __restrict__ acc) {
-  __shared__ float4 sA[AUX_CHUNK];
-  __shared__ float4 sB[AUX_CHUNK];
-  __shared__ float2 sZ[AUX_CHUNK];
-  __shared__ float sSum[AUX_SUMS][AUX_CHUNK];
+  __shared__ float4 sA[MAP_CHUNK];
+  __shared__ float4 sB[MAP_CHUNK];
+  __shared__ float2 sZ[MAP_CHUNK];
+  __shared__ float sSum[AUX_SUMS][MAP_CHUNK];
   __shared__ uint32_t sMax[4];
   const int tid = threadIdx.x;
   const int lane = tid & (WAVE - 1);
-  const int tile = __builtin_amdgcn_readfirstlane((int)tile_order[blockIdx.x]);
-  const int tile_x = tile % grid_x, tile_y = tile / grid_x;
-  const int px = tile_x * TILE + (tid & (TILE - 1)), py = tile_y * TILE + tid / TILE;
-  const bool inside = px < W && py < H;
-  const size_t pix = (size_t)py * W + px, HW = (size_t)W * H;
-  const float pxf = (float)px, pyf = (float)py;
-  const uint2 range = ranges[tile];
-  const uint32_t start = range.x, len = range.y - range.x;
-  const uint32_t last = inside ? min(n_contrib[pix], len) : 0u;
+  const MapPixel m = map_pixel(W, H, grid_x, tile_order, ranges);
+  const bool inside = m.inside;
+  const size_t pix = m.pix, HW = (size_t)W * H;
+  const float pxf = (float)m.px, pyf = (float)m.py;
+  const uint32_t last = map_last(m, n_contrib, inside);
   const uint32_t tmax = block_max_u32(last, sMax);
   float T = inside ? final_T[pix] : 0.0f;
   const float g0 = inside ? dL_dmaps[pix] : 0.0f, g1 = inside ? dL_dmaps[HW + pix] : 0.0f,
@@ -163,61 +122,34 @@ __global__ __launch_bounds__(AUX_CHUNK) void aux_maps_bwd_kernel(int W, int H, i
 
   uint32_t hi = tmax;
   while (hi > 0) {
-    const uint32_t lo = hi > (uint32_t)AUX_CHUNK ? hi - AUX_CHUNK : 0u;
+    const uint32_t lo = hi > (uint32_t)MAP_CHUNK ? hi - MAP_CHUNK : 0u;
     const uint32_t n = hi - lo;
-    AuxEntry e;
-    e.cxx = e.cxy = e.cyy = e.opacity = 0.0f;
-    e.id = 0u;
+    MapEntry e;
     if ((uint32_t)tid < n) {
-      aux_load_entry(rec, bin, point_list[start + lo + tid], e);
+      e = load_entry(rec, point_list[m.start + lo + tid]);
+      const float z = bin[e.id].depth;
       sA[tid] = e.lr.A;
       sB[tid] = e.lr.B;
-      sZ[tid] = make_float2(e.z, 1.0f / e.z);
+      sZ[tid] = make_float2(z, 1.0f / z);
     }
 #pragma unroll
     for (int q = 0; q < AUX_SUMS; ++q) sSum[q][tid] = 0.0f;
     __syncthreads();
     for (uint32_t k = n; k-- > 0;) {
-      const float4 a = sA[k], b = sB[k];
-      const float dx = a.x - pxf, dy = a.y - pyf;
-      const float ar = __builtin_amdgcn_exp2f(pair_p2(dx, dy, a.z, a.w, b.x, b.y));      // opacity * G
-      const bool ok = lo + k < last && ar >= ALPHA_MIN;      // (the clamp is above the threshold: same test on either)
-      if (__builtin_amdgcn_ballot_w64(ok) == 0ull) continue;      // uniform over the wave
+      const float4 b = sB[k];
+      MapStep st = map_bwd_test(sA[k], b, pxf, pyf, lo + k < last);
+      if (__builtin_amdgcn_ballot_w64(st.ok) == 0ull) continue;      // uniform over the wave
       const float2 z = sZ[k];
-      // lanes the entry does not reach run the same instructions on alpha = 0: T and U stay, every sum gets zero
-      const float arm = ok ? ar : 0.0f;
-      const float am = clamp_alpha(arm, b.x);
-      T = T / (1.0f - am);                                   // transmittance in front of this entry
+      map_bwd_advance(st, b, T);
       const float cg = __builtin_fmaf(z.x, g0, __builtin_fmaf(z.y, g1, g2));
-      const float Dv = cg - U;
-      const float h = arm * T * Dv;                          // the clamp passes the gradient on, as in the colour backward
-      U = __builtin_fmaf(am, Dv, U);
+      const float h = map_bwd_dalpha(st, T, cg, U);
       float v[AUX_SUMS];
-      v[0] = h * dx; v[1] = h * dy; v[2] = v[0] * dx; v[3] = v[0] * dy; v[4] = v[1] * dy; v[5] = h;
-      v[6] = am * T * (g0 - g1 * z.y * z.y);
-#pragma unroll
-      for (int q = 0; q < AUX_SUMS; ++q) {
-        const float s = wave_reduce_add_f32(v[q]);
-        if (lane == 0) atomicAdd(&sSum[q][k], s);
-      }
+      geom_terms(h, st.dx, st.dy, v);
+      v[6] = st.am * T * (g0 - g1 * z.y * z.y);
+      map_add_sums(v, sSum, k, lane);
     }
     __syncthreads();
-    if ((uint32_t)tid < n) {
-      float s[AUX_SUMS];
-      uint32_t bits = 0u;
-#pragma unroll
-      for (int q = 0; q < AUX_SUMS; ++q) { s[q] = sSum[q][tid]; bits |= __float_as_uint(s[q]); }
-      if ((bits << 1) != 0u) {
-        float* row = acc + 8 * (size_t)e.id;
-        atomicAdd(row + 0, -(e.cxx * s[0] + e.cxy * s[1]));      // d mean2D, pixel units
-        atomicAdd(row + 1, -(e.cxy * s[0] + e.cyy * s[1]));
-        atomicAdd(row + 2, -0.5f * s[2]);                        // d conic xx, xy (true derivative), yy
-        atomicAdd(row + 3, -s[3]);
-        atomicAdd(row + 4, -0.5f * s[4]);
-        atomicAdd(row + 5, s[5] / e.opacity);                    // d opacity
-        atomicAdd(row + 6, s[6]);                                // d z
-      }
-    }
+    if ((uint32_t)tid < n) map_flush_acc<AUX_SUMS>(sSum, tid, e, acc);
     __syncthreads();
     hi = lo;
   }
@@ -428,20 +360,14 @@ __global__ __launch_bounds__(PRE_BLOCK) void aux_geom_bwd_kernel(GsrParams p, co
   }
 }
 
-void launch_aux_maps_fwd(int W, int H, const uint2* ranges, const uint32_t* point_list, const GeomRec* rec,
-                         const BinInfo* bin, const uint32_t* n_contrib, const uint32_t* tile_order, float* out,
-                         hipStream_t s) {
-  const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
-  hipLaunchKernelGGL(aux_maps_fwd_kernel, dim3(gx * gy), dim3(AUX_CHUNK), 0, s, W, H, gx, tile_order, ranges, point_list, rec,
-                     bin, n_contrib, out);
+void launch_aux_maps_fwd(const MapFrame& f, float* out, hipStream_t s) {
+  hipLaunchKernelGGL(aux_maps_fwd_kernel, dim3(f.tiles), dim3(MAP_CHUNK), 0, s, f.W, f.H, f.grid_x, f.tile_order, f.ranges,
+                     f.point_list, f.rec, f.bin, f.n_contrib, out);
 }
 
-void launch_aux_maps_bwd(int W, int H, const uint2* ranges, const uint32_t* point_list, const GeomRec* rec,
-                         const BinInfo* bin, const uint32_t* n_contrib, const float* final_T, const uint32_t* tile_order,
-                         const float* dL_dmaps, float* acc, hipStream_t s) {
-  const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
-  hipLaunchKernelGGL(aux_maps_bwd_kernel, dim3(gx * gy), dim3(AUX_CHUNK), 0, s, W, H, gx, tile_order, ranges, point_list, rec,
-                     bin, n_contrib, final_T, dL_dmaps, acc);
+void launch_aux_maps_bwd(const MapFrame& f, const float* dL_dmaps, float* acc, hipStream_t s) {
+  hipLaunchKernelGGL(aux_maps_bwd_kernel, dim3(f.tiles), dim3(MAP_CHUNK), 0, s, f.W, f.H, f.grid_x, f.tile_order, f.ranges,
+                     f.point_list, f.rec, f.bin, f.n_contrib, f.final_T, dL_dmaps, acc);
 }
 
 void launch_aux_geom_bwd(const GsrParams& p, const int32_t* radii, const float* acc, const GsrAuxGrads& g, hipStream_t s) {

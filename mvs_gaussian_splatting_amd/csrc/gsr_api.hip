@@ -378,6 +378,34 @@ static int enqueue_stage2(const GsrParams* p, void* geom_ws, void* bin_ws, size_
   return check(p, s, "render_fwd");
 }
 
+// ---- shared by the map entry points below (depth, features, distortion, median, contribution) ----------------------
+// what the map kernels read of a validated frame that is not empty
+static MapFrame map_frame(const GsrAuxFrame* f) {
+  const ImageLayout I(f->width, f->height);
+  const GeomLayout L(f->P);
+  const SortedViews sv = sorted_views(f->bin_ws, f->num_rendered, f->num_visible, f->width, f->height, f->binning_mode);
+  return MapFrame{f->width, f->height, I.grid_x, I.tiles, at<uint2>(f->img_ws, I.ranges), sv.point_list,
+                  at<GeomRec>(f->geom_ws, L.rec), at<BinInfo>(f->geom_ws, L.bin), at<uint32_t>(f->img_ws, I.n_contrib),
+                  at<float>(f->img_ws, I.final_T), at<uint32_t>(f->img_ws, I.tile_order)};
+}
+
+// A map's backward behind its refusals: zero acc [P,8] (nullptr: the geometry side is not wanted, and g is NULL), then
+// also_zero (the features' dL_dfeatures; nullptr: nothing), run the map's own kernel (launch, named where) on the frame's
+// lists, then take acc to the inputs with aux_geom_bwd
+template <typename Launch>
+static int run_geom_backward(const GsrParams* p, const GsrAuxFrame* f, float* acc, const GsrAuxGrads* g, hipStream_t s,
+                             const char* where, Launch launch, void* also_zero = nullptr, size_t also_zero_bytes = 0) {
+  if (acc) GSR_HIP(hipMemsetAsync(acc, 0, 32 * (size_t)p->P, s));
+  if (also_zero) GSR_HIP(hipMemsetAsync(also_zero, 0, also_zero_bytes, s));
+  if (f->num_rendered > 0) {
+    launch(map_frame(f));
+    if (int rc = check(p, s, where)) return rc;
+  }
+  if (!g) return 0;
+  launch_aux_geom_bwd(*p, f->radii, acc, *g, s);
+  return check(p, s, "aux_geom_bwd");
+}
+
 extern "C" {
 
 int gsr_forward_preprocess(const GsrParams* p, void* geom_ws, int32_t* radii, void* stream, uint32_t* num_rendered,
@@ -593,53 +621,62 @@ static int validate_aux_inputs(const GsrParams* p) {
   return 0;
 }
 
+// nothing was binned: every list is empty
+static bool frame_is_empty(const GsrAuxFrame* f) { return f->P == 0 || f->num_rendered == 0; }
+
+// The refusals the maps' backwards share.  A map's own argument checks sit between them, where they have always sat:
+// refuse_backward opens every backward, refuse_mismatch follows the map's checks, and behind the "P == 0: nothing to
+// do" return come refuse_geom_outputs (the maps with a [P,8] accumulator) or refuse_acc_ws alone (the median).
+static int refuse_backward(const GsrParams* p, const GsrAuxFrame* f) {
+  if (!p) return fail(GSR_E_BADARG, "params is NULL");
+  if (p->forward_only) return fail(GSR_E_BADARG, "the forward ran with forward_only = 1: no state for a backward");
+  return validate_aux_frame(f);
+}
+static int refuse_mismatch(const GsrParams* p, const GsrAuxFrame* f) {
+  if (f->P != p->P || f->width != p->width || f->height != p->height) return fail(GSR_E_BADARG, "frame and params disagree");
+  return 0;
+}
+// short_code: what a workspace of fewer than `need` bytes is answered with
+static int refuse_acc_ws(const void* acc_ws, size_t acc_ws_bytes, size_t need, int short_code) {
+  if (acc_ws_bytes < need) return fail(short_code, "accumulator workspace too small");
+  if (((uintptr_t)acc_ws & 255u) != 0) return fail(GSR_E_ALIGN, "acc_ws must be 256-byte aligned");
+  return 0;
+}
+// have_inputs: the map's own input pointers are all there
+static int refuse_geom_outputs(const GsrParams* p, const GsrAuxFrame* f, bool have_inputs, const void* acc_ws,
+                               size_t acc_ws_bytes, const GsrAuxGrads* g, int short_code) {
+  if (!have_inputs || !acc_ws || !f->radii) return fail(GSR_E_BADARG, "NULL workspace / input");
+  if (!g->dL_dmeans3D || !g->dL_dmeans2D || !g->dL_dopacities)
+    return fail(GSR_E_BADARG, "dL_dmeans3D / dL_dmeans2D / dL_dopacities must be non-NULL");
+  return refuse_acc_ws(acc_ws, acc_ws_bytes, gsr_aux_maps_backward_bytes(p->P), short_code);
+}
+
 size_t gsr_aux_maps_backward_bytes(int32_t P) { return align_up(32 * (size_t)(P > 0 ? P : 1), 256); }
 
 int gsr_aux_maps_forward(const GsrAuxFrame* f, float* maps, void* stream) {
   if (int rc = validate_aux_frame(f)) return rc;
   if (!maps) return fail(GSR_E_BADARG, "maps is NULL");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const ImageLayout I(f->width, f->height);
-  if (f->P == 0 || f->num_rendered == 0) {      // nothing was binned: every list is empty
+  if (frame_is_empty(f)) {
     GSR_HIP(hipMemsetAsync(maps, 0, 12 * (size_t)f->width * f->height, s));
     return 0;
   }
-  const GeomLayout L(f->P);
-  const SortedViews sv = sorted_views(f->bin_ws, f->num_rendered, f->num_visible, f->width, f->height, f->binning_mode);
-  launch_aux_maps_fwd(f->width, f->height, at<uint2>(f->img_ws, I.ranges), sv.point_list, at<GeomRec>(f->geom_ws, L.rec),
-                      at<BinInfo>(f->geom_ws, L.bin), at<uint32_t>(f->img_ws, I.n_contrib),
-                      at<uint32_t>(f->img_ws, I.tile_order), maps, s);
+  launch_aux_maps_fwd(map_frame(f), maps, s);
   return check(nullptr, s, "aux_maps_fwd");
 }
 
 int gsr_aux_maps_backward(const GsrParams* p, const GsrAuxFrame* f, const float* dL_dmaps, void* acc_ws,
                           size_t acc_ws_bytes, const GsrAuxGrads* g, void* stream) {
-  if (!p) return fail(GSR_E_BADARG, "params is NULL");
-  if (p->forward_only) return fail(GSR_E_BADARG, "the forward ran with forward_only = 1: no state for a backward");
-  if (int rc = validate_aux_frame(f)) return rc;
+  if (int rc = refuse_backward(p, f)) return rc;
   if (int rc = validate_aux_inputs(p)) return rc;
-  if (f->P != p->P || f->width != p->width || f->height != p->height) return fail(GSR_E_BADARG, "frame and params disagree");
+  if (int rc = refuse_mismatch(p, f)) return rc;
   if (!g) return fail(GSR_E_BADARG, "grads is NULL");
   if (p->P == 0) return 0;
-  if (!dL_dmaps || !acc_ws || !f->radii) return fail(GSR_E_BADARG, "NULL workspace / input");
-  if (!g->dL_dmeans3D || !g->dL_dmeans2D || !g->dL_dopacities)
-    return fail(GSR_E_BADARG, "dL_dmeans3D / dL_dmeans2D / dL_dopacities must be non-NULL");
-  if (acc_ws_bytes < gsr_aux_maps_backward_bytes(p->P)) return fail(GSR_E_CAPACITY, "accumulator workspace too small");
-  if (((uintptr_t)acc_ws & 255u) != 0) return fail(GSR_E_ALIGN, "acc_ws must be 256-byte aligned");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const ImageLayout I(f->width, f->height);
-  const GeomLayout L(f->P);
+  if (int rc = refuse_geom_outputs(p, f, dL_dmaps != nullptr, acc_ws, acc_ws_bytes, g, GSR_E_CAPACITY)) return rc;
   float* acc = static_cast<float*>(acc_ws);
-  GSR_HIP(hipMemsetAsync(acc, 0, 32 * (size_t)p->P, s));
-  if (f->num_rendered > 0) {
-    const SortedViews sv = sorted_views(f->bin_ws, f->num_rendered, f->num_visible, f->width, f->height, f->binning_mode);
-    launch_aux_maps_bwd(f->width, f->height, at<uint2>(f->img_ws, I.ranges), sv.point_list, at<GeomRec>(f->geom_ws, L.rec),
-                        at<BinInfo>(f->geom_ws, L.bin), at<uint32_t>(f->img_ws, I.n_contrib), at<float>(f->img_ws, I.final_T),
-                        at<uint32_t>(f->img_ws, I.tile_order), dL_dmaps, acc, s);
-    if (int rc = check(p, s, "aux_maps_bwd")) return rc;
-  }
-  launch_aux_geom_bwd(*p, f->radii, acc, *g, s);
-  return check(p, s, "aux_geom_bwd");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return run_geom_backward(p, f, acc, g, s, "aux_maps_bwd",
+                           [&](const MapFrame& mf) { launch_aux_maps_bwd(mf, dL_dmaps, acc, s); });
 }
 
 // ---- per-Gaussian feature vectors composited to C-channel maps (csrc/features.hip) ---------------------------------
@@ -657,55 +694,32 @@ int gsr_feature_maps_forward(const GsrAuxFrame* f, const float* features, int32_
   if (int rc = validate_features(features, C)) return rc;
   if (!maps) return fail(GSR_E_BADARG, "maps is NULL");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const ImageLayout I(f->width, f->height);
-  if (f->P == 0 || f->num_rendered == 0) {      // nothing was binned: every list is empty
+  if (frame_is_empty(f)) {
     GSR_HIP(hipMemsetAsync(maps, 0, 4 * (size_t)C * f->width * f->height, s));
     return 0;
   }
-  const GeomLayout L(f->P);
-  const SortedViews sv = sorted_views(f->bin_ws, f->num_rendered, f->num_visible, f->width, f->height, f->binning_mode);
-  launch_feature_maps_fwd(f->width, f->height, at<uint2>(f->img_ws, I.ranges), sv.point_list,
-                          at<GeomRec>(f->geom_ws, L.rec), at<uint32_t>(f->img_ws, I.n_contrib),
-                          at<uint32_t>(f->img_ws, I.tile_order), features, C, maps, s);
+  launch_feature_maps_fwd(map_frame(f), features, C, maps, s);
   return check(nullptr, s, "feature_maps_fwd");
 }
 
 int gsr_feature_maps_backward(const GsrParams* p, const GsrAuxFrame* f, const float* features, int32_t C,
                               const float* dL_dmaps, float* dL_dfeatures, void* acc_ws, size_t acc_ws_bytes,
                               const GsrAuxGrads* g, void* stream) {
-  if (!p) return fail(GSR_E_BADARG, "params is NULL");
-  if (p->forward_only) return fail(GSR_E_BADARG, "the forward ran with forward_only = 1: no state for a backward");
-  if (int rc = validate_aux_frame(f)) return rc;
+  if (int rc = refuse_backward(p, f)) return rc;
   if (int rc = validate_features(features, C)) return rc;
-  if (f->P != p->P || f->width != p->width || f->height != p->height) return fail(GSR_E_BADARG, "frame and params disagree");
+  if (int rc = refuse_mismatch(p, f)) return rc;
   if (p->P == 0 || (!g && !dL_dfeatures)) return 0;
   if (!dL_dmaps) return fail(GSR_E_BADARG, "dL_dmaps is NULL");
-  float* acc = nullptr;
   if (g) {
     if (int rc = validate_aux_inputs(p)) return rc;
-    if (!acc_ws || !f->radii) return fail(GSR_E_BADARG, "NULL workspace / input");
-    if (!g->dL_dmeans3D || !g->dL_dmeans2D || !g->dL_dopacities)
-      return fail(GSR_E_BADARG, "dL_dmeans3D / dL_dmeans2D / dL_dopacities must be non-NULL");
-    if (acc_ws_bytes < gsr_feature_maps_backward_bytes(p->P)) return fail(GSR_E_CAPACITY, "accumulator workspace too small");
-    if (((uintptr_t)acc_ws & 255u) != 0) return fail(GSR_E_ALIGN, "acc_ws must be 256-byte aligned");
-    acc = static_cast<float*>(acc_ws);
+    if (int rc = refuse_geom_outputs(p, f, true, acc_ws, acc_ws_bytes, g, GSR_E_CAPACITY)) return rc;
   }
+  float* acc = g ? static_cast<float*>(acc_ws) : nullptr;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const ImageLayout I(f->width, f->height);
-  const GeomLayout L(f->P);
-  if (acc) GSR_HIP(hipMemsetAsync(acc, 0, 32 * (size_t)p->P, s));
-  if (dL_dfeatures) GSR_HIP(hipMemsetAsync(dL_dfeatures, 0, 4 * (size_t)p->P * (size_t)C, s));
-  if (f->num_rendered > 0) {
-    const SortedViews sv = sorted_views(f->bin_ws, f->num_rendered, f->num_visible, f->width, f->height, f->binning_mode);
-    launch_feature_maps_bwd(f->width, f->height, at<uint2>(f->img_ws, I.ranges), sv.point_list,
-                            at<GeomRec>(f->geom_ws, L.rec), at<uint32_t>(f->img_ws, I.n_contrib),
-                            at<float>(f->img_ws, I.final_T), at<uint32_t>(f->img_ws, I.tile_order), features, C, dL_dmaps,
-                            acc, dL_dfeatures, s);
-    if (int rc = check(p, s, "feature_maps_bwd")) return rc;
-  }
-  if (!g) return 0;
-  launch_aux_geom_bwd(*p, f->radii, acc, *g, s);
-  return check(p, s, "aux_geom_bwd");
+  return run_geom_backward(
+      p, f, acc, g, s, "feature_maps_bwd",
+      [&](const MapFrame& mf) { launch_feature_maps_bwd(mf, features, C, dL_dmaps, acc, dL_dfeatures, s); }, dL_dfeatures,
+      dL_dfeatures ? 4 * (size_t)p->P * (size_t)C : 0);
 }
 
 // ---- depth-distortion map (csrc/distortion.hip) --------------------------------------------------------------------
@@ -724,51 +738,31 @@ int gsr_distortion_forward(const GsrAuxFrame* f, int32_t mapping, float near, fl
   if (int rc = validate_distortion_mapping(mapping, near, far)) return rc;
   if (!dist || !state) return fail(GSR_E_BADARG, "dist / state is NULL");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const ImageLayout I(f->width, f->height);
-  if (f->P == 0 || f->num_rendered == 0) {      // nothing was binned: every list is empty
+  if (frame_is_empty(f)) {
     GSR_HIP(hipMemsetAsync(dist, 0, 4 * (size_t)f->width * f->height, s));
     GSR_HIP(hipMemsetAsync(state, 0, 8 * (size_t)f->width * f->height, s));
     return 0;
   }
-  const GeomLayout L(f->P);
-  const SortedViews sv = sorted_views(f->bin_ws, f->num_rendered, f->num_visible, f->width, f->height, f->binning_mode);
-  launch_distortion_fwd(f->width, f->height, at<uint2>(f->img_ws, I.ranges), sv.point_list, at<GeomRec>(f->geom_ws, L.rec),
-                        at<BinInfo>(f->geom_ws, L.bin), at<uint32_t>(f->img_ws, I.n_contrib),
-                        at<uint32_t>(f->img_ws, I.tile_order), mapping, near, far, dist, state, s);
+  launch_distortion_fwd(map_frame(f), mapping, near, far, dist, state, s);
   return check(nullptr, s, "distortion_fwd");
 }
 
 int gsr_distortion_backward(const GsrParams* p, const GsrAuxFrame* f, int32_t mapping, float near, float far,
                             const float* state, const float* dL_ddist, void* acc_ws, size_t acc_ws_bytes,
                             const GsrAuxGrads* g, void* stream) {
-  if (!p) return fail(GSR_E_BADARG, "params is NULL");
-  if (p->forward_only) return fail(GSR_E_BADARG, "the forward ran with forward_only = 1: no state for a backward");
-  if (int rc = validate_aux_frame(f)) return rc;
+  if (int rc = refuse_backward(p, f)) return rc;
   if (int rc = validate_distortion_mapping(mapping, near, far)) return rc;
   if (int rc = validate_aux_inputs(p)) return rc;
-  if (f->P != p->P || f->width != p->width || f->height != p->height) return fail(GSR_E_BADARG, "frame and params disagree");
+  if (int rc = refuse_mismatch(p, f)) return rc;
   if (!g) return fail(GSR_E_BADARG, "grads is NULL");
   if (p->P == 0) return 0;
-  if (!state || !dL_ddist || !acc_ws || !f->radii) return fail(GSR_E_BADARG, "NULL workspace / input");
-  if (!g->dL_dmeans3D || !g->dL_dmeans2D || !g->dL_dopacities)
-    return fail(GSR_E_BADARG, "dL_dmeans3D / dL_dmeans2D / dL_dopacities must be non-NULL");
-  if (acc_ws_bytes < gsr_distortion_backward_bytes(p->P)) return fail(GSR_E_BADARG, "accumulator workspace too small");
-  if (((uintptr_t)acc_ws & 255u) != 0) return fail(GSR_E_ALIGN, "acc_ws must be 256-byte aligned");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const ImageLayout I(f->width, f->height);
-  const GeomLayout L(f->P);
+  // a short workspace is GSR_E_BADARG here, GSR_E_CAPACITY in the other backwards: callers have seen both
+  if (int rc = refuse_geom_outputs(p, f, state && dL_ddist, acc_ws, acc_ws_bytes, g, GSR_E_BADARG)) return rc;
   float* acc = static_cast<float*>(acc_ws);
-  GSR_HIP(hipMemsetAsync(acc, 0, 32 * (size_t)p->P, s));
-  if (f->num_rendered > 0) {
-    const SortedViews sv = sorted_views(f->bin_ws, f->num_rendered, f->num_visible, f->width, f->height, f->binning_mode);
-    launch_distortion_bwd(f->width, f->height, at<uint2>(f->img_ws, I.ranges), sv.point_list, at<GeomRec>(f->geom_ws, L.rec),
-                          at<BinInfo>(f->geom_ws, L.bin), at<uint32_t>(f->img_ws, I.n_contrib),
-                          at<float>(f->img_ws, I.final_T), at<uint32_t>(f->img_ws, I.tile_order), mapping, near, far, state,
-                          dL_ddist, acc, s);
-    if (int rc = check(p, s, "distortion_bwd")) return rc;
-  }
-  launch_aux_geom_bwd(*p, f->radii, acc, *g, s);
-  return check(p, s, "aux_geom_bwd");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return run_geom_backward(p, f, acc, g, s, "distortion_bwd", [&](const MapFrame& mf) {
+    launch_distortion_bwd(mf, mapping, near, far, state, dL_ddist, acc, s);
+  });
 }
 
 // ---- median-depth map and Gaussian id map (csrc/median.hip) ----------------------------------------------------------
@@ -778,41 +772,30 @@ int gsr_median_depth_forward(const GsrAuxFrame* f, float* median, int32_t* media
   if (int rc = validate_aux_frame(f)) return rc;
   if (!median || !median_id || !state) return fail(GSR_E_BADARG, "median / median_id / state is NULL");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const ImageLayout I(f->width, f->height);
-  if (f->P == 0 || f->num_rendered == 0) {      // nothing was binned: every list is empty
+  if (frame_is_empty(f)) {
     const size_t hw = (size_t)f->width * f->height;
     GSR_HIP(hipMemsetAsync(median, 0, 4 * hw, s));
     GSR_HIP(hipMemsetAsync(median_id, 0xff, 4 * hw, s));      // -1
     GSR_HIP(hipMemsetAsync(state, 0xff, 4 * hw, s));          // no entry
     return 0;
   }
-  const GeomLayout L(f->P);
-  const SortedViews sv = sorted_views(f->bin_ws, f->num_rendered, f->num_visible, f->width, f->height, f->binning_mode);
-  launch_median_depth_fwd(f->width, f->height, at<uint2>(f->img_ws, I.ranges), sv.point_list, at<GeomRec>(f->geom_ws, L.rec),
-                          at<BinInfo>(f->geom_ws, L.bin), at<uint32_t>(f->img_ws, I.n_contrib),
-                          at<uint32_t>(f->img_ws, I.tile_order), median, median_id, state, s);
+  launch_median_depth_fwd(map_frame(f), median, median_id, state, s);
   return check(nullptr, s, "median_depth_fwd");
 }
 
 int gsr_median_depth_backward(const GsrParams* p, const GsrAuxFrame* f, const uint32_t* state, const float* dL_dmedian,
                               void* acc_ws, size_t acc_ws_bytes, float* dL_dmeans3D, void* stream) {
-  if (!p) return fail(GSR_E_BADARG, "params is NULL");
-  if (p->forward_only) return fail(GSR_E_BADARG, "the forward ran with forward_only = 1: no state for a backward");
-  if (int rc = validate_aux_frame(f)) return rc;
-  if (f->P != p->P || f->width != p->width || f->height != p->height) return fail(GSR_E_BADARG, "frame and params disagree");
+  if (int rc = refuse_backward(p, f)) return rc;
+  if (int rc = refuse_mismatch(p, f)) return rc;
   if (p->P == 0) return 0;
   if (!p->viewmatrix) return fail(GSR_E_BADARG, "viewmatrix must be non-NULL");
   if (!state || !dL_dmedian || !acc_ws || !dL_dmeans3D) return fail(GSR_E_BADARG, "NULL workspace / input / output");
-  if (acc_ws_bytes < gsr_median_depth_backward_bytes(p->P)) return fail(GSR_E_CAPACITY, "accumulator workspace too small");
-  if (((uintptr_t)acc_ws & 255u) != 0) return fail(GSR_E_ALIGN, "acc_ws must be 256-byte aligned");
+  if (int rc = refuse_acc_ws(acc_ws, acc_ws_bytes, gsr_median_depth_backward_bytes(p->P), GSR_E_CAPACITY)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const ImageLayout I(f->width, f->height);
   float* acc = static_cast<float*>(acc_ws);
   GSR_HIP(hipMemsetAsync(acc, 0, 4 * (size_t)p->P, s));
   if (f->num_rendered > 0) {
-    const SortedViews sv = sorted_views(f->bin_ws, f->num_rendered, f->num_visible, f->width, f->height, f->binning_mode);
-    launch_median_depth_bwd(f->width, f->height, at<uint2>(f->img_ws, I.ranges), sv.point_list,
-                            at<uint32_t>(f->img_ws, I.tile_order), state, dL_dmedian, acc, s);
+    launch_median_depth_bwd(map_frame(f), state, dL_dmedian, acc, s);
     if (int rc = check(p, s, "median_depth_bwd")) return rc;
   }
   launch_median_depth_finish(p->P, p->viewmatrix, acc, dL_dmeans3D, s);
@@ -822,15 +805,11 @@ int gsr_median_depth_backward(const GsrParams* p, const GsrAuxFrame* f, const ui
 // ---- per-Gaussian contribution statistics (csrc/contribution.hip) --------------------------------------------------
 int gsr_contribution_accumulate(const GsrAuxFrame* f, const uint8_t* pixel_mask, int64_t* stats, void* stream) {
   if (int rc = validate_aux_frame(f)) return rc;
-  if (f->P == 0 || f->num_rendered == 0) return 0;      // nothing was binned: every list is empty
+  if (frame_is_empty(f)) return 0;
   if (!stats) return fail(GSR_E_BADARG, "stats is NULL");
   if (((uintptr_t)stats & 7u) != 0) return fail(GSR_E_ALIGN, "stats must be 8-byte aligned");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const ImageLayout I(f->width, f->height);
-  const GeomLayout L(f->P);
-  const SortedViews sv = sorted_views(f->bin_ws, f->num_rendered, f->num_visible, f->width, f->height, f->binning_mode);
-  launch_contribution(f->width, f->height, at<uint2>(f->img_ws, I.ranges), sv.point_list, at<GeomRec>(f->geom_ws, L.rec),
-                      at<uint32_t>(f->img_ws, I.n_contrib), at<uint32_t>(f->img_ws, I.tile_order), pixel_mask, stats, s);
+  launch_contribution(map_frame(f), pixel_mask, stats, s);
   return check(nullptr, s, "contribution");
 }
 

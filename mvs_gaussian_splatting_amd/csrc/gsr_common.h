@@ -302,4 +302,16 @@ __device__ inline float wave_reduce_add_f32(float v) {
   return v;
 }
 
+__device__ inline double wave_reduce_add_f64(double v) {
+#pragma unroll
+  for (int d = WAVE / 2; d > 0; d >>= 1) v += __shfl_xor(v, d, WAVE);
+  return v;
+}
+
+__device__ inline uint32_t wave_reduce_max_u32(uint32_t v) {
+#pragma unroll
+  for (int d = WAVE / 2; d > 0; d >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, d, WAVE));
+  return v;
+}
+
 }  // namespace gsr

@@ -103,53 +103,48 @@ void launch_render_bwd(int W, int H, const uint2* ranges, const uint32_t* point_
                        const float* dL_dpix, GradRow* rows, uint8_t* row_flags, const uint32_t* tile_order,
                        hipStream_t s, const uint16_t* inst_mask);
 
+// What the map kernels read of a rendered frame (gsr_api.hip: map_frame builds it from a validated GsrAuxFrame).
+struct MapFrame {
+  int W, H, grid_x, tiles;
+  const uint2* ranges;
+  const uint32_t* point_list;
+  const GeomRec* rec;
+  const BinInfo* bin;
+  const uint32_t* n_contrib;
+  const float* final_T;
+  const uint32_t* tile_order;
+};
+
 // depth.hip: depth / inverse-depth / alpha maps of a rendered frame and their gradients (acc: zeroed [P,8] floats)
-void launch_aux_maps_fwd(int W, int H, const uint2* ranges, const uint32_t* point_list, const GeomRec* rec,
-                         const BinInfo* bin, const uint32_t* n_contrib, const uint32_t* tile_order, float* out,
-                         hipStream_t s);
-void launch_aux_maps_bwd(int W, int H, const uint2* ranges, const uint32_t* point_list, const GeomRec* rec,
-                         const BinInfo* bin, const uint32_t* n_contrib, const float* final_T, const uint32_t* tile_order,
-                         const float* dL_dmaps, float* acc, hipStream_t s);
+void launch_aux_maps_fwd(const MapFrame& f, float* out, hipStream_t s);
+void launch_aux_maps_bwd(const MapFrame& f, const float* dL_dmaps, float* acc, hipStream_t s);
 void launch_aux_geom_bwd(const GsrParams& p, const int32_t* radii, const float* acc, const GsrAuxGrads& g, hipStream_t s);
 
 // features.hip: per-Gaussian feature rows features[P,C] composited to C-channel maps of a rendered frame (the entries and
 // weights of depth.hip), and the backward: geometry sums into acc [P,8] (the layout launch_aux_geom_bwd reads; nullptr:
 // not wanted), dL/dfeatures added into dL_dfeatures [P,C] (zeroed by the caller; nullptr: not wanted)
-void launch_feature_maps_fwd(int W, int H, const uint2* ranges, const uint32_t* point_list, const GeomRec* rec,
-                             const uint32_t* n_contrib, const uint32_t* tile_order, const float* features, int C,
-                             float* out, hipStream_t s);
-void launch_feature_maps_bwd(int W, int H, const uint2* ranges, const uint32_t* point_list, const GeomRec* rec,
-                             const uint32_t* n_contrib, const float* final_T, const uint32_t* tile_order,
-                             const float* features, int C, const float* dL_dmaps, float* acc, float* dL_dfeatures,
-                             hipStream_t s);
+void launch_feature_maps_fwd(const MapFrame& f, const float* features, int C, float* out, hipStream_t s);
+void launch_feature_maps_bwd(const MapFrame& f, const float* features, int C, const float* dL_dmaps, float* acc,
+                             float* dL_dfeatures, hipStream_t s);
 
 // distortion.hip: the depth-distortion map dist [1,H,W] of a rendered frame (the entries and weights of depth.hip; mapping
 // 0: m = z, 1: m = far / (far - near) (1 - near / z)), the per-pixel state [2,H,W] its backward reads, and the backward:
 // sums into acc [P,8] (zeroed by the caller; the layout launch_aux_geom_bwd reads, d z word included)
-void launch_distortion_fwd(int W, int H, const uint2* ranges, const uint32_t* point_list, const GeomRec* rec,
-                           const BinInfo* bin, const uint32_t* n_contrib, const uint32_t* tile_order, int mapping,
-                           float near, float far, float* dist, float* state, hipStream_t s);
-void launch_distortion_bwd(int W, int H, const uint2* ranges, const uint32_t* point_list, const GeomRec* rec,
-                           const BinInfo* bin, const uint32_t* n_contrib, const float* final_T, const uint32_t* tile_order,
-                           int mapping, float near, float far, const float* state, const float* dL_ddist, float* acc,
-                           hipStream_t s);
+void launch_distortion_fwd(const MapFrame& f, int mapping, float near, float far, float* dist, float* state, hipStream_t s);
+void launch_distortion_bwd(const MapFrame& f, int mapping, float near, float far, const float* state, const float* dL_ddist,
+                           float* acc, hipStream_t s);
 
 // median.hip: the median-depth map median [1,H,W] of a rendered frame (z of the last composited entry whose transmittance
 // in front of it exceeds one half; the entries of depth.hip), the id of that entry's Gaussian median_id [H,W] (-1: none) and
 // its list position state [H,W] (0xffffffff: none); the backward adds dL_dmedian into acc [P] (zeroed by the caller, one
 // global atomic per tile and entry) and the finish kernel writes d_means3D [P,3] = acc * viewmatrix[0:3, 2] in full
-void launch_median_depth_fwd(int W, int H, const uint2* ranges, const uint32_t* point_list, const GeomRec* rec,
-                             const BinInfo* bin, const uint32_t* n_contrib, const uint32_t* tile_order, float* median,
-                             int32_t* median_id, uint32_t* state, hipStream_t s);
-void launch_median_depth_bwd(int W, int H, const uint2* ranges, const uint32_t* point_list, const uint32_t* tile_order,
-                             const uint32_t* state, const float* dL_dmedian, float* acc, hipStream_t s);
+void launch_median_depth_fwd(const MapFrame& f, float* median, int32_t* median_id, uint32_t* state, hipStream_t s);
+void launch_median_depth_bwd(const MapFrame& f, const uint32_t* state, const float* dL_dmedian, float* acc, hipStream_t s);
 void launch_median_depth_finish(int P, const float* viewmatrix, const float* acc, float* d_means3D, hipStream_t s);
 
 // contribution.hip: per-Gaussian blending-weight statistics of a rendered frame, added into stats [P,3] (int64: sum of
 // round(w 2^30), pixel count, float bits of the largest w) with integer atomics; pixel_mask: nullptr or [H,W] bytes
-void launch_contribution(int W, int H, const uint2* ranges, const uint32_t* point_list, const GeomRec* rec,
-                         const uint32_t* n_contrib, const uint32_t* tile_order, const uint8_t* pixel_mask, int64_t* stats,
-                         hipStream_t s);
+void launch_contribution(const MapFrame& f, const uint8_t* pixel_mask, int64_t* stats, hipStream_t s);
 
 // loss.hip
 void launch_l1_dssim(const float* x, const float* gt, int C, int H, int W, float lambda, int dssim_mode, float* sums,

@@ -5,8 +5,8 @@
 //   median = z_{k*},   median_id = id_{k*}                 (0 / -1 on a pixel without a composited entry)
 //
 // over the list entries the colour pass composited at the pixel -- the entries of depth.hip (§7.9): the first
-// n_contrib[pixel] entries of the tile's list whose alpha passes the 1/255 test, alpha evaluated with the colour pass's own
-// functions (render_pair.h) and T updated with its single fma, so the decisions and the running T come out bit for bit.
+// n_contrib[pixel] entries of the tile's list whose alpha passes the 1/255 test, alpha evaluated by the walk the maps share
+// (map_walk.h) and T updated with the colour pass's single fma, so the decisions and the running T come out bit for bit.
 // z is BinInfo::depth.  This is 2DGS's rule `if (T > 0.5) { median_depth = depth; median_contributor = i; }`, taken
 // before the blend: the first composited entry always qualifies (T = 1), and a ray that never gets below one half keeps
 // its last composited entry.
@@ -23,21 +23,11 @@
 // Built with the flags of depth.o; the arithmetic that has to match the colour pass is explicit fma.
 #include "gsr_common.h"
 #include "gsr_launch.h"
-#include "render_pair.h"
+#include "map_walk.h"
 
 namespace gsr {
 
-constexpr int MED_CHUNK = 256;                  // list entries staged per round: one per lane of the workgroup
 constexpr uint32_t MED_NONE = 0xffffffffu;      // state of a pixel without a composited entry
-
-// largest value of v over the workgroup's 256 lanes (every lane calls it)
-__device__ inline uint32_t med_block_max_u32(uint32_t v, uint32_t* s4) {
-#pragma unroll
-  for (int d = WAVE / 2; d > 0; d >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, d, WAVE));
-  if ((threadIdx.x & (WAVE - 1)) == 0) s4[threadIdx.x / WAVE] = v;
-  __syncthreads();
-  return max(max(s4[0], s4[1]), max(s4[2], s4[3]));
-}
 
 // ------------------------------------------------------------------------------------------------------------------
 // Forward: one 256-lane workgroup per tile (the colour pass's tile order), one lane per pixel.  A round stages up to 256
@@ -46,7 +36,7 @@ __device__ inline uint32_t med_block_max_u32(uint32_t v, uint32_t* s4) {
 // behind the barrier that also ends the previous round: both barriers of a round are reached by all 256 lanes, the
 // lane-dependent work sits between them.  No atomics: the maps are the same bits from run to run.
 // ------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(MED_CHUNK) void median_depth_fwd_kernel(int W, int H, int grid_x,
+__global__ __launch_bounds__(MAP_CHUNK) void median_depth_fwd_kernel(int W, int H, int grid_x,
                                                                      const uint32_t* __restrict__ tile_order,
                                                                      const uint2* __restrict__ ranges,
                                                                      const uint32_t* __restrict__ point_list,
@@ -56,57 +46,42 @@ __global__ __launch_bounds__(MED_CHUNK) void median_depth_fwd_kernel(int W, int 
                                                                      float* __restrict__ median,
                                                                      int32_t* __restrict__ median_id,
                                                                      uint32_t* __restrict__ state) {
-  __shared__ float4 sA[MED_CHUNK];
-  __shared__ float4 sB[MED_CHUNK];
-  __shared__ float sZ[MED_CHUNK];
-  __shared__ uint32_t sId[MED_CHUNK];
+  __shared__ float4 sA[MAP_CHUNK];
+  __shared__ float4 sB[MAP_CHUNK];
+  __shared__ float sZ[MAP_CHUNK];
+  __shared__ uint32_t sId[MAP_CHUNK];
   __shared__ uint32_t sMax[4];
   __shared__ uint32_t sLive[4];
   const int tid = threadIdx.x;
-  const int tile = __builtin_amdgcn_readfirstlane((int)tile_order[blockIdx.x]);
-  const int tile_x = tile % grid_x, tile_y = tile / grid_x;
-  const int px = tile_x * TILE + (tid & (TILE - 1)), py = tile_y * TILE + tid / TILE;
-  const bool inside = px < W && py < H;
-  const size_t pix = (size_t)py * W + px;
-  const float pxf = (float)px, pyf = (float)py;
-  const uint2 range = ranges[tile];
-  const uint32_t start = range.x, len = range.y - range.x;
-  const uint32_t last = inside ? min(n_contrib[pix], len) : 0u;
-  const uint32_t tmax = med_block_max_u32(last, sMax);
+  const MapPixel m = map_pixel(W, H, grid_x, tile_order, ranges);
+  const float pxf = (float)m.px, pyf = (float)m.py;
+  const uint32_t last = map_last(m, n_contrib, m.inside);
+  const uint32_t tmax = block_max_u32(last, sMax);
 
   float T = 1.0f, med = 0.0f;
   int32_t mid = -1;
   uint32_t pos = MED_NONE;
   bool live = last > 0u;      // not done: T > 0.5 and entries of its own left
-  for (uint32_t base = 0;; base += MED_CHUNK) {
+  for (uint32_t base = 0;; base += MAP_CHUNK) {
     const bool wave_live = __builtin_amdgcn_ballot_w64(live) != 0ull;
     if ((tid & (WAVE - 1)) == 0) sLive[tid / WAVE] = wave_live ? 1u : 0u;
     __syncthreads();      // the flags are in; every lane has left the previous round's entries
     if ((sLive[0] | sLive[1] | sLive[2] | sLive[3]) == 0u) break;      // the same four words in every lane
     // a live lane has last > base, so tmax > base
-    const uint32_t n = min((uint32_t)MED_CHUNK, tmax - base);
+    const uint32_t n = min((uint32_t)MAP_CHUNK, tmax - base);
     if ((uint32_t)tid < n) {
-      const uint32_t id = point_list[start + base + tid];
-      const GeomRec* r = rec + id;
-      Staged st;
-      st.q0 = make_float4(r->x, r->y, r->cxx, 0.0f);
-      st.q1 = make_float4(0.0f, r->opacity, 0.0f, 0.0f);
-      st.q2 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      st.kk = r->kk;
-      st.isyy = r->isyy;
-      LdsRec lr;
-      make_lds(st, lr);
-      sA[tid] = lr.A;
-      sB[tid] = lr.B;
-      sZ[tid] = bin[id].depth;
-      sId[tid] = id;
+      const MapEntry e = load_entry(rec, point_list[m.start + base + tid]);
+      sA[tid] = e.lr.A;
+      sB[tid] = e.lr.B;
+      sZ[tid] = bin[e.id].depth;
+      sId[tid] = e.id;
     }
     __syncthreads();      // the round is staged; the flags have been read
     if (live) {
       const uint32_t mine = min(n, last - base);
       for (uint32_t k = 0; k < mine; ++k) {
         const float4 a = sA[k], b = sB[k];
-        const float alpha = clamp_alpha(__builtin_amdgcn_exp2f(pair_p2(a.x - pxf, a.y - pyf, a.z, a.w, b.x, b.y)), b.x);
+        const float alpha = map_alpha(a, b, pxf, pyf);
         if (alpha >= ALPHA_MIN) {
           // T > 0.5 here: the walk leaves at the first update that takes it to one half
           med = sZ[k];
@@ -119,10 +94,10 @@ __global__ __launch_bounds__(MED_CHUNK) void median_depth_fwd_kernel(int W, int 
       live = T > 0.5f && last - base > n;
     }
   }
-  if (inside) {
-    median[pix] = med;
-    median_id[pix] = mid;
-    state[pix] = pos;
+  if (m.inside) {
+    median[m.pix] = med;
+    median_id[m.pix] = mid;
+    state[m.pix] = pos;
   }
 }
 
@@ -132,34 +107,29 @@ __global__ __launch_bounds__(MED_CHUNK) void median_depth_fwd_kernel(int W, int 
 // non-zero slot: at most one per tile and entry, however many of the tile's pixels chose it.  acc [P] is zeroed by the
 // caller.  Rounds in front of the tile's first chosen position and behind its last are not visited.
 // ------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(MED_CHUNK) void median_depth_bwd_kernel(int W, int H, int grid_x,
+__global__ __launch_bounds__(MAP_CHUNK) void median_depth_bwd_kernel(int W, int H, int grid_x,
                                                                      const uint32_t* __restrict__ tile_order,
                                                                      const uint2* __restrict__ ranges,
                                                                      const uint32_t* __restrict__ point_list,
                                                                      const uint32_t* __restrict__ state,
                                                                      const float* __restrict__ dL_dmedian,
                                                                      float* __restrict__ acc) {
-  __shared__ float sSum[MED_CHUNK];
+  __shared__ float sSum[MAP_CHUNK];
   __shared__ uint32_t sMax[4];
   __shared__ uint32_t sMin[4];
   const int tid = threadIdx.x;
-  const int tile = __builtin_amdgcn_readfirstlane((int)tile_order[blockIdx.x]);
-  const int tile_x = tile % grid_x, tile_y = tile / grid_x;
-  const int px = tile_x * TILE + (tid & (TILE - 1)), py = tile_y * TILE + tid / TILE;
-  const bool inside = px < W && py < H;
-  const size_t pix = (size_t)py * W + px;
-  const uint2 range = ranges[tile];
-  const uint32_t start = range.x, len = range.y - range.x;
-  uint32_t pos = inside ? state[pix] : MED_NONE;
-  if (pos >= len) pos = MED_NONE;      // a state of this frame never is; no index leaves the tile's list whatever it holds
-  const float g = pos != MED_NONE ? dL_dmedian[pix] : 0.0f;
-  const uint32_t end = med_block_max_u32(pos != MED_NONE ? pos + 1u : 0u, sMax);                 // one past the last chosen
-  const uint32_t first = MED_NONE - med_block_max_u32(pos != MED_NONE ? MED_NONE - pos : 0u, sMin);  // the first chosen
+  const MapPixel m = map_pixel(W, H, grid_x, tile_order, ranges);
+  const uint32_t start = m.start;
+  uint32_t pos = m.inside ? state[m.pix] : MED_NONE;
+  if (pos >= m.len) pos = MED_NONE;      // a state of this frame never is; no index leaves the tile's list whatever it holds
+  const float g = pos != MED_NONE ? dL_dmedian[m.pix] : 0.0f;
+  const uint32_t end = block_max_u32(pos != MED_NONE ? pos + 1u : 0u, sMax);                 // one past the last chosen
+  const uint32_t first = MED_NONE - block_max_u32(pos != MED_NONE ? MED_NONE - pos : 0u, sMin);  // the first chosen
 
-  for (uint32_t base = end > 0u ? first - first % MED_CHUNK : 0u; base < end; base += MED_CHUNK) {
+  for (uint32_t base = end > 0u ? first - first % MAP_CHUNK : 0u; base < end; base += MAP_CHUNK) {
     sSum[tid] = 0.0f;
     __syncthreads();
-    if (pos != MED_NONE && pos - base < (uint32_t)MED_CHUNK) atomicAdd(&sSum[pos - base], g);      // pos >= base: unsigned wrap
+    if (pos != MED_NONE && pos - base < (uint32_t)MAP_CHUNK) atomicAdd(&sSum[pos - base], g);      // pos >= base: unsigned wrap
     __syncthreads();
     // the lane reads the slot it zeroes in the next round: no barrier between the two
     if ((uint32_t)tid < end - base) {
@@ -190,19 +160,14 @@ __global__ __launch_bounds__(PRE_BLOCK) void median_depth_finish_kernel(int P, c
   d_means3D[3 * (size_t)idx + 2] = d2;
 }
 
-void launch_median_depth_fwd(int W, int H, const uint2* ranges, const uint32_t* point_list, const GeomRec* rec,
-                             const BinInfo* bin, const uint32_t* n_contrib, const uint32_t* tile_order, float* median,
-                             int32_t* median_id, uint32_t* state, hipStream_t s) {
-  const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
-  hipLaunchKernelGGL(median_depth_fwd_kernel, dim3(gx * gy), dim3(MED_CHUNK), 0, s, W, H, gx, tile_order, ranges, point_list,
-                     rec, bin, n_contrib, median, median_id, state);
+void launch_median_depth_fwd(const MapFrame& f, float* median, int32_t* median_id, uint32_t* state, hipStream_t s) {
+  hipLaunchKernelGGL(median_depth_fwd_kernel, dim3(f.tiles), dim3(MAP_CHUNK), 0, s, f.W, f.H, f.grid_x, f.tile_order,
+                     f.ranges, f.point_list, f.rec, f.bin, f.n_contrib, median, median_id, state);
 }
 
-void launch_median_depth_bwd(int W, int H, const uint2* ranges, const uint32_t* point_list, const uint32_t* tile_order,
-                             const uint32_t* state, const float* dL_dmedian, float* acc, hipStream_t s) {
-  const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
-  hipLaunchKernelGGL(median_depth_bwd_kernel, dim3(gx * gy), dim3(MED_CHUNK), 0, s, W, H, gx, tile_order, ranges, point_list,
-                     state, dL_dmedian, acc);
+void launch_median_depth_bwd(const MapFrame& f, const uint32_t* state, const float* dL_dmedian, float* acc, hipStream_t s) {
+  hipLaunchKernelGGL(median_depth_bwd_kernel, dim3(f.tiles), dim3(MAP_CHUNK), 0, s, f.W, f.H, f.grid_x, f.tile_order,
+                     f.ranges, f.point_list, state, dL_dmedian, acc);
 }
 
 void launch_median_depth_finish(int P, const float* viewmatrix, const float* acc, float* d_means3D, hipStream_t s) {

@@ -101,12 +101,6 @@ __global__ __launch_bounds__(EV_THREADS) void eval_image_kernel(const float* __r
   }
 }
 
-__device__ inline double wave_reduce_add_f64(double v) {
-#pragma unroll
-  for (int d = WAVE / 2; d > 0; d >>= 1) v += __shfl_xor(v, d, WAVE);
-  return v;
-}
-
 // utils/image_utils.py:17-19 (mse == 0 gives +inf there too)
 __device__ inline double psnr_of(double mse) { return 20.0 * log10(1.0 / sqrt(mse)); }
 

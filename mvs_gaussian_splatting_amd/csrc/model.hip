@@ -71,12 +71,6 @@ __global__ __launch_bounds__(OS_THREADS) void opacity_sparsity_kernel(const floa
   }
 }
 
-__device__ __forceinline__ double wave_reduce_add_f64(double v) {
-#pragma unroll
-  for (int d = WAVE / 2; d > 0; d >>= 1) v += __shfl_xor(v, d, WAVE);
-  return v;
-}
-
 // One block.  Lane t adds pairs t, t + 256, ... in order, then a fixed butterfly and a fixed walk over the waves.
 // record = {float loss, uint32 n, float weight / n, 0}; n == 0 gives loss = factor = 0 (train.py:104 skips the term).
 __global__ __launch_bounds__(OS_FIN_THREADS) void opacity_sparsity_finish_kernel(const float* __restrict__ part_sum,

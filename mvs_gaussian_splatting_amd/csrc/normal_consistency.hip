@@ -47,12 +47,6 @@ struct NcStencil {
   float gtx[3], gty[3];
 };
 
-__device__ inline double nc_wave_reduce_add_f64(double v) {
-#pragma unroll
-  for (int d = WAVE / 2; d > 0; d >>= 1) v += __shfl_xor(v, d, WAVE);
-  return v;
-}
-
 // The stencil centred on image pixel (x, y) = LDS position (lx, ly) of the staged depth, 1 <= lx, ly <= NC_D - 2.
 template <bool GRAD>
 __device__ inline void nc_stencil(const float (&sd)[NC_D][NC_D + 1], const uint8_t (&sc)[NC_D][NC_D], int lx, int ly,
@@ -142,7 +136,7 @@ __global__ __launch_bounds__(NC_T* NC_T) void normal_consistency_kernel(
 
   // the workgroup's loss partial and count: fixed butterfly, then the waves in order
   const int lane = tid & (WAVE - 1), wid = tid / WAVE;
-  const double ws = nc_wave_reduce_add_f64(e);
+  const double ws = wave_reduce_add_f64(e);
   const uint32_t wn = wave_reduce_add_u32(own.valid ? 1u : 0u);
   if (lane == 0) { red_s[wid] = ws; red_n[wid] = wn; }
 
@@ -215,7 +209,7 @@ __global__ __launch_bounds__(NC_FIN_THREADS) void normal_consistency_finish_kern
     n += part_n[i];
   }
   const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-  s = nc_wave_reduce_add_f64(s);
+  s = wave_reduce_add_f64(s);
   n = wave_reduce_add_u32(n);
   if (lane == 0) { red_s[wid] = s; red_n[wid] = n; }
   __syncthreads();

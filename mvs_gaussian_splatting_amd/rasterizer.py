@@ -493,6 +493,61 @@ def _aux_frame(frame: _Frame, P: int, W: int, H: int, binning_mode: int) -> "_li
     return f
 
 
+def _geometry_inputs(dev, means3D, opacities, scales, rotations, cov3Ds_precomp):
+    """The geometry inputs of a map node as contiguous float32 tensors on ``dev`` (rotations 16-byte aligned)."""
+    return (_f32c(means3D, "means3D", dev), _f32c(opacities, "opacities", dev), _f32c(scales, "scales", dev),
+            _f32c(rotations, "rotations", dev, align16=True), _f32c(cov3Ds_precomp, "cov3D_precomp", dev))
+
+
+def _stash_frame(ctx, raster_settings, frame: _Frame, binning_mode: int, tensors, act_flags: int = 0, has_means2D=False):
+    """What a map node keeps for its backward: the settings, the frame's layout and counts, and ``tensors`` followed by
+    the frame's four workspaces -- ``_frame_of`` takes those from the end of what was saved."""
+    ctx.raster_settings = raster_settings
+    ctx.layout = (frame.layout_R, frame.layout_V)
+    ctx.frame_pending = frame.pending
+    ctx.counts = frame.counts
+    ctx.binning_mode = binning_mode
+    ctx.act_flags = int(act_flags)
+    ctx.has_means2D = has_means2D
+    ctx.save_for_backward(*tensors, frame.radii, frame.geom, frame.binning, frame.img)
+
+
+def _open_backward(ctx, saved, means3D, *geometry):
+    """The start of a map node's backward: -> (dev, P, params, keep, aux_frame).  ``geometry``: the saved opacities,
+    scales, rotations and cov3D_precomp (none for a node that reads means3D alone).  ``keep`` holds what ``params``
+    points at; the caller drops it after its library call."""
+    frame, binning_mode = _frame_of(ctx, saved)
+    settings = ctx.raster_settings
+    dev = means3D.device
+    P = int(means3D.shape[0])
+    H, W = int(settings.image_height), int(settings.image_width)
+    if frame.pending is not None:
+        _verify(frame.pending, block=True)      # deferred mode: as the colour backward
+    empty = torch.empty(0, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        params, keep = _make_params(dev, settings, means3D, empty, empty, *(geometry or (empty,) * 4),
+                                    act_flags=ctx.act_flags)
+    params.profile = None
+    params.binning_mode = binning_mode
+    return dev, P, params, keep, _aux_frame(frame, P, W, H, binning_mode)
+
+
+def _geometry_grads(dev, P, nbytes_of, opacities, scales, rotations, cov3Ds_precomp):
+    """The outputs of a map's geometry backward: -> (the six gradient tensors for means3D, means2D, opacities, scales,
+    rotations, cov3D_precomp (None where the input is absent), ``GsrAuxGrads`` over them, the accumulator workspace of
+    ``nbytes_of(P)`` bytes, that size)."""
+    new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
+    g = (new(P, 3), new(P, 3), new(*opacities.shape)) + tuple(
+        new(P, n) if t.numel() else None for t, n in ((scales, 3), (rotations, 4), (cov3Ds_precomp, 6)))
+    nbytes = nbytes_of(P)
+    return g, _lib.GsrAuxGrads(*(_ptr(t) for t in g)), torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
+
+
+def _geometry_result(ctx, g, *rest):
+    """``backward``'s return tuple: the six geometry gradients (means2D's only if the input was given), then ``rest``."""
+    return (g[0], g[1] if ctx.has_means2D else None) + tuple(g[2:]) + rest
+
+
 class _AuxMaps(torch.autograd.Function):
     """Depth, inverse-depth and accumulated-opacity maps ``[3,H,W]`` of a frame the colour operator has rendered
     (``include/gsr.h``: gsr_aux_maps_*; ``csrc/depth.hip``).  A node of its own next to the colour node: it reads the
@@ -506,25 +561,13 @@ class _AuxMaps(torch.autograd.Function):
         lib = _lib.load()
         dev = _require_gpu(means3D)
         P = int(means3D.shape[0])
-        means3D = _f32c(means3D, "means3D", dev)
-        opacities = _f32c(opacities, "opacities", dev)
-        scales = _f32c(scales, "scales", dev)
-        rotations = _f32c(rotations, "rotations", dev, align16=True)
-        cov3Ds_precomp = _f32c(cov3Ds_precomp, "cov3D_precomp", dev)
+        geometry = _geometry_inputs(dev, means3D, opacities, scales, rotations, cov3Ds_precomp)
         H, W = int(raster_settings.image_height), int(raster_settings.image_width)
         maps = torch.empty(3, H, W, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             _lib.check(lib.gsr_aux_maps_forward(C.byref(_aux_frame(frame, P, W, H, binning_mode)), maps.data_ptr(),
                                                 _stream(dev)), "gsr_aux_maps_forward")
-        ctx.raster_settings = raster_settings
-        ctx.layout = (frame.layout_R, frame.layout_V)
-        ctx.frame_pending = frame.pending
-        ctx.counts = frame.counts
-        ctx.binning_mode = binning_mode
-        ctx.act_flags = int(act_flags)
-        ctx.has_means2D = means2D is not None
-        ctx.save_for_backward(means3D, opacities, scales, rotations, cov3Ds_precomp, frame.radii, frame.geom,
-                              frame.binning, frame.img)
+        _stash_frame(ctx, raster_settings, frame, binning_mode, geometry, act_flags, means2D is not None)
         return maps
 
     @staticmethod
@@ -533,34 +576,14 @@ class _AuxMaps(torch.autograd.Function):
             return (None,) * 10
         lib = _lib.load()
         saved = ctx.saved_tensors
-        means3D, opacities, scales, rotations, cov3Ds_precomp = saved[:5]
-        frame, binning_mode = _frame_of(ctx, saved)
-        settings = ctx.raster_settings
-        dev = means3D.device
-        P = int(means3D.shape[0])
-        H, W = int(settings.image_height), int(settings.image_width)
-        if frame.pending is not None:
-            _verify(frame.pending, block=True)      # deferred mode: as the colour backward
+        dev, P, params, keep, aux_frame = _open_backward(ctx, saved, *saved[:5])
         grad_maps = _f32c(grad_maps, "grad_maps", dev)
-        empty = torch.empty(0, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            params, keep = _make_params(dev, settings, means3D, empty, empty, opacities, scales, rotations,
-                                        cov3Ds_precomp, act_flags=ctx.act_flags)
-            params.profile = None
-            params.binning_mode = binning_mode
-            new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
-            g_means3D, g_means2D, g_opac = new(P, 3), new(P, 3), new(*opacities.shape)
-            g_scales, g_rot, g_cov = (new(P, n) if t.numel() else None
-                                      for t, n in ((scales, 3), (rotations, 4), (cov3Ds_precomp, 6)))
-            grads = _lib.GsrAuxGrads(_ptr(g_means3D), _ptr(g_means2D), _ptr(g_opac), _ptr(g_scales), _ptr(g_rot),
-                                     _ptr(g_cov))
-            nbytes = lib.gsr_aux_maps_backward_bytes(P)
-            acc = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            _lib.check(lib.gsr_aux_maps_backward(C.byref(params), C.byref(_aux_frame(frame, P, W, H, binning_mode)),
-                                                 grad_maps.data_ptr(), acc.data_ptr(), nbytes, C.byref(grads),
-                                                 _stream(dev)), "gsr_aux_maps_backward")
+            g, grads, acc, nbytes = _geometry_grads(dev, P, lib.gsr_aux_maps_backward_bytes, *saved[1:5])
+            _lib.check(lib.gsr_aux_maps_backward(C.byref(params), C.byref(aux_frame), grad_maps.data_ptr(), acc.data_ptr(),
+                                                 nbytes, C.byref(grads), _stream(dev)), "gsr_aux_maps_backward")
         del keep
-        return (g_means3D, g_means2D if ctx.has_means2D else None, g_opac, g_scales, g_rot, g_cov, None, None, None, None)
+        return _geometry_result(ctx, g, None, None, None, None)
 
 
 def _aux_maps_of(node, grad: bool, means3D, means2D, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
@@ -585,11 +608,7 @@ class _FeatureMaps(torch.autograd.Function):
         lib = _lib.load()
         dev = _require_gpu(means3D)
         P = int(means3D.shape[0])
-        means3D = _f32c(means3D, "means3D", dev)
-        opacities = _f32c(opacities, "opacities", dev)
-        scales = _f32c(scales, "scales", dev)
-        rotations = _f32c(rotations, "rotations", dev, align16=True)
-        cov3Ds_precomp = _f32c(cov3Ds_precomp, "cov3D_precomp", dev)
+        geometry = _geometry_inputs(dev, means3D, opacities, scales, rotations, cov3Ds_precomp)
         features = _f32c(features, "features", dev)
         n_ch = int(features.shape[1])
         H, W = int(raster_settings.image_height), int(raster_settings.image_width)
@@ -601,15 +620,7 @@ class _FeatureMaps(torch.autograd.Function):
                 _lib.check(lib.gsr_feature_maps_forward(C.byref(_aux_frame(frame, P, W, H, binning_mode)),
                                                         features.data_ptr(), n_ch, maps.data_ptr(), _stream(dev)),
                            "gsr_feature_maps_forward")
-        ctx.raster_settings = raster_settings
-        ctx.layout = (frame.layout_R, frame.layout_V)
-        ctx.frame_pending = frame.pending
-        ctx.counts = frame.counts
-        ctx.binning_mode = binning_mode
-        ctx.act_flags = int(act_flags)
-        ctx.has_means2D = means2D is not None
-        ctx.save_for_backward(means3D, opacities, scales, rotations, cov3Ds_precomp, features, frame.radii, frame.geom,
-                              frame.binning, frame.img)
+        _stash_frame(ctx, raster_settings, frame, binning_mode, geometry + (features,), act_flags, means2D is not None)
         return maps
 
     @staticmethod
@@ -622,42 +633,23 @@ class _FeatureMaps(torch.autograd.Function):
             return (None,) * 11
         lib = _lib.load()
         saved = ctx.saved_tensors
-        means3D, opacities, scales, rotations, cov3Ds_precomp, features = saved[:6]
-        frame, binning_mode = _frame_of(ctx, saved)
-        settings = ctx.raster_settings
-        dev = means3D.device
-        P, n_ch = int(means3D.shape[0]), int(features.shape[1])
-        H, W = int(settings.image_height), int(settings.image_width)
-        if frame.pending is not None:
-            _verify(frame.pending, block=True)      # deferred mode: as the colour backward
+        features = saved[5]
+        dev, P, params, keep, aux_frame = _open_backward(ctx, saved, *saved[:5])
+        n_ch = int(features.shape[1])
         grad_maps = _f32c(grad_maps, "grad_maps", dev)
-        empty = torch.empty(0, dtype=torch.float32, device=dev)
-        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
-        g_means3D = g_means2D = g_opac = g_scales = g_rot = g_cov = g_feat = acc = grads = None
-        nbytes = 0
+        g, grads, acc, nbytes, g_feat = (None,) * 6, None, None, 0, None
         with torch.cuda.device(dev):
-            params, keep = _make_params(dev, settings, means3D, empty, empty, opacities, scales, rotations,
-                                        cov3Ds_precomp, act_flags=ctx.act_flags)
-            params.profile = None
-            params.binning_mode = binning_mode
             if want_geom:
-                g_means3D, g_means2D, g_opac = new(P, 3), new(P, 3), new(*opacities.shape)
-                g_scales, g_rot, g_cov = (new(P, n) if t.numel() else None
-                                          for t, n in ((scales, 3), (rotations, 4), (cov3Ds_precomp, 6)))
-                grads = _lib.GsrAuxGrads(_ptr(g_means3D), _ptr(g_means2D), _ptr(g_opac), _ptr(g_scales), _ptr(g_rot),
-                                         _ptr(g_cov))
-                nbytes = lib.gsr_feature_maps_backward_bytes(P)
-                acc = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+                g, grads, acc, nbytes = _geometry_grads(dev, P, lib.gsr_feature_maps_backward_bytes, *saved[1:5])
             if want_feat:
-                g_feat = new(P, n_ch)
+                g_feat = torch.empty(P, n_ch, dtype=torch.float32, device=dev)
             if P > 0:
                 _lib.check(lib.gsr_feature_maps_backward(
-                    C.byref(params), C.byref(_aux_frame(frame, P, W, H, binning_mode)), features.data_ptr(), n_ch,
-                    grad_maps.data_ptr(), _ptr(g_feat), _ptr(acc), nbytes, None if grads is None else C.byref(grads),
-                    _stream(dev)), "gsr_feature_maps_backward")
+                    C.byref(params), C.byref(aux_frame), features.data_ptr(), n_ch, grad_maps.data_ptr(), _ptr(g_feat),
+                    _ptr(acc), nbytes, None if grads is None else C.byref(grads), _stream(dev)),
+                    "gsr_feature_maps_backward")
         del keep
-        return (g_means3D, g_means2D if ctx.has_means2D else None, g_opac, g_scales, g_rot, g_cov, g_feat, None, None,
-                None, None)
+        return _geometry_result(ctx, g, g_feat, None, None, None, None)
 
 
 def _feature_maps_of(node, grad: bool, features, means3D, means2D, opacities, scales, rotations, cov3Ds_precomp,
@@ -708,11 +700,7 @@ class _DistortionMap(torch.autograd.Function):
         lib = _lib.load()
         dev = _require_gpu(means3D)
         P = int(means3D.shape[0])
-        means3D = _f32c(means3D, "means3D", dev)
-        opacities = _f32c(opacities, "opacities", dev)
-        scales = _f32c(scales, "scales", dev)
-        rotations = _f32c(rotations, "rotations", dev, align16=True)
-        cov3Ds_precomp = _f32c(cov3Ds_precomp, "cov3D_precomp", dev)
+        geometry = _geometry_inputs(dev, means3D, opacities, scales, rotations, cov3Ds_precomp)
         H, W = int(raster_settings.image_height), int(raster_settings.image_width)
         mapping, near, far = spec
         dist = torch.empty(1, H, W, dtype=torch.float32, device=dev)
@@ -721,16 +709,8 @@ class _DistortionMap(torch.autograd.Function):
             _lib.check(lib.gsr_distortion_forward(C.byref(_aux_frame(frame, P, W, H, binning_mode)), mapping, near, far,
                                                   dist.data_ptr(), state.data_ptr(), _stream(dev)),
                        "gsr_distortion_forward")
-        ctx.raster_settings = raster_settings
-        ctx.layout = (frame.layout_R, frame.layout_V)
-        ctx.frame_pending = frame.pending
-        ctx.counts = frame.counts
-        ctx.binning_mode = binning_mode
-        ctx.act_flags = int(act_flags)
         ctx.spec = (int(mapping), float(near), float(far))
-        ctx.has_means2D = means2D is not None
-        ctx.save_for_backward(means3D, opacities, scales, rotations, cov3Ds_precomp, state, frame.radii, frame.geom,
-                              frame.binning, frame.img)
+        _stash_frame(ctx, raster_settings, frame, binning_mode, geometry + (state,), act_flags, means2D is not None)
         return dist
 
     @staticmethod
@@ -739,37 +719,17 @@ class _DistortionMap(torch.autograd.Function):
             return (None,) * 11
         lib = _lib.load()
         saved = ctx.saved_tensors
-        means3D, opacities, scales, rotations, cov3Ds_precomp, state = saved[:6]
-        frame, binning_mode = _frame_of(ctx, saved)
-        settings = ctx.raster_settings
-        dev = means3D.device
-        P = int(means3D.shape[0])
-        H, W = int(settings.image_height), int(settings.image_width)
-        if frame.pending is not None:
-            _verify(frame.pending, block=True)      # deferred mode: as the colour backward
+        state = saved[5]
+        dev, P, params, keep, aux_frame = _open_backward(ctx, saved, *saved[:5])
         grad_dist = _f32c(grad_dist, "grad_dist", dev)
-        empty = torch.empty(0, dtype=torch.float32, device=dev)
         mapping, near, far = ctx.spec
         with torch.cuda.device(dev):
-            params, keep = _make_params(dev, settings, means3D, empty, empty, opacities, scales, rotations,
-                                        cov3Ds_precomp, act_flags=ctx.act_flags)
-            params.profile = None
-            params.binning_mode = binning_mode
-            new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
-            g_means3D, g_means2D, g_opac = new(P, 3), new(P, 3), new(*opacities.shape)
-            g_scales, g_rot, g_cov = (new(P, n) if t.numel() else None
-                                      for t, n in ((scales, 3), (rotations, 4), (cov3Ds_precomp, 6)))
-            grads = _lib.GsrAuxGrads(_ptr(g_means3D), _ptr(g_means2D), _ptr(g_opac), _ptr(g_scales), _ptr(g_rot),
-                                     _ptr(g_cov))
-            nbytes = lib.gsr_distortion_backward_bytes(P)
-            acc = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            _lib.check(lib.gsr_distortion_backward(C.byref(params), C.byref(_aux_frame(frame, P, W, H, binning_mode)),
-                                                   mapping, near, far, state.data_ptr(), grad_dist.data_ptr(),
-                                                   acc.data_ptr(), nbytes, C.byref(grads), _stream(dev)),
-                       "gsr_distortion_backward")
+            g, grads, acc, nbytes = _geometry_grads(dev, P, lib.gsr_distortion_backward_bytes, *saved[1:5])
+            _lib.check(lib.gsr_distortion_backward(C.byref(params), C.byref(aux_frame), mapping, near, far,
+                                                   state.data_ptr(), grad_dist.data_ptr(), acc.data_ptr(), nbytes,
+                                                   C.byref(grads), _stream(dev)), "gsr_distortion_backward")
         del keep
-        return (g_means3D, g_means2D if ctx.has_means2D else None, g_opac, g_scales, g_rot, g_cov, None, None, None, None,
-                None)
+        return _geometry_result(ctx, g, None, None, None, None, None)
 
 
 def _distortion_of(node, grad: bool, spec, means3D, means2D, opacities, scales, rotations, cov3Ds_precomp,
@@ -819,12 +779,7 @@ class _MedianDepth(torch.autograd.Function):
             _lib.check(lib.gsr_median_depth_forward(C.byref(_aux_frame(frame, P, W, H, binning_mode)), median.data_ptr(),
                                                     median_id.data_ptr(), state.data_ptr(), _stream(dev)),
                        "gsr_median_depth_forward")
-        ctx.raster_settings = raster_settings
-        ctx.layout = (frame.layout_R, frame.layout_V)
-        ctx.frame_pending = frame.pending
-        ctx.counts = frame.counts
-        ctx.binning_mode = binning_mode
-        ctx.save_for_backward(means3D, state, frame.radii, frame.geom, frame.binning, frame.img)
+        _stash_frame(ctx, raster_settings, frame, binning_mode, (means3D, state))
         ctx.mark_non_differentiable(median_id)
         ctx.set_materialize_grads(False)
         return median, median_id
@@ -835,26 +790,16 @@ class _MedianDepth(torch.autograd.Function):
             return (None,) * 4
         lib = _lib.load()
         saved = ctx.saved_tensors
-        means3D, state = saved[:2]
-        frame, binning_mode = _frame_of(ctx, saved)
-        settings = ctx.raster_settings
-        dev = means3D.device
-        P = int(means3D.shape[0])
-        H, W = int(settings.image_height), int(settings.image_width)
-        if frame.pending is not None:
-            _verify(frame.pending, block=True)      # deferred mode: as the colour backward
+        state = saved[1]
+        dev, P, params, keep, aux_frame = _open_backward(ctx, saved, saved[0])
         grad_median = _f32c(grad_median, "grad_median", dev)
-        empty = torch.empty(0, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            params, keep = _make_params(dev, settings, means3D, empty, empty, empty, empty, empty, empty)
-            params.profile = None
-            params.binning_mode = binning_mode
             g_means3D = torch.empty(P, 3, dtype=torch.float32, device=dev)
             nbytes = lib.gsr_median_depth_backward_bytes(P)
             acc = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            _lib.check(lib.gsr_median_depth_backward(C.byref(params), C.byref(_aux_frame(frame, P, W, H, binning_mode)),
-                                                     state.data_ptr(), grad_median.data_ptr(), acc.data_ptr(), nbytes,
-                                                     _ptr(g_means3D), _stream(dev)), "gsr_median_depth_backward")
+            _lib.check(lib.gsr_median_depth_backward(C.byref(params), C.byref(aux_frame), state.data_ptr(),
+                                                     grad_median.data_ptr(), acc.data_ptr(), nbytes, _ptr(g_means3D),
+                                                     _stream(dev)), "gsr_median_depth_backward")
         del keep
         return (g_means3D, None, None, None)
 

@@ -84,3 +84,44 @@ def map_weights(H, W, seed=4711):
 
 def maps_loss(maps, weights):
     return (maps * weights.to(maps.dtype).to(maps.device)).sum() / weights.numel()
+
+
+# ---- the scene that takes every map's round loop past two full rounds ---------------------------------------------------
+STACKED = dict(P=720, sh_degree=3, width=40, height=24, focal=30.0, scale=0.25, seed=5)
+ROUND = 256      # list entries a map kernel stages per round
+
+
+def stacked_scene():
+    """720 faint Gaussians on the ray through the middle of tile (0, 0) of a 40 x 24 image (neither a multiple of 16).
+    Every eighteenth is wide (40 pixels of standard deviation, opacity 0.04: composited on every pixel of the image, well
+    above the alpha threshold); the others are narrow (1.5 pixels, opacity 0.006, scattered over the tile) and pass the
+    alpha test on a few pixels each, so a pixel's list positions run far ahead of its composited entries.  T stays near
+    0.2 at the end of the list: n_contrib is the whole list, and T falls through one half after some 17 wide entries,
+    past list position 256, in steps of 0.02 (few pixels come within the fragility bound of one half)."""
+    from conftest import small_scene
+    model, cam, bg, _ = small_scene(**STACKED)
+    P, f = STACKED["P"], STACKED["focal"]
+    g = torch.Generator().manual_seed(11)
+    z = 3.0 + 6.0 * torch.rand(P, generator=g)
+    wide = torch.arange(P) % 18 == 0
+    centre = torch.tensor([(8.0 - 0.5 * STACKED["width"]) / f, (8.0 - 0.5 * STACKED["height"]) / f])
+    jitter = (torch.rand(P, 2, generator=g) * 2 - 1) * torch.where(wide, 2.0, 8.0)[:, None] / f
+    xy = centre + jitter
+    model._xyz = torch.stack([xy[:, 0] * z, xy[:, 1] * z, z], dim=1).contiguous()
+    sigma = torch.where(wide, 40.0, 1.5) / f
+    # mildly anisotropic (a sphere has no rotation gradient to compare); one Gaussian behind the camera is culled
+    model._scaling = (torch.log(z * sigma)[:, None] + 0.25 * (torch.rand(P, 3, generator=g) * 2 - 1)).contiguous()
+    model._xyz[1, 2] = -4.0
+    model._opacity = torch.logit(torch.where(wide, 0.04, 0.006))[:, None].contiguous()
+    return model, cam, bg
+
+
+def assert_rounds_covered(aux, pos=None):
+    """(a) a partial last tile row and column, (b) a pixel whose composited prefix needs a full, a full and a partial
+    round, (c) with ``pos`` (the median's list positions): a pixel whose chosen entry lies past the first round."""
+    H, W = aux["n_contrib"].shape
+    assert H % TILE != 0 and W % TILE != 0, "the image must end in partial tiles on both axes"
+    n = int(aux["n_contrib"].max())
+    assert n > 2 * ROUND and n % ROUND != 0, f"the longest prefix ({n}) must take two full rounds and a partial one"
+    if pos is not None:
+        assert int(pos.max()) >= ROUND, f"no pixel's median entry lies past the first round (largest position {int(pos.max())})"

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from conftest import make_settings, small_scene
-from depth_restate import ALPHA_MAX, ALPHA_MIN, TILE
+from depth_restate import ALPHA_MAX, ALPHA_MIN, TILE, stacked_scene
 from grad_util import MARGIN, oracle_operator_inputs
 from oracle import rasterize_ref
 
@@ -112,6 +112,8 @@ def median_loss(median, weights):
 def scene(name):
     """small / big: the scenes of tests/test_gpu_depth.py; behind: its variant of small with Gaussians behind the camera and
     inside the near plane; faint: big with every raw opacity lowered by 4, so that rays stay above one half for long."""
+    if name == "stacked":      # depth_restate.stacked_scene: the median entry lies past the first 256-entry round
+        return stacked_scene()
     model, cam, bg, _ = small_scene(**SCENES["big" if name in ("big", "faint") else "small"])
     if name == "behind":
         model._xyz[3, 2] = -4.0          # behind the camera

@@ -22,6 +22,7 @@ import pytest
 import torch
 
 from conftest import ROOT, make_settings
+from depth_restate import assert_rounds_covered
 from contribution_restate import members_near, stats_from_lists
 from gpu_util import product_settings
 from grad_util import MARGIN, TOL, linear_weights, oracle_operator_inputs, weighted_sum
@@ -93,9 +94,11 @@ def _compare(stats, ref, label, rows=None):
           + "; ".join(report))
 
 
-@pytest.mark.parametrize("name", ["small", "big", "behind"])
+@pytest.mark.parametrize("name", ["small", "big", "behind", "stacked"])
 def test_statistics_match_the_float64_restatement_on_the_robust_pixels(gpu_device, name):
     ref = _reference(name)
+    if name == "stacked":
+        assert_rounds_covered(ref["aux"])
     if name == "big":
         aux = ref["aux"]
         assert int((aux["ranges"][:, 1] - aux["ranges"][:, 0]).max()) > 256, "a list must exceed one 256-entry round"

@@ -20,7 +20,7 @@ import pytest
 import torch
 
 from conftest import make_settings, small_scene
-from depth_restate import map_weights, maps_from_lists, maps_loss, maps_ref
+from depth_restate import assert_rounds_covered, map_weights, maps_from_lists, maps_loss, maps_ref, stacked_scene
 from gpu_util import product_settings
 from grad_util import MARGIN, TOL, compare_grads, linear_weights, oracle_operator_inputs, weighted_sum
 
@@ -34,6 +34,8 @@ MAX_LEFT_OUT = 0.05
 
 
 def _scene(name):
+    if name == "stacked":
+        return stacked_scene()
     model, cam, bg, _ = small_scene(**SCENES["small" if name == "behind" else name])
     if name == "behind":
         model._xyz[3, 2] = -4.0          # behind the camera
@@ -118,9 +120,11 @@ def _check_forward(maps, ref, label):
     assert float(got[:, ~covered & robust].abs().max() if bool((~covered & robust).any()) else 0.0) == 0.0
 
 
-@pytest.mark.parametrize("name", ["small", "big", "behind"])
+@pytest.mark.parametrize("name", ["small", "big", "behind", "stacked"])
 def test_maps_and_gradients_match_the_float64_restatement(gpu_device, name):
     ref = _reference(name)
+    if name == "stacked":
+        assert_rounds_covered(ref["aux"])
     leaves, (color, radii, maps) = _hip(gpu_device, name)
     assert tuple(maps.shape) == (3,) + tuple(ref["robust"].shape) and maps.dtype == torch.float32
     assert torch.equal(radii.cpu(), ref["radii"].to(torch.int32))

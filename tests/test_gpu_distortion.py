@@ -29,6 +29,7 @@ import pytest
 import torch
 
 from conftest import ROOT, make_settings, small_scene
+from depth_restate import assert_rounds_covered, stacked_scene
 from distortion_restate import dist_loss, dist_weights, distortion_ref, slab_model
 from gpu_util import product_settings
 from grad_util import MARGIN, compare_grads, linear_weights, oracle_operator_inputs, weighted_sum
@@ -45,6 +46,8 @@ MAX_LEFT_OUT = 0.05
 
 
 def _scene(name):
+    if name == "stacked":
+        return stacked_scene()
     model, cam, bg, _ = small_scene(**SCENES["big" if name == "big" else "small"])
     if name == "behind":
         model._xyz[3, 2] = -4.0          # behind the camera
@@ -127,9 +130,11 @@ def _check_forward(dist, ref, label):
 
 
 @pytest.mark.parametrize("name,mapping", [("small", "ndc"), ("small", "linear"), ("big", "ndc"), ("behind", "ndc"),
-                                          ("slab", "linear")])
+                                          ("slab", "linear"), ("stacked", "ndc")])
 def test_map_and_gradients_match_the_float64_restatement(gpu_device, name, mapping):
     ref = _reference(name, mapping)
+    if name == "stacked":
+        assert_rounds_covered(ref["aux"])
     leaves, (color, radii, dist) = _hip(gpu_device, name, mapping)
     assert torch.equal(radii.cpu(), ref["radii"].to(torch.int32))
     if name == "big":

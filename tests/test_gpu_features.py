@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from conftest import make_settings, small_scene
+from depth_restate import assert_rounds_covered, stacked_scene
 from features_restate import feature_maps_from_lists, feature_rows, feature_weights
 from gpu_util import product_settings
 from grad_util import MARGIN, TOL, compare_grads, linear_weights, oracle_operator_inputs, weighted_sum
@@ -30,6 +31,8 @@ BEHIND = [3, 17, 101]
 
 
 def _scene(name):
+    if name == "stacked":
+        return stacked_scene()
     model, cam, bg, _ = small_scene(**SCENES["small" if name == "behind" else name])
     if name == "behind":
         model._xyz[3, 2] = -4.0          # behind the camera
@@ -147,12 +150,14 @@ def _check_forward(feat, ref, label):
     assert float(got[:, empty].abs().max() if bool(empty.any()) else 0.0) == 0.0
 
 
-CASES = [("small", 1), ("small", 3), ("small", 8), ("small", 19), ("big", 19), ("behind", 3)]
+CASES = [("small", 1), ("small", 3), ("small", 8), ("small", 19), ("big", 19), ("behind", 3), ("stacked", 9)]
 
 
 @pytest.mark.parametrize("name,C", CASES, ids=[f"{n}-C{c}" for n, c in CASES])
 def test_map_and_gradients_match_the_float64_restatement(gpu_device, name, C):
     ref = _reference(name, C)
+    if name == "stacked":
+        assert_rounds_covered(ref["aux"])
     leaves, (color, radii, feat) = _hip(gpu_device, name, ref["F"])
     assert tuple(feat.shape) == (C,) + tuple(ref["robust"].shape) and feat.dtype == torch.float32
     assert torch.equal(radii.cpu(), ref["radii"].to(torch.int32))

@@ -29,6 +29,7 @@ import torch
 from conftest import ROOT, small_scene
 from gpu_util import product_settings
 from grad_util import MARGIN, TOL, compare_grads, linear_weights, weighted_sum
+from depth_restate import assert_rounds_covered
 from median_restate import BEHIND, SCENES, median_loss, median_weights, reference, scene
 
 sys.path.insert(0, os.path.join(ROOT, "examples"))
@@ -119,11 +120,13 @@ def _check_grads(leaves, median, ref, label, behind=False):
 
 
 @pytest.mark.parametrize("name,use_cov", [("small", False), ("big", False), ("faint", False), ("behind", False),
-                                          ("small", True)])
+                                          ("small", True), ("stacked", False)])
 def test_id_median_and_gradient_match_the_float64_restatement(gpu_device, name, use_cov):
     """Tests 1 and 3 of the issue: the two maps on the kept pixels, uncovered pixels exactly 0 / -1, dL/dxyz of
     sum(weights * median) at the bar of compare_grads, every other leaf without a gradient."""
     ref = reference(name, use_cov)
+    if name == "stacked":
+        assert_rounds_covered(ref["aux"], ref[torch.float64]["pos"])
     label = name + (", cov3D_precomp" if use_cov else "")
     leaves, (color, radii, median, median_id) = _hip(gpu_device, name, use_cov)
     assert torch.equal(radii.cpu(), ref["radii"].to(torch.int32))
