@@ -3,7 +3,7 @@ the surface by marching tetrahedra, all on the HIP path (``mvs_gaussian_splattin
 
     python examples/extract_mesh.py -m <model directory> [--iteration N] [--voxel_size S | --resolution R]
                                     [--sdf_trunc T] [--alpha_min A] [--max_depth D] [--depth_ratio R]
-                                    [-s <dataset>] [-r ...]
+                                    [--num_cluster N] [--min_cluster_faces M] [-s <dataset>] [-r ...]
 
 The scene is loaded as ``examples/render.py`` loads it (``cfg_args.json`` of the model directory; ``-s`` and the other
 switches override it).  The volume bounds the bulk of the model's positions (``tsdf.volume_for_points``); ``--resolution``
@@ -12,7 +12,10 @@ view contributes its expected depth ``depth / alpha`` where ``alpha >= --alpha_m
 the blend ``(1 - R) expected + R median`` depth (``surface_depth``): 2DGS meshes bounded scenes at 1, where a pixel that sees
 a thin edge in front of a far wall lands on one of the two instead of between them.
 
-writes ``<model>/mesh/iteration_<N>/tsdf_mesh.ply`` (binary PLY, vertex colours from the renders).
+writes ``<model>/mesh/iteration_<N>/tsdf_mesh.ply`` (binary PLY, vertex colours from the renders).  With ``--num_cluster N``
+and / or ``--min_cluster_faces M`` (50 when only ``--num_cluster`` is given; 2DGS: 50 and 50) the mesh is cleaned as 2DGS
+cleans it -- the connected triangles are clustered and the clusters at least as large as the N-th largest, and of at
+least M faces, are kept (``mesh.clean_mesh``) -- and written next to the raw one as ``tsdf_mesh_post.ply``.
 """
 import argparse
 import json
@@ -23,12 +26,13 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from mvs_gaussian_splatting_amd import GaussianModel, ModelParams, Scene, fuse_views, volume_for_points  # noqa: E402
+from mvs_gaussian_splatting_amd.mesh import clean_mesh  # noqa: E402
 from mvs_gaussian_splatting_amd.ply_io import write_ply_mesh  # noqa: E402
 from mvs_gaussian_splatting_amd.synthetic import PipelineParams  # noqa: E402
 
 
 def extract(dataset, iteration, voxel_size=None, resolution=None, sdf_trunc=None, alpha_min=0.5, max_depth=None,
-            depth_ratio=0.0):
+            depth_ratio=0.0, num_cluster=None, min_cluster_faces=None):
     with torch.no_grad():
         gaussians = GaussianModel(dataset.sh_degree)
         scene = Scene(dataset, gaussians, load_iteration=iteration, shuffle=False)
@@ -43,6 +47,15 @@ def extract(dataset, iteration, voxel_size=None, resolution=None, sdf_trunc=None
     path = os.path.join(dataset.model_path, "mesh", "iteration_{}".format(scene.loaded_iter), "tsdf_mesh.ply")
     write_ply_mesh(path, vertices, faces, colors)
     print(f"{vertices.shape[0]} vertices, {faces.shape[0]} faces -> {path}")
+    if num_cluster is None and min_cluster_faces is None:
+        return path
+    if min_cluster_faces is None:
+        min_cluster_faces = 50
+    kept_v, kept_f, kept_c = clean_mesh(vertices, faces, colors, keep_largest=num_cluster, min_faces=min_cluster_faces)
+    post = os.path.join(os.path.dirname(path), "tsdf_mesh_post.ply")
+    write_ply_mesh(post, kept_v, kept_f, kept_c)
+    print(f"cleaned (num_cluster {num_cluster}, min_cluster_faces {min_cluster_faces}): {kept_v.shape[0]} of "
+          f"{vertices.shape[0]} vertices, {kept_f.shape[0]} of {faces.shape[0]} faces -> {post}")
     return path
 
 
@@ -64,7 +77,15 @@ def main(argv=None):
     ap.add_argument("--max_depth", type=float, default=None)
     ap.add_argument("--depth_ratio", type=float, default=0.0,
                     help="share of the median depth in the fused surface (2DGS: 0 unbounded, 1 bounded)")
+    ap.add_argument("--num_cluster", type=int, default=None,
+                    help="clean the mesh: keep the clusters at least as large as the N-th largest (2DGS: 50)")
+    ap.add_argument("--min_cluster_faces", type=int, default=None,
+                    help="clean the mesh: drop clusters of fewer faces (50 when --num_cluster is given)")
     args = ap.parse_args(argv)
+    if args.num_cluster is not None and args.num_cluster < 1:
+        ap.error("--num_cluster must be positive")
+    if args.min_cluster_faces is not None and args.min_cluster_faces < 0:
+        ap.error("--min_cluster_faces must not be negative")
     fields = {}
     cfg = os.path.join(args.model_path, "cfg_args.json")
     if os.path.exists(cfg):
@@ -80,7 +101,8 @@ def main(argv=None):
     dataset = ModelParams(model_path=args.model_path, **fields)
     print("Extracting a mesh from " + args.model_path)
     extract(dataset, args.iteration, args.voxel_size, args.resolution, args.sdf_trunc, args.alpha_min, args.max_depth,
-            args.depth_ratio)
+            args.depth_ratio, **({} if args.num_cluster is None and args.min_cluster_faces is None else
+                                 {"num_cluster": args.num_cluster, "min_cluster_faces": args.min_cluster_faces}))
 
 
 if __name__ == "__main__":

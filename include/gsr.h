@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 30
+#define GSR_ABI_VERSION 31
 
 enum {
   GSR_OK = 0,
@@ -872,6 +872,73 @@ int gsr_normal_consistency_fwd_bwd(const float* depth, const float* alpha, const
                                    float tanfovx, float tanfovy, float alpha_min, float* record, float* dL_ddepth,
                                    float* dL_dalpha, float* dL_dnormal, float* depth_normal, void* workspace,
                                    void* stream);
+
+/* ---- Mesh cleaning: connected components of an indexed triangle mesh and compaction, ABI v31 (csrc/mesh.hip; mesh.py;
+ * DESIGN.md §7.18).  faces [F,3] int32, vertices / colors [V,3] float32, device, contiguous; 1 <= V, F < 2^31.
+ * Every call checks its arguments before any HIP call (GSR_E_BADARG: a NULL pointer that is not marked optional, a size
+ * outside its range; GSR_E_ALIGN: int32 / float arrays 4-byte, int64 / uint64 arrays 8-byte), is asynchronous on
+ * `stream`, allocates nothing and reads nothing back; an empty mesh needs no call.
+ * status: device int32 [1], zeroed by the caller.  A face with an index outside 0..V-1 is never used as an index: the
+ * kernel that meets it skips it and stores 1 there; the caller reads the word back with its sizes and refuses the mesh.
+ * stats: NULL, or device uint64 [2], zeroed by the caller: the hooks add their find steps to [0] and their retries (an
+ * atomicMin that found its node linked already) to [1].  The labelling is the same with and without.
+ *
+ * Labelling is a lock-free union-find over n nodes, parent int32 [n]; parent[x] <= x at every instant, every loop step
+ * strictly lowers an index, and no lane waits for another.  The call sequence on one stream:
+ *   vertex connectivity (nodes = vertices, n = V; faces that share a vertex are connected):
+ *     gsr_mesh_cc_init(V, parent, first); gsr_mesh_cc_hook_faces; gsr_mesh_cc_flatten(V, parent);
+ *     gsr_mesh_cc_mark(faces, F, V, parent, first, face_root, mark)
+ *   edge connectivity (nodes = faces, n = F; faces that share an undirected edge are connected):
+ *     gsr_mesh_cc_init(F, parent, NULL); gsr_mesh_edge_keys; the caller sorts the keys; gsr_mesh_cc_hook_runs;
+ *     gsr_mesh_cc_flatten(F, parent); gsr_mesh_cc_mark(NULL, F, 0, parent, NULL, NULL, mark)  (face_root is parent)
+ *   then: ids = exclusive scan of mark (int64), K = its total; gsr_mesh_cc_label.
+ * After flatten parent[x] is the smallest node of x's component, whatever order the atomics landed in: the same bits
+ * from run to run, as is every output below. */
+/* parent[i] = i; first (NULL, or int32 [n]): first[i] = INT32_MAX. */
+int gsr_mesh_cc_init(int64_t n, int32_t* parent, int32_t* first, void* stream);
+/* Each face (v0, v1, v2) unites (v0, v1) and (v0, v2) in parent [V]: find both roots, atomicMin(parent[larger], smaller),
+ * and from the value returned again if it is not `larger`. */
+int gsr_mesh_cc_hook_faces(const int32_t* faces, int64_t F, int64_t V, int32_t* parent, int32_t* status, uint64_t* stats,
+                           void* stream);
+/* keys int64 [3 F], owner int32 [3 F]: slot 3 f + e holds (min(a, b) << 32) | max(a, b) for the edge (a, b) =
+ * (v_e, v_(e+1) mod 3) of face f, and f.  A self-pair (a, a) is an ordinary key.  The three keys of a refused face are
+ * -(3 f + e) - 1: equal to no other. */
+int gsr_mesh_edge_keys(const int32_t* faces, int64_t F, int64_t V, int64_t* keys, int32_t* owner, int32_t* status,
+                       void* stream);
+/* keys_sorted int64 [m]: the keys in ascending order; order int64 [m]: the slot each came from (a sort's indices);
+ * owner int32 [m] as written above (unsorted); m = 3 F, n = F.  For every i with keys_sorted[i] == keys_sorted[i-1]:
+ * unite(owner[order[i-1]], owner[order[i]]) in parent [n].  An order or owner entry out of range is skipped and sets
+ * status. */
+int gsr_mesh_cc_hook_runs(const int64_t* keys_sorted, const int64_t* order, const int32_t* owner, int64_t m, int64_t n,
+                          int32_t* parent, int32_t* status, uint64_t* stats, void* stream);
+/* A launch of its own behind the hooks: parent[i] = root of i. */
+int gsr_mesh_cc_flatten(int64_t n, int32_t* parent, void* stream);
+/* mark uint8 [F]: 1 where face f is the smallest face of its component, else 0.  faces, first and face_root all NULL
+ * (parent is [F], nodes are faces): mark[f] = parent[f] == f.  All three given (parent and first are [V], first as
+ * gsr_mesh_cc_init left it): two launches, first[parent[v0]] = min over the faces f (one atomicMin per wave and root),
+ * then face_root[f] = first[parent[v0]], int32 [F], and mark[f] = face_root[f] == f.  A refused face stands alone. */
+int gsr_mesh_cc_mark(const int32_t* faces, int64_t F, int64_t V, const int32_t* parent, int32_t* first,
+                     int32_t* face_root, uint8_t* mark, void* stream);
+/* face_root int32 [F]: the smallest face of each face's component (parent itself with face nodes); ids int64 [F]: the
+ * exclusive scan of mark; K = the number of marks, 1 <= K <= F.  face_component[f] = ids[face_root[f]], int32 [F]:
+ * components are numbered 0..K-1 in the order of their smallest face.  component_faces int64 [K], zeroed by the caller:
+ * the number of faces of each component, accumulated with integer atomics (one per wave and component).  A face whose
+ * root or id is out of range is not written or counted. */
+int gsr_mesh_cc_label(const int32_t* face_root, const int64_t* ids, int64_t F, int64_t K, int32_t* face_component,
+                      int64_t* component_faces, void* stream);
+/* Compaction, first half.  keep uint8 [F]; vertex_mark uint8 [V], zeroed by the caller: plain stores of 1 at the three
+ * vertices of every face with keep[f] != 0. */
+int gsr_mesh_mark_vertices(const int32_t* faces, const uint8_t* keep, int64_t F, int64_t V, uint8_t* vertex_mark,
+                           int32_t* status, void* stream);
+/* Second half, one launch.  vert_offs int64 [V] / face_offs int64 [F]: the exclusive scans of vertex_mark / keep != 0;
+ * Vk, Fk: their totals, 1 <= Vk <= V, 1 <= Fk <= F (an empty result needs no call).  Marked vertex i: row i of vertices
+ * (and of colors, given together with out_colors or both NULL) is copied to row vert_offs[i] of out_vertices [Vk,3]
+ * (out_colors).  Kept face f: out_faces [Fk,3] row face_offs[f] = vert_offs of its three indices.  Vertices and faces
+ * keep their order, the rows are bit-copies, and nothing at or beyond row Vk / Fk is written whatever the scans hold. */
+int gsr_mesh_compact(const float* vertices, const float* colors, const int32_t* faces, const uint8_t* keep,
+                     const uint8_t* vertex_mark, const int64_t* vert_offs, const int64_t* face_offs, int64_t V, int64_t F,
+                     int64_t Vk, int64_t Fk, float* out_vertices, float* out_colors, int32_t* out_faces, int32_t* status,
+                     void* stream);
 
 #ifdef __cplusplus
 }

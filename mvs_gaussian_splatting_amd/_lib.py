@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # instead of copying it over the in-tree library
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")
 
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 
 class GsrParams(C.Structure):
@@ -276,6 +276,16 @@ SYMBOLS = {
     # depth-normal consistency loss of a rendered frame, value and unit gradients (csrc/normal_consistency.hip)
     "gsr_normal_consistency_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "gsr_normal_consistency_fwd_bwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 2 + [C.c_float] * 3 + [C.c_void_p] * 7),
+    # connected components of an indexed triangle mesh (lock-free union-find) and compaction (csrc/mesh.hip; mesh.py)
+    "gsr_mesh_cc_init": (C.c_int, [C.c_int64] + [C.c_void_p] * 3),
+    "gsr_mesh_cc_hook_faces": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 4),
+    "gsr_mesh_edge_keys": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 4),
+    "gsr_mesh_cc_hook_runs": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int64] + [C.c_void_p] * 4),
+    "gsr_mesh_cc_flatten": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p]),
+    "gsr_mesh_cc_mark": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 5),
+    "gsr_mesh_cc_label": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 3),
+    "gsr_mesh_mark_vertices": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 3),
+    "gsr_mesh_compact": (C.c_int, [C.c_void_p] * 7 + [C.c_int64] * 4 + [C.c_void_p] * 5),
 }
 
 _lib = None

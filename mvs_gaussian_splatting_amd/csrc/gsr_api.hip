@@ -6,6 +6,7 @@
 #include <string.h>
 #include <cmath>
 #include <atomic>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -1518,6 +1519,109 @@ int gsr_tsdf_mesh_emit(const GsrTsdfVolume* vol, const uint8_t* tri_count, const
   hipStream_t s = static_cast<hipStream_t>(stream);
   launch_tsdf_mesh_emit(*vol, tri_count, edge_mask, vert_offs, tri_offs, V, F, vertices, vcolors, faces, s);
   return check(nullptr, s, "tsdf_mesh_emit");
+}
+
+// ---- mesh cleaning: connected components and compaction (csrc/mesh.hip) -----------------------------------------------
+static bool mesh_size_ok(int64_t n) { return n >= 1 && n <= (int64_t)INT32_MAX; }
+static bool mesh_aligned(std::initializer_list<const void*> ptrs, uintptr_t mask) {
+  uintptr_t bits = 0;
+  for (const void* p : ptrs) bits |= (uintptr_t)p;
+  return (bits & mask) == 0;
+}
+int gsr_mesh_cc_init(int64_t n, int32_t* parent, int32_t* first, void* stream) {
+  if (!mesh_size_ok(n)) return fail(GSR_E_BADARG, "n must lie in 1..2^31-1");
+  if (!parent) return fail(GSR_E_BADARG, "parent is NULL");
+  if (!mesh_aligned({parent, first}, 3u)) return fail(GSR_E_ALIGN, "parent / first must be 4-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_mesh_cc_init(n, parent, first, s);
+  return check(nullptr, s, "mesh_cc_init");
+}
+int gsr_mesh_cc_hook_faces(const int32_t* faces, int64_t F, int64_t V, int32_t* parent, int32_t* status, uint64_t* stats,
+                           void* stream) {
+  if (!mesh_size_ok(F) || !mesh_size_ok(V)) return fail(GSR_E_BADARG, "F and V must lie in 1..2^31-1");
+  if (!faces || !parent || !status) return fail(GSR_E_BADARG, "NULL argument");
+  if (!mesh_aligned({faces, parent, status}, 3u)) return fail(GSR_E_ALIGN, "faces / parent / status must be 4-byte aligned");
+  if (!mesh_aligned({stats}, 7u)) return fail(GSR_E_ALIGN, "stats must be 8-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_mesh_cc_hook_faces(faces, F, V, parent, status, stats, s);
+  return check(nullptr, s, "mesh_cc_hook_faces");
+}
+int gsr_mesh_edge_keys(const int32_t* faces, int64_t F, int64_t V, int64_t* keys, int32_t* owner, int32_t* status,
+                       void* stream) {
+  if (!mesh_size_ok(F) || !mesh_size_ok(V)) return fail(GSR_E_BADARG, "F and V must lie in 1..2^31-1");
+  if (!faces || !keys || !owner || !status) return fail(GSR_E_BADARG, "NULL argument");
+  if (!mesh_aligned({faces, owner, status}, 3u)) return fail(GSR_E_ALIGN, "faces / owner / status must be 4-byte aligned");
+  if (!mesh_aligned({keys}, 7u)) return fail(GSR_E_ALIGN, "keys must be 8-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_mesh_edge_keys(faces, F, V, keys, owner, status, s);
+  return check(nullptr, s, "mesh_edge_keys");
+}
+int gsr_mesh_cc_hook_runs(const int64_t* keys_sorted, const int64_t* order, const int32_t* owner, int64_t m, int64_t n,
+                          int32_t* parent, int32_t* status, uint64_t* stats, void* stream) {
+  if (m < 1 || m > 3 * (int64_t)INT32_MAX || !mesh_size_ok(n))
+    return fail(GSR_E_BADARG, "n must lie in 1..2^31-1 and m in 1..3 (2^31-1)");
+  if (!keys_sorted || !order || !owner || !parent || !status) return fail(GSR_E_BADARG, "NULL argument");
+  if (!mesh_aligned({owner, parent, status}, 3u)) return fail(GSR_E_ALIGN, "owner / parent / status must be 4-byte aligned");
+  if (!mesh_aligned({keys_sorted, order, stats}, 7u)) return fail(GSR_E_ALIGN, "keys / order / stats must be 8-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_mesh_cc_hook_runs(keys_sorted, order, owner, m, n, parent, status, stats, s);
+  return check(nullptr, s, "mesh_cc_hook_runs");
+}
+int gsr_mesh_cc_flatten(int64_t n, int32_t* parent, void* stream) {
+  if (!mesh_size_ok(n)) return fail(GSR_E_BADARG, "n must lie in 1..2^31-1");
+  if (!parent) return fail(GSR_E_BADARG, "parent is NULL");
+  if (!mesh_aligned({parent}, 3u)) return fail(GSR_E_ALIGN, "parent must be 4-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_mesh_cc_flatten(n, parent, s);
+  return check(nullptr, s, "mesh_cc_flatten");
+}
+int gsr_mesh_cc_mark(const int32_t* faces, int64_t F, int64_t V, const int32_t* parent, int32_t* first,
+                     int32_t* face_root, uint8_t* mark, void* stream) {
+  if (!mesh_size_ok(F)) return fail(GSR_E_BADARG, "F must lie in 1..2^31-1");
+  if (!parent || !mark) return fail(GSR_E_BADARG, "NULL argument");
+  const int given = (faces != nullptr) + (first != nullptr) + (face_root != nullptr);
+  if (given != 0 && given != 3) return fail(GSR_E_BADARG, "give faces, first and face_root together (vertex nodes) or none");
+  if (given == 3 && !mesh_size_ok(V)) return fail(GSR_E_BADARG, "V must lie in 1..2^31-1");
+  if (!mesh_aligned({faces, parent, first, face_root}, 3u)) return fail(GSR_E_ALIGN, "int32 arrays must be 4-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_mesh_cc_mark(faces, F, V, parent, first, face_root, mark, s);
+  return check(nullptr, s, "mesh_cc_mark");
+}
+int gsr_mesh_cc_label(const int32_t* face_root, const int64_t* ids, int64_t F, int64_t K, int32_t* face_component,
+                      int64_t* component_faces, void* stream) {
+  if (!mesh_size_ok(F) || K < 1 || K > F) return fail(GSR_E_BADARG, "F must lie in 1..2^31-1 and K in 1..F");
+  if (!face_root || !ids || !face_component || !component_faces) return fail(GSR_E_BADARG, "NULL argument");
+  if (!mesh_aligned({face_root, face_component}, 3u)) return fail(GSR_E_ALIGN, "int32 arrays must be 4-byte aligned");
+  if (!mesh_aligned({ids, component_faces}, 7u)) return fail(GSR_E_ALIGN, "int64 arrays must be 8-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_mesh_cc_label(face_root, ids, F, K, face_component, component_faces, s);
+  return check(nullptr, s, "mesh_cc_label");
+}
+int gsr_mesh_mark_vertices(const int32_t* faces, const uint8_t* keep, int64_t F, int64_t V, uint8_t* vertex_mark,
+                           int32_t* status, void* stream) {
+  if (!mesh_size_ok(F) || !mesh_size_ok(V)) return fail(GSR_E_BADARG, "F and V must lie in 1..2^31-1");
+  if (!faces || !keep || !vertex_mark || !status) return fail(GSR_E_BADARG, "NULL argument");
+  if (!mesh_aligned({faces, status}, 3u)) return fail(GSR_E_ALIGN, "faces / status must be 4-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_mesh_mark_vertices(faces, keep, F, V, vertex_mark, status, s);
+  return check(nullptr, s, "mesh_mark_vertices");
+}
+int gsr_mesh_compact(const float* vertices, const float* colors, const int32_t* faces, const uint8_t* keep,
+                     const uint8_t* vertex_mark, const int64_t* vert_offs, const int64_t* face_offs, int64_t V, int64_t F,
+                     int64_t Vk, int64_t Fk, float* out_vertices, float* out_colors, int32_t* out_faces, int32_t* status,
+                     void* stream) {
+  if (!mesh_size_ok(F) || !mesh_size_ok(V)) return fail(GSR_E_BADARG, "F and V must lie in 1..2^31-1");
+  if (Vk < 1 || Vk > V || Fk < 1 || Fk > F) return fail(GSR_E_BADARG, "Vk must lie in 1..V and Fk in 1..F");
+  if (!vertices || !faces || !keep || !vertex_mark || !vert_offs || !face_offs || !out_vertices || !out_faces || !status)
+    return fail(GSR_E_BADARG, "NULL argument");
+  if ((colors != nullptr) != (out_colors != nullptr)) return fail(GSR_E_BADARG, "give colors and out_colors together or neither");
+  if (!mesh_aligned({vertices, colors, faces, out_vertices, out_colors, out_faces, status}, 3u))
+    return fail(GSR_E_ALIGN, "float and int32 arrays must be 4-byte aligned");
+  if (!mesh_aligned({vert_offs, face_offs}, 7u)) return fail(GSR_E_ALIGN, "offsets must be 8-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_mesh_compact(vertices, colors, faces, keep, vertex_mark, vert_offs, face_offs, V, F, Vk, Fk, out_vertices,
+                      out_colors, out_faces, status, s);
+  return check(nullptr, s, "mesh_compact");
 }
 
 // ---- depth-normal consistency loss (csrc/normal_consistency.hip) ------------------------------------------------------

@@ -269,6 +269,28 @@ void launch_tsdf_mesh_emit(const GsrTsdfVolume& vol, const uint8_t* tri_count, c
                            const int64_t* vert_offs, const int64_t* tri_offs, int64_t V, int64_t F, float* vertices,
                            float* vcolors, int32_t* faces, hipStream_t s);
 
+// mesh.hip: connected components of an indexed triangle mesh by a lock-free union-find, and the compaction that keeps
+// a subset of its faces (include/gsr.h).  One lane per node / face / key / vertex, 256-lane workgroups; the entry points
+// have checked every size (1 .. 2^31 - 1) and pointer
+void launch_mesh_cc_init(int64_t n, int32_t* parent, int32_t* first, hipStream_t s);
+void launch_mesh_cc_hook_faces(const int32_t* faces, int64_t F, int64_t V, int32_t* parent, int32_t* status,
+                               uint64_t* stats, hipStream_t s);
+void launch_mesh_edge_keys(const int32_t* faces, int64_t F, int64_t V, int64_t* keys, int32_t* owner, int32_t* status,
+                           hipStream_t s);
+void launch_mesh_cc_hook_runs(const int64_t* keys, const int64_t* order, const int32_t* owner, int64_t m, int64_t n,
+                              int32_t* parent, int32_t* status, uint64_t* stats, hipStream_t s);
+void launch_mesh_cc_flatten(int64_t n, int32_t* parent, hipStream_t s);
+void launch_mesh_cc_mark(const int32_t* faces, int64_t F, int64_t V, const int32_t* parent, int32_t* first,
+                         int32_t* face_root, uint8_t* mark, hipStream_t s);
+void launch_mesh_cc_label(const int32_t* face_root, const int64_t* ids, int64_t F, int64_t K, int32_t* face_component,
+                          int64_t* component_faces, hipStream_t s);
+void launch_mesh_mark_vertices(const int32_t* faces, const uint8_t* keep, int64_t F, int64_t V, uint8_t* vertex_mark,
+                               int32_t* status, hipStream_t s);
+void launch_mesh_compact(const float* vertices, const float* colors, const int32_t* faces, const uint8_t* keep,
+                         const uint8_t* vertex_mark, const int64_t* vert_offs, const int64_t* face_offs, int64_t V,
+                         int64_t F, int64_t Vk, int64_t Fk, float* out_vertices, float* out_colors, int32_t* out_faces,
+                         int32_t* status, hipStream_t s);
+
 // normal_consistency.hip: the depth-normal consistency loss of a rendered frame, value and unit gradients in one launch
 // plus a one-block finish (include/gsr.h).  The three gradient pointers are all set or all nullptr (forward only);
 // depth_normal may be nullptr.  normal_consistency_blocks is false when the launch would exceed 2^32 work-items

@@ -1,0 +1,200 @@
+"""The last step from a fused volume to a usable surface: cluster the connected triangles of an indexed mesh and keep
+the large clusters, on the HIP path (``csrc/mesh.hip`` behind the ``gsr_mesh_*`` entry points).
+
+    vertices, faces, colors = volume.extract_mesh()
+    vertices, faces, colors = clean_mesh(vertices, faces, colors, keep_largest=50, min_faces=50)
+
+The mesh of a trained scene is the surface plus thousands of floaters: every blob of fused depth that crosses zero is a
+small closed shell of its own.  2DGS clusters the connected triangles, keeps the ``num_cluster`` largest clusters and
+drops the vertices nothing refers to; ``clean_mesh`` is that rule.  The labelling is a lock-free union-find on the device
+(init, hook, flatten), the numbering and the compaction are scans (torch) around small kernels; the mesh never leaves the
+device.  There is no CPU path.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Tuple
+
+import torch
+
+from . import _lib
+
+CONNECTIVITIES = ("edge", "vertex")
+
+
+def _check_faces(faces, num_vertices: Optional[int], what: str) -> Tuple[int, Optional[int]]:
+    if not isinstance(faces, torch.Tensor) or faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"faces must be an int32 [F,3] tensor, got {getattr(faces, 'dtype', type(faces))} "
+                         f"{tuple(getattr(faces, 'shape', ()))}")
+    F = int(faces.shape[0])
+    if F >= 2 ** 31:
+        raise ValueError(f"{what} takes fewer than 2^31 faces, got {F}")
+    if num_vertices is not None:
+        if isinstance(num_vertices, bool) or not isinstance(num_vertices, int):
+            raise ValueError(f"num_vertices must be an int, got {num_vertices!r}")
+        if not 0 <= num_vertices < 2 ** 31:
+            raise ValueError(f"num_vertices must lie in 0..2^31-1, got {num_vertices}")
+        if F > 0 and num_vertices == 0:
+            raise ValueError(f"{F} faces refer to vertices, but num_vertices is 0")
+    return F, num_vertices
+
+
+def _check_connectivity(connectivity) -> None:
+    if connectivity not in CONNECTIVITIES:
+        raise ValueError(f"connectivity must be one of {CONNECTIVITIES}, got {connectivity!r}")
+
+
+def _need_gpu(t: torch.Tensor, what: str) -> None:
+    if not t.is_cuda:
+        raise _lib.GsrError(f"{what} needs the mesh on a ROCm GPU (no CPU path)")
+
+
+def _label(faces: torch.Tensor, V: int, connectivity: str, stats: Optional[torch.Tensor] = None):
+    """The native part of ``connected_components`` on contiguous device faces, F > 0 -> (face_component, component_faces)."""
+    lib, dev = _lib.load(), faces.device
+    F = int(faces.shape[0])
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    mark = torch.empty(F, dtype=torch.uint8, device=dev)
+    st = None if stats is None else stats.data_ptr()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if connectivity == "vertex":
+            parent = torch.empty(V, dtype=torch.int32, device=dev)
+            first = torch.empty(V, dtype=torch.int32, device=dev)
+            face_root = torch.empty(F, dtype=torch.int32, device=dev)
+            _lib.check(lib.gsr_mesh_cc_init(V, parent.data_ptr(), first.data_ptr(), stream), "gsr_mesh_cc_init")
+            _lib.check(lib.gsr_mesh_cc_hook_faces(faces.data_ptr(), F, V, parent.data_ptr(), status.data_ptr(), st, stream),
+                       "gsr_mesh_cc_hook_faces")
+            _lib.check(lib.gsr_mesh_cc_flatten(V, parent.data_ptr(), stream), "gsr_mesh_cc_flatten")
+            _lib.check(lib.gsr_mesh_cc_mark(faces.data_ptr(), F, V, parent.data_ptr(), first.data_ptr(),
+                                            face_root.data_ptr(), mark.data_ptr(), stream), "gsr_mesh_cc_mark")
+        else:
+            parent = torch.empty(F, dtype=torch.int32, device=dev)
+            keys = torch.empty(3 * F, dtype=torch.int64, device=dev)
+            owner = torch.empty(3 * F, dtype=torch.int32, device=dev)
+            _lib.check(lib.gsr_mesh_cc_init(F, parent.data_ptr(), None, stream), "gsr_mesh_cc_init")
+            _lib.check(lib.gsr_mesh_edge_keys(faces.data_ptr(), F, V, keys.data_ptr(), owner.data_ptr(), status.data_ptr(),
+                                              stream), "gsr_mesh_edge_keys")
+            keys_sorted, order = torch.sort(keys)                                # plumbing: stays in torch
+            _lib.check(lib.gsr_mesh_cc_hook_runs(keys_sorted.data_ptr(), order.data_ptr(), owner.data_ptr(), 3 * F, F,
+                                                 parent.data_ptr(), status.data_ptr(), st, stream), "gsr_mesh_cc_hook_runs")
+            _lib.check(lib.gsr_mesh_cc_flatten(F, parent.data_ptr(), stream), "gsr_mesh_cc_flatten")
+            _lib.check(lib.gsr_mesh_cc_mark(None, F, 0, parent.data_ptr(), None, None, mark.data_ptr(), stream),
+                       "gsr_mesh_cc_mark")
+            face_root = parent
+        ends = torch.cumsum(mark, dim=0, dtype=torch.int64)
+        K, bad = (int(v) for v in torch.stack((ends[-1], status[0].to(torch.int64))).tolist())       # the one read-back
+        if bad:
+            raise _lib.GsrError(f"connected_components failed: a face refers to a vertex outside 0..{V - 1}")
+        ids = ends - mark                                                        # exclusive scan
+        face_component = torch.empty(F, dtype=torch.int32, device=dev)
+        component_faces = torch.zeros(K, dtype=torch.int64, device=dev)
+        _lib.check(lib.gsr_mesh_cc_label(face_root.data_ptr(), ids.data_ptr(), F, K, face_component.data_ptr(),
+                                         component_faces.data_ptr(), stream), "gsr_mesh_cc_label")
+    return face_component, component_faces
+
+
+def connected_components(faces: torch.Tensor, num_vertices: Optional[int] = None, connectivity: str = "edge",
+                         ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The connected components of the faces of an indexed triangle mesh ->
+    ``(face_component int32 [F], component_faces int64 [K])`` on the device of ``faces`` (int32 ``[F,3]``).
+
+    ``connectivity="edge"`` (the default; Open3D's ``cluster_connected_triangles``, what 2DGS uses): two faces are
+    connected when they share an undirected edge ``{a, b}``; an edge of three or more faces joins all of them.
+    ``connectivity="vertex"``: two faces are connected when they share a vertex.  Vertices are identified by index (a
+    mesh whose faces repeat positions under different indices is not welded here).  Components are numbered ``0..K-1``
+    in the order of their smallest face index; ``component_faces[c]`` is the number of faces of component ``c``.  The
+    same bits from run to run.
+
+    ``num_vertices``: the number of vertices ``V``; every index must lie in ``0..V-1``, which is checked on the device
+    (``GsrError``).  ``None``: ``max(faces) + 1``, one read-back more.  Otherwise one host read-back (``K``, together
+    with the range check); everything runs on the current stream.  ``F == 0``: empty tensors and no native call."""
+    F, V = _check_faces(faces, num_vertices, "connected_components")
+    _check_connectivity(connectivity)
+    _need_gpu(faces, "connected_components")
+    dev = faces.device
+    if F == 0:
+        return torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int64, device=dev)
+    faces = faces.detach().contiguous()
+    if V is None:
+        V = min(max(int(faces.max()) + 1, 1), 2 ** 31 - 1)            # a negative index is then refused on the device
+    return _label(faces, V, connectivity)
+
+
+def clean_mesh(vertices: torch.Tensor, faces: torch.Tensor, colors: Optional[torch.Tensor] = None, *,
+               keep_largest: Optional[int] = None, min_faces: int = 0, connectivity: str = "edge",
+               ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """Keep the large connected components of a mesh and drop the vertices nothing refers to any more ->
+    ``(vertices float32 [V',3], faces int32 [F',3], colors float32 [V',3] or None)``, new tensors on the same device.
+
+    2DGS's post-processing rule.  With the components of ``connected_components(faces, V, connectivity)``:
+    ``threshold = max(min_faces, size of the keep_largest-th largest component)``, where the size term counts as 0 when
+    ``keep_largest`` is ``None`` or at least ``K``; a face is kept when its component has at least ``threshold`` faces.
+    Components that tie with the ``keep_largest``-th largest all survive, so more than ``keep_largest`` components may
+    remain.  (2DGS: ``keep_largest=50, min_faces=50``.)
+
+    Kept vertices and kept faces stay in their original order; the kept vertex and colour rows are bit-copies, the kept
+    faces are re-indexed.  Nothing is kept: ``[0,3]`` tensors.  Two host read-backs (``K`` with the index check, then
+    ``V'`` and ``F'``); everything else stays on the device and on the current stream.  ``F == 0`` makes no native call."""
+    if not isinstance(vertices, torch.Tensor) or vertices.dtype != torch.float32 or vertices.dim() != 2 \
+            or vertices.shape[1] != 3:
+        raise ValueError(f"vertices must be a float32 [V,3] tensor, got {getattr(vertices, 'dtype', type(vertices))} "
+                         f"{tuple(getattr(vertices, 'shape', ()))}")
+    V = int(vertices.shape[0])
+    F, _ = _check_faces(faces, V, "clean_mesh")
+    dev = vertices.device
+    if faces.device != dev:
+        raise ValueError(f"faces must be on the device of vertices ({dev}), got {faces.device}")
+    if colors is not None and (not isinstance(colors, torch.Tensor) or colors.dtype != torch.float32
+                               or tuple(colors.shape) != (V, 3) or colors.device != dev):
+        raise ValueError(f"colors must be a float32 [{V},3] tensor on {dev}, got "
+                         f"{getattr(colors, 'dtype', type(colors))} {tuple(getattr(colors, 'shape', ()))} on "
+                         f"{getattr(colors, 'device', None)}")
+    if keep_largest is not None and (isinstance(keep_largest, bool) or not isinstance(keep_largest, int)
+                                     or keep_largest < 1):
+        raise ValueError(f"keep_largest must be a positive int or None, got {keep_largest!r}")
+    if isinstance(min_faces, bool) or not isinstance(min_faces, int) or min_faces < 0:
+        raise ValueError(f"min_faces must be a non-negative int, got {min_faces!r}")
+    _check_connectivity(connectivity)
+    _need_gpu(vertices, "clean_mesh")
+
+    def empty():
+        return (torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty((0, 3), dtype=torch.int32, device=dev),
+                None if colors is None else torch.empty((0, 3), dtype=torch.float32, device=dev))
+
+    if F == 0:
+        return empty()
+    lib = _lib.load()
+    vertices_c, faces_c = vertices.detach().contiguous(), faces.detach().contiguous()
+    colors_c = None if colors is None else colors.detach().contiguous()
+    face_component, component_faces = _label(faces_c, V, connectivity)              # read-back 1: K
+    K = int(component_faces.shape[0])
+    threshold = torch.full((), min_faces, dtype=torch.int64, device=dev)
+    if keep_largest is not None and keep_largest < K:
+        kth = torch.topk(component_faces, keep_largest, largest=True, sorted=True).values[-1]
+        threshold = torch.maximum(threshold, kth)
+    keep = (component_faces[face_component.to(torch.int64)] >= threshold).to(torch.uint8)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    vertex_mark = torch.zeros(V, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(lib.gsr_mesh_mark_vertices(faces_c.data_ptr(), keep.data_ptr(), F, V, vertex_mark.data_ptr(),
+                                              status.data_ptr(), stream), "gsr_mesh_mark_vertices")
+        vert_end = torch.cumsum(vertex_mark, dim=0, dtype=torch.int64)
+        face_end = torch.cumsum(keep, dim=0, dtype=torch.int64)
+        Vk, Fk = (int(v) for v in torch.stack((vert_end[-1], face_end[-1])).tolist())              # read-back 2: V', F'
+        if Fk == 0:
+            return empty()
+        out_vertices = torch.empty((Vk, 3), dtype=torch.float32, device=dev)
+        out_faces = torch.empty((Fk, 3), dtype=torch.int32, device=dev)
+        out_colors = None if colors_c is None else torch.empty((Vk, 3), dtype=torch.float32, device=dev)
+        vert_offs, face_offs = vert_end - vertex_mark, face_end - keep                              # exclusive scans
+        _lib.check(lib.gsr_mesh_compact(vertices_c.data_ptr(), None if colors_c is None else colors_c.data_ptr(),
+                                        faces_c.data_ptr(), keep.data_ptr(), vertex_mark.data_ptr(), vert_offs.data_ptr(),
+                                        face_offs.data_ptr(), V, F, Vk, Fk, out_vertices.data_ptr(),
+                                        None if out_colors is None else out_colors.data_ptr(), out_faces.data_ptr(),
+                                        status.data_ptr(), stream), "gsr_mesh_compact")
+    return out_vertices, out_faces, out_colors
+
+
+__all__ = ["connected_components", "clean_mesh"]
