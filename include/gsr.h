@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 31
+#define GSR_ABI_VERSION 32
 
 enum {
   GSR_OK = 0,
@@ -939,6 +939,29 @@ int gsr_mesh_compact(const float* vertices, const float* colors, const int32_t* 
                      const uint8_t* vertex_mark, const int64_t* vert_offs, const int64_t* face_offs, int64_t V, int64_t F,
                      int64_t Vk, int64_t Fk, float* out_vertices, float* out_colors, int32_t* out_faces, int32_t* status,
                      void* stream);
+
+/* ---- Cross-set nearest point, ABI v32 (csrc/nearest.hip on the index of csrc/knn.hip; geometry_eval.py).
+ * ref [R,3], query [Q,3] float32, device, contiguous, 4-byte aligned; 0 <= R, Q <= GSR_NN_MAX_POINTS = 2^31 - 256 (a box
+ * of 128 points and a workgroup of 256 queries past the last one still index in 32 bits; more is GSR_E_BADARG).  For every query point the
+ * minimum over the reference of d2 = ((dx dx + dy dy) + dz dz), dx = q.x - r.x, every operation rounded to float32 on its
+ * own (no fused multiply-add), and the smallest reference index that attains it: exact, the bits of a float32 brute force.
+ * Coordinates must be finite: NaN / Inf give an unspecified value, never an access out of range.
+ * Every call checks its arguments before any HIP call (GSR_E_BADARG: a NULL pointer, a negative count; GSR_E_CAPACITY: a
+ * buffer shorter than the matching *_bytes; GSR_E_ALIGN: index / workspace 256-byte, the arrays 4-byte), is asynchronous
+ * on `stream`, allocates nothing and reads nothing back.
+ * index: caller-owned device memory of gsr_nn_index_bytes(R) bytes, written by gsr_nn_build and read by any number of
+ * gsr_nn_query calls: the encoded bounding box, the sorted 30-bit Morton keys, the sorted points as (x, y, z, original
+ * index), the bounds of every box of 128 sorted points and of every super-box of 64 boxes -- and the scratch of the build,
+ * so that a build needs no second buffer.  Nothing in it is read before the build wrote it.  R = 0 needs no build (the
+ * call is a success that writes nothing) and no index. */
+#define GSR_NN_MAX_POINTS 2147483392
+size_t gsr_nn_index_bytes(int32_t R);
+int gsr_nn_build(const float* ref, int32_t R, void* index, size_t index_bytes, void* stream);
+/* dist2 float32 [Q], nearest int32 [Q]; workspace: gsr_nn_query_workspace_bytes(Q) bytes (the queries' Morton keys, their
+ * sort).  R = 0: dist2 = +inf, nearest = -1 (index and workspace may be NULL).  Q = 0: success, nothing is written. */
+size_t gsr_nn_query_workspace_bytes(int32_t Q);
+int gsr_nn_query(const void* index, size_t index_bytes, int32_t R, const float* query, int32_t Q, float* dist2,
+                 int32_t* nearest, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -20,6 +20,7 @@ from .mcmc import mcmc_regularizer, inject_noise, relocate_gs, add_new_gs  # noq
 from .normal_consistency import normal_consistency_loss, depth_to_normals  # noqa: F401
 from .surface import surface_depth  # noqa: F401
 from .mesh import connected_components, clean_mesh  # noqa: F401
+from .geometry_eval import NearestIndex, nearest_points, sample_surface, evaluate_points, evaluate_mesh  # noqa: F401
 
 __all__ = ["Scene", "Camera", "MiniCam", "PoseCamera", "ModelParams", "load_image", "load_image_host",
            "GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "render", "l1_loss", "apply_exposure", "save_exposures", "load_exposures", "l1_dssim_loss",
@@ -27,4 +28,5 @@ __all__ = ["Scene", "Camera", "MiniCam", "PoseCamera", "ModelParams", "load_imag
            "evaluate_views", "ContributionStats", "measure", "prune_points_", "prune_by_contribution",
            "mcmc_regularizer", "inject_noise", "relocate_gs", "add_new_gs", "gaussian_normals",
            "TSDFVolume", "fuse_views", "volume_for_points", "normal_consistency_loss", "depth_to_normals",
-           "surface_depth", "connected_components", "clean_mesh"]
+           "surface_depth", "connected_components", "clean_mesh", "NearestIndex", "nearest_points", "sample_surface",
+           "evaluate_points", "evaluate_mesh"]

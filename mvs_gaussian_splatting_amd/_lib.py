@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # instead of copying it over the in-tree library
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")
 
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 
 class GsrParams(C.Structure):
@@ -286,6 +286,12 @@ SYMBOLS = {
     "gsr_mesh_cc_label": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 3),
     "gsr_mesh_mark_vertices": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 3),
     "gsr_mesh_compact": (C.c_int, [C.c_void_p] * 7 + [C.c_int64] * 4 + [C.c_void_p] * 5),
+    # cross-set nearest point on the Morton-box index of distCUDA2 (csrc/nearest.hip; geometry_eval.py)
+    "gsr_nn_index_bytes": (C.c_size_t, [C.c_int32]),
+    "gsr_nn_build": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gsr_nn_query_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "gsr_nn_query": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_size_t, C.c_void_p]),
 }
 
 _lib = None

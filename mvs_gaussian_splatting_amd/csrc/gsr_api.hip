@@ -1121,6 +1121,40 @@ int gsr_dist2_knn3(const float* points, int32_t N, float* mean_dist2, void* work
   return check(nullptr, s, "knn3");
 }
 
+// ---- cross-set nearest point (csrc/nearest.hip) ------------------------------------------------------------------------
+size_t gsr_nn_index_bytes(int32_t R) { return nn_index_bytes(R); }
+size_t gsr_nn_query_workspace_bytes(int32_t Q) { return nn_query_workspace_bytes(Q); }
+int gsr_nn_build(const float* ref, int32_t R, void* index, size_t index_bytes, void* stream) {
+  if (R < 0 || R > GSR_NN_MAX_POINTS) return fail(GSR_E_BADARG, "R must lie in 0..2^31-256");
+  if (R == 0) return 0;
+  if (!ref || !index) return fail(GSR_E_BADARG, "NULL argument");
+  if (index_bytes < nn_index_bytes(R)) return fail(GSR_E_CAPACITY, "nn index too small");
+  if (((uintptr_t)index & 255u) != 0) return fail(GSR_E_ALIGN, "index must be 256-byte aligned");
+  if (((uintptr_t)ref & 3u) != 0) return fail(GSR_E_ALIGN, "ref must be 4-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_nn_build(ref, R, index, s);
+  return check(nullptr, s, "nn_build");
+}
+int gsr_nn_query(const void* index, size_t index_bytes, int32_t R, const float* query, int32_t Q, float* dist2,
+                 int32_t* nearest, void* workspace, size_t workspace_bytes, void* stream) {
+  if (R < 0 || Q < 0 || R > GSR_NN_MAX_POINTS || Q > GSR_NN_MAX_POINTS)
+    return fail(GSR_E_BADARG, "R and Q must lie in 0..2^31-256");
+  if (Q == 0) return 0;
+  if (!query || !dist2 || !nearest) return fail(GSR_E_BADARG, "NULL argument");
+  if ((((uintptr_t)query | (uintptr_t)dist2 | (uintptr_t)nearest) & 3u) != 0)
+    return fail(GSR_E_ALIGN, "query / dist2 / nearest must be 4-byte aligned");
+  if (R > 0) {
+    if (!index || !workspace) return fail(GSR_E_BADARG, "NULL index / workspace");
+    if (index_bytes < nn_index_bytes(R)) return fail(GSR_E_CAPACITY, "nn index too small");
+    if (workspace_bytes < nn_query_workspace_bytes(Q)) return fail(GSR_E_CAPACITY, "nn query workspace too small");
+    if ((((uintptr_t)index | (uintptr_t)workspace) & 255u) != 0)
+      return fail(GSR_E_ALIGN, "index / workspace must be 256-byte aligned");
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_nn_query(index, R, query, Q, dist2, nearest, workspace, s);
+  return check(nullptr, s, "nn_query");
+}
+
 int gsr_densify_stats(int32_t P, const float* dL_dmeans2D, const int32_t* radii, float* xyz_gradient_accum, float* denom,
                       float* max_radii2D, void* stream) {
   if (P < 0) return fail(GSR_E_BADARG, "P < 0");

@@ -303,6 +303,12 @@ void launch_normal_consistency(const float* depth, const float* alpha, const flo
 // knn.hip
 size_t knn_workspace_bytes(int N);
 void launch_knn3(const float* pts, int N, float* mean_dist2, void* ws, hipStream_t s);
+// nearest.hip
+size_t nn_index_bytes(int R);
+size_t nn_query_workspace_bytes(int Q);
+void launch_nn_build(const float* ref, int R, void* index, hipStream_t s);
+void launch_nn_query(const void* index, int R, const float* query, int Q, float* dist2, int32_t* nearest, void* ws,
+                     hipStream_t s);
 
 // aux.hip
 size_t l1_loss_workspace_bytes();

@@ -11,24 +11,13 @@
 
 #include "gsr_common.h"
 #include "gsr_launch.h"
+#include "knn_index.h"
 
 namespace gsr {
 
 constexpr int KNN_BOX = 128;        // points per box
 constexpr int KNN_SUPER = 64;       // boxes per super-box
-
-__device__ inline unsigned f2ord(float f) {   // order-preserving float -> uint
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__host__ __device__ inline float ord2f(unsigned o) {
-  const unsigned u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __uint_as_float(u);
-#else
-  float f; memcpy(&f, &u, 4); return f;
-#endif
-}
+static_assert(KNN_BOX == KNN_INDEX_BOX && KNN_SUPER == KNN_INDEX_SUPER, "the kernels walk the index knn_index.h lays out");
 
 __global__ __launch_bounds__(256) void knn_bbox_kernel(const float* __restrict__ pts, int N, unsigned* __restrict__ mm) {
   unsigned lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
@@ -64,29 +53,12 @@ __device__ inline void keep3(float d, float* best) {
   }
 }
 
-__device__ inline uint32_t spread10(uint32_t v) {   // 10 bits -> every third bit
-  v &= 0x3ffu;
-  v = (v | (v << 16)) & 0x030000ffu;
-  v = (v | (v << 8)) & 0x0300f00fu;
-  v = (v | (v << 4)) & 0x030c30c3u;
-  v = (v | (v << 2)) & 0x09249249u;
-  return v;
-}
-
 __global__ __launch_bounds__(256) void knn_morton_kernel(const float* __restrict__ pts, int N,
                                                          const unsigned* __restrict__ mm, uint32_t* __restrict__ keys,
                                                          uint32_t* __restrict__ vals) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= N) return;
-  uint32_t code = 0;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float lo = ord2f(mm[a]), hi = ord2f(mm[3 + a]);
-    const float t = (pts[3 * (size_t)i + a] - lo) / fmaxf(hi - lo, 1e-30f);
-    const uint32_t q = (uint32_t)fminf(1023.0f, fmaxf(0.0f, t * 1023.0f));
-    code |= spread10(q) << a;
-  }
-  keys[i] = code;
+  keys[i] = morton30(pts + 3 * (size_t)i, mm);
   vals[i] = (uint32_t)i;
 }
 
@@ -180,35 +152,12 @@ __global__ __launch_bounds__(256) void knn_query_kernel(int N, int nboxes, int n
   mean_dist2[__float_as_uint(me.w)] = (best[0] + best[1] + best[2]) / 3.0f;
 }
 
-struct KnnLayout {
-  size_t mm, ka, kb, va, vb, spts, box_lo, box_hi, sup_lo, sup_hi, sort, bytes;
-  int nboxes, nsuper;
-  explicit KnnLayout(int N) {
-    const size_t n = N > 0 ? (size_t)N : 1;
-    nboxes = (int)((n + KNN_BOX - 1) / KNN_BOX);
-    nsuper = (nboxes + KNN_SUPER - 1) / KNN_SUPER;
-    size_t o = 0;
-    mm = o;     o = align_up(o + 64, 256);
-    ka = o;     o = align_up(o + 4 * n, 256);
-    kb = o;     o = align_up(o + 4 * n, 256);
-    va = o;     o = align_up(o + 4 * n, 256);
-    vb = o;     o = align_up(o + 4 * n, 256);
-    spts = o;   o = align_up(o + 16 * n, 256);
-    box_lo = o; o = align_up(o + 12 * (size_t)nboxes, 256);
-    box_hi = o; o = align_up(o + 12 * (size_t)nboxes, 256);
-    sup_lo = o; o = align_up(o + 12 * (size_t)nsuper, 256);
-    sup_hi = o; o = align_up(o + 12 * (size_t)nsuper, 256);
-    sort = o;   o = align_up(o + SortLayout((uint32_t)n).bytes, 256);
-    bytes = o;
-  }
-};
-
 size_t knn_workspace_bytes(int N) { return KnnLayout(N).bytes; }
 
-void launch_knn3(const float* pts, int N, float* mean_dist2, void* ws, hipStream_t s) {
-  if (N <= 0) return;
+// The index build (knn_index.h): what distCUDA2 and the cross-set query of nearest.hip share.
+void launch_knn_build(const float* pts, int N, void* index, hipStream_t s) {
   const KnnLayout L(N);
-  char* b = static_cast<char*>(ws);
+  char* b = static_cast<char*>(index);
   unsigned* mm = reinterpret_cast<unsigned*>(b + L.mm);
   uint32_t* ka = reinterpret_cast<uint32_t*>(b + L.ka);
   uint32_t* kb = reinterpret_cast<uint32_t*>(b + L.kb);
@@ -225,11 +174,20 @@ void launch_knn3(const float* pts, int N, float* mean_dist2, void* ws, hipStream
   const int nb = (N + 255) / 256;
   hipLaunchKernelGGL(knn_bbox_kernel, dim3(nb < 1024 ? nb : 1024), dim3(256), 0, s, pts, N, mm);
   hipLaunchKernelGGL(knn_morton_kernel, dim3(nb), dim3(256), 0, s, pts, N, mm, ka, va);
-  const bool in_b = launch_sort_pairs_u32(ka, va, kb, vb, (uint32_t)N, 30, b + L.sort, s);
+  const bool in_b = launch_sort_pairs_u32(ka, va, kb, vb, (uint32_t)N, KNN_KEY_BITS, b + L.sort, s);
   hipLaunchKernelGGL(knn_boxes_kernel, dim3(L.nboxes), dim3(KNN_BOX), 0, s, pts, N, in_b ? vb : va, spts, box_lo, box_hi);
   hipLaunchKernelGGL(knn_super_kernel, dim3(L.nsuper), dim3(KNN_SUPER), 0, s, L.nboxes, box_lo, box_hi, sup_lo, sup_hi);
-  hipLaunchKernelGGL(knn_query_kernel, dim3(nb), dim3(256), 0, s, N, L.nboxes, L.nsuper, spts, box_lo, box_hi, sup_lo,
-                     sup_hi, mean_dist2);
+}
+
+void launch_knn3(const float* pts, int N, float* mean_dist2, void* ws, hipStream_t s) {
+  if (N <= 0) return;
+  const KnnLayout L(N);
+  const char* b = static_cast<const char*>(ws);
+  launch_knn_build(pts, N, ws, s);
+  hipLaunchKernelGGL(knn_query_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, L.nboxes, L.nsuper,
+                     reinterpret_cast<const float4*>(b + L.spts), reinterpret_cast<const float*>(b + L.box_lo),
+                     reinterpret_cast<const float*>(b + L.box_hi), reinterpret_cast<const float*>(b + L.sup_lo),
+                     reinterpret_cast<const float*>(b + L.sup_hi), mean_dist2);
 }
 
 }  // namespace gsr

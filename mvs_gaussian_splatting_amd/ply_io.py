@@ -150,6 +150,101 @@ def read_ply_vertices(path: str) -> Tuple[np.ndarray, List[str]]:
     return data, [n for n, _ in props]
 
 
+def read_ply_mesh(path: str):
+    """What ``write_ply_mesh`` writes, back: ``(vertices float32 [V,3], faces int32 [F,3], colors uint8 [V,3] or None)`` as
+    numpy arrays.  Reads binary little-endian and ascii files, any scalar vertex properties (x, y, z and, if all three are
+    there, red, green, blue are used), a face list of any integer count and index type (``uchar`` counts with ``int`` /
+    ``uint`` indices are the common forms); further face properties and further elements after ``face`` are not supported.
+    A face that is not a triangle is refused."""
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError(f"{path}: not a PLY file")
+        fmt, elements = None, []
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError(f"{path}: unterminated PLY header")
+            tok = line.decode("ascii", "replace").split()
+            if not tok or tok[0] in ("comment", "obj_info"):
+                continue
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                elements.append((tok[1], int(tok[2]), []))
+            elif tok[0] == "property":
+                if not elements:
+                    raise ValueError(f"{path}: a property before any element")
+                try:
+                    if tok[1] == "list":
+                        elements[-1][2].append((tok[4], _PLY_TYPES[tok[2]], _PLY_TYPES[tok[3]]))
+                    else:
+                        elements[-1][2].append((tok[2], _PLY_TYPES[tok[1]], None))
+                except (KeyError, IndexError):
+                    raise ValueError(f"{path}: cannot read the property line {line!r}") from None
+            elif tok[0] == "end_header":
+                break
+        if fmt not in ("binary_little_endian", "ascii"):
+            raise ValueError(f"{path}: unsupported PLY format {fmt!r}")
+        names = [e[0] for e in elements]
+        if names[:1] != ["vertex"]:
+            raise ValueError(f"{path}: the first element must be 'vertex'")
+        if len(names) > 2 or (len(names) == 2 and names[1] != "face"):
+            raise ValueError(f"{path}: elements other than 'vertex' and 'face' are not supported")
+        _, V, vprops = elements[0]
+        if any(p[2] is not None for p in vprops):
+            raise ValueError(f"{path}: list properties of the vertex element are not supported")
+        F, fprops = (elements[1][1], elements[1][2]) if len(elements) == 2 else (0, [])
+        if len(elements) == 2 and (len(fprops) != 1 or fprops[0][2] is None or fprops[0][1][0] not in "iu"
+                                   or fprops[0][2][0] not in "iu"):
+            raise ValueError(f"{path}: the face element must hold one integer list property")
+        vdtype = np.dtype([(n, "<" + t) for n, t, _ in vprops])
+        if fmt == "binary_little_endian":
+            raw = f.read()
+            if len(raw) < V * vdtype.itemsize:
+                raise ValueError(f"{path}: the file ends inside the vertex element")
+            vert = np.frombuffer(raw, dtype=vdtype, count=V)
+            faces = np.zeros((F, 3), dtype=np.int32)
+            if F:
+                fdtype = np.dtype([("n", "<" + fprops[0][1]), ("idx", "<" + fprops[0][2], (3,))])
+                body = raw[V * vdtype.itemsize:]
+                first = np.frombuffer(body, dtype="<" + fprops[0][1], count=1) if len(body) >= fdtype["n"].itemsize else [3]
+                if int(first[0]) != 3:
+                    raise ValueError(f"{path}: face 0 has {int(first[0])} vertices; only triangles are supported")
+                if len(body) < F * fdtype.itemsize:
+                    raise ValueError(f"{path}: the file ends inside the face element (or a face is not a triangle)")
+                face = np.frombuffer(body, dtype=fdtype, count=F)
+                bad = np.flatnonzero(face["n"] != 3)
+                if bad.size:
+                    raise ValueError(f"{path}: face {int(bad[0])} is not a triangle; only triangles are supported")
+                idx = face["idx"]
+        else:
+            rows = [ln.split() for ln in f.read().decode("ascii", "replace").splitlines() if ln.strip()]
+            if len(rows) < V + F:
+                raise ValueError(f"{path}: {len(rows)} data lines for {V} vertices and {F} faces")
+            vert = np.zeros(V, dtype=vdtype)
+            flat = np.array([r[:len(vprops)] for r in rows[:V]], dtype=np.float64).reshape(V, len(vprops))
+            for i, (n, _, _) in enumerate(vprops):
+                vert[n] = flat[:, i]
+            faces = np.zeros((F, 3), dtype=np.int32)
+            if F:
+                for k, r in enumerate(rows[V:V + F]):
+                    if int(r[0]) != 3 or len(r) < 4:
+                        raise ValueError(f"{path}: face {k} has {r[0]} vertices; only triangles are supported")
+                idx = np.array([r[1:4] for r in rows[V:V + F]], dtype=np.int64)
+        if F:
+            if idx.min() < 0 or idx.max() >= V or idx.max() > np.iinfo(np.int32).max:
+                raise ValueError(f"{path}: a face refers to a vertex outside 0..{V - 1}")
+            faces = np.array(idx, dtype=np.int32, order="C").reshape(F, 3).copy()      # packed rows: never a view
+    have = set(vert.dtype.names or ())
+    if not {"x", "y", "z"} <= have:
+        raise ValueError(f"{path}: the vertex element has no x, y, z")
+    vertices = np.stack([np.asarray(vert[n], dtype=np.float32) for n in ("x", "y", "z")], axis=1).reshape(V, 3)
+    colors = None
+    if {"red", "green", "blue"} <= have:
+        colors = np.stack([np.asarray(vert[n], dtype=np.uint8) for n in ("red", "green", "blue")], axis=1).reshape(V, 3)
+    return vertices, faces, colors
+
+
 def load_ply(path: str, max_sh_degree: int = 3, device="cpu") -> Dict[str, torch.Tensor]:
     """``GaussianModel.load_ply``: returns the raw parameter tensors in the model's layout
     (``_features_dc [P,1,3]``, ``_features_rest [P,(deg+1)^2-1,3]``), float32, on ``device``."""
