@@ -12,7 +12,7 @@
 //            with a non-temporal load: it is read once); the last, partial chunk and unaligned tensors go per element
 //   values : torch's foreach ops one by one, each rounded to float32 (see adam_update); no LDS, no atomics
 #include "gsr_common.h"
-#include "gsr_launch.h"
+#include "gsr_entry.h"
 
 namespace gsr {
 
@@ -242,8 +242,7 @@ __global__ __launch_bounds__(ADAM_BLOCK) void adam_step_rows_kernel(const AdamRo
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
-}  // namespace
-
+// one launch over the batch's tensors; returns nonzero (nothing enqueued) if the grid would exceed 2^32 work-items
 int launch_adam_step(const GsrAdamBatch& batch, hipStream_t s) {
   AdamLaunch L = {};
   L.count = batch.count;
@@ -262,6 +261,7 @@ int launch_adam_step(const GsrAdamBatch& batch, hipStream_t s) {
   return 0;
 }
 
+// the row-masked step; the caller has checked that rows > 0 divides the numel of every non-empty entry
 int launch_adam_step_rows(const GsrAdamRowsBatch& batch, hipStream_t s) {
   AdamRowsLaunch R = {};
   AdamLaunch& L = R.a;
@@ -286,4 +286,52 @@ int launch_adam_step_rows(const GsrAdamRowsBatch& batch, hipStream_t s) {
   return 0;
 }
 
+}  // namespace
+
 }  // namespace gsr
+
+// ---- entry points (include/gsr.h) -----------------------------------------------------------------------------------
+using namespace gsr;
+
+extern "C" {
+
+int gsr_adam_step(const GsrAdamBatch* batch, void* stream) {
+  if (!batch) return fail(GSR_E_BADARG, "NULL batch");
+  if (batch->count < 0 || batch->count > GSR_ADAM_MAX_TENSORS)
+    return fail(GSR_E_BADARG, "count must be 0..GSR_ADAM_MAX_TENSORS");
+  for (int k = 0; k < batch->count; ++k) {
+    const GsrAdamTensor& t = batch->t[k];
+    if (t.numel < 0) return fail(GSR_E_BADARG, "negative numel");
+    if (t.numel > 0 && (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq))
+      return fail(GSR_E_BADARG, "NULL param / grad / exp_avg / exp_avg_sq");
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (launch_adam_step(*batch, s)) return fail(GSR_E_BADARG, "batch too large for one launch (more than 2^32 work-items)");
+  return check(false, s, "adam_step");
+}
+
+int gsr_adam_step_rows(const GsrAdamRowsBatch* batch, void* stream) {
+  if (!batch) return fail(GSR_E_BADARG, "NULL batch");
+  if (batch->count < 0 || batch->count > GSR_ADAM_MAX_TENSORS)
+    return fail(GSR_E_BADARG, "count must be 0..GSR_ADAM_MAX_TENSORS");
+  if (batch->visibility_kind != GSR_ADAM_VIS_U8 && batch->visibility_kind != GSR_ADAM_VIS_I32)
+    return fail(GSR_E_BADARG, "unknown visibility_kind");
+  if (batch->rows < 0) return fail(GSR_E_BADARG, "negative rows");
+  for (int k = 0; k < batch->count; ++k) {
+    const GsrAdamTensor& t = batch->t[k];
+    if (t.numel < 0) return fail(GSR_E_BADARG, "negative numel");
+    if (t.numel == 0) continue;
+    if (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq)
+      return fail(GSR_E_BADARG, "NULL param / grad / exp_avg / exp_avg_sq");
+    if (!batch->visibility) return fail(GSR_E_BADARG, "NULL visibility with a non-empty tensor");
+    if (batch->rows == 0 || t.numel % batch->rows != 0) return fail(GSR_E_BADARG, "numel is not a multiple of rows");
+  }
+  if (batch->visibility_kind == GSR_ADAM_VIS_I32 && !aligned({batch->visibility}, 3u))
+    return fail(GSR_E_ALIGN, "an int32 visibility must be 4-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (launch_adam_step_rows(*batch, s))
+    return fail(GSR_E_BADARG, "batch too large for one launch (more than 2^32 work-items)");
+  return check(false, s, "adam_step_rows");
+}
+
+}  // extern "C"

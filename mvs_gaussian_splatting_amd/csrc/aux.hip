@@ -3,6 +3,7 @@
 //   densification statistics        scene/gaussian_model.py:775-777, train.py:130 (§8 a13)
 // plus the unpack kernels behind the gsr_debug_read_* inspection entry points.
 #include "gsr_common.h"
+#include "gsr_entry.h"
 #include "gsr_launch.h"
 
 namespace gsr {
@@ -118,24 +119,13 @@ __global__ __launch_bounds__(PRE_BLOCK) void unpack_geom_kernel(int P, const Geo
 }
 
 
-size_t l1_loss_workspace_bytes() { return sizeof(float) * L1_MAX_BLOCKS; }
-void launch_l1_loss(const float* x, const float* gt, size_t n, float scale, float* loss_sum, float* dL_dx,
-                    float* partials, hipStream_t s) {
+static void launch_l1_loss(const float* x, const float* gt, size_t n, float scale, float* loss_sum, float* dL_dx,
+                           float* partials, hipStream_t s) {
   size_t blocks = (n / 4 + L1_THREADS - 1) / L1_THREADS;
   if (blocks > (size_t)L1_MAX_BLOCKS) blocks = L1_MAX_BLOCKS;
   if (blocks == 0) blocks = 1;
   hipLaunchKernelGGL(l1_loss_kernel, dim3((unsigned)blocks), dim3(L1_THREADS), 0, s, x, gt, n, scale, partials, dL_dx);
   hipLaunchKernelGGL(l1_loss_finish_kernel, dim3(1), dim3(WAVE), 0, s, partials, (int)blocks, loss_sum);
-}
-void launch_densify_stats(int P, const float* dL_dmeans2D, const int32_t* radii, float* accum, float* denom,
-                          float* max_radii2D, hipStream_t s) {
-  if (P <= 0) return;
-  hipLaunchKernelGGL(densify_stats_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, dL_dmeans2D, radii, accum, denom,
-                     max_radii2D);
-}
-void launch_mark_visible(int P, const float* means3D, const float* viewmatrix, uint8_t* visible, hipStream_t s) {
-  if (P <= 0) return;
-  hipLaunchKernelGGL(mark_visible_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, means3D, viewmatrix, visible);
 }
 void launch_unpack_geom(int P, const GeomRec* rec, const BinInfo* bin, const uint32_t* block_offs, float* xy,
                         float* conic_opacity, float* rgb, float* depth, uint32_t* tiles, uint32_t* point_offsets,
@@ -146,3 +136,40 @@ void launch_unpack_geom(int P, const GeomRec* rec, const BinInfo* bin, const uin
 }
 
 }  // namespace gsr
+
+// ---- entry points (include/gsr.h) -----------------------------------------------------------------------------------
+using namespace gsr;
+
+extern "C" {
+
+size_t gsr_l1_loss_workspace_bytes(void) { return sizeof(float) * L1_MAX_BLOCKS; }
+int gsr_l1_loss_fwd_bwd(const float* x, const float* gt, size_t n, float scale, float* loss_sum, float* dL_dx,
+                        void* workspace, void* stream) {
+  if (!x || !gt || !loss_sum || !workspace) return fail(GSR_E_BADARG, "NULL input");
+  if (!aligned({x, gt, dL_dx}, 15u)) return fail(GSR_E_ALIGN, "16-byte alignment required");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_l1_loss(x, gt, n, scale, loss_sum, dL_dx, static_cast<float*>(workspace), s);
+  return check(false, s, "l1_loss");
+}
+
+int gsr_densify_stats(int32_t P, const float* dL_dmeans2D, const int32_t* radii, float* xyz_gradient_accum, float* denom,
+                      float* max_radii2D, void* stream) {
+  if (P < 0) return fail(GSR_E_BADARG, "P < 0");
+  if (P == 0) return 0;
+  if (!dL_dmeans2D || !radii || !xyz_gradient_accum || !denom || !max_radii2D) return fail(GSR_E_BADARG, "NULL input");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(densify_stats_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, dL_dmeans2D, radii,
+                     xyz_gradient_accum, denom, max_radii2D);
+  return check(false, s, "densify_stats");
+}
+
+int gsr_mark_visible(int32_t P, const float* means3D, const float* viewmatrix, uint8_t* visible, void* stream) {
+  if (P < 0) return fail(GSR_E_BADARG, "P < 0");
+  if (P == 0) return 0;
+  if (!means3D || !viewmatrix || !visible) return fail(GSR_E_BADARG, "NULL argument");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(mark_visible_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, means3D, viewmatrix, visible);
+  return check(false, s, "mark_visible");
+}
+
+}  // extern "C"

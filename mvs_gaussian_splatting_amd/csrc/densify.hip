@@ -14,6 +14,7 @@
 //   gather    : dst row <- src row for kept / clone / child rows (moments: zeros for the new rows, :458-459)
 //   children  : xyz = R(rotation) (exp(scaling) * noise) + xyz ;  scaling = log(exp(scaling) / (0.8 * 2))
 #include "gsr_common.h"
+#include "gsr_entry.h"
 #include "gsr_launch.h"
 
 namespace gsr {
@@ -139,6 +140,12 @@ __global__ void densify_split_children_kernel(int P, const float* __restrict__ x
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------
+// counts = {kept originals, kept clones, kept children per copy, split-selected}
+struct DensifyLayout {
+  size_t flags, block_counts, block_offs, totals, pos, bytes;
+  int nblocks;
+  explicit DensifyLayout(int P);
+};
 DensifyLayout::DensifyLayout(int P) {
   nblocks = (P + DN_BLOCK - 1) / DN_BLOCK;
   if (nblocks < 1) nblocks = 1;
@@ -151,8 +158,9 @@ DensifyLayout::DensifyLayout(int P) {
   bytes = o;
 }
 
-void launch_densify_plan(int P, const float* accum, const float* denom, const float* scaling, const float* opacity,
-                         float thr, float pde, float min_opacity, float ws_limit, int use_ws, void* ws, hipStream_t s) {
+static void launch_densify_plan(int P, const float* accum, const float* denom, const float* scaling, const float* opacity,
+                                float thr, float pde, float min_opacity, float ws_limit, int use_ws, void* ws,
+                                hipStream_t s) {
   const DensifyLayout L(P);
   char* base = static_cast<char*>(ws);
   uint8_t* flags = reinterpret_cast<uint8_t*>(base + L.flags);
@@ -169,8 +177,8 @@ void launch_densify_plan(int P, const float* accum, const float* denom, const fl
   hipLaunchKernelGGL(densify_positions_kernel, dim3(nb), dim3(DN_BLOCK), 0, s, P, flags, offs, nb, pos);
 }
 
-void launch_densify_gather_rows(int P, int w, const float* src, const void* ws, const uint32_t counts[4], int zero_new,
-                                float* dst, hipStream_t s) {
+static void launch_densify_gather_rows(int P, int w, const float* src, const void* ws, const uint32_t counts[4],
+                                       int zero_new, float* dst, hipStream_t s) {
   const DensifyLayout L(P);
   const int32_t* pos = reinterpret_cast<const int32_t*>(static_cast<const char*>(ws) + L.pos);
   const size_t total = (size_t)P * w;
@@ -179,9 +187,9 @@ void launch_densify_gather_rows(int P, int w, const float* src, const void* ws, 
                      src, pos, counts[0], counts[1], counts[2], zero_new, dst);
 }
 
-void launch_densify_split_children(int P, const float* xyz, const float* scaling, const float* rotation,
-                                   const float* noise, const void* ws, const uint32_t counts[4], float* dst_xyz,
-                                   float* dst_scaling, hipStream_t s) {
+static void launch_densify_split_children(int P, const float* xyz, const float* scaling, const float* rotation,
+                                          const float* noise, const void* ws, const uint32_t counts[4], float* dst_xyz,
+                                          float* dst_scaling, hipStream_t s) {
   const DensifyLayout L(P);
   const int32_t* pos = reinterpret_cast<const int32_t*>(static_cast<const char*>(ws) + L.pos);
   if (P == 0 || counts[2] == 0) return;
@@ -190,3 +198,54 @@ void launch_densify_split_children(int P, const float* xyz, const float* scaling
 }
 
 }  // namespace gsr
+
+// ---- entry points (include/gsr.h) -----------------------------------------------------------------------------------
+using namespace gsr;
+
+extern "C" {
+
+size_t gsr_densify_workspace_bytes(int32_t P) { return P < 0 ? 0 : DensifyLayout(P).bytes; }
+int gsr_densify_plan(int32_t P, const float* xyz_gradient_accum, const float* denom, const float* scaling_raw,
+                     const float* opacity_raw, float grad_threshold, float percent_dense_extent, float min_opacity,
+                     float max_world_scale, void* workspace, size_t workspace_bytes, uint32_t counts_host[4],
+                     void* stream) {
+  if (P < 0) return fail(GSR_E_BADARG, "P < 0");
+  if (!counts_host) return fail(GSR_E_BADARG, "NULL counts_host");
+  counts_host[0] = counts_host[1] = counts_host[2] = counts_host[3] = 0;
+  if (P == 0) return 0;
+  if (!xyz_gradient_accum || !denom || !scaling_raw || !opacity_raw || !workspace) return fail(GSR_E_BADARG, "NULL input");
+  if (!aligned({workspace}, 255u)) return fail(GSR_E_ALIGN, "workspace must be 256-byte aligned");
+  const DensifyLayout L(P);
+  if (workspace_bytes < L.bytes) return fail(GSR_E_CAPACITY, "densify workspace too small");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_densify_plan(P, xyz_gradient_accum, denom, scaling_raw, opacity_raw, grad_threshold, percent_dense_extent,
+                      min_opacity, max_world_scale, max_world_scale >= 0.0f ? 1 : 0, workspace, s);
+  if (int rc = check(false, s, "densify_plan")) return rc;
+  GSR_HIP(hipMemcpyAsync(counts_host, static_cast<char*>(workspace) + L.totals, 16, hipMemcpyDeviceToHost, s));
+  GSR_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+int gsr_densify_gather_rows(int32_t P, int32_t row_floats, const float* src, const void* workspace,
+                            const uint32_t counts[4], int32_t zero_new, float* dst, void* stream) {
+  if (P < 0 || row_floats <= 0) return fail(GSR_E_BADARG, "bad P / row_floats");
+  if (P == 0) return 0;
+  if (!src || !workspace || !counts) return fail(GSR_E_BADARG, "NULL argument");
+  if (!dst && counts[0] + counts[1] + counts[2] > 0) return fail(GSR_E_BADARG, "NULL dst");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_densify_gather_rows(P, row_floats, src, workspace, counts, zero_new, dst, s);
+  return check(false, s, "densify_gather_rows");
+}
+int gsr_densify_split_children(int32_t P, const float* xyz, const float* scaling_raw, const float* rotation_raw,
+                               const float* noise, const void* workspace, const uint32_t counts[4], float* dst_xyz,
+                               float* dst_scaling, void* stream) {
+  if (P < 0) return fail(GSR_E_BADARG, "P < 0");
+  if (!counts) return fail(GSR_E_BADARG, "NULL counts");
+  if (P == 0 || counts[2] == 0) return 0;
+  if (!xyz || !scaling_raw || !rotation_raw || !noise || !workspace || !dst_xyz || !dst_scaling)
+    return fail(GSR_E_BADARG, "NULL argument");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_densify_split_children(P, xyz, scaling_raw, rotation_raw, noise, workspace, counts, dst_xyz, dst_scaling, s);
+  return check(false, s, "densify_split_children");
+}
+
+}  // extern "C"

@@ -26,6 +26,7 @@
 //
 // The per-Gaussian arithmetic keeps the reference's float32 operation order (built with -ffp-contract=off).
 #include "gsr_common.h"
+#include "gsr_entry.h"
 #include "gsr_launch.h"
 #include "grow_common.h"
 
@@ -259,6 +260,12 @@ __global__ __launch_bounds__(256) void densify_fork_rows_dir_kernel(ForkRowsArgs
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------
+// counts = {kept originals, kept clones / grown, kept children per copy, split-selected, selected}
+struct DensifyForkLayout {
+  size_t flags, block_counts, block_offs, totals, pos, sel_src, bytes;
+  int nblocks;
+  explicit DensifyForkLayout(int P);
+};
 DensifyForkLayout::DensifyForkLayout(int P) {
   nblocks = (P + DF_BLOCK - 1) / DF_BLOCK;
   if (nblocks < 1) nblocks = 1;
@@ -273,9 +280,9 @@ DensifyForkLayout::DensifyForkLayout(int P) {
   bytes = o;
 }
 
-void launch_densify_fork_plan(int P, const float* accum, const float* denom, const float* scaling,
-                              const float* opacity, const float* split_scale, float thr, float pde, float min_opacity,
-                              float ws_limit, int use_ws, void* ws, hipStream_t s) {
+static void launch_densify_fork_plan(int P, const float* accum, const float* denom, const float* scaling,
+                                     const float* opacity, const float* split_scale, float thr, float pde,
+                                     float min_opacity, float ws_limit, int use_ws, void* ws, hipStream_t s) {
   const DensifyForkLayout L(P);
   char* base = static_cast<char*>(ws);
   uint8_t* flags = reinterpret_cast<uint8_t*>(base + L.flags);
@@ -293,8 +300,8 @@ void launch_densify_fork_plan(int P, const float* accum, const float* denom, con
   hipLaunchKernelGGL(densify_fork_positions_kernel, dim3(nb), dim3(DF_BLOCK), 0, s, P, flags, offs, nb, pos, sel_src);
 }
 
-void launch_densify_fork_gather_rows(int P, int w, const float* src, const void* ws, const uint32_t counts[5],
-                                     int ncopies, int policy, float value, float* dst, hipStream_t s) {
+static void launch_densify_fork_gather_rows(int P, int w, const float* src, const void* ws, const uint32_t counts[5],
+                                            int ncopies, int policy, float value, float* dst, hipStream_t s) {
   const DensifyForkLayout L(P);
   const char* base = static_cast<const char*>(ws);
   const uint8_t* flags = reinterpret_cast<const uint8_t*>(base + L.flags);
@@ -314,8 +321,8 @@ void launch_densify_fork_gather_rows(int P, int w, const float* src, const void*
                        counts[0], counts[1], counts[2], ncopies, po, pe, pc, value, dst);
 }
 
-void launch_densify_fork_rows(const GsrDensifyFork& f, const void* ws, const uint32_t counts[5], float* xyz_out,
-                              float* scaling_out, float* conti_out, hipStream_t s) {
+static void launch_densify_fork_rows(const GsrDensifyFork& f, const void* ws, const uint32_t counts[5], float* xyz_out,
+                                     float* scaling_out, float* conti_out, hipStream_t s) {
   const DensifyForkLayout L(f.P);
   const char* base = static_cast<const char*>(ws);
   ForkRowsArgs a;
@@ -332,3 +339,73 @@ void launch_densify_fork_rows(const GsrDensifyFork& f, const void* ws, const uin
 }
 
 }  // namespace gsr
+
+// ---- entry points (include/gsr.h) -----------------------------------------------------------------------------------
+using namespace gsr;
+
+extern "C" {
+
+size_t gsr_densify_fork_workspace_bytes(int32_t P) { return P < 0 ? 0 : DensifyForkLayout(P).bytes; }
+int gsr_densify_fork_plan(int32_t P, const float* xyz_gradient_accum, const float* denom, const float* scaling_raw,
+                          const float* opacity_raw, const float* split_scale_raw, float grad_threshold,
+                          float percent_dense_extent, float min_opacity, float max_world_scale, void* workspace,
+                          size_t workspace_bytes, uint32_t counts_host[5], void* stream) {
+  if (P < 0) return fail(GSR_E_BADARG, "P < 0");
+  if (!counts_host) return fail(GSR_E_BADARG, "NULL counts_host");
+  for (int k = 0; k < 5; ++k) counts_host[k] = 0;
+  if (P == 0) return 0;
+  if (!xyz_gradient_accum || !denom || !scaling_raw || !opacity_raw || !workspace) return fail(GSR_E_BADARG, "NULL input");
+  if (!aligned({workspace}, 255u)) return fail(GSR_E_ALIGN, "workspace must be 256-byte aligned");
+  const DensifyForkLayout L(P);
+  if (workspace_bytes < L.bytes) return fail(GSR_E_CAPACITY, "densify_fork workspace too small");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_densify_fork_plan(P, xyz_gradient_accum, denom, scaling_raw, opacity_raw, split_scale_raw, grad_threshold,
+                           percent_dense_extent, min_opacity, max_world_scale, max_world_scale >= 0.0f ? 1 : 0,
+                           workspace, s);
+  if (int rc = check(false, s, "densify_fork_plan")) return rc;
+  GSR_HIP(hipMemcpyAsync(counts_host, static_cast<char*>(workspace) + L.totals, 20, hipMemcpyDeviceToHost, s));
+  GSR_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+int gsr_densify_fork_gather_rows(int32_t P, int32_t row_floats, const float* src, const void* workspace,
+                                 const uint32_t counts[5], int32_t grow_branch, int32_t policy, float value, float* dst,
+                                 void* stream) {
+  if (P < 0 || row_floats <= 0) return fail(GSR_E_BADARG, "bad P / row_floats");
+  if (policy < 0 || policy >= 64 || (policy & 3) == 3 || ((policy >> 2) & 3) == 3 || ((policy >> 4) & 3) == 3)
+    return fail(GSR_E_BADARG, "bad row policy");
+  if (P == 0) return 0;
+  if (!src || !workspace || !counts) return fail(GSR_E_BADARG, "NULL argument");
+  if (!dst && counts[0] + counts[1] + counts[2] > 0) return fail(GSR_E_BADARG, "NULL dst");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_densify_fork_gather_rows(P, row_floats, src, workspace, counts, grow_branch ? 4 : 2, policy, value, dst, s);
+  return check(false, s, "densify_fork_gather_rows");
+}
+int gsr_densify_fork_rows(const GsrDensifyFork* f, const void* workspace, const uint32_t counts[5], float* xyz_out,
+                          float* scaling_out, float* conti_dirs_out, void* stream) {
+  if (!f || !counts) return fail(GSR_E_BADARG, "NULL argument");
+  if (f->P < 0) return fail(GSR_E_BADARG, "P < 0");
+  if (f->P == 0 || counts[4] == 0 || counts[0] + counts[1] + counts[2] == 0) return 0;     // nothing to write
+  if (counts[4] > (uint32_t)f->P || counts[3] > counts[4] || counts[2] > counts[3])
+    return fail(GSR_E_BADARG, "counts do not come from gsr_densify_fork_plan of this P");
+  GsrDensifyFork g = *f;
+  const int grow = (g.mode & GSR_DENSIFY_GROW) != 0;
+  if (grow && ((g.mode & GSR_GROW_DIR) != 0) == ((g.mode & GSR_GROW_CONTINUOUS) != 0))
+    return fail(GSR_E_BADARG, "the grow branch needs exactly one of GSR_GROW_DIR and GSR_GROW_CONTINUOUS");
+  if (!g.xyz || !g.scaling || !g.rotation || !workspace || !xyz_out || !scaling_out)
+    return fail(GSR_E_BADARG, "NULL model tensor or output");
+  if (grow && (g.mode & GSR_GROW_DIR) && (!g.dirs_prob || !g.dirs || g.num_dirs <= 0))
+    return fail(GSR_E_BADARG, "GSR_GROW_DIR needs dirs_prob, dirs and num_dirs > 0");
+  if (grow && (g.mode & GSR_GROW_CONTINUOUS) && !g.conti_dirs) return fail(GSR_E_BADARG, "NULL conti_dirs");
+  if (grow && (g.mode & GSR_GROW_DISTANCE) && !g.grow_dist) return fail(GSR_E_BADARG, "NULL grow_dist");
+  if ((g.mode & GSR_SPLIT_DISTANCE) && !g.split_distance) return fail(GSR_E_BADARG, "NULL split_distance");
+  if ((g.mode & GSR_SPLIT_SCALE) && !g.split_scale) return fail(GSR_E_BADARG, "NULL split_scale");
+  if (!(g.mode & GSR_SPLIT_DISTANCE) && counts[3] > 0 && !g.noise) return fail(GSR_E_BADARG, "NULL noise");
+  if (conti_dirs_out && (!grow || !(g.mode & GSR_GROW_CONTINUOUS) || !g.dir_noise))
+    return fail(GSR_E_BADARG, "conti_dirs_out needs the continuous grow branch and dir_noise");
+  if (!(g.mode & GSR_SPLIT_SCALE)) g.split_scale = nullptr;     // the kernels read k = 1.6 from a NULL split_scale
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_densify_fork_rows(g, workspace, counts, xyz_out, scaling_out, conti_dirs_out, s);
+  return check(false, s, "densify_fork_rows");
+}
+
+}  // extern "C"

@@ -15,12 +15,13 @@
 //     the workspace; exposure_grad_finish_kernel (one block) adds the slots in a fixed order and rounds once to
 //     float32.  No atomics: dA depends on H, W and the data only, and is the same bits from run to run.
 #include "gsr_common.h"
-#include "gsr_launch.h"
+#include "gsr_entry.h"
 
 namespace gsr {
 
 namespace {
 
+constexpr int EXPOSURE_MAX_BLOCKS = 480;      // just under two 256-lane blocks per CU; 30 slots per finish stripe
 constexpr int EXP_THREADS = 256;
 constexpr int EXP_WAVES = EXP_THREADS / WAVE;
 constexpr int EXP_TERMS = 12;                                    // dA[k][c] at 4 k + c, as A is laid out
@@ -121,16 +122,8 @@ int exposure_blocks(size_t pixels) {
   return (int)(b < (size_t)EXPOSURE_MAX_BLOCKS ? (b ? b : 1) : (size_t)EXPOSURE_MAX_BLOCKS);
 }
 
-}  // namespace
-
-size_t exposure_workspace_bytes(size_t pixels) {
-  return align_up((size_t)exposure_blocks(pixels) * EXP_TERMS * sizeof(double), 256);
-}
-
-void launch_exposure_apply_fwd(const float* x, const float* A, size_t pixels, float* y, hipStream_t s) {
-  hipLaunchKernelGGL(exposure_apply_fwd_kernel, dim3(exposure_blocks(pixels)), dim3(EXP_THREADS), 0, s, x, A, pixels, y);
-}
-
+// dx / dA may be nullptr; with dA the backward leaves 12 double sums per block in `workspace` (at most
+// EXPOSURE_MAX_BLOCKS slots) and a one-block kernel behind it adds them in a fixed order
 void launch_exposure_apply_bwd(const float* x, const float* A, const float* g, size_t pixels, float* dx, float* dA,
                                void* workspace, hipStream_t s) {
   const int blocks = exposure_blocks(pixels);
@@ -142,4 +135,38 @@ void launch_exposure_apply_bwd(const float* x, const float* A, const float* g, s
   if (dA) hipLaunchKernelGGL(exposure_grad_finish_kernel, dim3(1), dim3(EXP_FIN_THREADS), 0, s, slots, blocks, dA);
 }
 
+}  // namespace
+
 }  // namespace gsr
+
+// ---- entry points (include/gsr.h) -----------------------------------------------------------------------------------
+using namespace gsr;
+
+extern "C" {
+
+size_t gsr_exposure_workspace_bytes(int32_t H, int32_t W) {
+  if (!image_shape_ok(H, W)) return 0;
+  return align_up((size_t)exposure_blocks((size_t)H * (size_t)W) * EXP_TERMS * sizeof(double), 256);
+}
+int gsr_exposure_apply_fwd(const float* x, const float* A, int32_t H, int32_t W, float* y, void* stream) {
+  if (!x || !A || !y) return fail(GSR_E_BADARG, "NULL argument");
+  if (!image_shape_ok(H, W)) return fail(GSR_E_BADARG, "bad image shape");
+  if (!aligned({x, A, y}, 3u)) return fail(GSR_E_ALIGN, "arrays must be 4-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t pixels = (size_t)H * (size_t)W;
+  hipLaunchKernelGGL(exposure_apply_fwd_kernel, dim3(exposure_blocks(pixels)), dim3(EXP_THREADS), 0, s, x, A, pixels, y);
+  return check(false, s, "exposure_apply_fwd");
+}
+int gsr_exposure_apply_bwd(const float* x, const float* A, const float* g, int32_t H, int32_t W, float* dx, float* dA,
+                           void* workspace, void* stream) {
+  if (!g || (dx && !A) || (dA && (!x || !workspace))) return fail(GSR_E_BADARG, "NULL argument");
+  if (!image_shape_ok(H, W)) return fail(GSR_E_BADARG, "bad image shape");
+  if (!aligned({x, A, g, dx, dA}, 3u)) return fail(GSR_E_ALIGN, "arrays must be 4-byte aligned");
+  if (dA && !aligned({workspace}, 7u)) return fail(GSR_E_ALIGN, "the workspace must be 8-byte aligned");
+  if (!dx && !dA) return 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_exposure_apply_bwd(x, A, g, (size_t)H * (size_t)W, dx, dA, workspace, s);
+  return check(false, s, "exposure_apply_bwd");
+}
+
+}  // extern "C"

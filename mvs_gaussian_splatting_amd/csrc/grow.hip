@@ -13,6 +13,7 @@
 //
 // The per-Gaussian arithmetic keeps the reference's float32 operation order (built with -ffp-contract=off).
 #include "gsr_common.h"
+#include "gsr_entry.h"
 #include "gsr_launch.h"
 #include "grow_common.h"
 
@@ -358,6 +359,11 @@ __global__ __launch_bounds__(GR_BLOCK) void grow_fold_dirs_kernel(GsrGrow g, Gsr
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------
+struct GrowLayout {
+  size_t flags, block_counts, block_offs, totals, bytes;
+  int nblocks;
+  explicit GrowLayout(int P);
+};
 GrowLayout::GrowLayout(int P) {
   nblocks = (P + GR_BLOCK - 1) / GR_BLOCK;
   if (nblocks < 1) nblocks = 1;
@@ -369,8 +375,8 @@ GrowLayout::GrowLayout(int P) {
   bytes = o;
 }
 
-void launch_grow_plan(int P, const float* accum, const float* denom, const float* scaling, float thr, float pde,
-                      int split_mode, void* ws, int32_t* vidx, int32_t* src, uint8_t* selected, hipStream_t s) {
+static void launch_grow_plan(int P, const float* accum, const float* denom, const float* scaling, float thr, float pde,
+                             int split_mode, void* ws, int32_t* vidx, int32_t* src, uint8_t* selected, hipStream_t s) {
   const GrowLayout L(P);
   char* base = static_cast<char*>(ws);
   uint8_t* flags = reinterpret_cast<uint8_t*>(base + L.flags);
@@ -390,7 +396,7 @@ static unsigned row_grid(size_t total) {
   return (unsigned)(b < 1 ? 1 : b);
 }
 
-void launch_grow_expand(const GsrGrow& g, float* const out[6], hipStream_t s) {
+static void launch_grow_expand(const GsrGrow& g, float* const out[6], hipStream_t s) {
   RowArrays a;
   const float* in[6] = {g.xyz, g.f_dc, g.f_rest, g.opacity, g.scaling, g.rotation};
   const int width[6] = {3, 3, g.n_rest, 1, 3, 4};
@@ -411,7 +417,7 @@ void launch_grow_expand(const GsrGrow& g, float* const out[6], hipStream_t s) {
     hipLaunchKernelGGL(grow_expand_split_kernel, dim3((g.G + 255) / 256), dim3(256), 0, s, g, out[0], out[4]);
 }
 
-void launch_grow_fold(const GsrGrow& g, const GsrGrowGrads& d, hipStream_t s) {
+static void launch_grow_fold(const GsrGrow& g, const GsrGrowGrads& d, hipStream_t s) {
   FoldArrays a;
   const int width[7] = {3, 3, 3, g.n_rest, 1, 3, 4};
   size_t widest = 0;
@@ -431,3 +437,87 @@ void launch_grow_fold(const GsrGrow& g, const GsrGrowGrads& d, hipStream_t s) {
 }
 
 }  // namespace gsr
+
+// ---- entry points (include/gsr.h) -----------------------------------------------------------------------------------
+using namespace gsr;
+
+extern "C" {
+
+size_t gsr_grow_workspace_bytes(int32_t P) { return P < 0 ? 0 : GrowLayout(P).bytes; }
+int gsr_grow_plan(int32_t P, const float* xyz_gradient_accum, const float* denom, const float* scaling_raw,
+                  float grad_threshold, float percent_dense_extent, int32_t mode, void* workspace, size_t workspace_bytes,
+                  int32_t* vidx, int32_t* src, uint8_t* selected, uint32_t counts_host[2], void* stream) {
+  if (P < 0) return fail(GSR_E_BADARG, "P < 0");
+  if (!counts_host) return fail(GSR_E_BADARG, "NULL counts_host");
+  counts_host[0] = counts_host[1] = 0;
+  if (P == 0) return 0;
+  if (!xyz_gradient_accum || !denom || !scaling_raw || !workspace || !vidx || !src || !selected)
+    return fail(GSR_E_BADARG, "NULL argument");
+  if (!aligned({workspace}, 255u)) return fail(GSR_E_ALIGN, "workspace must be 256-byte aligned");
+  const GrowLayout L(P);
+  if (workspace_bytes < L.bytes) return fail(GSR_E_CAPACITY, "grow workspace too small");
+  const int grow = (mode & (GSR_GROW_DIR | GSR_GROW_CONTINUOUS)) != 0;
+  if (!grow && !(mode & (GSR_SPLIT_DISTANCE | GSR_SPLIT_SCALE))) return fail(GSR_E_BADARG, "mode selects no branch");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_grow_plan(P, xyz_gradient_accum, denom, scaling_raw, grad_threshold, percent_dense_extent, grow ? 0 : 1,
+                   workspace, vidx, src, selected, s);
+  if (int rc = check(false, s, "grow_plan")) return rc;
+  GSR_HIP(hipMemcpyAsync(counts_host, static_cast<char*>(workspace) + L.totals, 8, hipMemcpyDeviceToHost, s));
+  GSR_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+static int grow_validate(const GsrGrow* g) {
+  if (!g) return fail(GSR_E_BADARG, "NULL GsrGrow");
+  if (g->P < 0 || g->G < 0 || g->G > g->P) return fail(GSR_E_BADARG, "bad P / G");
+  if (g->n_rest != 0 && g->n_rest != 45) return fail(GSR_E_BADARG, "n_rest must be 0 or 45");
+  if (g->P > 0 && (!g->xyz || !g->f_dc || !g->opacity || !g->scaling || !g->rotation || (g->n_rest && !g->f_rest)))
+    return fail(GSR_E_BADARG, "NULL model tensor");
+  const int grow = (g->mode & (GSR_GROW_DIR | GSR_GROW_CONTINUOUS)) != 0;
+  if ((g->mode & GSR_GROW_DIR) && (g->mode & GSR_GROW_CONTINUOUS))
+    return fail(GSR_E_BADARG, "GSR_GROW_DIR and GSR_GROW_CONTINUOUS are exclusive");
+  if (!grow && !(g->mode & (GSR_SPLIT_DISTANCE | GSR_SPLIT_SCALE))) return fail(GSR_E_BADARG, "mode selects no branch");
+  if (g->P == 0) return 0;
+  if (!g->vidx || (g->G > 0 && !g->src)) return fail(GSR_E_BADARG, "NULL vidx / src");
+  if ((g->mode & GSR_GROW_DIR) && (!g->dirs_prob || !g->dirs || g->num_dirs <= 0))
+    return fail(GSR_E_BADARG, "GSR_GROW_DIR needs dirs_prob, dirs and num_dirs > 0");
+  if ((g->mode & GSR_GROW_CONTINUOUS) && !g->conti_dirs) return fail(GSR_E_BADARG, "NULL conti_dirs");
+  if (grow && (g->mode & GSR_GROW_DISTANCE) && !g->grow_dist) return fail(GSR_E_BADARG, "NULL grow_dist");
+  if (!grow && (g->mode & GSR_SPLIT_DISTANCE) && !g->split_distance) return fail(GSR_E_BADARG, "NULL split_distance");
+  if (!grow && (g->mode & GSR_SPLIT_SCALE) && !g->split_scale) return fail(GSR_E_BADARG, "NULL split_scale");
+  if (!grow && !(g->mode & GSR_SPLIT_DISTANCE) && g->G > 0 && !g->noise) return fail(GSR_E_BADARG, "NULL noise");
+  return 0;
+}
+
+int gsr_grow_expand(const GsrGrow* g, float* xyz_out, float* f_dc_out, float* f_rest_out, float* opacity_out,
+                    float* scaling_out, float* rotation_out, void* stream) {
+  if (int rc = grow_validate(g)) return rc;
+  if (g->P == 0) return 0;
+  if (!xyz_out || !f_dc_out || !opacity_out || !scaling_out || !rotation_out || (g->n_rest && !f_rest_out))
+    return fail(GSR_E_BADARG, "NULL output");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  float* const out[6] = {xyz_out, f_dc_out, f_rest_out, opacity_out, scaling_out, rotation_out};
+  launch_grow_expand(*g, out, s);
+  return check(false, s, "grow_expand");
+}
+
+int gsr_grow_fold(const GsrGrow* g, const GsrGrowGrads* grads, void* stream) {
+  if (int rc = grow_validate(g)) return rc;
+  if (!grads) return fail(GSR_E_BADARG, "NULL grads");
+  if (g->P == 0) return 0;
+  for (int k = 0; k < 7; ++k) {
+    if (k == 3 && !g->n_rest) continue;
+    if (!grads->in[k] || !grads->out[k]) return fail(GSR_E_BADARG, "NULL gradient array");
+  }
+  const int grow = (g->mode & (GSR_GROW_DIR | GSR_GROW_CONTINUOUS)) != 0;
+  if (((g->mode & GSR_GROW_DIR) && !grads->d_dirs_prob) || ((g->mode & GSR_GROW_CONTINUOUS) && !grads->d_conti_dirs) ||
+      (grow && (g->mode & GSR_GROW_DISTANCE) && !grads->d_grow_dist) ||
+      (!grow && (g->mode & GSR_SPLIT_DISTANCE) && !grads->d_split_distance) ||
+      (!grow && (g->mode & GSR_SPLIT_SCALE) && !grads->d_split_scale))
+    return fail(GSR_E_BADARG, "NULL gradient of a learned tensor of the mode");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_grow_fold(*g, *grads, s);
+  return check(false, s, "grow_fold");
+}
+
+}  // extern "C"

@@ -1,5 +1,7 @@
-// Host-side launchers, one per kernel; each is defined next to its kernel so that the
-// translation units can be compiled with different floating-point contraction settings.
+// The host-side launchers that cross a file boundary: those gsr_api.hip sequences into a frame (preprocess, binning,
+// render, the maps, launch_unpack_geom) and the few that one kernel file borrows from another (the scan and the pair
+// sort; launch_ssim_metric).  Each is defined next to its kernel, so that the translation units can be compiled with
+// different floating-point contraction settings.  A launcher with one caller in its own file is not declared here.
 #pragma once
 #include "gsr_common.h"
 
@@ -146,177 +148,12 @@ void launch_median_depth_finish(int P, const float* viewmatrix, const float* acc
 // round(w 2^30), pixel count, float bits of the largest w) with integer atomics; pixel_mask: nullptr or [H,W] bytes
 void launch_contribution(const MapFrame& f, const uint8_t* pixel_mask, int64_t* stats, hipStream_t s);
 
-// loss.hip
-void launch_l1_dssim(const float* x, const float* gt, int C, int H, int W, float lambda, int dssim_mode, float* sums,
-                     float* dL_dx, float* maps, hipStream_t s);
-
-// forward-only SSIM of the evaluation path: one partial per 16x16 tile and channel, no derivative maps
+// loss.hip, called by metrics.hip: forward-only SSIM of the evaluation path, one partial per 16x16 tile and channel, no
+// derivative maps
 void launch_ssim_metric(const float* x, const float* gt, int C, int H, int W, int clamp_flags, float* partials,
                         hipStream_t s);
 
-// metrics.hip: gt == nullptr converts only.  workspace: 6 floats per streaming block, then eval_ssim_blocks floats
-constexpr int EVAL_MAX_BLOCKS = 2048;
-size_t eval_ssim_blocks(int H, int W);
-void launch_eval_image(const float* x, const float* gt, int H, int W, int flags, float* view, double* acc, uint8_t* u8,
-                       float* workspace, hipStream_t s);
-
-// splat2d.hip (BASELINE config 1)
-struct Splat2dLayout {
-  size_t rec, flag, pre, gmask, partial, bytes;
-  int chunks, per_chunk;
-  Splat2dLayout(int N, int H, int W);
-};
-int splat2d_max_kernel_size();
-void launch_splat2d_fwd(int N, int K, int H, int W, const float* sx, const float* sy, const float* rho,
-                        const float* coords, const float* colours, const float* ax, void* ws, float* out,
-                        hipStream_t s);
-void launch_splat2d_bwd(int N, int K, int H, int W, const float* sx, const float* sy, const float* rho, const float* ax,
-                        void* ws, const float* dL_dout, float* d_sx, float* d_sy, float* d_rho, float* d_coords,
-                        float* d_colours, hipStream_t s);
-
-// densify.hip.  counts = {kept originals, kept clones, kept children per copy, split-selected}
-struct GrowLayout {
-  size_t flags, block_counts, block_offs, totals, bytes;
-  int nblocks;
-  explicit GrowLayout(int P);
-};
-void launch_grow_plan(int P, const float* accum, const float* denom, const float* scaling, float thr, float pde,
-                      int split_mode, void* ws, int32_t* vidx, int32_t* src, uint8_t* selected, hipStream_t s);
-void launch_grow_expand(const GsrGrow& g, float* const out[6], hipStream_t s);
-void launch_grow_fold(const GsrGrow& g, const GsrGrowGrads& d, hipStream_t s);
-
-struct DensifyLayout {
-  size_t flags, block_counts, block_offs, totals, pos, bytes;
-  int nblocks;
-  explicit DensifyLayout(int P);
-};
-void launch_densify_plan(int P, const float* accum, const float* denom, const float* scaling, const float* opacity,
-                         float thr, float pde, float min_opacity, float ws_limit, int use_ws, void* ws, hipStream_t s);
-void launch_densify_gather_rows(int P, int w, const float* src, const void* ws, const uint32_t counts[4], int zero_new,
-                                float* dst, hipStream_t s);
-void launch_densify_split_children(int P, const float* xyz, const float* scaling, const float* rotation,
-                                   const float* noise, const void* ws, const uint32_t counts[4], float* dst_xyz,
-                                   float* dst_scaling, hipStream_t s);
-
-// densify_fork.hip.  counts = {kept originals, kept clones / grown, kept children per copy, split-selected, selected}
-struct DensifyForkLayout {
-  size_t flags, block_counts, block_offs, totals, pos, sel_src, bytes;
-  int nblocks;
-  explicit DensifyForkLayout(int P);
-};
-void launch_densify_fork_plan(int P, const float* accum, const float* denom, const float* scaling,
-                              const float* opacity, const float* split_scale, float thr, float pde, float min_opacity,
-                              float ws_limit, int use_ws, void* ws, hipStream_t s);
-void launch_densify_fork_gather_rows(int P, int w, const float* src, const void* ws, const uint32_t counts[5],
-                                     int ncopies, int policy, float value, float* dst, hipStream_t s);
-void launch_densify_fork_rows(const GsrDensifyFork& f, const void* ws, const uint32_t counts[5], float* xyz_out,
-                              float* scaling_out, float* conti_out, hipStream_t s);
-
-// adam.hip: one launch over the batch's tensors; returns nonzero (nothing enqueued) if the grid would exceed 2^32
-// work-items
-int launch_adam_step(const GsrAdamBatch& batch, hipStream_t s);
-// the row-masked step; the caller has checked that rows > 0 divides the numel of every non-empty entry
-int launch_adam_step_rows(const GsrAdamRowsBatch& batch, hipStream_t s);
-
-// model.hip: the opacity sparsity term (workspace: OPACITY_MAX_BLOCKS float sums, then as many uint32 counts; record:
-// {float loss, uint32 n, float weight / n, 0}) and the in-place opacity reset (moments may be nullptr)
-constexpr int OPACITY_MAX_BLOCKS = 2048;
-void launch_opacity_sparsity_fwd(const float* raw, size_t P, float weight, float thr, float* record, void* workspace,
-                                 hipStream_t s);
-void launch_opacity_sparsity_bwd(const float* raw, size_t P, float thr, const float* record, const float* grad_out,
-                                 float* grad_raw, hipStream_t s);
-void launch_reset_opacity(float* raw, size_t P, float cap, float* exp_avg, float* exp_avg_sq, hipStream_t s);
-
-// exposure.hip: the per-image 3x4 colour affine on a [3,pixels] image and its gradients.  dx / dA may be nullptr; with
-// dA the backward leaves 12 double sums per block in `workspace` (exposure_workspace_bytes(pixels): at most
-// EXPOSURE_MAX_BLOCKS slots) and a one-block kernel behind it adds them in a fixed order
-constexpr int EXPOSURE_MAX_BLOCKS = 480;      // just under two 256-lane blocks per CU; 30 slots per finish stripe
-size_t exposure_workspace_bytes(size_t pixels);
-void launch_exposure_apply_fwd(const float* x, const float* A, size_t pixels, float* y, hipStream_t s);
-void launch_exposure_apply_bwd(const float* x, const float* A, const float* g, size_t pixels, float* dx, float* dA,
-                               void* workspace, hipStream_t s);
-
-// mcmc.hip: the MCMC strategy's per-Gaussian steps on the RAW tensors (include/gsr.h).  Streaming kernels cap their
-// grid at MCMC_MAX_BLOCKS 256-lane blocks and stride; the priors leave one (sum o, sum s) pair of doubles per block in
-// their workspace; the sampler's workspace holds the int64 prefix sums [P], the scan-block offsets and the total
-constexpr int MCMC_MAX_BLOCKS = 2048;
-size_t mcmc_reg_workspace_bytes();
-size_t mcmc_sample_workspace_bytes(size_t P);
-void launch_mcmc_noise(size_t P, float* xyz, const float* scaling, const float* rotation, const float* opacity,
-                       const float* noise, float step_scale, hipStream_t s);
-void launch_mcmc_reg_fwd(size_t P, const float* opacity, const float* scaling, float opacity_reg, float scale_reg,
-                         float* record, void* workspace, hipStream_t s);
-void launch_mcmc_reg_bwd(size_t P, const float* opacity, const float* scaling, const float* record,
-                         const float* grad_out, float* grad_opacity, float* grad_scaling, hipStream_t s);
-void launch_mcmc_sample(size_t P, const float* opacity, float alive_threshold, const int64_t* draws, size_t n,
-                        int32_t* idx_out, int32_t* count_out, void* workspace, hipStream_t s);
-void launch_mcmc_relocation(size_t n, const int32_t* idx, const int32_t* count, const float* opacity,
-                            const float* scaling, float* new_opacity, float* new_scaling, hipStream_t s);
-
-// image.hip: load-time ingest of uint8 HWC images (one resize pass per call; bounds / taps: include/gsr.h)
-void launch_image_composite_u8(const uint8_t* rgba, size_t pixels, const double bg[3], uint8_t* rgb, hipStream_t s);
-void launch_image_resize_pass(bool vertical, int C, const uint8_t* in, int in_len, int out_len, int other,
-                              const int32_t* bounds, const int32_t* taps, int ksize, uint8_t* out, hipStream_t s);
-void launch_image_to_float_chw(const uint8_t* in, int C, size_t pixels, float* out, hipStream_t s);
-
-// tsdf.hip: depth-map fusion into a dense TSDF volume and marching-tetrahedra extraction (include/gsr.h).  All kernels
-// share one launch shape; tsdf_grid_blocks is false when it would exceed 2^32 work-items (then nothing is launched)
-bool tsdf_grid_blocks(int nx, int ny, int nz, unsigned* xchunks, unsigned* blocks);
-void launch_tsdf_integrate(const GsrTsdfVolume& vol, const GsrTsdfView& view, hipStream_t s);
-void launch_tsdf_mesh_count(const GsrTsdfVolume& vol, float min_weight, uint8_t* tri_count, uint8_t* edge_mask,
-                            uint8_t* vert_count, hipStream_t s);
-void launch_tsdf_mesh_emit(const GsrTsdfVolume& vol, const uint8_t* tri_count, const uint8_t* edge_mask,
-                           const int64_t* vert_offs, const int64_t* tri_offs, int64_t V, int64_t F, float* vertices,
-                           float* vcolors, int32_t* faces, hipStream_t s);
-
-// mesh.hip: connected components of an indexed triangle mesh by a lock-free union-find, and the compaction that keeps
-// a subset of its faces (include/gsr.h).  One lane per node / face / key / vertex, 256-lane workgroups; the entry points
-// have checked every size (1 .. 2^31 - 1) and pointer
-void launch_mesh_cc_init(int64_t n, int32_t* parent, int32_t* first, hipStream_t s);
-void launch_mesh_cc_hook_faces(const int32_t* faces, int64_t F, int64_t V, int32_t* parent, int32_t* status,
-                               uint64_t* stats, hipStream_t s);
-void launch_mesh_edge_keys(const int32_t* faces, int64_t F, int64_t V, int64_t* keys, int32_t* owner, int32_t* status,
-                           hipStream_t s);
-void launch_mesh_cc_hook_runs(const int64_t* keys, const int64_t* order, const int32_t* owner, int64_t m, int64_t n,
-                              int32_t* parent, int32_t* status, uint64_t* stats, hipStream_t s);
-void launch_mesh_cc_flatten(int64_t n, int32_t* parent, hipStream_t s);
-void launch_mesh_cc_mark(const int32_t* faces, int64_t F, int64_t V, const int32_t* parent, int32_t* first,
-                         int32_t* face_root, uint8_t* mark, hipStream_t s);
-void launch_mesh_cc_label(const int32_t* face_root, const int64_t* ids, int64_t F, int64_t K, int32_t* face_component,
-                          int64_t* component_faces, hipStream_t s);
-void launch_mesh_mark_vertices(const int32_t* faces, const uint8_t* keep, int64_t F, int64_t V, uint8_t* vertex_mark,
-                               int32_t* status, hipStream_t s);
-void launch_mesh_compact(const float* vertices, const float* colors, const int32_t* faces, const uint8_t* keep,
-                         const uint8_t* vertex_mark, const int64_t* vert_offs, const int64_t* face_offs, int64_t V,
-                         int64_t F, int64_t Vk, int64_t Fk, float* out_vertices, float* out_colors, int32_t* out_faces,
-                         int32_t* status, hipStream_t s);
-
-// normal_consistency.hip: the depth-normal consistency loss of a rendered frame, value and unit gradients in one launch
-// plus a one-block finish (include/gsr.h).  The three gradient pointers are all set or all nullptr (forward only);
-// depth_normal may be nullptr.  normal_consistency_blocks is false when the launch would exceed 2^32 work-items
-bool normal_consistency_blocks(int H, int W, unsigned* xtiles, unsigned* blocks);
-size_t normal_consistency_workspace_bytes(int H, int W);
-void launch_normal_consistency(const float* depth, const float* alpha, const float* normal, int H, int W, float fx,
-                               float fy, float alpha_min, float* record, float* dL_ddepth, float* dL_dalpha,
-                               float* dL_dnormal, float* depth_normal, void* workspace, hipStream_t s);
-
-// knn.hip
-size_t knn_workspace_bytes(int N);
-void launch_knn3(const float* pts, int N, float* mean_dist2, void* ws, hipStream_t s);
-// nearest.hip
-size_t nn_index_bytes(int R);
-size_t nn_query_workspace_bytes(int Q);
-void launch_nn_build(const float* ref, int R, void* index, hipStream_t s);
-void launch_nn_query(const void* index, int R, const float* query, int Q, float* dist2, int32_t* nearest, void* ws,
-                     hipStream_t s);
-
-// aux.hip
-size_t l1_loss_workspace_bytes();
-void launch_l1_loss(const float* x, const float* gt, size_t n, float scale, float* loss_sum, float* dL_dx,
-                    float* partials, hipStream_t s);
-void launch_densify_stats(int P, const float* dL_dmeans2D, const int32_t* radii, float* accum, float* denom,
-                          float* max_radii2D, hipStream_t s);
-void launch_mark_visible(int P, const float* means3D, const float* viewmatrix, uint8_t* visible, hipStream_t s);
+// aux.hip: the unpack kernel behind gsr_debug_read_geom
 void launch_unpack_geom(int P, const GeomRec* rec, const BinInfo* bin, const uint32_t* block_offs, float* xy,
                         float* conic_opacity, float* rgb, float* depth, uint32_t* tiles, uint32_t* point_offsets,
                         uint32_t* rect, uint32_t* clamped, hipStream_t s);

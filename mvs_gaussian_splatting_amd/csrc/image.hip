@@ -12,7 +12,7 @@
 // operation is rounded on its own, as numpy and torch do on the host.  One thread per output pixel; every kernel is a
 // stream of bytes in and out, bound by memory.
 #include "gsr_common.h"
-#include "gsr_launch.h"
+#include "gsr_entry.h"
 
 namespace gsr {
 
@@ -111,21 +111,72 @@ void resize_pass(bool vertical, const uint8_t* in, int in_len, int out_len, int 
     resize_pass_kernel<C, false><<<blocks_for(n), IMG_THREADS, 0, s>>>(in, in_len, out_len, other, bounds, taps, ksize, out);
 }
 
-}  // namespace
-
-void launch_image_composite_u8(const uint8_t* rgba, size_t pixels, const double bg[3], uint8_t* rgb, hipStream_t s) {
-  composite_u8_kernel<<<blocks_for(pixels), IMG_THREADS, 0, s>>>(rgba, pixels, bg[0], bg[1], bg[2], rgb);
-}
-
+// one resize pass per call; bounds / taps: include/gsr.h
 void launch_image_resize_pass(bool vertical, int C, const uint8_t* in, int in_len, int out_len, int other,
                               const int32_t* bounds, const int32_t* taps, int ksize, uint8_t* out, hipStream_t s) {
   if (C == 3) resize_pass<3>(vertical, in, in_len, out_len, other, bounds, taps, ksize, out, s);
   else resize_pass<1>(vertical, in, in_len, out_len, other, bounds, taps, ksize, out, s);
 }
 
-void launch_image_to_float_chw(const uint8_t* in, int C, size_t pixels, float* out, hipStream_t s) {
-  if (C == 4) to_float_chw_kernel<4><<<blocks_for(pixels), IMG_THREADS, 0, s>>>(in, pixels, out);
-  else to_float_chw_kernel<3><<<blocks_for(pixels), IMG_THREADS, 0, s>>>(in, pixels, out);
-}
+}  // namespace
 
 }  // namespace gsr
+
+// ---- entry points (include/gsr.h) -----------------------------------------------------------------------------------
+using namespace gsr;
+
+extern "C" {
+
+int gsr_image_composite_u8(const uint8_t* rgba, int32_t H, int32_t W, double bg_r, double bg_g, double bg_b,
+                           uint8_t* rgb, void* stream) {
+  if (!rgba || !rgb) return fail(GSR_E_BADARG, "NULL image");
+  if (!image_shape_ok(H, W)) return fail(GSR_E_BADARG, "bad image shape");
+  const double bg[3] = {bg_r, bg_g, bg_b};
+  for (double b : bg)
+    if (!(b >= 0.0 && b <= 1.0)) return fail(GSR_E_BADARG, "background must lie in [0, 1]");
+  if (!aligned({rgba}, 3u)) return fail(GSR_E_ALIGN, "the RGBA image must be 4-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t pixels = (size_t)H * (size_t)W;
+  composite_u8_kernel<<<blocks_for(pixels), IMG_THREADS, 0, s>>>(rgba, pixels, bg_r, bg_g, bg_b, rgb);
+  return check(false, s, "image_composite_u8");
+}
+int gsr_image_resize_u8(const uint8_t* src, int32_t C, int32_t in_h, int32_t in_w, int32_t out_h, int32_t out_w,
+                        const int32_t* h_bounds, const int32_t* h_taps, int32_t h_ksize, const int32_t* v_bounds,
+                        const int32_t* v_taps, int32_t v_ksize, uint8_t* tmp, uint8_t* dst, void* stream) {
+  if (!src || !dst) return fail(GSR_E_BADARG, "NULL image");
+  if (C != 1 && C != 3) return fail(GSR_E_BADARG, "resize takes 1 or 3 channels");
+  if (!image_shape_ok(in_h, in_w) || !image_shape_ok(out_h, out_w) || !image_shape_ok(in_h, out_w))
+    return fail(GSR_E_BADARG, "bad image shape");
+  const bool horiz = out_w != in_w, vert = out_h != in_h;
+  if (horiz && (!h_bounds || !h_taps || h_ksize <= 0)) return fail(GSR_E_BADARG, "horizontal pass needs its tap table");
+  if (vert && (!v_bounds || !v_taps || v_ksize <= 0)) return fail(GSR_E_BADARG, "vertical pass needs its tap table");
+  if (horiz && vert && !tmp) return fail(GSR_E_BADARG, "two passes need the intermediate image");
+  if (!aligned({h_bounds, h_taps, v_bounds, v_taps}, 3u)) return fail(GSR_E_ALIGN, "tap tables must be 4-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (!horiz && !vert) {
+    GSR_HIP(hipMemcpyAsync(dst, src, (size_t)in_h * (size_t)in_w * (size_t)C, hipMemcpyDeviceToDevice, s));
+    return 0;
+  }
+  const uint8_t* mid = src;
+  if (horiz) {
+    uint8_t* out = vert ? tmp : dst;
+    launch_image_resize_pass(false, C, src, in_w, out_w, in_h, h_bounds, h_taps, h_ksize, out, s);
+    mid = out;
+  }
+  if (vert) launch_image_resize_pass(true, C, mid, in_h, out_h, out_w, v_bounds, v_taps, v_ksize, dst, s);
+  return check(false, s, "image_resize_u8");
+}
+int gsr_image_to_float_chw(const uint8_t* src, int32_t C, int32_t H, int32_t W, float* dst, void* stream) {
+  if (!src || !dst) return fail(GSR_E_BADARG, "NULL image");
+  if (C != 3 && C != 4) return fail(GSR_E_BADARG, "the float target needs a 3- or 4-channel image");
+  if (!image_shape_ok(H, W)) return fail(GSR_E_BADARG, "bad image shape");
+  if (!aligned({dst}, 3u) || (C == 4 && !aligned({src}, 3u)))
+    return fail(GSR_E_ALIGN, "the float image and a 4-channel source must be 4-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t pixels = (size_t)H * (size_t)W;
+  if (C == 4) to_float_chw_kernel<4><<<blocks_for(pixels), IMG_THREADS, 0, s>>>(src, pixels, dst);
+  else to_float_chw_kernel<3><<<blocks_for(pixels), IMG_THREADS, 0, s>>>(src, pixels, dst);
+  return check(false, s, "image_to_float_chw");
+}
+
+}  // extern "C"

@@ -10,6 +10,7 @@
 #include <float.h>
 
 #include "gsr_common.h"
+#include "gsr_entry.h"
 #include "gsr_launch.h"
 #include "knn_index.h"
 
@@ -152,8 +153,6 @@ __global__ __launch_bounds__(256) void knn_query_kernel(int N, int nboxes, int n
   mean_dist2[__float_as_uint(me.w)] = (best[0] + best[1] + best[2]) / 3.0f;
 }
 
-size_t knn_workspace_bytes(int N) { return KnnLayout(N).bytes; }
-
 // The index build (knn_index.h): what distCUDA2 and the cross-set query of nearest.hip share.
 void launch_knn_build(const float* pts, int N, void* index, hipStream_t s) {
   const KnnLayout L(N);
@@ -179,8 +178,7 @@ void launch_knn_build(const float* pts, int N, void* index, hipStream_t s) {
   hipLaunchKernelGGL(knn_super_kernel, dim3(L.nsuper), dim3(KNN_SUPER), 0, s, L.nboxes, box_lo, box_hi, sup_lo, sup_hi);
 }
 
-void launch_knn3(const float* pts, int N, float* mean_dist2, void* ws, hipStream_t s) {
-  if (N <= 0) return;
+static void launch_knn3(const float* pts, int N, float* mean_dist2, void* ws, hipStream_t s) {
   const KnnLayout L(N);
   const char* b = static_cast<const char*>(ws);
   launch_knn_build(pts, N, ws, s);
@@ -191,3 +189,23 @@ void launch_knn3(const float* pts, int N, float* mean_dist2, void* ws, hipStream
 }
 
 }  // namespace gsr
+
+// ---- entry points (include/gsr.h) -----------------------------------------------------------------------------------
+using namespace gsr;
+
+extern "C" {
+
+size_t gsr_knn3_workspace_bytes(int32_t N) { return KnnLayout(N).bytes; }
+int gsr_dist2_knn3(const float* points, int32_t N, float* mean_dist2, void* workspace, size_t workspace_bytes,
+                   void* stream) {
+  if (N < 0) return fail(GSR_E_BADARG, "N < 0");
+  if (N == 0) return 0;
+  if (!points || !mean_dist2 || !workspace) return fail(GSR_E_BADARG, "NULL argument");
+  if (workspace_bytes < KnnLayout(N).bytes) return fail(GSR_E_CAPACITY, "knn workspace too small");
+  if (!aligned({workspace}, 255u)) return fail(GSR_E_ALIGN, "workspace must be 256-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_knn3(points, N, mean_dist2, workspace, s);
+  return check(false, s, "knn3");
+}
+
+}  // extern "C"

@@ -8,6 +8,7 @@
 //             A = dL/dmu1, B = dL/dE[x^2], Cm = dL/dE[xy]  (the loss depends on x only through them)
 //   backward: dL/dx = w * A + 2 x (w * B) + y (w * Cm) + (1-lambda) sign(x-y)/n      (w symmetric)
 #include "gsr_common.h"
+#include "gsr_entry.h"
 #include "gsr_launch.h"
 
 namespace gsr {
@@ -194,8 +195,8 @@ static Win11 make_window() {
   return win;
 }
 
-void launch_l1_dssim(const float* x, const float* gt, int C, int H, int W, float lambda, int dssim_mode, float* sums,
-                     float* dL_dx, float* maps, hipStream_t s) {
+static void launch_l1_dssim(const float* x, const float* gt, int C, int H, int W, float lambda, int dssim_mode,
+                            float* sums, float* dL_dx, float* maps, hipStream_t s) {
   const Win11 win = make_window();
   const dim3 grid((W + SS_T - 1) / SS_T, (H + SS_T - 1) / SS_T, C);
   const float inv_n = 1.0f / ((float)C * (float)H * (float)W);
@@ -217,3 +218,26 @@ void launch_ssim_metric(const float* x, const float* gt, int C, int H, int W, in
 }
 
 }  // namespace gsr
+
+// ---- entry points (include/gsr.h) -----------------------------------------------------------------------------------
+using namespace gsr;
+
+extern "C" {
+
+size_t gsr_l1_dssim_workspace_bytes(int32_t C, int32_t H, int32_t W) {
+  if (C <= 0 || H <= 0 || W <= 0) return 0;
+  const size_t blocks = (size_t)((W + 15) / 16) * (size_t)((H + 15) / 16) * (size_t)C;      // 16x16 output tiles
+  return sizeof(float) * (3 * (size_t)C * (size_t)H * (size_t)W + 2 * blocks);
+}
+int gsr_l1_dssim_loss_fwd_bwd(const float* x, const float* gt, int32_t C, int32_t H, int32_t W, float lambda_dssim,
+                              int32_t dssim_mode, float* sums, float* dL_dx, void* workspace, void* stream) {
+  if (!x || !gt || !sums || !dL_dx || !workspace) return fail(GSR_E_BADARG, "NULL argument");
+  if (C <= 0 || H <= 0 || W <= 0 || C > 65535) return fail(GSR_E_BADARG, "bad image shape");
+  if (dssim_mode != GSR_DSSIM_ONE_MINUS_MEAN && dssim_mode != GSR_DSSIM_CLAMPED_HALF)
+    return fail(GSR_E_BADARG, "unknown dssim_mode");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_l1_dssim(x, gt, C, H, W, lambda_dssim, dssim_mode, sums, dL_dx, static_cast<float*>(workspace), s);
+  return check(false, s, "l1_dssim");
+}
+
+}  // extern "C"

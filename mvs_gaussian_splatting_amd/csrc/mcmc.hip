@@ -23,12 +23,13 @@
 //
 // Built with -ffp-contract=off: the noise step's order above is the contract.
 #include "gsr_common.h"
-#include "gsr_launch.h"
+#include "gsr_entry.h"
 
 namespace gsr {
 
 namespace {
 
+constexpr int MCMC_MAX_BLOCKS = 2048;                                // streaming kernels cap their grid here and stride
 constexpr int MC_THREADS = 256;
 constexpr int MC_WAVES = MC_THREADS / WAVE;
 constexpr int MC_RELOC_THREADS = 64;
@@ -304,18 +305,12 @@ __global__ __launch_bounds__(MC_RELOC_THREADS) void mcmc_relocation_kernel(size_
 
 size_t scan_blocks(size_t P) { return (P + MC_SCAN_BLOCK - 1) / MC_SCAN_BLOCK; }
 
-}  // namespace
-
+// the priors leave one (sum o, sum s) pair of doubles per block in their workspace
 size_t mcmc_reg_workspace_bytes() { return (size_t)MCMC_MAX_BLOCKS * 2 * sizeof(double); }
 
+// the sampler's workspace: the int64 prefix sums [P], then the scan-block offsets and the total
 size_t mcmc_sample_workspace_bytes(size_t P) {
   return align_up(P * sizeof(long long), 256) + align_up((scan_blocks(P) + 1) * sizeof(long long), 256);
-}
-
-void launch_mcmc_noise(size_t P, float* xyz, const float* scaling, const float* rotation, const float* opacity,
-                       const float* noise, float step_scale, hipStream_t s) {
-  hipLaunchKernelGGL(mcmc_noise_kernel, dim3(capped_blocks(P, MC_THREADS, MCMC_MAX_BLOCKS)), dim3(MC_THREADS), 0, s, P,
-                     xyz, scaling, reinterpret_cast<const float4*>(rotation), opacity, noise, step_scale);
 }
 
 void launch_mcmc_reg_fwd(size_t P, const float* opacity, const float* scaling, float opacity_reg, float scale_reg,
@@ -325,12 +320,6 @@ void launch_mcmc_reg_fwd(size_t P, const float* opacity, const float* scaling, f
   hipLaunchKernelGGL(mcmc_reg_kernel, dim3(blocks), dim3(MC_THREADS), 0, s, P, opacity, scaling, slots);
   hipLaunchKernelGGL(mcmc_reg_finish_kernel, dim3(1), dim3(MC_THREADS), 0, s, slots, blocks, (double)P, opacity_reg,
                      scale_reg, record);
-}
-
-void launch_mcmc_reg_bwd(size_t P, const float* opacity, const float* scaling, const float* record,
-                         const float* grad_out, float* grad_opacity, float* grad_scaling, hipStream_t s) {
-  hipLaunchKernelGGL(mcmc_reg_bwd_kernel, dim3(capped_blocks(P, MC_THREADS, MCMC_MAX_BLOCKS)), dim3(MC_THREADS), 0, s, P,
-                     opacity, scaling, record, grad_out, grad_opacity, grad_scaling);
 }
 
 void launch_mcmc_sample(size_t P, const float* opacity, float alive_threshold, const int64_t* draws, size_t n,
@@ -348,11 +337,84 @@ void launch_mcmc_sample(size_t P, const float* opacity, float alive_threshold, c
                        C, sums + nb, reinterpret_cast<const long long*>(draws), n, idx_out, count_out);
 }
 
-void launch_mcmc_relocation(size_t n, const int32_t* idx, const int32_t* count, const float* opacity,
-                            const float* scaling, float* new_opacity, float* new_scaling, hipStream_t s) {
-  const size_t blocks = (n + MC_RELOC_THREADS - 1) / MC_RELOC_THREADS;
-  hipLaunchKernelGGL(mcmc_relocation_kernel, dim3((unsigned)blocks), dim3(MC_RELOC_THREADS), 0, s, n, idx, count, opacity,
-                     scaling, new_opacity, new_scaling);
-}
+}  // namespace
 
 }  // namespace gsr
+
+// ---- entry points (include/gsr.h) -----------------------------------------------------------------------------------
+using namespace gsr;
+
+extern "C" {
+
+static int mcmc_rows_ok(int64_t P) { return P >= 0 && P <= (int64_t)INT32_MAX; }
+int gsr_mcmc_noise(int64_t P, float* xyz, const float* scaling_raw, const float* rotation_raw, const float* opacity_raw,
+                   const float* noise, float step_scale, void* stream) {
+  if (!mcmc_rows_ok(P)) return fail(GSR_E_BADARG, "P must lie in 0..2^31-1");
+  if (P > 0 && (!xyz || !scaling_raw || !rotation_raw || !opacity_raw || !noise)) return fail(GSR_E_BADARG, "NULL argument");
+  if (!aligned({xyz, scaling_raw, opacity_raw, noise}, 3u) || !aligned({rotation_raw}, 15u))
+    return fail(GSR_E_ALIGN, "arrays must be 4-byte aligned, rotations 16-byte aligned");
+  if (P == 0) return 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(mcmc_noise_kernel, dim3(capped_blocks((size_t)P, MC_THREADS, MCMC_MAX_BLOCKS)), dim3(MC_THREADS), 0, s,
+                     (size_t)P, xyz, scaling_raw, reinterpret_cast<const float4*>(rotation_raw), opacity_raw, noise,
+                     step_scale);
+  return check(false, s, "mcmc_noise");
+}
+size_t gsr_mcmc_reg_workspace_bytes(void) { return mcmc_reg_workspace_bytes(); }
+int gsr_mcmc_reg_fwd(const float* opacity_raw, const float* scaling_raw, int64_t P, float opacity_reg, float scale_reg,
+                     float* record, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!mcmc_rows_ok(P)) return fail(GSR_E_BADARG, "P must lie in 0..2^31-1");
+  if (!record || !workspace || (P > 0 && (!opacity_raw || !scaling_raw))) return fail(GSR_E_BADARG, "NULL argument");
+  if (workspace_bytes < mcmc_reg_workspace_bytes()) return fail(GSR_E_BADARG, "workspace smaller than gsr_mcmc_reg_workspace_bytes()");
+  if (!aligned({opacity_raw, scaling_raw}, 3u) || !aligned({workspace}, 7u) || !aligned({record}, 15u))
+    return fail(GSR_E_ALIGN, "arrays must be 4-byte, the workspace 8-byte and the record 16-byte aligned");
+  if (P == 0) return 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_mcmc_reg_fwd((size_t)P, opacity_raw, scaling_raw, opacity_reg, scale_reg, record, workspace, s);
+  return check(false, s, "mcmc_reg_fwd");
+}
+int gsr_mcmc_reg_bwd(const float* opacity_raw, const float* scaling_raw, int64_t P, const float* record,
+                     const float* grad_out, float* grad_opacity, float* grad_scaling, void* stream) {
+  if (!mcmc_rows_ok(P)) return fail(GSR_E_BADARG, "P must lie in 0..2^31-1");
+  if (!record || !grad_out || (P > 0 && (!opacity_raw || !scaling_raw || !grad_opacity || !grad_scaling)))
+    return fail(GSR_E_BADARG, "NULL argument");
+  if (!aligned({opacity_raw, scaling_raw, record, grad_out, grad_opacity, grad_scaling}, 3u))
+    return fail(GSR_E_ALIGN, "arrays must be 4-byte aligned");
+  if (P == 0) return 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(mcmc_reg_bwd_kernel, dim3(capped_blocks((size_t)P, MC_THREADS, MCMC_MAX_BLOCKS)), dim3(MC_THREADS), 0,
+                     s, (size_t)P, opacity_raw, scaling_raw, record, grad_out, grad_opacity, grad_scaling);
+  return check(false, s, "mcmc_reg_bwd");
+}
+size_t gsr_mcmc_sample_workspace_bytes(int64_t P) { return mcmc_rows_ok(P) ? mcmc_sample_workspace_bytes((size_t)P) : 0; }
+int gsr_mcmc_sample(int64_t P, const float* opacity_raw, float alive_threshold, const int64_t* draws, int64_t n,
+                    int32_t* idx_out, int32_t* count_out, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!mcmc_rows_ok(P) || !mcmc_rows_ok(n)) return fail(GSR_E_BADARG, "P and n must lie in 0..2^31-1");
+  if ((P > 0 && (!opacity_raw || !count_out || !workspace)) || (n > 0 && (!draws || !idx_out)))
+    return fail(GSR_E_BADARG, "NULL argument");
+  if (n > 0 && P == 0) return fail(GSR_E_BADARG, "samples asked of an empty model");
+  if (P > 0 && workspace_bytes < mcmc_sample_workspace_bytes((size_t)P))
+    return fail(GSR_E_BADARG, "workspace smaller than gsr_mcmc_sample_workspace_bytes(P)");
+  if (!aligned({opacity_raw, idx_out, count_out}, 3u) || !aligned({draws, workspace}, 7u))
+    return fail(GSR_E_ALIGN, "float / int32 arrays must be 4-byte, draws and workspace 8-byte aligned");
+  if (P == 0) return 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_mcmc_sample((size_t)P, opacity_raw, alive_threshold, draws, (size_t)n, idx_out, count_out, workspace, s);
+  return check(false, s, "mcmc_sample");
+}
+int gsr_mcmc_relocation(int64_t n, const int32_t* idx, const int32_t* count, const float* opacity_raw,
+                        const float* scaling_raw, float* new_opacity_raw, float* new_scaling_raw, void* stream) {
+  if (!mcmc_rows_ok(n)) return fail(GSR_E_BADARG, "n must lie in 0..2^31-1");
+  if (n > 0 && (!idx || !count || !opacity_raw || !scaling_raw || !new_opacity_raw || !new_scaling_raw))
+    return fail(GSR_E_BADARG, "NULL argument");
+  if (!aligned({idx, count, opacity_raw, scaling_raw, new_opacity_raw, new_scaling_raw}, 3u))
+    return fail(GSR_E_ALIGN, "arrays must be 4-byte aligned");
+  if (n == 0) return 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t blocks = ((size_t)n + MC_RELOC_THREADS - 1) / MC_RELOC_THREADS;
+  hipLaunchKernelGGL(mcmc_relocation_kernel, dim3((unsigned)blocks), dim3(MC_RELOC_THREADS), 0, s, (size_t)n, idx, count,
+                     opacity_raw, scaling_raw, new_opacity_raw, new_scaling_raw);
+  return check(false, s, "mcmc_relocation");
+}
+
+}  // extern "C"

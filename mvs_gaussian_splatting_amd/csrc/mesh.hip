@@ -43,7 +43,7 @@
 //
 // A face index outside 0..V-1 is never used as an index: the face is skipped and *status is set to 1.
 #include "gsr_common.h"
-#include "gsr_launch.h"
+#include "gsr_entry.h"
 
 namespace gsr {
 
@@ -289,38 +289,77 @@ __global__ void __launch_bounds__(MESH_BLOCK) mesh_compact_kernel(const float* v
 }
 
 inline dim3 mesh_grid(int64_t n) { return dim3((unsigned)((n + MESH_BLOCK - 1) / MESH_BLOCK)); }
+inline bool mesh_size_ok(int64_t n) { return n >= 1 && n <= (int64_t)INT32_MAX; }
 
 }  // namespace
 
-void launch_mesh_cc_init(int64_t n, int32_t* parent, int32_t* first, hipStream_t s) {
-  hipLaunchKernelGGL(mesh_init_kernel, mesh_grid(n), dim3(MESH_BLOCK), 0, s, n, parent, first);
-}
+}  // namespace gsr
 
-void launch_mesh_cc_hook_faces(const int32_t* faces, int64_t F, int64_t V, int32_t* parent, int32_t* status,
-                               uint64_t* stats, hipStream_t s) {
+// ---- entry points (include/gsr.h): every size is checked to lie in 1 .. 2^31 - 1, every pointer for NULL and alignment
+using namespace gsr;
+
+extern "C" {
+
+int gsr_mesh_cc_init(int64_t n, int32_t* parent, int32_t* first, void* stream) {
+  if (!mesh_size_ok(n)) return fail(GSR_E_BADARG, "n must lie in 1..2^31-1");
+  if (!parent) return fail(GSR_E_BADARG, "parent is NULL");
+  if (!aligned({parent, first}, 3u)) return fail(GSR_E_ALIGN, "parent / first must be 4-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(mesh_init_kernel, mesh_grid(n), dim3(MESH_BLOCK), 0, s, n, parent, first);
+  return check(false, s, "mesh_cc_init");
+}
+int gsr_mesh_cc_hook_faces(const int32_t* faces, int64_t F, int64_t V, int32_t* parent, int32_t* status, uint64_t* stats,
+                           void* stream) {
+  if (!mesh_size_ok(F) || !mesh_size_ok(V)) return fail(GSR_E_BADARG, "F and V must lie in 1..2^31-1");
+  if (!faces || !parent || !status) return fail(GSR_E_BADARG, "NULL argument");
+  if (!aligned({faces, parent, status}, 3u)) return fail(GSR_E_ALIGN, "faces / parent / status must be 4-byte aligned");
+  if (!aligned({stats}, 7u)) return fail(GSR_E_ALIGN, "stats must be 8-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(mesh_hook_faces_kernel, mesh_grid(F), dim3(MESH_BLOCK), 0, s, faces, F, (uint32_t)V, parent, status,
                      reinterpret_cast<unsigned long long*>(stats));
+  return check(false, s, "mesh_cc_hook_faces");
 }
-
-void launch_mesh_edge_keys(const int32_t* faces, int64_t F, int64_t V, int64_t* keys, int32_t* owner, int32_t* status,
-                           hipStream_t s) {
+int gsr_mesh_edge_keys(const int32_t* faces, int64_t F, int64_t V, int64_t* keys, int32_t* owner, int32_t* status,
+                       void* stream) {
+  if (!mesh_size_ok(F) || !mesh_size_ok(V)) return fail(GSR_E_BADARG, "F and V must lie in 1..2^31-1");
+  if (!faces || !keys || !owner || !status) return fail(GSR_E_BADARG, "NULL argument");
+  if (!aligned({faces, owner, status}, 3u)) return fail(GSR_E_ALIGN, "faces / owner / status must be 4-byte aligned");
+  if (!aligned({keys}, 7u)) return fail(GSR_E_ALIGN, "keys must be 8-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(mesh_edge_keys_kernel, mesh_grid(F), dim3(MESH_BLOCK), 0, s, faces, F, (uint32_t)V, keys, owner,
                      status);
+  return check(false, s, "mesh_edge_keys");
 }
-
-void launch_mesh_cc_hook_runs(const int64_t* keys, const int64_t* order, const int32_t* owner, int64_t m, int64_t n,
-                              int32_t* parent, int32_t* status, uint64_t* stats, hipStream_t s) {
-  if (m < 2) return;
-  hipLaunchKernelGGL(mesh_hook_runs_kernel, mesh_grid(m - 1), dim3(MESH_BLOCK), 0, s, keys, order, owner, m, (uint32_t)n,
-                     parent, status, reinterpret_cast<unsigned long long*>(stats));
+int gsr_mesh_cc_hook_runs(const int64_t* keys_sorted, const int64_t* order, const int32_t* owner, int64_t m, int64_t n,
+                          int32_t* parent, int32_t* status, uint64_t* stats, void* stream) {
+  if (m < 1 || m > 3 * (int64_t)INT32_MAX || !mesh_size_ok(n))
+    return fail(GSR_E_BADARG, "n must lie in 1..2^31-1 and m in 1..3 (2^31-1)");
+  if (!keys_sorted || !order || !owner || !parent || !status) return fail(GSR_E_BADARG, "NULL argument");
+  if (!aligned({owner, parent, status}, 3u)) return fail(GSR_E_ALIGN, "owner / parent / status must be 4-byte aligned");
+  if (!aligned({keys_sorted, order, stats}, 7u)) return fail(GSR_E_ALIGN, "keys / order / stats must be 8-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (m >= 2)       // one lane per pair of neighbouring keys
+    hipLaunchKernelGGL(mesh_hook_runs_kernel, mesh_grid(m - 1), dim3(MESH_BLOCK), 0, s, keys_sorted, order, owner, m,
+                       (uint32_t)n, parent, status, reinterpret_cast<unsigned long long*>(stats));
+  return check(false, s, "mesh_cc_hook_runs");
 }
-
-void launch_mesh_cc_flatten(int64_t n, int32_t* parent, hipStream_t s) {
+int gsr_mesh_cc_flatten(int64_t n, int32_t* parent, void* stream) {
+  if (!mesh_size_ok(n)) return fail(GSR_E_BADARG, "n must lie in 1..2^31-1");
+  if (!parent) return fail(GSR_E_BADARG, "parent is NULL");
+  if (!aligned({parent}, 3u)) return fail(GSR_E_ALIGN, "parent must be 4-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(mesh_flatten_kernel, mesh_grid(n), dim3(MESH_BLOCK), 0, s, n, parent);
+  return check(false, s, "mesh_cc_flatten");
 }
-
-void launch_mesh_cc_mark(const int32_t* faces, int64_t F, int64_t V, const int32_t* parent, int32_t* first,
-                         int32_t* face_root, uint8_t* mark, hipStream_t s) {
+int gsr_mesh_cc_mark(const int32_t* faces, int64_t F, int64_t V, const int32_t* parent, int32_t* first,
+                     int32_t* face_root, uint8_t* mark, void* stream) {
+  if (!mesh_size_ok(F)) return fail(GSR_E_BADARG, "F must lie in 1..2^31-1");
+  if (!parent || !mark) return fail(GSR_E_BADARG, "NULL argument");
+  const int given = (faces != nullptr) + (first != nullptr) + (face_root != nullptr);
+  if (given != 0 && given != 3) return fail(GSR_E_BADARG, "give faces, first and face_root together (vertex nodes) or none");
+  if (given == 3 && !mesh_size_ok(V)) return fail(GSR_E_BADARG, "V must lie in 1..2^31-1");
+  if (!aligned({faces, parent, first, face_root}, 3u)) return fail(GSR_E_ALIGN, "int32 arrays must be 4-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
   if (faces) {
     hipLaunchKernelGGL(mesh_face_min_kernel, mesh_grid(F), dim3(MESH_BLOCK), 0, s, faces, F, (uint32_t)V, parent, first);
     hipLaunchKernelGGL(mesh_mark_kernel<true>, mesh_grid(F), dim3(MESH_BLOCK), 0, s, faces, F, (uint32_t)V, parent, first,
@@ -329,26 +368,45 @@ void launch_mesh_cc_mark(const int32_t* faces, int64_t F, int64_t V, const int32
     hipLaunchKernelGGL(mesh_mark_kernel<false>, mesh_grid(F), dim3(MESH_BLOCK), 0, s, faces, F, 0u, parent, first,
                        face_root, mark);
   }
+  return check(false, s, "mesh_cc_mark");
 }
-
-void launch_mesh_cc_label(const int32_t* face_root, const int64_t* ids, int64_t F, int64_t K, int32_t* face_component,
-                          int64_t* component_faces, hipStream_t s) {
+int gsr_mesh_cc_label(const int32_t* face_root, const int64_t* ids, int64_t F, int64_t K, int32_t* face_component,
+                      int64_t* component_faces, void* stream) {
+  if (!mesh_size_ok(F) || K < 1 || K > F) return fail(GSR_E_BADARG, "F must lie in 1..2^31-1 and K in 1..F");
+  if (!face_root || !ids || !face_component || !component_faces) return fail(GSR_E_BADARG, "NULL argument");
+  if (!aligned({face_root, face_component}, 3u)) return fail(GSR_E_ALIGN, "int32 arrays must be 4-byte aligned");
+  if (!aligned({ids, component_faces}, 7u)) return fail(GSR_E_ALIGN, "int64 arrays must be 8-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(mesh_label_kernel, mesh_grid(F), dim3(MESH_BLOCK), 0, s, face_root, ids, F, K, face_component,
                      reinterpret_cast<unsigned long long*>(component_faces));
+  return check(false, s, "mesh_cc_label");
 }
-
-void launch_mesh_mark_vertices(const int32_t* faces, const uint8_t* keep, int64_t F, int64_t V, uint8_t* vertex_mark,
-                               int32_t* status, hipStream_t s) {
+int gsr_mesh_mark_vertices(const int32_t* faces, const uint8_t* keep, int64_t F, int64_t V, uint8_t* vertex_mark,
+                           int32_t* status, void* stream) {
+  if (!mesh_size_ok(F) || !mesh_size_ok(V)) return fail(GSR_E_BADARG, "F and V must lie in 1..2^31-1");
+  if (!faces || !keep || !vertex_mark || !status) return fail(GSR_E_BADARG, "NULL argument");
+  if (!aligned({faces, status}, 3u)) return fail(GSR_E_ALIGN, "faces / status must be 4-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(mesh_mark_vertices_kernel, mesh_grid(F), dim3(MESH_BLOCK), 0, s, faces, keep, F, (uint32_t)V,
                      vertex_mark, status);
+  return check(false, s, "mesh_mark_vertices");
 }
-
-void launch_mesh_compact(const float* vertices, const float* colors, const int32_t* faces, const uint8_t* keep,
-                         const uint8_t* vertex_mark, const int64_t* vert_offs, const int64_t* face_offs, int64_t V,
-                         int64_t F, int64_t Vk, int64_t Fk, float* out_vertices, float* out_colors, int32_t* out_faces,
-                         int32_t* status, hipStream_t s) {
+int gsr_mesh_compact(const float* vertices, const float* colors, const int32_t* faces, const uint8_t* keep,
+                     const uint8_t* vertex_mark, const int64_t* vert_offs, const int64_t* face_offs, int64_t V, int64_t F,
+                     int64_t Vk, int64_t Fk, float* out_vertices, float* out_colors, int32_t* out_faces, int32_t* status,
+                     void* stream) {
+  if (!mesh_size_ok(F) || !mesh_size_ok(V)) return fail(GSR_E_BADARG, "F and V must lie in 1..2^31-1");
+  if (Vk < 1 || Vk > V || Fk < 1 || Fk > F) return fail(GSR_E_BADARG, "Vk must lie in 1..V and Fk in 1..F");
+  if (!vertices || !faces || !keep || !vertex_mark || !vert_offs || !face_offs || !out_vertices || !out_faces || !status)
+    return fail(GSR_E_BADARG, "NULL argument");
+  if ((colors != nullptr) != (out_colors != nullptr)) return fail(GSR_E_BADARG, "give colors and out_colors together or neither");
+  if (!aligned({vertices, colors, faces, out_vertices, out_colors, out_faces, status}, 3u))
+    return fail(GSR_E_ALIGN, "float and int32 arrays must be 4-byte aligned");
+  if (!aligned({vert_offs, face_offs}, 7u)) return fail(GSR_E_ALIGN, "offsets must be 8-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(mesh_compact_kernel, mesh_grid(V > F ? V : F), dim3(MESH_BLOCK), 0, s, vertices, colors, faces, keep,
                      vertex_mark, vert_offs, face_offs, V, F, Vk, Fk, out_vertices, out_colors, out_faces, status);
+  return check(false, s, "mesh_compact");
 }
 
-}  // namespace gsr
+}  // extern "C"

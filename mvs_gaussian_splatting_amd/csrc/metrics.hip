@@ -6,10 +6,12 @@
 // views needs one read-back.
 // Built with -ffp-contract=off: the byte image is torch's clamp, mul, (add,) truncate, each rounded on its own.
 #include "gsr_common.h"
+#include "gsr_entry.h"
 #include "gsr_launch.h"
 
 namespace gsr {
 
+constexpr int EVAL_MAX_BLOCKS = 2048;      // the streaming grid's cap: the workspace holds 6 floats for each
 constexpr int EV_THREADS = 256;
 constexpr int EV_WAVES = EV_THREADS / WAVE;
 constexpr int FIN_THREADS = 512;      // one block; the double-precision log10 wants more than 128 registers
@@ -156,10 +158,11 @@ static int eval_blocks(size_t hw, bool vec) {
   return (int)(b < (size_t)EVAL_MAX_BLOCKS ? (b ? b : 1) : (size_t)EVAL_MAX_BLOCKS);
 }
 
-size_t eval_ssim_blocks(int H, int W) { return (size_t)((W + 15) / 16) * (size_t)((H + 15) / 16) * 3; }
+static size_t eval_ssim_blocks(int H, int W) { return (size_t)((W + 15) / 16) * (size_t)((H + 15) / 16) * 3; }
 
-void launch_eval_image(const float* x, const float* gt, int H, int W, int flags, float* view, double* acc, uint8_t* u8,
-                       float* workspace, hipStream_t s) {
+// gt == nullptr converts only.  workspace: 6 floats per streaming block, then eval_ssim_blocks floats
+static void launch_eval_image(const float* x, const float* gt, int H, int W, int flags, float* view, double* acc,
+                              uint8_t* u8, float* workspace, hipStream_t s) {
   const size_t hw = (size_t)H * W;
   const bool vec = hw % 4 == 0 && (((uintptr_t)x | (uintptr_t)gt) & 15u) == 0 && ((uintptr_t)u8 & 3u) == 0;
   const int blocks = eval_blocks(hw, vec);
@@ -178,3 +181,41 @@ void launch_eval_image(const float* x, const float* gt, int H, int W, int flags,
 }
 
 }  // namespace gsr
+
+// ---- entry points (include/gsr.h) -----------------------------------------------------------------------------------
+using namespace gsr;
+
+extern "C" {
+
+static const int32_t kEvalFlags = GSR_EVAL_CLAMP_X | GSR_EVAL_CLAMP_GT | GSR_EVAL_SSIM | GSR_EVAL_PSNR_WHOLE |
+                                  GSR_EVAL_U8_TRUNCATE;
+size_t gsr_eval_workspace_bytes(int32_t C, int32_t H, int32_t W, int32_t flags) {
+  if (C != 3 || H <= 0 || W <= 0 || (flags & ~kEvalFlags)) return 0;
+  return sizeof(float) * (6 * (size_t)EVAL_MAX_BLOCKS + ((flags & GSR_EVAL_SSIM) ? eval_ssim_blocks(H, W) : 0));
+}
+int gsr_eval_image(const float* x, const float* gt, int32_t C, int32_t H, int32_t W, int32_t flags, float* view_out,
+                   double* acc, uint8_t* u8_out, void* workspace, void* stream) {
+  if (!x || !gt) return fail(GSR_E_BADARG, "NULL image");
+  if (!workspace) return fail(GSR_E_BADARG, "NULL workspace");
+  if (!view_out && !acc && !u8_out) return fail(GSR_E_BADARG, "no output: view_out, acc and u8_out are all NULL");
+  if (H <= 0 || W <= 0) return fail(GSR_E_BADARG, "bad image shape");
+  if (C != 3) return fail(GSR_E_BADARG, "evaluation needs a 3-channel image");
+  if (flags & ~kEvalFlags) return fail(GSR_E_BADARG, "unknown evaluation flag bits");
+  if (!aligned({x, gt, view_out, workspace}, 3u) || !aligned({acc}, 7u))
+    return fail(GSR_E_ALIGN, "images, view_out and workspace must be 4-byte aligned, acc 8-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_eval_image(x, gt, H, W, flags, view_out, acc, u8_out, static_cast<float*>(workspace), s);
+  return check(false, s, "eval_image");
+}
+int gsr_image_to_u8(const float* x, int32_t C, int32_t H, int32_t W, int32_t flags, uint8_t* u8_out, void* stream) {
+  if (!x || !u8_out) return fail(GSR_E_BADARG, "NULL image");
+  if (H <= 0 || W <= 0) return fail(GSR_E_BADARG, "bad image shape");
+  if (C != 3) return fail(GSR_E_BADARG, "the 8-bit output needs a 3-channel image");
+  if (flags & ~GSR_EVAL_U8_TRUNCATE) return fail(GSR_E_BADARG, "unknown conversion flag bits");
+  if (!aligned({x}, 3u)) return fail(GSR_E_ALIGN, "image must be 4-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_eval_image(x, nullptr, H, W, flags, nullptr, nullptr, u8_out, nullptr, s);
+  return check(false, s, "image_to_u8");
+}
+
+}  // extern "C"

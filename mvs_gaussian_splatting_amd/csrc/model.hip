@@ -10,12 +10,13 @@
 //
 // Built with -ffp-contract=off: sigmoid, min, sub, div, log are torch's ops, each rounded to float32 on its own.
 #include "gsr_common.h"
-#include "gsr_launch.h"
+#include "gsr_entry.h"
 
 namespace gsr {
 
 namespace {
 
+constexpr int OPACITY_MAX_BLOCKS = 2048;      // the streaming grid's cap: one float sum and one uint32 count for each
 constexpr int OS_THREADS = 256;
 constexpr int OS_WAVES = OS_THREADS / WAVE;
 constexpr int OS_FIN_THREADS = 256;
@@ -179,8 +180,7 @@ int stream_blocks(size_t P, bool vec) {
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
-}  // namespace
-
+// record: {float loss, uint32 n, float weight / n, 0}
 void launch_opacity_sparsity_fwd(const float* raw, size_t P, float weight, float thr, float* record, void* workspace,
                                  hipStream_t s) {
   float* part_sum = static_cast<float*>(workspace);              // [OPACITY_MAX_BLOCKS] sums, then as many counts
@@ -208,4 +208,45 @@ void launch_reset_opacity(float* raw, size_t P, float cap, float* exp_avg, float
   else hipLaunchKernelGGL((reset_opacity_kernel<false>), dim3(blocks), dim3(OS_THREADS), 0, s, raw, P, cap, exp_avg, exp_avg_sq);
 }
 
+}  // namespace
+
 }  // namespace gsr
+
+// ---- entry points (include/gsr.h) -----------------------------------------------------------------------------------
+using namespace gsr;
+
+extern "C" {
+
+size_t gsr_opacity_sparsity_workspace_bytes(void) { return (size_t)OPACITY_MAX_BLOCKS * (sizeof(float) + sizeof(uint32_t)); }
+int gsr_opacity_sparsity_fwd(const float* opacity_raw, int64_t P, float weight, float threshold, float* record,
+                             void* workspace, void* stream) {
+  if (P < 0) return fail(GSR_E_BADARG, "negative P");
+  if (!record || !workspace || (P > 0 && !opacity_raw)) return fail(GSR_E_BADARG, "NULL argument");
+  if (!aligned({opacity_raw, workspace}, 3u) || !aligned({record}, 15u))
+    return fail(GSR_E_ALIGN, "opacity and workspace must be 4-byte aligned, the record 16-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_opacity_sparsity_fwd(opacity_raw, (size_t)P, weight, threshold, record, workspace, s);
+  return check(false, s, "opacity_sparsity_fwd");
+}
+int gsr_opacity_sparsity_bwd(const float* opacity_raw, int64_t P, float threshold, const float* record,
+                             const float* grad_out, float* grad_raw, void* stream) {
+  if (P < 0) return fail(GSR_E_BADARG, "negative P");
+  if (!record || !grad_out || (P > 0 && (!opacity_raw || !grad_raw))) return fail(GSR_E_BADARG, "NULL argument");
+  if (!aligned({opacity_raw, grad_raw, record, grad_out}, 3u)) return fail(GSR_E_ALIGN, "arrays must be 4-byte aligned");
+  if (P == 0) return 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_opacity_sparsity_bwd(opacity_raw, (size_t)P, threshold, record, grad_out, grad_raw, s);
+  return check(false, s, "opacity_sparsity_bwd");
+}
+int gsr_reset_opacity(float* opacity_raw, int64_t P, float cap, float* exp_avg, float* exp_avg_sq, void* stream) {
+  if (P < 0) return fail(GSR_E_BADARG, "negative P");
+  if (P > 0 && !opacity_raw) return fail(GSR_E_BADARG, "NULL opacity");
+  if (!(cap > 0.0f && cap < 1.0f)) return fail(GSR_E_BADARG, "cap must lie in (0, 1)");
+  if (!aligned({opacity_raw, exp_avg, exp_avg_sq}, 3u)) return fail(GSR_E_ALIGN, "arrays must be 4-byte aligned");
+  if (P == 0) return 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_reset_opacity(opacity_raw, (size_t)P, cap, exp_avg, exp_avg_sq, s);
+  return check(false, s, "reset_opacity");
+}
+
+}  // extern "C"

@@ -27,12 +27,13 @@
 // Safety.  Every loop is bounded at launch: 32 search steps, nsuper, KNN_INDEX_SUPER, KNN_INDEX_BOX.  No lane waits
 // on another lane, wave or workgroup.  A query index read from the sorted values is checked against Q before use;
 // the search position is clamped to 0..R-1; box and point indices are formed from loop counters clamped to nboxes
-// and R.  R and Q are at most GSR_NN_MAX_POINTS = 2^31 - 256 (gsr_api.hip refuses more), so first + KNN_INDEX_BOX
+// and R.  R and Q are at most GSR_NN_MAX_POINTS = 2^31 - 256 (the entry points below refuse more), so first + KNN_INDEX_BOX
 // and the index of the last workgroup's last lane stay inside int.  NaN / Inf coordinates give an unspecified value
 // (a NaN distance compares false and is never kept) and change no bound.
 #include <float.h>
 
 #include "gsr_common.h"
+#include "gsr_entry.h"
 #include "gsr_launch.h"
 #include "knn_index.h"
 
@@ -51,9 +52,6 @@ struct NnQueryLayout {
     bytes = o;
   }
 };
-
-size_t nn_index_bytes(int R) { return KnnLayout(R).bytes; }
-size_t nn_query_workspace_bytes(int Q) { return NnQueryLayout(Q).bytes; }
 
 __global__ __launch_bounds__(256) void nn_morton_kernel(const float* __restrict__ query, int Q,
                                                         const unsigned* __restrict__ mm, uint32_t* __restrict__ keys,
@@ -124,14 +122,8 @@ __global__ __launch_bounds__(256) void nn_query_kernel(int R, int Q, int nboxes,
   nearest[qi] = (int32_t)bi;
 }
 
-void launch_nn_build(const float* ref, int R, void* index, hipStream_t s) {
-  if (R <= 0) return;
-  launch_knn_build(ref, R, index, s);
-}
-
-void launch_nn_query(const void* index, int R, const float* query, int Q, float* dist2, int32_t* nearest, void* ws,
-                     hipStream_t s) {
-  if (Q <= 0) return;
+static void launch_nn_query(const void* index, int R, const float* query, int Q, float* dist2, int32_t* nearest, void* ws,
+                            hipStream_t s) {
   const int nb = (Q + 255) / 256;
   if (R <= 0) {
     hipLaunchKernelGGL(nn_empty_kernel, dim3(nb), dim3(256), 0, s, Q, dist2, nearest);
@@ -155,3 +147,41 @@ void launch_nn_query(const void* index, int R, const float* query, int Q, float*
 }
 
 }  // namespace gsr
+
+// ---- entry points (include/gsr.h) -----------------------------------------------------------------------------------
+using namespace gsr;
+
+extern "C" {
+
+size_t gsr_nn_index_bytes(int32_t R) { return KnnLayout(R).bytes; }
+size_t gsr_nn_query_workspace_bytes(int32_t Q) { return NnQueryLayout(Q).bytes; }
+int gsr_nn_build(const float* ref, int32_t R, void* index, size_t index_bytes, void* stream) {
+  if (R < 0 || R > GSR_NN_MAX_POINTS) return fail(GSR_E_BADARG, "R must lie in 0..2^31-256");
+  if (R == 0) return 0;
+  if (!ref || !index) return fail(GSR_E_BADARG, "NULL argument");
+  if (index_bytes < KnnLayout(R).bytes) return fail(GSR_E_CAPACITY, "nn index too small");
+  if (!aligned({index}, 255u)) return fail(GSR_E_ALIGN, "index must be 256-byte aligned");
+  if (!aligned({ref}, 3u)) return fail(GSR_E_ALIGN, "ref must be 4-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_knn_build(ref, R, index, s);
+  return check(false, s, "nn_build");
+}
+int gsr_nn_query(const void* index, size_t index_bytes, int32_t R, const float* query, int32_t Q, float* dist2,
+                 int32_t* nearest, void* workspace, size_t workspace_bytes, void* stream) {
+  if (R < 0 || Q < 0 || R > GSR_NN_MAX_POINTS || Q > GSR_NN_MAX_POINTS)
+    return fail(GSR_E_BADARG, "R and Q must lie in 0..2^31-256");
+  if (Q == 0) return 0;
+  if (!query || !dist2 || !nearest) return fail(GSR_E_BADARG, "NULL argument");
+  if (!aligned({query, dist2, nearest}, 3u)) return fail(GSR_E_ALIGN, "query / dist2 / nearest must be 4-byte aligned");
+  if (R > 0) {
+    if (!index || !workspace) return fail(GSR_E_BADARG, "NULL index / workspace");
+    if (index_bytes < KnnLayout(R).bytes) return fail(GSR_E_CAPACITY, "nn index too small");
+    if (workspace_bytes < NnQueryLayout(Q).bytes) return fail(GSR_E_CAPACITY, "nn query workspace too small");
+    if (!aligned({index, workspace}, 255u)) return fail(GSR_E_ALIGN, "index / workspace must be 256-byte aligned");
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_nn_query(index, R, query, Q, dist2, nearest, workspace, s);
+  return check(false, s, "nn_query");
+}
+
+}  // extern "C"

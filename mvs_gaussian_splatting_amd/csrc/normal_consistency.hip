@@ -24,7 +24,7 @@
 // The loss: e in double, a fixed butterfly per wave, the four waves in order, one (double sum, uint32 count) pair per
 // workgroup in the workspace; a one-block kernel behind it adds the pairs in a fixed order and writes the record.
 #include "gsr_common.h"
-#include "gsr_launch.h"
+#include "gsr_entry.h"
 
 namespace gsr {
 
@@ -223,8 +223,7 @@ __global__ __launch_bounds__(NC_FIN_THREADS) void normal_consistency_finish_kern
   record[3] = 0.0f;
 }
 
-}  // namespace
-
+// false when the launch would exceed 2^32 work-items
 bool normal_consistency_blocks(int H, int W, unsigned* xtiles, unsigned* blocks) {
   if (H < 1 || W < 1) return false;
   const unsigned long long xt = ((unsigned long long)W + NC_T - 1) / NC_T, yt = ((unsigned long long)H + NC_T - 1) / NC_T;
@@ -234,12 +233,7 @@ bool normal_consistency_blocks(int H, int W, unsigned* xtiles, unsigned* blocks)
   return true;
 }
 
-size_t normal_consistency_workspace_bytes(int H, int W) {
-  unsigned xtiles, blocks;
-  if (!normal_consistency_blocks(H, W, &xtiles, &blocks)) return 0;
-  return (size_t)blocks * (sizeof(double) + sizeof(uint32_t));
-}
-
+// The three gradient pointers are all set or all nullptr (forward only); depth_normal may be nullptr
 void launch_normal_consistency(const float* depth, const float* alpha, const float* normal, int H, int W, float fx,
                                float fy, float alpha_min, float* record, float* dL_ddepth, float* dL_dalpha,
                                float* dL_dnormal, float* depth_normal, void* workspace, hipStream_t s) {
@@ -261,4 +255,44 @@ void launch_normal_consistency(const float* depth, const float* alpha, const flo
                      inv_hw, record);
 }
 
+}  // namespace
+
 }  // namespace gsr
+
+// ---- entry points (include/gsr.h) -----------------------------------------------------------------------------------
+using namespace gsr;
+
+extern "C" {
+
+size_t gsr_normal_consistency_workspace_bytes(int32_t H, int32_t W) {
+  unsigned xtiles, blocks;
+  if (!image_shape_ok(H, W) || !normal_consistency_blocks(H, W, &xtiles, &blocks)) return 0;
+  return (size_t)blocks * (sizeof(double) + sizeof(uint32_t));
+}
+int gsr_normal_consistency_fwd_bwd(const float* depth, const float* alpha, const float* normal, int32_t H, int32_t W,
+                                   float tanfovx, float tanfovy, float alpha_min, float* record, float* dL_ddepth,
+                                   float* dL_dalpha, float* dL_dnormal, float* depth_normal, void* workspace,
+                                   void* stream) {
+  unsigned xtiles, blocks;
+  if (!image_shape_ok(H, W) || !normal_consistency_blocks(H, W, &xtiles, &blocks))
+    return fail(GSR_E_BADARG, "bad image shape");
+  if (!(tanfovx > 0.0f) || !(tanfovy > 0.0f) || tanfovx > 3.0e38f || tanfovy > 3.0e38f)
+    return fail(GSR_E_BADARG, "tanfovx and tanfovy must be positive and finite");
+  if (!(alpha_min > 0.0f) || !(alpha_min <= 1.0f)) return fail(GSR_E_BADARG, "alpha_min must lie in (0, 1]");
+  if (!depth || !alpha || !normal || !record || !workspace) return fail(GSR_E_BADARG, "NULL argument");
+  const int ngrad = (dL_ddepth != nullptr) + (dL_dalpha != nullptr) + (dL_dnormal != nullptr);
+  if (ngrad != 0 && ngrad != 3) return fail(GSR_E_BADARG, "give all three gradient pointers or none");
+  if (!aligned({depth, alpha, normal, dL_ddepth, dL_dalpha, dL_dnormal, depth_normal}, 3u))
+    return fail(GSR_E_ALIGN, "maps must be 4-byte aligned");
+  if (!aligned({record}, 15u)) return fail(GSR_E_ALIGN, "the record must be 16-byte aligned");
+  if (!aligned({workspace}, 7u)) return fail(GSR_E_ALIGN, "the workspace must be 8-byte aligned");
+  // each focal length is one double division and one cast: nothing for -ffp-contract to fuse, so this file's flags
+  // give the bits the default flags gave
+  const float fx = (float)((double)W / (2.0 * (double)tanfovx)), fy = (float)((double)H / (2.0 * (double)tanfovy));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_normal_consistency(depth, alpha, normal, H, W, fx, fy, alpha_min, record, dL_ddepth, dL_dalpha, dL_dnormal,
+                            depth_normal, workspace, s);
+  return check(false, s, "normal_consistency_fwd_bwd");
+}
+
+}  // extern "C"

@@ -12,7 +12,7 @@
 //   forward : 16 x 16 pixel tiles x Gaussian chunks -> partial images (deterministic), then a chunk sum + clamp
 //   backward: one 256-lane block per Gaussian over its support rectangle, block-reduced -- no atomics
 #include "gsr_common.h"
-#include "gsr_launch.h"
+#include "gsr_entry.h"
 
 namespace gsr {
 
@@ -241,6 +241,11 @@ __global__ __launch_bounds__(256) void splat2d_bwd_kernel(int N, int K, int H, i
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------
+struct Splat2dLayout {
+  size_t rec, flag, pre, gmask, partial, bytes;
+  int chunks, per_chunk;
+  Splat2dLayout(int N, int H, int W);
+};
 Splat2dLayout::Splat2dLayout(int N, int H, int W) {
   const size_t plane3 = 3 * (size_t)H * W;
   const int pix_blocks = ((W + S2_TILE - 1) / S2_TILE) * ((H + S2_TILE - 1) / S2_TILE);
@@ -260,9 +265,9 @@ Splat2dLayout::Splat2dLayout(int N, int H, int W) {
   bytes = o;
 }
 
-void launch_splat2d_fwd(int N, int K, int H, int W, const float* sx, const float* sy, const float* rho,
-                        const float* coords, const float* colours, const float* ax, void* ws, float* out,
-                        hipStream_t s) {
+static void launch_splat2d_fwd(int N, int K, int H, int W, const float* sx, const float* sy, const float* rho,
+                               const float* coords, const float* colours, const float* ax, void* ws, float* out,
+                               hipStream_t s) {
   const Splat2dLayout L(N, H, W);
   char* base = static_cast<char*>(ws);
   Splat2dRec* rec = reinterpret_cast<Splat2dRec*>(base + L.rec);
@@ -280,9 +285,9 @@ void launch_splat2d_fwd(int N, int K, int H, int W, const float* sx, const float
                      pre, out);
 }
 
-void launch_splat2d_bwd(int N, int K, int H, int W, const float* sx, const float* sy, const float* rho, const float* ax,
-                        void* ws, const float* dL_dout, float* d_sx, float* d_sy, float* d_rho, float* d_coords,
-                        float* d_colours, hipStream_t s) {
+static void launch_splat2d_bwd(int N, int K, int H, int W, const float* sx, const float* sy, const float* rho,
+                               const float* ax, void* ws, const float* dL_dout, float* d_sx, float* d_sy, float* d_rho,
+                               float* d_coords, float* d_colours, hipStream_t s) {
   const Splat2dLayout L(N, H, W);
   char* base = static_cast<char*>(ws);
   const Splat2dRec* rec = reinterpret_cast<const Splat2dRec*>(base + L.rec);
@@ -295,6 +300,54 @@ void launch_splat2d_bwd(int N, int K, int H, int W, const float* sx, const float
                        d_rho, d_coords, d_colours);
 }
 
-int splat2d_max_kernel_size() { return S2_MAX_K; }
-
 }  // namespace gsr
+
+// ---- entry points (include/gsr.h) -----------------------------------------------------------------------------------
+using namespace gsr;
+
+extern "C" {
+
+size_t gsr_splat2d_workspace_bytes(int32_t N, int32_t H, int32_t W) {
+  return (N < 0 || H <= 0 || W <= 0) ? 0 : Splat2dLayout(N, H, W).bytes;
+}
+static int splat2d_validate(int32_t N, int32_t K, int32_t H, int32_t W, const void* ws, size_t ws_bytes) {
+  if (N < 0 || H <= 0 || W <= 0 || K <= 0) return fail(GSR_E_BADARG, "bad N / K / image size");
+  if (K > H || K > W) return fail(GSR_E_BADARG, "Kernel size should be smaller or equal to the image size.");
+  if (K > S2_MAX_K) return fail(GSR_E_BADARG, "kernel size above 2048");
+  if (!ws) return fail(GSR_E_BADARG, "NULL workspace");
+  if (!aligned({ws}, 255u)) return fail(GSR_E_ALIGN, "workspace must be 256-byte aligned");
+  if (ws_bytes < Splat2dLayout(N, H, W).bytes) return fail(GSR_E_CAPACITY, "splat2d workspace too small");
+  return 0;
+}
+int gsr_splat2d_forward(int32_t N, int32_t K, int32_t H, int32_t W, const float* sigma_x, const float* sigma_y,
+                        const float* rho, const float* coords, const float* colours, const float* ax, void* workspace,
+                        size_t workspace_bytes, float* out, int32_t* not_pd_host, void* stream) {
+  if (int rc = splat2d_validate(N, K, H, W, workspace, workspace_bytes)) return rc;
+  if (!out || !ax) return fail(GSR_E_BADARG, "NULL argument");
+  if (N > 0 && (!sigma_x || !sigma_y || !rho || !coords || !colours)) return fail(GSR_E_BADARG, "NULL input");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_splat2d_fwd(N, K, H, W, sigma_x, sigma_y, rho, coords, colours, ax, workspace, out, s);
+  if (int rc = check(false, s, "splat2d_forward")) return rc;
+  if (not_pd_host) {
+    int flag = 0;
+    GSR_HIP(hipMemcpyAsync(&flag, static_cast<char*>(workspace) + Splat2dLayout(N, H, W).flag, 4, hipMemcpyDeviceToHost, s));
+    GSR_HIP(hipStreamSynchronize(s));
+    *not_pd_host = flag;
+  }
+  return 0;
+}
+int gsr_splat2d_backward(int32_t N, int32_t K, int32_t H, int32_t W, const float* sigma_x, const float* sigma_y,
+                         const float* rho, const float* ax, void* workspace, size_t workspace_bytes,
+                         const float* dL_dout, float* dL_dsigma_x, float* dL_dsigma_y, float* dL_drho,
+                         float* dL_dcoords, float* dL_dcolours, void* stream) {
+  if (int rc = splat2d_validate(N, K, H, W, workspace, workspace_bytes)) return rc;
+  if (!dL_dout || !ax) return fail(GSR_E_BADARG, "NULL argument");
+  if (N > 0 && (!sigma_x || !sigma_y || !rho || !dL_dsigma_x || !dL_dsigma_y || !dL_drho || !dL_dcoords || !dL_dcolours))
+    return fail(GSR_E_BADARG, "NULL input / gradient");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_splat2d_bwd(N, K, H, W, sigma_x, sigma_y, rho, ax, workspace, dL_dout, dL_dsigma_x, dL_dsigma_y, dL_drho,
+                     dL_dcoords, dL_dcolours, s);
+  return check(false, s, "splat2d_backward");
+}
+
+}  // extern "C"

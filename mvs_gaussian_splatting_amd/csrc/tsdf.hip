@@ -42,7 +42,7 @@
 //   * tsdf_emit_faces_kernel: the triangles of cube, tetrahedron, case order at tri_offset[cube], each corner the index
 //     of its edge's vertex.  Plain stores to slots fixed by the scans: the same bits from run to run.
 #include "gsr_common.h"
-#include "gsr_launch.h"
+#include "gsr_entry.h"
 
 namespace gsr {
 
@@ -266,8 +266,7 @@ __global__ __launch_bounds__(TSDF_X* TSDF_ROWS) void tsdf_emit_faces_kernel(GsrT
   }
 }
 
-}  // namespace
-
+// All kernels share one launch shape; false when it would exceed 2^32 work-items (then nothing is launched)
 bool tsdf_grid_blocks(int nx, int ny, int nz, unsigned* xchunks, unsigned* blocks) {
   const unsigned long long xc = ((unsigned long long)nx + TSDF_X - 1) / TSDF_X;
   const unsigned long long rb = ((unsigned long long)ny * (unsigned long long)nz + TSDF_ROWS - 1) / TSDF_ROWS;
@@ -307,4 +306,67 @@ void launch_tsdf_mesh_emit(const GsrTsdfVolume& vol, const uint8_t* tri_count, c
                      F, faces);
 }
 
+}  // namespace
+
 }  // namespace gsr
+
+// ---- entry points (include/gsr.h) -----------------------------------------------------------------------------------
+using namespace gsr;
+
+extern "C" {
+
+static int tsdf_volume_ok(const GsrTsdfVolume* v) {
+  if (!v) return fail(GSR_E_BADARG, "volume is NULL");
+  if (v->nx <= 0 || v->ny <= 0 || v->nz <= 0) return fail(GSR_E_BADARG, "volume dims must be positive");
+  // 32-bit indices with seven edge slots per grid point: never wrap
+  if ((unsigned long long)v->nx * (unsigned long long)v->ny >= (1ull << 31) ||
+      7ull * (unsigned long long)v->nx * (unsigned long long)v->ny * (unsigned long long)v->nz >= (1ull << 31))
+    return fail(GSR_E_BADARG, "volume too large: 7 * nx * ny * nz must stay below 2^31");
+  unsigned xchunks, blocks;
+  if (!tsdf_grid_blocks(v->nx, v->ny, v->nz, &xchunks, &blocks))
+    return fail(GSR_E_BADARG, "volume shape needs a launch of 2^32 work-items or more");
+  if (!(v->voxel_size > 0.0f) || !(v->sdf_trunc > 0.0f)) return fail(GSR_E_BADARG, "voxel_size and sdf_trunc must be positive");
+  if (!v->tsdf || !v->weight) return fail(GSR_E_BADARG, "tsdf / weight is NULL");
+  if (!aligned({v->tsdf, v->weight, v->color}, 3u)) return fail(GSR_E_ALIGN, "volume fields must be 4-byte aligned");
+  return 0;
+}
+int gsr_tsdf_integrate(const GsrTsdfVolume* vol, const GsrTsdfView* view, void* stream) {
+  if (int rc = tsdf_volume_ok(vol)) return rc;
+  if (!view) return fail(GSR_E_BADARG, "view is NULL");
+  if (!image_shape_ok(view->height, view->width)) return fail(GSR_E_BADARG, "bad image shape");
+  if (!view->viewmatrix || !view->depth) return fail(GSR_E_BADARG, "viewmatrix / depth is NULL");
+  if ((vol->color != nullptr) != (view->color != nullptr))
+    return fail(GSR_E_BADARG, "a colour image is given exactly when the volume has a colour field");
+  if (!(view->fx > 0.0f) || !(view->fy > 0.0f) || !(view->weight > 0.0f) || !(view->max_depth > 0.0f) ||
+      !(view->max_weight > 0.0f))
+    return fail(GSR_E_BADARG, "fx, fy, weight, max_depth and max_weight must be positive (+inf: no limit)");
+  if (!aligned({view->viewmatrix, view->depth, view->color}, 3u)) return fail(GSR_E_ALIGN, "view arrays must be 4-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_tsdf_integrate(*vol, *view, s);
+  return check(false, s, "tsdf_integrate");
+}
+int gsr_tsdf_mesh_count(const GsrTsdfVolume* vol, float min_weight, uint8_t* tri_count, uint8_t* edge_mask,
+                        uint8_t* vert_count, void* stream) {
+  if (int rc = tsdf_volume_ok(vol)) return rc;
+  if (!tri_count || !edge_mask || !vert_count) return fail(GSR_E_BADARG, "NULL argument");
+  if (min_weight != min_weight) return fail(GSR_E_BADARG, "min_weight is NaN");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_tsdf_mesh_count(*vol, min_weight, tri_count, edge_mask, vert_count, s);
+  return check(false, s, "tsdf_mesh_count");
+}
+int gsr_tsdf_mesh_emit(const GsrTsdfVolume* vol, const uint8_t* tri_count, const uint8_t* edge_mask,
+                       const int64_t* vert_offs, const int64_t* tri_offs, int64_t V, int64_t F, float* vertices,
+                       float* vcolors, int32_t* faces, void* stream) {
+  if (int rc = tsdf_volume_ok(vol)) return rc;
+  if (!tri_count || !edge_mask || !vert_offs || !tri_offs || !vertices || !faces) return fail(GSR_E_BADARG, "NULL argument");
+  if (vcolors && !vol->color) return fail(GSR_E_BADARG, "vertex colours need a volume with a colour field");
+  const int64_t N = (int64_t)vol->nx * vol->ny * vol->nz;
+  if (V <= 0 || F <= 0 || V > 7 * N || F > 12 * N) return fail(GSR_E_BADARG, "V must lie in 1..7 N and F in 1..12 N");
+  if (!aligned({vert_offs, tri_offs}, 7u)) return fail(GSR_E_ALIGN, "offsets must be 8-byte aligned");
+  if (!aligned({vertices, vcolors, faces}, 3u)) return fail(GSR_E_ALIGN, "outputs must be 4-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_tsdf_mesh_emit(*vol, tri_count, edge_mask, vert_offs, tri_offs, V, F, vertices, vcolors, faces, s);
+  return check(false, s, "tsdf_mesh_emit");
+}
+
+}  // extern "C"

@@ -36,7 +36,9 @@ def test_entry_points_are_exported_and_the_three_abi_numbers_agree():
 def test_the_makefile_builds_the_unit_without_contraction():
     mk = open(os.path.join(ROOT, "mvs_gaussian_splatting_amd", "csrc", "Makefile")).read()
     assert re.search(r"^OBJS = .*\bexposure\.o\b", mk, re.M)
-    assert re.search(r"^exposure\.o:.*\n\t.*\$\(CONTRACT_OFF\)", mk, re.M)
+    assert re.search(r"^CONTRACT_OFF_OBJS :?\+?= *exposure\.o\b", mk, re.M)
+    flags = re.search(r"^\$\(CONTRACT_OFF_OBJS\): (\w+) \+= -ffp-contract=off$", mk, re.M)
+    assert flags and re.search(r"^%\.o: %\.hip.*\n\t.*\$\(" + flags.group(1) + r"\)", mk, re.M)
 
 
 def test_optimization_params_carry_upstreams_exposure_defaults():

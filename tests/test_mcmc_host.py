@@ -31,7 +31,9 @@ def test_entry_points_are_exported_and_the_three_abi_numbers_agree():
 def test_the_makefile_builds_the_unit_without_contraction():
     mk = open(os.path.join(ROOT, "mvs_gaussian_splatting_amd", "csrc", "Makefile")).read()
     assert re.search(r"^OBJS = .*\bmcmc\.o\b", mk, re.M)
-    assert re.search(r"^mcmc\.o:.*\n\t.*\$\(CONTRACT_OFF\)", mk, re.M)
+    assert re.search(r"^CONTRACT_OFF_OBJS :?\+?= *mcmc\.o\b", mk, re.M)
+    flags = re.search(r"^\$\(CONTRACT_OFF_OBJS\): (\w+) \+= -ffp-contract=off$", mk, re.M)
+    assert flags and re.search(r"^%\.o: %\.hip.*\n\t.*\$\(" + flags.group(1) + r"\)", mk, re.M)
 
 
 def test_every_entry_point_refuses_bad_arguments_without_a_device():
