@@ -3,7 +3,8 @@ the surface by marching tetrahedra, all on the HIP path (``mvs_gaussian_splattin
 
     python examples/extract_mesh.py -m <model directory> [--iteration N] [--voxel_size S | --resolution R]
                                     [--sdf_trunc T] [--alpha_min A] [--max_depth D] [--depth_ratio R]
-                                    [--num_cluster N] [--min_cluster_faces M] [-s <dataset>] [-r ...]
+                                    [--num_cluster N] [--min_cluster_faces M] [--unbounded [--mesh_res N]]
+                                    [-s <dataset>] [-r ...]
 
 The scene is loaded as ``examples/render.py`` loads it (``cfg_args.json`` of the model directory; ``-s`` and the other
 switches override it).  The volume bounds the bulk of the model's positions (``tsdf.volume_for_points``); ``--resolution``
@@ -16,6 +17,13 @@ writes ``<model>/mesh/iteration_<N>/tsdf_mesh.ply`` (binary PLY, vertex colours 
 and / or ``--min_cluster_faces M`` (50 when only ``--num_cluster`` is given; 2DGS: 50 and 50) the mesh is cleaned as 2DGS
 cleans it -- the connected triangles are clustered and the clusters at least as large as the N-th largest, and of at
 least M faces, are kept (``mesh.clean_mesh``) -- and written next to the raw one as ``tsdf_mesh_post.ply``.
+
+``--unbounded`` meshes an unbounded scene as 2DGS's ``extract_mesh_unbounded`` does: the sphere of the
+training cameras (``tsdf.bounding_sphere``) normalises the scene, the volume is a cube of contracted space with
+``--mesh_res`` samples per side (default 512) that holds 95 % of the model (``tsdf.contracted_volume_for_points``), the
+truncation is 5 voxels of the unit ball and grows with the distance (``--sdf_trunc`` overrides it), and the vertices go
+back through the inverse contraction.  The mesh is written as ``tsdf_mesh_unbounded.ply``, the cleaned one as
+``tsdf_mesh_unbounded_post.ply``; ``--voxel_size`` and ``--resolution`` belong to the bounded path.
 """
 import argparse
 import json
@@ -25,26 +33,35 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from mvs_gaussian_splatting_amd import GaussianModel, ModelParams, Scene, fuse_views, volume_for_points  # noqa: E402
+from mvs_gaussian_splatting_amd import (GaussianModel, ModelParams, Scene, bounding_sphere,  # noqa: E402
+                                        contracted_volume_for_points, fuse_views, volume_for_points)
 from mvs_gaussian_splatting_amd.mesh import clean_mesh  # noqa: E402
 from mvs_gaussian_splatting_amd.ply_io import write_ply_mesh  # noqa: E402
 from mvs_gaussian_splatting_amd.synthetic import PipelineParams  # noqa: E402
 
 
 def extract(dataset, iteration, voxel_size=None, resolution=None, sdf_trunc=None, alpha_min=0.5, max_depth=None,
-            depth_ratio=0.0, num_cluster=None, min_cluster_faces=None):
+            depth_ratio=0.0, num_cluster=None, min_cluster_faces=None, unbounded=False, mesh_res=None):
     with torch.no_grad():
         gaussians = GaussianModel(dataset.sh_degree)
         scene = Scene(dataset, gaussians, load_iteration=iteration, shuffle=False)
         bg_color = [1, 1, 1] if dataset.white_background else [0, 0, 0]
         background = torch.tensor(bg_color, dtype=torch.float32, device="cuda")
-        volume = volume_for_points(gaussians.get_xyz, voxel_size=voxel_size, resolution=resolution, sdf_trunc=sdf_trunc)
+        if unbounded:
+            center, radius = bounding_sphere(scene.getTrainCameras())
+            print(f"bounding sphere of the training cameras: center ({center[0]:.5g}, {center[1]:.5g}, {center[2]:.5g}), "
+                  f"radius {radius:.5g}")
+            volume = contracted_volume_for_points(gaussians.get_xyz, center, radius,
+                                                  resolution=512 if mesh_res is None else mesh_res, sdf_trunc=sdf_trunc)
+        else:
+            volume = volume_for_points(gaussians.get_xyz, voxel_size=voxel_size, resolution=resolution, sdf_trunc=sdf_trunc)
         print(f"volume {volume.dims[0]} x {volume.dims[1]} x {volume.dims[2]}, voxel {volume.voxel_size:.5g}, "
               f"truncation {volume.sdf_trunc:.5g}")
         fuse_views(scene.getTrainCameras(), gaussians, PipelineParams(), background, volume, alpha_min=alpha_min,
                    max_depth=max_depth, **({"depth_ratio": depth_ratio} if depth_ratio else {}))
         vertices, faces, colors = volume.extract_mesh()
-    path = os.path.join(dataset.model_path, "mesh", "iteration_{}".format(scene.loaded_iter), "tsdf_mesh.ply")
+    path = os.path.join(dataset.model_path, "mesh", "iteration_{}".format(scene.loaded_iter),
+                        "tsdf_mesh_unbounded.ply" if unbounded else "tsdf_mesh.ply")
     write_ply_mesh(path, vertices, faces, colors)
     print(f"{vertices.shape[0]} vertices, {faces.shape[0]} faces -> {path}")
     if num_cluster is None and min_cluster_faces is None:
@@ -52,7 +69,7 @@ def extract(dataset, iteration, voxel_size=None, resolution=None, sdf_trunc=None
     if min_cluster_faces is None:
         min_cluster_faces = 50
     kept_v, kept_f, kept_c = clean_mesh(vertices, faces, colors, keep_largest=num_cluster, min_faces=min_cluster_faces)
-    post = os.path.join(os.path.dirname(path), "tsdf_mesh_post.ply")
+    post = path[:-len(".ply")] + "_post.ply"
     write_ply_mesh(post, kept_v, kept_f, kept_c)
     print(f"cleaned (num_cluster {num_cluster}, min_cluster_faces {min_cluster_faces}): {kept_v.shape[0]} of "
           f"{vertices.shape[0]} vertices, {kept_f.shape[0]} of {faces.shape[0]} faces -> {post}")
@@ -81,7 +98,16 @@ def main(argv=None):
                     help="clean the mesh: keep the clusters at least as large as the N-th largest (2DGS: 50)")
     ap.add_argument("--min_cluster_faces", type=int, default=None,
                     help="clean the mesh: drop clusters of fewer faces (50 when --num_cluster is given)")
+    ap.add_argument("--unbounded", action="store_true",
+                    help="fuse in contracted space about the training cameras' sphere (2DGS's extract_mesh_unbounded)")
+    ap.add_argument("--mesh_res", type=int, default=None, help="with --unbounded: samples per side of the contracted cube (512)")
     args = ap.parse_args(argv)
+    if args.mesh_res is not None and not args.unbounded:
+        ap.error("--mesh_res belongs to --unbounded")
+    if args.mesh_res is not None and args.mesh_res < 2:
+        ap.error("--mesh_res must be at least 2")
+    if args.unbounded and (args.voxel_size is not None or args.resolution is not None):
+        ap.error("--voxel_size and --resolution belong to the bounded path: give --mesh_res")
     if args.num_cluster is not None and args.num_cluster < 1:
         ap.error("--num_cluster must be positive")
     if args.min_cluster_faces is not None and args.min_cluster_faces < 0:
@@ -102,7 +128,8 @@ def main(argv=None):
     print("Extracting a mesh from " + args.model_path)
     extract(dataset, args.iteration, args.voxel_size, args.resolution, args.sdf_trunc, args.alpha_min, args.max_depth,
             args.depth_ratio, **({} if args.num_cluster is None and args.min_cluster_faces is None else
-                                 {"num_cluster": args.num_cluster, "min_cluster_faces": args.min_cluster_faces}))
+                                 {"num_cluster": args.num_cluster, "min_cluster_faces": args.min_cluster_faces}),
+            **({"unbounded": True, "mesh_res": args.mesh_res} if args.unbounded else {}))
 
 
 if __name__ == "__main__":

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 32
+#define GSR_ABI_VERSION 33
 
 enum {
   GSR_OK = 0,
@@ -845,6 +845,31 @@ int gsr_tsdf_mesh_count(const GsrTsdfVolume* vol, float min_weight, uint8_t* tri
 int gsr_tsdf_mesh_emit(const GsrTsdfVolume* vol, const uint8_t* tri_count, const uint8_t* edge_mask,
                        const int64_t* vert_offs, const int64_t* tri_offs, int64_t V, int64_t F, float* vertices,
                        float* vcolors, int32_t* faces, void* stream);
+
+/* ---- TSDF fusion in contracted space: unbounded scenes, ABI v33 (csrc/tsdf.hip; tsdf.py)
+ * The Mip-NeRF 360 contraction of a normalised point x = (p - center) / radius: contract(x) = x for |x| <= 1 and
+ * (2 - 1 / |x|) x / |x| otherwise.  Its inverse on |q| < 2 with m = |q|: s = 1, g = 1 for m <= 1; s = 1 / ((2 - m) m),
+ * g = 1 / (2 - m) for m > 1; p = center + radius * (q * s).  A contracted volume is a GsrTsdfVolume (same fields, layout
+ * and index limits) whose grid point (i, j, k) is the contracted-space sample q = origin + voxel_size * (i, j, k);
+ * sdf_trunc stays in world units, as it applies inside the unit ball. */
+typedef struct GsrTsdfContraction {
+  float center[3];
+  float radius;                 /* > 0, finite */
+  float q_max;                  /* in (1, 2): grid points with |q| >= q_max are never touched */
+} GsrTsdfContraction;
+/* gsr_tsdf_integrate on a contracted volume, one launch of the same kernel body.  Per grid point, float32, every
+ * operation rounded on its own: m2 = (q.x q.x + q.y q.y) + q.z q.z, skip unless m2 < q_max q_max (before any load);
+ * m = sqrtf(m2); p = center + radius * (q * s); trunc = sdf_trunc * g; then the sequence of gsr_tsdf_integrate from p on
+ * with trunc in the place of sdf_trunc.  With center 0, radius 1 and every |q| <= 1 the result is gsr_tsdf_integrate's
+ * bit for bit.  Checked before any HIP call: everything gsr_tsdf_integrate checks, and GSR_E_BADARG for a NULL
+ * contraction, a center or radius that is not finite, radius <= 0, q_max outside (1, 2). */
+int gsr_tsdf_integrate_contracted(const GsrTsdfVolume* vol, const GsrTsdfContraction* contraction, const GsrTsdfView* view,
+                                  void* stream);
+/* xyz device float32 [n,3], in place, one lane per row: q -> center + radius * (q * s), s as above from
+ * m2 = (q.x q.x + q.y q.y) + q.z q.z -- the vertices gsr_tsdf_mesh_emit wrote for a contracted volume, taken to world
+ * space (rows must have |q| < 2; every vertex of such a mesh has |q| < q_max).  0 <= n < 2^31; n == 0 is a successful
+ * no-op (xyz may be NULL).  Asynchronous on `stream`, allocates nothing, reads nothing back. */
+int gsr_tsdf_uncontract_points(float* xyz, int64_t n, const GsrTsdfContraction* contraction, void* stream);
 
 /* ---- Depth-normal consistency loss, ABI v28 (csrc/normal_consistency.hip; normal_consistency.py)
  * The normal-consistency term of 2DGS on the maps of a rendered frame: depth [H,W] = sum w z, alpha [H,W] = sum w,

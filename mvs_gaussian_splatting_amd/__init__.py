@@ -15,7 +15,8 @@ from .image_ingest import load_image, load_image_host  # noqa: F401
 from .scene import Scene, Camera, MiniCam, PoseCamera, ModelParams  # noqa: F401
 from .contribution import ContributionStats, measure, prune_points_, prune_by_contribution  # noqa: F401
 from .features import gaussian_normals  # noqa: F401
-from .tsdf import TSDFVolume, fuse_views, volume_for_points  # noqa: F401
+from .tsdf import (TSDFVolume, ContractedTSDFVolume, fuse_views, volume_for_points,  # noqa: F401
+                   contracted_volume_for_points, bounding_sphere)
 from .mcmc import mcmc_regularizer, inject_noise, relocate_gs, add_new_gs  # noqa: F401
 from .normal_consistency import normal_consistency_loss, depth_to_normals  # noqa: F401
 from .surface import surface_depth  # noqa: F401
@@ -27,6 +28,7 @@ __all__ = ["Scene", "Camera", "MiniCam", "PoseCamera", "ModelParams", "load_imag
            "opacity_sparsity_loss", "add_densification_stats", "Adam", "GaussianModel", "psnr", "ssim", "image_metrics", "to_uint8_hwc", "EvalAccumulator",
            "evaluate_views", "ContributionStats", "measure", "prune_points_", "prune_by_contribution",
            "mcmc_regularizer", "inject_noise", "relocate_gs", "add_new_gs", "gaussian_normals",
-           "TSDFVolume", "fuse_views", "volume_for_points", "normal_consistency_loss", "depth_to_normals",
+           "TSDFVolume", "ContractedTSDFVolume", "fuse_views", "volume_for_points", "contracted_volume_for_points",
+           "bounding_sphere", "normal_consistency_loss", "depth_to_normals",
            "surface_depth", "connected_components", "clean_mesh", "NearestIndex", "nearest_points", "sample_surface",
            "evaluate_points", "evaluate_mesh"]

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # instead of copying it over the in-tree library
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")
 
-ABI_VERSION = 32
+ABI_VERSION = 33
 
 
 class GsrParams(C.Structure):
@@ -62,6 +62,11 @@ class GsrTsdfVolume(C.Structure):
     _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("origin", C.c_float * 3),
                 ("voxel_size", C.c_float), ("sdf_trunc", C.c_float),
                 ("tsdf", C.c_void_p), ("weight", C.c_void_p), ("color", C.c_void_p)]
+
+
+class GsrTsdfContraction(C.Structure):
+    """The scene contraction of a contracted TSDF volume (include/gsr.h, ABI v33; tsdf.ContractedTSDFVolume)."""
+    _fields_ = [("center", C.c_float * 3), ("radius", C.c_float), ("q_max", C.c_float)]
 
 
 class GsrTsdfView(C.Structure):
@@ -273,6 +278,10 @@ SYMBOLS = {
     "gsr_tsdf_mesh_count": (C.c_int, [C.POINTER(GsrTsdfVolume), C.c_float] + [C.c_void_p] * 4),
     "gsr_tsdf_mesh_emit": (C.c_int, [C.POINTER(GsrTsdfVolume)] + [C.c_void_p] * 4 + [C.c_int64, C.c_int64] +
                            [C.c_void_p] * 4),
+    # the same on a volume in contracted space, and its vertices back to world space (csrc/tsdf.hip; tsdf.py)
+    "gsr_tsdf_integrate_contracted": (C.c_int, [C.POINTER(GsrTsdfVolume), C.POINTER(GsrTsdfContraction),
+                                                C.POINTER(GsrTsdfView), C.c_void_p]),
+    "gsr_tsdf_uncontract_points": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(GsrTsdfContraction), C.c_void_p]),
     # depth-normal consistency loss of a rendered frame, value and unit gradients (csrc/normal_consistency.hip)
     "gsr_normal_consistency_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "gsr_normal_consistency_fwd_bwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 2 + [C.c_float] * 3 + [C.c_void_p] * 7),

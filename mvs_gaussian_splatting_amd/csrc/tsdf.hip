@@ -22,6 +22,24 @@
 //     weight = min(w_old + w, max_weight)
 // A skipped point is not written.  A missing max_depth / max_weight arrives as +inf.
 //
+// Contracted volumes (unbounded scenes; ABI v33).  The Mip-NeRF 360 contraction of a normalised point
+// x = (p - center) / radius keeps the unit ball and squeezes the rest of space into the shell 1 < |q| < 2:
+//     contract(x) = x for |x| <= 1,   (2 - 1 / |x|) x / |x| otherwise.
+// Its inverse on |q| < 2, m = |q|:   m <= 1: s = 1, g = 1;   m > 1: s = 1 / ((2 - m) m), g = 1 / (2 - m);
+//     p = center + radius * (q * s).
+// A contracted volume is the same GsrTsdfVolume with its grid in contracted space, q = origin + voxel_size * (i, j, k),
+// and a GsrTsdfContraction { center, radius > 0, 1 < q_max < 2 }; sdf_trunc is in world units, as it applies inside the
+// unit ball.  tsdf_integrate_kernel<*, true> puts in front of the sequence above, per grid point:
+//     q    = origin + voxel_size * (i, j, k)                   (multiply, then add, per axis)
+//     m2   = (q.x q.x + q.y q.y) + q.z q.z                     skip unless m2 < q_max q_max: the first test, before any load
+//     m    = sqrtf(m2);  s, g as above                         (m <= 1 is the identity branch: q = 0 divides by nothing)
+//     p    = center + radius * (q * s)                         (per axis: q s, times radius, plus center)
+//     trunc = sdf_trunc * g                                    (2DGS: the truncation grows as 1 / (2 - m))
+// and goes on from p with trunc in the place of sdf_trunc.  With center 0, radius 1 and every |q| <= 1 it is the plain
+// kernel bit for bit.  The mesh is extracted on the grid by the kernels below, which cannot tell the difference;
+// contract_points_inverse_kernel then maps every vertex row q -> center + radius * (q * s) in place, one lane per row,
+// with the same s, so a vertex that coincides with a grid point lands on the point the integration projected.
+//
 // Mesh extraction, marching tetrahedra on the Kuhn decomposition.  Cube corner c = x + 2 y + 4 z.  The six tetrahedra
 // around the diagonal 0 -- 7, in the order of the axis permutations xyz, xzy, yxz, yzx, zxy, zyx, each written
 // positively oriented (det [v1 - v0, v2 - v0, v3 - v0] > 0; the odd permutations have their middle corners swapped):
@@ -66,15 +84,39 @@ __device__ inline bool tsdf_point(int nx, int ny, int nz, unsigned xchunks, Tsdf
   return true;
 }
 
-template <bool COLOR>
-__global__ __launch_bounds__(TSDF_X* TSDF_ROWS) void tsdf_integrate_kernel(GsrTsdfVolume vol, GsrTsdfView view,
-                                                                            unsigned xchunks) {
+// the inverse contraction's scale s and the growth g of the truncation at |q|^2 = m2 (header comment)
+__device__ inline void uncontract_scale(float m2, float& s, float& g) {
+  const float m = sqrtf(m2);
+  if (m <= 1.0f) {
+    s = 1.0f;
+    g = 1.0f;
+  } else {
+    s = 1.0f / ((2.0f - m) * m);
+    g = 1.0f / (2.0f - m);
+  }
+}
+
+// CONTRACTED: the grid lives in contracted space (con); otherwise con is not read
+template <bool COLOR, bool CONTRACTED>
+__global__ __launch_bounds__(TSDF_X* TSDF_ROWS) void tsdf_integrate_kernel(GsrTsdfVolume vol, GsrTsdfContraction con,
+                                                                            GsrTsdfView view, unsigned xchunks) {
   TsdfPoint p;
   if (!tsdf_point(vol.nx, vol.ny, vol.nz, xchunks, p)) return;
   const float* __restrict__ M = view.viewmatrix;
-  const float wx = vol.origin[0] + vol.voxel_size * (float)p.i;
-  const float wy = vol.origin[1] + vol.voxel_size * (float)p.j;
-  const float wz = vol.origin[2] + vol.voxel_size * (float)p.k;
+  float wx = vol.origin[0] + vol.voxel_size * (float)p.i;
+  float wy = vol.origin[1] + vol.voxel_size * (float)p.j;
+  float wz = vol.origin[2] + vol.voxel_size * (float)p.k;
+  float trunc = vol.sdf_trunc;
+  if constexpr (CONTRACTED) {
+    const float m2 = (wx * wx + wy * wy) + wz * wz;
+    if (!(m2 < con.q_max * con.q_max)) return;
+    float s, g;
+    uncontract_scale(m2, s, g);
+    wx = con.center[0] + con.radius * (wx * s);
+    wy = con.center[1] + con.radius * (wy * s);
+    wz = con.center[2] + con.radius * (wz * s);
+    trunc = vol.sdf_trunc * g;
+  }
   const float z = ((wx * M[2] + wy * M[6]) + wz * M[10]) + M[14];
   if (!(z > 0.2f)) return;
   const float x = ((wx * M[0] + wy * M[4]) + wz * M[8]) + M[12];
@@ -88,8 +130,8 @@ __global__ __launch_bounds__(TSDF_X* TSDF_ROWS) void tsdf_integrate_kernel(GsrTs
   const float d = view.depth[pix];
   if (!(d > 0.0f) || d > view.max_depth) return;
   const float sdf = d - z;
-  if (sdf < -vol.sdf_trunc) return;
-  const float t = fminf(1.0f, sdf / vol.sdf_trunc);
+  if (sdf < -trunc) return;
+  const float t = fminf(1.0f, sdf / trunc);
   const float w = view.weight, w_old = vol.weight[p.idx], w_sum = w_old + w;
   vol.tsdf[p.idx] = (vol.tsdf[p.idx] * w_old + t * w) / w_sum;
   if constexpr (COLOR) {
@@ -99,6 +141,21 @@ __global__ __launch_bounds__(TSDF_X* TSDF_ROWS) void tsdf_integrate_kernel(GsrTs
     for (int ch = 0; ch < 3; ++ch) c[ch] = (c[ch] * w_old + view.color[ch * plane + pix] * w) / w_sum;
   }
   vol.weight[p.idx] = fminf(w_sum, view.max_weight);
+}
+
+constexpr int POINTS_BLOCK = 256;
+
+__global__ __launch_bounds__(POINTS_BLOCK) void contract_points_inverse_kernel(float* __restrict__ xyz, int64_t n,
+                                                                               GsrTsdfContraction con) {
+  const int64_t row = (int64_t)blockIdx.x * POINTS_BLOCK + threadIdx.x;
+  if (row >= n) return;
+  float* q = xyz + 3 * row;
+  const float qx = q[0], qy = q[1], qz = q[2];
+  float s, g;
+  uncontract_scale((qx * qx + qy * qy) + qz * qz, s, g);
+  q[0] = con.center[0] + con.radius * (qx * s);
+  q[1] = con.center[1] + con.radius * (qy * s);
+  q[2] = con.center[2] + con.radius * (qz * s);
 }
 
 // ---- marching tetrahedra ---------------------------------------------------------------------------------------------
@@ -277,12 +334,22 @@ bool tsdf_grid_blocks(int nx, int ny, int nz, unsigned* xchunks, unsigned* block
   return true;
 }
 
-void launch_tsdf_integrate(const GsrTsdfVolume& vol, const GsrTsdfView& view, hipStream_t s) {
+// con: NULL for a world-space volume
+void launch_tsdf_integrate(const GsrTsdfVolume& vol, const GsrTsdfContraction* con, const GsrTsdfView& view,
+                           hipStream_t s) {
   unsigned xchunks, blocks;
   if (!tsdf_grid_blocks(vol.nx, vol.ny, vol.nz, &xchunks, &blocks)) return;
   const dim3 grid(blocks), block(TSDF_X, TSDF_ROWS);
-  if (vol.color && view.color) hipLaunchKernelGGL(tsdf_integrate_kernel<true>, grid, block, 0, s, vol, view, xchunks);
-  else hipLaunchKernelGGL(tsdf_integrate_kernel<false>, grid, block, 0, s, vol, view, xchunks);
+  const bool color = vol.color && view.color;
+  const GsrTsdfContraction c = con ? *con : GsrTsdfContraction{};
+  auto kernel = con ? (color ? tsdf_integrate_kernel<true, true> : tsdf_integrate_kernel<false, true>)
+                    : (color ? tsdf_integrate_kernel<true, false> : tsdf_integrate_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, grid, block, 0, s, vol, c, view, xchunks);
+}
+
+void launch_contract_points_inverse(float* xyz, int64_t n, const GsrTsdfContraction& con, hipStream_t s) {
+  const dim3 grid((unsigned)((n + POINTS_BLOCK - 1) / POINTS_BLOCK)), block(POINTS_BLOCK);
+  hipLaunchKernelGGL(contract_points_inverse_kernel, grid, block, 0, s, xyz, n, con);
 }
 
 void launch_tsdf_mesh_count(const GsrTsdfVolume& vol, float min_weight, uint8_t* tri_count, uint8_t* edge_mask,
@@ -330,8 +397,7 @@ static int tsdf_volume_ok(const GsrTsdfVolume* v) {
   if (!aligned({v->tsdf, v->weight, v->color}, 3u)) return fail(GSR_E_ALIGN, "volume fields must be 4-byte aligned");
   return 0;
 }
-int gsr_tsdf_integrate(const GsrTsdfVolume* vol, const GsrTsdfView* view, void* stream) {
-  if (int rc = tsdf_volume_ok(vol)) return rc;
+static int tsdf_view_ok(const GsrTsdfVolume* vol, const GsrTsdfView* view) {
   if (!view) return fail(GSR_E_BADARG, "view is NULL");
   if (!image_shape_ok(view->height, view->width)) return fail(GSR_E_BADARG, "bad image shape");
   if (!view->viewmatrix || !view->depth) return fail(GSR_E_BADARG, "viewmatrix / depth is NULL");
@@ -341,9 +407,42 @@ int gsr_tsdf_integrate(const GsrTsdfVolume* vol, const GsrTsdfView* view, void* 
       !(view->max_weight > 0.0f))
     return fail(GSR_E_BADARG, "fx, fy, weight, max_depth and max_weight must be positive (+inf: no limit)");
   if (!aligned({view->viewmatrix, view->depth, view->color}, 3u)) return fail(GSR_E_ALIGN, "view arrays must be 4-byte aligned");
+  return 0;
+}
+static int tsdf_contraction_ok(const GsrTsdfContraction* c) {
+  if (!c) return fail(GSR_E_BADARG, "contraction is NULL");
+  const auto finite = [](float v) { return v - v == 0.0f; };             // false for NaN and +-inf
+  if (!finite(c->center[0]) || !finite(c->center[1]) || !finite(c->center[2]))
+    return fail(GSR_E_BADARG, "the contraction's center must be finite");
+  if (!(c->radius > 0.0f) || !finite(c->radius)) return fail(GSR_E_BADARG, "the contraction's radius must be positive and finite");
+  if (!(c->q_max > 1.0f && c->q_max < 2.0f)) return fail(GSR_E_BADARG, "q_max must lie in (1, 2)");
+  return 0;
+}
+int gsr_tsdf_integrate(const GsrTsdfVolume* vol, const GsrTsdfView* view, void* stream) {
+  if (int rc = tsdf_volume_ok(vol)) return rc;
+  if (int rc = tsdf_view_ok(vol, view)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  launch_tsdf_integrate(*vol, *view, s);
+  launch_tsdf_integrate(*vol, nullptr, *view, s);
   return check(false, s, "tsdf_integrate");
+}
+int gsr_tsdf_integrate_contracted(const GsrTsdfVolume* vol, const GsrTsdfContraction* contraction, const GsrTsdfView* view,
+                                  void* stream) {
+  if (int rc = tsdf_volume_ok(vol)) return rc;
+  if (int rc = tsdf_contraction_ok(contraction)) return rc;
+  if (int rc = tsdf_view_ok(vol, view)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_tsdf_integrate(*vol, contraction, *view, s);
+  return check(false, s, "tsdf_integrate_contracted");
+}
+int gsr_tsdf_uncontract_points(float* xyz, int64_t n, const GsrTsdfContraction* contraction, void* stream) {
+  if (int rc = tsdf_contraction_ok(contraction)) return rc;
+  if (n < 0 || n >= ((int64_t)1 << 31)) return fail(GSR_E_BADARG, "n must lie in 0 .. 2^31 - 1");
+  if (n == 0) return 0;
+  if (!xyz) return fail(GSR_E_BADARG, "xyz is NULL");
+  if (!aligned({xyz}, 3u)) return fail(GSR_E_ALIGN, "xyz must be 4-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_contract_points_inverse(xyz, n, *contraction, s);
+  return check(false, s, "tsdf_uncontract_points");
 }
 int gsr_tsdf_mesh_count(const GsrTsdfVolume* vol, float min_weight, uint8_t* tri_count, uint8_t* edge_mask,
                         uint8_t* vert_count, void* stream) {

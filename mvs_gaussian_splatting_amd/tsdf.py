@@ -12,6 +12,13 @@ Grid point ``(i, j, k)`` is the sample at ``origin + voxel_size * (i, j, k)``; t
 The extraction is marching tetrahedra on the Kuhn decomposition of every cube; its definitions and output order are in
 ``TSDFVolume.extract_mesh``.  There is no CPU path: a volume may be built on the CPU to be filled or inspected, but
 ``integrate`` and ``extract_mesh`` need it on a ROCm GPU.
+
+Unbounded scenes are fused on a grid in contracted space, 2DGS's ``extract_mesh_unbounded``:
+
+    center, radius = bounding_sphere(scene.getTrainCameras())
+    volume = contracted_volume_for_points(gaussians.get_xyz, center, radius, resolution=512)
+    fuse_views(scene.getTrainCameras(), gaussians, pipe, background, volume)
+    vertices, faces, colors = volume.extract_mesh()              # vertices in world space
 """
 from __future__ import annotations
 
@@ -139,8 +146,10 @@ class TSDFVolume:
         view.viewmatrix, view.depth = viewmatrix.data_ptr(), depth_c.data_ptr()
         view.color = None if color_c is None else color_c.data_ptr()
         with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(_lib.load().gsr_tsdf_integrate(C.byref(vol), C.byref(view), stream), "gsr_tsdf_integrate")
+            self._integrate_native(vol, view, torch.cuda.current_stream(dev).cuda_stream)
+
+    def _integrate_native(self, vol, view, stream) -> None:
+        _lib.check(_lib.load().gsr_tsdf_integrate(C.byref(vol), C.byref(view), stream), "gsr_tsdf_integrate")
 
     # ---- extraction ----------------------------------------------------------------------------------------------------
     def extract_mesh(self, min_weight: float = 1e-6) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
@@ -180,6 +189,124 @@ class TSDFVolume:
                                               None if colors is None else colors.data_ptr(), faces.data_ptr(), stream),
                        "gsr_tsdf_mesh_emit")
         return vertices, faces, colors
+
+
+Q_MAX = 1.9                            # 2DGS's bound of the contracted grid; the contraction itself ends at |q| = 2
+
+
+def _contraction(center, radius, q_max) -> Tuple[Tuple[float, float, float], float, float]:
+    center = tuple(float(v) for v in center)
+    if len(center) != 3 or not all(math.isfinite(v) for v in center):
+        raise ValueError(f"center has three finite entries, got {center}")
+    radius, q_max = float(radius), float(q_max)
+    if not radius > 0.0 or not math.isfinite(radius):
+        raise ValueError(f"radius must be positive and finite, got {radius}")
+    if not 1.0 < q_max < 2.0:
+        raise ValueError(f"q_max must lie in (1, 2), got {q_max}")
+    return center, radius, q_max
+
+
+def contract(x: torch.Tensor) -> torch.Tensor:
+    """The Mip-NeRF 360 contraction of normalised points ``x [...,3]``: ``x`` inside the unit ball,
+    ``(2 - 1 / |x|) x / |x|`` outside.  Plain torch, in the dtype of ``x``."""
+    m = torch.linalg.norm(x, dim=-1, keepdim=True)
+    far = m > 1.0
+    safe = torch.where(far, m, torch.ones_like(m))
+    return torch.where(far, (2.0 - 1.0 / safe) * (x / safe), x)
+
+
+class ContractedTSDFVolume(TSDFVolume):
+    """A ``TSDFVolume`` whose grid lives in contracted space, for unbounded scenes: grid point
+    ``(i, j, k)`` is ``q = origin + voxel_size * (i, j, k)`` and stands for the world point ``center + radius * (q * s)``,
+    ``s = 1`` for ``m = |q| <= 1`` and ``1 / ((2 - m) m)`` beyond -- the inverse of ``contract((p - center) / radius)``.
+    Same fields, layout and index limits as the base.  ``sdf_trunc`` is in world units as it applies inside the unit
+    ball; at ``m > 1`` the truncation is ``sdf_trunc / (2 - m)``.  Grid points with ``|q| >= q_max`` are never touched."""
+
+    def __init__(self, origin: Sequence[float], voxel_size: float, dims: Sequence[int], sdf_trunc: float,
+                 center: Sequence[float], radius: float, q_max: float = Q_MAX, with_color: bool = True, device="cuda"):
+        self.center, self.radius, self.q_max = _contraction(center, radius, q_max)
+        super().__init__(origin, voxel_size, dims, sdf_trunc, with_color=with_color, device=device)
+
+    def _native_contraction(self) -> "_lib.GsrTsdfContraction":
+        c = _lib.GsrTsdfContraction()
+        c.center[0], c.center[1], c.center[2] = self.center
+        c.radius, c.q_max = self.radius, self.q_max
+        return c
+
+    def _integrate_native(self, vol, view, stream) -> None:
+        con = self._native_contraction()
+        _lib.check(_lib.load().gsr_tsdf_integrate_contracted(C.byref(vol), C.byref(con), C.byref(view), stream),
+                   "gsr_tsdf_integrate_contracted")
+
+    def extract_mesh(self, min_weight: float = 1e-6, contracted: bool = False):
+        """``TSDFVolume.extract_mesh`` on the contracted grid, then every vertex through the inverse contraction, in
+        place, in one launch (``gsr_tsdf_uncontract_points``); faces and colours are the base's.  ``contracted=True``
+        returns the vertices in grid coordinates, as the base would."""
+        vertices, faces, colors = super().extract_mesh(min_weight)
+        if not contracted and vertices.shape[0] > 0:
+            con = self._native_contraction()
+            with torch.cuda.device(vertices.device):
+                stream = torch.cuda.current_stream(vertices.device).cuda_stream
+                _lib.check(_lib.load().gsr_tsdf_uncontract_points(vertices.data_ptr(), int(vertices.shape[0]),
+                                                                  C.byref(con), stream), "gsr_tsdf_uncontract_points")
+        return vertices, faces, colors
+
+
+def bounding_sphere(cameras) -> Tuple[Tuple[float, float, float], float]:
+    """2DGS's ``estimate_bounding_sphere``: ``center`` is the least-squares point nearest all optical axes and ``radius``
+    the smallest camera distance from it.  Per camera, from ``world_view_transform`` (row-vector convention), ``o`` the
+    position and ``d`` the unit view direction: ``A_i = (I - d d^T)^T (I - d d^T)``, ``center = (mean A_i)^-1 mean(A_i o)``.
+    Host, float64.  ``ValueError`` for fewer than two cameras and for a singular system (parallel axes)."""
+    import numpy as np
+    cameras = list(cameras)
+    if len(cameras) < 2:
+        raise ValueError(f"bounding_sphere needs at least two cameras, got {len(cameras)}")
+    A_sum, b_sum, origins = np.zeros((3, 3)), np.zeros(3), []
+    for cam in cameras:
+        M = cam.world_view_transform.detach().to(device="cpu", dtype=torch.float64).numpy()
+        c2w = np.linalg.inv(M[:3, :3])                 # rows: the camera's axes in the world
+        o = -M[3, :3] @ c2w
+        d = c2w[2] / np.linalg.norm(c2w[2])
+        P = np.eye(3) - np.outer(d, d)
+        A = P.T @ P
+        A_sum += A
+        b_sum += A @ o
+        origins.append(o)
+    A_mean, b_mean = A_sum / len(cameras), b_sum / len(cameras)
+    if np.linalg.cond(A_mean) > 1e12:
+        raise ValueError("the optical axes are parallel: no point is nearest all of them")
+    center = np.linalg.solve(A_mean, b_mean)
+    radius = float(np.linalg.norm(np.asarray(origins) - center, axis=1).min())
+    if not radius > 0.0:
+        raise ValueError("a camera sits at the centre of the optical axes: the sphere has no radius")
+    return tuple(float(v) for v in center), radius
+
+
+def contracted_volume_for_points(xyz: torch.Tensor, center: Sequence[float], radius: float, *, resolution: int = 512,
+                                 quantile: float = 0.95, sdf_trunc: Optional[float] = None, q_max: float = Q_MAX,
+                                 with_color: bool = True, device=None) -> ContractedTSDFVolume:
+    """2DGS's box for an unbounded scene: with ``R = min(quantile of |contract((xyz - center) / radius)| + 0.01, 1.9)``
+    (the quantile interpolated linearly between neighbours) the cube ``[-R, R]^3`` of contracted space with
+    ``resolution`` samples per side, ``voxel_size = 2 R / (resolution - 1)``.  ``sdf_trunc`` defaults to 5 world voxels,
+    ``5 * radius * voxel_size``.  Plain torch; one read-back."""
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] == 0:
+        raise ValueError(f"xyz must be [P,3] with P > 0, got {tuple(xyz.shape)}")
+    center, radius, q_max = _contraction(center, radius, q_max)
+    resolution = int(resolution)
+    if resolution < 2:
+        raise ValueError("resolution must be at least 2")
+    if not 0.0 <= quantile <= 1.0:
+        raise ValueError(f"quantile must lie in [0, 1], got {quantile}")
+    pts = xyz.detach().to(torch.float32)
+    x = (pts - torch.tensor(center, dtype=torch.float32, device=pts.device)) / radius
+    norms = torch.sort(torch.linalg.norm(contract(x), dim=-1)).values
+    at = quantile * (norms.shape[0] - 1)
+    lo_v, hi_v = norms[[int(math.floor(at)), int(math.ceil(at))]].tolist()         # the one read-back
+    R = min(lo_v + (hi_v - lo_v) * (at - math.floor(at)) + 0.01, 1.9)
+    voxel_size = 2.0 * R / (resolution - 1)
+    return ContractedTSDFVolume((-R, -R, -R), voxel_size, (resolution,) * 3,
+                                5.0 * radius * voxel_size if sdf_trunc is None else sdf_trunc, center, radius, q_max,
+                                with_color=with_color, device=xyz.device if device is None else device)
 
 
 def fuse_views(cameras, model, pipe, bg, volume: TSDFVolume, *, alpha_min: float = 0.5,
@@ -244,4 +371,5 @@ def volume_for_points(xyz: torch.Tensor, *, voxel_size: Optional[float] = None, 
                       device=xyz.device if device is None else device)
 
 
-__all__ = ["TSDFVolume", "fuse_views", "volume_for_points"]
+__all__ = ["TSDFVolume", "ContractedTSDFVolume", "fuse_views", "volume_for_points", "contracted_volume_for_points",
+           "bounding_sphere", "contract"]
