@@ -4,6 +4,7 @@ the surface by marching tetrahedra, all on the HIP path (``mvs_gaussian_splattin
     python examples/extract_mesh.py -m <model directory> [--iteration N] [--voxel_size S | --resolution R]
                                     [--sdf_trunc T] [--alpha_min A] [--max_depth D] [--depth_ratio R]
                                     [--num_cluster N] [--min_cluster_faces M] [--unbounded [--mesh_res N]]
+                                    [--consistent K] [--n_sources S] [--points]
                                     [-s <dataset>] [-r ...]
 
 The scene is loaded as ``examples/render.py`` loads it (``cfg_args.json`` of the model directory; ``-s`` and the other
@@ -24,24 +25,46 @@ training cameras (``tsdf.bounding_sphere``) normalises the scene, the volume is 
 truncation is 5 voxels of the unit ball and grows with the distance (``--sdf_trunc`` overrides it), and the vertices go
 back through the inverse contraction.  The mesh is written as ``tsdf_mesh_unbounded.ply``, the cleaned one as
 ``tsdf_mesh_unbounded_post.ply``; ``--voxel_size`` and ``--resolution`` belong to the bounded path.
+
+``--consistent K`` filters every view's depth by multi-view geometric consistency before it is fused (``mvs.py``; DESIGN.md
+§7.21): a pixel is integrated only if at least K of the view's ``--n_sources`` (default 4) nearest source views see it
+where and as deep as it does, so floaters and depth that hangs between two surfaces never reach the volume.  ``--points``
+also writes ``fused_points.ply`` next to the mesh: the fused point cloud of ``mvs.fuse_depth_points`` (xyz and 8-bit
+colour; K defaults to 2 there), the product DTU-style evaluation is defined on.  Without these flags the output is unchanged.
 """
 import argparse
 import json
 import os
 import sys
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from mvs_gaussian_splatting_amd import (GaussianModel, ModelParams, Scene, bounding_sphere,  # noqa: E402
-                                        contracted_volume_for_points, fuse_views, volume_for_points)
+                                        contracted_volume_for_points, fuse_depth_points, fuse_views,
+                                        volume_for_points)
 from mvs_gaussian_splatting_amd.mesh import clean_mesh  # noqa: E402
-from mvs_gaussian_splatting_amd.ply_io import write_ply_mesh  # noqa: E402
+from mvs_gaussian_splatting_amd.ply_io import write_ply_mesh, write_ply_vertices  # noqa: E402
 from mvs_gaussian_splatting_amd.synthetic import PipelineParams  # noqa: E402
 
 
+def write_points(path, xyz, rgb):
+    """A point cloud as binary PLY: float x, y, z and uchar red, green, blue (colours clamped to [0, 1], times 255, rounded)."""
+    xyz = xyz.detach().cpu().numpy()
+    rgb = np.rint(np.clip(rgb.detach().cpu().numpy(), 0.0, 1.0) * 255.0).astype(np.uint8)
+    elements = np.empty(xyz.shape[0], dtype=[("x", "f4"), ("y", "f4"), ("z", "f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+    for c, name in enumerate(("x", "y", "z")):
+        elements[name] = xyz[:, c]
+    for c, name in enumerate(("red", "green", "blue")):
+        elements[name] = rgb[:, c]
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    write_ply_vertices(path, elements)
+
+
 def extract(dataset, iteration, voxel_size=None, resolution=None, sdf_trunc=None, alpha_min=0.5, max_depth=None,
-            depth_ratio=0.0, num_cluster=None, min_cluster_faces=None, unbounded=False, mesh_res=None):
+            depth_ratio=0.0, num_cluster=None, min_cluster_faces=None, unbounded=False, mesh_res=None, consistent=None,
+            n_sources=4, points=False):
     with torch.no_grad():
         gaussians = GaussianModel(dataset.sh_degree)
         scene = Scene(dataset, gaussians, load_iteration=iteration, shuffle=False)
@@ -58,12 +81,20 @@ def extract(dataset, iteration, voxel_size=None, resolution=None, sdf_trunc=None
         print(f"volume {volume.dims[0]} x {volume.dims[1]} x {volume.dims[2]}, voxel {volume.voxel_size:.5g}, "
               f"truncation {volume.sdf_trunc:.5g}")
         fuse_views(scene.getTrainCameras(), gaussians, PipelineParams(), background, volume, alpha_min=alpha_min,
-                   max_depth=max_depth, **({"depth_ratio": depth_ratio} if depth_ratio else {}))
+                   max_depth=max_depth, **({"depth_ratio": depth_ratio} if depth_ratio else {}),
+                   **({} if consistent is None else {"consistency": {"n_sources": n_sources, "min_views": consistent}}))
         vertices, faces, colors = volume.extract_mesh()
     path = os.path.join(dataset.model_path, "mesh", "iteration_{}".format(scene.loaded_iter),
                         "tsdf_mesh_unbounded.ply" if unbounded else "tsdf_mesh.ply")
     write_ply_mesh(path, vertices, faces, colors)
     print(f"{vertices.shape[0]} vertices, {faces.shape[0]} faces -> {path}")
+    if points:
+        xyz, rgb = fuse_depth_points(scene.getTrainCameras(), gaussians, PipelineParams(), background, n_sources=n_sources,
+                                     min_views=2 if consistent is None else consistent, alpha_min=alpha_min,
+                                     depth_ratio=depth_ratio)
+        cloud = os.path.join(os.path.dirname(path), "fused_points.ply")
+        write_points(cloud, xyz, rgb)
+        print(f"{xyz.shape[0]} fused points -> {cloud}")
     if num_cluster is None and min_cluster_faces is None:
         return path
     if min_cluster_faces is None:
@@ -101,7 +132,15 @@ def main(argv=None):
     ap.add_argument("--unbounded", action="store_true",
                     help="fuse in contracted space about the training cameras' sphere (2DGS's extract_mesh_unbounded)")
     ap.add_argument("--mesh_res", type=int, default=None, help="with --unbounded: samples per side of the contracted cube (512)")
+    ap.add_argument("--consistent", type=int, default=None, metavar="K",
+                    help="fuse only pixels that at least K source views confirm (multi-view geometric consistency)")
+    ap.add_argument("--n_sources", type=int, default=4, help="source views per view for --consistent / --points (4)")
+    ap.add_argument("--points", action="store_true", help="also write the fused point cloud fused_points.ply")
     args = ap.parse_args(argv)
+    if args.consistent is not None and args.consistent < 0:
+        ap.error("--consistent must not be negative")
+    if not 1 <= args.n_sources <= 64:
+        ap.error("--n_sources must lie in 1..64")
     if args.mesh_res is not None and not args.unbounded:
         ap.error("--mesh_res belongs to --unbounded")
     if args.mesh_res is not None and args.mesh_res < 2:
@@ -129,7 +168,9 @@ def main(argv=None):
     extract(dataset, args.iteration, args.voxel_size, args.resolution, args.sdf_trunc, args.alpha_min, args.max_depth,
             args.depth_ratio, **({} if args.num_cluster is None and args.min_cluster_faces is None else
                                  {"num_cluster": args.num_cluster, "min_cluster_faces": args.min_cluster_faces}),
-            **({"unbounded": True, "mesh_res": args.mesh_res} if args.unbounded else {}))
+            **({"unbounded": True, "mesh_res": args.mesh_res} if args.unbounded else {}),
+            **({} if args.consistent is None and not args.points else
+               {"consistent": args.consistent, "n_sources": args.n_sources, "points": args.points}))
 
 
 if __name__ == "__main__":

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 33
+#define GSR_ABI_VERSION 34
 
 enum {
   GSR_OK = 0,
@@ -987,6 +987,41 @@ int gsr_nn_build(const float* ref, int32_t R, void* index, size_t index_bytes, v
 size_t gsr_nn_query_workspace_bytes(int32_t Q);
 int gsr_nn_query(const void* index, size_t index_bytes, int32_t R, const float* query, int32_t Q, float* dist2,
                  int32_t* nearest, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Multi-view geometric consistency of depth maps and back-projection, ABI v34 (csrc/mvs.hip; mvs.py).
+ * The check of MVSNet's / COLMAP's fusion: a reference pixel goes into a source view at its depth, the source's depth is
+ * read there (bilinear over four pixels that all hold depth), the result comes back, and the pixel is consistent with
+ * that source when it lands within pix_thresh pixels of where it started and within depth_thresh (relative) of the depth
+ * it started with.  Pixel convention of GsrTsdfView: cx = (W - 1) / 2, cy = (H - 1) / 2; depth 0 = none.  The float32
+ * operation order is the header comment of csrc/mvs.hip (-ffp-contract=off).
+ * One row of the device-resident source table, 8-byte aligned, 152 bytes: the source's depth [height,width] (device,
+ * float32, contiguous, 4-byte aligned), its intrinsics, and ref_to_src = inv(V_ref) V_src, src_to_ref = inv(V_src) V_ref in
+ * the row-vector convention (M[4 * row + col]), formed in float64 from the float32 view matrices and rounded once. */
+#define GSR_MVS_MAX_SOURCES 64
+typedef struct GsrMvsSource {
+  const float* depth;
+  int32_t width, height;
+  float fx, fy;
+  float ref_to_src[16];
+  float src_to_ref[16];
+} GsrMvsSource;
+/* depth [H,W] -> count uint8 [H,W]: the number of sources (table order, 0 <= S <= 64) the pixel is consistent with;
+ * fused float32 [H,W]: (d + sum of the consistent round-trip depths) / (count + 1) where count >= min_views, else 0.  A
+ * pixel without depth gives 0, 0; every pixel of both outputs is written; S = 0 is valid (count 0; fused = depth when
+ * min_views = 0, else 0).  One launch with the loop over the sources inside; sums in table order in registers: the same
+ * bits from run to run.  Checked before any HIP call: GSR_E_BADARG for a NULL pointer, H or W < 1 or H W > 2^28, S outside
+ * 0..64, a NULL table with S > 0, fx / fy / pix_thresh / depth_thresh not positive and finite, min_views < 0;
+ * GSR_E_ALIGN for depth / fused (4 bytes) and the table (8).  Asynchronous, allocates nothing, reads nothing back.  The
+ * table's rows are device memory and are not checked: width / height must describe the row's depth array. */
+int gsr_mvs_consistency(const float* depth, int32_t H, int32_t W, float fx, float fy, const GsrMvsSource* sources, int32_t S,
+                        float pix_thresh, float depth_thresh, int32_t min_views, uint8_t* count, float* fused, void* stream);
+/* depth [H,W] -> xyz [H W,3] (device): pixel (px, py) with depth d > 0 is (((px - cx) d) / fx, ((py - cy) d) / fy, d)
+ * through cam_to_world (HOST, 16 floats, row-vector convention: the float64 inverse of the view matrix rounded once; it
+ * is read during the call), x = ((xr M[0] + yr M[4]) + zr M[8]) + M[12] and likewise y, z; a pixel without depth gives a
+ * zero row.  H W = 0 is a successful no-op (after the scalar checks).  GSR_E_BADARG: negative H / W, H W > 2^28, fx / fy
+ * not positive and finite, a NULL pointer; GSR_E_ALIGN: 4 bytes. */
+int gsr_depth_backproject(const float* depth, int32_t H, int32_t W, float fx, float fy, const float* cam_to_world,
+                          float* xyz, void* stream);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # instead of copying it over the in-tree library
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")
 
-ABI_VERSION = 33
+ABI_VERSION = 34
 
 
 class GsrParams(C.Structure):
@@ -73,6 +73,15 @@ class GsrTsdfView(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_float), ("fy", C.c_float),
                 ("weight", C.c_float), ("max_depth", C.c_float), ("max_weight", C.c_float),
                 ("viewmatrix", C.c_void_p), ("depth", C.c_void_p), ("color", C.c_void_p)]
+
+
+MVS_MAX_SOURCES = 64
+
+
+class GsrMvsSource(C.Structure):
+    """One row of the source table of ``gsr_mvs_consistency`` (include/gsr.h, ABI v34; mvs.py): 152 bytes."""
+    _fields_ = [("depth", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_float), ("fy", C.c_float),
+                ("ref_to_src", C.c_float * 16), ("src_to_ref", C.c_float * 16)]
 
 
 class GsrGrow(C.Structure):
@@ -301,6 +310,11 @@ SYMBOLS = {
     "gsr_nn_query_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "gsr_nn_query": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.c_size_t, C.c_void_p]),
+    # multi-view geometric consistency of depth maps and back-projection to points (csrc/mvs.hip; mvs.py)
+    "gsr_mvs_consistency": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_int32,
+                                      C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsr_depth_backproject": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
 }
 
 _lib = None

@@ -1,0 +1,229 @@
+"""Multi-view geometric consistency of rendered depth, and the fused point cloud it yields, on the HIP path
+(``csrc/mvs.hip`` behind ``gsr_mvs_consistency`` / ``gsr_depth_backproject``).
+
+    sources = select_source_views(cameras, n_sources=4)
+    count, fused = depth_consistency(depths[i], cameras[i], [depths[j] for j in sources[i]], [cameras[j] for j in sources[i]])
+    xyz, rgb = fuse_depth_points(scene.getTrainCameras(), gaussians, pipe, background)        # a DTU-style cloud
+    fuse_views(cameras, gaussians, pipe, background, volume, consistency=dict(min_views=2))   # a filtered TSDF
+
+The check is MVSNet's / COLMAP's: a reference pixel is taken into a source view at its depth, the source's depth is read
+there (bilinear, only where all four neighbours hold depth), the result is taken back, and the pixel is consistent with
+that source when it lands within ``pix_thresh`` pixels of where it started and within ``depth_thresh`` (relative) of its
+own depth.  ``count`` is the number of sources a pixel is consistent with; ``fused`` the mean of its depth and the
+round-trip depths where ``count >= min_views`` and 0 elsewhere.  Depth 0 means no depth, the pixel centre convention is
+``tsdf.py``'s (``cx = (W - 1) / 2``), and the float32 order of operations is the header comment of ``csrc/mvs.hip``.  There
+is no CPU path.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+
+
+def _view64(camera) -> np.ndarray:
+    """The camera's float32 ``world_view_transform`` (row-vector convention) as float64 on the host."""
+    M = camera.world_view_transform.detach().to(device="cpu", dtype=torch.float32).to(torch.float64).numpy()
+    if M.shape != (4, 4):
+        raise ValueError(f"world_view_transform must be 4 x 4, got {M.shape}")
+    return M
+
+
+def _focal(camera) -> Tuple[int, int, float, float]:
+    H, W = int(camera.image_height), int(camera.image_width)
+    if H <= 0 or W <= 0:
+        raise ValueError("the camera has an empty image")
+    return H, W, W / (2.0 * math.tan(float(camera.FoVx) * 0.5)), H / (2.0 * math.tan(float(camera.FoVy) * 0.5))
+
+
+def _depth_map(depth, camera, dev, what: str) -> torch.Tensor:
+    H, W = int(camera.image_height), int(camera.image_width)
+    if not isinstance(depth, torch.Tensor) or depth.dtype != torch.float32 or (dev is not None and depth.device != dev) \
+            or tuple(depth.shape) not in ((H, W), (1, H, W)):
+        raise ValueError(f"{what} must be a float32 [{H},{W}] or [1,{H},{W}] tensor{'' if dev is None else f' on {dev}'}, "
+                         f"got {getattr(depth, 'dtype', type(depth))} {tuple(getattr(depth, 'shape', ()))} on "
+                         f"{getattr(depth, 'device', None)}")
+    return depth.detach().contiguous()
+
+
+def _thresholds(pix_thresh, depth_thresh, min_views) -> Tuple[float, float, int]:
+    pix_thresh, depth_thresh = float(pix_thresh), float(depth_thresh)
+    if not pix_thresh > 0.0 or not math.isfinite(pix_thresh):
+        raise ValueError(f"pix_thresh must be positive and finite, got {pix_thresh}")
+    if not depth_thresh > 0.0 or not math.isfinite(depth_thresh):
+        raise ValueError(f"depth_thresh must be positive and finite, got {depth_thresh}")
+    if isinstance(min_views, bool) or int(min_views) != min_views or min_views < 0:
+        raise ValueError(f"min_views must be a non-negative integer, got {min_views!r}")
+    return pix_thresh, depth_thresh, int(min_views)
+
+
+def select_source_views(cameras, n_sources: int, max_angle_deg: float = 60.0) -> List[List[int]]:
+    """For every view the indices of its source views: the other views whose forward direction is within
+    ``max_angle_deg`` of its own, the ``n_sources`` of them with the nearest camera centres, nearest first, ties to the
+    smaller index; fewer candidates give a shorter list.  Host, float64, from ``world_view_transform`` only: with
+    ``V = world_view_transform.T = [R|t]`` the centre is ``-R^T t`` and the forward direction the third row of ``R``."""
+    if isinstance(n_sources, bool) or int(n_sources) != n_sources or n_sources < 0:
+        raise ValueError(f"n_sources must be a non-negative integer, got {n_sources!r}")
+    max_angle_deg = float(max_angle_deg)
+    if not 0.0 < max_angle_deg <= 180.0:
+        raise ValueError(f"max_angle_deg must lie in (0, 180], got {max_angle_deg}")
+    cameras = list(cameras)
+    n = len(cameras)
+    if n == 0:
+        return []
+    centres, forwards = np.zeros((n, 3)), np.zeros((n, 3))
+    for i, cam in enumerate(cameras):
+        V = _view64(cam).T
+        R, t = V[:3, :3], V[:3, 3]
+        centres[i] = -R.T @ t
+        forwards[i] = R[2] / np.linalg.norm(R[2])
+    out = []
+    for i in range(n):
+        angle = np.degrees(np.arccos(np.clip(forwards @ forwards[i], -1.0, 1.0)))
+        dist = np.linalg.norm(centres - centres[i], axis=1)
+        order = np.argsort(dist, kind="stable")                            # stable: ties keep the smaller index first
+        out.append([int(j) for j in order if j != i and angle[j] <= max_angle_deg][:int(n_sources)])
+    return out
+
+
+def depth_consistency(depth: torch.Tensor, camera, src_depths: Sequence[torch.Tensor], src_cameras: Sequence, *,
+                      pix_thresh: float = 1.0, depth_thresh: float = 0.01,
+                      min_views: int = 2) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The consistency of one reference view with up to 64 source views, in one launch on the current stream ->
+    ``(count uint8 [H,W], fused float32 [H,W])``.  ``depth`` float32 ``[H,W]`` or ``[1,H,W]`` on a ROCm GPU, 0 where there
+    is none; ``camera``: anything with ``world_view_transform``, ``FoVx``, ``FoVy``, ``image_width``, ``image_height``;
+    ``src_depths[k]`` the depth map of ``src_cameras[k]``, of that camera's size, which may differ from the reference's.
+    ``count``: the number of sources a pixel is consistent with (module docstring), ``fused``: where ``count >=
+    min_views`` the mean of the pixel's depth and its round-trip depths from the consistent sources, else 0.  Pixels
+    without depth give 0, 0.  The two transforms per source, ``inv(V_ref) V_src`` and ``inv(V_src) V_ref``, are formed here in
+    float64 and rounded once.  The table of sources is one small host-to-device copy; nothing is read back."""
+    pix_thresh, depth_thresh, min_views = _thresholds(pix_thresh, depth_thresh, min_views)
+    H, W, fx, fy = _focal(camera)
+    dev = getattr(depth, "device", None)
+    depth_c = _depth_map(depth, camera, None, "depth")
+    src_depths, src_cameras = list(src_depths), list(src_cameras)
+    if len(src_depths) != len(src_cameras):
+        raise ValueError(f"{len(src_depths)} source depth maps for {len(src_cameras)} source cameras")
+    S = len(src_cameras)
+    if S > _lib.MVS_MAX_SOURCES:
+        raise ValueError(f"at most {_lib.MVS_MAX_SOURCES} source views, got {S}")
+    if H * W > 2 ** 28:
+        raise ValueError(f"an image of {W} x {H} exceeds 2^28 pixels")
+    M_ref = _view64(camera)
+    inv_ref = np.linalg.inv(M_ref)
+    table = (_lib.GsrMvsSource * max(S, 1))()
+    keep = []
+    for k, (sd, sc) in enumerate(zip(src_depths, src_cameras)):
+        Hs, Ws, fxs, fys = _focal(sc)
+        if Hs * Ws > 2 ** 28:
+            raise ValueError(f"source {k}: an image of {Ws} x {Hs} exceeds 2^28 pixels")
+        sd_c = _depth_map(sd, sc, dev, f"src_depths[{k}]")
+        keep.append(sd_c)
+        M_src = _view64(sc)
+        row = table[k]
+        row.depth, row.width, row.height, row.fx, row.fy = sd_c.data_ptr(), Ws, Hs, fxs, fys
+        A = (inv_ref @ M_src).astype(np.float32).reshape(-1)
+        B = (np.linalg.inv(M_src) @ M_ref).astype(np.float32).reshape(-1)
+        for i in range(16):
+            row.ref_to_src[i], row.src_to_ref[i] = float(A[i]), float(B[i])
+    if not depth_c.is_cuda:
+        raise _lib.GsrError("depth_consistency needs the depth maps on a ROCm GPU (no CPU path)")
+    lib = _lib.load()
+    count = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    fused = torch.empty((H, W), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        table_dev = None
+        if S > 0:
+            table_dev = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(lib.gsr_mvs_consistency(depth_c.data_ptr(), H, W, fx, fy,
+                                           None if table_dev is None else table_dev.data_ptr(), S, pix_thresh,
+                                           depth_thresh, min_views, count.data_ptr(), fused.data_ptr(), stream),
+                   "gsr_mvs_consistency")
+    return count, fused
+
+
+def backproject_depth(depth: torch.Tensor, camera) -> torch.Tensor:
+    """``depth`` float32 ``[H,W]`` or ``[1,H,W]`` on a ROCm GPU -> world points ``xyz`` float32 ``[H*W,3]`` in pixel order
+    (row ``py * W + px``): the pixel's ray ``((px - cx) / fx, (py - cy) / fy, 1)`` times its depth, through the float64
+    inverse of the view matrix rounded once to float32.  Rows of pixels without depth (0) are zeros; compact with a
+    boolean index (``xyz[depth.reshape(-1) > 0]``).  One launch, nothing is read back."""
+    H, W, fx, fy = _focal(camera)
+    depth_c = _depth_map(depth, camera, None, "depth")
+    if H * W > 2 ** 28:
+        raise ValueError(f"an image of {W} x {H} exceeds 2^28 pixels")
+    c2w = (C.c_float * 16)(*[float(v) for v in np.linalg.inv(_view64(camera)).astype(np.float32).reshape(-1)])
+    if not depth_c.is_cuda:
+        raise _lib.GsrError("backproject_depth needs the depth map on a ROCm GPU (no CPU path)")
+    dev = depth_c.device
+    xyz = torch.empty((H * W, 3), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(_lib.load().gsr_depth_backproject(depth_c.data_ptr(), H, W, fx, fy, C.addressof(c2w), xyz.data_ptr(),
+                                                     stream), "gsr_depth_backproject")
+    return xyz
+
+
+def consistency_options(consistency) -> dict:
+    """The ``consistency`` argument of ``tsdf.fuse_views`` with its defaults filled in; ``ValueError`` for an unknown key."""
+    options = dict(n_sources=4, min_views=2, pix_thresh=1.0, depth_thresh=0.01, max_angle_deg=60.0)
+    unknown = set(consistency) - set(options)
+    if unknown:
+        raise ValueError(f"consistency has unknown keys {sorted(unknown)}: it takes {sorted(options)}")
+    options.update(consistency)
+    _thresholds(options["pix_thresh"], options["depth_thresh"], options["min_views"])
+    return options
+
+
+def filter_views(cameras, depths, *, n_sources: int, min_views: int, pix_thresh: float, depth_thresh: float,
+                 max_angle_deg: float):
+    """``depth_consistency`` of every view against its ``select_source_views`` -> a generator of ``(count, fused)`` in view
+    order; ``depths[i]`` is the depth map of ``cameras[i]``."""
+    sources = select_source_views(cameras, n_sources, max_angle_deg)
+    for i, camera in enumerate(cameras):
+        yield depth_consistency(depths[i], camera, [depths[j] for j in sources[i]], [cameras[j] for j in sources[i]],
+                                pix_thresh=pix_thresh, depth_thresh=depth_thresh, min_views=min_views)
+
+
+def fuse_depth_points(cameras, model, pipe, bg, *, n_sources: int = 4, min_views: int = 2, pix_thresh: float = 1.0,
+                      depth_thresh: float = 0.01, alpha_min: float = 0.5, depth_ratio: float = 0.0,
+                      max_angle_deg: float = 60.0, renderer=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The fused point cloud of a trained model, the product DTU-style evaluation is defined on -> ``(xyz float32 [N,3],
+    rgb float32 [N,3])`` on the device.  Every view is rendered once under ``no_grad`` with ``renderer`` (default
+    ``render``); its surface depth -- the expression ``tsdf.fuse_views`` integrates, ``alpha_min`` and ``depth_ratio``
+    included -- and its colour stay on the device (``N_views H W (4 + 12)`` bytes).  Each view is filtered against its
+    ``select_source_views(cameras, n_sources, max_angle_deg)``; its ``fused`` depth is back-projected and the pixels with
+    ``fused > 0`` are gathered in pixel order, views concatenated in view order.  Duplicate points from overlapping views
+    are kept.  One host synchronisation per view (the boolean index)."""
+    from .tsdf import render_surface
+    _thresholds(pix_thresh, depth_thresh, min_views)
+    if not (isinstance(depth_ratio, (int, float)) and 0.0 <= depth_ratio <= 1.0):
+        raise ValueError(f"depth_ratio must lie in [0, 1], got {depth_ratio!r}")
+    if renderer is None:
+        from .renderer import render as renderer
+    cameras = list(cameras)
+    xyz, rgb = [], []
+    with torch.no_grad():
+        depths, colors = [], []
+        for camera in cameras:
+            expected, pkg = render_surface(renderer, camera, model, pipe, bg, alpha_min, depth_ratio)
+            depths.append(expected)
+            colors.append(pkg["render"])
+        filtered = filter_views(cameras, depths, n_sources=n_sources, min_views=min_views, pix_thresh=pix_thresh,
+                                depth_thresh=depth_thresh, max_angle_deg=max_angle_deg)
+        for camera, color, (_, fused) in zip(cameras, colors, filtered):
+            valid = fused.reshape(-1) > 0
+            xyz.append(backproject_depth(fused, camera)[valid])
+            rgb.append(color.detach().reshape(3, -1).t()[valid].to(torch.float32))
+    if not xyz:
+        dev = bg.device if isinstance(bg, torch.Tensor) else None
+        return torch.zeros((0, 3), device=dev), torch.zeros((0, 3), device=dev)
+    return torch.cat(xyz), torch.cat(rgb)
+
+
+__all__ = ["select_source_views", "depth_consistency", "backproject_depth", "fuse_depth_points"]

@@ -309,29 +309,59 @@ def contracted_volume_for_points(xyz: torch.Tensor, center: Sequence[float], rad
                                 with_color=with_color, device=xyz.device if device is None else device)
 
 
+def render_surface(renderer, camera, model, pipe, bg, alpha_min: float, depth_ratio: float):
+    """One view's surface depth as ``fuse_views`` integrates it -> ``(depth [1,H,W], the renderer's package)``: at
+    ``depth_ratio`` 0 the expected depth ``depth / alpha`` where ``alpha >= alpha_min`` and 0 elsewhere, from
+    ``renderer(camera, model, pipe, bg, return_depth=True)``; above 0 ``surface.surface_depth`` of a frame rendered with
+    ``return_median_depth=True`` as well."""
+    if depth_ratio > 0.0:
+        pkg = renderer(camera, model, pipe, bg, return_depth=True, return_median_depth=True)
+        return surface_depth(pkg["depth"], pkg["alpha"], pkg["median_depth"], depth_ratio, alpha_min), pkg
+    pkg = renderer(camera, model, pipe, bg, return_depth=True)
+    depth, alpha = pkg["depth"], pkg["alpha"]
+    return torch.where(alpha >= alpha_min, depth / alpha, torch.zeros_like(depth)), pkg
+
+
 def fuse_views(cameras, model, pipe, bg, volume: TSDFVolume, *, alpha_min: float = 0.5,
-               max_depth: Optional[float] = None, renderer=None, depth_ratio: float = 0.0) -> TSDFVolume:
+               max_depth: Optional[float] = None, renderer=None, depth_ratio: float = 0.0,
+               consistency: Optional[dict] = None) -> TSDFVolume:
     """Render every camera with ``renderer(camera, model, pipe, bg, return_depth=True)`` (default: ``render``) under
     ``no_grad`` and integrate its expected depth ``depth / alpha`` where ``alpha >= alpha_min`` (0, invalid, elsewhere)
     with the rendered colour.  No host synchronisation per view.
     depth_ratio (2DGS's, in [0, 1]; it meshes bounded scenes at 1): above 0 the frames are rendered with
     ``return_median_depth=True`` as well and ``surface.surface_depth(depth, alpha, median, depth_ratio, alpha_min)`` is
     integrated -- at 1 the median depth, which lies on a surface at a depth edge where the expected depth floats between
-    two.  At 0 the renderer is called with exactly the keyword arguments above."""
+    two.  At 0 the renderer is called with exactly the keyword arguments above.
+    consistency (default None: every pixel above is integrated, view by view as it is rendered): a dict with any of
+    ``n_sources`` (4), ``min_views`` (2), ``pix_thresh`` (1.0), ``depth_thresh`` (0.01), ``max_angle_deg`` (60.0) turns on
+    the multi-view geometric consistency filter of ``mvs.py``, in two passes.  The first renders every
+    view and keeps its surface depth and, if the volume has colour, its image on the device: ``N H W (4 + 12)`` bytes
+    for ``N`` views of ``H x W`` pixels (``4 N H W`` without colour).  The second checks each view against its
+    ``mvs.select_source_views`` and integrates the view's own depth with the pixels of ``count < min_views`` set to 0:
+    floaters, depth that hangs between two surfaces at a silhouette and fog in front of a wall, which no neighbour
+    confirms, never reach the volume."""
     if not (isinstance(depth_ratio, (int, float)) and 0.0 <= depth_ratio <= 1.0):
         raise ValueError(f"depth_ratio must lie in [0, 1], got {depth_ratio!r}")
+    if consistency is not None:
+        from .mvs import consistency_options, filter_views
+        options = consistency_options(consistency)
     if renderer is None:
         from .renderer import render as renderer
     with torch.no_grad():
+        if consistency is None:
+            for camera in cameras:
+                expected, pkg = render_surface(renderer, camera, model, pipe, bg, alpha_min, depth_ratio)
+                volume.integrate(expected, camera, color=pkg["render"] if volume.with_color else None, max_depth=max_depth)
+            return volume
+        cameras = list(cameras)
+        depths, colors = [], []
         for camera in cameras:
-            if depth_ratio > 0.0:
-                pkg = renderer(camera, model, pipe, bg, return_depth=True, return_median_depth=True)
-                expected = surface_depth(pkg["depth"], pkg["alpha"], pkg["median_depth"], depth_ratio, alpha_min)
-            else:
-                pkg = renderer(camera, model, pipe, bg, return_depth=True)
-                depth, alpha = pkg["depth"], pkg["alpha"]
-                expected = torch.where(alpha >= alpha_min, depth / alpha, torch.zeros_like(depth))
-            volume.integrate(expected, camera, color=pkg["render"] if volume.with_color else None, max_depth=max_depth)
+            expected, pkg = render_surface(renderer, camera, model, pipe, bg, alpha_min, depth_ratio)
+            depths.append(expected)
+            colors.append(pkg["render"] if volume.with_color else None)
+        for camera, depth, color, (count, _) in zip(cameras, depths, colors, filter_views(cameras, depths, **options)):
+            kept = torch.where((count >= options["min_views"]).view(depth.shape), depth, torch.zeros_like(depth))
+            volume.integrate(kept, camera, color=color, max_depth=max_depth)
     return volume
 
 
