@@ -12,6 +12,8 @@ SH degree steps, densification, opacity resets, the optional opacity sparsity te
                              [--strategy mcmc --cap_max N [--noise_lr LR] [--opacity_reg W] [--scale_reg W]]
                              [--lambda_normal L [--normal_from_iter N] [--depth_ratio R]]
                              [--lambda_dist L [--dist_from_iter N]]
+                             [--lambda_multi_view_geo L [--multi_view_sources K] [--multi_view_from_iter N]
+                              [--multi_view_pix_max P]]
 
 ``--strategy mcmc --cap_max N`` (both forms) densifies the MCMC way (``mcmc.py``): a budget of N Gaussians, dead ones
 relocated onto live ones, 5 % growth a round, position noise and L1 priors on opacity and scale.
@@ -22,6 +24,10 @@ surface to be ``(1 - R) expected + R median`` depth: 2DGS uses 0 for unbounded s
 ``--lambda_dist L`` (both forms; off by default) adds the depth-distortion term of 2DGS from iteration
 ``--dist_from_iter`` on: ``L`` times the mean of the rasterizer's distortion map, which pulls every ray's blending weights
 together in depth.  2DGS uses 100 to 1000 from iteration 3000.
+``--lambda_multi_view_geo L`` (both forms; off by default) adds the multi-view geometric term of PGSR from iteration
+``--multi_view_from_iter`` on (``mvs.multi_view_geo_loss``): every view's ``--multi_view_sources`` nearest neighbours are
+chosen once (``select_source_views``), each iteration draws one of the frame's at random, renders it too, and penalises
+the forward-backward reprojection error between the two depth maps.  A view without neighbours trains without the term.
 ``--optimizer_type sparse_adam`` (both forms) steps only the Gaussians each frame saw (``optim.SparseGaussianAdam``).
 
 With ``-s`` the example trains on a dataset through ``Scene`` (``scene.py``) and saves
@@ -49,7 +55,8 @@ import types
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from mvs_gaussian_splatting_amd import GaussianModel, measure, prune_by_contribution, render  # noqa: E402
+from mvs_gaussian_splatting_amd import (GaussianModel, measure, prune_by_contribution, render,  # noqa: E402
+                                        select_source_views)
 from mvs_gaussian_splatting_amd.sh import SH2RGB  # noqa: E402
 from mvs_gaussian_splatting_amd.synthetic import PipelineParams, SyntheticGaussianModel, orbit_camera  # noqa: E402
 from mvs_gaussian_splatting_amd.trainer import (OptimizationParams, load_checkpoint, save_checkpoint,  # noqa: E402
@@ -127,20 +134,37 @@ def prune_step(model, cameras, pipe, bg, iteration, prune, log=print):
     return out
 
 
+def source_views(cameras, opt, n_sources):
+    """Per view the indices of its ``n_sources`` source views, computed once; None while the multi-view term is off."""
+    if not float(getattr(opt, "lambda_multi_view_geo", 0.0)) > 0.0:
+        return None
+    return select_source_views(cameras, n_sources)
+
+
+def draw_source(cameras, sources, index, rng):
+    """One of view ``index``'s source cameras at random; None when the term is off or the view has no source."""
+    if not sources or not sources[index]:
+        return None
+    return cameras[rng.choice(sources[index])]
+
+
 def train(model, problem, opt, first_iter=0, last_iter=None, dataset=None, pipe=None, seed=0, log=None, on_iteration=None,
-          prune=None):
+          prune=None, multi_view_sources=4):
     """Iterations ``first_iter + 1 .. last_iter`` (default ``opt.iterations``), as ``train.py:54`` counts them.  The
     device generator is seeded from the iteration number before each one, so that the draws of a densification are the
-    same in a resumed run as in an uninterrupted one.  ``prune``: ``prune_options``.  Returns the losses as device
-    tensors."""
+    same in a resumed run as in an uninterrupted one.  ``prune``: ``prune_options``.  ``multi_view_sources``: how many
+    source views each view gets while ``opt.lambda_multi_view_geo > 0``.  Returns the losses as device tensors."""
     cams, bg, _ = problem
     pipe = pipe or PipelineParams()
     losses = []
+    sources = source_views(cams, opt, multi_view_sources)
     for iteration in range(first_iter + 1, (last_iter or opt.iterations) + 1):
         torch.manual_seed(seed * 1_000_003 + iteration)
-        cam = cams[(iteration * 3) % len(cams)]
-        losses.append(training_iteration(model, cam, opt, pipe, bg, iteration, dataset=dataset,
-                                         cameras_extent=CAMERAS_EXTENT))
+        index = (iteration * 3) % len(cams)
+        source = draw_source(cams, sources, index, random.Random(seed * 1_000_003 + iteration))
+        losses.append(training_iteration(model, cams[index], opt, pipe, bg, iteration, dataset=dataset,
+                                         cameras_extent=CAMERAS_EXTENT,
+                                         **({"source_camera": source} if source is not None else {})))
         prune_step(model, cams, pipe, bg, iteration, prune, log)
         if on_iteration:
             on_iteration(iteration, model)
@@ -156,7 +180,9 @@ def strategy_options(args):
         raise SystemExit("--strategy mcmc needs --cap_max N, the budget of Gaussians")
     return dict(strategy=args.strategy, cap_max=args.cap_max, noise_lr=args.noise_lr, opacity_reg=args.opacity_reg,
                 scale_reg=args.scale_reg, lambda_normal=args.lambda_normal, normal_from_iter=args.normal_from_iter,
-                lambda_dist=args.lambda_dist, dist_from_iter=args.dist_from_iter, depth_ratio=args.depth_ratio)
+                lambda_dist=args.lambda_dist, dist_from_iter=args.dist_from_iter, depth_ratio=args.depth_ratio,
+                lambda_multi_view_geo=args.lambda_multi_view_geo, multi_view_from_iter=args.multi_view_from_iter,
+                multi_view_pix_max=args.multi_view_pix_max)
 
 
 def train_scene(args, dev):
@@ -189,13 +215,16 @@ def train_scene(args, dev):
         from mvs_gaussian_splatting_amd import PoseCamera
         train_cameras = [PoseCamera(c) for c in train_cameras]
         pose_optimizer = torch.optim.Adam([p for c in train_cameras for p in c.parameters()], lr=args.pose_lr)
+    sources = source_views(train_cameras, opt, args.multi_view_sources)
     for iteration in range(first_iter + 1, n + 1):
         if not stack:
-            stack = train_cameras.copy()
-        cam = stack.pop(random.randint(0, len(stack) - 1))
-        loss = training_iteration(model, cam, opt, pipe, bg, iteration, dataset=dataset,
+            stack = list(range(len(train_cameras)))
+        index = stack.pop(random.randint(0, len(stack) - 1))
+        source = draw_source(train_cameras, sources, index, random)
+        loss = training_iteration(model, train_cameras[index], opt, pipe, bg, iteration, dataset=dataset,
                                   cameras_extent=scene.cameras_extent, pose_optimizer=pose_optimizer,
-                                  train_exposure=args.train_exposure)
+                                  train_exposure=args.train_exposure,
+                                  **({"source_camera": source} if source is not None else {}))
         prune_step(model, train_cameras, pipe, bg, iteration, prune)
         if iteration % 10 == 0:
             print(f"iteration {iteration}: loss {float(loss):.5f}  points {model._xyz.shape[0]}")
@@ -255,6 +284,14 @@ def main(argv=None):
                     help="weight of the depth-distortion term (the rasterizer's distortion map); 2DGS uses 100 to 1000; 0: off")
     ap.add_argument("--dist_from_iter", type=int, default=OptimizationParams.dist_from_iter,
                     help="first iteration the term joins the loss at (2DGS: 3000)")
+    ap.add_argument("--lambda_multi_view_geo", type=float, default=OptimizationParams.lambda_multi_view_geo,
+                    help="weight of the multi-view geometric term (mvs.multi_view_geo_loss; PGSR's); 0: off")
+    ap.add_argument("--multi_view_sources", type=int, default=4,
+                    help="with --lambda_multi_view_geo: source views per view (select_source_views), one drawn an iteration")
+    ap.add_argument("--multi_view_from_iter", type=int, default=OptimizationParams.multi_view_from_iter,
+                    help="first iteration the term joins the loss at (PGSR: 7000)")
+    ap.add_argument("--multi_view_pix_max", type=float, default=OptimizationParams.multi_view_pix_max,
+                    help="reprojection error, in pixels, below which a pixel takes part in the term (PGSR: 1)")
     ap.add_argument("--out", default=os.path.dirname(os.path.abspath(__file__)))
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
@@ -280,7 +317,7 @@ def main(argv=None):
             print(f"[ITER {iteration}] saved checkpoint {path}")
 
     losses = train(model, problem, opt, first_iter, dataset=dataset, log=print, on_iteration=on_iteration,
-                   prune=prune_options(args))
+                   prune=prune_options(args), multi_view_sources=args.multi_view_sources)
     ply = os.path.join(args.out, "point_cloud.ply")
     model.save_ply(ply)
     if losses:

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 34
+#define GSR_ABI_VERSION 35
 
 enum {
   GSR_OK = 0,
@@ -1022,6 +1022,29 @@ int gsr_mvs_consistency(const float* depth, int32_t H, int32_t W, float fx, floa
  * not positive and finite, a NULL pointer; GSR_E_ALIGN: 4 bytes. */
 int gsr_depth_backproject(const float* depth, int32_t H, int32_t W, float fx, float fy, const float* cam_to_world,
                           float* xyz, void* stream);
+
+/* ---- Multi-view geometric consistency loss, value and gradients, ABI v35 (csrc/mvs_loss.hip; mvs.multi_view_geo_loss;
+ * DESIGN.md §7.22).  The multi-view geometric term of PGSR on one (reference, source) pair: per reference pixel with
+ * depth, the round trip of gsr_mvs_consistency (the same code, the same bits) up to (ub, vb, zb); phi = sqrt(du^2 + dv^2).
+ * The pixel is valid when every gate of that check passes (zs > 0.2, the 2 x 2 footprint inside the source, four taps > 0,
+ * zb > 0.2), phi < pix_max, and -- only with depth_thresh > 0 -- |zb - d| < depth_thresh d.  With w = exp(-phi) held
+ * constant: raw = sum_valid w phi, n = the number of valid pixels, loss = raw / max(n, 1).
+ * source: ONE GsrMvsSource row in device memory.  record (device, float[4]): (loss, n as uint32 bits, raw, 0), written.
+ * grad_ref [H,W], may be NULL: d raw / d ref_depth, every pixel written (zero where not valid).  grad_src [src_H,src_W],
+ * may be NULL: d raw / d source depth, zeroed on the stream by this call, then accumulated with float atomic adds.  Both
+ * are UNIT gradients of raw: the caller applies upstream / max(n, 1).  src_H, src_W size the zeroing of grad_src and must
+ * equal the row's height and width (the row lives on the device and is not read here; the kernel leaves grad_src zero
+ * when they differ); they are ignored when grad_src is NULL.  record and grad_ref are the same bits from run to run;
+ * grad_src is NOT (the order of the atomic additions varies).  workspace: gsr_mvs_geo_loss_workspace_bytes(H, W) bytes,
+ * 8-byte aligned (per-workgroup partial sums); the size is 0 for a shape the call refuses.
+ * Checked before any HIP call: GSR_E_BADARG for NULL ref_depth / source / record / workspace, H or W < 1, H W > 2^28 or a
+ * launch of 2^32 work-items or more, fx / fy / pix_max not positive and finite, a NaN depth_thresh (<= 0: the depth test
+ * is off), a bad src_H / src_W with grad_src; GSR_E_ALIGN for the float arrays (4 bytes), the row and the workspace (8).
+ * Asynchronous, allocates nothing, reads nothing back. */
+size_t gsr_mvs_geo_loss_workspace_bytes(int32_t H, int32_t W);
+int gsr_mvs_geo_loss_fwd_bwd(const float* ref_depth, int32_t H, int32_t W, float fx, float fy, const GsrMvsSource* source,
+                             float pix_max, float depth_thresh, float* record, float* grad_ref, float* grad_src,
+                             int32_t src_H, int32_t src_W, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

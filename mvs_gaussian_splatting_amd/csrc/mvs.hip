@@ -46,29 +46,15 @@
 // the caller's error (mvs.depth_consistency checks every source against its camera before it builds the table).
 #include "gsr_common.h"
 #include "gsr_entry.h"
-
-#ifndef MVS_TILE_X
-#define MVS_TILE_X 64
-#endif
+#include "mvs_geom.h"      // the round trip, shared with mvs_loss.hip: MVS_TILE_X, MVS_BLOCK, mvs_transform, mvs_round_trip
 
 namespace gsr {
 
 namespace {
 
-constexpr int MVS_BLOCK = 256;
-constexpr int MVS_TILE_Y = MVS_BLOCK / MVS_TILE_X;
-static_assert(MVS_TILE_X * MVS_TILE_Y == MVS_BLOCK && MVS_TILE_X >= 1, "a tile is one 256-lane workgroup");
-
 struct Mat4 {
   float m[16];
 };
-
-// (x, y, z, 1) through M, row-vector convention, the association of the header comment
-__device__ inline void transform(const float* __restrict__ M, float x, float y, float z, float& ox, float& oy, float& oz) {
-  ox = ((x * M[0] + y * M[4]) + z * M[8]) + M[12];
-  oy = ((x * M[1] + y * M[5]) + z * M[9]) + M[13];
-  oz = ((x * M[2] + y * M[6]) + z * M[10]) + M[14];
-}
 
 __global__ __launch_bounds__(MVS_BLOCK) void mvs_consistency_kernel(const float* __restrict__ depth, int H, int W, float fx,
                                                                     float fy, const GsrMvsSource* __restrict__ sources,
@@ -93,31 +79,11 @@ __global__ __launch_bounds__(MVS_BLOCK) void mvs_consistency_kernel(const float*
   int n = 0;
   float sum = 0.0f;
   for (int s = 0; s < S; ++s) {
-    const GsrMvsSource& src = sources[s];                                // uniform across the wave: scalar loads
-    float xs, ys, zs;
-    transform(src.ref_to_src, xr, yr, d, xs, ys, zs);
-    if (!(zs > 0.2f)) continue;
-    const float Ws = (float)src.width, Hs = (float)src.height;
-    const float cxs = (Ws - 1.0f) * 0.5f, cys = (Hs - 1.0f) * 0.5f;
-    const float us = (src.fx * xs) / zs + cxs;
-    const float vs = (src.fy * ys) / zs + cys;
-    const float x0 = floorf(us), y0 = floorf(vs);
-    if (!(x0 >= 0.0f && x0 + 1.0f <= Ws - 1.0f && y0 >= 0.0f && y0 + 1.0f <= Hs - 1.0f)) continue;   // a NaN fails
-    const float ax = us - x0, ay = vs - y0;
-    const float* __restrict__ row0 = src.depth + (size_t)(int)y0 * (size_t)src.width + (size_t)(int)x0;
-    const float* __restrict__ row1 = row0 + src.width;
-    const float d00 = row0[0], d10 = row0[1], d01 = row1[0], d11 = row1[1];
-    if (!(d00 > 0.0f && d10 > 0.0f && d01 > 0.0f && d11 > 0.0f)) continue;
-    const float ds = (d00 * (1.0f - ax) + d10 * ax) * (1.0f - ay) + (d01 * (1.0f - ax) + d11 * ax) * ay;
-    const float xb0 = ((us - cxs) * ds) / src.fx, yb0 = ((vs - cys) * ds) / src.fy;
-    float xb, yb, zb;
-    transform(src.src_to_ref, xb0, yb0, ds, xb, yb, zb);
-    if (!(zb > 0.2f)) continue;
-    const float ub = (fx * xb) / zb + cx, vb = (fy * yb) / zb + cy;
-    const float du = ub - fpx, dv = vb - fpy;
-    if (du * du + dv * dv < pix2 && fabsf(zb - d) < dtol) {
+    MvsTrip t;                                                           // sources[s]: uniform across the wave, scalar loads
+    if (!mvs_round_trip(sources[s], fpx, fpy, cx, cy, fx, fy, xr, yr, d, t)) continue;
+    if (t.du * t.du + t.dv * t.dv < pix2 && fabsf(t.zb - d) < dtol) {
       n += 1;
-      sum += zb;
+      sum += t.zb;
     }
   }
   count[pix] = (uint8_t)n;
@@ -134,7 +100,7 @@ __global__ __launch_bounds__(MVS_BLOCK) void depth_backproject_kernel(const floa
   if (d > 0.0f) {
     const float cx = ((float)W - 1.0f) * 0.5f, cy = ((float)H - 1.0f) * 0.5f;
     const float xr = (((float)px - cx) * d) / fx, yr = (((float)py - cy) * d) / fy;
-    transform(c2w.m, xr, yr, d, x, y, z);
+    mvs_transform(c2w.m, xr, yr, d, x, y, z);
   }
   float* __restrict__ row = xyz + 3 * (size_t)pix;
   row[0] = x;
@@ -149,8 +115,6 @@ void launch_mvs_consistency(const float* depth, int H, int W, float fx, float fy
   hipLaunchKernelGGL(mvs_consistency_kernel, dim3(xtiles * ytiles), dim3(MVS_BLOCK), 0, s, depth, H, W, fx, fy, sources, S,
                      pix_thresh, depth_thresh, min_views, xtiles, count, fused);
 }
-
-inline bool positive_finite(float v) { return v > 0.0f && v - v == 0.0f; }   // false for NaN and +-inf
 
 }  // namespace
 
@@ -168,8 +132,8 @@ int gsr_mvs_consistency(const float* depth, int32_t H, int32_t W, float fx, floa
   if (!image_shape_ok(H, W)) return fail(GSR_E_BADARG, "H and W must be positive and H * W at most 2^28");
   if (S < 0 || S > GSR_MVS_MAX_SOURCES) return fail(GSR_E_BADARG, "S must lie in 0..64");
   if (S > 0 && !sources) return fail(GSR_E_BADARG, "the source table is NULL");
-  if (!positive_finite(fx) || !positive_finite(fy)) return fail(GSR_E_BADARG, "fx and fy must be positive and finite");
-  if (!positive_finite(pix_thresh) || !positive_finite(depth_thresh))
+  if (!mvs_positive_finite(fx) || !mvs_positive_finite(fy)) return fail(GSR_E_BADARG, "fx and fy must be positive and finite");
+  if (!mvs_positive_finite(pix_thresh) || !mvs_positive_finite(depth_thresh))
     return fail(GSR_E_BADARG, "pix_thresh and depth_thresh must be positive and finite");
   if (min_views < 0) return fail(GSR_E_BADARG, "min_views must not be negative");
   if (!aligned({depth, fused}, 3u)) return fail(GSR_E_ALIGN, "depth and fused must be 4-byte aligned");
@@ -183,7 +147,7 @@ int gsr_depth_backproject(const float* depth, int32_t H, int32_t W, float fx, fl
                           float* xyz, void* stream) {
   if (H < 0 || W < 0 || (int64_t)H * (int64_t)W > (int64_t)1 << 28)
     return fail(GSR_E_BADARG, "H and W must not be negative and H * W at most 2^28");
-  if (!positive_finite(fx) || !positive_finite(fy)) return fail(GSR_E_BADARG, "fx and fy must be positive and finite");
+  if (!mvs_positive_finite(fx) || !mvs_positive_finite(fy)) return fail(GSR_E_BADARG, "fx and fy must be positive and finite");
   if (!cam_to_world) return fail(GSR_E_BADARG, "cam_to_world is NULL");
   if (H == 0 || W == 0) return 0;
   if (!depth || !xyz) return fail(GSR_E_BADARG, "depth / xyz is NULL");

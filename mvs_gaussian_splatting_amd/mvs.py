@@ -1,10 +1,12 @@
 """Multi-view geometric consistency of rendered depth, and the fused point cloud it yields, on the HIP path
-(``csrc/mvs.hip`` behind ``gsr_mvs_consistency`` / ``gsr_depth_backproject``).
+(``csrc/mvs.hip`` behind ``gsr_mvs_consistency`` / ``gsr_depth_backproject``), and the same round trip as
+a training loss with gradients (``csrc/mvs_loss.hip`` behind ``gsr_mvs_geo_loss_fwd_bwd``).
 
     sources = select_source_views(cameras, n_sources=4)
     count, fused = depth_consistency(depths[i], cameras[i], [depths[j] for j in sources[i]], [cameras[j] for j in sources[i]])
     xyz, rgb = fuse_depth_points(scene.getTrainCameras(), gaussians, pipe, background)        # a DTU-style cloud
     fuse_views(cameras, gaussians, pipe, background, volume, consistency=dict(min_views=2))   # a filtered TSDF
+    loss = loss + 0.05 * multi_view_geo_loss(depth_i, cameras[i], depth_j, cameras[j])        # PGSR's multi-view term
 
 The check is MVSNet's / COLMAP's: a reference pixel is taken into a source view at its depth, the source's depth is read
 there (bilinear, only where all four neighbours hold depth), the result is taken back, and the pixel is consistent with
@@ -226,4 +228,104 @@ def fuse_depth_points(cameras, model, pipe, bg, *, n_sources: int = 4, min_views
     return torch.cat(xyz), torch.cat(rgb)
 
 
-__all__ = ["select_source_views", "depth_consistency", "backproject_depth", "fuse_depth_points"]
+# ---- the multi-view geometric loss (csrc/mvs_loss.hip) -------------------------------------------------
+def _loss_map(depth, camera, dev, what: str) -> Tuple[int, int, float, float]:
+    """``depth`` is a float32 ``[H,W]`` / ``[1,H,W]`` tensor of ``camera``'s size (on ``dev`` when given); it keeps its graph."""
+    H, W, fx, fy = _focal(camera)
+    if not isinstance(depth, torch.Tensor):
+        raise TypeError(f"multi_view_geo_loss: {what} must be a torch.Tensor, got {type(depth).__name__}")
+    if depth.dtype != torch.float32:
+        raise TypeError(f"multi_view_geo_loss: {what} must be float32, got {depth.dtype}")
+    if tuple(depth.shape) not in ((H, W), (1, H, W)):
+        raise ValueError(f"multi_view_geo_loss: {what} must be [{H},{W}] or [1,{H},{W}] like its camera, got "
+                         f"{tuple(depth.shape)}")
+    if dev is not None and depth.device != dev:
+        raise ValueError(f"multi_view_geo_loss: depth is on {dev}, {what} on {depth.device}")
+    if H * W > 2 ** 28:
+        raise ValueError(f"multi_view_geo_loss: {what} of {W} x {H} exceeds 2^28 pixels")
+    if dev is None and ((W + 63) // 64) * ((H + 3) // 4) * 256 >= 2 ** 32:     # the reference: one lane per pixel of a 64 x 4 tile
+        raise ValueError(f"multi_view_geo_loss: {what} of {W} x {H} needs a launch of 2^32 work-items or more (64 x 4 tiles)")
+    return H, W, fx, fy
+
+
+class _MultiViewGeo(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, depth, src_depth, H, W, fx, fy, Hs, Ws, row, pix_max, depth_thresh, holder):
+        lib = _lib.load()
+        dev = depth.device
+        need_ref, need_src = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        dc, sc = depth.contiguous(), src_depth.contiguous()
+        row.depth = sc.data_ptr()
+        record = torch.empty(4, dtype=torch.float32, device=dev)
+        ws = torch.empty(lib.gsr_mvs_geo_loss_workspace_bytes(H, W), dtype=torch.uint8, device=dev)     # block partials
+        g_ref = torch.empty((H, W), dtype=torch.float32, device=dev) if need_ref else None
+        g_src = torch.empty((Hs, Ws), dtype=torch.float32, device=dev) if need_src else None
+        with torch.cuda.device(dev):
+            table = torch.frombuffer(bytearray(bytes(row)), dtype=torch.uint8).to(dev)      # the one small upload
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.gsr_mvs_geo_loss_fwd_bwd(dc.data_ptr(), H, W, fx, fy, table.data_ptr(), pix_max, depth_thresh,
+                                                    record.data_ptr(), None if g_ref is None else g_ref.data_ptr(),
+                                                    None if g_src is None else g_src.data_ptr(), Hs, Ws, ws.data_ptr(),
+                                                    stream), "gsr_mvs_geo_loss_fwd_bwd")
+        if need_ref or need_src:
+            # 1 / max(n_valid, 1) from the record, on the device: the backward's one factor besides the upstream gradient
+            inv_n = record.view(torch.int32)[1].clamp(min=1).to(torch.float32).reciprocal()
+            ctx.save_for_backward(inv_n, *(g for g in (g_ref, g_src) if g is not None))
+        ctx.shapes = (depth.shape, src_depth.shape)
+        holder.append(record)
+        return record[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        inv_n, *units = ctx.saved_tensors
+        k = g.to(torch.float32) * inv_n                              # a 0-dim device tensor: never .item()
+        units = iter(units)
+        out = [(next(units) * k).view(shape) if need else None
+               for shape, need in zip(ctx.shapes, ctx.needs_input_grad[:2])]
+        return (*out, None, None, None, None, None, None, None, None, None, None)
+
+
+def multi_view_geo_loss(depth: torch.Tensor, camera, src_depth: torch.Tensor, src_camera, *, pix_max: float = 1.0,
+                        depth_thresh: Optional[float] = None, return_record: bool = False):
+    """The multi-view geometric term of PGSR between a frame and one neighbouring frame, a 0-dim device tensor with
+    gradients to ``depth`` and ``src_depth`` (each only where it requires one).  ``depth`` float32 ``[H,W]`` or ``[1,H,W]``
+    on a ROCm GPU, 0 where there is none; ``src_depth`` the depth map of ``src_camera``, of that camera's size, which may
+    differ; the cameras as ``depth_consistency`` reads them.  A reference pixel makes the round trip of
+    ``depth_consistency`` (the same code, the same bits) and lands ``phi`` pixels from where it started; it is valid when
+    every gate of that check passes, ``phi < pix_max`` (PGSR: 1) and, with ``depth_thresh`` given (default None: no depth
+    test, as in PGSR), the round-trip depth is within ``depth_thresh`` (relative) of its own.  The loss is
+    ``sum_valid exp(-phi) phi / max(n_valid, 1)`` with the weight ``exp(-phi)`` held constant; which pixels are valid is a
+    decision and carries no gradient.  One kernel call computes the value and the unit gradients the inputs need; the
+    backward multiplies them by ``upstream / max(n_valid, 1)`` on the device.  Nothing the kernel writes is read back.  The
+    two ``world_view_transform``s are read on the host, where the float64 products are formed: for cameras that keep them
+    on the GPU that is two 64-byte device-to-host copies, one synchronisation per call (as in ``depth_consistency``).  The value and the
+    gradient to ``depth`` are the same bits from run to run; the gradient to ``src_depth`` is accumulated with float
+    atomic adds and is NOT bit-reproducible.  No camera gradients.  No CPU path.
+    return_record: also return the kernel's record, float32 ``[4]`` on the device: ``(loss, n_valid as uint32 bits, the
+    raw sum, 0)`` (``record.view(torch.int32)[1]`` is the number of valid pixels)."""
+    pix_max = float(pix_max)
+    if not pix_max > 0.0 or not math.isfinite(pix_max):
+        raise ValueError(f"multi_view_geo_loss: pix_max must be positive and finite, got {pix_max}")
+    if depth_thresh is not None:
+        depth_thresh = float(depth_thresh)
+        if not depth_thresh > 0.0 or not math.isfinite(depth_thresh):
+            raise ValueError(f"multi_view_geo_loss: depth_thresh must be None or positive and finite, got {depth_thresh}")
+    H, W, fx, fy = _loss_map(depth, camera, None, "depth")
+    Hs, Ws, fxs, fys = _loss_map(src_depth, src_camera, depth.device, "src_depth")
+    M_ref, M_src = _view64(camera), _view64(src_camera)
+    row = _lib.GsrMvsSource()
+    row.width, row.height, row.fx, row.fy = Ws, Hs, fxs, fys       # the size grad_src is zeroed by is the row's own
+    A = (np.linalg.inv(M_ref) @ M_src).astype(np.float32).reshape(-1)
+    B = (np.linalg.inv(M_src) @ M_ref).astype(np.float32).reshape(-1)
+    for i in range(16):
+        row.ref_to_src[i], row.src_to_ref[i] = float(A[i]), float(B[i])
+    if not depth.is_cuda:
+        raise _lib.GsrError("multi_view_geo_loss needs the depth maps on a ROCm GPU (no CPU path)")
+    holder = []
+    loss = _MultiViewGeo.apply(depth, src_depth, H, W, fx, fy, Hs, Ws, row, pix_max,
+                               0.0 if depth_thresh is None else depth_thresh, holder)
+    return (loss, holder[0]) if return_record else loss
+
+
+__all__ = ["select_source_views", "depth_consistency", "backproject_depth", "fuse_depth_points",
+           "multi_view_geo_loss"]

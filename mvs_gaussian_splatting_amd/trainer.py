@@ -19,8 +19,10 @@ import torch
 from .densify import densify_and_prune, is_fork
 from .losses import add_densification_stats, l1_dssim_loss, opacity_sparsity_loss
 from .mcmc import add_new_gs, inject_noise, mcmc_regularizer, relocate_gs
+from .mvs import multi_view_geo_loss
 from .normal_consistency import normal_consistency_loss
 from .renderer import render
+from .surface import surface_depth
 from .synthetic import PipelineParams  # noqa: F401  (the two parameter classes live side by side)
 
 
@@ -75,6 +77,12 @@ class OptimizationParams:
     # as it is
     lambda_dist = 0.0
     dist_from_iter = 3000
+    # multi-view geometric consistency (mvs.multi_view_geo_loss; PGSR's multi-view term, from iteration 7000 there):
+    # the forward-backward reprojection error between the frame and training_iteration(source_camera=), valid below
+    # multi_view_pix_max pixels; reads depth_ratio for the surface depth of both frames; 0 leaves the iteration as it is
+    lambda_multi_view_geo = 0.0
+    multi_view_from_iter = 7000
+    multi_view_pix_max = 1.0
 
     def __init__(self, **overrides):
         for k, v in overrides.items():
@@ -97,7 +105,7 @@ def schedule(opt, iteration: int, white_background: bool = False) -> dict:
 
 def training_iteration(model, camera, opt, pipe, background, iteration, *, dataset=None, cameras_extent,
                        first_reset=None, gt_image=None, densify_kwargs=None, pose_optimizer=None, depth_loss=None,
-                       train_exposure=False, mcmc_kwargs=None):
+                       train_exposure=False, mcmc_kwargs=None, source_camera=None):
     """``train.py:72-142`` for one camera, in the reference's order: learning rate, SH degree, background, ``render``
     with the fork's keyword arguments, L1 + D-SSIM against ``camera.original_image``, the opacity sparsity term
     (``opt.opacitysparse``), ``backward``; then, without gradients, the densification statistics, ``densify_and_prune``,
@@ -138,7 +146,15 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
     [0, 1].  ``depth_ratio = 0``, or the normal term off: exactly the calls made without it.
     ``opt.lambda_dist > 0`` from ``opt.dist_from_iter`` on: the frame is rendered with ``return_distortion=True`` and
     ``lambda_dist * distortion.mean()`` joins the loss; statistics, combinations and refusals as for ``lambda_normal``.
-    ``lambda_dist = 0``: exactly the calls made without it."""
+    ``lambda_dist = 0``: exactly the calls made without it.
+    ``opt.lambda_multi_view_geo > 0`` from ``opt.multi_view_from_iter`` on: ``source_camera`` (one of the frame's
+    ``mvs.select_source_views``) is required, ``ValueError`` without it.  The frame is rendered with ``return_depth=True``
+    (and ``return_median_depth=True`` when ``opt.depth_ratio > 0``), the source camera once more with the same options and
+    background -- its colour enters no loss term -- and ``lambda_multi_view_geo * multi_view_geo_loss(surface, camera,
+    source surface, source_camera, pix_max=opt.multi_view_pix_max)`` joins the loss before the one ``backward``, both
+    surfaces from ``surface.surface_depth(..., opt.depth_ratio)``.  Densification statistics come from the main frame
+    only; a ``sparse_adam`` step takes the rows either frame saw.  Refusals as for ``lambda_normal``.  With the term off
+    ``source_camera`` is ignored: exactly the calls made without it."""
     strategy = getattr(opt, "strategy", "default")
     if strategy not in ("default", "mcmc"):
         raise ValueError(f"strategy must be 'default' or 'mcmc', got {strategy!r}")
@@ -166,7 +182,20 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
                                                    "learn_split_scale")):
             raise ValueError("lambda_normal > 0 does not support the fork's grow / learned-split models: render refuses "
                              "return_depth / return_normals on their frames (virtual rows appended)")
-    depth_ratio = float(getattr(opt, "depth_ratio", 0.0)) if normal_on else 0.0
+    mv_on = (float(getattr(opt, "lambda_multi_view_geo", 0.0)) > 0.0
+             and iteration >= int(getattr(opt, "multi_view_from_iter", 0)))
+    if mv_on:
+        if source_camera is None:
+            raise ValueError("lambda_multi_view_geo > 0 needs source_camera, a neighbouring view of the frame "
+                             "(mvs.select_source_views)")
+        if pose_optimizer is not None:
+            raise ValueError("lambda_multi_view_geo > 0 does not combine with pose_optimizer: the depth maps and the "
+                             "multi-view term carry no camera gradient")
+        if is_fork(model) or any(flag(n) for n in ("grow_dir", "continous_dir", "learn_split_distance",
+                                                   "learn_split_scale")):
+            raise ValueError("lambda_multi_view_geo > 0 does not support the fork's grow / learned-split models: render "
+                             "refuses return_depth on their frames (virtual rows appended)")
+    depth_ratio = float(getattr(opt, "depth_ratio", 0.0)) if normal_on or mv_on else 0.0
     if not 0.0 <= depth_ratio <= 1.0:
         raise ValueError(f"opt.depth_ratio must lie in [0, 1], got {depth_ratio}")
     median_on = depth_ratio > 0.0
@@ -186,14 +215,15 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
     if todo["sh_up"]:                                                                           # :75-76
         model.oneupSHdegree()
     bg = torch.rand((3), device=background.device) if opt.random_background else background    # :89
-    pkg = render(camera, model, pipe, bg, grow_dir=flag("grow_dir"), densify_grad_threshold=opt.densify_grad_threshold,
-                 iteration=iteration, opt=opt, continous_dir=flag("continous_dir"), grow_distance=flag("grow_distance"),
-                 modelcg=dataset, cameras_extent=cameras_extent,                                # :91
-                 **({"return_depth": True} if depth_loss is not None or normal_on else {}),
-                 **({"return_normals": True} if normal_on else {}),
-                 **({"return_distortion": True} if dist_on else {}),
-                 **({"return_median_depth": True} if median_on else {}),
-                 **({"use_trained_exp": True} if train_exposure else {}))
+    render_kwargs = dict(grow_dir=flag("grow_dir"), densify_grad_threshold=opt.densify_grad_threshold,
+                         iteration=iteration, opt=opt, continous_dir=flag("continous_dir"),
+                         grow_distance=flag("grow_distance"), modelcg=dataset, cameras_extent=cameras_extent,
+                         **({"return_depth": True} if depth_loss is not None or normal_on or mv_on else {}),
+                         **({"return_normals": True} if normal_on else {}),
+                         **({"return_distortion": True} if dist_on else {}),
+                         **({"return_median_depth": True} if median_on else {}),
+                         **({"use_trained_exp": True} if train_exposure else {}))
+    pkg = render(camera, model, pipe, bg, **render_kwargs)                                      # :91
     gt = camera.original_image if gt_image is None else gt_image
     loss = l1_dssim_loss(pkg["render"], gt.to(pkg["render"].device), opt.lambda_dssim)          # :99-101
     if opt.opacitysparse > 0:                                                                   # :102-106
@@ -209,6 +239,13 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
             **({"median": pkg["median_depth"], "depth_ratio": depth_ratio} if median_on else {}))
     if dist_on:
         loss = loss + float(opt.lambda_dist) * pkg["distortion"].mean()
+    src_pkg = None
+    if mv_on:
+        src_pkg = render(source_camera, model, pipe, bg, **render_kwargs)        # for its depth: the colour enters no term
+        surfaces = [surface_depth(p["depth"], p["alpha"], p["median_depth"] if median_on else None, depth_ratio)
+                    for p in (pkg, src_pkg)]
+        loss = loss + float(opt.lambda_multi_view_geo) * multi_view_geo_loss(
+            surfaces[0], camera, surfaces[1], source_camera, pix_max=float(getattr(opt, "multi_view_pix_max", 1.0)))
     loss.backward()                                                                             # :107
     with torch.no_grad():
         if mcmc:
@@ -230,6 +267,8 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
                 visibility = pkg["visibility_filter"]
                 if pkg["selected_pts_mask"] is not None:
                     visibility = visibility | pkg["selected_pts_mask"]
+                if src_pkg is not None:
+                    visibility = visibility | src_pkg["visibility_filter"]       # the source frame's rows have gradients too
                 dense = ("opacity", "scaling") if mcmc else (("opacity",) if opt.opacitysparse > 0 else ())
                 model.optimizer.step(visibility, dense=dense)
             else:
