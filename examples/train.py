@@ -14,6 +14,7 @@ SH degree steps, densification, opacity resets, the optional opacity sparsity te
                              [--lambda_dist L [--dist_from_iter N]]
                              [--lambda_multi_view_geo L [--multi_view_sources K] [--multi_view_from_iter N]
                               [--multi_view_pix_max P]]
+                             [--lambda_multi_view_ncc L [--multi_view_ncc_samples N] [--multi_view_patch_radius R]]
 
 ``--strategy mcmc --cap_max N`` (both forms) densifies the MCMC way (``mcmc.py``): a budget of N Gaussians, dead ones
 relocated onto live ones, 5 % growth a round, position noise and L1 priors on opacity and scale.
@@ -28,6 +29,11 @@ together in depth.  2DGS uses 100 to 1000 from iteration 3000.
 ``--multi_view_from_iter`` on (``mvs.multi_view_geo_loss``): every view's ``--multi_view_sources`` nearest neighbours are
 chosen once (``select_source_views``), each iteration draws one of the frame's at random, renders it too, and penalises
 the forward-backward reprojection error between the two depth maps.  A view without neighbours trains without the term.
+``--lambda_multi_view_ncc L`` (both forms; off by default; PGSR: 0.15) adds the multi-view photometric term of PGSR from
+the same iteration on (``mvs.multi_view_ncc_loss``): at ``--multi_view_ncc_samples`` pixels drawn per iteration the
+``(2R+1)^2`` patch (``--multi_view_patch_radius``) of the frame's photograph is carried into the source's by the homography
+of the rendered plane, and one minus their normalised cross-correlation is penalised.  Sources are selected when either
+multi-view weight is positive; the one source render serves both terms.
 ``--optimizer_type sparse_adam`` (both forms) steps only the Gaussians each frame saw (``optim.SparseGaussianAdam``).
 
 With ``-s`` the example trains on a dataset through ``Scene`` (``scene.py``) and saves
@@ -135,8 +141,8 @@ def prune_step(model, cameras, pipe, bg, iteration, prune, log=print):
 
 
 def source_views(cameras, opt, n_sources):
-    """Per view the indices of its ``n_sources`` source views, computed once; None while the multi-view term is off."""
-    if not float(getattr(opt, "lambda_multi_view_geo", 0.0)) > 0.0:
+    """Per view the indices of its ``n_sources`` source views, computed once; None while both multi-view terms are off."""
+    if not (float(getattr(opt, "lambda_multi_view_geo", 0.0)) > 0.0 or float(getattr(opt, "lambda_multi_view_ncc", 0.0)) > 0.0):
         return None
     return select_source_views(cameras, n_sources)
 
@@ -153,7 +159,7 @@ def train(model, problem, opt, first_iter=0, last_iter=None, dataset=None, pipe=
     """Iterations ``first_iter + 1 .. last_iter`` (default ``opt.iterations``), as ``train.py:54`` counts them.  The
     device generator is seeded from the iteration number before each one, so that the draws of a densification are the
     same in a resumed run as in an uninterrupted one.  ``prune``: ``prune_options``.  ``multi_view_sources``: how many
-    source views each view gets while ``opt.lambda_multi_view_geo > 0``.  Returns the losses as device tensors."""
+    source views each view gets while ``opt.lambda_multi_view_geo > 0`` or ``opt.lambda_multi_view_ncc > 0``.  Returns the losses as device tensors."""
     cams, bg, _ = problem
     pipe = pipe or PipelineParams()
     losses = []
@@ -182,7 +188,8 @@ def strategy_options(args):
                 scale_reg=args.scale_reg, lambda_normal=args.lambda_normal, normal_from_iter=args.normal_from_iter,
                 lambda_dist=args.lambda_dist, dist_from_iter=args.dist_from_iter, depth_ratio=args.depth_ratio,
                 lambda_multi_view_geo=args.lambda_multi_view_geo, multi_view_from_iter=args.multi_view_from_iter,
-                multi_view_pix_max=args.multi_view_pix_max)
+                multi_view_pix_max=args.multi_view_pix_max, lambda_multi_view_ncc=args.lambda_multi_view_ncc,
+                multi_view_ncc_samples=args.multi_view_ncc_samples, multi_view_patch_radius=args.multi_view_patch_radius)
 
 
 def train_scene(args, dev):
@@ -292,6 +299,12 @@ def main(argv=None):
                     help="first iteration the term joins the loss at (PGSR: 7000)")
     ap.add_argument("--multi_view_pix_max", type=float, default=OptimizationParams.multi_view_pix_max,
                     help="reprojection error, in pixels, below which a pixel takes part in the term (PGSR: 1)")
+    ap.add_argument("--lambda_multi_view_ncc", type=float, default=OptimizationParams.lambda_multi_view_ncc,
+                    help="weight of the multi-view photometric (NCC) term (mvs.multi_view_ncc_loss; PGSR: 0.15); 0: off")
+    ap.add_argument("--multi_view_ncc_samples", type=int, default=OptimizationParams.multi_view_ncc_samples,
+                    help="with --lambda_multi_view_ncc: pixels drawn per iteration (PGSR: 102400)")
+    ap.add_argument("--multi_view_patch_radius", type=int, default=OptimizationParams.multi_view_patch_radius,
+                    help="with --lambda_multi_view_ncc: the patch is (2R+1)^2 pixels, R in 1..4 (PGSR: 3)")
     ap.add_argument("--out", default=os.path.dirname(os.path.abspath(__file__)))
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")

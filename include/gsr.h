@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 35
+#define GSR_ABI_VERSION 36
 
 enum {
   GSR_OK = 0,
@@ -1045,6 +1045,34 @@ size_t gsr_mvs_geo_loss_workspace_bytes(int32_t H, int32_t W);
 int gsr_mvs_geo_loss_fwd_bwd(const float* ref_depth, int32_t H, int32_t W, float fx, float fy, const GsrMvsSource* source,
                              float pix_max, float depth_thresh, float* record, float* grad_ref, float* grad_src,
                              int32_t src_H, int32_t src_W, void* workspace, void* stream);
+
+/* ---- Multi-view photometric (NCC) loss, value and gradients, ABI v36 (csrc/mvs_ncc.hip; mvs.multi_view_ncc_loss;
+ * DESIGN.md §7.23).  The photometric half of PGSR's multi-view term on one (reference, source) pair: per reference pixel
+ * p with depth d > 0 and view-space normal N (camera-facing, any magnitude), the plane m = N / (d (N . r(p))) carries the
+ * (2 patch_radius + 1)^2 patch of ref_gray about p into src_gray (Y = r(q) A[0:3,0:3] + (m . r(q)) A[3,0:3], A =
+ * ref_to_src), where it is read bilinearly; ncc = clamp(1 - cross^2 / (var_r var_s + 1e-8), 0, 2) over the patch's sums.
+ * The pixel counts when its whole patch lies in the reference, |N|^2 > 1e-12, |N . r(p)| >= min_cos |N| |r(p)|, the round
+ * trip of gsr_mvs_consistency passes every gate with phi < pix_max, every tap has m . r(q) > 0, Y_z > 0 and its 2 x 2
+ * footprint inside the source, and ncc < ncc_max.  With w = exp(-phi) held constant: raw = sum_counted w ncc, n = the
+ * number of counted pixels, loss = raw / max(n, 1).  The float32 order of operations is the kernel file's header comment.
+ * ref_depth [H,W], ref_normal [3,H,W], ref_gray [H,W]; source: ONE GsrMvsSource row in device memory (its depth enters
+ * the weight and the gates only); src_gray: [source height, source width].  pixels: NULL (every pixel, n_pixels ignored
+ * beyond its range check) or n_pixels flat indices py W + px, one lane each; an index outside [0, H W) is skipped;
+ * duplicate indices are the caller's error.  record (device, float[4]): (loss, n as uint32 bits, raw, 0), written.
+ * grad_depth [H,W] and grad_normal [3,H,W], each may be NULL: d raw / d ref_depth and d raw / d ref_normal.  Without a
+ * list every pixel is written (zero where not counted); with one both maps are zeroed on the stream by this call and the
+ * listed pixels written.  No atomics: record and both gradients are the same bits from run to run.  workspace:
+ * gsr_mvs_ncc_loss_workspace_bytes(H, W, n_pixels) bytes (n_pixels = 0 for a call without a list), 8-byte aligned; the
+ * size is 0 for a shape the call refuses.
+ * Checked before any HIP call: GSR_E_BADARG for a NULL required pointer, H or W < 1, H W > 2^28 or a launch of 2^32
+ * work-items, n_pixels < 0 or > H W, patch_radius outside 1..4, non-positive or non-finite fx / fy / pix_max, ncc_max
+ * outside (0, 2], min_cos outside [0, 1); GSR_E_ALIGN for the float and index arrays (4 bytes), the row and the workspace
+ * (8).  Asynchronous, allocates nothing, reads nothing back. */
+size_t gsr_mvs_ncc_loss_workspace_bytes(int32_t H, int32_t W, int32_t n_pixels);
+int gsr_mvs_ncc_loss_fwd_bwd(const float* ref_depth, const float* ref_normal, const float* ref_gray, int32_t H, int32_t W,
+                             float fx, float fy, const GsrMvsSource* source, const float* src_gray, const int32_t* pixels,
+                             int32_t n_pixels, int32_t patch_radius, float pix_max, float ncc_max, float min_cos,
+                             float* record, float* grad_depth, float* grad_normal, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

@@ -23,7 +23,7 @@ from .surface import surface_depth  # noqa: F401
 from .mesh import connected_components, clean_mesh  # noqa: F401
 from .geometry_eval import NearestIndex, nearest_points, sample_surface, evaluate_points, evaluate_mesh  # noqa: F401
 from .mvs import (select_source_views, depth_consistency, backproject_depth, fuse_depth_points,  # noqa: F401
-                  multi_view_geo_loss)
+                  multi_view_geo_loss, multi_view_ncc_loss, gray_image)
 
 __all__ = ["Scene", "Camera", "MiniCam", "PoseCamera", "ModelParams", "load_image", "load_image_host",
            "GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "render", "l1_loss", "apply_exposure", "save_exposures", "load_exposures", "l1_dssim_loss",
@@ -34,4 +34,5 @@ __all__ = ["Scene", "Camera", "MiniCam", "PoseCamera", "ModelParams", "load_imag
            "bounding_sphere", "normal_consistency_loss", "depth_to_normals",
            "surface_depth", "connected_components", "clean_mesh", "NearestIndex", "nearest_points", "sample_surface",
            "evaluate_points", "evaluate_mesh", "select_source_views", "depth_consistency", "backproject_depth",
-           "fuse_depth_points", "multi_view_geo_loss"]
+           "fuse_depth_points", "multi_view_geo_loss", "multi_view_ncc_loss",
+           "gray_image"]

@@ -1,12 +1,16 @@
 """Multi-view geometric consistency of rendered depth, and the fused point cloud it yields, on the HIP path
 (``csrc/mvs.hip`` behind ``gsr_mvs_consistency`` / ``gsr_depth_backproject``), and the same round trip as
-a training loss with gradients (``csrc/mvs_loss.hip`` behind ``gsr_mvs_geo_loss_fwd_bwd``).
+a training loss with gradients (``csrc/mvs_loss.hip`` behind ``gsr_mvs_geo_loss_fwd_bwd``), and the
+photometric half of that loss, the patch NCC between the two photographs under the rendered plane's homography
+(``csrc/mvs_ncc.hip`` behind ``gsr_mvs_ncc_loss_fwd_bwd``).
 
     sources = select_source_views(cameras, n_sources=4)
     count, fused = depth_consistency(depths[i], cameras[i], [depths[j] for j in sources[i]], [cameras[j] for j in sources[i]])
     xyz, rgb = fuse_depth_points(scene.getTrainCameras(), gaussians, pipe, background)        # a DTU-style cloud
     fuse_views(cameras, gaussians, pipe, background, volume, consistency=dict(min_views=2))   # a filtered TSDF
     loss = loss + 0.05 * multi_view_geo_loss(depth_i, cameras[i], depth_j, cameras[j])        # PGSR's multi-view term
+    loss = loss + 0.15 * multi_view_ncc_loss(depth_i, normal_i, cameras[i].original_image, cameras[i],
+                                             depth_j, cameras[j].original_image, cameras[j], n_samples=102400)
 
 The check is MVSNet's / COLMAP's: a reference pixel is taken into a source view at its depth, the source's depth is read
 there (bilinear, only where all four neighbours hold depth), the result is taken back, and the pixel is consistent with
@@ -327,5 +331,185 @@ def multi_view_geo_loss(depth: torch.Tensor, camera, src_depth: torch.Tensor, sr
     return (loss, holder[0]) if return_record else loss
 
 
+# ---- the multi-view photometric (NCC) loss (csrc/mvs_ncc.hip) -------------------------------------------
+GRAY_WEIGHTS = (0.299, 0.587, 0.114)           # PGSR's (ITU-R BT.601)
+
+
+def gray_image(image, device=None) -> torch.Tensor:
+    """The grey image the NCC term compares -> float32 ``[H,W]``, contiguous, on ``device`` (default: the image's own).
+    ``image``: a float32 ``[3,H,W]`` tensor (``(0.299 R + 0.587 G) + 0.114 B``, PGSR's weights), a ``[H,W]`` / ``[1,H,W]``
+    tensor that is grey already, or a camera (anything with ``original_image``): its result is cached on the camera as
+    ``_gray_image`` and reused while ``original_image`` is the same tensor and the device the same, so training converts
+    (and, for cameras that keep their photographs on the host, uploads) each photograph once."""
+    if not isinstance(image, torch.Tensor):
+        photo = getattr(image, "original_image", None)
+        if not isinstance(photo, torch.Tensor):
+            raise TypeError(f"gray_image: expected a tensor or a camera with original_image, got {type(image).__name__}")
+        device = photo.device if device is None else torch.device(device)
+        cached = getattr(image, "_gray_image", None)
+        if cached is not None and cached[0] is photo and cached[1].device == device:
+            return cached[1]
+        gray = gray_image(photo).to(device)
+        try:
+            image._gray_image = (photo, gray)
+        except AttributeError:                 # a camera that takes no new attributes: converted every time
+            pass
+        return gray
+    if image.dtype != torch.float32:
+        raise TypeError(f"gray_image: the image must be float32, got {image.dtype}")
+    if image.dim() == 3 and image.shape[0] == 3:
+        r, g, b = image.detach().unbind(0)
+        gray = ((GRAY_WEIGHTS[0] * r + GRAY_WEIGHTS[1] * g) + GRAY_WEIGHTS[2] * b).contiguous()
+    elif image.dim() == 2 or (image.dim() == 3 and image.shape[0] == 1):
+        gray = image.detach().reshape(image.shape[-2:]).contiguous()
+    else:
+        raise ValueError(f"gray_image: the image must be [3,H,W], [1,H,W] or [H,W], got {tuple(image.shape)}")
+    return gray if device is None else gray.to(device)
+
+
+def _ncc_image(image, camera, dev, what: str):
+    """Checks ``image`` against ``camera`` -> the ``device`` argument of ``gray_image`` that puts its grey image on ``dev``:
+    a tensor must be there already, a camera's photograph is taken there."""
+    H, W = int(camera.image_height), int(camera.image_width)
+    is_tensor = isinstance(image, torch.Tensor)
+    photo = image if is_tensor else getattr(image, "original_image", None)
+    if not isinstance(photo, torch.Tensor):
+        raise TypeError(f"multi_view_ncc_loss: {what} must be a torch.Tensor or a camera, got {type(image).__name__}")
+    if photo.dtype != torch.float32:
+        raise TypeError(f"multi_view_ncc_loss: {what} must be float32, got {photo.dtype}")
+    if tuple(photo.shape) not in ((3, H, W), (1, H, W), (H, W)):
+        raise ValueError(f"multi_view_ncc_loss: {what} must be [3,{H},{W}], [1,{H},{W}] or [{H},{W}] like its camera, got "
+                         f"{tuple(photo.shape)}")
+    if is_tensor and photo.device != dev:
+        raise ValueError(f"multi_view_ncc_loss: depth is on {dev}, {what} on {photo.device}")
+    return None if is_tensor else dev
+
+
+class _MultiViewNcc(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, depth, normal, gray, src_depth, src_gray, pixels, H, W, fx, fy, row, radius, pix_max, ncc_max,
+                min_cos, holder):
+        lib = _lib.load()
+        dev = depth.device
+        need_d, need_n = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        dc, nc, sc = depth.contiguous(), normal.contiguous(), src_depth.contiguous()
+        row.depth = sc.data_ptr()
+        n_pixels = 0 if pixels is None else int(pixels.numel())
+        record = torch.empty(4, dtype=torch.float32, device=dev)
+        ws = torch.empty(lib.gsr_mvs_ncc_loss_workspace_bytes(H, W, n_pixels), dtype=torch.uint8, device=dev)
+        g_d = torch.empty((H, W), dtype=torch.float32, device=dev) if need_d else None
+        g_n = torch.empty((3, H, W), dtype=torch.float32, device=dev) if need_n else None
+        with torch.cuda.device(dev):
+            table = torch.frombuffer(bytearray(bytes(row)), dtype=torch.uint8).to(dev)      # the one small upload
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.gsr_mvs_ncc_loss_fwd_bwd(dc.data_ptr(), nc.data_ptr(), gray.data_ptr(), H, W, fx, fy,
+                                                    table.data_ptr(), src_gray.data_ptr(),
+                                                    None if pixels is None else pixels.data_ptr(), n_pixels, radius,
+                                                    pix_max, ncc_max, min_cos, record.data_ptr(),
+                                                    None if g_d is None else g_d.data_ptr(),
+                                                    None if g_n is None else g_n.data_ptr(), ws.data_ptr(), stream),
+                       "gsr_mvs_ncc_loss_fwd_bwd")
+        if need_d or need_n:
+            inv_n = record.view(torch.int32)[1].clamp(min=1).to(torch.float32).reciprocal()
+            ctx.save_for_backward(inv_n, *(g for g in (g_d, g_n) if g is not None))
+        ctx.shapes = (depth.shape, normal.shape)
+        holder.append(record)
+        return record[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        inv_n, *units = ctx.saved_tensors
+        k = g.to(torch.float32) * inv_n                              # a 0-dim device tensor: never .item()
+        units = iter(units)
+        out = [(next(units) * k).view(shape) if need else None
+               for shape, need in zip(ctx.shapes, ctx.needs_input_grad[:2])]
+        return (*out, *([None] * 14))
+
+
+def multi_view_ncc_loss(depth: torch.Tensor, normal: torch.Tensor, image, camera, src_depth: torch.Tensor, src_image,
+                        src_camera, *, patch_radius: int = 3, pix_max: float = 1.0, ncc_max: float = 0.9,
+                        min_cos: float = 0.05, n_samples: Optional[int] = None, generator=None, pixels=None,
+                        return_record: bool = False):
+    """The multi-view photometric term of PGSR between a frame and one neighbouring frame, a 0-dim device tensor with
+    gradients to ``depth`` and ``normal`` (each only where it requires one).  ``depth`` float32 ``[H,W]`` / ``[1,H,W]`` on
+    a ROCm GPU, 0 where there is none; ``normal`` float32 ``[3,H,W]``, the view-space map ``render(return_normals=True)``
+    gives (camera-facing, any magnitude: the term is of degree 0 in it, so it needs no normalisation and no division by
+    alpha); ``image`` / ``src_image`` the two photographs, float32 ``[3,H,W]`` (turned to grey by ``gray_image``), grey
+    ``[H,W]`` / ``[1,H,W]``, or the cameras themselves (``gray_image`` caches on them); ``src_depth`` the depth map of
+    ``src_camera``, of that camera's size, which may differ.  Per reference pixel the plane through its point with its
+    normal carries the ``(2 patch_radius + 1)^2`` patch about it into the source image (read bilinearly);
+    ``ncc = clamp(1 - cross^2 / (var_r var_s + 1e-8), 0, 2)`` over the patch's centred sums.  The pixel counts when its
+    patch lies inside the reference, the plane is not grazing (``|N . r| >= min_cos |N| |r|``), the round trip of
+    ``depth_consistency`` passes with ``phi < pix_max``, every tap lands inside the source in front of it, and
+    ``ncc < ncc_max``.  The loss is ``sum_counted exp(-phi) ncc / max(n_counted, 1)`` with ``exp(-phi)`` held constant;
+    which pixels count is a decision without gradient; the photographs and the source depth receive none.
+    n_samples: evaluate ``n_samples`` distinct pixels drawn uniformly from all ``H W`` on the device
+    (``torch.randperm(H W, device=, generator=)[:n_samples]``, nothing read back; at least ``H W``: every pixel); drawn
+    pixels that fail a gate simply do not count.  PGSR draws from the valid pixels instead, which needs a host
+    synchronisation to learn how many there are; here the share of drawn pixels that count is the share of valid ones.
+    pixels: an int32 tensor of distinct flat indices ``py W + px`` on the device instead (entries outside ``[0, H W)``
+    are skipped; duplicates are the caller's error).  Neither: every pixel.
+    One kernel call computes the value and the unit gradients; the backward multiplies them by ``upstream /
+    max(n_counted, 1)`` on the device.  Value and gradients are the same bits from run to run.  The two
+    ``world_view_transform``s are read on the host as in ``multi_view_geo_loss``.  No camera gradients.  No CPU path.
+    return_record: also return the kernel's record, float32 ``[4]``: ``(loss, n_counted as uint32 bits, raw sum, 0)``."""
+    name = "multi_view_ncc_loss"
+    if isinstance(patch_radius, bool) or not isinstance(patch_radius, int) or not 1 <= patch_radius <= 4:
+        raise ValueError(f"{name}: patch_radius must be an integer in 1..4, got {patch_radius!r}")
+    pix_max, ncc_max, min_cos = float(pix_max), float(ncc_max), float(min_cos)
+    if not pix_max > 0.0 or not math.isfinite(pix_max):
+        raise ValueError(f"{name}: pix_max must be positive and finite, got {pix_max}")
+    if not 0.0 < ncc_max <= 2.0:
+        raise ValueError(f"{name}: ncc_max must lie in (0, 2], got {ncc_max}")
+    if not 0.0 <= min_cos < 1.0:
+        raise ValueError(f"{name}: min_cos must lie in [0, 1), got {min_cos}")
+    if n_samples is not None and pixels is not None:
+        raise ValueError(f"{name}: give n_samples or pixels, not both")
+    if n_samples is not None and (isinstance(n_samples, bool) or not isinstance(n_samples, int) or n_samples < 1):
+        raise ValueError(f"{name}: n_samples must be a positive integer, got {n_samples!r}")
+    try:
+        H, W, fx, fy = _loss_map(depth, camera, None, "depth")
+        dev = depth.device
+        Hs, Ws, fxs, fys = _loss_map(src_depth, src_camera, dev, "src_depth")
+    except (TypeError, ValueError) as e:
+        raise type(e)(str(e).replace("multi_view_geo_loss", name)) from None
+    if not isinstance(normal, torch.Tensor):
+        raise TypeError(f"{name}: normal must be a torch.Tensor, got {type(normal).__name__}")
+    if normal.dtype != torch.float32:
+        raise TypeError(f"{name}: normal must be float32, got {normal.dtype}")
+    if tuple(normal.shape) != (3, H, W):
+        raise ValueError(f"{name}: normal must be [3,{H},{W}] like its camera, got {tuple(normal.shape)}")
+    if normal.device != dev:
+        raise ValueError(f"{name}: depth is on {dev}, normal on {normal.device}")
+    gray_dev, src_gray_dev = _ncc_image(image, camera, dev, "image"), _ncc_image(src_image, src_camera, dev, "src_image")
+    if pixels is not None:
+        if not isinstance(pixels, torch.Tensor) or pixels.dtype != torch.int32 or pixels.dim() != 1:
+            raise TypeError(f"{name}: pixels must be a 1-d int32 tensor, got {getattr(pixels, 'dtype', type(pixels).__name__)} "
+                            f"{tuple(getattr(pixels, 'shape', ()))}")
+        if not 1 <= pixels.numel() <= H * W:
+            raise ValueError(f"{name}: pixels must hold 1..{H * W} indices, got {pixels.numel()}")
+        if pixels.device != dev:
+            raise ValueError(f"{name}: depth is on {dev}, pixels on {pixels.device}")
+        pixels = pixels.contiguous()
+    if generator is not None and n_samples is None:
+        raise ValueError(f"{name}: generator is read only with n_samples")
+    M_ref, M_src = _view64(camera), _view64(src_camera)
+    row = _lib.GsrMvsSource()
+    row.width, row.height, row.fx, row.fy = Ws, Hs, fxs, fys
+    A = (np.linalg.inv(M_ref) @ M_src).astype(np.float32).reshape(-1)
+    B = (np.linalg.inv(M_src) @ M_ref).astype(np.float32).reshape(-1)
+    for i in range(16):
+        row.ref_to_src[i], row.src_to_ref[i] = float(A[i]), float(B[i])
+    if not depth.is_cuda:
+        raise _lib.GsrError(f"{name} needs the maps and the images on a ROCm GPU (no CPU path)")
+    gray, src_gray = gray_image(image, gray_dev), gray_image(src_image, src_gray_dev)
+    if n_samples is not None and n_samples < H * W:
+        pixels = torch.randperm(H * W, device=dev, generator=generator)[:n_samples].to(torch.int32)
+    holder = []
+    loss = _MultiViewNcc.apply(depth, normal, gray, src_depth, src_gray, pixels, H, W, fx, fy, row, patch_radius, pix_max,
+                               ncc_max, min_cos, holder)
+    return (loss, holder[0]) if return_record else loss
+
+
 __all__ = ["select_source_views", "depth_consistency", "backproject_depth", "fuse_depth_points",
-           "multi_view_geo_loss"]
+           "multi_view_geo_loss", "multi_view_ncc_loss", "gray_image"]

@@ -19,7 +19,7 @@ import torch
 from .densify import densify_and_prune, is_fork
 from .losses import add_densification_stats, l1_dssim_loss, opacity_sparsity_loss
 from .mcmc import add_new_gs, inject_noise, mcmc_regularizer, relocate_gs
-from .mvs import multi_view_geo_loss
+from .mvs import multi_view_geo_loss, multi_view_ncc_loss
 from .normal_consistency import normal_consistency_loss
 from .renderer import render
 from .surface import surface_depth
@@ -83,6 +83,14 @@ class OptimizationParams:
     lambda_multi_view_geo = 0.0
     multi_view_from_iter = 7000
     multi_view_pix_max = 1.0
+    # multi-view photometric consistency (mvs.multi_view_ncc_loss; PGSR's NCC term, weight 0.15 there): one minus the
+    # patch NCC between the frame's photograph and source_camera's under the homography of the rendered plane, at
+    # multi_view_ncc_samples pixels drawn per iteration; shares multi_view_from_iter and multi_view_pix_max with the
+    # geometric term; 0 leaves the iteration as it is, whatever the other three fields say
+    lambda_multi_view_ncc = 0.0
+    multi_view_ncc_samples = 102400
+    multi_view_patch_radius = 3
+    multi_view_ncc_max = 0.9
 
     def __init__(self, **overrides):
         for k, v in overrides.items():
@@ -154,7 +162,16 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
     source surface, source_camera, pix_max=opt.multi_view_pix_max)`` joins the loss before the one ``backward``, both
     surfaces from ``surface.surface_depth(..., opt.depth_ratio)``.  Densification statistics come from the main frame
     only; a ``sparse_adam`` step takes the rows either frame saw.  Refusals as for ``lambda_normal``.  With the term off
-    ``source_camera`` is ignored: exactly the calls made without it."""
+    ``source_camera`` is ignored: exactly the calls made without it.
+    ``opt.lambda_multi_view_ncc > 0`` from ``opt.multi_view_from_iter`` on: ``source_camera`` is required in the same way.
+    The frame is rendered with ``return_depth=True, return_normals=True`` (and the median under ``opt.depth_ratio > 0``),
+    the source camera once for its depth -- the one source render when both multi-view terms are on -- and
+    ``lambda_multi_view_ncc * multi_view_ncc_loss(surface, normal, camera, camera, source surface, source_camera,
+    source_camera, patch_radius=opt.multi_view_patch_radius, pix_max=opt.multi_view_pix_max,
+    ncc_max=opt.multi_view_ncc_max, n_samples=opt.multi_view_ncc_samples)`` joins the loss before the one ``backward``:
+    the photographs are the two cameras' ``original_image``, turned to grey once per camera (``mvs.gray_image``).
+    Statistics, the ``sparse_adam`` union and the refusals are the geometric term's.  ``lambda_multi_view_ncc = 0``:
+    exactly the calls made without it, whatever the other new fields say."""
     strategy = getattr(opt, "strategy", "default")
     if strategy not in ("default", "mcmc"):
         raise ValueError(f"strategy must be 'default' or 'mcmc', got {strategy!r}")
@@ -182,19 +199,21 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
                                                    "learn_split_scale")):
             raise ValueError("lambda_normal > 0 does not support the fork's grow / learned-split models: render refuses "
                              "return_depth / return_normals on their frames (virtual rows appended)")
-    mv_on = (float(getattr(opt, "lambda_multi_view_geo", 0.0)) > 0.0
-             and iteration >= int(getattr(opt, "multi_view_from_iter", 0)))
+    mv_from = int(getattr(opt, "multi_view_from_iter", 0))
+    geo_on = float(getattr(opt, "lambda_multi_view_geo", 0.0)) > 0.0 and iteration >= mv_from
+    ncc_on = float(getattr(opt, "lambda_multi_view_ncc", 0.0)) > 0.0 and iteration >= mv_from
+    mv_on = geo_on or ncc_on
     if mv_on:
+        which = "lambda_multi_view_geo > 0" if geo_on else "lambda_multi_view_ncc > 0"
         if source_camera is None:
-            raise ValueError("lambda_multi_view_geo > 0 needs source_camera, a neighbouring view of the frame "
-                             "(mvs.select_source_views)")
+            raise ValueError(f"{which} needs source_camera, a neighbouring view of the frame (mvs.select_source_views)")
         if pose_optimizer is not None:
-            raise ValueError("lambda_multi_view_geo > 0 does not combine with pose_optimizer: the depth maps and the "
-                             "multi-view term carry no camera gradient")
+            raise ValueError(f"{which} does not combine with pose_optimizer: the depth maps and the multi-view term carry "
+                             "no camera gradient")
         if is_fork(model) or any(flag(n) for n in ("grow_dir", "continous_dir", "learn_split_distance",
                                                    "learn_split_scale")):
-            raise ValueError("lambda_multi_view_geo > 0 does not support the fork's grow / learned-split models: render "
-                             "refuses return_depth on their frames (virtual rows appended)")
+            raise ValueError(f"{which} does not support the fork's grow / learned-split models: render refuses "
+                             "return_depth on their frames (virtual rows appended)")
     depth_ratio = float(getattr(opt, "depth_ratio", 0.0)) if normal_on or mv_on else 0.0
     if not 0.0 <= depth_ratio <= 1.0:
         raise ValueError(f"opt.depth_ratio must lie in [0, 1], got {depth_ratio}")
@@ -219,7 +238,7 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
                          iteration=iteration, opt=opt, continous_dir=flag("continous_dir"),
                          grow_distance=flag("grow_distance"), modelcg=dataset, cameras_extent=cameras_extent,
                          **({"return_depth": True} if depth_loss is not None or normal_on or mv_on else {}),
-                         **({"return_normals": True} if normal_on else {}),
+                         **({"return_normals": True} if normal_on or ncc_on else {}),
                          **({"return_distortion": True} if dist_on else {}),
                          **({"return_median_depth": True} if median_on else {}),
                          **({"use_trained_exp": True} if train_exposure else {}))
@@ -244,8 +263,16 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
         src_pkg = render(source_camera, model, pipe, bg, **render_kwargs)        # for its depth: the colour enters no term
         surfaces = [surface_depth(p["depth"], p["alpha"], p["median_depth"] if median_on else None, depth_ratio)
                     for p in (pkg, src_pkg)]
-        loss = loss + float(opt.lambda_multi_view_geo) * multi_view_geo_loss(
-            surfaces[0], camera, surfaces[1], source_camera, pix_max=float(getattr(opt, "multi_view_pix_max", 1.0)))
+        pix_max = float(getattr(opt, "multi_view_pix_max", 1.0))
+        if geo_on:
+            loss = loss + float(opt.lambda_multi_view_geo) * multi_view_geo_loss(
+                surfaces[0], camera, surfaces[1], source_camera, pix_max=pix_max)
+        if ncc_on:
+            loss = loss + float(opt.lambda_multi_view_ncc) * multi_view_ncc_loss(
+                surfaces[0], pkg["normal"], camera, camera, surfaces[1], source_camera, source_camera,
+                patch_radius=int(getattr(opt, "multi_view_patch_radius", 3)), pix_max=pix_max,
+                ncc_max=float(getattr(opt, "multi_view_ncc_max", 0.9)),
+                n_samples=int(getattr(opt, "multi_view_ncc_samples", 102400)))
     loss.backward()                                                                             # :107
     with torch.no_grad():
         if mcmc:
