@@ -4,7 +4,7 @@ the surface by marching tetrahedra, all on the HIP path (``mvs_gaussian_splattin
     python examples/extract_mesh.py -m <model directory> [--iteration N] [--voxel_size S | --resolution R]
                                     [--sdf_trunc T] [--alpha_min A] [--max_depth D] [--depth_ratio R]
                                     [--num_cluster N] [--min_cluster_faces M] [--unbounded [--mesh_res N]]
-                                    [--consistent K] [--n_sources S] [--points]
+                                    [--consistent K] [--n_sources S] [--points] [--unbiased_depth]
                                     [-s <dataset>] [-r ...]
 
 The scene is loaded as ``examples/render.py`` loads it (``cfg_args.json`` of the model directory; ``-s`` and the other
@@ -31,6 +31,10 @@ back through the inverse contraction.  The mesh is written as ``tsdf_mesh_unboun
 where and as deep as it does, so floaters and depth that hangs between two surfaces never reach the volume.  ``--points``
 also writes ``fused_points.ply`` next to the mesh: the fused point cloud of ``mvs.fuse_depth_points`` (xyz and 8-bit
 colour; K defaults to 2 there), the product DTU-style evaluation is defined on.  Without these flags the output is unchanged.
+
+``--unbiased_depth`` fuses PGSR's unbiased depth (``fuse_views(unbiased_depth=True)``) where the expected
+depth stood: the depth at which each pixel's ray meets the blended plane of the Gaussians it sees, which lies on a slanted
+surface where the expected depth bends towards the camera.  ``--depth_ratio`` blends the median into it as before.
 """
 import argparse
 import json
@@ -64,7 +68,7 @@ def write_points(path, xyz, rgb):
 
 def extract(dataset, iteration, voxel_size=None, resolution=None, sdf_trunc=None, alpha_min=0.5, max_depth=None,
             depth_ratio=0.0, num_cluster=None, min_cluster_faces=None, unbounded=False, mesh_res=None, consistent=None,
-            n_sources=4, points=False):
+            n_sources=4, points=False, unbiased_depth=False):
     with torch.no_grad():
         gaussians = GaussianModel(dataset.sh_degree)
         scene = Scene(dataset, gaussians, load_iteration=iteration, shuffle=False)
@@ -82,7 +86,8 @@ def extract(dataset, iteration, voxel_size=None, resolution=None, sdf_trunc=None
               f"truncation {volume.sdf_trunc:.5g}")
         fuse_views(scene.getTrainCameras(), gaussians, PipelineParams(), background, volume, alpha_min=alpha_min,
                    max_depth=max_depth, **({"depth_ratio": depth_ratio} if depth_ratio else {}),
-                   **({} if consistent is None else {"consistency": {"n_sources": n_sources, "min_views": consistent}}))
+                   **({} if consistent is None else {"consistency": {"n_sources": n_sources, "min_views": consistent}}),
+                   **({"unbiased_depth": True} if unbiased_depth else {}))
         vertices, faces, colors = volume.extract_mesh()
     path = os.path.join(dataset.model_path, "mesh", "iteration_{}".format(scene.loaded_iter),
                         "tsdf_mesh_unbounded.ply" if unbounded else "tsdf_mesh.ply")
@@ -136,6 +141,8 @@ def main(argv=None):
                     help="fuse only pixels that at least K source views confirm (multi-view geometric consistency)")
     ap.add_argument("--n_sources", type=int, default=4, help="source views per view for --consistent / --points (4)")
     ap.add_argument("--points", action="store_true", help="also write the fused point cloud fused_points.ply")
+    ap.add_argument("--unbiased_depth", action="store_true",
+                    help="fuse PGSR's unbiased plane depth instead of the expected depth")
     args = ap.parse_args(argv)
     if args.consistent is not None and args.consistent < 0:
         ap.error("--consistent must not be negative")
@@ -170,7 +177,8 @@ def main(argv=None):
                                  {"num_cluster": args.num_cluster, "min_cluster_faces": args.min_cluster_faces}),
             **({"unbounded": True, "mesh_res": args.mesh_res} if args.unbounded else {}),
             **({} if args.consistent is None and not args.points else
-               {"consistent": args.consistent, "n_sources": args.n_sources, "points": args.points}))
+               {"consistent": args.consistent, "n_sources": args.n_sources, "points": args.points}),
+            **({"unbiased_depth": True} if args.unbiased_depth else {}))
 
 
 if __name__ == "__main__":

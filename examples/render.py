@@ -3,7 +3,7 @@ write every view of the scene as PNG.
 
     python examples/render.py -m <model directory> [--iteration N] [--skip_train] [--skip_test]
                               [-s <COLMAP or Blender directory>] [-r ...] [--eval] [--white_background] [--depth]
-                              [--use_trained_exp] [--normals] [--depth_normals] [--distortion] [--median_depth]
+                              [--use_trained_exp] [--normals] [--depth_normals] [--distortion] [--median_depth] [--plane_depth]
 
 The dataset's location and options come from the ``cfg_args.json`` that ``examples/train.py -s ... -m ...`` left in the
 model directory; ``-s`` and the other switches override it.
@@ -21,6 +21,8 @@ the consistency loss pulls ``--normals`` towards; pixels without a valid normal 
 ``--median_depth`` also writes ``.../median_depth/%05d.png``: 2DGS's median depth (``render(return_median_depth=True)``)
 as a 16-bit greyscale PNG scaled like ``--depth`` (``.../median_depth/scales.json``), and ``.../median_depth/%05d_id.npy``:
 the int32 ``[H,W]`` map of the Gaussian that owns each pixel (-1: none).
+``--plane_depth`` also writes ``.../plane_depth/%05d.png``: PGSR's unbiased depth (``render(return_plane_depth=True)``;
+0 where the frame has no surface) as a 16-bit greyscale PNG scaled like ``--depth`` (``.../plane_depth/scales.json``).
 ``--use_trained_exp`` renders every view that has one with the exposure saved in the iteration's ``exposure.json``
 (``examples/train.py --train_exposure``); test views have none and are rendered as they are.
 """
@@ -64,6 +66,16 @@ def save_median_png(median, median_id, path, id_path):
     return step
 
 
+def save_plane_depth_png(plane, path):
+    """The unbiased plane depth as 16-bit greyscale; returns the depth one step stands for."""
+    import numpy as np
+    from PIL import Image
+    top = float(plane.max())
+    step = top / 65535.0 if top > 0 else 1.0
+    Image.fromarray(torch.round(plane[0] / step).clamp(0, 65535).cpu().numpy().astype(np.uint16)).save(path)
+    return step
+
+
 def save_depth_png(depth, alpha, path):
     """``depth / alpha`` as 16-bit greyscale; returns the depth one step stands for."""
     import numpy as np
@@ -77,7 +89,8 @@ def save_depth_png(depth, alpha, path):
 
 
 def render_set(model_path, name, iteration, views, gaussians, pipeline, background, depth=False,
-               use_trained_exp=False, normals=False, depth_normals=False, distortion=False, median_depth=False):
+               use_trained_exp=False, normals=False, depth_normals=False, distortion=False, median_depth=False,
+               plane_depth=False):
     render_path = os.path.join(model_path, name, "ours_{}".format(iteration), "renders")
     gts_path = os.path.join(model_path, name, "ours_{}".format(iteration), "gt")
     depth_path = os.path.join(model_path, name, "ours_{}".format(iteration), "depth")
@@ -100,12 +113,17 @@ def render_set(model_path, name, iteration, views, gaussians, pipeline, backgrou
     median_scales = []
     if median_depth:
         os.makedirs(median_path, exist_ok=True)
+    plane_path = os.path.join(model_path, name, "ours_{}".format(iteration), "plane_depth")
+    plane_scales = []
+    if plane_depth:
+        os.makedirs(plane_path, exist_ok=True)
     for idx, view in enumerate(views):
         with_exp = use_trained_exp and view.image_name in (gaussians.pretrained_exposures or {})
         pkg = render(view, gaussians, pipeline, background, **({"return_depth": True} if depth or depth_normals else {}),
                      **({"use_trained_exp": True} if with_exp else {}), **({"return_normals": True} if normals else {}),
                      **({"return_distortion": True} if distortion else {}),
-                     **({"return_median_depth": True} if median_depth else {}))
+                     **({"return_median_depth": True} if median_depth else {}),
+                     **({"return_plane_depth": True} if plane_depth else {}))
         rendering = pkg["render"]
         save_png(rendering, os.path.join(render_path, "{0:05d}".format(idx) + ".png"))
         save_png(view.original_image[0:3, :, :].to(rendering.device), os.path.join(gts_path, "{0:05d}".format(idx) + ".png"))
@@ -122,6 +140,12 @@ def render_set(model_path, name, iteration, views, gaussians, pipeline, backgrou
         if median_depth:
             stem = os.path.join(median_path, "{0:05d}".format(idx))
             median_scales.append(save_median_png(pkg["median_depth"], pkg["median_id"], stem + ".png", stem + "_id.npy"))
+        if plane_depth:
+            plane_scales.append(save_plane_depth_png(pkg["plane_depth"],
+                                                     os.path.join(plane_path, "{0:05d}".format(idx) + ".png")))
+    if plane_depth:
+        with open(os.path.join(plane_path, "scales.json"), "w") as f:
+            json.dump(plane_scales, f)
     if median_depth:
         with open(os.path.join(median_path, "scales.json"), "w") as f:
             json.dump(median_scales, f)
@@ -134,7 +158,7 @@ def render_set(model_path, name, iteration, views, gaussians, pipeline, backgrou
 
 
 def render_sets(dataset, iteration, pipeline, skip_train=False, skip_test=False, depth=False, use_trained_exp=False,
-                normals=False, depth_normals=False, distortion=False, median_depth=False):
+                normals=False, depth_normals=False, distortion=False, median_depth=False, plane_depth=False):
     with torch.no_grad():
         gaussians = GaussianModel(dataset.sh_degree)
         scene = Scene(dataset, gaussians, load_iteration=iteration, shuffle=False)
@@ -144,10 +168,12 @@ def render_sets(dataset, iteration, pipeline, skip_train=False, skip_test=False,
             raise FileNotFoundError("--use_trained_exp: the iteration's point-cloud directory has no exposure.json")
         if not skip_train:
             render_set(dataset.model_path, "train", scene.loaded_iter, scene.getTrainCameras(), gaussians, pipeline,
-                       background, depth, use_trained_exp, normals, depth_normals, distortion, median_depth)
+                       background, depth, use_trained_exp, normals, depth_normals, distortion, median_depth,
+                       **({"plane_depth": True} if plane_depth else {}))
         if not skip_test:
             render_set(dataset.model_path, "test", scene.loaded_iter, scene.getTestCameras(), gaussians, pipeline,
-                       background, depth, use_trained_exp, normals, depth_normals, distortion, median_depth)
+                       background, depth, use_trained_exp, normals, depth_normals, distortion, median_depth,
+                       **({"plane_depth": True} if plane_depth else {}))
     return scene
 
 
@@ -170,6 +196,8 @@ def main(argv=None):
                     help="also write the depth-distortion map of every view as a 16-bit PNG scaled by its maximum")
     ap.add_argument("--median_depth", action="store_true",
                     help="also write the median depth of every view as a 16-bit PNG and the Gaussian id map as .npy")
+    ap.add_argument("--plane_depth", action="store_true",
+                    help="also write PGSR's unbiased plane depth of every view as a 16-bit PNG")
     ap.add_argument("--use_trained_exp", action="store_true", help="apply the saved per-image exposures")
     args = ap.parse_args(argv)
     fields = {}
@@ -185,7 +213,8 @@ def main(argv=None):
     dataset = ModelParams(model_path=args.model_path, **fields)
     print("Rendering " + args.model_path)
     render_sets(dataset, args.iteration, PipelineParams(), args.skip_train, args.skip_test, args.depth,
-                args.use_trained_exp, args.normals, args.depth_normals, args.distortion, args.median_depth)
+                args.use_trained_exp, args.normals, args.depth_normals, args.distortion, args.median_depth,
+                **({"plane_depth": True} if args.plane_depth else {}))
 
 
 if __name__ == "__main__":

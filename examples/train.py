@@ -189,7 +189,8 @@ def strategy_options(args):
                 lambda_dist=args.lambda_dist, dist_from_iter=args.dist_from_iter, depth_ratio=args.depth_ratio,
                 lambda_multi_view_geo=args.lambda_multi_view_geo, multi_view_from_iter=args.multi_view_from_iter,
                 multi_view_pix_max=args.multi_view_pix_max, lambda_multi_view_ncc=args.lambda_multi_view_ncc,
-                multi_view_ncc_samples=args.multi_view_ncc_samples, multi_view_patch_radius=args.multi_view_patch_radius)
+                multi_view_ncc_samples=args.multi_view_ncc_samples, multi_view_patch_radius=args.multi_view_patch_radius,
+                unbiased_depth=args.unbiased_depth)
 
 
 def train_scene(args, dev):
@@ -305,6 +306,9 @@ def main(argv=None):
                     help="with --lambda_multi_view_ncc: pixels drawn per iteration (PGSR: 102400)")
     ap.add_argument("--multi_view_patch_radius", type=int, default=OptimizationParams.multi_view_patch_radius,
                     help="with --lambda_multi_view_ncc: the patch is (2R+1)^2 pixels, R in 1..4 (PGSR: 3)")
+    ap.add_argument("--unbiased_depth", action="store_true",
+                    help="with --lambda_normal or a multi-view term: they see PGSR's unbiased plane depth "
+                         "(render(return_plane_depth=True)) instead of the expected depth")
     ap.add_argument("--out", default=os.path.dirname(os.path.abspath(__file__)))
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 36
+#define GSR_ABI_VERSION 37
 
 enum {
   GSR_OK = 0,
@@ -1073,6 +1073,45 @@ int gsr_mvs_ncc_loss_fwd_bwd(const float* ref_depth, const float* ref_normal, co
                              float fx, float fy, const GsrMvsSource* source, const float* src_gray, const int32_t* pixels,
                              int32_t n_pixels, int32_t patch_radius, float pix_max, float ncc_max, float min_cos,
                              float* record, float* grad_depth, float* grad_normal, void* workspace, void* stream);
+
+/* ---- Per-Gaussian planes and PGSR's unbiased plane depth, ABI v37 (csrc/planes.hip, csrc/plane_depth.hip;
+ * features.gaussian_planes, surface.plane_depth).
+ * gsr_gaussian_planes_fwd: planes [P,4] from scales [P,3] (only their order is read), rotations [P,4] (raw quaternions
+ * r, x, y, z) and means3D [P,3], all device.  viewmatrix (16 floats, row-vector convention, its upper-left 3 x 3 is read)
+ * and campos (3 floats) are HOST memory, read during the call: they travel as kernel arguments.  Per row q = rot /
+ * max(|rot|, 1e-12), R the rotation matrix of q, axis the index of the smallest scale (the smallest index among equals),
+ * n_w = R[:, axis] times -1 when n_w . (campos - mean) < 0 (exactly 0 keeps +1); planes = (n_w @ viewmatrix[:3,:3],
+ * n_w . (campos - mean)): the view-space unit normal and the distance of the camera centre from the Gaussian's plane,
+ * >= 0.  gsr_gaussian_planes_bwd: from dL_dplanes [P,4] it writes dL_drotations [P,4] (through the matrix column and the
+ * normalisation) and dL_dmeans3D [P,3] = -dL/dd n_w; axis and sign are decisions and carry no gradient.  Every row of
+ * every output is written.  One launch each, no atomics: the same bits from run to run.  Intermediates are doubles; each
+ * output is rounded to float32 once.
+ * P = 0 is a successful no-op (after the checks of P, viewmatrix and campos).  Checked before any HIP call: GSR_E_BADARG
+ * for P < 0, a NULL pointer, a viewmatrix[:3,:3] or campos that is not finite; GSR_E_ALIGN: rotations, planes, dL_dplanes
+ * and dL_drotations 16 bytes, the others 4.  Asynchronous, allocates nothing, reads nothing back. */
+int gsr_gaussian_planes_fwd(const float* scales, const float* rotations, const float* means3D, int32_t P,
+                            const float* viewmatrix, const float* campos, float* planes, void* stream);
+int gsr_gaussian_planes_bwd(const float* scales, const float* rotations, const float* means3D, int32_t P,
+                            const float* viewmatrix, const float* campos, const float* dL_dplanes, float* dL_drotations,
+                            float* dL_dmeans3D, void* stream);
+
+/* gsr_plane_depth_fwd: normal [3,H,W] = sum w n (un-normalised), distance [H,W] = sum w d, alpha [H,W] = sum w, device.
+ * Pixel convention of GsrTsdfView and gsr_normal_consistency_fwd_bwd: fx = W / (2 tanfovx) and fy = H / (2 tanfovy),
+ * each rounded to float32 once on the host, cx = (W - 1) / 2, cy = (H - 1) / 2, r = ((x - cx) / fx, (y - cy) / fy, 1).
+ * c = -(N . r); a pixel is valid when alpha >= alpha_min, D > 0, c > 0, c >= min_cos |N| |r|, every input is finite
+ * and every result is a finite float32.  z [H,W] = D / c on valid pixels, 0 elsewhere.  dz_ddistance [H,W] = 1 / c and
+ * dz_dnormal [3,H,W] = (D / c^2) r, zeros on pixels that are not valid: both NULL (value only; z has the same bits) or
+ * both set.  alpha decides validity only.  gsr_plane_depth_bwd: dL_ddistance = dL_dz dz_ddistance and dL_dnormal[a] =
+ * dL_dz dz_dnormal[a] per pixel, exactly 0 where the unit gradient is 0.  One launch each, no atomics: the same bits
+ * from run to run.
+ * Checked before any HIP call: GSR_E_BADARG for H or W < 1, H W > 2^28, tanfovx / tanfovy not positive and finite,
+ * alpha_min outside (0, 1], min_cos outside [0, 1), a NULL required pointer, one unit-gradient pointer without the other;
+ * GSR_E_ALIGN: 4 bytes.  Asynchronous, allocates nothing, reads nothing back. */
+int gsr_plane_depth_fwd(const float* normal, const float* distance, const float* alpha, int32_t H, int32_t W,
+                        float tanfovx, float tanfovy, float alpha_min, float min_cos, float* z, float* dz_ddistance,
+                        float* dz_dnormal, void* stream);
+int gsr_plane_depth_bwd(const float* dL_dz, const float* dz_ddistance, const float* dz_dnormal, int32_t H, int32_t W,
+                        float* dL_ddistance, float* dL_dnormal, void* stream);
 
 #ifdef __cplusplus
 }

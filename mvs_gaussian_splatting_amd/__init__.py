@@ -14,12 +14,12 @@ from .metrics import psnr, ssim, image_metrics, to_uint8_hwc, EvalAccumulator, e
 from .image_ingest import load_image, load_image_host  # noqa: F401
 from .scene import Scene, Camera, MiniCam, PoseCamera, ModelParams  # noqa: F401
 from .contribution import ContributionStats, measure, prune_points_, prune_by_contribution  # noqa: F401
-from .features import gaussian_normals  # noqa: F401
+from .features import gaussian_normals, gaussian_planes  # noqa: F401
 from .tsdf import (TSDFVolume, ContractedTSDFVolume, fuse_views, volume_for_points,  # noqa: F401
                    contracted_volume_for_points, bounding_sphere)
 from .mcmc import mcmc_regularizer, inject_noise, relocate_gs, add_new_gs  # noqa: F401
 from .normal_consistency import normal_consistency_loss, depth_to_normals  # noqa: F401
-from .surface import surface_depth  # noqa: F401
+from .surface import surface_depth, plane_depth  # noqa: F401
 from .mesh import connected_components, clean_mesh  # noqa: F401
 from .geometry_eval import NearestIndex, nearest_points, sample_surface, evaluate_points, evaluate_mesh  # noqa: F401
 from .mvs import (select_source_views, depth_consistency, backproject_depth, fuse_depth_points,  # noqa: F401
@@ -29,10 +29,10 @@ __all__ = ["Scene", "Camera", "MiniCam", "PoseCamera", "ModelParams", "load_imag
            "GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "render", "l1_loss", "apply_exposure", "save_exposures", "load_exposures", "l1_dssim_loss",
            "opacity_sparsity_loss", "add_densification_stats", "Adam", "GaussianModel", "psnr", "ssim", "image_metrics", "to_uint8_hwc", "EvalAccumulator",
            "evaluate_views", "ContributionStats", "measure", "prune_points_", "prune_by_contribution",
-           "mcmc_regularizer", "inject_noise", "relocate_gs", "add_new_gs", "gaussian_normals",
+           "mcmc_regularizer", "inject_noise", "relocate_gs", "add_new_gs", "gaussian_normals", "gaussian_planes",
            "TSDFVolume", "ContractedTSDFVolume", "fuse_views", "volume_for_points", "contracted_volume_for_points",
            "bounding_sphere", "normal_consistency_loss", "depth_to_normals",
-           "surface_depth", "connected_components", "clean_mesh", "NearestIndex", "nearest_points", "sample_surface",
+           "surface_depth", "plane_depth", "connected_components", "clean_mesh", "NearestIndex", "nearest_points", "sample_surface",
            "evaluate_points", "evaluate_mesh", "select_source_views", "depth_consistency", "backproject_depth",
            "fuse_depth_points", "multi_view_geo_loss", "multi_view_ncc_loss",
            "gray_image"]

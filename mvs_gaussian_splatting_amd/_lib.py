@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # instead of copying it over the in-tree library
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")
 
-ABI_VERSION = 36
+ABI_VERSION = 37
 
 
 class GsrParams(C.Structure):
@@ -325,6 +325,14 @@ SYMBOLS = {
     "gsr_mvs_ncc_loss_fwd_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float,
                                            C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # per-Gaussian planes (view-space normal, camera-to-plane distance) and their gradients (csrc/planes.hip;
+    # features.gaussian_planes); viewmatrix and campos are host arrays
+    "gsr_gaussian_planes_fwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 4),
+    "gsr_gaussian_planes_bwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 6),
+    # PGSR's unbiased depth of a rendered frame, value and unit gradients, and their scaling by the upstream map
+    # (csrc/plane_depth.hip; surface.plane_depth)
+    "gsr_plane_depth_fwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 2 + [C.c_float] * 4 + [C.c_void_p] * 4),
+    "gsr_plane_depth_bwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 2 + [C.c_void_p] * 3),
 }
 
 _lib = None

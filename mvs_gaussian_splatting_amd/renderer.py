@@ -17,9 +17,10 @@ import torch
 
 from . import grow
 from .exposure import apply_exposure
-from .features import gaussian_normals
+from .features import gaussian_normals, gaussian_planes
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, _grown_key, rasterize_gaussians_fused
 from .sh import eval_sh
+from .surface import plane_depth as _plane_depth
 
 
 def _can_fuse(pc, pipe, override_color) -> bool:
@@ -94,7 +95,7 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier:
            override_color=None, grow_dir=False, densify_grad_threshold=0, iteration=None, opt=None,
            continous_dir=False, grow_distance=False, modelcg=None, cameras_extent=None, return_depth=False,
            use_trained_exp=False, contribution=None, contribution_mask=None, features=None, return_normals=False,
-           return_distortion=False, distortion_kwargs=None, return_median_depth=False):
+           return_distortion=False, distortion_kwargs=None, return_median_depth=False, return_plane_depth=False):
     """Render the scene; ``bg_color`` must be on the GPU.  Returns the reference's result dict
     (``gaussian_renderer/__init__.py:309-313``).  The keyword arguments after ``override_color`` are the reference's
     (``:19``) and drive the grow / learned-split branch (module docstring); the frame of a closed branch is unchanged.
@@ -136,14 +137,25 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier:
     Gaussian in front of which the transmittance still exceeds one half (2DGS's median depth, what it meshes bounded scenes
     from; 0 where nothing was composited), differentiable in the positions alone, and ``"median_id"`` ``[H,W]`` (int32),
     the row of that Gaussian (-1 where nothing was composited) (``rasterizer`` module docstring).  The
-    same two conditions as for ``return_depth`` apply."""
+    same two conditions as for ``return_depth`` apply.
+
+    ``return_plane_depth=True`` (PGSR's unbiased depth): implies ``return_depth`` and ``return_normals``.
+    The per-Gaussian rows ``(n_view, d) = features.gaussian_planes(pc.get_scaling, pc.get_rotation, ...)`` -- one HIP
+    launch -- ride as four feature channels behind the caller's ``features``, so the dict gains ``"distance"`` ``[1,H,W]``
+    = ``sum w d`` (``d`` the distance of the camera centre from the Gaussian's plane) next to ``"normal"``, and
+    ``"plane_depth"`` ``[1,H,W]`` = ``surface.plane_depth(normal, distance, alpha, tan(FoVx / 2), tan(FoVy / 2))``: the
+    depth at which the pixel's ray meets the blended plane, 0 where there is no surface.  Differentiable in the
+    rotations, the positions and the blending weights.  On such a frame ``"normal"`` comes from the planes kernel and may
+    differ from the torch path of ``return_normals`` alone in the last bits.  Combines with ``features=``,
+    ``return_median_depth`` and ``return_distortion``; the same two conditions as for ``return_depth`` apply."""
     if distortion_kwargs is not None and not return_distortion:
         raise ValueError("distortion_kwargs needs return_distortion=True")
     pkg = _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, grow_dir,
                   densify_grad_threshold, iteration, opt, continous_dir, grow_distance, modelcg, cameras_extent,
                   return_depth, contribution, contribution_mask, features, return_normals,
                   (True if distortion_kwargs is None else dict(distortion_kwargs)) if return_distortion else None,
-                  **({"median_depth": True} if return_median_depth else {}))
+                  **({"median_depth": True} if return_median_depth else {}),
+                  **({"plane_depth": True} if return_plane_depth else {}))
     if use_trained_exp:
         pkg["render"] = apply_exposure(pkg["render"], pc.get_exposure_from_name(viewpoint_camera.image_name))
     return pkg
@@ -151,10 +163,16 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier:
 
 def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, grow_dir, densify_grad_threshold,
             iteration, opt, continous_dir, grow_distance, modelcg, cameras_extent, return_depth, contribution=None,
-            contribution_mask=None, features=None, return_normals=False, distortion=None, median_depth=False):
+            contribution_mask=None, features=None, return_normals=False, distortion=None, median_depth=False,
+            plane_depth=False):
     """The frame of ``render`` as the rasterizer leaves it.  ``distortion``: None, or the operator's ``distortion=``;
-    ``median_depth``: the operator's ``median_depth=``."""
+    ``median_depth``: the operator's ``median_depth=``; ``plane_depth``: ``render``'s ``return_plane_depth``."""
     which = grow.branch(iteration, opt, grow_dir, continous_dir, modelcg)
+    if plane_depth:
+        if which is not None:
+            raise ValueError("return_plane_depth=True is not available on a frame of the open grow / learned-split branch "
+                             "(virtual rows appended): render the maps in a frame of their own")
+        return_depth = return_normals = True
     if which is not None and contribution is not None:
         raise ValueError("contribution statistics are not available on a frame of the open grow / learned-split branch "
                          "(virtual rows appended): measure in a frame of its own")
@@ -190,7 +208,10 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
     raster_settings = _settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier)
     if want_feat:
         rows = [] if features is None else [features]
-        if return_normals:
+        if plane_depth:
+            rows.append(gaussian_planes(pc.get_scaling, pc.get_rotation, xyz, raster_settings.viewmatrix,
+                                        raster_settings.campos))
+        elif return_normals:
             rows.append(gaussian_normals(pc.get_scaling, pc.get_rotation, xyz, raster_settings.viewmatrix,
                                          raster_settings.campos))
         extra_stats = dict(extra_stats, features=rows[0] if len(rows) == 1 else torch.cat(rows, dim=1))
@@ -214,9 +235,17 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
             return {}
         n_user = 0 if features is None else int(features.shape[1])
         out = {} if features is None else {"features": feat[:n_user]}
-        if return_normals:
+        if plane_depth:
+            out["normal"], out["distance"] = feat[n_user:n_user + 3], feat[n_user + 3:]
+        elif return_normals:
             out["normal"] = feat[n_user:]
         return out
+
+    def with_plane_depth(pkg):
+        if plane_depth:
+            pkg["plane_depth"] = _plane_depth(pkg["normal"], pkg["distance"], pkg["alpha"], raster_settings.tanfovx,
+                                              raster_settings.tanfovy)
+        return pkg
 
     if _can_fuse(pc, pipe, override_color):
         # same result as the getter path below, without materialising cat(f_dc, f_rest), exp, normalize, sigmoid (and
@@ -229,9 +258,9 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
                                             pc._scaling, pc._rotation, raster_settings, visible=visible,
                                             **({"aux_maps": True} if return_depth else {}), **extra_stats,
                                             **({} if distortion is None else {"distortion": distortion}), **median_kw)
-            return {"render": out[0], "viewspace_points": screenspace_points, "visibility_filter": visible,
-                    "radii": out[1], "selected_pts_mask": None, **(_aux_entries(out[2]) if return_depth else {}),
-                    **feature_entries(out)}
+            return with_plane_depth({"render": out[0], "viewspace_points": screenspace_points,
+                                     "visibility_filter": visible, "radii": out[1], "selected_pts_mask": None,
+                                     **(_aux_entries(out[2]) if return_depth else {}), **feature_entries(out)})
         rendered_image, radii = rasterize_gaussians_fused(xyz, screenspace_points, pc._features_dc, pc._features_rest,
                                                           pc._opacity, pc._scaling, pc._rotation, raster_settings,
                                                           densify_stats=stats, visible=visible, **extra_stats)
@@ -267,13 +296,13 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
                      colors_precomp=colors_precomp, opacities=pc.get_opacity, scales=scales,
                      rotations=rotations, cov3D_precomp=cov3D_precomp, **extra)
     rendered_image, radii = out[0], out[1]
-    return {"render": rendered_image,
-            "viewspace_points": screenspace_points,
-            "visibility_filter": radii > 0,
-            "radii": radii,
-            "selected_pts_mask": None,
-            **(_aux_entries(out[2]) if return_depth else {}),
-            **feature_entries(out)}
+    return with_plane_depth({"render": rendered_image,
+                             "viewspace_points": screenspace_points,
+                             "visibility_filter": radii > 0,
+                             "radii": radii,
+                             "selected_pts_mask": None,
+                             **(_aux_entries(out[2]) if return_depth else {}),
+                             **feature_entries(out)})
 
 
 def _render_grown(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, which, grow_dir,

@@ -22,7 +22,7 @@ from .mcmc import add_new_gs, inject_noise, mcmc_regularizer, relocate_gs
 from .mvs import multi_view_geo_loss, multi_view_ncc_loss
 from .normal_consistency import normal_consistency_loss
 from .renderer import render
-from .surface import surface_depth
+from .surface import blend_plane_depth, surface_depth
 from .synthetic import PipelineParams  # noqa: F401  (the two parameter classes live side by side)
 
 
@@ -91,6 +91,10 @@ class OptimizationParams:
     multi_view_ncc_samples = 102400
     multi_view_patch_radius = 3
     multi_view_ncc_max = 0.9
+    # PGSR's unbiased depth (render(return_plane_depth=True); surface.plane_depth): while the normal term or a multi-view
+    # term is on, the surface they see is the ray-plane depth of the blended plane instead of the expected depth; read
+    # only then; False leaves the iteration as it is
+    unbiased_depth = False
 
     def __init__(self, **overrides):
         for k, v in overrides.items():
@@ -171,7 +175,16 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
     ncc_max=opt.multi_view_ncc_max, n_samples=opt.multi_view_ncc_samples)`` joins the loss before the one ``backward``:
     the photographs are the two cameras' ``original_image``, turned to grey once per camera (``mvs.gray_image``).
     Statistics, the ``sparse_adam`` union and the refusals are the geometric term's.  ``lambda_multi_view_ncc = 0``:
-    exactly the calls made without it, whatever the other new fields say."""
+    exactly the calls made without it, whatever the other new fields say.
+    ``opt.unbiased_depth`` while ``lambda_normal``, ``lambda_multi_view_geo`` or ``lambda_multi_view_ncc`` is active: the
+    frame, and the source frame, are also rendered with ``return_plane_depth=True`` and the surface those terms see is
+    ``"plane_depth"``, PGSR's unbiased depth, where it was ``depth / alpha``: the normal term is fed
+    ``plane_depth * alpha`` (it divides by ``alpha`` itself) with ``alpha`` set to 0 on the pixels that have no plane
+    depth, so that they are uncovered there as they are for the multi-view terms; the multi-view terms are fed
+    ``plane_depth``; the median is blended in under ``opt.depth_ratio`` as before (``surface.blend_plane_depth``); the
+    NCC term's normal map is the planes kernel's.
+    The refusals are those terms' own.  ``unbiased_depth = False``, or none of the three terms active: exactly the calls
+    made without it."""
     strategy = getattr(opt, "strategy", "default")
     if strategy not in ("default", "mcmc"):
         raise ValueError(f"strategy must be 'default' or 'mcmc', got {strategy!r}")
@@ -218,6 +231,7 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
     if not 0.0 <= depth_ratio <= 1.0:
         raise ValueError(f"opt.depth_ratio must lie in [0, 1], got {depth_ratio}")
     median_on = depth_ratio > 0.0
+    unbiased = bool(getattr(opt, "unbiased_depth", False)) and (normal_on or mv_on)
     dist_on = float(getattr(opt, "lambda_dist", 0.0)) > 0.0 and iteration >= int(getattr(opt, "dist_from_iter", 0))
     if dist_on:
         if pose_optimizer is not None:
@@ -241,6 +255,7 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
                          **({"return_normals": True} if normal_on or ncc_on else {}),
                          **({"return_distortion": True} if dist_on else {}),
                          **({"return_median_depth": True} if median_on else {}),
+                         **({"return_plane_depth": True} if unbiased else {}),
                          **({"use_trained_exp": True} if train_exposure else {}))
     pkg = render(camera, model, pipe, bg, **render_kwargs)                                      # :91
     gt = camera.original_image if gt_image is None else gt_image
@@ -253,16 +268,26 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
         depth_target, depth_weight = depth_loss
         loss = loss + float(depth_weight) * (pkg["invdepth"] - depth_target.to(pkg["invdepth"].device)).abs().mean()
     if normal_on:
+        n_depth, n_alpha = pkg["depth"], pkg["alpha"]
+        if unbiased:
+            # a pixel whose plane depth was refused has no surface: alpha 0 takes it out of the term's stencils, where
+            # a depth of 0 under its real alpha would stand as a surface at the camera
+            n_alpha = torch.where(pkg["plane_depth"] > 0, n_alpha, torch.zeros_like(n_alpha))
+            n_depth = pkg["plane_depth"] * n_alpha
         loss = loss + float(opt.lambda_normal) * normal_consistency_loss(
-            pkg["depth"], pkg["alpha"], pkg["normal"], math.tan(camera.FoVx * 0.5), math.tan(camera.FoVy * 0.5),
+            n_depth, n_alpha, pkg["normal"], math.tan(camera.FoVx * 0.5), math.tan(camera.FoVy * 0.5),
             **({"median": pkg["median_depth"], "depth_ratio": depth_ratio} if median_on else {}))
     if dist_on:
         loss = loss + float(opt.lambda_dist) * pkg["distortion"].mean()
     src_pkg = None
     if mv_on:
         src_pkg = render(source_camera, model, pipe, bg, **render_kwargs)        # for its depth: the colour enters no term
-        surfaces = [surface_depth(p["depth"], p["alpha"], p["median_depth"] if median_on else None, depth_ratio)
-                    for p in (pkg, src_pkg)]
+        if unbiased:
+            surfaces = [blend_plane_depth(p["plane_depth"], p["median_depth"] if median_on else None, depth_ratio)
+                        for p in (pkg, src_pkg)]
+        else:
+            surfaces = [surface_depth(p["depth"], p["alpha"], p["median_depth"] if median_on else None, depth_ratio)
+                        for p in (pkg, src_pkg)]
         pix_max = float(getattr(opt, "multi_view_pix_max", 1.0))
         if geo_on:
             loss = loss + float(opt.lambda_multi_view_geo) * multi_view_geo_loss(

@@ -29,7 +29,7 @@ from typing import Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from .surface import surface_depth
+from .surface import blend_plane_depth, plane_depth, surface_depth
 
 _INF = float("inf")
 _BLOCK_X, _BLOCK_ROWS = 64, 4          # the launch shape of csrc/tsdf.hip (tsdf_grid_blocks)
@@ -309,11 +309,22 @@ def contracted_volume_for_points(xyz: torch.Tensor, center: Sequence[float], rad
                                 with_color=with_color, device=xyz.device if device is None else device)
 
 
-def render_surface(renderer, camera, model, pipe, bg, alpha_min: float, depth_ratio: float):
+def render_surface(renderer, camera, model, pipe, bg, alpha_min: float, depth_ratio: float,
+                   unbiased_depth: bool = False):
     """One view's surface depth as ``fuse_views`` integrates it -> ``(depth [1,H,W], the renderer's package)``: at
     ``depth_ratio`` 0 the expected depth ``depth / alpha`` where ``alpha >= alpha_min`` and 0 elsewhere, from
     ``renderer(camera, model, pipe, bg, return_depth=True)``; above 0 ``surface.surface_depth`` of a frame rendered with
-    ``return_median_depth=True`` as well."""
+    ``return_median_depth=True`` as well.  ``unbiased_depth``: the frame is rendered with ``return_plane_depth=True`` and
+    PGSR's unbiased depth -- the frame's ``"plane_depth"`` at ``alpha_min`` 0.5, ``surface.plane_depth(normal, distance,
+    alpha, ..., alpha_min)`` of its maps otherwise; 0 where it has no surface -- stands where the expected depth stood, the median blended into it by ``surface.blend_plane_depth``."""
+    if unbiased_depth:
+        pkg = renderer(camera, model, pipe, bg, return_plane_depth=True,
+                       **({"return_median_depth": True} if depth_ratio > 0.0 else {}))
+        plane = pkg["plane_depth"]                       # render's own map: alpha_min 0.5
+        if alpha_min != 0.5:
+            plane = plane_depth(pkg["normal"], pkg["distance"], pkg["alpha"], math.tan(camera.FoVx * 0.5),
+                                math.tan(camera.FoVy * 0.5), alpha_min)
+        return blend_plane_depth(plane, pkg["median_depth"] if depth_ratio > 0.0 else None, depth_ratio), pkg
     if depth_ratio > 0.0:
         pkg = renderer(camera, model, pipe, bg, return_depth=True, return_median_depth=True)
         return surface_depth(pkg["depth"], pkg["alpha"], pkg["median_depth"], depth_ratio, alpha_min), pkg
@@ -324,7 +335,7 @@ def render_surface(renderer, camera, model, pipe, bg, alpha_min: float, depth_ra
 
 def fuse_views(cameras, model, pipe, bg, volume: TSDFVolume, *, alpha_min: float = 0.5,
                max_depth: Optional[float] = None, renderer=None, depth_ratio: float = 0.0,
-               consistency: Optional[dict] = None) -> TSDFVolume:
+               consistency: Optional[dict] = None, unbiased_depth: bool = False) -> TSDFVolume:
     """Render every camera with ``renderer(camera, model, pipe, bg, return_depth=True)`` (default: ``render``) under
     ``no_grad`` and integrate its expected depth ``depth / alpha`` where ``alpha >= alpha_min`` (0, invalid, elsewhere)
     with the rendered colour.  No host synchronisation per view.
@@ -339,7 +350,11 @@ def fuse_views(cameras, model, pipe, bg, volume: TSDFVolume, *, alpha_min: float
     for ``N`` views of ``H x W`` pixels (``4 N H W`` without colour).  The second checks each view against its
     ``mvs.select_source_views`` and integrates the view's own depth with the pixels of ``count < min_views`` set to 0:
     floaters, depth that hangs between two surfaces at a silhouette and fog in front of a wall, which no neighbour
-    confirms, never reach the volume."""
+    confirms, never reach the volume.
+    unbiased_depth (default False: exactly the calls above): the frames are rendered with ``return_plane_depth=True`` and
+    PGSR's unbiased depth ``surface.plane_depth`` is what is integrated (``render_surface``): on a slanted
+    surface it lies on the surface where the expected depth bends towards the camera.  The first frame of each camera
+    copies its view matrix and centre to the host (``features.gaussian_planes``): one synchronisation per camera."""
     if not (isinstance(depth_ratio, (int, float)) and 0.0 <= depth_ratio <= 1.0):
         raise ValueError(f"depth_ratio must lie in [0, 1], got {depth_ratio!r}")
     if consistency is not None:
@@ -350,13 +365,15 @@ def fuse_views(cameras, model, pipe, bg, volume: TSDFVolume, *, alpha_min: float
     with torch.no_grad():
         if consistency is None:
             for camera in cameras:
-                expected, pkg = render_surface(renderer, camera, model, pipe, bg, alpha_min, depth_ratio)
+                expected, pkg = render_surface(renderer, camera, model, pipe, bg, alpha_min, depth_ratio,
+                                               **({"unbiased_depth": True} if unbiased_depth else {}))
                 volume.integrate(expected, camera, color=pkg["render"] if volume.with_color else None, max_depth=max_depth)
             return volume
         cameras = list(cameras)
         depths, colors = [], []
         for camera in cameras:
-            expected, pkg = render_surface(renderer, camera, model, pipe, bg, alpha_min, depth_ratio)
+            expected, pkg = render_surface(renderer, camera, model, pipe, bg, alpha_min, depth_ratio,
+                                               **({"unbiased_depth": True} if unbiased_depth else {}))
             depths.append(expected)
             colors.append(pkg["render"] if volume.with_color else None)
         for camera, depth, color, (count, _) in zip(cameras, depths, colors, filter_views(cameras, depths, **options)):
