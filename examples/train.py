@@ -8,6 +8,7 @@ SH degree steps, densification, opacity resets, the optional opacity sparsity te
                              [--refine_poses [--pose_lr LR]]
                              [--train_exposure [--exposure_lr_init LR] [--exposure_lr_final LR]
                               [--exposure_lr_delay_steps N] [--exposure_lr_delay_mult M]]
+                             [--bilateral_grid [--bilateral_grid_shape W H L]]
                              [--prune_iterations N [N ...] --prune_keep_ratio R [--prune_kind sum|max|count|mean]]
                              [--strategy mcmc --cap_max N [--noise_lr LR] [--opacity_reg W] [--scale_reg W]]
                              [--lambda_normal L [--normal_from_iter N] [--depth_ratio R]]
@@ -42,7 +43,11 @@ With ``-s`` the example trains on a dataset through ``Scene`` (``scene.py``) and
 (Adam at ``--pose_lr`` on the six pose parameters of each camera); the refined poses are written to
 ``<output>/refined_poses.json`` at the end.  ``--train_exposure`` (off by default; upstream 3DGS's option) gives every
 training image a learnable 3x4 colour affine, trains it with the model and saves ``exposure.json`` next to each point
-cloud; ``examples/render.py --use_trained_exp`` renders with it.  ``--prune_iterations`` (both forms; off by default):
+cloud; ``examples/render.py --use_trained_exp`` renders with it.  ``--bilateral_grid`` (off by default; gsplat's
+``--use_bilateral_grid``) gives every training image a bilateral grid of ``--bilateral_grid_shape`` (default 16 16 8)
+colour affines (``bilagrid.py``), trained with the model; the grids are saved as ``bilateral_grid_<iteration>.pt`` next to
+each checkpoint and loaded with it on resume.  Evaluation and ``examples/render.py`` do not apply them: test views have
+none.  ``--prune_iterations`` (both forms; off by default):
 after each of those iterations the blending-weight statistics of every training camera are measured (``contribution.py``)
 and the ``--prune_keep_ratio`` share of the Gaussians with the highest ``--prune_kind`` score is kept
 (``examples/prune.py`` does the same to a saved scene).  Without ``-s``:
@@ -215,6 +220,15 @@ def train_scene(args, dev):
         model.setup_exposures([c.image_name for c in scene.getTrainCameras()])
     model.training_setup(opt)
     first_iter = load_checkpoint(model, args.start_checkpoint, opt) if args.start_checkpoint else 0
+    grids = None
+    if args.bilateral_grid:
+        from mvs_gaussian_splatting_amd import BilateralGrids
+        grids = BilateralGrids([c.image_name for c in scene.getTrainCameras()], shape=tuple(args.bilateral_grid_shape),
+                               device=dev)
+        grids.training_setup(opt)
+        if args.start_checkpoint:
+            grids.load(os.path.join(os.path.dirname(os.path.abspath(args.start_checkpoint)),
+                                    f"bilateral_grid_{first_iter}.pt"))
     bg = torch.tensor([1.0, 1.0, 1.0] if dataset.white_background else [0.0, 0.0, 0.0], device=dev)
     pipe, stack, loss = PipelineParams(), None, None
     prune = prune_options(args)
@@ -232,6 +246,7 @@ def train_scene(args, dev):
         loss = training_iteration(model, train_cameras[index], opt, pipe, bg, iteration, dataset=dataset,
                                   cameras_extent=scene.cameras_extent, pose_optimizer=pose_optimizer,
                                   train_exposure=args.train_exposure,
+                                  **({"bilateral_grids": grids} if grids is not None else {}),
                                   **({"source_camera": source} if source is not None else {}))
         prune_step(model, train_cameras, pipe, bg, iteration, prune)
         if iteration % 10 == 0:
@@ -241,6 +256,8 @@ def train_scene(args, dev):
             print(f"[ITER {iteration}] saved the Gaussians under {args.model_path}")
         if iteration in args.checkpoint_iterations:
             save_checkpoint(model, iteration, os.path.join(args.model_path, f"chkpnt{iteration}.pth"))
+            if grids is not None:
+                grids.save(os.path.join(args.model_path, f"bilateral_grid_{iteration}.pt"))
     if args.refine_poses:
         poses = {c.image_name: dict(zip(("R", "T"), (a.tolist() for a in c.pose()))) for c in train_cameras}
         with open(os.path.join(args.model_path, "refined_poses.json"), "w") as f:
@@ -271,6 +288,9 @@ def main(argv=None):
     ap.add_argument("--exposure_lr_final", type=float, default=OptimizationParams.exposure_lr_final)
     ap.add_argument("--exposure_lr_delay_steps", type=int, default=OptimizationParams.exposure_lr_delay_steps)
     ap.add_argument("--exposure_lr_delay_mult", type=float, default=OptimizationParams.exposure_lr_delay_mult)
+    ap.add_argument("--bilateral_grid", action="store_true",
+                    help="with -s: learn a bilateral grid of colour affines per training image (bilateral_grid_<N>.pt)")
+    ap.add_argument("--bilateral_grid_shape", type=int, nargs=3, default=[16, 16, 8], metavar=("W", "H", "L"))
     ap.add_argument("--prune_iterations", type=int, nargs="*", default=[],
                     help="after these iterations: measure every training view and prune by contribution")
     ap.add_argument("--prune_keep_ratio", type=float, default=None, help="share of the Gaussians a pruning keeps")

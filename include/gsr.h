@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 37
+#define GSR_ABI_VERSION 38
 
 enum {
   GSR_OK = 0,
@@ -1112,6 +1112,46 @@ int gsr_plane_depth_fwd(const float* normal, const float* distance, const float*
                         float* dz_dnormal, void* stream);
 int gsr_plane_depth_bwd(const float* dL_dz, const float* dz_ddistance, const float* dz_dnormal, int32_t H, int32_t W,
                         float* dL_ddistance, float* dL_dnormal, void* stream);
+
+/* ---- Per-image bilateral grids, ABI v38 (csrc/bilagrid.hip, csrc/bilagrid_math.h; bilagrid.py).
+ * The grid of "Bilateral Guided Radiance Field Processing": grid [12,L,Hg,Wg] (device), channel 4 c + k = A[c,k] with c
+ * the output colour, k the input colour and k = 3 the offset; 2 <= Wg, Hg <= 64, 2 <= L <= 16.  For pixel (px, py) of
+ * the image x [3,H,W]: u = (px + 0.5) / W (Wg - 1), v = (py + 0.5) / H (Hg - 1), gray = 0.299 x0 + 0.587 x1 + 0.114 x2,
+ * z = clamp(gray, 0, 1) (L - 1); cell i0 = min(floor(u), Wg - 2), tu = u - i0, likewise v and z; every coefficient by
+ * nested lerps a + t (b - a) along x, then y, then z; y[c] = A[c,0] x0 + A[c,1] x1 + A[c,2] x2 + A[c,3], no clamp.
+ * Doubles between the float32 loads and the one rounding of each output.  A grid that is constant over a pixel's cell
+ * gives that value bit for bit: with the identity grid (A = eye(3,4) everywhere) y = x and dx = g bit for bit on finite
+ * input.
+ * gsr_bilagrid_slice_fwd: y [3,H,W].  staging: GSR_BILAGRID_STAGE_AUTO (the library's choice: LDS for a grid that
+ * fits under an image of at least 262144 pixels), _CACHE (the cells are read through the caches) or _LDS (a workgroup
+ * first copies the whole grid into LDS; GSR_E_BADARG for a grid of more than 24576 floats); the bits of y, and of dx
+ * below, do not depend on it.
+ * gsr_bilagrid_slice_bwd: from g = dL/dy [3,H,W], dx [3,H,W] = dL/dx (may be NULL; grid may then be NULL), with the
+ * second path through the luminance: dx[k] = sum_c A[c,k] g[c] + coef_k dz/dgray sum_c g[c] sum_k' dA[c,k']/dz xt[k'],
+ * xt = (x0, x1, x2, 1), dz/dgray = L - 1 for 0 < gray < 1 and exactly 0 otherwise (a gray that is not finite included);
+ * and dgrid [12,L,Hg,Wg] = dL/dgrid (may be NULL), dgrid[4 c + k, cell] = sum_p w_cell(p) g[c,p] xt[k,p] with the
+ * trilinear weight of pixel p on the cell.  Which cells a pixel touches and whether gray is clamped are decisions and
+ * carry no gradient.  dgrid is gathered by grid vertex into double partial sums in `workspace`
+ * (gsr_bilagrid_workspace_bytes(H, W, Wg, Hg, L) bytes, 8-byte aligned) and added in a fixed order, no atomics: the
+ * same bits from run to run; every element is written, zero where no pixel touches it.  Both NULL: a no-op.
+ * gsr_bilagrid_tv_fwd_bwd: grids [N,12,L,Hg,Wg], 1 <= N <= 65536; value (device, one float) = (1/N) sum_n sum_{axis in
+ * z,y,x} mean((grids[n] shifted by one along the axis - grids[n])^2), the mean over the 12 * (size with that axis
+ * reduced by one) differences of one image; dgrids (same shape, may be NULL) = d value / d grids.  Sums in double in a
+ * fixed order: the same bits from run to run.  workspace: gsr_bilagrid_workspace_bytes(0, 0, Wg, Hg, L) bytes (H = W = 0
+ * names this call's workspace, which does not depend on N), 8-byte aligned.
+ * gsr_bilagrid_workspace_bytes is 0 for a shape the calls refuse.
+ * Checked before any HIP call: GSR_E_BADARG for a NULL required pointer, H or W < 1, H W > 2^28, a grid size outside its
+ * range, N outside its range, an unknown staging; GSR_E_ALIGN for the float arrays (4 bytes) and the workspace (8).
+ * Asynchronous, allocates nothing, reads nothing back. */
+enum { GSR_BILAGRID_STAGE_AUTO = 0, GSR_BILAGRID_STAGE_CACHE = 1, GSR_BILAGRID_STAGE_LDS = 2 };
+size_t gsr_bilagrid_workspace_bytes(int32_t H, int32_t W, int32_t Wg, int32_t Hg, int32_t L);
+int gsr_bilagrid_slice_fwd(const float* x, const float* grid, int32_t H, int32_t W, int32_t Wg, int32_t Hg, int32_t L,
+                           int32_t staging, float* y, void* stream);
+int gsr_bilagrid_slice_bwd(const float* x, const float* grid, const float* g, int32_t H, int32_t W, int32_t Wg,
+                           int32_t Hg, int32_t L, int32_t staging, float* dx, float* dgrid, void* workspace,
+                           void* stream);
+int gsr_bilagrid_tv_fwd_bwd(const float* grids, int32_t N, int32_t Wg, int32_t Hg, int32_t L, float* value,
+                            float* dgrids, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

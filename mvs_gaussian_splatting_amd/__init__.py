@@ -9,6 +9,7 @@ from .renderer import render  # noqa: F401
 from .losses import l1_loss, l1_dssim_loss, opacity_sparsity_loss, add_densification_stats  # noqa: F401
 from .optim import Adam  # noqa: F401
 from .exposure import apply_exposure, save_exposures, load_exposures  # noqa: F401
+from .bilagrid import slice_bilateral_grid, bilateral_grid_tv_loss, BilateralGrids  # noqa: F401
 from .model import GaussianModel  # noqa: F401
 from .metrics import psnr, ssim, image_metrics, to_uint8_hwc, EvalAccumulator, evaluate_views  # noqa: F401
 from .image_ingest import load_image, load_image_host  # noqa: F401
@@ -35,4 +36,4 @@ __all__ = ["Scene", "Camera", "MiniCam", "PoseCamera", "ModelParams", "load_imag
            "surface_depth", "plane_depth", "connected_components", "clean_mesh", "NearestIndex", "nearest_points", "sample_surface",
            "evaluate_points", "evaluate_mesh", "select_source_views", "depth_consistency", "backproject_depth",
            "fuse_depth_points", "multi_view_geo_loss", "multi_view_ncc_loss",
-           "gray_image"]
+           "gray_image", "slice_bilateral_grid", "bilateral_grid_tv_loss", "BilateralGrids"]

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # instead of copying it over the in-tree library
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")
 
-ABI_VERSION = 37
+ABI_VERSION = 38
 
 
 class GsrParams(C.Structure):
@@ -116,6 +116,7 @@ ACT_SCALE_EXP, ACT_ROT_NORMALIZE, ACT_OPACITY_SIGMOID = 1, 2, 4
 BINNING_TWO_LEVEL, BINNING_KEYS64, BINNING_TWO_LEVEL_CULLED = 0, 1, 2
 DSSIM_ONE_MINUS_MEAN, DSSIM_CLAMPED_HALF = 0, 1
 DEBUG_NO_MINIBLOCK_CULL = 1
+BILAGRID_STAGE_AUTO, BILAGRID_STAGE_CACHE, BILAGRID_STAGE_LDS = 0, 1, 2
 # gsr_eval_image flags and the floats of its per-view record (l1, psnr, ssim, 3 x sum|d|, 3 x sum d^2, 3 x psnr_c)
 EVAL_CLAMP_X, EVAL_CLAMP_GT, EVAL_SSIM, EVAL_PSNR_WHOLE, EVAL_U8_TRUNCATE = 1, 2, 4, 8, 16
 EVAL_VIEW_FLOATS = 12
@@ -333,6 +334,12 @@ SYMBOLS = {
     # (csrc/plane_depth.hip; surface.plane_depth)
     "gsr_plane_depth_fwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 2 + [C.c_float] * 4 + [C.c_void_p] * 4),
     "gsr_plane_depth_bwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 2 + [C.c_void_p] * 3),
+    # per-image bilateral grids: trilinear slice of a grid of 3x4 colour affines, its gradients and the TV term
+    # (csrc/bilagrid.hip; bilagrid.py)
+    "gsr_bilagrid_workspace_bytes": (C.c_size_t, [C.c_int32] * 5),
+    "gsr_bilagrid_slice_fwd": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 6 + [C.c_void_p] * 2),
+    "gsr_bilagrid_slice_bwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 6 + [C.c_void_p] * 4),
+    "gsr_bilagrid_tv_fwd_bwd": (C.c_int, [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p] * 4),
 }
 
 _lib = None

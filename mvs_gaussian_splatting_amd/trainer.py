@@ -16,6 +16,7 @@ import math
 
 import torch
 
+from .bilagrid import bilateral_grid_tv_loss, slice_bilateral_grid
 from .densify import densify_and_prune, is_fork
 from .losses import add_densification_stats, l1_dssim_loss, opacity_sparsity_loss
 from .mcmc import add_new_gs, inject_noise, mcmc_regularizer, relocate_gs
@@ -95,6 +96,11 @@ class OptimizationParams:
     # term is on, the surface they see is the ray-plane depth of the blended plane instead of the expected depth; read
     # only then; False leaves the iteration as it is
     unbiased_depth = False
+    # per-image bilateral grids (bilagrid.py; training_iteration(bilateral_grids=)): their Adam's exponential schedule
+    # over `iterations` steps and the weight of their total-variation term; read only with grids
+    bilateral_grid_lr_init = 2e-3
+    bilateral_grid_lr_final = 2e-5
+    lambda_tv = 10.0
 
     def __init__(self, **overrides):
         for k, v in overrides.items():
@@ -117,7 +123,7 @@ def schedule(opt, iteration: int, white_background: bool = False) -> dict:
 
 def training_iteration(model, camera, opt, pipe, background, iteration, *, dataset=None, cameras_extent,
                        first_reset=None, gt_image=None, densify_kwargs=None, pose_optimizer=None, depth_loss=None,
-                       train_exposure=False, mcmc_kwargs=None, source_camera=None):
+                       train_exposure=False, mcmc_kwargs=None, source_camera=None, bilateral_grids=None):
     """``train.py:72-142`` for one camera, in the reference's order: learning rate, SH degree, background, ``render``
     with the fork's keyword arguments, L1 + D-SSIM against ``camera.original_image``, the opacity sparsity term
     (``opt.opacitysparse``), ``backward``; then, without gradients, the densification statistics, ``densify_and_prune``,
@@ -184,7 +190,14 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
     ``plane_depth``; the median is blended in under ``opt.depth_ratio`` as before (``surface.blend_plane_depth``); the
     NCC term's normal map is the planes kernel's.
     The refusals are those terms' own.  ``unbiased_depth = False``, or none of the three terms active: exactly the calls
-    made without it."""
+    made without it.
+    bilateral_grids: a ``bilagrid.BilateralGrids`` after its ``training_setup``.  The frame's image is
+    sliced through ``bilateral_grids.grid_for(camera.image_name)`` before the colour loss -- after the exposure when
+    ``train_exposure`` is on too -- ``opt.lambda_tv * bilateral_grid_tv_loss(bilateral_grids.grids)`` joins the loss, its
+    learning rate follows the iteration and its optimizer is stepped and zeroed where the model's is.  The source frame
+    of the multi-view terms is not sliced: its colour enters no term.  ``KeyError`` for a camera without a grid and
+    ``ValueError`` before ``training_setup``, both before anything is rendered.  None: exactly the calls made without
+    it."""
     strategy = getattr(opt, "strategy", "default")
     if strategy not in ("default", "mcmc"):
         raise ValueError(f"strategy must be 'default' or 'mcmc', got {strategy!r}")
@@ -202,6 +215,11 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
         raise ValueError("mcmc_kwargs needs opt.strategy == 'mcmc'")
     if train_exposure and getattr(model, "exposure_optimizer", None) is None:
         raise ValueError("train_exposure=True needs model.setup_exposures(image names) before training_setup")
+    frame_grid = None
+    if bilateral_grids is not None:
+        if getattr(bilateral_grids, "optimizer", None) is None:
+            raise ValueError("bilateral_grids needs its training_setup(opt) before the first iteration")
+        frame_grid = bilateral_grids.grid_for(camera.image_name)
     flag = lambda name: bool(getattr(dataset, name, False))      # noqa: E731
     normal_on = float(getattr(opt, "lambda_normal", 0.0)) > 0.0 and iteration >= int(getattr(opt, "normal_from_iter", 0))
     if normal_on:
@@ -245,6 +263,8 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
         first_reset = flag("white_background")
     todo = schedule(opt, iteration, first_reset)
     model.update_learning_rate(iteration)                                                       # :72
+    if bilateral_grids is not None:
+        bilateral_grids.update_learning_rate(iteration)
     if todo["sh_up"]:                                                                           # :75-76
         model.oneupSHdegree()
     bg = torch.rand((3), device=background.device) if opt.random_background else background    # :89
@@ -259,7 +279,10 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
                          **({"use_trained_exp": True} if train_exposure else {}))
     pkg = render(camera, model, pipe, bg, **render_kwargs)                                      # :91
     gt = camera.original_image if gt_image is None else gt_image
-    loss = l1_dssim_loss(pkg["render"], gt.to(pkg["render"].device), opt.lambda_dssim)          # :99-101
+    image = pkg["render"] if frame_grid is None else slice_bilateral_grid(pkg["render"], frame_grid)
+    loss = l1_dssim_loss(image, gt.to(image.device), opt.lambda_dssim)                          # :99-101
+    if bilateral_grids is not None:
+        loss = loss + float(getattr(opt, "lambda_tv", 10.0)) * bilateral_grid_tv_loss(bilateral_grids.grids)
     if opt.opacitysparse > 0:                                                                   # :102-106
         loss = loss + opacity_sparsity_loss(model._opacity, opt.opacitysparse)
     if mcmc:
@@ -331,6 +354,9 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
             if train_exposure:
                 model.exposure_optimizer.step()
                 model.exposure_optimizer.zero_grad(set_to_none=True)
+            if bilateral_grids is not None:
+                bilateral_grids.optimizer.step()
+                bilateral_grids.optimizer.zero_grad(set_to_none=True)
             if pose_optimizer is not None:
                 pose_optimizer.step()
                 pose_optimizer.zero_grad(set_to_none=True)
