@@ -5,7 +5,7 @@ the surface by marching tetrahedra, all on the HIP path (``mvs_gaussian_splattin
                                     [--sdf_trunc T] [--alpha_min A] [--max_depth D] [--depth_ratio R]
                                     [--num_cluster N] [--min_cluster_faces M] [--unbounded [--mesh_res N]]
                                     [--consistent K] [--n_sources S] [--points] [--unbiased_depth]
-                                    [-s <dataset>] [-r ...]
+                                    [--simplify_voxel S] [-s <dataset>] [-r ...]
 
 The scene is loaded as ``examples/render.py`` loads it (``cfg_args.json`` of the model directory; ``-s`` and the other
 switches override it).  The volume bounds the bulk of the model's positions (``tsdf.volume_for_points``); ``--resolution``
@@ -35,6 +35,11 @@ colour; K defaults to 2 there), the product DTU-style evaluation is defined on. 
 ``--unbiased_depth`` fuses PGSR's unbiased depth (``fuse_views(unbiased_depth=True)``) where the expected
 depth stood: the depth at which each pixel's ray meets the blended plane of the Gaussians it sees, which lies on a slanted
 surface where the expected depth bends towards the camera.  ``--depth_ratio`` blends the median into it as before.
+
+``--simplify_voxel S`` makes the mesh smaller by vertex clustering on a grid of cells of S world units (``mesh.simplify_mesh``;
+DESIGN.md §7.26): the vertices of a cell become their mean, the faces that collapse or repeat go.  It runs on the cleaned
+mesh when the mesh is cleaned, else on the raw one, and writes ``tsdf_mesh_simplified.ply`` (``tsdf_mesh_unbounded_simplified.ply``)
+next to the others.  A cell of two or three TSDF voxels suits a marching-tetrahedra mesh.  Without the flag nothing changes.
 """
 import argparse
 import json
@@ -48,7 +53,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 from mvs_gaussian_splatting_amd import (GaussianModel, ModelParams, Scene, bounding_sphere,  # noqa: E402
                                         contracted_volume_for_points, fuse_depth_points, fuse_views,
                                         volume_for_points)
-from mvs_gaussian_splatting_amd.mesh import clean_mesh  # noqa: E402
+from mvs_gaussian_splatting_amd.mesh import clean_mesh, simplify_mesh  # noqa: E402
 from mvs_gaussian_splatting_amd.ply_io import write_ply_mesh, write_ply_vertices  # noqa: E402
 from mvs_gaussian_splatting_amd.synthetic import PipelineParams  # noqa: E402
 
@@ -68,7 +73,7 @@ def write_points(path, xyz, rgb):
 
 def extract(dataset, iteration, voxel_size=None, resolution=None, sdf_trunc=None, alpha_min=0.5, max_depth=None,
             depth_ratio=0.0, num_cluster=None, min_cluster_faces=None, unbounded=False, mesh_res=None, consistent=None,
-            n_sources=4, points=False, unbiased_depth=False):
+            n_sources=4, points=False, unbiased_depth=False, simplify_voxel=None):
     with torch.no_grad():
         gaussians = GaussianModel(dataset.sh_degree)
         scene = Scene(dataset, gaussians, load_iteration=iteration, shuffle=False)
@@ -100,15 +105,21 @@ def extract(dataset, iteration, voxel_size=None, resolution=None, sdf_trunc=None
         cloud = os.path.join(os.path.dirname(path), "fused_points.ply")
         write_points(cloud, xyz, rgb)
         print(f"{xyz.shape[0]} fused points -> {cloud}")
-    if num_cluster is None and min_cluster_faces is None:
-        return path
-    if min_cluster_faces is None:
-        min_cluster_faces = 50
-    kept_v, kept_f, kept_c = clean_mesh(vertices, faces, colors, keep_largest=num_cluster, min_faces=min_cluster_faces)
-    post = path[:-len(".ply")] + "_post.ply"
-    write_ply_mesh(post, kept_v, kept_f, kept_c)
-    print(f"cleaned (num_cluster {num_cluster}, min_cluster_faces {min_cluster_faces}): {kept_v.shape[0]} of "
-          f"{vertices.shape[0]} vertices, {kept_f.shape[0]} of {faces.shape[0]} faces -> {post}")
+    if num_cluster is not None or min_cluster_faces is not None:
+        if min_cluster_faces is None:
+            min_cluster_faces = 50
+        kept_v, kept_f, kept_c = clean_mesh(vertices, faces, colors, keep_largest=num_cluster, min_faces=min_cluster_faces)
+        post = path[:-len(".ply")] + "_post.ply"
+        write_ply_mesh(post, kept_v, kept_f, kept_c)
+        print(f"cleaned (num_cluster {num_cluster}, min_cluster_faces {min_cluster_faces}): {kept_v.shape[0]} of "
+              f"{vertices.shape[0]} vertices, {kept_f.shape[0]} of {faces.shape[0]} faces -> {post}")
+        vertices, faces, colors = kept_v, kept_f, kept_c
+    if simplify_voxel is not None:
+        small_v, small_f, small_c = simplify_mesh(vertices, faces, colors, voxel_size=simplify_voxel)
+        simplified = path[:-len(".ply")] + "_simplified.ply"
+        write_ply_mesh(simplified, small_v, small_f, small_c)
+        print(f"simplified (cells of {simplify_voxel:.5g}): {small_v.shape[0]} of {vertices.shape[0]} vertices, "
+              f"{small_f.shape[0]} of {faces.shape[0]} faces -> {simplified}")
     return path
 
 
@@ -143,7 +154,11 @@ def main(argv=None):
     ap.add_argument("--points", action="store_true", help="also write the fused point cloud fused_points.ply")
     ap.add_argument("--unbiased_depth", action="store_true",
                     help="fuse PGSR's unbiased plane depth instead of the expected depth")
+    ap.add_argument("--simplify_voxel", type=float, default=None, metavar="S",
+                    help="simplify the mesh by vertex clustering on cells of S world units (after the cleaning, if any)")
     args = ap.parse_args(argv)
+    if args.simplify_voxel is not None and not 0 < args.simplify_voxel < float("inf"):
+        ap.error("--simplify_voxel must be positive and finite")
     if args.consistent is not None and args.consistent < 0:
         ap.error("--consistent must not be negative")
     if not 1 <= args.n_sources <= 64:
@@ -178,7 +193,8 @@ def main(argv=None):
             **({"unbounded": True, "mesh_res": args.mesh_res} if args.unbounded else {}),
             **({} if args.consistent is None and not args.points else
                {"consistent": args.consistent, "n_sources": args.n_sources, "points": args.points}),
-            **({"unbiased_depth": True} if args.unbiased_depth else {}))
+            **({"unbiased_depth": True} if args.unbiased_depth else {}),
+            **({} if args.simplify_voxel is None else {"simplify_voxel": args.simplify_voxel}))
 
 
 if __name__ == "__main__":

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 38
+#define GSR_ABI_VERSION 39
 
 enum {
   GSR_OK = 0,
@@ -1152,6 +1152,60 @@ int gsr_bilagrid_slice_bwd(const float* x, const float* grid, const float* g, in
                            void* stream);
 int gsr_bilagrid_tv_fwd_bwd(const float* grids, int32_t N, int32_t Wg, int32_t Hg, int32_t L, float* value,
                             float* dgrids, void* workspace, void* stream);
+
+/* ---- Mesh simplification by vertex clustering on a uniform grid, ABI v39 (csrc/mesh_simplify.hip,
+ * csrc/mesh_simplify_math.h; mesh.simplify_mesh).  The kernels around the caller's sorts and scans;
+ * gsr_mesh_mark_vertices and gsr_mesh_compact (above) mark the referenced vertices in front and compact behind.
+ * vertices / colors [V,3] float32, faces [F,3] int32, device, contiguous; 1 <= V, F < 2^31; 1 <= K <= V clusters.
+ * Every call checks its arguments before any HIP call (GSR_E_BADARG: a NULL pointer that is not marked optional, a size
+ * outside its range; GSR_E_ALIGN: int32 / float arrays 4-byte, int64 / double arrays 8-byte), is asynchronous on
+ * `stream`, allocates nothing and reads nothing back.  No float atomics: every output is the same bits from run to run.
+ * status: device int32 [1], zeroed by the caller; the kernels OR the bits below into it and never use what they refuse
+ * as an index.  The caller reads the word back with its sizes and refuses the mesh. */
+enum {
+  GSR_SIMPLIFY_BAD_INDEX = 1,     /* a face, order, start or cluster index outside its range */
+  GSR_SIMPLIFY_NOT_FINITE = 2,    /* a marked vertex has a coordinate that is not finite */
+  GSR_SIMPLIFY_OUT_OF_RANGE = 4   /* a marked vertex has a cell index outside 0 .. 2^21 - 1 */
+};
+/* The default origin, three launches: origin (three doubles on the device) = the per-axis minimum over the finite
+ * coordinates of the vertices with vertex_mark[v] != 0, converted to double, minus voxel_size / 2.  lowest int32 [3]:
+ * scratch (the minimum as integers that order as the floats do, by integer atomicMin: the same bits whatever order they
+ * land in).  No finite marked coordinate: origin is NaN, and gsr_simplify_cell_keys refuses every marked vertex. */
+int gsr_simplify_default_origin(const float* vertices, const uint8_t* vertex_mark, int64_t V, double voxel_size,
+                                int32_t* lowest, double* origin, void* stream);
+/* keys int64 [V].  vertex_mark uint8 [V]; origin: three doubles on the device; h = voxel_size, finite and positive.  A
+ * marked vertex gets ix << 42 | iy << 21 | iz with i = floor(((double)x - origin) / h) per axis; an unmarked one, and a
+ * marked one that sets GSR_SIMPLIFY_NOT_FINITE or _OUT_OF_RANGE, gets INT64_MAX, which sorts last. */
+int gsr_simplify_cell_keys(const float* vertices, const uint8_t* vertex_mark, int64_t V, const double* origin,
+                           double voxel_size, int64_t* keys, int32_t* status, void* stream);
+/* keys_sorted int64 [V] ascending; head uint8 [V]: 1 where slot i holds a cell (not INT64_MAX) that slot i - 1 does not.
+ * The inclusive scan of head, minus one, is the cluster of every slot; its total is K. */
+int gsr_simplify_run_heads(const int64_t* keys_sorted, int64_t V, uint8_t* head, void* stream);
+/* order int64 [V]: the vertex each sorted slot came from (a stable sort's indices, so a cell's members ascend); ends int64
+ * [V]: the inclusive scan of head.  Two launches.  start int32 [K + 1] (scratch): the first slot of every cluster, then
+ * the first slot without a cell (or V); cluster_of_vertex int32 [V]: the cluster of every vertex, -1 for one without a
+ * cell.  Then one lane per cluster: out_vertices [K,3] (out_colors [K,3], given together with colors or both NULL) = the
+ * mean of the members' rows, summed in float64 in slot order from the first member on and rounded to float32 once: a
+ * cluster of one member is a bit-copy. */
+int gsr_simplify_reduce(const float* vertices, const float* colors, const int64_t* keys_sorted, const int64_t* order,
+                        const int64_t* ends, int64_t V, int64_t K, int32_t* start, float* out_vertices, float* out_colors,
+                        int32_t* cluster_of_vertex, int32_t* status, void* stream);
+/* tri int32 [F,3]: the clusters of each face's corners, in corner order; keep uint8 [F]: 1 unless two of them are equal;
+ * key_first int64 [F], key_third int32 [F]: the triple rotated so that its smallest index comes first, as first << 32 |
+ * second and third; INT64_MAX and INT32_MAX for a face that is not kept.  A face with a corner outside 0..V-1 or without
+ * a cluster sets GSR_SIMPLIFY_BAD_INDEX and is not kept. */
+int gsr_simplify_face_keys(const int32_t* faces, const int32_t* cluster_of_vertex, int64_t F, int64_t V, int64_t K,
+                           int32_t* tri, uint8_t* keep, int64_t* key_first, int32_t* key_third, int32_t* status,
+                           void* stream);
+/* The caller sorts the faces stably by key_third and then stably by key_first: first_sorted int64 [F] is key_first in
+ * that order, perm int64 [F] the face of every slot; key_third stays unsorted.  A slot whose rotated triple equals its
+ * predecessor's clears keep of its face: of the faces with one triple the smallest face index survives. */
+int gsr_simplify_face_unique(const int64_t* first_sorted, const int64_t* perm, const int32_t* key_third, int64_t F,
+                             uint8_t* keep, int32_t* status, void* stream);
+/* cluster_mark uint8 [K] and cluster_offs int64 [K]: what gsr_mesh_mark_vertices wrote for tri and keep, and its
+ * exclusive scan.  vertex_cluster int32 [V] = cluster_offs[c] for a vertex whose cluster c is marked, else -1. */
+int gsr_simplify_vertex_map(const int32_t* cluster_of_vertex, const uint8_t* cluster_mark, const int64_t* cluster_offs,
+                            int64_t V, int64_t K, int32_t* vertex_cluster, void* stream);
 
 #ifdef __cplusplus
 }

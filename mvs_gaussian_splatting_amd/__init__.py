@@ -21,7 +21,7 @@ from .tsdf import (TSDFVolume, ContractedTSDFVolume, fuse_views, volume_for_poin
 from .mcmc import mcmc_regularizer, inject_noise, relocate_gs, add_new_gs  # noqa: F401
 from .normal_consistency import normal_consistency_loss, depth_to_normals  # noqa: F401
 from .surface import surface_depth, plane_depth  # noqa: F401
-from .mesh import connected_components, clean_mesh  # noqa: F401
+from .mesh import connected_components, clean_mesh, simplify_mesh  # noqa: F401
 from .geometry_eval import NearestIndex, nearest_points, sample_surface, evaluate_points, evaluate_mesh  # noqa: F401
 from .mvs import (select_source_views, depth_consistency, backproject_depth, fuse_depth_points,  # noqa: F401
                   multi_view_geo_loss, multi_view_ncc_loss, gray_image)
@@ -33,7 +33,7 @@ __all__ = ["Scene", "Camera", "MiniCam", "PoseCamera", "ModelParams", "load_imag
            "mcmc_regularizer", "inject_noise", "relocate_gs", "add_new_gs", "gaussian_normals", "gaussian_planes",
            "TSDFVolume", "ContractedTSDFVolume", "fuse_views", "volume_for_points", "contracted_volume_for_points",
            "bounding_sphere", "normal_consistency_loss", "depth_to_normals",
-           "surface_depth", "plane_depth", "connected_components", "clean_mesh", "NearestIndex", "nearest_points", "sample_surface",
+           "surface_depth", "plane_depth", "connected_components", "clean_mesh", "simplify_mesh", "NearestIndex", "nearest_points", "sample_surface",
            "evaluate_points", "evaluate_mesh", "select_source_views", "depth_consistency", "backproject_depth",
            "fuse_depth_points", "multi_view_geo_loss", "multi_view_ncc_loss",
            "gray_image", "slice_bilateral_grid", "bilateral_grid_tv_loss", "BilateralGrids"]

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # instead of copying it over the in-tree library
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")
 
-ABI_VERSION = 38
+ABI_VERSION = 39
 
 
 class GsrParams(C.Structure):
@@ -340,6 +340,15 @@ SYMBOLS = {
     "gsr_bilagrid_slice_fwd": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 6 + [C.c_void_p] * 2),
     "gsr_bilagrid_slice_bwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 6 + [C.c_void_p] * 4),
     "gsr_bilagrid_tv_fwd_bwd": (C.c_int, [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p] * 4),
+    # mesh simplification by vertex clustering on a uniform grid: the kernels around the sorts and scans of
+    # mesh.simplify_mesh (csrc/mesh_simplify.hip)
+    "gsr_simplify_default_origin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double] + [C.c_void_p] * 3),
+    "gsr_simplify_cell_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_double] + [C.c_void_p] * 3),
+    "gsr_simplify_run_heads": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "gsr_simplify_reduce": (C.c_int, [C.c_void_p] * 5 + [C.c_int64] * 2 + [C.c_void_p] * 6),
+    "gsr_simplify_face_keys": (C.c_int, [C.c_void_p] * 2 + [C.c_int64] * 3 + [C.c_void_p] * 6),
+    "gsr_simplify_face_unique": (C.c_int, [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 3),
+    "gsr_simplify_vertex_map": (C.c_int, [C.c_void_p] * 3 + [C.c_int64] * 2 + [C.c_void_p] * 2),
 }
 
 _lib = None

@@ -9,10 +9,19 @@ small closed shell of its own.  2DGS clusters the connected triangles, keeps the
 drops the vertices nothing refers to; ``clean_mesh`` is that rule.  The labelling is a lock-free union-find on the device
 (init, hook, flatten), the numbering and the compaction are scans (torch) around small kernels; the mesh never leaves the
 device.  There is no CPU path.
+
+    vertices, faces, colors = simplify_mesh(vertices, faces, colors, voxel_size=2 * volume.voxel_size)
+
+Marching tetrahedra ties the triangle size to the TSDF voxel, not to the detail of the surface.  ``simplify_mesh`` makes
+the mesh smaller by vertex clustering on a uniform grid (``csrc/mesh_simplify.hip`` behind the ``gsr_simplify_*`` entry
+points): the vertices of a grid cell become their mean, the faces that collapse or repeat go.  The same
+key-sort-run pattern, the same compaction.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
+import sys
 from typing import Optional, Tuple
 
 import torch
@@ -197,4 +206,166 @@ def clean_mesh(vertices: torch.Tensor, faces: torch.Tensor, colors: Optional[tor
     return out_vertices, out_faces, out_colors
 
 
-__all__ = ["connected_components", "clean_mesh"]
+CELL_BITS = 21                      # bits per axis of a cell key (csrc/mesh_simplify_math.h)
+_BAD_INDEX, _NOT_FINITE, _OUT_OF_RANGE = 1, 2, 4       # bits of the status word (include/gsr.h: GSR_SIMPLIFY_*)
+
+
+def _simplify_status(bad: int, V: int, voxel_size: float) -> None:
+    if bad & _BAD_INDEX:
+        raise _lib.GsrError(f"simplify_mesh failed: a face refers to a vertex outside 0..{V - 1}")
+    if bad & _NOT_FINITE:
+        raise _lib.GsrError("simplify_mesh failed: a vertex that a face refers to has a coordinate that is not finite")
+    if bad & _OUT_OF_RANGE:
+        raise _lib.GsrError(f"simplify_mesh failed: a cell index lies outside 0..2^{CELL_BITS}-1: voxel_size "
+                            f"{voxel_size!r} is too small for the extent of the mesh, or the origin lies above a vertex")
+    if bad:
+        raise _lib.GsrError(f"simplify_mesh failed: status {bad}")
+
+
+def simplify_mesh(vertices: torch.Tensor, faces: torch.Tensor, colors: Optional[torch.Tensor] = None, *,
+                  voxel_size: float, origin=None, return_map: bool = False):
+    """Simplify a mesh by vertex clustering on a uniform grid (Rossignac-Borrel; Open3D's ``simplify_vertex_clustering``
+    with the averaging contraction) -> ``(vertices float32 [V',3], faces int32 [F',3], colors float32 [V',3] or None)``,
+    with ``return_map=True`` also ``vertex_cluster int32 [V]``; new tensors on the same device (csrc/mesh_simplify.hip;
+    DESIGN.md §7.26).
+
+    The rule, step by step:
+
+    1. Only the vertices that a face refers to take part; the others may hold anything.  A face index outside
+       ``0..V-1`` and a referenced coordinate that is not finite raise ``GsrError``.
+    2. The cell of a vertex is ``floor(((double)x - origin) / voxel_size)`` per axis, in float64.  ``origin`` (three
+       finite floats) defaults to the per-axis minimum of the referenced vertices minus ``voxel_size / 2``.  Every cell
+       index must lie in ``0..2^21-1``, or ``GsrError`` says that ``voxel_size`` is too small for the extent or that the
+       origin lies above a vertex.  Key: ``ix << 42 | iy << 21 | iz``.
+    3. The clusters are the distinct keys, in ascending order.
+    4. A cluster's position and colour are the means of its members' float32 rows, summed in float64 in ascending vertex
+       index and rounded to float32 once: the same bits from run to run, and a cluster of one member is a bit-copy.
+    5. A face becomes the clusters of its corners.  A face with two equal corners is dropped.  Of the faces that have the
+       same corners in the same cyclic order the one with the smallest index stays; faces of opposite winding are
+       different faces.  The faces that stay keep their relative order and their corner order.
+    6. Clusters that no remaining face refers to are dropped; the rest keep their key order.  ``vertex_cluster[v]`` is
+       the output vertex that ``v`` went to, ``-1`` for a vertex that took no part or whose cluster was dropped.
+
+    What vertex clustering does not preserve: manifoldness and closedness.  A thin wall whose two sides fall into the
+    same cells folds onto itself, a tunnel narrower than a cell closes, an edge may end up in more than two faces, and a
+    closed surface may open where faces degenerate.  What it does bound: every output vertex lies within the cell of its
+    members, so within ``sqrt(3) * voxel_size`` of each of them.  Triangles larger than a cell pass through untouched.
+
+    Two host read-backs (the number of clusters with the status word, then ``F'`` and ``V'``); the default origin stays
+    on the device.  Everything runs on the current stream and no input is written.  ``F == 0``: ``[0,3]`` tensors (and a
+    map of ``-1``) without a native call.  There is no CPU path."""
+    if not isinstance(vertices, torch.Tensor) or vertices.dtype != torch.float32 or vertices.dim() != 2 \
+            or vertices.shape[1] != 3:
+        raise ValueError(f"vertices must be a float32 [V,3] tensor, got {getattr(vertices, 'dtype', type(vertices))} "
+                         f"{tuple(getattr(vertices, 'shape', ()))}")
+    V = int(vertices.shape[0])
+    F, _ = _check_faces(faces, V, "simplify_mesh")
+    dev = vertices.device
+    if faces.device != dev:
+        raise ValueError(f"faces must be on the device of vertices ({dev}), got {faces.device}")
+    if colors is not None and (not isinstance(colors, torch.Tensor) or colors.dtype != torch.float32
+                               or tuple(colors.shape) != (V, 3) or colors.device != dev):
+        raise ValueError(f"colors must be a float32 [{V},3] tensor on {dev}, got "
+                         f"{getattr(colors, 'dtype', type(colors))} {tuple(getattr(colors, 'shape', ()))} on "
+                         f"{getattr(colors, 'device', None)}")
+    if isinstance(voxel_size, bool) or not isinstance(voxel_size, (int, float)) \
+            or not 0 < voxel_size <= sys.float_info.max:
+        raise ValueError(f"voxel_size must be a finite positive float, got {voxel_size!r}")
+    h = float(voxel_size)
+    if origin is not None:
+        try:
+            origin = tuple(float(o) for o in origin)
+        except (TypeError, ValueError):
+            raise ValueError(f"origin must be None or three finite floats, got {origin!r}") from None
+        if len(origin) != 3 or not all(math.isfinite(o) for o in origin):
+            raise ValueError(f"origin must be None or three finite floats, got {origin!r}")
+    if not isinstance(return_map, bool):
+        raise ValueError(f"return_map must be a bool, got {return_map!r}")
+    _need_gpu(vertices, "simplify_mesh")
+
+    def empty():
+        out = (torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty((0, 3), dtype=torch.int32, device=dev),
+               None if colors is None else torch.empty((0, 3), dtype=torch.float32, device=dev))
+        return out + (torch.full((V,), -1, dtype=torch.int32, device=dev),) if return_map else out
+
+    if F == 0:
+        return empty()
+    lib = _lib.load()
+    vertices_c, faces_c = vertices.detach().contiguous(), faces.detach().contiguous()
+    colors_c = None if colors is None else colors.detach().contiguous()
+    ptr = lambda t: None if t is None else t.data_ptr()                                          # noqa: E731
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        # step 1: the vertices that take part are those gsr_mesh_mark_vertices marks with every face kept
+        every_face = torch.ones(F, dtype=torch.uint8, device=dev)
+        vertex_mark = torch.zeros(V, dtype=torch.uint8, device=dev)
+        _lib.check(lib.gsr_mesh_mark_vertices(faces_c.data_ptr(), every_face.data_ptr(), F, V, vertex_mark.data_ptr(),
+                                              status.data_ptr(), stream), "gsr_mesh_mark_vertices")
+        # step 2: cells.  The default origin never leaves the device
+        if origin is None:
+            origin_dev = torch.empty(3, dtype=torch.float64, device=dev)
+            lowest = torch.empty(3, dtype=torch.int32, device=dev)
+            _lib.check(lib.gsr_simplify_default_origin(vertices_c.data_ptr(), vertex_mark.data_ptr(), V, h, lowest.data_ptr(),
+                                                       origin_dev.data_ptr(), stream), "gsr_simplify_default_origin")
+        else:
+            origin_dev = torch.tensor(origin, dtype=torch.float64, device=dev)
+        keys = torch.empty(V, dtype=torch.int64, device=dev)
+        _lib.check(lib.gsr_simplify_cell_keys(vertices_c.data_ptr(), vertex_mark.data_ptr(), V, origin_dev.data_ptr(), h,
+                                              keys.data_ptr(), status.data_ptr(), stream), "gsr_simplify_cell_keys")
+        # step 3: stable, so that the members of a cell stay in ascending vertex index (plumbing: stays in torch)
+        keys_sorted, order = torch.sort(keys, stable=True)
+        head = torch.empty(V, dtype=torch.uint8, device=dev)
+        _lib.check(lib.gsr_simplify_run_heads(keys_sorted.data_ptr(), V, head.data_ptr(), stream), "gsr_simplify_run_heads")
+        ends = torch.cumsum(head, dim=0, dtype=torch.int64)
+        K, bad = (int(v) for v in torch.stack((ends[-1], status[0].to(torch.int64))).tolist())       # read-back 1
+        _simplify_status(bad, V, voxel_size)
+        # step 4: the representatives
+        start = torch.empty(K + 1, dtype=torch.int32, device=dev)
+        means = torch.empty((K, 3), dtype=torch.float32, device=dev)
+        mean_colors = None if colors_c is None else torch.empty((K, 3), dtype=torch.float32, device=dev)
+        cluster_of_vertex = torch.empty(V, dtype=torch.int32, device=dev)
+        _lib.check(lib.gsr_simplify_reduce(vertices_c.data_ptr(), ptr(colors_c), keys_sorted.data_ptr(), order.data_ptr(),
+                                           ends.data_ptr(), V, K, start.data_ptr(), means.data_ptr(), ptr(mean_colors),
+                                           cluster_of_vertex.data_ptr(), status.data_ptr(), stream), "gsr_simplify_reduce")
+        # step 5: the faces.  Three 31-bit indices do not fit one int64 key: two stable sorts, the third index first
+        tri = torch.empty((F, 3), dtype=torch.int32, device=dev)
+        keep = torch.empty(F, dtype=torch.uint8, device=dev)
+        key_first = torch.empty(F, dtype=torch.int64, device=dev)
+        key_third = torch.empty(F, dtype=torch.int32, device=dev)
+        _lib.check(lib.gsr_simplify_face_keys(faces_c.data_ptr(), cluster_of_vertex.data_ptr(), F, V, K, tri.data_ptr(),
+                                              keep.data_ptr(), key_first.data_ptr(), key_third.data_ptr(),
+                                              status.data_ptr(), stream), "gsr_simplify_face_keys")
+        by_third = torch.sort(key_third, stable=True).indices
+        first_sorted, by_first = torch.sort(key_first[by_third], stable=True)
+        perm = by_third[by_first]
+        _lib.check(lib.gsr_simplify_face_unique(first_sorted.data_ptr(), perm.data_ptr(), key_third.data_ptr(), F,
+                                                keep.data_ptr(), status.data_ptr(), stream), "gsr_simplify_face_unique")
+        # step 6: compaction, with the cluster means as the vertices
+        cluster_mark = torch.zeros(K, dtype=torch.uint8, device=dev)
+        _lib.check(lib.gsr_mesh_mark_vertices(tri.data_ptr(), keep.data_ptr(), F, K, cluster_mark.data_ptr(),
+                                              status.data_ptr(), stream), "gsr_mesh_mark_vertices")
+        vert_end = torch.cumsum(cluster_mark, dim=0, dtype=torch.int64)
+        face_end = torch.cumsum(keep, dim=0, dtype=torch.int64)
+        Vk, Fk, bad = (int(v) for v in torch.stack((vert_end[-1], face_end[-1],
+                                                    status[0].to(torch.int64))).tolist())            # read-back 2
+        _simplify_status(bad, V, voxel_size)
+        if Fk == 0:
+            return empty()
+        out_vertices = torch.empty((Vk, 3), dtype=torch.float32, device=dev)
+        out_faces = torch.empty((Fk, 3), dtype=torch.int32, device=dev)
+        out_colors = None if colors_c is None else torch.empty((Vk, 3), dtype=torch.float32, device=dev)
+        vert_offs, face_offs = vert_end - cluster_mark, face_end - keep                              # exclusive scans
+        _lib.check(lib.gsr_mesh_compact(means.data_ptr(), ptr(mean_colors), tri.data_ptr(), keep.data_ptr(),
+                                        cluster_mark.data_ptr(), vert_offs.data_ptr(), face_offs.data_ptr(), K, F, Vk, Fk,
+                                        out_vertices.data_ptr(), ptr(out_colors), out_faces.data_ptr(),
+                                        status.data_ptr(), stream), "gsr_mesh_compact")
+        if not return_map:
+            return out_vertices, out_faces, out_colors
+        vertex_cluster = torch.empty(V, dtype=torch.int32, device=dev)
+        _lib.check(lib.gsr_simplify_vertex_map(cluster_of_vertex.data_ptr(), cluster_mark.data_ptr(), vert_offs.data_ptr(),
+                                               V, K, vertex_cluster.data_ptr(), stream), "gsr_simplify_vertex_map")
+    return out_vertices, out_faces, out_colors, vertex_cluster
+
+
+__all__ = ["connected_components", "clean_mesh", "simplify_mesh"]
