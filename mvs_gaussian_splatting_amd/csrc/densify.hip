@@ -28,7 +28,7 @@ __global__ __launch_bounds__(DN_BLOCK) void densify_plan_kernel(int P, const flo
                                                                  const float* __restrict__ opacity, float thr, float pde,
                                                                  float min_opacity, float ws_limit, int use_ws,
                                                                  uint8_t* __restrict__ flags,
-                                                                 uint32_t* __restrict__ block_counts, int nblocks) {
+                                                                 uint32_t* __restrict__ block_counts, int stride) {
   __shared__ uint32_t cnt[4];
   if (threadIdx.x < 4) cnt[threadIdx.x] = 0;
   __syncthreads();
@@ -59,13 +59,13 @@ __global__ __launch_bounds__(DN_BLOCK) void densify_plan_kernel(int P, const flo
     if ((threadIdx.x & (WAVE - 1)) == 0 && m) atomicAdd(&cnt[b], (uint32_t)__builtin_popcountll(m));
   }
   __syncthreads();
-  if (threadIdx.x < 4) block_counts[threadIdx.x * (nblocks + 1) + blockIdx.x] = cnt[threadIdx.x];
+  if (threadIdx.x < 4) block_counts[(size_t)threadIdx.x * stride + blockIdx.x] = cnt[threadIdx.x];
 }
 
 // pos[c][i] = output row of Gaussian i in class c (keep / clone / child), or -1; sel_rank[i] = rank among the
 // split-selected (the row of its first noise sample), or -1.
 __global__ __launch_bounds__(DN_BLOCK) void densify_positions_kernel(int P, const uint8_t* __restrict__ flags,
-                                                                      const uint32_t* __restrict__ block_offs, int nblocks,
+                                                                      const uint32_t* __restrict__ block_offs, int stride,
                                                                       int32_t* __restrict__ pos) {
   __shared__ uint32_t wave_tot[4][DN_BLOCK / WAVE];
   const int i = blockIdx.x * DN_BLOCK + threadIdx.x;
@@ -82,7 +82,7 @@ __global__ __launch_bounds__(DN_BLOCK) void densify_positions_kernel(int P, cons
   if (i >= P) return;
 #pragma unroll
   for (int b = 0; b < 4; ++b) {
-    uint32_t base = block_offs[b * (nblocks + 1) + blockIdx.x];
+    uint32_t base = block_offs[(size_t)b * stride + blockIdx.x];
     for (int w = 0; w < wid; ++w) base += wave_tot[b][w];
     pos[(size_t)b * P + i] = ((f >> b) & 1) ? (int32_t)(base + rank[b]) : -1;
   }
@@ -140,7 +140,8 @@ __global__ void densify_split_children_kernel(int P, const float* __restrict__ x
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------
-// counts = {kept originals, kept clones, kept children per copy, split-selected}
+// counts = {kept originals, kept clones, kept children per copy, split-selected}; the four counter arrays (and their
+// offsets) lie scan_array_stride(nblocks) words apart: launch_scan_block_sums needs every one of them aligned
 struct DensifyLayout {
   size_t flags, block_counts, block_offs, totals, pos, bytes;
   int nblocks;
@@ -151,8 +152,8 @@ DensifyLayout::DensifyLayout(int P) {
   if (nblocks < 1) nblocks = 1;
   size_t o = 0;
   flags = o;        o = align_up(o + (size_t)(P > 0 ? P : 1), 256);
-  block_counts = o; o = align_up(o + 4 * 4 * (size_t)(nblocks + 1), 256);
-  block_offs = o;   o = align_up(o + 4 * 4 * (size_t)(nblocks + 1), 256);
+  block_counts = o; o = align_up(o + 4 * 4 * (size_t)scan_array_stride(nblocks), 256);
+  block_offs = o;   o = align_up(o + 4 * 4 * (size_t)scan_array_stride(nblocks), 256);
   totals = o;       o = align_up(o + 64, 256);
   pos = o;          o = align_up(o + 4 * 4 * (size_t)(P > 0 ? P : 1), 256);
   bytes = o;
@@ -168,13 +169,13 @@ static void launch_densify_plan(int P, const float* accum, const float* denom, c
   uint32_t* offs = reinterpret_cast<uint32_t*>(base + L.block_offs);
   uint32_t* totals = reinterpret_cast<uint32_t*>(base + L.totals);
   int32_t* pos = reinterpret_cast<int32_t*>(base + L.pos);
-  const int nb = L.nblocks, stride = nb + 1;
+  const int nb = L.nblocks, stride = scan_array_stride(nb);
   hipLaunchKernelGGL(densify_plan_kernel, dim3(nb), dim3(DN_BLOCK), 0, s, P, accum, denom, scaling, opacity, thr, pde,
-                     min_opacity, ws_limit, use_ws, flags, counts, nb);
+                     min_opacity, ws_limit, use_ws, flags, counts, stride);
   launch_scan_block_sums(counts, offs, totals, counts + stride, offs + stride, totals + 1, nb, s);
   launch_scan_block_sums(counts + 2 * stride, offs + 2 * stride, totals + 2, counts + 3 * stride, offs + 3 * stride,
                          totals + 3, nb, s);
-  hipLaunchKernelGGL(densify_positions_kernel, dim3(nb), dim3(DN_BLOCK), 0, s, P, flags, offs, nb, pos);
+  hipLaunchKernelGGL(densify_positions_kernel, dim3(nb), dim3(DN_BLOCK), 0, s, P, flags, offs, stride, pos);
 }
 
 static void launch_densify_gather_rows(int P, int w, const float* src, const void* ws, const uint32_t counts[4],

@@ -48,7 +48,7 @@ __global__ __launch_bounds__(DF_BLOCK) void densify_fork_plan_kernel(int P, cons
                                                                       const float* __restrict__ split_scale, float thr,
                                                                       float pde, float min_opacity, float ws_limit,
                                                                       int use_ws, uint8_t* __restrict__ flags,
-                                                                      uint32_t* __restrict__ block_counts, int nblocks) {
+                                                                      uint32_t* __restrict__ block_counts, int stride) {
   __shared__ uint32_t cnt[DF_NC];
   if (threadIdx.x < DF_NC) cnt[threadIdx.x] = 0;
   __syncthreads();
@@ -79,13 +79,13 @@ __global__ __launch_bounds__(DF_BLOCK) void densify_fork_plan_kernel(int P, cons
     if ((threadIdx.x & (WAVE - 1)) == 0 && m) atomicAdd(&cnt[b], (uint32_t)__builtin_popcountll(m));
   }
   __syncthreads();
-  if (threadIdx.x < DF_NC) block_counts[threadIdx.x * (nblocks + 1) + blockIdx.x] = cnt[threadIdx.x];
+  if (threadIdx.x < DF_NC) block_counts[(size_t)threadIdx.x * stride + blockIdx.x] = cnt[threadIdx.x];
 }
 
 // pos[c * P + i] = rank of row i in class c, or -1; sel_src[rank among the selected] = i
 __global__ __launch_bounds__(DF_BLOCK) void densify_fork_positions_kernel(int P, const uint8_t* __restrict__ flags,
                                                                            const uint32_t* __restrict__ block_offs,
-                                                                           int nblocks, int32_t* __restrict__ pos,
+                                                                           int stride, int32_t* __restrict__ pos,
                                                                            int32_t* __restrict__ sel_src) {
   __shared__ uint32_t wave_tot[DF_NC][DF_BLOCK / WAVE];
   const int i = blockIdx.x * DF_BLOCK + threadIdx.x;
@@ -102,7 +102,7 @@ __global__ __launch_bounds__(DF_BLOCK) void densify_fork_positions_kernel(int P,
   if (i >= P) return;
 #pragma unroll
   for (int b = 0; b < DF_NC; ++b) {
-    uint32_t base = block_offs[b * (nblocks + 1) + blockIdx.x];
+    uint32_t base = block_offs[(size_t)b * stride + blockIdx.x];
     for (int w = 0; w < wid; ++w) base += wave_tot[b][w];
     const int32_t r = ((f >> b) & 1) ? (int32_t)(base + rank[b]) : -1;
     pos[(size_t)b * P + i] = r;
@@ -260,7 +260,8 @@ __global__ __launch_bounds__(256) void densify_fork_rows_dir_kernel(ForkRowsArgs
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------
-// counts = {kept originals, kept clones / grown, kept children per copy, split-selected, selected}
+// counts = {kept originals, kept clones / grown, kept children per copy, split-selected, selected}; the five counter
+// arrays (and their offsets) lie scan_array_stride(nblocks) words apart, each aligned for launch_scan_block_sums
 struct DensifyForkLayout {
   size_t flags, block_counts, block_offs, totals, pos, sel_src, bytes;
   int nblocks;
@@ -272,8 +273,8 @@ DensifyForkLayout::DensifyForkLayout(int P) {
   const size_t Pn = (size_t)(P > 0 ? P : 1);
   size_t o = 0;
   flags = o;        o = align_up(o + Pn, 256);
-  block_counts = o; o = align_up(o + 4 * DF_NC * (size_t)(nblocks + 1), 256);
-  block_offs = o;   o = align_up(o + 4 * DF_NC * (size_t)(nblocks + 1), 256);
+  block_counts = o; o = align_up(o + 4 * DF_NC * (size_t)scan_array_stride(nblocks), 256);
+  block_offs = o;   o = align_up(o + 4 * DF_NC * (size_t)scan_array_stride(nblocks), 256);
   totals = o;       o = align_up(o + 64, 256);
   pos = o;          o = align_up(o + 4 * DF_NC * Pn, 256);
   sel_src = o;      o = align_up(o + 4 * Pn, 256);
@@ -291,13 +292,13 @@ static void launch_densify_fork_plan(int P, const float* accum, const float* den
   uint32_t* totals = reinterpret_cast<uint32_t*>(base + L.totals);
   int32_t* pos = reinterpret_cast<int32_t*>(base + L.pos);
   int32_t* sel_src = reinterpret_cast<int32_t*>(base + L.sel_src);
-  const int nb = L.nblocks, st = nb + 1;
+  const int nb = L.nblocks, st = scan_array_stride(nb);
   hipLaunchKernelGGL(densify_fork_plan_kernel, dim3(nb), dim3(DF_BLOCK), 0, s, P, accum, denom, scaling, opacity,
-                     split_scale, thr, pde, min_opacity, ws_limit, use_ws, flags, counts, nb);
+                     split_scale, thr, pde, min_opacity, ws_limit, use_ws, flags, counts, st);
   launch_scan_block_sums(counts, offs, totals, counts + st, offs + st, totals + 1, nb, s);
   launch_scan_block_sums(counts + 2 * st, offs + 2 * st, totals + 2, counts + 3 * st, offs + 3 * st, totals + 3, nb, s);
   launch_scan_block_sums(counts + 4 * st, offs + 4 * st, totals + 4, nullptr, nullptr, nullptr, nb, s);
-  hipLaunchKernelGGL(densify_fork_positions_kernel, dim3(nb), dim3(DF_BLOCK), 0, s, P, flags, offs, nb, pos, sel_src);
+  hipLaunchKernelGGL(densify_fork_positions_kernel, dim3(nb), dim3(DF_BLOCK), 0, s, P, flags, offs, st, pos, sel_src);
 }
 
 static void launch_densify_fork_gather_rows(int P, int w, const float* src, const void* ws, const uint32_t counts[5],

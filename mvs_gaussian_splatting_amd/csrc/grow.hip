@@ -54,7 +54,7 @@ __global__ __launch_bounds__(GR_BLOCK) void grow_plan_kernel(int P, const float*
                                                               const float* __restrict__ denom,
                                                               const float* __restrict__ scaling, float thr, float pde,
                                                               int split_mode, uint8_t* __restrict__ flags,
-                                                              uint32_t* __restrict__ block_counts, int nblocks) {
+                                                              uint32_t* __restrict__ block_counts, int stride) {
   __shared__ uint32_t cnt[2];
   if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
   __syncthreads();
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(GR_BLOCK) void grow_plan_kernel(int P, const float*
     if ((threadIdx.x & (WAVE - 1)) == 0 && m) atomicAdd(&cnt[b], (uint32_t)__builtin_popcountll(m));
   }
   __syncthreads();
-  if (threadIdx.x < 2) block_counts[threadIdx.x * (nblocks + 1) + blockIdx.x] = cnt[threadIdx.x];
+  if (threadIdx.x < 2) block_counts[(size_t)threadIdx.x * stride + blockIdx.x] = cnt[threadIdx.x];
 }
 
 __global__ __launch_bounds__(GR_BLOCK) void grow_positions_kernel(int P, const uint8_t* __restrict__ flags,
@@ -369,8 +369,9 @@ GrowLayout::GrowLayout(int P) {
   if (nblocks < 1) nblocks = 1;
   size_t o = 0;
   flags = o;        o = align_up(o + (size_t)(P > 0 ? P : 1), 256);
-  block_counts = o; o = align_up(o + 2 * 4 * (size_t)(nblocks + 1), 256);
-  block_offs = o;   o = align_up(o + 2 * 4 * (size_t)(nblocks + 1), 256);
+  // two counter arrays scan_array_stride(nblocks) words apart, each aligned for launch_scan_block_sums
+  block_counts = o; o = align_up(o + 2 * 4 * (size_t)scan_array_stride(nblocks), 256);
+  block_offs = o;   o = align_up(o + 2 * 4 * (size_t)scan_array_stride(nblocks), 256);
   totals = o;       o = align_up(o + 64, 256);
   bytes = o;
 }
@@ -383,9 +384,9 @@ static void launch_grow_plan(int P, const float* accum, const float* denom, cons
   uint32_t* counts = reinterpret_cast<uint32_t*>(base + L.block_counts);
   uint32_t* offs = reinterpret_cast<uint32_t*>(base + L.block_offs);
   uint32_t* totals = reinterpret_cast<uint32_t*>(base + L.totals);
-  const int nb = L.nblocks, stride = nb + 1;
+  const int nb = L.nblocks, stride = scan_array_stride(nb);
   hipLaunchKernelGGL(grow_plan_kernel, dim3(nb), dim3(GR_BLOCK), 0, s, P, accum, denom, scaling, thr, pde, split_mode,
-                     flags, counts, nb);
+                     flags, counts, stride);
   launch_scan_block_sums(counts, offs, totals, counts + stride, offs + stride, totals + 1, nb, s);
   hipLaunchKernelGGL(grow_positions_kernel, dim3(nb), dim3(GR_BLOCK), 0, s, P, flags, offs, vidx, src, selected);
 }

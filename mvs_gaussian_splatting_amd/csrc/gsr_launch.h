@@ -18,7 +18,10 @@ void launch_preprocess_fwd(const GsrParams& p, GeomRec* rec, BinInfo* bin, uint3
 void launch_sum_big_rows(const uint32_t* big_count, const uint32_t* big_offs, int nb, const uint32_t* big_list,
                          const GeomRec* rec, const uint32_t* slot_base, GradRow* rows, uint8_t* row_flags, hipStream_t s);
 // exclusive scans of up to three per-block arrays in one launch (block 0: a, block 1: b, block 3: c; block 2 folds
-// block_range, and c comes only with it); total_x = grand total
+// block_range, and c comes only with it); total_x = grand total.  Every sums_x and offs_x must be 16-byte aligned (the
+// kernel moves whole 32-entry lines as uint4) and offs_x holds nb + 1 entries; arrays carved out of one buffer sit
+// scan_array_stride(nb) words apart, which keeps each of them 256-byte aligned when the first one is
+inline int scan_array_stride(int nb) { return (int)align_up((size_t)nb + 1, 64); }
 void launch_scan_block_sums(const uint32_t* sums_a, uint32_t* offs_a, uint32_t* total_a, const uint32_t* sums_b,
                             uint32_t* offs_b, uint32_t* total_b, int nb, hipStream_t s,
                             uint32_t* host_mirror = nullptr, const uint2* block_range = nullptr,

@@ -99,7 +99,9 @@ def _check(m, ref, info, n_sel, with_optimizer):
 
 
 @pytest.mark.parametrize("P,with_optimizer,max_screen_size", [
-    (20000, True, 20), (20000, True, None), (5000, False, 20), (257, True, 20), (1, False, None)])
+    (20000, True, 20), (20000, True, None), (5000, False, 20), (257, True, 20), (1, False, None),
+    # 33 and 34 blocks: past one 32-entry line of the block-counter scan, nb + 1 not a multiple of 4
+    (256 * 32 + 1, True, 20), (256 * 33 + 1, False, None)])
 def test_densify_and_prune_matches_reference_restatement(dev, P, with_optimizer, max_screen_size):
     m, ref, info, n_sel = _run_both(dev, P, 7 + P, with_optimizer, max_screen_size)
     _check(m, ref, info, n_sel, with_optimizer)

@@ -149,13 +149,24 @@ RANDOM = {
 
 @pytest.mark.parametrize("name", list(RANDOM))
 def test_hip_matches_the_restatement_at_4k(gpu_device, name):
-    c = _random_case(4096, 7 + len(name), RANDOM[name], iteration=1000 if name.startswith("clone") else 3100)
+    _matches_the_restatement(gpu_device, name, 4096)
+
+
+@pytest.mark.parametrize("P", [256 * 32 + 1, 256 * 33 + 1])
+@pytest.mark.parametrize("name", list(RANDOM))
+def test_hip_matches_the_restatement_past_one_scan_line(gpu_device, name, P):
+    """33 and 34 blocks of 256 rows: the block-counter scan moves a whole 32-entry line, and nb + 1 is no multiple of 4."""
+    _matches_the_restatement(gpu_device, name, P)
+
+
+def _matches_the_restatement(gpu_device, name, P):
+    c = _random_case(P, 7 + len(name), RANDOM[name], iteration=1000 if name.startswith("clone") else 3100)
     p, mo, info = restate(c["params"], c["moments"], c["accum"], c["denom"], c["flags"], 0.01, c["max_grad"],
                           c["min_opacity"], c["extent"], c["max_screen_size"], c["iteration"], c["reset"],
                           dirs=c["dirs"], noise=c["noise"], dir_noise=c["dir_noise"])
     m, hinfo = _hip(c, gpu_device)
     assert hinfo["selected"] == info["selected"] and hinfo["branch"] == info["branch"]
-    assert hinfo["points"] == p["xyz"].shape[0] > 4096
+    assert hinfo["points"] == p["xyz"].shape[0] > P
     _compare(m, c["names"], {k: (p[k], mo[k][0], mo[k][1]) for k in c["names"]}, name)
 
 

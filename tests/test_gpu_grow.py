@@ -204,14 +204,21 @@ def test_grown_frame_end_to_end(gpu_device, variant):
     _grown_frame_end_to_end(gpu_device, variant)
 
 
-def _grown_frame_end_to_end(gpu_device, variant, active_sh_degree=None):
+@pytest.mark.parametrize("P", [256 * 32 + 1, 256 * 33 + 1])
+def test_grown_frame_end_to_end_past_one_scan_line(gpu_device, P):
+    """33 and 34 blocks of 256 Gaussians: the plan's block-counter scan moves a whole 32-entry line, and the two counter
+    arrays lie nb + 1 = 34 and 35 words apart before the padding."""
+    _grown_frame_end_to_end(gpu_device, "grow_dir_distance", P=P)
+
+
+def _grown_frame_end_to_end(gpu_device, variant, active_sh_degree=None, P=3000):
     """active_sh_degree: None renders at the stored degree; a value below it is set on the model first (the reference
     restatement then runs at that degree too: both read it from the model).  Returns (folded gradients, P)."""
     from mvs_gaussian_splatting_amd import render
     from mvs_gaussian_splatting_amd.rasterizer import GaussianRasterizer
     from mvs_gaussian_splatting_amd.renderer import _settings
     from mvs_gaussian_splatting_amd.synthetic import PipelineParams
-    model, cam, bg, target = _scene(gpu_device)
+    model, cam, bg, target = _scene(gpu_device, P=P)
     if active_sh_degree is not None:
         model.active_sh_degree = active_sh_degree
     P = model._xyz.shape[0]
