@@ -195,7 +195,8 @@ def strategy_options(args):
                 lambda_multi_view_geo=args.lambda_multi_view_geo, multi_view_from_iter=args.multi_view_from_iter,
                 multi_view_pix_max=args.multi_view_pix_max, lambda_multi_view_ncc=args.lambda_multi_view_ncc,
                 multi_view_ncc_samples=args.multi_view_ncc_samples, multi_view_patch_radius=args.multi_view_patch_radius,
-                unbiased_depth=args.unbiased_depth)
+                unbiased_depth=args.unbiased_depth, abs_grad=args.abs_grad,
+                densify_abs_grad_threshold=args.densify_abs_grad_threshold)
 
 
 def train_scene(args, dev):
@@ -329,6 +330,10 @@ def main(argv=None):
     ap.add_argument("--unbiased_depth", action="store_true",
                     help="with --lambda_normal or a multi-view term: they see PGSR's unbiased plane depth "
                          "(render(return_plane_depth=True)) instead of the expected depth")
+    ap.add_argument("--abs_grad", action="store_true",
+                    help="absolute-gradient densification (AbsGS / PGSR): a large Gaussian is also split when its "
+                         "accumulated absolute view-space gradient reaches --densify_abs_grad_threshold")
+    ap.add_argument("--densify_abs_grad_threshold", type=float, default=0.0008, metavar="T")
     ap.add_argument("--out", default=os.path.dirname(os.path.abspath(__file__)))
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")

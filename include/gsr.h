@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 39
+#define GSR_ABI_VERSION 40
 
 enum {
   GSR_OK = 0,
@@ -268,6 +268,22 @@ int gsr_feature_maps_backward(const GsrParams* p, const GsrAuxFrame* frame, cons
                               const float* dL_dmaps, float* dL_dfeatures, void* acc_ws, size_t acc_ws_bytes,
                               const GsrAuxGrads* grads, void* stream);
 
+/* ---- absolute view-space gradient of a rendered frame (AbsGS), ABI v40 (csrc/abs_grad.hip) ----------
+ * For Gaussian k let p run over the pixels where the colour pass composited k (the rule above), d = mean2D_k - p (pixels),
+ * (cxx, cxy, cyy) its conic and h_kp = opacity_k G_kp dL/dalpha_kp of the COLOUR image for the incoming dL_dcolor,
+ * background term included (the 0.99 clamp passes the gradient on, as in gsr_backward):
+ *     abs_means2D[k][0] = 0.5 W sum_p | h_kp (cxx dx + cxy dy) |
+ *     abs_means2D[k][1] = 0.5 H sum_p | h_kp (cxy dx + cyy dy) |,      abs_means2D[k][2] = 0
+ * GsrGrads.dL_dmeans2D is the same sum taken with the terms' signs (times -1), so abs >= |dL_dmeans2D| per component up
+ * to rounding.  A kernel of its own on the maps' walk; gsr_backward is untouched and a frame that does not call this entry
+ * point runs exactly the launches it ran before.  The frame is only read, as for gsr_aux_maps_backward.
+ * p: the inputs of the frame's forward; only P, width, height, forward_only, debug and bg are read.  dL_dcolor: device
+ * [3,H,W].  abs_means2D: device [P,3], written in full (zero-filled, then added into with at most two float atomics per
+ * tile and list entry): rows of Gaussians with radii == 0 and of Gaussians nothing composited are exactly 0.
+ * Reproducible to rounding, not bit for bit. */
+int gsr_abs_grad_backward(const GsrParams* p, const GsrAuxFrame* frame, const float* dL_dcolor, float* abs_means2D,
+                          void* stream);
+
 /* ---- depth-distortion map of a rendered frame, ABI v29 (csrc/distortion.hip) -------------------------
  * With i, w_i, z_i as above (the entries and weights of the depth / alpha maps), the regulariser of 2DGS:
  *     dist = sum_i sum_{j<i} w_i w_j (m_i - m_j)^2,   m_i = m(z_i)        (no background term)
@@ -484,6 +500,10 @@ int gsr_dist2_knn3(const float* points, int32_t N, float* mean_dist2, void* work
  * xyz_gradient_accum += ||dL_dmeans2D.xy||, denom += 1, max_radii2D = max(max_radii2D, radii) */
 int gsr_densify_stats(int32_t P, const float* dL_dmeans2D /*[P,3]*/, const int32_t* radii,
                       float* xyz_gradient_accum, float* denom, float* max_radii2D, void* stream);
+/* ABI v40, the accumulator of AbsGS / PGSR next to it: for radii>0: xyz_gradient_accum_abs += ||abs_means2D.xy||, with
+ * abs_means2D what gsr_abs_grad_backward wrote.  The count (denom) is the one gsr_densify_stats keeps. */
+int gsr_densify_stats_abs(int32_t P, const float* abs_means2D /*[P,3]*/, const int32_t* radii,
+                          float* xyz_gradient_accum_abs, void* stream);
 
 /* scene/gaussian_model.py:750-772 `densify_and_prune` (plain branch: clone :580-610, split :506-578 with N = 2,
  * postfix :466-504, prune :401-449) as one plan and one read-once / write-once pass per tensor.
@@ -504,6 +524,20 @@ int gsr_densify_plan(int32_t P, const float* xyz_gradient_accum, const float* de
                      const float* opacity_raw, float grad_threshold, float percent_dense_extent, float min_opacity,
                      float max_world_scale, void* workspace, size_t workspace_bytes, uint32_t counts_host[4],
                      void* stream);
+/* ABI v40: gsr_densify_plan with the absolute-gradient accumulator of AbsGS / PGSR (xyz_gradient_accum_abs [P], what
+ * gsr_densify_stats-style accumulation of ||abs_means2D.xy|| left; same denom) and its threshold
+ * (densify_abs_grad_threshold).  With grad = accum / denom and grad_abs = accum_abs / denom (NaN -> 0 each) and
+ * big = max(exp(scaling)) > percent_dense_extent:
+ *     clone  unchanged: grad >= grad_threshold and !big
+ *     split           : (grad >= grad_threshold || grad_abs >= abs_grad_threshold) and big
+ *     prune  unchanged
+ * This rule and nothing more: no parity with any one upstream trainer is claimed beyond it.  xyz_gradient_accum_abs ==
+ * NULL: the rule of gsr_densify_plan (which is this call with NULL), abs_grad_threshold is not read.  Workspace, counts
+ * and the gather / children calls are those of gsr_densify_plan. */
+int gsr_densify_plan_abs(int32_t P, const float* xyz_gradient_accum, const float* xyz_gradient_accum_abs,
+                         const float* denom, const float* scaling_raw, const float* opacity_raw, float grad_threshold,
+                         float abs_grad_threshold, float percent_dense_extent, float min_opacity, float max_world_scale,
+                         void* workspace, size_t workspace_bytes, uint32_t counts_host[4], void* stream);
 int gsr_densify_gather_rows(int32_t P, int32_t row_floats, const float* src, const void* workspace,
                             const uint32_t counts[4], int32_t zero_new, float* dst, void* stream);
 int gsr_densify_split_children(int32_t P, const float* xyz, const float* scaling_raw, const float* rotation_raw,

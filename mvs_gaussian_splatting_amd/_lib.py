@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # instead of copying it over the in-tree library
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")
 
-ABI_VERSION = 39
+ABI_VERSION = 40
 
 
 class GsrParams(C.Structure):
@@ -177,6 +177,7 @@ SYMBOLS = {
     "gsr_feature_maps_backward": (C.c_int, [C.POINTER(GsrParams), C.POINTER(GsrAuxFrame), C.c_void_p, C.c_int32, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(GsrAuxGrads), C.c_void_p]),
     # depth-distortion map [1,H,W] of a rendered frame, its per-pixel state [2,H,W] and its gradients (csrc/distortion.hip)
+    "gsr_abs_grad_backward": (C.c_int, [C.POINTER(GsrParams), C.POINTER(GsrAuxFrame), C.c_void_p, C.c_void_p, C.c_void_p]),
     "gsr_distortion_forward": (C.c_int, [C.POINTER(GsrAuxFrame), C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),
     "gsr_distortion_backward_bytes": (C.c_size_t, [C.c_int32]),
@@ -229,6 +230,9 @@ SYMBOLS = {
     "gsr_densify_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "gsr_densify_plan": (C.c_int, [C.c_int32] + [C.c_void_p] * 4 + [C.c_float] * 4 + [C.c_void_p, C.c_size_t,
                                    C.POINTER(C.c_uint32), C.c_void_p]),
+    "gsr_densify_stats_abs": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsr_densify_plan_abs": (C.c_int, [C.c_int32] + [C.c_void_p] * 5 + [C.c_float] * 5 + [C.c_void_p, C.c_size_t,
+                                       C.POINTER(C.c_uint32), C.c_void_p]),
     "gsr_densify_gather_rows": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_int32,
                                           C.c_void_p, C.c_void_p]),
     "gsr_densify_split_children": (C.c_int, [C.c_int32] + [C.c_void_p] * 5 + [C.POINTER(C.c_uint32), C.c_void_p,

@@ -67,6 +67,15 @@ __global__ __launch_bounds__(256) void densify_stats_kernel(int P, const float* 
   }
 }
 
+// the absolute-gradient accumulator of AbsGS next to the one above: the same norm of abs_means2D.xy, the same rows
+__global__ __launch_bounds__(256) void densify_stats_abs_kernel(int P, const float* __restrict__ abs_means2D,
+                                                                const int32_t* __restrict__ radii,
+                                                                float* __restrict__ accum_abs) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= P) return;
+  if (radii[i] > 0) accum_abs[i] += densify_grad_norm(abs_means2D[3 * (size_t)i], abs_means2D[3 * (size_t)i + 1]);
+}
+
 // markVisible of the upstream module (unused by the reference, kept for API completeness): the near-plane test of
 // the preprocess stage, view z > 0.2.
 __global__ __launch_bounds__(256) void mark_visible_kernel(int P, const float* __restrict__ means3D,
@@ -161,6 +170,17 @@ int gsr_densify_stats(int32_t P, const float* dL_dmeans2D, const int32_t* radii,
   hipLaunchKernelGGL(densify_stats_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, dL_dmeans2D, radii,
                      xyz_gradient_accum, denom, max_radii2D);
   return check(false, s, "densify_stats");
+}
+
+int gsr_densify_stats_abs(int32_t P, const float* abs_means2D, const int32_t* radii, float* xyz_gradient_accum_abs,
+                          void* stream) {
+  if (P < 0) return fail(GSR_E_BADARG, "P < 0");
+  if (P == 0) return 0;
+  if (!abs_means2D || !radii || !xyz_gradient_accum_abs) return fail(GSR_E_BADARG, "NULL input");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(densify_stats_abs_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, abs_means2D, radii,
+                     xyz_gradient_accum_abs);
+  return check(false, s, "densify_stats_abs");
 }
 
 int gsr_mark_visible(int32_t P, const float* means3D, const float* viewmatrix, uint8_t* visible, void* stream) {

@@ -9,6 +9,8 @@
 //
 //   plan      : per Gaussian  grad = accum / denom (NaN -> 0);  sel = grad >= thr;  big = max(exp(scaling)) > pd*extent
 //               clone = sel & !big; split = sel & big;  prune = sigmoid(opacity) < min_opacity | max scale > 0.1*extent
+//               with the absolute-gradient accumulator of AbsGS / PGSR (gsr_densify_plan_abs): split = (sel | sel_abs) & big,
+//               sel_abs = accum_abs / denom (NaN -> 0) >= abs_thr; clone and prune as without it
 //               (the screen-size test of :762 always reads the zeros that densification_postfix has just stored, :503)
 //   positions : exclusive scans (block totals -> block offsets -> in-block) of the four flag classes
 //   gather    : dst row <- src row for kept / clone / child rows (moments: zeros for the new rows, :458-459)
@@ -23,6 +25,7 @@ constexpr int DN_BLOCK = PRE_BLOCK;
 enum : uint8_t { DN_KEEP = 1, DN_CLONE = 2, DN_CHILD = 4, DN_SPLIT_SEL = 8 };
 
 __global__ __launch_bounds__(DN_BLOCK) void densify_plan_kernel(int P, const float* __restrict__ accum,
+                                                                 const float* __restrict__ accum_abs, float abs_thr,
                                                                  const float* __restrict__ denom,
                                                                  const float* __restrict__ scaling,
                                                                  const float* __restrict__ opacity, float thr, float pde,
@@ -40,7 +43,13 @@ __global__ __launch_bounds__(DN_BLOCK) void densify_plan_kernel(int P, const flo
     const float s0 = expf(scaling[3 * i]), s1 = expf(scaling[3 * i + 1]), s2 = expf(scaling[3 * i + 2]);
     const float mx = fmaxf(fmaxf(s0, s1), s2);
     const bool sel = g >= thr;
-    const bool clone = sel && mx <= pde, split = sel && mx > pde;
+    bool sel_split = sel;
+    if (accum_abs) {      // uniform over the grid
+      float ga = accum_abs[i] / denom[i];
+      if (ga != ga) ga = 0.0f;
+      sel_split = sel || ga >= abs_thr;
+    }
+    const bool clone = sel && mx <= pde, split = sel_split && mx > pde;
     const float op = 1.0f / (1.0f + expf(-opacity[i]));
     const bool low = op < min_opacity;
     const bool prune_o = low || (use_ws && mx > ws_limit);
@@ -159,8 +168,8 @@ DensifyLayout::DensifyLayout(int P) {
   bytes = o;
 }
 
-static void launch_densify_plan(int P, const float* accum, const float* denom, const float* scaling, const float* opacity,
-                                float thr, float pde, float min_opacity, float ws_limit, int use_ws, void* ws,
+static void launch_densify_plan(int P, const float* accum, const float* accum_abs, float abs_thr, const float* denom,
+                                const float* scaling, const float* opacity, float thr, float pde, float min_opacity, float ws_limit, int use_ws, void* ws,
                                 hipStream_t s) {
   const DensifyLayout L(P);
   char* base = static_cast<char*>(ws);
@@ -170,7 +179,8 @@ static void launch_densify_plan(int P, const float* accum, const float* denom, c
   uint32_t* totals = reinterpret_cast<uint32_t*>(base + L.totals);
   int32_t* pos = reinterpret_cast<int32_t*>(base + L.pos);
   const int nb = L.nblocks, stride = scan_array_stride(nb);
-  hipLaunchKernelGGL(densify_plan_kernel, dim3(nb), dim3(DN_BLOCK), 0, s, P, accum, denom, scaling, opacity, thr, pde,
+  hipLaunchKernelGGL(densify_plan_kernel, dim3(nb), dim3(DN_BLOCK), 0, s, P, accum, accum_abs, abs_thr, denom, scaling,
+                     opacity, thr, pde,
                      min_opacity, ws_limit, use_ws, flags, counts, stride);
   launch_scan_block_sums(counts, offs, totals, counts + stride, offs + stride, totals + 1, nb, s);
   launch_scan_block_sums(counts + 2 * stride, offs + 2 * stride, totals + 2, counts + 3 * stride, offs + 3 * stride,
@@ -206,10 +216,10 @@ using namespace gsr;
 extern "C" {
 
 size_t gsr_densify_workspace_bytes(int32_t P) { return P < 0 ? 0 : DensifyLayout(P).bytes; }
-int gsr_densify_plan(int32_t P, const float* xyz_gradient_accum, const float* denom, const float* scaling_raw,
-                     const float* opacity_raw, float grad_threshold, float percent_dense_extent, float min_opacity,
-                     float max_world_scale, void* workspace, size_t workspace_bytes, uint32_t counts_host[4],
-                     void* stream) {
+int gsr_densify_plan_abs(int32_t P, const float* xyz_gradient_accum, const float* xyz_gradient_accum_abs,
+                         const float* denom, const float* scaling_raw, const float* opacity_raw, float grad_threshold,
+                         float abs_grad_threshold, float percent_dense_extent, float min_opacity, float max_world_scale,
+                         void* workspace, size_t workspace_bytes, uint32_t counts_host[4], void* stream) {
   if (P < 0) return fail(GSR_E_BADARG, "P < 0");
   if (!counts_host) return fail(GSR_E_BADARG, "NULL counts_host");
   counts_host[0] = counts_host[1] = counts_host[2] = counts_host[3] = 0;
@@ -219,12 +229,20 @@ int gsr_densify_plan(int32_t P, const float* xyz_gradient_accum, const float* de
   const DensifyLayout L(P);
   if (workspace_bytes < L.bytes) return fail(GSR_E_CAPACITY, "densify workspace too small");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  launch_densify_plan(P, xyz_gradient_accum, denom, scaling_raw, opacity_raw, grad_threshold, percent_dense_extent,
-                      min_opacity, max_world_scale, max_world_scale >= 0.0f ? 1 : 0, workspace, s);
+  launch_densify_plan(P, xyz_gradient_accum, xyz_gradient_accum_abs, abs_grad_threshold, denom, scaling_raw, opacity_raw,
+                      grad_threshold, percent_dense_extent, min_opacity, max_world_scale, max_world_scale >= 0.0f ? 1 : 0, workspace, s);
   if (int rc = check(false, s, "densify_plan")) return rc;
   GSR_HIP(hipMemcpyAsync(counts_host, static_cast<char*>(workspace) + L.totals, 16, hipMemcpyDeviceToHost, s));
   GSR_HIP(hipStreamSynchronize(s));
   return 0;
+}
+int gsr_densify_plan(int32_t P, const float* xyz_gradient_accum, const float* denom, const float* scaling_raw,
+                     const float* opacity_raw, float grad_threshold, float percent_dense_extent, float min_opacity,
+                     float max_world_scale, void* workspace, size_t workspace_bytes, uint32_t counts_host[4],
+                     void* stream) {
+  return gsr_densify_plan_abs(P, xyz_gradient_accum, nullptr, denom, scaling_raw, opacity_raw, grad_threshold, 0.0f,
+                              percent_dense_extent, min_opacity, max_world_scale, workspace, workspace_bytes, counts_host,
+                              stream);
 }
 int gsr_densify_gather_rows(int32_t P, int32_t row_floats, const float* src, const void* workspace,
                             const uint32_t counts[4], int32_t zero_new, float* dst, void* stream) {

@@ -711,6 +711,20 @@ int gsr_feature_maps_backward(const GsrParams* p, const GsrAuxFrame* f, const fl
       dL_dfeatures ? 4 * (size_t)p->P * (size_t)C : 0);
 }
 
+// ---- absolute view-space gradient of the colour image (csrc/abs_grad.hip) ------------------------------------------
+int gsr_abs_grad_backward(const GsrParams* p, const GsrAuxFrame* f, const float* dL_dcolor, float* abs_means2D,
+                          void* stream) {
+  if (int rc = refuse_backward(p, f)) return rc;
+  if (int rc = refuse_mismatch(p, f)) return rc;
+  if (p->P == 0) return 0;
+  if (!dL_dcolor || !abs_means2D || !p->bg) return fail(GSR_E_BADARG, "dL_dcolor / abs_means2D / bg is NULL");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  GSR_HIP(hipMemsetAsync(abs_means2D, 0, 12 * (size_t)p->P, s));
+  if (frame_is_empty(f)) return 0;
+  launch_abs_grad_bwd(map_frame(f), p->bg, dL_dcolor, abs_means2D, s);
+  return check(p->debug, s, "abs_grad_bwd");
+}
+
 // ---- depth-distortion map (csrc/distortion.hip) --------------------------------------------------------------------
 static int validate_distortion_mapping(int32_t mapping, float near, float far) {
   if (mapping != 0 && mapping != 1) return fail(GSR_E_BADARG, "mapping must be 0 (linear) or 1 (ndc)");

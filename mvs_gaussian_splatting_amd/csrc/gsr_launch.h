@@ -132,6 +132,11 @@ void launch_feature_maps_fwd(const MapFrame& f, const float* features, int C, fl
 void launch_feature_maps_bwd(const MapFrame& f, const float* features, int C, const float* dL_dmaps, float* acc,
                              float* dL_dfeatures, hipStream_t s);
 
+// abs_grad.hip: the absolute view-space gradient of the COLOUR image (AbsGS): per Gaussian the sum over its composited
+// pixels of |d colour-loss / d mean2D| per component, added into abs_means2D [P,3] (zeroed by the caller; columns 0 and 1,
+// GsrGrads.dL_dmeans2D's scale); bg: device [3], the frame's background; dL_dcolor: device [3,H,W]
+void launch_abs_grad_bwd(const MapFrame& f, const float* bg, const float* dL_dcolor, float* abs_means2D, hipStream_t s);
+
 // distortion.hip: the depth-distortion map dist [1,H,W] of a rendered frame (the entries and weights of depth.hip; mapping
 // 0: m = z, 1: m = far / (far - near) (1 - near / z)), the per-pixel state [2,H,W] its backward reads, and the backward:
 // sums into acc [P,8] (zeroed by the caller; the layout launch_aux_geom_bwd reads, d z word included)

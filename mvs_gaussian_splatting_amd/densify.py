@@ -81,7 +81,7 @@ def branch(model, opt=None, iteration=None) -> str:
 @torch.no_grad()
 def densify_and_prune(model, max_grad: float, min_opacity: float, extent: float, max_screen_size,
                       noise: Optional[torch.Tensor] = None, spatial_order: bool = False, *, opt=None, iteration=None,
-                      dir_noise: Optional[torch.Tensor] = None) -> Dict[str, int]:
+                      dir_noise: Optional[torch.Tensor] = None, abs_grad_threshold: Optional[float] = None) -> Dict[str, int]:
     """In-place equivalent of ``gaussians.densify_and_prune(max_grad, min_opacity, extent, max_screen_size)``
     (``train.py:134``).  ``noise`` (``[2 * n_split_selected, 3]`` standard normal; default: ``torch.randn`` on the
     device) stands for the draws of ``torch.normal(mean=0, std=stds)`` at ``:537-539``.  ``spatial_order`` (this build's
@@ -94,7 +94,20 @@ def densify_and_prune(model, max_grad: float, min_opacity: float, extent: float,
     split's standard-normal draws in the reference's order over its split rows (``[2n,3]``, ``[n,3]`` with
     ``symmetric_split``, ``[0,3]`` with ``learn_split_distance``) and ``dir_noise`` (``[selected,3]``) the
     ``torch.randn`` of the continuous re-init (``:650``); both default to fresh draws.  The returned dict then also
-    holds ``branch``, ``grown`` and ``selected``."""
+    holds ``branch``, ``grown`` and ``selected``.
+
+    ``abs_grad_threshold`` (AbsGS / PGSR's ``densify_abs_grad_threshold``; None: the call above, bit for bit): the plan also
+    reads ``model.xyz_gradient_accum_abs`` (``losses.add_densification_stats(..., viewspace_abs=)``) and SPLITS a large
+    Gaussian when ``grad >= max_grad`` or ``grad_abs >= abs_grad_threshold``; clone and prune are unchanged
+    (``gsr_densify_plan_abs``, ``include/gsr.h``).  Not available for a fork model (``ValueError``)."""
+    if abs_grad_threshold is not None:
+        if is_fork(model):
+            raise ValueError("abs_grad_threshold is not available for a grow / learned-split (fork) model: its plan has no "
+                             "absolute-gradient rule")
+        accum_abs = getattr(model, "xyz_gradient_accum_abs", None)
+        if not isinstance(accum_abs, torch.Tensor) or accum_abs.numel() != int(model._xyz.shape[0]):
+            raise ValueError("abs_grad_threshold needs model.xyz_gradient_accum_abs with one value per Gaussian "
+                             "(add_densification_stats(..., viewspace_abs=) fills it)")
     if is_fork(model):
         return _densify_fork(model, max_grad, min_opacity, extent, max_screen_size, noise, spatial_order, opt,
                              iteration, dir_noise)
@@ -117,10 +130,16 @@ def densify_and_prune(model, max_grad: float, min_opacity: float, extent: float,
         stream = torch.cuda.current_stream(dev).cuda_stream
         scaling = params["scaling"].detach().contiguous()
         opacity = params["opacity"].detach().contiguous()
-        _lib.check(lib.gsr_densify_plan(P, accum.data_ptr(), denom.data_ptr(), scaling.data_ptr(), opacity.data_ptr(),
-                                        float(max_grad), float(model.percent_dense * extent), float(min_opacity),
-                                        float(0.1 * extent) if max_screen_size else -1.0, ws.data_ptr(), ws.numel(),
-                                        counts, stream), "gsr_densify_plan")
+        tail = (float(model.percent_dense * extent), float(min_opacity), float(0.1 * extent) if max_screen_size else -1.0,
+                ws.data_ptr(), ws.numel(), counts, stream)
+        if abs_grad_threshold is None:
+            _lib.check(lib.gsr_densify_plan(P, accum.data_ptr(), denom.data_ptr(), scaling.data_ptr(), opacity.data_ptr(),
+                                            float(max_grad), *tail), "gsr_densify_plan")
+        else:
+            accum_abs = model.xyz_gradient_accum_abs.detach().to(dev, torch.float32).contiguous()
+            _lib.check(lib.gsr_densify_plan_abs(P, accum.data_ptr(), accum_abs.data_ptr(), denom.data_ptr(),
+                                                scaling.data_ptr(), opacity.data_ptr(), float(max_grad),
+                                                float(abs_grad_threshold), *tail), "gsr_densify_plan_abs")
         n_keep, n_clone, n_child, n_sel = (int(v) for v in counts)
         n_out = n_keep + n_clone + 2 * n_child
         if noise is None:
@@ -158,6 +177,8 @@ def densify_and_prune(model, max_grad: float, min_opacity: float, extent: float,
     model.xyz_gradient_accum = torch.zeros((n_out, 1), dtype=torch.float32, device=dev)      # :501-503
     model.denom = torch.zeros((n_out, 1), dtype=torch.float32, device=dev)
     model.max_radii2D = torch.zeros((n_out,), dtype=torch.float32, device=dev)
+    if getattr(model, "xyz_gradient_accum_abs", None) is not None:
+        model.xyz_gradient_accum_abs = torch.zeros((n_out, 1), dtype=torch.float32, device=dev)
     if spatial_order:
         from .layout import reorder_gaussians_
         reorder_gaussians_(model)

@@ -26,7 +26,7 @@ from torch import nn
 
 from .densify import FORK_ATTR, GROUP_ATTR
 
-STATS_ATTR = ("xyz_gradient_accum", "denom", "max_radii2D")
+STATS_ATTR = ("xyz_gradient_accum", "denom", "max_radii2D", "xyz_gradient_accum_abs")
 
 
 def _spread3(v: torch.Tensor) -> torch.Tensor:

@@ -129,12 +129,37 @@ def opacity_sparsity_loss(raw_opacity: torch.Tensor, weight: float, threshold: f
     return (loss, holder[0]) if return_record else loss
 
 
+def _add_abs_stats(lib, model, viewspace_abs: torch.Tensor, radii: torch.Tensor) -> None:
+    grad = viewspace_abs.grad
+    if grad is None:
+        raise ValueError("viewspace_points_abs has no .grad (call backward first)")
+    if not grad.is_cuda:
+        raise _lib.GsrError("add_densification_stats needs ROCm GPU tensors (no CPU path)")
+    grad = grad.contiguous()
+    P = int(grad.shape[0])
+    acc = getattr(model, "xyz_gradient_accum_abs", None)
+    if acc is None:
+        acc = model.xyz_gradient_accum_abs = torch.zeros((P, 1), dtype=torch.float32, device=grad.device)
+    if not (acc.is_contiguous() and acc.dtype == torch.float32 and acc.numel() == P and acc.device == grad.device):
+        raise TypeError("xyz_gradient_accum_abs must be contiguous float32 with one element per Gaussian")
+    with torch.cuda.device(grad.device):
+        stream = torch.cuda.current_stream(grad.device).cuda_stream
+        _lib.check(lib.gsr_densify_stats_abs(P, grad.data_ptr(), radii.contiguous().data_ptr(), acc.data_ptr(), stream),
+                   "gsr_densify_stats_abs")
+
+
 @torch.no_grad()
-def add_densification_stats(model, viewspace_point_tensor: torch.Tensor, radii: torch.Tensor) -> None:
+def add_densification_stats(model, viewspace_point_tensor: torch.Tensor, radii: torch.Tensor,
+                            viewspace_abs: torch.Tensor = None) -> None:
     """``train.py:130-131`` in one kernel: for radii > 0 accumulate ||grad.xy||, count, track max radius.
-    A frame rendered with ``pipe.fuse_densify_stats`` has had them taken by its backward already."""
+    A frame rendered with ``pipe.fuse_densify_stats`` has had them taken by its backward already.
+    ``viewspace_abs`` (``render(..., abs_grad=True)["viewspace_points_abs"]``, after the backward): also add
+    ``||viewspace_abs.grad.xy||`` into ``model.xyz_gradient_accum_abs [P,1]`` for radii > 0 (AbsGS / PGSR; created as
+    zeros when the model has none yet).  ``denom`` is shared: the count is taken once."""
     lib = _lib.load()
     grad = viewspace_point_tensor.grad
+    if viewspace_abs is not None:
+        _add_abs_stats(lib, model, viewspace_abs, radii)
     if getattr(viewspace_point_tensor, "_gsr_stats_fused", False):
         if grad is None:
             raise ValueError("viewspace_points has no .grad (call backward first)")

@@ -280,7 +280,7 @@ def add_new_gs(model, cap_max: int, generator: Optional[torch.Generator] = None,
             t = nn.Parameter(t, requires_grad=old.requires_grad) if isinstance(old, nn.Parameter) \
                 else t.requires_grad_(old.requires_grad)
         setattr(model, a, t)
-    for a in ("xyz_gradient_accum", "denom", "max_radii2D"):
+    for a in ("xyz_gradient_accum", "denom", "max_radii2D", "xyz_gradient_accum_abs"):
         t = getattr(model, a, None)
         if isinstance(t, torch.Tensor) and t.dim() >= 1 and t.shape[0] == P:
             setattr(model, a, torch.cat([t, torch.zeros((n,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)]))

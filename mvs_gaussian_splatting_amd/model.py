@@ -80,6 +80,8 @@ class GaussianModel:
         self.max_radii2D = torch.empty(0)
         self.xyz_gradient_accum = torch.empty(0)
         self.denom = torch.empty(0)
+        self.xyz_gradient_accum_abs = None      # AbsGS / PGSR's accumulator [P,1]: training_setup with opt.abs_grad, or the
+                                                # first add_densification_stats(..., viewspace_abs=), creates it
         self.optimizer = None
         self.percent_dense = 0
         self.spatial_lr_scale = 0
@@ -327,22 +329,28 @@ class GaussianModel:
         if self.has_exposures:                        # last, and told from the fork's dict by its "exposure_mapping" key
             out = out + ({"exposure": self._exposure, "exposure_mapping": dict(self.exposure_mapping),
                           "exposure_optimizer": self.exposure_optimizer.state_dict()},)
+        if self.xyz_gradient_accum_abs is not None:   # behind everything else, and only when it exists: a model without
+            out = out + ({"xyz_gradient_accum_abs": self.xyz_gradient_accum_abs},)      # it writes the tuples above
         return out
 
     def restore(self, model_args, training_args, optimizer_cls=None):
         """``:133-149``; accepts every form ``capture`` returns: the 12-tuple, with the fork's dict, and either with the
-        exposures' dict (``ValueError`` when the checkpoint has exposures and this model none, or the reverse: call
+        exposures' dict, and any of them with the absolute-gradient accumulator's dict last (``ValueError`` when the checkpoint has exposures and this model none, or the reverse: call
         ``setup_exposures`` first, or not at all).  ``training_setup`` runs first, with
         ``optimizer_cls`` (default: the class ``training_setup`` was last given, else the one
         ``training_args.optimizer_type`` names: ``optim.Adam`` unless it says ``"sparse_adam"``), then the saved
         state is loaded into it: state dicts move freely between ``torch.optim.Adam`` and ``optim.Adam``."""
         model_args = tuple(model_args)
+        accum_abs = None
+        if model_args and isinstance(model_args[-1], dict) and set(model_args[-1]) == {"xyz_gradient_accum_abs"}:
+            accum_abs, model_args = model_args[-1]["xyz_gradient_accum_abs"], model_args[:-1]
         exposures = None
         if len(model_args) in (13, 14) and isinstance(model_args[-1], dict) and "exposure_mapping" in model_args[-1]:
             exposures, model_args = model_args[-1], model_args[:-1]
         if len(model_args) not in (12, 13):
             raise ValueError(f"restore expects the 12- or 13-element tuple of capture(), with the exposures' dict behind "
-                             f"it for a model that has them, got {len(model_args) + (exposures is not None)} elements")
+                             f"it for a model that has them, got {len(model_args) + (exposures is not None) + (accum_abs is not None)} "
+                             f"elements")
         if (exposures is not None) != self.has_exposures:
             raise ValueError("the checkpoint holds exposures and this model has none (call setup_exposures before restore)"
                              if exposures is not None else
@@ -364,6 +372,8 @@ class GaussianModel:
         self.training_setup(training_args, optimizer_cls or self._optimizer_cls)
         self.xyz_gradient_accum = xyz_gradient_accum
         self.denom = denom
+        if accum_abs is not None:                     # a checkpoint without it leaves what training_setup made
+            self.xyz_gradient_accum_abs = accum_abs
         self.optimizer.load_state_dict(opt_dict)
         if exposures is not None:
             self.exposure_optimizer.load_state_dict(exposures["exposure_optimizer"])

@@ -268,7 +268,8 @@ EXPOSURE_LR_INIT, EXPOSURE_LR_FINAL = 0.01, 0.001      # upstream's defaults, fo
 
 def training_setup(model, opt, optimizer_cls=None):
     """``GaussianModel.training_setup(training_args)`` (``scene/gaussian_model.py:240-268``) with this module's
-    ``Adam``: sets ``percent_dense``, zeroed ``xyz_gradient_accum`` / ``denom`` ``[P, 1]`` on the model's device,
+    ``Adam``: sets ``percent_dense``, zeroed ``xyz_gradient_accum`` / ``denom`` ``[P, 1]`` on the model's device
+    (and ``xyz_gradient_accum_abs`` with ``opt.abs_grad``, else None),
     ``optimizer`` (``lr=0.0, eps=1e-15``) and ``xyz_scheduler_args``; for a model with exposures
     (``GaussianModel.setup_exposures``) also ``exposure_optimizer`` (``Adam([_exposure], lr=0.0, eps=1e-8)``, always
     dense) and ``exposure_scheduler_args`` over ``opt.iterations`` steps, else ``exposure_optimizer = None``.  optimizer_cls: None takes the class
@@ -279,6 +280,8 @@ def training_setup(model, opt, optimizer_cls=None):
     P, dev = model._xyz.shape[0], model._xyz.device
     model.xyz_gradient_accum = torch.zeros((P, 1), device=dev)
     model.denom = torch.zeros((P, 1), device=dev)
+    # the absolute-gradient accumulator of AbsGS / PGSR: only for a run that asked for it (opt.abs_grad)
+    model.xyz_gradient_accum_abs = torch.zeros((P, 1), device=dev) if getattr(opt, "abs_grad", False) else None
     model.optimizer = optimizer_cls(param_groups(model, opt), lr=0.0, eps=1e-15)
     model.xyz_scheduler_args = expon_lr_func(lr_init=opt.position_lr_init * model.spatial_lr_scale,
                                              lr_final=opt.position_lr_final * model.spatial_lr_scale,

@@ -50,6 +50,13 @@ transmittance still exceeds one half (2DGS's median depth; 0 where nothing was c
 the row of that entry's Gaussian (-1 where nothing was composited) (``csrc/median.hip``), behind a node of
 its own (``_MedianDepth``) that reads the colour node's frame.  Only means3D receives a gradient.  Without ``median_depth``
 nothing of it runs.
+
+Absolute gradient.  ``GaussianRasterizer(settings, abs_grad=True)`` takes a second dummy ``means2D_abs [P,3]`` in its
+call: after ``backward`` its ``.grad`` holds AbsGS's absolute ("homodirectional") view-space gradient of the COLOUR image,
+``sum over the Gaussian's pixels of |d L / d mean2D|`` per component in ``means2D.grad``'s scale, z = 0 (``csrc/abs_grad.hip``;
+DESIGN.md §7.27).  A node of its own (``_AbsGrad``) that passes the colour image and its incoming gradient through
+untouched and reads the colour node's frame: colour, radii and every other gradient are what they are without it.  The
+gradient of the map nodes above takes no part in it.  Without ``abs_grad`` nothing of it runs.
 """
 from __future__ import annotations
 
@@ -848,6 +855,56 @@ def _check_feature_request(features, means3D, cam, state_key=None, densify_stats
         raise ValueError(f"features is on {features.device}, expected {means3D.device}")
 
 
+class _AbsGrad(torch.autograd.Function):
+    """AbsGS's absolute view-space gradient of a frame the colour operator has rendered (``include/gsr.h``:
+    gsr_abs_grad_backward; ``csrc/abs_grad.hip``).  The node sits on the colour image: the forward hands the image on,
+    the backward hands the incoming gradient on (the same tensor: the colour node sees what it sees without this node) and,
+    from that gradient and the colour node's frame (read by reference), fills ``means2D_abs``'s gradient ``[P,3]``."""
+
+    @staticmethod
+    def forward(ctx, color, means2D_abs, means3D, raster_settings: GaussianRasterizationSettings, frame: _Frame,
+                binning_mode: int):
+        _stash_frame(ctx, raster_settings, frame, binning_mode, (means3D,))
+        return color.view_as(color)
+
+    @staticmethod
+    def backward(ctx, grad_color):
+        if grad_color is None or not ctx.needs_input_grad[1]:
+            return (grad_color, None, None, None, None, None)
+        lib = _lib.load()
+        saved = ctx.saved_tensors
+        dev, P, params, keep, aux_frame = _open_backward(ctx, saved, saved[0])
+        g = _f32c(grad_color, "grad_out_color", dev)
+        with torch.cuda.device(dev):
+            g_abs = torch.empty(P, 3, dtype=torch.float32, device=dev)
+            if P > 0:
+                _lib.check(lib.gsr_abs_grad_backward(C.byref(params), C.byref(aux_frame), g.data_ptr(), g_abs.data_ptr(),
+                                                     _stream(dev)), "gsr_abs_grad_backward")
+        del keep
+        return (grad_color, g_abs, None, None, None, None)
+
+
+def _check_abs_request(means2D_abs, means3D, cam, state_key=None, densify_stats=None) -> None:
+    """The refusals of an ``abs_grad=True`` request (those of ``aux_maps=True``), before anything is enqueued (and before
+    a GPU is asked for)."""
+    if densify_stats is not None:
+        raise ValueError("abs_grad=True cannot be combined with densify_stats: the in-backward statistics know nothing "
+                         "of the absolute gradient (take both from means2D.grad and means2D_abs.grad after the backward)")
+    if cam:
+        raise ValueError("abs_grad=True cannot be combined with camera tensors that require grad (detach viewmatrix / "
+                         "projmatrix / campos)")
+    if state_key is not None:
+        raise ValueError("abs_grad=True is not available on a frame with grown / split rows appended")
+    P = int(means3D.shape[0])
+    if not isinstance(means2D_abs, torch.Tensor) or means2D_abs.dtype != torch.float32 or \
+            tuple(means2D_abs.shape) != (P, 3):
+        raise ValueError(f"abs_grad=True needs means2D_abs, a float32 [P={P}, 3] tensor whose .grad receives the absolute "
+                         f"gradient, got {getattr(means2D_abs, 'dtype', type(means2D_abs).__name__)} "
+                         f"{list(getattr(means2D_abs, 'shape', ()))}")
+    if means2D_abs.device != means3D.device:
+        raise ValueError(f"means2D_abs is on {means2D_abs.device}, expected {means3D.device}")
+
+
 def _check_aux_request(cam, state_key=None, densify_stats=None) -> None:
     if densify_stats is not None:
         raise ValueError("aux_maps=True cannot be combined with densify_stats: the in-backward statistics would see the "
@@ -919,13 +976,16 @@ def _with_frame_outputs(color, radii, node, grad: bool, geometry, aux_maps, cont
 
 
 def _rasterize(fn, tensors, raster_settings, tail, geometry, densify_stats, aux_maps, contribution, contribution_mask,
-               state_key=None, features=None, distortion=None, median_depth=False):
+               state_key=None, features=None, distortion=None, median_depth=False, means2D_abs=None, abs_grad=False):
     """One frame through the colour operator ``fn``.  ``tensors``: its forward's arguments in front of ``raster_settings``;
     ``tail``: those between ``stats`` and the camera's; ``geometry``: the arguments of ``_aux_maps_of`` after ``grad``
     when ``aux_maps``, ``contribution``, ``features``, ``distortion`` or ``median_depth`` ask for the frame's state, else
     None.
-    ``distortion``: None, or the (mapping, near, far) of ``_distortion_spec``."""
+    ``distortion``: None, or the (mapping, near, far) of ``_distortion_spec``.
+    ``abs_grad``: ``means2D_abs``'s gradient is wanted (``_AbsGrad``); a frame no backward can follow is issued without."""
     cam = _camera_inputs(raster_settings)
+    if abs_grad:
+        _check_abs_request(means2D_abs, tensors[0], cam, state_key, densify_stats)
     if aux_maps:
         _check_aux_request(cam, state_key, densify_stats)
     if distortion is not None:
@@ -955,15 +1015,19 @@ def _rasterize(fn, tensors, raster_settings, tail, geometry, densify_stats, aux_
         # only ``features`` requires grad: its node is built with grad mode as the caller has it
         return head + (_feature_maps_of(node, True, features, *geometry),) + dist
     out = fn.apply(*tensors, raster_settings, False, densify_stats, *tail, *cam)
+    node = out[0].grad_fn
+    if abs_grad and means2D_abs.requires_grad:
+        out = (_AbsGrad.apply(out[0], means2D_abs, tensors[0], raster_settings, *_frame_of(node)),) + tuple(out[1:])
     if geometry is None:
         return out
-    return _with_frame_outputs(*out, out[0].grad_fn, True, geometry, aux_maps, contribution, contribution_mask, features,
+    return _with_frame_outputs(*out, node, True, geometry, aux_maps, contribution, contribution_mask, features,
                                distortion=distortion, median_depth=median_depth)
 
 
 def rasterize_gaussians_fused(means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations, raster_settings,
                               densify_stats=None, visible=None, _state_key=None, aux_maps=False, contribution=None,
-                              contribution_mask=None, features=None, distortion=None, median_depth=False):
+                              contribution_mask=None, features=None, distortion=None, median_depth=False,
+                              means2D_abs=None, abs_grad=False):
     """``densify_stats``: None, or (xyz_gradient_accum, denom, max_radii2D) -- the backward then also accumulates the
     densification statistics of ``scene/gaussian_model.py:775-777`` / ``train.py:130``.
     ``visible``: None, or a bool [P] tensor that receives ``radii > 0`` from the preprocess kernel.
@@ -972,7 +1036,8 @@ def rasterize_gaussians_fused(means3D, means2D, f_dc, f_rest, raw_opacity, raw_s
     ``contribution`` / ``contribution_mask``: accumulate the frame's contribution statistics (module docstring).
     ``features``: float32 ``[P,C]``; also return ``feat [C,H,W] = sum w features[id]`` (``_FeatureMaps``) after ``aux``.
     ``distortion``: True or ``dict(mapping=, near=, far=)``; also return ``dist [1,H,W]`` (``_DistortionMap``) after ``feat``.
-    ``median_depth``: also return ``median [1,H,W]`` and ``median_id [H,W]`` (``_MedianDepth``) as the last two results."""
+    ``median_depth``: also return ``median [1,H,W]`` and ``median_id [H,W]`` (``_MedianDepth``) as the last two results.
+    ``abs_grad`` / ``means2D_abs``: float32 ``[P,3]`` whose ``.grad`` receives the absolute gradient (``_AbsGrad``)."""
     geometry = None
     distortion = _distortion_spec(distortion)
     median_depth = bool(median_depth)
@@ -983,12 +1048,12 @@ def rasterize_gaussians_fused(means3D, means2D, f_dc, f_rest, raw_opacity, raw_s
     return _rasterize(_RasterizeGaussiansFused,
                       (means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations), raster_settings,
                       (visible, _state_key), geometry, densify_stats, aux_maps, contribution, contribution_mask, _state_key,
-                      features, distortion, median_depth)
+                      features, distortion, median_depth, means2D_abs, abs_grad)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings, densify_stats=None, aux_maps=False, contribution=None, contribution_mask=None,
-                        features=None, distortion=None, median_depth=False):
+                        features=None, distortion=None, median_depth=False, means2D_abs=None, abs_grad=False):
     distortion = _distortion_spec(distortion)
     median_depth = bool(median_depth)
     geometry = (means3D, means2D, opacities, scales, rotations, cov3Ds_precomp, raster_settings) \
@@ -996,7 +1061,8 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     return _rasterize(_RasterizeGaussians,
                       (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp),
                       raster_settings, (), geometry, densify_stats, aux_maps, contribution, contribution_mask,
-                      features=features, distortion=distortion, median_depth=median_depth)
+                      features=features, distortion=distortion, median_depth=median_depth, means2D_abs=means2D_abs,
+                      abs_grad=abs_grad)
 
 
 class GaussianRasterizer(nn.Module):
@@ -1004,7 +1070,8 @@ class GaussianRasterizer(nn.Module):
     (``gaussian_renderer/__init__.py:57``) and calls at ``:257-265``."""
 
     def __init__(self, raster_settings: GaussianRasterizationSettings, aux_maps: bool = False, contribution=None,
-                 contribution_mask: Optional[torch.Tensor] = None, distortion=None, median_depth: bool = False):
+                 contribution_mask: Optional[torch.Tensor] = None, distortion=None, median_depth: bool = False,
+                 abs_grad: bool = False):
         """``aux_maps=True``: the call returns ``(color, radii, aux)`` with ``aux [3,H,W]`` = the depth
         (``sum w z``), inverse-depth (``sum w / z``) and accumulated-opacity (``sum w``) maps of the frame,
         differentiable in means3D, means2D, opacities and scales / rotations or cov3D_precomp.
@@ -1013,7 +1080,9 @@ class GaussianRasterizer(nn.Module):
         ``distortion``: True, or ``dict(mapping="linear" | "ndc", near=0.2, far=100.0)``: the call's results gain a
         trailing ``dist [1,H,W]``, the depth-distortion map (module docstring), differentiable in the geometry inputs.
         ``median_depth=True``: the call's results gain, after everything else, ``median [1,H,W]`` (2DGS's median depth,
-        differentiable in means3D alone) and ``median_id [H,W]`` (int32: the Gaussian that owns the pixel, -1 for none)."""
+        differentiable in means3D alone) and ``median_id [H,W]`` (int32: the Gaussian that owns the pixel, -1 for none).
+        ``abs_grad=True``: the call takes ``means2D_abs [P,3]``, whose ``.grad`` holds AbsGS's absolute view-space gradient
+        of the colour image after ``backward`` (module docstring); the call's results are what they are without it."""
         super().__init__()
         _distortion_spec(distortion)        # a malformed request is refused here, not at the first frame
         self.raster_settings = raster_settings
@@ -1022,6 +1091,7 @@ class GaussianRasterizer(nn.Module):
         self.contribution_mask = contribution_mask
         self.distortion = distortion
         self.median_depth = bool(median_depth)
+        self.abs_grad = bool(abs_grad)
 
     def markVisible(self, positions: torch.Tensor) -> torch.Tensor:
         """Frustum (near-plane) visibility of the upstream module's ``markVisible``; bool ``[P]``."""
@@ -1036,10 +1106,12 @@ class GaussianRasterizer(nn.Module):
         return vis.bool()
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, densify_stats=None, features=None):
+                cov3D_precomp=None, densify_stats=None, features=None, means2D_abs=None):
         """``features``: float32 ``[P,C]``, C >= 1: the call's results gain a trailing ``feat [C,H,W] = sum w features[id]``
-        (after ``aux`` when ``aux_maps=True``), differentiable in ``features`` and the geometry inputs."""
+        (after ``aux`` when ``aux_maps=True``), differentiable in ``features`` and the geometry inputs.
+        ``means2D_abs``: with ``abs_grad=True``, the ``[P,3]`` tensor whose ``.grad`` receives the absolute gradient."""
         raster_settings = self.raster_settings
+        self._check_means2D_abs(means2D_abs)
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")
         if ((scales is None or rotations is None) and cov3D_precomp is None) or \
@@ -1055,14 +1127,21 @@ class GaussianRasterizer(nn.Module):
                                    cov3D_precomp, raster_settings, densify_stats, aux_maps=self.aux_maps,
                                    contribution=self.contribution, contribution_mask=self.contribution_mask,
                                    features=features, **({} if self.distortion is None else {"distortion": self.distortion}),
-                                   **({"median_depth": True} if self.median_depth else {}))
+                                   **({"median_depth": True} if self.median_depth else {}),
+                                   **({"means2D_abs": means2D_abs, "abs_grad": True} if self.abs_grad else {}))
+
+    def _check_means2D_abs(self, means2D_abs) -> None:
+        if means2D_abs is not None and not self.abs_grad:
+            raise ValueError("means2D_abs needs GaussianRasterizer(..., abs_grad=True)")
 
     def forward_fused(self, means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations, densify_stats=None,
-                      features=None):
+                      features=None, means2D_abs=None):
         """Raw-parameter entry: see :class:`_RasterizeGaussiansFused`."""
+        self._check_means2D_abs(means2D_abs)
         return rasterize_gaussians_fused(means3D, means2D, f_dc, f_rest, raw_opacity, raw_scales, raw_rotations,
                                          self.raster_settings, densify_stats, aux_maps=self.aux_maps,
                                          contribution=self.contribution, contribution_mask=self.contribution_mask,
                                          features=features,
                                          **({} if self.distortion is None else {"distortion": self.distortion}),
-                                         **({"median_depth": True} if self.median_depth else {}))
+                                         **({"median_depth": True} if self.median_depth else {}),
+                                         **({"means2D_abs": means2D_abs, "abs_grad": True} if self.abs_grad else {}))

@@ -95,7 +95,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier:
            override_color=None, grow_dir=False, densify_grad_threshold=0, iteration=None, opt=None,
            continous_dir=False, grow_distance=False, modelcg=None, cameras_extent=None, return_depth=False,
            use_trained_exp=False, contribution=None, contribution_mask=None, features=None, return_normals=False,
-           return_distortion=False, distortion_kwargs=None, return_median_depth=False, return_plane_depth=False):
+           return_distortion=False, distortion_kwargs=None, return_median_depth=False, return_plane_depth=False,
+           abs_grad=False):
     """Render the scene; ``bg_color`` must be on the GPU.  Returns the reference's result dict
     (``gaussian_renderer/__init__.py:309-313``).  The keyword arguments after ``override_color`` are the reference's
     (``:19``) and drive the grow / learned-split branch (module docstring); the frame of a closed branch is unchanged.
@@ -147,7 +148,14 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier:
     depth at which the pixel's ray meets the blended plane, 0 where there is no surface.  Differentiable in the
     rotations, the positions and the blending weights.  On such a frame ``"normal"`` comes from the planes kernel and may
     differ from the torch path of ``return_normals`` alone in the last bits.  Combines with ``features=``,
-    ``return_median_depth`` and ``return_distortion``; the same two conditions as for ``return_depth`` apply."""
+    ``return_median_depth`` and ``return_distortion``; the same two conditions as for ``return_depth`` apply.
+
+    ``abs_grad=True`` (AbsGS; PGSR's ``viewspace_point_tensor_abs``): the dict gains
+    ``"viewspace_points_abs"``, a second zero leaf ``[P,3]`` whose ``.grad`` after the backward holds, per Gaussian and
+    component, the sum over its pixels of ``|d L / d mean2D|`` of the COLOUR image (the maps' losses take no part), in
+    ``viewspace_points.grad``'s scale, z = 0.  ``"render"``, ``"radii"`` and every other gradient are bit-identical to the
+    frame without it.  The same two conditions as for ``return_depth`` apply; hand both leaves to
+    ``add_densification_stats(model, viewspace_points, radii, viewspace_abs=viewspace_points_abs)``."""
     if distortion_kwargs is not None and not return_distortion:
         raise ValueError("distortion_kwargs needs return_distortion=True")
     pkg = _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, grow_dir,
@@ -155,7 +163,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier:
                   return_depth, contribution, contribution_mask, features, return_normals,
                   (True if distortion_kwargs is None else dict(distortion_kwargs)) if return_distortion else None,
                   **({"median_depth": True} if return_median_depth else {}),
-                  **({"plane_depth": True} if return_plane_depth else {}))
+                  **({"plane_depth": True} if return_plane_depth else {}),
+                  **({"abs_grad": True} if abs_grad else {}))
     if use_trained_exp:
         pkg["render"] = apply_exposure(pkg["render"], pc.get_exposure_from_name(viewpoint_camera.image_name))
     return pkg
@@ -164,8 +173,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier:
 def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, grow_dir, densify_grad_threshold,
             iteration, opt, continous_dir, grow_distance, modelcg, cameras_extent, return_depth, contribution=None,
             contribution_mask=None, features=None, return_normals=False, distortion=None, median_depth=False,
-            plane_depth=False):
-    """The frame of ``render`` as the rasterizer leaves it.  ``distortion``: None, or the operator's ``distortion=``;
+            plane_depth=False, abs_grad=False):
+    """The frame of ``render`` as the rasterizer leaves it.  ``abs_grad``: ``render``'s.  ``distortion``: None, or the operator's ``distortion=``;
     ``median_depth``: the operator's ``median_depth=``; ``plane_depth``: ``render``'s ``return_plane_depth``."""
     which = grow.branch(iteration, opt, grow_dir, continous_dir, modelcg)
     if plane_depth:
@@ -191,6 +200,9 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
     if which is not None and median_depth:
         raise ValueError("return_median_depth=True is not available on a frame of the open grow / learned-split branch "
                          "(virtual rows appended): render the map in a frame of its own")
+    if which is not None and abs_grad:
+        raise ValueError("abs_grad=True is not available on a frame of the open grow / learned-split branch "
+                         "(virtual rows appended)")
     if which is not None:
         return _render_grown(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, which, grow_dir,
                              densify_grad_threshold, continous_dir, grow_distance, modelcg, cameras_extent)
@@ -201,7 +213,11 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
     # The operator never reads (or writes) its values, so every frame's leaf aliases one cached block of zeros: a
     # fresh 72 MB memset per frame is 20 us of the 6 M-Gaussian forward.
     screenspace_points = _zero_leaf(xyz)
-    stats = None if return_depth or want_feat or distortion is not None or median_depth else _fused_stats(pc, pipe, xyz)
+    stats = None if return_depth or want_feat or distortion is not None or median_depth or abs_grad \
+        else _fused_stats(pc, pipe, xyz)
+    # the second leaf of an abs_grad frame travels only when the caller asked: a frame without it is issued exactly as before
+    abs_kw = {"means2D_abs": _zero_leaf(xyz), "abs_grad": True} if abs_grad else {}
+    abs_entry = {"viewspace_points_abs": abs_kw["means2D_abs"]} if abs_grad else {}
     if stats is not None:
         screenspace_points._gsr_stats_fused = True      # read by losses.add_densification_stats
 
@@ -257,19 +273,21 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
             out = rasterize_gaussians_fused(xyz, screenspace_points, pc._features_dc, pc._features_rest, pc._opacity,
                                             pc._scaling, pc._rotation, raster_settings, visible=visible,
                                             **({"aux_maps": True} if return_depth else {}), **extra_stats,
-                                            **({} if distortion is None else {"distortion": distortion}), **median_kw)
-            return with_plane_depth({"render": out[0], "viewspace_points": screenspace_points,
+                                            **({} if distortion is None else {"distortion": distortion}), **median_kw,
+                                            **abs_kw)
+            return with_plane_depth({"render": out[0], "viewspace_points": screenspace_points, **abs_entry,
                                      "visibility_filter": visible, "radii": out[1], "selected_pts_mask": None,
                                      **(_aux_entries(out[2]) if return_depth else {}), **feature_entries(out)})
         rendered_image, radii = rasterize_gaussians_fused(xyz, screenspace_points, pc._features_dc, pc._features_rest,
                                                           pc._opacity, pc._scaling, pc._rotation, raster_settings,
-                                                          densify_stats=stats, visible=visible, **extra_stats)
-        return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": visible,
-                "radii": radii, "selected_pts_mask": None}
+                                                          densify_stats=stats, visible=visible, **extra_stats, **abs_kw)
+        return {"render": rendered_image, "viewspace_points": screenspace_points, **abs_entry,
+                "visibility_filter": visible, "radii": radii, "selected_pts_mask": None}
 
     feat_kw = {"features": extra_stats.pop("features")} if want_feat else {}
     rasterizer = GaussianRasterizer(raster_settings=raster_settings, **({"aux_maps": True} if return_depth else {}),
-                                    **extra_stats, **({} if distortion is None else {"distortion": distortion}), **median_kw)
+                                    **extra_stats, **({} if distortion is None else {"distortion": distortion}), **median_kw,
+                                    **({"abs_grad": True} if abs_grad else {}))
     scales = rotations = cov3D_precomp = None
     if getattr(pipe, "compute_cov3D_python", False):
         cov3D_precomp = pc.get_covariance(scaling_modifier)
@@ -292,12 +310,14 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
     # exactly the reference's eight keyword arguments (gaussian_renderer/__init__.py:257-265); the statistics request of
     # this build travels as a ninth only when the caller asked for it
     extra = dict(feat_kw) if stats is None else {"densify_stats": stats}
+    if abs_grad:
+        extra["means2D_abs"] = abs_kw["means2D_abs"]
     out = rasterizer(means3D=xyz, means2D=screenspace_points, shs=shs,
                      colors_precomp=colors_precomp, opacities=pc.get_opacity, scales=scales,
                      rotations=rotations, cov3D_precomp=cov3D_precomp, **extra)
     rendered_image, radii = out[0], out[1]
     return with_plane_depth({"render": rendered_image,
-                             "viewspace_points": screenspace_points,
+                             "viewspace_points": screenspace_points, **abs_entry,
                              "visibility_filter": radii > 0,
                              "radii": radii,
                              "selected_pts_mask": None,

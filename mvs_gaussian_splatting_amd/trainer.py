@@ -101,6 +101,11 @@ class OptimizationParams:
     bilateral_grid_lr_init = 2e-3
     bilateral_grid_lr_final = 2e-5
     lambda_tv = 10.0
+    # absolute-gradient densification (AbsGS; PGSR's densify_abs_grad_threshold): the frame is rendered with
+    # render(abs_grad=True) and a large Gaussian is also split when its accumulated absolute gradient reaches the second
+    # threshold; read only under strategy "default"; False leaves the iteration as it is
+    abs_grad = False
+    densify_abs_grad_threshold = 0.0008
 
     def __init__(self, **overrides):
         for k, v in overrides.items():
@@ -197,7 +202,15 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
     learning rate follows the iteration and its optimizer is stepped and zeroed where the model's is.  The source frame
     of the multi-view terms is not sliced: its colour enters no term.  ``KeyError`` for a camera without a grid and
     ``ValueError`` before ``training_setup``, both before anything is rendered.  None: exactly the calls made without
-    it."""
+    it.
+    ``opt.abs_grad`` (AbsGS / PGSR), on the iterations that take densification statistics
+    (``iteration < opt.densify_until_iter``): the frame is rendered with ``abs_grad=True`` -- which, like the map
+    losses, takes the densification statistics out of the backward for the frame (``pipe.fuse_densify_stats`` is not
+    honoured on it) -- ``add_densification_stats`` is handed both leaves, and ``densify_and_prune`` gets
+    ``abs_grad_threshold=opt.densify_abs_grad_threshold``.  The absolute gradient is that of the colour loss; with a
+    multi-view term on, only the reference frame's is accumulated (the source frame is rendered without the switch).
+    ``ValueError`` for a fork model, ``strategy="mcmc"`` and ``pose_optimizer``.  ``abs_grad = False``: exactly the calls
+    made without it."""
     strategy = getattr(opt, "strategy", "default")
     if strategy not in ("default", "mcmc"):
         raise ValueError(f"strategy must be 'default' or 'mcmc', got {strategy!r}")
@@ -213,6 +226,18 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
             raise ValueError(f"mcmc_kwargs: unknown keys {sorted(unknown)}")
     elif mcmc_kwargs is not None:
         raise ValueError("mcmc_kwargs needs opt.strategy == 'mcmc'")
+    abs_on = bool(getattr(opt, "abs_grad", False))
+    if abs_on:
+        if mcmc:
+            raise ValueError("opt.abs_grad does not combine with strategy='mcmc': relocation reads no gradient statistics")
+        if is_fork(model) or any(bool(getattr(dataset, n, False)) for n in (
+                "grow_dir", "continous_dir", "grow_distance", "learn_split_distance", "learn_split_scale")):
+            raise ValueError("opt.abs_grad does not support the fork's grow / learned-split models: their densification "
+                             "plan has no absolute-gradient rule")
+        if pose_optimizer is not None:
+            raise ValueError("opt.abs_grad does not combine with pose_optimizer: the operator refuses abs_grad=True with "
+                             "camera tensors that require grad")
+        abs_on = iteration < opt.densify_until_iter      # the pass runs while statistics are taken (schedule's "stats")
     if train_exposure and getattr(model, "exposure_optimizer", None) is None:
         raise ValueError("train_exposure=True needs model.setup_exposures(image names) before training_setup")
     frame_grid = None
@@ -277,7 +302,7 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
                          **({"return_median_depth": True} if median_on else {}),
                          **({"return_plane_depth": True} if unbiased else {}),
                          **({"use_trained_exp": True} if train_exposure else {}))
-    pkg = render(camera, model, pipe, bg, **render_kwargs)                                      # :91
+    pkg = render(camera, model, pipe, bg, **render_kwargs, **({"abs_grad": True} if abs_on else {}))      # :91
     gt = camera.original_image if gt_image is None else gt_image
     image = pkg["render"] if frame_grid is None else slice_bilateral_grid(pkg["render"], frame_grid)
     loss = l1_dssim_loss(image, gt.to(image.device), opt.lambda_dssim)                          # :99-101
@@ -328,10 +353,12 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
                 relocate_gs(model, generator=mk.get("generator"), draws=mk.get("draws"))
                 add_new_gs(model, opt.cap_max, generator=mk.get("generator"), draws=mk.get("draws"))
         elif todo["stats"]:                                                                     # :127-137
-            add_densification_stats(model, pkg["viewspace_points"], pkg["radii"])
+            add_densification_stats(model, pkg["viewspace_points"], pkg["radii"],
+                                    **({"viewspace_abs": pkg["viewspace_points_abs"]} if abs_on else {}))
             if todo["densify"]:
                 densify_and_prune(model, opt.densify_grad_threshold, opt.min_opacity, cameras_extent,
-                                  todo["size_threshold"], opt=opt, iteration=iteration, **(densify_kwargs or {}))
+                                  todo["size_threshold"], opt=opt, iteration=iteration, **(densify_kwargs or {}),
+                                  **({"abs_grad_threshold": opt.densify_abs_grad_threshold} if abs_on else {}))
             if todo["reset"]:
                 model.reset_opacity()
         if todo["step"]:                                                                        # :140-142
