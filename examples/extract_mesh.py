@@ -5,7 +5,8 @@ the surface by marching tetrahedra, all on the HIP path (``mvs_gaussian_splattin
                                     [--sdf_trunc T] [--alpha_min A] [--max_depth D] [--depth_ratio R]
                                     [--num_cluster N] [--min_cluster_faces M] [--unbounded [--mesh_res N]]
                                     [--consistent K] [--n_sources S] [--points] [--unbiased_depth]
-                                    [--simplify_voxel S] [-s <dataset>] [-r ...]
+                                    [--simplify_voxel S] [--cull_views K|all] [--cull_masks DIR] [--cull_dilate R]
+                                    [--cull_occluded TOL] [-s <dataset>] [-r ...]
 
 The scene is loaded as ``examples/render.py`` loads it (``cfg_args.json`` of the model directory; ``-s`` and the other
 switches override it).  The volume bounds the bulk of the model's positions (``tsdf.volume_for_points``); ``--resolution``
@@ -40,6 +41,15 @@ surface where the expected depth bends towards the camera.  ``--depth_ratio`` bl
 DESIGN.md §7.26): the vertices of a cell become their mean, the faces that collapse or repeat go.  It runs on the cleaned
 mesh when the mesh is cleaned, else on the raw one, and writes ``tsdf_mesh_simplified.ply`` (``tsdf_mesh_unbounded_simplified.ply``)
 next to the others.  A cell of two or three TSDF voxels suits a marching-tetrahedra mesh.  Without the flag nothing changes.
+
+``--cull_views K|all``, ``--cull_masks DIR`` and ``--cull_occluded TOL`` cull the mesh by the training views
+(``mesh.cull_mesh_by_views``), after the cleaning and before the simplification, and write
+``tsdf_mesh_culled.ply`` (``tsdf_mesh_unbounded_culled.ply``) next to the others.  Every vertex is projected into every
+training view; a view sees it when it lands inside the image, on the object mask if there are masks
+(``DIR/<image_name>.png``, non-zero is object, resized with nearest to the camera's size; ``--cull_dilate R`` dilates them
+by R pixels first, 2DGS: 25), and, with ``--cull_occluded TOL``, not more than TOL (relative) behind the surface the view
+itself renders.  A vertex stays when K views see it; ``all``: every view whose image holds it, DTU's rule, the default
+with masks (1 without).  Faces with a dropped corner go.  Without these flags nothing changes.
 """
 import argparse
 import json
@@ -52,8 +62,8 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from mvs_gaussian_splatting_amd import (GaussianModel, ModelParams, Scene, bounding_sphere,  # noqa: E402
                                         contracted_volume_for_points, fuse_depth_points, fuse_views,
-                                        volume_for_points)
-from mvs_gaussian_splatting_amd.mesh import clean_mesh, simplify_mesh  # noqa: E402
+                                        view_counts_for_views, volume_for_points)
+from mvs_gaussian_splatting_amd.mesh import clean_mesh, cull_mesh_by_views, dilate_mask, simplify_mesh  # noqa: E402
 from mvs_gaussian_splatting_amd.ply_io import write_ply_mesh, write_ply_vertices  # noqa: E402
 from mvs_gaussian_splatting_amd.synthetic import PipelineParams  # noqa: E402
 
@@ -71,9 +81,24 @@ def write_points(path, xyz, rgb):
     write_ply_vertices(path, elements)
 
 
+def read_mask(folder, camera):
+    """``folder/<image_name>.png`` as a uint8 [H,W] tensor on the GPU: non-zero (in any channel) is object; a mask of
+    another size is resized with nearest to the camera's."""
+    from PIL import Image
+    image = Image.open(os.path.join(folder, camera.image_name + ".png"))
+    size = (int(camera.image_width), int(camera.image_height))
+    if image.size != size:
+        image = image.resize(size, Image.NEAREST)
+    pixels = np.asarray(image)
+    if pixels.ndim == 3:
+        pixels = pixels.any(axis=2)
+    return torch.from_numpy(np.ascontiguousarray(pixels != 0).astype(np.uint8)).to("cuda")
+
+
 def extract(dataset, iteration, voxel_size=None, resolution=None, sdf_trunc=None, alpha_min=0.5, max_depth=None,
             depth_ratio=0.0, num_cluster=None, min_cluster_faces=None, unbounded=False, mesh_res=None, consistent=None,
-            n_sources=4, points=False, unbiased_depth=False, simplify_voxel=None):
+            n_sources=4, points=False, unbiased_depth=False, simplify_voxel=None, cull_views=None, cull_masks=None,
+            cull_dilate=0, cull_occluded=None):
     with torch.no_grad():
         gaussians = GaussianModel(dataset.sh_degree)
         scene = Scene(dataset, gaussians, load_iteration=iteration, shuffle=False)
@@ -114,6 +139,25 @@ def extract(dataset, iteration, voxel_size=None, resolution=None, sdf_trunc=None
         print(f"cleaned (num_cluster {num_cluster}, min_cluster_faces {min_cluster_faces}): {kept_v.shape[0]} of "
               f"{vertices.shape[0]} vertices, {kept_f.shape[0]} of {faces.shape[0]} faces -> {post}")
         vertices, faces, colors = kept_v, kept_f, kept_c
+    if cull_views is not None or cull_masks is not None or cull_occluded is not None:
+        cameras = scene.getTrainCameras()
+        masks = None if cull_masks is None else [read_mask(cull_masks, camera) for camera in cameras]
+        if masks is not None and cull_dilate:
+            masks = [dilate_mask(mask, cull_dilate) for mask in masks]
+        if cull_views is None:
+            cull_views = 1 if masks is None else "all"
+        counts = view_counts_for_views(cameras, gaussians, PipelineParams(), background, vertices, masks=masks,
+                                       occlusion=cull_occluded is not None, alpha_min=alpha_min,
+                                       **({"depth_ratio": depth_ratio} if depth_ratio else {}),
+                                       **({"unbiased_depth": True} if unbiased_depth else {}),
+                                       **({} if cull_occluded is None else {"depth_tol": cull_occluded}))
+        seen_v, seen_f, seen_c = cull_mesh_by_views(vertices, faces, colors, cameras=[], counts=counts, min_views=cull_views)
+        culled = path[:-len(".ply")] + "_culled.ply"
+        write_ply_mesh(culled, seen_v, seen_f, seen_c)
+        print(f"culled by {len(cameras)} views (cull_views {cull_views}, masks {cull_masks}, dilate {cull_dilate}, "
+              f"occluded {cull_occluded}): {seen_v.shape[0]} of {vertices.shape[0]} vertices, {seen_f.shape[0]} of "
+              f"{faces.shape[0]} faces -> {culled}")
+        vertices, faces, colors = seen_v, seen_f, seen_c
     if simplify_voxel is not None:
         small_v, small_f, small_c = simplify_mesh(vertices, faces, colors, voxel_size=simplify_voxel)
         simplified = path[:-len(".ply")] + "_simplified.ply"
@@ -156,7 +200,26 @@ def main(argv=None):
                     help="fuse PGSR's unbiased plane depth instead of the expected depth")
     ap.add_argument("--simplify_voxel", type=float, default=None, metavar="S",
                     help="simplify the mesh by vertex clustering on cells of S world units (after the cleaning, if any)")
+    ap.add_argument("--cull_views", default=None, metavar="K|all",
+                    help="cull the mesh: keep the vertices that K training views see; all: every view whose image holds them")
+    ap.add_argument("--cull_masks", default=None, metavar="DIR",
+                    help="cull the mesh: a view sees a vertex only on its object mask DIR/<image_name>.png (non-zero)")
+    ap.add_argument("--cull_dilate", type=int, default=0, metavar="R", help="dilate the masks by R pixels first (2DGS: 25)")
+    ap.add_argument("--cull_occluded", type=float, default=None, metavar="TOL",
+                    help="cull the mesh: a view sees a vertex only within TOL (relative) of the surface it renders")
     args = ap.parse_args(argv)
+    if args.cull_views is not None and args.cull_views != "all":
+        if not args.cull_views.isdigit():
+            ap.error("--cull_views must be a non-negative integer or all")
+        args.cull_views = int(args.cull_views)
+    if not 0 <= args.cull_dilate <= 1024:
+        ap.error("--cull_dilate must lie in 0..1024")
+    if args.cull_dilate and args.cull_masks is None:
+        ap.error("--cull_dilate belongs to --cull_masks")
+    if args.cull_masks is not None and not os.path.isdir(args.cull_masks):
+        ap.error("--cull_masks must be a directory")
+    if args.cull_occluded is not None and not 0 <= args.cull_occluded < float("inf"):
+        ap.error("--cull_occluded must be finite and not negative")
     if args.simplify_voxel is not None and not 0 < args.simplify_voxel < float("inf"):
         ap.error("--simplify_voxel must be positive and finite")
     if args.consistent is not None and args.consistent < 0:
@@ -194,7 +257,10 @@ def main(argv=None):
             **({} if args.consistent is None and not args.points else
                {"consistent": args.consistent, "n_sources": args.n_sources, "points": args.points}),
             **({"unbiased_depth": True} if args.unbiased_depth else {}),
-            **({} if args.simplify_voxel is None else {"simplify_voxel": args.simplify_voxel}))
+            **({} if args.simplify_voxel is None else {"simplify_voxel": args.simplify_voxel}),
+            **({} if args.cull_views is None and args.cull_masks is None and args.cull_occluded is None else
+               {"cull_views": args.cull_views, "cull_masks": args.cull_masks, "cull_dilate": args.cull_dilate,
+                "cull_occluded": args.cull_occluded}))
 
 
 if __name__ == "__main__":

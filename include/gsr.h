@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 40
+#define GSR_ABI_VERSION 41
 
 enum {
   GSR_OK = 0,
@@ -1240,6 +1240,54 @@ int gsr_simplify_face_unique(const int64_t* first_sorted, const int64_t* perm, c
  * exclusive scan.  vertex_cluster int32 [V] = cluster_offs[c] for a vertex whose cluster c is marked, else -1. */
 int gsr_simplify_vertex_map(const int32_t* cluster_of_vertex, const uint8_t* cluster_mark, const int64_t* cluster_offs,
                             int64_t V, int64_t K, int32_t* vertex_cluster, void* stream);
+
+/* ---- Culling a mesh by the views that saw it, ABI v41 (csrc/mesh_cull.hip, csrc/mesh_cull_math.h; mesh.vertex_view_counts,
+ * mesh.cull_mesh_by_views, mesh.dilate_mask).  Every vertex is projected into every view of a table and
+ * two things are counted: the views whose image it lands in, and of those the views in which it lands on the object mask
+ * and not behind the view's depth map.  The protocols are rules on these counts (DTU: visible in every view that was
+ * counted, with dilated masks; Tanks and Temples: visible somewhere).  Pixel convention of GsrTsdfView / GsrMvsSource:
+ * cx = (W - 1) / 2, cy = (H - 1) / 2.  The float32 operation order is csrc/mesh_cull_math.h (-ffp-contract=off), written
+ * once for device and host.
+ * One row of the device-resident view table, 8-byte aligned, 96 bytes.  The rows are device memory and are not checked:
+ * width and height (each 1 .. 2^24, width height at most 2^28) must describe the row's mask and depth arrays -- that is
+ * the caller's contract; mesh.vertex_view_counts checks every map against its camera before it builds the table. */
+#define GSR_CULL_MAX_VIEWS 65535
+typedef struct GsrCullView {
+  const uint8_t* mask;     /* device [height,width] or NULL (no mask); non-zero = object */
+  const float* depth;      /* device [height,width], 4-byte aligned, or NULL (no occlusion test); 0 = no surface */
+  int32_t width, height;
+  float fx, fy;
+  float world_to_view[16]; /* row-vector convention, M[4 * row + col]: the camera's float32 world_view_transform */
+} GsrCullView;
+/* vertices [V,3] float32 -> in_view int32 [V], visible int32 [V].  Per vertex (x, y, z) and per row in table order:
+ *     (xv, yv, zv) = (x, y, z, 1) through world_to_view, x' = ((x M[0] + y M[4]) + z M[8]) + M[12] and likewise y', z'
+ *     next view unless zv > near_plane                                     (a NaN fails)
+ *     u = (fx xv) / zv + cx, v = (fy yv) / zv + cy;  ix = floorf(u + 0.5f), iy = floorf(v + 0.5f)
+ *     next view unless 0 <= ix <= width - 1 and 0 <= iy <= height - 1       (in float; a NaN fails)
+ *     in_view += 1
+ *     next view if mask and mask[iy, ix] == 0
+ *     next view if depth and not (ds = depth[iy, ix]) > 0 and zv - ds <= depth_tol ds
+ *     visible += 1
+ * Every row of both outputs is written.  accumulate != 0: the counters start from the arrays' contents instead of 0, so
+ * the views can be fed in chunks; counts over chunks equal counts over one table.  One launch, one lane per vertex, the
+ * loop over the views inside, integer counters in registers: the same bits from run to run.  V = 0 is a success that
+ * writes nothing; S = 0 writes zeros (or, accumulating, leaves the arrays as they are).  Checked before any HIP call:
+ * GSR_E_BADARG for V outside 0 .. 2^31 - 1, S outside 0 .. 65535, a NULL table with S > 0, a NULL array with V > 0,
+ * near_plane not finite and positive, depth_tol not finite or negative; GSR_E_ALIGN for the arrays (4 bytes) and the table
+ * (8).  Asynchronous, allocates nothing, reads nothing back. */
+int gsr_cull_view_counts(const float* vertices, int64_t V, const GsrCullView* views, int32_t S, float near_plane,
+                         float depth_tol, int32_t accumulate, int32_t* in_view, int32_t* visible, void* stream);
+/* faces int32 [F,3], vkeep uint8 [V] -> keep uint8 [F]: 1 where all three corners have vkeep != 0, else 0.  A corner
+ * outside 0 .. V - 1 ORs 1 into status (device int32 [1], zeroed by the caller) and keeps nothing, as
+ * gsr_mesh_mark_vertices refuses it.  0 <= F, V <= 2^31 - 1; F = 0 is a success that writes nothing. */
+int gsr_cull_face_keep(const int32_t* faces, const uint8_t* vkeep, int64_t F, int64_t V, uint8_t* keep, int32_t* status,
+                       void* stream);
+/* Binary dilation of mask uint8 [H,W] (non-zero = set) by a (2 radius + 1) x (2 radius + 1) square -> out uint8 [H,W] of
+ * 0 / 1, as two separable passes: rows into tmp uint8 [H,W] (scratch), then columns into out.  Pixels outside the image
+ * count as 0; radius = 0 only normalises the mask.  out may be mask itself; tmp may be neither.  GSR_E_BADARG: a NULL
+ * pointer, H or W < 1 or H W > 2^28, radius outside 0 .. 1024, tmp equal to mask or out. */
+#define GSR_DILATE_MAX_RADIUS 1024
+int gsr_mask_dilate(const uint8_t* mask, int32_t H, int32_t W, int32_t radius, uint8_t* tmp, uint8_t* out, void* stream);
 
 #ifdef __cplusplus
 }

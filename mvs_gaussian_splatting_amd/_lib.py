@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # instead of copying it over the in-tree library
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")
 
-ABI_VERSION = 40
+ABI_VERSION = 41
 
 
 class GsrParams(C.Structure):
@@ -82,6 +82,16 @@ class GsrMvsSource(C.Structure):
     """One row of the source table of ``gsr_mvs_consistency`` (include/gsr.h, ABI v34; mvs.py): 152 bytes."""
     _fields_ = [("depth", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_float), ("fy", C.c_float),
                 ("ref_to_src", C.c_float * 16), ("src_to_ref", C.c_float * 16)]
+
+
+CULL_MAX_VIEWS = 65535
+DILATE_MAX_RADIUS = 1024
+
+
+class GsrCullView(C.Structure):
+    """One row of the view table of ``gsr_cull_view_counts`` (include/gsr.h, ABI v41; mesh.py): 96 bytes."""
+    _fields_ = [("mask", C.c_void_p), ("depth", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32),
+                ("fx", C.c_float), ("fy", C.c_float), ("world_to_view", C.c_float * 16)]
 
 
 class GsrGrow(C.Structure):
@@ -353,6 +363,12 @@ SYMBOLS = {
     "gsr_simplify_face_keys": (C.c_int, [C.c_void_p] * 2 + [C.c_int64] * 3 + [C.c_void_p] * 6),
     "gsr_simplify_face_unique": (C.c_int, [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 3),
     "gsr_simplify_vertex_map": (C.c_int, [C.c_void_p] * 3 + [C.c_int64] * 2 + [C.c_void_p] * 2),
+    # culling a mesh by the views that saw it: per-vertex view counts, the face rule and mask dilation
+    # (csrc/mesh_cull.hip; mesh.vertex_view_counts, mesh.cull_mesh_by_views, mesh.dilate_mask)
+    "gsr_cull_view_counts": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int32] +
+                             [C.c_void_p] * 3),
+    "gsr_cull_face_keep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 3),
+    "gsr_mask_dilate": (C.c_int, [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p] * 3),
 }
 
 _lib = None

@@ -16,6 +16,15 @@ Marching tetrahedra ties the triangle size to the TSDF voxel, not to the detail 
 the mesh smaller by vertex clustering on a uniform grid (``csrc/mesh_simplify.hip`` behind the ``gsr_simplify_*`` entry
 points): the vertices of a grid cell become their mean, the faces that collapse or repeat go.  The same
 key-sort-run pattern, the same compaction.
+
+    counts = view_counts_for_views(cameras, gaussians, pipe, background, vertices)                  # tsdf.py: renders
+    vertices, faces, colors = cull_mesh_by_views(vertices, faces, colors, cameras=[], counts=counts, min_views=1)
+
+The published mesh protocols cull before they score: DTU keeps a vertex where it lands on the dilated object mask of
+every view that holds it, the unbounded ones drop what no camera saw.  ``vertex_view_counts`` projects every vertex into
+every view and counts, per vertex, the views whose image holds it and those that see it (mask, depth map);
+``cull_mesh_by_views`` is the rule on those counts and the same compaction; ``dilate_mask`` is the masks' dilation
+(``csrc/mesh_cull.hip`` behind ``gsr_cull_view_counts``, ``gsr_cull_face_keep``, ``gsr_mask_dilate``).
 """
 from __future__ import annotations
 
@@ -184,6 +193,15 @@ def clean_mesh(vertices: torch.Tensor, faces: torch.Tensor, colors: Optional[tor
         threshold = torch.maximum(threshold, kth)
     keep = (component_faces[face_component.to(torch.int64)] >= threshold).to(torch.uint8)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
+    return _compact_kept(lib, vertices_c, colors_c, faces_c, keep, status, "clean_mesh") or empty()   # read-back 2: V', F'
+
+
+def _compact_kept(lib, vertices_c, colors_c, faces_c, keep, status, what):
+    """The tail that ``clean_mesh`` and ``cull_mesh_by_views`` share: with ``keep`` uint8 ``[F]`` (0 / 1) over contiguous
+    device tensors, F > 0, mark the vertices of the kept faces, scan, read ``V'``, ``F'`` and the status word back (the one
+    read-back) and compact -> ``(vertices, faces, colors or None)``, or ``None`` when no face is kept.  A status word that
+    is not 0 -- a face index outside ``0..V-1``, here or in the caller's kernels before -- raises ``GsrError``."""
+    V, F, dev = int(vertices_c.shape[0]), int(faces_c.shape[0]), vertices_c.device
     vertex_mark = torch.zeros(V, dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
@@ -191,9 +209,11 @@ def clean_mesh(vertices: torch.Tensor, faces: torch.Tensor, colors: Optional[tor
                                               status.data_ptr(), stream), "gsr_mesh_mark_vertices")
         vert_end = torch.cumsum(vertex_mark, dim=0, dtype=torch.int64)
         face_end = torch.cumsum(keep, dim=0, dtype=torch.int64)
-        Vk, Fk = (int(v) for v in torch.stack((vert_end[-1], face_end[-1])).tolist())              # read-back 2: V', F'
+        Vk, Fk, bad = (int(v) for v in torch.stack((vert_end[-1], face_end[-1], status[0].to(torch.int64))).tolist())
+        if bad:
+            raise _lib.GsrError(f"{what} failed: a face refers to a vertex outside 0..{V - 1}")
         if Fk == 0:
-            return empty()
+            return None
         out_vertices = torch.empty((Vk, 3), dtype=torch.float32, device=dev)
         out_faces = torch.empty((Fk, 3), dtype=torch.int32, device=dev)
         out_colors = None if colors_c is None else torch.empty((Vk, 3), dtype=torch.float32, device=dev)
@@ -368,4 +388,235 @@ def simplify_mesh(vertices: torch.Tensor, faces: torch.Tensor, colors: Optional[
     return out_vertices, out_faces, out_colors, vertex_cluster
 
 
-__all__ = ["connected_components", "clean_mesh", "simplify_mesh"]
+def _check_mesh(vertices, faces, colors, what: str, with_faces: bool = True) -> Tuple[int, int]:
+    if not isinstance(vertices, torch.Tensor) or vertices.dtype != torch.float32 or vertices.dim() != 2 \
+            or vertices.shape[1] != 3:
+        raise ValueError(f"vertices must be a float32 [V,3] tensor, got {getattr(vertices, 'dtype', type(vertices))} "
+                         f"{tuple(getattr(vertices, 'shape', ()))}")
+    V = int(vertices.shape[0])
+    if V >= 2 ** 31:
+        raise ValueError(f"{what} takes fewer than 2^31 vertices, got {V}")
+    if not with_faces:
+        return V, 0
+    F, _ = _check_faces(faces, V, what)
+    dev = vertices.device
+    if faces.device != dev:
+        raise ValueError(f"faces must be on the device of vertices ({dev}), got {faces.device}")
+    if colors is not None and (not isinstance(colors, torch.Tensor) or colors.dtype != torch.float32
+                               or tuple(colors.shape) != (V, 3) or colors.device != dev):
+        raise ValueError(f"colors must be a float32 [{V},3] tensor on {dev}, got "
+                         f"{getattr(colors, 'dtype', type(colors))} {tuple(getattr(colors, 'shape', ()))} on "
+                         f"{getattr(colors, 'device', None)}")
+    return V, F
+
+
+def _view_map(m, H: int, W: int, dev, dtypes, what: str) -> torch.Tensor:
+    if not isinstance(m, torch.Tensor) or m.dtype not in dtypes or m.device != dev \
+            or tuple(m.shape) not in ((H, W), (1, H, W)):
+        names = " or ".join(str(d).replace("torch.", "") for d in dtypes)
+        raise ValueError(f"{what} must be a {names} [{H},{W}] or [1,{H},{W}] tensor on {dev}, got "
+                         f"{getattr(m, 'dtype', type(m))} {tuple(getattr(m, 'shape', ()))} on {getattr(m, 'device', None)}")
+    m = m.detach().reshape(H, W).contiguous()
+    return m.view(torch.uint8) if m.dtype == torch.bool else m
+
+
+def _cull_scalars(near, depth_tol) -> Tuple[float, float]:
+    for name, v in (("near", near), ("depth_tol", depth_tol)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError(f"{name} must be a finite float, got {v!r}")
+    if not near > 0:
+        raise ValueError(f"near must be positive, got {near!r}")
+    if depth_tol < 0:
+        raise ValueError(f"depth_tol must not be negative, got {depth_tol!r}")
+    return float(near), float(depth_tol)
+
+
+def _per_view(maps, S: int, name: str) -> list:
+    if maps is None:
+        return [None] * S
+    try:
+        maps = list(maps)
+    except TypeError:
+        raise ValueError(f"{name} must be None or a sequence of {S} maps, got {type(maps)}") from None
+    if len(maps) != S:
+        raise ValueError(f"{len(maps)} {name} for {S} cameras")
+    return maps
+
+
+def dilate_mask(mask: torch.Tensor, radius: int) -> torch.Tensor:
+    """The binary dilation of ``mask`` (uint8 or bool ``[H,W]`` on a ROCm GPU; non-zero is set) by a
+    ``(2 radius + 1) x (2 radius + 1)`` square -> a new uint8 ``[H,W]`` tensor of 0 / 1 (csrc/mesh_cull.hip, two separable
+    passes).  Pixels outside the image count as 0; ``radius = 0`` only normalises the mask; ``radius`` lies in 0..1024.
+    2DGS dilates DTU's object masks with a 50 x 50 kernel before it culls: ``radius=25`` here.  Two launches on the current
+    stream, nothing is read back."""
+    if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.uint8, torch.bool) or mask.dim() != 2 \
+            or mask.shape[0] < 1 or mask.shape[1] < 1:
+        raise ValueError(f"mask must be a uint8 or bool [H,W] tensor with H, W >= 1, got "
+                         f"{getattr(mask, 'dtype', type(mask))} {tuple(getattr(mask, 'shape', ()))}")
+    H, W = int(mask.shape[0]), int(mask.shape[1])
+    if H * W > 2 ** 28:
+        raise ValueError(f"a mask of {W} x {H} exceeds 2^28 pixels")
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= _lib.DILATE_MAX_RADIUS:
+        raise ValueError(f"radius must be an int in 0..{_lib.DILATE_MAX_RADIUS}, got {radius!r}")
+    _need_gpu(mask, "dilate_mask")
+    lib, dev = _lib.load(), mask.device
+    mask_c = _view_map(mask, H, W, dev, (torch.uint8, torch.bool), "mask")
+    tmp = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    out = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(lib.gsr_mask_dilate(mask_c.data_ptr(), H, W, radius, tmp.data_ptr(), out.data_ptr(), stream),
+                   "gsr_mask_dilate")
+    return out
+
+
+def vertex_view_counts(vertices: torch.Tensor, cameras, *, masks=None, depths=None, near: float = 0.2,
+                       depth_tol: float = 0.01, counts=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """How many views see each vertex -> ``(in_view int32 [V], visible int32 [V])`` on the device of ``vertices`` (float32
+    ``[V,3]`` on a ROCm GPU), in one launch on the current stream (csrc/mesh_cull.hip).
+
+    ``cameras``: up to 65535 of anything with ``world_view_transform``, ``FoVx``, ``FoVy``, ``image_width``,
+    ``image_height``.  Per vertex and camera, in float32 with every operation rounded on its own (csrc/mesh_cull_math.h):
+    the vertex goes through ``world_view_transform``; a view counts only if ``zv > near``; it lands at
+    ``u = fx xv / zv + cx``, ``v = fy yv / zv + cy`` with ``cx = (W - 1) / 2``, and the pixel is ``floor(u + 0.5)``,
+    ``floor(v + 0.5)``; a view whose image holds that pixel adds 1 to ``in_view``.  It adds 1 to ``visible`` as well unless
+    ``masks[k]`` (uint8 or bool ``[H,W]``; non-zero is object) is 0 there, or ``depths[k]`` (float32 ``[H,W]``; 0 is no
+    surface) holds no surface there or one in front of the vertex: ``zv - ds > depth_tol * ds``.  ``masks`` / ``depths``:
+    ``None`` or one entry per camera, each ``None`` or a map of that camera's size on the vertices' device.
+
+    ``counts=(in_view, visible)``: two int32 ``[V]`` tensors that the counts are added into (and that are returned), so
+    that views can be fed in chunks and each chunk's depth maps freed; counts over chunks equal counts over one call.
+    NaN coordinates count nowhere.  The table of views is one small host-to-device copy; nothing is read back."""
+    V, _ = _check_mesh(vertices, None, None, "vertex_view_counts", with_faces=False)
+    views = _view_table(V, vertices.device, cameras, masks, depths, near, depth_tol, counts)
+    _need_gpu(vertices, "vertex_view_counts")
+    return _count_views(vertices, views, counts)
+
+
+def _view_table(V: int, dev, cameras, masks, depths, near, depth_tol, counts):
+    """Every check of ``vertex_view_counts`` behind the vertices', on the host, and the table of views ->
+    ``(S, table, maps, near, depth_tol)``; ``maps[k] = [mask or None, depth or None]``, the contiguous ``[H,W]`` maps
+    whose addresses the rows hold."""
+    try:
+        cameras = list(cameras)
+    except TypeError:
+        raise ValueError(f"cameras must be a sequence of cameras, got {type(cameras)}") from None
+    S = len(cameras)
+    if S > _lib.CULL_MAX_VIEWS:
+        raise ValueError(f"at most {_lib.CULL_MAX_VIEWS} views in one call, got {S}: feed them in chunks through counts=")
+    near, depth_tol = _cull_scalars(near, depth_tol)
+    masks, depths = _per_view(masks, S, "masks"), _per_view(depths, S, "depths")
+    if counts is not None:
+        if not isinstance(counts, (tuple, list)) or len(counts) != 2 or any(
+                not isinstance(c, torch.Tensor) or c.dtype != torch.int32 or tuple(c.shape) != (V,) or c.device != dev
+                or not c.is_contiguous() for c in counts) or (V > 0 and counts[0].data_ptr() == counts[1].data_ptr()):
+            raise ValueError(f"counts must be two distinct contiguous int32 [{V}] tensors on {dev}")
+    from .mvs import _focal
+    table = (_lib.GsrCullView * max(S, 1))()
+    maps = []
+    for k, (cam, m, d) in enumerate(zip(cameras, masks, depths)):
+        H, W, fx, fy = _focal(cam)
+        if H * W > 2 ** 28 or max(H, W) > 2 ** 24:
+            raise ValueError(f"camera {k}: an image of {W} x {H} exceeds 2^28 pixels or 2^24 a side")
+        M = cam.world_view_transform.detach().to(device="cpu", dtype=torch.float32)
+        if tuple(M.shape) != (4, 4):
+            raise ValueError(f"camera {k}: world_view_transform must be 4 x 4, got {tuple(M.shape)}")
+        row = table[k]
+        row.width, row.height, row.fx, row.fy = W, H, fx, fy
+        row.world_to_view[:] = M.reshape(-1).tolist()
+        if m is not None:
+            m = _view_map(m, H, W, dev, (torch.uint8, torch.bool), f"masks[{k}]")
+            row.mask = m.data_ptr()
+        if d is not None:
+            d = _view_map(d, H, W, dev, (torch.float32,), f"depths[{k}]")
+            row.depth = d.data_ptr()
+        maps.append([m, d])
+    return S, table, maps, near, depth_tol
+
+
+def _count_views(vertices: torch.Tensor, views, counts) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The launch of ``vertex_view_counts`` for the table of ``_view_table``, on device vertices."""
+    S, table, maps, near, depth_tol = views
+    V, dev = int(vertices.shape[0]), vertices.device
+    if counts is None:
+        in_view = torch.empty(V, dtype=torch.int32, device=dev)
+        visible = torch.empty(V, dtype=torch.int32, device=dev)
+    else:
+        in_view, visible = counts
+    if V == 0:
+        return in_view, visible
+    lib = _lib.load()
+    vertices_c = vertices.detach().contiguous()
+    with torch.cuda.device(dev):
+        table_dev = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev) if S > 0 else None
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(lib.gsr_cull_view_counts(vertices_c.data_ptr(), V, None if table_dev is None else table_dev.data_ptr(), S,
+                                            near, depth_tol, 0 if counts is None else 1, in_view.data_ptr(),
+                                            visible.data_ptr(), stream), "gsr_cull_view_counts")
+    return in_view, visible
+
+
+def cull_mesh_by_views(vertices: torch.Tensor, faces: torch.Tensor, colors: Optional[torch.Tensor] = None, *, cameras,
+                       masks=None, depths=None, min_views=1, near: float = 0.2, depth_tol: float = 0.01, dilate: int = 0,
+                       counts=None, return_counts: bool = False):
+    """Keep the part of a mesh that the views saw -> ``(vertices float32 [V',3], faces int32 [F',3], colors float32 [V',3]
+    or None)``, with ``return_counts=True`` also ``(in_view, visible)`` of the input vertices; new tensors on the same
+    device (csrc/mesh_cull.hip).
+
+    With ``(in_view, visible) = vertex_view_counts(vertices, cameras, masks=..., depths=..., near=..., depth_tol=...,
+    counts=...)``: a vertex is kept when ``visible >= min_views``.  ``min_views="all"`` stands for the vertex's own
+    ``in_view``, the number of views that counted it: the vertex must be visible in every view whose image it lands in,
+    which with object masks is DTU's rule (2DGS's ``cull_scan``; a vertex no view holds passes it, as it does there).
+    ``min_views=1`` without masks and with ``depths`` is the rule of the unbounded protocols: what no camera saw goes.
+    ``dilate``: every mask is dilated by that radius first (``dilate_mask``; 2DGS: 25).  ``counts``: counts of earlier
+    chunks of views to add to (``vertex_view_counts``); ``cameras`` may then be empty.
+
+    A face is kept when all three of its corners are; then the vertices that no kept face refers to go as well.  Kept
+    vertices and faces stay in their original order; the kept vertex and colour rows are bit-copies, the kept faces are
+    re-indexed.  Nothing is kept: ``[0,3]`` tensors.  One host read-back (``V'`` and ``F'``, with the check that every
+    face index lies in ``0..V-1``, else ``GsrError``); everything else stays on the device and on the current stream.
+    ``F == 0`` makes no native call (the counts returned are then the ones given, or zeros).  There is no CPU path."""
+    V, F = _check_mesh(vertices, faces, colors, "cull_mesh_by_views")
+    if min_views != "all" and (isinstance(min_views, bool) or not isinstance(min_views, int) or min_views < 0):
+        raise ValueError(f"min_views must be a non-negative int or \"all\", got {min_views!r}")
+    if isinstance(dilate, bool) or not isinstance(dilate, int) or not 0 <= dilate <= _lib.DILATE_MAX_RADIUS:
+        raise ValueError(f"dilate must be an int in 0..{_lib.DILATE_MAX_RADIUS}, got {dilate!r}")
+    if not isinstance(return_counts, bool):
+        raise ValueError(f"return_counts must be a bool, got {return_counts!r}")
+    if min_views != "all" and min_views >= 2 ** 31:
+        raise ValueError(f"min_views must fit an int32, got {min_views!r}")
+    dev = vertices.device
+
+    def result(mesh, in_view=None, visible=None):
+        if mesh is None:
+            mesh = (torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty((0, 3), dtype=torch.int32, device=dev),
+                    None if colors is None else torch.empty((0, 3), dtype=torch.float32, device=dev))
+        return mesh + ((in_view, visible),) if return_counts else mesh
+
+    views = _view_table(V, dev, cameras, masks, depths, near, depth_tol, counts)
+    _need_gpu(vertices, "cull_mesh_by_views")
+    if F == 0:                          # nothing to cull and nothing counted: the counts given, or zeros
+        zeros = torch.zeros(V, dtype=torch.int32, device=dev)
+        return result(None, *(counts if counts is not None else (zeros, zeros.clone())))
+    if dilate:
+        table, maps = views[1], views[2]
+        for k, pair in enumerate(maps):
+            if pair[0] is not None:
+                pair[0] = dilate_mask(pair[0], dilate)
+                table[k].mask = pair[0].data_ptr()
+    in_view, visible = _count_views(vertices, views, counts)
+    lib = _lib.load()
+    vertices_c, faces_c = vertices.detach().contiguous(), faces.detach().contiguous()
+    colors_c = None if colors is None else colors.detach().contiguous()
+    vkeep = (visible >= (in_view if min_views == "all" else min_views)).to(torch.uint8)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    keep = torch.empty(F, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(lib.gsr_cull_face_keep(faces_c.data_ptr(), vkeep.data_ptr(), F, V, keep.data_ptr(), status.data_ptr(),
+                                          stream), "gsr_cull_face_keep")
+    return result(_compact_kept(lib, vertices_c, colors_c, faces_c, keep, status, "cull_mesh_by_views"), in_view, visible)
+
+
+__all__ = ["connected_components", "clean_mesh", "simplify_mesh", "dilate_mask", "vertex_view_counts",
+           "cull_mesh_by_views"]

@@ -382,6 +382,46 @@ def fuse_views(cameras, model, pipe, bg, volume: TSDFVolume, *, alpha_min: float
     return volume
 
 
+def view_counts_for_views(cameras, model, pipe, bg, vertices: torch.Tensor, *, masks=None, occlusion: bool = True,
+                          chunk: int = 16, alpha_min: float = 0.5, renderer=None, depth_ratio: float = 0.0,
+                          unbiased_depth: bool = False, near: float = 0.2, depth_tol: float = 0.01):
+    """``mesh.vertex_view_counts`` of ``vertices`` over the training views, with each view's own rendered surface as its
+    depth map -> ``(in_view int32 [V], visible int32 [V])``: what ``mesh.cull_mesh_by_views(counts=...)`` culls by.
+    The views are taken ``chunk`` at a time: a chunk's surfaces are rendered under ``no_grad`` with ``render_surface``
+    (``alpha_min``, ``depth_ratio``, ``unbiased_depth`` and ``renderer`` as ``fuse_views`` takes them), counted into the
+    running counts and freed, so at most ``chunk`` depth maps are alive and the counts equal those of one table over all
+    views.  ``occlusion=False`` renders nothing: only the images' frames and ``masks`` (``None`` or one entry per camera)
+    count.  No host synchronisation beyond ``vertex_view_counts``' own."""
+    from .mesh import vertex_view_counts
+    if isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1:
+        raise ValueError(f"chunk must be a positive int, got {chunk!r}")
+    if not isinstance(occlusion, bool):
+        raise ValueError(f"occlusion must be a bool, got {occlusion!r}")
+    if not (isinstance(depth_ratio, (int, float)) and 0.0 <= depth_ratio <= 1.0):
+        raise ValueError(f"depth_ratio must lie in [0, 1], got {depth_ratio!r}")
+    cameras = list(cameras)
+    if masks is not None:
+        masks = list(masks)
+        if len(masks) != len(cameras):
+            raise ValueError(f"{len(masks)} masks for {len(cameras)} cameras")
+    if renderer is None and occlusion:
+        from .renderer import render as renderer
+    counts = None
+    with torch.no_grad():
+        for at in range(0, len(cameras), chunk):
+            some = cameras[at:at + chunk]
+            depths = None
+            if occlusion:
+                depths = [render_surface(renderer, camera, model, pipe, bg, alpha_min, depth_ratio,
+                                         **({"unbiased_depth": True} if unbiased_depth else {}))[0] for camera in some]
+            counts = vertex_view_counts(vertices, some, masks=None if masks is None else masks[at:at + chunk],
+                                        depths=depths, near=near, depth_tol=depth_tol, counts=counts)
+            del depths
+        if counts is None:                  # no cameras: zeros, through the same checks
+            counts = vertex_view_counts(vertices, [], near=near, depth_tol=depth_tol)
+    return counts
+
+
 def volume_for_points(xyz: torch.Tensor, *, voxel_size: Optional[float] = None, resolution: Optional[int] = None,
                       margin: float = 0.05, quantile: float = 0.01, sdf_trunc: Optional[float] = None,
                       with_color: bool = True, device=None) -> TSDFVolume:
@@ -419,4 +459,4 @@ def volume_for_points(xyz: torch.Tensor, *, voxel_size: Optional[float] = None, 
 
 
 __all__ = ["TSDFVolume", "ContractedTSDFVolume", "fuse_views", "volume_for_points", "contracted_volume_for_points",
-           "bounding_sphere", "contract"]
+           "bounding_sphere", "contract", "view_counts_for_views"]
