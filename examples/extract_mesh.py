@@ -6,7 +6,7 @@ the surface by marching tetrahedra, all on the HIP path (``mvs_gaussian_splattin
                                     [--num_cluster N] [--min_cluster_faces M] [--unbounded [--mesh_res N]]
                                     [--consistent K] [--n_sources S] [--points] [--unbiased_depth]
                                     [--simplify_voxel S] [--cull_views K|all] [--cull_masks DIR] [--cull_dilate R]
-                                    [--cull_occluded TOL] [-s <dataset>] [-r ...]
+                                    [--cull_occluded TOL] [--cull_invisible K] [-s <dataset>] [-r ...]
 
 The scene is loaded as ``examples/render.py`` loads it (``cfg_args.json`` of the model directory; ``-s`` and the other
 switches override it).  The volume bounds the bulk of the model's positions (``tsdf.volume_for_points``); ``--resolution``
@@ -50,6 +50,11 @@ training view; a view sees it when it lands inside the image, on the object mask
 by R pixels first, 2DGS: 25), and, with ``--cull_occluded TOL``, not more than TOL (relative) behind the surface the view
 itself renders.  A vertex stays when K views see it; ``all``: every view whose image holds it, DTU's rule, the default
 with masks (1 without).  Faces with a dropped corner go.  Without these flags nothing changes.
+
+``--cull_invisible K`` then removes the faces that fewer than K training views see in the mesh's own z-buffer
+(``mesh.cull_invisible_faces``): inner walls, shells inside closed objects and the back of the truncation
+band, which a vertex test within a depth tolerance keeps.  It runs after the view culling and before the simplification and
+writes ``tsdf_mesh_visible.ply`` (``tsdf_mesh_unbounded_visible.ply``).
 """
 import argparse
 import json
@@ -63,7 +68,8 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 from mvs_gaussian_splatting_amd import (GaussianModel, ModelParams, Scene, bounding_sphere,  # noqa: E402
                                         contracted_volume_for_points, fuse_depth_points, fuse_views,
                                         view_counts_for_views, volume_for_points)
-from mvs_gaussian_splatting_amd.mesh import clean_mesh, cull_mesh_by_views, dilate_mask, simplify_mesh  # noqa: E402
+from mvs_gaussian_splatting_amd.mesh import (clean_mesh, cull_invisible_faces, cull_mesh_by_views, dilate_mask,  # noqa: E402
+                                             simplify_mesh)
 from mvs_gaussian_splatting_amd.ply_io import write_ply_mesh, write_ply_vertices  # noqa: E402
 from mvs_gaussian_splatting_amd.synthetic import PipelineParams  # noqa: E402
 
@@ -98,7 +104,7 @@ def read_mask(folder, camera):
 def extract(dataset, iteration, voxel_size=None, resolution=None, sdf_trunc=None, alpha_min=0.5, max_depth=None,
             depth_ratio=0.0, num_cluster=None, min_cluster_faces=None, unbounded=False, mesh_res=None, consistent=None,
             n_sources=4, points=False, unbiased_depth=False, simplify_voxel=None, cull_views=None, cull_masks=None,
-            cull_dilate=0, cull_occluded=None):
+            cull_dilate=0, cull_occluded=None, cull_invisible=None):
     with torch.no_grad():
         gaussians = GaussianModel(dataset.sh_degree)
         scene = Scene(dataset, gaussians, load_iteration=iteration, shuffle=False)
@@ -158,6 +164,14 @@ def extract(dataset, iteration, voxel_size=None, resolution=None, sdf_trunc=None
               f"occluded {cull_occluded}): {seen_v.shape[0]} of {vertices.shape[0]} vertices, {seen_f.shape[0]} of "
               f"{faces.shape[0]} faces -> {culled}")
         vertices, faces, colors = seen_v, seen_f, seen_c
+    if cull_invisible is not None:
+        cameras = scene.getTrainCameras()
+        seen_v, seen_f, seen_c = cull_invisible_faces(vertices, faces, colors, cameras=cameras, min_views=cull_invisible)
+        visible = path[:-len(".ply")] + "_visible.ply"
+        write_ply_mesh(visible, seen_v, seen_f, seen_c)
+        print(f"faces seen by at least {cull_invisible} of {len(cameras)} views: {seen_f.shape[0]} of {faces.shape[0]} faces, "
+              f"{seen_v.shape[0]} of {vertices.shape[0]} vertices -> {visible}")
+        vertices, faces, colors = seen_v, seen_f, seen_c
     if simplify_voxel is not None:
         small_v, small_f, small_c = simplify_mesh(vertices, faces, colors, voxel_size=simplify_voxel)
         simplified = path[:-len(".ply")] + "_simplified.ply"
@@ -207,7 +221,11 @@ def main(argv=None):
     ap.add_argument("--cull_dilate", type=int, default=0, metavar="R", help="dilate the masks by R pixels first (2DGS: 25)")
     ap.add_argument("--cull_occluded", type=float, default=None, metavar="TOL",
                     help="cull the mesh: a view sees a vertex only within TOL (relative) of the surface it renders")
+    ap.add_argument("--cull_invisible", type=int, default=None, metavar="K",
+                    help="drop the faces that fewer than K training views see in the mesh's own z-buffer")
     args = ap.parse_args(argv)
+    if args.cull_invisible is not None and args.cull_invisible < 0:
+        ap.error("--cull_invisible must not be negative")
     if args.cull_views is not None and args.cull_views != "all":
         if not args.cull_views.isdigit():
             ap.error("--cull_views must be a non-negative integer or all")
@@ -260,7 +278,8 @@ def main(argv=None):
             **({} if args.simplify_voxel is None else {"simplify_voxel": args.simplify_voxel}),
             **({} if args.cull_views is None and args.cull_masks is None and args.cull_occluded is None else
                {"cull_views": args.cull_views, "cull_masks": args.cull_masks, "cull_dilate": args.cull_dilate,
-                "cull_occluded": args.cull_occluded}))
+                "cull_occluded": args.cull_occluded}),
+            **({} if args.cull_invisible is None else {"cull_invisible": args.cull_invisible}))
 
 
 if __name__ == "__main__":

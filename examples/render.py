@@ -23,6 +23,9 @@ as a 16-bit greyscale PNG scaled like ``--depth`` (``.../median_depth/scales.jso
 the int32 ``[H,W]`` map of the Gaussian that owns each pixel (-1: none).
 ``--plane_depth`` also writes ``.../plane_depth/%05d.png``: PGSR's unbiased depth (``render(return_plane_depth=True)``;
 0 where the frame has no surface) as a 16-bit greyscale PNG scaled like ``--depth`` (``.../plane_depth/scales.json``).
+``--mesh PLY`` also rasterizes that triangle mesh from every view (``rasterize_mesh``, ``face_normal_map``):
+``.../mesh_depth/%05d.png``, its depth as a 16-bit greyscale PNG scaled like ``--depth`` (``.../mesh_depth/scales.json``; 0: no
+surface), and ``.../mesh_normal/%05d.png``, its view-space face normals as colours, next to the renders.
 ``--use_trained_exp`` renders every view that has one with the exposure saved in the iteration's ``exposure.json``
 (``examples/train.py --train_exposure``); test views have none and are rendered as they are.
 """
@@ -88,9 +91,24 @@ def save_depth_png(depth, alpha, path):
     return step
 
 
+def save_mesh_pngs(mesh, view, depth_path, normal_path):
+    """The mesh ``(vertices, faces)`` from ``view``: its depth as 16-bit greyscale (0: no surface) and its view-space face
+    normals as colours; returns the depth one step stands for."""
+    import numpy as np
+    from PIL import Image
+    from mvs_gaussian_splatting_amd import face_normal_map, rasterize_mesh
+    depth, face_id = rasterize_mesh(mesh[0], mesh[1], view)
+    top = float(depth.max())
+    step = top / 65535.0 if top > 0 else 1.0
+    Image.fromarray(torch.round(depth / step).clamp(0, 65535).cpu().numpy().astype(np.uint16)).save(depth_path)
+    normal = face_normal_map(mesh[0], mesh[1], face_id, view)
+    save_png(torch.where(face_id[None] >= 0, normal * 0.5 + 0.5, torch.zeros_like(normal)), normal_path)
+    return step
+
+
 def render_set(model_path, name, iteration, views, gaussians, pipeline, background, depth=False,
                use_trained_exp=False, normals=False, depth_normals=False, distortion=False, median_depth=False,
-               plane_depth=False):
+               plane_depth=False, mesh=None):
     render_path = os.path.join(model_path, name, "ours_{}".format(iteration), "renders")
     gts_path = os.path.join(model_path, name, "ours_{}".format(iteration), "gt")
     depth_path = os.path.join(model_path, name, "ours_{}".format(iteration), "depth")
@@ -117,6 +135,12 @@ def render_set(model_path, name, iteration, views, gaussians, pipeline, backgrou
     plane_scales = []
     if plane_depth:
         os.makedirs(plane_path, exist_ok=True)
+    mesh_depth_path = os.path.join(model_path, name, "ours_{}".format(iteration), "mesh_depth")
+    mesh_normal_path = os.path.join(model_path, name, "ours_{}".format(iteration), "mesh_normal")
+    mesh_scales = []
+    if mesh is not None:
+        os.makedirs(mesh_depth_path, exist_ok=True)
+        os.makedirs(mesh_normal_path, exist_ok=True)
     for idx, view in enumerate(views):
         with_exp = use_trained_exp and view.image_name in (gaussians.pretrained_exposures or {})
         pkg = render(view, gaussians, pipeline, background, **({"return_depth": True} if depth or depth_normals else {}),
@@ -143,6 +167,12 @@ def render_set(model_path, name, iteration, views, gaussians, pipeline, backgrou
         if plane_depth:
             plane_scales.append(save_plane_depth_png(pkg["plane_depth"],
                                                      os.path.join(plane_path, "{0:05d}".format(idx) + ".png")))
+        if mesh is not None:
+            mesh_scales.append(save_mesh_pngs(mesh, view, os.path.join(mesh_depth_path, "{0:05d}".format(idx) + ".png"),
+                                              os.path.join(mesh_normal_path, "{0:05d}".format(idx) + ".png")))
+    if mesh is not None:
+        with open(os.path.join(mesh_depth_path, "scales.json"), "w") as f:
+            json.dump(mesh_scales, f)
     if plane_depth:
         with open(os.path.join(plane_path, "scales.json"), "w") as f:
             json.dump(plane_scales, f)
@@ -158,8 +188,12 @@ def render_set(model_path, name, iteration, views, gaussians, pipeline, backgrou
 
 
 def render_sets(dataset, iteration, pipeline, skip_train=False, skip_test=False, depth=False, use_trained_exp=False,
-                normals=False, depth_normals=False, distortion=False, median_depth=False, plane_depth=False):
+                normals=False, depth_normals=False, distortion=False, median_depth=False, plane_depth=False, mesh=None):
     with torch.no_grad():
+        if mesh is not None:
+            from mvs_gaussian_splatting_amd.ply_io import read_ply_mesh
+            mesh_v, mesh_f, _ = read_ply_mesh(mesh)
+            mesh = (torch.from_numpy(mesh_v).to("cuda"), torch.from_numpy(mesh_f).to("cuda"))
         gaussians = GaussianModel(dataset.sh_degree)
         scene = Scene(dataset, gaussians, load_iteration=iteration, shuffle=False)
         bg_color = [1, 1, 1] if dataset.white_background else [0, 0, 0]
@@ -169,11 +203,11 @@ def render_sets(dataset, iteration, pipeline, skip_train=False, skip_test=False,
         if not skip_train:
             render_set(dataset.model_path, "train", scene.loaded_iter, scene.getTrainCameras(), gaussians, pipeline,
                        background, depth, use_trained_exp, normals, depth_normals, distortion, median_depth,
-                       **({"plane_depth": True} if plane_depth else {}))
+                       **({"plane_depth": True} if plane_depth else {}), **({} if mesh is None else {"mesh": mesh}))
         if not skip_test:
             render_set(dataset.model_path, "test", scene.loaded_iter, scene.getTestCameras(), gaussians, pipeline,
                        background, depth, use_trained_exp, normals, depth_normals, distortion, median_depth,
-                       **({"plane_depth": True} if plane_depth else {}))
+                       **({"plane_depth": True} if plane_depth else {}), **({} if mesh is None else {"mesh": mesh}))
     return scene
 
 
@@ -199,6 +233,8 @@ def main(argv=None):
     ap.add_argument("--plane_depth", action="store_true",
                     help="also write PGSR's unbiased plane depth of every view as a 16-bit PNG")
     ap.add_argument("--use_trained_exp", action="store_true", help="apply the saved per-image exposures")
+    ap.add_argument("--mesh", default=None, metavar="PLY",
+                    help="also rasterize this triangle mesh from every view: mesh_depth/ (16-bit) and mesh_normal/ PNGs")
     args = ap.parse_args(argv)
     fields = {}
     cfg = os.path.join(args.model_path, "cfg_args.json")
@@ -214,7 +250,7 @@ def main(argv=None):
     print("Rendering " + args.model_path)
     render_sets(dataset, args.iteration, PipelineParams(), args.skip_train, args.skip_test, args.depth,
                 args.use_trained_exp, args.normals, args.depth_normals, args.distortion, args.median_depth,
-                **({"plane_depth": True} if args.plane_depth else {}))
+                **({"plane_depth": True} if args.plane_depth else {}), **({} if args.mesh is None else {"mesh": args.mesh}))
 
 
 if __name__ == "__main__":

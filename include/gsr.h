@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 41
+#define GSR_ABI_VERSION 42
 
 enum {
   GSR_OK = 0,
@@ -1288,6 +1288,47 @@ int gsr_cull_face_keep(const int32_t* faces, const uint8_t* vkeep, int64_t F, in
  * pointer, H or W < 1 or H W > 2^28, radius outside 0 .. 1024, tmp equal to mask or out. */
 #define GSR_DILATE_MAX_RADIUS 1024
 int gsr_mask_dilate(const uint8_t* mask, int32_t H, int32_t W, int32_t radius, uint8_t* tmp, uint8_t* out, void* stream);
+
+/* ---- Rasterizing a mesh from a camera, ABI v42 (csrc/mesh_raster.hip, csrc/mesh_raster_math.h; mesh.rasterize_mesh,
+ * mesh.face_view_counts, mesh.cull_invisible_faces).  A z-buffer of one uint64 per pixel,
+ * key = float_bits(z) << 32 | face, all ones where nothing landed, kept by integer atomicMin: the nearest surface wins, the
+ * smallest face index at equal depth, and the result is the same bits whatever order the faces arrive in.  The rule of a
+ * (face, view) pair -- view transform, near-plane clipping, the snap to 8 sub-pixel bits, int64 edge functions with the
+ * top-left rule, perspective-correct depth in float64 -- is stated in csrc/mesh_raster_math.h, one body for device and
+ * host, built with -ffp-contract=off.  The camera is a HOST GsrCullView row (mask and depth are not read); its width and
+ * height are at most 2^14 each and 2^28 together.
+ * Workspaces, the caller's: keys uint64 [height width], 8-byte aligned; queue: gsr_raster_queue_bytes(F) bytes, 8-byte
+ * aligned -- a 256-byte head (uint32 words: the queue's length, the pieces dropped, the faces with an index outside
+ * 0 .. V-1) and one uint32 slot for each of the 2 F pieces a mesh can have.  gsr_raster_queue_bytes is 0 for an F the
+ * calls refuse.  Every call checks its arguments before any HIP call (GSR_E_BADARG, GSR_E_ALIGN, GSR_E_CAPACITY for a
+ * short queue), is asynchronous on `stream`, allocates nothing and reads nothing back. */
+#define GSR_RASTER_MAX_SIDE 16384
+#define GSR_RASTER_LANE_PIXELS 16   /* a piece whose clipped bounding box holds more pixels than this goes to the queue */
+#define GSR_RASTER_DRAIN_WAVES 256  /* the fixed grid that drains the queue: 64 workgroups of four waves, one piece per wave */
+enum {
+  GSR_RASTER_CLEAR = 1,           /* first set every key to all ones and zero the head's dropped / bad-face counts */
+  GSR_RASTER_CULL_BACKFACES = 2,  /* drop the pieces that face away (csrc/mesh_raster_math.h, step 4) */
+  GSR_RASTER_NO_LOAD_SKIP = 4     /* A/B only: every covered centre issues its atomicMin, no load in front (same keys) */
+};
+size_t gsr_raster_queue_bytes(int64_t F);
+/* vertices float32 [V,3], faces int32 [F,3] (device) into keys.  A face with an index outside 0 .. V-1 is counted in the
+ * head and skipped; a piece with a snapped coordinate outside +-2^29 is counted and dropped.  view_scratch: NULL, or
+ * float32 [V,3] device scratch -- then the vertices are taken to view space once, in a launch of their own, and the faces
+ * gather from it (the same keys; which is faster is recorded in profiles/mesh_raster/NOTES.md).  Without GSR_RASTER_CLEAR
+ * the keys are only ever lowered, so several meshes can share one buffer if their face indices are kept apart.
+ * 0 <= V, F <= 2^31 - 1; F = 0 still clears. */
+int gsr_raster_view(const float* vertices, int64_t V, const int32_t* faces, int64_t F, const GsrCullView* view,
+                    float near_plane, int32_t flags, uint64_t* keys, void* queue, size_t queue_bytes, float* view_scratch,
+                    void* stream);
+/* keys -> depth float32 [H,W] (0 where no surface, the project's convention) and face_id int32 [H,W] (-1 there).  Every
+ * pixel of both is written. */
+int gsr_raster_resolve(const uint64_t* keys, int32_t H, int32_t W, float* depth, int32_t* face_id, void* stream);
+/* counts int32 [F] += 1 for every face that owns at least one pixel of keys, once per view: stamp int32 [F] (the
+ * caller's, zeroed before the first view) is exchanged with stamp_value = view + 1 (positive, distinct per view) and the
+ * count is raised when the old stamp differed.  A face id at or above F is ignored.  Integer atomics only: the counts are
+ * the same from run to run.  F = 0 is a success that launches nothing. */
+int gsr_raster_count_faces(const uint64_t* keys, int32_t H, int32_t W, int64_t F, int32_t stamp_value, int32_t* stamp,
+                           int32_t* counts, void* stream);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # instead of copying it over the in-tree library
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")
 
-ABI_VERSION = 41
+ABI_VERSION = 42
 
 
 class GsrParams(C.Structure):
@@ -92,6 +92,12 @@ class GsrCullView(C.Structure):
     """One row of the view table of ``gsr_cull_view_counts`` (include/gsr.h, ABI v41; mesh.py): 96 bytes."""
     _fields_ = [("mask", C.c_void_p), ("depth", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32),
                 ("fx", C.c_float), ("fy", C.c_float), ("world_to_view", C.c_float * 16)]
+
+
+# the mesh rasterizer (include/gsr.h, ABI v42; mesh.py): image limits, the two launch constants and the flags
+RASTER_MAX_SIDE = 16384
+RASTER_LANE_PIXELS, RASTER_DRAIN_WAVES = 16, 256
+RASTER_CLEAR, RASTER_CULL_BACKFACES, RASTER_NO_LOAD_SKIP = 1, 2, 4
 
 
 class GsrGrow(C.Structure):
@@ -369,6 +375,14 @@ SYMBOLS = {
                              [C.c_void_p] * 3),
     "gsr_cull_face_keep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 3),
     "gsr_mask_dilate": (C.c_int, [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p] * 3),
+    # rasterizing a mesh from a camera: z-buffer of (depth, face) keys, its resolve, per-face view counts
+    # (csrc/mesh_raster.hip; mesh.rasterize_mesh, mesh.face_view_counts, mesh.cull_invisible_faces)
+    "gsr_raster_queue_bytes": (C.c_size_t, [C.c_int64]),
+    "gsr_raster_view": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(GsrCullView), C.c_float, C.c_int32,
+                                  C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "gsr_raster_resolve": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsr_raster_count_faces": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
 }
 
 _lib = None

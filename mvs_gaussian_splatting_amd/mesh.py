@@ -25,6 +25,14 @@ every view that holds it, the unbounded ones drop what no camera saw.  ``vertex_
 every view and counts, per vertex, the views whose image holds it and those that see it (mask, depth map);
 ``cull_mesh_by_views`` is the rule on those counts and the same compaction; ``dilate_mask`` is the masks' dilation
 (``csrc/mesh_cull.hip`` behind ``gsr_cull_view_counts``, ``gsr_cull_face_keep``, ``gsr_mask_dilate``).
+
+    depth, face_id = rasterize_mesh(vertices, faces, camera)
+    vertices, faces, colors = cull_invisible_faces(vertices, faces, colors, cameras=cameras, min_views=1)
+
+Looking at the mesh itself: ``rasterize_mesh`` draws it from a camera into a z-buffer with a face id per pixel,
+``face_normal_map`` turns the ids into a normal picture, ``face_view_counts`` counts the views in which a face owns a pixel
+and ``cull_invisible_faces`` removes the faces no view sees -- inner walls and back layers that vertex tests keep
+(``csrc/mesh_raster.hip`` behind ``gsr_raster_view``, ``gsr_raster_resolve``, ``gsr_raster_count_faces``).
 """
 from __future__ import annotations
 
@@ -618,5 +626,215 @@ def cull_mesh_by_views(vertices: torch.Tensor, faces: torch.Tensor, colors: Opti
     return result(_compact_kept(lib, vertices_c, colors_c, faces_c, keep, status, "cull_mesh_by_views"), in_view, visible)
 
 
+def _raster_scalars(near, **flags) -> float:
+    if isinstance(near, bool) or not isinstance(near, (int, float)) or not math.isfinite(near):
+        raise ValueError(f"near must be a finite float, got {near!r}")
+    if not near > 0:
+        raise ValueError(f"near must be positive, got {near!r}")
+    for name, v in flags.items():
+        if not isinstance(v, bool):
+            raise ValueError(f"{name} must be a bool, got {v!r}")
+    return float(near)
+
+
+def _raster_rows(cameras):
+    """The host rows of the cameras, checked -> a list of ``_lib.GsrCullView``."""
+    try:
+        cameras = list(cameras)
+    except TypeError:
+        raise ValueError(f"cameras must be a sequence of cameras, got {type(cameras)}") from None
+    from .mvs import _focal
+    rows = []
+    for k, cam in enumerate(cameras):
+        H, W, fx, fy = _focal(cam)
+        if H * W > 2 ** 28 or max(H, W) > _lib.RASTER_MAX_SIDE:
+            raise ValueError(f"camera {k}: an image of {W} x {H} exceeds 2^28 pixels or 2^14 a side")
+        M = cam.world_view_transform.detach().to(device="cpu", dtype=torch.float32)
+        if tuple(M.shape) != (4, 4):
+            raise ValueError(f"camera {k}: world_view_transform must be 4 x 4, got {tuple(M.shape)}")
+        row = _lib.GsrCullView()
+        row.width, row.height, row.fx, row.fy = W, H, fx, fy
+        row.world_to_view[:] = M.reshape(-1).tolist()
+        rows.append(row)
+    return rows
+
+
+class _RasterWorkspace:
+    """The key buffer and the queue of the rasterizer for a mesh of F faces and images of up to ``pixels`` pixels."""
+
+    def __init__(self, lib, F: int, pixels: int, dev):
+        self.queue_bytes = int(lib.gsr_raster_queue_bytes(F))
+        self.queue = torch.empty(self.queue_bytes, dtype=torch.uint8, device=dev)
+        self.keys = torch.empty(max(pixels, 1), dtype=torch.int64, device=dev)
+
+    def head(self):
+        """(queued, dropped, bad faces) of the last view: a read-back."""
+        return self.queue[:12].view(torch.int32).tolist()
+
+
+def _raster_view(lib, ws, vertices_c, faces_c, row, near: float, flags: int, stream, view_scratch=None) -> None:
+    _lib.check(lib.gsr_raster_view(vertices_c.data_ptr(), int(vertices_c.shape[0]), faces_c.data_ptr(),
+                                   int(faces_c.shape[0]), C.byref(row), near, flags, ws.keys.data_ptr(), ws.queue.data_ptr(),
+                                   ws.queue_bytes, None if view_scratch is None else view_scratch.data_ptr(), stream),
+               "gsr_raster_view")
+
+
+def rasterize_mesh(vertices: torch.Tensor, faces: torch.Tensor, camera, *, near: float = 0.2, cull_backfaces: bool = False,
+                   stats: bool = False):
+    """Rasterize a mesh from ``camera`` -> ``(depth float32 [H,W], face_id int32 [H,W])`` on the device of ``vertices``
+    (float32 ``[V,3]``, ``faces`` int32 ``[F,3]``, on a ROCm GPU), with ``stats=True`` also ``{"dropped": n,
+    "bad_faces": m}`` (csrc/mesh_raster.hip).
+
+    ``depth`` is the view-space z of the nearest surface at each pixel centre, 0 where there is none (the convention of
+    ``render(return_depth=True)``); ``face_id`` is the face that owns the pixel, -1 where there is none; at equal depth
+    the smallest face index owns it.  The rule (csrc/mesh_raster_math.h): corners through ``world_view_transform`` in
+    float32; faces clipped against ``z = near``; ``u = fx xv / zv + (W - 1) / 2`` snapped to 1/256 pixel; coverage by
+    exact integer edge functions with the top-left rule, so that two faces sharing an edge cover every centre on it
+    exactly once; depth interpolated perspective-correctly in float64 and rounded to float32 once.  Both windings are
+    drawn unless ``cull_backfaces``.  The result does not depend on the order of the faces and is the same bits from run
+    to run.
+
+    Limits: an image of at most 2^14 pixels a side; a piece of a face with a corner farther than 2^21 pixels from the
+    image's origin is dropped and counted (``stats``: ``dropped``; a read-back made only then), as is a face with an index
+    outside ``0..V-1`` (``bad_faces``).  ``F == 0``: zeros and -1.  Everything runs on the current stream."""
+    V, F = _check_mesh(vertices, faces, None, "rasterize_mesh")
+    near = _raster_scalars(near, cull_backfaces=cull_backfaces, stats=stats)
+    row, = _raster_rows([camera])
+    _need_gpu(vertices, "rasterize_mesh")
+    lib, dev = _lib.load(), vertices.device
+    H, W = row.height, row.width
+    vertices_c, faces_c = vertices.detach().contiguous(), faces.detach().contiguous()
+    depth = torch.empty((H, W), dtype=torch.float32, device=dev)
+    face_id = torch.empty((H, W), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ws = _RasterWorkspace(lib, F, H * W, dev)
+        flags = _lib.RASTER_CLEAR | (_lib.RASTER_CULL_BACKFACES if cull_backfaces else 0)
+        _raster_view(lib, ws, vertices_c, faces_c, row, near, flags, stream)
+        _lib.check(lib.gsr_raster_resolve(ws.keys.data_ptr(), H, W, depth.data_ptr(), face_id.data_ptr(), stream),
+                   "gsr_raster_resolve")
+        if stats:
+            _, dropped, bad = ws.head()
+            return depth, face_id, {"dropped": dropped, "bad_faces": bad}
+    return depth, face_id
+
+
+def face_normal_map(vertices: torch.Tensor, faces: torch.Tensor, face_id: torch.Tensor, camera) -> torch.Tensor:
+    """The view-space unit normal of the face that owns each pixel -> float32 ``[3,H,W]``: ``(b - a) x (c - a)`` of the
+    face's corners in view space, normalised, flipped so that it points towards the camera (``n . a <= 0``), and 0 where
+    ``face_id < 0`` or the face has no area.  ``face_id``: int32 ``[H,W]`` as ``rasterize_mesh`` gives it.  Plain torch
+    gathers on the device of ``vertices``: this one is not hot."""
+    V, F = _check_mesh(vertices, faces, None, "face_normal_map")
+    row, = _raster_rows([camera])
+    dev = vertices.device
+    if not isinstance(face_id, torch.Tensor) or face_id.dtype != torch.int32 or face_id.device != dev \
+            or tuple(face_id.shape) != (row.height, row.width):
+        raise ValueError(f"face_id must be an int32 [{row.height},{row.width}] tensor on {dev}, got "
+                         f"{getattr(face_id, 'dtype', type(face_id))} {tuple(getattr(face_id, 'shape', ()))} on "
+                         f"{getattr(face_id, 'device', None)}")
+    out = torch.zeros((3, row.height, row.width), dtype=torch.float32, device=dev)
+    if F == 0:
+        return out
+    M = camera.world_view_transform.detach().to(device=dev, dtype=torch.float32)
+    hit = (face_id >= 0) & (face_id < F)
+    corners = vertices.detach()[faces.detach()[face_id[hit].to(torch.int64)].to(torch.int64)]          # [n,3,3]
+    corners = corners @ M[:3, :3] + M[3, :3]
+    a = corners[:, 0]
+    n = torch.cross(corners[:, 1] - a, corners[:, 2] - a, dim=1)
+    n = torch.where(((n * a).sum(1) > 0)[:, None], -n, n)
+    length = n.norm(dim=1, keepdim=True)
+    n = torch.where(length > 0, n / length.clamp_min(1e-38), torch.zeros_like(n))
+    out.permute(1, 2, 0)[hit] = n
+    return out
+
+
+def _check_face_counts(counts, F: int, dev) -> None:
+    if counts is not None and (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32
+                               or tuple(counts.shape) != (F,) or counts.device != dev or not counts.is_contiguous()):
+        raise ValueError(f"counts must be a contiguous int32 [{F}] tensor on {dev}")
+
+
+def _count_face_views(vertices, faces, rows, near: float, counts):
+    """The launches of ``face_view_counts`` for the rows of ``_raster_rows``, on a device mesh."""
+    F, dev = int(faces.shape[0]), vertices.device
+    if counts is None:
+        counts = torch.zeros(F, dtype=torch.int32, device=dev)
+    if F == 0 or not rows:
+        return counts
+    lib = _lib.load()
+    vertices_c, faces_c = vertices.detach().contiguous(), faces.detach().contiguous()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ws = _RasterWorkspace(lib, F, max(r.height * r.width for r in rows), dev)        # one key buffer for every view
+        stamp = torch.zeros(F, dtype=torch.int32, device=dev)
+        for k, row in enumerate(rows):
+            _raster_view(lib, ws, vertices_c, faces_c, row, near, _lib.RASTER_CLEAR, stream)
+            _lib.check(lib.gsr_raster_count_faces(ws.keys.data_ptr(), row.height, row.width, F, k + 1, stamp.data_ptr(),
+                                                  counts.data_ptr(), stream), "gsr_raster_count_faces")
+    return counts
+
+
+def face_view_counts(vertices: torch.Tensor, faces: torch.Tensor, cameras, *, near: float = 0.2,
+                     counts: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """In how many views each face owns at least one pixel -> int32 ``[F]`` on the device of the mesh (a ROCm GPU).
+
+    Every camera rasterizes the whole mesh as ``rasterize_mesh`` does (one key buffer, reused from view to view) and
+    every face that owns a pixel of the result -- nearest at that pixel centre, smallest index at equal depth -- counts
+    once for that view.  A face that is hidden behind others, covers no pixel centre or lies outside every image counts
+    nowhere.  ``counts``: an int32 ``[F]`` tensor the views are added into (and that is
+    returned), so that views can be fed in chunks; counts over chunks equal counts over one call.  Integer atomics only:
+    the same counts from run to run.  Nothing is read back; everything runs on the current stream."""
+    V, F = _check_mesh(vertices, faces, None, "face_view_counts")
+    near = _raster_scalars(near)
+    rows = _raster_rows(cameras)
+    _check_face_counts(counts, F, vertices.device)
+    _need_gpu(vertices, "face_view_counts")
+    return _count_face_views(vertices, faces, rows, near, counts)
+
+
+def cull_invisible_faces(vertices: torch.Tensor, faces: torch.Tensor, colors: Optional[torch.Tensor] = None, *, cameras,
+                         min_views: int = 1, near: float = 0.2, counts: Optional[torch.Tensor] = None,
+                         return_counts: bool = False):
+    """Remove the faces that too few views see -> ``(vertices float32 [V',3], faces int32 [F',3], colors float32 [V',3] or
+    None)``, with ``return_counts=True`` also the ``face_view_counts`` of the input faces; new tensors on the same device
+    (csrc/mesh_raster.hip).
+
+    With ``n = face_view_counts(vertices, faces, cameras, near=near, counts=counts)`` a face is kept when
+    ``n >= min_views``; then the vertices that no kept face refers to go as well.  ``min_views=1`` removes what no view
+    sees: inner walls, shells inside closed objects, the back of a TSDF's truncation band -- by the mesh's own z-buffer,
+    so it needs neither the trained model nor a depth tolerance.  ``counts``: counts of earlier chunks of views to add
+    to; ``cameras`` may then be empty.
+
+    Kept vertices and faces stay in their original order; the kept vertex and colour rows are bit-copies, the kept faces
+    are re-indexed.  Nothing is kept: ``[0,3]`` tensors.  One host read-back (``V'`` and ``F'``, with the check that every
+    face index lies in ``0..V-1``, else ``GsrError``).  ``F == 0`` makes no native call.  There is no CPU path."""
+    V, F = _check_mesh(vertices, faces, colors, "cull_invisible_faces")
+    if isinstance(min_views, bool) or not isinstance(min_views, int) or not 0 <= min_views < 2 ** 31:
+        raise ValueError(f"min_views must be a non-negative int that fits an int32, got {min_views!r}")
+    if not isinstance(return_counts, bool):
+        raise ValueError(f"return_counts must be a bool, got {return_counts!r}")
+    near = _raster_scalars(near)
+    rows = _raster_rows(cameras)
+    dev = vertices.device
+    _check_face_counts(counts, F, dev)
+    _need_gpu(vertices, "cull_invisible_faces")
+
+    def result(mesh, n):
+        if mesh is None:
+            mesh = (torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty((0, 3), dtype=torch.int32, device=dev),
+                    None if colors is None else torch.empty((0, 3), dtype=torch.float32, device=dev))
+        return mesh + (n,) if return_counts else mesh
+
+    n = _count_face_views(vertices, faces, rows, near, counts)
+    if F == 0:
+        return result(None, n)
+    lib = _lib.load()
+    vertices_c, faces_c = vertices.detach().contiguous(), faces.detach().contiguous()
+    colors_c = None if colors is None else colors.detach().contiguous()
+    keep = (n >= min_views).to(torch.uint8)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    return result(_compact_kept(lib, vertices_c, colors_c, faces_c, keep, status, "cull_invisible_faces"), n)
+
+
 __all__ = ["connected_components", "clean_mesh", "simplify_mesh", "dilate_mask", "vertex_view_counts",
-           "cull_mesh_by_views"]
+           "cull_mesh_by_views", "rasterize_mesh", "face_normal_map", "face_view_counts", "cull_invisible_faces"]
