@@ -13,11 +13,13 @@
 //               sel_abs = accum_abs / denom (NaN -> 0) >= abs_thr; clone and prune as without it
 //               (the screen-size test of :762 always reads the zeros that densification_postfix has just stored, :503)
 //   positions : exclusive scans (block totals -> block offsets -> in-block) of the four flag classes
-//   gather    : dst row <- src row for kept / clone / child rows (moments: zeros for the new rows, :458-459)
+//   gather    : dst row <- src row for kept / clone / child rows (moments: zeros for the new rows, :458-459), by
+//               densify_fork.hip's gather kernel (launch_gather_rows)
 //   children  : xyz = R(rotation) (exp(scaling) * noise) + xyz ;  scaling = log(exp(scaling) / (0.8 * 2))
 #include "gsr_common.h"
 #include "gsr_entry.h"
 #include "gsr_launch.h"
+#include "row_plan.h"
 
 namespace gsr {
 
@@ -32,9 +34,6 @@ __global__ __launch_bounds__(DN_BLOCK) void densify_plan_kernel(int P, const flo
                                                                  float min_opacity, float ws_limit, int use_ws,
                                                                  uint8_t* __restrict__ flags,
                                                                  uint32_t* __restrict__ block_counts, int stride) {
-  __shared__ uint32_t cnt[4];
-  if (threadIdx.x < 4) cnt[threadIdx.x] = 0;
-  __syncthreads();
   const int i = blockIdx.x * DN_BLOCK + threadIdx.x;
   uint8_t f = 0;
   if (i < P) {
@@ -62,13 +61,7 @@ __global__ __launch_bounds__(DN_BLOCK) void densify_plan_kernel(int P, const flo
     if (split) f |= DN_SPLIT_SEL;
     flags[i] = f;
   }
-#pragma unroll
-  for (int b = 0; b < 4; ++b) {
-    const uint64_t m = __builtin_amdgcn_ballot_w64((f >> b) & 1);
-    if ((threadIdx.x & (WAVE - 1)) == 0 && m) atomicAdd(&cnt[b], (uint32_t)__builtin_popcountll(m));
-  }
-  __syncthreads();
-  if (threadIdx.x < 4) block_counts[(size_t)threadIdx.x * stride + blockIdx.x] = cnt[threadIdx.x];
+  block_count_classes<4>(f, block_counts, stride);
 }
 
 // pos[c][i] = output row of Gaussian i in class c (keep / clone / child), or -1; sel_rank[i] = rank among the
@@ -76,45 +69,12 @@ __global__ __launch_bounds__(DN_BLOCK) void densify_plan_kernel(int P, const flo
 __global__ __launch_bounds__(DN_BLOCK) void densify_positions_kernel(int P, const uint8_t* __restrict__ flags,
                                                                       const uint32_t* __restrict__ block_offs, int stride,
                                                                       int32_t* __restrict__ pos) {
-  __shared__ uint32_t wave_tot[4][DN_BLOCK / WAVE];
   const int i = blockIdx.x * DN_BLOCK + threadIdx.x;
-  const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-  const uint8_t f = i < P ? flags[i] : 0;
-  uint32_t rank[4];
-#pragma unroll
-  for (int b = 0; b < 4; ++b) {
-    const uint64_t m = __builtin_amdgcn_ballot_w64((f >> b) & 1);
-    rank[b] = (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_tot[b][wid] = (uint32_t)__builtin_popcountll(m);
-  }
-  __syncthreads();
+  int32_t rank[4];
+  block_rank_classes<4>(i < P ? flags[i] : 0, block_offs, stride, rank);
   if (i >= P) return;
 #pragma unroll
-  for (int b = 0; b < 4; ++b) {
-    uint32_t base = block_offs[(size_t)b * stride + blockIdx.x];
-    for (int w = 0; w < wid; ++w) base += wave_tot[b][w];
-    pos[(size_t)b * P + i] = ((f >> b) & 1) ? (int32_t)(base + rank[b]) : -1;
-  }
-}
-
-// One element of one row per thread; rows are `w` floats wide.  zero_new: the appended rows receive zeros (Adam
-// moments of new points, :458-459) instead of copies.
-__global__ void densify_gather_rows_kernel(size_t total, int w, int P, const float* __restrict__ src,
-                                           const int32_t* __restrict__ pos, uint32_t n_keep, uint32_t n_clone,
-                                           uint32_t n_child, int zero_new, float* __restrict__ dst) {
-  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= total) return;
-  const uint32_t i = (uint32_t)(e / (size_t)w), c = (uint32_t)(e - (size_t)i * w);
-  const int32_t pk = pos[i], pc = pos[(size_t)P + i], ph = pos[2 * (size_t)P + i];
-  if (pk < 0 && pc < 0 && ph < 0) return;
-  const float v = src[e];
-  const float nv = zero_new ? 0.0f : v;
-  if (pk >= 0) dst[(size_t)pk * w + c] = v;
-  if (pc >= 0) dst[((size_t)n_keep + pc) * w + c] = nv;
-  if (ph >= 0) {
-    dst[((size_t)n_keep + n_clone + ph) * w + c] = nv;
-    dst[((size_t)n_keep + n_clone + n_child + ph) * w + c] = nv;
-  }
+  for (int b = 0; b < 4; ++b) pos[(size_t)b * P + i] = rank[b];
 }
 
 __global__ void densify_split_children_kernel(int P, const float* __restrict__ xyz, const float* __restrict__ scaling,
@@ -149,60 +109,29 @@ __global__ void densify_split_children_kernel(int P, const float* __restrict__ x
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------
-// counts = {kept originals, kept clones, kept children per copy, split-selected}; the four counter arrays (and their
-// offsets) lie scan_array_stride(nblocks) words apart: launch_scan_block_sums needs every one of them aligned
-struct DensifyLayout {
-  size_t flags, block_counts, block_offs, totals, pos, bytes;
-  int nblocks;
-  explicit DensifyLayout(int P);
+// counts = {kept originals, kept clones, kept children per copy, split-selected}; behind the plan's head, pos[4][P]
+struct DensifyLayout : RowPlanLayout {
+  size_t pos;
+  explicit DensifyLayout(int P) : RowPlanLayout(P, 4) { pos = bytes; bytes = align_up(pos + 4 * 4 * rows, 256); }
+  int32_t* pos_of(const void* ws) const { return at<int32_t>(ws, pos); }
 };
-DensifyLayout::DensifyLayout(int P) {
-  nblocks = (P + DN_BLOCK - 1) / DN_BLOCK;
-  if (nblocks < 1) nblocks = 1;
-  size_t o = 0;
-  flags = o;        o = align_up(o + (size_t)(P > 0 ? P : 1), 256);
-  block_counts = o; o = align_up(o + 4 * 4 * (size_t)scan_array_stride(nblocks), 256);
-  block_offs = o;   o = align_up(o + 4 * 4 * (size_t)scan_array_stride(nblocks), 256);
-  totals = o;       o = align_up(o + 64, 256);
-  pos = o;          o = align_up(o + 4 * 4 * (size_t)(P > 0 ? P : 1), 256);
-  bytes = o;
-}
 
 static void launch_densify_plan(int P, const float* accum, const float* accum_abs, float abs_thr, const float* denom,
                                 const float* scaling, const float* opacity, float thr, float pde, float min_opacity, float ws_limit, int use_ws, void* ws,
                                 hipStream_t s) {
   const DensifyLayout L(P);
-  char* base = static_cast<char*>(ws);
-  uint8_t* flags = reinterpret_cast<uint8_t*>(base + L.flags);
-  uint32_t* counts = reinterpret_cast<uint32_t*>(base + L.block_counts);
-  uint32_t* offs = reinterpret_cast<uint32_t*>(base + L.block_offs);
-  uint32_t* totals = reinterpret_cast<uint32_t*>(base + L.totals);
-  int32_t* pos = reinterpret_cast<int32_t*>(base + L.pos);
-  const int nb = L.nblocks, stride = scan_array_stride(nb);
-  hipLaunchKernelGGL(densify_plan_kernel, dim3(nb), dim3(DN_BLOCK), 0, s, P, accum, accum_abs, abs_thr, denom, scaling,
-                     opacity, thr, pde,
-                     min_opacity, ws_limit, use_ws, flags, counts, stride);
-  launch_scan_block_sums(counts, offs, totals, counts + stride, offs + stride, totals + 1, nb, s);
-  launch_scan_block_sums(counts + 2 * stride, offs + 2 * stride, totals + 2, counts + 3 * stride, offs + 3 * stride,
-                         totals + 3, nb, s);
-  hipLaunchKernelGGL(densify_positions_kernel, dim3(nb), dim3(DN_BLOCK), 0, s, P, flags, offs, stride, pos);
-}
-
-static void launch_densify_gather_rows(int P, int w, const float* src, const void* ws, const uint32_t counts[4],
-                                       int zero_new, float* dst, hipStream_t s) {
-  const DensifyLayout L(P);
-  const int32_t* pos = reinterpret_cast<const int32_t*>(static_cast<const char*>(ws) + L.pos);
-  const size_t total = (size_t)P * w;
-  if (total == 0) return;
-  hipLaunchKernelGGL(densify_gather_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, total, w, P,
-                     src, pos, counts[0], counts[1], counts[2], zero_new, dst);
+  hipLaunchKernelGGL(densify_plan_kernel, dim3(L.nblocks), dim3(DN_BLOCK), 0, s, P, accum, accum_abs, abs_thr, denom,
+                     scaling, opacity, thr, pde, min_opacity, ws_limit, use_ws, L.flags_of(ws), L.block_counts_of(ws),
+                     L.stride);
+  launch_class_scans(L, ws, s);
+  hipLaunchKernelGGL(densify_positions_kernel, dim3(L.nblocks), dim3(DN_BLOCK), 0, s, P, L.flags_of(ws),
+                     L.block_offs_of(ws), L.stride, L.pos_of(ws));
 }
 
 static void launch_densify_split_children(int P, const float* xyz, const float* scaling, const float* rotation,
                                           const float* noise, const void* ws, const uint32_t counts[4], float* dst_xyz,
                                           float* dst_scaling, hipStream_t s) {
-  const DensifyLayout L(P);
-  const int32_t* pos = reinterpret_cast<const int32_t*>(static_cast<const char*>(ws) + L.pos);
+  const int32_t* pos = DensifyLayout(P).pos_of(ws);
   if (P == 0 || counts[2] == 0) return;
   hipLaunchKernelGGL(densify_split_children_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, xyz, scaling, rotation,
                      noise, pos, counts[0], counts[1], counts[2], counts[3], dst_xyz, dst_scaling);
@@ -232,9 +161,7 @@ int gsr_densify_plan_abs(int32_t P, const float* xyz_gradient_accum, const float
   launch_densify_plan(P, xyz_gradient_accum, xyz_gradient_accum_abs, abs_grad_threshold, denom, scaling_raw, opacity_raw,
                       grad_threshold, percent_dense_extent, min_opacity, max_world_scale, max_world_scale >= 0.0f ? 1 : 0, workspace, s);
   if (int rc = check(false, s, "densify_plan")) return rc;
-  GSR_HIP(hipMemcpyAsync(counts_host, static_cast<char*>(workspace) + L.totals, 16, hipMemcpyDeviceToHost, s));
-  GSR_HIP(hipStreamSynchronize(s));
-  return 0;
+  return read_class_totals(L, workspace, counts_host, s);
 }
 int gsr_densify_plan(int32_t P, const float* xyz_gradient_accum, const float* denom, const float* scaling_raw,
                      const float* opacity_raw, float grad_threshold, float percent_dense_extent, float min_opacity,
@@ -251,7 +178,12 @@ int gsr_densify_gather_rows(int32_t P, int32_t row_floats, const float* src, con
   if (!src || !workspace || !counts) return fail(GSR_E_BADARG, "NULL argument");
   if (!dst && counts[0] + counts[1] + counts[2] > 0) return fail(GSR_E_BADARG, "NULL dst");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  launch_densify_gather_rows(P, row_floats, src, workspace, counts, zero_new, dst, s);
+  // the fork's gather with two child copies: originals copy, clones and children copy or (zero_new: the Adam moments of
+  // new points, :458-459) receive zeros; no policy looks at a selected bit, so the flag bytes are not read
+  const DensifyLayout L(P);
+  const int pol_new = zero_new ? GSR_ROW_CONST : GSR_ROW_COPY;
+  launch_gather_rows(P, row_floats, src, L.flags_of(workspace), L.pos_of(workspace), counts, 2, GSR_ROW_COPY, pol_new,
+                     pol_new, 0.0f, dst, s);
   return check(false, s, "densify_gather_rows");
 }
 int gsr_densify_split_children(int32_t P, const float* xyz, const float* scaling_raw, const float* rotation_raw,

@@ -29,6 +29,7 @@
 #include "gsr_entry.h"
 #include "gsr_launch.h"
 #include "grow_common.h"
+#include "row_plan.h"
 
 namespace gsr {
 
@@ -49,9 +50,6 @@ __global__ __launch_bounds__(DF_BLOCK) void densify_fork_plan_kernel(int P, cons
                                                                       float pde, float min_opacity, float ws_limit,
                                                                       int use_ws, uint8_t* __restrict__ flags,
                                                                       uint32_t* __restrict__ block_counts, int stride) {
-  __shared__ uint32_t cnt[DF_NC];
-  if (threadIdx.x < DF_NC) cnt[threadIdx.x] = 0;
-  __syncthreads();
   const int i = blockIdx.x * DF_BLOCK + threadIdx.x;
   uint8_t f = 0;
   if (i < P) {
@@ -73,13 +71,7 @@ __global__ __launch_bounds__(DF_BLOCK) void densify_fork_plan_kernel(int P, cons
     if (sel) f |= DF_SEL;
     flags[i] = f;
   }
-#pragma unroll
-  for (int b = 0; b < DF_NC; ++b) {
-    const uint64_t m = __builtin_amdgcn_ballot_w64((f >> b) & 1);
-    if ((threadIdx.x & (WAVE - 1)) == 0 && m) atomicAdd(&cnt[b], (uint32_t)__builtin_popcountll(m));
-  }
-  __syncthreads();
-  if (threadIdx.x < DF_NC) block_counts[(size_t)threadIdx.x * stride + blockIdx.x] = cnt[threadIdx.x];
+  block_count_classes<DF_NC>(f, block_counts, stride);
 }
 
 // pos[c * P + i] = rank of row i in class c, or -1; sel_src[rank among the selected] = i
@@ -87,34 +79,22 @@ __global__ __launch_bounds__(DF_BLOCK) void densify_fork_positions_kernel(int P,
                                                                            const uint32_t* __restrict__ block_offs,
                                                                            int stride, int32_t* __restrict__ pos,
                                                                            int32_t* __restrict__ sel_src) {
-  __shared__ uint32_t wave_tot[DF_NC][DF_BLOCK / WAVE];
   const int i = blockIdx.x * DF_BLOCK + threadIdx.x;
-  const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-  const uint8_t f = i < P ? flags[i] : 0;
-  uint32_t rank[DF_NC];
-#pragma unroll
-  for (int b = 0; b < DF_NC; ++b) {
-    const uint64_t m = __builtin_amdgcn_ballot_w64((f >> b) & 1);
-    rank[b] = (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_tot[b][wid] = (uint32_t)__builtin_popcountll(m);
-  }
-  __syncthreads();
+  int32_t rank[DF_NC];
+  block_rank_classes<DF_NC>(i < P ? flags[i] : 0, block_offs, stride, rank);
   if (i >= P) return;
 #pragma unroll
-  for (int b = 0; b < DF_NC; ++b) {
-    uint32_t base = block_offs[(size_t)b * stride + blockIdx.x];
-    for (int w = 0; w < wid; ++w) base += wave_tot[b][w];
-    const int32_t r = ((f >> b) & 1) ? (int32_t)(base + rank[b]) : -1;
-    pos[(size_t)b * P + i] = r;
-    if (b == DF_NC - 1 && r >= 0) sel_src[r] = i;      // r < #selected <= P
-  }
+  for (int b = 0; b < DF_NC; ++b) pos[(size_t)b * P + i] = rank[b];
+  if (rank[DF_NC - 1] >= 0) sel_src[rank[DF_NC - 1]] = i;      // rank < #selected <= P
 }
 
 __device__ inline float splat_const(float, float c) { return c; }
 __device__ inline float4 splat_const(float4, float c) { return make_float4(c, c, c, c); }
 
 // One chunk (a float or a float4) of one source row per thread; every output role of the row gets its policy's value.
-// Non-selected originals always copy.  ncopies: children per split row (2 clone + split, 4 grow).
+// Non-selected originals always copy: the flag byte's DF_SEL bit is read only when pol_orig is not a copy, so a plan
+// whose flags have no such bit (densify.hip's) is served with pol_orig = GSR_ROW_COPY.  ncopies: children per split row
+// (2 clone + split, 4 grow).
 template <typename V>
 __global__ __launch_bounds__(256) void densify_fork_gather_kernel(size_t total, int wv, int P,
                                                                    const V* __restrict__ src,
@@ -127,7 +107,7 @@ __global__ __launch_bounds__(256) void densify_fork_gather_kernel(size_t total, 
   if (e >= total) return;
   const uint32_t i = (uint32_t)(e / (size_t)wv), c = (uint32_t)(e - (size_t)i * wv);
   const int32_t po = pos[i], pe = pos[(size_t)P + i], pc = pos[2 * (size_t)P + i];
-  const int o_pol = (flags[i] & DF_SEL) ? pol_orig : GSR_ROW_COPY;
+  const int o_pol = (pol_orig != GSR_ROW_COPY && (flags[i] & DF_SEL)) ? pol_orig : GSR_ROW_COPY;
   const bool w_o = po >= 0 && o_pol != GSR_ROW_SKIP, w_e = pe >= 0 && pol_extra != GSR_ROW_SKIP,
              w_c = pc >= 0 && pol_child != GSR_ROW_SKIP;
   if (!w_o && !w_e && !w_c) return;
@@ -260,54 +240,35 @@ __global__ __launch_bounds__(256) void densify_fork_rows_dir_kernel(ForkRowsArgs
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------
-// counts = {kept originals, kept clones / grown, kept children per copy, split-selected, selected}; the five counter
-// arrays (and their offsets) lie scan_array_stride(nblocks) words apart, each aligned for launch_scan_block_sums
-struct DensifyForkLayout {
-  size_t flags, block_counts, block_offs, totals, pos, sel_src, bytes;
-  int nblocks;
-  explicit DensifyForkLayout(int P);
+// counts = {kept originals, kept clones / grown, kept children per copy, split-selected, selected}; behind the plan's
+// head, pos[5][P] and sel_src[P]
+struct DensifyForkLayout : RowPlanLayout {
+  size_t pos, sel_src;
+  explicit DensifyForkLayout(int P) : RowPlanLayout(P, DF_NC) {
+    pos = bytes;
+    sel_src = align_up(pos + 4 * DF_NC * rows, 256);
+    bytes = align_up(sel_src + 4 * rows, 256);
+  }
+  int32_t* pos_of(const void* ws) const { return at<int32_t>(ws, pos); }
+  int32_t* sel_src_of(const void* ws) const { return at<int32_t>(ws, sel_src); }
 };
-DensifyForkLayout::DensifyForkLayout(int P) {
-  nblocks = (P + DF_BLOCK - 1) / DF_BLOCK;
-  if (nblocks < 1) nblocks = 1;
-  const size_t Pn = (size_t)(P > 0 ? P : 1);
-  size_t o = 0;
-  flags = o;        o = align_up(o + Pn, 256);
-  block_counts = o; o = align_up(o + 4 * DF_NC * (size_t)scan_array_stride(nblocks), 256);
-  block_offs = o;   o = align_up(o + 4 * DF_NC * (size_t)scan_array_stride(nblocks), 256);
-  totals = o;       o = align_up(o + 64, 256);
-  pos = o;          o = align_up(o + 4 * DF_NC * Pn, 256);
-  sel_src = o;      o = align_up(o + 4 * Pn, 256);
-  bytes = o;
-}
 
 static void launch_densify_fork_plan(int P, const float* accum, const float* denom, const float* scaling,
                                      const float* opacity, const float* split_scale, float thr, float pde,
                                      float min_opacity, float ws_limit, int use_ws, void* ws, hipStream_t s) {
   const DensifyForkLayout L(P);
-  char* base = static_cast<char*>(ws);
-  uint8_t* flags = reinterpret_cast<uint8_t*>(base + L.flags);
-  uint32_t* counts = reinterpret_cast<uint32_t*>(base + L.block_counts);
-  uint32_t* offs = reinterpret_cast<uint32_t*>(base + L.block_offs);
-  uint32_t* totals = reinterpret_cast<uint32_t*>(base + L.totals);
-  int32_t* pos = reinterpret_cast<int32_t*>(base + L.pos);
-  int32_t* sel_src = reinterpret_cast<int32_t*>(base + L.sel_src);
-  const int nb = L.nblocks, st = scan_array_stride(nb);
-  hipLaunchKernelGGL(densify_fork_plan_kernel, dim3(nb), dim3(DF_BLOCK), 0, s, P, accum, denom, scaling, opacity,
-                     split_scale, thr, pde, min_opacity, ws_limit, use_ws, flags, counts, st);
-  launch_scan_block_sums(counts, offs, totals, counts + st, offs + st, totals + 1, nb, s);
-  launch_scan_block_sums(counts + 2 * st, offs + 2 * st, totals + 2, counts + 3 * st, offs + 3 * st, totals + 3, nb, s);
-  launch_scan_block_sums(counts + 4 * st, offs + 4 * st, totals + 4, nullptr, nullptr, nullptr, nb, s);
-  hipLaunchKernelGGL(densify_fork_positions_kernel, dim3(nb), dim3(DF_BLOCK), 0, s, P, flags, offs, st, pos, sel_src);
+  hipLaunchKernelGGL(densify_fork_plan_kernel, dim3(L.nblocks), dim3(DF_BLOCK), 0, s, P, accum, denom, scaling, opacity,
+                     split_scale, thr, pde, min_opacity, ws_limit, use_ws, L.flags_of(ws), L.block_counts_of(ws),
+                     L.stride);
+  launch_class_scans(L, ws, s);
+  hipLaunchKernelGGL(densify_fork_positions_kernel, dim3(L.nblocks), dim3(DF_BLOCK), 0, s, P, L.flags_of(ws),
+                     L.block_offs_of(ws), L.stride, L.pos_of(ws), L.sel_src_of(ws));
 }
 
-static void launch_densify_fork_gather_rows(int P, int w, const float* src, const void* ws, const uint32_t counts[5],
-                                            int ncopies, int policy, float value, float* dst, hipStream_t s) {
-  const DensifyForkLayout L(P);
-  const char* base = static_cast<const char*>(ws);
-  const uint8_t* flags = reinterpret_cast<const uint8_t*>(base + L.flags);
-  const int32_t* pos = reinterpret_cast<const int32_t*>(base + L.pos);
-  const int po = policy & 3, pe = (policy >> 2) & 3, pc = (policy >> 4) & 3;
+// gsr_launch.h: the gather of this file's plan and of densify.hip's (whose pos holds the same first three classes)
+void launch_gather_rows(int P, int w, const float* src, const uint8_t* flags, const int32_t* pos,
+                        const uint32_t counts[3], int ncopies, int po, int pe, int pc, float value, float* dst,
+                        hipStream_t s) {
   const bool vec = (w & 3) == 0 && (((uintptr_t)src | (uintptr_t)dst) & 15u) == 0;
   const int wv = vec ? w / 4 : w;
   const size_t total = (size_t)P * wv;
@@ -325,11 +286,10 @@ static void launch_densify_fork_gather_rows(int P, int w, const float* src, cons
 static void launch_densify_fork_rows(const GsrDensifyFork& f, const void* ws, const uint32_t counts[5], float* xyz_out,
                                      float* scaling_out, float* conti_out, hipStream_t s) {
   const DensifyForkLayout L(f.P);
-  const char* base = static_cast<const char*>(ws);
   ForkRowsArgs a;
   a.f = f;
-  a.pos = reinterpret_cast<const int32_t*>(base + L.pos);
-  a.sel_src = reinterpret_cast<const int32_t*>(base + L.sel_src);
+  a.pos = L.pos_of(ws);
+  a.sel_src = L.sel_src_of(ws);
   a.n_orig = counts[0]; a.n_extra = counts[1]; a.n_child = counts[2]; a.n_split = counts[3]; a.n_sel = counts[4];
   a.xyz_out = xyz_out; a.scaling_out = scaling_out; a.conti_out = conti_out;
   if (a.n_sel == 0) return;
@@ -364,9 +324,7 @@ int gsr_densify_fork_plan(int32_t P, const float* xyz_gradient_accum, const floa
                            percent_dense_extent, min_opacity, max_world_scale, max_world_scale >= 0.0f ? 1 : 0,
                            workspace, s);
   if (int rc = check(false, s, "densify_fork_plan")) return rc;
-  GSR_HIP(hipMemcpyAsync(counts_host, static_cast<char*>(workspace) + L.totals, 20, hipMemcpyDeviceToHost, s));
-  GSR_HIP(hipStreamSynchronize(s));
-  return 0;
+  return read_class_totals(L, workspace, counts_host, s);
 }
 int gsr_densify_fork_gather_rows(int32_t P, int32_t row_floats, const float* src, const void* workspace,
                                  const uint32_t counts[5], int32_t grow_branch, int32_t policy, float value, float* dst,
@@ -378,7 +336,9 @@ int gsr_densify_fork_gather_rows(int32_t P, int32_t row_floats, const float* src
   if (!src || !workspace || !counts) return fail(GSR_E_BADARG, "NULL argument");
   if (!dst && counts[0] + counts[1] + counts[2] > 0) return fail(GSR_E_BADARG, "NULL dst");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  launch_densify_fork_gather_rows(P, row_floats, src, workspace, counts, grow_branch ? 4 : 2, policy, value, dst, s);
+  const DensifyForkLayout L(P);
+  launch_gather_rows(P, row_floats, src, L.flags_of(workspace), L.pos_of(workspace), counts, grow_branch ? 4 : 2,
+                     policy & 3, (policy >> 2) & 3, (policy >> 4) & 3, value, dst, s);
   return check(false, s, "densify_fork_gather_rows");
 }
 int gsr_densify_fork_rows(const GsrDensifyFork* f, const void* workspace, const uint32_t counts[5], float* xyz_out,

@@ -16,6 +16,7 @@
 #include "gsr_entry.h"
 #include "gsr_launch.h"
 #include "grow_common.h"
+#include "row_plan.h"
 
 namespace gsr {
 
@@ -55,9 +56,6 @@ __global__ __launch_bounds__(GR_BLOCK) void grow_plan_kernel(int P, const float*
                                                               const float* __restrict__ scaling, float thr, float pde,
                                                               int split_mode, uint8_t* __restrict__ flags,
                                                               uint32_t* __restrict__ block_counts, int stride) {
-  __shared__ uint32_t cnt[2];
-  if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
-  __syncthreads();
   const int i = blockIdx.x * GR_BLOCK + threadIdx.x;
   uint8_t f = 0;
   if (i < P) {
@@ -70,34 +68,20 @@ __global__ __launch_bounds__(GR_BLOCK) void grow_plan_kernel(int P, const float*
     f = (sel ? 1 : 0) | ((sel && big) ? 2 : 0);
     flags[i] = f;
   }
-#pragma unroll
-  for (int b = 0; b < 2; ++b) {
-    const uint64_t m = __builtin_amdgcn_ballot_w64((f >> b) & 1);
-    if ((threadIdx.x & (WAVE - 1)) == 0 && m) atomicAdd(&cnt[b], (uint32_t)__builtin_popcountll(m));
-  }
-  __syncthreads();
-  if (threadIdx.x < 2) block_counts[(size_t)threadIdx.x * stride + blockIdx.x] = cnt[threadIdx.x];
+  block_count_classes<2>(f, block_counts, stride);
 }
 
 __global__ __launch_bounds__(GR_BLOCK) void grow_positions_kernel(int P, const uint8_t* __restrict__ flags,
                                                                    const uint32_t* __restrict__ block_offs,
                                                                    int32_t* __restrict__ vidx, int32_t* __restrict__ src,
                                                                    uint8_t* __restrict__ selected) {
-  __shared__ uint32_t wave_tot[GR_WAVES];
   const int i = blockIdx.x * GR_BLOCK + threadIdx.x;
-  const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-  const bool sel = i < P && (flags[i] & 1);
-  const uint64_t m = __builtin_amdgcn_ballot_w64(sel);
-  const uint32_t rank = (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull));
-  if (lane == 0) wave_tot[wid] = (uint32_t)__builtin_popcountll(m);
-  __syncthreads();
+  int32_t j[1];      // the rank among the selected (class 0) alone: the virtual row
+  block_rank_classes<1>(i < P ? flags[i] : 0, block_offs, 0, j);
   if (i >= P) return;
-  uint32_t base = block_offs[blockIdx.x];
-  for (int w = 0; w < wid; ++w) base += wave_tot[w];
-  const int32_t j = sel ? (int32_t)(base + rank) : -1;
-  vidx[i] = j;
-  selected[i] = sel ? 1 : 0;
-  if (sel) src[j] = i;       // j < G <= P
+  vidx[i] = j[0];
+  selected[i] = j[0] >= 0 ? 1 : 0;
+  if (j[0] >= 0) src[j[0]] = i;       // j < G <= P
 }
 
 // ---- expand -------------------------------------------------------------------------------------------------------
@@ -359,36 +343,15 @@ __global__ __launch_bounds__(GR_BLOCK) void grow_fold_dirs_kernel(GsrGrow g, Gsr
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------
-struct GrowLayout {
-  size_t flags, block_counts, block_offs, totals, bytes;
-  int nblocks;
-  explicit GrowLayout(int P);
-};
-GrowLayout::GrowLayout(int P) {
-  nblocks = (P + GR_BLOCK - 1) / GR_BLOCK;
-  if (nblocks < 1) nblocks = 1;
-  size_t o = 0;
-  flags = o;        o = align_up(o + (size_t)(P > 0 ? P : 1), 256);
-  // two counter arrays scan_array_stride(nblocks) words apart, each aligned for launch_scan_block_sums
-  block_counts = o; o = align_up(o + 2 * 4 * (size_t)scan_array_stride(nblocks), 256);
-  block_offs = o;   o = align_up(o + 2 * 4 * (size_t)scan_array_stride(nblocks), 256);
-  totals = o;       o = align_up(o + 64, 256);
-  bytes = o;
-}
-
+// the plan's workspace is the shared head alone: classes {selected, selected & big}
 static void launch_grow_plan(int P, const float* accum, const float* denom, const float* scaling, float thr, float pde,
                              int split_mode, void* ws, int32_t* vidx, int32_t* src, uint8_t* selected, hipStream_t s) {
-  const GrowLayout L(P);
-  char* base = static_cast<char*>(ws);
-  uint8_t* flags = reinterpret_cast<uint8_t*>(base + L.flags);
-  uint32_t* counts = reinterpret_cast<uint32_t*>(base + L.block_counts);
-  uint32_t* offs = reinterpret_cast<uint32_t*>(base + L.block_offs);
-  uint32_t* totals = reinterpret_cast<uint32_t*>(base + L.totals);
-  const int nb = L.nblocks, stride = scan_array_stride(nb);
-  hipLaunchKernelGGL(grow_plan_kernel, dim3(nb), dim3(GR_BLOCK), 0, s, P, accum, denom, scaling, thr, pde, split_mode,
-                     flags, counts, stride);
-  launch_scan_block_sums(counts, offs, totals, counts + stride, offs + stride, totals + 1, nb, s);
-  hipLaunchKernelGGL(grow_positions_kernel, dim3(nb), dim3(GR_BLOCK), 0, s, P, flags, offs, vidx, src, selected);
+  const RowPlanLayout L(P, 2);
+  hipLaunchKernelGGL(grow_plan_kernel, dim3(L.nblocks), dim3(GR_BLOCK), 0, s, P, accum, denom, scaling, thr, pde,
+                     split_mode, L.flags_of(ws), L.block_counts_of(ws), L.stride);
+  launch_class_scans(L, ws, s);
+  hipLaunchKernelGGL(grow_positions_kernel, dim3(L.nblocks), dim3(GR_BLOCK), 0, s, P, L.flags_of(ws),
+                     L.block_offs_of(ws), vidx, src, selected);
 }
 
 static unsigned row_grid(size_t total) {
@@ -444,7 +407,7 @@ using namespace gsr;
 
 extern "C" {
 
-size_t gsr_grow_workspace_bytes(int32_t P) { return P < 0 ? 0 : GrowLayout(P).bytes; }
+size_t gsr_grow_workspace_bytes(int32_t P) { return P < 0 ? 0 : RowPlanLayout(P, 2).bytes; }
 int gsr_grow_plan(int32_t P, const float* xyz_gradient_accum, const float* denom, const float* scaling_raw,
                   float grad_threshold, float percent_dense_extent, int32_t mode, void* workspace, size_t workspace_bytes,
                   int32_t* vidx, int32_t* src, uint8_t* selected, uint32_t counts_host[2], void* stream) {
@@ -455,7 +418,7 @@ int gsr_grow_plan(int32_t P, const float* xyz_gradient_accum, const float* denom
   if (!xyz_gradient_accum || !denom || !scaling_raw || !workspace || !vidx || !src || !selected)
     return fail(GSR_E_BADARG, "NULL argument");
   if (!aligned({workspace}, 255u)) return fail(GSR_E_ALIGN, "workspace must be 256-byte aligned");
-  const GrowLayout L(P);
+  const RowPlanLayout L(P, 2);
   if (workspace_bytes < L.bytes) return fail(GSR_E_CAPACITY, "grow workspace too small");
   const int grow = (mode & (GSR_GROW_DIR | GSR_GROW_CONTINUOUS)) != 0;
   if (!grow && !(mode & (GSR_SPLIT_DISTANCE | GSR_SPLIT_SCALE))) return fail(GSR_E_BADARG, "mode selects no branch");
@@ -463,9 +426,7 @@ int gsr_grow_plan(int32_t P, const float* xyz_gradient_accum, const float* denom
   launch_grow_plan(P, xyz_gradient_accum, denom, scaling_raw, grad_threshold, percent_dense_extent, grow ? 0 : 1,
                    workspace, vidx, src, selected, s);
   if (int rc = check(false, s, "grow_plan")) return rc;
-  GSR_HIP(hipMemcpyAsync(counts_host, static_cast<char*>(workspace) + L.totals, 8, hipMemcpyDeviceToHost, s));
-  GSR_HIP(hipStreamSynchronize(s));
-  return 0;
+  return read_class_totals(L, workspace, counts_host, s);
 }
 
 static int grow_validate(const GsrGrow* g) {

@@ -1,6 +1,6 @@
 // The host-side launchers that cross a file boundary: those gsr_api.hip sequences into a frame (preprocess, binning,
 // render, the maps, launch_unpack_geom) and the few that one kernel file borrows from another (the scan and the pair
-// sort; launch_ssim_metric).  Each is defined next to its kernel, so that the translation units can be compiled with
+// sort; launch_ssim_metric; launch_gather_rows).  Each is defined next to its kernel, so that the translation units can be compiled with
 // different floating-point contraction settings.  A launcher with one caller in its own file is not declared here.
 #pragma once
 #include "gsr_common.h"
@@ -159,6 +159,15 @@ void launch_contribution(const MapFrame& f, const uint8_t* pixel_mask, int64_t* 
 // loss.hip, called by metrics.hip: forward-only SSIM of the evaluation path, one partial per 16x16 tile and channel, no
 // derivative maps
 void launch_ssim_metric(const float* x, const float* gt, int C, int H, int W, int clamp_flags, float* partials,
+                        hipStream_t s);
+
+// densify_fork.hip, called by densify.hip too: one gather of a densification plan.  Source row i (w floats) goes to
+// dst rows pos[i] (original), counts[0] + pos[P + i] (clone / grown) and counts[0] + counts[1] + j counts[2] + pos[2P + i]
+// (child copy j < ncopies), wherever that pos is not -1.  po / pe / pc: GSR_ROW_COPY, GSR_ROW_CONST (`value`) or
+// GSR_ROW_SKIP per role; po binds only the originals whose flag byte has the fork's selected bit, the others copy, and
+// with po = GSR_ROW_COPY flags is not read.  Bit copies only: no contraction setting can change its results.
+void launch_gather_rows(int P, int w, const float* src, const uint8_t* flags, const int32_t* pos,
+                        const uint32_t counts[3], int ncopies, int po, int pe, int pc, float value, float* dst,
                         hipStream_t s);
 
 // aux.hip: the unpack kernel behind gsr_debug_read_geom

@@ -38,13 +38,54 @@ FORK_FLAG = {"dirs_prob": "grow_dir", "conti_dirs": "continous_dir", "grow_dist"
 GROW, CLONE_SPLIT = "grow", "clone_split"
 
 
-def _rows(lib, P, src, ws, counts, n_out, zero_new, stream):
+def swap_rows_(model, attrs, new, moment) -> None:
+    """The optimizer surgery every change of the row count shares (``_prune_optimizer`` / ``cat_tensors_to_optimizer``,
+    ``:401-422``, ``:451-472``).  ``attrs``: ``{group name: model attribute}``; ``new``: ``{group name: new tensor}``;
+    ``moment``: maps an old ``exp_avg`` / ``exp_avg_sq`` tensor to the new one.
+
+    Every group of ``model.optimizer`` (if any) named in ``new`` gets a fresh ``nn.Parameter`` over the new tensor.  The
+    state dict of the old parameter always moves to the new one, whatever it holds: ``exp_avg`` and ``exp_avg_sq`` go
+    through ``moment`` where present, every other key (``step`` included) is carried over as it is, and no entry stays
+    behind under the dead parameter.  A tensor that no group owns keeps its kind (``nn.Parameter`` or plain tensor) and
+    its ``requires_grad``.  The model's attributes are then set."""
+    optimizer = getattr(model, "optimizer", None)
+    owned = {}
+    for group in optimizer.param_groups if optimizer is not None else ():
+        name = group.get("name")
+        if name not in new:
+            continue
+        old = group["params"][0]
+        owned[name] = group["params"][0] = nn.Parameter(new[name].requires_grad_(True))
+        stored = optimizer.state.pop(old, None)
+        if stored is not None:
+            for key in ("exp_avg", "exp_avg_sq"):
+                if key in stored:
+                    stored[key] = moment(stored[key])
+            optimizer.state[owned[name]] = stored
+    for k, a in attrs.items():
+        t, old = owned.get(k), getattr(model, a)
+        if t is None:
+            t = nn.Parameter(new[k], requires_grad=old.requires_grad) if isinstance(old, nn.Parameter) \
+                else new[k].requires_grad_(old.requires_grad)
+        setattr(model, a, t)
+
+
+def _gather(call, name, P, src, n_out):
+    """``call(row floats, src pointer, dst pointer)`` -- a ``gsr_densify_*gather_rows`` -- over one ``[P, ...]`` tensor
+    -> ``[n_out, ...]``.  A tensor without rows or without width (``_features_rest`` ``[P,0,3]`` at degree 0) has
+    nothing to gather: the library refuses ``row_floats <= 0``."""
     src = src.detach().contiguous()
     w = src.numel() // max(P, 1)
     dst = torch.empty((n_out,) + tuple(src.shape[1:]), dtype=torch.float32, device=src.device)
-    _lib.check(lib.gsr_densify_gather_rows(P, w, src.data_ptr(), ws.data_ptr(), counts, 1 if zero_new else 0,
-                                           dst.data_ptr(), stream), "gsr_densify_gather_rows")
+    if P > 0 and w > 0:
+        _lib.check(call(w, src.data_ptr(), dst.data_ptr()), name)
     return dst
+
+
+def _reset_stats(model, n_out, dev) -> None:
+    model.xyz_gradient_accum = torch.zeros((n_out, 1), dtype=torch.float32, device=dev)      # :501-503
+    model.denom = torch.zeros((n_out, 1), dtype=torch.float32, device=dev)
+    model.max_radii2D = torch.zeros((n_out,), dtype=torch.float32, device=dev)
 
 
 def _flag(obj, name) -> bool:
@@ -123,7 +164,6 @@ def densify_and_prune(model, max_grad: float, min_opacity: float, extent: float,
             raise TypeError(f"{k}: expected float32 with {P} rows")
     accum = model.xyz_gradient_accum.detach().to(torch.float32).contiguous()
     denom = model.denom.detach().to(torch.float32).contiguous()
-    optimizer = getattr(model, "optimizer", None)
     ws = torch.empty(max(lib.gsr_densify_workspace_bytes(P), 256), dtype=torch.uint8, device=dev)
     counts = (C.c_uint32 * 4)()
     with torch.cuda.device(dev):
@@ -147,53 +187,22 @@ def densify_and_prune(model, max_grad: float, min_opacity: float, extent: float,
         noise = noise.to(dev, torch.float32).contiguous()
         if tuple(noise.shape) != (2 * n_sel, 3):
             raise ValueError(f"noise must be [{2 * n_sel}, 3] (2 x split-selected), got {tuple(noise.shape)}")
-        new = {k: _rows(lib, P, t, ws, counts, n_out, False, stream) for k, t in params.items()}
+        def rows(t, zero_new):
+            return _gather(lambda w, src, dst: lib.gsr_densify_gather_rows(P, w, src, ws.data_ptr(), counts, zero_new, dst,
+                                                                           stream), "gsr_densify_gather_rows", P, t, n_out)
+        new = {k: rows(t, 0) for k, t in params.items()}
         _lib.check(lib.gsr_densify_split_children(P, params["xyz"].detach().contiguous().data_ptr(), scaling.data_ptr(),
                                                   params["rotation"].detach().contiguous().data_ptr(), noise.data_ptr(),
                                                   ws.data_ptr(), counts, new["xyz"].data_ptr(), new["scaling"].data_ptr(),
                                                   stream), "gsr_densify_split_children")
-        if optimizer is not None:
-            for group in optimizer.param_groups:
-                name = group.get("name")
-                if name not in new:
-                    continue
-                old = group["params"][0]
-                stored = optimizer.state.get(old, None)
-                if stored is not None and "exp_avg" in stored:
-                    stored["exp_avg"] = _rows(lib, P, stored["exp_avg"], ws, counts, n_out, True, stream)
-                    stored["exp_avg_sq"] = _rows(lib, P, stored["exp_avg_sq"], ws, counts, n_out, True, stream)
-                    del optimizer.state[old]
-                    group["params"][0] = nn.Parameter(new[name].requires_grad_(True))
-                    optimizer.state[group["params"][0]] = stored
-                else:
-                    group["params"][0] = nn.Parameter(new[name].requires_grad_(True))
-                new[name] = group["params"][0]
-    for k, a in GROUP_ATTR.items():
-        t, old = new[k], getattr(model, a)
-        if not isinstance(t, nn.Parameter):                      # no optimizer group owns it: keep the old kind
-            t = nn.Parameter(t, requires_grad=old.requires_grad) if isinstance(old, nn.Parameter) \
-                else t.requires_grad_(old.requires_grad)
-        setattr(model, a, t)
-    model.xyz_gradient_accum = torch.zeros((n_out, 1), dtype=torch.float32, device=dev)      # :501-503
-    model.denom = torch.zeros((n_out, 1), dtype=torch.float32, device=dev)
-    model.max_radii2D = torch.zeros((n_out,), dtype=torch.float32, device=dev)
+        swap_rows_(model, GROUP_ATTR, new, lambda m: rows(m, 1))          # new rows: zero moments (:458-459)
+    _reset_stats(model, n_out, dev)
     if getattr(model, "xyz_gradient_accum_abs", None) is not None:
         model.xyz_gradient_accum_abs = torch.zeros((n_out, 1), dtype=torch.float32, device=dev)
     if spatial_order:
         from .layout import reorder_gaussians_
         reorder_gaussians_(model)
     return {"points": n_out, "kept": n_keep, "cloned": n_clone, "split_selected": n_sel, "children_per_copy": n_child}
-
-
-def _fork_rows(lib, P, src, ws, counts, n_out, grow, policy, value, stream):
-    src = src.detach().contiguous()
-    w = src.numel() // max(P, 1)
-    dst = torch.empty((n_out,) + tuple(src.shape[1:]), dtype=torch.float32, device=src.device)
-    if P > 0 and w > 0:
-        _lib.check(lib.gsr_densify_fork_gather_rows(P, w, src.data_ptr(), ws.data_ptr(), counts, 1 if grow else 0,
-                                                    policy, float(value), dst.data_ptr(), stream),
-                   "gsr_densify_fork_gather_rows")
-    return dst
 
 
 def _fork_inputs(model, P):
@@ -252,7 +261,6 @@ def _densify_fork(model, max_grad, min_opacity, extent, max_screen_size, noise, 
     denom = model.denom.detach().to(torch.float32).contiguous()
     if accum.numel() != P or denom.numel() != P:
         raise ValueError("xyz_gradient_accum / denom need one value per Gaussian")
-    optimizer = getattr(model, "optimizer", None)
     ws = torch.empty(max(lib.gsr_densify_fork_workspace_bytes(P), 256), dtype=torch.uint8, device=dev)
     counts = (C.c_uint32 * 5)()
     with torch.cuda.device(dev):
@@ -305,7 +313,12 @@ def _densify_fork(model, max_grad, min_opacity, extent, max_screen_size, noise, 
             for k in ("split_distance", "split_scale"):
                 if k in src:
                     policy[k] = (_lib.ROW_POLICY(cp, cp, const), 0.0)
-        new = {k: _fork_rows(lib, P, t, ws, counts, n_out, grow, *policy[k], stream) for k, t in src.items()}
+        def rows(t, pol, value):
+            return _gather(lambda w, s, dst: lib.gsr_densify_fork_gather_rows(P, w, s, ws.data_ptr(), counts,
+                                                                              1 if grow else 0, pol, float(value), dst,
+                                                                              stream),
+                           "gsr_densify_fork_gather_rows", P, t, n_out)
+        new = {k: rows(t, *policy[k]) for k, t in src.items()}
         fk = _lib.GsrDensifyFork()
         fk.P, fk.mode = P, mode
         fk.num_dirs = int(model.num_dirs) if flags["grow_dir"] else 0
@@ -319,33 +332,10 @@ def _densify_fork(model, max_grad, min_opacity, extent, max_screen_size, noise, 
                                              new["scaling"].data_ptr(),
                                              new["conti_dirs"].data_ptr() if conti_reinit else None, stream),
                    "gsr_densify_fork_rows")
-        if optimizer is not None:
-            zero_new = _lib.ROW_POLICY(cp, const, const)                     # :458-459
-            for group in optimizer.param_groups:
-                name = group.get("name")
-                if name not in new:
-                    continue
-                old = group["params"][0]
-                stored = optimizer.state.get(old, None)
-                if stored is not None and "exp_avg" in stored:
-                    for key in ("exp_avg", "exp_avg_sq"):
-                        stored[key] = _fork_rows(lib, P, stored[key], ws, counts, n_out, grow, zero_new, 0.0, stream)
-                    del optimizer.state[old]
-                    group["params"][0] = nn.Parameter(new[name].requires_grad_(True))
-                    optimizer.state[group["params"][0]] = stored
-                else:
-                    group["params"][0] = nn.Parameter(new[name].requires_grad_(True))
-                new[name] = group["params"][0]
-    attrs = dict(GROUP_ATTR, **{k: FORK_ATTR[k] for k in learned})
-    for k, a in attrs.items():
-        t, old = new[k], getattr(model, a)
-        if not isinstance(t, nn.Parameter):                      # no optimizer group owns it: keep the old kind
-            t = nn.Parameter(t, requires_grad=old.requires_grad) if isinstance(old, nn.Parameter) \
-                else t.requires_grad_(old.requires_grad)
-        setattr(model, a, t)
-    model.xyz_gradient_accum = torch.zeros((n_out, 1), dtype=torch.float32, device=dev)      # :501-503
-    model.denom = torch.zeros((n_out, 1), dtype=torch.float32, device=dev)
-    model.max_radii2D = torch.zeros((n_out,), dtype=torch.float32, device=dev)
+        zero_new = _lib.ROW_POLICY(cp, const, const)                     # new rows: zero moments (:458-459)
+        swap_rows_(model, dict(GROUP_ATTR, **{k: FORK_ATTR[k] for k in learned}), new,
+                   lambda m: rows(m, zero_new, 0.0))
+    _reset_stats(model, n_out, dev)
     if spatial_order:
         from .layout import reorder_gaussians_
         reorder_gaussians_(model)

@@ -22,9 +22,8 @@ from __future__ import annotations
 from typing import Optional
 
 import torch
-from torch import nn
 
-from .densify import FORK_ATTR, GROUP_ATTR
+from .densify import FORK_ATTR, GROUP_ATTR, swap_rows_
 
 STATS_ATTR = ("xyz_gradient_accum", "denom", "max_radii2D", "xyz_gradient_accum_abs")
 
@@ -64,31 +63,9 @@ def _take_rows_(model, index: torch.Tensor, P: int) -> None:
         t = getattr(model, a, None)
         if isinstance(t, torch.Tensor) and t.dim() >= 1 and t.shape[0] == P and P > 0:
             attrs[k] = a
-    new = {k: getattr(model, a).detach()[index].contiguous() for k, a in attrs.items()}
-    optimizer = getattr(model, "optimizer", None)
-    owned = set()
-    if optimizer is not None:
-        for group in optimizer.param_groups:
-            name = group.get("name")
-            if name not in new:
-                continue
-            old = group["params"][0]
-            stored = optimizer.state.get(old, None)
-            group["params"][0] = nn.Parameter(new[name].requires_grad_(True))
-            if stored is not None:
-                for key in ("exp_avg", "exp_avg_sq"):
-                    if key in stored:
-                        stored[key] = stored[key][index].contiguous()
-                del optimizer.state[old]
-                optimizer.state[group["params"][0]] = stored
-            new[name] = group["params"][0]
-            owned.add(name)
-    for k, a in attrs.items():
-        t, old = new[k], getattr(model, a)
-        if k not in owned:
-            t = nn.Parameter(t, requires_grad=old.requires_grad) if isinstance(old, nn.Parameter) \
-                else t.requires_grad_(old.requires_grad)
-        setattr(model, a, t)
+    def take(t):
+        return t.detach()[index].contiguous()
+    swap_rows_(model, attrs, {k: take(getattr(model, a)) for k, a in attrs.items()}, take)
     for a in STATS_ATTR:
         t = getattr(model, a, None)
         if isinstance(t, torch.Tensor) and t.dim() >= 1 and t.shape[0] == P:

@@ -17,10 +17,9 @@ from __future__ import annotations
 from typing import Optional
 
 import torch
-from torch import nn
 
 from . import _lib
-from .densify import GROUP_ATTR, is_fork
+from .densify import GROUP_ATTR, is_fork, swap_rows_
 
 DRAW_HIGH = 2 ** 63 - 1      # torch.randint's largest exclusive bound: draws are uniform in [0, 2^63 - 1)
 
@@ -258,32 +257,13 @@ def add_new_gs(model, cap_max: int, generator: Optional[torch.Generator] = None,
     _zero_moments(model, src, found.reshape(-1))
     new = {k: torch.cat([getattr(model, a).detach(), getattr(model, a).detach()[src]], dim=0)
            for k, a in GROUP_ATTR.items()}
-    optimizer = getattr(model, "optimizer", None)
-    if optimizer is not None:
-        for group in optimizer.param_groups:
-            name = group.get("name")
-            if name not in new:
-                continue
-            old = group["params"][0]
-            stored = optimizer.state.get(old, None)
-            group["params"][0] = nn.Parameter(new[name].requires_grad_(True))
-            if stored is not None and "exp_avg" in stored:
-                for key in ("exp_avg", "exp_avg_sq"):
-                    m = stored[key]
-                    stored[key] = torch.cat([m, torch.zeros((n,) + tuple(m.shape[1:]), dtype=m.dtype, device=m.device)])
-                del optimizer.state[old]
-                optimizer.state[group["params"][0]] = stored
-            new[name] = group["params"][0]
-    for k, a in GROUP_ATTR.items():
-        t, old = new[k], getattr(model, a)
-        if not isinstance(t, nn.Parameter):                         # no optimizer group owns it: keep the old kind
-            t = nn.Parameter(t, requires_grad=old.requires_grad) if isinstance(old, nn.Parameter) \
-                else t.requires_grad_(old.requires_grad)
-        setattr(model, a, t)
+    def with_zero_rows(t):
+        return torch.cat([t, torch.zeros((n,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)])
+    swap_rows_(model, GROUP_ATTR, new, with_zero_rows)
     for a in ("xyz_gradient_accum", "denom", "max_radii2D", "xyz_gradient_accum_abs"):
         t = getattr(model, a, None)
         if isinstance(t, torch.Tensor) and t.dim() >= 1 and t.shape[0] == P:
-            setattr(model, a, torch.cat([t, torch.zeros((n,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)]))
+            setattr(model, a, with_zero_rows(t))
     return n
 
 

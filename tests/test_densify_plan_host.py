@@ -95,7 +95,7 @@ def test_every_class_has_a_distinct_non_zero_count(cases, name):
 @pytest.mark.parametrize("name", list(R.CASES))
 def test_workspaces_hold_counter_arrays_a_multiple_of_64_words_apart(cases, name):
     """The scan moves whole lines as 16-byte words, so each of a plan's n counter arrays (and n offset arrays) starts
-    (nb + 1 rounded up to 64) words after the one before: the layouts of densify.hip, densify_fork.hip and grow.hip."""
+    (nb + 1 rounded up to 64) words after the one before: row_plan.h's layout, the head of the workspaces of densify.hip, densify_fork.hip and grow.hip."""
     from mvs_gaussian_splatting_amd import _lib
     lib = _lib.load()
     c = cases[name]

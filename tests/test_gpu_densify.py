@@ -58,10 +58,10 @@ class _Model:
                                     self.optimizer.state[getattr(self, ATTR[k])]["exp_avg_sq"].cpu()) for k in GROUPS}
 
 
-def _run_both(dev, P, seed, with_optimizer, max_screen_size, max_grad=0.0002, min_opacity=0.005, extent=5.0):
+def _run_both(dev, P, seed, with_optimizer, max_screen_size, max_grad=0.0002, min_opacity=0.005, extent=5.0, sh_rest=15):
     from mvs_gaussian_splatting_amd.densify import densify_and_prune
     from oracle.densify_ref import densify_and_prune_ref, count_split_selected_ref
-    m = _Model(P, seed, dev, with_optimizer)
+    m = _Model(P, seed, dev, with_optimizer, sh_rest)
     n_sel = count_split_selected_ref(m.cpu_params, m.cpu_accum.clone(), m.cpu_denom, m.percent_dense, max_grad, extent)
     noise = torch.randn(2 * n_sel, 3, generator=torch.Generator().manual_seed(seed + 100))
     ref = densify_and_prune_ref(m.cpu_params, m.cpu_moments, m.cpu_accum, m.cpu_denom, m.cpu_radii, m.percent_dense,
@@ -108,6 +108,17 @@ def test_densify_and_prune_matches_reference_restatement(dev, P, with_optimizer,
     if P >= 5000:       # the scene exercises every class
         assert info["cloned"] > 0 and info["children_per_copy"] > 0 and info["kept"] < P
         assert info["split_selected"] >= info["children_per_copy"]
+
+
+def test_densify_a_degree_0_model_whose_features_rest_has_no_width(dev):
+    """``_features_rest`` of shape ``[P,0,3]`` (and its moments) has no row to gather: the plain path accepts it, as the
+    fork's does.  P = 257: a partial second block."""
+    m, ref, info, n_sel = _run_both(dev, 257, 31, True, 20, sh_rest=0)
+    assert m._features_rest.shape == (info["points"], 0, 3) and info["points"] > 0
+    _check(m, ref, info, n_sel, True)
+    for p in (g["params"][0] for g in m.optimizer.param_groups):
+        p.grad = torch.ones_like(p)
+    m.optimizer.step()
 
 
 def test_densify_nothing_selected_and_everything_pruned(dev):
