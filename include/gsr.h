@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 42
+#define GSR_ABI_VERSION 43
 
 enum {
   GSR_OK = 0,
@@ -1021,6 +1021,32 @@ int gsr_nn_build(const float* ref, int32_t R, void* index, size_t index_bytes, v
 size_t gsr_nn_query_workspace_bytes(int32_t Q);
 int gsr_nn_query(const void* index, size_t index_bytes, int32_t R, const float* query, int32_t Q, float* dist2,
                  int32_t* nearest, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Point-to-point ICP between two nearest-point queries, ABI v43 (csrc/icp.hip, csrc/icp_math.h; geometry_eval.py;
+ * DESIGN.md §7.30).  Device arrays are float32 / int32, contiguous, 4-byte aligned; `matrix` and `pivots` are HOST arrays
+ * of finite doubles, read before the call returns.  0 <= Q, R <= GSR_NN_MAX_POINTS.  Every call checks its arguments
+ * before any HIP call, is asynchronous on `stream`, allocates nothing and reads nothing back.  No atomics: the same
+ * arguments give the same bits whatever the workspace held.
+ * gsr_icp_transform: matrix = the upper 3x4 of a similarity, row-major (s R | t).  out[i] = (float)(((m0 x + m1 y) + m2 z)
+ * + m3) per axis, in float64, every operation rounded on its own (no fused multiply-add), one rounding to float32.
+ * out may be points.  Q = 0: success, nothing is written. */
+#define GSR_ICP_WORDS 18
+#define GSR_ICP_BLOCK 256
+#define GSR_ICP_MAX_BLOCKS 1024
+int gsr_icp_transform(const float* points, int32_t Q, const double* matrix, float* out, void* stream);
+/* gsr_icp_accumulate: q [Q,3] the transformed source; dist2 [Q], nearest [Q] as gsr_nn_query wrote them against target
+ * [R,3]; pivots = c_q (3), c_r (3).  A pair i is accepted when dist2[i] <= thr2 (thr2 >= 0, +inf allowed; a NaN dist2 is
+ * not accepted) and 0 <= nearest[i] < R (-1, the empty target, never is).  With a = (double)q_i - c_q and b =
+ * (double)target[nearest[i]] - c_r, out (device, 8-byte aligned, GSR_ICP_WORDS 8-byte words) receives the int64 count of
+ * accepted pairs and 17 doubles: sum a (3), sum b (3), sum a_i b_j row-major (9), sum ((a0 a0 + a1 a1) + a2 a2), sum
+ * (double)dist2.  Accumulation is float64 in a fixed order (the header comment of csrc/icp.hip): min(ceil(Q / 256),
+ * GSR_ICP_MAX_BLOCKS) workgroups leave one partial each in `workspace` (gsr_icp_workspace_bytes(Q) bytes, 256-byte
+ * aligned), and a second launch of one workgroup adds the partials.  No pair accepted: count 0 and sums +0.0.  Q = 0:
+ * out is still written (zeros); the arrays and the workspace may be NULL. */
+size_t gsr_icp_workspace_bytes(int32_t Q);
+int gsr_icp_accumulate(const float* q, const float* dist2, const int32_t* nearest, int32_t Q, const float* target,
+                       int32_t R, float thr2, const double* pivots, void* workspace, size_t workspace_bytes, void* out,
+                       void* stream);
 
 /* ---- Multi-view geometric consistency of depth maps and back-projection, ABI v34 (csrc/mvs.hip; mvs.py).
  * The check of MVSNet's / COLMAP's fusion: a reference pixel goes into a source view at its depth, the source's depth is

@@ -24,6 +24,8 @@ from .surface import surface_depth, plane_depth  # noqa: F401
 from .mesh import (connected_components, clean_mesh, simplify_mesh, dilate_mask, vertex_view_counts,  # noqa: F401
                    cull_mesh_by_views, rasterize_mesh, face_normal_map, face_view_counts, cull_invisible_faces)
 from .geometry_eval import NearestIndex, nearest_points, sample_surface, evaluate_points, evaluate_mesh  # noqa: F401
+from .geometry_eval import (transform_points, voxel_down_sample, estimate_similarity, align_cameras,  # noqa: F401
+                            icp_step, icp_registration, register_tnt, load_crop_volume, crop_points)
 from .mvs import (select_source_views, depth_consistency, backproject_depth, fuse_depth_points,  # noqa: F401
                   multi_view_geo_loss, multi_view_ncc_loss, gray_image)
 
@@ -39,4 +41,6 @@ __all__ = ["Scene", "Camera", "MiniCam", "PoseCamera", "ModelParams", "load_imag
            "fuse_depth_points", "multi_view_geo_loss", "multi_view_ncc_loss",
            "gray_image", "slice_bilateral_grid", "bilateral_grid_tv_loss", "BilateralGrids", "dilate_mask",
            "vertex_view_counts", "cull_mesh_by_views", "view_counts_for_views",
-           "rasterize_mesh", "face_normal_map", "face_view_counts", "cull_invisible_faces"]
+           "rasterize_mesh", "face_normal_map", "face_view_counts", "cull_invisible_faces",
+           "transform_points", "voxel_down_sample", "estimate_similarity", "align_cameras", "icp_step", "icp_registration",
+           "register_tnt", "load_crop_volume", "crop_points"]

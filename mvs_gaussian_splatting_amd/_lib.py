@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # instead of copying it over the in-tree library
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")
 
-ABI_VERSION = 42
+ABI_VERSION = 43
 
 
 class GsrParams(C.Structure):
@@ -331,6 +331,12 @@ SYMBOLS = {
     "gsr_nn_query_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "gsr_nn_query": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.c_size_t, C.c_void_p]),
+    # point-to-point ICP between two nearest-point queries: transform by a float64 3x4, the 18 sums of the accepted pairs
+    # (csrc/icp.hip; geometry_eval.icp_step); matrix and pivots are host arrays
+    "gsr_icp_transform": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsr_icp_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "gsr_icp_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float,
+                                     C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     # multi-view geometric consistency of depth maps and back-projection to points (csrc/mvs.hip; mvs.py)
     "gsr_mvs_consistency": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_int32,
                                       C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
