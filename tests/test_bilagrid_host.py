@@ -1,8 +1,10 @@
 """Per-image bilateral grids without a GPU: the float64 restatement against central differences, the
 kernels' arithmetic (csrc/bilagrid_math.h) built for the host and held to the GPU test's bar on the GPU test's inputs,
 the identity properties, every refusal of the wrappers, of ``BilateralGrids`` and of the four C entry points, the ABI,
-the trainer's switch, and the census of the fragile pixels of the inputs tests/test_gpu_bilagrid.py runs on."""
+the trainer's switch, the census of the fragile pixels of the inputs tests/test_gpu_bilagrid.py runs on, and that the
+cases at the limits of the accepted shapes reach the lanes, row shares, blocks and passes they are there for."""
 import ctypes as C
+import math
 import os
 import re
 import shutil
@@ -342,3 +344,164 @@ def test_the_trainer_switch_is_off_by_default_and_refuses_before_rendering(monke
     assert {k: v for k, v in on.items() if k != "opt"} == {k: v for k, v in today.items() if k != "opt"}
     assert grids.optimizer.param_groups[0]["lr"] == pytest.approx(grids.scheduler_args(10))
     assert not sliced
+
+
+# ---- the limits of the accepted shapes, the large image, black pixels and the TV term past its block cap -------------
+WAVE, BG_TERMS, BG_MAX_XY, BG_MAX_L = 64, 12, 64, 16               # the constants of csrc/bilagrid.hip, mirrored
+BG_STAGE_FLOATS, BG_STAGE_BLOCKS, BG_STAGE_THREADS, BG_MAX_SHARES = 24576, 256, 1024, 8
+BG_TV_THREADS, BG_TV_MAX_BLOCKS, BG_TV_FIN_THREADS = 256, 1024, 256
+
+
+def _shares(H, Hg):
+    """``bilagrid_shares`` of csrc/bilagrid.hip."""
+    rows = 2 * (H // (Hg - 1) + 1) + 3
+    return min(max((rows + 15) // 16, 1), BG_MAX_SHARES)
+
+
+def _vertex_range(i, n_px, n_v):
+    """``bg_vertex_range`` of csrc/bilagrid_math.h."""
+    scale = n_px / (n_v - 1)
+    lo, hi = math.floor((i - 1) * scale - 0.5) - 1.0, math.ceil((i + 1) * scale - 0.5) + 1.0
+    return int(max(lo, 0.0)), int(min(hi, n_px - 1.0))
+
+
+def _tv_launch(N, shape):
+    """(elements, blocks of bilagrid_tv_kernel, passes of its grid stride, trips of the finish kernel over the slots)."""
+    Wg, Hg, L = shape
+    total = N * BG_TERMS * L * Hg * Wg
+    blocks = min(-(-total // BG_TV_THREADS), BG_TV_MAX_BLOCKS)
+    return total, blocks, -(-total // (blocks * BG_TV_THREADS)), -(-blocks // BG_TV_FIN_THREADS)
+
+
+def test_the_mirrored_constants_are_the_sources():
+    text = ""
+    for name in ("bilagrid.hip", "bilagrid_math.h", "gsr_common.h"):
+        with open(os.path.join(CSRC, name)) as f:
+            text += f.read()
+    for name, value in (("BG_TERMS", BG_TERMS), ("BG_MAX_XY", BG_MAX_XY), ("BG_MAX_L", BG_MAX_L),
+                        ("BG_STAGE_BLOCKS", BG_STAGE_BLOCKS), ("BG_STAGE_THREADS", BG_STAGE_THREADS),
+                        ("BG_MAX_SHARES", BG_MAX_SHARES), ("BG_TV_THREADS", BG_TV_THREADS),
+                        ("BG_TV_MAX_BLOCKS", BG_TV_MAX_BLOCKS), ("BG_TV_FIN_THREADS", BG_TV_FIN_THREADS), ("WAVE", WAVE)):
+        found = re.search(r"\b%s = (\d+)\b" % name, text)
+        assert found and int(found.group(1)) == value, name
+    assert "BG_STAGE_FLOATS = BG_TERMS * 8 * 16 * 16;" in text and BG_STAGE_FLOATS == BG_TERMS * 8 * 16 * 16
+    assert "__launch_bounds__(WAVE * BG_MAX_L)" in text
+
+
+def test_the_limit_cases_have_the_shapes_they_are_there_for():
+    assert len(R.LIMIT_CASES) <= 16
+    for (H, W), (Wg, Hg, L), lanes, fits, shares in R.LIMIT_CASES:
+        assert 2 <= Wg <= BG_MAX_XY and 2 <= Hg <= BG_MAX_XY and 2 <= L <= BG_MAX_L
+        assert lanes == WAVE * L <= WAVE * BG_MAX_L
+        assert fits == (BG_TERMS * L * Hg * Wg <= BG_STAGE_FLOATS), ((H, W), (Wg, Hg, L))
+        assert shares == _shares(H, Hg), ((H, W), (Wg, Hg, L))
+    cases = [c[:2] for c in R.LIMIT_CASES]
+    by_shape = {shape: (lanes, fits) for _, shape, lanes, fits, _ in R.LIMIT_CASES}
+    # L = 16: the block of 1024 lanes, beside the smallest extents, odd ones and the default ones
+    for shape in ((2, 2, 16), (5, 3, 16), (16, 16, 16)):
+        assert by_shape[shape][0] == 1024 and ((70, 37), shape) in cases and ((3, 130), shape) in cases
+    # each extent at 64 on an image narrower than the grid and on a wider one; (16,16,16) and (64,64,2) do not fit LDS
+    for shape in ((64, 2, 2), (2, 64, 2), (64, 64, 2), (64, 64, 16)):
+        assert ((7, 5), shape) in cases and ((70, 37), shape) in cases
+    assert not by_shape[(16, 16, 16)][1] and not by_shape[(64, 64, 2)][1] and not by_shape[(64, 64, 16)][1]
+    assert by_shape[(64, 64, 16)][0] == 1024 and ((65, 9), (33, 17, 9)) in cases
+    assert {c[4] for c in R.LIMIT_CASES} >= {1, 2, 5, 8}, "one share, a few and the most"
+    # no case widens the tables that were there
+    assert not {shape for _, shape in cases} & set(R.GRID_SHAPES)
+
+
+def test_census_of_the_new_gpu_test_inputs():
+    H, W = R.LARGE_IMAGE
+    inputs = [(f"{h}x{w}", R.make_image(h, w), shape[2]) for (h, w), shape, *_ in R.LIMIT_CASES]
+    inputs += [(f"{H}x{W}", R.make_image(H, W), shape[2]) for shape in R.LARGE_GRIDS]
+    inputs += [("black %dx%d" % R.BLACK_IMAGE, R.make_image_with_black(*R.BLACK_IMAGE)[0], shape[2])
+               for shape in R.BLACK_GRIDS]
+    seen = set()
+    for label, x, L in inputs:
+        if (label, L) in seen:
+            continue
+        seen.add((label, L))
+        n, pixels, cap = R.census(x, L)
+        print(f"census {label} L={L}: {n} fragile of {pixels} (cap {cap})")
+        assert n <= cap
+
+
+def test_the_host_build_meets_the_bar_at_the_limits_of_the_shape_range(host_program, tmp_path):
+    for (H, W), shape, *_ in R.LIMIT_CASES:
+        x, grid, up = R.make_image(H, W), R.make_grid(shape), R.make_upstream(H, W)
+        got = _run_host(host_program, tmp_path, x, grid, up)
+        label = f"{H}x{W} grid {shape}"
+        R.check_slice(got, x, grid, up, label)
+        assert all(bool(torch.isfinite(t).all()) for t in got)
+        none = R.check_untouched(got[2], x, shape, label)
+        if (H, W) == (7, 5) and max(shape[:2]) == 64:
+            assert 2 * none > shape[0] * shape[1] * shape[2], "narrower than the grid: most vertices see no pixel"
+
+
+def test_the_large_image_has_several_row_shares_and_column_trips_and_the_host_build_meets_the_bar(host_program, tmp_path):
+    H, W = R.LARGE_IMAGE
+    assert H * W >= BG_STAGE_BLOCKS * BG_STAGE_THREADS > (H - 2) * W, "staged by AUTO, and the first such height but one"
+    assert H * W > BG_STAGE_BLOCKS * BG_STAGE_THREADS, "more than one pass of the staged kernel's grid stride"
+    fits = [BG_TERMS * L * Hg * Wg <= BG_STAGE_FLOATS for Wg, Hg, L in R.LARGE_GRIDS]
+    assert fits == [True, False]
+    for Wg, Hg, L in R.LARGE_GRIDS:
+        assert _shares(H, Hg) == 5
+        widths = [hi - lo + 1 for lo, hi in (_vertex_range(i, W, Wg) for i in range(Wg))]
+        print(f"{H}x{W} grid {(Wg, Hg, L)}: {_shares(H, Hg)} row shares, {min(widths)}..{max(widths)} columns a vertex")
+        assert max(widths) > WAVE and sorted(widths)[Wg // 2] > WAVE, "more than one 64-lane trip along a row"
+    shape = R.LARGE_GRIDS[0]
+    x, grid, up = R.make_image(H, W), R.make_grid(shape), R.make_upstream(H, W)
+    R.check_slice(_run_host(host_program, tmp_path, x, grid, up), x, grid, up, f"{H}x{W} grid {shape}")
+
+
+def test_grid_sample_has_no_coordinate_gradient_on_the_border_and_black_pixels_meet_the_bar_on_the_host(host_program,
+                                                                                                      tmp_path):
+    """torch's ``grid_sample(padding_mode="border")`` gives a coordinate exactly on the border a zero gradient, as
+    ``bg_pixel`` does with ``gray > 0``: so the restatement is the reference at a black pixel as it stands."""
+    import torch.nn.functional as F
+    grid = R.make_grid((3, 5, 4)).to(F64)[None]
+    for z, zero in ((-1.0, True), (1.0, True), (-1.0 + 1e-9, False), (1.0 - 1e-9, False)):
+        for dtype in (F64, torch.float32):
+            c = torch.tensor([[[[[0.3, -0.2, z]]]]], dtype=dtype, requires_grad=True)
+            F.grid_sample(grid.to(dtype), c, mode="bilinear", padding_mode="border", align_corners=True).sum().backward()
+            assert (float(c.grad[..., 2]) == 0.0) == (zero or dtype == torch.float32), (z, dtype)
+            assert float(c.grad[..., 0]) != 0.0
+    H, W = R.BLACK_IMAGE
+    x, black = R.make_image_with_black(H, W)
+    up = R.make_upstream(H, W)
+    assert 30 < int(black.sum()) < 40 and bool((R.gray(x.to(F64))[black] == 0).all())
+    assert bool((x[:, black] == 0).all()) and torch.equal(x[:, ~black], R.make_image(H, W)[:, ~black])
+    for shape in R.BLACK_GRIDS:
+        Wg, Hg, L = shape
+        grid = R.make_grid(shape)
+        # the rectangle lies across a cell boundary in x and in y
+        ys, xs = torch.nonzero(black[H // 2 - 20:H // 2 - 14].any(1)), torch.nonzero(black[H // 2 - 17])
+        ys = ys.flatten() + H // 2 - 20
+        assert len({int((int(py) + 0.5) / H * (Hg - 1)) for py in ys}) > 1
+        assert len({int((int(px) + 0.5) / W * (Wg - 1)) for px in xs.flatten()}) > 1
+        _, dx64, _ = R.slice_with_grads(x, grid, up)
+        want = R.image_grad_without_the_luminance(x, grid, up)
+        assert R.rel_err(dx64[:, black], want[:, black]) < 1e-14, "autograd of the restatement: nothing through z"
+        assert R.rel_err(dx64[:, ~black], want[:, ~black]) > 1e-3, "elsewhere the luminance path carries weight"
+        got = _run_host(host_program, tmp_path, x, grid, up)
+        label = f"black {H}x{W} grid {shape}"
+        R.check_slice(got, x, grid, up, label)
+        R.check_black(got[1], x, black, grid, up, label)
+
+
+def test_the_tv_limit_cases_reach_the_blocks_and_passes_they_claim():
+    assert max(_tv_launch(N, shape)[1] for N, shape in R.TV_CASES) <= BG_TV_FIN_THREADS, "what was there: one trip each"
+    for N, shape, blocks, passes in R.TV_LIMIT_CASES:
+        assert _tv_launch(N, shape)[1:3] == (blocks, passes), (N, shape)
+    launch = {(N, shape): _tv_launch(N, shape) for N, shape, *_ in R.TV_LIMIT_CASES}
+    assert launch[(3, (16, 16, 8))] == (73728, 288, 1, 2), "the finish kernel's second trip over the slots"
+    assert launch[(11, (16, 16, 8))] == (270336, 1024, 2, 4) and 270336 - 1024 * 256 == 8192
+    assert launch[(1, (64, 64, 16))] == (786432, 1024, 3, 4)
+    for shape in ((2, 2, 16), (64, 2, 2), (2, 64, 2)):
+        assert any(s == shape for _, s, *_ in R.TV_LIMIT_CASES)
+    assert _tv_launch(*R.TV_STRUCTURAL_CASE)[1:3] == (1024, 2) and _tv_launch(10, (16, 16, 8))[2] == 1
+    # the structural grids: every difference inside a term is 0, so the value and the gradient are exact zeros
+    grids = R.make_constant_term_grids(*R.TV_STRUCTURAL_CASE)
+    assert grids.unique().numel() == 12 * R.TV_STRUCTURAL_CASE[0] and bool((grids == grids.round()).all())
+    value, grad = R.tv_with_grad(grids)
+    assert float(value) == 0.0 and bool((grad == 0).all())

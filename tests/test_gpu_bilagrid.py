@@ -131,8 +131,7 @@ def test_non_contiguous_inputs_give_the_results_of_their_contiguous_copies(gpu_d
     assert torch.equal(_bits(bilateral_grid_tv_loss(strided)), _bits(bilateral_grid_tv_loss(grids)))
 
 
-@pytest.mark.parametrize("N,shape", R.TV_CASES, ids=[f"{n}-{'x'.join(map(str, s))}" for n, s in R.TV_CASES])
-def test_tv_value_and_gradient_meet_the_bar_and_are_reproducible(gpu_device, N, shape):
+def _check_tv(gpu_device, N, shape):
     from mvs_gaussian_splatting_amd import bilateral_grid_tv_loss
     grids = R.make_grids(N, shape)
     v64, g64 = R.tv_with_grad(grids)
@@ -151,6 +150,139 @@ def test_tv_value_and_gradient_meet_the_bar_and_are_reproducible(gpu_device, N, 
         assert err <= R.bar(own), f"tv {name}: {err:.3e} above the bar {R.bar(own):.3e}"
     no_grad = bilateral_grid_tv_loss(grids.to(gpu_device))
     assert torch.equal(_bits(no_grad.cpu()), _bits(runs[0][0])) and not no_grad.requires_grad
+
+
+@pytest.mark.parametrize("N,shape", R.TV_CASES, ids=[f"{n}-{'x'.join(map(str, s))}" for n, s in R.TV_CASES])
+def test_tv_value_and_gradient_meet_the_bar_and_are_reproducible(gpu_device, N, shape):
+    _check_tv(gpu_device, N, shape)
+
+
+@pytest.mark.parametrize("N,shape", [c[:2] for c in R.TV_LIMIT_CASES],
+                         ids=[f"{n}-{'x'.join(map(str, s))}" for n, s, *_ in R.TV_LIMIT_CASES])
+def test_tv_past_256_slots_past_the_block_cap_and_at_every_extent(gpu_device, N, shape):
+    """More blocks than one trip of the finish kernel reads, more elements than one pass of the capped launch covers
+    (tests/test_bilagrid_host.py asserts the block and pass counts), and each extent at the largest accepted."""
+    _check_tv(gpu_device, N, shape)
+
+
+def test_tv_of_grids_constant_within_each_term_is_exactly_zero_past_the_block_cap(gpu_device):
+    """Every difference inside a term of an image is exactly 0 and every difference across a row, slab, term or image
+    boundary is a non-zero integer: a kernel that takes one of those, in the first pass or in the grid stride's second,
+    gives a value or a gradient element that is not zero."""
+    from mvs_gaussian_splatting_amd import bilateral_grid_tv_loss
+    grids = R.make_constant_term_grids(*R.TV_STRUCTURAL_CASE).to(gpu_device).requires_grad_(True)
+    value = bilateral_grid_tv_loss(grids)
+    value.backward()
+    value = float(value.detach())
+    print(f"tv of constant terms: value {value!r}, {int((grids.grad != 0).sum())} gradient elements not zero, "
+          f"largest {float(grids.grad.abs().max())!r}")
+    assert value == 0.0
+    assert bool((grids.grad == 0).all()), "every gradient element is an exact zero, of either sign"
+
+
+# ---- the limits of the shape range, the large image, black pixels ----------------------------------------------------
+GSR_E_BADARG = -1
+STAGINGS = ("AUTO", "CACHE", "LDS")
+
+
+def _raw(dev, lib, x, grid, up, staging):
+    """The two raw entry points under one staging, into NaN-filled outputs and from a 0xff-filled workspace ->
+    (status of the forward, status of the backward, Y, dX, dG), the tensors on the device."""
+    H, W = x.shape[1:]
+    L, Hg, Wg = grid.shape[1:]
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    y, dx, dg = torch.full_like(x, float("nan")), torch.full_like(x, float("nan")), torch.full_like(grid, float("nan"))
+    ws = torch.full((lib.gsr_bilagrid_workspace_bytes(H, W, Wg, Hg, L),), 0xff, dtype=torch.uint8, device=dev)
+    fwd = lib.gsr_bilagrid_slice_fwd(x.data_ptr(), grid.data_ptr(), H, W, Wg, Hg, L, staging, y.data_ptr(), stream)
+    bwd = lib.gsr_bilagrid_slice_bwd(x.data_ptr(), grid.data_ptr(), up.data_ptr(), H, W, Wg, Hg, L, staging,
+                                     dx.data_ptr(), dg.data_ptr(), ws.data_ptr(), stream)
+    return fwd, bwd, y, dx, dg
+
+
+def _every_staging_gives(dev, want, x, grid, up, fits, label):
+    """Every accepted staging writes every element of NaN-filled outputs, from a 0xff-filled workspace, with the bits of
+    ``want``; GSR_BILAGRID_STAGE_LDS with a grid that does not fit LDS is refused with the bad-argument status and leaves
+    the NaN-filled outputs as they were, bit for bit."""
+    from mvs_gaussian_splatting_amd import _lib
+    lib = _lib.load()
+    xd, gd, ud = x.to(dev), grid.to(dev), up.to(dev)
+    for name in STAGINGS:
+        fwd, bwd, y, dx, dg = _raw(dev, lib, xd, gd, ud, getattr(_lib, "BILAGRID_STAGE_" + name))
+        if name == "LDS" and not fits:
+            assert (fwd, bwd) == (GSR_E_BADARG, GSR_E_BADARG), f"{label}: a grid that does not fit LDS is refused"
+            assert b"24576" in lib.gsr_last_error()
+            for t in (y, dx, dg):
+                assert torch.equal(_bits(t), _bits(torch.full_like(t, float("nan")))), "a refusal writes nothing"
+            continue
+        assert (fwd, bwd) == (0, 0), f"{label} {name}: {lib.gsr_last_error()}"
+        for what, t, w in zip(("Y", "dX", "dG"), (y, dx, dg), want):
+            assert torch.equal(_bits(t.cpu()), _bits(w)), f"{label}: {what} under {name} has the wrapper's bits"
+
+
+LIMITS = [(c[0], c[1], c[3]) for c in R.LIMIT_CASES]
+
+
+@pytest.mark.parametrize("hw,shape,fits", LIMITS, ids=[f"{h}x{w}-{'x'.join(map(str, s))}" for (h, w), s, _ in LIMITS])
+def test_at_the_limits_of_the_shape_range_the_bar_is_met_and_the_bits_are_the_same_every_way(gpu_device, hw, shape, fits):
+    """L = 16 (a grid-gradient block of 1024 lanes), each extent at 64, a grid that LDS does not hold, an image narrower
+    than the grid and an odd shape: tests/test_bilagrid_host.py asserts that the cases are those."""
+    (H, W) = hw
+    x, grid, up = R.make_image(H, W), R.make_grid(shape), R.make_upstream(H, W)
+    label = f"{H}x{W} grid {shape}"
+    got = _call(gpu_device, x, grid, up)
+    R.check_slice(got, x, grid, up, label)
+    R.check_untouched(got[2], x, shape, label)
+    again = _call(gpu_device, x, grid, up, fill=float("nan"))
+    for a, b in zip(got, again):
+        assert torch.equal(_bits(a), _bits(b)), "two runs, the second into garbage-filled buffers, give the same bits"
+    _every_staging_gives(gpu_device, got, x, grid, up, fits, label)
+
+
+@pytest.fixture(scope="module")
+def large_inputs():
+    H, W = R.LARGE_IMAGE
+    return R.make_image(H, W), R.make_upstream(H, W)
+
+
+def test_the_large_image_meets_the_bar_and_its_grid_gradient_is_the_same_bits_under_every_staging(gpu_device, large_inputs):
+    """513 x 512 under the default grid: AUTO stages the grid in LDS and walks more than one pass of its grid stride,
+    the grid gradient has 5 row shares and more than one 64-lane trip per row (tests/test_bilagrid_host.py)."""
+    x, up = large_inputs
+    shape = R.LARGE_GRIDS[0]
+    grid = R.make_grid(shape)
+    label = "%dx%d grid %s" % (*R.LARGE_IMAGE, shape)
+    got = _call(gpu_device, x, grid, up)
+    R.check_slice(got, x, grid, up, label)
+    _every_staging_gives(gpu_device, got, x, grid, up, True, label)
+
+
+def test_the_large_image_under_a_grid_that_lds_does_not_hold_takes_the_cache_path_and_refuses_lds(gpu_device, large_inputs):
+    """513 x 512 under (16,16,16): AUTO must not stage 49152 floats, so its bits are the forced cache path's; forcing LDS
+    is refused on valid memory with every output untouched, and the call after the refusal is right."""
+    x, up = large_inputs
+    shape = R.LARGE_GRIDS[1]
+    grid = R.make_grid(shape)
+    label = "%dx%d grid %s" % (*R.LARGE_IMAGE, shape)
+    got = _call(gpu_device, x, grid, up)
+    _every_staging_gives(gpu_device, got, x, grid, up, False, label)
+    after = _call(gpu_device, x, grid, up, fill=float("nan"))
+    R.check_slice(after, x, grid, up, label + " after the refusal")
+    for a, b in zip(got, after):
+        assert torch.equal(_bits(a), _bits(b))
+
+
+@pytest.mark.parametrize("shape", R.BLACK_GRIDS, ids=["x".join(map(str, s)) for s in R.BLACK_GRIDS])
+def test_exactly_black_pixels_meet_the_bar_and_their_gradient_is_the_affines_alone(gpu_device, shape):
+    """A luminance of exactly 0 is the strict side of ``gray > 0``: ``dz/dgray = 0`` and ``dX = A^T g``."""
+    H, W = R.BLACK_IMAGE
+    (x, black), grid, up = R.make_image_with_black(H, W), R.make_grid(shape), R.make_upstream(H, W)
+    label = f"black {H}x{W} grid {shape}"
+    got = _call(gpu_device, x, grid, up)
+    R.check_slice(got, x, grid, up, label)
+    R.check_black(got[1], x, black, grid, up, label)
+    again = _call(gpu_device, x, grid, up, fill=float("nan"))
+    for a, b in zip(got, again):
+        assert torch.equal(_bits(a), _bits(b))
 
 
 # ---- the training iteration ------------------------------------------------------------------------------------------
