@@ -16,7 +16,14 @@ SH degree steps, densification, opacity resets, the optional opacity sparsity te
                              [--lambda_multi_view_geo L [--multi_view_sources K] [--multi_view_from_iter N]
                               [--multi_view_pix_max P]]
                              [--lambda_multi_view_ncc L [--multi_view_ncc_samples N] [--multi_view_patch_radius R]]
+                             [-d DIR [--depth_prior_mode l1|aligned_l1|pearson] [--depth_l1_weight_init W]
+                              [--depth_l1_weight_final W]]
 
+``-d DIR`` (with ``-s``; upstream 3DGS's option, off by default) regularises training with a per-image inverse-depth prior:
+``<scene>/DIR/<image stem>.png``, 16-bit, for every training image, aligned by ``<scene>/sparse/0/depth_params.json`` when
+upstream's ``make_depth_scale.py`` wrote one.  The term (``depth_prior.py``) is ``--depth_prior_mode``: ``l1``, upstream's,
+which needs that file; ``aligned_l1`` or ``pearson``, which fit the alignment per frame and take raw monocular maps.  Its
+weight decays from ``--depth_l1_weight_init`` to ``--depth_l1_weight_final`` over the run.
 ``--strategy mcmc --cap_max N`` (both forms) densifies the MCMC way (``mcmc.py``): a budget of N Gaussians, dead ones
 relocated onto live ones, 5 % growth a round, position noise and L1 priors on opacity and scale.
 ``--lambda_normal L`` (both forms; off by default) adds the depth-normal consistency term of 2DGS from iteration
@@ -205,15 +212,17 @@ def train_scene(args, dev):
     from mvs_gaussian_splatting_amd import ModelParams, Scene
     dataset = ModelParams(source_path=args.source_path, model_path=args.model_path, images=args.images,
                           resolution=args.resolution, white_background=args.white_background,
-                          data_device=args.data_device, eval=args.eval)
+                          data_device=args.data_device, eval=args.eval, **({"depths": args.depths} if args.depths else {}))
     n = args.iterations
     over = dict(opacitysparse=args.opacitysparse, optimizer_type=args.optimizer_type,
+                depth_l1_weight_init=args.depth_l1_weight_init, depth_l1_weight_final=args.depth_l1_weight_final,
+                depth_prior_mode=args.depth_prior_mode,
                 exposure_lr_init=args.exposure_lr_init, exposure_lr_final=args.exposure_lr_final,
                 exposure_lr_delay_steps=args.exposure_lr_delay_steps, exposure_lr_delay_mult=args.exposure_lr_delay_mult,
                 **strategy_options(args))
     opt = example_opt(n, **over) if n < 3000 else OptimizationParams(iterations=n, **over)
     model = GaussianModel(dataset.sh_degree)
-    scene = Scene(dataset, model)
+    scene = Scene(dataset, model, **({"depth_prior_mode": opt.depth_prior_mode} if args.depths else {}))
     with open(os.path.join(args.model_path, "cfg_args.json"), "w") as f:         # what examples/render.py -m needs
         json.dump({k: getattr(dataset, k) for k in ("source_path", "images", "resolution", "white_background", "eval",
                                                     "sh_degree")}, f)
@@ -334,6 +343,15 @@ def main(argv=None):
                     help="absolute-gradient densification (AbsGS / PGSR): a large Gaussian is also split when its "
                          "accumulated absolute view-space gradient reaches --densify_abs_grad_threshold")
     ap.add_argument("--densify_abs_grad_threshold", type=float, default=0.0008, metavar="T")
+    ap.add_argument("-d", "--depths", default="", metavar="DIR",
+                    help="with -s: the folder of 16-bit inverse-depth PNGs under the scene, one per training image "
+                         "(upstream 3DGS's -d); adds the depth-prior term (depth_prior.py)")
+    ap.add_argument("--depth_l1_weight_init", type=float, default=OptimizationParams.depth_l1_weight_init)
+    ap.add_argument("--depth_l1_weight_final", type=float, default=OptimizationParams.depth_l1_weight_final)
+    ap.add_argument("--depth_prior_mode", choices=("l1", "aligned_l1", "pearson"),
+                    default=OptimizationParams.depth_prior_mode,
+                    help="with -d: l1 is upstream's term and needs sparse/0/depth_params.json; aligned_l1 and pearson fit "
+                         "the scale and shift per frame")
     ap.add_argument("--out", default=os.path.dirname(os.path.abspath(__file__)))
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")

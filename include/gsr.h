@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 43
+#define GSR_ABI_VERSION 44
 
 enum {
   GSR_OK = 0,
@@ -1047,6 +1047,37 @@ size_t gsr_icp_workspace_bytes(int32_t Q);
 int gsr_icp_accumulate(const float* q, const float* dist2, const int32_t* nearest, int32_t Q, const float* target,
                        int32_t R, float thr2, const double* pivots, void* workspace, size_t workspace_bytes, void* out,
                        void* stream);
+
+/* ---- Depth-prior loss of a rendered inverse-depth map, ABI v44 (csrc/depth_prior.hip, csrc/depth_prior_math.h;
+ * depth_prior.py).  invdepth (x), prior (y) and the optional weight (w; NULL: 1 everywhere) are device
+ * float32 [H,W], contiguous, 4-byte aligned, 1 <= H W <= 2^28.  A pixel is valid when w > 0 and w, x, y are finite; an
+ * invalid pixel enters no sum and gets gradient +0.  mode:
+ *   GSR_DEPTH_PRIOR_L1          sum w |x - (scale y + offset)| / (H W), upstream 3DGS's term; scale, offset finite
+ *   GSR_DEPTH_PRIOR_ALIGNED_L1  sum w |x - (s y + t)| / sum w under the weighted least-squares fit s, t of x on y, a constant
+ *   GSR_DEPTH_PRIOR_PEARSON     1 - r, r the weighted Pearson correlation of x and y
+ * (scale and offset are ignored by the two fitted modes).  A fitted mode is degenerate below 2 valid pixels or when the
+ * weighted variance of x or of y is not above 2^-40 of its mean square: loss 0, gradient 0, s = 1, t = 0, r = 0.
+ * record (device, 8-byte aligned, 8 doubles) receives (loss, valid pixels, sum w, s, t, r, degenerate 0 / 1, 0); in the l1
+ * mode s, t are scale, offset and r is 0.  grad (device [H,W] float32, or NULL: not written) receives dL/dx, computed in
+ * float64 and rounded once.  Sums are float64 in a fixed order (the header comment of csrc/depth_prior.hip): min(ceil(H W /
+ * GSR_DEPTH_PRIOR_BLOCK), GSR_DEPTH_PRIOR_MAX_BLOCKS) workgroups leave one partial each in `workspace`
+ * (gsr_depth_prior_workspace_bytes(H, W) bytes, 256-byte aligned) and a launch of one workgroup adds them; no atomics: the
+ * same arguments give the same bits whatever the workspace held.  After a fitted mode the workspace's 8-byte words
+ * GSR_DEPTH_PRIOR_FIT_COUNT_WORD .. + GSR_DEPTH_PRIOR_SUM_WORDS - 1 hold the int64 count of valid pixels and the six sums
+ * of w, wx, wy, wxx, wxy, wyy.  2 (l1), 4 (aligned_l1) or 3 (pearson) launches on `stream`; every argument is checked
+ * before any HIP call; nothing is allocated or read back. */
+#define GSR_DEPTH_PRIOR_L1 0
+#define GSR_DEPTH_PRIOR_ALIGNED_L1 1
+#define GSR_DEPTH_PRIOR_PEARSON 2
+#define GSR_DEPTH_PRIOR_BLOCK 256
+#define GSR_DEPTH_PRIOR_MAX_BLOCKS 1024
+#define GSR_DEPTH_PRIOR_SUM_WORDS 7
+#define GSR_DEPTH_PRIOR_RECORD_WORDS 8
+#define GSR_DEPTH_PRIOR_FIT_COUNT_WORD 16
+size_t gsr_depth_prior_workspace_bytes(int32_t H, int32_t W);
+int gsr_depth_prior_fwd_bwd(const float* invdepth, const float* prior, const float* weight, int32_t H, int32_t W,
+                            int32_t mode, double scale, double offset, double* record, float* grad, void* workspace,
+                            size_t workspace_bytes, void* stream);
 
 /* ---- Multi-view geometric consistency of depth maps and back-projection, ABI v34 (csrc/mvs.hip; mvs.py).
  * The check of MVSNet's / COLMAP's fusion: a reference pixel goes into a source view at its depth, the source's depth is

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # instead of copying it over the in-tree library
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")
 
-ABI_VERSION = 43
+ABI_VERSION = 44
 
 
 class GsrParams(C.Structure):
@@ -337,6 +337,10 @@ SYMBOLS = {
     "gsr_icp_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "gsr_icp_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float,
                                      C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    # depth-prior loss of a rendered inverse-depth map, value and unit gradient (csrc/depth_prior.hip; depth_prior.py)
+    "gsr_depth_prior_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "gsr_depth_prior_fwd_bwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_double] * 2 + [C.c_void_p] * 3 +
+                                [C.c_size_t, C.c_void_p]),
     # multi-view geometric consistency of depth maps and back-projection to points (csrc/mvs.hip; mvs.py)
     "gsr_mvs_consistency": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_int32,
                                       C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),

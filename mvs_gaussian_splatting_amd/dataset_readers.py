@@ -51,6 +51,10 @@ class CameraInfo(NamedTuple):
     width: int
     height: int
     composite_bg: Optional[np.ndarray] = None
+    # upstream 3DGS's depth prior (``-d``): the 16-bit PNG of the image's inverse depth ("" for none) and its entry of
+    # ``sparse/0/depth_params.json`` with ``med_scale`` added (None without the file or without an entry)
+    depth_path: str = ""
+    depth_params: Optional[dict] = None
 
 
 class SceneInfo(NamedTuple):
@@ -232,6 +236,33 @@ def _open_image(path: str):
     return Image.open(path)
 
 
+def read_depth_params(path: str) -> Optional[dict]:
+    """``sparse/0/depth_params.json`` as upstream reads it: ``{image stem: {"scale": s, "offset": o}}``, every entry given
+    ``med_scale``, the median of the positive scales (0 when none is positive).  None when the file is not there."""
+    if not os.path.isfile(path):
+        return None
+    with open(path, "r") as f:
+        params = json.load(f)
+    scales = np.array([params[key]["scale"] for key in params], dtype=np.float64)
+    med_scale = float(np.median(scales[scales > 0])) if (scales > 0).sum() else 0.0
+    for key in params:
+        params[key]["med_scale"] = med_scale
+    return params
+
+
+def _with_depth_priors(train_cams: list, depths_folder: str, depths_params: Optional[dict]) -> list:
+    """The training cameras with ``depth_path = <folder>/<image stem>.png`` and their ``depth_params`` entry; a training
+    camera without its PNG is an error."""
+    out = []
+    for c in train_cams:
+        depth_path = os.path.join(depths_folder, c.image_name + ".png")
+        if not os.path.isfile(depth_path):
+            raise FileNotFoundError(f"depth prior of image {c.image_name!r} not found: {depth_path}")
+        out.append(c._replace(depth_path=depth_path,
+                              depth_params=None if depths_params is None else depths_params.get(c.image_name)))
+    return out
+
+
 def readColmapCameras(cam_extrinsics: dict, cam_intrinsics: dict, images_folder: str, open_image=_open_image) -> list:
     cam_infos = []
     for key in cam_extrinsics:
@@ -247,7 +278,9 @@ def readColmapCameras(cam_extrinsics: dict, cam_intrinsics: dict, images_folder:
     return cam_infos
 
 
-def readColmapSceneInfo(path: str, images, eval: bool, llffhold: int = 8) -> SceneInfo:
+def readColmapSceneInfo(path: str, images, eval: bool, llffhold: int = 8, depths: str = "") -> SceneInfo:
+    """``depths``: upstream's ``-d``, a folder under ``path`` with one 16-bit inverse-depth PNG per training image, aligned
+    by ``sparse/0/depth_params.json`` when that file is there; test cameras of an ``eval`` split carry no prior."""
     sparse = os.path.join(path, "sparse/0")
     try:
         cam_extrinsics = read_extrinsics_binary(os.path.join(sparse, "images.bin"))
@@ -263,6 +296,9 @@ def readColmapSceneInfo(path: str, images, eval: bool, llffhold: int = 8) -> Sce
         test_cam_infos = [c for idx, c in enumerate(cam_infos) if idx % llffhold == 0]
     else:
         train_cam_infos, test_cam_infos = cam_infos, []
+    if depths:
+        train_cam_infos = _with_depth_priors(train_cam_infos, os.path.join(path, depths),
+                                             read_depth_params(os.path.join(sparse, "depth_params.json")))
     nerf_normalization = getNerfppNorm(train_cam_infos)
     ply_path = os.path.join(path, "sparse/0/points3D.ply")
     if not os.path.exists(ply_path):
@@ -304,12 +340,16 @@ def readCamerasFromTransforms(path: str, transformsfile: str, white_background: 
     return cam_infos
 
 
-def readNerfSyntheticInfo(path: str, white_background: bool, eval: bool, extension: str = ".png") -> SceneInfo:
+def readNerfSyntheticInfo(path: str, white_background: bool, eval: bool, extension: str = ".png",
+                          depths: str = "") -> SceneInfo:
+    """``depths``: as in ``readColmapSceneInfo``; a Blender scene has no ``depth_params.json``, so the priors are raw."""
     train_cam_infos = readCamerasFromTransforms(path, "transforms_train.json", white_background, extension)
     test_cam_infos = readCamerasFromTransforms(path, "transforms_test.json", white_background, extension)
     if not eval:
         train_cam_infos.extend(test_cam_infos)
         test_cam_infos = []
+    if depths:
+        train_cam_infos = _with_depth_priors(train_cam_infos, os.path.join(path, depths), None)
     nerf_normalization = getNerfppNorm(train_cam_infos)
     ply_path = os.path.join(path, "points3d.ply")
     if not os.path.exists(ply_path):
@@ -327,6 +367,19 @@ def readNerfSyntheticInfo(path: str, white_background: bool, eval: bool, extensi
 
 
 sceneLoadTypeCallbacks = {"Colmap": readColmapSceneInfo, "Blender": readNerfSyntheticInfo}
+
+
+def decode_invdepth(path: str) -> np.ndarray:
+    """The ``[h, w]`` float32 inverse depth of a prior's PNG, ``uint16 / 65536`` (upstream's ``cv2.imread(path, -1) /
+    2**16``), decoded with Pillow.  Anything but a 16-bit single-channel image is a ``ValueError`` that names the file."""
+    from PIL import Image
+    with Image.open(path) as image:
+        if not image.mode.startswith("I;16"):
+            raise ValueError(f"{path}: a depth prior must be a 16-bit single-channel PNG, got image mode {image.mode!r}")
+        a = np.array(image)
+    if a.ndim != 2:
+        raise ValueError(f"{path}: a depth prior must be a 16-bit single-channel PNG, got an array of shape {a.shape}")
+    return a.astype(np.float32) / np.float32(65536.0)
 
 
 def decode_image(cam_info: CameraInfo) -> np.ndarray:

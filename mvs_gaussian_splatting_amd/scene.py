@@ -23,7 +23,7 @@ import torch
 
 from . import image_ingest
 from .exposure import load_exposures, save_exposures
-from .dataset_readers import decode_image, fov2focal, sceneLoadTypeCallbacks
+from .dataset_readers import decode_image, decode_invdepth, fov2focal, sceneLoadTypeCallbacks
 from .synthetic import get_projection_matrix, get_world2view2
 
 
@@ -33,6 +33,7 @@ class ModelParams:
     source_path = ""
     model_path = ""
     images = "images"
+    depths = ""              # upstream 3DGS's -d: the folder of per-image inverse-depth PNGs under source_path; "" for none
     resolution = -1
     white_background = False
     data_device = "cuda"
@@ -59,10 +60,17 @@ class ModelParams:
 class Camera:
     """``scene/cameras.py:17-57``.  image: the finished ``[3, H, W]`` float32 target (``image_ingest.load_image`` has
     clamped and masked it already); gt_alpha_mask: a further ``[1, H, W]`` mask to multiply in, as the reference's
-    constructor does.  The matrices live on ``device``, the target on ``data_device``."""
+    constructor does.  The matrices live on ``device``, the target on ``data_device``.
+    invdepthmap, depth_params: upstream 3DGS's depth prior (``scene/cameras.py``): the ``[1, H, W]`` (or ``[H, W]``) float32
+    inverse depth already at the camera's resolution, and its ``depth_params.json`` entry ``{"scale", "offset",
+    "med_scale"}`` or None.  Negatives are clamped to 0; with an entry whose ``scale`` lies outside ``[0.2, 5] med_scale``
+    the prior is unreliable (``depth_reliable = False``, ``depth_mask`` zeros); ``invdepth * scale + offset`` is applied
+    when ``scale > 0``.  Attributes: ``invdepthmap`` and ``depth_mask`` (``[1, H, W]`` float32 on ``data_device``) and
+    ``depth_reliable``; without a map None, None and False."""
 
     def __init__(self, colmap_id, R, T, FoVx, FoVy, image, gt_alpha_mask, image_name, uid,
-                 trans=np.array([0.0, 0.0, 0.0]), scale=1.0, data_device="cuda", device="cuda"):
+                 trans=np.array([0.0, 0.0, 0.0]), scale=1.0, data_device="cuda", device="cuda", *,
+                 invdepthmap=None, depth_params=None):
         self.uid = uid
         self.colmap_id = colmap_id
         self.R = R
@@ -81,6 +89,20 @@ class Camera:
         self.image_height = self.original_image.shape[1]
         if gt_alpha_mask is not None:
             self.original_image *= gt_alpha_mask.to(self.data_device)
+        self.invdepthmap, self.depth_mask, self.depth_reliable = None, None, False
+        if invdepthmap is not None:
+            m = torch.as_tensor(invdepthmap, dtype=torch.float32).reshape(1, self.image_height, self.image_width)
+            m = m.to(self.data_device).clamp(min=0.0)
+            self.depth_mask = torch.ones_like(m)
+            self.depth_reliable = True
+            if depth_params is not None:
+                if (depth_params["scale"] < 0.2 * depth_params["med_scale"]
+                        or depth_params["scale"] > 5 * depth_params["med_scale"]):
+                    self.depth_reliable = False
+                    self.depth_mask = torch.zeros_like(m)
+                if depth_params["scale"] > 0:
+                    m = m * float(depth_params["scale"]) + float(depth_params["offset"])
+            self.invdepthmap = m
         self.zfar = 100.0
         self.znear = 0.01
         self.trans = trans
@@ -260,14 +282,31 @@ def load_resolution(orig_w: int, orig_h: int, resolution, resolution_scale: floa
     return int(orig_w / scale), int(orig_h / scale)
 
 
+def load_invdepth(path: str, resolution, device="cuda") -> torch.Tensor:
+    """The prior of ``path`` (``dataset_readers.decode_invdepth``: ``uint16 / 65536``) as ``[1, H, W]`` float32 on ``device``
+    at ``resolution = (W, H)``: resized with ``interpolate(mode="bilinear", align_corners=False, antialias=False)``, the
+    sampling rule of ``cv2.INTER_LINEAR`` that upstream resizes with (not claimed bit-equal to OpenCV's fixed-point
+    arithmetic).  Once per image, at load."""
+    m = torch.from_numpy(decode_invdepth(path)).to(device)[None, None]
+    W, H = int(resolution[0]), int(resolution[1])
+    if tuple(m.shape[-2:]) != (H, W):
+        m = torch.nn.functional.interpolate(m, size=(H, W), mode="bilinear", align_corners=False, antialias=False)
+    return m[0]
+
+
 def load_cam(args, id, cam_info, resolution_scale, device="cuda") -> Camera:
-    """``loadCam``: decode on the host, then composite / resize / convert on ``device``."""
+    """``loadCam``: decode on the host, then composite / resize / convert on ``device``.  A camera whose ``CameraInfo``
+    names a depth prior gets it through ``load_invdepth``; any other camera is built by the calls made before priors."""
     orig_w, orig_h = cam_info.image.size
     resolution = load_resolution(orig_w, orig_h, args.resolution, resolution_scale)
     target = image_ingest.load_image(decode_image(cam_info), resolution, device, composite_bg=cam_info.composite_bg)
+    prior = {}
+    if getattr(cam_info, "depth_path", ""):
+        prior = {"invdepthmap": load_invdepth(cam_info.depth_path, resolution, device),
+                 "depth_params": cam_info.depth_params}
     return Camera(colmap_id=cam_info.uid, R=cam_info.R, T=cam_info.T, FoVx=cam_info.FovX, FoVy=cam_info.FovY,
                   image=target, gt_alpha_mask=None, image_name=cam_info.image_name, uid=id,
-                  data_device=args.data_device, device=device)
+                  data_device=args.data_device, device=device, **prior)
 
 
 loadCam = load_cam
@@ -297,10 +336,13 @@ def searchForMaxIteration(folder: str) -> int:
 
 class Scene:
     """``scene/__init__.py:21-93``.  defer_cameras: stop after the host work (readers, ``input.ply``, ``cameras.json``,
-    shuffle, ``cameras_extent``, the model's initialisation) and leave the images to a later ``load_cameras()``."""
+    shuffle, ``cameras_extent``, the model's initialisation) and leave the images to a later ``load_cameras()``.
+    depth_prior_mode: the ``OptimizationParams.depth_prior_mode`` the scene will be trained with; read only with
+    ``args.depths``.  Priors without a ``depth_params.json`` are raw monocular maps, meaningless under the fixed identity
+    affine of ``"l1"``: that combination is a ``ValueError``."""
 
     def __init__(self, args, gaussians, load_iteration=None, shuffle=True, resolution_scales=[1.0], *,
-                 defer_cameras=False, device="cuda"):
+                 defer_cameras=False, device="cuda", depth_prior_mode="l1"):
         self.model_path = args.model_path
         self.loaded_iter = None
         self.gaussians = gaussians
@@ -315,16 +357,21 @@ class Scene:
             print("Loading trained model at iteration {}".format(self.loaded_iter))
         self.train_cameras = {}
         self.test_cameras = {}
+        depths = {"depths": args.depths} if getattr(args, "depths", "") else {}     # no prior: the readers' old calls
 
         if os.path.exists(os.path.join(args.source_path, "sparse")):
-            scene_info = sceneLoadTypeCallbacks["Colmap"](args.source_path, args.images, args.eval)
+            scene_info = sceneLoadTypeCallbacks["Colmap"](args.source_path, args.images, args.eval, **depths)
         elif os.path.exists(os.path.join(args.source_path, "transforms_train.json")):
             print("Found transforms_train.json file, assuming Blender data set!")
-            scene_info = sceneLoadTypeCallbacks["Blender"](args.source_path, args.white_background, args.eval)
+            scene_info = sceneLoadTypeCallbacks["Blender"](args.source_path, args.white_background, args.eval, **depths)
         else:
             raise ValueError(f"Could not recognize scene type of {args.source_path!r}: neither sparse/ nor "
                              f"transforms_train.json is there")
         self.scene_info = scene_info
+        if depths and depth_prior_mode == "l1" and all(c.depth_params is None for c in scene_info.train_cameras):
+            raise ValueError(f"depths={args.depths!r} without sparse/0/depth_params.json: raw depth priors have no scale or "
+                             f"offset, so depth_prior_mode='l1' (a fixed identity affine) is meaningless on them; train "
+                             f"with depth_prior_mode='aligned_l1' or 'pearson', which fit the alignment per frame")
 
         if not self.loaded_iter:
             os.makedirs(self.model_path, exist_ok=True)
@@ -376,5 +423,5 @@ class Scene:
         return self.test_cameras[scale]
 
 
-__all__ = ["ModelParams", "Camera", "MiniCam", "PoseCamera", "so3_exp", "pose_transforms", "Scene", "load_cam", "loadCam", "load_resolution",
+__all__ = ["ModelParams", "Camera", "MiniCam", "PoseCamera", "so3_exp", "pose_transforms", "Scene", "load_cam", "loadCam", "load_invdepth", "load_resolution",
            "cameraList_from_camInfos", "camera_to_JSON", "searchForMaxIteration"]

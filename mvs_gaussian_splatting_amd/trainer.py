@@ -18,10 +18,12 @@ import torch
 
 from .bilagrid import bilateral_grid_tv_loss, slice_bilateral_grid
 from .densify import densify_and_prune, is_fork
+from .depth_prior import depth_prior_loss
 from .losses import add_densification_stats, l1_dssim_loss, opacity_sparsity_loss
 from .mcmc import add_new_gs, inject_noise, mcmc_regularizer, relocate_gs
 from .mvs import multi_view_geo_loss, multi_view_ncc_loss
 from .normal_consistency import normal_consistency_loss
+from .optim import expon_lr_func
 from .renderer import render
 from .surface import blend_plane_depth, surface_depth
 from .synthetic import PipelineParams  # noqa: F401  (the two parameter classes live side by side)
@@ -106,6 +108,12 @@ class OptimizationParams:
     # threshold; read only under strategy "default"; False leaves the iteration as it is
     abs_grad = False
     densify_abs_grad_threshold = 0.0008
+    # upstream 3DGS's depth-prior regularisation (depth_prior.py; scene.Camera.invdepthmap): the weight decays from init to
+    # final over `iterations` (optim.expon_lr_func) and the term is `depth_prior_mode`, "l1" (upstream's, under the affine of
+    # depth_params.json), "aligned_l1" or "pearson"; read only on a camera that carries a reliable prior
+    depth_l1_weight_init = 1.0
+    depth_l1_weight_final = 0.01
+    depth_prior_mode = "l1"
 
     def __init__(self, **overrides):
         for k, v in overrides.items():
@@ -124,6 +132,15 @@ def schedule(opt, iteration: int, white_background: bool = False) -> dict:
     return {"sh_up": iteration % 1000 == 0, "stats": stats, "densify": densify,
             "size_threshold": 20 if iteration > opt.opacity_reset_interval else None,
             "reset": reset, "step": iteration < opt.iterations}
+
+
+def depth_prior_weight(opt, iteration: int) -> float:
+    """The weight of the depth-prior term at ``iteration``: upstream's ``get_expon_lr_func(depth_l1_weight_init,
+    depth_l1_weight_final, max_steps=iterations)`` -- ``init`` at iteration 0, ``final`` at ``opt.iterations``, log-linear
+    in between; 0 when both are 0."""
+    return float(expon_lr_func(float(getattr(opt, "depth_l1_weight_init", 0.0)),
+                               float(getattr(opt, "depth_l1_weight_final", 0.0)),
+                               max_steps=int(opt.iterations))(iteration))
 
 
 def training_iteration(model, camera, opt, pipe, background, iteration, *, dataset=None, cameras_extent,
@@ -210,7 +227,20 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
     ``abs_grad_threshold=opt.densify_abs_grad_threshold``.  The absolute gradient is that of the colour loss; with a
     multi-view term on, only the reference frame's is accumulated (the source frame is rendered without the switch).
     ``ValueError`` for a fork model, ``strategy="mcmc"`` and ``pose_optimizer``.  ``abs_grad = False``: exactly the calls
-    made without it."""
+    made without it.
+    A camera that carries a reliable depth prior (``getattr(camera, "depth_reliable", False)``: ``scene.Camera`` built with
+    ``invdepthmap=``) while ``depth_prior_weight(opt, iteration) > 0``: the frame is rendered with
+    ``return_depth=True`` and ``weight * depth_prior_loss(invdepth, camera.invdepthmap, camera.depth_mask,
+    mode=opt.depth_prior_mode)`` joins the loss before the one ``backward``; combinations, statistics and refusals are
+    those of ``depth_loss`` frames, and the term adds to ``depth_loss`` when both are given.  ``ValueError`` for an unknown
+    ``opt.depth_prior_mode``, before anything is rendered.  A camera without a prior, or an unreliable one: exactly the
+    calls made without it."""
+    prior_weight = depth_prior_weight(opt, iteration) if getattr(camera, "depth_reliable", False) else 0.0
+    prior_on = prior_weight > 0.0
+    if prior_on:
+        prior_mode = getattr(opt, "depth_prior_mode", "l1")
+        if prior_mode not in ("l1", "aligned_l1", "pearson"):
+            raise ValueError(f"opt.depth_prior_mode must be 'l1', 'aligned_l1' or 'pearson', got {prior_mode!r}")
     strategy = getattr(opt, "strategy", "default")
     if strategy not in ("default", "mcmc"):
         raise ValueError(f"strategy must be 'default' or 'mcmc', got {strategy!r}")
@@ -296,7 +326,7 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
     render_kwargs = dict(grow_dir=flag("grow_dir"), densify_grad_threshold=opt.densify_grad_threshold,
                          iteration=iteration, opt=opt, continous_dir=flag("continous_dir"),
                          grow_distance=flag("grow_distance"), modelcg=dataset, cameras_extent=cameras_extent,
-                         **({"return_depth": True} if depth_loss is not None or normal_on or mv_on else {}),
+                         **({"return_depth": True} if depth_loss is not None or normal_on or mv_on or prior_on else {}),
                          **({"return_normals": True} if normal_on or ncc_on else {}),
                          **({"return_distortion": True} if dist_on else {}),
                          **({"return_median_depth": True} if median_on else {}),
@@ -315,6 +345,10 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
     if depth_loss is not None:
         depth_target, depth_weight = depth_loss
         loss = loss + float(depth_weight) * (pkg["invdepth"] - depth_target.to(pkg["invdepth"].device)).abs().mean()
+    if prior_on:
+        dev = pkg["invdepth"].device
+        loss = loss + prior_weight * depth_prior_loss(pkg["invdepth"], camera.invdepthmap.to(dev),
+                                                      camera.depth_mask.to(dev), mode=prior_mode)
     if normal_on:
         n_depth, n_alpha = pkg["depth"], pkg["alpha"]
         if unbiased:
@@ -403,4 +437,4 @@ def load_checkpoint(model, path: str, opt, optimizer_cls=None) -> int:
     return int(first_iter)
 
 
-__all__ = ["OptimizationParams", "PipelineParams", "schedule", "training_iteration", "save_checkpoint", "load_checkpoint"]
+__all__ = ["OptimizationParams", "PipelineParams", "schedule", "depth_prior_weight", "training_iteration", "save_checkpoint", "load_checkpoint"]
