@@ -18,6 +18,14 @@ SH degree steps, densification, opacity resets, the optional opacity sparsity te
                              [--lambda_multi_view_ncc L [--multi_view_ncc_samples N] [--multi_view_patch_radius R]]
                              [-d DIR [--depth_prior_mode l1|aligned_l1|pearson] [--depth_l1_weight_init W]
                               [--depth_l1_weight_final W]]
+                             [--masks DIR [--mask_normalize image|mask] [--no_mask_photometric] [--lambda_alpha_mask L]]
+
+``--masks DIR`` (with ``-s``; off by default) trains under per-image masks: ``DIR/<image stem>.png`` or COLMAP's
+``DIR/<image file name>.png`` for every training image, ``DIR`` under the scene or absolute, non-zero keeps the pixel.  The
+colour loss then ignores what a mask hides (``masked_loss.py``), normalised by the image (``--mask_normalize image``,
+upstream 3DGS's and gsplat's rule) or by the mask's area (``mask``); ``--no_mask_photometric`` leaves the colour loss
+unmasked.  ``--lambda_alpha_mask L`` adds ``L`` times the binary cross-entropy of the rendered opacity against the mask: the
+silhouette term of object captures, which keeps the background empty before meshing.
 
 ``-d DIR`` (with ``-s``; upstream 3DGS's option, off by default) regularises training with a per-image inverse-depth prior:
 ``<scene>/DIR/<image stem>.png``, 16-bit, for every training image, aligned by ``<scene>/sparse/0/depth_params.json`` when
@@ -212,11 +220,14 @@ def train_scene(args, dev):
     from mvs_gaussian_splatting_amd import ModelParams, Scene
     dataset = ModelParams(source_path=args.source_path, model_path=args.model_path, images=args.images,
                           resolution=args.resolution, white_background=args.white_background,
-                          data_device=args.data_device, eval=args.eval, **({"depths": args.depths} if args.depths else {}))
+                          data_device=args.data_device, eval=args.eval, **({"depths": args.depths} if args.depths else {}),
+                          **({"masks": args.masks} if args.masks else {}))
     n = args.iterations
     over = dict(opacitysparse=args.opacitysparse, optimizer_type=args.optimizer_type,
                 depth_l1_weight_init=args.depth_l1_weight_init, depth_l1_weight_final=args.depth_l1_weight_final,
                 depth_prior_mode=args.depth_prior_mode,
+                mask_photometric=not args.no_mask_photometric, mask_normalize=args.mask_normalize,
+                lambda_alpha_mask=args.lambda_alpha_mask,
                 exposure_lr_init=args.exposure_lr_init, exposure_lr_final=args.exposure_lr_final,
                 exposure_lr_delay_steps=args.exposure_lr_delay_steps, exposure_lr_delay_mult=args.exposure_lr_delay_mult,
                 **strategy_options(args))
@@ -352,6 +363,17 @@ def main(argv=None):
                     default=OptimizationParams.depth_prior_mode,
                     help="with -d: l1 is upstream's term and needs sparse/0/depth_params.json; aligned_l1 and pearson fit "
                          "the scale and shift per frame")
+    ap.add_argument("--masks", default="", metavar="DIR",
+                    help="with -s: the folder of per-image mask PNGs (non-zero keeps the pixel), under the scene or "
+                         "absolute; trains under them (masked_loss.py)")
+    ap.add_argument("--mask_normalize", choices=("image", "mask"), default=OptimizationParams.mask_normalize,
+                    help="with --masks: divide the masked colour loss by the image's size (upstream 3DGS, gsplat) or by "
+                         "the mask's area")
+    ap.add_argument("--no_mask_photometric", action="store_true",
+                    help="with --masks: leave the colour loss unmasked (the masks then feed only --lambda_alpha_mask "
+                         "and the depth prior)")
+    ap.add_argument("--lambda_alpha_mask", type=float, default=OptimizationParams.lambda_alpha_mask, metavar="L",
+                    help="with --masks: weight of the rendered opacity's cross-entropy against the mask; 0: off")
     ap.add_argument("--out", default=os.path.dirname(os.path.abspath(__file__)))
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 44
+#define GSR_ABI_VERSION 45
 
 enum {
   GSR_OK = 0,
@@ -1078,6 +1078,48 @@ size_t gsr_depth_prior_workspace_bytes(int32_t H, int32_t W);
 int gsr_depth_prior_fwd_bwd(const float* invdepth, const float* prior, const float* weight, int32_t H, int32_t W,
                             int32_t mode, double scale, double offset, double* record, float* grad, void* workspace,
                             size_t workspace_bytes, void* stream);
+
+/* ---- Training under a per-image mask, ABI v45 (csrc/masked_loss.hip; masked_loss.py).
+ * gsr_masked_l1_dssim_loss_fwd_bwd: the training loss of gsr_l1_dssim_loss_fwd_bwd (GSR_DSSIM_ONE_MINUS_MEAN) under a mask.
+ * x, gt (device float32 [C,H,W]) and mask (device float32 [H,W], values in [0, 1]: documented, not checked) are contiguous
+ * and 4-byte aligned; 1 <= C <= 65535, 1 <= H W <= 2^28, H <= 16 * 65535.  With x' = m x and y' = m gt, float32 products
+ * rounded once (+0 where m is 0, whatever the images hold there), and S the SSIM map of x', y' (the window, padding and
+ * constants of the unmasked loss):
+ *   GSR_MASKED_LOSS_NORM_IMAGE  L1 = sum|x' - y'| / (C H W), Ds = 1 - sum S / (C H W): upstream 3DGS's and gsplat's rule,
+ *                               the unmasked loss of the pre-multiplied images
+ *   GSR_MASKED_LOSS_NORM_MASK   Z = C sum m; L1 = sum|x' - y'| / Z, Ds = sum_{c,p} m_p (1 - S_cp) / Z; with Z = 0 the loss
+ *                               and every gradient are 0 and the record's degenerate word is 1
+ * loss = (1 - lambda) L1 + lambda Ds, lambda in [0, 1].  record (device, 8-byte aligned, GSR_MASKED_LOSS_RECORD_WORDS
+ * doubles) receives (loss, L1, Ds, Z, sum m (0 in image mode), degenerate 0 / 1, 0, 0).  dL_dx (device [C,H,W] float32, or
+ * NULL: the backward launch is left out) receives dL/dx = m dL/dx', +0 where m is 0; gt and mask get no gradient.  sum m is
+ * reduced on the device (at most GSR_MASKED_LOSS_MAX_BLOCKS partials) and read from device memory by the later launches.
+ * Every sum is one partial per workgroup added by a one-workgroup launch in float64 in a fixed order, no atomics: the same
+ * arguments give the same bits whatever `workspace` (gsr_masked_l1_dssim_workspace_bytes(C, H, W) bytes, 256-byte
+ * aligned) held.  3 (image) or 5 (mask) launches on `stream`, one fewer without dL_dx; every argument is checked before
+ * any HIP call (GSR_E_BADARG: NULL pointer, shape, lambda, unknown normalize; GSR_E_CAPACITY; GSR_E_ALIGN); nothing is
+ * allocated or read back. */
+#define GSR_MASKED_LOSS_NORM_IMAGE 0
+#define GSR_MASKED_LOSS_NORM_MASK 1
+#define GSR_MASKED_LOSS_RECORD_WORDS 8
+#define GSR_MASKED_LOSS_MAX_BLOCKS 1024
+size_t gsr_masked_l1_dssim_workspace_bytes(int32_t C, int32_t H, int32_t W);
+int gsr_masked_l1_dssim_loss_fwd_bwd(const float* x, const float* gt, const float* mask, int32_t C, int32_t H, int32_t W,
+                                     double lambda_dssim, int32_t normalize, double* record, float* dL_dx, void* workspace,
+                                     size_t workspace_bytes, void* stream);
+/* gsr_alpha_mask_loss_fwd_bwd: the silhouette term of a rendered alpha map against the mask, both device float32 [H,W],
+ * contiguous, 4-byte aligned, 1 <= H W <= 2^28.  mode:
+ *   GSR_ALPHA_MASK_L1   mean|a - m|; gradient sign(a - m) / (H W), sign(0) = 0
+ *   GSR_ALPHA_MASK_BCE  -mean(m log a^ + (1 - m) log(1 - a^)), a^ = clamp(a, 1e-6f, 1 - 1e-6f) (float32 constants); gradient
+ *                       (a^ - m) / (a^ (1 - a^)) / (H W), and 0 where a was clamped
+ * evaluated per pixel in float64 and rounded once.  record (device, 8-byte aligned, 4 doubles) receives (loss, H W, mode, 0);
+ * dL_dalpha (device [H,W] float32, or NULL: not written) the gradient; the mask gets none.  One elementwise launch of at most
+ * GSR_MASKED_LOSS_MAX_BLOCKS workgroups and the same fixed-order float64 finish; workspace:
+ * gsr_alpha_mask_workspace_bytes(H, W) bytes, 8-byte aligned.  Checked before any HIP call as above. */
+#define GSR_ALPHA_MASK_L1 0
+#define GSR_ALPHA_MASK_BCE 1
+size_t gsr_alpha_mask_workspace_bytes(int32_t H, int32_t W);
+int gsr_alpha_mask_loss_fwd_bwd(const float* alpha, const float* mask, int32_t H, int32_t W, int32_t mode, double* record,
+                                float* dL_dalpha, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- Multi-view geometric consistency of depth maps and back-projection, ABI v34 (csrc/mvs.hip; mvs.py).
  * The check of MVSNet's / COLMAP's fusion: a reference pixel goes into a source view at its depth, the source's depth is

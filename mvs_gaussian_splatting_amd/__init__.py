@@ -21,6 +21,7 @@ from .tsdf import (TSDFVolume, ContractedTSDFVolume, fuse_views, volume_for_poin
 from .mcmc import mcmc_regularizer, inject_noise, relocate_gs, add_new_gs  # noqa: F401
 from .normal_consistency import normal_consistency_loss, depth_to_normals  # noqa: F401
 from .depth_prior import depth_prior_loss  # noqa: F401
+from .masked_loss import alpha_mask_loss, masked_l1_dssim_loss  # noqa: F401
 from .surface import surface_depth, plane_depth  # noqa: F401
 from .mesh import (connected_components, clean_mesh, simplify_mesh, dilate_mask, vertex_view_counts,  # noqa: F401
                    cull_mesh_by_views, rasterize_mesh, face_normal_map, face_view_counts, cull_invisible_faces)
@@ -44,4 +45,5 @@ __all__ = ["Scene", "Camera", "MiniCam", "PoseCamera", "ModelParams", "load_imag
            "vertex_view_counts", "cull_mesh_by_views", "view_counts_for_views",
            "rasterize_mesh", "face_normal_map", "face_view_counts", "cull_invisible_faces",
            "transform_points", "voxel_down_sample", "estimate_similarity", "align_cameras", "icp_step", "icp_registration",
-           "register_tnt", "load_crop_volume", "crop_points", "depth_prior_loss"]
+           "register_tnt", "load_crop_volume", "crop_points", "depth_prior_loss",
+           "masked_l1_dssim_loss", "alpha_mask_loss"]

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # instead of copying it over the in-tree library
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")
 
-ABI_VERSION = 44
+ABI_VERSION = 45
 
 
 class GsrParams(C.Structure):
@@ -131,6 +131,8 @@ def ROW_POLICY(orig_sel: int, extra: int, child: int) -> int:
 ACT_SCALE_EXP, ACT_ROT_NORMALIZE, ACT_OPACITY_SIGMOID = 1, 2, 4
 BINNING_TWO_LEVEL, BINNING_KEYS64, BINNING_TWO_LEVEL_CULLED = 0, 1, 2
 DSSIM_ONE_MINUS_MEAN, DSSIM_CLAMPED_HALF = 0, 1
+MASKED_LOSS_NORM_IMAGE, MASKED_LOSS_NORM_MASK = 0, 1
+ALPHA_MASK_L1, ALPHA_MASK_BCE = 0, 1
 DEBUG_NO_MINIBLOCK_CULL = 1
 BILAGRID_STAGE_AUTO, BILAGRID_STAGE_CACHE, BILAGRID_STAGE_LDS = 0, 1, 2
 # gsr_eval_image flags and the floats of its per-view record (l1, psnr, ssim, 3 x sum|d|, 3 x sum d^2, 3 x psnr_c)
@@ -341,6 +343,13 @@ SYMBOLS = {
     "gsr_depth_prior_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "gsr_depth_prior_fwd_bwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_double] * 2 + [C.c_void_p] * 3 +
                                 [C.c_size_t, C.c_void_p]),
+    # training under a per-image mask: fused masked L1 + D-SSIM and the alpha-versus-mask term, value and unit gradient
+    # (csrc/masked_loss.hip; masked_loss.py)
+    "gsr_masked_l1_dssim_workspace_bytes": (C.c_size_t, [C.c_int32] * 3),
+    "gsr_masked_l1_dssim_loss_fwd_bwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_double, C.c_int32] +
+                                         [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]),
+    "gsr_alpha_mask_workspace_bytes": (C.c_size_t, [C.c_int32] * 2),
+    "gsr_alpha_mask_loss_fwd_bwd": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 3 + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]),
     # multi-view geometric consistency of depth maps and back-projection to points (csrc/mvs.hip; mvs.py)
     "gsr_mvs_consistency": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_int32,
                                       C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),

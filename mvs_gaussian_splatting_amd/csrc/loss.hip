@@ -10,18 +10,9 @@
 #include "gsr_common.h"
 #include "gsr_entry.h"
 #include "gsr_launch.h"
+#include "ssim_window.h"     // the window, the tile shape and the halo load, shared with masked_loss.hip
 
 namespace gsr {
-
-constexpr int SS_T = 16;                 // output tile edge
-constexpr int SS_R = 5;                  // window radius (11 taps)
-constexpr int SS_H = SS_T + 2 * SS_R;    // halo edge (26)
-
-struct Win11 { float w[11]; };
-
-__device__ inline float halo_load(const float* __restrict__ img, int W, int H, int x, int y) {
-  return (x >= 0 && x < W && y >= 0 && y < H) ? img[(size_t)y * W + x] : 0.0f;
-}
 
 // METRIC = false: the training loss (value partials + the three derivative maps).  METRIC = true: SSIM as a metric
 // (metrics.py:75, csrc/metrics.hip): no derivative maps and no workspace for them, one SSIM partial per block, and the
@@ -181,18 +172,6 @@ __global__ __launch_bounds__(SS_T * SS_T) void ssim_bwd_kernel(const float* __re
     const float sg = d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f);
     dL_dx[o] = ga + 2.0f * xv * gb + yv * gc + l1_scale * sg;
   }
-}
-
-static Win11 make_window() {
-  Win11 win;
-  double g[11], tot = 0.0;
-  for (int i = 0; i < 11; ++i) { g[i] = exp(-(double)((i - 5) * (i - 5)) / (2.0 * 1.5 * 1.5)); tot += g[i]; }
-  // utils/loss_utils.py:23-25 builds the window in float32: exp() per tap, then a float32 normalisation
-  float gf[11], totf = 0.f;
-  for (int i = 0; i < 11; ++i) { gf[i] = (float)g[i]; totf += gf[i]; }
-  for (int i = 0; i < 11; ++i) win.w[i] = gf[i] / totf;
-  (void)tot;
-  return win;
 }
 
 static void launch_l1_dssim(const float* x, const float* gt, int C, int H, int W, float lambda, int dssim_mode,

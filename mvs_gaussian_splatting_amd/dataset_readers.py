@@ -51,6 +51,8 @@ class CameraInfo(NamedTuple):
     width: int
     height: int
     composite_bg: Optional[np.ndarray] = None
+    # the image's training mask (``masks=``): the PNG ``decode_mask`` reads, non-zero keeps the pixel; None for none
+    mask_path: Optional[str] = None
     # upstream 3DGS's depth prior (``-d``): the 16-bit PNG of the image's inverse depth ("" for none) and its entry of
     # ``sparse/0/depth_params.json`` with ``med_scale`` added (None without the file or without an entry)
     depth_path: str = ""
@@ -263,6 +265,44 @@ def _with_depth_priors(train_cams: list, depths_folder: str, depths_params: Opti
     return out
 
 
+def find_mask(masks_folder: str, cam: CameraInfo) -> Optional[str]:
+    """The mask file of a camera: ``<folder>/<image_name>.png`` (the convention of ``examples/extract_mesh.py
+    --cull_masks``), else ``<folder>/<image file name>.png`` (COLMAP's ``img.jpg.png``); None when neither is there."""
+    for name in (cam.image_name, os.path.basename(cam.image_path)):
+        path = os.path.join(masks_folder, name + ".png")
+        if os.path.isfile(path):
+            return path
+    return None
+
+
+def _with_masks(train_cams: list, masks_folder: str) -> list:
+    """The training cameras with their ``mask_path``; a training camera without a mask file is an error."""
+    out = []
+    for c in train_cams:
+        path = find_mask(masks_folder, c)
+        if path is None:
+            raise FileNotFoundError(f"mask of image {c.image_name!r} not found: neither {c.image_name}.png nor "
+                                    f"{os.path.basename(c.image_path)}.png is in {masks_folder}")
+        out.append(c._replace(mask_path=path))
+    return out
+
+
+def decode_mask(path: str) -> np.ndarray:
+    """The ``[h, w]`` uint8 mask of a file, decoded with Pillow: 255 where the pixel is non-zero -- in any channel of a
+    multi-channel file --, else 0.  Non-zero keeps the pixel, as in ``examples/extract_mesh.py``'s ``read_mask`` and in
+    COLMAP; a 0 / 1 label image and a 0 / 255 one are the same mask."""
+    from PIL import Image
+    with Image.open(path) as image:
+        if image.mode == "P":                               # palette indices are not values
+            image = image.convert("RGBA")
+        a = np.array(image)
+    if a.ndim == 3:
+        a = a.any(axis=2)
+    if a.ndim != 2:
+        raise ValueError(f"{path}: a mask must be an image, got an array of shape {a.shape}")
+    return np.ascontiguousarray((a != 0).astype(np.uint8) * np.uint8(255))
+
+
 def readColmapCameras(cam_extrinsics: dict, cam_intrinsics: dict, images_folder: str, open_image=_open_image) -> list:
     cam_infos = []
     for key in cam_extrinsics:
@@ -278,9 +318,11 @@ def readColmapCameras(cam_extrinsics: dict, cam_intrinsics: dict, images_folder:
     return cam_infos
 
 
-def readColmapSceneInfo(path: str, images, eval: bool, llffhold: int = 8, depths: str = "") -> SceneInfo:
+def readColmapSceneInfo(path: str, images, eval: bool, llffhold: int = 8, depths: str = "", masks: str = "") -> SceneInfo:
     """``depths``: upstream's ``-d``, a folder under ``path`` with one 16-bit inverse-depth PNG per training image, aligned
-    by ``sparse/0/depth_params.json`` when that file is there; test cameras of an ``eval`` split carry no prior."""
+    by ``sparse/0/depth_params.json`` when that file is there; test cameras of an ``eval`` split carry no prior.
+    ``masks``: a folder, under ``path`` or absolute, with one mask PNG per training image (``find_mask``); test cameras
+    carry none."""
     sparse = os.path.join(path, "sparse/0")
     try:
         cam_extrinsics = read_extrinsics_binary(os.path.join(sparse, "images.bin"))
@@ -299,6 +341,8 @@ def readColmapSceneInfo(path: str, images, eval: bool, llffhold: int = 8, depths
     if depths:
         train_cam_infos = _with_depth_priors(train_cam_infos, os.path.join(path, depths),
                                              read_depth_params(os.path.join(sparse, "depth_params.json")))
+    if masks:
+        train_cam_infos = _with_masks(train_cam_infos, os.path.join(path, masks))
     nerf_normalization = getNerfppNorm(train_cam_infos)
     ply_path = os.path.join(path, "sparse/0/points3D.ply")
     if not os.path.exists(ply_path):
@@ -341,8 +385,9 @@ def readCamerasFromTransforms(path: str, transformsfile: str, white_background: 
 
 
 def readNerfSyntheticInfo(path: str, white_background: bool, eval: bool, extension: str = ".png",
-                          depths: str = "") -> SceneInfo:
-    """``depths``: as in ``readColmapSceneInfo``; a Blender scene has no ``depth_params.json``, so the priors are raw."""
+                          depths: str = "", masks: str = "") -> SceneInfo:
+    """``depths``: as in ``readColmapSceneInfo``; a Blender scene has no ``depth_params.json``, so the priors are raw.
+    ``masks``: as in ``readColmapSceneInfo``; the alpha channel of the RGBA frames is not taken as a mask."""
     train_cam_infos = readCamerasFromTransforms(path, "transforms_train.json", white_background, extension)
     test_cam_infos = readCamerasFromTransforms(path, "transforms_test.json", white_background, extension)
     if not eval:
@@ -350,6 +395,8 @@ def readNerfSyntheticInfo(path: str, white_background: bool, eval: bool, extensi
         test_cam_infos = []
     if depths:
         train_cam_infos = _with_depth_priors(train_cam_infos, os.path.join(path, depths), None)
+    if masks:
+        train_cam_infos = _with_masks(train_cam_infos, os.path.join(path, masks))
     nerf_normalization = getNerfppNorm(train_cam_infos)
     ply_path = os.path.join(path, "points3d.ply")
     if not os.path.exists(ply_path):

@@ -23,7 +23,7 @@ import torch
 
 from . import image_ingest
 from .exposure import load_exposures, save_exposures
-from .dataset_readers import decode_image, decode_invdepth, fov2focal, sceneLoadTypeCallbacks
+from .dataset_readers import decode_image, decode_invdepth, decode_mask, fov2focal, sceneLoadTypeCallbacks
 from .synthetic import get_projection_matrix, get_world2view2
 
 
@@ -34,6 +34,7 @@ class ModelParams:
     model_path = ""
     images = "images"
     depths = ""              # upstream 3DGS's -d: the folder of per-image inverse-depth PNGs under source_path; "" for none
+    masks = ""               # the folder of per-image training masks (PNG, non-zero keeps), under source_path or absolute; "" for none
     resolution = -1
     white_background = False
     data_device = "cuda"
@@ -66,11 +67,16 @@ class Camera:
     "med_scale"}`` or None.  Negatives are clamped to 0; with an entry whose ``scale`` lies outside ``[0.2, 5] med_scale``
     the prior is unreliable (``depth_reliable = False``, ``depth_mask`` zeros); ``invdepth * scale + offset`` is applied
     when ``scale > 0``.  Attributes: ``invdepthmap`` and ``depth_mask`` (``[1, H, W]`` float32 on ``data_device``) and
-    ``depth_reliable``; without a map None, None and False."""
+    ``depth_reliable``; without a map None, None and False.
+    alpha_mask: the image's training mask (``dataset_readers.decode_mask``), a uint8 ``[h, w]`` array or
+    tensor, 0 to 255, or a float one already in ``[0, 1]`` at the camera's size.  It is kept as the attribute ``alpha_mask``,
+    ``[1, H, W]`` float32 in ``[0, 1]`` on ``data_device``, for the masked losses -- it is NOT multiplied into
+    ``original_image``, which is what ``gt_alpha_mask`` does.  A uint8 mask of another size is resized to the camera's
+    with ``mask_to_float``.  Without one the attribute is None."""
 
     def __init__(self, colmap_id, R, T, FoVx, FoVy, image, gt_alpha_mask, image_name, uid,
                  trans=np.array([0.0, 0.0, 0.0]), scale=1.0, data_device="cuda", device="cuda", *,
-                 invdepthmap=None, depth_params=None):
+                 invdepthmap=None, depth_params=None, alpha_mask=None):
         self.uid = uid
         self.colmap_id = colmap_id
         self.R = R
@@ -103,6 +109,9 @@ class Camera:
                 if depth_params["scale"] > 0:
                     m = m * float(depth_params["scale"]) + float(depth_params["offset"])
             self.invdepthmap = m
+        self.alpha_mask = None
+        if alpha_mask is not None:
+            self.alpha_mask = mask_to_float(alpha_mask, (self.image_width, self.image_height), self.data_device)
         self.zfar = 100.0
         self.znear = 0.01
         self.trans = trans
@@ -113,6 +122,36 @@ class Camera:
         self.full_proj_transform = (self.world_view_transform.unsqueeze(0)
                                     .bmm(self.projection_matrix.unsqueeze(0))).squeeze(0)
         self.camera_center = self.world_view_transform.inverse()[3, :3]
+
+
+def mask_to_float(mask, size, device) -> torch.Tensor:
+    """A training mask as ``[1, H, W]`` float32 in ``[0, 1]`` on ``device``; ``size`` is (width, height).  A uint8 ``[h, w]``
+    mask (0 to 255) of another size is first resized with Pillow's 8-bit bicubic, the filter the photographs are resized
+    with: ``image_ingest.resize_u8`` on a GPU, Pillow itself -- the same bytes -- when ``device`` is the host; then ``/ 255``
+    and a clamp.  A floating-point mask must already have the size and is only clamped."""
+    W, H = int(size[0]), int(size[1])
+    device = torch.device(device)
+    m = torch.as_tensor(mask)
+    if m.dim() == 3 and 1 in (m.shape[0], m.shape[2]):
+        m = m.reshape(m.shape[1], m.shape[2]) if m.shape[0] == 1 else m.reshape(m.shape[0], m.shape[1])
+    if m.dim() != 2 or m.numel() == 0:
+        raise ValueError(f"alpha_mask must be [h, w], got {tuple(torch.as_tensor(mask).shape)}")
+    if m.dtype == torch.uint8:
+        if tuple(m.shape) != (H, W):
+            if device.type == "cuda":
+                m = image_ingest.resize_u8(m.to(device)[:, :, None].contiguous(), (W, H))[:, :, 0]
+            else:
+                from PIL import Image                           # lazy: the package imports without Pillow
+                m = torch.from_numpy(np.array(Image.fromarray(m.cpu().numpy()).resize((W, H), Image.BICUBIC)))
+        # v / 255 from a table rounded on the host: the same float32 whichever device divides
+        m = (torch.arange(256, dtype=torch.float32) / 255.0).to(device)[m.to(device).long()]
+    elif m.dtype.is_floating_point:
+        if tuple(m.shape) != (H, W):
+            raise ValueError(f"a floating-point alpha_mask must be at the camera's size {H} x {W}, got {tuple(m.shape)}")
+        m = m.to(device).to(torch.float32)
+    else:
+        raise TypeError(f"alpha_mask must be uint8 (0 to 255) or floating point (0 to 1), got {m.dtype}")
+    return m.clamp(0.0, 1.0).reshape(1, H, W).contiguous()
 
 
 class MiniCam:
@@ -244,7 +283,7 @@ class PoseCamera(torch.nn.Module):
         if isinstance(b, Camera):
             dev = b.world_view_transform.device
             return Camera(b.colmap_id, R, T, b.FoVx, b.FoVy, b.original_image, None, b.image_name, b.uid,
-                          data_device=b.data_device, device=dev)
+                          data_device=b.data_device, device=dev, alpha_mask=getattr(b, "alpha_mask", None))
         if isinstance(b, MiniCam):
             with torch.no_grad():
                 view, full, _ = self.transforms()
@@ -296,7 +335,8 @@ def load_invdepth(path: str, resolution, device="cuda") -> torch.Tensor:
 
 def load_cam(args, id, cam_info, resolution_scale, device="cuda") -> Camera:
     """``loadCam``: decode on the host, then composite / resize / convert on ``device``.  A camera whose ``CameraInfo``
-    names a depth prior gets it through ``load_invdepth``; any other camera is built by the calls made before priors."""
+    names a depth prior gets it through ``load_invdepth``, one that names a mask gets ``decode_mask``'s array as its
+    ``alpha_mask``; any other camera is built by the calls made before priors and masks."""
     orig_w, orig_h = cam_info.image.size
     resolution = load_resolution(orig_w, orig_h, args.resolution, resolution_scale)
     target = image_ingest.load_image(decode_image(cam_info), resolution, device, composite_bg=cam_info.composite_bg)
@@ -304,6 +344,8 @@ def load_cam(args, id, cam_info, resolution_scale, device="cuda") -> Camera:
     if getattr(cam_info, "depth_path", ""):
         prior = {"invdepthmap": load_invdepth(cam_info.depth_path, resolution, device),
                  "depth_params": cam_info.depth_params}
+    if getattr(cam_info, "mask_path", None):
+        prior["alpha_mask"] = decode_mask(cam_info.mask_path)
     return Camera(colmap_id=cam_info.uid, R=cam_info.R, T=cam_info.T, FoVx=cam_info.FovX, FoVy=cam_info.FovY,
                   image=target, gt_alpha_mask=None, image_name=cam_info.image_name, uid=id,
                   data_device=args.data_device, device=device, **prior)
@@ -358,12 +400,14 @@ class Scene:
         self.train_cameras = {}
         self.test_cameras = {}
         depths = {"depths": args.depths} if getattr(args, "depths", "") else {}     # no prior: the readers' old calls
+        masks = {"masks": args.masks} if getattr(args, "masks", "") else {}         # no masks: likewise
 
         if os.path.exists(os.path.join(args.source_path, "sparse")):
-            scene_info = sceneLoadTypeCallbacks["Colmap"](args.source_path, args.images, args.eval, **depths)
+            scene_info = sceneLoadTypeCallbacks["Colmap"](args.source_path, args.images, args.eval, **depths, **masks)
         elif os.path.exists(os.path.join(args.source_path, "transforms_train.json")):
             print("Found transforms_train.json file, assuming Blender data set!")
-            scene_info = sceneLoadTypeCallbacks["Blender"](args.source_path, args.white_background, args.eval, **depths)
+            scene_info = sceneLoadTypeCallbacks["Blender"](args.source_path, args.white_background, args.eval, **depths,
+                                                           **masks)
         else:
             raise ValueError(f"Could not recognize scene type of {args.source_path!r}: neither sparse/ nor "
                              f"transforms_train.json is there")
@@ -424,4 +468,5 @@ class Scene:
 
 
 __all__ = ["ModelParams", "Camera", "MiniCam", "PoseCamera", "so3_exp", "pose_transforms", "Scene", "load_cam", "loadCam", "load_invdepth", "load_resolution",
+           "mask_to_float",
            "cameraList_from_camInfos", "camera_to_JSON", "searchForMaxIteration"]

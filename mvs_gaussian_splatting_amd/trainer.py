@@ -20,6 +20,7 @@ from .bilagrid import bilateral_grid_tv_loss, slice_bilateral_grid
 from .densify import densify_and_prune, is_fork
 from .depth_prior import depth_prior_loss
 from .losses import add_densification_stats, l1_dssim_loss, opacity_sparsity_loss
+from .masked_loss import alpha_mask_loss, masked_l1_dssim_loss
 from .mcmc import add_new_gs, inject_noise, mcmc_regularizer, relocate_gs
 from .mvs import multi_view_geo_loss, multi_view_ncc_loss
 from .normal_consistency import normal_consistency_loss
@@ -114,6 +115,14 @@ class OptimizationParams:
     depth_l1_weight_init = 1.0
     depth_l1_weight_final = 0.01
     depth_prior_mode = "l1"
+    # training masks (masked_loss.py; scene.Camera.alpha_mask), read only on a camera that carries one:
+    # mask_photometric puts the colour loss under the mask, normalised by the image ("image": upstream 3DGS's and gsplat's
+    # rule) or by the mask's area ("mask"); lambda_alpha_mask > 0 adds that weight times the silhouette term of the
+    # rendered opacity against the mask, alpha_mask_mode "bce" or "l1" (2DGS / NeuS / PGSR object captures)
+    mask_photometric = True
+    mask_normalize = "image"
+    lambda_alpha_mask = 0.0
+    alpha_mask_mode = "bce"
 
     def __init__(self, **overrides):
         for k, v in overrides.items():
@@ -234,6 +243,15 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
     mode=opt.depth_prior_mode)`` joins the loss before the one ``backward``; combinations, statistics and refusals are
     those of ``depth_loss`` frames, and the term adds to ``depth_loss`` when both are given.  ``ValueError`` for an unknown
     ``opt.depth_prior_mode``, before anything is rendered.  A camera without a prior, or an unreliable one: exactly the
+    calls made without it.
+    A camera that carries a training mask (``getattr(camera, "alpha_mask", None)``: ``scene.Camera`` built with
+    ``alpha_mask=``): with ``opt.mask_photometric`` the colour loss is ``masked_l1_dssim_loss(image, gt,
+    mask, opt.lambda_dssim, normalize=opt.mask_normalize)`` where ``l1_dssim_loss`` stands otherwise, after the exposure and
+    the bilateral-grid slice; with ``opt.lambda_alpha_mask > 0`` the frame is rendered with ``return_depth=True`` and
+    ``lambda_alpha_mask * alpha_mask_loss(alpha, mask, mode=opt.alpha_mask_mode)`` joins the loss (statistics,
+    combinations and refusals as on ``depth_loss`` frames); an active depth prior's ``depth_mask`` is multiplied by the
+    mask.  The normal, distortion and multi-view terms do not see the mask.  ``ValueError`` for an unknown
+    ``opt.mask_normalize`` or ``opt.alpha_mask_mode``, before anything is rendered.  A camera without a mask: exactly the
     calls made without it."""
     prior_weight = depth_prior_weight(opt, iteration) if getattr(camera, "depth_reliable", False) else 0.0
     prior_on = prior_weight > 0.0
@@ -241,6 +259,14 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
         prior_mode = getattr(opt, "depth_prior_mode", "l1")
         if prior_mode not in ("l1", "aligned_l1", "pearson"):
             raise ValueError(f"opt.depth_prior_mode must be 'l1', 'aligned_l1' or 'pearson', got {prior_mode!r}")
+    mask = getattr(camera, "alpha_mask", None)
+    mask_color = mask is not None and bool(getattr(opt, "mask_photometric", True))
+    alpha_weight = float(getattr(opt, "lambda_alpha_mask", 0.0)) if mask is not None else 0.0
+    alpha_on = alpha_weight > 0.0
+    if mask_color and getattr(opt, "mask_normalize", "image") not in ("image", "mask"):
+        raise ValueError(f"opt.mask_normalize must be 'image' or 'mask', got {opt.mask_normalize!r}")
+    if alpha_on and getattr(opt, "alpha_mask_mode", "bce") not in ("bce", "l1"):
+        raise ValueError(f"opt.alpha_mask_mode must be 'bce' or 'l1', got {opt.alpha_mask_mode!r}")
     strategy = getattr(opt, "strategy", "default")
     if strategy not in ("default", "mcmc"):
         raise ValueError(f"strategy must be 'default' or 'mcmc', got {strategy!r}")
@@ -326,7 +352,8 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
     render_kwargs = dict(grow_dir=flag("grow_dir"), densify_grad_threshold=opt.densify_grad_threshold,
                          iteration=iteration, opt=opt, continous_dir=flag("continous_dir"),
                          grow_distance=flag("grow_distance"), modelcg=dataset, cameras_extent=cameras_extent,
-                         **({"return_depth": True} if depth_loss is not None or normal_on or mv_on or prior_on else {}),
+                         **({"return_depth": True} if depth_loss is not None or normal_on or mv_on or prior_on or alpha_on
+                            else {}),
                          **({"return_normals": True} if normal_on or ncc_on else {}),
                          **({"return_distortion": True} if dist_on else {}),
                          **({"return_median_depth": True} if median_on else {}),
@@ -335,7 +362,14 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
     pkg = render(camera, model, pipe, bg, **render_kwargs, **({"abs_grad": True} if abs_on else {}))      # :91
     gt = camera.original_image if gt_image is None else gt_image
     image = pkg["render"] if frame_grid is None else slice_bilateral_grid(pkg["render"], frame_grid)
-    loss = l1_dssim_loss(image, gt.to(image.device), opt.lambda_dssim)                          # :99-101
+    if mask_color:
+        loss = masked_l1_dssim_loss(image, gt.to(image.device), mask.to(image.device), opt.lambda_dssim,
+                                    normalize=getattr(opt, "mask_normalize", "image"))
+    else:
+        loss = l1_dssim_loss(image, gt.to(image.device), opt.lambda_dssim)                      # :99-101
+    if alpha_on:
+        loss = loss + alpha_weight * alpha_mask_loss(pkg["alpha"], mask.to(pkg["alpha"].device),
+                                                     mode=getattr(opt, "alpha_mask_mode", "bce"))
     if bilateral_grids is not None:
         loss = loss + float(getattr(opt, "lambda_tv", 10.0)) * bilateral_grid_tv_loss(bilateral_grids.grids)
     if opt.opacitysparse > 0:                                                                   # :102-106
@@ -347,8 +381,9 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
         loss = loss + float(depth_weight) * (pkg["invdepth"] - depth_target.to(pkg["invdepth"].device)).abs().mean()
     if prior_on:
         dev = pkg["invdepth"].device
-        loss = loss + prior_weight * depth_prior_loss(pkg["invdepth"], camera.invdepthmap.to(dev),
-                                                      camera.depth_mask.to(dev), mode=prior_mode)
+        prior_mask = camera.depth_mask.to(dev) if mask is None else camera.depth_mask.to(dev) * mask.to(dev)
+        loss = loss + prior_weight * depth_prior_loss(pkg["invdepth"], camera.invdepthmap.to(dev), prior_mask,
+                                                      mode=prior_mode)
     if normal_on:
         n_depth, n_alpha = pkg["depth"], pkg["alpha"]
         if unbiased:
