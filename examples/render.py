@@ -4,6 +4,7 @@ write every view of the scene as PNG.
     python examples/render.py -m <model directory> [--iteration N] [--skip_train] [--skip_test]
                               [-s <COLMAP or Blender directory>] [-r ...] [--eval] [--white_background] [--depth]
                               [--use_trained_exp] [--normals] [--depth_normals] [--distortion] [--median_depth] [--plane_depth]
+                              [--point_cloud <.ply or .npz>]
 
 The dataset's location and options come from the ``cfg_args.json`` that ``examples/train.py -s ... -m ...`` left in the
 model directory; ``-s`` and the other switches override it.
@@ -26,6 +27,8 @@ the int32 ``[H,W]`` map of the Gaussian that owns each pixel (-1: none).
 ``--mesh PLY`` also rasterizes that triangle mesh from every view (``rasterize_mesh``, ``face_normal_map``):
 ``.../mesh_depth/%05d.png``, its depth as a 16-bit greyscale PNG scaled like ``--depth`` (``.../mesh_depth/scales.json``; 0: no
 surface), and ``.../mesh_normal/%05d.png``, its view-space face normals as colours, next to the renders.
+``--point_cloud FILE`` renders that file in place of the iteration's ``point_cloud.ply``: a ``.ply``, or by its extension
+the vector-quantised ``.npz`` that ``examples/compress.py`` writes (``GaussianModel.load_compressed``).
 ``--use_trained_exp`` renders every view that has one with the exposure saved in the iteration's ``exposure.json``
 (``examples/train.py --train_exposure``); test views have none and are rendered as they are.
 """
@@ -188,7 +191,8 @@ def render_set(model_path, name, iteration, views, gaussians, pipeline, backgrou
 
 
 def render_sets(dataset, iteration, pipeline, skip_train=False, skip_test=False, depth=False, use_trained_exp=False,
-                normals=False, depth_normals=False, distortion=False, median_depth=False, plane_depth=False, mesh=None):
+                normals=False, depth_normals=False, distortion=False, median_depth=False, plane_depth=False, mesh=None,
+                point_cloud=None):
     with torch.no_grad():
         if mesh is not None:
             from mvs_gaussian_splatting_amd.ply_io import read_ply_mesh
@@ -196,6 +200,8 @@ def render_sets(dataset, iteration, pipeline, skip_train=False, skip_test=False,
             mesh = (torch.from_numpy(mesh_v).to("cuda"), torch.from_numpy(mesh_f).to("cuda"))
         gaussians = GaussianModel(dataset.sh_degree)
         scene = Scene(dataset, gaussians, load_iteration=iteration, shuffle=False)
+        if point_cloud is not None:                              # this file instead of the iteration's point_cloud.ply
+            (gaussians.load_compressed if point_cloud.endswith(".npz") else gaussians.load_ply)(point_cloud)
         bg_color = [1, 1, 1] if dataset.white_background else [0, 0, 0]
         background = torch.tensor(bg_color, dtype=torch.float32, device="cuda")
         if use_trained_exp and gaussians.pretrained_exposures is None:
@@ -235,6 +241,9 @@ def main(argv=None):
     ap.add_argument("--use_trained_exp", action="store_true", help="apply the saved per-image exposures")
     ap.add_argument("--mesh", default=None, metavar="PLY",
                     help="also rasterize this triangle mesh from every view: mesh_depth/ (16-bit) and mesh_normal/ PNGs")
+    ap.add_argument("--point_cloud", default=None, metavar="FILE",
+                    help="render this file instead of the iteration's point_cloud.ply: a .ply, or the .npz of "
+                         "examples/compress.py (chosen by extension)")
     args = ap.parse_args(argv)
     fields = {}
     cfg = os.path.join(args.model_path, "cfg_args.json")
@@ -250,7 +259,8 @@ def main(argv=None):
     print("Rendering " + args.model_path)
     render_sets(dataset, args.iteration, PipelineParams(), args.skip_train, args.skip_test, args.depth,
                 args.use_trained_exp, args.normals, args.depth_normals, args.distortion, args.median_depth,
-                **({"plane_depth": True} if args.plane_depth else {}), **({} if args.mesh is None else {"mesh": args.mesh}))
+                **({"plane_depth": True} if args.plane_depth else {}), **({} if args.mesh is None else {"mesh": args.mesh}),
+                **({} if args.point_cloud is None else {"point_cloud": args.point_cloud}))
 
 
 if __name__ == "__main__":

@@ -3,6 +3,8 @@ a set of orbit views through the drop-in ``render`` and write them as binary PPM
 
     python examples/render_ply.py point_cloud.ply out_dir [n_views] [width] [height]
 
+A path that ends in ``.npz`` is read as the vector-quantised file of ``compress.save_compressed`` instead.
+
 By default the model is rendered in the order the PLY stores it: the images are then those of the reference's stable
 index-order sort.  ``render_set(..., spatial_order=True)`` (opt-in) puts the loaded model along a Morton curve first
 (``mvs_gaussian_splatting_amd/layout.py``: frames 5-7 % faster at 6 M Gaussians, but equal-depth ties inside a tile may blend
@@ -14,6 +16,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from mvs_gaussian_splatting_amd.compress import load_compressed  # noqa: E402
 from mvs_gaussian_splatting_amd.graphed import GraphedRenderer  # noqa: E402
 from mvs_gaussian_splatting_amd.layout import reorder_gaussians_  # noqa: E402
 from mvs_gaussian_splatting_amd.metrics import to_uint8_hwc  # noqa: E402
@@ -25,7 +28,12 @@ class PlyModel:
     """The attributes ``render`` reads from ``GaussianModel`` (``scene/gaussian_model.py:151-194``)."""
 
     def __init__(self, path, device, max_sh_degree=3):
-        for k, v in load_ply(path, max_sh_degree, device).items():
+        if str(path).endswith(".npz"):                       # the vector-quantised file (compress.py), by extension
+            tensors = load_compressed(path).decode(device)
+            max_sh_degree = tensors["active_sh_degree"]
+        else:
+            tensors = load_ply(path, max_sh_degree, device)
+        for k, v in tensors.items():
             setattr(self, k, v)
         self.max_sh_degree = max_sh_degree
         self.scaling_activation, self.opacity_activation = torch.exp, torch.sigmoid

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 45
+#define GSR_ABI_VERSION 46
 
 enum {
   GSR_OK = 0,
@@ -1120,6 +1120,39 @@ int gsr_masked_l1_dssim_loss_fwd_bwd(const float* x, const float* gt, const floa
 size_t gsr_alpha_mask_workspace_bytes(int32_t H, int32_t W);
 int gsr_alpha_mask_loss_fwd_bwd(const float* alpha, const float* mask, int32_t H, int32_t W, int32_t mode, double* record,
                                 float* dL_dalpha, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- k-means vector quantisation of attribute rows, ABI v46 (csrc/kmeans.hip, csrc/kmeans_math.h; compress.py;
+ * DESIGN.md §7.33).  All arrays are device memory, contiguous, row-major; 1 <= D <= GSR_KMEANS_MAX_D,
+ * 1 <= K <= GSR_KMEANS_MAX_K, 1 <= N <= 2^31 - 1.  The rule (kmeans_math.h), for a point x[D] and a code c[D]:
+ *   dot = fmaf(x[D-1], c[D-1], ... fmaf(x[0], c[0], 0.0f)), cnorm = the same chain of c with itself,
+ *   score = fmaf(-2.0f, dot, cnorm); index = the code of the smallest score, the smallest index among equal scores;
+ *   dist2 = max(0, xnorm + score) with xnorm the chain of x with itself (a diagnostic).
+ * Inputs are expected finite (compress.py refuses others); nothing here checks values.
+ * gsr_kmeans_code_norms: cnorm[K] of codebook [K,D]; one launch.
+ * gsr_kmeans_assign: index_out int32 [N] and, unless NULL, dist2_out float [N], of x [N,D] against codebook [K,D] with the
+ *   cnorm that gsr_kmeans_code_norms wrote; one launch, the dot products on v_mfma_f32_32x32x2_f32, whose accumulator is
+ *   that fmaf chain bit for bit.  No atomics; the same bits from run to run and whatever the order of the rows of x.
+ * gsr_kmeans_assign_valu: the same rule and the same bits on the vector ALU, D <= 4 only (GSR_E_BADARG above): the
+ *   cross-check of the matrix-core path.
+ * gsr_kmeans_update: the new centres.  keys_sorted int64 [N] and order int64 [N] are the caller's stable ascending sort of
+ *   the indices (values and permutation), head uint8 [N] what gsr_simplify_run_heads gives for keys_sorted.  For every code
+ *   c with rows: codebook[c] = (float)(sum_i w_i x_i / sum_i w_i), float64 sums over its rows in ascending row index from
+ *   the first row on, the products exact, one rounding to float32; weights float [N] or NULL (w = 1).  A code without a row
+ *   or with sum w = 0 keeps its centre and adds 1 to counters[0]; counters[1] becomes 1 if an index lies outside 0..K-1
+ *   or a slot of order outside 0..N-1 (such rows are skipped).  counters (int32 [2]) is only ever added to / or-ed: the
+ *   caller zeroes it once.  runs: int32 [2 K] workspace.  One memset and two launches.
+ * Every call checks its arguments before any HIP call (GSR_E_BADARG: NULL pointer, a size outside its range; GSR_E_ALIGN:
+ * float / int32 arrays 4-byte, int64 arrays 8-byte), is asynchronous on `stream`, allocates nothing and reads nothing back. */
+#define GSR_KMEANS_MAX_D 64
+#define GSR_KMEANS_MAX_K 65536
+int gsr_kmeans_code_norms(const float* codebook, int32_t K, int32_t D, float* cnorm, void* stream);
+int gsr_kmeans_assign(const float* x, int64_t N, int32_t D, const float* codebook, const float* cnorm, int32_t K,
+                      int32_t* index_out, float* dist2_out, void* stream);
+int gsr_kmeans_assign_valu(const float* x, int64_t N, int32_t D, const float* codebook, const float* cnorm, int32_t K,
+                           int32_t* index_out, float* dist2_out, void* stream);
+int gsr_kmeans_update(const float* x, const float* weights, int64_t N, int32_t D, const int64_t* keys_sorted,
+                      const int64_t* order, const uint8_t* head, int32_t K, int32_t* runs, float* codebook,
+                      int32_t* counters, void* stream);
 
 /* ---- Multi-view geometric consistency of depth maps and back-projection, ABI v34 (csrc/mvs.hip; mvs.py).
  * The check of MVSNet's / COLMAP's fusion: a reference pixel goes into a source view at its depth, the source's depth is

@@ -30,6 +30,8 @@ from .geometry_eval import (transform_points, voxel_down_sample, estimate_simila
                             icp_step, icp_registration, register_tnt, load_crop_volume, crop_points)
 from .mvs import (select_source_views, depth_consistency, backproject_depth, fuse_depth_points,  # noqa: F401
                   multi_view_geo_loss, multi_view_ncc_loss, gray_image)
+from .compress import (kmeans_assign, kmeans, compress_model, CompressedGaussians, save_compressed,  # noqa: F401
+                       load_compressed)
 
 __all__ = ["Scene", "Camera", "MiniCam", "PoseCamera", "ModelParams", "load_image", "load_image_host",
            "GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "render", "l1_loss", "apply_exposure", "save_exposures", "load_exposures", "l1_dssim_loss",
@@ -46,4 +48,5 @@ __all__ = ["Scene", "Camera", "MiniCam", "PoseCamera", "ModelParams", "load_imag
            "rasterize_mesh", "face_normal_map", "face_view_counts", "cull_invisible_faces",
            "transform_points", "voxel_down_sample", "estimate_similarity", "align_cameras", "icp_step", "icp_registration",
            "register_tnt", "load_crop_volume", "crop_points", "depth_prior_loss",
-           "masked_l1_dssim_loss", "alpha_mask_loss"]
+           "masked_l1_dssim_loss", "alpha_mask_loss",
+           "kmeans_assign", "kmeans", "compress_model", "CompressedGaussians", "save_compressed", "load_compressed"]

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # instead of copying it over the in-tree library
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")
 
-ABI_VERSION = 45
+ABI_VERSION = 46
 
 
 class GsrParams(C.Structure):
@@ -339,6 +339,15 @@ SYMBOLS = {
     "gsr_icp_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "gsr_icp_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float,
                                      C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    # k-means vector quantisation: code norms, assignment on the matrix cores (and its vector-ALU cross-check for D <= 4),
+    # atomic-free centre update (csrc/kmeans.hip; compress.py)
+    "gsr_kmeans_code_norms": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "gsr_kmeans_assign": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
+    "gsr_kmeans_assign_valu": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    "gsr_kmeans_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     # depth-prior loss of a rendered inverse-depth map, value and unit gradient (csrc/depth_prior.hip; depth_prior.py)
     "gsr_depth_prior_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "gsr_depth_prior_fwd_bwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_double] * 2 + [C.c_void_p] * 3 +

@@ -394,5 +394,28 @@ class GaussianModel:
             setattr(self, a, nn.Parameter(tensors[a].requires_grad_(True)))
         self.active_sh_degree = self.max_sh_degree
 
+    # ---- vector-quantised file (compress.py) -----------------------------------------------------------
+    def save_compressed(self, path, **kw):
+        """``compress.compress_model(self, **kw)`` written to ``path`` (one ``.npz``); returns the container."""
+        from . import compress
+        cg = compress.compress_model(self, **kw)
+        compress.save_compressed(path, cg)
+        return cg
+
+    def load_compressed(self, path, device=None):
+        """``load_ply`` for the file ``save_compressed`` writes: the six decoded parameters on ``device``."""
+        from . import compress
+        if device is None:
+            device = self._xyz.device if self._xyz.is_cuda else "cuda"
+        if torch.device(device).type != "cuda" or not torch.cuda.is_available():
+            raise _lib.GsrError("load_compressed needs a ROCm GPU (no CPU path)")
+        cg = compress.load_compressed(path)
+        if cg.sh_degree != self.max_sh_degree:
+            raise ValueError(f"{path}: SH degree {cg.sh_degree} does not match the model's {self.max_sh_degree}")
+        tensors = cg.decode(device)
+        for a in GROUP_ATTR.values():
+            setattr(self, a, nn.Parameter(tensors[a].requires_grad_(True)))
+        self.active_sh_degree = self.max_sh_degree
+
 
 __all__ = ["GaussianModel", "sphere_points", "inverse_sigmoid"]
