@@ -5,12 +5,13 @@
 #include "gsr_common.h"
 #include "gsr_entry.h"
 #include "gsr_launch.h"
+#include "ordered_sum.h"
 
 namespace gsr {
 
 // partials[block] = sum over the block's elements of |x - gt| ; dL_dx = sign(x - gt) * scale.  Streaming, 16 B per lane.
 // No atomics: the block partials are summed in block order by l1_loss_finish_kernel, so the loss is bitwise
-// reproducible from run to run (like loss.hip's ordered sums and the atomic-free backward).
+// reproducible from run to run (the block sum of ordered_sum.h, like loss.hip's, and the atomic-free backward).
 constexpr int L1_THREADS = 1024;
 constexpr int L1_MAX_BLOCKS = 512;     // two 16-wave blocks per CU
 __global__ __launch_bounds__(L1_THREADS) void l1_loss_kernel(const float* __restrict__ x, const float* __restrict__ gt,
@@ -33,15 +34,8 @@ __global__ __launch_bounds__(L1_THREADS) void l1_loss_kernel(const float* __rest
     acc += fabsf(d);
     if (dL_dx) dL_dx[i] = sgn(d) * scale;
   }
-  acc = wave_reduce_add_f32(acc);
-  if ((threadIdx.x & (WAVE - 1)) == 0) wsum[threadIdx.x / WAVE] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s = 0.0f;
-#pragma unroll
-    for (int w = 0; w < L1_THREADS / WAVE; ++w) s += wsum[w];
-    partials[blockIdx.x] = s;
-  }
+  acc = ordered_block_sum<L1_THREADS / WAVE, FROM_ZERO>(acc, wsum);
+  if (threadIdx.x == 0) partials[blockIdx.x] = acc;
 }
 // one wave: lane l sums partials l, l+64, ... in order, then a fixed butterfly
 __global__ __launch_bounds__(WAVE) void l1_loss_finish_kernel(const float* __restrict__ partials, int blocks,

@@ -17,10 +17,11 @@
 //     rounds once.  Every element is written, zero where no pixel touches it.  The order is fixed by the shapes alone:
 //     the same bits from run to run.
 //   * bilagrid_tv_kernel: one lane per grid element computes the element's forward and backward differences along z, y
-//     and x: the forward ones give its share of the value, both give d tv / d element.  Block sums in double (butterfly,
-//     waves in wave order), bilagrid_tv_finish_kernel adds the block slots in a fixed order and rounds once.
+//     and x: the forward ones give its share of the value, both give d tv / d element.  Block sums in double
+//     (ordered_sum.h), bilagrid_tv_finish_kernel adds the block slots in a fixed order and rounds once.
 #include "gsr_common.h"
 #include "gsr_entry.h"
+#include "ordered_sum.h"
 #include "bilagrid_math.h"
 
 namespace gsr {
@@ -164,16 +165,8 @@ __global__ __launch_bounds__(BG_TV_THREADS) void bilagrid_tv_kernel(const float*
     if (dG) dG[e] = (float)grad;
   }
   __shared__ double wave_sum[BG_TV_WAVES];
-  const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-  const double d = wave_reduce_add_f64(value);
-  if (lane == 0) wave_sum[wid] = d;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double b = wave_sum[0];
-#pragma unroll
-    for (int w = 1; w < BG_TV_WAVES; ++w) b += wave_sum[w];
-    slots[blockIdx.x] = b;
-  }
+  const double b = ordered_block_sum<BG_TV_WAVES, FROM_WAVE0>(value, wave_sum);
+  if (threadIdx.x == 0) slots[blockIdx.x] = b;
 }
 
 // One block.  Thread t walks the slots t, t + 256, ...; the 256 sums are added in thread order and rounded once.

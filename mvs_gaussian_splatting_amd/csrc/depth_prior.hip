@@ -2,16 +2,14 @@
 // DESIGN.md §7.31): upstream 3DGS's L1 term under a given affine, the same term under the weighted least-squares fit of
 // the render on the prior, and one minus their weighted Pearson correlation.  The arithmetic of a pixel and of the fit is
 // depth_prior_math.h, float64 with no fused multiply-add (this file is compiled with -ffp-contract=off), as
-// tests/depth_prior_host_check.cpp builds it on the host.  The reduction is the one of csrc/icp.hip.
+// tests/depth_prior_host_check.cpp builds it on the host.  The reduction is the word form of ordered_sum.h.
 //
 //   * depth_prior_sums_kernel    at most DEPTH_PRIOR_MAX_BLOCKS workgroups of 256 lanes.  Lane t of workgroup g takes the
 //                                pixels g 256 + t, + gridDim 256, ... in ascending order and adds the six terms of every
-//                                valid pixel to its own float64 sums, and 1 to its count.  The wave adds its 64 lanes with
-//                                the xor butterfly (distance 32 first), lane 0 of every wave leaves 7 words in LDS, and
-//                                lanes 0..6 add the four waves' words in wave order and store the workgroup's partial at
-//                                partials[word][g].
+//                                valid pixel to its own float64 sums, and 1 to its count.  Lanes 0..6 store the
+//                                workgroup's 7 words (ordered_block_words) at partials[word][g].
 //   * depth_prior_fit_kernel     ONE workgroup.  Per word, lane t adds partials[word][t], [t + 256], ... in ascending
-//                                order, then the same butterfly and the same LDS step; lane 0 computes the fit
+//                                order (ordered_read_words), then the same block sum; lane 0 computes the fit
 //                                (depth_prior_fit), stores it and the sums in the workspace's fit block and writes the
 //                                record (for pearson with its loss 1 - r).  Not launched in the l1 mode.
 //   * depth_prior_apply_kernel   the same grid and walk.  The affine and the moments are uniform: kernel arguments in the
@@ -42,6 +40,7 @@
 #include "depth_prior_math.h"
 #include "gsr_common.h"
 #include "gsr_entry.h"
+#include "ordered_sum.h"
 
 namespace gsr {
 
@@ -57,7 +56,7 @@ constexpr int DP_APPLY_WORDS = 1 + DP_APPLY_SUMS;
 constexpr int DP_FIT_BLOCK_WORDS = 32;
 constexpr int DP_FIT_COUNT = 16;
 
-static_assert(DEPTH_PRIOR_SUM_WORDS <= WAVE, "lanes 0..words-1 of the first wave fold the waves' words");
+static_assert(DEPTH_PRIOR_SUM_WORDS == 1 + DEPTH_PRIOR_SUMS, "the count and the sums");
 static_assert(sizeof(DepthPriorFit) == 8 * DEPTH_PRIOR_FIT_WORDS && DEPTH_PRIOR_FIT_WORDS <= DP_FIT_COUNT &&
                   DP_FIT_COUNT + DEPTH_PRIOR_SUM_WORDS <= DP_FIT_BLOCK_WORDS,
               "layout of the fit block");
@@ -73,64 +72,13 @@ inline int dp_blocks(int64_t N) {
 }
 inline int dp_stride_words(int nb) { return (int)align_up((size_t)(nb > 0 ? nb : 1), 32); }
 
-// one result or partial in registers: word 0 is the count
-template <int NS>
-struct DpAcc {
-  long long n;
-  double s[NS];
-};
-
-template <int NS>
-__device__ inline void dp_zero(DpAcc<NS>& acc) {
-  acc.n = 0;
-  for (int k = 0; k < NS; ++k) acc.s[k] = 0.0;
-}
-
-// The sum of the workgroup's 256 accumulators, valid in lanes 0..NS as word `threadIdx.x` (count as the bits of an
-// int64).  Every lane of the workgroup must call it.
-template <int NS>
-__device__ inline unsigned long long dp_block_word(DpAcc<NS>& acc, unsigned long long (*part)[1 + NS]) {
-  for (int d = WAVE / 2; d > 0; d >>= 1) {
-    acc.n += __shfl_xor(acc.n, d, WAVE);
-    for (int k = 0; k < NS; ++k) acc.s[k] += __shfl_xor(acc.s[k], d, WAVE);
-  }
-  const int wave = threadIdx.x / WAVE;
-  if ((threadIdx.x & (WAVE - 1)) == 0) {
-    part[wave][0] = (unsigned long long)acc.n;
-    for (int k = 0; k < NS; ++k) part[wave][1 + k] = (unsigned long long)__double_as_longlong(acc.s[k]);
-  }
-  __syncthreads();
-  unsigned long long word = 0;
-  if (threadIdx.x == 0) {
-    long long n = (long long)part[0][0];
-    for (int w = 1; w < DP_WAVES; ++w) n += (long long)part[w][0];
-    word = (unsigned long long)n;
-  } else if (threadIdx.x < 1 + NS) {
-    double v = __longlong_as_double((long long)part[0][threadIdx.x]);
-    for (int w = 1; w < DP_WAVES; ++w) v += __longlong_as_double((long long)part[w][threadIdx.x]);
-    word = (unsigned long long)__double_as_longlong(v);
-  }
-  return word;
-}
-
-// the partials of `nb` workgroups added per word, lane t taking t, t + 256, ... in ascending order
-template <int NS>
-__device__ inline void dp_read_partials(DpAcc<NS>& acc, const unsigned long long* __restrict__ partials, int nb,
-                                        int stride_words) {
-  dp_zero(acc);
-  for (int g = threadIdx.x; g < nb; g += DP_TRIP) {
-    acc.n += (long long)partials[g];
-    for (int k = 0; k < NS; ++k) acc.s[k] += __longlong_as_double((long long)partials[(size_t)(1 + k) * stride_words + g]);
-  }
-}
-
 __global__ void __launch_bounds__(DP_BLOCK) depth_prior_sums_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                                     const float* __restrict__ w, int64_t N,
                                                                     unsigned long long* __restrict__ partials,
                                                                     int stride_words) {
   __shared__ unsigned long long part[DP_WAVES][DEPTH_PRIOR_SUM_WORDS];
-  DpAcc<DEPTH_PRIOR_SUMS> acc;
-  dp_zero(acc);
+  CountSums<DEPTH_PRIOR_SUMS> acc;
+  acc.zero();
   const int64_t stride = (int64_t)gridDim.x * DP_BLOCK;
   for (int64_t i = (int64_t)blockIdx.x * DP_BLOCK + threadIdx.x; i < N; i += stride) {
     const float xi = x[i], yi = y[i];
@@ -141,7 +89,7 @@ __global__ void __launch_bounds__(DP_BLOCK) depth_prior_sums_kernel(const float*
     acc.n += 1;
     for (int k = 0; k < DEPTH_PRIOR_SUMS; ++k) acc.s[k] += t[k];
   }
-  const unsigned long long word = dp_block_word(acc, part);
+  const unsigned long long word = ordered_block_words<DP_WAVES>(acc, part);
   if (threadIdx.x < DEPTH_PRIOR_SUM_WORDS) partials[(size_t)threadIdx.x * stride_words + blockIdx.x] = word;
 }
 
@@ -151,9 +99,9 @@ __global__ void __launch_bounds__(DP_BLOCK) depth_prior_fit_kernel(const unsigne
                                                                    double* __restrict__ record) {
   __shared__ unsigned long long part[DP_WAVES][DEPTH_PRIOR_SUM_WORDS];
   __shared__ unsigned long long total[DEPTH_PRIOR_SUM_WORDS + 1];
-  DpAcc<DEPTH_PRIOR_SUMS> acc;
-  dp_read_partials(acc, partials, nb, stride_words);
-  const unsigned long long word = dp_block_word(acc, part);
+  CountSums<DEPTH_PRIOR_SUMS> acc;
+  ordered_read_words<DP_TRIP>(acc, partials, nb, stride_words);
+  const unsigned long long word = ordered_block_words<DP_WAVES>(acc, part);
   if (threadIdx.x < DEPTH_PRIOR_SUM_WORDS) total[threadIdx.x] = word;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -218,8 +166,8 @@ __global__ void __launch_bounds__(DP_BLOCK) depth_prior_apply_kernel(const float
     denom = f.Sw;
   }
   const bool live = f.degenerate == 0.0;
-  DpAcc<DP_APPLY_SUMS> acc;
-  dp_zero(acc);
+  CountSums<DP_APPLY_SUMS> acc;
+  acc.zero();
   const int64_t stride = (int64_t)gridDim.x * DP_BLOCK;
   for (int64_t i = (int64_t)blockIdx.x * DP_BLOCK + threadIdx.x; i < N; i += stride) {
     const float xi = x[i], yi = y[i];
@@ -239,7 +187,7 @@ __global__ void __launch_bounds__(DP_BLOCK) depth_prior_apply_kernel(const float
     if (grad) grad[i] = g;
   }
   if (mode != DEPTH_PRIOR_PEARSON) {  // a kernel argument: every lane of every workgroup takes the same side
-    const unsigned long long word = dp_block_word(acc, part);
+    const unsigned long long word = ordered_block_words<DP_WAVES>(acc, part);
     if (threadIdx.x < DP_APPLY_WORDS) partials[(size_t)threadIdx.x * stride_words + blockIdx.x] = word;
   }
 }
@@ -251,9 +199,9 @@ __global__ void __launch_bounds__(DP_BLOCK) depth_prior_finish_kernel(const unsi
                                                                       double* __restrict__ record) {
   __shared__ unsigned long long part[DP_WAVES][DP_APPLY_WORDS];
   __shared__ unsigned long long total[DP_APPLY_WORDS + 1];
-  DpAcc<DP_APPLY_SUMS> acc;
-  dp_read_partials(acc, partials, nb, stride_words);
-  const unsigned long long word = dp_block_word(acc, part);
+  CountSums<DP_APPLY_SUMS> acc;
+  ordered_read_words<DP_TRIP>(acc, partials, nb, stride_words);
+  const unsigned long long word = ordered_block_words<DP_WAVES>(acc, part);
   if (threadIdx.x < DP_APPLY_WORDS) total[threadIdx.x] = word;
   __syncthreads();
   if (threadIdx.x == 0) {

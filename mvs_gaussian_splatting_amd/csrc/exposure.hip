@@ -10,12 +10,13 @@
 //     writes 256 consecutive bytes of each plane.  The sums above are written left to right in float32 and the unit is
 //     built with -ffp-contract=off, so with A = eye(3,4) the products by 1 and 0 and the sums with 0 leave y = x and
 //     dx = g bit for bit (finite inputs; a -0 comes out as +0).
-//   * dA: a lane keeps the 12 sums in double (operands converted before the multiply, so a product is exact), the wave
-//     adds them with an xor butterfly, the block adds its waves in wave order and stores 12 doubles in its own slot of
-//     the workspace; exposure_grad_finish_kernel (one block) adds the slots in a fixed order and rounds once to
-//     float32.  No atomics: dA depends on H, W and the data only, and is the same bits from run to run.
+//   * dA: a lane keeps the 12 sums in double (operands converted before the multiply, so a product is exact), the
+//     block adds them in the fixed order of ordered_sum.h and stores 12 doubles in its own slot of the workspace;
+//     exposure_grad_finish_kernel (one block) adds the slots in a fixed order and rounds once to float32.  No atomics:
+//     dA depends on H, W and the data only, and is the same bits from run to run.
 #include "gsr_common.h"
 #include "gsr_entry.h"
+#include "ordered_sum.h"
 
 namespace gsr {
 
@@ -77,24 +78,10 @@ __global__ __launch_bounds__(EXP_THREADS) void exposure_apply_bwd_kernel(const f
     }
   }
   if constexpr (DA) {
-    // every lane of the block arrives here (a lane without a pixel carries zeros).  Wave: xor butterfly (a lane's
-    // partners are fixed); block: the wave sums in wave order -- as preprocess_bwd_kernel<true> leaves its camera sums.
+    // every lane of the block arrives here (a lane without a pixel carries zeros); term t is folded by lane t
     __shared__ double wave_sum[EXP_WAVES][EXP_TERMS];
-    const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-#pragma unroll
-    for (int t = 0; t < EXP_TERMS; ++t) {
-      double d = acc[t];
-#pragma unroll
-      for (int off = WAVE / 2; off > 0; off >>= 1) d += __shfl_xor(d, off, WAVE);
-      if (lane == 0) wave_sum[wid][t] = d;
-    }
-    __syncthreads();
-    if (threadIdx.x < EXP_TERMS) {
-      double d = wave_sum[0][threadIdx.x];
-#pragma unroll
-      for (int w = 1; w < EXP_WAVES; ++w) d += wave_sum[w][threadIdx.x];
-      slots[(size_t)blockIdx.x * EXP_TERMS + threadIdx.x] = d;
-    }
+    const double d = ordered_block_sum_by_lane<EXP_WAVES>(acc, wave_sum);
+    if (threadIdx.x < EXP_TERMS) slots[(size_t)blockIdx.x * EXP_TERMS + threadIdx.x] = d;
   }
 }
 

@@ -8,12 +8,11 @@
 //   * icp_accumulate_kernel   at most ICP_MAX_BLOCKS workgroups of 256 lanes.  Lane t of workgroup g takes the points
 //                             g 256 + t, + gridDim 256, ... in ascending order and adds the 17 terms of every accepted
 //                             pair (dist2 <= thr2, 0 <= nearest < R) to its own float64 sums, and 1 to its count.  The
-//                             wave adds its 64 lanes with the xor butterfly (distance 32 first), lane 0 of every wave
-//                             leaves 18 words in LDS (576 bytes, the only LDS), and lanes 0..17 add the four waves'
-//                             words in wave order and store the workgroup's partial at partials[word][g].
+//                             workgroup's 18 words are the word form of ordered_sum.h (576 bytes of LDS, the only
+//                             LDS); lanes 0..17 store them at partials[word][g].
 //   * icp_finish_kernel       ONE workgroup of 256 lanes, a launch of its own behind the first on the stream.  Per
 //                             word, lane t adds partials[word][t], [t + 256], ... in ascending order (a trip reads
-//                             ICP_FINISH_TRIP = 256 partials, coalesced), then the same butterfly and the same LDS step.
+//                             ICP_FINISH_TRIP = 256 partials, coalesced), then the same block sum.
 //
 // No atomics of any kind and no ticket: which workgroup finishes first changes nothing.  The order of every addition is
 // a function of Q alone (through the grid size), so a call gives the same bits from run to run and whatever the
@@ -32,6 +31,7 @@
 #include "gsr_common.h"
 #include "gsr_entry.h"
 #include "icp_math.h"
+#include "ordered_sum.h"
 
 namespace gsr {
 
@@ -51,37 +51,8 @@ inline int icp_blocks(int64_t Q) {
   return (int)(nb < ICP_MAX_BLOCKS ? nb : ICP_MAX_BLOCKS);
 }
 
-// one result or partial in registers: word 0 is the count
-struct IcpAcc {
-  long long n;
-  double s[ICP_SUMS];
-};
-
-// The sum of the workgroup's 256 accumulators, valid in lanes 0..ICP_WORDS-1 as word `threadIdx.x` (count as the bits
-// of an int64).  Every lane of the workgroup must call it.
-__device__ inline unsigned long long icp_block_word(IcpAcc& acc, unsigned long long (*part)[ICP_WORDS]) {
-  for (int d = WAVE / 2; d > 0; d >>= 1) {
-    acc.n += __shfl_xor(acc.n, d, WAVE);
-    for (int k = 0; k < ICP_SUMS; ++k) acc.s[k] += __shfl_xor(acc.s[k], d, WAVE);
-  }
-  const int wave = threadIdx.x / WAVE;
-  if ((threadIdx.x & (WAVE - 1)) == 0) {
-    part[wave][0] = (unsigned long long)acc.n;
-    for (int k = 0; k < ICP_SUMS; ++k) part[wave][1 + k] = (unsigned long long)__double_as_longlong(acc.s[k]);
-  }
-  __syncthreads();
-  unsigned long long word = 0;
-  if (threadIdx.x == 0) {
-    long long n = (long long)part[0][0];
-    for (int w = 1; w < ICP_WAVES; ++w) n += (long long)part[w][0];
-    word = (unsigned long long)n;
-  } else if (threadIdx.x < ICP_WORDS) {
-    double v = __longlong_as_double((long long)part[0][threadIdx.x]);
-    for (int w = 1; w < ICP_WAVES; ++w) v += __longlong_as_double((long long)part[w][threadIdx.x]);
-    word = (unsigned long long)__double_as_longlong(v);
-  }
-  return word;
-}
+using IcpAcc = CountSums<ICP_SUMS>;         // one result or partial in registers (ordered_sum.h): word 0 is the count
+static_assert(ICP_WORDS == 1 + ICP_SUMS, "the count and the sums");
 
 __global__ void __launch_bounds__(ICP_BLOCK) icp_transform_kernel(const float* __restrict__ points, int Q, IcpMatrix M,
                                                                   float* __restrict__ out) {
@@ -101,8 +72,7 @@ __global__ void __launch_bounds__(ICP_BLOCK) icp_accumulate_kernel(const float* 
                                                                    int stride_words) {
   __shared__ unsigned long long part[ICP_WAVES][ICP_WORDS];
   IcpAcc acc;
-  acc.n = 0;
-  for (int k = 0; k < ICP_SUMS; ++k) acc.s[k] = 0.0;
+  acc.zero();
   const int64_t stride = (int64_t)gridDim.x * ICP_BLOCK;
   for (int64_t i = (int64_t)blockIdx.x * ICP_BLOCK + threadIdx.x; i < Q; i += stride) {
     const float d = dist2[i];
@@ -115,7 +85,7 @@ __global__ void __launch_bounds__(ICP_BLOCK) icp_accumulate_kernel(const float* 
     acc.n += 1;
     for (int k = 0; k < ICP_SUMS; ++k) acc.s[k] += t[k];
   }
-  const unsigned long long word = icp_block_word(acc, part);
+  const unsigned long long word = ordered_block_words<ICP_WAVES>(acc, part);
   if (threadIdx.x < ICP_WORDS) partials[(size_t)threadIdx.x * stride_words + blockIdx.x] = word;
 }
 
@@ -123,13 +93,8 @@ __global__ void __launch_bounds__(ICP_BLOCK) icp_finish_kernel(const unsigned lo
                                                                int stride_words, unsigned long long* __restrict__ out) {
   __shared__ unsigned long long part[ICP_WAVES][ICP_WORDS];
   IcpAcc acc;
-  acc.n = 0;
-  for (int k = 0; k < ICP_SUMS; ++k) acc.s[k] = 0.0;
-  for (int g = threadIdx.x; g < nb; g += ICP_FINISH_TRIP) {
-    acc.n += (long long)partials[g];
-    for (int k = 0; k < ICP_SUMS; ++k) acc.s[k] += __longlong_as_double((long long)partials[(size_t)(1 + k) * stride_words + g]);
-  }
-  const unsigned long long word = icp_block_word(acc, part);
+  ordered_read_words<ICP_FINISH_TRIP>(acc, partials, nb, stride_words);
+  const unsigned long long word = ordered_block_words<ICP_WAVES>(acc, part);
   if (threadIdx.x < ICP_WORDS) out[threadIdx.x] = word;
 }
 

@@ -1,10 +1,10 @@
 // Training under a per-image mask (include/gsr.h, ABI v45; masked_loss.py): the fused L1 + D-SSIM loss
 // of the masked images x' = m x, y' = m gt with its gradient for x, and the silhouette term of a rendered alpha map
-// against the mask.  The SSIM is the one of csrc/loss.hip -- same window, tile and passes (ssim_window.h) -- on x', y':
+// against the mask.  The SSIM is the one of csrc/loss.hip -- the tile core of ssim_tile.h, but s by a true division -- on x', y':
 //
 //   * ml_mask_sum_kernel      mask mode only.  At most ML_MAX_BLOCKS workgroups of 256 lanes; lane t of workgroup g adds
 //                             the pixels g 256 + t, + gridDim 256, ... of the mask in ascending order in float64; the
-//                             workgroup's sum (ml_block_sum) goes to mask_partials[g].
+//                             workgroup's sum goes to mask_partials[g].
 //   * ml_mask_total_kernel    mask mode only, ONE workgroup: adds the partials, lane t taking t, t + 256, ..., and stores
 //                             sum m and Z = C sum m in the header block.  The later kernels read Z from there: the host
 //                             never sees it.
@@ -25,15 +25,14 @@
 // only what an earlier launch on the stream wrote, every sum has a fixed order, so value and gradient are the same bits
 // from run to run and whatever the workspace held.
 //
-// LDS: the layout of csrc/loss.hip -- rows of 27 and 17 dwords, odd strides, so that the 16 lanes of a tile row and the
-// rows under them fall on different banks in both passes.  Reductions: the xor butterfly over the 64 lanes, one word per
-// wave in LDS, thread 0 adds the waves in order.
+// LDS: the layout of csrc/loss.hip (ssim_tile.h).  Reductions: ordered_sum.h.
 //
 // Safety.  Every global read and write of the tile kernels is under 0 <= x < W, 0 <= y < H; the walks are under i < N.
 // Every barrier is reached by every lane: none sits under a lane-dependent branch.
 #include "gsr_common.h"
 #include "gsr_entry.h"
-#include "ssim_window.h"
+#include "ordered_sum.h"
+#include "ssim_tile.h"
 
 namespace gsr {
 
@@ -54,37 +53,13 @@ inline int ml_blocks(int64_t N) {
   return (int)(nb < ML_MAX_BLOCKS ? nb : ML_MAX_BLOCKS);
 }
 
-// The sums of the workgroup's NV-vectors, valid in thread 0.  Every lane of the workgroup must call it.
-template <int NV, int WAVES>
-__device__ inline void ml_block_sum(double (&v)[NV], double (*part)[NV]) {
-#pragma unroll
-  for (int d = WAVE / 2; d > 0; d >>= 1) {
-#pragma unroll
-    for (int k = 0; k < NV; ++k) v[k] += __shfl_xor(v[k], d, WAVE);
-  }
-  const int wave = threadIdx.x / WAVE;
-  if ((threadIdx.x & (WAVE - 1)) == 0) {
-#pragma unroll
-    for (int k = 0; k < NV; ++k) part[wave][k] = v[k];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-      double s = part[0][k];
-      for (int w = 1; w < WAVES; ++w) s += part[w][k];
-      v[k] = s;
-    }
-  }
-}
-
 __global__ void __launch_bounds__(ML_BLOCK) ml_mask_sum_kernel(const float* __restrict__ mask, int64_t N,
                                                                double* __restrict__ mask_partials) {
   __shared__ double part[ML_WAVES][1];
   double v[1] = {0.0};
   const int64_t stride = (int64_t)gridDim.x * ML_BLOCK;
   for (int64_t i = (int64_t)blockIdx.x * ML_BLOCK + threadIdx.x; i < N; i += stride) v[0] += (double)mask[i];
-  ml_block_sum<1, ML_WAVES>(v, part);
+  ordered_block_sum<ML_WAVES, FROM_WAVE0>(v, part);
   if (threadIdx.x == 0) mask_partials[blockIdx.x] = v[0];
 }
 
@@ -93,7 +68,7 @@ __global__ void __launch_bounds__(ML_BLOCK) ml_mask_total_kernel(const double* _
   __shared__ double part[ML_WAVES][1];
   double v[1] = {0.0};
   for (int g = threadIdx.x; g < nb; g += ML_BLOCK) v[0] += mask_partials[g];
-  ml_block_sum<1, ML_WAVES>(v, part);
+  ordered_block_sum<ML_WAVES, FROM_WAVE0>(v, part);
   if (threadIdx.x == 0) {
     hdr[0] = v[0];
     hdr[1] = (double)C * v[0];
@@ -122,85 +97,50 @@ __global__ __launch_bounds__(SS_T * SS_T) void masked_ssim_fwd_kernel(const floa
   __shared__ float sx[SS_H][SS_H + 1];
   __shared__ float sy[SS_H][SS_H + 1];
   __shared__ float hz[5][SS_H][SS_T + 1];   // horizontally filtered x', y', x'x', y'y', x'y'
-  __shared__ float red[2][SS_T * SS_T / WAVE];
+  __shared__ float red[SS_T * SS_T / WAVE][2];
   const int tx = threadIdx.x & (SS_T - 1), ty = threadIdx.x / SS_T;
   const int x0 = blockIdx.x * SS_T, y0 = blockIdx.y * SS_T;
   const size_t plane = (size_t)W * H;
   const float* __restrict__ xc = X + plane * blockIdx.z;
   const float* __restrict__ yc = Y + plane * blockIdx.z;
   const float inv_z = ml_inv_z<BY_MASK>(inv_n, hdr);
-  for (int i = threadIdx.x; i < SS_H * SS_H; i += SS_T * SS_T) {
-    const int hy = i / SS_H, hx = i - hy * SS_H;
-    const int gx = x0 + hx - SS_R, gy = y0 + hy - SS_R;
-    float xv = 0.0f, yv = 0.0f;
+  const SsimMoments m = ssim_tile_moments(sx, sy, hz, win, x0, y0, [&](int gx, int gy, float& xv, float& yv) {
+    xv = yv = 0.0f;
     if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
       const size_t o = (size_t)gy * W + gx;
-      const float m = M[o];
-      if (m != 0.0f) {                          // a masked-out pixel is +0 whatever the images hold there
-        xv = m * xc[o];
-        yv = m * yc[o];
+      const float mo = M[o];
+      if (mo != 0.0f) {                         // a masked-out pixel is +0 whatever the images hold there
+        xv = mo * xc[o];
+        yv = mo * yc[o];
       }
     }
-    sx[hy][hx] = xv;
-    sy[hy][hx] = yv;
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < SS_H * SS_T; i += SS_T * SS_T) {
-    const int hy = i / SS_T, ox = i - hy * SS_T;
-    float a = 0.f, b = 0.f, aa = 0.f, bb = 0.f, ab = 0.f;
-#pragma unroll
-    for (int k = 0; k < 11; ++k) {
-      const float xv = sx[hy][ox + k], yv = sy[hy][ox + k], wk = win.w[k];
-      a += wk * xv; b += wk * yv; aa += wk * xv * xv; bb += wk * yv * yv; ab += wk * xv * yv;
-    }
-    hz[0][hy][ox] = a; hz[1][hy][ox] = b; hz[2][hy][ox] = aa; hz[3][hy][ox] = bb; hz[4][hy][ox] = ab;
-  }
-  __syncthreads();
-  float m1 = 0.f, m2 = 0.f, exx = 0.f, eyy = 0.f, exy = 0.f;
-#pragma unroll
-  for (int k = 0; k < 11; ++k) {
-    const float wk = win.w[k];
-    m1 += wk * hz[0][ty + k][tx]; m2 += wk * hz[1][ty + k][tx]; exx += wk * hz[2][ty + k][tx];
-    eyy += wk * hz[3][ty + k][tx]; exy += wk * hz[4][ty + k][tx];
-  }
+  });
   const int px = x0 + tx, py = y0 + ty;
-  float s_acc = 0.f, l1 = 0.f;
+  float v[2] = {0.f, 0.f};                      // the lane's |x' - y'| and its SSIM term
   if (px < W && py < H) {
-    const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-    const float mu1_sq = m1 * m1, mu2_sq = m2 * m2, mu12 = m1 * m2;
-    const float s1 = exx - mu1_sq, s2 = eyy - mu2_sq, s12 = exy - mu12;
-    const float N1 = 2.0f * mu12 + C1, N2 = 2.0f * s12 + C2, D1 = mu1_sq + mu2_sq + C1, D2 = s1 + s2 + C2;
-    const float num = N1 * N2, den = D1 * D2;
-    const float inv = 1.0f / den;
-    const float s = num / den;                  // a true division: exactly 1 where the two images agree on the window
+    const SsimTerms t = ssim_terms(m);
+    const float s = (t.N1 * t.N2) / t.den;      // a true division: exactly 1 where the two images agree on the window
     float dLds = -lambda * inv_z;               // d/ds of lambda (1 - mean s)
     if constexpr (BY_MASK) {
       const float mp = M[(size_t)py * W + px];
       dLds *= mp;                               // d/ds of lambda sum m (1 - s) / Z
-      s_acc = mp * (1.0f - s);
+      v[1] = mp * (1.0f - s);
     } else {
-      s_acc = s;
+      v[1] = s;
     }
-    const float ds_dm1 = 2.0f * m2 * (N2 - N1) * inv - s * 2.0f * m1 * (D2 - D1) * inv;
+    const SsimDerivs ds = ssim_derivs(m, t, s);
     const size_t o = plane * blockIdx.z + (size_t)py * W + px;
     const size_t total = plane * gridDim.z;
-    maps[o] = dLds * ds_dm1;
-    maps[total + o] = dLds * (-s / D2);
-    maps[2 * total + o] = dLds * (2.0f * N1 * inv);
-    l1 = fabsf(sx[ty + SS_R][tx + SS_R] - sy[ty + SS_R][tx + SS_R]);
+    maps[o] = dLds * ds.dm1;
+    maps[total + o] = dLds * ds.dexx;
+    maps[2 * total + o] = dLds * ds.dexy;
+    v[0] = fabsf(sx[ty + SS_R][tx + SS_R] - sy[ty + SS_R][tx + SS_R]);
   }
-  s_acc = wave_reduce_add_f32(s_acc);
-  l1 = wave_reduce_add_f32(l1);
-  const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-  if (lane == 0) { red[0][wid] = l1; red[1][wid] = s_acc; }
-  __syncthreads();
+  ordered_block_sum<SS_T * SS_T / WAVE, FROM_ZERO>(v, red);
   if (threadIdx.x == 0) {
-    float a = 0.f, b = 0.f;
-#pragma unroll
-    for (int w = 0; w < SS_T * SS_T / WAVE; ++w) { a += red[0][w]; b += red[1][w]; }
     const size_t blk = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    partials[2 * blk] = a;
-    partials[2 * blk + 1] = b;
+    partials[2 * blk] = v[0];
+    partials[2 * blk + 1] = v[1];
   }
 }
 
@@ -214,7 +154,7 @@ __global__ __launch_bounds__(ML_FINISH) void masked_finish_kernel(size_t nblocks
     v[0] += (double)partials[2 * i];
     v[1] += (double)partials[2 * i + 1];
   }
-  ml_block_sum<2, ML_FINISH / WAVE>(v, part);
+  ordered_block_sum<ML_FINISH / WAVE, FROM_WAVE0>(v, part);
   if (threadIdx.x == 0) {
     const double Z = by_mask ? hdr[1] : n;
     const bool live = Z > 0.0;
@@ -240,43 +180,19 @@ __global__ __launch_bounds__(SS_T * SS_T) void masked_ssim_bwd_kernel(const floa
                                                                        float* __restrict__ dL_dx) {
   __shared__ float sm[3][SS_H][SS_H + 1];
   __shared__ float hz[3][SS_H][SS_T + 1];
-  const int tx = threadIdx.x & (SS_T - 1), ty = threadIdx.x / SS_T;
   const int x0 = blockIdx.x * SS_T, y0 = blockIdx.y * SS_T;
   const size_t plane = (size_t)W * H, total = plane * gridDim.z;
   const float l1_scale = (1.0f - lambda) * ml_inv_z<BY_MASK>(inv_n, hdr);
-  for (int i = threadIdx.x; i < SS_H * SS_H; i += SS_T * SS_T) {
-    const int hy = i / SS_H, hx = i - hy * SS_H;
-#pragma unroll
-    for (int m = 0; m < 3; ++m)
-      sm[m][hy][hx] = halo_load(maps + m * total + plane * blockIdx.z, W, H, x0 + hx - SS_R, y0 + hy - SS_R);
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < SS_H * SS_T; i += SS_T * SS_T) {
-    const int hy = i / SS_T, ox = i - hy * SS_T;
-    float a = 0.f, b = 0.f, c = 0.f;
-#pragma unroll
-    for (int k = 0; k < 11; ++k) {
-      const float wk = win.w[k];
-      a += wk * sm[0][hy][ox + k]; b += wk * sm[1][hy][ox + k]; c += wk * sm[2][hy][ox + k];
-    }
-    hz[0][hy][ox] = a; hz[1][hy][ox] = b; hz[2][hy][ox] = c;
-  }
-  __syncthreads();
-  const int px = x0 + tx, py = y0 + ty;
+  const SsimMapGrads c = ssim_convolve_maps(sm, hz, win, maps + plane * blockIdx.z, total, W, H, x0, y0);
+  const int px = x0 + (threadIdx.x & (SS_T - 1)), py = y0 + threadIdx.x / SS_T;
   if (px < W && py < H) {
-    float ga = 0.f, gb = 0.f, gc = 0.f;
-#pragma unroll
-    for (int k = 0; k < 11; ++k) {
-      const float wk = win.w[k];
-      ga += wk * hz[0][ty + k][tx]; gb += wk * hz[1][ty + k][tx]; gc += wk * hz[2][ty + k][tx];
-    }
     const size_t p = (size_t)py * W + px, o = plane * blockIdx.z + p;
     const float m = M[p];
     float g = 0.0f;                             // +0 on a masked-out pixel, whatever the images hold there
     if (m != 0.0f) {
       const float xv = m * X[o], yv = m * Y[o], d = xv - yv;
       const float sg = d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f);
-      g = m * (ga + 2.0f * xv * gb + yv * gc + l1_scale * sg);
+      g = m * (c.ga + 2.0f * xv * c.gb + yv * c.gc + l1_scale * sg);
     }
     dL_dx[o] = g;
   }
@@ -308,7 +224,7 @@ __global__ void __launch_bounds__(ML_BLOCK) alpha_mask_kernel(const float* __res
     v[0] += term;
     if (grad) grad[i] = (float)g;
   }
-  ml_block_sum<1, ML_WAVES>(v, part);
+  ordered_block_sum<ML_WAVES, FROM_WAVE0>(v, part);
   if (threadIdx.x == 0) partials[blockIdx.x] = v[0];
 }
 
@@ -317,7 +233,7 @@ __global__ void __launch_bounds__(ML_BLOCK) alpha_mask_finish_kernel(const doubl
   __shared__ double part[ML_WAVES][1];
   double v[1] = {0.0};
   for (int g = threadIdx.x; g < nb; g += ML_BLOCK) v[0] += partials[g];
-  ml_block_sum<1, ML_WAVES>(v, part);
+  ordered_block_sum<ML_WAVES, FROM_WAVE0>(v, part);
   if (threadIdx.x == 0) {
     record[0] = v[0] / n;
     record[1] = n;
@@ -331,7 +247,7 @@ __global__ void __launch_bounds__(ML_BLOCK) alpha_mask_finish_kernel(const doubl
 struct MlLayout {
   size_t mask_partials, maps, partials, bytes, nblocks;
   MlLayout(int C, int H, int W) {
-    nblocks = (size_t)((W + SS_T - 1) / SS_T) * (size_t)((H + SS_T - 1) / SS_T) * (size_t)C;
+    nblocks = ssim_tiles(C, H, W);
     mask_partials = 8 * (size_t)ML_HDR_WORDS;
     maps = mask_partials + 8 * (size_t)ML_MAX_BLOCKS;
     partials = maps + sizeof(float) * 3 * (size_t)C * (size_t)H * (size_t)W;

@@ -8,6 +8,7 @@
 #include "gsr_common.h"
 #include "gsr_entry.h"
 #include "gsr_launch.h"
+#include "ssim_tile.h"       // ssim_tiles: the SSIM partials of loss.hip's forward-only tile kernel
 
 namespace gsr {
 
@@ -158,7 +159,7 @@ static int eval_blocks(size_t hw, bool vec) {
   return (int)(b < (size_t)EVAL_MAX_BLOCKS ? (b ? b : 1) : (size_t)EVAL_MAX_BLOCKS);
 }
 
-static size_t eval_ssim_blocks(int H, int W) { return (size_t)((W + 15) / 16) * (size_t)((H + 15) / 16) * 3; }
+static size_t eval_ssim_blocks(int H, int W) { return ssim_tiles(3, H, W); }
 
 // gt == nullptr converts only.  workspace: 6 floats per streaming block, then eval_ssim_blocks floats
 static void launch_eval_image(const float* x, const float* gt, int H, int W, int flags, float* view, double* acc,

@@ -2,7 +2,7 @@
 //
 //   * the fork's opacity sparsity term of train.py:102-106, `w * mean(|o - 1|)` over the rows with o = sigmoid(raw)
 //     below 0.005: opacity_sparsity_kernel streams the [P,1] tensor once and leaves one (sum, count) pair per block,
-//     opacity_sparsity_finish_kernel adds the pairs in a fixed order in double and writes the record the backward reads
+//     opacity_sparsity_finish_kernel adds the pairs in a fixed order in double (ordered_sum.h) and writes the record the backward reads
 //     from device memory (loss, n, w / n), opacity_sparsity_bwd_kernel writes the dense gradient.  No atomics: the
 //     value does not depend on arrival order.  The host never sees n, so a train step keeps its queue full.
 //   * reset_opacity (scene/gaussian_model.py:312-315 with replace_tensor_to_optimizer :386-399) in place:
@@ -11,6 +11,7 @@
 // Built with -ffp-contract=off: sigmoid, min, sub, div, log are torch's ops, each rounded to float32 on its own.
 #include "gsr_common.h"
 #include "gsr_entry.h"
+#include "ordered_sum.h"
 
 namespace gsr {
 
@@ -41,8 +42,7 @@ template <bool VEC>
 __global__ __launch_bounds__(OS_THREADS) void opacity_sparsity_kernel(const float* __restrict__ raw, size_t P, float thr,
                                                                       float* __restrict__ part_sum,
                                                                       uint32_t* __restrict__ part_n) {
-  __shared__ float red_s[OS_WAVES];
-  __shared__ uint32_t red_n[OS_WAVES];
+  __shared__ PairSlots<float, OS_WAVES> red;
   SparsityAcc a = {0.0f, 0u};
   const size_t stride = (size_t)gridDim.x * OS_THREADS;
   const size_t first = (size_t)blockIdx.x * OS_THREADS + threadIdx.x;
@@ -57,44 +57,24 @@ __global__ __launch_bounds__(OS_THREADS) void opacity_sparsity_kernel(const floa
   } else {
     for (size_t i = first; i < P; i += stride) a.add(raw[i], thr);
   }
-  const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-  const float s = wave_reduce_add_f32(a.sum);
-  const uint32_t n = wave_reduce_add_u32(a.n);
-  if (lane == 0) { red_s[wid] = s; red_n[wid] = n; }
-  __syncthreads();
+  ordered_pair_sum(a.sum, a.n, red);
   if (threadIdx.x == 0) {
-    float ts = 0.0f;
-    uint32_t tn = 0u;
-#pragma unroll
-    for (int w = 0; w < OS_WAVES; ++w) { ts += red_s[w]; tn += red_n[w]; }
-    part_sum[blockIdx.x] = ts;                                   // one pair per block: no atomics, see metrics.hip
-    part_n[blockIdx.x] = tn;
+    part_sum[blockIdx.x] = a.sum;                                // one pair per block: no atomics, see ordered_sum.h
+    part_n[blockIdx.x] = a.n;
   }
 }
 
-// One block.  Lane t adds pairs t, t + 256, ... in order, then a fixed butterfly and a fixed walk over the waves.
+// One block: the pairs in the fixed order of ordered_pair_finish, the float partials widened to double as they are added.
 // record = {float loss, uint32 n, float weight / n, 0}; n == 0 gives loss = factor = 0 (train.py:104 skips the term).
 __global__ __launch_bounds__(OS_FIN_THREADS) void opacity_sparsity_finish_kernel(const float* __restrict__ part_sum,
                                                                                  const uint32_t* __restrict__ part_n,
                                                                                  int nblocks, float weight,
                                                                                  float* __restrict__ record) {
-  __shared__ double red_s[OS_FIN_THREADS / WAVE];
-  __shared__ uint32_t red_n[OS_FIN_THREADS / WAVE];
-  double s = 0.0;
-  uint32_t n = 0u;
-  for (int i = threadIdx.x; i < nblocks; i += OS_FIN_THREADS) {
-    s += (double)part_sum[i];
-    n += part_n[i];
-  }
-  const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-  s = wave_reduce_add_f64(s);
-  n = wave_reduce_add_u32(n);
-  if (lane == 0) { red_s[wid] = s; red_n[wid] = n; }
-  __syncthreads();
+  __shared__ PairSlots<double, OS_FIN_THREADS / WAVE> red;
+  double ts;
+  uint32_t tn;
+  ordered_pair_finish(part_sum, part_n, nblocks, ts, tn, red);
   if (threadIdx.x != 0) return;
-  double ts = 0.0;
-  uint32_t tn = 0u;
-  for (int w = 0; w < OS_FIN_THREADS / WAVE; ++w) { ts += red_s[w]; tn += red_n[w]; }
   const double factor = tn ? (double)weight / (double)tn : 0.0;
   record[0] = (float)(factor * ts);
   reinterpret_cast<uint32_t*>(record)[1] = tn;

@@ -29,9 +29,9 @@
 // scalar loads.  grad_ref is a gather: every lane writes its own pixel (zero where not valid), the same bits from run to
 // run.  grad_src is a scatter: four atomicAdd(float*) per valid pixel into a map the entry point zeroed on the stream
 // (global_atomic_add_f32, no compare-and-swap loop); the order of the additions varies, so grad_src is NOT
-// bit-reproducible.  The loss: e in double, a fixed butterfly per wave, the four waves in order, one (double sum, uint32
-// count) pair per workgroup in the workspace; a one-block kernel behind it adds the pairs in block order and writes the
-// record -- the same bits from run to run (the scheme of normal_consistency.hip).  LDS: the eight reduction slots only.
+// bit-reproducible.  The loss: e in double, one (double sum, uint32 count) pair per workgroup in the workspace; a
+// one-block kernel behind it adds the pairs and writes the record -- every sum in the fixed order of ordered_sum.h, the
+// same bits from run to run.  LDS: the eight reduction slots only.
 //
 // Safety.  Every gather and every atomic is behind the footprint test of mvs_round_trip, formed from the row's own W_s,
 // H_s, so the four addresses lie inside [0, W_s H_s) of the row's depth.  grad_src is sized by the caller's src_H, src_W:
@@ -41,6 +41,7 @@
 #include "gsr_common.h"
 #include "gsr_entry.h"
 #include "mvs_geom.h"
+#include "ordered_sum.h"
 
 namespace gsr {
 
@@ -55,8 +56,7 @@ __global__ __launch_bounds__(MVS_BLOCK) void mvs_geo_loss_kernel(const float* __
                                                                  float* __restrict__ grad_src,
                                                                  double* __restrict__ part_sum,
                                                                  uint32_t* __restrict__ part_n) {
-  __shared__ double red_s[MVS_BLOCK / WAVE];
-  __shared__ uint32_t red_n[MVS_BLOCK / WAVE];
+  __shared__ PairSlots<double, MVS_BLOCK / WAVE> red;
   const unsigned tx = blockIdx.x % xtiles, ty = blockIdx.x / xtiles;
   const int px = (int)(tx * MVS_TILE_X + threadIdx.x % MVS_TILE_X);
   const int py = (int)(ty * MVS_TILE_Y + threadIdx.x / MVS_TILE_X);
@@ -113,44 +113,26 @@ __global__ __launch_bounds__(MVS_BLOCK) void mvs_geo_loss_kernel(const float* __
   }
   if (in && grad_ref) grad_ref[pix] = g_ref;
 
-  // the workgroup's partial and count: fixed butterfly, then the waves in order
-  const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-  const double ws = wave_reduce_add_f64((double)e);
-  const uint32_t wn = wave_reduce_add_u32(valid ? 1u : 0u);
-  if (lane == 0) { red_s[wid] = ws; red_n[wid] = wn; }
-  __syncthreads();
+  // the workgroup's partial and count (ordered_sum.h)
+  double ts = (double)e;
+  uint32_t tn = valid ? 1u : 0u;
+  ordered_pair_sum(ts, tn, red);
   if (threadIdx.x == 0) {
-    double ts = 0.0;
-    uint32_t tn = 0u;
-#pragma unroll
-    for (int k = 0; k < MVS_BLOCK / WAVE; ++k) { ts += red_s[k]; tn += red_n[k]; }
     part_sum[blockIdx.x] = ts;
     part_n[blockIdx.x] = tn;
   }
 }
 
-// One block.  Lane t adds pairs t, t + 1024, ... in order, then a fixed butterfly and a fixed walk over the waves.
+// One block: the pairs in the fixed order of ordered_pair_finish.
 // record = {float raw / max(n, 1), uint32 n, float raw, 0}: written, not accumulated.
 __global__ __launch_bounds__(MVL_FIN_THREADS) void mvs_geo_loss_finish_kernel(const double* __restrict__ part_sum,
                                                                               const uint32_t* __restrict__ part_n,
                                                                               unsigned nblocks, float* __restrict__ record) {
-  __shared__ double red_s[MVL_FIN_THREADS / WAVE];
-  __shared__ uint32_t red_n[MVL_FIN_THREADS / WAVE];
-  double s = 0.0;
-  uint32_t n = 0u;
-  for (unsigned i = threadIdx.x; i < nblocks; i += MVL_FIN_THREADS) {
-    s += part_sum[i];
-    n += part_n[i];
-  }
-  const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-  s = wave_reduce_add_f64(s);
-  n = wave_reduce_add_u32(n);
-  if (lane == 0) { red_s[wid] = s; red_n[wid] = n; }
-  __syncthreads();
+  __shared__ PairSlots<double, MVL_FIN_THREADS / WAVE> red;
+  double ts;
+  uint32_t tn;
+  ordered_pair_finish(part_sum, part_n, nblocks, ts, tn, red);
   if (threadIdx.x != 0) return;
-  double ts = 0.0;
-  uint32_t tn = 0u;
-  for (int w = 0; w < MVL_FIN_THREADS / WAVE; ++w) { ts += red_s[w]; tn += red_n[w]; }
   record[0] = (float)(ts / (double)(tn > 0u ? tn : 1u));
   reinterpret_cast<uint32_t*>(record)[1] = tn;
   record[2] = (float)ts;

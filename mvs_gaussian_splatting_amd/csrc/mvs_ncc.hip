@@ -43,9 +43,9 @@
 // accumulators; there is no second walk and no per-tap storage.  Every gradient is a gather onto the lane's own pixel: no
 // atomics, all outputs the same bits from run to run.  Dense mode writes every pixel (zero where not counted); with a
 // list the entry point zeroes both maps on the stream first and the lanes write their own pixels only (duplicate indices
-// are the caller's error: the lanes would race, with equal values).  The value: e in double, a fixed butterfly per wave,
-// the four waves in order, one (double, uint32) pair per workgroup in the workspace, a one-block finish kernel in block
-// order (the scheme of mvs_loss.hip).  LDS: the eight reduction slots only.
+// are the caller's error: the lanes would race, with equal values).  The value: e in double, one (double, uint32) pair
+// per workgroup in the workspace, a one-block finish kernel behind it, every sum in the fixed order of ordered_sum.h.
+// LDS: the eight reduction slots only.
 //
 // Safety.  A list entry outside [0, H W) is skipped before anything is addressed with it.  Reference taps lie inside the
 // image by the patch gate; source taps are behind the footprint test formed from the row's own width and height; the
@@ -54,6 +54,7 @@
 #include "gsr_common.h"
 #include "gsr_entry.h"
 #include "mvs_geom.h"
+#include "ordered_sum.h"
 
 namespace gsr {
 
@@ -98,8 +99,7 @@ __global__ __launch_bounds__(MVS_BLOCK) void mvs_ncc_loss_kernel(
     float fy, const GsrMvsSource* __restrict__ source, const float* __restrict__ src_gray, const int* __restrict__ pixels,
     int n_pixels, int R, float pix_max, float ncc_max, float min_cos, unsigned xtiles, float* __restrict__ grad_depth,
     float* __restrict__ grad_normal, double* __restrict__ part_sum, uint32_t* __restrict__ part_n) {
-  __shared__ double red_s[MVS_BLOCK / WAVE];
-  __shared__ uint32_t red_n[MVS_BLOCK / WAVE];
+  __shared__ PairSlots<double, MVS_BLOCK / WAVE> red;
   const int HW = H * W;                                                  // at most 2^28
   int px, py;
   bool in;
@@ -193,44 +193,26 @@ __global__ __launch_bounds__(MVS_BLOCK) void mvs_ncc_loss_kernel(
     }
   }
 
-  // the workgroup's partial and count: fixed butterfly, then the waves in order
-  const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-  const double ws = wave_reduce_add_f64((double)e);
-  const uint32_t wn = wave_reduce_add_u32(counted ? 1u : 0u);
-  if (lane == 0) { red_s[wid] = ws; red_n[wid] = wn; }
-  __syncthreads();
+  // the workgroup's partial and count (ordered_sum.h)
+  double ts = (double)e;
+  uint32_t tn = counted ? 1u : 0u;
+  ordered_pair_sum(ts, tn, red);
   if (threadIdx.x == 0) {
-    double ts = 0.0;
-    uint32_t tn = 0u;
-#pragma unroll
-    for (int k = 0; k < MVS_BLOCK / WAVE; ++k) { ts += red_s[k]; tn += red_n[k]; }
     part_sum[blockIdx.x] = ts;
     part_n[blockIdx.x] = tn;
   }
 }
 
-// One block.  Lane t adds pairs t, t + 1024, ... in order, then a fixed butterfly and a fixed walk over the waves.
+// One block: the pairs in the fixed order of ordered_pair_finish.
 // record = {float raw / max(n, 1), uint32 n, float raw, 0}: written, not accumulated.  nblocks may be 0 (an empty list).
 __global__ __launch_bounds__(NCC_FIN_THREADS) void mvs_ncc_loss_finish_kernel(const double* __restrict__ part_sum,
                                                                               const uint32_t* __restrict__ part_n,
                                                                               unsigned nblocks, float* __restrict__ record) {
-  __shared__ double red_s[NCC_FIN_THREADS / WAVE];
-  __shared__ uint32_t red_n[NCC_FIN_THREADS / WAVE];
-  double s = 0.0;
-  uint32_t n = 0u;
-  for (unsigned i = threadIdx.x; i < nblocks; i += NCC_FIN_THREADS) {
-    s += part_sum[i];
-    n += part_n[i];
-  }
-  const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-  s = wave_reduce_add_f64(s);
-  n = wave_reduce_add_u32(n);
-  if (lane == 0) { red_s[wid] = s; red_n[wid] = n; }
-  __syncthreads();
+  __shared__ PairSlots<double, NCC_FIN_THREADS / WAVE> red;
+  double ts;
+  uint32_t tn;
+  ordered_pair_finish(part_sum, part_n, nblocks, ts, tn, red);
   if (threadIdx.x != 0) return;
-  double ts = 0.0;
-  uint32_t tn = 0u;
-  for (int w = 0; w < NCC_FIN_THREADS / WAVE; ++w) { ts += red_s[w]; tn += red_n[w]; }
   record[0] = (float)(ts / (double)(tn > 0u ? tn : 1u));
   reinterpret_cast<uint32_t*>(record)[1] = tn;
   record[2] = (float)ts;

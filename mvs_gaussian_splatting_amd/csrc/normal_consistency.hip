@@ -21,10 +21,11 @@
 // also one of the 68 ring pixels (1.27 stencils per pixel instead of 5), and G_tx, G_ty of the 18x18 pixels go to LDS;
 // after one barrier every lane gathers its four neighbours' entries.  `normal` is read straight from memory: every
 // stencil reads its own pixel's only, so LDS would not save a byte.  No atomics; nothing waits on another workgroup.
-// The loss: e in double, a fixed butterfly per wave, the four waves in order, one (double sum, uint32 count) pair per
-// workgroup in the workspace; a one-block kernel behind it adds the pairs in a fixed order and writes the record.
+// The loss: e in double, one (double sum, uint32 count) pair per workgroup in the workspace; a one-block kernel behind
+// it adds the pairs and writes the record.  Every sum in the fixed order of ordered_sum.h.
 #include "gsr_common.h"
 #include "gsr_entry.h"
+#include "ordered_sum.h"
 
 namespace gsr {
 
@@ -96,8 +97,7 @@ __global__ __launch_bounds__(NC_T* NC_T) void normal_consistency_kernel(
   __shared__ float sd[NC_D][NC_D + 1];
   __shared__ uint8_t sc[NC_D][NC_D];
   __shared__ float sg[GRAD ? 6 : 1][NC_G][NC_G + 1];
-  __shared__ double red_s[NC_T * NC_T / WAVE];
-  __shared__ uint32_t red_n[NC_T * NC_T / WAVE];
+  __shared__ PairSlots<double, NC_T * NC_T / WAVE> red;
   const int tid = threadIdx.x, lx0 = tid & (NC_T - 1), ly0 = tid / NC_T;
   const int x0 = (int)(blockIdx.x % xtiles) * NC_T, y0 = (int)(blockIdx.x / xtiles) * NC_T;
   const size_t plane = (size_t)W * (size_t)H;
@@ -134,11 +134,8 @@ __global__ __launch_bounds__(NC_T* NC_T) void normal_consistency_kernel(
     for (int a = 0; a < 3; ++a) depth_normal[a * plane + pix] = own.n[a];
   }
 
-  // the workgroup's loss partial and count: fixed butterfly, then the waves in order
-  const int lane = tid & (WAVE - 1), wid = tid / WAVE;
-  const double ws = wave_reduce_add_f64(e);
-  const uint32_t wn = wave_reduce_add_u32(own.valid ? 1u : 0u);
-  if (lane == 0) { red_s[wid] = ws; red_n[wid] = wn; }
+  // the workgroup's loss partial and count (ordered_sum.h, the split form: the barrier below is the kernel's one)
+  ordered_pair_stage(e, own.valid ? 1u : 0u, red);
 
   if constexpr (GRAD) {
 #pragma unroll
@@ -164,10 +161,9 @@ __global__ __launch_bounds__(NC_T* NC_T) void normal_consistency_kernel(
   __syncthreads();
 
   if (tid == 0) {
-    double ts = 0.0;
-    uint32_t tn = 0u;
-#pragma unroll
-    for (int w = 0; w < NC_T * NC_T / WAVE; ++w) { ts += red_s[w]; tn += red_n[w]; }
+    double ts;
+    uint32_t tn;
+    ordered_pair_fold(red, ts, tn);
     part_sum[blockIdx.x] = ts;
     part_n[blockIdx.x] = tn;
   }
@@ -194,29 +190,17 @@ __global__ __launch_bounds__(NC_T* NC_T) void normal_consistency_kernel(
   }
 }
 
-// One block.  Lane t adds pairs t, t + 1024, ... in order, then a fixed butterfly and a fixed walk over the waves.
+// One block: the pairs in the fixed order of ordered_pair_finish.
 // record = {float loss, uint32 n_valid, 0, 0}: written, not accumulated.
 __global__ __launch_bounds__(NC_FIN_THREADS) void normal_consistency_finish_kernel(const double* __restrict__ part_sum,
                                                                                    const uint32_t* __restrict__ part_n,
                                                                                    unsigned nblocks, double inv_hw,
                                                                                    float* __restrict__ record) {
-  __shared__ double red_s[NC_FIN_THREADS / WAVE];
-  __shared__ uint32_t red_n[NC_FIN_THREADS / WAVE];
-  double s = 0.0;
-  uint32_t n = 0u;
-  for (unsigned i = threadIdx.x; i < nblocks; i += NC_FIN_THREADS) {
-    s += part_sum[i];
-    n += part_n[i];
-  }
-  const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-  s = wave_reduce_add_f64(s);
-  n = wave_reduce_add_u32(n);
-  if (lane == 0) { red_s[wid] = s; red_n[wid] = n; }
-  __syncthreads();
+  __shared__ PairSlots<double, NC_FIN_THREADS / WAVE> red;
+  double ts;
+  uint32_t tn;
+  ordered_pair_finish(part_sum, part_n, nblocks, ts, tn, red);
   if (threadIdx.x != 0) return;
-  double ts = 0.0;
-  uint32_t tn = 0u;
-  for (int w = 0; w < NC_FIN_THREADS / WAVE; ++w) { ts += red_s[w]; tn += red_n[w]; }
   record[0] = (float)(ts * inv_hw);
   reinterpret_cast<uint32_t*>(record)[1] = tn;
   record[2] = 0.0f;
