@@ -192,7 +192,7 @@ def render_set(model_path, name, iteration, views, gaussians, pipeline, backgrou
 
 def render_sets(dataset, iteration, pipeline, skip_train=False, skip_test=False, depth=False, use_trained_exp=False,
                 normals=False, depth_normals=False, distortion=False, median_depth=False, plane_depth=False, mesh=None,
-                point_cloud=None):
+                point_cloud=None, fuse_filter=False):
     with torch.no_grad():
         if mesh is not None:
             from mvs_gaussian_splatting_amd.ply_io import read_ply_mesh
@@ -202,6 +202,14 @@ def render_sets(dataset, iteration, pipeline, skip_train=False, skip_test=False,
         scene = Scene(dataset, gaussians, load_iteration=iteration, shuffle=False)
         if point_cloud is not None:                              # this file instead of the iteration's point_cloud.ply
             (gaussians.load_compressed if point_cloud.endswith(".npz") else gaussians.load_ply)(point_cloud)
+        # a filter_3D property in the PLY (examples/train.py --filter_3d) is on the model now and every frame below is drawn
+        # through it
+        if fuse_filter:
+            if gaussians.filter_3D is None:
+                raise SystemExit("--fuse_filter: the point cloud carries no filter_3D property")
+            fused = os.path.join(dataset.model_path, "point_cloud", f"iteration_{scene.loaded_iter}", "point_cloud_fused.ply")
+            gaussians.save_ply(fused, fuse_filter=True)
+            print(f"wrote {fused}: a standard PLY with the 3D filter baked into scale_* and opacity")
         bg_color = [1, 1, 1] if dataset.white_background else [0, 0, 0]
         background = torch.tensor(bg_color, dtype=torch.float32, device="cuda")
         if use_trained_exp and gaussians.pretrained_exposures is None:
@@ -244,6 +252,9 @@ def main(argv=None):
     ap.add_argument("--point_cloud", default=None, metavar="FILE",
                     help="render this file instead of the iteration's point_cloud.ply: a .ply, or the .npz of "
                          "examples/compress.py (chosen by extension)")
+    ap.add_argument("--fuse_filter", action="store_true",
+                    help="also write point_cloud_fused.ply next to the point cloud: a standard PLY with the model's 3D "
+                         "smoothing filter baked in, for viewers that know nothing of the filter_3D property")
     args = ap.parse_args(argv)
     fields = {}
     cfg = os.path.join(args.model_path, "cfg_args.json")
@@ -260,7 +271,8 @@ def main(argv=None):
     render_sets(dataset, args.iteration, PipelineParams(), args.skip_train, args.skip_test, args.depth,
                 args.use_trained_exp, args.normals, args.depth_normals, args.distortion, args.median_depth,
                 **({"plane_depth": True} if args.plane_depth else {}), **({} if args.mesh is None else {"mesh": args.mesh}),
-                **({} if args.point_cloud is None else {"point_cloud": args.point_cloud}))
+                **({} if args.point_cloud is None else {"point_cloud": args.point_cloud}),
+                **({"fuse_filter": True} if args.fuse_filter else {}))
 
 
 if __name__ == "__main__":

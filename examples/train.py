@@ -190,6 +190,7 @@ def train(model, problem, opt, first_iter=0, last_iter=None, dataset=None, pipe=
         source = draw_source(cams, sources, index, random.Random(seed * 1_000_003 + iteration))
         losses.append(training_iteration(model, cams[index], opt, pipe, bg, iteration, dataset=dataset,
                                          cameras_extent=CAMERAS_EXTENT,
+                                         **({"filter_cameras": cams} if getattr(opt, "filter_3d", False) else {}),
                                          **({"source_camera": source} if source is not None else {})))
         prune_step(model, cams, pipe, bg, iteration, prune, log)
         if on_iteration:
@@ -211,7 +212,8 @@ def strategy_options(args):
                 multi_view_pix_max=args.multi_view_pix_max, lambda_multi_view_ncc=args.lambda_multi_view_ncc,
                 multi_view_ncc_samples=args.multi_view_ncc_samples, multi_view_patch_radius=args.multi_view_patch_radius,
                 unbiased_depth=args.unbiased_depth, abs_grad=args.abs_grad,
-                densify_abs_grad_threshold=args.densify_abs_grad_threshold)
+                densify_abs_grad_threshold=args.densify_abs_grad_threshold,
+                filter_3d=args.filter_3d, filter_3d_rule=args.filter_3d_rule)
 
 
 def train_scene(args, dev):
@@ -268,6 +270,7 @@ def train_scene(args, dev):
                                   cameras_extent=scene.cameras_extent, pose_optimizer=pose_optimizer,
                                   train_exposure=args.train_exposure,
                                   **({"bilateral_grids": grids} if grids is not None else {}),
+                                  **({"filter_cameras": train_cameras} if args.filter_3d else {}),
                                   **({"source_camera": source} if source is not None else {}))
         prune_step(model, train_cameras, pipe, bg, iteration, prune)
         if iteration % 10 == 0:
@@ -354,6 +357,11 @@ def main(argv=None):
                     help="absolute-gradient densification (AbsGS / PGSR): a large Gaussian is also split when its "
                          "accumulated absolute view-space gradient reaches --densify_abs_grad_threshold")
     ap.add_argument("--densify_abs_grad_threshold", type=float, default=0.0008, metavar="T")
+    ap.add_argument("--filter_3d", action="store_true",
+                    help="Mip-Splatting's 3D smoothing filter: band-limit every Gaussian by the training cameras' sampling "
+                         "rate; the saved PLY carries a filter_3D property (examples/render.py --fuse_filter bakes it in)")
+    ap.add_argument("--filter_3d_rule", choices=("mip_splatting", "paper"), default="mip_splatting",
+                    help="the filter's width: the published code's (min depth / max focal) or the paper's (1 / max rate)")
     ap.add_argument("-d", "--depths", default="", metavar="DIR",
                     help="with -s: the folder of 16-bit inverse-depth PNGs under the scene, one per training image "
                          "(upstream 3DGS's -d); adds the depth-prior term (depth_prior.py)")

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 46
+#define GSR_ABI_VERSION 47
 
 enum {
   GSR_OK = 0,
@@ -1461,6 +1461,68 @@ int gsr_raster_resolve(const uint64_t* keys, int32_t H, int32_t W, float* depth,
  * the same from run to run.  F = 0 is a success that launches nothing. */
 int gsr_raster_count_faces(const uint64_t* keys, int32_t H, int32_t W, int64_t F, int32_t stamp_value, int32_t* stamp,
                            int32_t* counts, void* stream);
+
+/* ---- Mip-Splatting's 3D smoothing filter, ABI v47 (csrc/filter3d.hip, csrc/filter3d_math.h; filter3d.py; DESIGN.md
+ * §7.34).  A per-Gaussian scalar `filter`, computed from the training cameras (the sampling pass and its finish), and its
+ * fused application to the raw scales and opacities, forward and backward.  The float32 operation order of the sampling
+ * pass and the float64 closed forms of the application are csrc/filter3d_math.h (-ffp-contract=off), written once for
+ * device and host.
+ * One row of the device-resident view table, 8-byte aligned, 80 bytes.  The rows are device memory and are not checked:
+ * finite entries, width and height 1 .. 2^24 are the caller's contract (filter3d.compute_3d_filter checks its cameras). */
+#define GSR_FILTER3D_MAX_VIEWS 65535
+enum { GSR_FILTER3D_MIP_SPLATTING = 0, GSR_FILTER3D_PAPER = 1 };
+typedef struct GsrFilterView {
+  float world_to_view[16]; /* row-vector convention, M[4 * row + col]: the camera's float32 world_view_transform */
+  float fx, fy;
+  int32_t width, height;
+} GsrFilterView;
+/* The workspace both calls share: one (max, min) pair of floats per 64 rows and the pass's 16-byte result.  0 for a P the
+ * calls refuse. */
+size_t gsr_filter3d_workspace_bytes(int64_t P);
+/* xyz float32 [P,3] -> min_depth float32 [P], max_rate float32 [P], seen uint8 [P].  Per row (x, y, z) and per view in
+ * table order, float32, every operation rounded on its own:
+ *     (xv, yv, zv) = (x, y, z, 1) through world_to_view, x' = ((x M[0] + y M[4]) + z M[8]) + M[12] and likewise y', z'
+ *     next view unless zv > near_plane                                      (a NaN fails)
+ *     u = (xv / zv) fx + W / 2,  w = (yv / zv) fy + H / 2
+ *     next view unless -margin W <= u <= (1 + margin) W and -margin H <= w <= (1 + margin) H     (inclusive; a NaN fails)
+ *     min_depth = min(min_depth, zv);  max_rate = max(max_rate, fx / zv);  seen = 1
+ * starting from (+inf, 0, 0) -- or, with accumulate != 0, from the arrays' contents, so that more than 65535 views can be
+ * fed in chunks; the result over chunks is the result over one table.  The call also leaves, in ws, per 64 rows the
+ * maximum of min_depth and the minimum of max_rate over the seen rows, for gsr_filter3d_finish: the last call's stand.
+ * One launch, one lane per row, the loop over the views inside; registers and wave shuffles only, no LDS, no atomics:
+ * the same bits from run to run.  P = 0 is a success that writes nothing; V = 0 writes the start values.  Checked before
+ * any HIP call: GSR_E_BADARG for P outside 0 .. 2^31 - 1, V outside 0 .. 65535, a NULL table with V > 0, a NULL array
+ * with P > 0, near_plane not finite and positive, margin not finite or negative; GSR_E_ALIGN for the arrays (4 bytes), the
+ * table (8) and ws (16); GSR_E_CAPACITY for a short ws.  Asynchronous, allocates nothing, reads nothing back. */
+int gsr_filter3d_sample(const float* xyz, int64_t P, const GsrFilterView* views, int32_t V, float near_plane, float margin,
+                        int32_t accumulate, float* min_depth, float* max_rate, uint8_t* seen, void* ws, size_t ws_bytes,
+                        void* stream);
+/* The three arrays and ws of gsr_filter3d_sample -> filter float32 [P] and none_seen int32 [1] (device; 1 when no row
+ * was seen, else 0; always written).  With D the largest min_depth and R the smallest max_rate over the seen rows:
+ *     GSR_FILTER3D_MIP_SPLATTING   filter = ((seen ? min_depth : D) / focal_max) sqrtf(variance)
+ *     GSR_FILTER3D_PAPER           filter = sqrtf(variance) / (seen ? max_rate : R)
+ * and 0 everywhere when no row was seen.  focal_max: the largest fx over ALL views, the caller's.  Two launches: one
+ * workgroup reduces the per-64-row pairs, then one lane per row writes.  A maximum does not depend on the order: the same
+ * bits from run to run.  GSR_E_BADARG for P outside 0 .. 2^31 - 1, an unknown rule, focal_max or variance not finite and
+ * positive, a NULL pointer (none_seen always; the arrays with P > 0); GSR_E_ALIGN; GSR_E_CAPACITY.  P = 0 writes
+ * none_seen = 1. */
+int gsr_filter3d_finish(int64_t P, const float* min_depth, const float* max_rate, const uint8_t* seen, int32_t rule,
+                        float focal_max, float variance, void* ws, size_t ws_bytes, float* filter, int32_t* none_seen,
+                        void* stream);
+/* Raw scales [P,3], raw opacities [P] and filter [P] (float32) -> the EFFECTIVE raw parameters: with f = filter,
+ * a_i = exp(2 s_i), c = sqrt(prod a_i / prod (a_i + f^2)),
+ *     s'_i = s_i + log1p(f^2 exp(-2 s_i)) / 2           so that exp(s'_i) = sqrt(a_i + f^2)
+ *     o'   = logit(sigmoid(o) c)                        so that sigmoid(o') = sigmoid(o) c
+ * o' in the form that is stable for large |o| (csrc/filter3d_math.h).  Evaluated in float64 inside the lane, each output
+ * the float64 result rounded once.  f = 0 returns s and o bit for bit.  One launch, one lane per row; the outputs may not
+ * alias the inputs.  P = 0 is a success that launches nothing. */
+int gsr_filter3d_apply(const float* scaling, const float* opacity, const float* filter, int64_t P, float* scaling_out,
+                       float* opacity_out, void* stream);
+/* The gradient of gsr_filter3d_apply: dL_dscaling_out [P,3], dL_dopacity_out [P] -> dL_dscaling [P,3], dL_dopacity [P];
+ * the filter carries no gradient.  Recomputed from the inputs in float64, one launch, rounded once. */
+int gsr_filter3d_apply_bwd(const float* scaling, const float* opacity, const float* filter, int64_t P,
+                           const float* dL_dscaling_out, const float* dL_dopacity_out, float* dL_dscaling,
+                           float* dL_dopacity, void* stream);
 
 #ifdef __cplusplus
 }

@@ -32,6 +32,7 @@ from .mvs import (select_source_views, depth_consistency, backproject_depth, fus
                   multi_view_geo_loss, multi_view_ncc_loss, gray_image)
 from .compress import (kmeans_assign, kmeans, compress_model, CompressedGaussians, save_compressed,  # noqa: F401
                        load_compressed)
+from .filter3d import compute_3d_filter, apply_3d_filter, filtered_scaling_opacity  # noqa: F401
 
 __all__ = ["Scene", "Camera", "MiniCam", "PoseCamera", "ModelParams", "load_image", "load_image_host",
            "GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "render", "l1_loss", "apply_exposure", "save_exposures", "load_exposures", "l1_dssim_loss",
@@ -49,4 +50,5 @@ __all__ = ["Scene", "Camera", "MiniCam", "PoseCamera", "ModelParams", "load_imag
            "transform_points", "voxel_down_sample", "estimate_similarity", "align_cameras", "icp_step", "icp_registration",
            "register_tnt", "load_crop_volume", "crop_points", "depth_prior_loss",
            "masked_l1_dssim_loss", "alpha_mask_loss",
-           "kmeans_assign", "kmeans", "compress_model", "CompressedGaussians", "save_compressed", "load_compressed"]
+           "kmeans_assign", "kmeans", "compress_model", "CompressedGaussians", "save_compressed", "load_compressed",
+           "compute_3d_filter", "apply_3d_filter", "filtered_scaling_opacity"]

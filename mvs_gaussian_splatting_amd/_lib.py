@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # instead of copying it over the in-tree library
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "libgsr_hip.so")
 
-ABI_VERSION = 46
+ABI_VERSION = 47
 
 
 class GsrParams(C.Structure):
@@ -92,6 +92,16 @@ class GsrCullView(C.Structure):
     """One row of the view table of ``gsr_cull_view_counts`` (include/gsr.h, ABI v41; mesh.py): 96 bytes."""
     _fields_ = [("mask", C.c_void_p), ("depth", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32),
                 ("fx", C.c_float), ("fy", C.c_float), ("world_to_view", C.c_float * 16)]
+
+
+FILTER3D_MAX_VIEWS = 65535
+FILTER3D_MIP_SPLATTING, FILTER3D_PAPER = 0, 1
+
+
+class GsrFilterView(C.Structure):
+    """One row of the view table of ``gsr_filter3d_sample`` (include/gsr.h, ABI v47; filter3d.py): 80 bytes."""
+    _fields_ = [("world_to_view", C.c_float * 16), ("fx", C.c_float), ("fy", C.c_float), ("width", C.c_int32),
+                ("height", C.c_int32)]
 
 
 # the mesh rasterizer (include/gsr.h, ABI v42; mesh.py): image limits, the two launch constants and the flags
@@ -411,6 +421,15 @@ SYMBOLS = {
     "gsr_raster_resolve": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gsr_raster_count_faces": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),
+    # Mip-Splatting's 3D smoothing filter: the sampling pass over the training views, its finish, and the fused
+    # application to raw scales and opacities with its gradient (csrc/filter3d.hip; filter3d.py)
+    "gsr_filter3d_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gsr_filter3d_sample": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int32] +
+                            [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
+    "gsr_filter3d_finish": (C.c_int, [C.c_int64] + [C.c_void_p] * 3 + [C.c_int32, C.c_float, C.c_float, C.c_void_p,
+                                                                       C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsr_filter3d_apply": (C.c_int, [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 3),
+    "gsr_filter3d_apply_bwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 5),
 }
 
 _lib = None

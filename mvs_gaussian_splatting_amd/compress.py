@@ -375,6 +375,10 @@ def compress_model(model_or_dict, codebook_size: int = 4096, iters: int = 10, gr
         raise ValueError(f"groups must be distinct names out of {GROUPS}, got {groups}")
     if xyz_dtype not in ("float32", "float16"):
         raise ValueError(f"xyz_dtype must be 'float32' or 'float16', got {xyz_dtype!r}")
+    carried = model_or_dict.get("filter_3D") if isinstance(model_or_dict, dict) else getattr(model_or_dict, "filter_3D", None)
+    if carried is not None:
+        raise ValueError("the model still carries a 3D smoothing filter, which the container has no place for: bake it in "
+                         "with fuse_filter_3D_() first (a dict: apply_3d_filter on its _scaling and _opacity)")
     m = _tensors_of(model_or_dict)
     P, degree = int(m["xyz"].shape[0]), m["degree"]
     weights = _check_weights(weights, P, m["xyz"])

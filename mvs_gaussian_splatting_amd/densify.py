@@ -38,6 +38,14 @@ FORK_FLAG = {"dirs_prob": "grow_dir", "conti_dirs": "continous_dir", "grow_dist"
 GROW, CLONE_SPLIT = "grow", "clone_split"
 
 
+def mark_filter_stale(model) -> None:
+    """Every package operation that removes, adds, moves or permutes rows calls this: a ``filter_3D`` computed for the old
+    rows must be recomputed (``GaussianModel.compute_3D_filter``) before ``render`` accepts the model again.  A model
+    without a filter is left exactly as it is."""
+    if getattr(model, "filter_3D", None) is not None:
+        model._filter_3D_stale = True
+
+
 def swap_rows_(model, attrs, new, moment) -> None:
     """The optimizer surgery every change of the row count shares (``_prune_optimizer`` / ``cat_tensors_to_optimizer``,
     ``:401-422``, ``:451-472``).  ``attrs``: ``{group name: model attribute}``; ``new``: ``{group name: new tensor}``;
@@ -47,7 +55,9 @@ def swap_rows_(model, attrs, new, moment) -> None:
     state dict of the old parameter always moves to the new one, whatever it holds: ``exp_avg`` and ``exp_avg_sq`` go
     through ``moment`` where present, every other key (``step`` included) is carried over as it is, and no entry stays
     behind under the dead parameter.  A tensor that no group owns keeps its kind (``nn.Parameter`` or plain tensor) and
-    its ``requires_grad``.  The model's attributes are then set."""
+    its ``requires_grad``.  The model's attributes are then set.  A model that carries a 3D smoothing filter
+    (``filter_3D``; filter3d.py) has it marked stale: its rows no longer belong to these rows."""
+    mark_filter_stale(model)
     optimizer = getattr(model, "optimizer", None)
     owned = {}
     for group in optimizer.param_groups if optimizer is not None else ():

@@ -19,7 +19,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .densify import GROUP_ATTR, is_fork, swap_rows_
+from .densify import GROUP_ATTR, is_fork, mark_filter_stale, swap_rows_
 
 DRAW_HIGH = 2 ** 63 - 1      # torch.randint's largest exclusive bound: draws are uniform in [0, 2^63 - 1)
 
@@ -215,6 +215,7 @@ def relocate_gs(model, dead_threshold: float = 0.005, generator: Optional[torch.
     idx, count = sample_alive(model._opacity, n, dead_threshold, draws)
     new_o, new_s = relocation(idx, count, model._opacity, model._scaling)
     found = idx >= 0
+    mark_filter_stale(model)                                        # dead rows move onto their sources
     src = torch.where(found, idx.long(), dead)
     new_o = torch.where(found[:, None], new_o, model._opacity.detach()[dead])
     new_s = torch.where(found[:, None], new_s, model._scaling.detach()[dead])

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import _lib, knn, optim, ply_io
+from . import _lib, filter3d, knn, optim, ply_io
 from .densify import FORK_ATTR, FORK_FLAG, GROUP_ATTR
 from .sh import RGB2SH
 
@@ -56,6 +56,24 @@ def covariance_from_scaling_rotation(scaling, scaling_modifier, rotation):
     L = R * s[:, None, :]
     cov = L @ L.transpose(1, 2)
     return torch.stack([cov[:, 0, 0], cov[:, 0, 1], cov[:, 0, 2], cov[:, 1, 1], cov[:, 1, 2], cov[:, 2, 2]], dim=1)
+
+
+checked_filter_3D = filter3d.checked_filter_3D
+
+
+def _required_filter(pc, what: str):
+    f = checked_filter_3D(pc, what)
+    if f is None:
+        raise ValueError(f"{what}: the model has no 3D filter; call compute_3D_filter(cameras) first")
+    return f
+
+
+class _Fused:
+    """What ``ply_io.save_ply`` reads of a model, with the effective raw scales and opacities in place of its own."""
+
+    def __init__(self, model, scaling, opacity):
+        self._xyz, self._features_dc, self._features_rest = model._xyz, model._features_dc, model._features_rest
+        self._rotation, self._scaling, self._opacity = model._rotation, scaling, opacity
 
 
 def _need_gpu(name: str, t: torch.Tensor) -> None:
@@ -109,6 +127,10 @@ class GaussianModel:
         self.exposure_mapping = {}
         self.pretrained_exposures = None
         self.exposure_optimizer = None
+        # Mip-Splatting's 3D smoothing filter (filter3d.py): absent until compute_3D_filter is called
+        self.filter_3D = None
+        self.filter_3D_none_seen = None         # device int32 [1]: 1 when the cameras saw no Gaussian (the filter is 0)
+        self._filter_3D_stale = False           # set by every operation that removes, adds, moves or permutes rows
         # :34-42; render's raw-parameter path recognises the model by these three
         self.scaling_activation = torch.exp
         self.scaling_inverse_activation = torch.log
@@ -157,6 +179,47 @@ class GaussianModel:
     @property
     def get_conti_dirs(self):
         return self._conti_dirs
+
+    # ---- the 3D smoothing filter (Mip-Splatting's scene/gaussian_model.py; filter3d.py) --------------------------------
+    @torch.no_grad()
+    def compute_3D_filter(self, cameras, **kw):
+        """``filter_3D [P]`` from the training cameras: ``filter3d.compute_3d_filter(self._xyz, cameras, **kw)`` (``near``,
+        ``margin``, ``variance``, ``rule``).  From then on ``render`` draws the filtered model, until
+        ``fuse_filter_3D_()`` bakes it in or ``filter_3D`` is set to None.  Call it again after every change of the rows
+        (densification, pruning, reordering, MCMC relocation): those mark the filter stale and ``render`` refuses it."""
+        _need_gpu("compute_3D_filter", self._xyz)
+        self.filter_3D, self.filter_3D_none_seen = filter3d.compute_3d_filter(self._xyz.detach(), cameras, **kw)
+        self._filter_3D_stale = False
+        return self.filter_3D
+
+    def checked_filter_3D(self, what: str = "render"):
+        """``filter_3D``, or None for a model without one; ``ValueError`` for a stale or wrongly sized filter.  Host code."""
+        return checked_filter_3D(self, what)
+
+    @property
+    def get_scaling_with_3D_filter(self):
+        """``sqrt(exp(2 s) + f^2)`` ``[P,3]``; ``ValueError`` without a valid filter."""
+        return filter3d.filtered_scaling_opacity(self._scaling, self._opacity, _required_filter(self, "get_scaling_with_3D_filter"))[0]
+
+    @property
+    def get_opacity_with_3D_filter(self):
+        """``sigmoid(o) sqrt(prod a_i / prod (a_i + f^2))`` ``[P,1]``; ``ValueError`` without a valid filter."""
+        return filter3d.filtered_scaling_opacity(self._scaling, self._opacity, _required_filter(self, "get_opacity_with_3D_filter"))[1]
+
+    @torch.no_grad()
+    def fuse_filter_3D_(self):
+        """Bakes the filter into ``_scaling`` and ``_opacity`` in place (the effective raw values of
+        ``filter3d.apply_3d_filter``; the ``Parameter`` objects and the optimizer's state stay) and drops it: the model
+        then renders the same frames without a filter, in any viewer.  Nothing happens without a filter."""
+        f = checked_filter_3D(self, "fuse_filter_3D_")
+        if f is None:
+            return self
+        s, o = filter3d.apply_3d_filter(self._scaling.detach(), self._opacity.detach(), f)
+        self._scaling.detach().copy_(s)
+        self._opacity.detach().copy_(o)
+        self.filter_3D = self.filter_3D_none_seen = None
+        self._filter_3D_stale = False
+        return self
 
     def get_covariance(self, scaling_modifier=1):
         return self.covariance_activation(self.get_scaling, scaling_modifier, self._rotation)
@@ -331,16 +394,22 @@ class GaussianModel:
                           "exposure_optimizer": self.exposure_optimizer.state_dict()},)
         if self.xyz_gradient_accum_abs is not None:   # behind everything else, and only when it exists: a model without
             out = out + ({"xyz_gradient_accum_abs": self.xyz_gradient_accum_abs},)      # it writes the tuples above
+        if self.filter_3D is not None:                # last of all, and only when it exists
+            out = out + ({"filter_3D": self.filter_3D, "filter_3D_stale": bool(self._filter_3D_stale)},)
         return out
 
     def restore(self, model_args, training_args, optimizer_cls=None):
         """``:133-149``; accepts every form ``capture`` returns: the 12-tuple, with the fork's dict, and either with the
-        exposures' dict, and any of them with the absolute-gradient accumulator's dict last (``ValueError`` when the checkpoint has exposures and this model none, or the reverse: call
+        exposures' dict, and any of them with the absolute-gradient accumulator's dict, and any of those with the 3D
+        filter's dict last (``ValueError`` when the checkpoint has exposures and this model none, or the reverse: call
         ``setup_exposures`` first, or not at all).  ``training_setup`` runs first, with
         ``optimizer_cls`` (default: the class ``training_setup`` was last given, else the one
         ``training_args.optimizer_type`` names: ``optim.Adam`` unless it says ``"sparse_adam"``), then the saved
         state is loaded into it: state dicts move freely between ``torch.optim.Adam`` and ``optim.Adam``."""
         model_args = tuple(model_args)
+        filter_dict = None
+        if model_args and isinstance(model_args[-1], dict) and "filter_3D" in model_args[-1]:
+            filter_dict, model_args = model_args[-1], model_args[:-1]
         accum_abs = None
         if model_args and isinstance(model_args[-1], dict) and set(model_args[-1]) == {"xyz_gradient_accum_abs"}:
             accum_abs, model_args = model_args[-1]["xyz_gradient_accum_abs"], model_args[:-1]
@@ -377,10 +446,27 @@ class GaussianModel:
         self.optimizer.load_state_dict(opt_dict)
         if exposures is not None:
             self.exposure_optimizer.load_state_dict(exposures["exposure_optimizer"])
+        # a checkpoint without the filter's dict restores a model without a filter
+        self.filter_3D = None if filter_dict is None else filter_dict["filter_3D"]
+        self.filter_3D_none_seen = None
+        self._filter_3D_stale = bool(filter_dict.get("filter_3D_stale", False)) if filter_dict is not None else False
 
     # ---- PLY :293-358 (ply_io.py) -----------------------------------------------------------------------------------
-    def save_ply(self, path):
-        ply_io.save_ply(self, path)
+    def save_ply(self, path, fuse_filter=False):
+        """``save_ply``.  A model that carries a 3D filter writes it as one more property, ``filter_3D``, behind ``rot_3``
+        (Mip-Splatting's layout); a model without one writes the bytes it always wrote.  ``fuse_filter=True``: a standard
+        PLY with the filter baked into ``scale_*`` and ``opacity`` (the effective raw values) and no ``filter_3D``
+        property -- Mip-Splatting's fused PLY, for viewers that know nothing of the filter; the model itself is left as
+        it is."""
+        f = checked_filter_3D(self, "save_ply")
+        if f is None:
+            ply_io.save_ply(self, path)
+        elif fuse_filter:
+            with torch.no_grad():
+                s, o = filter3d.apply_3d_filter(self._scaling.detach(), self._opacity.detach(), f)
+            ply_io.save_ply(_Fused(self, s, o), path)
+        else:
+            ply_io.save_ply(self, path, filter_3D=f)
 
     def load_ply(self, path, device=None):
         """``load_ply``: the six parameters from the file, on ``device`` (default: where the model lives, else the
@@ -393,6 +479,9 @@ class GaussianModel:
         for a in GROUP_ATTR.values():
             setattr(self, a, nn.Parameter(tensors[a].requires_grad_(True)))
         self.active_sh_degree = self.max_sh_degree
+        self.filter_3D = tensors.get("filter_3D")          # the file's, or None: a standard PLY carries no filter
+        self.filter_3D_none_seen = None
+        self._filter_3D_stale = False
 
     # ---- vector-quantised file (compress.py) -----------------------------------------------------------
     def save_compressed(self, path, **kw):
@@ -416,6 +505,8 @@ class GaussianModel:
         for a in GROUP_ATTR.values():
             setattr(self, a, nn.Parameter(tensors[a].requires_grad_(True)))
         self.active_sh_degree = self.max_sh_degree
+        self.filter_3D = self.filter_3D_none_seen = None
+        self._filter_3D_stale = False
 
 
-__all__ = ["GaussianModel", "sphere_points", "inverse_sigmoid"]
+__all__ = ["GaussianModel", "sphere_points", "inverse_sigmoid", "checked_filter_3D"]

@@ -36,9 +36,11 @@ def attribute_names(n_dc: int, n_rest: int, n_scale: int = 3, n_rot: int = 4) ->
     return names
 
 
-def save_ply(model, path: str) -> None:
+def save_ply(model, path: str, filter_3D=None) -> None:
     """Write ``model`` (anything with ``_xyz, _features_dc [P,1,3], _features_rest [P,k,3], _opacity, _scaling,
-    _rotation``) exactly as ``GaussianModel.save_ply`` does."""
+    _rotation``) exactly as ``GaussianModel.save_ply`` does.  ``filter_3D`` (``[P]``; Mip-Splatting's 3D smoothing
+    filter): written as one more ``float`` property of that name behind ``rot_3``, as Mip-Splatting's ``save_ply`` does;
+    None writes the standard file, byte for byte."""
     d = os.path.dirname(path)
     if d:
         os.makedirs(d, exist_ok=True)
@@ -50,6 +52,12 @@ def save_ply(model, path: str) -> None:
     rot = model._rotation.detach().cpu().numpy()
     cols = np.concatenate((xyz, np.zeros_like(xyz), f_dc, f_rest, opac, scale, rot), axis=1).astype("<f4")
     names = attribute_names(f_dc.shape[1], f_rest.shape[1], scale.shape[1], rot.shape[1])
+    if filter_3D is not None:
+        extra = filter_3D.detach().cpu().numpy().reshape(-1, 1).astype("<f4")
+        if extra.shape[0] != cols.shape[0]:
+            raise ValueError(f"filter_3D has {extra.shape[0]} values for {cols.shape[0]} Gaussians")
+        cols = np.concatenate((cols, extra), axis=1)
+        names.append("filter_3D")
     assert cols.shape[1] == len(names)
     header = ["ply", "format binary_little_endian 1.0", f"element vertex {cols.shape[0]}"]
     header += [f"property float {n}" for n in names]
@@ -263,6 +271,8 @@ def load_ply(path: str, max_sh_degree: int = 3, device="cpu") -> Dict[str, torch
     rots = np.stack([col(n) for n in sorted((n for n in names if n.startswith("rot")),
                                             key=lambda s: int(s.split("_")[-1]))], axis=1)
     t = lambda a: torch.tensor(a, dtype=torch.float32, device=device)  # noqa: E731
+    # Mip-Splatting's extra property, only when the file has it: a standard file gives the standard dict
+    extra = {"filter_3D": t(col("filter_3D"))} if "filter_3D" in names else {}
     return {"_xyz": t(xyz), "_features_dc": t(f_dc).transpose(1, 2).contiguous(),
             "_features_rest": t(f_rest).transpose(1, 2).contiguous(), "_opacity": t(col("opacity")[:, None]),
-            "_scaling": t(scales), "_rotation": t(rots), "active_sh_degree": max_sh_degree}
+            "_scaling": t(scales), "_rotation": t(rots), "active_sh_degree": max_sh_degree, **extra}

@@ -18,6 +18,7 @@ import torch
 from . import grow
 from .exposure import apply_exposure
 from .features import gaussian_normals, gaussian_planes
+from .filter3d import apply_3d_filter, checked_filter_3D
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, _grown_key, rasterize_gaussians_fused
 from .sh import eval_sh
 from .surface import plane_depth as _plane_depth
@@ -155,7 +156,17 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier:
     component, the sum over its pixels of ``|d L / d mean2D|`` of the COLOUR image (the maps' losses take no part), in
     ``viewspace_points.grad``'s scale, z = 0.  ``"render"``, ``"radii"`` and every other gradient are bit-identical to the
     frame without it.  The same two conditions as for ``return_depth`` apply; hand both leaves to
-    ``add_densification_stats(model, viewspace_points, radii, viewspace_abs=viewspace_points_abs)``."""
+    ``add_densification_stats(model, viewspace_points, radii, viewspace_abs=viewspace_points_abs)``.
+
+    ``pc.filter_3D`` set (Mip-Splatting's 3D smoothing filter; ``GaussianModel.compute_3D_filter``): the
+    frame draws the filtered model.  The fused path hands the operator the effective raw tensors of
+    ``filter3d.apply_3d_filter(pc._scaling, pc._opacity, pc.filter_3D)`` where ``_scaling`` and ``_opacity`` went (one more
+    launch, and one in the backward; the gradients land on ``_scaling`` and ``_opacity``); the getter path hands it their
+    activations.  ``gaussian_normals`` and ``gaussian_planes`` keep the unfiltered scales: adding the same ``f^2`` to all
+    three squared axes does not change which axis is the flattest, so the normal is the same.  A filter that is stale
+    (rows were removed, added or reordered since it was computed) or not ``[P]`` is refused with a ``ValueError`` that
+    names ``compute_3D_filter``, before a GPU is asked for; so is a filter on a frame of the open grow / learned-split
+    branch.  Without a filter the frame is issued exactly as before."""
     if distortion_kwargs is not None and not return_distortion:
         raise ValueError("distortion_kwargs needs return_distortion=True")
     pkg = _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, grow_dir,
@@ -176,7 +187,13 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
             plane_depth=False, abs_grad=False):
     """The frame of ``render`` as the rasterizer leaves it.  ``abs_grad``: ``render``'s.  ``distortion``: None, or the operator's ``distortion=``;
     ``median_depth``: the operator's ``median_depth=``; ``plane_depth``: ``render``'s ``return_plane_depth``."""
+    filt = checked_filter_3D(pc)                       # host checks only; None for a model without a filter
     which = grow.branch(iteration, opt, grow_dir, continous_dir, modelcg)
+    if which is not None and filt is not None:
+        raise ValueError("a 3D filter is not available on a frame of the open grow / learned-split branch (virtual rows "
+                         "appended): set filter_3D = None, or call compute_3D_filter after the branch has closed")
+    if filt is not None and not all(hasattr(pc, k) for k in ("_scaling", "_opacity")):
+        raise ValueError("a 3D filter needs the model's raw _scaling and _opacity (exp / sigmoid activations)")
     if plane_depth:
         if which is not None:
             raise ValueError("return_plane_depth=True is not available on a frame of the open grow / learned-split branch "
@@ -233,6 +250,10 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
         extra_stats = dict(extra_stats, features=rows[0] if len(rows) == 1 else torch.cat(rows, dim=1))
 
     median_kw = {"median_depth": True} if median_depth else {}
+    # the tensors the operator is handed where _scaling and _opacity go: the model's own, or with a 3D filter the
+    # effective raw ones (their exp / sigmoid are the filtered values)
+    raw_scaling, raw_opacity = (getattr(pc, "_scaling", None), getattr(pc, "_opacity", None)) if filt is None \
+        else apply_3d_filter(pc._scaling, pc._opacity, filt)
 
     def feature_entries(out):
         """The operator's trailing ``feat`` / ``dist`` / ``median``, ``median_id`` as the dict's ``"features"`` /
@@ -270,8 +291,8 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
         # a torch compare over 6 M radii is a 9-us kernel per frame
         visible = torch.empty(xyz.shape[0], dtype=torch.bool, device=xyz.device)
         if return_depth or want_feat or distortion is not None or median_depth:
-            out = rasterize_gaussians_fused(xyz, screenspace_points, pc._features_dc, pc._features_rest, pc._opacity,
-                                            pc._scaling, pc._rotation, raster_settings, visible=visible,
+            out = rasterize_gaussians_fused(xyz, screenspace_points, pc._features_dc, pc._features_rest, raw_opacity,
+                                            raw_scaling, pc._rotation, raster_settings, visible=visible,
                                             **({"aux_maps": True} if return_depth else {}), **extra_stats,
                                             **({} if distortion is None else {"distortion": distortion}), **median_kw,
                                             **abs_kw)
@@ -279,7 +300,7 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
                                      "visibility_filter": visible, "radii": out[1], "selected_pts_mask": None,
                                      **(_aux_entries(out[2]) if return_depth else {}), **feature_entries(out)})
         rendered_image, radii = rasterize_gaussians_fused(xyz, screenspace_points, pc._features_dc, pc._features_rest,
-                                                          pc._opacity, pc._scaling, pc._rotation, raster_settings,
+                                                          raw_opacity, raw_scaling, pc._rotation, raster_settings,
                                                           densify_stats=stats, visible=visible, **extra_stats, **abs_kw)
         return {"render": rendered_image, "viewspace_points": screenspace_points, **abs_entry,
                 "visibility_filter": visible, "radii": radii, "selected_pts_mask": None}
@@ -289,10 +310,13 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
                                     **extra_stats, **({} if distortion is None else {"distortion": distortion}), **median_kw,
                                     **({"abs_grad": True} if abs_grad else {}))
     scales = rotations = cov3D_precomp = None
+    if filt is not None:
+        filtered_scales, filtered_opacity = torch.exp(raw_scaling), torch.sigmoid(raw_opacity)
     if getattr(pipe, "compute_cov3D_python", False):
-        cov3D_precomp = pc.get_covariance(scaling_modifier)
+        cov3D_precomp = pc.get_covariance(scaling_modifier) if filt is None else \
+            pc.covariance_activation(filtered_scales, scaling_modifier, pc._rotation)
     else:
-        scales, rotations = pc.get_scaling, pc.get_rotation
+        scales, rotations = pc.get_scaling if filt is None else filtered_scales, pc.get_rotation
 
     shs = colors_precomp = None
     if override_color is None:
@@ -313,7 +337,8 @@ def _render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_col
     if abs_grad:
         extra["means2D_abs"] = abs_kw["means2D_abs"]
     out = rasterizer(means3D=xyz, means2D=screenspace_points, shs=shs,
-                     colors_precomp=colors_precomp, opacities=pc.get_opacity, scales=scales,
+                     colors_precomp=colors_precomp, opacities=pc.get_opacity if filt is None else filtered_opacity,
+                     scales=scales,
                      rotations=rotations, cov3D_precomp=cov3D_precomp, **extra)
     rendered_image, radii = out[0], out[1]
     return with_plane_depth({"render": rendered_image,

@@ -123,6 +123,14 @@ class OptimizationParams:
     mask_normalize = "image"
     lambda_alpha_mask = 0.0
     alpha_mask_mode = "bce"
+    # Mip-Splatting's 3D smoothing filter (filter3d.py; training_iteration(filter_cameras=)): the model is
+    # rendered through model.filter_3D, recomputed from the training cameras after every densification step, at iteration 1
+    # and every filter_3d_interval iterations once densification has ended; filter_3d_rule "mip_splatting" (the published
+    # code's width) or "paper"; False leaves the iteration as it is
+    filter_3d = False
+    filter_3d_interval = 100
+    filter_3d_rule = "mip_splatting"
+    filter_3d_variance = 0.2
 
     def __init__(self, **overrides):
         for k, v in overrides.items():
@@ -154,7 +162,8 @@ def depth_prior_weight(opt, iteration: int) -> float:
 
 def training_iteration(model, camera, opt, pipe, background, iteration, *, dataset=None, cameras_extent,
                        first_reset=None, gt_image=None, densify_kwargs=None, pose_optimizer=None, depth_loss=None,
-                       train_exposure=False, mcmc_kwargs=None, source_camera=None, bilateral_grids=None):
+                       train_exposure=False, mcmc_kwargs=None, source_camera=None, bilateral_grids=None,
+                       filter_cameras=None):
     """``train.py:72-142`` for one camera, in the reference's order: learning rate, SH degree, background, ``render``
     with the fork's keyword arguments, L1 + D-SSIM against ``camera.original_image``, the opacity sparsity term
     (``opt.opacitysparse``), ``backward``; then, without gradients, the densification statistics, ``densify_and_prune``,
@@ -252,7 +261,30 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
     combinations and refusals as on ``depth_loss`` frames); an active depth prior's ``depth_mask`` is multiplied by the
     mask.  The normal, distortion and multi-view terms do not see the mask.  ``ValueError`` for an unknown
     ``opt.mask_normalize`` or ``opt.alpha_mask_mode``, before anything is rendered.  A camera without a mask: exactly the
-    calls made without it."""
+    calls made without it.
+    ``opt.filter_3d`` (Mip-Splatting's 3D smoothing filter): ``filter_cameras``, the training cameras, is
+    required (``ValueError`` without it, for an unknown ``opt.filter_3d_rule``, and for a fork grow / learned-split model,
+    whose frames ``render`` refuses a filter on).  ``model.compute_3D_filter(filter_cameras, rule=opt.filter_3d_rule,
+    variance=opt.filter_3d_variance)`` runs before the frame at iteration 1 (and whenever the model has no valid filter,
+    as after a restart), after every ``densify_and_prune`` and after MCMC's relocate / add, and, once densification has
+    ended (``iteration > opt.densify_until_iter``), every ``opt.filter_3d_interval`` iterations up to one interval before
+    ``opt.iterations``; every frame is rendered through the filter and the gradients land on ``_scaling`` and
+    ``_opacity``.  ``filter_3d = False``: ``filter_cameras`` is ignored, exactly the calls made without it."""
+    filter_on = bool(getattr(opt, "filter_3d", False))
+    if filter_on:
+        if filter_cameras is None:
+            raise ValueError("opt.filter_3d needs filter_cameras, the training cameras the filter is computed from")
+        filter_kw = dict(rule=getattr(opt, "filter_3d_rule", "mip_splatting"),
+                         variance=float(getattr(opt, "filter_3d_variance", 0.2)))
+        if filter_kw["rule"] not in ("mip_splatting", "paper"):
+            raise ValueError(f"opt.filter_3d_rule must be 'mip_splatting' or 'paper', got {filter_kw['rule']!r}")
+        filter_interval = int(getattr(opt, "filter_3d_interval", 100))
+        if filter_interval <= 0:
+            raise ValueError(f"opt.filter_3d_interval must be positive, got {filter_interval}")
+        if is_fork(model) or any(bool(getattr(dataset, n, False)) for n in (
+                "grow_dir", "continous_dir", "learn_split_distance", "learn_split_scale")):
+            raise ValueError("opt.filter_3d does not support the fork's grow / learned-split models: render refuses a 3D "
+                             "filter on their frames (virtual rows appended)")
     prior_weight = depth_prior_weight(opt, iteration) if getattr(camera, "depth_reliable", False) else 0.0
     prior_on = prior_weight > 0.0
     if prior_on:
@@ -348,6 +380,9 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
         bilateral_grids.update_learning_rate(iteration)
     if todo["sh_up"]:                                                                           # :75-76
         model.oneupSHdegree()
+    if filter_on and (iteration == 1 or getattr(model, "filter_3D", None) is None
+                      or getattr(model, "_filter_3D_stale", False)):
+        model.compute_3D_filter(filter_cameras, **filter_kw)
     bg = torch.rand((3), device=background.device) if opt.random_background else background    # :89
     render_kwargs = dict(grow_dir=flag("grow_dir"), densify_grad_threshold=opt.densify_grad_threshold,
                          iteration=iteration, opt=opt, continous_dir=flag("continous_dir"),
@@ -421,6 +456,8 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
             if todo["densify"]:
                 relocate_gs(model, generator=mk.get("generator"), draws=mk.get("draws"))
                 add_new_gs(model, opt.cap_max, generator=mk.get("generator"), draws=mk.get("draws"))
+                if filter_on:
+                    model.compute_3D_filter(filter_cameras, **filter_kw)
         elif todo["stats"]:                                                                     # :127-137
             add_densification_stats(model, pkg["viewspace_points"], pkg["radii"],
                                     **({"viewspace_abs": pkg["viewspace_points_abs"]} if abs_on else {}))
@@ -428,8 +465,13 @@ def training_iteration(model, camera, opt, pipe, background, iteration, *, datas
                 densify_and_prune(model, opt.densify_grad_threshold, opt.min_opacity, cameras_extent,
                                   todo["size_threshold"], opt=opt, iteration=iteration, **(densify_kwargs or {}),
                                   **({"abs_grad_threshold": opt.densify_abs_grad_threshold} if abs_on else {}))
+                if filter_on:
+                    model.compute_3D_filter(filter_cameras, **filter_kw)
             if todo["reset"]:
                 model.reset_opacity()
+        if filter_on and iteration > opt.densify_until_iter and iteration % filter_interval == 0 \
+                and iteration < opt.iterations - filter_interval:
+            model.compute_3D_filter(filter_cameras, **filter_kw)
         if todo["step"]:                                                                        # :140-142
             if getattr(opt, "optimizer_type", "default") == "sparse_adam":
                 # the rows this frame produced a gradient for: the ones it saw, and on a grown / learned-split frame the
