@@ -365,7 +365,9 @@ def compress_model(model_or_dict, codebook_size: int = 4096, iters: int = 10, gr
     still canonical).  Positions are float32, or float16 with ``xyz_dtype="float16"``; opacity is raw float16.
     ``weights``: a per-Gaussian importance, float32 ``[P]``, finite and not negative (for instance
     ``ContributionStats``' blending-weight sum: LightGaussian's weighting); the centres are then weighted means.
-    A value that is not finite anywhere in the model is refused before any launch.  A group with at most
+    A value that is not finite anywhere in the model is refused before any launch, and so is a listed group whose rows
+    are wider than ``MAX_D`` = 64, which is ``f_rest`` at SH degree 4 (D = 72): such a model is compressed with
+    ``groups=("f_dc", "scaling", "rotation")`` and keeps its ``f_rest`` as float16.  A group with at most
     ``codebook_size`` rows is stored losslessly (``kmeans``' short-cut)."""
     K = _check_int(codebook_size, "codebook_size", 1, MAX_K)
     iters = _check_int(iters, "iters", 0, 10 ** 6)
@@ -381,6 +383,11 @@ def compress_model(model_or_dict, codebook_size: int = 4096, iters: int = 10, gr
                          "with fuse_filter_3D_() first (a dict: apply_3d_filter on its _scaling and _opacity)")
     m = _tensors_of(model_or_dict)
     P, degree = int(m["xyz"].shape[0]), m["degree"]
+    width = {"f_dc": 3, "f_rest": 3 * int(m["f_rest"].shape[1]), "scaling": 3, "rotation": 4}
+    for name in groups:
+        if width[name] > MAX_D:
+            raise ValueError(f"group {name} has D = {width[name]} at SH degree {degree}; k-means takes D in 1..{MAX_D}.  "
+                             f"Leave {name} out of groups and it is stored as float16")
     weights = _check_weights(weights, P, m["xyz"])
     rows = {"f_dc": m["f_dc"].reshape(P, 3), "f_rest": m["f_rest"].reshape(P, -1), "scaling": m["scaling"],
             "rotation": canonical_rotation(m["rotation"])}

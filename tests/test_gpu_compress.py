@@ -2,7 +2,8 @@
 DESIGN.md §7.33) on a synthetic model of 2000 Gaussians at SH degree 3: what comes back from the file is codebook[index]
 for the quantised groups and the float16 round trip for the others, rotations stay unit, the decoded model renders, and
 the two lossless corners -- a codebook no smaller than the model, and all the weight on one row -- reproduce their input
-bit for bit.  No image-quality number is pinned."""
+bit for bit.  At SH degrees 0, 1 and 2, with every group quantised under dense weights, each stored codebook and index is
+the restatement's Lloyd trajectory (``R.lloyd``) from the same init.  No image-quality number is pinned."""
 import math
 
 import numpy as np
@@ -66,6 +67,41 @@ def test_compress_save_load_decode_and_render(scene, gpu_device, tmp_path):
     mse = float(((img.detach() - ref.detach()) ** 2).mean())
     print(f"decoded against original: PSNR {10 * math.log10(1.0 / max(mse, 1e-20)):.2f} dB, payload {cg.nbytes()} bytes "
           f"against {P * 62 * 4}")
+
+
+@pytest.mark.parametrize("degree", [0, 1, 2])
+def test_every_group_is_the_restatements_trajectory_from_the_same_init(gpu_device, degree):
+    """All four groups quantised under dense weights at SH degree 0 (no f_rest), 1 (D = 9) and 2 (D = 24: the 16-step
+    instantiation of the matrix-core kernel through the public entry), positions as float16."""
+    n, K, iters, seed = 1500, 64, 3, 5
+    arrays, w = R.model_arrays(n, degree)
+    model = {k: torch.from_numpy(v).to(gpu_device) for k, v in arrays.items()}
+    cg = compress_model(model, codebook_size=K, iters=iters, xyz_dtype="float16", seed=seed,
+                        weights=torch.from_numpy(w).to(gpu_device))
+    assert cg.sh_degree == degree and set(cg.groups) == set(ROWS) - ({"f_rest"} if degree == 0 else set())
+    gen = torch.Generator(device="cpu")
+    gen.manual_seed(seed)
+    perm = torch.randperm(n, generator=gen).numpy()
+    for name, g in cg.groups.items():
+        rows = arrays[ROWS[name]].reshape(n, -1)
+        if name == "rotation":               # normalised on the device, as compress_model does, before it is clustered
+            rows = canonical_rotation(model["_rotation"]).cpu().numpy()
+        assert set(g) == {"codebook", "index"} and g["index"].dtype == np.uint16, name
+        books, index, _, _ = R.lloyd(rows, R.first_distinct(rows, perm, K), iters, w)
+        assert g["codebook"].shape == books[-1].shape == (K, {"f_dc": 3, "f_rest": 3 * ((degree + 1) ** 2 - 1), "scaling": 3,
+                                                              "rotation": 4}[name]), name
+        assert np.array_equal(g["index"].astype(np.int32), index), name
+        if name != "rotation":
+            assert np.array_equal(g["codebook"].view(np.uint32), books[-1].view(np.uint32)), name
+        else:        # the last codebook of the trajectory, each centre back at unit length: a float32 norm of four terms
+            q = g["codebook"].astype(np.float64)         # (at most 3 U relative) and one division (U), components <= 1
+            assert np.abs(np.linalg.norm(q, axis=1) - 1).max() <= 8 * R.U and (q[:, 0] >= 0).all()
+            assert np.abs(q - R.canonical_rotation(books[-1])).max() <= 8 * R.U
+    dec = cg.decode(gpu_device)
+    assert cg.xyz.dtype == np.float16 and torch.equal(dec["_xyz"], model["_xyz"].half().float())
+    g = cg.groups["scaling"]
+    assert np.array_equal(dec["_scaling"].cpu().numpy().view(np.uint32), g["codebook"][g["index"].astype(np.int64)].view(np.uint32))
+    assert dec["_features_rest"].shape == (n, (degree + 1) ** 2 - 1, 3)
 
 
 def test_a_codebook_no_smaller_than_the_model_is_lossless(scene, gpu_device):

@@ -1,10 +1,14 @@
 """GPU checks of the k-means layer (csrc/kmeans.hip; compress.kmeans_assign / kmeans_update / kmeans)
 against the numpy restatement (tests/kmeans_restate.py): the assignment bit for bit and within the derived float64 gap,
 padding, ties, repeatability, the two paths against each other, the centre update bit for bit, and Lloyd's iteration
-as a whole (monotone up to the stated slack, lossless on few distinct rows).
+as a whole (its init and every codebook of its trajectory bit for bit, monotone up to the stated slack, lossless on few
+distinct rows).
 
 The codebook stage of the kernel is 128 codes, its tile 32: K = 4097 is 32 full stages and a last stage of one code,
-K = 33 and K = 100 end inside a tile, K = 1 and 2 inside the first.  Every odd D meets only ragged K."""
+K = 33 and K = 100 end inside a tile, K = 1 and 2 inside the first, K = 128 and 256 fill their last stage, K = 65536 is
+the limit.  The first ten CASES leave D = 17..32 (one of the five instantiations of the kernel), the other edges of the
+dispatch on D, and every N that ends past wave 0 of its workgroup unvisited: ``R.ASSIGN_EDGE_CASES`` names those, and
+tests/test_kmeans_host.py checks which instantiation each reaches."""
 import functools
 
 import numpy as np
@@ -12,13 +16,13 @@ import pytest
 import torch
 
 import kmeans_restate as R
-from mvs_gaussian_splatting_amd.compress import kmeans, kmeans_assign, kmeans_update
+from mvs_gaussian_splatting_amd.compress import _distinct_rows, kmeans, kmeans_assign, kmeans_update
 
 pytestmark = pytest.mark.gpu
 
 #          N    K     D
 CASES = [(1, 1, 1), (31, 2, 3), (33, 33, 9), (257, 100, 45), (33, 4097, 63), (257, 4097, 4), (31, 100, 48),
-         (257, 33, 64), (33, 4097, 1), (257, 2, 45)]
+         (257, 33, 64), (33, 4097, 1), (257, 2, 45)] + [c[:3] for c in R.ASSIGN_EDGE_CASES]
 RANGES = ("unit", "wide")
 
 
@@ -103,11 +107,25 @@ def test_same_bits_twice_and_under_a_permutation_of_the_rows(gpu_device):
     assert np.array_equal(c[0], a[0][perm]) and np.array_equal(c[1].view(np.uint32), a[1][perm].view(np.uint32))
 
 
-@pytest.mark.parametrize("D", [3, 4])
-def test_vector_alu_path_agrees_with_the_matrix_core_path_bit_for_bit(gpu_device, D):
+def test_the_last_code_of_the_largest_codebook_can_win(gpu_device):
+    x, cb, rows, codes = R.largest_codebook_case()
+    index, dist2 = run(x, cb, gpu_device)
+    assert np.array_equal(index, R.assign(x, cb)[0])
+    assert np.array_equal(index[rows], codes) and (dist2[rows] == 0).all(), "a point equal to a code"
+    assert index.max() == 65535
+
+
+# every D of the vector-ALU kernel is an instantiation of its own; its stage is 1024 codes, so K = 1024 fills one and
+# K = 1025 leaves one code to a second.  (D = 3 and 4 at K = 4097 keep the ids they had before the other cases came.)
+VALU_CASES = [pytest.param(D, K, id=str(D) if D >= 3 and K == 4097 else f"{D}-{K}")
+              for D in (1, 2, 3, 4) for K in (1024, 1025, 4097)]
+
+
+@pytest.mark.parametrize("D,K", VALU_CASES)
+def test_vector_alu_path_agrees_with_the_matrix_core_path_bit_for_bit(gpu_device, D, K):
     rng = np.random.default_rng(D)
     x = rng.standard_normal((257, D)).astype(np.float32)
-    cb = rng.standard_normal((4097, D)).astype(np.float32)
+    cb = rng.standard_normal((K, D)).astype(np.float32)
     a, b = run(x, cb, gpu_device), run(x, cb, gpu_device, path="valu")
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.uint32), b[1].view(np.uint32))
 
@@ -145,7 +163,66 @@ def test_update_with_one_code_owning_every_row(gpu_device):
     assert empty == 2 and np.array_equal(got.cpu().numpy().view(np.uint32), want.view(np.uint32))
 
 
+@pytest.mark.parametrize("weighted", [False, True])
+def test_update_with_runs_that_end_where_a_workgroup_ends(gpu_device, weighted):
+    x, index, cb, w = R.workgroup_edge_update_input()
+    w = w if weighted else None
+    want, want_empty = R.update(x, index, cb, w)
+    t = lambda a: None if a is None else torch.from_numpy(a).to(gpu_device)                      # noqa: E731
+    got, empty = kmeans_update(t(x), t(index), t(cb), t(w))
+    got = got.cpu().numpy()
+    assert empty == want_empty == 2
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    assert np.array_equal(got[2], cb[2]) and np.array_equal(got[4], cb[4]), "an empty code keeps its centre"
+
+
 # ---- Lloyd's iteration -----------------------------------------------------------------------------------------------------
+def host_permutation(N, seed):
+    """The permutation ``kmeans`` walks for its init."""
+    gen = torch.Generator(device="cpu")
+    gen.manual_seed(seed)
+    return torch.randperm(N, generator=gen)
+
+
+@pytest.mark.parametrize("weighted", [False, True])
+def test_lloyds_trajectory_is_the_restatements_bit_for_bit(gpu_device, weighted):
+    x, w, K, iters, seed = R.trajectory_input()
+    w = w if weighted else None
+    first = R.first_distinct(x, host_permutation(len(x), seed).numpy(), K)
+    books, want_index, want_empty, dist2s = R.lloyd(x, first, iters, w)
+    codebook, index, info = kmeans(torch.from_numpy(x).to(gpu_device), K, iters=iters, seed=seed, history=True,
+                                   weights=None if w is None else torch.from_numpy(w).to(gpu_device))
+    assert len(info["codebooks"]) == len(books) == iters + 1 and not info["shortcut"]
+    for t, (got, want) in enumerate(zip(info["codebooks"], books)):
+        assert got.shape == want.shape == (K, x.shape[1]), t
+        differ = (got.view(np.uint32) != want.view(np.uint32)).any(axis=1)
+        assert not differ.any(), f"codebook {t}: codes {np.flatnonzero(differ)[:8]} differ in their bits"
+    assert np.array_equal(codebook.cpu().numpy().view(np.uint32), books[-1].view(np.uint32))
+    assert np.array_equal(index.cpu().numpy(), want_index)
+    assert info["empty"] == want_empty
+    assert len(info["objective"]) == iters + 1
+    for t, d in enumerate(dist2s):         # the float64 sum of the same float32 values: only the order of the sum differs
+        want = float(d.astype(np.float64).sum())
+        print(f"step {t}: objective {info['objective'][t]!r} against {want!r}")
+        assert abs(info["objective"][t] - want) <= 1e-6 * want, t
+
+
+def test_init_takes_the_first_k_distinct_rows_in_permutation_order(gpu_device):
+    x, seed = R.init_input()
+    perm = host_permutation(len(x), seed)
+    assert len(np.unique(x[perm.numpy()[:64]], axis=0)) < 64, "the first chunk has to leave the init short of K = 64"
+    xd = torch.from_numpy(x).to(gpu_device)
+    for K, rows in ((64, 64), (128, 90)):
+        want = R.first_distinct(x, perm.numpy(), K)
+        got = _distinct_rows(xd, perm.to(gpu_device), K).cpu().numpy()
+        assert len(want) == rows and np.array_equal(got, want), K
+    codebook, index, info = kmeans(xd, 128, iters=2, seed=seed)
+    assert codebook.shape == (90, x.shape[1]) and not info["shortcut"]
+    assert np.array_equal(codebook.cpu().numpy().view(np.uint32), x[R.first_distinct(x, perm.numpy(), 128)].view(np.uint32))
+    rebuilt = codebook.index_select(0, index.long()).cpu().numpy()
+    assert np.array_equal(rebuilt.view(np.uint32), x.view(np.uint32))
+
+
 def test_objective_does_not_rise_by_more_than_the_rounding_of_the_centres(gpu_device):
     rng = np.random.default_rng(21)
     centres = 4.0 * rng.standard_normal((12, 6))

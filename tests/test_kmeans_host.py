@@ -127,7 +127,8 @@ def host_check(tmp_path_factory):
     return run
 
 
-@pytest.mark.parametrize("N,K,D", [(40, 1, 1), (60, 70, 3), (50, 33, 4), (40, 100, 9), (30, 50, 45), (20, 40, 64)])
+@pytest.mark.parametrize("N,K,D", [(40, 1, 1), (60, 70, 3), (50, 33, 4), (40, 100, 9), (30, 50, 45), (20, 40, 64),
+                                   (30, 40, 17), (30, 40, 24), (30, 40, 32), (30, 40, 33)])
 def test_host_build_of_the_rule_gives_the_restatements_bits(host_check, N, K, D):
     rng = np.random.default_rng(100 * K + D)
     x = (rng.standard_normal((N, D)) * 10.0 ** rng.uniform(-2, 2, size=(N, 1))).astype(np.float32)
@@ -155,6 +156,90 @@ def test_fma32_is_correctly_rounded():
         got = Fraction(float(R.fma32(a[i], b[i], c[i])))
         lo, hi = np.nextafter(np.float32(got), np.float32(-np.inf)), np.nextafter(np.float32(got), np.float32(np.inf))
         assert abs(exact - got) <= abs(exact - Fraction(float(lo))) and abs(exact - got) <= abs(exact - Fraction(float(hi)))
+
+
+# ---- the premises of the GPU tests' inputs (kmeans_restate.py), checked on the restatement -----------------------------------
+def _host_permutation(N, seed):
+    gen = torch.Generator(device="cpu")
+    gen.manual_seed(seed)
+    return torch.randperm(N, generator=gen)
+
+
+def _dispatch_of_the_matrix_core_kernel():
+    """[(largest D, STEPS)] read from gsr_kmeans_assign in csrc/kmeans.hip, the last entry for every larger D."""
+    with open(os.path.join(ROOT, "mvs_gaussian_splatting_amd", "csrc", "kmeans.hip")) as f:
+        body = f.read().split("int gsr_kmeans_assign(", 1)[1].split("#undef GSR_KMEANS_LAUNCH", 1)[0]
+    table = [(int(d), int(s)) for d, s in re.findall(r"if \(D <= (\d+)\) GSR_KMEANS_LAUNCH\((\d+)\);", body)]
+    table.append((compress.MAX_D, int(re.search(r"\belse GSR_KMEANS_LAUNCH\((\d+)\);", body).group(1))))
+    return table
+
+
+def test_every_assignment_edge_case_reaches_the_instantiation_it_is_listed_for():
+    table = _dispatch_of_the_matrix_core_kernel()
+    assert table == [(4, 2), (16, 8), (32, 16), (48, 24), (64, 32)], "the dispatch moved: the edge cases are to move with it"
+    steps_of = lambda D: next(s for d, s in table if D <= d)                                      # noqa: E731
+    for N, K, D, steps, why in R.ASSIGN_EDGE_CASES:
+        assert steps_of(D) == steps and 2 * steps >= D, (N, K, D, why)
+    reached = {steps_of(D) for _, _, D, _, _ in R.ASSIGN_EDGE_CASES}
+    assert reached == {s for _, s in table}, "an instantiation without an edge case"
+    Ds = {D for _, _, D, _, _ in R.ASSIGN_EDGE_CASES}
+    # (D = 48 is among the first ten cases of tests/test_gpu_kmeans.py)
+    assert {d for d, _ in table[:-1]} | {d + 1 for d, _ in table[:-1]} <= Ds | {48}, "both sides of every threshold on D"
+    ends = {((N - 1) % 256 // 64, (N - 1) % 64 // 32) for N, _, _, _, _ in R.ASSIGN_EDGE_CASES}      # (wave, tile) of the last point
+    assert {(1, 1), (2, 1), (3, 0), (0, 0), (0, 1), (3, 1)} <= ends
+    Ks = {K for _, K, _, _, _ in R.ASSIGN_EDGE_CASES}
+    assert {128, 256, 129} <= Ks and all(1 <= K <= compress.MAX_K and N * K * D <= 3.5e7 for N, K, D, _, _ in R.ASSIGN_EDGE_CASES)
+    assert len({c[:3] for c in R.ASSIGN_EDGE_CASES}) == len(R.ASSIGN_EDGE_CASES)
+
+
+def test_largest_codebook_case_has_its_copies_where_it_says():
+    x, cb, rows, codes = R.largest_codebook_case()
+    assert cb.shape == (compress.MAX_K, 3) and x.shape == (97, 3) and len(set(rows)) == len(rows) == len(codes) == 8
+    assert list(codes) == [65535, 65534, 65408, 65407, 32768, 127, 128, 0] and 65408 % 128 == 0
+    assert np.array_equal(x[rows].view(np.uint32), cb[codes].view(np.uint32))
+    assert len(np.unique(cb.view(np.uint32), axis=0)) == len(cb), "two equal codes: the copy of the higher one would lose"
+    index, dist2 = R.assign(x, cb)
+    assert np.array_equal(index[rows], codes) and (dist2[rows] == 0).all() and index.max() == 65535
+
+
+def test_trajectory_input_has_duplicates_in_its_init_an_empty_code_and_codebooks_that_move():
+    x, w, K, iters, seed = R.trajectory_input()
+    assert x.shape == (1500, 6) and (K, iters) == (40, 5) and w.min() == 0 and w.max() <= 3
+    assert len(x) - len(np.unique(x.view(np.uint32), axis=0)) == 300 and 0.07 <= (w == 0).mean() <= 0.13
+    perm = _host_permutation(len(x), seed).numpy()
+    first = R.first_distinct(x, perm, K)
+    assert len(first) == K and not np.array_equal(first, perm[:K]), "the init meets no duplicate"
+    assert len(np.unique(x[first].view(np.uint32), axis=0)) == K
+    for weights in (None, w):
+        books, index, empties, dist2s = R.lloyd(x, first, iters, weights)
+        assert len(books) == len(dist2s) == iters + 1 and len(empties) == iters and np.array_equal(books[0], x[first])
+        assert np.array_equal(index, R.assign(x, books[-1])[0])
+        assert sum(not np.array_equal(books[t], books[t + 1]) for t in range(iters)) >= 2
+        if weights is not None:
+            assert min(empties) >= 1, "no code without weight in the weighted run"
+    books0, index0, empties0, _ = R.lloyd(x, first, 0)
+    assert len(books0) == 1 and empties0 == [] and np.array_equal(index0, R.assign(x, x[first])[0])
+
+
+def test_init_input_sends_the_init_round_its_loop_again_and_the_host_init_is_the_restatements():
+    x, seed = R.init_input()
+    perm = _host_permutation(len(x), seed)
+    assert len(np.unique(x.view(np.uint32), axis=0)) == 90 and len(x) == 5000
+    assert len(np.unique(x[perm.numpy()[:64]].view(np.uint32), axis=0)) < 64, "the first chunk of 64 would do"
+    assert len(np.unique(x[perm.numpy()[:64 + 128]].view(np.uint32), axis=0)) < 90, "K = 128 would be done after two chunks"
+    for K, rows in ((64, 64), (128, 90), (1, 1), (90, 90)):
+        want = R.first_distinct(x, perm.numpy(), K)
+        assert len(want) == rows and len(np.unique(x[want].view(np.uint32), axis=0)) == rows
+        order = np.argsort(perm.numpy())                       # the position of every row in the permutation
+        assert (np.diff(order[want]) > 0).all(), "not in the order of the permutation"
+        assert np.array_equal(compress._distinct_rows(torch.from_numpy(x), perm, K).numpy(), want), K     # torch ops only
+
+
+def test_update_input_has_its_runs_on_workgroup_edges():
+    x, index, cb, w = R.workgroup_edge_update_input()
+    assert len(x) == len(index) == len(w) == 768 and cb.shape == (5, x.shape[1]) and (w > 0).all()
+    assert np.array_equal(np.flatnonzero(np.diff(index)) + 1, [256, 512]) and sorted(set(index)) == [0, 1, 3]
+    assert R.update(x, index, cb)[1] == R.update(x, index, cb, w)[1] == 2
 
 
 # ---- the container -----------------------------------------------------------------------------------------------------------
@@ -279,3 +364,39 @@ def test_compress_model_on_a_dict_of_sh_degree_0(tmp_path):
             compress_model(d, **kw)
     with pytest.raises(ValueError):
         compress_model({"_xyz": d["_xyz"]})
+
+
+def test_sh_degree_4_is_refused_by_name_before_kmeans_is_entered(monkeypatch):
+    """f_rest at SH degree 4 has D = 72 > MAX_D: with f_rest listed (the default) nothing is clustered first."""
+    def entered(*a, **k):
+        raise AssertionError("kmeans was entered")
+    monkeypatch.setattr(compress, "kmeans", entered)
+    d = _model_dict(300, 4)
+    for kw in (dict(), dict(codebook_size=64), dict(codebook_size=300), dict(groups=("rotation", "f_rest"))):
+        with pytest.raises(ValueError) as e:
+            compress_model(d, **kw)
+        message = str(e.value)
+        assert "f_rest" in message and "72" in message and "64" in message and "groups" in message and "float16" in message
+    with pytest.raises(AssertionError, match="kmeans was entered"):          # what the patch does to a call that is let through
+        compress_model(d, groups=("f_dc",))
+    with pytest.raises(AssertionError, match="kmeans was entered"):          # D = 45 at degree 3 is still clustered
+        compress_model(_model_dict(300, 3))
+
+
+def test_sh_degree_4_compresses_with_f_rest_left_as_float16(tmp_path):
+    P = 120
+    d = _model_dict(P, 4)
+    cg = compress_model(d, codebook_size=P, groups=("f_dc", "scaling", "rotation"))          # P <= K: the short-cut, no launch
+    assert cg.sh_degree == 4 and set(cg.groups["f_rest"]) == {"half"} and cg.groups["f_rest"]["half"].shape == (P, 72)
+    want = d["_features_rest"].reshape(P, 72).half()
+    assert np.array_equal(cg.groups["f_rest"]["half"].view(np.uint16), want.numpy().view(np.uint16))
+    path = str(tmp_path / "deg4.npz")
+    save_compressed(path, cg)
+    back = load_compressed(path)
+    assert back.sh_degree == 4 and back.groups["f_rest"]["half"].tobytes() == cg.groups["f_rest"]["half"].tobytes()
+    dec = back.decode()
+    assert dec["_features_rest"].shape == (P, 24, 3) and dec["active_sh_degree"] == 4
+    assert torch.equal(dec["_features_rest"], want.float().reshape(P, 24, 3))
+    for key in ("_features_dc", "_scaling"):
+        assert torch.equal(dec[key], d[key]), key
+    assert torch.equal(dec["_rotation"], compress.canonical_rotation(d["_rotation"]))
