@@ -1,9 +1,12 @@
 """CPU-side checks of the 3D smoothing filter (csrc/filter3d.hip, csrc/filter3d_math.h; filter3d.py): the
 ABI and the refusals of the entry points and of the Python functions -- all before a GPU is asked for --, the header built
 by the host compiler (tests/filter3d_host_check.cpp) against the numpy restatement (tests/filter3d_restate.py), the
-boundary cases of the sampling rule, the closed forms against the definition, and the model's side: checkpoints, PLY
-files, staleness, the refusals of ``render`` and ``compress_model``."""
+boundary cases of the sampling rule, the closed forms against the definition (in float64 on a narrow box, and against the
+definition in 80-digit decimal arithmetic over the range float32 parameters hold), the premises of the planted reduction
+cases of tests/test_gpu_filter3d.py, and the model's side: checkpoints, PLY files, staleness, the refusals of ``render``
+and ``compress_model``."""
 import ctypes as C
+import math
 import os
 import re
 import shutil
@@ -273,6 +276,153 @@ def test_host_build_of_the_application_is_within_one_float32_place(host_check):
     # one float32 place, plus what 64 places of float64 rounding can move a sum of two terms of this size
     assert (np.abs(got["do"].astype(np.float64) - d_o) <= np.spacing(np.abs(d_o).astype(F)) + 1e-14 * np.abs(d_o)).all()
     assert (np.abs(got["ds"].astype(np.float64) - d_s) <= np.spacing(np.abs(d_s).astype(F)) + 1e-14 * cond).all()
+
+
+# ---- the application against the definition itself, at range ----------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def exact():
+    """The rows of ``R.exact_case`` and ``R.apply_exact`` of them, computed once and left unchanged."""
+    s, o, f, _, _ = _apply_case(300, seed=2)
+    s, o, f, g_s, g_o, n_grid = R.exact_case((s, o, f))
+    return types.SimpleNamespace(s=s, o=o, f=f, g_s=g_s, g_o=g_o, n_grid=n_grid, ex=R.apply_exact(s, o, f))
+
+
+def test_the_exact_grid_drops_six_scale_ratio_pairs_and_nothing_else():
+    """``f = float32(e^s0 ratio)``: e^87 = 6.1e37 overflows from ratio 100 on (float32 ends at 3.4e38), e^-87 = 1.6e-38
+    falls below half the smallest denormal (7e-46) from ratio 1e-8 down; e^-87 x 1e-4 = 1.6e-42 is a denormal and stays."""
+    s, o, f, dropped = R.exact_grid()
+    assert dropped == {(-87.0, 1e-12), (-87.0, 1e-8), (87.0, 1e2), (87.0, 1e4), (87.0, 1e8), (87.0, 1e12)}
+    assert len(o) == 1023 == 11 * (99 - 6) and s.dtype == o.dtype == f.dtype == F
+    assert np.isfinite(f).all() and (f > 0).all() and f.min() < 2.0 ** -126 and np.abs(s).max() < 88.4
+    # every (s0, o, ratio) that stays is there once, in the grid's order
+    want = [(s0, o_, F(math.exp(s0) * ratio)) for s0 in R.GRID_S0 for ratio in R.GRID_RATIO if (s0, ratio) not in dropped
+            for o_ in R.GRID_O]
+    assert [(float(a), float(b), c) for a, b, c in zip(s[:, 0], o, f)] == [(float(F(a)), float(F(b)), c) for a, b, c in want]
+    assert same_bits(s[:, 1], (s[:, 0].astype(np.float64) + 0.7).astype(F)) and \
+        same_bits(s[:, 2], (s[:, 0].astype(np.float64) - 1.3).astype(F))
+
+
+def test_the_exact_reference_is_the_definition_and_its_derivatives():
+    """``apply_exact`` against itself: its activations are the definition's, and its three derivative factors are central
+    differences of its own ``s'`` and ``o'`` in ``decimal`` (h = 1e-25 at 80 digits: a truncation error of h^2) -- so a
+    sign or a factor written down wrongly there cannot pass."""
+    import decimal as dec
+    rows = [((-87.0, -86.3, -88.3), -88.0, 1.6e-42), ((0.0, 0.7, -1.3), 1.0, 100.0), ((5.0, 5.7, 3.7), 88.0, 1.5e-6),
+            ((-3.0, -2.3, -4.3), -1e-3, 0.05), ((87.0, 87.7, 85.7), 40.0, 6.0e25), ((-20.0, -19.3, -21.3), 17.0, 2.0e3)]
+    s = np.array([r[0] for r in rows], dtype=F)
+    o, f = np.array([r[1] for r in rows], dtype=F), np.array([r[2] for r in rows], dtype=F)
+    ex = R.apply_exact(s, o, f)
+
+    def value(sd, od, f2):
+        af, p, c, omx = R._filtered(dec, sd, od, f2)
+        return [y.ln() / 2 for y in af], (p * c / omx).ln()
+
+    with dec.localcontext() as ctx:
+        ctx.prec = R.EXACT_DIGITS
+        h = dec.Decimal("1e-25")
+        for i in range(len(rows)):
+            sd, od, f2 = [dec.Decimal(float(v)) for v in s[i]], dec.Decimal(float(o[i])), dec.Decimal(float(f[i])) ** 2
+            so, oo = value(sd, od, f2)
+            assert [float(v) for v in so] == list(ex.s[i]) and float(oo) == ex.o[i]
+            assert np.allclose(np.exp(ex.s[i]), np.sqrt(np.exp(2.0 * s[i].astype(np.float64)) + float(f[i]) ** 2), rtol=1e-13)
+            d_o = (value(sd, od + h, f2)[1] - value(sd, od - h, f2)[1]) / (2 * h)
+            assert abs(float(d_o) / ex.do_do[i] - 1.0) < 1e-15, (i, "do'/do")
+            for j in range(3):
+                up, down = list(sd), list(sd)
+                up[j], down[j] = sd[j] + h, sd[j] - h
+                (su, ou), (sl, ol) = value(up, od, f2), value(down, od, f2)
+                assert abs(float((su[j] - sl[j]) / (2 * h)) / ex.ds_ds[i, j] - 1.0) < 1e-15, (i, j, "ds'/ds")
+                assert abs(float((ou - ol) / (2 * h)) / ex.do_ds[i, j] - 1.0) < 1e-15, (i, j, "do'/ds")
+    assert (ex.do_ds > 0).all() and (ex.ds_ds > 0).all() and (ex.do_do > 0).all()
+
+
+def test_closed_forms_against_the_exact_definition_at_range(exact):
+    """``R.apply_torch`` / ``R.apply_bwd`` (float64, the header's algebra written a second time) against ``apply_exact``
+    over |s| <= 87, |o| <= 88 and f from 1e-12 to 1e12 times the scale: every branch of ``o'`` and of the backward.
+    Measured: the float64 closed form is within 1.4e-13 relative of the exact ``o'`` and 1.6e-15 of ``s'`` on the grid
+    (8.4e-15 with the random rows, where ``s'`` passes near 0); rounded once it is the exact value's float32 in every row
+    (0 places), and the backward stays inside the 1e-14 allowance (0.00 spacings over it)."""
+    assert exact.n_grid == 1023 and len(exact.o) == 1023 + 300 + 3
+    se, oe = R.apply(exact.s, exact.o, exact.f)
+    d_s, d_o, cond = R.apply_bwd(exact.s, exact.o, exact.f, exact.g_s, exact.g_o)
+    s64, o64 = (t.numpy() for t in R.apply_torch(*(torch.from_numpy(a.astype(np.float64)) for a in (exact.s, exact.o, exact.f))))
+    moved = exact.f != 0
+    rel_s = np.max(np.abs(s64[moved] / exact.ex.s[moved] - 1.0))
+    rel_o = np.max(np.abs(o64[moved] / exact.ex.o[moved] - 1.0))
+    print(f"[filter3d exact] float64 closed form: s' within {rel_s:.1e} relative, o' within {rel_o:.1e}")
+    assert rel_s < 1e-14 and rel_o < 1e-12
+    R.assert_exact_bars(se, oe, d_s, d_o, exact, "float64 closed form")
+    assert np.allclose(cond, R.exact_bwd(exact.ex, exact.g_s, exact.g_o)[2], rtol=1e-12, atol=0)
+
+
+def test_host_build_of_the_application_against_the_exact_definition(host_check, exact):
+    """csrc/filter3d_math.h itself, built by the host compiler, on the same rows against ``apply_exact``.  Measured: forward
+    0 places in every branch; backward at most 0.50 of a spacing (the one rounding to float32)."""
+    rows = np.concatenate([exact.s, exact.o[:, None], exact.f[:, None], exact.g_s, exact.g_o[:, None]], axis=1)
+    _, got = host_check(np.zeros((len(rows), 3), dtype=F), [], rows=rows)
+    R.assert_exact_bars(got["s"], got["o"], got["ds"], got["do"], exact, "host build")
+
+
+# ---- the global reduction: the premise of every planted case (tests/test_gpu_filter3d.py runs them) -----------------------------
+def test_planted_cases_reach_the_reduce_lanes_waves_and_trips_they_claim():
+    """csrc/filter3d.hip: ``filter3d_sample_kernel`` writes the pair of rows 64 k .. 64 k + 63 to slot k;
+    ``filter3d_reduce_kernel`` is one workgroup of F3D_REDUCE_BLOCK lanes whose lane t folds pairs t, t + block, ...
+    (trip = pair / block), whose waves of 64 fold their lanes, and whose lane 0 folds waves 1 .. block / 64 - 1 in.  Read
+    from the source, so that a change of the block size cannot hollow the cases out unnoticed."""
+    with open(os.path.join(ROOT, "mvs_gaussian_splatting_amd", "csrc", "filter3d.hip")) as f:
+        src = f.read()
+    block = int(re.search(r"constexpr int F3D_REDUCE_BLOCK = (\d+);", src).group(1))
+    assert int(re.search(r"constexpr int F3D_BLOCK = (\d+);", src).group(1)) % R.WAVE == 0, "a wave's first row: 64 k"
+    assert "k += F3D_REDUCE_BLOCK" in src and "for (int w = 1; w < F3D_REDUCE_BLOCK / WAVE; ++w)" in src
+    assert "dim3(1), dim3(F3D_REDUCE_BLOCK)" in src
+    reach = {k: (k % block, k % block // R.WAVE, k // block) for k in R.PLANT_PAIRS}             # lane, wave, trip
+    assert reach == {0: (0, 0, 0), 15: (15, 0, 0), 16: (16, 0, 0), 63: (63, 0, 0), 64: (64, 1, 0), 1023: (1023, 15, 0),
+                     1024: (0, 0, 1), 1087: (63, 0, 1), 2047: (1023, 15, 1), 2048: (0, 0, 2)}
+    assert R.PLANT_SIZES == (4097, 65536, 65537, 131073)
+    last = {P: R.plant_pairs(P)[-1] for P in R.PLANT_SIZES}
+    assert last == {4097: 64, 65536: 1023, 65537: 1024, 131073: 2048}
+    # 4097: reduce wave 1 holds data; 65536: every lane one pair, one trip; 65537: lane 0 alone a second; 131073: a third
+    assert {P: (last[P] % block // R.WAVE, last[P] // block + 1, P - R.WAVE * last[P]) for P in R.PLANT_SIZES} == \
+        {4097: (1, 1, 1), 65536: (15, 1, 64), 65537: (0, 2, 1), 131073: (0, 3, 1)}
+    assert [len(R.plant_pairs(P)) for P in R.PLANT_SIZES] == [5, 6, 7, 10]
+    for P in R.PLANT_SIZES:
+        rows = [R.plant_row(P, k) for k in R.plant_pairs(P)]
+        assert all(0 <= i < P and i // R.WAVE == k for i, k in zip(rows, R.plant_pairs(P)))
+        assert {i % R.WAVE for i in rows} == {0, 15, 16, 63}, "k % 64: a lane that differs between neighbours in the list"
+        for name, d, r, hit in R.planted_cases(P):
+            m = re.fullmatch(r"D in pair (\d+), R in pair (\d+)", name)
+            if m:
+                kd, kr = int(m.group(1)), int(m.group(2))
+                assert kd != kr and d[R.plant_row(P, kd)] == 9.0 and r[R.plant_row(P, kr)] == 0.5
+                seen = hit.astype(bool)
+                assert d[seen].max() == 9.0 and r[seen].min() == 0.5 and (d[seen] == 9.0).sum() == (r[seen] == 0.5).sum() == 1
+                assert 0.1 < 1.0 - seen.mean() < 0.2
+    pairs = {(kd // block, kr // block) for P in R.PLANT_SIZES for kd, kr in
+             (map(int, re.findall(r"\d+", n)) for n, *_ in R.planted_cases(P) if n.startswith("D in"))}
+    assert {(0, 1), (1, 0), (1, 2), (2, 1)} <= pairs, "D in one trip while R sits in another"
+
+
+def test_a_model_of_the_reduction_tells_the_planted_cases_from_a_broken_combine_or_stride():
+    """The planted cases through a host model of the reduce kernel's data flow: the kernel's own parameters give D, R and
+    the flag of the definition in every case; a serial combine that starts at wave 2, or a strided loop that steps by
+    2048, is told apart by at least one case (the broken kernels themselves are never run)."""
+    broken = {"combine from w = 2": dict(first_wave=2), "stride 2048": dict(step=2048)}
+    caught = {name: [] for name in broken}
+    for P in R.PLANT_SIZES:
+        for name, d, r, hit in R.planted_cases(P):
+            seen = hit.astype(bool)
+            pairs = R.wave_pairs(d, r, hit)
+            want = (d[seen].max(), r[seen].min(), 0)
+            assert R.reduce_model(pairs) == want, (P, name)
+            for what, kw in broken.items():
+                if R.reduce_model(pairs, **kw) != want:
+                    caught[what].append((P, name))
+    print({k: len(v) for k, v in caught.items()})
+    assert (4097, "one seen row, pair 64") in caught["combine from w = 2"]
+    assert (65537, "one seen row, pair 1024") in caught["stride 2048"]
+    assert all(len(v) >= 4 for v in caught.values())
+    d, r, hit = R._unseen(65537)
+    assert R.reduce_model(R.wave_pairs(d, r, hit)) == (F(-np.inf), F(np.inf), 1)
 
 
 # ---- the model: checkpoints, PLY files, staleness --------------------------------------------------------------------------------

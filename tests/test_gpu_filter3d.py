@@ -1,7 +1,8 @@
 """The 3D smoothing filter on the device (csrc/filter3d.hip; filter3d.py): the sampling pass and the width
 against the float32 restatement (tests/filter3d_restate.py) bit for bit, the fused application and its gradient against
-the float64 restatement rounded once, ``render`` with a filter on both paths, and three training iterations across a
-densification."""
+the float64 restatement rounded once and against the exact definition at range, planted per-row states through the global
+reduction past one wave and one trip, ``accumulate`` and V = 0 at the entry points, ``render`` with a filter on both
+paths, three training iterations across a densification, and the trainer's periodic and MCMC recomputes."""
 import numpy as np
 import pytest
 import torch
@@ -77,6 +78,175 @@ def test_sampling_arrays_boundaries_and_the_unseen(gpu_device):
     assert tuple(got.shape) == (0,) and int(flag) == 1
 
 
+# ---- the entry points themselves: planted per-row states, accumulate, V = 0 ---------------------------------------------------------
+class _Pass:
+    """The two calls of a sampling pass through the C ABI, over arrays the test owns: ``P`` rows, the workspace filled with
+    0xAB bytes, ``min_depth`` / ``max_rate`` / ``seen`` set by ``plant``."""
+
+    def __init__(self, dev, P, xyz=None):
+        from mvs_gaussian_splatting_amd import _lib
+        self._lib, self.lib, self.dev, self.P = _lib, _lib.load(), dev, P
+        self.xyz = torch.zeros(P, 3, device=dev) if xyz is None else torch.from_numpy(np.ascontiguousarray(xyz, dtype=F)).to(dev)
+        self.min_depth, self.max_rate = torch.empty(P, device=dev), torch.empty(P, device=dev)
+        self.seen = torch.empty(P, dtype=torch.uint8, device=dev)
+        self.ws_bytes = int(self.lib.gsr_filter3d_workspace_bytes(P))
+        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
+        self.filter, self.flag = torch.empty(P, device=dev), torch.empty(1, dtype=torch.int32, device=dev)
+        self.stream = torch.cuda.current_stream(dev).cuda_stream
+
+    def plant(self, min_depth, max_rate, seen):
+        for dst, src in ((self.min_depth, min_depth), (self.max_rate, max_rate), (self.seen, seen)):
+            dst.copy_(torch.from_numpy(np.ascontiguousarray(src)) if isinstance(src, np.ndarray) else torch.full_like(dst, src))
+        self.ws.fill_(0xAB)
+
+    def sample(self, cams, accumulate, near=0.2, margin=0.15):
+        from mvs_gaussian_splatting_amd import filter3d
+        table = None
+        if cams:
+            table = torch.frombuffer(bytearray(bytes(filter3d.view_table(cams)[0])), dtype=torch.uint8).to(self.dev)
+        self._lib.check(self.lib.gsr_filter3d_sample(self.xyz.data_ptr(), self.P, table.data_ptr() if cams else None, len(cams),
+                                                     near, margin, accumulate, self.min_depth.data_ptr(),
+                                                     self.max_rate.data_ptr(), self.seen.data_ptr(), self.ws.data_ptr(),
+                                                     self.ws_bytes, self.stream), "gsr_filter3d_sample")
+        torch.cuda.synchronize(self.dev)                             # the table lives until the launch has read it
+
+    def finish(self, rule, focal_max, variance=0.2):
+        self.filter.fill_(float("nan"))
+        self.flag.fill_(-1)
+        self._lib.check(self.lib.gsr_filter3d_finish(self.P, self.min_depth.data_ptr(), self.max_rate.data_ptr(),
+                                                     self.seen.data_ptr(), R.RULES[rule], focal_max, variance,
+                                                     self.ws.data_ptr(), self.ws_bytes, self.filter.data_ptr(),
+                                                     self.flag.data_ptr(), self.stream), "gsr_filter3d_finish")
+        return bits(self.filter), int(self.flag)
+
+    def arrays(self):
+        return bits(self.min_depth), bits(self.max_rate), self.seen.cpu().numpy()
+
+    def pairs(self):
+        """The per-64-row (max, min) pairs the sampling call left at the head of the workspace."""
+        n = (self.P + R.WAVE - 1) // R.WAVE
+        return self.ws[:8 * n].cpu().numpy().view(F).reshape(n, 2)
+
+
+@pytest.mark.parametrize("P", R.PLANT_SIZES)
+def test_planted_states_through_the_reduction_past_one_wave_and_one_trip(gpu_device, P):
+    """``gsr_filter3d_sample(V = 0, views = NULL, accumulate = 1)`` loads the caller's per-row state, runs an empty view
+    loop, writes the state back unchanged and the per-wave pairs from it; ``gsr_filter3d_finish`` follows.  So D, R and
+    the none-seen flag come from rows the test chose: a single seen row in each of the pairs ``R.plant_pairs(P)``; D and R
+    planted in different pairs, reduce waves and trips of the strided loop, every 7th row unseen; pairs 1 to 62 and the
+    partial last wave wholly unseen.  (tests/test_filter3d_host.py pins the reduce lane, wave and trip each pair reaches:
+    4097 rows put data in reduce wave 1, 65536 give every lane one pair, 65537 give lane 0 a second trip, 131073 a third.)
+    A maximum and a minimum do not depend on the order: the filter is ``R.width`` of the planted arrays bit for bit under
+    both rules, the flag exactly, the pairs exactly, and a second run gives the same bits.
+    Measured on an MI355X: 16, 19, 22 and 31 planted states at the four sizes, each under both rules, all bit-equal to the
+    restatement, and the second run equal to the first in every bit."""
+    run = _Pass(gpu_device, P)
+    cam = R.camera(64, 48, 64.0, 64.0)                              # read for its focal length alone
+    focal_max = float(R.focal(cam)[2])
+    cases = R.planted_cases(P)
+    for name, d, r, hit in cases:
+        seen = hit.astype(bool)
+        run.plant(d, r, hit)
+        run.sample([], 1)
+        got_d, got_r, got_hit = run.arrays()
+        assert np.array_equal(got_d, d.view(np.uint32)) and np.array_equal(got_r, r.view(np.uint32)) and \
+            np.array_equal(got_hit, hit), (name, "V = 0 with accumulate = 1 writes the arrays back unchanged")
+        assert np.array_equal(run.pairs().view(np.uint32), R.wave_pairs(d, r, hit).view(np.uint32)), (name, "per-wave pairs")
+        for rule in ("mip_splatting", "paper"):
+            want, want_flag = R.width(d, r, seen, [cam], rule=rule)
+            got, flag = run.finish(rule, focal_max)
+            assert flag == want_flag == 0, (name, rule, "none_seen")
+            assert np.array_equal(got, want.view(np.uint32)), (name, rule, int((got != want.view(np.uint32)).sum()))
+            again, flag2 = run.finish(rule, focal_max)
+            assert flag2 == 0 and np.array_equal(again, got), (name, rule, "the same bits from run to run")
+            if name.startswith("D in"):                              # the unseen take exactly the planted value's width
+                own = R.width(np.array([9.0], dtype=F), np.array([0.5], dtype=F), np.array([True]), [cam], rule=rule)[0][0]
+                assert (want[~seen] == own).all() and (~seen).sum() > P // 8
+            elif name.startswith("one seen"):
+                assert (want == want[seen][0]).all() and want[0] > 0
+    neutral = run.pairs()                                            # of the last case: the wholly unseen waves
+    assert cases[-1][0].startswith("pairs 1 to 62") and np.isneginf(neutral[1:63, 0]).all() and np.isposinf(neutral[1:63, 1]).all()
+    assert np.isneginf(neutral[-1, 0]) and np.isposinf(neutral[-1, 1]) and np.isfinite(neutral[[0, 63]]).all()
+    print(f"[filter3d] P={P}: {len(cases)} planted states x 2 rules bit-equal to the restatement, twice")
+    if P == 65537:
+        d, r, hit = R._unseen(P)
+        run.plant(d, r, hit)
+        run.sample([], 1)
+        for rule in ("mip_splatting", "paper"):
+            got, flag = run.finish(rule, focal_max)
+            assert flag == 1 and not got.any(), "nothing seen: the flag, and a filter whose bits are all zero"
+
+
+@pytest.mark.parametrize("P,late", [(4097, 64), (65537, 1024)])
+def test_the_public_pass_takes_its_maximum_from_a_late_pair(gpu_device, P, late):
+    """``compute_3d_filter`` on a constructed scene: the identity camera, points on the optical axis at distinct dyadic
+    depths 1 + i 2^-17 (every float32 operation exact), rows from 64 on behind the camera except one row of pair ``late``
+    at depth 4, the farthest seen.  D and R come from that pair alone -- reduce wave 1 at 4097 rows, lane 0's second trip
+    at 65537 --, and about every row past 63 is unseen and takes them.  Bit for bit ``R.compute``, both rules."""
+    from mvs_gaussian_splatting_amd import compute_3d_filter
+    cam = R.camera(64, 32, 32.0, 32.0)
+    xyz = np.zeros((P, 3), dtype=F)
+    xyz[:, 2] = 1.0 + np.arange(P) * 2.0 ** -17
+    xyz[64:, 2] *= -1.0
+    far = R.plant_row(P, late)
+    xyz[far, 2] = 4.0
+    min_depth, max_rate, seen = R.sample(xyz, [cam])
+    assert seen.sum() == 65 and seen[far] and far // 64 == late and len(np.unique(min_depth[seen])) == 65
+    assert min_depth[seen].max() == min_depth[far] == 4.0 and max_rate[seen].min() == max_rate[far] == 8.0
+    dev_xyz = torch.from_numpy(xyz).to(gpu_device)
+    for rule in ("mip_splatting", "paper"):
+        want, _ = R.width(min_depth, max_rate, seen, [cam], rule=rule)
+        got, flag = compute_3d_filter(dev_xyz, [cam], rule=rule)
+        assert int(flag) == 0 and np.array_equal(bits(got), want.view(np.uint32)), rule
+        assert (want[~seen] == want[far]).all() and want[far] > want[:64].max()
+
+
+def test_accumulate_and_an_empty_table_at_the_entry_points(gpu_device):
+    """The promises of include/gsr.h, on 130 rows (two full waves and two rows) into arrays full of garbage:
+    ``accumulate = 0`` ignores what the arrays hold, also with V = 0 (the start values); ``accumulate = 1`` carries all
+    three arrays forward, across a launch that sees nothing and across V = 0 with a NULL table; two chunks give the bits of
+    one table."""
+    P = 130
+    xyz, (cam_a, cam_b) = R.gate_scene(P, 2)
+    behind = np.eye(4, dtype=F)
+    behind[3, 2] = -100.0
+    blind = R.camera(64, 48, 60.0, 66.0, behind)
+    w_a, w_ab = R.sample(xyz, [cam_a]), R.sample(xyz, [cam_a, cam_b])
+    only_a = w_a[2] & ~R.sample(xyz, [cam_b])[2]
+    assert only_a.any() and (w_ab[2] & ~w_a[2]).any() and not w_ab[2].all() and not R.sample(xyz, [blind])[2].any()
+    run = _Pass(gpu_device, P, xyz)
+
+    def same(want):
+        d, r, hit = run.arrays()
+        pairs = R.wave_pairs(want[0], want[1], want[2])
+        return np.array_equal(d, want[0].view(np.uint32)) and np.array_equal(r, want[1].view(np.uint32)) and \
+            np.array_equal(hit, want[2].astype(np.uint8)) and np.array_equal(run.pairs().view(np.uint32), pairs.view(np.uint32))
+
+    run.plant(-7.0, 1e9, 9)
+    run.sample([], 0)
+    assert same((np.full(P, np.inf, dtype=F), np.zeros(P, dtype=F), np.zeros(P, dtype=bool))), "V = 0: the start values"
+    run.plant(-7.0, 1e9, 9)
+    run.sample([cam_a], 0)
+    assert same(w_a), "accumulate = 0 ignores the garbage"
+    run.sample([cam_b], 1)
+    assert same(w_ab), "two chunks are one table"
+    run.plant(-7.0, 1e9, 9)
+    run.sample([cam_a], 0)
+    run.sample([blind], 1)
+    assert same(w_a), "a launch that sees nothing changes nothing"
+    run.sample([cam_b], 1)
+    assert same(w_ab), "a row seen only by the first chunk stays seen, with its values"
+    d, r, hit = run.arrays()
+    assert hit[only_a].all() and np.array_equal(d[only_a], w_a[0][only_a].view(np.uint32))
+    run.ws.fill_(0xAB)
+    run.sample([], 1)
+    assert same(w_ab), "accumulate = 1 with V = 0 and a NULL table changes nothing (and writes the pairs again)"
+    for rule in ("mip_splatting", "paper"):
+        want, want_flag = R.width(*w_ab, [cam_a, cam_b], rule=rule)
+        got, flag = run.finish(rule, focal_max=float(max(R.focal(c)[2] for c in (cam_a, cam_b))))
+        assert flag == want_flag == 0 and np.array_equal(got, want.view(np.uint32)), rule
+
+
 # ---- application ----------------------------------------------------------------------------------------------------------------
 def _apply_case(n, seed=0):
     """Raw scales in [-12, 4], raw opacities in [-12, 12], filters from 0 to 10 times the scale, and rows with f = 0."""
@@ -130,6 +300,31 @@ def test_application_and_its_gradient_against_float64(gpu_device, n):
     d_scale, d_opacity = R.apply_direct(s, o, f)
     assert np.allclose(scale.cpu().numpy(), d_scale, rtol=2e-6, atol=0)
     assert np.allclose(opacity.cpu().numpy().reshape(-1), d_opacity, rtol=2e-5, atol=1e-30)
+
+
+def test_application_and_its_gradient_against_the_exact_definition_at_range(gpu_device):
+    """``apply_3d_filter`` forward and backward against ``R.apply_exact`` -- the definition in 80-digit decimal arithmetic,
+    none of the kernel's algebra -- on the 1023-row grid |s| <= 87, |o| <= 88, f from 1e-12 to 1e12 times the scale
+    (tests/test_filter3d_host.py asserts the grid row for row), 300 rows of the narrow box and f = 0 at o in {-88, -0.0,
+    88}.  The bars of the test above, now against the definition: forward at most one float32 place; backward one float32
+    spacing plus 1e-14 x the magnitudes of the terms; f = 0 rows bit copies in both directions.
+    Measured on an MI355X, worst per branch: o <= 0 (678 rows) forward 0 places (s') / 0 (o'), backward 0.50 of a spacing
+    (dL/ds, row 617) / 0.50 (dL/do, row 1035); o > 0 (602 rows) forward 0 / 0, backward 0.50 (row 611) / 0.50 (row 922);
+    f = 0 (46 rows) 0 / 0 and 0.00 / 0.00.  Every forward value is the exact value's float32; the half spacing of the
+    backward is the one rounding to float32.  The host build of the header gives the same figures at the same rows."""
+    from mvs_gaussian_splatting_amd import apply_3d_filter
+    import types
+    s, o, f, _, _ = _apply_case(300, seed=2)
+    s, o, f, g_s, g_o, n_grid = R.exact_case((s, o, f))
+    assert n_grid == 1023 and len(o) == 1326
+    case = types.SimpleNamespace(s=s, o=o, f=f, g_s=g_s, g_o=g_o, ex=R.apply_exact(s, o, f))
+    ds, do, df = (torch.from_numpy(a).to(gpu_device) for a in (s, o, f))
+    ds.requires_grad_(True)
+    do.requires_grad_(True)
+    se, oe = apply_3d_filter(ds, do, df)
+    torch.autograd.backward([se, oe], [torch.from_numpy(g_s).to(gpu_device), torch.from_numpy(g_o).to(gpu_device)])
+    R.assert_exact_bars(se.detach().cpu().numpy(), oe.detach().cpu().numpy(), ds.grad.cpu().numpy(), do.grad.cpu().numpy(),
+                        case, "device")
 
 
 # ---- render ---------------------------------------------------------------------------------------------------------------------
@@ -293,3 +488,95 @@ def test_training_iterations_across_a_densification(gpu_device):
         parent, _ = rasterize_gaussians_fused(a._xyz, _zero_leaf(a._xyz), a._features_dc, a._features_rest, a._opacity,
                                               a._scaling, a._rotation, _settings(cam, a, pipe, bg, 1.0), visible=visible)
     assert torch.equal(frame, parent)
+
+
+def _recorded(m, monkeypatch, now):
+    """Wraps ``m.compute_3D_filter``: every call appends (the iteration in ``now[0]``, a clone of ``_xyz``, the filter it
+    made) to the returned list."""
+    calls, real = [], m.compute_3D_filter
+
+    def compute(cameras, **kw):
+        xyz = m._xyz.detach().clone()
+        out = real(cameras, **kw)
+        calls.append((now[0], xyz, m.filter_3D))
+        return out
+
+    monkeypatch.setattr(m, "compute_3D_filter", compute)
+    return calls
+
+
+def _assert_recorded_filters(calls, cams, rule="mip_splatting"):
+    for it, xyz, filt in calls:
+        want, flag = R.compute(xyz.cpu().numpy(), cams, rule=rule)
+        assert flag == 0 and tuple(filt.shape) == (len(xyz),) and np.array_equal(bits(filt), want.view(np.uint32)), it
+
+
+def test_trainer_recomputes_every_interval_once_densification_has_ended(gpu_device, monkeypatch):
+    """``densify_until_iter = 2, filter_3d_interval = 2, iterations = 10``: the filter is computed at iteration 1 before
+    the frame and again after that iteration's densification, then exactly at iterations 4 and 6 -- not at 2 (not yet past
+    ``densify_until_iter``), not at 8 (``iteration < iterations - interval`` fails) or later.  ``filter_3D`` is a new tensor
+    at exactly those iterations and the same object in between, and every computed filter is ``R.compute`` of the ``_xyz``
+    of that moment, bit for bit."""
+    from mvs_gaussian_splatting_amd.synthetic import PipelineParams, orbit_camera
+    from mvs_gaussian_splatting_amd.trainer import OptimizationParams, training_iteration
+    _, cam, bg, target = _scene(gpu_device)
+    cams = [cam, orbit_camera(1, 8, 64, 48, 60.0, 60.0)]
+    opt = OptimizationParams(filter_3d=True, filter_3d_interval=2, iterations=10, position_lr_max_steps=10,
+                             densify_from_iter=0, densification_interval=1, densify_until_iter=2, densify_grad_threshold=1e-9)
+    m = _trainable(gpu_device, opt)
+    now = [0]
+    calls = _recorded(m, monkeypatch, now)
+    held, sizes = [], []
+    for it in range(1, 11):
+        now[0] = it
+        torch.manual_seed(it)
+        loss = training_iteration(m, cam, opt, PipelineParams(), bg, it, cameras_extent=1.0, gt_image=target,
+                                  filter_cameras=cams)
+        assert bool(torch.isfinite(loss)) and not m._filter_3D_stale
+        held.append(m.filter_3D)
+        sizes.append(int(m._xyz.shape[0]))
+    assert [c[0] for c in calls] == [1, 1, 4, 6], [c[0] for c in calls]
+    assert sizes[0] > 300 and len(set(sizes)) == 1, "iteration 1 densifies, nothing does after it"
+    assert calls[0][1].shape[0] == 300 and calls[1][1].shape[0] == sizes[0] and held[0] is calls[1][2]
+    changed = [it for it in range(2, 11) if held[it - 1] is not held[it - 2]]
+    assert changed == [4, 6] and held[3] is calls[2][2] and held[5] is calls[3][2] and held[9] is calls[3][2]
+    assert not torch.equal(calls[2][1], calls[1][1]) and not torch.equal(calls[3][1], calls[2][1]), "the points had moved"
+    _assert_recorded_filters(calls, cams)
+
+
+def test_trainer_recomputes_after_an_mcmc_relocation_and_growth(gpu_device, monkeypatch):
+    """``strategy = "mcmc"`` with a cap of 310 on 300 rows, densifying at iterations 2 and 4.  Iteration 2 relocates 7 dead
+    rows in place and appends 10: the trainer recomputes the filter right after the two steps, so it has 310 rows, is not
+    stale, and iteration 3 -- whose ``render`` would refuse a stale or short filter -- draws with that very tensor.
+    Iteration 4 is at the cap: relocation alone, P stays, the filter is recomputed all the same.  Every computed filter is
+    ``R.compute`` of the ``_xyz`` of that moment, bit for bit."""
+    from mvs_gaussian_splatting_amd.synthetic import PipelineParams, orbit_camera
+    from mvs_gaussian_splatting_amd.trainer import OptimizationParams, training_iteration
+    _, cam, bg, target = _scene(gpu_device)
+    cams = [cam, orbit_camera(1, 8, 64, 48, 60.0, 60.0)]
+    opt = OptimizationParams(filter_3d=True, filter_3d_rule="paper", strategy="mcmc", cap_max=310, iterations=30,
+                             position_lr_max_steps=30, densify_from_iter=1, densification_interval=2, densify_until_iter=10)
+    m = _trainable(gpu_device, opt)
+    now = [0]
+    calls = _recorded(m, monkeypatch, now)
+    draws = torch.from_numpy(np.random.default_rng(5).integers(0, 2 ** 63, size=64, dtype=np.int64))
+    held, sizes = [], []
+    for it in range(1, 6):
+        now[0] = it
+        if it in (2, 4):
+            with torch.no_grad():
+                m._opacity[5:40:5] = -7.0                              # seven dead rows: something to relocate
+        torch.manual_seed(it)
+        loss = training_iteration(m, cam, opt, PipelineParams(), bg, it, cameras_extent=1.0, gt_image=target,
+                                  filter_cameras=cams, mcmc_kwargs={"draws": draws})
+        assert bool(torch.isfinite(loss)) and not m._filter_3D_stale
+        held.append(m.filter_3D)
+        sizes.append(int(m._xyz.shape[0]))
+        assert tuple(m.filter_3D.shape) == (sizes[-1],)
+    assert sizes == [300, 310, 310, 310, 310] and [c[0] for c in calls] == [1, 2, 4], [c[0] for c in calls]
+    assert [int(c[1].shape[0]) for c in calls] == [300, 310, 310]
+    assert held[1] is calls[1][2] and held[2] is held[1] and held[3] is calls[2][2] and held[3] is not held[2] and held[4] is held[3]
+    for xyz, rows in ((calls[1][1], list(range(5, 40, 5)) + list(range(300, 310))), (calls[2][1], range(5, 40, 5))):
+        twins = [int((xyz == xyz[i]).all(dim=1).sum()) for i in rows]
+        assert min(twins) >= 2, "the filter was computed with the relocated and the new rows on their sources' positions"
+    _assert_recorded_filters(calls, cams, rule="paper")
